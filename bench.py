@@ -147,6 +147,28 @@ def make_step(scene, parallel, S_total, rank, world, phase=None, sync=None):
     return step
 
 
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """Writes what the timed path returned in its last step as `path/<name>.npy` (float32 / float64 as computed).  Arrays are in
+    the reference's axis order [nVZA, nStokes, nSpec]; if they hold more than 64 MB together, the same fixed, seeded sample of
+    spectral points (last axis, ascending) is written for every array."""
+    arrays = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
+    for k, v in arrays.items():
+        if v.dtype not in (np.float32, np.float64):
+            raise TypeError("dump_outputs: %s is %s, not float32 / float64" % (k, v.dtype))
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_BYTES_MAX:
+        S = next(iter(arrays.values())).shape[-1]
+        keep = max(1, int(S * DUMP_BYTES_MAX // total))
+        idx = np.sort(np.random.default_rng(0).choice(S, size=keep, replace=False))
+        arrays = {k: np.ascontiguousarray(v[..., idx]) for k, v in arrays.items()}
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -164,7 +186,12 @@ def main():
     ap.add_argument("--no-secondary", action="store_true",
                     help="skip config.secondary (one timed step each of C4, the linearized C2 shape, the linearized C3 scene, C5 at 4000 points)")
     ap.add_argument("--cpu-sample", type=int, default=96, help="upper bound of spectral points PER HOST CORE of the CPU-baseline sample (sized for ~15 s)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the R / T (C5: also ieR / ieT) of the last timed step as DIR/<name>.npy "
+                         "(rank 0; a fixed sample of spectral points beyond 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
 
     import torch
     # --gpus N without a launcher: start the N ranks ourselves (one process per GPU over RCCL), or fail loudly
@@ -172,9 +199,11 @@ def main():
         have = torch.cuda.device_count()
         if have < args.gpus:
             sys.exit("bench.py: --gpus %d requested but only %d GPU(s) are visible -- refusing to report a smaller run" % (args.gpus, have))
-        os.execvp(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
-                                   "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.abspath(__file__)]
-                  + sys.argv[1:])
+        import subprocess
+        rc = subprocess.call([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
+                              "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.abspath(__file__)]
+                             + sys.argv[1:])
+        sys.exit(rc)
     if int(os.environ.get("WORLD_SIZE", "1")) != args.gpus:
         sys.exit("bench.py: --gpus %d does not match the launcher's WORLD_SIZE=%s" % (args.gpus, os.environ.get("WORLD_SIZE")))
 
@@ -240,6 +269,9 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     timed_region_s = dt
+    if args.dump_outputs and rank == 0:
+        R_out, T_out = parallel.unpack_RT(out, model.polarization_type.n, len(model.vza))
+        dump_outputs(args.dump_outputs, {"R": R_out, "T": T_out})
     mg = {"rccl_ranks": 1, "per_rank_step_ms": [1e3 * dt / args.steps], "per_rank_device": [torch.cuda.get_device_name(local)]}
     if world > 1:
         dist = torch.distributed
@@ -437,6 +469,8 @@ def bench_c5(args, vsm, parallel, torch, rank, world, local):
         out = step()
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(zip(("R", "T", "ieR", "ieT"), out)))
     mg = {"rccl_ranks": 1, "per_rank_step_ms": [1e3 * dt / args.steps], "per_rank_device": [torch.cuda.get_device_name(local)]}
     if world > 1:
         dist = torch.distributed
