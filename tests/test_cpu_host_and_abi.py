@@ -51,6 +51,17 @@ def test_no_cpu_fallback(vsm):
     assert "oracle" not in " ".join(sys.modules[k].__name__ for k in list(sys.modules) if k.startswith("vsmartmom_jl_amd"))
 
 
+def test_host_moment_limits_equal_the_library_limit(vsm):
+    """The host layer's moments-per-launch limits are copies of VSM_MM_MAX (csrc/vsm_internal.h): Scene.run's groups of a small
+    batch (vsm_layer_forward_multi, vsm_run_*) and SceneLin's chunks of vsm_mix_Z_moments must not outgrow what the library takes."""
+    src = open(os.path.join(ROOT, "vsmartmom.jl_amd", "csrc", "vsm_internal.h")).read()
+    found = re.findall(r"constexpr\s+int\s+VSM_MM_MAX\s*=\s*(\d+)\s*;", src)
+    assert len(found) == 1, found
+    mm_max = int(found[0])
+    assert vsm.CoreRT.MOMENT_BATCH_MAX == mm_max
+    assert vsm.CoreRTLin.MIX_Z_MOMENTS_MAX == mm_max
+
+
 def test_architectures_surface(vsm):
     A = vsm.Architectures
     assert repr(A.CPU()) == "Architectures.CPU()" and isinstance(A.default_architecture(), (A.CPU, A.GPU))

@@ -170,6 +170,8 @@ def _pp_args(pol, qp, vza, vaz, m, weight, dtype):
     return row0, w
 
 
+# Fourier moments per vsm_mix_Z_moments call (VSM_MM_MAX of the library: the kernel's argument block holds that many stacks)
+MIX_Z_MOMENTS_MAX = 24
 REDUCE_M0 = True   # A/B switch (module attribute): False = the moment m = 0 with all Stokes components of the model
 
 
@@ -541,10 +543,15 @@ class SceneLin:
             single = 0
             if not mixed:   # (one scatterer: the props hold the one-block views Zc[m][k : k + 1])
                 single = int(fwd.zcomp[iz][1])
-            zp = (C.c_void_p * n)(*[fwd.Zc[mom["m"]][0].data_ptr() for mom in group])
-            zm = (C.c_void_p * n)(*[fwd.Zc[mom["m"]][1].data_ptr() for mom in group])
-            _lib.call("vsm_mix_Z_moments", self.dt, N, S, int(p0.fcomp.shape[1]) if mixed else 0, n, zp, zm, single,
-                      CR._ptr(p0.fcomp) if mixed else None, CR._ptr(Zf[0, iz]), CR._ptr(Zf[1, iz]), CR._stream_ptr())
+            # (at most MIX_Z_MOMENTS_MAX moments per launch: chunk i0 writes the blocks (im S + s) of moments i0 .. i0 + nc - 1)
+            for i0 in range(0, n, MIX_Z_MOMENTS_MAX):
+                chunk = group[i0:i0 + MIX_Z_MOMENTS_MAX]
+                nc = len(chunk)
+                zp = (C.c_void_p * nc)(*[fwd.Zc[mom["m"]][0].data_ptr() for mom in chunk])
+                zm = (C.c_void_p * nc)(*[fwd.Zc[mom["m"]][1].data_ptr() for mom in chunk])
+                _lib.call("vsm_mix_Z_moments", self.dt, N, S, int(p0.fcomp.shape[1]) if mixed else 0, nc, zp, zm, single,
+                          CR._ptr(p0.fcomp) if mixed else None, CR._ptr(Zf[0, iz, i0 * S:]), CR._ptr(Zf[1, iz, i0 * S:]),
+                          CR._stream_ptr())
             props = CR.DeviceLayerOptics(tau_f[iz], varpi_f[iz], Zf[0, iz], Zf[1, iz], p0.max_tau_varpi, p0.tau_h, p0.varpi_h)
             g["layers"].append(dict(props=props, dtau=dtau_f[iz], tau_sum=tsum_f[iz], dtd=dtd_f[iz], vd=vd_f[iz], tsd=tsd_f[iz]))
         if self.PARALLEL_LAYERS and 0 < Sf <= self.PARALLEL_LAYER_POINTS:
@@ -558,7 +565,7 @@ class SceneLin:
         pol, qp, dt, S, N, P, pl = self.pol, self.qp, self.dt, self.S, self.N, self.P, self.pl
         moms = self.fwd.moments
         groups = [[m_ for m_ in moms if m_["m"] == 0], [m_ for m_ in moms if m_["m"] > 0]]
-        if self.MERGE_M0 and groups[0] and groups[1] and len(moms) <= 24:
+        if self.MERGE_M0 and groups[0] and groups[1]:
             # ONE folded batch: the pairs of m = 0 in front (vsm_elemental_lin_fold tells them apart; doubling! and interaction!
             # do not know the moment) -- half the launches of the layer walk, one chain of interactions instead of two
             groups = [[], groups[0] + groups[1]]
