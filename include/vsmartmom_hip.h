@@ -616,8 +616,16 @@ int vsm_mix_Z_moments_f32(int N, int S, int ncomp, int nm, const float* const* Z
  * interaction.jl:207-266 compute in FT): the caller's arrays, the native records and the arithmetic (v_mfma_f32_16x16x4_f32) are
  * single precision, blocks of up to 128 rows (vsm_run_supported_f32; workspace: vsm_run_workspace_bytes_f32 -- half of
  * vsm_run_workspace_bytes, which stays sufficient).  A run is used with the entry points of its own type.
+ * Sources-only runs.  vsm_run_create_ex_* with flags = VSM_RUN_SOURCES_ONLY creates a run for callers that read only R+-, T--,
+ * J0+ and J0- of the composite (rt_run's SFI outputs: R_SFI, T_SFI, hdr and bhr read J0+- after the surface step, whose own
+ * R+-, T--, J0+- depend on the composite's R+-, T--, J0+- alone).  Its layer steps neither read nor write R-+ and T++ (five
+ * products fewer per interaction, half the composite traffic); vsm_run_export writes R-+ and T++ as quiet NaNs -- they are
+ * UNDEFINED, and everything derived from them (the R-+ and T++ of a later interaction) is too.  R+-, T--, J0+- equal those of a
+ * full run up to rounding (the interaction is re-associated around (I - r-+ R+-)^-1).  FP64 runs only: an _f32 run accepts the
+ * flag and keeps the full recurrences.  vsm_run_create_* = vsm_run_create_ex_* with flags = 0 (the full composite).
  * Stream: see Conventions; library scratch (the pre-pass images of the layer). */
 typedef struct vsm_run vsm_run;
+enum { VSM_RUN_SOURCES_ONLY = 1 };
 int vsm_run_supported(int N, int n_stokes, int coupling);
 size_t vsm_run_workspace_bytes(int N, int n_stokes, int S, int nm, const int* coupling_h);
 int vsm_run_supported_f32(int N, int n_stokes, int coupling);
@@ -626,6 +634,10 @@ int vsm_run_create_f64(const vsm_quad_f64* q, int S, int nm, const int* m_h, con
                        size_t workspace_bytes, vsm_run** run);
 int vsm_run_create_f32(const vsm_quad_f32* q, int S, int nm, const int* m_h, const int* coupling_h, void* workspace,
                        size_t workspace_bytes, vsm_run** run);
+int vsm_run_create_ex_f64(const vsm_quad_f64* q, int S, int nm, const int* m_h, const int* coupling_h, void* workspace,
+                          size_t workspace_bytes, unsigned flags, vsm_run** run);
+int vsm_run_create_ex_f32(const vsm_quad_f32* q, int S, int nm, const int* m_h, const int* coupling_h, void* workspace,
+                          size_t workspace_bytes, unsigned flags, vsm_run** run);
 int vsm_run_layer_f64(vsm_run* run, int ndoubl, const double* dtau, const double* varpi, const double* tau_sum,
                       const double* F0, int ncomp, const double* const* Zpp, const double* const* Zmp, long long z_stride,
                       const double* fcomp, int toa, const int* layer_coupling_h, void* stream);

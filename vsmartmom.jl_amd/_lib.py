@@ -145,6 +145,7 @@ _SIGS = {
     "vsm_run_supported_f32": (_I, [_I, _I, _I]),
     "vsm_run_workspace_bytes_f32": (_SZ, [_I, _I, _I, _I, _P]),
     "vsm_run_create_{T}": (_I, [_P, _I, _I, _P, _P, _P, _SZ, _P]),
+    "vsm_run_create_ex_{T}": (_I, [_P, _I, _I, _P, _P, _P, _SZ, C.c_uint, _P]),
     "vsm_run_layer_{T}": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _P, _LL, _P, _I, _P, _P]),
     "vsm_run_export_{T}": (_I, [_P, _P, _P]),
     "vsm_run_import_{T}": (_I, [_P, _P, _P]),

@@ -39,6 +39,8 @@ MOMENT_BATCH_MAX = 24  # ... for small spectral batches: every moment of the run
 MOMENT_BATCHING = True  # False: Scene.run walks the Fourier moments one by one
 THERMAL_FUSION = True   # False: the `:thermal` slot at operator level (tools/thermal_timing.py)
 NATIVE_RUN = True       # False: the layer loop on the reference-layout CompositeLayer (vsm_layer_forward_multi) instead of vsm_run_*
+NATIVE_SOURCES_ONLY = True  # Scene.run without `streams`: the native run keeps only R+-, T-- and J0+- of the composite (vsm_run_create_ex,
+#                         VSM_RUN_SOURCES_ONLY: the SFI outputs read nothing else); its exported R-+ / T++ are NaN.  False: full runs
 NATIVE_DROPIN = True    # rt_kernel_ keeps the CompositeLayer it is handed in the kernels' native layout between its calls (a per-
 #                         composite registry, exported lazily: the path of the reference's own driver order, rt_run.jl:383-453)
 REFERENCE_ORDER = False  # True: Scene.run walks `for m` outside `for iz`, one rt_kernel_ call per (m, iz) on ONE CompositeLayer --
@@ -198,6 +200,7 @@ class CompositeLayer:
         dev, dt = devi(arch), _torch_dtype(FT)
         z = lambda: torch.zeros((nSpec, N, N), dtype=dt, device=dev)
         self._native = None       # NativeSlot while rt_kernel_ keeps this composite in the kernels' strip layout
+        self._sources_only = False  # set by Scene.run for its own walk: the native copy may be a sources-only run (R-+, T++ NaN)
         self._native_ws = None    # its workspace (grow-only, reused from moment to moment)
         # the reference's arrays; read through the properties below, which bring them up to date first
         self._arr = dict(R_mp=z(), R_pm=z(), T_pp=z(), T_mm=z(), J0_p=torch.zeros((nSpec, N), dtype=dt, device=dev),
@@ -618,7 +621,8 @@ def _native_open(comp: CompositeLayer, dq: DeviceQuad, m: int, mask: int, import
     q = dq.cstruct()
     comp._native_q = (q, dq)                     # (the run keeps q's mu / wt pointers: they must outlive it)
     run = C.c_void_p()
-    _lib.call("vsm_run_create", comp.dtype, C.byref(q), S, 1, marr, carr, _ptr(ws), nbytes, C.byref(run))
+    flags = 1 if (comp._sources_only and NATIVE_SOURCES_ONLY) else 0   # VSM_RUN_SOURCES_ONLY
+    _lib.call("vsm_run_create_ex", comp.dtype, C.byref(q), S, 1, marr, carr, _ptr(ws), nbytes, flags, C.byref(run))
     if import_arrays:
         try:
             cc = (_lib.vsm_composite * 1)(comp._cstruct_raw())
@@ -995,12 +999,17 @@ class Scene:
         # (REFERENCE_ORDER: every layer step is an rt_kernel_ call on the ONE CompositeLayer, like the reference's driver; the native
         # layout is then reached through rt_kernel_'s per-composite registry, NATIVE_DROPIN, instead of _run_layers_native)
         native = self._native_moments() if trace is None and not has_noscat and not REFERENCE_ORDER else set()
+        # (nothing of this walk reads R-+ / T++ of its composites unless `streams` asks for them: the REFERENCE_ORDER walk lets the
+        #  drop-in registry run sources-only too -- the same kernels as _run_layers_native, the same bits)
+        walk_src = streams is None and trace is None and not has_noscat
+        for c in self._composites:
+            c._sources_only = walk_src and REFERENCE_ORDER
         for g0 in range(0, len(self.moments), nb):
             group = self.moments[g0:g0 + nb]
             comps = self._composites[:len(group)]
             nat = [k for k in range(len(group)) if (g0 + k) in native]
             if nat:   # the layer loop on the native-layout composite (vsm_run_*), then the reference's arrays for the surface step
-                self._run_layers_native([group[k] for k in nat], [comps[k] for k in nat])
+                self._run_layers_native([group[k] for k in nat], [comps[k] for k in nat], sources_only=streams is None)
             rest = [k for k in range(len(group)) if (g0 + k) not in native]
             group_l, comps_l = [group[k] for k in rest], [comps[k] for k in rest]
             for iz in range(self.Nz if rest else 0):
@@ -1032,6 +1041,8 @@ class Scene:
                         Jm += self._th_comp.J0_m
                         Jp += self._th_comp.J0_p
                     streams.append(dict(m=m, weight=float(weight), R_mp=comp.R_mp.clone(), T_pp=comp.T_pp.clone(), J0_m=Jm, J0_p=Jp))
+        for c in self._composites:
+            c._sources_only = False
         if isinstance(model.surface, H.CoxMunkSurface) and self.ss_correction:   # rt_run.jl:520-524 (SFI is always on here)
             apply_ss_correction_(self.R_SFI, model.surface, pol, model.vza, model.vaz, self.qp.mu0,
                                  self.moments[-1]["tau_sum_surface"], model.m_max, self.arch, FT)
@@ -1050,9 +1061,11 @@ class Scene:
                 return set()
         return {i for i, mom in enumerate(self.moments) if run_supported(self.dt, self.N, self.pol.n, int(self.coupling[mom["m"]]))}
 
-    def _run_layers_native(self, group, comps):
+    def _run_layers_native(self, group, comps, sources_only: bool = True):
         """rt_run's layer loop (rt_run.jl:383-453) for the moments of `group` with the CompositeLayer in kernel-native layout:
-        vsm_run_create -> Nz x vsm_run_layer -> vsm_run_export into the reference-layout CompositeLayers `comps`."""
+        vsm_run_create -> Nz x vsm_run_layer -> vsm_run_export into the reference-layout CompositeLayers `comps`.
+        sources_only (and NATIVE_SOURCES_ONLY): only R+-, T-- and J0+- of `comps` are computed, R-+ and T++ come back as NaN --
+        for callers that read the composite through the surface step and the SFI post-processing alone."""
         L = _lib.lib()
         nm, N, S, ns = len(group), self.N, self.S, self.pol.n
         marr = (C.c_int * nm)(*[int(mom["m"]) for mom in group])
@@ -1063,7 +1076,8 @@ class Scene:
             ws = self._native_ws = _lib.poison(torch.empty(max(nbytes // 8, 2), dtype=torch.float64, device=self.dev))
         q = self.dq.cstruct()
         run = C.c_void_p()
-        _lib.call("vsm_run_create", self.dt, C.byref(q), S, nm, marr, carr, _ptr(ws), nbytes, C.byref(run))
+        flags = 1 if (sources_only and NATIVE_SOURCES_ONLY) else 0   # VSM_RUN_SOURCES_ONLY
+        _lib.call("vsm_run_create_ex", self.dt, C.byref(q), S, nm, marr, carr, _ptr(ws), nbytes, flags, C.byref(run))
         try:
             for iz in range(self.Nz):
                 ly0 = group[0]["layers"][iz]

@@ -347,6 +347,145 @@ __device__ __forceinline__ void nia_body_native(nsmem<RT, (4 * KS + 2 > 16 * RT)
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
+// interaction_helper!(::ScatteringInterface_11) for a SOURCES-ONLY run (VSM_RUN_SOURCES_ONLY): the new R+-, T-- and J0+- of the
+// composite depend on its R+-, T--, J0+- and the added layer alone (interaction.jl:207-266); R-+ and T++ feed only their own
+// recurrences, so they are neither read nor written.  With G1 = (I - r-+ R+-)^-1 and the push-through identity G2 R+- = R+- G1
+// (G2 = (I - R+- r-+)^-1), P = t++ R+- and W = G1 t--:
+//   T--' = T-- W ,  R+-' = r+- + P W ,  J0-' = J0- + T-- g ,  J0+' = j0+ + t++ J0+ + P g    (u = r-+ J0+ + j0-, g = G1 u)
+// (J0+' from G2 = I + R+- G1 r-+: the terms in j0- cancel).  The source terms ride in ONE spare column c1 of every strip:
+//   [E1 | r-+ J0+] = r-+ [R+- | J0+] ;  [P | t++ J0+] = t++ [R+- | J0+]     A = P = [r-+], Q = [t++]   (one pass, shared B)
+//   G1 = (I - E1)^-1                                                       the interaction's series / pivoted inverse on [E1] in P
+//   [W | g] = G1 [t-- | u]                                                 A = P = [G1]
+//   [T--' | T-- g] = T-- [W | g] ;  [R+-' | J0+'] = [r+- | j0+ + t++ J0+] + P [W | g]     A = P = [T--], Q = [P]
+// Products: 2 + the inverse + 1 + 2: four plus the series order (nine at order 7, four products of ninvert7), against the full
+// body's nine plus the order.  At most five live strips.  Blocks without spare columns take the source terms by mat-vecs.
+// ---------------------------------------------------------------------------------------------------------------------------
+template <int RT, int KS>
+__device__ __forceinline__ void nia_body_src(nsmem<RT, (4 * KS + 2 > 16 * RT)>& sm, npos<RT>& p, int n, double* __restrict__ comp,
+                                             nstrip<RT>& r_s, nstrip<RT>& t_s, int* status) {
+  using G = ngeo<RT>;
+  constexpr unsigned dP = 0, dQ = G::AF * 8;
+  double* vjp = sm.vec[0];
+  double* vjm = sm.vec[1];
+  double* vJp = sm.vec[2];
+  double* vJm = sm.vec[3];
+  double* vu = sm.vec[4];    // (mat-vec source path) u, then j0+ + t++ J0+
+  double* vtJ = sm.vec[5];
+  double* vg = sm.vec[6];    // g = G1 u
+  const int tid = threadIdx.x;
+  double* R_pm = comp + NC_RPM * G::AF;
+  double* T_mm = comp + NC_TMM * G::AF;
+  double* J0_p = comp + 4 * G::AF;
+  double* J0_m = J0_p + G::NP;
+  constexpr int c1 = 4 * KS, c2 = 4 * KS + 1;
+  constexpr bool RID = c2 < G::NP;
+  const bool own_wave = RID && p.wave == (c1 >> 4);
+  const bool laneA = own_wave && (p.col == c1);
+  // (three, five and six row tiles: the addend of the R+- update waits in the R+- record across the inverse -- its old contents
+  //  are in registers by then; a lane reads back exactly the addresses it wrote -- as nia_body_native's Z)
+  constexpr bool PARK = VSM_NATIVE_PARK_RT > 0 && (RT == VSM_NATIVE_PARK_RT || RT >= 5);
+  int slot = 0;
+  const ndpar<RT> dp(sm.usg, p);
+  const ninv_ctx cx{dP, sm.P, sm.gjs, status};
+  // ---- stage: composite vectors, [r-+] -> P, [t++] -> Q, R+- as the right operand -------------------------------------------
+  if (tid < G::NP) {
+    vJp[tid] = J0_p[tid];
+    vJm[tid] = J0_m[tid];
+  }
+  nstrip<RT> B;
+  nld_native(B, R_pm, p);
+  nstore(dP, r_s, p);
+  nstore(dQ, t_s, p);
+  __syncthreads();                                                                                       // (a)
+  {   // columns >= n of the record may carry a rider of the step above: cleared; J0+ rides in c1
+    const bool cin = p.col < n;
+#pragma unroll
+    for (int ta = 0; ta < RT; ++ta)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) B.v[ta][r] = cin ? B.v[ta][r] : (laneA ? vJp[p.row(ta, r)] : 0.0);
+  }
+  if constexpr (!RID) {   // r-+ J0+ , t++ J0+
+    nmv_rows<RT, KS>(dP, vJp, 1.0, sm.mv[0], p);
+    nmv_rows<RT, KS>(dQ, vJp, 1.0, sm.mv[1], p);
+  }
+  nstrip<RT> E, Bs;
+  double nrm;
+  {
+    nstrip<RT> Pm;
+    nmm2a<RT, KS, true, true>(E, dP, Pm, dQ, B, p);    // [E1 | r-+ J0+] ; [P | t++ J0+]
+    // Bs <- [t-- | u], r_s <- [r+- | j0+ + t++ J0+] (the addend of the R+- update; r-+ is in P for the norm's barrier)
+    ndsym(Bs, t_s, dp);
+    ndsym(r_s, r_s, dp);
+    if (own_wave) {
+#pragma unroll
+      for (int ta = 0; ta < RT; ++ta)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = p.row(ta, r);
+          Bs.v[ta][r] = laneA ? E.v[ta][r] + vjm[row] : Bs.v[ta][r];
+          r_s.v[ta][r] = laneA ? Pm.v[ta][r] + vjp[row] : r_s.v[ta][r];
+        }
+    }
+    if constexpr (PARK) nst_native(R_pm, r_s, p);
+    nrm = nnorm(E, n, sm, slot, p);                  // (b): every wave is done reading [r-+], [t++]
+    nstore(dQ, Pm, p);                               // [P] -> Q (read after the barriers of the inverse)
+  }
+  if constexpr (!RID) {   // u = r-+ J0+ + j0- ; j0+ + t++ J0+
+    if (tid < G::NP) {
+      vu[tid] = sm.mv[0][tid] + vjm[tid];
+      vtJ[tid] = sm.mv[1][tid] + vjp[tid];
+    }
+  }
+  nstrip<RT> W;
+  {
+    nstrip<RT> Gs;
+    const int K = ninv_order(nrm, status);                       // [E1] -> P, series
+    if (K == 7) ninvert7<RT, KS>(E, Gs, n, cx, p);               // (the usual order, in four products)
+    else ninvert<RT, KS>(K, E, Gs, n, cx, p);
+    __syncthreads();                                             // (c): [E1] no longer read
+    nstore(dP, Gs, p);                                           // [G1] -> P (its rider columns are never a contraction index)
+  }
+  __syncthreads();                                               // (d)
+  if constexpr (!RID) nmv_rows<RT, KS>(dP, vu, 1.0, vg, p);      // g = G1 u
+  {
+    nstrip<RT> Tm;
+    nld_native(Tm, T_mm, p);                                     // (requested under the product)
+    if constexpr (PARK) nld_native(r_s, R_pm, p);
+    nmm<RT, KS, true>(W, dP, Bs, p);                             // [W | g] = G1 [t-- | u]
+    __syncthreads();                                             // (e): [G1] no longer read
+    nstore(dP, Tm, p);                                           // [T--] -> P
+  }
+  __syncthreads();                                               // (f)
+  if constexpr (!RID) {   // T-- g , P g
+    nmv_rows<RT, KS>(dP, vg, 1.0, sm.mv[0], p);
+    nmv_rows<RT, KS>(dQ, vg, 1.0, sm.mv[1], p);
+  }
+  {
+    nstrip<RT> Tn;
+    nmm2a<RT, KS, true, false>(Tn, dP, r_s, dQ, W, p);   // [T--' | T-- g] = T-- [W | g] ; [R+-' | J0+'] = r_s + P [W | g]
+    nst_native(R_pm, r_s, p);
+    nst_native(T_mm, Tn, p);
+    if (laneA) {
+#pragma unroll
+      for (int ta = 0; ta < RT; ++ta)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = p.row(ta, r);
+          J0_p[row] = r_s.v[ta][r];
+          J0_m[row] = vJm[row] + Tn.v[ta][r];
+        }
+    }
+  }
+  if constexpr (!RID) {   // J0- = J0- + T-- g ; J0+ = j0+ + t++ J0+ + P g
+    __syncthreads();
+    if (tid < G::NP) {
+      J0_m[tid] = vJm[tid] + sm.mv[0][tid];
+      J0_p[tid] = vtJ[tid] + sm.mv[1][tid];
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
 // I/O of the standalone interaction (k_ia_native: vsm_interaction_f64 for N <= 64 -- the surface interaction of every run, the
 // callers of the operator API): the composite and the added layer in the reference's [N,N,S] arrays.
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -822,7 +961,8 @@ static_assert(sizeof(nsmem<3, true>) * 3 <= 163840, "three row tiles, mat-vec so
 static_assert(sizeof(nsmem<4, true>) * 2 <= 163840, "four row tiles: two workgroups per CU");
 static_assert(sizeof(nsmem<6, true>) <= 163840 && sizeof(nsmem<6>) <= 163840, "six row tiles: one workgroup per CU");
 
-template <int RT, int KS>
+// SRC: a sources-only run (VSM_RUN_SOURCES_ONLY): R-+ and T++ of the composite are neither read nor written (nia_body_src)
+template <int RT, int KS, bool SRC>
 __global__ __launch_bounds__(ngeo<RT>::NT, ngeo<RT>::WPS) void k_layer_native(int n, int gsz, unsigned uvmask, int ndoubl,
                                                                                 int toa, const double* __restrict__ pre,
                                                                                 nlayer_comps a, int* status) {
@@ -838,8 +978,10 @@ __global__ __launch_bounds__(ngeo<RT>::NT, ngeo<RT>::WPS) void k_layer_native(in
   ned_body<RT, KS>(sm, p, n, gsz, uvmask, ndoubl, img, r_s, t_s, status);
   if (toa) {   // copy_added_to_composite! (rt_helpers.jl:188-200)
     const ndpar<RT> dp(sm.usg, p);
-    nst_native(comp + NC_RMP * G::AF, r_s, p);
-    nst_native(comp + NC_TPP * G::AF, t_s, p);
+    if constexpr (!SRC) {
+      nst_native(comp + NC_RMP * G::AF, r_s, p);
+      nst_native(comp + NC_TPP * G::AF, t_s, p);
+    }
     nstrip<RT> d;
     ndsym(d, r_s, dp);
     nst_native(comp + NC_RPM * G::AF, d, p);
@@ -851,7 +993,8 @@ __global__ __launch_bounds__(ngeo<RT>::NT, ngeo<RT>::WPS) void k_layer_native(in
     }
     return;
   }
-  nia_body_native<RT, KS>(sm, p, n, comp, r_s, t_s, status);
+  if constexpr (SRC) nia_body_src<RT, KS>(sm, p, n, comp, r_s, t_s, status);
+  else nia_body_native<RT, KS>(sm, p, n, comp, r_s, t_s, status);
 }
 
 }  // namespace
@@ -860,12 +1003,13 @@ __global__ __launch_bounds__(ngeo<RT>::NT, ngeo<RT>::WPS) void k_layer_native(in
 #define VSM_NCAT2(a, b) a##b
 #define VSM_NCAT(a, b) VSM_NCAT2(a, b)
 #define VSM_NATIVE_DECL(KS) \
-  int VSM_NCAT(launch_layer_native_, KS)(int, int, int, unsigned, int, int, int, const double*, const nlayer_comps&, int*, hipStream_t); \
+  int VSM_NCAT(launch_layer_native_, KS)(int, int, int, unsigned, int, int, int, int, const double*, const nlayer_comps&, int*, \
+                                         hipStream_t);                                                                           \
   int VSM_NCAT(launch_ia_native_, KS)(int, int, const composite<double>&, const added<double>&, int*, hipStream_t);
 
 #ifdef VSM_NATIVE_KS
 VSM_NATIVE_DECL(VSM_NATIVE_KS)
-int VSM_NCAT(launch_layer_native_, VSM_NATIVE_KS)(int S, int nsub, int n, unsigned uvmask, int gsz, int ndoubl, int toa,
+int VSM_NCAT(launch_layer_native_, VSM_NATIVE_KS)(int S, int nsub, int n, unsigned uvmask, int gsz, int ndoubl, int toa, int src,
                                                   const double* pre, const nlayer_comps& comps, int* status, hipStream_t st) {
   constexpr int KS = VSM_NATIVE_KS;
   // KS = 4, 8, 12, 16 (n = 13..16, 29..32, 45..48, 61..64): KS / 4 row tiles without spare columns (mat-vec source path) instead of one row
@@ -873,7 +1017,7 @@ int VSM_NCAT(launch_layer_native_, VSM_NATIVE_KS)(int S, int nsub, int n, unsign
   constexpr int RT = (KS % 4 == 0 && KS >= 4) ? KS / 4 : (4 * KS + 2 + 15) / 16;
   static_assert(RT >= 1 && RT <= 6, "n <= 96");
   using SM = nsmem<RT, (4 * KS + 2 > 16 * RT)>;
-  auto kern = k_layer_native<RT, KS>;
+  auto kern = src ? k_layer_native<RT, KS, true> : k_layer_native<RT, KS, false>;
   const int prepared = ensure_dyn_lds(reinterpret_cast<const void*>(kern), sizeof(SM), "hipFuncSetAttribute(k_layer_native)");
   if (prepared) return prepared;
   hipLaunchKernelGGL(kern, dim3(S, nsub), dim3(ngeo<RT>::NT), sizeof(SM), st, n, gsz, uvmask, ndoubl, toa, pre, comps, status);
@@ -1090,8 +1234,9 @@ __device__ __forceinline__ int nnat_idx_rt(int rt, int i, int j) {   // nnat_idx
   const int lane = (kq << 4) | l15, u = 2 * ta + (r >> 1);
   return ((w * 2 * rt + u) * 64 + lane) * 2 + (r & 1);
 }
+// src: a sources-only run -- its R-+ and T++ are undefined and leave as quiet NaNs (a consumer fails loudly, never on stale data)
 template <typename ST>
-__global__ __launch_bounds__(256) void k_native_export(int N, int ns, ngroup_map gm, composite<ST> c) {
+__global__ __launch_bounds__(256) void k_native_export(int N, int ns, int src, ngroup_map gm, composite<ST> c) {
   const int s = blockIdx.x, tid = threadIdx.x;
   const long long NN = (long long)N * N;
   ST* out[4] = {c.R_mp + s * NN, c.R_pm + s * NN, c.T_pp + s * NN, c.T_mm + s * NN};
@@ -1108,6 +1253,7 @@ __global__ __launch_bounds__(256) void k_native_export(int N, int ns, ngroup_map
 #pragma unroll
       for (int k = 0; k < 4; ++k) v[k] = cn[k * af + ix];
     }
+    if (src) v[NC_RMP] = v[NC_TPP] = __builtin_nan("");
 #pragma unroll
     for (int k = 0; k < 4; ++k) out[k][e] = (ST)v[k];
   }
@@ -1212,9 +1358,9 @@ struct ndiag_args {
   int g0[NSUB_MAX];    // the group's Stokes components, 4 bits each
 };
 // mode 0: the scaling above; 1: TOA; 2: the composite is still (R = 0, T = diag, J = 0) -- every layer above was such a step --:
-// only the two diagonals change.
+// only the two diagonals change.  src: a sources-only run -- R-+ and T++ are left alone.
 template <typename ST>
-__global__ __launch_bounds__(256) void k_native_diag_layer(quad<ST> q, int rt, int n, double scale, int mode,
+__global__ __launch_bounds__(256) void k_native_diag_layer(quad<ST> q, int rt, int n, double scale, int mode, int src,
                                                            const ST* __restrict__ dtau, ndiag_args a) {
   __shared__ double tt[NATIVE_MAX_ROWS];
   const int s = blockIdx.x, isub = blockIdx.y, tid = threadIdx.x;
@@ -1229,7 +1375,7 @@ __global__ __launch_bounds__(256) void k_native_diag_layer(quad<ST> q, int rt, i
     tt[tid] = t;
     if (mode == 2 && tid < n) {
       const int ix = nnat_idx_rt(rt, tid, tid);
-      comp[NC_TPP * af + ix] *= t;
+      if (!src) comp[NC_TPP * af + ix] *= t;
       comp[NC_TMM * af + ix] *= t;
     }
   }
@@ -1242,13 +1388,15 @@ __global__ __launch_bounds__(256) void k_native_diag_layer(quad<ST> q, int rt, i
     const double ti = tt[i], tj = tt[j];
     if (toa) {
       const double d = (i == j) ? ti : 0.0;
-      comp[NC_RMP * af + e] = 0.0;
+      if (!src) {
+        comp[NC_RMP * af + e] = 0.0;
+        comp[NC_TPP * af + e] = d;
+      }
       comp[NC_RPM * af + e] = 0.0;
-      comp[NC_TPP * af + e] = d;
       comp[NC_TMM * af + e] = d;
     } else {
       comp[NC_RPM * af + e] *= ti * tj;
-      comp[NC_TPP * af + e] *= ti;
+      if (!src) comp[NC_TPP * af + e] *= ti;
       comp[NC_TMM * af + e] *= tj;
     }
   }
@@ -1350,10 +1498,10 @@ static int plan_subs(bool f32, int N, int ns, int nm, const int* m, const int* c
   return VSM_OK;
 }
 
-static int launch_layer_native(int ks, int S, int nsub, int n, unsigned uvmask, int gsz, int ndoubl, int toa, const double* pre,
-                               const nlayer_comps& comps, int* status, hipStream_t st) {
+static int launch_layer_native(int ks, int S, int nsub, int n, unsigned uvmask, int gsz, int ndoubl, int toa, int src,
+                               const double* pre, const nlayer_comps& comps, int* status, hipStream_t st) {
 #define VSM_NL(KS) \
-  case KS: return VSM_NCAT(launch_layer_native_, KS)(S, nsub, n, uvmask, gsz, ndoubl, toa, pre, comps, status, st);
+  case KS: return VSM_NCAT(launch_layer_native_, KS)(S, nsub, n, uvmask, gsz, ndoubl, toa, src, pre, comps, status, st);
   switch (ks) {
     VSM_NL(1) VSM_NL(2) VSM_NL(3) VSM_NL(4) VSM_NL(5) VSM_NL(6) VSM_NL(7) VSM_NL(8) VSM_NL(9) VSM_NL(10) VSM_NL(11) VSM_NL(12)
     VSM_NL(13) VSM_NL(14) VSM_NL(15) VSM_NL(16) VSM_NL(17) VSM_NL(18) VSM_NL(19) VSM_NL(20) VSM_NL(21) VSM_NL(22) VSM_NL(23) VSM_NL(24)
@@ -1424,8 +1572,9 @@ static quad<ST> run_quad(const vsm_run* run) {
 
 template <typename ST, typename Q>
 static int run_create(const Q* q, int S, int nm, const int* m, const int* coupling, void* workspace, size_t workspace_bytes,
-                      vsm_run** run_out) {
+                      unsigned flags, vsm_run** run_out) {
   VSM_REQUIRE(q && q->mu && q->wt && run_out && m, "vsm_run_create: null argument");
+  VSM_REQUIRE((flags & ~(unsigned)VSM_RUN_SOURCES_ONLY) == 0, "vsm_run_create_ex: unknown flags 0x%x", flags);
   VSM_REQUIRE(S >= 0 && nm >= 1 && nm <= NSUB_MAX, "vsm_run_create: bad S = %d / nm = %d (at most %d moments per run)", S, nm,
               NSUB_MAX);
   vsm_run* run = new vsm_run;
@@ -1438,6 +1587,8 @@ static int run_create(const Q* q, int S, int nm, const int* m, const int* coupli
   run->elem_size = (int)sizeof(ST);
   run->S = S;
   run->nm = nm;
+  // (the FP32 family keeps the full recurrences: R-+ and T++ stay defined there)
+  run->flags = sizeof(ST) == 8 ? flags : 0u;
   run->m.assign(m, m + nm);
   size_t total = 0;
   const int rc = plan_subs(sizeof(ST) == 4, q->N, q->n_stokes, nm, m, coupling, run->subs, (size_t)S, total);
@@ -1514,6 +1665,7 @@ static int run_layer(vsm_run* run, int ndoubl, const ST* dtau, const ST* varpi, 
     return native32_run_layer(run, ndoubl, dtau, varpi, tau_sum, F0, ncomp, Zpp, Zmp, z_stride, fcomp, toa, layer_coupling, status, st);
   } else {
   double* const ws = static_cast<double*>(run->ws);
+  const int src = (run->flags & VSM_RUN_SOURCES_ONLY) ? 1 : 0;
   // the pre-pass images of the layer: one record per (sub-problem, point)
   size_t pre_total = 0;
   for (const nat_sub& sb : run->subs)
@@ -1549,8 +1701,8 @@ static int run_layer(vsm_run* run, int ndoubl, const ST* dtau, const ST* varpi, 
         da.gsz[k] = sb.gsz;
         da.g0[k] = sb.g[0] | (sb.g[1] << 4) | (sb.g[2] << 8) | (sb.g[3] << 12);
       }
-      hipLaunchKernelGGL((k_native_diag_layer<ST>), dim3(run->S, nt), dim3(256), 0, st, q, h.rt, h.n, ldexp(1.0, ndoubl), mode, dtau,
-                         da);
+      hipLaunchKernelGGL((k_native_diag_layer<ST>), dim3(run->S, nt), dim3(256), 0, st, q, h.rt, h.n, ldexp(1.0, ndoubl), mode, src,
+                         dtau, da);
       VSM_LAUNCH_CHECK("k_native_diag_layer");
     }
     const int nsub = (int)act.size();
@@ -1577,7 +1729,7 @@ static int run_layer(vsm_run* run, int ndoubl, const ST* dtau, const ST* varpi, 
       default: launch_pre<6, ST>(ncomp > 0, q, run->S, nsub, h.n, ndoubl, dtau, varpi, tau_sum, F0, pa, pre_cl, st); break;
     }
     VSM_LAUNCH_CHECK("k_elemental_native");
-    const int rc = launch_layer_native(h.ks, run->S, nsub, h.n, h.uvmask, h.gsz, ndoubl, toa, pre_cl, lc, status, st);
+    const int rc = launch_layer_native(h.ks, run->S, nsub, h.n, h.uvmask, h.gsz, ndoubl, toa, src, pre_cl, lc, status, st);
     if (rc) return rc;
   }
   return VSM_OK;
@@ -1603,7 +1755,8 @@ static int run_convert(vsm_run* run, const CS* comps, void* stream) {
     if (IMPORT)
       hipLaunchKernelGGL((k_native_import<ST>), dim3(run->S), dim3(256), 0, as_stream(stream), run->N, run->ns, gm, cc);
     else
-      hipLaunchKernelGGL((k_native_export<ST>), dim3(run->S), dim3(256), 0, as_stream(stream), run->N, run->ns, gm, cc);
+      hipLaunchKernelGGL((k_native_export<ST>), dim3(run->S), dim3(256), 0, as_stream(stream), run->N, run->ns,
+                         (run->flags & VSM_RUN_SOURCES_ONLY) ? 1 : 0, gm, cc);
     VSM_LAUNCH_CHECK("k_native_export / import");
   }
   return VSM_OK;
@@ -1655,11 +1808,19 @@ size_t vsm_run_workspace_bytes_f32(int N, int n_stokes, int S, int nm, const int
 
 int vsm_run_create_f64(const vsm_quad_f64* q, int S, int nm, const int* m, const int* coupling, void* workspace,
                        size_t workspace_bytes, vsm_run** run_out) {
-  return run_create<double>(q, S, nm, m, coupling, workspace, workspace_bytes, run_out);
+  return run_create<double>(q, S, nm, m, coupling, workspace, workspace_bytes, 0u, run_out);
 }
 int vsm_run_create_f32(const vsm_quad_f32* q, int S, int nm, const int* m, const int* coupling, void* workspace,
                        size_t workspace_bytes, vsm_run** run_out) {
-  return run_create<float>(q, S, nm, m, coupling, workspace, workspace_bytes, run_out);
+  return run_create<float>(q, S, nm, m, coupling, workspace, workspace_bytes, 0u, run_out);
+}
+int vsm_run_create_ex_f64(const vsm_quad_f64* q, int S, int nm, const int* m, const int* coupling, void* workspace,
+                          size_t workspace_bytes, unsigned flags, vsm_run** run_out) {
+  return run_create<double>(q, S, nm, m, coupling, workspace, workspace_bytes, flags, run_out);
+}
+int vsm_run_create_ex_f32(const vsm_quad_f32* q, int S, int nm, const int* m, const int* coupling, void* workspace,
+                          size_t workspace_bytes, unsigned flags, vsm_run** run_out) {
+  return run_create<float>(q, S, nm, m, coupling, workspace, workspace_bytes, flags, run_out);
 }
 
 int vsm_run_destroy(vsm_run* run) {

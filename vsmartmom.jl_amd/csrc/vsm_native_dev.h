@@ -168,6 +168,35 @@ __device__ __forceinline__ void nmm2(nstrip<RT>& acc1, nstrip<RT>& acc2, unsigne
     VSM_NKSTEP_FENCE();
   }
 }
+// acc1 += [A1] B ; acc2 += [A2] B  (two left operands, one right operand: 2 RT independent accumulators per k-step)
+template <int RT, int KS, bool Z1 = false, bool Z2 = false>
+__device__ __forceinline__ void nmm2a(nstrip<RT>& acc1, unsigned dA1, nstrip<RT>& acc2, unsigned dA2, const nstrip<RT>& B,
+                                      npos<RT>& p) {
+  p.opaque();
+  double a1[2][RT], a2[2][RT];
+#pragma unroll
+  for (int t = 0; t < RT; ++t) {
+    a1[0][t] = *p.aptr(dA1, t, 0);
+    a2[0][t] = *p.aptr(dA2, t, 0);
+  }
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) {
+    if (ks + 1 < KS) {
+#pragma unroll
+      for (int t = 0; t < RT; ++t) {
+        a1[(ks + 1) & 1][t] = *p.aptr(dA1, t, ks + 1);
+        a2[(ks + 1) & 1][t] = *p.aptr(dA2, t, ks + 1);
+      }
+    }
+    const double b = B.v[ks >> 2][ks & 3];
+#pragma unroll
+    for (int t = 0; t < RT; ++t) {
+      acc1.v[t] = mfma<double>::mma(a1[ks & 1][t], b, (Z1 && ks == 0) ? acc_zero<double>() : acc1.v[t]);
+      acc2.v[t] = mfma<double>::mma(a2[ks & 1][t], b, (Z2 && ks == 0) ? acc_zero<double>() : acc2.v[t]);
+    }
+    VSM_NKSTEP_FENCE();
+  }
+}
 
 // ---- strip <-> A-form ---------------------------------------------------------------------------------------------------------
 template <int RT>

@@ -27,6 +27,7 @@ struct vsm_run {
   double mu0;
   int elem_size;           // 8: FP64 model (FP64 records and arithmetic), 4: Float32 model (FP32 records and arithmetic)
   int S, nm;
+  unsigned flags;          // vsm_run_create_ex: VSM_RUN_SOURCES_ONLY (FP64 runs)
   std::vector<int> m;
   std::vector<vsm::nat_sub> subs;
   std::vector<std::vector<int>> classes;   // indices into subs with equal (n, gsz, uvmask)
