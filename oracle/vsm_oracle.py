@@ -24,7 +24,7 @@ vectors are v[s, i].  The reference's Julia layout is A[i, j, s] column-major;
 from __future__ import annotations
 
 import math
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -421,6 +421,26 @@ class RTModel:
     varpi_cabannes: float = 1.0
     numerics: Numerics = field(default_factory=Numerics)
     F0: Optional[np.ndarray] = None  # [nStokes, S]; default SolarBeam e1 (solar_beam.jl:115-121)
+    # The type that DECIDES (None: FT): the 1024 eps doubling floor and doubling_number, the 2 eps scatter test, the
+    # eps active-stream masks.  With FT = float64 and decide_FT = float32 the oracle runs a Float32 model's algorithm
+    # (its decisions, its single-precision quadrature) in double arithmetic: see exact_model.
+    decide_FT: Optional[type] = None
+
+
+def deciding_type(model: RTModel) -> type:
+    return model.FT if model.decide_FT is None else model.decide_FT
+
+
+def exact_model(model: RTModel) -> RTModel:
+    """The exact reference of a Float32 (or any) model's algorithm: the same decisions, taken in model.FT, with FP64
+    arithmetic.  Quadrature nodes, weights and mu0 are the model's own values upcast, not recomputed in double; the
+    optical inputs stay the double-precision values they are built from.  Differences between a single-precision run and
+    this model are rounding only -- unlike the FP64 model, whose ndoubl (floor 1024 eps(Float64)) and nodes differ."""
+    q = model.quad_points
+    up = lambda a: np.asarray(a).astype(np.float64)
+    qp = QuadPoints(mu0=float(q.mu0), imu0=q.imu0, qp_mu=up(q.qp_mu), wt_mu=up(q.wt_mu), qp_muN=up(q.qp_muN),
+                    wt_muN=up(q.wt_muN), Nquad=q.Nquad, Nstreams=q.Nstreams)
+    return replace(model, quad_points=qp, FT=np.float64, decide_FT=deciding_type(model))
 
 
 def construct_core_optical_properties(model: RTModel, m: int) -> List[CoreScatteringOpticalProperties]:
@@ -445,15 +465,16 @@ def get_scattering_interface(prev: str, scatter: bool, iz: int) -> str:
     return "11" if scatter else "10"
 
 
-def extract_effective_props(lods: List[CoreScatteringOpticalProperties], FT):
-    """compEffectiveLayerProperties.jl:75-93."""
+def extract_effective_props(lods: List[CoreScatteringOpticalProperties], FT, DT=None):
+    """compEffectiveLayerProperties.jl:75-93.  DT: the type whose eps decides (RTModel.decide_FT; default FT)."""
+    DT = FT if DT is None else DT
     S = len(np.atleast_1d(lods[0].tau))
     L = len(lods)
     iface = "00"
     ifaces = []
     tau_sum = np.zeros((S, L + 1), dtype=np.float64)
     for iz in range(L):
-        scatter = np.max(lods[iz].tau * lods[iz].varpi) > 2 * eps(FT)
+        scatter = np.max(lods[iz].tau * lods[iz].varpi) > 2 * eps(DT)
         iface = get_scattering_interface(iface, bool(scatter), iz + 1)
         ifaces.append(iface)
         tau_sum[:, iz + 1] = tau_sum[:, iz] + lods[iz].tau
@@ -478,7 +499,7 @@ def expand_optical_properties(p: CoreScatteringOpticalProperties, FT) -> CoreSca
 
 
 def doubling_number(dtau_max, tau_end, FT):
-    """src/CoreRT/tools/rt_helper_functions.jl:49-69."""
+    """src/CoreRT/tools/rt_helper_functions.jl:49-69.  (FT here is the deciding type: only ndoubl of the result is used.)"""
     dtau_max = FT(dtau_max)
     tau_end = FT(tau_end)
     if tau_end <= dtau_max:
@@ -496,15 +517,16 @@ def doubling_number(dtau_max, tau_end, FT):
     return FT(10) ** x, ndoubl
 
 
-def get_dtau_ndoubl(tau, varpi, qp: QuadPoints, FT, numerics: Numerics = Numerics()):
-    """src/CoreRT/CoreKernel/rt_kernel.jl:266-287."""
-    threshold = FT(0.001 if numerics.dtau_max_threshold is None else numerics.dtau_max_threshold)
-    floor_val = FT(1024 * eps(FT) if numerics.dtau_min_floor is None else numerics.dtau_min_floor)
-    real = qp.qp_mu[qp.wt_mu > eps(FT)]
-    mu_min = FT(np.min(qp.qp_mu) if len(real) == 0 else np.min(real))
-    tw = FT(np.max(tau.astype(FT) * varpi.astype(FT)))
-    dtau_max = max(floor_val, min(tw, FT(threshold * mu_min)))
-    _, ndoubl = doubling_number(dtau_max, tw, FT)
+def get_dtau_ndoubl(tau, varpi, qp: QuadPoints, FT, numerics: Numerics = Numerics(), DT=None):
+    """src/CoreRT/CoreKernel/rt_kernel.jl:266-287.  ndoubl is decided in DT (RTModel.decide_FT; default FT), dtau is FT."""
+    DT = FT if DT is None else DT
+    threshold = DT(0.001 if numerics.dtau_max_threshold is None else numerics.dtau_max_threshold)
+    floor_val = DT(1024 * eps(DT) if numerics.dtau_min_floor is None else numerics.dtau_min_floor)
+    real = qp.qp_mu[qp.wt_mu > eps(DT)]
+    mu_min = DT(np.min(qp.qp_mu) if len(real) == 0 else np.min(real))
+    tw = DT(np.max(tau.astype(DT) * varpi.astype(DT)))
+    dtau_max = max(floor_val, min(tw, DT(threshold * mu_min)))
+    _, ndoubl = doubling_number(dtau_max, tw, DT)
     dtau = (tau / FT(2 ** ndoubl)).astype(FT)
     return dtau, ndoubl
 
@@ -558,9 +580,10 @@ def make_composite_layer(FT, N, S) -> CompositeLayer:
 
 
 def elemental(pol: Polarization, tau_sum, dtau, F0, varpi, Zpp, Zmp, m: int, ndoubl: int,
-              qp: QuadPoints, added: AddedLayer, FT):
+              qp: QuadPoints, added: AddedLayer, FT, DT=None):
     """src/CoreRT/CoreKernel/elemental.jl:174-230 with kernels :289-334 (get_elem_rt!),
-    :348-392 (get_elem_rt_SFI!), :403-422 (apply_D_elemental!)."""
+    :348-392 (get_elem_rt_SFI!), :403-422 (apply_D_elemental!).  DT: the type of the active-stream mask (default FT)."""
+    DT = FT if DT is None else DT
     mu = qp.qp_muN.astype(FT)
     N = len(mu)
     S = len(dtau)
@@ -574,7 +597,7 @@ def elemental(pol: Polarization, tau_sum, dtau, F0, varpi, Zpp, Zmp, m: int, ndo
     Zpp = np.broadcast_to(np.asarray(Zpp, dtype=FT), (S, N, N))
     Zmp = np.broadcast_to(np.asarray(Zmp, dtype=FT), (S, N, N))
     one = FT(1)
-    active = (wct > eps(FT))[None, None, :]
+    active = (wct > eps(DT))[None, None, :]
     with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
         r = w * Zmp * (mj / (mi + mj)) * wj * (-np.expm1(-d * ((one / mi) + (one / mj))))
         t_off = w * Zpp * (mj / (mi - mj)) * wj * expdiff_neg(d / mi, d / mj)
@@ -739,15 +762,16 @@ def copy_added_to_composite(comp: CompositeLayer, add: AddedLayer):
 
 
 def rt_kernel(pol, added, comp, props: CoreScatteringOpticalProperties, iface, tau_sum, m, qp, iz, F0, FT,
-              numerics: Numerics = Numerics(), trace=None):
-    """src/CoreRT/CoreKernel/rt_kernel.jl:175-250 (noRS).  iz is 1-based."""
+              numerics: Numerics = Numerics(), trace=None, DT=None):
+    """src/CoreRT/CoreKernel/rt_kernel.jl:175-250 (noRS).  iz is 1-based.  DT: the deciding type (default FT)."""
+    DT = FT if DT is None else DT
     tau, varpi = props.tau, props.varpi
-    scatter = np.max(tau * varpi) > 2 * eps(FT)
+    scatter = np.max(tau.astype(DT) * varpi.astype(DT)) > 2 * eps(DT)
     ndoubl = 0
     if scatter:
-        dtau, ndoubl = get_dtau_ndoubl(tau, varpi, qp, FT, numerics)
+        dtau, ndoubl = get_dtau_ndoubl(tau, varpi, qp, FT, numerics, DT)
         expk = np.exp(-dtau / FT(qp.mu0)).astype(FT)
-        elemental(pol, tau_sum, dtau, F0, varpi, props.Zpp, props.Zmp, m, ndoubl, qp, added, FT)
+        elemental(pol, tau_sum, dtau, F0, varpi, props.Zpp, props.Zmp, m, ndoubl, qp, added, FT, DT)
         doubling(pol, expk, ndoubl, added, FT)
     else:
         zero_added_noscat(added, tau, qp, FT)
@@ -863,7 +887,7 @@ def interaction_hdrf(comp: CompositeLayer, added_surf: AddedLayer, m, pol, qp: Q
 def rt_run(model: RTModel, trace=None, per_m=None, hdrf=None):
     """src/CoreRT/rt_run.jl:238-539 (noRS, SFI=true, Lambertian surface).  Returns (R_SFI, T_SFI); with `hdrf` = a dict it is
     filled with hdr [nVZA, nStokes, S], bhr_uw, bhr_dw [nStokes, S] (the reference returns bhr_uw[1,:], bhr_dw[1,:])."""
-    FT = model.FT
+    FT, DT = model.FT, deciding_type(model)
     pol, qp = model.pol, model.quad_points
     S, L = model.tau_rayl.shape
     N = qp.Nquad * pol.n
@@ -880,11 +904,11 @@ def rt_run(model: RTModel, trace=None, per_m=None, hdrf=None):
     for m in range(model.m_max + 1):
         weight = FT(0.5 / math.pi) if m == 0 else FT(1.0 / math.pi)
         lods = construct_core_optical_properties(model, m)
-        ifaces, tau_sum_all = extract_effective_props(lods, FT)
+        ifaces, tau_sum_all = extract_effective_props(lods, FT, DT)
         for iz in range(L):
             lo = expand_optical_properties(lods[iz], FT)
             rt_kernel(pol, added, comp, lo, ifaces[iz], tau_sum_all[:, iz].astype(FT), m, qp, iz + 1, F0, FT,
-                      model.numerics, trace)
+                      model.numerics, trace, DT)
         if np.ndim(model.albedo) == 1:     # spectrally varying Lambertian albedo (Legendre / spline surfaces)
             create_surface_layer_lambertian_spectral(model.albedo, added_surf, m, pol, qp, tau_sum_all[:, -1], FT)
         else:
@@ -914,16 +938,17 @@ def planck_spectrum_wn(T, nu):
     return 1.1910427e-5 * nu ** 3 / (np.exp(1.4387752 * nu / T) - 1.0)
 
 
-def thermal_source(pol: Polarization, qp: QuadPoints, dtau, varpi, B, FT):
+def thermal_source(pol: Polarization, qp: QuadPoints, dtau, varpi, B, FT, DT=None):
     """contribute!(::PreparedThermalEmission, ...) (src/CoreRT/Sources/thermal_emission.jl:241-301): the elemental layer's
     thermal source, identical up and down, on the Stokes-I rows:  2 pi (1 - varpi) B (1 - exp(-dtau / mu_i)).  [S, N]"""
+    DT = FT if DT is None else DT
     mu = qp.qp_mu.astype(FT)
     n = pol.n
     S = len(dtau)
     j = np.zeros((S, len(mu) * n), dtype=FT)
     coeff = FT(2 * math.pi) * (FT(1) - np.asarray(varpi, dtype=FT)) * np.asarray(B, dtype=FT)
     for i, mi in enumerate(mu):
-        if mi > eps(FT):
+        if mi > eps(DT):
             j[:, i * n] = coeff * (-np.expm1(-np.asarray(dtau, dtype=FT) / mi))
     return j
 
@@ -944,7 +969,7 @@ def rt_run_thermal(model: RTModel, B_layer, reset_slot_in_nonscattering_layers: 
     The Fourier loop below walks all moments the way the reference does and skips those in which the slot provably stays zero.
     `reset_slot_in_nonscattering_layers=True` is the corrected variant (the slot of a non-scattering layer is zero: such a layer
     emits nothing here, like the reference's, and carries nothing over) -- an explicit option, not the default."""
-    FT = model.FT
+    FT, DT = model.FT, deciding_type(model)
     pol, qp = model.pol, model.quad_points
     S, L = model.tau_rayl.shape
     N = qp.Nquad * pol.n
@@ -961,14 +986,14 @@ def rt_run_thermal(model: RTModel, B_layer, reset_slot_in_nonscattering_layers: 
         comp = make_composite_layer(FT, N, S)
         weight = FT(0.5 / math.pi) if m == 0 else FT(1.0 / math.pi)
         lods = construct_core_optical_properties(model, m)
-        ifaces, tau_sum_all = extract_effective_props(lods, FT)
+        ifaces, tau_sum_all = extract_effective_props(lods, FT, DT)
         for iz in range(L):
             lo = expand_optical_properties(lods[iz], FT)
             tau, varpi = lo.tau, lo.varpi
-            if np.max(tau * varpi) > 2 * eps(FT):
-                dtau, nd = get_dtau_ndoubl(tau, varpi, qp, FT, model.numerics)
-                elemental(pol, tau_sum_all[:, iz].astype(FT), dtau, F0, varpi, lo.Zpp, lo.Zmp, m, nd, qp, added, FT)
-                j = (thermal_source(pol, qp, dtau, varpi, B_layer[iz], FT) if (m == 0 and iz < B_layer.shape[0])
+            if np.max(tau.astype(DT) * varpi.astype(DT)) > 2 * eps(DT):
+                dtau, nd = get_dtau_ndoubl(tau, varpi, qp, FT, model.numerics, DT)
+                elemental(pol, tau_sum_all[:, iz].astype(FT), dtau, F0, varpi, lo.Zpp, lo.Zmp, m, nd, qp, added, FT, DT)
+                j = (thermal_source(pol, qp, dtau, varpi, B_layer[iz], FT, DT) if (m == 0 and iz < B_layer.shape[0])
                      else np.zeros((S, N), dtype=FT))                            # reset (:217-221) + contribute! (m = 0 only)
                 added.j0_p[...] = j
                 added.j0_m[...] = j

@@ -79,10 +79,12 @@ def _zdot(Zd, p, S, N, FT):
 
 
 def elemental_lin(pol, tau_sum, tau_sum_dot, dtau, F0, varpi, Zpp, Zmp, lin: LayerOpticsLin, m, ndoubl, qp,
-                  added: O.AddedLayer, added_lin: AddedLayerLin, FT):
+                  added: O.AddedLayer, added_lin: AddedLayerLin, FT, DT=None):
     """elemental_lin.jl:77-206 with kernels :456-591 (get_elem_rt_fused!) and :602-712 (get_elem_rt_SFI_fused!).
-    tau_sum_dot: [S, p].  Forward fields of `added` are filled as by the forward elemental!."""
-    O.elemental(pol, tau_sum, dtau, F0, varpi, Zpp, Zmp, m, ndoubl, qp, added, FT)
+    tau_sum_dot: [S, p].  Forward fields of `added` are filled as by the forward elemental!.  DT: the type of the
+    active-stream mask (RTModel.decide_FT; default FT)."""
+    DT = FT if DT is None else DT
+    O.elemental(pol, tau_sum, dtau, F0, varpi, Zpp, Zmp, m, ndoubl, qp, added, FT, DT)
     mu = qp.qp_muN.astype(FT)
     N, S = len(mu), len(dtau)
     n = pol.n
@@ -95,7 +97,7 @@ def elemental_lin(pol, tau_sum, tau_sum_dot, dtau, F0, varpi, Zpp, Zmp, lin: Lay
     w = varpi.astype(FT)[:, None, None]
     Zpp_b = np.broadcast_to(np.asarray(Zpp, dtype=FT), (S, N, N))
     Zmp_b = np.broadcast_to(np.asarray(Zmp, dtype=FT), (S, N, N))
-    active = (wct > O.eps(FT))[None, None, :]
+    active = (wct > O.eps(DT))[None, None, :]
     eye = np.eye(N, dtype=bool)[None]
     one = FT(1)
     D = O._dsign(pol, N).astype(FT)
@@ -549,8 +551,9 @@ def layer_optics_lin(model: O.RTModel, lin: LinModel, lods: List[O.CoreScatterin
 
 def rt_run_lin(model: O.RTModel, lin: LinModel):
     """rt_run_lin.jl:102-326 (noRS, SFI, Lambertian, all layers scattering).  Returns (R, T, Rdot, Tdot) with
-    Rdot/Tdot [nVZA, nStokes, S, P], P = n_layer_params + 1 (albedo last)."""
-    FT = model.FT
+    Rdot/Tdot [nVZA, nStokes, S, P], P = n_layer_params + 1 (albedo last).  O.exact_model(model) gives the exact reference
+    of a Float32 model's linearized run."""
+    FT, DT = model.FT, O.deciding_type(model)
     pol, qp = model.pol, model.quad_points
     S, L = model.tau_rayl.shape
     N = qp.Nquad * pol.n
@@ -571,16 +574,16 @@ def rt_run_lin(model: O.RTModel, lin: LinModel):
         weight = FT(0.5 / math.pi) if m == 0 else FT(1.0 / math.pi)
         lods = O.construct_core_optical_properties(model, m)
         lins = layer_optics_lin(model, lin, lods, m)
-        ifaces, tau_sum_all = O.extract_effective_props(lods, FT)
+        ifaces, tau_sum_all = O.extract_effective_props(lods, FT, DT)
         tsd = np.zeros((S, pl, L + 1))
         for iz in range(L):
             tsd[:, :, iz + 1] = tsd[:, :, iz] + lins[iz].tau_dot
         for iz in range(L):
             lo = O.expand_optical_properties(lods[iz], FT)
-            dtau, nd = O.get_dtau_ndoubl(lo.tau, lo.varpi, qp, FT, model.numerics)
+            dtau, nd = O.get_dtau_ndoubl(lo.tau, lo.varpi, qp, FT, model.numerics, DT)
             expk = np.exp(-dtau / FT(qp.mu0)).astype(FT)
             elemental_lin(pol, tau_sum_all[:, iz].astype(FT), tsd[:, :, iz], dtau, F0, lo.varpi, lo.Zpp, lo.Zmp,
-                          lins[iz], m, nd, qp, added, al, FT)
+                          lins[iz], m, nd, qp, added, al, FT, DT)
             dall = np.zeros((S, P), dtype=FT)
             dall[:, :pl] = lins[iz].tau_dot / FT(2 ** nd)
             doubling_lin(pol, expk, nd, added, al, dall, qp.mu0, pl, FT)
