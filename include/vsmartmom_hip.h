@@ -740,6 +740,41 @@ int vsm_postprocess_vza_ie_f64(int N, int n_stokes, int S, int K, int nV, const 
 int vsm_postprocess_vza_ie_f32(int N, int n_stokes, int S, int K, int nV, const int* row0_h, const float* w_h,
                                const float* ieJ0_m, const float* ieJ0_p, float* ieR, float* ieT, void* stream);
 
+/* ---- multi-sensor runs: radiances at an interior level of the column ---------------------------------------------------
+ * The level equation of rt_run_test_ms (rt_run_multisensor.jl; interlayer_flux_helper!, CoreKernel/interlayer_flux.jl:1-19,
+ * applied by postprocessing_vza_ms!, tools/postprocessing_vza_ms.jl:7-52) at ONE boundary, for S spectral points:
+ *   dw = (I - A B)^-1 (a + A c),   uw = (I - B A)^-1 (c + B a)
+ * A = top_R_pm (R⁺⁻ of the composite above the level) [N,N,S], a = top_J0_p (its J₀⁺) [N,1,S], B = bot_R_mp (R⁻⁺ of the composite
+ * below) [N,N,S] with bot_stride = N*N, or one [N,N] block shared by every point with bot_stride = 0 (a surface layer alone),
+ * c = bot_J0_m (its J₀⁻) [N,1,S].  Only these four arrays are read: a sources-only run (VSM_RUN_SOURCES_ONLY) may supply the top.
+ * uw = c + B dw (push-through identity), so the kernel does ONE pivoted elimination of [I - A B | a + A c] and no inverse.
+ * Level conventions of the multi-sensor driver (vsmartmom.jl_amd/core_rt_ms.py): level l = the boundary below layer l counted from
+ * the TOA; level 0 is the TOA composite after its surface interaction (uw = J₀⁻, dw = J₀⁺: no call here); levels 1..Nz-1 take the
+ * top composite of layers 1..l and the bottom composite of layers l+1..Nz with the surface; level Nz takes the surface layer
+ * ALONE as the bottom (the prototype never initialises that composite: a documented deviation).
+ * Outputs: uw / dw [nV,n_stokes,S] are ACCUMULATED, R[v,k,s] += w[v,k] * level[row0[v]+k, s], with row0_h / w_h exactly as in
+ * vsm_postprocess_vza (the same rows for uw and dw).  dw_full / uw_full (nullable, [N,1,S]): the level vectors at all streams.
+ * N <= 128: one fused kernel (MFMA product into LDS, Gauss-Jordan with the pivot rule of vsm_batch_inv, mat-vec, VZA rows; work
+ * may be NULL); N > 128: the operator-level twin, which needs work = vsm_level_radiance_work_elems(N, S) elements.
+ * An exactly zero pivot raises VSM_DEVSTAT_SINGULAR, a NaN / Inf in [I - A B | a + A c] VSM_DEVSTAT_NONFINITE (fused path). */
+size_t vsm_level_radiance_work_elems(int N, int S);
+int vsm_level_radiance_f64(int N, int n_stokes, int S, int nV, const int* row0_h, const double* w_h, const double* top_R_pm,
+                           const double* top_J0_p, const double* bot_R_mp, long long bot_stride, const double* bot_J0_m,
+                           double* uw, double* dw, double* dw_full, double* uw_full, double* work, void* stream);
+int vsm_level_radiance_f32(int N, int n_stokes, int S, int nV, const int* row0_h, const float* w_h, const float* top_R_pm,
+                           const float* top_J0_p, const float* bot_R_mp, long long bot_stride, const float* bot_J0_m,
+                           float* uw, float* dw, float* dw_full, float* uw_full, float* work, void* stream);
+/* Same contract, always operator level (batched products + vsm_batch_inv + products + vsm_postprocess_vza): the path for
+ * N > 128 and the cross-check of the fused kernel.  work is required. */
+int vsm_level_radiance_oplevel_f64(int N, int n_stokes, int S, int nV, const int* row0_h, const double* w_h,
+                                   const double* top_R_pm, const double* top_J0_p, const double* bot_R_mp, long long bot_stride,
+                                   const double* bot_J0_m, double* uw, double* dw, double* dw_full, double* uw_full,
+                                   double* work, void* stream);
+int vsm_level_radiance_oplevel_f32(int N, int n_stokes, int S, int nV, const int* row0_h, const float* w_h,
+                                   const float* top_R_pm, const float* top_J0_p, const float* bot_R_mp, long long bot_stride,
+                                   const float* bot_J0_m, float* uw, float* dw, float* dw_full, float* uw_full, float* work,
+                                   void* stream);
+
 /* ---- diagnostics used by the parity tests -------------------------------- */
 /* Runs the LDS-resident MFMA tile product used inside the fused kernels on plain
  * [N,N,S] inputs: C = A*B.  (Checks fragment layouts / swizzle independently.) */

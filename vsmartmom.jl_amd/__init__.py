@@ -8,7 +8,8 @@ be imported with a plain `import` statement; use the shim at the repo root:
 
 Sub-modules
     Architectures   CPU()/GPU() dispatch surface (src/Architectures.jl)
-    CoreRT          batched_mul / batch_inv_ / elemental_ / doubling_ / interaction_ / rt_kernel_ / rt_run
+    CoreRT          batched_mul / batch_inv_ / elemental_ / doubling_ / interaction_ / rt_kernel_ / rt_run /
+                    rt_run_multisensor (core_rt_ms: radiances at any level of the column)
     host_model      host-side producers of the hot path's inputs (streams, Z moments, layer mixing)
     CoreRTLin       linearized (Jacobian) pass: rt_run(model, lin_model, ...)
     CoreRTRaman     rotational-Raman pass: rt_run(RS_type::RRS, model, iBand)
@@ -17,11 +18,15 @@ Sub-modules
 from . import _lib, host_model  # noqa: F401
 from . import architectures as Architectures  # noqa: F401
 from . import core_rt as CoreRT  # noqa: F401
+from . import core_rt_ms  # noqa: F401
 from . import parallel  # noqa: F401
 from . import core_rt_lin as CoreRTLin  # noqa: F401
 from . import core_rt_raman as CoreRTRaman  # noqa: F401
 from . import raman_inputs  # noqa: F401
 from . import io_yaml  # noqa: F401
 from ._lib import VSMError, LIB_PATH  # noqa: F401
+
+CoreRT.rt_run_multisensor = core_rt_ms.rt_run_multisensor
+CoreRT.MultiSensorResult = core_rt_ms.MultiSensorResult
 
 __version__ = "0.1.0"

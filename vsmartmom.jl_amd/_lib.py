@@ -151,6 +151,9 @@ _SIGS = {
     "vsm_run_import_{T}": (_I, [_P, _P, _P]),
     "vsm_run_destroy": (_I, [_P]),
     "vsm_stokes_coupling_{T}": (_I, [_I, _I, _I, _P, _P, _P, _P]),
+    "vsm_level_radiance_work_elems": (_SZ, [_I, _I]),
+    "vsm_level_radiance_{T}": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _LL, _P, _P, _P, _P, _P, _P, _P]),
+    "vsm_level_radiance_oplevel_{T}": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _LL, _P, _P, _P, _P, _P, _P, _P]),
     "vsm_test_lds_mm_{T}": (_I, [_I, _I, _P, _P, _P, _P]),
     "vsm_test_lds_inv_{T}": (_I, [_I, _I, _P, _P, _I, _P, _P]),
     "vsm_test_poison_lds": (_I, [_P]),

@@ -1061,11 +1061,13 @@ class Scene:
                 return set()
         return {i for i, mom in enumerate(self.moments) if run_supported(self.dt, self.N, self.pol.n, int(self.coupling[mom["m"]]))}
 
-    def _run_layers_native(self, group, comps, sources_only: bool = True):
+    def _run_layers_native(self, group, comps, sources_only: bool = True, export_at=None):
         """rt_run's layer loop (rt_run.jl:383-453) for the moments of `group` with the CompositeLayer in kernel-native layout:
         vsm_run_create -> Nz x vsm_run_layer -> vsm_run_export into the reference-layout CompositeLayers `comps`.
         sources_only (and NATIVE_SOURCES_ONLY): only R+-, T-- and J0+- of `comps` are computed, R-+ and T++ come back as NaN --
-        for callers that read the composite through the surface step and the SFI post-processing alone."""
+        for callers that read the composite through the surface step and the SFI post-processing alone.
+        export_at: {l: callback} -- after layer l (1-based) the run is also exported into `comps` (the run itself goes on
+        unchanged) and callback(comps) is called: the multi-sensor run takes its top composites there (core_rt_ms.py)."""
         L = _lib.lib()
         nm, N, S, ns = len(group), self.N, self.S, self.pol.n
         marr = (C.c_int * nm)(*[int(mom["m"]) for mom in group])
@@ -1089,6 +1091,10 @@ class Scene:
                 lc = (C.c_int * nm)(*[self._layer_coupling(mom["m"], iz) for mom in group])
                 run_layer_native_(run, nm, int(ly0["nd"]), ly0["dtau"], p0.varpi, ly0["tau_sum"], self.F0, ncomp, zpp, zmp,
                                   0 if ncomp else p0.z_stride, p0.fcomp, iz == 0, lc, self.dt)
+                if export_at and (iz + 1) in export_at:
+                    cc = (type(comps[0].cstruct()) * nm)(*[c.cstruct() for c in comps])
+                    _lib.call("vsm_run_export", self.dt, run, cc, _stream_ptr())
+                    export_at[iz + 1](comps)
             cc = (type(comps[0].cstruct()) * nm)(*[c.cstruct() for c in comps])
             _lib.call("vsm_run_export", self.dt, run, cc, _stream_ptr())
         finally:

@@ -1,0 +1,227 @@
+// Level equation of the multi-sensor run (vsm_level_radiance_*): the radiance field at an interior boundary of the column from the
+// composite above it (top) and the composite below it (bottom).  Restates interlayer_flux_helper! (CoreKernel/interlayer_flux.jl:
+// 1-19; called through compute_interlayer_flux!, :185-201, by postprocessing_vza_ms!, tools/postprocessing_vza_ms.jl:7-52):
+//
+//   dw = (I - A B)^-1 (a + A c),   uw = (I - B A)^-1 (c + B a),   A = top R+-, a = top J0+, B = bottom R-+, c = bottom J0-
+//
+// The reference forms two inverses and four products.  Here uw comes from dw by the push-through identity
+// (I - B A)^-1 (c + B a) = c + B (I - A B)^-1 (a + A c) = c + B dw, and dw from ONE pivoted Gauss-Jordan elimination of [M | d]:
+//   1. [M | d] = [I - A B | a + A c] in one MFMA product (c rides as the spare column N of B), written to LDS;
+//   2. Gauss-Jordan on [M | d] in LDS, the pivot rule of vsm_inverse.h (largest |m_ik|, first occurrence) -- no inverse;
+//   3. uw = c + B dw (mat-vec), then the VZA rows of uw / dw added into the caller's [nV, n_stokes, S] outputs.
+// One spectral point per 256-thread workgroup, N <= 128 (FP64 [M | d]: 129 KiB of LDS at N = 128).  Larger N: the operator-level
+// twin (batched products + vsm_batch_inv + products + vsm_postprocess_vza), the same contract.
+#include "vsm_common.h"
+#include "vsm_internal.h"
+#include "vsm_inverse.h"
+
+namespace vsm {
+
+constexpr int LEVEL_FUSED_MAX_N = 128;
+constexpr int LEVEL_NT = 256;
+
+struct level_pp {
+  int row0[64];
+  double w[256];
+};
+
+template <typename T>
+__global__ void __launch_bounds__(LEVEL_NT) k_level_radiance(int N, int ns, int nV, int nVtot, level_pp pa, const T* __restrict__ A,
+                                                             const T* __restrict__ a, const T* __restrict__ B, long long bstride,
+                                                             const T* __restrict__ c, T* uw, T* dw, T* dw_full, T* uw_full,
+                                                             int* status) {
+  extern __shared__ __align__(16) unsigned char lds_raw[];
+  T* L = reinterpret_cast<T*>(lds_raw);          // [M | d], row-major, leading dimension LD = N + 1
+  const int LD = N + 1;
+  T* xs = L + (size_t)N * LD;                    // dw
+  T* ys = xs + N;                                // uw
+  __shared__ int s_piv, s_flag;
+  const long long s = blockIdx.x;
+  const T* As = A + s * (long long)N * N;
+  const T* Bs = B + s * bstride;
+  const T* as_ = a + s * N;
+  const T* cs = c + s * N;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, kq = lane >> 4;
+  if (tid == 0) s_flag = 0;
+
+  // 1. [M | d] = [I | a] - [A B | -A c]: 16 x 16 output tiles over the N x (N + 1) block, round-robin over the four waves
+  const int MT = (N + 15) / 16, CT = (N + 16) / 16;
+  bool bad = false;
+  for (int t = wave; t < MT * CT; t += LEVEL_NT / 64) {
+    const int ti = t / CT, tj = t % CT;
+    const int row = 16 * ti + li, col = 16 * tj + li;
+    typename mfma<T>::acc_t acc = acc_zero<T>();
+    for (int k0 = 0; k0 < N; k0 += 4) {
+      const int k = k0 + kq;
+      const T av = (row < N && k < N) ? As[(long long)k * N + row] : T(0);
+      const T bv = (k < N) ? (col < N ? Bs[(long long)col * N + k] : (col == N ? cs[k] : T(0))) : T(0);
+      acc = mfma<T>::mma(av, bv, acc);
+    }
+    const int ocol = 16 * tj + li;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int orow = 16 * ti + mfma<T>::crow(lane, r);
+      if (orow < N && ocol <= N) {
+        const T v = ocol < N ? ((orow == ocol ? T(1) : T(0)) - acc[r]) : as_[orow] + acc[r];
+        bad |= !isfinite(v);
+        L[orow * LD + ocol] = v;
+      }
+    }
+  }
+  if (bad) s_flag = 1;
+  __syncthreads();
+  if (s_flag && tid == 0) atomicOr(&status[0], (int)VSM_DEVSTAT_NONFINITE);
+
+  // 2. Gauss-Jordan elimination of [M | d]: row k is the pivot row of step k and is not normalised; dw_i = d_i / m_ii at the end
+  const int tj = tid & 63, ti = tid >> 6;
+  for (int k = 0; k < N; ++k) {
+    if (wave == 0) {
+      const bool in0 = lane >= k && lane < N, in1 = lane + 64 >= k && lane + 64 < N;
+      const T v0 = in0 ? fabs(L[lane * LD + k]) : T(-1);
+      const T v1 = in1 ? fabs(L[(lane + 64) * LD + k]) : T(-1);
+      const T best = wave_max(v0 > v1 ? v0 : v1);
+      const unsigned long long m0 = __ballot(in0 && v0 == best), m1 = __ballot(in1 && v1 == best);
+      const int p = m0 ? (__ffsll((long long)m0) - 1) : (m1 ? 64 + __ffsll((long long)m1) - 1 : k);
+      if (lane == 0) s_piv = p;
+    }
+    __syncthreads();
+    const int p = s_piv;
+    if (p != k) {
+      for (int j = k + tid; j <= N; j += LEVEL_NT) {
+        const T tmp = L[k * LD + j];
+        L[k * LD + j] = L[p * LD + j];
+        L[p * LD + j] = tmp;
+      }
+      __syncthreads();
+    }
+    const T pv = L[k * LD + k];
+    if (pv == T(0) && tid == 0) atomicOr(&status[0], (int)VSM_DEVSTAT_SINGULAR);
+    const T inv = T(1) / pv;
+    for (int i = ti; i < N; i += LEVEL_NT / 64) {
+      if (i == k) continue;
+      const T f = L[i * LD + k] * inv;
+      for (int j = k + 1 + tj; j <= N; j += 64) L[i * LD + j] -= f * L[k * LD + j];
+    }
+    __syncthreads();
+  }
+  for (int i = tid; i < N; i += LEVEL_NT) xs[i] = L[i * LD + N] / L[i * LD + i];
+  __syncthreads();
+
+  // 3. uw = c + B dw
+  for (int i = tid; i < N; i += LEVEL_NT) {
+    T y = cs[i];
+    for (int j = 0; j < N; ++j) y += Bs[(long long)j * N + i] * xs[j];
+    ys[i] = y;
+    if (dw_full) dw_full[s * N + i] = xs[i];
+    if (uw_full) uw_full[s * N + i] = y;
+  }
+  __syncthreads();
+  for (int e = tid; e < nV * ns; e += LEVEL_NT) {
+    const int v = e % nV, k = e / nV;
+    const T w = (T)pa.w[v + nV * k];
+    const long long dst = (s * ns + k) * nVtot + v;
+    uw[dst] += w * ys[pa.row0[v] + k];
+    dw[dst] += w * xs[pa.row0[v] + k];
+  }
+}
+
+template <typename T>
+static int level_radiance_fused(int N, int ns, int S, int nV, const int* row0_h, const T* w_h, const T* A, const T* a, const T* B,
+                                long long bstride, const T* c, T* uw, T* dw, T* dw_full, T* uw_full, hipStream_t st) {
+  int* status = device_status();
+  if (!status) return VSM_ERR_HIP;
+  const size_t lds = ((size_t)N * (N + 1) + 2 * (size_t)N) * sizeof(T);
+  const int rc = ensure_dyn_lds(reinterpret_cast<const void*>(k_level_radiance<T>), lds, "hipFuncSetAttribute(k_level_radiance)");
+  if (rc) return rc;
+  level_pp pa = {};
+  if (nV <= 64) {
+    for (int v = 0; v < nV; ++v) pa.row0[v] = row0_h[v];
+    for (int k = 0; k < ns; ++k)
+      for (int v = 0; v < nV; ++v) pa.w[v + nV * k] = (double)w_h[v + nV * k];
+    hipLaunchKernelGGL(k_level_radiance<T>, dim3(S), dim3(LEVEL_NT), lds, st, N, ns, nV, nV, pa, A, a, B, bstride, c, uw, dw,
+                       dw_full, uw_full, status);
+    VSM_LAUNCH_CHECK("k_level_radiance");
+    return VSM_OK;
+  }
+  // more than the 64 viewing angles one launch carries: the level vectors in full, then the VZA rows by vsm_postprocess_vza
+  T* full = dw_full && uw_full ? nullptr : static_cast<T*>(scratch(2 * (size_t)N * S * sizeof(T), 0, st));
+  if (!dw_full || !uw_full) {
+    if (!full) return VSM_ERR_HIP;
+    if (!dw_full) dw_full = full;
+    if (!uw_full) uw_full = full + (size_t)N * S;
+  }
+  hipLaunchKernelGGL(k_level_radiance<T>, dim3(S), dim3(LEVEL_NT), lds, st, N, ns, 0, 0, pa, A, a, B, bstride, c, uw, dw, dw_full,
+                     uw_full, status);
+  VSM_LAUNCH_CHECK("k_level_radiance");
+  return postprocess_vza<T>(N, ns, S, nV, row0_h, w_h, uw_full, dw_full, uw, dw, st);
+}
+
+// operator-level twin: M = I - A B, d = a + A c (two batched products), dw = M^-1 d (vsm_batch_inv + product), uw = c + B dw
+template <typename T>
+static int level_radiance_oplevel(int N, int ns, int S, int nV, const int* row0_h, const T* w_h, const T* A, const T* a, const T* B,
+                                  long long bstride, const T* c, T* uw, T* dw, T* dw_full, T* uw_full, T* work, hipStream_t st) {
+  const long long NN = (long long)N * N;
+  T* M = work;
+  T* Minv = M + NN * S;
+  T* d = Minv + NN * S;
+  T* x = dw_full ? dw_full : d + (long long)N * S;
+  T* y = uw_full ? uw_full : d + 2 * (long long)N * S;
+  int rc = gemm<T>(N, N, N, S, A, NN, B, bstride, M, NN, T(-1), (const T*)nullptr, 0, T(0), T(1), st);
+  if (!rc) rc = gemm<T>(N, 1, N, S, A, NN, c, N, d, N, T(1), a, N, T(1), T(0), st);
+  if (!rc) rc = batch_inv<T>(N, S, M, Minv, nullptr, st);
+  if (!rc) rc = gemm<T>(N, 1, N, S, Minv, NN, d, N, x, N, T(1), (const T*)nullptr, 0, T(0), T(0), st);
+  if (!rc) rc = gemm<T>(N, 1, N, S, B, bstride, x, N, y, N, T(1), c, N, T(1), T(0), st);
+  if (!rc) rc = postprocess_vza<T>(N, ns, S, nV, row0_h, w_h, y, x, uw, dw, st);
+  return rc;
+}
+
+template <typename T>
+static int level_check(int N, int ns, int S, int nV, const int* row0_h, const T* w_h, const T* A, const T* a, const T* B,
+                       long long bstride, const T* c, T* uw, T* dw) {
+  VSM_REQUIRE(N > 0 && ns >= 1 && ns <= 4 && N % ns == 0 && S >= 0 && nV >= 0, "level_radiance: bad size (N %d, n_stokes %d, S %d, nV %d)",
+              N, ns, S, nV);
+  VSM_REQUIRE(bstride == 0 || bstride == (long long)N * N, "level_radiance: bot_stride must be 0 or N*N");
+  VSM_REQUIRE(S == 0 || (A && a && B && c), "level_radiance: null operand");
+  VSM_REQUIRE(S == 0 || nV == 0 || (row0_h && w_h && uw && dw), "level_radiance: null output / viewing-angle table");
+  for (int v = 0; v < nV; ++v)
+    VSM_REQUIRE(row0_h[v] >= 0 && row0_h[v] + ns <= N, "level_radiance: row0[%d] = %d outside the %d streams", v, row0_h[v], N);
+  return VSM_OK;
+}
+
+}  // namespace vsm
+
+using namespace vsm;
+
+extern "C" {
+
+size_t vsm_level_radiance_work_elems(int N, int S) {
+  return N <= 0 || S <= 0 ? 0 : 2 * (size_t)N * N * S + 3 * (size_t)N * S;
+}
+
+#define VSM_LEVEL_API(T, SFX)                                                                                                   \
+  int vsm_level_radiance_##SFX(int N, int n_stokes, int S, int nV, const int* row0_h, const T* w_h, const T* top_R_pm,          \
+                               const T* top_J0_p, const T* bot_R_mp, long long bot_stride, const T* bot_J0_m, T* uw, T* dw,    \
+                               T* dw_full, T* uw_full, T* work, void* stream) {                                                \
+    int rc = level_check<T>(N, n_stokes, S, nV, row0_h, w_h, top_R_pm, top_J0_p, bot_R_mp, bot_stride, bot_J0_m, uw, dw);      \
+    if (rc || S == 0) return rc;                                                                                                \
+    if (N <= LEVEL_FUSED_MAX_N)                                                                                                 \
+      return level_radiance_fused<T>(N, n_stokes, S, nV, row0_h, w_h, top_R_pm, top_J0_p, bot_R_mp, bot_stride, bot_J0_m, uw, \
+                                     dw, dw_full, uw_full, as_stream(stream));                                                  \
+    VSM_REQUIRE(work, "level_radiance: N = %d > %d takes the operator-level path: work (vsm_level_radiance_work_elems) required", \
+                N, LEVEL_FUSED_MAX_N);                                                                                          \
+    return level_radiance_oplevel<T>(N, n_stokes, S, nV, row0_h, w_h, top_R_pm, top_J0_p, bot_R_mp, bot_stride, bot_J0_m, uw,  \
+                                     dw, dw_full, uw_full, work, as_stream(stream));                                            \
+  }                                                                                                                             \
+  int vsm_level_radiance_oplevel_##SFX(int N, int n_stokes, int S, int nV, const int* row0_h, const T* w_h, const T* top_R_pm,  \
+                                       const T* top_J0_p, const T* bot_R_mp, long long bot_stride, const T* bot_J0_m, T* uw,    \
+                                       T* dw, T* dw_full, T* uw_full, T* work, void* stream) {                                  \
+    int rc = level_check<T>(N, n_stokes, S, nV, row0_h, w_h, top_R_pm, top_J0_p, bot_R_mp, bot_stride, bot_J0_m, uw, dw);      \
+    if (rc || S == 0) return rc;                                                                                                \
+    VSM_REQUIRE(work, "level_radiance_oplevel: work (vsm_level_radiance_work_elems) required");                                 \
+    return level_radiance_oplevel<T>(N, n_stokes, S, nV, row0_h, w_h, top_R_pm, top_J0_p, bot_R_mp, bot_stride, bot_J0_m, uw,  \
+                                     dw, dw_full, uw_full, work, as_stream(stream));                                            \
+  }
+VSM_LEVEL_API(double, f64)
+VSM_LEVEL_API(float, f32)
+
+}  // extern "C"
