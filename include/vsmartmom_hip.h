@@ -623,9 +623,20 @@ int vsm_mix_Z_moments_f32(int N, int S, int ncomp, int nm, const float* const* Z
  * UNDEFINED, and everything derived from them (the R-+ and T++ of a later interaction) is too.  R+-, T--, J0+- equal those of a
  * full run up to rounding (the interaction is re-associated around (I - r-+ R+-)^-1).  FP64 runs only: an _f32 run accepts the
  * flag and keeps the full recurrences.  vsm_run_create_* = vsm_run_create_ex_* with flags = 0 (the full composite).
+ * Zero-weight tail.  flags |= VSM_RUN_ZW_TAIL (or vsm_run_zw_tail(run) before the run's first layer step: the same): the library
+ * reads q->wt once (a synchronous copy on the legacy stream -- not while a stream is being captured into a graph), and
+ * finds the trailing run of quadrature nodes whose weight is exactly 0 (rt_set_streams appends the VZA and SZA nodes behind the
+ * Gauss-Legendre nodes with weight 0; a zero weight elsewhere does not count).  Their streams are the last rows of every block
+ * (rows are node-major), and every matrix the layer steps form has their columns zero off the diagonal (elemental! gives r a zero
+ * column and t a diagonal one there; sums, products and the inverses keep that): the products of the layer steps skip the k-steps
+ * that cover only such streams and add their diagonal terms lane by lane instead.  Per block: real rows = (real nodes) x (components
+ * of the block), k-steps formed = ceil(real rows / 4).  No trailing zero-weight node (e.g. a VZA that is a Gauss-Legendre node):
+ * the dense products, bit for bit.  The composite must then come from this run's own layer steps: vsm_run_import drops the flag
+ * for the rest of the run (a caller's arrays need not have those zero columns).  R+-, T--, J0+- (and R-+, T++ of a full run) equal
+ * those of a run without the flag up to rounding.  FP64 runs only: an _f32 run accepts the flag and ignores it.
  * Stream: see Conventions; library scratch (the pre-pass images of the layer). */
 typedef struct vsm_run vsm_run;
-enum { VSM_RUN_SOURCES_ONLY = 1 };
+enum { VSM_RUN_SOURCES_ONLY = 1, VSM_RUN_ZW_TAIL = 2 };
 int vsm_run_supported(int N, int n_stokes, int coupling);
 size_t vsm_run_workspace_bytes(int N, int n_stokes, int S, int nm, const int* coupling_h);
 int vsm_run_supported_f32(int N, int n_stokes, int coupling);
@@ -648,6 +659,7 @@ int vsm_run_export_f64(vsm_run* run, const vsm_composite_f64* comps, void* strea
 int vsm_run_export_f32(vsm_run* run, const vsm_composite_f32* comps, void* stream);
 int vsm_run_import_f64(vsm_run* run, const vsm_composite_f64* comps, void* stream);
 int vsm_run_import_f32(vsm_run* run, const vsm_composite_f32* comps, void* stream);
+int vsm_run_zw_tail(vsm_run* run);
 int vsm_run_destroy(vsm_run* run);
 int vsm_stokes_coupling_f64(int N, int n_stokes, int nblocks, const double* Zpp, const double* Zmp, int* mask_d, void* stream);
 int vsm_stokes_coupling_f32(int N, int n_stokes, int nblocks, const float* Zpp, const float* Zmp, int* mask_d, void* stream);

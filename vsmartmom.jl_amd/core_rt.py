@@ -41,6 +41,8 @@ THERMAL_FUSION = True   # False: the `:thermal` slot at operator level (tools/th
 NATIVE_RUN = True       # False: the layer loop on the reference-layout CompositeLayer (vsm_layer_forward_multi) instead of vsm_run_*
 NATIVE_SOURCES_ONLY = True  # Scene.run without `streams`: the native run keeps only R+-, T-- and J0+- of the composite (vsm_run_create_ex,
 #                         VSM_RUN_SOURCES_ONLY: the SFI outputs read nothing else); its exported R-+ / T++ are NaN.  False: full runs
+NATIVE_ZW_TAIL = True   # Scene's native runs skip the k-steps of the zero-weight VZA / SZA streams in every product (vsm_run_zw_tail =
+#                         VSM_RUN_ZW_TAIL: those columns are zero off the diagonal in every matrix of the layer steps).  False: dense
 NATIVE_DROPIN = True    # rt_kernel_ keeps the CompositeLayer it is handed in the kernels' native layout between its calls (a per-
 #                         composite registry, exported lazily: the path of the reference's own driver order, rt_run.jl:383-453)
 REFERENCE_ORDER = False  # True: Scene.run walks `for m` outside `for iz`, one rt_kernel_ call per (m, iz) on ONE CompositeLayer --
@@ -1081,6 +1083,10 @@ class Scene:
         flags = 1 if (sources_only and NATIVE_SOURCES_ONLY) else 0   # VSM_RUN_SOURCES_ONLY
         _lib.call("vsm_run_create_ex", self.dt, C.byref(q), S, nm, marr, carr, _ptr(ws), nbytes, flags, C.byref(run))
         try:
+            # VSM_RUN_ZW_TAIL (the run starts from its own TOA layer).  Its synchronous read of the weights cannot be captured into
+            # a graph: a captured run keeps the dense products -- the same bits wherever no pivoted inverse is taken
+            if NATIVE_ZW_TAIL and not torch.cuda.is_current_stream_capturing():
+                _lib.check(L.vsm_run_zw_tail(run))
             for iz in range(self.Nz):
                 ly0 = group[0]["layers"][iz]
                 props = [mom["layers"][iz]["props"] for mom in group]

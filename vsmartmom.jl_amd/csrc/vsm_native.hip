@@ -36,7 +36,7 @@ namespace {
 // ---------------------------------------------------------------------------------------------------------------------------
 // On return (all waves past a barrier): r_s = strip of the final r-+ (row signs of apply_D applied), t_s = strip of t++ (rider
 // columns cleared), sm.vec[0] = j0+, sm.vec[1] = j0- (final sign), sm.usg filled.
-template <int RT, int KS>
+template <int RT, int KS, int KZ = KS>
 __device__ __forceinline__ void ned_body(nsmem<RT, (4 * KS + 2 > 16 * RT)>& sm, npos<RT>& p, int n, int gsz, unsigned uvmask, int ndoubl,
                                          const double* __restrict__ img, nstrip<RT>& r_s, nstrip<RT>& t_s, int* status) {
   using G = ngeo<RT>;
@@ -80,14 +80,14 @@ __device__ __forceinline__ void ned_body(nsmem<RT, (4 * KS + 2 > 16 * RT)>& sm, 
     nstrip<RT> W, tt;
     const double fW = laneA ? expk : (laneB ? 1.0 : 0.0), fR = laneB ? expk : 1.0;
     if constexpr (!RID) {   // r j0+ , r j1-   (P = [r])
-      nmv_rows<RT, KS>(dP, jp, 1.0, sm.mv[0], p);
-      nmv_rows<RT, KS>(dP, jm, expk, sm.mv[1], p);
+      nmv_rows<RT, KS, KZ>(dP, jp, 1.0, sm.mv[0], p);
+      nmv_rows<RT, KS, KZ>(dP, jm, expk, sm.mv[1], p);
     }
     {
       nstrip<RT> Gs;
       {
         nstrip<RT> E;
-        nmm2<RT, KS, true, true>(E, W, dP, r_s, t_s, p);
+        nmm2<RT, KS, true, true, KZ>(E, W, dP, r_s, t_s, p);
         if (own_wave) {
 #pragma unroll
           for (int ta = 0; ta < RT; ++ta)
@@ -104,21 +104,21 @@ __device__ __forceinline__ void ned_body(nsmem<RT, (4 * KS + 2 > 16 * RT)>& sm, 
             sm.vec[5][tid] = jp[tid] + sm.mv[1][tid];
           }
         }
-        ninvert<RT, KS>(ninv_order(nrm, status), E, Gs, n, cx, p);
+        ninvert<RT, KS, false, KZ>(ninv_order(nrm, status), E, Gs, n, cx, p);
       }
-      nmm<RT, KS, true>(tt, dQ, Gs, p);    // tt = t G
+      nmm<RT, KS, true, KZ>(tt, dQ, Gs, p);    // tt = t G
     }
     nload(t_s, dQ, p);                     // t's strip (with its riders) is not kept in registers across the inverse
     __syncthreads();                       // P ([E]) and Q ([t]) no longer read
     nstore(dP, tt, p);
     __syncthreads();
     if constexpr (!RID) {   // tt u1 , tt u2   (the partial sums of r j were consumed two barriers ago)
-      nmv_rows<RT, KS>(dP, sm.vec[4], 1.0, sm.mv[0], p);
-      nmv_rows<RT, KS>(dP, sm.vec[5], 1.0, sm.mv[1], p);
+      nmv_rows<RT, KS, KZ>(dP, sm.vec[4], 1.0, sm.mv[0], p);
+      nmv_rows<RT, KS, KZ>(dP, sm.vec[5], 1.0, sm.mv[1], p);
     }
     {
       nstrip<RT> tn;
-      nmm2<RT, KS, false, true>(r_s, tn, dP, W, t_s, p);   // r' = r + tt W (riders: the new j0-, j0+) ; t' = tt t
+      nmm2<RT, KS, false, true, KZ>(r_s, tn, dP, W, t_s, p);   // r' = r + tt W (riders: the new j0-, j0+) ; t' = tt t
       t_s = tn;
     }
     const double expk_step = expk;
@@ -178,7 +178,7 @@ __device__ __forceinline__ void ned_body(nsmem<RT, (4 * KS + 2 > 16 * RT)>& sm, 
 // record here and nothing of what nia_body does about exposed loads pays (each measured: DESIGN.md 4.0b).  Kept as a function of
 // its own: routed through nia_body's I/O policy the same statements came out with 14 spilled VGPRs instead of 8.
 // ---------------------------------------------------------------------------------------------------------------------------
-template <int RT, int KS>
+template <int RT, int KS, int KZ = KS>
 __device__ __forceinline__ void nia_body_native(nsmem<RT, (4 * KS + 2 > 16 * RT)>& sm, npos<RT>& p, int n, double* __restrict__ comp, nstrip<RT>& r_s,
                                          nstrip<RT>& t_s, int* status) {
   using G = ngeo<RT>;
@@ -229,12 +229,12 @@ __device__ __forceinline__ void nia_body_native(nsmem<RT, (4 * KS + 2 > 16 * RT)
   ndsym(t_s, t_s, dp);   // t-- = D t++ D in place (undone below: D is an involution)
   __syncthreads();                                                                                       // (a)
   if constexpr (!RID) {   // R+- j0- , T-- j0-
-    nmv_rows<RT, KS>(dP, vjm, 1.0, sm.mv[0], p);
-    nmv_rows<RT, KS>(dQ, vjm, 1.0, sm.mv[1], p);
+    nmv_rows<RT, KS, KZ>(dP, vjm, 1.0, sm.mv[0], p);
+    nmv_rows<RT, KS, KZ>(dQ, vjm, 1.0, sm.mv[1], p);
   }
   {
     nstrip<RT> E;
-    nmm2<RT, KS, true, true>(E, Z, dP, r_s, t_s, p);
+    nmm2<RT, KS, true, true, KZ>(E, Z, dP, r_s, t_s, p);
     if (own_wave) {
       double* zd = laneB ? vz : sm.vec[7];   // (the other lanes write to a dummy vector)
 #pragma unroll
@@ -253,12 +253,12 @@ __device__ __forceinline__ void nia_body_native(nsmem<RT, (4 * KS + 2 > 16 * RT)
         vs[tid] = sm.mv[1][tid];
       }
     }
-    ninvert<RT, KS>(ninv_order(nrm, status), E, Gs, n, cx, p);   // [E2] -> P, barrier (c), series
+    ninvert<RT, KS, false, KZ>(ninv_order(nrm, status), E, Gs, n, cx, p);   // [E2] -> P, barrier (c), series
   }
   nstrip<RT> V;
   {
     nstrip<RT> S;
-    nmm2<RT, KS, true, true>(S, V, dQ, r_s, t_s, p);   // (Q = [T--] has not been touched since (a))
+    nmm2<RT, KS, true, true, KZ>(S, V, dQ, r_s, t_s, p);   // (Q = [T--] has not been touched since (a))
     if (own_wave) {
       double* sd = laneB ? vs : sm.vec[7];
 #pragma unroll
@@ -276,8 +276,8 @@ __device__ __forceinline__ void nia_body_native(nsmem<RT, (4 * KS + 2 > 16 * RT)
   __syncthreads();                        // (e)
   {
     nstrip<RT> X, Y;
-    nmm<RT, KS, true>(X, dP, Gs, p);      // T21 = t++ G2
-    nmm<RT, KS, true>(Y, dQ, Gs, p);      // Y = S G2 = T01 r-+
+    nmm<RT, KS, true, KZ>(X, dP, Gs, p);      // T21 = t++ G2
+    nmm<RT, KS, true, KZ>(Y, dQ, Gs, p);      // Y = S G2 = T01 r-+
     __syncthreads();                      // (f): [t++], [S] no longer read
     nstore(dP, X, p);                     // [T21] -> P
     nstore(dQ, Y, p);                     // [Y]   -> Q
@@ -288,8 +288,8 @@ __device__ __forceinline__ void nia_body_native(nsmem<RT, (4 * KS + 2 > 16 * RT)
   if constexpr (PARK) nld_native(Z, R_pm, p); else nld_native(Rmp, R_mp, p);
   __syncthreads();                        // (g)
   if constexpr (!RID) {   // T21 z , Y z
-    nmv_rows<RT, KS>(dP, vz, 1.0, sm.mv[0], p);
-    nmv_rows<RT, KS>(dQ, vz, 1.0, sm.mv[1], p);
+    nmv_rows<RT, KS, KZ>(dP, vz, 1.0, sm.mv[0], p);
+    nmv_rows<RT, KS, KZ>(dQ, vz, 1.0, sm.mv[1], p);
   }
   if (own_wave) {  // z rides in the spare column c1 of T++:  (T21 T++)[:, c1] = T21 z, (Y T++)[:, c1] = Y z
 #pragma unroll
@@ -302,7 +302,7 @@ __device__ __forceinline__ void nia_body_native(nsmem<RT, (4 * KS + 2 > 16 * RT)
   }
   {
     nstrip<RT> acc;
-    nmm2<RT, KS, false, true>(r_s, acc, dP, Z, Tpp, p);   // R+- = r+- + T21 Z ; T++ = T21 T++
+    nmm2<RT, KS, false, true, KZ>(r_s, acc, dP, Z, Tpp, p);   // R+- = r+- + T21 Z ; T++ = T21 T++
     nst_native(R_pm, r_s, p);
     nst_native(T_pp, acc, p);
     if (laneA) {
@@ -325,7 +325,7 @@ __device__ __forceinline__ void nia_body_native(nsmem<RT, (4 * KS + 2 > 16 * RT)
         for (int r = 0; r < 4; ++r) Rmp.v[ta][r] = laneA ? 0.0 : Rmp.v[ta][r];
     }
   }
-  nmm2<RT, KS>(Rmp, V, dQ, Tpp, Z, p);       // R-+ = R-+ + Y T++ ; T-- = V + Y Z
+  nmm2<RT, KS, false, false, KZ>(Rmp, V, dQ, Tpp, Z, p);       // R-+ = R-+ + Y T++ ; T-- = V + Y Z
   nst_native(R_mp, Rmp, p);
   nst_native(T_mm, V, p);
   if (laneA) {
@@ -360,7 +360,7 @@ __device__ __forceinline__ void nia_body_native(nsmem<RT, (4 * KS + 2 > 16 * RT)
 // Products: 2 + the inverse + 1 + 2: four plus the series order (nine at order 7, four products of ninvert7), against the full
 // body's nine plus the order.  At most five live strips.  Blocks without spare columns take the source terms by mat-vecs.
 // ---------------------------------------------------------------------------------------------------------------------------
-template <int RT, int KS>
+template <int RT, int KS, int KZ = KS>
 __device__ __forceinline__ void nia_body_src(nsmem<RT, (4 * KS + 2 > 16 * RT)>& sm, npos<RT>& p, int n, double* __restrict__ comp,
                                              nstrip<RT>& r_s, nstrip<RT>& t_s, int* status) {
   using G = ngeo<RT>;
@@ -405,14 +405,14 @@ __device__ __forceinline__ void nia_body_src(nsmem<RT, (4 * KS + 2 > 16 * RT)>& 
       for (int r = 0; r < 4; ++r) B.v[ta][r] = cin ? B.v[ta][r] : (laneA ? vJp[p.row(ta, r)] : 0.0);
   }
   if constexpr (!RID) {   // r-+ J0+ , t++ J0+
-    nmv_rows<RT, KS>(dP, vJp, 1.0, sm.mv[0], p);
-    nmv_rows<RT, KS>(dQ, vJp, 1.0, sm.mv[1], p);
+    nmv_rows<RT, KS, KZ>(dP, vJp, 1.0, sm.mv[0], p);
+    nmv_rows<RT, KS, KZ>(dQ, vJp, 1.0, sm.mv[1], p);
   }
   nstrip<RT> E, Bs;
   double nrm;
   {
     nstrip<RT> Pm;
-    nmm2a<RT, KS, true, true>(E, dP, Pm, dQ, B, p);    // [E1 | r-+ J0+] ; [P | t++ J0+]
+    nmm2a<RT, KS, true, true, KZ>(E, dP, Pm, dQ, B, p);    // [E1 | r-+ J0+] ; [P | t++ J0+]
     // Bs <- [t-- | u], r_s <- [r+- | j0+ + t++ J0+] (the addend of the R+- update; r-+ is in P for the norm's barrier)
     ndsym(Bs, t_s, dp);
     ndsym(r_s, r_s, dp);
@@ -440,29 +440,29 @@ __device__ __forceinline__ void nia_body_src(nsmem<RT, (4 * KS + 2 > 16 * RT)>& 
   {
     nstrip<RT> Gs;
     const int K = ninv_order(nrm, status);                       // [E1] -> P, series
-    if (K == 7) ninvert7<RT, KS>(E, Gs, n, cx, p);               // (the usual order, in four products)
-    else ninvert<RT, KS>(K, E, Gs, n, cx, p);
+    if (K == 7) ninvert7<RT, KS, KZ>(E, Gs, n, cx, p);               // (the usual order, in four products)
+    else ninvert<RT, KS, false, KZ>(K, E, Gs, n, cx, p);
     __syncthreads();                                             // (c): [E1] no longer read
     nstore(dP, Gs, p);                                           // [G1] -> P (its rider columns are never a contraction index)
   }
   __syncthreads();                                               // (d)
-  if constexpr (!RID) nmv_rows<RT, KS>(dP, vu, 1.0, vg, p);      // g = G1 u
+  if constexpr (!RID) nmv_rows<RT, KS, KZ>(dP, vu, 1.0, vg, p);      // g = G1 u
   {
     nstrip<RT> Tm;
     nld_native(Tm, T_mm, p);                                     // (requested under the product)
     if constexpr (PARK) nld_native(r_s, R_pm, p);
-    nmm<RT, KS, true>(W, dP, Bs, p);                             // [W | g] = G1 [t-- | u]
+    nmm<RT, KS, true, KZ>(W, dP, Bs, p);                             // [W | g] = G1 [t-- | u]
     __syncthreads();                                             // (e): [G1] no longer read
     nstore(dP, Tm, p);                                           // [T--] -> P
   }
   __syncthreads();                                               // (f)
   if constexpr (!RID) {   // T-- g , P g
-    nmv_rows<RT, KS>(dP, vg, 1.0, sm.mv[0], p);
-    nmv_rows<RT, KS>(dQ, vg, 1.0, sm.mv[1], p);
+    nmv_rows<RT, KS, KZ>(dP, vg, 1.0, sm.mv[0], p);
+    nmv_rows<RT, KS, KZ>(dQ, vg, 1.0, sm.mv[1], p);
   }
   {
     nstrip<RT> Tn;
-    nmm2a<RT, KS, true, false>(Tn, dP, r_s, dQ, W, p);   // [T--' | T-- g] = T-- [W | g] ; [R+-' | J0+'] = r_s + P [W | g]
+    nmm2a<RT, KS, true, false, KZ>(Tn, dP, r_s, dQ, W, p);   // [T--' | T-- g] = T-- [W | g] ; [R+-' | J0+'] = r_s + P [W | g]
     nst_native(R_pm, r_s, p);
     nst_native(T_mm, Tn, p);
     if (laneA) {
@@ -962,7 +962,8 @@ static_assert(sizeof(nsmem<4, true>) * 2 <= 163840, "four row tiles: two workgro
 static_assert(sizeof(nsmem<6, true>) <= 163840 && sizeof(nsmem<6>) <= 163840, "six row tiles: one workgroup per CU");
 
 // SRC: a sources-only run (VSM_RUN_SOURCES_ONLY): R-+ and T++ of the composite are neither read nor written (nia_body_src)
-template <int RT, int KS, bool SRC>
+// TZ: the last TZ k-steps cover zero-weight streams only (VSM_RUN_ZW_TAIL): every product skips them (KZ = KS - TZ)
+template <int RT, int KS, bool SRC, int TZ>
 __global__ __launch_bounds__(ngeo<RT>::NT, ngeo<RT>::WPS) void k_layer_native(int n, int gsz, unsigned uvmask, int ndoubl,
                                                                                 int toa, const double* __restrict__ pre,
                                                                                 nlayer_comps a, int* status) {
@@ -975,7 +976,8 @@ __global__ __launch_bounds__(ngeo<RT>::NT, ngeo<RT>::WPS) void k_layer_native(in
   const double* img = pre + ((long long)isub * gridDim.x + s) * G::PRE_STRIDE;
   double* comp = a.c[isub] + (long long)s * G::COMP_STRIDE;
   nstrip<RT> r_s, t_s;
-  ned_body<RT, KS>(sm, p, n, gsz, uvmask, ndoubl, img, r_s, t_s, status);
+  constexpr int KZ = KS - TZ;
+  ned_body<RT, KS, KZ>(sm, p, n, gsz, uvmask, ndoubl, img, r_s, t_s, status);
   if (toa) {   // copy_added_to_composite! (rt_helpers.jl:188-200)
     const ndpar<RT> dp(sm.usg, p);
     if constexpr (!SRC) {
@@ -993,8 +995,8 @@ __global__ __launch_bounds__(ngeo<RT>::NT, ngeo<RT>::WPS) void k_layer_native(in
     }
     return;
   }
-  if constexpr (SRC) nia_body_src<RT, KS>(sm, p, n, comp, r_s, t_s, status);
-  else nia_body_native<RT, KS>(sm, p, n, comp, r_s, t_s, status);
+  if constexpr (SRC) nia_body_src<RT, KS, KZ>(sm, p, n, comp, r_s, t_s, status);
+  else nia_body_native<RT, KS, KZ>(sm, p, n, comp, r_s, t_s, status);
 }
 
 }  // namespace
@@ -1002,22 +1004,29 @@ __global__ __launch_bounds__(ngeo<RT>::NT, ngeo<RT>::WPS) void k_layer_native(in
 // one object per k-step count (parallel build): vsm_native_<KS>.o is this file built with -DVSM_NATIVE_KS=<KS>
 #define VSM_NCAT2(a, b) a##b
 #define VSM_NCAT(a, b) VSM_NCAT2(a, b)
+// zero-weight tails instantiated per object: TZ = 0 .. min(VSM_NATIVE_TZ_MAX, KS - 1) (the dispatcher takes the largest one that
+// does not exceed a block's tail -- any shorter tail is exact too)
+#define VSM_NATIVE_TZ_MAX 1
 #define VSM_NATIVE_DECL(KS) \
-  int VSM_NCAT(launch_layer_native_, KS)(int, int, int, unsigned, int, int, int, int, const double*, const nlayer_comps&, int*, \
-                                         hipStream_t);                                                                           \
+  int VSM_NCAT(launch_layer_native_, KS)(int, int, int, unsigned, int, int, int, int, int, const double*, const nlayer_comps&, \
+                                         int*, hipStream_t);                                                                     \
   int VSM_NCAT(launch_ia_native_, KS)(int, int, const composite<double>&, const added<double>&, int*, hipStream_t);
 
 #ifdef VSM_NATIVE_KS
 VSM_NATIVE_DECL(VSM_NATIVE_KS)
 int VSM_NCAT(launch_layer_native_, VSM_NATIVE_KS)(int S, int nsub, int n, unsigned uvmask, int gsz, int ndoubl, int toa, int src,
-                                                  const double* pre, const nlayer_comps& comps, int* status, hipStream_t st) {
+                                                  int tz, const double* pre, const nlayer_comps& comps, int* status,
+                                                  hipStream_t st) {
   constexpr int KS = VSM_NATIVE_KS;
   // KS = 4, 8, 12, 16 (n = 13..16, 29..32, 45..48, 61..64): KS / 4 row tiles without spare columns (mat-vec source path) instead of one row
   // tile more for the two rider columns
   constexpr int RT = (KS % 4 == 0 && KS >= 4) ? KS / 4 : (4 * KS + 2 + 15) / 16;
   static_assert(RT >= 1 && RT <= 6, "n <= 96");
   using SM = nsmem<RT, (4 * KS + 2 > 16 * RT)>;
-  auto kern = src ? k_layer_native<RT, KS, true> : k_layer_native<RT, KS, false>;
+  constexpr int TZ1 = KS - 1 < 1 ? 0 : 1, TZ2 = KS - 1 < VSM_NATIVE_TZ_MAX ? TZ1 : VSM_NATIVE_TZ_MAX;
+  tz = tz < TZ2 ? (tz < TZ1 ? 0 : TZ1) : TZ2;
+  auto kern = src ? (tz == TZ2 ? k_layer_native<RT, KS, true, TZ2> : tz == TZ1 ? k_layer_native<RT, KS, true, TZ1> : k_layer_native<RT, KS, true, 0>)
+                  : (tz == TZ2 ? k_layer_native<RT, KS, false, TZ2> : tz == TZ1 ? k_layer_native<RT, KS, false, TZ1> : k_layer_native<RT, KS, false, 0>);
   const int prepared = ensure_dyn_lds(reinterpret_cast<const void*>(kern), sizeof(SM), "hipFuncSetAttribute(k_layer_native)");
   if (prepared) return prepared;
   hipLaunchKernelGGL(kern, dim3(S, nsub), dim3(ngeo<RT>::NT), sizeof(SM), st, n, gsz, uvmask, ndoubl, toa, pre, comps, status);
@@ -1489,6 +1498,7 @@ static int plan_subs(bool f32, int N, int ns, int nm, const int* m, const int* c
         return VSM_ERR_UNSUPPORTED;
       }
       sb.ks = (sb.n + 3) / 4;
+      sb.kz = sb.ks;
       sb.rt = f32 ? native32_rt_of(sb.n) : rt_of(sb.n);
       sb.comp_off = total;
       total += (f32 ? native32_comp_stride(sb.rt) : comp_stride_rt(sb.rt)) * S;
@@ -1498,10 +1508,10 @@ static int plan_subs(bool f32, int N, int ns, int nm, const int* m, const int* c
   return VSM_OK;
 }
 
-static int launch_layer_native(int ks, int S, int nsub, int n, unsigned uvmask, int gsz, int ndoubl, int toa, int src,
+static int launch_layer_native(int ks, int tz, int S, int nsub, int n, unsigned uvmask, int gsz, int ndoubl, int toa, int src,
                                const double* pre, const nlayer_comps& comps, int* status, hipStream_t st) {
 #define VSM_NL(KS) \
-  case KS: return VSM_NCAT(launch_layer_native_, KS)(S, nsub, n, uvmask, gsz, ndoubl, toa, src, pre, comps, status, st);
+  case KS: return VSM_NCAT(launch_layer_native_, KS)(S, nsub, n, uvmask, gsz, ndoubl, toa, src, tz, pre, comps, status, st);
   switch (ks) {
     VSM_NL(1) VSM_NL(2) VSM_NL(3) VSM_NL(4) VSM_NL(5) VSM_NL(6) VSM_NL(7) VSM_NL(8) VSM_NL(9) VSM_NL(10) VSM_NL(11) VSM_NL(12)
     VSM_NL(13) VSM_NL(14) VSM_NL(15) VSM_NL(16) VSM_NL(17) VSM_NL(18) VSM_NL(19) VSM_NL(20) VSM_NL(21) VSM_NL(22) VSM_NL(23) VSM_NL(24)
@@ -1570,11 +1580,32 @@ static quad<ST> run_quad(const vsm_run* run) {
   return quad<ST>{static_cast<const ST*>(run->mu), static_cast<const ST*>(run->wt), run->N, run->ns, run->i_mu0, (ST)run->mu0};
 }
 
+// VSM_RUN_ZW_TAIL: the trailing run of quadrature nodes whose weight is exactly 0 (the VZA / SZA nodes rt_set_streams appends
+// behind the Gauss-Legendre nodes).  Rows are node-major in every block (row = node gsz + position), so they are its last rows:
+// kz = ceil(real rows / 4).  One synchronous read of the run's weights (on the legacy stream, behind the caller's pending work).
+template <typename ST>
+static int zw_tail(vsm_run* run) {
+  const int N = run->N, ns = run->ns, nq = N / ns;
+  std::vector<ST> w((size_t)N);
+  VSM_HIP(hipMemcpy(w.data(), run->wt, sizeof(ST) * (size_t)N, hipMemcpyDefault));
+  int z = 0;   // trailing zero-weight nodes
+  for (int node = nq - 1; node >= 0; --node) {
+    bool zero = true;
+    for (int a = 0; a < ns; ++a) zero = zero && w[(size_t)node * ns + a] == ST(0);
+    if (!zero) break;
+    ++z;
+  }
+  if (z == nq) z = 0;   // (no real stream at all: nothing to truncate against)
+  for (nat_sub& sb : run->subs) sb.kz = ((nq - z) * sb.gsz + 3) / 4;
+  run->flags |= VSM_RUN_ZW_TAIL;
+  return VSM_OK;
+}
+
 template <typename ST, typename Q>
 static int run_create(const Q* q, int S, int nm, const int* m, const int* coupling, void* workspace, size_t workspace_bytes,
                       unsigned flags, vsm_run** run_out) {
   VSM_REQUIRE(q && q->mu && q->wt && run_out && m, "vsm_run_create: null argument");
-  VSM_REQUIRE((flags & ~(unsigned)VSM_RUN_SOURCES_ONLY) == 0, "vsm_run_create_ex: unknown flags 0x%x", flags);
+  VSM_REQUIRE((flags & ~(unsigned)(VSM_RUN_SOURCES_ONLY | VSM_RUN_ZW_TAIL)) == 0, "vsm_run_create_ex: unknown flags 0x%x", flags);
   VSM_REQUIRE(S >= 0 && nm >= 1 && nm <= NSUB_MAX, "vsm_run_create: bad S = %d / nm = %d (at most %d moments per run)", S, nm,
               NSUB_MAX);
   vsm_run* run = new vsm_run;
@@ -1600,6 +1631,13 @@ static int run_create(const Q* q, int S, int nm, const int* m, const int* coupli
     set_error("vsm_run_create: workspace of %zu bytes (16-byte aligned) required, got %zu", total * sizeof(ST), workspace_bytes);
     delete run;
     return VSM_ERR_INVALID_ARG;
+  }
+  if (run->flags & VSM_RUN_ZW_TAIL) {
+    const int rc2 = zw_tail<ST>(run);
+    if (rc2) {
+      delete run;
+      return rc2;
+    }
   }
   run->ws = workspace;
   run->ws_elems = total;
@@ -1629,6 +1667,7 @@ static int run_layer(vsm_run* run, int ndoubl, const ST* dtau, const ST* varpi, 
   VSM_REQUIRE(run && dtau && varpi && tau_sum && F0 && Zpp && Zmp, "vsm_run_layer: null argument");
   VSM_REQUIRE(run->elem_size == (int)sizeof(ST), "vsm_run_layer: the run was created for %d-byte arrays", run->elem_size);
   VSM_REQUIRE(ndoubl >= 0 && ndoubl < 60 && ncomp >= 0 && ncomp <= 4 && (ncomp == 0 || fcomp), "vsm_run_layer: bad ndoubl / component mix");
+  ++run->layers;
   if (run->S == 0) return VSM_OK;
   hipStream_t st = as_stream(stream);
   int* status = device_status();
@@ -1729,7 +1768,7 @@ static int run_layer(vsm_run* run, int ndoubl, const ST* dtau, const ST* varpi, 
       default: launch_pre<6, ST>(ncomp > 0, q, run->S, nsub, h.n, ndoubl, dtau, varpi, tau_sum, F0, pa, pre_cl, st); break;
     }
     VSM_LAUNCH_CHECK("k_elemental_native");
-    const int rc = launch_layer_native(h.ks, run->S, nsub, h.n, h.uvmask, h.gsz, ndoubl, toa, src, pre_cl, lc, status, st);
+    const int rc = launch_layer_native(h.ks, h.ks - h.kz, run->S, nsub, h.n, h.uvmask, h.gsz, ndoubl, toa, src, pre_cl, lc, status, st);
     if (rc) return rc;
   }
   return VSM_OK;
@@ -1741,7 +1780,12 @@ static int run_convert(vsm_run* run, const CS* comps, void* stream) {
   VSM_REQUIRE(run && comps, "vsm_run_export / import: null argument");
   VSM_REQUIRE(run->elem_size == (int)sizeof(ST), "vsm_run_export / import: the run was created for %d-byte arrays", run->elem_size);
   if (run->S == 0) return VSM_OK;
-  if (IMPORT) run->pure_diag.assign(run->subs.size(), 0);
+  if (IMPORT) {
+    run->pure_diag.assign(run->subs.size(), 0);
+    // a caller's arrays need not have the zero-weight columns of DESIGN.md 4.0: the dense products from here on
+    run->flags &= ~(unsigned)VSM_RUN_ZW_TAIL;
+    for (nat_sub& sb : run->subs) sb.kz = sb.ks;
+  }
   for (int im = 0; im < run->nm; ++im) {
     const CS& c = comps[im];
     VSM_REQUIRE(c.R_mp && c.R_pm && c.T_pp && c.T_mm && c.J0_p && c.J0_m, "vsm_run_export / import: null composite array (moment %d)", im);
@@ -1821,6 +1865,12 @@ int vsm_run_create_ex_f64(const vsm_quad_f64* q, int S, int nm, const int* m, co
 int vsm_run_create_ex_f32(const vsm_quad_f32* q, int S, int nm, const int* m, const int* coupling, void* workspace,
                           size_t workspace_bytes, unsigned flags, vsm_run** run_out) {
   return run_create<float>(q, S, nm, m, coupling, workspace, workspace_bytes, flags, run_out);
+}
+
+int vsm_run_zw_tail(vsm_run* run) {
+  VSM_REQUIRE(run, "vsm_run_zw_tail: null argument");
+  VSM_REQUIRE(run->layers == 0, "vsm_run_zw_tail: the run has taken layer steps already");
+  return run->elem_size == 8 ? zw_tail<double>(run) : VSM_OK;   // (_f32 runs: dense products)
 }
 
 int vsm_run_destroy(vsm_run* run) {

@@ -108,15 +108,33 @@ __device__ __forceinline__ double ndpp_swap1(double x) {
 
 // ---- products: acc += [A] B, A-form at byte distance dA, B a strip in registers; pipelined by one k-step -------------------
 // (Z / Z1 / Z2: the accumulator starts from zero -- the first k-step takes the constant 0 as its addend: no register is cleared)
-template <int RT, int KS, bool Z = false>
+// KZ <= KS: the k-steps over real streams (run flag VSM_RUN_ZW_TAIL).  The k-steps ks in [KZ, KS) cover only zero-weight streams
+// (and padding): every left operand of the layer kernels has those columns zero off the diagonal, A[:, k] = A[k, k] e_k (DESIGN.md
+// 4.0), so such a k-step adds A[row, row] B[row, :] to its own row alone -- a lane-local FMA on the very register B.v[ks >> 2][ks & 3]
+// the k-step would have read (row = 4 ks + kq), with A[row, row] read from the A-form.  KZ = KS: the dense product.
+template <int RT>
+__device__ __forceinline__ double ndiag(unsigned dA, int ks, const npos<RT>& p) {
+  // A[row, row] of the lane's row 4 ks + kq: word kq << 4 of block ks RT + (ks >> 2) (naf_idx with m ^ (kk | (ks & 3) << 2) = 0)
+  unsigned b = p.fb[0] - 8u * (unsigned)(p.l15 ^ p.kq);   // fb[0] = base + 8 (16 kq + (l15 ^ kq))
+  asm volatile("" : "+v"(b));
+  b += dA;
+  return *(reinterpret_cast<const nlds_d*>((unsigned long long)b) + 64 * (ks * RT + (ks >> 2)));
+}
+template <int RT, int KS, int KZ>
+__device__ __forceinline__ void nzw_fix(nstrip<RT>& acc, unsigned dA, const nstrip<RT>& B, const npos<RT>& p) {
+  static_assert(KZ >= 1 && KZ <= KS, "zero-weight tail: 1 <= KZ <= KS");
+#pragma unroll
+  for (int ks = KZ; ks < KS; ++ks) acc.v[ks >> 2][ks & 3] = fma(ndiag<RT>(dA, ks, p), B.v[ks >> 2][ks & 3], acc.v[ks >> 2][ks & 3]);
+}
+template <int RT, int KS, bool Z = false, int KZ = KS>
 __device__ __forceinline__ void nmm(nstrip<RT>& acc, unsigned dA, const nstrip<RT>& B, npos<RT>& p) {
   p.opaque();
   double a[2][RT];
 #pragma unroll
   for (int t = 0; t < RT; ++t) a[0][t] = *p.aptr(dA, t, 0);
 #pragma unroll
-  for (int ks = 0; ks < KS; ++ks) {
-    if (ks + 1 < KS) {
+  for (int ks = 0; ks < KZ; ++ks) {
+    if (ks + 1 < KZ) {
 #pragma unroll
       for (int t = 0; t < RT; ++t) a[(ks + 1) & 1][t] = *p.aptr(dA, t, ks + 1);
     }
@@ -125,17 +143,18 @@ __device__ __forceinline__ void nmm(nstrip<RT>& acc, unsigned dA, const nstrip<R
     for (int t = 0; t < RT; ++t) acc.v[t] = mfma<double>::mma(a[ks & 1][t], b, (Z && ks == 0) ? acc_zero<double>() : acc.v[t]);
     VSM_NKSTEP_FENCE();
   }
+  nzw_fix<RT, KS, KZ>(acc, dA, B, p);
 }
 // out = C0 + [A] B
-template <int RT, int KS>
+template <int RT, int KS, int KZ = KS>
 __device__ __forceinline__ void nmm_c(nstrip<RT>& out, const nstrip<RT>& C0, unsigned dA, const nstrip<RT>& B, npos<RT>& p) {
   p.opaque();
   double a[2][RT];
 #pragma unroll
   for (int t = 0; t < RT; ++t) a[0][t] = *p.aptr(dA, t, 0);
 #pragma unroll
-  for (int ks = 0; ks < KS; ++ks) {
-    if (ks + 1 < KS) {
+  for (int ks = 0; ks < KZ; ++ks) {
+    if (ks + 1 < KZ) {
 #pragma unroll
       for (int t = 0; t < RT; ++t) a[(ks + 1) & 1][t] = *p.aptr(dA, t, ks + 1);
     }
@@ -144,9 +163,10 @@ __device__ __forceinline__ void nmm_c(nstrip<RT>& out, const nstrip<RT>& C0, uns
     for (int t = 0; t < RT; ++t) out.v[t] = mfma<double>::mma(a[ks & 1][t], b, ks == 0 ? C0.v[t] : out.v[t]);
     VSM_NKSTEP_FENCE();
   }
+  nzw_fix<RT, KS, KZ>(out, dA, B, p);
 }
 // acc1 += [A] B1 ; acc2 += [A] B2  (shared fragments)
-template <int RT, int KS, bool Z1 = false, bool Z2 = false>
+template <int RT, int KS, bool Z1 = false, bool Z2 = false, int KZ = KS>
 __device__ __forceinline__ void nmm2(nstrip<RT>& acc1, nstrip<RT>& acc2, unsigned dA, const nstrip<RT>& B1,
                                      const nstrip<RT>& B2, npos<RT>& p) {
   p.opaque();
@@ -154,8 +174,8 @@ __device__ __forceinline__ void nmm2(nstrip<RT>& acc1, nstrip<RT>& acc2, unsigne
 #pragma unroll
   for (int t = 0; t < RT; ++t) a[0][t] = *p.aptr(dA, t, 0);
 #pragma unroll
-  for (int ks = 0; ks < KS; ++ks) {
-    if (ks + 1 < KS) {
+  for (int ks = 0; ks < KZ; ++ks) {
+    if (ks + 1 < KZ) {
 #pragma unroll
       for (int t = 0; t < RT; ++t) a[(ks + 1) & 1][t] = *p.aptr(dA, t, ks + 1);
     }
@@ -167,9 +187,15 @@ __device__ __forceinline__ void nmm2(nstrip<RT>& acc1, nstrip<RT>& acc2, unsigne
     }
     VSM_NKSTEP_FENCE();
   }
+#pragma unroll
+  for (int ks = KZ; ks < KS; ++ks) {
+    const double d = ndiag<RT>(dA, ks, p);
+    acc1.v[ks >> 2][ks & 3] = fma(d, B1.v[ks >> 2][ks & 3], acc1.v[ks >> 2][ks & 3]);
+    acc2.v[ks >> 2][ks & 3] = fma(d, B2.v[ks >> 2][ks & 3], acc2.v[ks >> 2][ks & 3]);
+  }
 }
 // acc1 += [A1] B ; acc2 += [A2] B  (two left operands, one right operand: 2 RT independent accumulators per k-step)
-template <int RT, int KS, bool Z1 = false, bool Z2 = false>
+template <int RT, int KS, bool Z1 = false, bool Z2 = false, int KZ = KS>
 __device__ __forceinline__ void nmm2a(nstrip<RT>& acc1, unsigned dA1, nstrip<RT>& acc2, unsigned dA2, const nstrip<RT>& B,
                                       npos<RT>& p) {
   p.opaque();
@@ -180,8 +206,8 @@ __device__ __forceinline__ void nmm2a(nstrip<RT>& acc1, unsigned dA1, nstrip<RT>
     a2[0][t] = *p.aptr(dA2, t, 0);
   }
 #pragma unroll
-  for (int ks = 0; ks < KS; ++ks) {
-    if (ks + 1 < KS) {
+  for (int ks = 0; ks < KZ; ++ks) {
+    if (ks + 1 < KZ) {
 #pragma unroll
       for (int t = 0; t < RT; ++t) {
         a1[(ks + 1) & 1][t] = *p.aptr(dA1, t, ks + 1);
@@ -196,6 +222,8 @@ __device__ __forceinline__ void nmm2a(nstrip<RT>& acc1, unsigned dA1, nstrip<RT>
     }
     VSM_NKSTEP_FENCE();
   }
+  nzw_fix<RT, KS, KZ>(acc1, dA1, B, p);
+  nzw_fix<RT, KS, KZ>(acc2, dA2, B, p);
 }
 
 // ---- strip <-> A-form ---------------------------------------------------------------------------------------------------------
@@ -507,7 +535,9 @@ __device__ __forceinline__ void ninvert_slow_body(int K, nstrip<RT>& E, nstrip<R
 // result, so whatever rides there stays in columns that are never a contraction index.  On the slow path the riders of G are
 // lost -- RIDERS tells whether the caller needs them (then it restores them itself: see the callers).
 // On return other waves may still be reading W.
-template <int RT, int KS, bool REGS = false>
+// KZ: the products of the Horner series skip the zero-weight tail (E = [E] is in the class of DESIGN.md 4.0); the out-of-line
+// orders keep the dense products.
+template <int RT, int KS, bool REGS = false, int KZ = KS>
 __device__ __forceinline__ void ninvert(int K, nstrip<RT>& E, nstrip<RT>& G, int n, const ninv_ctx& cx, npos<RT>& p) {
   if (K < 1 || K > 8) {
     nstrip<RT> Es = E, Gs;
@@ -521,11 +551,11 @@ __device__ __forceinline__ void ninvert(int K, nstrip<RT>& E, nstrip<RT>& G, int
   } else {
     nstore(cx.dW, E, p);
     __syncthreads();
-    nmm_c<RT, KS>(G, E, cx.dW, E, p);     // X1 = E + E E
+    nmm_c<RT, KS, KZ>(G, E, cx.dW, E, p);     // X1 = E + E E
     for (int j = 2; j < K; ++j) {          // X_j = E + E X_{j-1}
       nstrip<RT> X;
       nload(X, cx.dW, p);
-      nmm<RT, KS>(X, cx.dW, G, p);
+      nmm<RT, KS, false, KZ>(X, cx.dW, G, p);
       G = X;
     }
   }
@@ -534,23 +564,23 @@ __device__ __forceinline__ void ninvert(int K, nstrip<RT>& E, nstrip<RT>& G, int
 // Order 7 without riders in G, in four products instead of Horner's six:  (I + E)(I + E^2)(I + E^4)  with
 //   W2 = E E,  T = E W2,  W4 = E T  (A = [E]),  S = E + W2 + T,  G = I + S + W4 + W4 S  (A = [W4]: one more A-form store).
 // The interaction's inverse: its G is only ever a B operand whose rider columns nobody reads.  Three live strips.
-template <int RT, int KS>
+template <int RT, int KS, int KZ = KS>
 __device__ __forceinline__ void ninvert7(nstrip<RT>& E, nstrip<RT>& G, int n, const ninv_ctx& cx, npos<RT>& p) {
   nstore(cx.dW, E, p);
   __syncthreads();
   nstrip<RT> X, Y;
-  nmm_c<RT, KS>(X, E, cx.dW, E, p);          // X = E + E^2
+  nmm_c<RT, KS, KZ>(X, E, cx.dW, E, p);      // X = E + E^2
   nload(Y, cx.dW, p);
-  nmm<RT, KS>(Y, cx.dW, X, p);               // Y = E + E X = S
+  nmm<RT, KS, false, KZ>(Y, cx.dW, X, p);    // Y = E + E X = S
 #pragma unroll
   for (int ta = 0; ta < RT; ++ta) X.v[ta] = Y.v[ta] - X.v[ta];   // E^3
-  nmm<RT, KS, true>(G, cx.dW, X, p);         // W4 = E E^3
+  nmm<RT, KS, true, KZ>(G, cx.dW, X, p);     // W4 = E E^3
   __syncthreads();                           // [E] no longer read
   nstore(cx.dW, G, p);
 #pragma unroll
   for (int ta = 0; ta < RT; ++ta) G.v[ta] += Y.v[ta];
   __syncthreads();
-  nmm<RT, KS>(G, cx.dW, Y, p);               // S + W4 + W4 S
+  nmm<RT, KS, false, KZ>(G, cx.dW, Y, p);    // S + W4 + W4 S
   nadd_identity(G, n, p);
 }
 __device__ __forceinline__ int ninv_order(double nrm, int* status) {
@@ -582,7 +612,9 @@ struct nsmem : nmv_slots<RT, MV> {
 // through the fragment pattern of the products (lane (m, kq): row 16 w + m, k = 4 ks + kq -- conflict-free, four per-lane bases +
 // instruction offsets: nothing for LICM to hoist into registers, which is what the column-wise form of round 5 paid its 160
 // spilled registers for), reduces over the four lane groups and writes its sixteen finished rows: no partial sums.
-template <int RT, int KS>
+// KZ < KS: the zero-weight tail as in the products -- rows 4 KZ .. 4 KS - 1 add A[row, row] x[row] to the partial sum of their
+// own lane group (the dense loop's order: the same bits).
+template <int RT, int KS, int KZ = KS>
 __device__ __forceinline__ void nmv_rows(unsigned dA, const double* x, double sc, double* out, npos<RT>& p) {
   unsigned ab[4];
 #pragma unroll
@@ -594,10 +626,19 @@ __device__ __forceinline__ void nmv_rows(unsigned dA, const double* x, double sc
   asm volatile("" : "+v"(xb));
   double acc = 0.0;
 #pragma unroll
-  for (int ks = 0; ks < KS; ++ks) {
+  for (int ks = 0; ks < KZ; ++ks) {
     const double a = *(reinterpret_cast<const nlds_d*>((unsigned long long)ab[ks & 3]) + 64 * ks * RT);
     const double xv = *(reinterpret_cast<const nlds_d*>((unsigned long long)xb) + 4 * ks);
     acc = fma(a, xv, acc);
+  }
+  if constexpr (KZ < KS) {   // (row 16 w + l15: its diagonal term in the lane group kq = row & 3, where the dense loop adds it)
+    const int row = 16 * p.wave + p.l15;
+    if (row >= 4 * KZ && row < 4 * KS && p.kq == (row & 3)) {
+      const nlds_d* Ad = reinterpret_cast<const nlds_d*>((unsigned long long)(p.fb[0] - 8u * (unsigned)(p.l15 ^ p.kq) - 128u * (unsigned)p.kq + dA));
+      const double d = Ad[naf_idx<RT>(row, row)];
+      const double xv = *(reinterpret_cast<const nlds_d*>((unsigned long long)nlds_addr(x)) + row);
+      acc = fma(d, xv, acc);
+    }
   }
   acc += __shfl_xor(acc, 16);
   acc += __shfl_xor(acc, 32);

@@ -16,6 +16,7 @@ struct nat_sub {
   int gsz, g[4];   // the Stokes components of the block
   unsigned uvmask;
   int n, rt, ks;
+  int kz;          // k-steps over real streams (VSM_RUN_ZW_TAIL; else ks): ks - kz trailing k-steps cover zero-weight streams only
   size_t comp_off;   // elements (of the run's record type) from the workspace base
 };
 
@@ -27,12 +28,13 @@ struct vsm_run {
   double mu0;
   int elem_size;           // 8: FP64 model (FP64 records and arithmetic), 4: Float32 model (FP32 records and arithmetic)
   int S, nm;
-  unsigned flags;          // vsm_run_create_ex: VSM_RUN_SOURCES_ONLY (FP64 runs)
+  unsigned flags;          // vsm_run_create_ex: VSM_RUN_SOURCES_ONLY, VSM_RUN_ZW_TAIL (FP64 runs; the latter dropped by vsm_run_import)
   std::vector<int> m;
   std::vector<vsm::nat_sub> subs;
   std::vector<std::vector<int>> classes;   // indices into subs with equal (n, gsz, uvmask)
   void* ws;
   size_t ws_elems;
+  int layers = 0;                // vsm_run_layer calls so far
   std::vector<char> pure_diag;   // per sub-problem: its composite is still (R = 0, T = diag, J = 0): only diagonal steps so far
 };
 
