@@ -11,11 +11,13 @@ N GPUs => N x 10 000 points (weak scaling; `--total-points` = strong scaling).  
 in total over the GPUs), `--config C5`: configs[4] (rotational Raman, 2 10^4 points in total, halo-extended blocks per rank).  `--gpus N` without a launcher
 starts its own N ranks (torch.distributed.run, one process per GPU over RCCL) or fails if N GPUs are not visible.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), including `roofline` for the dominant
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times the steps, writes
+`--dump-outputs` and prints the headline.  `--full` adds what takes runs or processes of its own: `roofline` for the dominant
 kernel (the native-layout layer step k_layer_native<4, 15> with its elemental pre-pass k_elemental_native<4, ...>; algorithmic flops /
-HIP-event time of the pair) and `cpu_baseline` (the oracle port timed on a bounded sample of the same workload, with `anchor`: the
-same port on the reference's published CPU shape).  `config.secondary` holds the other configurations and the two DROP-IN entries:
-the same C2 step issued in the call order of the reference's unpatched driver (rt_run.jl:383-453).
+HIP-event time of the pair), the phase split and device-only time of one extra pass, `cpu_baseline` (the oracle port timed on a bounded
+sample of the same workload, with `anchor`: the same port on the reference's published CPU shape) and `config.secondary`: the other
+configurations and the two DROP-IN entries, the same C2 step issued in the call order of the reference's unpatched driver
+(rt_run.jl:383-453).
 """
 import argparse
 import json
@@ -182,10 +184,15 @@ def main():
     ap.add_argument("--variant", default="rayleigh", choices=["rayleigh", "aerosol"],
                     help="aerosol: SURVEY 8(d) variant -- HG aerosol (g=0.7, ssa=0.95, tau=0.2) in the lowest 6 layers, "
                          "2*nstreams-1 moments: Z differs per point and all 2*nstreams Fourier moments run")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: phase split, device-only pass and roofline of the dominant kernel (runs of their own), "
+                         "config.secondary and the CPU baseline (a plain run prints the headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip config.secondary (one timed step each of C4, the linearized C2 shape, the linearized C3 scene, C5 at 4000 points)")
-    ap.add_argument("--cpu-sample", type=int, default=96, help="upper bound of spectral points PER HOST CORE of the CPU-baseline sample (sized for ~15 s)")
+                    help="with --full: skip config.secondary (one timed step each of C4, the linearized C2 shape, the linearized C3 "
+                         "scene, C5 at 4000 points)")
+    ap.add_argument("--cpu-sample", type=int, default=96,
+                    help="with --full: upper bound of spectral points PER HOST CORE of the CPU-baseline sample (sized for ~15 s)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the R / T (C5: also ieR / ieT) of the last timed step as DIR/<name>.npy "
                          "(rank 0; a fixed sample of spectral points beyond 64 MB)")
@@ -289,8 +296,57 @@ def main():
             mg["note"] = "per-rank diagnostics unavailable: %s" % ex
         dt = float(tmax.item())
         timed_region_s = dt
-    step(split=True)   # phase attribution, outside the timed region
+    peak = PEAK_TFLOPS[cfg["FT"]]
+    if args.full:
+        step(split=True)   # phase attribution, outside the timed region
+        run_ms, roofline = dominant_kernel_roofline(vsm, torch, scene, cfg, N, S_local, args.variant)
 
+    if rank == 0:
+        flops_pt = scene.flops_per_point()
+        pts_per_s = S_total * args.steps / dt
+        nds = [ly["nd"] for ly in scene.moments[0]["layers"]]
+        line = {
+            "metric": "spectral-points/s (whole node) for rt_run, O2-A band",
+            "value": pts_per_s, "unit": "spectral-points/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True,
+            "scaling": scaling, "vs_baseline": None, "dtype": cfg["FT"], "data": "synthetic",
+            "config": {"workload": "%s: O2-A 759-770 nm, nStokes=3, Nquad=%d (N=%d), %d layers, %d spectral points/GPU, "
+                                   "m=0..%d, Rayleigh%s+synthetic O2 absorption, Lambertian 0.15" %
+                                   (args.config, model.quad_points.Nquad, N, L, S_local, m_max,
+                                    "+HG aerosol (lowest 6 layers)" if args.variant == "aerosol" else ""),
+                       "timed_step": "full rt_run-equivalent: H2D of tau_rayl/tau_abs + device layer optics + all moments/layers/"
+                                     "surface/post-processing + gather + D2H of R,T",
+                       "ranks": world, "collective_backend": "nccl (RCCL)" if world > 1 else "none (1 rank)",
+                       "multi_gpu": mg, "timed_region_s": timed_region_s,
+                       "N": N, "layers": L, "points_per_gpu": S_local, "fourier_moments": m_max + 1,
+                       "ndoubl_per_layer": nds, "algorithmic_gflop_per_point": flops_pt / 1e9,
+                       "whole_run_tflops": pts_per_s * flops_pt / 1e12,
+                       "whole_run_frac_of_mfma_peak": pts_per_s * flops_pt / 1e12 / (peak * world)},
+        }
+        if args.full:
+            line["config"].update({"phase_ms (one extra untimed pass with syncs)": {k: 1e3 * v for k, v in phase.items()},
+                                   "device_pass_ms (run() only, HIP events)": run_ms,
+                                   "device_pass_points_per_s_per_gpu": S_local / (run_ms * 1e-3)})
+            line["roofline"] = roofline
+            if world == 1 and args.config == "C2" and args.variant == "rayleigh" and not args.no_secondary and not args.points:
+                import bench_secondary
+                del scene
+                torch.cuda.empty_cache()
+                t_sec = time.perf_counter()
+                line["config"]["secondary"] = bench_secondary.run_all(vsm, torch, arch, o2a_atmosphere)
+                line["config"]["secondary_wall_s"] = time.perf_counter() - t_sec
+            torch.cuda.synchronize()   # (marker: everything on the GPU is done before the CPU baseline starts)
+            if not args.no_cpu_baseline and world == 1:
+                line["cpu_baseline"] = cpu_baseline(cfg, args.cpu_sample, L)
+        print(json.dumps(line))
+    if world > 1:
+        torch.distributed.barrier()
+        torch.distributed.destroy_process_group()
+
+
+def dominant_kernel_roofline(vsm, torch, scene, cfg, N, S_local, variant):
+    """`--full`: the device-only time of one more run() and the roofline of the dominant kernel, from passes of their own
+    (HIP event pairs around every layer-step call).  Returns (run() ms, the line's `roofline`)."""
     # ---- roofline of the dominant kernel: timed live with events on the launch stream ----------
     # one extra pass with an event pair around every layer-step call; the same pass gives the device-only time of run()
     ev = []
@@ -380,55 +436,15 @@ def main():
     tk = ([kernel_name, "k_elemental_%s<%d," % ("native32" if cfg["FT"] == "f32" else "native", native_rt(N))] if native and dense
           else [kernel_name, "k_elemental_img"])
     traffic, traffic_src, traffic_hash, traffic_note = (hbm_traffic_per_launch(tk, cfg, S_local, build["source_hash"])
-                                                        if args.variant == "rayleigh" else (None, None, None, "no profile of this variant"))
-
-    if rank == 0:
-        flops_pt = scene.flops_per_point()
-        pts_per_s = S_total * args.steps / dt
-        nds = [ly["nd"] for ly in scene.moments[0]["layers"]]
-        line = {
-            "metric": "spectral-points/s (whole node) for rt_run, O2-A band",
-            "value": pts_per_s, "unit": "spectral-points/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True,
-            "scaling": scaling, "vs_baseline": None, "dtype": cfg["FT"], "data": "synthetic",
-            "config": {"workload": "%s: O2-A 759-770 nm, nStokes=3, Nquad=%d (N=%d), %d layers, %d spectral points/GPU, "
-                                   "m=0..%d, Rayleigh%s+synthetic O2 absorption, Lambertian 0.15" %
-                                   (args.config, model.quad_points.Nquad, N, L, S_local, m_max,
-                                    "+HG aerosol (lowest 6 layers)" if args.variant == "aerosol" else ""),
-                       "timed_step": "full rt_run-equivalent: H2D of tau_rayl/tau_abs + device layer optics + all moments/layers/"
-                                     "surface/post-processing + gather + D2H of R,T",
-                       "ranks": world, "collective_backend": "nccl (RCCL)" if world > 1 else "none (1 rank)",
-                       "multi_gpu": mg, "timed_region_s": timed_region_s,
-                       "N": N, "layers": L, "points_per_gpu": S_local, "fourier_moments": m_max + 1,
-                       "ndoubl_per_layer": nds, "algorithmic_gflop_per_point": flops_pt / 1e9,
-                       "whole_run_tflops": pts_per_s * flops_pt / 1e12,
-                       "whole_run_frac_of_mfma_peak": pts_per_s * flops_pt / 1e12 / (peak * world),
-                       "phase_ms (one extra untimed pass with syncs)": {k: 1e3 * v for k, v in phase.items()},
-                       "device_pass_ms (run() only, HIP events)": run_ms,
-                       "device_pass_points_per_s_per_gpu": S_local / (run_ms * 1e-3)},
-            "roofline": {"bound": "mfma", "kernel": kernel_name, "achieved": achieved, "peak": peak,
-                         "unit": "TFLOP/s", "frac": achieved / peak, "traffic": traffic,
-                         "traffic_unit": "bytes/launch", "traffic_source": traffic_src,
-                         "traffic_profile_head": traffic_hash, "traffic_note": traffic_note, "library": build,
-                         "launches": n_launch, "avg_launch_ms": k_ms / max(n_launch, 1),
-                         "kernels_in_timed_interval": interval_kernels,
-                         "fourier_moments_per_launch": moments_per_launch,
-                         "layer_step_all_moments": layer_step},
-        }
-        if world == 1 and args.config == "C2" and args.variant == "rayleigh" and not args.no_secondary and not args.points:
-            import bench_secondary
-            del scene
-            torch.cuda.empty_cache()
-            t_sec = time.perf_counter()
-            line["config"]["secondary"] = bench_secondary.run_all(vsm, torch, arch, o2a_atmosphere)
-            line["config"]["secondary_wall_s"] = time.perf_counter() - t_sec
-        torch.cuda.synchronize()   # (marker: everything on the GPU is done before the CPU baseline starts)
-        if not args.no_cpu_baseline and world == 1:
-            line["cpu_baseline"] = cpu_baseline(cfg, args.cpu_sample, L)
-        print(json.dumps(line))
-    if world > 1:
-        torch.distributed.barrier()
-        torch.distributed.destroy_process_group()
+                                                        if variant == "rayleigh" else (None, None, None, "no profile of this variant"))
+    return run_ms, {"bound": "mfma", "kernel": kernel_name, "achieved": achieved, "peak": peak,
+                    "unit": "TFLOP/s", "frac": achieved / peak, "traffic": traffic,
+                    "traffic_unit": "bytes/launch", "traffic_source": traffic_src,
+                    "traffic_profile_head": traffic_hash, "traffic_note": traffic_note, "library": build,
+                    "launches": n_launch, "avg_launch_ms": k_ms / max(n_launch, 1),
+                    "kernels_in_timed_interval": interval_kernels,
+                    "fourier_moments_per_launch": moments_per_launch,
+                    "layer_step_all_moments": layer_step}
 
 
 def bench_c5(args, vsm, parallel, torch, rank, world, local):

@@ -26,7 +26,7 @@ do not couple: DESIGN 4.0), so an as-written fraction can exceed what the MFMA p
 executed work differs say so (`frac_of_mfma_peak_executed_products`, `note`).  A step is what the
 headline times: H2D of the raw inputs (`upload()`), device layer optics (`prepare()`), the device pass (`run()`) and the D2H of the
 result, on a scene whose buffers are allocated beforehand, with one untimed warm-up; the C5 and C1 steps are whole `rt_run(...)`
-calls (host optics, allocation, H2D, device pass, D2H).  Only bench.py imports this module, on rank 0 of a 1-GPU run.
+calls (host optics, allocation, H2D, device pass, D2H).  Only bench.py imports this module, on rank 0 of a 1-GPU `--full` run.
 """
 import json
 import os

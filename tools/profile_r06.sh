@@ -20,12 +20,12 @@ prof() {   # tag sources [profile_any options ...] -- command
 }
 for w in "$@"; do
   case $w in
-    c2)     prof c2 "$FWD" --dtype f64 -- python bench.py --points 4096 --steps 1 --warmup 0 --no-cpu-baseline --no-secondary ;;
-    c2pmc10k) prof c2_10k "$FWD" --dtype f64 -- python bench.py --points 10000 --steps 1 --warmup 0 --no-cpu-baseline --no-secondary ;;
-    c2full) prof c2_default "$FWD" --skip-pmc -- python bench.py --no-cpu-baseline --no-secondary ;;
-    c2aer)  prof c2_aer "$FWD" --dtype f64 -- python bench.py --variant aerosol --points 4096 --steps 1 --warmup 0 --no-cpu-baseline --no-secondary ;;
-    c4)     prof c4 "$F32" --dtype f32 -- python bench.py --config C4 --points 4096 --steps 1 --warmup 0 --no-cpu-baseline ;;
-    c4full) prof c4_default "$F32" --skip-pmc -- python bench.py --config C4 --no-cpu-baseline ;;
+    c2)     prof c2 "$FWD" --dtype f64 -- python bench.py --full --points 4096 --steps 1 --warmup 0 --no-cpu-baseline --no-secondary ;;
+    c2pmc10k) prof c2_10k "$FWD" --dtype f64 -- python bench.py --full --points 10000 --steps 1 --warmup 0 --no-cpu-baseline --no-secondary ;;
+    c2full) prof c2_default "$FWD" --skip-pmc -- python bench.py --full --no-cpu-baseline --no-secondary ;;
+    c2aer)  prof c2_aer "$FWD" --dtype f64 -- python bench.py --full --variant aerosol --points 4096 --steps 1 --warmup 0 --no-cpu-baseline --no-secondary ;;
+    c4)     prof c4 "$F32" --dtype f32 -- python bench.py --full --config C4 --points 4096 --steps 1 --warmup 0 --no-cpu-baseline ;;
+    c4full) prof c4_default "$F32" --skip-pmc -- python bench.py --full --config C4 --no-cpu-baseline ;;
     lin)    prof lin "$LIN" --dtype f64 -- python tools/lin_timing.py --points 2048 ;;
     lin112) prof lin112 "$LIN" --dtype f64 -- python tools/shape_cliff_timing.py --cases IQUV:51 ;;
     lin64)  prof lin64 "$LIN" --dtype f64 -- python tools/shape_cliff_timing.py --cases IQUV:27 ;;
