@@ -787,6 +787,29 @@ int vsm_level_radiance_oplevel_f32(int N, int n_stokes, int S, int nV, const int
                                    const float* bot_J0_m, float* uw, float* dw, float* dw_full, float* uw_full, float* work,
                                    void* stream);
 
+/* The inelastic (rotational-Raman) level equation of rt_run_test_ms(::RRS) (interlayer_flux_helper!(::RRS), CoreKernel/
+ * interlayer_flux.jl:21-77, applied by postprocessing_vza_ms!(::RRS), tools/postprocessing_vza_ms.jl:55-118) at ONE boundary, the
+ * lines summed: for recipient point n1 and line k with donor n0 = n1 + shift[k] (in-band pairs only, 0 <= n0 < S),
+ *   q = sum_k [c_ie,k + B_ie,k dw(n0)],   r = sum_k [a_ie,k + A_ie,k uw(n0)] + A(n1) q,
+ *   dw_ie = (I - A(n1) B(n1))^-1 r,       uw_ie = q + B(n1) dw_ie
+ * which is the line sum of the reference's per-line two-inverse formula (push-through identity).  A = top_R_pm [N,N,S], B = bot_R_mp
+ * with bot_stride (N*N, or 0: one block shared by every point), dw / uw = dw_full / uw_full [N,1,S] of the ELASTIC level call
+ * (vsm_level_radiance_*) at the same level; A_ie = top_ieR_pm [N,N,S,K], a_ie = top_ieJ0_p [N,1,S,K] (the RS layout above);
+ * B_ie = bot_ieR_mp, c_ie = bot_ieJ0_m in the same layout, both NULL for a bottom without an inelastic part (the surface layer
+ * alone: q = 0).  shift [K] (device).  Outputs as in vsm_level_radiance_*: uwie / dwie [nV,n_stokes,S] ACCUMULATED with row0_h /
+ * w_h, dwie_full / uwie_full (nullable) [N,1,S] the summed inelastic level vectors at all streams.  N <= 128: one workgroup per
+ * recipient point streams its 2K inelastic blocks, then solves [I - A B | r] by the elastic kernel's elimination (same pivot rule,
+ * VSM_DEVSTAT_SINGULAR / _NONFINITE).  No work buffer. */
+int vsm_level_radiance_ie_f64(int N, int n_stokes, int S, int K, const int* shift, int nV, const int* row0_h, const double* w_h,
+                              const double* top_R_pm, const double* bot_R_mp, long long bot_stride, const double* dw_full,
+                              const double* uw_full, const double* top_ieR_pm, const double* top_ieJ0_p, const double* bot_ieR_mp,
+                              const double* bot_ieJ0_m, double* uwie, double* dwie, double* dwie_full, double* uwie_full,
+                              void* stream);
+int vsm_level_radiance_ie_f32(int N, int n_stokes, int S, int K, const int* shift, int nV, const int* row0_h, const float* w_h,
+                              const float* top_R_pm, const float* bot_R_mp, long long bot_stride, const float* dw_full,
+                              const float* uw_full, const float* top_ieR_pm, const float* top_ieJ0_p, const float* bot_ieR_mp,
+                              const float* bot_ieJ0_m, float* uwie, float* dwie, float* dwie_full, float* uwie_full, void* stream);
+
 /* ---- diagnostics used by the parity tests -------------------------------- */
 /* Runs the LDS-resident MFMA tile product used inside the fused kernels on plain
  * [N,N,S] inputs: C = A*B.  (Checks fragment layouts / swizzle independently.) */

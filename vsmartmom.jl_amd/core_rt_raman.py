@@ -298,10 +298,15 @@ class SceneRRS:
         return tuple(to_host(t[self.crop]).transpose(2, 1, 0).copy() for t in self.out)
 
 
-def raman_bytes_per_point(N: int, K: int, itemsize: int) -> int:
+def raman_bytes_per_point(N: int, K: int, itemsize: int, n_tops: int = 0, segments: bool = False) -> int:
     """Device bytes one spectral point of a SceneRRS holds: the 12 + 10 four-dimensional inelastic arrays of the added / surface /
-    composite layers and of the kernels' work space (N x N x K each), the elastic layers and their work space."""
-    return int(itemsize * (22 * K * N * N + 8 * K * N + 40 * N * N))
+    composite layers and of the kernels' work space (N x N x K each), the elastic layers and their work space.
+    Multi-sensor runs (core_rt_ms_raman) add the kept tops, (1 + K)(N^2 + N) each (R+-, J0+, ieR+-, ieJ0+), and with `segments`
+    the two segment composites (elastic and RS: 4 (1 + K) N^2 + 2 (1 + K) N) and the level vectors at all streams (4 N)."""
+    extra = n_tops * (1 + K) * (N * N + N)
+    if segments:
+        extra += 2 * (4 * (1 + K) * N * N + 2 * (1 + K) * N) + 4 * N
+    return int(itemsize * (22 * K * N * N + 8 * K * N + 40 * N * N + extra))
 
 
 def rt_run(RS_type: RRS, model: H.RTModel, iBand: int = 1, trace: Optional[list] = None, spec_slice: Optional[slice] = None,

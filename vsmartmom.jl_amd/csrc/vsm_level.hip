@@ -11,6 +11,9 @@
 //   3. uw = c + B dw (mat-vec), then the VZA rows of uw / dw added into the caller's [nV, n_stokes, S] outputs.
 // One spectral point per 256-thread workgroup, N <= 128 (FP64 [M | d]: 129 KiB of LDS at N = 128).  Larger N: the operator-level
 // twin (batched products + vsm_batch_inv + products + vsm_postprocess_vza), the same contract.
+//
+// vsm_level_radiance_ie_*: the first-order (Raman) part of the same equation, interlayer_flux_helper!(::RRS) (interlayer_flux.jl:
+// 21-77), per recipient point with the lines summed before ONE solve of the same [I - A B | r] (k_level_radiance_ie, below).
 #include "vsm_common.h"
 #include "vsm_internal.h"
 #include "vsm_inverse.h"
@@ -25,24 +28,20 @@ struct level_pp {
   double w[256];
 };
 
+// Steps 1-3 for ONE point: [M | d] = [I - A B | a + A c] into L, Gauss-Jordan, dw -> xs, uw = c + B dw -> ys, then dw_full /
+// uw_full [N,1,S] (nullable) and the VZA rows accumulated into uw / dw.  Shared by the elastic level kernel and the inelastic one
+// (vsm_level_radiance_ie_*), which hands over its line sums (r, q) from LDS as (a, c).  The whole workgroup enters; sh: 2 ints of
+// LDS (pivot row, non-finite flag).
 template <typename T>
-__global__ void __launch_bounds__(LEVEL_NT) k_level_radiance(int N, int ns, int nV, int nVtot, level_pp pa, const T* __restrict__ A,
-                                                             const T* __restrict__ a, const T* __restrict__ B, long long bstride,
-                                                             const T* __restrict__ c, T* uw, T* dw, T* dw_full, T* uw_full,
-                                                             int* status) {
-  extern __shared__ __align__(16) unsigned char lds_raw[];
-  T* L = reinterpret_cast<T*>(lds_raw);          // [M | d], row-major, leading dimension LD = N + 1
+__device__ __forceinline__ void level_solve_point(int N, int ns, int nV, int nVtot, const level_pp& pa, long long s, const T* As,
+                                                  const T* as_, const T* Bs, const T* cs, T* L, T* xs, T* ys, T* uw, T* dw,
+                                                  T* dw_full, T* uw_full, int* sh, int* status) {
   const int LD = N + 1;
-  T* xs = L + (size_t)N * LD;                    // dw
-  T* ys = xs + N;                                // uw
-  __shared__ int s_piv, s_flag;
-  const long long s = blockIdx.x;
-  const T* As = A + s * (long long)N * N;
-  const T* Bs = B + s * bstride;
-  const T* as_ = a + s * N;
-  const T* cs = c + s * N;
+  int& s_piv = sh[0];
+  int& s_flag = sh[1];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, kq = lane >> 4;
   if (tid == 0) s_flag = 0;
+  __syncthreads();
 
   // 1. [M | d] = [I | a] - [A B | -A c]: 16 x 16 output tiles over the N x (N + 1) block, round-robin over the four waves
   const int MT = (N + 15) / 16, CT = (N + 16) / 16;
@@ -126,6 +125,84 @@ __global__ void __launch_bounds__(LEVEL_NT) k_level_radiance(int N, int ns, int 
 }
 
 template <typename T>
+__global__ void __launch_bounds__(LEVEL_NT) k_level_radiance(int N, int ns, int nV, int nVtot, level_pp pa, const T* __restrict__ A,
+                                                             const T* __restrict__ a, const T* __restrict__ B, long long bstride,
+                                                             const T* __restrict__ c, T* uw, T* dw, T* dw_full, T* uw_full,
+                                                             int* status) {
+  extern __shared__ __align__(16) unsigned char lds_raw[];
+  T* L = reinterpret_cast<T*>(lds_raw);          // [M | d], row-major, leading dimension LD = N + 1
+  T* xs = L + (size_t)N * (N + 1);               // dw
+  T* ys = xs + N;                                // uw
+  __shared__ int sh[2];
+  const long long s = blockIdx.x;
+  level_solve_point<T>(N, ns, nV, nVtot, pa, s, A + s * (long long)N * N, a + s * N, B + s * bstride, c + s * N, L, xs, ys, uw, dw,
+                       dw_full, uw_full, sh, status);
+}
+
+// The inelastic level equation (vsm_level_radiance_ie_*) of recipient point n1 = blockIdx.x, lines summed before the solve:
+//   q = sum_k [c_ie,k + B_ie,k dw(n0)],  r = sum_k [a_ie,k + A_ie,k uw(n0)] + A q,  dw_ie = (I - A B)^-1 r,  uw_ie = q + B dw_ie
+// over the in-band lines k (n0 = n1 + shift[k] in 0..S-1); dw / uw are the ELASTIC level vectors of the donors.
+// Phase 1 streams the 2K ie blocks of the point: thread (g, i) = (tid / N, tid % N) of G = 256 / N column groups takes row i of
+// columns j = g, g + G, ... (column N = the vector), so the workgroup reads G consecutive columns, G N contiguous elements, per
+// step; the per-group partial sums are added in group order in LDS.  Phase 2 is level_solve_point with (a, c) = (r - A q, q).
+template <typename T>
+__global__ void __launch_bounds__(LEVEL_NT) k_level_radiance_ie(int N, int ns, int S, int K, const int* __restrict__ shift, int nV,
+                                                                int nVtot, level_pp pa, const T* __restrict__ A,
+                                                                const T* __restrict__ B, long long bstride,
+                                                                const T* __restrict__ dwf, const T* __restrict__ uwf,
+                                                                const T* __restrict__ Aie, const T* __restrict__ aie,
+                                                                const T* __restrict__ Bie, const T* __restrict__ cie, T* uwie,
+                                                                T* dwie, T* dwie_full, T* uwie_full, int* status) {
+  extern __shared__ __align__(16) unsigned char lds_raw[];
+  T* L = reinterpret_cast<T*>(lds_raw);          // [M | r], row-major, leading dimension N + 1
+  T* xs = L + (size_t)N * (N + 1);               // dw_ie
+  T* ys = xs + N;                                // uw_ie
+  T* qs = ys + N;                                // q
+  T* ps = qs + N;                                // sum_k [a_ie + A_ie uw(n0)]
+  T* part = ps + N;                              // [2][G][N] partial sums
+  __shared__ int sh[2];
+  const int tid = threadIdx.x;
+  const int n1 = blockIdx.x;
+  const long long NN = (long long)N * N;
+  const int G = LEVEL_NT / N, g = tid / N, i = tid - g * N;
+  T sp = T(0), sq = T(0);
+  if (g < G) {
+    for (int k = 0; k < K; ++k) {
+      const int n0 = n1 + shift[k];
+      if (n0 < 0 || n0 >= S) continue;
+      const long long blk = (long long)k * S + n1;
+      const T* Ak = Aie + blk * NN;
+      const T* Bk = Bie ? Bie + blk * NN : nullptr;
+      const T* u0 = uwf + (long long)n0 * N;
+      const T* d0 = dwf + (long long)n0 * N;
+      for (int j = g; j < N; j += G) {
+        sp += Ak[(long long)j * N + i] * u0[j];
+        if (Bk) sq += Bk[(long long)j * N + i] * d0[j];
+      }
+      if (g == (N % G)) {                          // column N: the vectors, taken by the group next in turn
+        sp += aie[blk * N + i];
+        if (cie) sq += cie[blk * N + i];
+      }
+    }
+    part[g * N + i] = sp;
+    part[(G + g) * N + i] = sq;
+  }
+  __syncthreads();
+  if (tid < N) {
+    T p = T(0), q = T(0);
+    for (int h = 0; h < G; ++h) {
+      p += part[h * N + tid];
+      q += part[(G + h) * N + tid];
+    }
+    ps[tid] = p;
+    qs[tid] = q;
+  }
+  __syncthreads();
+  level_solve_point<T>(N, ns, nV, nVtot, pa, n1, A + n1 * NN, ps, B + n1 * bstride, qs, L, xs, ys, uwie, dwie, dwie_full, uwie_full,
+                       sh, status);
+}
+
+template <typename T>
 static int level_radiance_fused(int N, int ns, int S, int nV, const int* row0_h, const T* w_h, const T* A, const T* a, const T* B,
                                 long long bstride, const T* c, T* uw, T* dw, T* dw_full, T* uw_full, hipStream_t st) {
   int* status = device_status();
@@ -154,6 +231,38 @@ static int level_radiance_fused(int N, int ns, int S, int nV, const int* row0_h,
                      uw_full, status);
   VSM_LAUNCH_CHECK("k_level_radiance");
   return postprocess_vza<T>(N, ns, S, nV, row0_h, w_h, uw_full, dw_full, uw, dw, st);
+}
+
+template <typename T>
+static int level_radiance_ie_fused(int N, int ns, int S, int K, const int* shift, int nV, const int* row0_h, const T* w_h, const T* A,
+                                   const T* B, long long bstride, const T* dwf, const T* uwf, const T* Aie, const T* aie,
+                                   const T* Bie, const T* cie, T* uwie, T* dwie, T* dwie_full, T* uwie_full, hipStream_t st) {
+  int* status = device_status();
+  if (!status) return VSM_ERR_HIP;
+  const size_t lds = ((size_t)N * (N + 1) + 4 * (size_t)N + 2 * (size_t)LEVEL_NT) * sizeof(T);
+  const int rc = ensure_dyn_lds(reinterpret_cast<const void*>(k_level_radiance_ie<T>), lds, "hipFuncSetAttribute(k_level_radiance_ie)");
+  if (rc) return rc;
+  level_pp pa = {};
+  if (nV <= 64) {
+    for (int v = 0; v < nV; ++v) pa.row0[v] = row0_h[v];
+    for (int k = 0; k < ns; ++k)
+      for (int v = 0; v < nV; ++v) pa.w[v + nV * k] = (double)w_h[v + nV * k];
+    hipLaunchKernelGGL(k_level_radiance_ie<T>, dim3(S), dim3(LEVEL_NT), lds, st, N, ns, S, K, shift, nV, nV, pa, A, B, bstride, dwf,
+                       uwf, Aie, aie, Bie, cie, uwie, dwie, dwie_full, uwie_full, status);
+    VSM_LAUNCH_CHECK("k_level_radiance_ie");
+    return VSM_OK;
+  }
+  // more than the 64 viewing angles one launch carries: the level vectors in full, then the VZA rows by vsm_postprocess_vza
+  T* full = dwie_full && uwie_full ? nullptr : static_cast<T*>(scratch(2 * (size_t)N * S * sizeof(T), 0, st));
+  if (!dwie_full || !uwie_full) {
+    if (!full) return VSM_ERR_HIP;
+    if (!dwie_full) dwie_full = full;
+    if (!uwie_full) uwie_full = full + (size_t)N * S;
+  }
+  hipLaunchKernelGGL(k_level_radiance_ie<T>, dim3(S), dim3(LEVEL_NT), lds, st, N, ns, S, K, shift, 0, 0, pa, A, B, bstride, dwf, uwf,
+                     Aie, aie, Bie, cie, uwie, dwie, dwie_full, uwie_full, status);
+  VSM_LAUNCH_CHECK("k_level_radiance_ie");
+  return postprocess_vza<T>(N, ns, S, nV, row0_h, w_h, uwie_full, dwie_full, uwie, dwie, st);
 }
 
 // operator-level twin: M = I - A B, d = a + A c (two batched products), dw = M^-1 d (vsm_batch_inv + product), uw = c + B dw
@@ -185,6 +294,22 @@ static int level_check(int N, int ns, int S, int nV, const int* row0_h, const T*
   VSM_REQUIRE(S == 0 || nV == 0 || (row0_h && w_h && uw && dw), "level_radiance: null output / viewing-angle table");
   for (int v = 0; v < nV; ++v)
     VSM_REQUIRE(row0_h[v] >= 0 && row0_h[v] + ns <= N, "level_radiance: row0[%d] = %d outside the %d streams", v, row0_h[v], N);
+  return VSM_OK;
+}
+
+template <typename T>
+static int level_ie_check(int N, int ns, int S, int K, const int* shift, int nV, const int* row0_h, const T* w_h, const T* A,
+                          const T* B, long long bstride, const T* dwf, const T* uwf, const T* Aie, const T* aie, const T* Bie,
+                          const T* cie, T* uwie, T* dwie) {
+  VSM_REQUIRE(N > 0 && N <= LEVEL_FUSED_MAX_N && ns >= 1 && ns <= 4 && N % ns == 0 && S >= 0 && K >= 0 && nV >= 0,
+              "level_radiance_ie: bad size (N %d <= %d, n_stokes %d, S %d, K %d, nV %d)", N, LEVEL_FUSED_MAX_N, ns, S, K, nV);
+  VSM_REQUIRE(bstride == 0 || bstride == (long long)N * N, "level_radiance_ie: bot_stride must be 0 or N*N");
+  VSM_REQUIRE(S == 0 || (A && B && dwf && uwf), "level_radiance_ie: null elastic operand");
+  VSM_REQUIRE(S == 0 || K == 0 || (shift && Aie && aie), "level_radiance_ie: null shift / top inelastic operand");
+  VSM_REQUIRE((Bie == nullptr) == (cie == nullptr), "level_radiance_ie: bot_ieR_mp and bot_ieJ0_m are both given or both NULL");
+  VSM_REQUIRE(S == 0 || nV == 0 || (row0_h && w_h && uwie && dwie), "level_radiance_ie: null output / viewing-angle table");
+  for (int v = 0; v < nV; ++v)
+    VSM_REQUIRE(row0_h[v] >= 0 && row0_h[v] + ns <= N, "level_radiance_ie: row0[%d] = %d outside the %d streams", v, row0_h[v], N);
   return VSM_OK;
 }
 
@@ -223,5 +348,20 @@ size_t vsm_level_radiance_work_elems(int N, int S) {
   }
 VSM_LEVEL_API(double, f64)
 VSM_LEVEL_API(float, f32)
+
+#define VSM_LEVEL_IE_API(T, SFX)                                                                                                \
+  int vsm_level_radiance_ie_##SFX(int N, int n_stokes, int S, int K, const int* shift, int nV, const int* row0_h, const T* w_h,  \
+                                  const T* top_R_pm, const T* bot_R_mp, long long bot_stride, const T* dw_full,               \
+                                  const T* uw_full, const T* top_ieR_pm, const T* top_ieJ0_p, const T* bot_ieR_mp,            \
+                                  const T* bot_ieJ0_m, T* uwie, T* dwie, T* dwie_full, T* uwie_full, void* stream) {          \
+    int rc = level_ie_check<T>(N, n_stokes, S, K, shift, nV, row0_h, w_h, top_R_pm, bot_R_mp, bot_stride, dw_full, uw_full,     \
+                               top_ieR_pm, top_ieJ0_p, bot_ieR_mp, bot_ieJ0_m, uwie, dwie);                                   \
+    if (rc || S == 0) return rc;                                                                                                \
+    return level_radiance_ie_fused<T>(N, n_stokes, S, K, shift, nV, row0_h, w_h, top_R_pm, bot_R_mp, bot_stride, dw_full,       \
+                                      uw_full, top_ieR_pm, top_ieJ0_p, bot_ieR_mp, bot_ieJ0_m, uwie, dwie, dwie_full,          \
+                                      uwie_full, as_stream(stream));                                                            \
+  }
+VSM_LEVEL_IE_API(double, f64)
+VSM_LEVEL_IE_API(float, f32)
 
 }  // extern "C"
