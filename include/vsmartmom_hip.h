@@ -810,6 +810,32 @@ int vsm_level_radiance_ie_f32(int N, int n_stokes, int S, int K, const int* shif
                               const float* uw_full, const float* top_ieR_pm, const float* top_ieJ0_p, const float* bot_ieR_mp,
                               const float* bot_ieJ0_m, float* uwie, float* dwie, float* dwie_full, float* uwie_full, void* stream);
 
+/* The derivative of the level equation (vsm_level_radiance_*) with respect to the Jacobian parameters of a linearized multi-sensor
+ * run (vsmartmom.jl_amd/core_rt_ms_lin.py) at ONE boundary: for every parameter p, with dw / uw = dw_full / uw_full [N,1,S] of the
+ * elastic level call at the same level and M = I - A B,
+ *   q_p = c'_p + B'_p dw,   dw'_p = M^-1 (a'_p + A'_p uw + A q_p),   uw'_p = q_p + B dw'_p
+ * (the derivative of interlayer_flux_helper!, CoreKernel/interlayer_flux.jl:1-19, in the push-through form).  A = top_R_pm [N,N,S],
+ * B = bot_R_mp with bot_stride (N*N, or 0: one block shared by every point).  Derivative stacks, the parameter axis slowest:
+ * A' = top_R_pm_lin with top_lin_pstride elements per parameter and N*N per point, a' = top_J0_p_lin [N,1,S,P_top]; slots
+ * >= P_top of the top are zero and not read (P_top = 0: both may be NULL).  B' = bot_R_mp_lin with bot_lin_stride per point (N*N,
+ * or 0: one block per parameter shared by every point) and bot_lin_pstride per parameter, c' = bot_J0_m_lin [N,1,S,P].
+ * Outputs: uw_lin / dw_lin [nV,n_stokes,S,P] ACCUMULATED with row0_h / w_h as in vsm_postprocess_vza_lin; dw_lin_full /
+ * uw_lin_full (nullable) [N,1,S,P] the derivative vectors at all streams.  N <= 128, 1 <= P <= 64: one workgroup per point, the
+ * parameters in chunks as extra right-hand sides of ONE Gauss-Jordan elimination of [M | r_1 .. r_PC] per chunk (the pivot rule
+ * of vsm_level_radiance_*, VSM_DEVSTAT_SINGULAR / _NONFINITE).  No work buffer. */
+int vsm_level_radiance_lin_f64(int N, int n_stokes, int S, int P, int P_top, int nV, const int* row0_h, const double* w_h,
+                               const double* top_R_pm, const double* bot_R_mp, long long bot_stride, const double* dw_full,
+                               const double* uw_full, const double* top_R_pm_lin, long long top_lin_pstride,
+                               const double* top_J0_p_lin, const double* bot_R_mp_lin, long long bot_lin_stride,
+                               long long bot_lin_pstride, const double* bot_J0_m_lin, double* uw_lin, double* dw_lin,
+                               double* dw_lin_full, double* uw_lin_full, void* stream);
+int vsm_level_radiance_lin_f32(int N, int n_stokes, int S, int P, int P_top, int nV, const int* row0_h, const float* w_h,
+                               const float* top_R_pm, const float* bot_R_mp, long long bot_stride, const float* dw_full,
+                               const float* uw_full, const float* top_R_pm_lin, long long top_lin_pstride,
+                               const float* top_J0_p_lin, const float* bot_R_mp_lin, long long bot_lin_stride,
+                               long long bot_lin_pstride, const float* bot_J0_m_lin, float* uw_lin, float* dw_lin,
+                               float* dw_lin_full, float* uw_lin_full, void* stream);
+
 /* ---- diagnostics used by the parity tests -------------------------------- */
 /* Runs the LDS-resident MFMA tile product used inside the fused kernels on plain
  * [N,N,S] inputs: C = A*B.  (Checks fragment layouts / swizzle independently.) */

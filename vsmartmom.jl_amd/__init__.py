@@ -11,7 +11,8 @@ Sub-modules
     CoreRT          batched_mul / batch_inv_ / elemental_ / doubling_ / interaction_ / rt_kernel_ / rt_run /
                     rt_run_multisensor (core_rt_ms: radiances at any level of the column)
     host_model      host-side producers of the hot path's inputs (streams, Z moments, layer mixing)
-    CoreRTLin       linearized (Jacobian) pass: rt_run(model, lin_model, ...)
+    CoreRTLin       linearized (Jacobian) pass: rt_run(model, lin_model, ...),
+                    rt_run_multisensor(model, lin_model, ..., sensor_levels) (core_rt_ms_lin: Jacobians at any level)
     CoreRTRaman     rotational-Raman pass: rt_run(RS_type::RRS, model, iBand),
                     rt_run_multisensor(RS_type, model, sensor_levels) (core_rt_ms_raman)
     parallel        spectral-axis sharding over the GPUs of one node (torch.distributed / RCCL)
@@ -24,6 +25,7 @@ from . import parallel  # noqa: F401
 from . import core_rt_lin as CoreRTLin  # noqa: F401
 from . import core_rt_raman as CoreRTRaman  # noqa: F401
 from . import core_rt_ms_raman  # noqa: F401
+from . import core_rt_ms_lin  # noqa: F401
 from . import raman_inputs  # noqa: F401
 from . import io_yaml  # noqa: F401
 from ._lib import VSMError, LIB_PATH  # noqa: F401
@@ -32,5 +34,7 @@ CoreRT.rt_run_multisensor = core_rt_ms.rt_run_multisensor
 CoreRT.MultiSensorResult = core_rt_ms.MultiSensorResult
 CoreRTRaman.rt_run_multisensor = core_rt_ms_raman.rt_run_multisensor
 CoreRTRaman.MultiSensorRamanResult = core_rt_ms_raman.MultiSensorRamanResult
+CoreRTLin.rt_run_multisensor = core_rt_ms_lin.rt_run_multisensor
+CoreRTLin.MultiSensorLinResult = core_rt_ms_lin.MultiSensorLinResult
 
 __version__ = "0.1.0"

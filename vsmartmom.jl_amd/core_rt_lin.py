@@ -724,37 +724,47 @@ class SceneLin:
             torch._foreach_add_([self.R, self.T, self.Rd, self.Td], [w["R"], w["T"], w["Rd"], w["Td"]])
         return self.R, self.T, self.Rd, self.Td
 
-    def _run_moment(self, mom, w):
-        """One Fourier moment on the workspace `w` (launches on the current stream)."""
-        model, pol, qp, FT, dt, fwd = self.model, self.pol, self.qp, self.FT, self.dt, self.fwd
-        N, S, P, pl = self.N, self.S, self.P, self.pl
+    def _run_moment(self, mom, w, after_layer=None):
+        """One Fourier moment on the workspace `w` (launches on the current stream).  after_layer(l, comp, cl): called after layer l
+        (1-based) has joined the composite (the multi-sensor run keeps its tops there)."""
+        N, S = self.N, self.S
         added, al, comp, cl = w["added"], w["al"], w["comp"], w["cl"]
-        mu0 = C.c_double(qp.mu0) if dt == torch.float64 else C.c_float(qp.mu0)
-        q_ = self.dq.cstruct()
-        m = mom["m"]
         for iz, ly in enumerate(mom["layers"]):
-            props = ly["props"]
-            dtd, vd, tsd = self.dtau_dot_all[iz], self.varpi_dot[iz], self.tau_sum_dot[iz]
-            if self.Zall is not None:
-                mixed, k = fwd.zcomp[iz]
-                a_, al_ = added.cstruct(), al.cstruct()
-                _lib.call("vsm_elemental_lin_mix", dt, C.byref(q_), S, m, ly["nd"], CR._ptr(ly["dtau"]), CR._ptr(props.varpi),
-                          CR._ptr(ly["tau_sum"]), CR._ptr(self.F0), self.C_, self.CT, CR._ptr(self.Zall[m][0]),
-                          CR._ptr(self.Zall[m][1]), -1 if mixed else k, CR._ptr(self.fz[iz]), pl, CR._ptr(dtd), CR._ptr(vd),
-                          CR._ptr(tsd), CR._ptr(self.zdcoef[iz]), C.byref(a_), C.byref(al_), CR._stream_ptr())
-            else:
-                zpd, zmd, zds = self.host_zdot[m][iz] if self.host_zdot is not None else (None, None, (0, 0))
-                elemental_lin_(pol, ly["tau_sum"], tsd, ly["dtau"], dtd, self.F0, props.materialize(), vd, zpd, zmd, zds, pl,
-                               m, ly["nd"], self.dq, added, al)
-            _lib.call("vsm_layer_expk", dt, S, CR._ptr(ly["dtau"]), mu0, CR._ptr(w["expk"]), CR._stream_ptr())
-            doubling_allparams_(pol, w["expk"], ly["nd"], added, al, dtd, qp.mu0, pl)
+            self._double_layer(mom, iz, w)
             if iz == 0:
                 CR.copy_added_to_composite_(comp, added)
                 a_, c_ = al.cstruct(), cl.cstruct()
-                _lib.call("vsm_copy_added_to_composite_lin", dt, N, S, C.byref(a_), C.byref(c_), CR._stream_ptr())
+                _lib.call("vsm_copy_added_to_composite_lin", self.dt, N, S, C.byref(a_), C.byref(c_), CR._stream_ptr())
             else:
                 interaction_lin_(ly["iface"], comp, cl, added, al, p_range=self._layer_slots)
+            if after_layer is not None:
+                after_layer(iz + 1, comp, cl)
         self._finish_moment(mom, w)
+
+    def _double_layer(self, mom, iz, w):
+        """elemental! (lin) + doubling! (lin) of layer iz (0-based) of one moment into w["added"] / w["al"]."""
+        pol, qp, dt, fwd = self.pol, self.qp, self.dt, self.fwd
+        S, pl = self.S, self.pl
+        added, al = w["added"], w["al"]
+        mu0 = C.c_double(qp.mu0) if dt == torch.float64 else C.c_float(qp.mu0)
+        q_ = self.dq.cstruct()
+        m = mom["m"]
+        ly = mom["layers"][iz]
+        props = ly["props"]
+        dtd, vd, tsd = self.dtau_dot_all[iz], self.varpi_dot[iz], self.tau_sum_dot[iz]
+        if self.Zall is not None:
+            mixed, k = fwd.zcomp[iz]
+            a_, al_ = added.cstruct(), al.cstruct()
+            _lib.call("vsm_elemental_lin_mix", dt, C.byref(q_), S, m, ly["nd"], CR._ptr(ly["dtau"]), CR._ptr(props.varpi),
+                      CR._ptr(ly["tau_sum"]), CR._ptr(self.F0), self.C_, self.CT, CR._ptr(self.Zall[m][0]),
+                      CR._ptr(self.Zall[m][1]), -1 if mixed else k, CR._ptr(self.fz[iz]), pl, CR._ptr(dtd), CR._ptr(vd),
+                      CR._ptr(tsd), CR._ptr(self.zdcoef[iz]), C.byref(a_), C.byref(al_), CR._stream_ptr())
+        else:
+            zpd, zmd, zds = self.host_zdot[m][iz] if self.host_zdot is not None else (None, None, (0, 0))
+            elemental_lin_(pol, ly["tau_sum"], tsd, ly["dtau"], dtd, self.F0, props.materialize(), vd, zpd, zmd, zds, pl,
+                           m, ly["nd"], self.dq, added, al)
+        _lib.call("vsm_layer_expk", dt, S, CR._ptr(ly["dtau"]), mu0, CR._ptr(w["expk"]), CR._stream_ptr())
+        doubling_allparams_(pol, w["expk"], ly["nd"], added, al, dtd, qp.mu0, pl)
 
     def _finish_moment(self, mom, w):
         """Surface layer, its interaction and the post-processing of one Fourier moment on the workspace `w`."""

@@ -111,11 +111,11 @@ def _layer(sc: RR.SceneRRS, mom, iz: int, comp, comp_rs, iz_local: int):
 
 
 def _expand_iq(v: torch.Tensor, n: int) -> torch.Tensor:
-    """(S, 2 Nquad) level vectors of the Stokes_IQ scene -> (S, n Nquad) with U = V = 0."""
-    S, N2 = int(v.shape[0]), int(v.shape[1])
-    out = torch.zeros((S, N2 // 2, n), dtype=v.dtype, device=v.device)
-    out[:, :, :2] = v.reshape(S, N2 // 2, 2)
-    return out.reshape(S, -1)
+    """(..., 2 Nquad) level vectors of the Stokes_IQ scene -> (..., n Nquad) with U = V = 0."""
+    lead, N2 = tuple(v.shape[:-1]), int(v.shape[-1])
+    out = torch.zeros(lead + (N2 // 2, n), dtype=v.dtype, device=v.device)
+    out[..., :2] = v.reshape(lead + (N2 // 2, 2))
+    return out.reshape(lead + (-1,))
 
 
 def _run_scene(sc: RR.SceneRRS, levels: List[int], streams: bool):

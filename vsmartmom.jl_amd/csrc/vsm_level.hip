@@ -14,6 +14,8 @@
 //
 // vsm_level_radiance_ie_*: the first-order (Raman) part of the same equation, interlayer_flux_helper!(::RRS) (interlayer_flux.jl:
 // 21-77), per recipient point with the lines summed before ONE solve of the same [I - A B | r] (k_level_radiance_ie, below).
+// vsm_level_radiance_lin_*: its derivative with respect to the Jacobian parameters, the parameters as extra right-hand sides of
+// ONE solve per chunk (k_level_radiance_lin, below).
 #include "vsm_common.h"
 #include "vsm_internal.h"
 #include "vsm_inverse.h"
@@ -265,6 +267,214 @@ static int level_radiance_ie_fused(int N, int ns, int S, int K, const int* shift
   return postprocess_vza<T>(N, ns, S, nV, row0_h, w_h, uwie_full, dwie_full, uwie, dwie, st);
 }
 
+// The derivative of the level equation (vsm_level_radiance_lin_*) at point s = blockIdx.x, for every parameter p:
+//   q_p = c'_p + B'_p dw,   r_p = a'_p + A'_p uw + A q_p,   dw'_p = (I - A B)^-1 r_p,   uw'_p = q_p + B dw'_p
+// with dw / uw the elastic level vectors of the point (vsm_level_radiance_* dw_full / uw_full).  The parameters run in chunks of
+// PC; per chunk:
+//   1. the bottom blocks B'_p, c'_p (every slot) and the top blocks A'_p, a'_p (slots < P_top) streamed by the column groups of
+//      k_level_radiance_ie (thread (g, i) of G = 256 / N groups, column N = the vector, partial sums added in group order):
+//      q_p -> Q[pc], s_p = a'_p + A'_p uw -> column N + pc of L;
+//   2. [M | r_1 .. r_PC] = [I - A B | s + A q] in ONE MFMA product (the q_p ride as extra columns of B, as c does in the elastic
+//      kernel), then ONE Gauss-Jordan elimination of the whole block with the pivot rule of level_solve_point (same M, same rule:
+//      the elastic call's pivots);
+//   3. dw'_p = column / m_ii (in place), uw'_p = q_p + B dw'_p (into Q), the VZA rows ACCUMULATED into [P, S, n_stokes, nV].
+// LDS: L [N][N + PC], Q [PC][N], dw / uw [2][N], partial sums [2][G][N].
+template <typename T>
+__global__ void __launch_bounds__(LEVEL_NT) k_level_radiance_lin(int N, int ns, int S, int P, int P_top, int PC, int nV, level_pp pa,
+                                                                 const T* __restrict__ A, const T* __restrict__ B, long long bstride,
+                                                                 const T* __restrict__ dwf, const T* __restrict__ uwf,
+                                                                 const T* __restrict__ Ad, long long ad_pstride,
+                                                                 const T* __restrict__ ad, const T* __restrict__ Bd,
+                                                                 long long bd_stride, long long bd_pstride, const T* __restrict__ cd,
+                                                                 T* uwd, T* dwd, T* dwd_full, T* uwd_full, int* status) {
+  extern __shared__ __align__(16) unsigned char lds_raw[];
+  const int LD = N + PC;
+  T* L = reinterpret_cast<T*>(lds_raw);          // [M | r_1 .. r_PC], row-major, leading dimension N + PC
+  T* Q = L + (size_t)N * LD;                     // q_p, then uw'_p
+  T* xs = Q + (size_t)PC * N;                    // dw
+  T* ys = xs + N;                                // uw
+  T* part = ys + N;                              // [2][G][N] partial sums
+  __shared__ int sh[2];
+  int& s_piv = sh[0];
+  int& s_flag = sh[1];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, kq = lane >> 4;
+  const long long s = blockIdx.x;
+  const long long NN = (long long)N * N, SN = (long long)S * N;
+  const T* As = A + s * NN;
+  const T* Bs = B + s * bstride;
+  const int G = LEVEL_NT / N, g = tid / N, i1 = tid - g * N;
+  for (int i = tid; i < N; i += LEVEL_NT) {
+    xs[i] = dwf[s * N + i];
+    ys[i] = uwf[s * N + i];
+  }
+  for (int p0 = 0; p0 < P; p0 += PC) {
+    const int pc_n = P - p0 < PC ? P - p0 : PC;
+    if (tid == 0) s_flag = 0;
+    __syncthreads();   // (dw / uw loaded; the previous chunk's outputs read L and Q)
+    // 1. q_p and s_p of the chunk
+    for (int pc = 0; pc < pc_n; ++pc) {
+      const int p = p0 + pc;
+      if (g < G) {
+        const bool top = p < P_top;
+        const T* Bk = Bd + p * bd_pstride + s * bd_stride;
+        const T* Ak = top ? Ad + p * ad_pstride + s * NN : nullptr;
+        T sq = T(0), sp = T(0);
+        for (int j = g; j < N; j += G) {
+          sq += Bk[(long long)j * N + i1] * xs[j];
+          if (top) sp += Ak[(long long)j * N + i1] * ys[j];
+        }
+        if (g == (N % G)) {                          // column N: the vectors, taken by the group next in turn
+          sq += cd[p * SN + s * N + i1];
+          if (top) sp += ad[p * SN + s * N + i1];
+        }
+        part[g * N + i1] = sq;
+        part[(G + g) * N + i1] = sp;
+      }
+      __syncthreads();
+      if (tid < N) {
+        T q = T(0), sp = T(0);
+        for (int h = 0; h < G; ++h) {
+          q += part[h * N + tid];
+          sp += part[(G + h) * N + tid];
+        }
+        Q[pc * N + tid] = q;
+        L[tid * LD + N + pc] = sp;
+      }
+      __syncthreads();
+    }
+    // 2. [M | r] = [I | s] - [A B | -A q]: 16 x 16 output tiles over the N x (N + pc_n) block, round-robin over the four waves
+    const int NC = N + pc_n;
+    const int MT = (N + 15) / 16, CT = (NC + 15) / 16;
+    bool bad = false;
+    for (int t = wave; t < MT * CT; t += LEVEL_NT / 64) {
+      const int ti = t / CT, tj = t % CT;
+      const int row = 16 * ti + li, col = 16 * tj + li;
+      typename mfma<T>::acc_t acc = acc_zero<T>();
+      for (int k0 = 0; k0 < N; k0 += 4) {
+        const int k = k0 + kq;
+        const T av = (row < N && k < N) ? As[(long long)k * N + row] : T(0);
+        const T bv = (k < N) ? (col < N ? Bs[(long long)col * N + k] : (col < NC ? Q[(col - N) * N + k] : T(0))) : T(0);
+        acc = mfma<T>::mma(av, bv, acc);
+      }
+      const int ocol = 16 * tj + li;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int orow = 16 * ti + mfma<T>::crow(lane, r);
+        if (orow < N && ocol < NC) {
+          const T v = ocol < N ? ((orow == ocol ? T(1) : T(0)) - acc[r]) : L[orow * LD + ocol] + acc[r];
+          bad |= !isfinite(v);
+          L[orow * LD + ocol] = v;
+        }
+      }
+    }
+    if (bad) s_flag = 1;
+    __syncthreads();
+    if (s_flag && tid == 0) atomicOr(&status[0], (int)VSM_DEVSTAT_NONFINITE);
+    // Gauss-Jordan elimination of [M | r]: the pivot rule and row operations of level_solve_point over NC columns
+    const int tj = tid & 63, ti = tid >> 6;
+    for (int k = 0; k < N; ++k) {
+      if (wave == 0) {
+        const bool in0 = lane >= k && lane < N, in1 = lane + 64 >= k && lane + 64 < N;
+        const T v0 = in0 ? fabs(L[lane * LD + k]) : T(-1);
+        const T v1 = in1 ? fabs(L[(lane + 64) * LD + k]) : T(-1);
+        const T best = wave_max(v0 > v1 ? v0 : v1);
+        const unsigned long long m0 = __ballot(in0 && v0 == best), m1 = __ballot(in1 && v1 == best);
+        const int p = m0 ? (__ffsll((long long)m0) - 1) : (m1 ? 64 + __ffsll((long long)m1) - 1 : k);
+        if (lane == 0) s_piv = p;
+      }
+      __syncthreads();
+      const int p = s_piv;
+      if (p != k) {
+        for (int j = k + tid; j < NC; j += LEVEL_NT) {
+          const T tmp = L[k * LD + j];
+          L[k * LD + j] = L[p * LD + j];
+          L[p * LD + j] = tmp;
+        }
+        __syncthreads();
+      }
+      const T pv = L[k * LD + k];
+      if (pv == T(0) && tid == 0) atomicOr(&status[0], (int)VSM_DEVSTAT_SINGULAR);
+      const T inv = T(1) / pv;
+      for (int i = ti; i < N; i += LEVEL_NT / 64) {
+        if (i == k) continue;
+        const T f = L[i * LD + k] * inv;
+        for (int j = k + 1 + tj; j < NC; j += 64) L[i * LD + j] -= f * L[k * LD + j];
+      }
+      __syncthreads();
+    }
+    // 3. dw'_p = r_p / m_ii (in place: each element is read and written by its own thread), then uw'_p = q_p + B dw'_p
+    for (int e = tid; e < N * pc_n; e += LEVEL_NT) {
+      const int i = e % N, pc = e / N;
+      L[i * LD + N + pc] = L[i * LD + N + pc] / L[i * LD + i];
+    }
+    __syncthreads();
+    for (int e = tid; e < N * pc_n; e += LEVEL_NT) {
+      const int i = e % N, pc = e / N;
+      T y = Q[pc * N + i];
+      for (int j = 0; j < N; ++j) y += Bs[(long long)j * N + i] * L[j * LD + N + pc];
+      Q[pc * N + i] = y;
+      const long long o = (long long)(p0 + pc) * SN + s * N + i;
+      if (dwd_full) dwd_full[o] = L[i * LD + N + pc];
+      if (uwd_full) uwd_full[o] = y;
+    }
+    __syncthreads();
+    for (int e = tid; e < nV * ns * pc_n; e += LEVEL_NT) {
+      const int v = e % nV, k = (e / nV) % ns, pc = e / (nV * ns);
+      const T w = (T)pa.w[v + nV * k];
+      const long long dst = (((long long)(p0 + pc) * S + s) * ns + k) * nV + v;
+      uwd[dst] += w * Q[pc * N + pa.row0[v] + k];
+      dwd[dst] += w * L[(pa.row0[v] + k) * LD + N + pc];
+    }
+  }
+}
+
+// Parameters per chunk of k_level_radiance_lin: as many as the LDS holds (160 KiB less room for the static words), at most P
+template <typename T>
+static int level_lin_chunk(int N, int P) {
+  const size_t budget = (160 * 1024 - 256) / sizeof(T), fixed = (size_t)N * N + 2 * (size_t)N + 2 * (size_t)LEVEL_NT;
+  const int pc = (int)((budget - fixed) / (2 * (size_t)N));
+  return pc < P ? pc : P;
+}
+
+template <typename T>
+static size_t level_lin_lds(int N, int PC) {
+  return ((size_t)N * (N + PC) + (size_t)PC * N + 2 * (size_t)N + 2 * (size_t)LEVEL_NT) * sizeof(T);
+}
+
+template <typename T>
+static int level_radiance_lin_fused(int N, int ns, int S, int P, int P_top, int nV, const int* row0_h, const T* w_h, const T* A,
+                                    const T* B, long long bstride, const T* dwf, const T* uwf, const T* Ad, long long ad_pstride,
+                                    const T* ad, const T* Bd, long long bd_stride, long long bd_pstride, const T* cd, T* uwd,
+                                    T* dwd, T* dwd_full, T* uwd_full, hipStream_t st) {
+  int* status = device_status();
+  if (!status) return VSM_ERR_HIP;
+  const int PC = level_lin_chunk<T>(N, P);
+  const size_t lds = level_lin_lds<T>(N, PC);
+  const int rc = ensure_dyn_lds(reinterpret_cast<const void*>(k_level_radiance_lin<T>), lds, "hipFuncSetAttribute(k_level_radiance_lin)");
+  if (rc) return rc;
+  level_pp pa = {};
+  if (nV <= 64) {
+    for (int v = 0; v < nV; ++v) pa.row0[v] = row0_h[v];
+    for (int k = 0; k < ns; ++k)
+      for (int v = 0; v < nV; ++v) pa.w[v + nV * k] = (double)w_h[v + nV * k];
+    hipLaunchKernelGGL(k_level_radiance_lin<T>, dim3(S), dim3(LEVEL_NT), lds, st, N, ns, S, P, P_top, PC, nV, pa, A, B, bstride, dwf,
+                       uwf, Ad, ad_pstride, ad, Bd, bd_stride, bd_pstride, cd, uwd, dwd, dwd_full, uwd_full, status);
+    VSM_LAUNCH_CHECK("k_level_radiance_lin");
+    return VSM_OK;
+  }
+  // more than the 64 viewing angles one launch carries: the derivative vectors in full, then the VZA rows by postprocess_vza_lin
+  T* full = dwd_full && uwd_full ? nullptr : static_cast<T*>(scratch(2 * (size_t)P * N * S * sizeof(T), 0, st));
+  if (!dwd_full || !uwd_full) {
+    if (!full) return VSM_ERR_HIP;
+    if (!dwd_full) dwd_full = full;
+    if (!uwd_full) uwd_full = full + (size_t)P * N * S;
+  }
+  hipLaunchKernelGGL(k_level_radiance_lin<T>, dim3(S), dim3(LEVEL_NT), lds, st, N, ns, S, P, P_top, PC, 0, pa, A, B, bstride, dwf, uwf,
+                     Ad, ad_pstride, ad, Bd, bd_stride, bd_pstride, cd, uwd, dwd, dwd_full, uwd_full, status);
+  VSM_LAUNCH_CHECK("k_level_radiance_lin");
+  return postprocess_vza_lin<T>(N, ns, S, nV, P, row0_h, w_h, uwd_full, dwd_full, uwd, dwd, st);
+}
+
 // operator-level twin: M = I - A B, d = a + A c (two batched products), dw = M^-1 d (vsm_batch_inv + product), uw = c + B dw
 template <typename T>
 static int level_radiance_oplevel(int N, int ns, int S, int nV, const int* row0_h, const T* w_h, const T* A, const T* a, const T* B,
@@ -310,6 +520,26 @@ static int level_ie_check(int N, int ns, int S, int K, const int* shift, int nV,
   VSM_REQUIRE(S == 0 || nV == 0 || (row0_h && w_h && uwie && dwie), "level_radiance_ie: null output / viewing-angle table");
   for (int v = 0; v < nV; ++v)
     VSM_REQUIRE(row0_h[v] >= 0 && row0_h[v] + ns <= N, "level_radiance_ie: row0[%d] = %d outside the %d streams", v, row0_h[v], N);
+  return VSM_OK;
+}
+
+template <typename T>
+static int level_lin_check(int N, int ns, int S, int P, int P_top, int nV, const int* row0_h, const T* w_h, const T* A, const T* B,
+                           long long bstride, const T* dwf, const T* uwf, const T* Ad, long long ad_pstride, const T* ad,
+                           const T* Bd, long long bd_stride, long long bd_pstride, const T* cd, T* uwd, T* dwd) {
+  VSM_REQUIRE(N > 0 && N <= LEVEL_FUSED_MAX_N && ns >= 1 && ns <= 4 && N % ns == 0 && S >= 0 && nV >= 0,
+              "level_radiance_lin: bad size (N %d <= %d, n_stokes %d, S %d, nV %d)", N, LEVEL_FUSED_MAX_N, ns, S, nV);
+  VSM_REQUIRE(P >= 1 && P <= 64 && P_top >= 0 && P_top <= P, "level_radiance_lin: bad parameter count (P %d in 1..64, P_top %d in 0..P)",
+              P, P_top);
+  VSM_REQUIRE(bstride == 0 || bstride == (long long)N * N, "level_radiance_lin: bot_stride must be 0 or N*N");
+  VSM_REQUIRE(bd_stride == 0 || bd_stride == (long long)N * N, "level_radiance_lin: bot_lin_stride must be 0 or N*N");
+  VSM_REQUIRE(bd_pstride >= (bd_stride ? (long long)S * N * N : (long long)N * N) && (P_top == 0 || ad_pstride >= (long long)S * N * N),
+              "level_radiance_lin: a per-parameter stride is shorter than one parameter's blocks");
+  VSM_REQUIRE(S == 0 || (A && B && dwf && uwf && Bd && cd), "level_radiance_lin: null operand");
+  VSM_REQUIRE(S == 0 || P_top == 0 || (Ad && ad), "level_radiance_lin: null top derivative operand");
+  VSM_REQUIRE(S == 0 || nV == 0 || (row0_h && w_h && uwd && dwd), "level_radiance_lin: null output / viewing-angle table");
+  for (int v = 0; v < nV; ++v)
+    VSM_REQUIRE(row0_h[v] >= 0 && row0_h[v] + ns <= N, "level_radiance_lin: row0[%d] = %d outside the %d streams", v, row0_h[v], N);
   return VSM_OK;
 }
 
@@ -363,5 +593,24 @@ VSM_LEVEL_API(float, f32)
   }
 VSM_LEVEL_IE_API(double, f64)
 VSM_LEVEL_IE_API(float, f32)
+
+#define VSM_LEVEL_LIN_API(T, SFX)                                                                                               \
+  int vsm_level_radiance_lin_##SFX(int N, int n_stokes, int S, int P, int P_top, int nV, const int* row0_h, const T* w_h,      \
+                                   const T* top_R_pm, const T* bot_R_mp, long long bot_stride, const T* dw_full,             \
+                                   const T* uw_full, const T* top_R_pm_lin, long long top_lin_pstride, const T* top_J0_p_lin, \
+                                   const T* bot_R_mp_lin, long long bot_lin_stride, long long bot_lin_pstride,               \
+                                   const T* bot_J0_m_lin, T* uw_lin, T* dw_lin, T* dw_lin_full, T* uw_lin_full,               \
+                                   void* stream) {                                                                            \
+    int rc = level_lin_check<T>(N, n_stokes, S, P, P_top, nV, row0_h, w_h, top_R_pm, bot_R_mp, bot_stride, dw_full, uw_full,  \
+                                top_R_pm_lin, top_lin_pstride, top_J0_p_lin, bot_R_mp_lin, bot_lin_stride, bot_lin_pstride,   \
+                                bot_J0_m_lin, uw_lin, dw_lin);                                                                \
+    if (rc || S == 0) return rc;                                                                                              \
+    return level_radiance_lin_fused<T>(N, n_stokes, S, P, P_top, nV, row0_h, w_h, top_R_pm, bot_R_mp, bot_stride, dw_full,    \
+                                       uw_full, top_R_pm_lin, top_lin_pstride, top_J0_p_lin, bot_R_mp_lin, bot_lin_stride,    \
+                                       bot_lin_pstride, bot_J0_m_lin, uw_lin, dw_lin, dw_lin_full, uw_lin_full,               \
+                                       as_stream(stream));                                                                    \
+  }
+VSM_LEVEL_LIN_API(double, f64)
+VSM_LEVEL_LIN_API(float, f32)
 
 }  // extern "C"
