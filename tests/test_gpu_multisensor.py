@@ -174,14 +174,22 @@ def _rand_level_inputs(N, S, rng, shared_bot):
 @pytest.mark.parametrize("N", [8, 60, 64, 96, 112, 128])
 @pytest.mark.parametrize("FT", [np.float64, np.float32], ids=["f64", "f32"])
 def test_level_kernel_fused_vs_oplevel(vsm, N, FT):
+    _fused_vs_oplevel(vsm, N, FT, [0.0, 30.0, 60.0], [0.0, 45.0, 120.0])
+
+
+@pytest.mark.parametrize("FT", [np.float64, np.float32], ids=["f64", "f32"])
+def test_level_kernel_fused_vs_oplevel_many_angles(vsm, FT):
+    """70 viewing angles: more than the 64 one launch of the fused kernel carries (full vectors, then vsm_postprocess_vza)."""
+    _fused_vs_oplevel(vsm, 60, FT, list(np.linspace(0.0, 80.0, 70)), list(np.linspace(0.0, 345.0, 70)))
+
+
+def _fused_vs_oplevel(vsm, N, FT, vza, vaz):
     CR, MSd = vsm.CoreRT, vsm.core_rt_ms
     H = vsm.host_model
     pol = H.polarization_type("IQU" if N % 3 == 0 else "I")
     S = 7
     rng = np.random.default_rng(N)
     qp = types.SimpleNamespace(qp_mu=np.linspace(1.0, 0.05, N // pol.n))     # (the rows of the viewing angles: all _vza_rows_weights reads)
-    vza = [0.0, 30.0, 60.0]
-    vaz = [0.0, 45.0, 120.0]
     dev = torch.device("cuda", 0)
     for shared in (False, True):
         A, a, B, c = _rand_level_inputs(N, S, rng, shared)

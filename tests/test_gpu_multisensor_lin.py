@@ -172,7 +172,7 @@ def test_multisensor_lin_fp32(vsm, arch, pol, lt):
 
 
 # ---- the kernel alone --------------------------------------------------------------------------------------------------------
-def _kernel_case(vsm, N, P, P_top, shared, S=3, FT=np.float64, ns=3, seed=0):
+def _kernel_case(vsm, N, P, P_top, shared, S=3, FT=np.float64, ns=3, seed=0, nV=2):
     rng = np.random.default_rng(seed + N + 7 * P)
     ns = ns if N % ns == 0 else 1
     A = 0.9 * rng.uniform(0, 1, (S, N, N)) / N
@@ -187,8 +187,7 @@ def _kernel_case(vsm, N, P, P_top, shared, S=3, FT=np.float64, ns=3, seed=0):
     uw, dw, uwd, dwd = MSL.level_lin_push_through(np.float64, A, a, B, c, Adz, adz, Bd, cd)
     dev = lambda x: torch.tensor(np.ascontiguousarray(x), dtype=torch.float64 if FT == np.float64 else torch.float32, device="cuda")
     sw = lambda M: np.swapaxes(M, -1, -2)                # math order -> the column-major layout
-    nV = 2
-    row0 = (C.c_int * nV)(0, N - ns)
+    row0 = (C.c_int * nV)(0, N - ns, *[ns * (v % (N // ns)) for v in range(2, nV)])
     ct = C.c_double if FT == np.float64 else C.c_float
     wv = rng.uniform(0.5, 1.5, nV * ns)
     w = (ct * (nV * ns))(*wv)
@@ -221,6 +220,13 @@ def test_level_kernel_lin_vs_numpy(vsm, N, P, P_top, shared):
     got, ref = _kernel_case(vsm, N, P, P_top, shared)
     for g, r in zip(got, ref):
         assert np.all(np.isfinite(g)) and np.abs(g - r).max() <= 1e-11 * np.abs(r).max(), (N, P)
+
+
+def test_level_kernel_lin_vs_numpy_many_angles(vsm):
+    """70 viewing angles: more than the 64 one launch carries (derivative vectors in full, then vsm_postprocess_vza_lin)."""
+    got, ref = _kernel_case(vsm, 21, 3, 2, True, nV=70)
+    for g, r in zip(got, ref):
+        assert np.all(np.isfinite(g)) and np.abs(g - r).max() <= 1e-11 * np.abs(r).max()
 
 
 @pytest.mark.parametrize("N,P", [(60, 17), (128, 40)])

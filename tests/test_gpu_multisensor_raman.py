@@ -158,6 +158,16 @@ def _kernel_cases():
 def test_level_ie_kernel_vs_numpy(vsm, FT, N, K, bottom):
     """Random inputs; shifts in band, partly in band and never in band; a per-point, a shared-block (bot_stride 0) and a NULL
     inelastic bottom; the stream outputs start as NaN and must be overwritten."""
+    _level_ie_vs_numpy(vsm, FT, N, K, bottom, 3)
+
+
+@pytest.mark.parametrize("FT", [np.float64, np.float32])
+def test_level_ie_kernel_vs_numpy_many_angles(vsm, FT):
+    """70 viewing angles: more than the 64 one launch carries (full vectors, then vsm_postprocess_vza)."""
+    _level_ie_vs_numpy(vsm, FT, 21, 9, "per_point", 70)
+
+
+def _level_ie_vs_numpy(vsm, FT, N, K, bottom, nV):
     S = 9 if N <= 33 else 5
     rng = np.random.default_rng(N * 1000 + K)
     ns = 3 if N % 3 == 0 else 1
@@ -169,10 +179,9 @@ def test_level_ie_kernel_vs_numpy(vsm, FT, N, K, bottom):
     Bie, cie = (None, None) if bottom == "null" else (0.05 * rng.random((K, S, N, N)) / N, 0.05 * rng.random((K, S, N)))
     cast = lambda x: None if x is None else x.astype(FT).astype(np.float64)
     uwie_r, dwie_r = MR.level_ie_push_through(np.float64, shifts, *map(cast, (A, B, dwf, uwf, Aie, aie, Bie, cie)))
-    row0 = [0, ns * ((N // ns) // 2), N - ns]
+    row0 = [0, ns * ((N // ns) // 2), N - ns] + [ns * (v % (N // ns)) for v in range(3, nV)]
     wv = rng.uniform(0.1, 1.0, len(row0) * ns)
     dt = torch.float64 if FT == np.float64 else torch.float32
-    nV = len(row0)
     uwie = torch.zeros((S, ns, nV), dtype=dt, device="cuda")
     dwie = torch.zeros((S, ns, nV), dtype=dt, device="cuda")
     dwief = torch.full((S, N), float("nan"), dtype=dt, device="cuda")

@@ -16,13 +16,17 @@ prototype runs one interaction per sensor and layer, O(Nz K) for K sensors.  Add
   4. one level-kernel call per level (vsm_level_radiance_*), level Nz with the surface layer alone as its bottom.
 
 Per moment: Nz + (Nz - l_1) layer steps, K + 1 further interactions and at most K + 1 level calls.
+
+The Raman (core_rt_ms_raman.py) and linearized (core_rt_ms_lin.py) runs are the same algorithm on their own composites.  What the
+three share lives here: the level plan, the walk below the top pass (walk_levels), the two-call level of the runs that solve a
+second equation on the elastic level vectors (level_pair_), the Stokes_IQ sub-scene of m = 0 (merge_sub0), the blocks of the
+spectral axis and the assembly of the results (spectral_blocks, gather_blocks).
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from dataclasses import dataclass
-from typing import List, Optional
+from typing import List
 
 import numpy as np
 import torch
@@ -52,6 +56,15 @@ class _CompositeAsAdded:
 _level_work = {}
 
 
+def level_call_setup(pol, qp, vza, vaz, m: int, weight: float, vec, bot_R_mp):
+    """(S, N, dtype, row0, w, bot_stride) of a level call, from one of its (S, N) vectors and the bottom's R-+; None for S = 0."""
+    S, N = int(vec.shape[0]), int(vec.shape[1])
+    if S == 0:
+        return None
+    row0, w = CR._vza_rows_weights(pol, vza, vaz, qp, m, weight, vec.dtype)
+    return S, N, vec.dtype, row0, w, (0 if int(bot_R_mp.shape[0]) == 1 and S > 1 else N * N)
+
+
 def level_radiance_(pol, qp, vza, vaz, m: int, weight: float, top_R_pm, top_J0_p, bot_R_mp, bot_J0_m, uw, dw,
                     dw_full=None, uw_full=None, oplevel: bool = False):
     """The level equation at one boundary (interlayer_flux_helper!, interlayer_flux.jl:1-19, + the VZA rows of
@@ -59,12 +72,10 @@ def level_radiance_(pol, qp, vza, vaz, m: int, weight: float, top_R_pm, top_J0_p
         dw = (I - A B)^-1 (a + A c),   uw = (I - B A)^-1 (c + B a)  [= c + B dw]
     with A = top_R_pm, a = top_J0_p (S, N[, N]), B = bot_R_mp ((S | 1, N, N): one block shared by every point is bot_stride 0),
     c = bot_J0_m.  dw_full / uw_full: (S, N) tensors that receive the level vectors at all streams."""
-    S, N = int(top_J0_p.shape[0]), int(top_J0_p.shape[1])
-    if S == 0:
+    setup = level_call_setup(pol, qp, vza, vaz, m, weight, top_J0_p, bot_R_mp)
+    if setup is None:
         return
-    dt = top_J0_p.dtype
-    row0, w = CR._vza_rows_weights(pol, vza, vaz, qp, m, weight, dt)
-    bot_stride = 0 if int(bot_R_mp.shape[0]) == 1 and S > 1 else N * N
+    S, N, dt, row0, w, bot_stride = setup
     oplevel = oplevel or LEVEL_OPLEVEL
     work = None
     if oplevel or N > LEVEL_FUSED_MAX_N:
@@ -80,10 +91,25 @@ def level_radiance_(pol, qp, vza, vaz, m: int, weight: float, top_R_pm, top_J0_p
               P(dw), P(dw_full), P(uw_full), P(work), CR._stream_ptr())
 
 
+def level_pair_(pol, qp, vza, vaz, m: int, weight: float, top, bot_R_mp, bot_J0_m, out, second, shape2, streams: bool):
+    """The level of the Raman and linearized runs: the elastic call (top[0], top[1] = R+-, J0+ of the top) into out[0], out[1],
+    then second(dwf, uwf, dw2, uw2), the flavour's call on the elastic level vectors (S, N), with dw2 / uw2 `shape2` tensors for
+    its own level vectors if `streams`, else None.  Returns (uwf, dwf, uw2, dw2)."""
+    a = top[1]
+    S, N = int(a.shape[0]), int(a.shape[1])
+    new = lambda *sh: torch.empty(sh, dtype=a.dtype, device=a.device)
+    dwf, uwf = new(S, N), new(S, N)
+    level_radiance_(pol, qp, vza, vaz, m, weight, top[0], a, bot_R_mp, bot_J0_m, out[0], out[1], dwf, uwf)
+    dw2, uw2 = (new(*shape2), new(*shape2)) if streams else (None, None)
+    second(dwf, uwf, dw2, uw2)
+    return uwf, dwf, uw2, dw2
+
+
 @dataclass
 class MultiSensorResult:
     """rt_run_multisensor(..., streams=True): per entry of sensor_levels the VZA outputs and, per Fourier moment, the level vectors
-    at ALL quadrature streams (the arrays postprocessing_vza_ms! reads its rows from: tuwJ / tdwJ [N, 1, nSpec])."""
+    at ALL quadrature streams (the arrays postprocessing_vza_ms! reads its rows from: tuwJ / tdwJ [N, 1, nSpec]).  The Raman and
+    linearized results add their own fields to these."""
     levels: List[int]
     uw: List[np.ndarray]                 # [nVZA, nStokes, nSpec] per level, like rt_run_test_ms's uwJ
     dw: List[np.ndarray]
@@ -95,8 +121,25 @@ class MultiSensorResult:
     mu0: float
     pol_n: int
 
+    FIELDS = ("uw", "dw")                # the outputs of a run, in the order rt_run_multisensor returns them
 
-def _validate(model: H.RTModel, sensor_levels):
+
+@dataclass(frozen=True)
+class LevelPlan:
+    """Which levels a run computes and how the column splits into segments between them."""
+    levels: List[int]      # the caller's sensor_levels, validated
+    distinct: List[int]    # sorted, each once
+    interior: List[int]    # those with 0 < l < Nz
+    tops_at: List[int]     # the levels whose top composite is kept: interior, and Nz if asked for
+    ends: List[int]        # per interior level, the last layer of the segment below it (the next interior level, or Nz)
+    Nz: int
+
+    @property
+    def n_tops(self) -> int:
+        return len(self.tops_at)
+
+
+def _validate(model: H.RTModel, sensor_levels) -> LevelPlan:
     Nz = int(np.asarray(model.tau_rayl).shape[1])
     levels = []
     for l in sensor_levels:
@@ -112,7 +155,105 @@ def _validate(model: H.RTModel, sensor_levels):
     if other or not srcs:
         raise _lib.VSMError("rt_run_multisensor: SolarBeam is the only source of a multi-sensor run (the prototype passes F0 alone, "
                             "rt_kernel_multisensor.jl:21); got %r" % (other[0] if other else None,))
-    return levels, Nz
+    distinct = sorted(set(levels))
+    interior = [l for l in distinct if 0 < l < Nz]
+    return LevelPlan(levels, distinct, interior, interior + ([Nz] if Nz in distinct else []), interior[1:] + [Nz], Nz)
+
+
+def fourier_weight(FT, m: int):
+    return FT(0.5 / math.pi) if m == 0 else FT(1.0 / math.pi)
+
+
+def refuse_non_scattering(layers, FT, who: str, why: str):
+    eps2 = 2 * np.finfo(FT).eps
+    noscat = [iz + 1 for iz, ly in enumerate(layers) if ly["props"].max_tau_varpi <= eps2]
+    if noscat:
+        raise NotImplementedError("%s: layer %d does not scatter (tau * varpi <= 2 eps)%s" % (who, noscat[0], why))
+
+
+def walk_levels(plan: LevelPlan, segs, run_segment, join_surface, join_bottom, level):
+    """The levels of one moment below the top pass (steps 2.-4.): level Nz against the surface layer alone, then the interior
+    levels from the surface up, their bottoms on the two alternating segment composites `segs`.  The flavour supplies
+        run_segment(seg, first, end)        layers first+1 .. end into seg, the first a copy
+        join_surface(seg)                   seg (+) surface
+        join_bottom(seg, bot, first, end)   seg (+) bot, the previous bottom (layers end+1 .. Nz and the surface)
+        level(l, seg)                       the level call(s) of level l on the bottom seg; seg None: the surface layer alone"""
+    if plan.Nz in plan.distinct:
+        level(plan.Nz, None)
+    bot = None
+    for i, (l, end) in enumerate(reversed(list(zip(plan.interior, plan.ends)))):
+        seg = segs[i % 2]
+        run_segment(seg, l, end)
+        if bot is None:
+            join_surface(seg)
+        else:
+            join_bottom(seg, bot, l, end)
+        level(l, seg)
+        bot = seg
+
+
+def _expand_iq(v: torch.Tensor, n: int) -> torch.Tensor:
+    """(..., 2 Nquad) level vectors of the Stokes_IQ scene -> (..., n Nquad) with U = V = 0."""
+    lead, N2 = tuple(v.shape[:-1]), int(v.shape[-1])
+    out = torch.zeros(lead + (N2 // 2, n), dtype=v.dtype, device=v.device)
+    out[..., :2] = v.reshape(lead + (N2 // 2, 2))
+    return out.reshape(lead + (-1,))
+
+
+def merge_sub0(sub, n: int, out, full):
+    """m = 0 from the Stokes_IQ sub-scene: sub = (out, full, weights) of the whole algorithm run on it.  Its I, Q rows are copied
+    into every level of `out`, where the later moments accumulate on top; its level vectors, expanded to n components, are full[0]."""
+    sub_out, sub_full, _ = sub
+    for l, parts in sub_out.items():
+        for whole, part in zip(out[l], parts):
+            whole[..., :2, :].copy_(part)
+    if full is not None:
+        full[0] = {l: tuple(_expand_iq(v, n) for v in vs) for l, vs in sub_full[0].items()}
+
+
+def spectral_blocks(S_full: int, max_points, least: int = 1):
+    """The spectral axis in blocks of max_points points (None or >= S_full: one block, None); no block shorter than `least`: the
+    last one absorbs a shorter tail."""
+    if max_points is None or max_points >= S_full:
+        return [None]
+    bs = max(int(max_points), least)
+    blocks = [slice(b0, min(b0 + bs, S_full)) for b0 in range(0, S_full, bs)]
+    if len(blocks) > 1 and blocks[-1].stop - blocks[-1].start < least:
+        blocks[-2:] = [slice(blocks[-2].start, S_full)]
+    return blocks
+
+
+def gather_blocks(model: H.RTModel, plan: LevelPlan, blocks, run_block, who: str, streams: bool, result_cls):
+    """Run every block, bring its outputs to the host, join the blocks along the spectral axis and order the levels as the caller
+    gave them.  run_block(sl) -> ({level: outputs (S, nStokes, nVZA) / (P, S, nStokes, nVZA)}, {m: {level: level vectors (S, N) /
+    (P, S, N)}} or None, Fourier weights) of the block's own points, as many per level as result_cls.FIELDS.  Returns one list
+    per output ([nVZA, nStokes, nSpec(, P)] per entry of plan.levels), or, with `streams`, a result_cls."""
+    parts = []
+    weights = None
+    for sl in blocks:
+        out, full, weights = run_block(sl)
+        synchronize_if_gpu()
+        _lib.check_device_status(who)
+        res = {l: [to_host(t).transpose().copy() for t in out[l]] for l in plan.distinct}
+        vec = None
+        if streams:
+            vec = {m: {l: [to_host(v).transpose()[:, None].copy() for v in vs] for l, vs in fv.items()} for m, fv in full.items()}
+        parts.append((res, vec))
+        del out, full
+        if len(blocks) > 1:
+            torch.cuda.empty_cache()
+    cat = (lambda xs: xs[0]) if len(parts) == 1 else (lambda xs: np.concatenate(xs, axis=2))
+    nf = len(result_cls.FIELDS)
+    res = {l: [cat([p[0][l][i] for p in parts]) for i in range(nf)] for l in plan.distinct}
+    outs = tuple([res[l][i].copy() for l in plan.levels] for i in range(nf))
+    if not streams:
+        return outs
+    ms = sorted(parts[0][1])
+    st = [[[cat([p[1][m][l][i] for p in parts]) for m in ms] for l in plan.levels] for i in range(nf)]
+    qp = model.quad_points
+    return result_cls(levels=plan.levels, weight=weights, qp_mu=np.asarray(qp.qp_mu, dtype=model.float_type).copy(),
+                      i_mu0=int(qp.imu0) + 1, mu0=float(qp.mu0), pol_n=model.polarization_type.n,
+                      **dict(zip(result_cls.FIELDS, outs)), **{f + "_streams": x for f, x in zip(result_cls.FIELDS, st)})
 
 
 def _snapshot(comp: CR.CompositeLayer):
@@ -138,30 +279,25 @@ def _run_segment(scene: CR.Scene, mom, seg: CR.CompositeLayer, first: int, end: 
                       iz - first + 1, scene.F0, scene.FT, model.numerics, dtau=ly["dtau"], ndoubl=ly["nd"], work=scene.work)
 
 
-def _run(scene: CR.Scene, levels: List[int], streams: bool):
+def _run(scene: CR.Scene, plan: LevelPlan, streams: bool):
     model, pol, FT = scene.model, scene.pol, scene.FT
     Nz, N, S = scene.Nz, scene.N, scene.S
-    eps2 = 2 * np.finfo(FT).eps
-    noscat = [iz + 1 for iz, ly in enumerate(scene.moments[0]["layers"]) if ly["props"].max_tau_varpi <= eps2]
-    if noscat:
-        raise NotImplementedError(
-            "rt_run_multisensor: layer %d does not scatter (tau * varpi <= 2 eps).  rt_run keeps the reference's stale-j0+ "
-            "quirk there (DESIGN.md §6) while the prototype hard-codes scatter = true (rt_kernel_multisensor.jl:29), so the two "
-            "reference drivers disagree on such columns; columns with a non-scattering layer are not supported" % noscat[0])
-    distinct = sorted(set(levels))
-    interior = [l for l in distinct if 0 < l < Nz]
-    tops_at = interior + ([Nz] if Nz in distinct else [])
+    refuse_non_scattering(scene.moments[0]["layers"], FT, "rt_run_multisensor",
+                          ".  rt_run keeps the reference's stale-j0+ quirk there (DESIGN.md §6) while the prototype hard-codes "
+                          "scatter = true (rt_kernel_multisensor.jl:29), so the two reference drivers disagree on such columns; "
+                          "columns with a non-scattering layer are not supported")
+    tops_at = plan.tops_at
     dev, dt = scene.dev, scene.dt
     nV = len(model.vza)
     out = {l: (torch.zeros((S, pol.n, nV), dtype=dt, device=dev), torch.zeros((S, pol.n, nV), dtype=dt, device=dev))
-           for l in distinct if l != 0}
+           for l in plan.distinct if l != 0}
     out[0] = (scene.R_SFI, scene.T_SFI)
     full = {} if streams else None
     scene.R_SFI.zero_()
     scene.T_SFI.zero_()
     weights = []
     if S == 0:
-        return out, full, [float(FT(0.5 / math.pi) if m == 0 else FT(1.0 / math.pi)) for m in range(model.m_max + 1)]
+        return out, full, [float(fourier_weight(FT, m)) for m in range(model.m_max + 1)]
     scene.added.j0_p.zero_()
     # the moment groups of Scene.run (level 0 is then rt_run's result bit for bit), fewer where the tops would not fit the device
     sequential = not CR.MOMENT_BATCHING or CR.REFERENCE_ORDER
@@ -174,7 +310,7 @@ def _run(scene: CR.Scene, levels: List[int], streams: bool):
         nb = max(1, min(nb, int(0.5 * free // per_moment)))
     while len(scene._composites) < nb:
         scene._composites.append(CR.make_composite_layer(FT, scene.arch, (N, N), S))
-    segs = [CR.make_composite_layer(FT, scene.arch, (N, N), S) for _ in range(2 if interior else 0)]
+    segs = [CR.make_composite_layer(FT, scene.arch, (N, N), S) for _ in range(2 if plan.interior else 0)]
     native = scene._native_moments() if not CR.REFERENCE_ORDER else set()
     for c in scene._composites:
         c._sources_only = CR.REFERENCE_ORDER
@@ -211,36 +347,25 @@ def _run(scene: CR.Scene, levels: List[int], streams: bool):
                         tops[k][iz + 1] = _snapshot(comp)
             for k, (mom, comp) in enumerate(zip(group, comps)):
                 m = mom["m"]
-                weight = FT(0.5 / math.pi) if m == 0 else FT(1.0 / math.pi)
+                weight = fourier_weight(FT, m)
                 weights.append(float(weight))
                 fv = {}
                 asurf = scene.added_surface
                 CR.create_surface_layer_(model.surface, asurf, m, scene.dq, mom["tau_sum_surface"], rho=mom["rho"])
 
-                def level(l, bot_R_mp, bot_J0_m):
-                    A, a = tops[k][l]
+                def level(l, seg):
+                    A, a = tops[k].pop(l)
+                    bot_R_mp, bot_J0_m = (asurf.r_mp, asurf.j0_m) if seg is None else (seg.R_mp, seg.J0_m)
                     dwf = torch.empty((S, N), dtype=dt, device=dev) if streams else None
                     uwf = torch.empty((S, N), dtype=dt, device=dev) if streams else None
                     level_radiance_(pol, scene.qp, model.vza, model.vaz, m, float(weight), A, a, bot_R_mp, bot_J0_m, out[l][0],
                                     out[l][1], dwf, uwf)
                     if streams:
                         fv[l] = (uwf, dwf)
-                # 4. level Nz: the surface layer alone below it
-                if Nz in distinct:
-                    level(Nz, asurf.r_mp, asurf.j0_m)
-                # 2.-4. segments and bottoms from the surface up, one level call per interior level
-                bot = None
-                ends = interior[1:] + [Nz]
-                for i, (l, end) in enumerate(reversed(list(zip(interior, ends)))):
-                    seg = segs[i % 2]
-                    _run_segment(scene, mom, seg, l, end)
-                    if bot is None:
-                        CR.interaction_(mom["iface_surface"], seg, asurf, work=scene.work)
-                    else:
-                        CR.interaction_("11", seg, _CompositeAsAdded(bot), work=scene.work)
-                    level(l, seg.R_mp, seg.J0_m)
-                    bot = seg
-                    del tops[k][l]
+                # 2.-4. the levels below the top pass
+                walk_levels(plan, segs, lambda seg, first, end: _run_segment(scene, mom, seg, first, end),
+                            lambda seg: CR.interaction_(mom["iface_surface"], seg, asurf, work=scene.work),
+                            lambda seg, bot, first, end: CR.interaction_("11", seg, _CompositeAsAdded(bot), work=scene.work), level)
                 # level 0: rt_run's surface interaction and post-processing (no Cox-Munk single-scattering correction)
                 CR.interaction_(mom["iface_surface"], comp, asurf, work=scene.work)
                 CR.postprocessing_vza_(pol, comp, model.vza, model.vaz, scene.qp, m, float(weight), scene.R_SFI, scene.T_SFI)
@@ -271,22 +396,10 @@ def rt_run_multisensor(model: H.RTModel, sensor_levels, streams: bool = False):
 
     streams=True: a MultiSensorResult, which also carries the level vectors at all quadrature streams per moment.
     SolarBeam sources only; columns with a non-scattering layer raise NotImplementedError."""
-    levels, Nz = _validate(model, sensor_levels)
-    scene = CR.prepare_scene(model)
-    scene.compute_hdrf = False
-    out, full, weights = _run(scene, levels, bool(streams))
-    synchronize_if_gpu()
-    _lib.check_device_status("rt_run_multisensor")
-    host = lambda t: to_host(t).transpose(2, 1, 0).copy()
-    res = {l: (host(u), host(d)) for l, (u, d) in out.items()}
-    uw = [res[l][0].copy() for l in levels]
-    dw = [res[l][1].copy() for l in levels]
-    if not streams:
-        return uw, dw
-    vec = lambda t: to_host(t).T[:, None, :].copy()
-    ms = sorted(full) if full else []
-    qp = model.quad_points
-    return MultiSensorResult(levels, uw, dw, [[vec(full[m][l][0]) for m in ms] for l in levels],
-                             [[vec(full[m][l][1]) for m in ms] for l in levels], weights,
-                             np.asarray(qp.qp_mu, dtype=model.float_type).copy(), int(qp.imu0) + 1, float(qp.mu0),
-                             model.polarization_type.n)
+    plan = _validate(model, sensor_levels)
+
+    def run_block(_sl):
+        scene = CR.prepare_scene(model)
+        scene.compute_hdrf = False
+        return _run(scene, plan, bool(streams))
+    return gather_blocks(model, plan, [None], run_block, "rt_run_multisensor", bool(streams), MultiSensorResult)

@@ -23,7 +23,6 @@ linearized level call per level other than 0.
 from __future__ import annotations
 
 import ctypes as C
-import math
 from dataclasses import dataclass
 from typing import List, Optional
 
@@ -34,9 +33,7 @@ from . import _lib
 from . import core_rt as CR
 from . import core_rt_lin as CL
 from . import core_rt_ms as MS
-from .core_rt_ms_raman import _expand_iq
 from . import host_model as H
-from .architectures import synchronize_if_gpu, to_host
 
 LEVEL_LIN_MAX_N = 128   # vsm_level_radiance_lin_*: one workgroup per point; there is no operator-level twin
 
@@ -49,12 +46,10 @@ def level_radiance_lin_(pol, qp, vza, vaz, m: int, weight: float, P: int, P_top:
     A = top_R_pm (S, N, N), B = bot_R_mp ((S | 1, N, N)), dw_full / uw_full (S, N) the elastic level vectors; top_R_pm_lin /
     top_J0_p_lin (P_top, S, N[, N]) (slots >= P_top of the top are zero), bot_R_mp_lin ((P, S | 1, N, N)), bot_J0_m_lin (P, S, N).
     dw_lin_full / uw_lin_full: (P, S, N) tensors that receive the derivative vectors at all streams."""
-    S, N = int(dw_full.shape[0]), int(dw_full.shape[1])
-    if S == 0:
+    setup = MS.level_call_setup(pol, qp, vza, vaz, m, weight, dw_full, bot_R_mp)
+    if setup is None:
         return
-    dt = dw_full.dtype
-    row0, w = CR._vza_rows_weights(pol, vza, vaz, qp, m, weight, dt)
-    bot_stride = 0 if int(bot_R_mp.shape[0]) == 1 and S > 1 else N * N
+    S, N, dt, row0, w, bot_stride = setup
     sb = int(bot_R_mp_lin.shape[1])
     bd_stride = 0 if sb == 1 and S > 1 else N * N
     Pt = CR._ptr
@@ -65,117 +60,82 @@ def level_radiance_lin_(pol, qp, vza, vaz, m: int, weight: float, P: int, P_top:
 
 
 @dataclass
-class MultiSensorLinResult:
+class MultiSensorLinResult(MS.MultiSensorResult):
     """rt_run_multisensor(model, lin_model, ..., streams=True): per entry of sensor_levels the VZA outputs and their Jacobians and,
-    per Fourier moment, the level vectors and their derivatives at ALL quadrature streams."""
-    levels: List[int]
-    uw: List[np.ndarray]                   # [nVZA, nStokes, nSpec] per level
-    dw: List[np.ndarray]
-    uw_dot: List[np.ndarray]               # [nVZA, nStokes, nSpec, Nparams] per level
+    per Fourier moment, the level vectors and their derivatives at ALL quadrature streams: the fields of MultiSensorResult and"""
+    uw_dot: List[np.ndarray]                # [nVZA, nStokes, nSpec, Nparams] per level
     dw_dot: List[np.ndarray]
-    uw_streams: List[List[np.ndarray]]     # [level][moment] -> [N, 1, nSpec]
-    dw_streams: List[List[np.ndarray]]
     uw_dot_streams: List[List[np.ndarray]]  # [level][moment] -> [N, 1, nSpec, Nparams]
     dw_dot_streams: List[List[np.ndarray]]
-    weight: List[float]                    # Fourier weight per moment
-    qp_mu: np.ndarray
-    i_mu0: int                             # 1-based, like StreamRTResult
-    mu0: float
-    pol_n: int
+
+    FIELDS = ("uw", "dw", "uw_dot", "dw_dot")
 
 
-def _refuse_non_scattering(sc: CL.SceneLin):
-    eps2 = 2 * np.finfo(sc.FT).eps
-    noscat = [iz + 1 for iz, ly in enumerate(sc.fwd.moments[0]["layers"]) if ly["props"].max_tau_varpi <= eps2]
-    if noscat:
-        raise NotImplementedError(
-            "rt_run_multisensor (linearized): layer %d does not scatter (tau * varpi <= 2 eps); columns with a non-scattering "
-            "layer are not supported (as for CoreRT.rt_run_multisensor)" % noscat[0])
-
-
-def _run_scene(sc: CL.SceneLin, levels: List[int], streams: bool):
+def _run_scene(sc: CL.SceneLin, plan: MS.LevelPlan, streams: bool):
     """The linearized multi-sensor algorithm on one SceneLin.  Returns ({level: [uw, dw, uw_dot, dw_dot]} of (S, nStokes, nVZA) /
     (P, S, nStokes, nVZA) device tensors, {m: {level: (uw, dw, uw_dot, dw_dot) (S, N) / (P, S, N)}} or None, the Fourier weights)."""
     model, fwd, FT, dt = sc.model, sc.fwd, sc.FT, sc.dt
     pol, qp = sc.pol, sc.qp
-    Nz, N, S, P, pl = fwd.Nz, sc.N, sc.S, sc.P, sc.pl
-    distinct = sorted(set(levels))
-    interior = [l for l in distinct if 0 < l < Nz]
-    tops_at = set(interior + ([Nz] if Nz in distinct else []))
+    N, S, P, pl = sc.N, sc.S, sc.P, sc.pl
     w = sc._lane_state(0)
     torch._foreach_zero_([w["R"], w["T"], w["Rd"], w["Td"]])
     dev = sc.R.device
     nV = len(model.vza)
     z = lambda *sh: torch.zeros(sh, dtype=dt, device=dev)
-    out = {l: [z(S, pol.n, nV), z(S, pol.n, nV), z(P, S, pol.n, nV), z(P, S, pol.n, nV)] for l in distinct if l != 0}
+    out = {l: [z(S, pol.n, nV), z(S, pol.n, nV), z(P, S, pol.n, nV), z(P, S, pol.n, nV)] for l in plan.distinct if l != 0}
     out[0] = [sc.R, sc.T, sc.Rd, sc.Td]
     full = {} if streams else None
-    weights = [float(FT(0.5 / math.pi) if m == 0 else FT(1.0 / math.pi)) for m in range(model.m_max + 1)]
+    weights = [float(MS.fourier_weight(FT, m)) for m in range(model.m_max + 1)]
     if S == 0:
         return out, full, weights
     reduced = sc.sub0 is not None
-    if reduced:      # m = 0 first, like SceneLin.run: the I, Q rows of the Stokes_IQ scene, the later moments accumulate on top
-        sub_out, sub_full, _ = _run_scene(sc.sub0, levels, streams)
-        for l in distinct:
-            for k, (whole, part) in enumerate(zip(out[l], sub_out[l])):
-                (whole[:, :2, :] if k < 2 else whole[:, :, :2, :]).copy_(part)
-        if streams:
-            full[0] = {l: tuple(_expand_iq(v, pol.n) for v in vs) for l, vs in sub_full[0].items()}
+    if reduced:      # m = 0 first, like SceneLin.run
+        MS.merge_sub0(_run_scene(sc.sub0, plan, streams), pol.n, out, full)
     segs = [(CR.make_composite_layer(FT, sc.arch, (N, N), S), CL.CompositeLayerLin(FT, sc.arch, P, N, S))
-            for _ in range(2 if interior else 0)]
+            for _ in range(2 if plan.interior else 0)]
     for mom in fwd.moments:
         m = mom["m"]
         if m == 0 and reduced:
             continue
-        weight = FT(0.5 / math.pi) if m == 0 else FT(1.0 / math.pi)
+        weight = float(MS.fourier_weight(FT, m))
         fv = {}
         tops = {}
 
         def keep(l, comp, cl):
-            if l in tops_at:
+            if l in plan.tops_at:
                 tops[l] = (comp.R_pm.clone(), comp.J0_p.clone(), cl.R_pm[:pl].clone(), cl.J0_p[:pl].clone())
 
         # 1. the top pass, level 0 included (its surface layer stays in w["added_s"] / w["als"] for the bottoms)
         sc._run_moment(mom, w, after_layer=keep)
         if streams:
             fv[0] = (w["comp"].J0_m.clone(), w["comp"].J0_p.clone(), w["cl"].J0_m.clone(), w["cl"].J0_p.clone())
-
-        def level(l, bot_R_mp, bot_J0_m, bot_R_mp_lin, bot_J0_m_lin):
-            A, a, Ad, ad = tops.pop(l)
-            dwf = torch.empty((S, N), dtype=dt, device=dev)
-            uwf = torch.empty((S, N), dtype=dt, device=dev)
-            MS.level_radiance_(pol, qp, model.vza, model.vaz, m, float(weight), A, a, bot_R_mp, bot_J0_m, out[l][0], out[l][1],
-                               dwf, uwf)
-            dwdf = torch.empty((P, S, N), dtype=dt, device=dev) if streams else None
-            uwdf = torch.empty((P, S, N), dtype=dt, device=dev) if streams else None
-            level_radiance_lin_(pol, qp, model.vza, model.vaz, m, float(weight), P, pl, A, bot_R_mp, dwf, uwf, Ad, ad, bot_R_mp_lin,
-                                bot_J0_m_lin, out[l][2], out[l][3], dwdf, uwdf)
-            if streams:
-                fv[l] = (uwf, dwf, uwdf, dwdf)
-
-        # 4. level Nz: the surface layer alone below it
         asurf, als = w["added_s"], w["als"]
-        if Nz in distinct:
-            level(Nz, asurf.r_mp, asurf.j0_m, als.ap_r_mp, als.ap_J0_m)
-        # 2.-4. linearized segments and bottoms from the surface up, the level calls of each interior level
-        bot = None
-        ends = interior[1:] + [Nz]
-        for i, (l, end) in enumerate(reversed(list(zip(interior, ends)))):
-            seg, segl = segs[i % 2]
-            for iz in range(l, end):
+
+        def run_segment(seg, first, end):
+            for iz in range(first, end):
                 sc._double_layer(mom, iz, w)
-                if iz == l:
-                    CR.copy_added_to_composite_(seg, w["added"])
-                    a_, c_ = w["al"].cstruct(), segl.cstruct()
+                if iz == first:
+                    CR.copy_added_to_composite_(seg[0], w["added"])
+                    a_, c_ = w["al"].cstruct(), seg[1].cstruct()
                     _lib.call("vsm_copy_added_to_composite_lin", dt, N, S, C.byref(a_), C.byref(c_), CR._stream_ptr())
                 else:
-                    CL.interaction_lin_(mom["layers"][iz]["iface"], seg, segl, w["added"], w["al"], p_range=sc._layer_slots)
-            if bot is None:
-                CL.interaction_lin_(mom["iface_surface"], seg, segl, asurf, als)
-            else:
-                CL.interaction_lin_("11", seg, segl, CL._CompositeAsAdded(bot[0]), CL._CompositeLinAsAdded(bot[1]))
-            level(l, seg.R_mp, seg.J0_m, segl.R_mp, segl.J0_m)
-            bot = (seg, segl)
+                    CL.interaction_lin_(mom["layers"][iz]["iface"], seg[0], seg[1], w["added"], w["al"], p_range=sc._layer_slots)
+
+        def level(l, seg):
+            top = tops.pop(l)
+            bot = (asurf.r_mp, asurf.j0_m, als.ap_r_mp, als.ap_J0_m) if seg is None else (seg[0].R_mp, seg[0].J0_m, seg[1].R_mp,
+                                                                                          seg[1].J0_m)
+            vs = MS.level_pair_(pol, qp, model.vza, model.vaz, m, weight, top, bot[0], bot[1], out[l],
+                                lambda dwf, uwf, dwdf, uwdf: level_radiance_lin_(
+                                    pol, qp, model.vza, model.vaz, m, weight, P, pl, top[0], bot[0], dwf, uwf, top[2], top[3],
+                                    bot[2], bot[3], out[l][2], out[l][3], dwdf, uwdf), (P, S, N), streams)
+            if streams:
+                fv[l] = vs
+        # 2.-4. linearized segments and bottoms from the surface up, the level calls of each level
+        MS.walk_levels(plan, segs, run_segment,
+                       lambda seg: CL.interaction_lin_(mom["iface_surface"], seg[0], seg[1], asurf, als),
+                       lambda seg, bot, first, end: CL.interaction_lin_("11", seg[0], seg[1], CL._CompositeAsAdded(bot[0]),
+                                                                        CL._CompositeLinAsAdded(bot[1])), level)
         if streams:
             full[m] = fv
     return out, full, weights
@@ -207,23 +167,20 @@ def rt_run_multisensor(model: H.RTModel, lin_model: H.LinModel, NAer: int, NGas:
     independent, ndoubl and the interface tags come from the full axis; a block has at least SceneLin.LANE_POINTS points where the
     axis has, so that the m = 0 sub-scene applies alike); None = as many as fit the device.
     SolarBeam sources only; columns with a non-scattering layer raise NotImplementedError; N <= 128."""
-    levels, Nz = MS._validate(model, sensor_levels)
+    plan = MS._validate(model, sensor_levels)
     qp, pol = model.quad_points, model.polarization_type
     N = qp.Nquad * pol.n
     if N > LEVEL_LIN_MAX_N:
         raise _lib.VSMError("rt_run_multisensor (linearized): N = %d streams x Stokes components > %d, the limit of the linearized "
                             "level kernel (vsm_level_radiance_lin_*)" % (N, LEVEL_LIN_MAX_N))
     S_full = int(np.asarray(model.tau_rayl).shape[0])
-    distinct = sorted(set(levels))
-    interior = [l for l in distinct if 0 < l < Nz]
-    n_tops = len(interior) + (1 if Nz in distinct else 0)
     if max_points is None and S_full > 0:
         layout = H.ParameterLayout(n_aerosols=NAer, n_gases=NGas, n_surface=NSurf)
         P, pl = layout.n_total, layout.n_layer_params
         isz, nV = np.dtype(model.float_type).itemsize, len(model.vza)
-        per = bytes_per_point(N, P, pl, Nz, n_tops, bool(interior), len(distinct), pol.n, nV, isz)
+        per = bytes_per_point(N, P, pl, plan.Nz, plan.n_tops, bool(plan.interior), len(plan.distinct), pol.n, nV, isz)
         if CL.REDUCE_M0 and pol.n >= 3:     # (the Stokes_IQ scene of m = 0, where it applies)
-            per += bytes_per_point(2 * qp.Nquad, P, pl, Nz, n_tops, bool(interior), len(distinct), 2, nV, isz)
+            per += bytes_per_point(2 * qp.Nquad, P, pl, plan.Nz, plan.n_tops, bool(plan.interior), len(plan.distinct), 2, nV, isz)
         free, _total = torch.cuda.mem_get_info()
         fit = int(0.5 * free // per)
         if fit < S_full:
@@ -231,43 +188,14 @@ def rt_run_multisensor(model: H.RTModel, lin_model: H.LinModel, NAer: int, NGas:
                 raise _lib.VSMError("rt_run_multisensor (linearized): not even one spectral point fits the device (%d bytes per "
                                     "point)" % per)
             max_points = fit
-    if max_points is None or max_points >= S_full:
-        blocks = [None]
-    else:
-        # SceneLin takes the Stokes_IQ sub-scene of m = 0 only for batches of at least LANE_POINTS points: where the whole axis
-        # has that many, so does every block (the last one absorbs a shorter tail), or the blocks would round differently
-        bs = int(max_points)
-        least = CL.SceneLin.LANE_POINTS if S_full >= CL.SceneLin.LANE_POINTS else 1
-        bs = max(bs, least)
-        blocks = [slice(b0, min(b0 + bs, S_full)) for b0 in range(0, S_full, bs)]
-        if len(blocks) > 1 and blocks[-1].stop - blocks[-1].start < least:
-            blocks[-2:] = [slice(blocks[-2].start, S_full)]
-    parts = []
-    weights = None
-    for sl in blocks:
+    # SceneLin takes the Stokes_IQ sub-scene of m = 0 only for batches of at least LANE_POINTS points: where the whole axis has
+    # that many, so does every block, or the blocks would round differently
+    least = CL.SceneLin.LANE_POINTS if S_full >= CL.SceneLin.LANE_POINTS else 1
+
+    def run_block(sl):
         sc = CL.SceneLin(model, lin_model, NAer, NGas, NSurf, spec_slice=sl)
-        _refuse_non_scattering(sc)
-        out, full, weights = _run_scene(sc, levels, bool(streams))
-        synchronize_if_gpu()
-        _lib.check_device_status("rt_run_multisensor (linearized)")
-        h3 = lambda t: to_host(t).transpose(2, 1, 0).copy()
-        h4 = lambda t: to_host(t).transpose(3, 2, 1, 0).copy()
-        res = {l: [h3(out[l][0]), h3(out[l][1]), h4(out[l][2]), h4(out[l][3])] for l in distinct}
-        vec = None
-        if streams:
-            v3 = lambda t: to_host(t).T[:, None, :].copy()
-            v4 = lambda t: to_host(t).transpose(2, 1, 0)[:, None].copy()
-            vec = {m: {l: [v3(vs[0]), v3(vs[1]), v4(vs[2]), v4(vs[3])] for l, vs in fv.items()} for m, fv in full.items()}
-        parts.append((res, vec))
-        del sc, out, full
-        if len(blocks) > 1:
-            torch.cuda.empty_cache()
-    cat = (lambda xs: xs[0]) if len(parts) == 1 else (lambda xs: np.concatenate(xs, axis=2))
-    res = {l: [cat([p[0][l][i] for p in parts]) for i in range(4)] for l in distinct}
-    outs = tuple([res[l][i].copy() for l in levels] for i in range(4))
-    if not streams:
-        return outs
-    ms = sorted(parts[0][1])
-    st = [[[cat([p[1][m][l][i] for p in parts]) for m in ms] for l in levels] for i in range(4)]
-    return MultiSensorLinResult(levels, *outs, *st, weights, np.asarray(qp.qp_mu, dtype=model.float_type).copy(), int(qp.imu0) + 1,
-                                float(qp.mu0), pol.n)
+        MS.refuse_non_scattering(sc.fwd.moments[0]["layers"], sc.FT, "rt_run_multisensor (linearized)",
+                                 "; columns with a non-scattering layer are not supported (as for CoreRT.rt_run_multisensor)")
+        return _run_scene(sc, plan, bool(streams))
+    return MS.gather_blocks(model, plan, MS.spectral_blocks(S_full, max_points, least), run_block,
+                            "rt_run_multisensor (linearized)", bool(streams), MultiSensorLinResult)

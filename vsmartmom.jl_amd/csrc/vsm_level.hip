@@ -30,23 +30,18 @@ struct level_pp {
   double w[256];
 };
 
-// Steps 1-3 for ONE point: [M | d] = [I - A B | a + A c] into L, Gauss-Jordan, dw -> xs, uw = c + B dw -> ys, then dw_full /
-// uw_full [N,1,S] (nullable) and the VZA rows accumulated into uw / dw.  Shared by the elastic level kernel and the inelastic one
-// (vsm_level_radiance_ie_*), which hands over its line sums (r, q) from LDS as (a, c).  The whole workgroup enters; sh: 2 ints of
-// LDS (pivot row, non-finite flag).
+// The two halves of every fused level kernel, on [M | r_1 .. r_{NC-N}] in L (row-major, leading dimension LD >= NC).  The whole
+// workgroup enters both; sh: 2 ints of LDS (pivot row, non-finite flag).
+
+// [M | r] = [I | s] - [A B | -A q]: 16 x 16 output tiles over the N x NC block, round-robin over the four waves, ONE MFMA product
+// (the q ride as the spare columns N .. NC-1 of B).  Before the barrier that precedes the call: the q in Q [NC - N][N], the s in
+// columns N .. NC-1 of L, sh[1] = 0.
 template <typename T>
-__device__ __forceinline__ void level_solve_point(int N, int ns, int nV, int nVtot, const level_pp& pa, long long s, const T* As,
-                                                  const T* as_, const T* Bs, const T* cs, T* L, T* xs, T* ys, T* uw, T* dw,
-                                                  T* dw_full, T* uw_full, int* sh, int* status) {
-  const int LD = N + 1;
-  int& s_piv = sh[0];
+__device__ __forceinline__ void level_form_system(int N, int NC, int LD, const T* As, const T* Bs, const T* Q, T* L, int* sh,
+                                                  int* status) {
   int& s_flag = sh[1];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, kq = lane >> 4;
-  if (tid == 0) s_flag = 0;
-  __syncthreads();
-
-  // 1. [M | d] = [I | a] - [A B | -A c]: 16 x 16 output tiles over the N x (N + 1) block, round-robin over the four waves
-  const int MT = (N + 15) / 16, CT = (N + 16) / 16;
+  const int MT = (N + 15) / 16, CT = (NC + 15) / 16;
   bool bad = false;
   for (int t = wave; t < MT * CT; t += LEVEL_NT / 64) {
     const int ti = t / CT, tj = t % CT;
@@ -55,15 +50,15 @@ __device__ __forceinline__ void level_solve_point(int N, int ns, int nV, int nVt
     for (int k0 = 0; k0 < N; k0 += 4) {
       const int k = k0 + kq;
       const T av = (row < N && k < N) ? As[(long long)k * N + row] : T(0);
-      const T bv = (k < N) ? (col < N ? Bs[(long long)col * N + k] : (col == N ? cs[k] : T(0))) : T(0);
+      const T bv = (k < N) ? (col < N ? Bs[(long long)col * N + k] : (col < NC ? Q[(col - N) * N + k] : T(0))) : T(0);
       acc = mfma<T>::mma(av, bv, acc);
     }
     const int ocol = 16 * tj + li;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int orow = 16 * ti + mfma<T>::crow(lane, r);
-      if (orow < N && ocol <= N) {
-        const T v = ocol < N ? ((orow == ocol ? T(1) : T(0)) - acc[r]) : as_[orow] + acc[r];
+      if (orow < N && ocol < NC) {
+        const T v = ocol < N ? ((orow == ocol ? T(1) : T(0)) - acc[r]) : L[orow * LD + ocol] + acc[r];
         bad |= !isfinite(v);
         L[orow * LD + ocol] = v;
       }
@@ -72,8 +67,14 @@ __device__ __forceinline__ void level_solve_point(int N, int ns, int nV, int nVt
   if (bad) s_flag = 1;
   __syncthreads();
   if (s_flag && tid == 0) atomicOr(&status[0], (int)VSM_DEVSTAT_NONFINITE);
+}
 
-  // 2. Gauss-Jordan elimination of [M | d]: row k is the pivot row of step k and is not normalised; dw_i = d_i / m_ii at the end
+// Gauss-Jordan elimination of [M | r] over NC columns, the pivot rule of vsm_inverse.h (largest |m_ik|, first occurrence): row k
+// is the pivot row of step k and is not normalised; the solutions are r_i / m_ii afterwards.
+template <typename T>
+__device__ __forceinline__ void level_eliminate(int N, int NC, int LD, T* L, int* sh, int* status) {
+  int& s_piv = sh[0];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int tj = tid & 63, ti = tid >> 6;
   for (int k = 0; k < N; ++k) {
     if (wave == 0) {
@@ -88,7 +89,7 @@ __device__ __forceinline__ void level_solve_point(int N, int ns, int nV, int nVt
     __syncthreads();
     const int p = s_piv;
     if (p != k) {
-      for (int j = k + tid; j <= N; j += LEVEL_NT) {
+      for (int j = k + tid; j < NC; j += LEVEL_NT) {
         const T tmp = L[k * LD + j];
         L[k * LD + j] = L[p * LD + j];
         L[p * LD + j] = tmp;
@@ -101,10 +102,23 @@ __device__ __forceinline__ void level_solve_point(int N, int ns, int nV, int nVt
     for (int i = ti; i < N; i += LEVEL_NT / 64) {
       if (i == k) continue;
       const T f = L[i * LD + k] * inv;
-      for (int j = k + 1 + tj; j <= N; j += 64) L[i * LD + j] -= f * L[k * LD + j];
+      for (int j = k + 1 + tj; j < NC; j += 64) L[i * LD + j] -= f * L[k * LD + j];
     }
     __syncthreads();
   }
+}
+
+// Steps 1-3 for ONE point with one right-hand side (elastic and inelastic kernel): [M | d] = [I - A B | a + A c], Gauss-Jordan,
+// dw -> xs, uw = c + B dw -> ys, then dw_full / uw_full [N,1,S] (nullable) and the VZA rows accumulated into uw / dw.  Before the
+// barrier that precedes the call: a in column N of L, c in cs (LDS; cs may be ys: thread i reads c_i before it writes uw_i),
+// sh[1] = 0.
+template <typename T>
+__device__ __forceinline__ void level_solve_point(int N, int ns, int nV, int nVtot, const level_pp& pa, long long s, const T* As,
+                                                  const T* Bs, const T* cs, T* L, T* xs, T* ys, T* uw, T* dw, T* dw_full,
+                                                  T* uw_full, int* sh, int* status) {
+  const int LD = N + 1, tid = threadIdx.x;
+  level_form_system<T>(N, N + 1, LD, As, Bs, cs, L, sh, status);
+  level_eliminate<T>(N, N + 1, LD, L, sh, status);
   for (int i = tid; i < N; i += LEVEL_NT) xs[i] = L[i * LD + N] / L[i * LD + i];
   __syncthreads();
 
@@ -134,19 +148,68 @@ __global__ void __launch_bounds__(LEVEL_NT) k_level_radiance(int N, int ns, int 
   extern __shared__ __align__(16) unsigned char lds_raw[];
   T* L = reinterpret_cast<T*>(lds_raw);          // [M | d], row-major, leading dimension LD = N + 1
   T* xs = L + (size_t)N * (N + 1);               // dw
-  T* ys = xs + N;                                // uw
+  T* ys = xs + N;                                // c, then uw
   __shared__ int sh[2];
   const long long s = blockIdx.x;
-  level_solve_point<T>(N, ns, nV, nVtot, pa, s, A + s * (long long)N * N, a + s * N, B + s * bstride, c + s * N, L, xs, ys, uw, dw,
-                       dw_full, uw_full, sh, status);
+  if (threadIdx.x == 0) sh[1] = 0;
+  for (int i = threadIdx.x; i < N; i += LEVEL_NT) {
+    L[i * (N + 1) + N] = a[s * N + i];
+    ys[i] = c[s * N + i];
+  }
+  __syncthreads();
+  level_solve_point<T>(N, ns, nV, nVtot, pa, s, A + s * (long long)N * N, B + s * bstride, ys, L, xs, ys, uw, dw, dw_full, uw_full,
+                       sh, status);
+}
+
+// The column-group streaming of the inelastic and the linearized kernel.  Thread (g, i) = (tid / N, tid % N) of the G = 256 / N
+// column groups takes row i of columns j = g, g + G, ... of a block [M | v] (column N = the vector, taken by the group next in
+// turn), so the workgroup reads G consecutive columns, G N contiguous elements, per step.  level_stream_pair adds [M1 | v1] x1 to
+// s1 and [M2 | v2] x2 to s2 (M2 == nullptr: no second block); level_stream_reduce adds the per-group partial sums in group order
+// (part: [2][G][N] of LDS) and writes row i of the two sums to d1[i ld1] and d2[i ld2].  The whole workgroup enters the reduction.
+template <typename T>
+struct level_sums {
+  T s1, s2;
+};
+
+template <typename T>
+__device__ __forceinline__ level_sums<T> level_stream_pair(int N, int G, int g, int i, const T* M1, const T* v1, const T* x1,
+                                                           const T* M2, const T* v2, const T* x2, level_sums<T> acc) {
+  for (int j = g; j < N; j += G) {
+    acc.s1 += M1[(long long)j * N + i] * x1[j];
+    if (M2) acc.s2 += M2[(long long)j * N + i] * x2[j];
+  }
+  if (g == (N % G)) {
+    acc.s1 += v1[i];
+    if (M2) acc.s2 += v2[i];
+  }
+  return acc;
+}
+
+template <typename T>
+__device__ __forceinline__ void level_stream_reduce(int N, int G, int g, int i, level_sums<T> acc, T* part, T* d1, int ld1, T* d2,
+                                                    int ld2) {
+  const int tid = threadIdx.x;
+  if (g < G) {
+    part[g * N + i] = acc.s1;
+    part[(G + g) * N + i] = acc.s2;
+  }
+  __syncthreads();
+  if (tid < N) {
+    T t1 = T(0), t2 = T(0);
+    for (int h = 0; h < G; ++h) {
+      t1 += part[h * N + tid];
+      t2 += part[(G + h) * N + tid];
+    }
+    d1[tid * ld1] = t1;
+    d2[tid * ld2] = t2;
+  }
+  __syncthreads();
 }
 
 // The inelastic level equation (vsm_level_radiance_ie_*) of recipient point n1 = blockIdx.x, lines summed before the solve:
 //   q = sum_k [c_ie,k + B_ie,k dw(n0)],  r = sum_k [a_ie,k + A_ie,k uw(n0)] + A q,  dw_ie = (I - A B)^-1 r,  uw_ie = q + B dw_ie
 // over the in-band lines k (n0 = n1 + shift[k] in 0..S-1); dw / uw are the ELASTIC level vectors of the donors.
-// Phase 1 streams the 2K ie blocks of the point: thread (g, i) = (tid / N, tid % N) of G = 256 / N column groups takes row i of
-// columns j = g, g + G, ... (column N = the vector), so the workgroup reads G consecutive columns, G N contiguous elements, per
-// step; the per-group partial sums are added in group order in LDS.  Phase 2 is level_solve_point with (a, c) = (r - A q, q).
+// Phase 1 streams the 2K ie blocks of the point by column groups; phase 2 is level_solve_point with (a, c) = (r - A q, q).
 template <typename T>
 __global__ void __launch_bounds__(LEVEL_NT) k_level_radiance_ie(int N, int ns, int S, int K, const int* __restrict__ shift, int nV,
                                                                 int nVtot, level_pp pa, const T* __restrict__ A,
@@ -160,48 +223,49 @@ __global__ void __launch_bounds__(LEVEL_NT) k_level_radiance_ie(int N, int ns, i
   T* xs = L + (size_t)N * (N + 1);               // dw_ie
   T* ys = xs + N;                                // uw_ie
   T* qs = ys + N;                                // q
-  T* ps = qs + N;                                // sum_k [a_ie + A_ie uw(n0)]
-  T* part = ps + N;                              // [2][G][N] partial sums
+  T* part = qs + N;                              // [2][G][N] partial sums
   __shared__ int sh[2];
   const int tid = threadIdx.x;
   const int n1 = blockIdx.x;
   const long long NN = (long long)N * N;
   const int G = LEVEL_NT / N, g = tid / N, i = tid - g * N;
-  T sp = T(0), sq = T(0);
+  level_sums<T> acc = {T(0), T(0)};
+  if (tid == 0) sh[1] = 0;
   if (g < G) {
     for (int k = 0; k < K; ++k) {
       const int n0 = n1 + shift[k];
       if (n0 < 0 || n0 >= S) continue;
       const long long blk = (long long)k * S + n1;
-      const T* Ak = Aie + blk * NN;
-      const T* Bk = Bie ? Bie + blk * NN : nullptr;
-      const T* u0 = uwf + (long long)n0 * N;
-      const T* d0 = dwf + (long long)n0 * N;
-      for (int j = g; j < N; j += G) {
-        sp += Ak[(long long)j * N + i] * u0[j];
-        if (Bk) sq += Bk[(long long)j * N + i] * d0[j];
-      }
-      if (g == (N % G)) {                          // column N: the vectors, taken by the group next in turn
-        sp += aie[blk * N + i];
-        if (cie) sq += cie[blk * N + i];
-      }
+      acc = level_stream_pair<T>(N, G, g, i, Aie + blk * NN, aie + blk * N, uwf + (long long)n0 * N, Bie ? Bie + blk * NN : nullptr,
+                                 cie ? cie + blk * N : nullptr, dwf + (long long)n0 * N, acc);
     }
-    part[g * N + i] = sp;
-    part[(G + g) * N + i] = sq;
   }
-  __syncthreads();
-  if (tid < N) {
-    T p = T(0), q = T(0);
-    for (int h = 0; h < G; ++h) {
-      p += part[h * N + tid];
-      q += part[(G + h) * N + tid];
-    }
-    ps[tid] = p;
-    qs[tid] = q;
+  level_stream_reduce<T>(N, G, g, i, acc, part, L + N, N + 1, qs, 1);
+  level_solve_point<T>(N, ns, nV, nVtot, pa, n1, A + n1 * NN, B + n1 * bstride, qs, L, xs, ys, uwie, dwie, dwie_full, uwie_full, sh,
+                       status);
+}
+
+// The VZA table of one launch and what to do above the 64 viewing angles it carries: the level vectors in full (the caller's
+// buffers, or scratch for full_elems each), a launch with nV = 0, then the VZA rows by post(uw_full, dw_full).
+// launch(nV, pa, dw_full, uw_full) launches the kernel and returns its launch status.
+template <typename T, typename Launch, typename Post>
+static int level_launch(int ns, int nV, const int* row0_h, const T* w_h, size_t full_elems, T* dw_full, T* uw_full, hipStream_t st,
+                        Launch launch, Post post) {
+  level_pp pa = {};
+  if (nV <= 64) {
+    for (int v = 0; v < nV; ++v) pa.row0[v] = row0_h[v];
+    for (int k = 0; k < ns; ++k)
+      for (int v = 0; v < nV; ++v) pa.w[v + nV * k] = (double)w_h[v + nV * k];
+    return launch(nV, pa, dw_full, uw_full);
   }
-  __syncthreads();
-  level_solve_point<T>(N, ns, nV, nVtot, pa, n1, A + n1 * NN, ps, B + n1 * bstride, qs, L, xs, ys, uwie, dwie, dwie_full, uwie_full,
-                       sh, status);
+  if (!dw_full || !uw_full) {
+    T* full = static_cast<T*>(scratch(2 * full_elems * sizeof(T), 0, st));
+    if (!full) return VSM_ERR_HIP;
+    if (!dw_full) dw_full = full;
+    if (!uw_full) uw_full = full + full_elems;
+  }
+  const int rc = launch(0, pa, dw_full, uw_full);
+  return rc ? rc : post(uw_full, dw_full);
 }
 
 template <typename T>
@@ -212,27 +276,15 @@ static int level_radiance_fused(int N, int ns, int S, int nV, const int* row0_h,
   const size_t lds = ((size_t)N * (N + 1) + 2 * (size_t)N) * sizeof(T);
   const int rc = ensure_dyn_lds(reinterpret_cast<const void*>(k_level_radiance<T>), lds, "hipFuncSetAttribute(k_level_radiance)");
   if (rc) return rc;
-  level_pp pa = {};
-  if (nV <= 64) {
-    for (int v = 0; v < nV; ++v) pa.row0[v] = row0_h[v];
-    for (int k = 0; k < ns; ++k)
-      for (int v = 0; v < nV; ++v) pa.w[v + nV * k] = (double)w_h[v + nV * k];
-    hipLaunchKernelGGL(k_level_radiance<T>, dim3(S), dim3(LEVEL_NT), lds, st, N, ns, nV, nV, pa, A, a, B, bstride, c, uw, dw,
-                       dw_full, uw_full, status);
-    VSM_LAUNCH_CHECK("k_level_radiance");
-    return VSM_OK;
-  }
-  // more than the 64 viewing angles one launch carries: the level vectors in full, then the VZA rows by vsm_postprocess_vza
-  T* full = dw_full && uw_full ? nullptr : static_cast<T*>(scratch(2 * (size_t)N * S * sizeof(T), 0, st));
-  if (!dw_full || !uw_full) {
-    if (!full) return VSM_ERR_HIP;
-    if (!dw_full) dw_full = full;
-    if (!uw_full) uw_full = full + (size_t)N * S;
-  }
-  hipLaunchKernelGGL(k_level_radiance<T>, dim3(S), dim3(LEVEL_NT), lds, st, N, ns, 0, 0, pa, A, a, B, bstride, c, uw, dw, dw_full,
-                     uw_full, status);
-  VSM_LAUNCH_CHECK("k_level_radiance");
-  return postprocess_vza<T>(N, ns, S, nV, row0_h, w_h, uw_full, dw_full, uw, dw, st);
+  return level_launch<T>(
+      ns, nV, row0_h, w_h, (size_t)N * S, dw_full, uw_full, st,
+      [&](int nv, const level_pp& pa, T* dwf, T* uwf) {
+        hipLaunchKernelGGL(k_level_radiance<T>, dim3(S), dim3(LEVEL_NT), lds, st, N, ns, nv, nv, pa, A, a, B, bstride, c, uw, dw, dwf,
+                           uwf, status);
+        VSM_LAUNCH_CHECK("k_level_radiance");
+        return (int)VSM_OK;
+      },
+      [&](const T* uwf, const T* dwf) { return postprocess_vza<T>(N, ns, S, nV, row0_h, w_h, uwf, dwf, uw, dw, st); });
 }
 
 template <typename T>
@@ -241,42 +293,28 @@ static int level_radiance_ie_fused(int N, int ns, int S, int K, const int* shift
                                    const T* Bie, const T* cie, T* uwie, T* dwie, T* dwie_full, T* uwie_full, hipStream_t st) {
   int* status = device_status();
   if (!status) return VSM_ERR_HIP;
-  const size_t lds = ((size_t)N * (N + 1) + 4 * (size_t)N + 2 * (size_t)LEVEL_NT) * sizeof(T);
+  const size_t lds = ((size_t)N * (N + 1) + 3 * (size_t)N + 2 * (size_t)LEVEL_NT) * sizeof(T);
   const int rc = ensure_dyn_lds(reinterpret_cast<const void*>(k_level_radiance_ie<T>), lds, "hipFuncSetAttribute(k_level_radiance_ie)");
   if (rc) return rc;
-  level_pp pa = {};
-  if (nV <= 64) {
-    for (int v = 0; v < nV; ++v) pa.row0[v] = row0_h[v];
-    for (int k = 0; k < ns; ++k)
-      for (int v = 0; v < nV; ++v) pa.w[v + nV * k] = (double)w_h[v + nV * k];
-    hipLaunchKernelGGL(k_level_radiance_ie<T>, dim3(S), dim3(LEVEL_NT), lds, st, N, ns, S, K, shift, nV, nV, pa, A, B, bstride, dwf,
-                       uwf, Aie, aie, Bie, cie, uwie, dwie, dwie_full, uwie_full, status);
-    VSM_LAUNCH_CHECK("k_level_radiance_ie");
-    return VSM_OK;
-  }
-  // more than the 64 viewing angles one launch carries: the level vectors in full, then the VZA rows by vsm_postprocess_vza
-  T* full = dwie_full && uwie_full ? nullptr : static_cast<T*>(scratch(2 * (size_t)N * S * sizeof(T), 0, st));
-  if (!dwie_full || !uwie_full) {
-    if (!full) return VSM_ERR_HIP;
-    if (!dwie_full) dwie_full = full;
-    if (!uwie_full) uwie_full = full + (size_t)N * S;
-  }
-  hipLaunchKernelGGL(k_level_radiance_ie<T>, dim3(S), dim3(LEVEL_NT), lds, st, N, ns, S, K, shift, 0, 0, pa, A, B, bstride, dwf, uwf,
-                     Aie, aie, Bie, cie, uwie, dwie, dwie_full, uwie_full, status);
-  VSM_LAUNCH_CHECK("k_level_radiance_ie");
-  return postprocess_vza<T>(N, ns, S, nV, row0_h, w_h, uwie_full, dwie_full, uwie, dwie, st);
+  return level_launch<T>(
+      ns, nV, row0_h, w_h, (size_t)N * S, dwie_full, uwie_full, st,
+      [&](int nv, const level_pp& pa, T* df, T* uf) {
+        hipLaunchKernelGGL(k_level_radiance_ie<T>, dim3(S), dim3(LEVEL_NT), lds, st, N, ns, S, K, shift, nv, nv, pa, A, B, bstride,
+                           dwf, uwf, Aie, aie, Bie, cie, uwie, dwie, df, uf, status);
+        VSM_LAUNCH_CHECK("k_level_radiance_ie");
+        return (int)VSM_OK;
+      },
+      [&](const T* uf, const T* df) { return postprocess_vza<T>(N, ns, S, nV, row0_h, w_h, uf, df, uwie, dwie, st); });
 }
 
 // The derivative of the level equation (vsm_level_radiance_lin_*) at point s = blockIdx.x, for every parameter p:
 //   q_p = c'_p + B'_p dw,   r_p = a'_p + A'_p uw + A q_p,   dw'_p = (I - A B)^-1 r_p,   uw'_p = q_p + B dw'_p
 // with dw / uw the elastic level vectors of the point (vsm_level_radiance_* dw_full / uw_full).  The parameters run in chunks of
 // PC; per chunk:
-//   1. the bottom blocks B'_p, c'_p (every slot) and the top blocks A'_p, a'_p (slots < P_top) streamed by the column groups of
-//      k_level_radiance_ie (thread (g, i) of G = 256 / N groups, column N = the vector, partial sums added in group order):
+//   1. the bottom blocks B'_p, c'_p (every slot) and the top blocks A'_p, a'_p (slots < P_top) streamed by column groups:
 //      q_p -> Q[pc], s_p = a'_p + A'_p uw -> column N + pc of L;
-//   2. [M | r_1 .. r_PC] = [I - A B | s + A q] in ONE MFMA product (the q_p ride as extra columns of B, as c does in the elastic
-//      kernel), then ONE Gauss-Jordan elimination of the whole block with the pivot rule of level_solve_point (same M, same rule:
-//      the elastic call's pivots);
+//   2. [M | r_1 .. r_PC] = [I - A B | s + A q] (level_form_system), then ONE Gauss-Jordan elimination of the whole block
+//      (level_eliminate: same M, same rule as the elastic call, hence its pivots);
 //   3. dw'_p = column / m_ii (in place), uw'_p = q_p + B dw'_p (into Q), the VZA rows ACCUMULATED into [P, S, n_stokes, nV].
 // LDS: L [N][N + PC], Q [PC][N], dw / uw [2][N], partial sums [2][G][N].
 template <typename T>
@@ -295,9 +333,7 @@ __global__ void __launch_bounds__(LEVEL_NT) k_level_radiance_lin(int N, int ns, 
   T* ys = xs + N;                                // uw
   T* part = ys + N;                              // [2][G][N] partial sums
   __shared__ int sh[2];
-  int& s_piv = sh[0];
-  int& s_flag = sh[1];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, kq = lane >> 4;
+  const int tid = threadIdx.x;
   const long long s = blockIdx.x;
   const long long NN = (long long)N * N, SN = (long long)S * N;
   const T* As = A + s * NN;
@@ -309,99 +345,22 @@ __global__ void __launch_bounds__(LEVEL_NT) k_level_radiance_lin(int N, int ns, 
   }
   for (int p0 = 0; p0 < P; p0 += PC) {
     const int pc_n = P - p0 < PC ? P - p0 : PC;
-    if (tid == 0) s_flag = 0;
+    if (tid == 0) sh[1] = 0;
     __syncthreads();   // (dw / uw loaded; the previous chunk's outputs read L and Q)
     // 1. q_p and s_p of the chunk
     for (int pc = 0; pc < pc_n; ++pc) {
       const int p = p0 + pc;
-      if (g < G) {
-        const bool top = p < P_top;
-        const T* Bk = Bd + p * bd_pstride + s * bd_stride;
-        const T* Ak = top ? Ad + p * ad_pstride + s * NN : nullptr;
-        T sq = T(0), sp = T(0);
-        for (int j = g; j < N; j += G) {
-          sq += Bk[(long long)j * N + i1] * xs[j];
-          if (top) sp += Ak[(long long)j * N + i1] * ys[j];
-        }
-        if (g == (N % G)) {                          // column N: the vectors, taken by the group next in turn
-          sq += cd[p * SN + s * N + i1];
-          if (top) sp += ad[p * SN + s * N + i1];
-        }
-        part[g * N + i1] = sq;
-        part[(G + g) * N + i1] = sp;
-      }
-      __syncthreads();
-      if (tid < N) {
-        T q = T(0), sp = T(0);
-        for (int h = 0; h < G; ++h) {
-          q += part[h * N + tid];
-          sp += part[(G + h) * N + tid];
-        }
-        Q[pc * N + tid] = q;
-        L[tid * LD + N + pc] = sp;
-      }
-      __syncthreads();
+      const bool top = p < P_top;
+      level_sums<T> acc = {T(0), T(0)};
+      if (g < G)
+        acc = level_stream_pair<T>(N, G, g, i1, Bd + p * bd_pstride + s * bd_stride, cd + p * SN + s * N, xs,
+                                   top ? Ad + p * ad_pstride + s * NN : nullptr, top ? ad + p * SN + s * N : nullptr, ys, acc);
+      level_stream_reduce<T>(N, G, g, i1, acc, part, Q + pc * N, 1, L + N + pc, LD);
     }
-    // 2. [M | r] = [I | s] - [A B | -A q]: 16 x 16 output tiles over the N x (N + pc_n) block, round-robin over the four waves
+    // 2. [M | r] and its elimination
     const int NC = N + pc_n;
-    const int MT = (N + 15) / 16, CT = (NC + 15) / 16;
-    bool bad = false;
-    for (int t = wave; t < MT * CT; t += LEVEL_NT / 64) {
-      const int ti = t / CT, tj = t % CT;
-      const int row = 16 * ti + li, col = 16 * tj + li;
-      typename mfma<T>::acc_t acc = acc_zero<T>();
-      for (int k0 = 0; k0 < N; k0 += 4) {
-        const int k = k0 + kq;
-        const T av = (row < N && k < N) ? As[(long long)k * N + row] : T(0);
-        const T bv = (k < N) ? (col < N ? Bs[(long long)col * N + k] : (col < NC ? Q[(col - N) * N + k] : T(0))) : T(0);
-        acc = mfma<T>::mma(av, bv, acc);
-      }
-      const int ocol = 16 * tj + li;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int orow = 16 * ti + mfma<T>::crow(lane, r);
-        if (orow < N && ocol < NC) {
-          const T v = ocol < N ? ((orow == ocol ? T(1) : T(0)) - acc[r]) : L[orow * LD + ocol] + acc[r];
-          bad |= !isfinite(v);
-          L[orow * LD + ocol] = v;
-        }
-      }
-    }
-    if (bad) s_flag = 1;
-    __syncthreads();
-    if (s_flag && tid == 0) atomicOr(&status[0], (int)VSM_DEVSTAT_NONFINITE);
-    // Gauss-Jordan elimination of [M | r]: the pivot rule and row operations of level_solve_point over NC columns
-    const int tj = tid & 63, ti = tid >> 6;
-    for (int k = 0; k < N; ++k) {
-      if (wave == 0) {
-        const bool in0 = lane >= k && lane < N, in1 = lane + 64 >= k && lane + 64 < N;
-        const T v0 = in0 ? fabs(L[lane * LD + k]) : T(-1);
-        const T v1 = in1 ? fabs(L[(lane + 64) * LD + k]) : T(-1);
-        const T best = wave_max(v0 > v1 ? v0 : v1);
-        const unsigned long long m0 = __ballot(in0 && v0 == best), m1 = __ballot(in1 && v1 == best);
-        const int p = m0 ? (__ffsll((long long)m0) - 1) : (m1 ? 64 + __ffsll((long long)m1) - 1 : k);
-        if (lane == 0) s_piv = p;
-      }
-      __syncthreads();
-      const int p = s_piv;
-      if (p != k) {
-        for (int j = k + tid; j < NC; j += LEVEL_NT) {
-          const T tmp = L[k * LD + j];
-          L[k * LD + j] = L[p * LD + j];
-          L[p * LD + j] = tmp;
-        }
-        __syncthreads();
-      }
-      const T pv = L[k * LD + k];
-      if (pv == T(0) && tid == 0) atomicOr(&status[0], (int)VSM_DEVSTAT_SINGULAR);
-      const T inv = T(1) / pv;
-      for (int i = ti; i < N; i += LEVEL_NT / 64) {
-        if (i == k) continue;
-        const T f = L[i * LD + k] * inv;
-        for (int j = k + 1 + tj; j < NC; j += 64) L[i * LD + j] -= f * L[k * LD + j];
-      }
-      __syncthreads();
-    }
+    level_form_system<T>(N, NC, LD, As, Bs, Q, L, sh, status);
+    level_eliminate<T>(N, NC, LD, L, sh, status);
     // 3. dw'_p = r_p / m_ii (in place: each element is read and written by its own thread), then uw'_p = q_p + B dw'_p
     for (int e = tid; e < N * pc_n; e += LEVEL_NT) {
       const int i = e % N, pc = e / N;
@@ -437,11 +396,6 @@ static int level_lin_chunk(int N, int P) {
 }
 
 template <typename T>
-static size_t level_lin_lds(int N, int PC) {
-  return ((size_t)N * (N + PC) + (size_t)PC * N + 2 * (size_t)N + 2 * (size_t)LEVEL_NT) * sizeof(T);
-}
-
-template <typename T>
 static int level_radiance_lin_fused(int N, int ns, int S, int P, int P_top, int nV, const int* row0_h, const T* w_h, const T* A,
                                     const T* B, long long bstride, const T* dwf, const T* uwf, const T* Ad, long long ad_pstride,
                                     const T* ad, const T* Bd, long long bd_stride, long long bd_pstride, const T* cd, T* uwd,
@@ -449,30 +403,18 @@ static int level_radiance_lin_fused(int N, int ns, int S, int P, int P_top, int 
   int* status = device_status();
   if (!status) return VSM_ERR_HIP;
   const int PC = level_lin_chunk<T>(N, P);
-  const size_t lds = level_lin_lds<T>(N, PC);
+  const size_t lds = ((size_t)N * (N + PC) + (size_t)PC * N + 2 * (size_t)N + 2 * (size_t)LEVEL_NT) * sizeof(T);
   const int rc = ensure_dyn_lds(reinterpret_cast<const void*>(k_level_radiance_lin<T>), lds, "hipFuncSetAttribute(k_level_radiance_lin)");
   if (rc) return rc;
-  level_pp pa = {};
-  if (nV <= 64) {
-    for (int v = 0; v < nV; ++v) pa.row0[v] = row0_h[v];
-    for (int k = 0; k < ns; ++k)
-      for (int v = 0; v < nV; ++v) pa.w[v + nV * k] = (double)w_h[v + nV * k];
-    hipLaunchKernelGGL(k_level_radiance_lin<T>, dim3(S), dim3(LEVEL_NT), lds, st, N, ns, S, P, P_top, PC, nV, pa, A, B, bstride, dwf,
-                       uwf, Ad, ad_pstride, ad, Bd, bd_stride, bd_pstride, cd, uwd, dwd, dwd_full, uwd_full, status);
-    VSM_LAUNCH_CHECK("k_level_radiance_lin");
-    return VSM_OK;
-  }
-  // more than the 64 viewing angles one launch carries: the derivative vectors in full, then the VZA rows by postprocess_vza_lin
-  T* full = dwd_full && uwd_full ? nullptr : static_cast<T*>(scratch(2 * (size_t)P * N * S * sizeof(T), 0, st));
-  if (!dwd_full || !uwd_full) {
-    if (!full) return VSM_ERR_HIP;
-    if (!dwd_full) dwd_full = full;
-    if (!uwd_full) uwd_full = full + (size_t)P * N * S;
-  }
-  hipLaunchKernelGGL(k_level_radiance_lin<T>, dim3(S), dim3(LEVEL_NT), lds, st, N, ns, S, P, P_top, PC, 0, pa, A, B, bstride, dwf, uwf,
-                     Ad, ad_pstride, ad, Bd, bd_stride, bd_pstride, cd, uwd, dwd, dwd_full, uwd_full, status);
-  VSM_LAUNCH_CHECK("k_level_radiance_lin");
-  return postprocess_vza_lin<T>(N, ns, S, nV, P, row0_h, w_h, uwd_full, dwd_full, uwd, dwd, st);
+  return level_launch<T>(
+      ns, nV, row0_h, w_h, (size_t)P * N * S, dwd_full, uwd_full, st,
+      [&](int nv, const level_pp& pa, T* df, T* uf) {
+        hipLaunchKernelGGL(k_level_radiance_lin<T>, dim3(S), dim3(LEVEL_NT), lds, st, N, ns, S, P, P_top, PC, nv, pa, A, B, bstride,
+                           dwf, uwf, Ad, ad_pstride, ad, Bd, bd_stride, bd_pstride, cd, uwd, dwd, df, uf, status);
+        VSM_LAUNCH_CHECK("k_level_radiance_lin");
+        return (int)VSM_OK;
+      },
+      [&](const T* uf, const T* df) { return postprocess_vza_lin<T>(N, ns, S, nV, P, row0_h, w_h, uf, df, uwd, dwd, st); });
 }
 
 // operator-level twin: M = I - A B, d = a + A c (two batched products), dw = M^-1 d (vsm_batch_inv + product), uw = c + B dw
@@ -494,16 +436,26 @@ static int level_radiance_oplevel(int N, int ns, int S, int nV, const int* row0_
   return rc;
 }
 
+// What every level entry point checks of its sizes, bot_stride and viewing-angle table (max_N = 0: any N)
+template <typename T>
+static int level_check_common(const char* who, int N, int max_N, int ns, int S, int nV, const int* row0_h, const T* w_h,
+                              long long bstride, const T* uw, const T* dw) {
+  VSM_REQUIRE(N > 0 && ns >= 1 && ns <= 4 && N % ns == 0 && S >= 0 && nV >= 0, "%s: bad size (N %d, n_stokes %d, S %d, nV %d)", who, N,
+              ns, S, nV);
+  VSM_REQUIRE(max_N == 0 || N <= max_N, "%s: N = %d > %d, the limit of its kernel", who, N, max_N);
+  VSM_REQUIRE(bstride == 0 || bstride == (long long)N * N, "%s: bot_stride must be 0 or N*N", who);
+  VSM_REQUIRE(S == 0 || nV == 0 || (row0_h && w_h && uw && dw), "%s: null output / viewing-angle table", who);
+  for (int v = 0; v < nV; ++v)
+    VSM_REQUIRE(row0_h[v] >= 0 && row0_h[v] + ns <= N, "%s: row0[%d] = %d outside the %d streams", who, v, row0_h[v], N);
+  return VSM_OK;
+}
+
 template <typename T>
 static int level_check(int N, int ns, int S, int nV, const int* row0_h, const T* w_h, const T* A, const T* a, const T* B,
                        long long bstride, const T* c, T* uw, T* dw) {
-  VSM_REQUIRE(N > 0 && ns >= 1 && ns <= 4 && N % ns == 0 && S >= 0 && nV >= 0, "level_radiance: bad size (N %d, n_stokes %d, S %d, nV %d)",
-              N, ns, S, nV);
-  VSM_REQUIRE(bstride == 0 || bstride == (long long)N * N, "level_radiance: bot_stride must be 0 or N*N");
+  const int rc = level_check_common<T>("level_radiance", N, 0, ns, S, nV, row0_h, w_h, bstride, uw, dw);
+  if (rc) return rc;
   VSM_REQUIRE(S == 0 || (A && a && B && c), "level_radiance: null operand");
-  VSM_REQUIRE(S == 0 || nV == 0 || (row0_h && w_h && uw && dw), "level_radiance: null output / viewing-angle table");
-  for (int v = 0; v < nV; ++v)
-    VSM_REQUIRE(row0_h[v] >= 0 && row0_h[v] + ns <= N, "level_radiance: row0[%d] = %d outside the %d streams", v, row0_h[v], N);
   return VSM_OK;
 }
 
@@ -511,15 +463,12 @@ template <typename T>
 static int level_ie_check(int N, int ns, int S, int K, const int* shift, int nV, const int* row0_h, const T* w_h, const T* A,
                           const T* B, long long bstride, const T* dwf, const T* uwf, const T* Aie, const T* aie, const T* Bie,
                           const T* cie, T* uwie, T* dwie) {
-  VSM_REQUIRE(N > 0 && N <= LEVEL_FUSED_MAX_N && ns >= 1 && ns <= 4 && N % ns == 0 && S >= 0 && K >= 0 && nV >= 0,
-              "level_radiance_ie: bad size (N %d <= %d, n_stokes %d, S %d, K %d, nV %d)", N, LEVEL_FUSED_MAX_N, ns, S, K, nV);
-  VSM_REQUIRE(bstride == 0 || bstride == (long long)N * N, "level_radiance_ie: bot_stride must be 0 or N*N");
+  const int rc = level_check_common<T>("level_radiance_ie", N, LEVEL_FUSED_MAX_N, ns, S, nV, row0_h, w_h, bstride, uwie, dwie);
+  if (rc) return rc;
+  VSM_REQUIRE(K >= 0, "level_radiance_ie: bad size (K %d)", K);
   VSM_REQUIRE(S == 0 || (A && B && dwf && uwf), "level_radiance_ie: null elastic operand");
   VSM_REQUIRE(S == 0 || K == 0 || (shift && Aie && aie), "level_radiance_ie: null shift / top inelastic operand");
   VSM_REQUIRE((Bie == nullptr) == (cie == nullptr), "level_radiance_ie: bot_ieR_mp and bot_ieJ0_m are both given or both NULL");
-  VSM_REQUIRE(S == 0 || nV == 0 || (row0_h && w_h && uwie && dwie), "level_radiance_ie: null output / viewing-angle table");
-  for (int v = 0; v < nV; ++v)
-    VSM_REQUIRE(row0_h[v] >= 0 && row0_h[v] + ns <= N, "level_radiance_ie: row0[%d] = %d outside the %d streams", v, row0_h[v], N);
   return VSM_OK;
 }
 
@@ -527,19 +476,15 @@ template <typename T>
 static int level_lin_check(int N, int ns, int S, int P, int P_top, int nV, const int* row0_h, const T* w_h, const T* A, const T* B,
                            long long bstride, const T* dwf, const T* uwf, const T* Ad, long long ad_pstride, const T* ad,
                            const T* Bd, long long bd_stride, long long bd_pstride, const T* cd, T* uwd, T* dwd) {
-  VSM_REQUIRE(N > 0 && N <= LEVEL_FUSED_MAX_N && ns >= 1 && ns <= 4 && N % ns == 0 && S >= 0 && nV >= 0,
-              "level_radiance_lin: bad size (N %d <= %d, n_stokes %d, S %d, nV %d)", N, LEVEL_FUSED_MAX_N, ns, S, nV);
+  const int rc = level_check_common<T>("level_radiance_lin", N, LEVEL_FUSED_MAX_N, ns, S, nV, row0_h, w_h, bstride, uwd, dwd);
+  if (rc) return rc;
   VSM_REQUIRE(P >= 1 && P <= 64 && P_top >= 0 && P_top <= P, "level_radiance_lin: bad parameter count (P %d in 1..64, P_top %d in 0..P)",
               P, P_top);
-  VSM_REQUIRE(bstride == 0 || bstride == (long long)N * N, "level_radiance_lin: bot_stride must be 0 or N*N");
   VSM_REQUIRE(bd_stride == 0 || bd_stride == (long long)N * N, "level_radiance_lin: bot_lin_stride must be 0 or N*N");
   VSM_REQUIRE(bd_pstride >= (bd_stride ? (long long)S * N * N : (long long)N * N) && (P_top == 0 || ad_pstride >= (long long)S * N * N),
               "level_radiance_lin: a per-parameter stride is shorter than one parameter's blocks");
   VSM_REQUIRE(S == 0 || (A && B && dwf && uwf && Bd && cd), "level_radiance_lin: null operand");
   VSM_REQUIRE(S == 0 || P_top == 0 || (Ad && ad), "level_radiance_lin: null top derivative operand");
-  VSM_REQUIRE(S == 0 || nV == 0 || (row0_h && w_h && uwd && dwd), "level_radiance_lin: null output / viewing-angle table");
-  for (int v = 0; v < nV; ++v)
-    VSM_REQUIRE(row0_h[v] >= 0 && row0_h[v] + ns <= N, "level_radiance_lin: row0[%d] = %d outside the %d streams", v, row0_h[v], N);
   return VSM_OK;
 }
 
