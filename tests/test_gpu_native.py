@@ -64,7 +64,21 @@ def test_stokes_coupling_of_the_fourier_moments(vsm, arch, pol, ns):
 def test_native_layout_import_export_roundtrip(vsm, arch, ns, nq, coupling):
     """vsm_run_import / vsm_run_export: reference layout -> native strips -> reference layout is the identity on composites whose
     uncoupled blocks are zero (what a run under that coupling produces); the blocks between the groups come back as zeros."""
+    _import_export_roundtrip(vsm, arch, ns, nq, coupling, np.float64)
+
+
+@pytest.mark.parametrize("ns,nq,coupling", [(3, 20, -1), (3, 20, 0x33 | 0x400), (4, 9, 0x33 | 0xCC00), (1, 7, -1), (3, 4, 0x33),
+                                             (4, 15, 0x8033), (2, 30, -1), (1, 120, -1)])
+def test_native_layout_import_export_roundtrip_float32(vsm, arch, ns, nq, coupling):
+    """The same round trip through the FP32 records (vsm_run_import_f32 / vsm_run_export_f32), and a block of 120 rows (eight row
+    tiles) that only the FP32 family takes."""
+    _import_export_roundtrip(vsm, arch, ns, nq, coupling, np.float32)
+
+
+def _import_export_roundtrip(vsm, arch, ns, nq, coupling, FT):
     L = vsm._lib.lib()
+    f32 = FT == np.float32
+    tdt = torch.float32 if f32 else torch.float64
     N, S = ns * nq, 5
     rng = np.random.default_rng(3)
     dev = "cuda:0"
@@ -77,25 +91,26 @@ def test_native_layout_import_export_roundtrip(vsm, arch, ns, nq, coupling):
     mask = np.tile(same, (nq, nq))                                    # [i, j]: rows / columns interleave the Stokes components
     mats = [rng.standard_normal((S, N, N)) * mask.T[None] for _ in range(4)]   # device tensors hold [s, j, i]
     vecs = [rng.standard_normal((S, N)) for _ in range(2)]
-    comp_in = vsm.CoreRT.make_composite_layer(np.float64, arch, (N, N), S)
-    comp_out = vsm.CoreRT.make_composite_layer(np.float64, arch, (N, N), S)
+    comp_in = vsm.CoreRT.make_composite_layer(FT, arch, (N, N), S)
+    comp_out = vsm.CoreRT.make_composite_layer(FT, arch, (N, N), S)
     for t, a in zip((comp_in.R_mp, comp_in.R_pm, comp_in.T_pp, comp_in.T_mm, comp_in.J0_p, comp_in.J0_m), mats + vecs):
-        t.copy_(torch.as_tensor(a, device=dev))
+        t.copy_(torch.as_tensor(a.astype(FT), device=dev))
     for t in (comp_out.R_mp, comp_out.R_pm, comp_out.T_pp, comp_out.T_mm, comp_out.J0_p, comp_out.J0_m):
         t.fill_(float("nan"))
-    assert L.vsm_run_supported(N, ns, coupling) == 1
+    assert (L.vsm_run_supported_f32 if f32 else L.vsm_run_supported)(N, ns, coupling) == 1
     carr, marr = (C.c_int * 1)(coupling), (C.c_int * 1)(0)
-    nbytes = int(L.vsm_run_workspace_bytes(N, ns, S, 1, carr))
+    nbytes = int((L.vsm_run_workspace_bytes_f32 if f32 else L.vsm_run_workspace_bytes)(N, ns, S, 1, carr))
     assert nbytes > 0
-    ws = torch.full((nbytes // 8,), float("nan"), dtype=torch.float64, device=dev)
-    mu = torch.ones(N, dtype=torch.float64, device=dev)
-    q = vsm._lib.vsm_quad_f64(mu.data_ptr(), mu.data_ptr(), N, ns, 0, 1.0)
+    ws = torch.full((nbytes // np.dtype(FT).itemsize,), float("nan"), dtype=tdt, device=dev)
+    mu = torch.ones(N, dtype=tdt, device=dev)
+    q = (vsm._lib.vsm_quad_f32 if f32 else vsm._lib.vsm_quad_f64)(mu.data_ptr(), mu.data_ptr(), N, ns, 0, 1.0)
     run = C.c_void_p()
-    vsm._lib.check(L.vsm_run_create_f64(C.byref(q), S, 1, marr, carr, C.c_void_p(ws.data_ptr()), nbytes, C.byref(run)))
+    create = L.vsm_run_create_f32 if f32 else L.vsm_run_create_f64
+    vsm._lib.check(create(C.byref(q), S, 1, marr, carr, C.c_void_p(ws.data_ptr()), nbytes, C.byref(run)))
     try:
         ci, co = (type(comp_in.cstruct()) * 1)(comp_in.cstruct()), (type(comp_out.cstruct()) * 1)(comp_out.cstruct())
-        vsm._lib.check(L.vsm_run_import_f64(run, ci, None))
-        vsm._lib.check(L.vsm_run_export_f64(run, co, None))
+        vsm._lib.check((L.vsm_run_import_f32 if f32 else L.vsm_run_import_f64)(run, ci, None))
+        vsm._lib.check((L.vsm_run_export_f32 if f32 else L.vsm_run_export_f64)(run, co, None))
         torch.cuda.synchronize()
     finally:
         L.vsm_run_destroy(run)
@@ -442,13 +457,34 @@ def test_native_run_diagonal_steps_of_rayleigh_layers_at_high_moments(vsm, arch,
     block there (only the two diagonals of T change while the composite is still diagonal; a scaling of the composite below the first
     aerosol layer), and U at m = 0 is a diagonal step in every layer -- rt_run equals the oracle (which forms every product, like
     the reference) and the reference-layout layer loop."""
+    Rn, Tn, Rl, Tl, Ro, To = _diagonal_steps_scene(vsm, arch, monkeypatch, pol, l_trunc, np.float64)
+    assert _rel(Rn, Ro) < 1e-8 and _rel(Tn, To) < 1e-8, (_rel(Rn, Ro), _rel(Tn, To))
+    assert _rel(Rn, Rl) < 1e-10 and _rel(Tn, Tl) < 1e-10
+
+
+@pytest.mark.parametrize("pol,l_trunc", [("IQU", 35), ("I", 15)])
+def test_native_run_diagonal_steps_of_rayleigh_layers_at_high_moments_float32(vsm, arch, monkeypatch, pol, l_trunc):
+    """The same scene as a Float32 model: the diagonal steps of the FP32 records (all three modes), within the gates of
+    test_native_run_float32_models -- 1e-2 against the oracle's Float32 run (the reference's own FP32 gate), 2e-3 against the Float32
+    kernels of the reference-layout layer loop.  Measured on the commit before the two families
+    shared one diagonal-step kernel (R, T): IQU 35: 6.0e-5, 1.1e-4 against the oracle, 2.5e-7, 1.3e-6 against the reference layout;
+    I 15: 8.4e-5, 1.1e-4 and 3.3e-7, 1.1e-6."""
+    Rn, Tn, Rl, Tl, Ro, To = _diagonal_steps_scene(vsm, arch, monkeypatch, pol, l_trunc, np.float32)
+    assert Rn.dtype == np.float32
+    print("diagonal steps f32 %s %d: vs oracle %.3e %.3e, vs reference layout %.3e %.3e"
+          % (pol, l_trunc, _rel(Rn, Ro), _rel(Tn, To), _rel(Rn, Rl), _rel(Tn, Tl)))
+    assert _rel(Rn, Ro) < 1e-2 and _rel(Tn, To) < 1e-2, (_rel(Rn, Ro), _rel(Tn, To))
+    assert _rel(Rn, Rl) < 2e-3 and _rel(Tn, Tl) < 2e-3, (_rel(Rn, Rl), _rel(Tn, Tl))
+
+
+def _diagonal_steps_scene(vsm, arch, monkeypatch, pol, l_trunc, FT):
     H = vsm.host_model
     rng = np.random.default_rng(53)
     S, L = 6, 6
     tau_aer = np.array([[0.0, 0.0, 0.0, 0.15, 0.0, 0.25]])       # Rayleigh | Rayleigh | Rayleigh | mixed | Rayleigh | mixed
     kw = dict(tau_rayl=np.tile(np.linspace(0.02, 0.12, L), (S, 1)), tau_abs=10.0 ** rng.uniform(-3, -0.5, (S, L)), depol=0.03,
               albedo=0.15, m_max=7, tau_aer=tau_aer)
-    model = H.model_from_arrays(arch, pol, l_trunc, 40.0, [30.0], [0.0],
+    model = H.model_from_arrays(arch, pol, l_trunc, 40.0, [30.0], [0.0], float_type=FT,
                                 aerosol_optics=[H.AerosolOptics(H.GreekCoefs(**vars(O.hg_greek(0.7, 10))), 0.95, 0.0)], **kw)
     monkeypatch.setattr(vsm.CoreRT, "NATIVE_RUN", True)
     sc = vsm.CoreRT.prepare_scene(model)
@@ -463,9 +499,9 @@ def test_native_run_diagonal_steps_of_rayleigh_layers_at_high_moments(vsm, arch,
     monkeypatch.setattr(vsm.CoreRT, "NATIVE_RUN", False)
     Rl, Tl = vsm.CoreRT.rt_run(model)
     monkeypatch.setattr(vsm.CoreRT, "NATIVE_RUN", True)
-    Ro, To = O.rt_run(O.build_model(pol, l_trunc, 40.0, [30.0], [0.0], aerosols=[O.AerosolOptics(O.hg_greek(0.7, 10), 0.95, 0.0)], **kw))
-    assert _rel(Rn, Ro) < 1e-8 and _rel(Tn, To) < 1e-8, (_rel(Rn, Ro), _rel(Tn, To))
-    assert _rel(Rn, Rl) < 1e-10 and _rel(Tn, Tl) < 1e-10
+    Ro, To = O.rt_run(O.build_model(pol, l_trunc, 40.0, [30.0], [0.0], aerosols=[O.AerosolOptics(O.hg_greek(0.7, 10), 0.95, 0.0)], FT=FT,
+                                    **kw))
+    return Rn, Tn, Rl, Tl, Ro, To
 
 
 @pytest.mark.parametrize("N,ns", [(1, 1), (3, 3), (9, 3), (13, 1), (16, 4), (21, 3), (29, 1), (32, 4), (33, 3), (45, 3), (47, 1), (48, 4), (57, 3),

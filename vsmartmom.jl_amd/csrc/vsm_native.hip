@@ -1105,22 +1105,10 @@ namespace {
 // (i / gsz) n_stokes + g[i % gsz] of the full problem.  Thread = (row, column phase): 16 consecutive threads write 16
 // consecutive rows of one column (128 contiguous bytes of an image block).
 // ---------------------------------------------------------------------------------------------------------------------------
-// ST = the storage type of the caller's arrays (double, or float: a Float32 run whose blocks fit these kernels -- inputs are
-// converted on load, everything from here to the export of the composite is FP64).
-template <typename ST>
-struct nsub_pre {
-  int m, gsz;
-  int g[4];
-  zsrc<ST> z;
-};
-template <typename ST>
-struct npre_args {
-  nsub_pre<ST> s[NSUB_MAX];
-};
-template <int RT, bool MIX, typename ST>
-__global__ __launch_bounds__(64 * RT) void k_elemental_native(quad<ST> q, int n, int ndoubl, const ST* __restrict__ dtau,
-                                                              const ST* __restrict__ varpi, const ST* __restrict__ tau_sum,
-                                                              const ST* __restrict__ F0, npre_args<ST> a,
+template <int RT, bool MIX>
+__global__ __launch_bounds__(64 * RT) void k_elemental_native(quad<double> q, int n, int ndoubl, const double* __restrict__ dtau,
+                                                              const double* __restrict__ varpi, const double* __restrict__ tau_sum,
+                                                              const double* __restrict__ F0, npre_args<double> a,
                                                               double* __restrict__ pre) {
   using G = ngeo<RT>;
   constexpr int NP = G::NP;
@@ -1128,38 +1116,38 @@ __global__ __launch_bounds__(64 * RT) void k_elemental_native(quad<ST> q, int n,
   __shared__ int frow[NP];
   __shared__ int thick_flag;
   const int s = blockIdx.x, isub = blockIdx.y, tid = threadIdx.x;
-  const nsub_pre<ST>& sp = a.s[isub];
+  const nsub_pre<double>& sp = a.s[isub];
   const int N = q.N, ns = q.n_stokes, m = sp.m, gsz = sp.gsz;
-  const zsrc<ST> z = sp.z;
-  const double d = (double)dtau[s], w = (double)varpi[s];
+  const zsrc<double> z = sp.z;
+  const double d = dtau[s], w = varpi[s];
   const int ncomp = MIX ? z.ncomp : 0;
   const long long NNz = (long long)N * N;
-  const ST* Zp = z.Zpp + (ncomp ? 0 : (long long)s * z.zs);
-  const ST* Zm = z.Zmp + (ncomp ? 0 : (long long)s * z.zs);
+  const double* Zp = z.Zpp + (ncomp ? 0 : (long long)s * z.zs);
+  const double* Zm = z.Zmp + (ncomp ? 0 : (long long)s * z.zs);
   double fk[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
   for (int k = 0; k < 4; ++k)
-    if (k < ncomp) fk[k] = (double)z.fcomp[(long long)s * ncomp + k];
-  auto zget = [&](const ST* Z, long long zo) {
-    if (ncomp == 0) return (double)Z[zo];
+    if (k < ncomp) fk[k] = z.fcomp[(long long)s * ncomp + k];
+  auto zget = [&](const double* Z, long long zo) {
+    if (ncomp == 0) return Z[zo];
     double acc = 0.0;
 #pragma unroll
     for (int k = 0; k < 4; ++k)
-      if (k < ncomp) acc += fk[k] * (double)Z[k * NNz + zo];
+      if (k < ncomp) acc += fk[k] * Z[k * NNz + zo];
     return acc;
   };
   if (tid < NP) {
     const bool in = tid < n;
     const int ga = sp.g[tid % gsz];
     const int fr = in ? (tid / gsz) * ns + ga : 0;
-    const double mu = in ? (double)q.mu[fr] : 1.0;
+    const double mu = in ? q.mu[fr] : 1.0;
     const double x = d / mu;
     frow[tid] = fr;
     mus[tid] = mu;
     xs[tid] = x;
     es[tid] = exp(-x);
     ems[tid] = expm1(-x);
-    wts[tid] = in ? (double)q.wt[fr] : 0.0;
+    wts[tid] = in ? q.wt[fr] : 0.0;
   }
   if (tid == 0) thick_flag = 0;
   __syncthreads();
@@ -1187,7 +1175,7 @@ __global__ __launch_bounds__(64 * RT) void k_elemental_native(quad<ST> q, int n,
       const long long zo = fi + (long long)N * frow[j];
       double rr, tt;
       elemental_pair(w, zget(Zp, zo), zget(Zm, zo), mi, xi, ai, ei, mus[j], xs[j], ems[j], es[j], wct, i == j, thick, rr, tt);
-      const bool active = wct > (double)num<ST>::eps();   // eps(FT) of the MODEL's float type (elemental.jl:296)
+      const bool active = wct > num<double>::eps();   // eps(FT) of the model's float type (elemental.jl:296)
       if (i < n) {
         rv = active ? rr * sg : 0.0;
         tv = active ? tt : ((i == j) ? ei : 0.0);
@@ -1198,22 +1186,22 @@ __global__ __launch_bounds__(64 * RT) void k_elemental_native(quad<ST> q, int n,
   }
   if (ph == 0) {   // SFI source of the solar beam: the same formulas with the solar column (see elemental_pair)
     const int i0 = ns * q.i_mu0;
-    const double mu0n = (double)q.mu[i0];
+    const double mu0n = q.mu[i0];
     const double x0 = d / mu0n, e0 = exp(-x0), a0 = expm1(-x0);
     double zp = 0.0, zm = 0.0;
     for (int qq = 0; qq < ns; ++qq) {
       const long long zo = fi + (long long)N * (i0 + qq);
-      const double f = (double)F0[qq + (long long)ns * s];
+      const double f = F0[qq + (long long)ns * s];
       zp += zget(Zp, zo) * f;
       zm += zget(Zm, zo) * f;
     }
     double rr, tt;
     // (the diagonal case mu_i == mu_0 of the source never takes the i == j form: elemental.jl:370-382)
     elemental_pair(w, zp, zm, mi, xi, ai, ei, mu0n, x0, a0, e0, (m == 0) ? 0.5 : 0.25, false, thick || x0 >= 0.5, rr, tt);
-    const double att = exp(-(double)tau_sum[s] / mu0n);
+    const double att = exp(-tau_sum[s] / mu0n);
     const double vp = (i < n) ? tt * att : 0.0;
     const double vm = (i < n) ? rr * att * sg : 0.0;
-    const double expk0 = exp(-d / (double)q.mu0);
+    const double expk0 = exp(-d / q.mu0);
     out[2 * G::AF + i] = vp;
     out[2 * G::AF + NP + i] = vm;
     out[2 * G::AF + 2 * NP + i] = expk0;
@@ -1229,6 +1217,8 @@ __global__ __launch_bounds__(64 * RT) void k_elemental_native(quad<ST> q, int n,
 // ---------------------------------------------------------------------------------------------------------------------------
 // native <-> reference layout ([N,N,S] column-major composite arrays), one workgroup per point
 // ---------------------------------------------------------------------------------------------------------------------------
+// T = the record type of the run: double (vsm_native_dev.h) or float (vsm_native32_dev.h); all arithmetic in T
+template <typename T>
 struct ngroup_map {
   int ngroups;
   int grp_of[4];    // group of Stokes component a
@@ -1236,76 +1226,90 @@ struct ngroup_map {
   int gsz[4];       // per group
   int rt[4];        // per group: row tiles
   int n[4];         // per group: rows
-  double* base[4];  // per group: native composites [S] (stride COMP_STRIDE of its RT)
+  T* base[4];       // per group: native composites [S] (stride COMP_STRIDE of its RT)
 };
-__device__ __forceinline__ int nnat_idx_rt(int rt, int i, int j) {   // nnat_idx<RT> with the row-tile count as an argument
+// nnat_idx<RT> / n32nat_idx<RT> with the row-tile count as an argument: the position of element (i, j) in a native matrix record
+__device__ __forceinline__ int nat_idx_rt(const double*, int rt, int i, int j) {
   const int w = j >> 4, l15 = j & 15, ta = i >> 4, mm = i & 15, kq = mm & 3, r = mm >> 2;
   const int lane = (kq << 4) | l15, u = 2 * ta + (r >> 1);
   return ((w * 2 * rt + u) * 64 + lane) * 2 + (r & 1);
 }
+__device__ __forceinline__ int nat_idx_rt(const float*, int rt, int i, int j) {
+  const int w = j >> 4, l15 = j & 15, ta = i >> 4, mm = i & 15, kq = mm & 3, r = mm >> 2;
+  return ((w * rt + ta) * 64 + ((kq << 4) | l15)) * 4 + r;
+}
+// ... and its inverse: the element (i, j) at position e
+__device__ __forceinline__ void nat_elem_rt(const double*, int rt, int e, int& i, int& j) {
+  const int half = e & 1, lane = (e >> 1) & 63, unit = (e >> 7) % (2 * rt), w = (e >> 7) / (2 * rt);
+  i = 16 * (unit >> 1) + (lane >> 4) + 4 * (2 * (unit & 1) + half), j = 16 * w + (lane & 15);
+}
+__device__ __forceinline__ void nat_elem_rt(const float*, int rt, int e, int& i, int& j) {
+  const int r = e & 3, lane = (e >> 2) & 63, ta = (e >> 8) % rt, w = (e >> 8) / rt;
+  i = 16 * ta + (lane >> 4) + 4 * r, j = 16 * w + (lane & 15);
+}
 // src: a sources-only run -- its R-+ and T++ are undefined and leave as quiet NaNs (a consumer fails loudly, never on stale data)
-template <typename ST>
-__global__ __launch_bounds__(256) void k_native_export(int N, int ns, int src, ngroup_map gm, composite<ST> c) {
+template <typename T>
+__global__ __launch_bounds__(256) void k_native_export(int N, int ns, int src, ngroup_map<T> gm, composite<T> c) {
   const int s = blockIdx.x, tid = threadIdx.x;
   const long long NN = (long long)N * N;
-  ST* out[4] = {c.R_mp + s * NN, c.R_pm + s * NN, c.T_pp + s * NN, c.T_mm + s * NN};
+  T* out[4] = {c.R_mp + s * NN, c.R_pm + s * NN, c.T_pp + s * NN, c.T_mm + s * NN};
   for (int e = tid; e < N * N; e += 256) {
     const int i = e % N, j = e / N;
     const int ai = i % ns, aj = j % ns;
     const int gi = gm.grp_of[ai];
-    double v[4] = {0.0, 0.0, 0.0, 0.0};
+    T v[4] = {0, 0, 0, 0};
     if (gi == gm.grp_of[aj]) {
       const int rt = gm.rt[gi], np = 16 * rt, af = np * np;
-      const double* cn = gm.base[gi] + (long long)s * (4 * af + 2 * np);
+      const T* cn = gm.base[gi] + (long long)s * (4 * af + 2 * np);
       const int is = (i / ns) * gm.gsz[gi] + gm.pos_in[ai], js = (j / ns) * gm.gsz[gi] + gm.pos_in[aj];
-      const int ix = nnat_idx_rt(rt, is, js);
+      const int ix = nat_idx_rt(cn, rt, is, js);
 #pragma unroll
       for (int k = 0; k < 4; ++k) v[k] = cn[k * af + ix];
     }
-    if (src) v[NC_RMP] = v[NC_TPP] = __builtin_nan("");
+    if (src) v[NC_RMP] = v[NC_TPP] = (T)__builtin_nan("");
 #pragma unroll
-    for (int k = 0; k < 4; ++k) out[k][e] = (ST)v[k];
+    for (int k = 0; k < 4; ++k) out[k][e] = v[k];
   }
   if (tid < N) {
     const int ai = tid % ns, gi = gm.grp_of[ai];
     const int rt = gm.rt[gi], np = 16 * rt, af = np * np;
-    const double* cn = gm.base[gi] + (long long)s * (4 * af + 2 * np);
+    const T* cn = gm.base[gi] + (long long)s * (4 * af + 2 * np);
     const int is = (tid / ns) * gm.gsz[gi] + gm.pos_in[ai];
-    c.J0_p[(long long)s * N + tid] = (ST)cn[4 * af + is];
-    c.J0_m[(long long)s * N + tid] = (ST)cn[4 * af + np + is];
+    c.J0_p[(long long)s * N + tid] = cn[4 * af + is];
+    c.J0_m[(long long)s * N + tid] = cn[4 * af + np + is];
   }
 }
 // reference layout -> native (padding zero); elements that couple different groups are dropped (they are exact zeros for a
 // composite that was built under the same coupling)
-template <typename ST>
-__global__ __launch_bounds__(256) void k_native_import(int N, int ns, ngroup_map gm, composite<ST> c) {
+template <typename T>
+__global__ __launch_bounds__(256) void k_native_import(int N, int ns, ngroup_map<T> gm, composite<T> c) {
   const int s = blockIdx.x, tid = threadIdx.x;
   const long long NN = (long long)N * N;
-  const ST* in[4] = {c.R_mp + s * NN, c.R_pm + s * NN, c.T_pp + s * NN, c.T_mm + s * NN};
+  const T* in[4] = {c.R_mp + s * NN, c.R_pm + s * NN, c.T_pp + s * NN, c.T_mm + s * NN};
   for (int g = 0; g < gm.ngroups; ++g) {
     const int rt = gm.rt[g], np = 16 * rt, af = np * np, n = gm.n[g], gsz = gm.gsz[g];
-    double* cn = gm.base[g] + (long long)s * (4 * af + 2 * np);
+    T* cn = gm.base[g] + (long long)s * (4 * af + 2 * np);
     int comp_of[4] = {0, 0, 0, 0};   // Stokes component of position k of the group
     for (int a = 0; a < ns; ++a)
       if (gm.grp_of[a] == g) comp_of[gm.pos_in[a]] = a;
     for (int e = tid; e < af; e += 256) {
       const int is = e % np, js = e / np;
-      double v[4] = {0.0, 0.0, 0.0, 0.0};
+      T v[4] = {0, 0, 0, 0};
       if (is < n && js < n) {
         const int i = (is / gsz) * ns + comp_of[is % gsz], j = (js / gsz) * ns + comp_of[js % gsz];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = (double)in[k][i + (long long)N * j];
+        for (int k = 0; k < 4; ++k) v[k] = in[k][i + (long long)N * j];
       }
-      const int ix = nnat_idx_rt(rt, is, js);
+      const int ix = nat_idx_rt(cn, rt, is, js);
 #pragma unroll
       for (int k = 0; k < 4; ++k) cn[k * af + ix] = v[k];
     }
     if (tid < np) {
-      double vp = 0.0, vm = 0.0;
+      T vp = 0, vm = 0;
       if (tid < n) {
         const int i = (tid / gsz) * ns + comp_of[tid % gsz];
-        vp = (double)c.J0_p[(long long)s * N + i];
-        vm = (double)c.J0_m[(long long)s * N + i];
+        vp = c.J0_p[(long long)s * N + i];
+        vm = c.J0_m[(long long)s * N + i];
       }
       cn[4 * af + tid] = vp;
       cn[4 * af + np + tid] = vm;
@@ -1315,16 +1319,16 @@ __global__ __launch_bounds__(256) void k_native_import(int N, int ns, ngroup_map
 
 // Which Stokes components a phase matrix couples: bit 4 a + b of mask[b] is set when some element (i, j) with i % ns == a,
 // j % ns == b of block b of Zpp / Zmp [N,N,nblocks] is not exactly zero.
-template <typename ST>
-__global__ __launch_bounds__(256) void k_stokes_coupling(int N, int ns, const ST* __restrict__ Zpp, const ST* __restrict__ Zmp,
+template <typename T>
+__global__ __launch_bounds__(256) void k_stokes_coupling(int N, int ns, const T* __restrict__ Zpp, const T* __restrict__ Zmp,
                                                          int* __restrict__ mask) {
   unsigned mm = 0;
   const long long NN = (long long)N * N;
-  const ST* zp = Zpp + NN * blockIdx.y;
-  const ST* zm = Zmp + NN * blockIdx.y;
+  const T* zp = Zpp + NN * blockIdx.y;
+  const T* zm = Zmp + NN * blockIdx.y;
   for (long long e = blockIdx.x * 256ll + threadIdx.x; e < NN; e += 256ll * gridDim.x) {
     const int i = (int)(e % N), j = (int)(e / N);
-    if (zp[e] != ST(0) || zm[e] != ST(0)) mm |= 1u << (4 * (i % ns) + (j % ns));
+    if (zp[e] != T(0) || zm[e] != T(0)) mm |= 1u << (4 * (i % ns) + (j % ns));
   }
   if (mm) atomicOr(mask + blockIdx.y, (int)mm);
 }
@@ -1334,22 +1338,22 @@ __global__ __launch_bounds__(256) void k_stokes_coupling(int N, int ns, const ST
 // block of the run AND that block not taken as a diagonal step in this layer.  Any other non-zero element of the layer's phase
 // matrices raises VSM_DEVSTAT_MASK (vsm_device_status): the run drops that coupling silently otherwise.  One workgroup per matrix
 // (blockIdx.x: the scatterer's block of a component stack, the spectral point of a per-point Z, or the one shared matrix).
-template <typename ST>
+template <typename T>
 struct nguard_args {
-  const ST* zp[NSUB_MAX];
-  const ST* zm[NSUB_MAX];
+  const T* zp[NSUB_MAX];
+  const T* zm[NSUB_MAX];
   unsigned allowed[NSUB_MAX];
 };
-template <typename ST>
-__global__ __launch_bounds__(256) void k_coupling_guard(int N, int ns, long long mat_stride, nguard_args<ST> a, int* status) {
+template <typename T>
+__global__ __launch_bounds__(256) void k_coupling_guard(int N, int ns, long long mat_stride, nguard_args<T> a, int* status) {
   const long long NN = (long long)N * N;
   const int im = blockIdx.y;
-  const ST* zp = a.zp[im] + mat_stride * blockIdx.x;
-  const ST* zm = a.zm[im] + mat_stride * blockIdx.x;
+  const T* zp = a.zp[im] + mat_stride * blockIdx.x;
+  const T* zm = a.zm[im] + mat_stride * blockIdx.x;
   unsigned mm = 0;
   for (int e = threadIdx.x; e < NN; e += 256) {
     const int i = e % N, j = e / N;
-    if (zp[e] != ST(0) || zm[e] != ST(0)) mm |= 1u << (4 * (i % ns) + (j % ns));
+    if (zp[e] != T(0) || zm[e] != T(0)) mm |= 1u << (4 * (i % ns) + (j % ns));
   }
   if (mm & ~a.allowed[im]) atomicOr(&status[0], (int)VSM_DEVSTAT_MASK);
 }
@@ -1361,29 +1365,30 @@ __global__ __launch_bounds__(256) void k_coupling_guard(int N, int ns, long long
 //   T++ <- t T++,  T-- <- T-- t,  R+- <- t R+- t,  J0+ <- t J0+;   R-+, J0- unchanged.
 // t = e^{-dtau 2^nd / mu_i} here (the doubled layer in one exponential).  One workgroup per (point, sub-problem) over the native
 // records: element (i, j) from its position.  TOA: the composite is the layer itself (R = 0, T = diag(t), J = 0).
+template <typename T>
 struct ndiag_args {
-  double* comp[NSUB_MAX];
+  T* comp[NSUB_MAX];
   int gsz[NSUB_MAX];
   int g0[NSUB_MAX];    // the group's Stokes components, 4 bits each
 };
 // mode 0: the scaling above; 1: TOA; 2: the composite is still (R = 0, T = diag, J = 0) -- every layer above was such a step --:
 // only the two diagonals change.  src: a sources-only run -- R-+ and T++ are left alone.
-template <typename ST>
-__global__ __launch_bounds__(256) void k_native_diag_layer(quad<ST> q, int rt, int n, double scale, int mode, int src,
-                                                           const ST* __restrict__ dtau, ndiag_args a) {
-  __shared__ double tt[NATIVE_MAX_ROWS];
+template <typename T>
+__global__ __launch_bounds__(256) void k_native_diag_layer(quad<T> q, int rt, int n, T scale, int mode, int src,
+                                                           const T* __restrict__ dtau, ndiag_args<T> a) {
+  __shared__ T tt[sizeof(T) == 4 ? NATIVE32_MAX_ROWS : NATIVE_MAX_ROWS];
   const int s = blockIdx.x, isub = blockIdx.y, tid = threadIdx.x;
   const int np = 16 * rt, af = np * np, gsz = a.gsz[isub];
-  double* comp = a.comp[isub] + (long long)s * (4 * af + 2 * np);
+  T* comp = a.comp[isub] + (long long)s * (4 * af + 2 * np);
   if (tid < np) {
-    double t = 0.0;
+    T t = 0;
     if (tid < n) {
       const int fr = (tid / gsz) * q.n_stokes + ((a.g0[isub] >> (4 * (tid % gsz))) & 15);
-      t = exp(-(double)dtau[s] * scale / (double)q.mu[fr]);
+      t = exp(-dtau[s] * scale / q.mu[fr]);
     }
     tt[tid] = t;
     if (mode == 2 && tid < n) {
-      const int ix = nnat_idx_rt(rt, tid, tid);
+      const int ix = nat_idx_rt(comp, rt, tid, tid);
       if (!src) comp[NC_TPP * af + ix] *= t;
       comp[NC_TMM * af + ix] *= t;
     }
@@ -1392,16 +1397,16 @@ __global__ __launch_bounds__(256) void k_native_diag_layer(quad<ST> q, int rt, i
   const int toa = mode == 1;
   __syncthreads();
   for (int e = tid; e < af; e += 256) {
-    const int half = e & 1, lane = (e >> 1) & 63, unit = (e >> 7) % (2 * rt), w = (e >> 7) / (2 * rt);
-    const int i = 16 * (unit >> 1) + (lane >> 4) + 4 * (2 * (unit & 1) + half), j = 16 * w + (lane & 15);
-    const double ti = tt[i], tj = tt[j];
+    int i, j;
+    nat_elem_rt(comp, rt, e, i, j);
+    const T ti = tt[i], tj = tt[j];
     if (toa) {
-      const double d = (i == j) ? ti : 0.0;
+      const T d = (i == j) ? ti : 0;
       if (!src) {
-        comp[NC_RMP * af + e] = 0.0;
+        comp[NC_RMP * af + e] = 0;
         comp[NC_TPP * af + e] = d;
       }
-      comp[NC_RPM * af + e] = 0.0;
+      comp[NC_RPM * af + e] = 0;
       comp[NC_TMM * af + e] = d;
     } else {
       comp[NC_RPM * af + e] *= ti * tj;
@@ -1411,8 +1416,8 @@ __global__ __launch_bounds__(256) void k_native_diag_layer(quad<ST> q, int rt, i
   }
   if (tid < np) {
     if (toa) {
-      comp[4 * af + tid] = 0.0;
-      comp[4 * af + np + tid] = 0.0;
+      comp[4 * af + tid] = 0;
+      comp[4 * af + np + tid] = 0;
     } else {
       comp[4 * af + tid] *= tt[tid];
     }
@@ -1461,13 +1466,6 @@ static int stokes_groups(int ns, int coupling, int grp_of[4], int groups[4][4], 
   }
   return ng;
 }
-static inline int rt_of(int n) {   // (as the launchers of the layer kernels choose it)
-  const int ks = (n + 3) / 4;
-  return (ks % 4 == 0 && ks >= 4) ? ks / 4 : (4 * ks + 2 + 15) / 16;
-}
-static inline size_t comp_stride_rt(int rt) { return (size_t)4 * (16 * rt) * (16 * rt) + 2 * 16 * rt; }
-static inline size_t pre_stride_rt(int rt) { return (size_t)2 * (16 * rt) * (16 * rt) + 3 * 16 * rt; }
-
 // f32: the FP32 family (vsm_native32.hip: blocks of <= 96 rows, records in floats); else the FP64 one (<= 64 rows, doubles)
 static int plan_subs(bool f32, int N, int ns, int nm, const int* m, const int* coupling, std::vector<nat_sub>& subs, size_t S,
                      size_t& total) {
@@ -1499,9 +1497,9 @@ static int plan_subs(bool f32, int N, int ns, int nm, const int* m, const int* c
       }
       sb.ks = (sb.n + 3) / 4;
       sb.kz = sb.ks;
-      sb.rt = f32 ? native32_rt_of(sb.n) : rt_of(sb.n);
+      sb.rt = rt_of(sb.n);
       sb.comp_off = total;
-      total += (f32 ? native32_comp_stride(sb.rt) : comp_stride_rt(sb.rt)) * S;
+      total += comp_stride_rt(sb.rt) * S;
       subs.push_back(sb);
     }
   }
@@ -1509,9 +1507,11 @@ static int plan_subs(bool f32, int N, int ns, int nm, const int* m, const int* c
 }
 
 static int launch_layer_native(int ks, int tz, int S, int nsub, int n, unsigned uvmask, int gsz, int ndoubl, int toa, int src,
-                               const double* pre, const nlayer_comps& comps, int* status, hipStream_t st) {
+                               const double* pre, double* const* comps, int* status, hipStream_t st) {
+  nlayer_comps lc;
+  for (int k = 0; k < NSUB_MAX; ++k) lc.c[k] = comps[k];
 #define VSM_NL(KS) \
-  case KS: return VSM_NCAT(launch_layer_native_, KS)(S, nsub, n, uvmask, gsz, ndoubl, toa, src, tz, pre, comps, status, st);
+  case KS: return VSM_NCAT(launch_layer_native_, KS)(S, nsub, n, uvmask, gsz, ndoubl, toa, src, tz, pre, lc, status, st);
   switch (ks) {
     VSM_NL(1) VSM_NL(2) VSM_NL(3) VSM_NL(4) VSM_NL(5) VSM_NL(6) VSM_NL(7) VSM_NL(8) VSM_NL(9) VSM_NL(10) VSM_NL(11) VSM_NL(12)
     VSM_NL(13) VSM_NL(14) VSM_NL(15) VSM_NL(16) VSM_NL(17) VSM_NL(18) VSM_NL(19) VSM_NL(20) VSM_NL(21) VSM_NL(22) VSM_NL(23) VSM_NL(24)
@@ -1541,18 +1541,47 @@ int native_interaction11(int N, int S, const composite<double>& c, const added<d
 }
 namespace {
 
-template <int RT, typename ST>
-static void launch_pre(bool mix, const quad<ST>& q, int S, int nsub, int n, int ndoubl, const ST* dtau, const ST* varpi,
-                       const ST* tau_sum, const ST* F0, const npre_args<ST>& a, double* pre, hipStream_t st) {
+template <int RT>
+static void launch_pre(bool mix, const quad<double>& q, int S, int nsub, int n, int ndoubl, const double* dtau, const double* varpi,
+                       const double* tau_sum, const double* F0, const npre_args<double>& a, double* pre, hipStream_t st) {
   const dim3 grid(S, nsub), block(64 * RT);
   if (mix)
-    hipLaunchKernelGGL((k_elemental_native<RT, true, ST>), grid, block, 0, st, q, n, ndoubl, dtau, varpi, tau_sum, F0, a, pre);
+    hipLaunchKernelGGL((k_elemental_native<RT, true>), grid, block, 0, st, q, n, ndoubl, dtau, varpi, tau_sum, F0, a, pre);
   else
-    hipLaunchKernelGGL((k_elemental_native<RT, false, ST>), grid, block, 0, st, q, n, ndoubl, dtau, varpi, tau_sum, F0, a, pre);
+    hipLaunchKernelGGL((k_elemental_native<RT, false>), grid, block, 0, st, q, n, ndoubl, dtau, varpi, tau_sum, F0, a, pre);
 }
 
-static ngroup_map group_map(const vsm_run* run, int im) {
-  ngroup_map gm;
+// What differs between the two families in a layer step: the pre-pass kernels (row tiles to 6 / to 8) and the layer kernels (the
+// FP64 ones take the zero-weight tail tz = ks - kz and src; a Float32 run has neither: run_create leaves its flags at 0).
+static void native_launch_pre(int rt, bool mix, const quad<double>& q, int S, int nsub, int n, int ndoubl, const double* dtau,
+                              const double* varpi, const double* tau_sum, const double* F0, const npre_args<double>& a, double* pre,
+                              hipStream_t st) {
+  switch (rt) {
+    case 1: launch_pre<1>(mix, q, S, nsub, n, ndoubl, dtau, varpi, tau_sum, F0, a, pre, st); break;
+    case 2: launch_pre<2>(mix, q, S, nsub, n, ndoubl, dtau, varpi, tau_sum, F0, a, pre, st); break;
+    case 3: launch_pre<3>(mix, q, S, nsub, n, ndoubl, dtau, varpi, tau_sum, F0, a, pre, st); break;
+    case 4: launch_pre<4>(mix, q, S, nsub, n, ndoubl, dtau, varpi, tau_sum, F0, a, pre, st); break;
+    case 5: launch_pre<5>(mix, q, S, nsub, n, ndoubl, dtau, varpi, tau_sum, F0, a, pre, st); break;
+    default: launch_pre<6>(mix, q, S, nsub, n, ndoubl, dtau, varpi, tau_sum, F0, a, pre, st); break;
+  }
+}
+static void native_launch_pre(int rt, bool mix, const quad<float>& q, int S, int nsub, int n, int ndoubl, const float* dtau,
+                              const float* varpi, const float* tau_sum, const float* F0, const npre_args<float>& a, float* pre,
+                              hipStream_t st) {
+  native32_launch_pre(rt, mix, q, S, nsub, n, ndoubl, dtau, varpi, tau_sum, F0, a, pre, st);
+}
+static int native_launch_layer(const nat_sub& h, int S, int nsub, int ndoubl, int toa, int src, const double* pre, double* const* comps,
+                               int* status, hipStream_t st) {
+  return launch_layer_native(h.ks, h.ks - h.kz, S, nsub, h.n, h.uvmask, h.gsz, ndoubl, toa, src, pre, comps, status, st);
+}
+static int native_launch_layer(const nat_sub& h, int S, int nsub, int ndoubl, int toa, int, const float* pre, float* const* comps,
+                               int* status, hipStream_t st) {
+  return native32_launch_layer(h.ks, S, nsub, h.n, h.uvmask, h.gsz, ndoubl, toa, pre, comps, status, st);
+}
+
+template <typename T>
+static ngroup_map<T> group_map(const vsm_run* run, int im) {
+  ngroup_map<T> gm;
   gm.ngroups = 0;
   for (int a = 0; a < 4; ++a) {
     gm.grp_of[a] = gm.pos_in[a] = 0;
@@ -1566,7 +1595,7 @@ static ngroup_map group_map(const vsm_run* run, int im) {
     gm.gsz[g] = sb.gsz;
     gm.rt[g] = sb.rt;
     gm.n[g] = sb.n;
-    gm.base[g] = static_cast<double*>(run->ws) + sb.comp_off;
+    gm.base[g] = static_cast<T*>(run->ws) + sb.comp_off;
     for (int k = 0; k < sb.gsz; ++k) {
       gm.grp_of[sb.g[k]] = g;
       gm.pos_in[sb.g[k]] = k;
@@ -1575,23 +1604,23 @@ static ngroup_map group_map(const vsm_run* run, int im) {
   return gm;
 }
 
-template <typename ST>
-static quad<ST> run_quad(const vsm_run* run) {
-  return quad<ST>{static_cast<const ST*>(run->mu), static_cast<const ST*>(run->wt), run->N, run->ns, run->i_mu0, (ST)run->mu0};
+template <typename T>
+static quad<T> run_quad(const vsm_run* run) {
+  return quad<T>{static_cast<const T*>(run->mu), static_cast<const T*>(run->wt), run->N, run->ns, run->i_mu0, (T)run->mu0};
 }
 
 // VSM_RUN_ZW_TAIL: the trailing run of quadrature nodes whose weight is exactly 0 (the VZA / SZA nodes rt_set_streams appends
 // behind the Gauss-Legendre nodes).  Rows are node-major in every block (row = node gsz + position), so they are its last rows:
 // kz = ceil(real rows / 4).  One synchronous read of the run's weights (on the legacy stream, behind the caller's pending work).
-template <typename ST>
+template <typename T>
 static int zw_tail(vsm_run* run) {
   const int N = run->N, ns = run->ns, nq = N / ns;
-  std::vector<ST> w((size_t)N);
-  VSM_HIP(hipMemcpy(w.data(), run->wt, sizeof(ST) * (size_t)N, hipMemcpyDefault));
+  std::vector<T> w((size_t)N);
+  VSM_HIP(hipMemcpy(w.data(), run->wt, sizeof(T) * (size_t)N, hipMemcpyDefault));
   int z = 0;   // trailing zero-weight nodes
   for (int node = nq - 1; node >= 0; --node) {
     bool zero = true;
-    for (int a = 0; a < ns; ++a) zero = zero && w[(size_t)node * ns + a] == ST(0);
+    for (int a = 0; a < ns; ++a) zero = zero && w[(size_t)node * ns + a] == T(0);
     if (!zero) break;
     ++z;
   }
@@ -1601,7 +1630,7 @@ static int zw_tail(vsm_run* run) {
   return VSM_OK;
 }
 
-template <typename ST, typename Q>
+template <typename T, typename Q>
 static int run_create(const Q* q, int S, int nm, const int* m, const int* coupling, void* workspace, size_t workspace_bytes,
                       unsigned flags, vsm_run** run_out) {
   VSM_REQUIRE(q && q->mu && q->wt && run_out && m, "vsm_run_create: null argument");
@@ -1615,25 +1644,25 @@ static int run_create(const Q* q, int S, int nm, const int* m, const int* coupli
   run->ns = q->n_stokes;
   run->i_mu0 = q->i_mu0;
   run->mu0 = (double)q->mu0;
-  run->elem_size = (int)sizeof(ST);
+  run->elem_size = (int)sizeof(T);
   run->S = S;
   run->nm = nm;
   // (the FP32 family keeps the full recurrences: R-+ and T++ stay defined there)
-  run->flags = sizeof(ST) == 8 ? flags : 0u;
+  run->flags = sizeof(T) == 8 ? flags : 0u;
   run->m.assign(m, m + nm);
   size_t total = 0;
-  const int rc = plan_subs(sizeof(ST) == 4, q->N, q->n_stokes, nm, m, coupling, run->subs, (size_t)S, total);
+  const int rc = plan_subs(sizeof(T) == 4, q->N, q->n_stokes, nm, m, coupling, run->subs, (size_t)S, total);
   if (rc) {
     delete run;
     return rc;
   }
-  if (total * sizeof(ST) > workspace_bytes || (total && !workspace) || ((size_t)workspace & 15)) {
-    set_error("vsm_run_create: workspace of %zu bytes (16-byte aligned) required, got %zu", total * sizeof(ST), workspace_bytes);
+  if (total * sizeof(T) > workspace_bytes || (total && !workspace) || ((size_t)workspace & 15)) {
+    set_error("vsm_run_create: workspace of %zu bytes (16-byte aligned) required, got %zu", total * sizeof(T), workspace_bytes);
     delete run;
     return VSM_ERR_INVALID_ARG;
   }
   if (run->flags & VSM_RUN_ZW_TAIL) {
-    const int rc2 = zw_tail<ST>(run);
+    const int rc2 = zw_tail<T>(run);
     if (rc2) {
       delete run;
       return rc2;
@@ -1660,19 +1689,19 @@ static int run_create(const Q* q, int S, int nm, const int* m, const int* coupli
   return VSM_OK;
 }
 
-template <typename ST>
-static int run_layer(vsm_run* run, int ndoubl, const ST* dtau, const ST* varpi, const ST* tau_sum, const ST* F0, int ncomp,
-                     const ST* const* Zpp, const ST* const* Zmp, long long z_stride, const ST* fcomp, int toa,
+template <typename T>
+static int run_layer(vsm_run* run, int ndoubl, const T* dtau, const T* varpi, const T* tau_sum, const T* F0, int ncomp,
+                     const T* const* Zpp, const T* const* Zmp, long long z_stride, const T* fcomp, int toa,
                      const int* layer_coupling, void* stream) {
   VSM_REQUIRE(run && dtau && varpi && tau_sum && F0 && Zpp && Zmp, "vsm_run_layer: null argument");
-  VSM_REQUIRE(run->elem_size == (int)sizeof(ST), "vsm_run_layer: the run was created for %d-byte arrays", run->elem_size);
+  VSM_REQUIRE(run->elem_size == (int)sizeof(T), "vsm_run_layer: the run was created for %d-byte arrays", run->elem_size);
   VSM_REQUIRE(ndoubl >= 0 && ndoubl < 60 && ncomp >= 0 && ncomp <= 4 && (ncomp == 0 || fcomp), "vsm_run_layer: bad ndoubl / component mix");
   ++run->layers;
   if (run->S == 0) return VSM_OK;
   hipStream_t st = as_stream(stream);
   int* status = device_status();
   if (!status) return VSM_ERR_HIP;
-  const quad<ST> q = run_quad<ST>(run);
+  const quad<T> q = run_quad<T>(run);
   // a sub-problem whose Stokes block the layer's phase matrices leave exactly zero takes the diagonal step
   auto trivial = [&](const nat_sub& sb) {
     if (!layer_coupling || layer_coupling[sb.im] < 0) return false;
@@ -1682,7 +1711,7 @@ static int run_layer(vsm_run* run, int ndoubl, const ST* dtau, const ST* varpi, 
     return true;
   };
   {   // the masks against the layer's actual phase matrices (VSM_DEVSTAT_MASK)
-    nguard_args<ST> ga;
+    nguard_args<T> ga;
     for (int k = 0; k < NSUB_MAX; ++k) {
       const int im = k < run->nm ? k : 0;
       VSM_REQUIRE(Zpp[im] && Zmp[im], "vsm_run_layer: null Z of moment %d", im);
@@ -1696,22 +1725,19 @@ static int run_layer(vsm_run* run, int ndoubl, const ST* dtau, const ST* varpi, 
         for (int b = 0; b < sb.gsz; ++b) ga.allowed[sb.im] |= 1u << (4 * sb.g[a] + sb.g[b]);
     }
     const int nmat = ncomp ? ncomp : (z_stride ? run->S : 1);
-    hipLaunchKernelGGL((k_coupling_guard<ST>), dim3(nmat, run->nm), dim3(256), 0, st, run->N, run->ns,
+    hipLaunchKernelGGL((k_coupling_guard<T>), dim3(nmat, run->nm), dim3(256), 0, st, run->N, run->ns,
                        ncomp ? (long long)run->N * run->N : z_stride, ga, status);
     VSM_LAUNCH_CHECK("k_coupling_guard");
   }
-  if constexpr (sizeof(ST) == 4) {   // Float32 model: FP32 records and arithmetic (vsm_native32.hip)
-    return native32_run_layer(run, ndoubl, dtau, varpi, tau_sum, F0, ncomp, Zpp, Zmp, z_stride, fcomp, toa, layer_coupling, status, st);
-  } else {
-  double* const ws = static_cast<double*>(run->ws);
+  T* const ws = static_cast<T*>(run->ws);
   const int src = (run->flags & VSM_RUN_SOURCES_ONLY) ? 1 : 0;
   // the pre-pass images of the layer: one record per (sub-problem, point)
   size_t pre_total = 0;
   for (const nat_sub& sb : run->subs)
     if (!trivial(sb)) pre_total += pre_stride_rt(sb.rt) * (size_t)run->S;
-  double* pre = nullptr;
+  T* pre = nullptr;
   if (pre_total) {
-    pre = static_cast<double*>(scratch(pre_total * sizeof(double), 3, st));
+    pre = static_cast<T*>(scratch(pre_total * sizeof(T), 3, st));
     if (!pre) return VSM_ERR_HIP;
   }
   size_t off = 0;
@@ -1732,7 +1758,7 @@ static int run_layer(vsm_run* run, int ndoubl, const ST* dtau, const ST* varpi, 
     }
     for (int mode = 0; mode < 3; ++mode) {
       if (triv[mode].empty()) continue;
-      ndiag_args da;
+      ndiag_args<T> da;
       const int nt = (int)triv[mode].size();
       for (int k = 0; k < NSUB_MAX; ++k) {
         const nat_sub& sb = run->subs[triv[mode][k < nt ? k : 0]];
@@ -1740,45 +1766,37 @@ static int run_layer(vsm_run* run, int ndoubl, const ST* dtau, const ST* varpi, 
         da.gsz[k] = sb.gsz;
         da.g0[k] = sb.g[0] | (sb.g[1] << 4) | (sb.g[2] << 8) | (sb.g[3] << 12);
       }
-      hipLaunchKernelGGL((k_native_diag_layer<ST>), dim3(run->S, nt), dim3(256), 0, st, q, h.rt, h.n, ldexp(1.0, ndoubl), mode, src,
-                         dtau, da);
+      hipLaunchKernelGGL((k_native_diag_layer<T>), dim3(run->S, nt), dim3(256), 0, st, q, h.rt, h.n, (T)ldexp(1.0, ndoubl), mode,
+                         src, dtau, da);
       VSM_LAUNCH_CHECK("k_native_diag_layer");
     }
     const int nsub = (int)act.size();
     if (!nsub) continue;
-    npre_args<ST> pa;
-    nlayer_comps lc;
+    npre_args<T> pa;
+    T* lc[NSUB_MAX];
     for (int k = 0; k < NSUB_MAX; ++k) {
       const nat_sub& sb = run->subs[act[k < nsub ? k : 0]];
       pa.s[k].m = sb.m;
       pa.s[k].gsz = sb.gsz;
       for (int a = 0; a < 4; ++a) pa.s[k].g[a] = sb.g[a];
       VSM_REQUIRE(Zpp[sb.im] && Zmp[sb.im], "vsm_run_layer: null Z of moment %d", sb.im);
-      pa.s[k].z = zsrc<ST>{Zpp[sb.im], Zmp[sb.im], ncomp ? 0 : z_stride, ncomp, fcomp};
-      lc.c[k] = ws + sb.comp_off;
+      pa.s[k].z = zsrc<T>{Zpp[sb.im], Zmp[sb.im], ncomp ? 0 : z_stride, ncomp, fcomp};
+      lc[k] = ws + sb.comp_off;
     }
-    double* pre_cl = pre + off;
+    T* pre_cl = pre + off;
     off += pre_stride_rt(h.rt) * (size_t)run->S * nsub;
-    switch (h.rt) {
-      case 1: launch_pre<1, ST>(ncomp > 0, q, run->S, nsub, h.n, ndoubl, dtau, varpi, tau_sum, F0, pa, pre_cl, st); break;
-      case 2: launch_pre<2, ST>(ncomp > 0, q, run->S, nsub, h.n, ndoubl, dtau, varpi, tau_sum, F0, pa, pre_cl, st); break;
-      case 3: launch_pre<3, ST>(ncomp > 0, q, run->S, nsub, h.n, ndoubl, dtau, varpi, tau_sum, F0, pa, pre_cl, st); break;
-      case 4: launch_pre<4, ST>(ncomp > 0, q, run->S, nsub, h.n, ndoubl, dtau, varpi, tau_sum, F0, pa, pre_cl, st); break;
-      case 5: launch_pre<5, ST>(ncomp > 0, q, run->S, nsub, h.n, ndoubl, dtau, varpi, tau_sum, F0, pa, pre_cl, st); break;
-      default: launch_pre<6, ST>(ncomp > 0, q, run->S, nsub, h.n, ndoubl, dtau, varpi, tau_sum, F0, pa, pre_cl, st); break;
-    }
+    native_launch_pre(h.rt, ncomp > 0, q, run->S, nsub, h.n, ndoubl, dtau, varpi, tau_sum, F0, pa, pre_cl, st);
     VSM_LAUNCH_CHECK("k_elemental_native");
-    const int rc = launch_layer_native(h.ks, h.ks - h.kz, run->S, nsub, h.n, h.uvmask, h.gsz, ndoubl, toa, src, pre_cl, lc, status, st);
+    const int rc = native_launch_layer(h, run->S, nsub, ndoubl, toa, src, pre_cl, lc, status, st);
     if (rc) return rc;
   }
   return VSM_OK;
-  }
 }
 
-template <typename ST, typename CS, bool IMPORT>
+template <typename T, typename CS, bool IMPORT>
 static int run_convert(vsm_run* run, const CS* comps, void* stream) {
   VSM_REQUIRE(run && comps, "vsm_run_export / import: null argument");
-  VSM_REQUIRE(run->elem_size == (int)sizeof(ST), "vsm_run_export / import: the run was created for %d-byte arrays", run->elem_size);
+  VSM_REQUIRE(run->elem_size == (int)sizeof(T), "vsm_run_export / import: the run was created for %d-byte arrays", run->elem_size);
   if (run->S == 0) return VSM_OK;
   if (IMPORT) {
     run->pure_diag.assign(run->subs.size(), 0);
@@ -1789,32 +1807,27 @@ static int run_convert(vsm_run* run, const CS* comps, void* stream) {
   for (int im = 0; im < run->nm; ++im) {
     const CS& c = comps[im];
     VSM_REQUIRE(c.R_mp && c.R_pm && c.T_pp && c.T_mm && c.J0_p && c.J0_m, "vsm_run_export / import: null composite array (moment %d)", im);
-    const composite<ST> cc{c.R_mp, c.R_pm, c.T_pp, c.T_mm, c.J0_p, c.J0_m};
-    if constexpr (sizeof(ST) == 4) {
-      const int rc = native32_convert(run, im, cc, IMPORT, as_stream(stream));
-      if (rc) return rc;
-      continue;
-    }
-    const ngroup_map gm = group_map(run, im);
+    const composite<T> cc{c.R_mp, c.R_pm, c.T_pp, c.T_mm, c.J0_p, c.J0_m};
+    const ngroup_map<T> gm = group_map<T>(run, im);
     if (IMPORT)
-      hipLaunchKernelGGL((k_native_import<ST>), dim3(run->S), dim3(256), 0, as_stream(stream), run->N, run->ns, gm, cc);
+      hipLaunchKernelGGL((k_native_import<T>), dim3(run->S), dim3(256), 0, as_stream(stream), run->N, run->ns, gm, cc);
     else
-      hipLaunchKernelGGL((k_native_export<ST>), dim3(run->S), dim3(256), 0, as_stream(stream), run->N, run->ns,
+      hipLaunchKernelGGL((k_native_export<T>), dim3(run->S), dim3(256), 0, as_stream(stream), run->N, run->ns,
                          (run->flags & VSM_RUN_SOURCES_ONLY) ? 1 : 0, gm, cc);
     VSM_LAUNCH_CHECK("k_native_export / import");
   }
   return VSM_OK;
 }
 
-template <typename ST>
-static int stokes_coupling(int N, int n_stokes, int nblocks, const ST* Zpp, const ST* Zmp, int* mask_d, void* stream) {
+template <typename T>
+static int stokes_coupling(int N, int n_stokes, int nblocks, const T* Zpp, const T* Zmp, int* mask_d, void* stream) {
   VSM_REQUIRE(N > 0 && n_stokes >= 1 && n_stokes <= 4 && N % n_stokes == 0 && nblocks >= 1 && nblocks <= 65535 && Zpp && Zmp &&
                   mask_d, "vsm_stokes_coupling: bad argument");
   hipStream_t st = as_stream(stream);
   VSM_HIP(hipMemsetAsync(mask_d, 0, sizeof(int) * nblocks, st));
   const long long tot = (long long)N * N;
   const int blocks = (int)((tot + 255) / 256 < 16 ? (tot + 255) / 256 : 16);
-  hipLaunchKernelGGL((k_stokes_coupling<ST>), dim3(blocks, nblocks), dim3(256), 0, st, N, n_stokes, Zpp, Zmp, mask_d);
+  hipLaunchKernelGGL((k_stokes_coupling<T>), dim3(blocks, nblocks), dim3(256), 0, st, N, n_stokes, Zpp, Zmp, mask_d);
   VSM_LAUNCH_CHECK("k_stokes_coupling");
   return VSM_OK;
 }

@@ -409,15 +409,13 @@ __global__ __launch_bounds__(n32geo<RT>::NT, n32geo<RT>::WPS) void k_layer_nativ
 #define VSM_NATIVE32_DECL(KS) \
   int VSM_N32CAT(launch_layer_native32_, KS)(int, int, int, unsigned, int, int, int, const float*, const n32layer_comps&, int*, hipStream_t);
 
-constexpr int native32_rt_of_ks(int ks) { return (ks % 4 == 0 && ks >= 4) ? ks / 4 : (4 * ks + 2 + 15) / 16; }
-
 #ifdef VSM_NATIVE32_KS
 VSM_NATIVE32_DECL(VSM_NATIVE32_KS)
 int VSM_N32CAT(launch_layer_native32_, VSM_NATIVE32_KS)(int S, int nsub, int n, unsigned uvmask, int gsz, int ndoubl, int toa,
                                                         const float* pre, const n32layer_comps& comps, int* status, hipStream_t st) {
   constexpr int KS = VSM_NATIVE32_KS;
   // KS = 4, 8, ... 24: KS / 4 row tiles without spare columns (mat-vec source path) instead of one row tile more for two columns
-  constexpr int RT = native32_rt_of_ks(KS);
+  constexpr int RT = rt_of(4 * KS);
   static_assert(RT >= 1 && RT <= 8, "n <= 128");
   using G = n32geo<RT>;
   using SM = n32smem<RT, (4 * KS + 2 > 16 * RT)>;
@@ -431,7 +429,7 @@ int VSM_N32CAT(launch_layer_native32_, VSM_NATIVE32_KS)(int S, int nsub, int n, 
 }
 }  // namespace vsm
 
-#else  // ---- dispatcher object: pre-pass, layout conversion, the FP32 side of the run object ---------------------------------------
+#else  // ---- dispatcher object: the pre-pass and the two launches the run driver (vsm_native.hip) calls -------------------------------
 
 VSM_NATIVE32_DECL(1)
 VSM_NATIVE32_DECL(2)
@@ -468,15 +466,6 @@ VSM_NATIVE32_DECL(32)
 
 namespace {
 
-__host__ __device__ __forceinline__ int n32af_idx_rt(int rt, int row, int k) {
-  const int ks = k >> 2, kk = k & 3, rl = row & 15;
-  return (ks * rt + (row >> 4)) * 64 + ((kk << 4) | ((rl & 3) << 2) | ((rl >> 2) ^ (ks & 3)));
-}
-__host__ __device__ __forceinline__ int n32nat_idx_rt(int rt, int i, int j) {
-  const int w = j >> 4, l15 = j & 15, ta = i >> 4, mm = i & 15, kq = mm & 3, r = mm >> 2;
-  return ((w * rt + ta) * 64 + ((kq << 4) | l15)) * 4 + r;
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------
 // Elemental pre-pass: elemental! incl. the SFI source (elemental.jl:289-392) of every (point, sub-problem) of a layer as two
 // A-form images + vectors (n32geo::PRE_STRIDE), in Float32 like the reference's Float32 run (vsm_elemental.h: the formulas of the
@@ -485,25 +474,17 @@ __host__ __device__ __forceinline__ int n32nat_idx_rt(int rt, int i, int j) {
 // 4 ks + k', ks = phase, phase + 4, ... -- the four words of an image block that are adjacent (n32af_idx): ONE 16-byte store per
 // image and column, sixteen threads (kqr, k') write 256 contiguous bytes.
 // ---------------------------------------------------------------------------------------------------------------------------
-struct n32sub_pre {
-  int m, gsz;
-  int g[4];
-  zsrc<float> z;
-};
-struct n32pre_args {
-  n32sub_pre s[NSUB_MAX];
-};
 template <int RT, bool MIX>
 __global__ __launch_bounds__(64 * RT) void k_elemental_native32(quad<float> q, int n, int ndoubl, const float* __restrict__ dtau,
                                                                 const float* __restrict__ varpi, const float* __restrict__ tau_sum,
-                                                                const float* __restrict__ F0, n32pre_args a, float* __restrict__ pre) {
+                                                                const float* __restrict__ F0, npre_args<float> a, float* __restrict__ pre) {
   using G = n32geo<RT>;
   constexpr int NP = G::NP;
   __shared__ float mus[NP], xs[NP], es[NP], ems[NP], wts[NP];
   __shared__ int frow[NP];
   __shared__ int thick_flag;
   const int s = blockIdx.x, isub = blockIdx.y, tid = threadIdx.x;
-  const n32sub_pre& sp = a.s[isub];
+  const nsub_pre<float>& sp = a.s[isub];
   const int N = q.N, ns = q.n_stokes, m = sp.m, gsz = sp.gsz;
   const zsrc<float> z = sp.z;
   const float d = dtau[s], w = varpi[s];
@@ -625,146 +606,29 @@ __global__ __launch_bounds__(64 * RT) void k_elemental_native32(quad<float> q, i
   }
 }
 
-// ---------------------------------------------------------------------------------------------------------------------------
-// native (FP32 records) <-> reference layout ([N,N,S] column-major composite arrays), one workgroup per point
-// ---------------------------------------------------------------------------------------------------------------------------
-struct n32group_map {
-  int ngroups;
-  int grp_of[4];    // group of Stokes component a
-  int pos_in[4];    // its position inside the group
-  int gsz[4];       // per group
-  int rt[4];        // per group: row tiles
-  int n[4];         // per group: rows
-  float* base[4];   // per group: native composites [S] (stride COMP_STRIDE of its RT)
-};
-__global__ __launch_bounds__(256) void k_native32_export(int N, int ns, n32group_map gm, composite<float> c) {
-  const int s = blockIdx.x, tid = threadIdx.x;
-  const long long NN = (long long)N * N;
-  float* out[4] = {c.R_mp + s * NN, c.R_pm + s * NN, c.T_pp + s * NN, c.T_mm + s * NN};
-  for (int e = tid; e < N * N; e += 256) {
-    const int i = e % N, j = e / N;
-    const int ai = i % ns, aj = j % ns;
-    const int gi = gm.grp_of[ai];
-    float v[4] = {0.f, 0.f, 0.f, 0.f};
-    if (gi == gm.grp_of[aj]) {
-      const int rt = gm.rt[gi], np = 16 * rt, af = np * np;
-      const float* cn = gm.base[gi] + (long long)s * (4 * af + 2 * np);
-      const int is = (i / ns) * gm.gsz[gi] + gm.pos_in[ai], js = (j / ns) * gm.gsz[gi] + gm.pos_in[aj];
-      const int ix = n32nat_idx_rt(rt, is, js);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) v[k] = cn[k * af + ix];
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) out[k][e] = v[k];
-  }
-  if (tid < N) {
-    const int ai = tid % ns, gi = gm.grp_of[ai];
-    const int rt = gm.rt[gi], np = 16 * rt, af = np * np;
-    const float* cn = gm.base[gi] + (long long)s * (4 * af + 2 * np);
-    const int is = (tid / ns) * gm.gsz[gi] + gm.pos_in[ai];
-    c.J0_p[(long long)s * N + tid] = cn[4 * af + is];
-    c.J0_m[(long long)s * N + tid] = cn[4 * af + np + is];
-  }
-}
-// reference layout -> native (padding zero); elements that couple different groups are dropped (they are exact zeros for a
-// composite that was built under the same coupling)
-__global__ __launch_bounds__(256) void k_native32_import(int N, int ns, n32group_map gm, composite<float> c) {
-  const int s = blockIdx.x, tid = threadIdx.x;
-  const long long NN = (long long)N * N;
-  const float* in[4] = {c.R_mp + s * NN, c.R_pm + s * NN, c.T_pp + s * NN, c.T_mm + s * NN};
-  for (int g = 0; g < gm.ngroups; ++g) {
-    const int rt = gm.rt[g], np = 16 * rt, af = np * np, n = gm.n[g], gsz = gm.gsz[g];
-    float* cn = gm.base[g] + (long long)s * (4 * af + 2 * np);
-    int comp_of[4] = {0, 0, 0, 0};   // Stokes component of position k of the group
-    for (int a = 0; a < ns; ++a)
-      if (gm.grp_of[a] == g) comp_of[gm.pos_in[a]] = a;
-    for (int e = tid; e < af; e += 256) {
-      const int is = e % np, js = e / np;
-      float v[4] = {0.f, 0.f, 0.f, 0.f};
-      if (is < n && js < n) {
-        const int i = (is / gsz) * ns + comp_of[is % gsz], j = (js / gsz) * ns + comp_of[js % gsz];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = in[k][i + (long long)N * j];
-      }
-      const int ix = n32nat_idx_rt(rt, is, js);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) cn[k * af + ix] = v[k];
-    }
-    if (tid < np) {
-      float vp = 0.f, vm = 0.f;
-      if (tid < n) {
-        const int i = (tid / gsz) * ns + comp_of[tid % gsz];
-        vp = c.J0_p[(long long)s * N + i];
-        vm = c.J0_m[(long long)s * N + i];
-      }
-      cn[4 * af + tid] = vp;
-      cn[4 * af + np + tid] = vm;
-    }
-  }
+}  // namespace
+
+void native32_launch_pre(int rt, bool mix, const quad<float>& q, int S, int nsub, int n, int ndoubl, const float* dtau,
+                         const float* varpi, const float* tau_sum, const float* F0, const npre_args<float>& a, float* pre,
+                         hipStream_t st) {
+  const dim3 grid(S, nsub), block(64 * rt);
+#define VSM_N32P(RT)                                                                                                             \
+  case RT:                                                                                                                       \
+    if (mix)                                                                                                                     \
+      hipLaunchKernelGGL((k_elemental_native32<RT, true>), grid, block, 0, st, q, n, ndoubl, dtau, varpi, tau_sum, F0, a, pre);  \
+    else                                                                                                                         \
+      hipLaunchKernelGGL((k_elemental_native32<RT, false>), grid, block, 0, st, q, n, ndoubl, dtau, varpi, tau_sum, F0, a, pre); \
+    break;
+  switch (rt) { VSM_N32P(1) VSM_N32P(2) VSM_N32P(3) VSM_N32P(4) VSM_N32P(5) VSM_N32P(6) VSM_N32P(7) VSM_N32P(8) }
+#undef VSM_N32P
 }
 
-// A layer step of a sub-problem whose block of the phase matrix is exactly zero in this layer (vsm_native.hip:
-// k_native_diag_layer): T++ <- t T++, T-- <- T-- t, R+- <- t R+- t, J0+ <- t J0+ with t = e^{-dtau 2^nd / mu_i}; R-+, J0- unchanged.
-// mode 0: that scaling; 1: TOA (R = 0, T = diag(t), J = 0); 2: the composite is still diagonal: only the two diagonals change.
-struct n32diag_args {
-  float* comp[NSUB_MAX];
-  int gsz[NSUB_MAX];
-  int g0[NSUB_MAX];    // the group's Stokes components, 4 bits each
-};
-__global__ __launch_bounds__(256) void k_native32_diag_layer(quad<float> q, int rt, int n, float scale, int mode,
-                                                             const float* __restrict__ dtau, n32diag_args a) {
-  __shared__ float tt[NATIVE32_MAX_ROWS];
-  const int s = blockIdx.x, isub = blockIdx.y, tid = threadIdx.x;
-  const int np = 16 * rt, af = np * np, gsz = a.gsz[isub];
-  float* comp = a.comp[isub] + (long long)s * (4 * af + 2 * np);
-  if (tid < np) {
-    float t = 0.f;
-    if (tid < n) {
-      const int fr = (tid / gsz) * q.n_stokes + ((a.g0[isub] >> (4 * (tid % gsz))) & 15);
-      t = exp(-dtau[s] * scale / q.mu[fr]);
-    }
-    tt[tid] = t;
-    if (mode == 2 && tid < n) {
-      const int ix = n32nat_idx_rt(rt, tid, tid);
-      comp[N32_TPP * af + ix] *= t;
-      comp[N32_TMM * af + ix] *= t;
-    }
-  }
-  if (mode == 2) return;
-  const int toa = mode == 1;
-  __syncthreads();
-  for (int e = tid; e < af; e += 256) {
-    const int r = e & 3, lane = (e >> 2) & 63, ta = (e >> 8) % rt, w = (e >> 8) / rt;
-    const int i = 16 * ta + (lane >> 4) + 4 * r, j = 16 * w + (lane & 15);
-    const float ti = tt[i], tj = tt[j];
-    if (toa) {
-      const float d = (i == j) ? ti : 0.f;
-      comp[N32_RMP * af + e] = 0.f;
-      comp[N32_RPM * af + e] = 0.f;
-      comp[N32_TPP * af + e] = d;
-      comp[N32_TMM * af + e] = d;
-    } else {
-      comp[N32_RPM * af + e] *= ti * tj;
-      comp[N32_TPP * af + e] *= ti;
-      comp[N32_TMM * af + e] *= tj;
-    }
-  }
-  if (tid < np) {
-    if (toa) {
-      comp[4 * af + tid] = 0.f;
-      comp[4 * af + np + tid] = 0.f;
-    } else {
-      comp[4 * af + tid] *= tt[tid];
-    }
-  }
-}
-
-static inline size_t pre32_stride_rt(int rt) { return (size_t)2 * (16 * rt) * (16 * rt) + 3 * 16 * rt; }
-
-static int launch_layer_native32(int ks, int S, int nsub, int n, unsigned uvmask, int gsz, int ndoubl, int toa, const float* pre,
-                                 const n32layer_comps& comps, int* status, hipStream_t st) {
+int native32_launch_layer(int ks, int S, int nsub, int n, unsigned uvmask, int gsz, int ndoubl, int toa, const float* pre,
+                          float* const* comps, int* status, hipStream_t st) {
+  n32layer_comps lc;
+  for (int k = 0; k < NSUB_MAX; ++k) lc.c[k] = comps[k];
 #define VSM_N32L(KS) \
-  case KS: return VSM_N32CAT(launch_layer_native32_, KS)(S, nsub, n, uvmask, gsz, ndoubl, toa, pre, comps, status, st);
+  case KS: return VSM_N32CAT(launch_layer_native32_, KS)(S, nsub, n, uvmask, gsz, ndoubl, toa, pre, lc, status, st);
   switch (ks) {
     VSM_N32L(1) VSM_N32L(2) VSM_N32L(3) VSM_N32L(4) VSM_N32L(5) VSM_N32L(6) VSM_N32L(7) VSM_N32L(8) VSM_N32L(9) VSM_N32L(10)
     VSM_N32L(11) VSM_N32L(12) VSM_N32L(13) VSM_N32L(14) VSM_N32L(15) VSM_N32L(16) VSM_N32L(17) VSM_N32L(18) VSM_N32L(19)
@@ -775,135 +639,6 @@ static int launch_layer_native32(int ks, int S, int nsub, int n, unsigned uvmask
 #undef VSM_N32L
   set_error("launch_layer_native32: no kernel for %d k-steps", ks);
   return VSM_ERR_UNSUPPORTED;
-}
-
-template <int RT>
-static void launch_pre32(bool mix, const quad<float>& q, int S, int nsub, int n, int ndoubl, const float* dtau, const float* varpi,
-                         const float* tau_sum, const float* F0, const n32pre_args& a, float* pre, hipStream_t st) {
-  const dim3 grid(S, nsub), block(64 * RT);
-  if (mix)
-    hipLaunchKernelGGL((k_elemental_native32<RT, true>), grid, block, 0, st, q, n, ndoubl, dtau, varpi, tau_sum, F0, a, pre);
-  else
-    hipLaunchKernelGGL((k_elemental_native32<RT, false>), grid, block, 0, st, q, n, ndoubl, dtau, varpi, tau_sum, F0, a, pre);
-}
-
-}  // namespace
-
-int native32_rt_of(int n) { return native32_rt_of_ks((n + 3) / 4); }
-size_t native32_comp_stride(int rt) { return (size_t)4 * (16 * rt) * (16 * rt) + 2 * 16 * rt; }
-
-// rt_kernel!(::noRS) of one scattering layer for all moments of a Float32 run (the body of vsm_run_layer_f32 behind the coupling guard)
-int native32_run_layer(vsm_run* run, int ndoubl, const float* dtau, const float* varpi, const float* tau_sum, const float* F0, int ncomp,
-                       const float* const* Zpp, const float* const* Zmp, long long z_stride, const float* fcomp, int toa,
-                       const int* layer_coupling, int* status, hipStream_t st) {
-  const quad<float> q{static_cast<const float*>(run->mu), static_cast<const float*>(run->wt), run->N, run->ns, run->i_mu0, (float)run->mu0};
-  float* ws = static_cast<float*>(run->ws);
-  // a sub-problem whose Stokes block the layer's phase matrices leave exactly zero takes the diagonal step
-  auto trivial = [&](const nat_sub& sb) {
-    if (!layer_coupling || layer_coupling[sb.im] < 0) return false;
-    for (int a = 0; a < sb.gsz; ++a)
-      for (int b = 0; b < sb.gsz; ++b)
-        if ((layer_coupling[sb.im] >> (4 * sb.g[a] + sb.g[b])) & 1) return false;
-    return true;
-  };
-  // the pre-pass images of the layer: one record per (sub-problem, point)
-  size_t pre_total = 0;
-  for (const nat_sub& sb : run->subs)
-    if (!trivial(sb)) pre_total += pre32_stride_rt(sb.rt) * (size_t)run->S;
-  float* pre = nullptr;
-  if (pre_total) {
-    pre = static_cast<float*>(scratch(pre_total * sizeof(float), 3, st));
-    if (!pre) return VSM_ERR_HIP;
-  }
-  size_t off = 0;
-  for (const auto& cl : run->classes) {
-    const nat_sub& h = run->subs[cl[0]];
-    // diagonal steps: the full pass (mode 0 / 1 at TOA), or only the diagonals while the composite is still diagonal (mode 2)
-    std::vector<int> act, triv[3];
-    for (int i : cl) {
-      if (!trivial(run->subs[i])) {
-        act.push_back(i);
-        run->pure_diag[i] = 0;
-      } else if (toa) {
-        triv[1].push_back(i);
-        run->pure_diag[i] = 1;
-      } else {
-        triv[run->pure_diag[i] ? 2 : 0].push_back(i);
-      }
-    }
-    for (int mode = 0; mode < 3; ++mode) {
-      if (triv[mode].empty()) continue;
-      n32diag_args da;
-      const int nt = (int)triv[mode].size();
-      for (int k = 0; k < NSUB_MAX; ++k) {
-        const nat_sub& sb = run->subs[triv[mode][k < nt ? k : 0]];
-        da.comp[k] = ws + sb.comp_off;
-        da.gsz[k] = sb.gsz;
-        da.g0[k] = sb.g[0] | (sb.g[1] << 4) | (sb.g[2] << 8) | (sb.g[3] << 12);
-      }
-      hipLaunchKernelGGL(k_native32_diag_layer, dim3(run->S, nt), dim3(256), 0, st, q, h.rt, h.n, (float)ldexp(1.0, ndoubl), mode, dtau,
-                         da);
-      VSM_LAUNCH_CHECK("k_native32_diag_layer");
-    }
-    const int nsub = (int)act.size();
-    if (!nsub) continue;
-    n32pre_args pa;
-    n32layer_comps lc;
-    for (int k = 0; k < NSUB_MAX; ++k) {
-      const nat_sub& sb = run->subs[act[k < nsub ? k : 0]];
-      pa.s[k].m = sb.m;
-      pa.s[k].gsz = sb.gsz;
-      for (int a = 0; a < 4; ++a) pa.s[k].g[a] = sb.g[a];
-      VSM_REQUIRE(Zpp[sb.im] && Zmp[sb.im], "vsm_run_layer: null Z of moment %d", sb.im);
-      pa.s[k].z = zsrc<float>{Zpp[sb.im], Zmp[sb.im], ncomp ? 0 : z_stride, ncomp, fcomp};
-      lc.c[k] = ws + sb.comp_off;
-    }
-    float* pre_cl = pre + off;
-    off += pre32_stride_rt(h.rt) * (size_t)run->S * nsub;
-    switch (h.rt) {
-      case 1: launch_pre32<1>(ncomp > 0, q, run->S, nsub, h.n, ndoubl, dtau, varpi, tau_sum, F0, pa, pre_cl, st); break;
-      case 2: launch_pre32<2>(ncomp > 0, q, run->S, nsub, h.n, ndoubl, dtau, varpi, tau_sum, F0, pa, pre_cl, st); break;
-      case 3: launch_pre32<3>(ncomp > 0, q, run->S, nsub, h.n, ndoubl, dtau, varpi, tau_sum, F0, pa, pre_cl, st); break;
-      case 4: launch_pre32<4>(ncomp > 0, q, run->S, nsub, h.n, ndoubl, dtau, varpi, tau_sum, F0, pa, pre_cl, st); break;
-      case 5: launch_pre32<5>(ncomp > 0, q, run->S, nsub, h.n, ndoubl, dtau, varpi, tau_sum, F0, pa, pre_cl, st); break;
-      case 6: launch_pre32<6>(ncomp > 0, q, run->S, nsub, h.n, ndoubl, dtau, varpi, tau_sum, F0, pa, pre_cl, st); break;
-      case 7: launch_pre32<7>(ncomp > 0, q, run->S, nsub, h.n, ndoubl, dtau, varpi, tau_sum, F0, pa, pre_cl, st); break;
-      default: launch_pre32<8>(ncomp > 0, q, run->S, nsub, h.n, ndoubl, dtau, varpi, tau_sum, F0, pa, pre_cl, st); break;
-    }
-    VSM_LAUNCH_CHECK("k_elemental_native32");
-    const int rc = launch_layer_native32(h.ks, run->S, nsub, h.n, h.uvmask, h.gsz, ndoubl, toa, pre_cl, lc, status, st);
-    if (rc) return rc;
-  }
-  return VSM_OK;
-}
-
-int native32_convert(vsm_run* run, int im, const composite<float>& c, bool import, hipStream_t st) {
-  n32group_map gm;
-  gm.ngroups = 0;
-  for (int a = 0; a < 4; ++a) {
-    gm.grp_of[a] = gm.pos_in[a] = 0;
-    gm.gsz[a] = gm.rt[a] = 1;
-    gm.n[a] = 0;
-    gm.base[a] = nullptr;
-  }
-  for (const nat_sub& sb : run->subs) {
-    if (sb.im != im) continue;
-    const int g = gm.ngroups++;
-    gm.gsz[g] = sb.gsz;
-    gm.rt[g] = sb.rt;
-    gm.n[g] = sb.n;
-    gm.base[g] = static_cast<float*>(run->ws) + sb.comp_off;
-    for (int k = 0; k < sb.gsz; ++k) {
-      gm.grp_of[sb.g[k]] = g;
-      gm.pos_in[sb.g[k]] = k;
-    }
-  }
-  if (import)
-    hipLaunchKernelGGL(k_native32_import, dim3(run->S), dim3(256), 0, st, run->N, run->ns, gm, c);
-  else
-    hipLaunchKernelGGL(k_native32_export, dim3(run->S), dim3(256), 0, st, run->N, run->ns, gm, c);
-  VSM_LAUNCH_CHECK("k_native32_export / import");
-  return VSM_OK;
 }
 
 }  // namespace vsm

@@ -40,14 +40,36 @@ struct vsm_run {
 
 namespace vsm {
 
-// ---- FP32 family (vsm_native32.hip) ------------------------------------------------------------------------------------------
-constexpr int NATIVE_MAX_ROWS = 96;     // FP64 family (vsm_native.hip): blocks of up to six row tiles
+constexpr int NATIVE_MAX_ROWS = 96;      // FP64 family (vsm_native.hip): blocks of up to six row tiles
 constexpr int NATIVE32_MAX_ROWS = 128;   // FP32 family (vsm_native32.hip): up to eight row tiles
-int native32_rt_of(int n);                 // row tiles of a block of n rows
-size_t native32_comp_stride(int rt);       // floats per point of a native composite
-int native32_run_layer(vsm_run* run, int ndoubl, const float* dtau, const float* varpi, const float* tau_sum, const float* F0,
-                       int ncomp, const float* const* Zpp, const float* const* Zmp, long long z_stride, const float* fcomp, int toa,
-                       const int* layer_coupling, int* status, hipStream_t st);
-int native32_convert(vsm_run* run, int im, const composite<float>& c, bool import, hipStream_t st);
+
+// Geometry of a block of n rows, in elements of the record type (the same for both families).  Row tiles: n = 13..16, 29..32, ...
+// (a multiple of four k-steps) take ks / 4 row tiles without spare columns (mat-vec source path) instead of one row tile more for
+// the two rider columns -- as the launchers of the layer kernels choose it.
+constexpr int rt_of(int n) {
+  const int ks = (n + 3) / 4;
+  return (ks % 4 == 0 && ks >= 4) ? ks / 4 : (4 * ks + 2 + 15) / 16;
+}
+constexpr size_t comp_stride_rt(int rt) { return (size_t)4 * (16 * rt) * (16 * rt) + 2 * 16 * rt; }   // native composite of a point
+constexpr size_t pre_stride_rt(int rt) { return (size_t)2 * (16 * rt) * (16 * rt) + 3 * 16 * rt; }    // pre-pass record of a point
+
+// the sub-problems of one pre-pass launch (both elemental pre-pass kernels)
+template <typename T>
+struct nsub_pre {
+  int m, gsz;
+  int g[4];
+  zsrc<T> z;
+};
+template <typename T>
+struct npre_args {
+  nsub_pre<T> s[NSUB_MAX];
+};
+
+// ---- what the run driver (vsm_native.hip) needs from the FP32 family (vsm_native32.hip) ---------------------------------------
+void native32_launch_pre(int rt, bool mix, const quad<float>& q, int S, int nsub, int n, int ndoubl, const float* dtau,
+                         const float* varpi, const float* tau_sum, const float* F0, const npre_args<float>& a, float* pre,
+                         hipStream_t st);
+int native32_launch_layer(int ks, int S, int nsub, int n, unsigned uvmask, int gsz, int ndoubl, int toa, const float* pre,
+                          float* const* comps, int* status, hipStream_t st);   // comps: NSUB_MAX native composites
 
 }  // namespace vsm
