@@ -787,6 +787,27 @@ int vsm_level_radiance_oplevel_f32(int N, int n_stokes, int S, int nV, const int
                                    const float* bot_J0_m, float* uw, float* dw, float* dw_full, float* uw_full, float* work,
                                    void* stream);
 
+/* The level equation for several SOURCES on the same operators: the per-source slots of a multi-sensor run (the solar slot and
+ * the `:thermal` slot of rt_run_multisensor(thermal=True), vsmartmom.jl_amd/core_rt_ms.py).  The equation is linear in (a, c), so
+ * for source pairs k = 0 .. n_src-1, a_k = top_J0_p[k], c_k = bot_J0_m[k] (HOST arrays of n_src device pointers, each [N,1,S]),
+ *   dw_k = (I - A B)^-1 (a_k + A c_k),   uw_k = c_k + B dw_k
+ * come from ONE pivoted elimination of [I - A B | d_0 .. d_{n_src-1}] per point (the c_k ride as spare columns of B in the MFMA
+ * product that forms the system), A = top_R_pm, B = bot_R_mp / bot_stride as in vsm_level_radiance_*.  Outputs: the SUM over k:
+ * its VZA rows ACCUMULATED into uw / dw [nV,n_stokes,S] (row0_h / w_h as in vsm_postprocess_vza), dw_full / uw_full (nullable,
+ * [N,1,S]) the summed level vectors.  1 <= n_src <= VSM_LEVEL_MAX_SRC and N <= 128, anything else is VSM_ERR_INVALID_ARG before
+ * any launch (larger N: one vsm_level_radiance_oplevel_* call per source, whose outputs accumulate).  n_src = 1 returns the
+ * bits of vsm_level_radiance_*: same system, same pivots, same order of operations.  Status words and pivot rule as there.
+ * work is not used and may be NULL. */
+#define VSM_LEVEL_MAX_SRC 4
+int vsm_level_radiance_src_f64(int N, int n_stokes, int S, int nV, const int* row0_h, const double* w_h, const double* top_R_pm,
+                               int n_src, const double* const* top_J0_p, const double* bot_R_mp, long long bot_stride,
+                               const double* const* bot_J0_m, double* uw, double* dw, double* dw_full, double* uw_full,
+                               double* work, void* stream);
+int vsm_level_radiance_src_f32(int N, int n_stokes, int S, int nV, const int* row0_h, const float* w_h, const float* top_R_pm,
+                               int n_src, const float* const* top_J0_p, const float* bot_R_mp, long long bot_stride,
+                               const float* const* bot_J0_m, float* uw, float* dw, float* dw_full, float* uw_full, float* work,
+                               void* stream);
+
 /* The inelastic (rotational-Raman) level equation of rt_run_test_ms(::RRS) (interlayer_flux_helper!(::RRS), CoreKernel/
  * interlayer_flux.jl:21-77, applied by postprocessing_vza_ms!(::RRS), tools/postprocessing_vza_ms.jl:55-118) at ONE boundary, the
  * lines summed: for recipient point n1 and line k with donor n0 = n1 + shift[k] (in-band pairs only, 0 <= n0 < S),

@@ -155,6 +155,7 @@ _SIGS = {
     "vsm_level_radiance_work_elems": (_SZ, [_I, _I]),
     "vsm_level_radiance_{T}": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _LL, _P, _P, _P, _P, _P, _P, _P]),
     "vsm_level_radiance_oplevel_{T}": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _LL, _P, _P, _P, _P, _P, _P, _P]),
+    "vsm_level_radiance_src_{T}": (_I, [_I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _LL, _P, _P, _P, _P, _P, _P, _P]),
     "vsm_level_radiance_ie_{T}": (_I, [_I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _LL, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vsm_level_radiance_lin_{T}": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _LL, _P, _P, _P, _LL, _P, _P, _LL, _LL, _P, _P, _P, _P, _P,
                                         _P]),

@@ -1110,7 +1110,8 @@ class Scene:
         """The `:thermal` per-source slot (rt_kernel.jl:204-232, doubling.jl:62-81, interaction.jl per-source recurrences,
         postprocessing_vza.jl:68-82): the solar slot's linear source recurrences driven by the thermal source
         (vsm_thermal_source between elemental! and doubling!, the slot's own expk = 1); its J0 is added to R_SFI / T_SFI.
-        On an AddedLayer / CompositeLayer of its own (r, t, R, T evolve exactly like the solar pass's).
+        On an AddedLayer / CompositeLayer of its own (r, t, R, T evolve exactly like the solar pass's): walk layers 1..Nz
+        (_thermal_walk), surface (_thermal_surface), post-process.
 
         State, as the reference carries it (default; ThermalEmission(reset_slot_in_nonscattering_layers=True) = the corrected
         variant): the slot's j0+- belong to the AddedLayer that is allocated once per run (rt_run.jl:326-335); only the scatter
@@ -1118,67 +1119,90 @@ class Scene:
         scattering layer before it, and a column that begins with non-scattering layers enters moment m = 1 with the slot the
         last scattering layer of moment m = 0 left behind -- that is the one case in which this pass runs for m = 1 (contribute!
         itself is m = 0 only; with a zero slot on entry every later moment stays zero)."""
-        model, pol, FT = self.model, self.pol, self.FT
-        N, S = self.N, self.S
-        m = mom["m"]
+        self._thermal_begin(mom)
+        comp = self._th_comp
+        self._thermal_walk(mom, comp, 0, self.Nz)
+        surf = self._thermal_surface(mom)
+        interaction_(mom["iface_surface"], comp, surf, oplevel=True, work=self.work)
+        postprocessing_vza_(self.pol, comp, self.model.vza, self.model.vaz, self.qp, mom["m"], weight, self.R_SFI, self.T_SFI)
+
+    def _thermal_begin(self, mom):
+        """The slot's own layers (allocated on first use) and, for m = 0, the slot state of a fresh AddedLayer."""
+        N, S, FT = self.N, self.S, self.FT
         if getattr(self, "_th_added", None) is None:
             self._th_added = make_added_layer(FT, self.arch, (N, N), S, d_symmetric=0)
             self._th_surf = make_added_layer(FT, self.arch, (N, N), S, shared=not self.spectral_surface)
             self._th_comp = make_composite_layer(FT, self.arch, (N, N), S)
             self._th_F0 = torch.zeros_like(self.F0)
             self._th_ones = torch.ones(max(S, 1), dtype=self.dt, device=self.dev)
-        added, comp = self._th_added, self._th_comp
+        if mom["m"] == 0:
+            eps2 = 2 * np.finfo(FT).eps
+            scat = [ly["props"].max_tau_varpi > eps2 for ly in mom["layers"]]
+            self._th_added.j0_p.zero_()                      # a fresh AddedLayer (rt_run.jl:326-335)
+            self._th_added.j0_m.zero_()
+            self._thermal_carry = (not self.thermal_reset_noscat and any(scat) and not scat[0] and self.model.m_max >= 1)
+
+    def _thermal_walk(self, mom, comp, first, end, after=None):
+        """Layers first+1 .. end (1-based) of the slot into the thermal composite `comp`, the first one a copy.  The slot has
+        expk = 1 and no beam attenuation, so a range that starts below the TOA needs no absolute tau_sum: its first layer is the
+        `first = 1` of the fused call.  after: {l: callback(comp)}, called once layer l is in the composite (like export_at of
+        _run_layers_native: the multi-sensor run takes its thermal tops there, core_rt_ms.py)."""
+        pol, FT = self.pol, self.FT
+        N, S = self.N, self.S
+        m = mom["m"]
+        added = self._th_added
         q = self.dq.cstruct()
         eps2 = 2 * np.finfo(FT).eps
         scat = [ly["props"].max_tau_varpi > eps2 for ly in mom["layers"]]
         keep_state = not self.thermal_reset_noscat          # the reference as written
-        if m == 0:
-            added.j0_p.zero_()                               # a fresh AddedLayer (rt_run.jl:326-335)
-            added.j0_m.zero_()
-            self._thermal_carry = keep_state and any(scat) and not scat[0] and model.m_max >= 1
         # FP64, 32 < N <= 60 / FP32, 64 < N <= 96: a scattering layer's slot in ONE fused launch (vsm_layer_forward_thermal: the strip layer kernel
         # with the thermal source and expk = 1; m = 0); everything else operator level, layer by layer on the same composite.  With
         # the reference's slot state and a non-scattering layer in the column the doubled slot must stay in the AddedLayer for the
         # layers below: no fused step then (as in the solar pass, rt_kernel_'s keep_added)
         fused = (THERMAL_FUSION and m == 0 and (all(scat) or not keep_state)
                  and _lib.lib().vsm_layer_thermal_fused(N, 1 if FT == np.float64 else 0) != 0)
-        for iz, ly in enumerate(mom["layers"]):
+        for iz in range(first, end):
+            ly = mom["layers"][iz]
             props = ly["props"]
             scatter = scat[iz]
-            if (fused and scatter and (iz == 0 or ly["iface"] == "11") and iz < self.thermal_B.shape[0]
+            if (fused and scatter and (iz == first or ly["iface"] == "11") and iz < self.thermal_B.shape[0]
                     and (props.fcomp is None or props.fcomp.shape[1] <= 4)):
                 c = comp.cstruct()
                 ncomp = 0 if props.fcomp is None else int(props.fcomp.shape[1])
                 _lib.call("vsm_layer_forward_thermal", self.dt, C.byref(q), S, ly["nd"], _ptr(ly["dtau"]), _ptr(props.varpi),
                           _ptr(self.thermal_B[iz]), ncomp, _ptr(props.Zpp), _ptr(props.Zmp),
-                          0 if ncomp else props.z_stride, _ptr(props.fcomp), 1 if iz == 0 else 0, C.byref(c), _stream_ptr())
-                continue
-            if scatter:
-                # elemental! with F0 = 0 leaves j0+- = 0: the slot reset of rt_kernel.jl:217-221
-                elemental_(pol, ly["tau_sum"], ly["dtau"], self._th_F0, props.materialize(), m, ly["nd"], self.dq, added)
-                if m == 0 and iz < self.thermal_B.shape[0]:           # contribute! (isotropic: m = 0 only)
-                    a = added.cstruct()
-                    _lib.call("vsm_thermal_source", self.dt, C.byref(q), S, _ptr(ly["dtau"]), _ptr(props.varpi),
-                              _ptr(self.thermal_B[iz]), C.byref(a), _stream_ptr())
-                self._th_ones.fill_(1.0)             # doubling! squares the slot's expk in place (1 stays 1)
-                doubling_(pol, self._th_ones, ly["nd"], added)
-            elif keep_state:
-                jm = added.j0_m.clone()              # zero_added_noscat! zeroes the SOLAR j0-, never a per-source slot
-                zero_added_noscat_(added, props.tau, self.dq)
-                added.j0_m.copy_(jm)
+                          0 if ncomp else props.z_stride, _ptr(props.fcomp), 1 if iz == first else 0, C.byref(c), _stream_ptr())
             else:
-                zero_added_noscat_(added, props.tau, self.dq)
-                added.j0_p.zero_()
-                added.j0_m.zero_()
-            if iz == 0:
-                copy_added_to_composite_(comp, added)
-            else:
-                interaction_(ly["iface"], comp, added, oplevel=True, work=self.work)
-        create_surface_layer_(model.surface, self._th_surf, m, self.dq, mom["tau_sum_surface"], rho=mom["rho"])
-        self._th_surf.j0_p.zero_()      # no solar beam in this slot (surface emission is a separate source type)
+                if scatter:
+                    # elemental! with F0 = 0 leaves j0+- = 0: the slot reset of rt_kernel.jl:217-221
+                    elemental_(pol, ly["tau_sum"], ly["dtau"], self._th_F0, props.materialize(), m, ly["nd"], self.dq, added)
+                    if m == 0 and iz < self.thermal_B.shape[0]:           # contribute! (isotropic: m = 0 only)
+                        a = added.cstruct()
+                        _lib.call("vsm_thermal_source", self.dt, C.byref(q), S, _ptr(ly["dtau"]), _ptr(props.varpi),
+                                  _ptr(self.thermal_B[iz]), C.byref(a), _stream_ptr())
+                    self._th_ones.fill_(1.0)             # doubling! squares the slot's expk in place (1 stays 1)
+                    doubling_(pol, self._th_ones, ly["nd"], added)
+                elif keep_state:
+                    jm = added.j0_m.clone()              # zero_added_noscat! zeroes the SOLAR j0-, never a per-source slot
+                    zero_added_noscat_(added, props.tau, self.dq)
+                    added.j0_m.copy_(jm)
+                else:
+                    zero_added_noscat_(added, props.tau, self.dq)
+                    added.j0_p.zero_()
+                    added.j0_m.zero_()
+                if iz == first:
+                    copy_added_to_composite_(comp, added)
+                else:
+                    interaction_(ly["iface"], comp, added, oplevel=True, work=self.work)
+            if after and (iz + 1) in after:
+                after[iz + 1](comp)
+
+    def _thermal_surface(self, mom):
+        """The slot's surface layer: the solar one without its beam terms (surface emission is a separate source type)."""
+        create_surface_layer_(self.model.surface, self._th_surf, mom["m"], self.dq, mom["tau_sum_surface"], rho=mom["rho"])
+        self._th_surf.j0_p.zero_()      # no solar beam in this slot
         self._th_surf.j0_m.zero_()
-        interaction_(mom["iface_surface"], comp, self._th_surf, oplevel=True, work=self.work)
-        postprocessing_vza_(pol, comp, model.vza, model.vaz, self.qp, m, weight, self.R_SFI, self.T_SFI)
+        return self._th_surf
 
     def run_graph(self):
         """`run()` replayed from a HIP graph: the launch sequence of a scene (per moment: one launch per layer, surface,

@@ -17,6 +17,12 @@ prototype runs one interaction per sensor and layer, O(Nz K) for K sensors.  Add
 
 Per moment: Nz + (Nz - l_1) layer steps, K + 1 further interactions and at most K + 1 level calls.
 
+thermal=True adds the `:thermal` per-source slot of rt_run (Scene._thermal_slot) for m = 0, the one moment an isotropic source
+has: the same four steps on thermal composites of its own (Scene._thermal_walk: the top pass keeps J0+ after each level, the
+segments need no tau_sum), thermal bottoms built beside the solar ones, and per level ONE call of vsm_level_radiance_src_*, which
+solves the solar and the thermal right-hand side on one elimination of [I - A B | .] with A, B of the solar pass (the thermal
+composites' own R differ from them only by rounding and are not read).  DESIGN.md §4.8d.
+
 The Raman (core_rt_ms_raman.py) and linearized (core_rt_ms_lin.py) runs are the same algorithm on their own composites.  What the
 three share lives here: the level plan, the walk below the top pass (walk_levels), the two-call level of the runs that solve a
 second equation on the elastic level vectors (level_pair_), the Stokes_IQ sub-scene of m = 0 (merge_sub0), the blocks of the
@@ -24,6 +30,7 @@ spectral axis and the assembly of the results (spectral_blocks, gather_blocks).
 """
 from __future__ import annotations
 
+import ctypes as C
 import math
 from dataclasses import dataclass
 from typing import List
@@ -91,6 +98,40 @@ def level_radiance_(pol, qp, vza, vaz, m: int, weight: float, top_R_pm, top_J0_p
               P(dw), P(dw_full), P(uw_full), P(work), CR._stream_ptr())
 
 
+LEVEL_MAX_SRC = 4          # VSM_LEVEL_MAX_SRC
+
+
+def level_radiance_src_(pol, qp, vza, vaz, m: int, weight: float, top_R_pm, tops_J0_p, bot_R_mp, bots_J0_m, uw, dw,
+                        dw_full=None, uw_full=None, oplevel: bool = False):
+    """level_radiance_ for several sources on the same operators: tops_J0_p / bots_J0_m are lists of (S, N) vectors, one pair per
+    source (the solar and the thermal slot); uw / dw and dw_full / uw_full receive the SUM over the sources.  N <= 128: ONE call
+    of vsm_level_radiance_src_* (one elimination for all right-hand sides).  N > 128 or operator level: one
+    vsm_level_radiance_oplevel_* call per source, the full vectors added here."""
+    n_src = len(tops_J0_p)
+    if n_src == 0 or n_src != len(bots_J0_m):
+        raise _lib.VSMError("level_radiance_src_: %d top and %d bottom source vectors" % (n_src, len(bots_J0_m)))
+    setup = level_call_setup(pol, qp, vza, vaz, m, weight, tops_J0_p[0], bot_R_mp)
+    if setup is None:
+        return
+    S, N, dt, row0, w, bot_stride = setup
+    oplevel = oplevel or LEVEL_OPLEVEL
+    if oplevel or N > LEVEL_FUSED_MAX_N:
+        for k, (a, c) in enumerate(zip(tops_J0_p, bots_J0_m)):
+            dwk = dw_full if k == 0 or dw_full is None else torch.empty_like(dw_full)
+            uwk = uw_full if k == 0 or uw_full is None else torch.empty_like(uw_full)
+            level_radiance_(pol, qp, vza, vaz, m, weight, top_R_pm, a, bot_R_mp, c, uw, dw, dwk, uwk, oplevel=oplevel)
+            if k and dw_full is not None:
+                dw_full += dwk
+            if k and uw_full is not None:
+                uw_full += uwk
+        return
+    P = CR._ptr
+    pa = (C.c_void_p * n_src)(*[P(t) for t in tops_J0_p])      # (n_src > LEVEL_MAX_SRC: the library refuses before any launch)
+    pc = (C.c_void_p * n_src)(*[P(t) for t in bots_J0_m])
+    _lib.call("vsm_level_radiance_src", dt, N, pol.n, S, len(vza), row0, w, P(top_R_pm), n_src, pa, P(bot_R_mp), bot_stride, pc,
+              P(uw), P(dw), P(dw_full), P(uw_full), None, CR._stream_ptr())
+
+
 def level_pair_(pol, qp, vza, vaz, m: int, weight: float, top, bot_R_mp, bot_J0_m, out, second, shape2, streams: bool):
     """The level of the Raman and linearized runs: the elastic call (top[0], top[1] = R+-, J0+ of the top) into out[0], out[1],
     then second(dwf, uwf, dw2, uw2), the flavour's call on the elastic level vectors (S, N), with dw2 / uw2 `shape2` tensors for
@@ -139,7 +180,9 @@ class LevelPlan:
         return len(self.tops_at)
 
 
-def _validate(model: H.RTModel, sensor_levels) -> LevelPlan:
+def _validate(model: H.RTModel, sensor_levels, thermal: bool = False) -> LevelPlan:
+    """The level plan of a run.  thermal: ThermalEmission is accepted beside (or instead of) SolarBeam -- rt_run_multisensor's
+    thermal=True; the Raman and linearized runs leave it off."""
     Nz = int(np.asarray(model.tau_rayl).shape[1])
     levels = []
     for l in sensor_levels:
@@ -151,10 +194,15 @@ def _validate(model: H.RTModel, sensor_levels) -> LevelPlan:
     if not levels:
         raise ValueError("rt_run_multisensor: no sensor level given")
     srcs = tuple(model.sources) if model.sources is not None else (H.SolarBeam(),)
-    other = [s for s in srcs if not isinstance(s, H.SolarBeam)]
+    accepted = (H.SolarBeam, H.ThermalEmission) if thermal else (H.SolarBeam,)
+    other = [s for s in srcs if not isinstance(s, accepted)]
     if other or not srcs:
+        if thermal:
+            raise _lib.VSMError("rt_run_multisensor(thermal=True): SolarBeam and ThermalEmission are the sources of a multi-sensor "
+                                "run; got %r" % (other[0] if other else None,))
         raise _lib.VSMError("rt_run_multisensor: SolarBeam is the only source of a multi-sensor run (the prototype passes F0 alone, "
-                            "rt_kernel_multisensor.jl:21); got %r" % (other[0] if other else None,))
+                            "rt_kernel_multisensor.jl:21; CoreRT.rt_run_multisensor(..., thermal=True) also takes ThermalEmission); "
+                            "got %r" % (other[0] if other else None,))
     distinct = sorted(set(levels))
     interior = [l for l in distinct if 0 < l < Nz]
     return LevelPlan(levels, distinct, interior, interior + ([Nz] if Nz in distinct else []), interior[1:] + [Nz], Nz)
@@ -303,14 +351,19 @@ def _run(scene: CR.Scene, plan: LevelPlan, streams: bool):
     sequential = not CR.MOMENT_BATCHING or CR.REFERENCE_ORDER
     want = max(CR.MOMENT_BATCH, min(CR.MOMENT_BATCH_MAX, 4096 // max(S, 1)))
     nb = 1 if sequential else min(want, len(scene.moments))
+    thermal = scene.thermal_B is not None
     if tops_at and dev.type == "cuda":
         elt = torch.finfo(dt).bits // 8
         per_moment = len(tops_at) * (N * N + N) * S * elt + (4 * N * N + 2 * N) * S * elt
+        if thermal:   # the thermal tops (J0+ alone), counted for every moment of a group although only m = 0 keeps them
+            per_moment += len(tops_at) * N * S * elt
         free = torch.cuda.mem_get_info(dev)[0]
         nb = max(1, min(nb, int(0.5 * free // per_moment)))
     while len(scene._composites) < nb:
         scene._composites.append(CR.make_composite_layer(FT, scene.arch, (N, N), S))
     segs = [CR.make_composite_layer(FT, scene.arch, (N, N), S) for _ in range(2 if plan.interior else 0)]
+    # the thermal twin of each segment composite (m = 0 only; never in native layout: the slot's calls take the reference's arrays)
+    th_of = {id(seg): CR.make_composite_layer(FT, scene.arch, (N, N), S) for seg in segs} if thermal else {}
     native = scene._native_moments() if not CR.REFERENCE_ORDER else set()
     for c in scene._composites:
         c._sources_only = CR.REFERENCE_ORDER
@@ -352,25 +405,63 @@ def _run(scene: CR.Scene, plan: LevelPlan, streams: bool):
                 fv = {}
                 asurf = scene.added_surface
                 CR.create_surface_layer_(model.surface, asurf, m, scene.dq, mom["tau_sum_surface"], rho=mom["rho"])
+                # the thermal slot (m = 0): its top pass on the slot's own composite, J0+ kept after each level of tops_at
+                th = thermal and m == 0
+                th_tops, th_surf = {}, None
+                if th:
+                    scene._thermal_begin(mom)
+
+                    def keep_th(l):
+                        def cb(c):
+                            th_tops[l] = c.J0_p.clone()
+                        return cb
+                    scene._thermal_walk(mom, scene._th_comp, 0, Nz, after={l: keep_th(l) for l in tops_at})
+                    th_surf = scene._thermal_surface(mom)
 
                 def level(l, seg):
                     A, a = tops[k].pop(l)
                     bot_R_mp, bot_J0_m = (asurf.r_mp, asurf.j0_m) if seg is None else (seg.R_mp, seg.J0_m)
                     dwf = torch.empty((S, N), dtype=dt, device=dev) if streams else None
                     uwf = torch.empty((S, N), dtype=dt, device=dev) if streams else None
-                    level_radiance_(pol, scene.qp, model.vza, model.vaz, m, float(weight), A, a, bot_R_mp, bot_J0_m, out[l][0],
-                                    out[l][1], dwf, uwf)
+                    if th:   # the solar and the thermal right-hand side on ONE system (A, B of the solar pass)
+                        th_J0_m = th_surf.j0_m if seg is None else th_of[id(seg)].J0_m
+                        level_radiance_src_(pol, scene.qp, model.vza, model.vaz, m, float(weight), A, [a, th_tops.pop(l)], bot_R_mp,
+                                            [bot_J0_m, th_J0_m], out[l][0], out[l][1], dwf, uwf)
+                    else:
+                        level_radiance_(pol, scene.qp, model.vza, model.vaz, m, float(weight), A, a, bot_R_mp, bot_J0_m, out[l][0],
+                                        out[l][1], dwf, uwf)
                     if streams:
                         fv[l] = (uwf, dwf)
+
+                def run_segment(seg, first, end):
+                    _run_segment(scene, mom, seg, first, end)
+                    if th:
+                        scene._thermal_walk(mom, th_of[id(seg)], first, end)
+
+                def join_surface(seg):
+                    CR.interaction_(mom["iface_surface"], seg, asurf, work=scene.work)
+                    if th:
+                        CR.interaction_(mom["iface_surface"], th_of[id(seg)], th_surf, oplevel=True, work=scene.work)
+
+                def join_bottom(seg, bot, first, end):
+                    CR.interaction_("11", seg, _CompositeAsAdded(bot), work=scene.work)
+                    if th:
+                        CR.interaction_("11", th_of[id(seg)], _CompositeAsAdded(th_of[id(bot)]), oplevel=True, work=scene.work)
                 # 2.-4. the levels below the top pass
-                walk_levels(plan, segs, lambda seg, first, end: _run_segment(scene, mom, seg, first, end),
-                            lambda seg: CR.interaction_(mom["iface_surface"], seg, asurf, work=scene.work),
-                            lambda seg, bot, first, end: CR.interaction_("11", seg, _CompositeAsAdded(bot), work=scene.work), level)
-                # level 0: rt_run's surface interaction and post-processing (no Cox-Munk single-scattering correction)
+                walk_levels(plan, segs, run_segment, join_surface, join_bottom, level)
+                # level 0: rt_run's surface interaction and post-processing (no Cox-Munk single-scattering correction), then the
+                # thermal slot's, in rt_run's order of accumulation into R_SFI / T_SFI
                 CR.interaction_(mom["iface_surface"], comp, asurf, work=scene.work)
                 CR.postprocessing_vza_(pol, comp, model.vza, model.vaz, scene.qp, m, float(weight), scene.R_SFI, scene.T_SFI)
+                if th:
+                    CR.interaction_(mom["iface_surface"], scene._th_comp, th_surf, oplevel=True, work=scene.work)
+                    CR.postprocessing_vza_(pol, scene._th_comp, model.vza, model.vaz, scene.qp, m, float(weight), scene.R_SFI,
+                                           scene.T_SFI)
                 if streams:
                     fv[0] = (comp.J0_m.clone(), comp.J0_p.clone())
+                    if th:     # per-source slots added, as Scene.run(streams=...) sums J0
+                        fv[0][0].add_(scene._th_comp.J0_m)
+                        fv[0][1].add_(scene._th_comp.J0_p)
                     full[m] = fv
                 tops[k].clear()
     finally:
@@ -381,7 +472,7 @@ def _run(scene: CR.Scene, plan: LevelPlan, streams: bool):
     return out, full, weights
 
 
-def rt_run_multisensor(model: H.RTModel, sensor_levels, streams: bool = False):
+def rt_run_multisensor(model: H.RTModel, sensor_levels, streams: bool = False, thermal: bool = False):
     """rt_run_test_ms(::noRS, sensor_levels, model, iBand) (rt_run_multisensor.jl): its first two return values (uwJ, dwJ), lists
     with one [nVZA, nStokes, nSpec] host array per entry of `sensor_levels`, in the caller's order (the inelastic uwieJ / dwieJ are
     zero for noRS and not returned).
@@ -395,8 +486,15 @@ def rt_run_multisensor(model: H.RTModel, sensor_levels, streams: bool = False):
     same rows for uw and dw.
 
     streams=True: a MultiSensorResult, which also carries the level vectors at all quadrature streams per moment.
-    SolarBeam sources only; columns with a non-scattering layer raise NotImplementedError."""
-    plan = _validate(model, sensor_levels)
+    SolarBeam sources only; columns with a non-scattering layer raise NotImplementedError.
+
+    thermal=True: model.sources may hold SolarBeam and / or ThermalEmission (Scene.__init__'s rule: without a SolarBeam F0 = 0;
+    the surface layer is built as rt_run builds it, with the Lambertian beam term of DESIGN.md §6); any other source raises.  uw /
+    dw per level are the sum of the solar and the thermal slot, as rt_run's R_SFI / T_SFI are, level 0 again rt_run's result bit
+    for bit; with streams=True the level vectors of m = 0 are the sum as well.  Columns with a non-scattering layer are refused
+    as before, so the slot-state behaviour of such layers never arises here and
+    ThermalEmission.reset_slot_in_nonscattering_layers has no effect.  No surface emission."""
+    plan = _validate(model, sensor_levels, thermal=bool(thermal))
 
     def run_block(_sl):
         scene = CR.prepare_scene(model)

@@ -16,6 +16,8 @@
 // 21-77), per recipient point with the lines summed before ONE solve of the same [I - A B | r] (k_level_radiance_ie, below).
 // vsm_level_radiance_lin_*: its derivative with respect to the Jacobian parameters, the parameters as extra right-hand sides of
 // ONE solve per chunk (k_level_radiance_lin, below).
+// vsm_level_radiance_src_*: the same equation for up to VSM_LEVEL_MAX_SRC source pairs (a_k, c_k) on the same A, B (the solar and
+// the thermal slot), the pairs as right-hand sides of ONE solve, their level vectors summed (k_level_radiance_src, below).
 #include "vsm_common.h"
 #include "vsm_internal.h"
 #include "vsm_inverse.h"
@@ -161,6 +163,80 @@ __global__ void __launch_bounds__(LEVEL_NT) k_level_radiance(int N, int ns, int 
                        sh, status);
 }
 
+// The level equation for K = n_src source pairs (a_k, c_k) on the SAME operators (vsm_level_radiance_src_*: the solar and the
+// thermal slot of a multi-sensor run), point s = blockIdx.x:
+//   [M | d_1 .. d_K] = [I - A B | a_k + A c_k] (level_form_system, the c_k as spare columns of B), ONE Gauss-Jordan elimination,
+//   dw_k = column / m_ii (in place),  uw_k = c_k + B dw_k (into Q),
+// then the SUM over k: dw_full / uw_full [N,1,S] (nullable) and the VZA rows accumulated into uw / dw.  K = 1 is k_level_radiance
+// operation for operation.  LDS: L [N][N + K], Q [K][N].
+template <typename T>
+struct level_srcs {
+  const T* a[VSM_LEVEL_MAX_SRC];
+  const T* c[VSM_LEVEL_MAX_SRC];
+};
+
+template <typename T>
+__global__ void __launch_bounds__(LEVEL_NT) k_level_radiance_src(int N, int ns, int K, int nV, level_pp pa, const T* __restrict__ A,
+                                                                 level_srcs<T> src, const T* __restrict__ B, long long bstride,
+                                                                 T* uw, T* dw, T* dw_full, T* uw_full, int* status) {
+  extern __shared__ __align__(16) unsigned char lds_raw[];
+  const int LD = N + K;
+  T* L = reinterpret_cast<T*>(lds_raw);          // [M | d_1 .. d_K], row-major, leading dimension N + K
+  T* Q = L + (size_t)N * LD;                     // c_k, then uw_k
+  __shared__ int sh[2];
+  const int tid = threadIdx.x;
+  const long long s = blockIdx.x;
+  const T* Bs = B + s * bstride;
+  if (tid == 0) sh[1] = 0;
+#pragma unroll
+  for (int k = 0; k < VSM_LEVEL_MAX_SRC; ++k) {
+    if (k < K) {
+      for (int i = tid; i < N; i += LEVEL_NT) {
+        L[i * LD + N + k] = src.a[k][s * N + i];
+        Q[k * N + i] = src.c[k][s * N + i];
+      }
+    }
+  }
+  __syncthreads();
+  level_form_system<T>(N, N + K, LD, A + s * (long long)N * N, Bs, Q, L, sh, status);
+  level_eliminate<T>(N, N + K, LD, L, sh, status);
+  for (int e = tid; e < N * K; e += LEVEL_NT) {
+    const int i = e % N, k = e / N;
+    L[i * LD + N + k] = L[i * LD + N + k] / L[i * LD + i];
+  }
+  __syncthreads();
+  for (int e = tid; e < N * K; e += LEVEL_NT) {
+    const int i = e % N, k = e / N;
+    T y = Q[k * N + i];
+    for (int j = 0; j < N; ++j) y += Bs[(long long)j * N + i] * L[j * LD + N + k];
+    Q[k * N + i] = y;
+  }
+  __syncthreads();
+  if (dw_full || uw_full) {
+    for (int i = tid; i < N; i += LEVEL_NT) {
+      T x = L[i * LD + N], y = Q[i];
+      for (int k = 1; k < K; ++k) {
+        x += L[i * LD + N + k];
+        y += Q[k * N + i];
+      }
+      if (dw_full) dw_full[s * N + i] = x;
+      if (uw_full) uw_full[s * N + i] = y;
+    }
+  }
+  for (int e = tid; e < nV * ns; e += LEVEL_NT) {
+    const int v = e % nV, c = e / nV, row = pa.row0[v] + c;
+    const T w = (T)pa.w[v + nV * c];
+    T x = L[row * LD + N], y = Q[row];
+    for (int k = 1; k < K; ++k) {
+      x += L[row * LD + N + k];
+      y += Q[k * N + row];
+    }
+    const long long dst = (s * ns + c) * nV + v;
+    uw[dst] += w * y;
+    dw[dst] += w * x;
+  }
+}
+
 // The column-group streaming of the inelastic and the linearized kernel.  Thread (g, i) = (tid / N, tid % N) of the G = 256 / N
 // column groups takes row i of columns j = g, g + G, ... of a block [M | v] (column N = the vector, taken by the group next in
 // turn), so the workgroup reads G consecutive columns, G N contiguous elements, per step.  level_stream_pair adds [M1 | v1] x1 to
@@ -282,6 +358,38 @@ static int level_radiance_fused(int N, int ns, int S, int nV, const int* row0_h,
         hipLaunchKernelGGL(k_level_radiance<T>, dim3(S), dim3(LEVEL_NT), lds, st, N, ns, nv, nv, pa, A, a, B, bstride, c, uw, dw, dwf,
                            uwf, status);
         VSM_LAUNCH_CHECK("k_level_radiance");
+        return (int)VSM_OK;
+      },
+      [&](const T* uwf, const T* dwf) { return postprocess_vza<T>(N, ns, S, nV, row0_h, w_h, uwf, dwf, uw, dw, st); });
+}
+
+// LDS of k_level_radiance_src against the budget of level_lin_chunk (160 KiB less room for the static words)
+template <typename T>
+static size_t level_src_lds(int N, int K) {
+  return ((size_t)N * (N + K) + (size_t)K * N) * sizeof(T);
+}
+
+template <typename T>
+static int level_radiance_src_fused(int N, int ns, int S, int nV, const int* row0_h, const T* w_h, const T* A, int K,
+                                    const T* const* a, const T* B, long long bstride, const T* const* c, T* uw, T* dw, T* dw_full,
+                                    T* uw_full, hipStream_t st) {
+  int* status = device_status();
+  if (!status) return VSM_ERR_HIP;
+  const size_t lds = level_src_lds<T>(N, K);
+  VSM_REQUIRE(lds <= 160 * 1024 - 256, "level_radiance_src: N = %d with %d sources needs %zu bytes of LDS", N, K, lds);
+  const int rc = ensure_dyn_lds(reinterpret_cast<const void*>(k_level_radiance_src<T>), lds, "hipFuncSetAttribute(k_level_radiance_src)");
+  if (rc) return rc;
+  level_srcs<T> src = {};
+  for (int k = 0; k < K; ++k) {
+    src.a[k] = a[k];
+    src.c[k] = c[k];
+  }
+  return level_launch<T>(
+      ns, nV, row0_h, w_h, (size_t)N * S, dw_full, uw_full, st,
+      [&](int nv, const level_pp& pa, T* dwf, T* uwf) {
+        hipLaunchKernelGGL(k_level_radiance_src<T>, dim3(S), dim3(LEVEL_NT), lds, st, N, ns, K, nv, pa, A, src, B, bstride, uw, dw,
+                           dwf, uwf, status);
+        VSM_LAUNCH_CHECK("k_level_radiance_src");
         return (int)VSM_OK;
       },
       [&](const T* uwf, const T* dwf) { return postprocess_vza<T>(N, ns, S, nV, row0_h, w_h, uwf, dwf, uw, dw, st); });
@@ -460,6 +568,17 @@ static int level_check(int N, int ns, int S, int nV, const int* row0_h, const T*
 }
 
 template <typename T>
+static int level_src_check(int N, int ns, int S, int nV, const int* row0_h, const T* w_h, const T* A, int K, const T* const* a,
+                           const T* B, long long bstride, const T* const* c, T* uw, T* dw) {
+  VSM_REQUIRE(K >= 1 && K <= VSM_LEVEL_MAX_SRC, "level_radiance_src: n_src = %d outside 1..%d", K, (int)VSM_LEVEL_MAX_SRC);
+  const int rc = level_check_common<T>("level_radiance_src", N, LEVEL_FUSED_MAX_N, ns, S, nV, row0_h, w_h, bstride, uw, dw);
+  if (rc) return rc;
+  VSM_REQUIRE(S == 0 || (A && B && a && c), "level_radiance_src: null operand");
+  for (int k = 0; k < K && S > 0; ++k) VSM_REQUIRE(a[k] && c[k], "level_radiance_src: null source %d", k);
+  return VSM_OK;
+}
+
+template <typename T>
 static int level_ie_check(int N, int ns, int S, int K, const int* shift, int nV, const int* row0_h, const T* w_h, const T* A,
                           const T* B, long long bstride, const T* dwf, const T* uwf, const T* Aie, const T* aie, const T* Bie,
                           const T* cie, T* uwie, T* dwie) {
@@ -524,7 +643,21 @@ size_t vsm_level_radiance_work_elems(int N, int S) {
 VSM_LEVEL_API(double, f64)
 VSM_LEVEL_API(float, f32)
 
-#define VSM_LEVEL_IE_API(T, SFX)                                                                                                \
+#define VSM_LEVEL_SRC_API(T, SFX)                                                                                               \
+  int vsm_level_radiance_src_##SFX(int N, int n_stokes, int S, int nV, const int* row0_h, const T* w_h, const T* top_R_pm,     \
+                                   int n_src, const T* const* top_J0_p, const T* bot_R_mp, long long bot_stride,              \
+                                   const T* const* bot_J0_m, T* uw, T* dw, T* dw_full, T* uw_full, T* work, void* stream) {   \
+    (void)work;                                                                                                                \
+    int rc = level_src_check<T>(N, n_stokes, S, nV, row0_h, w_h, top_R_pm, n_src, top_J0_p, bot_R_mp, bot_stride, bot_J0_m,   \
+                                uw, dw);                                                                                       \
+    if (rc || S == 0) return rc;                                                                                               \
+    return level_radiance_src_fused<T>(N, n_stokes, S, nV, row0_h, w_h, top_R_pm, n_src, top_J0_p, bot_R_mp, bot_stride,      \
+                                       bot_J0_m, uw, dw, dw_full, uw_full, as_stream(stream));                                \
+  }
+VSM_LEVEL_SRC_API(double, f64)
+VSM_LEVEL_SRC_API(float, f32)
+
+#define VSM_LEVEL_IE_API(T, SFX)                                                                                               \
   int vsm_level_radiance_ie_##SFX(int N, int n_stokes, int S, int K, const int* shift, int nV, const int* row0_h, const T* w_h,  \
                                   const T* top_R_pm, const T* bot_R_mp, long long bot_stride, const T* dw_full,               \
                                   const T* uw_full, const T* top_ieR_pm, const T* top_ieJ0_p, const T* bot_ieR_mp,            \
