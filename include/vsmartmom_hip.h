@@ -634,9 +634,34 @@ int vsm_mix_Z_moments_f32(int N, int S, int ncomp, int nm, const float* const* Z
  * the dense products, bit for bit.  The composite must then come from this run's own layer steps: vsm_run_import drops the flag
  * for the rest of the run (a caller's arrays need not have those zero columns).  R+-, T--, J0+- (and R-+, T++ of a full run) equal
  * those of a run without the flag up to rounding.  FP64 runs only: an _f32 run accepts the flag and ignores it.
+ * Viewing rows.  A sources-only run whose caller reads T-- and J0- in a few rows alone: rt_run's SFI outputs after a surface step,
+ * where T-- enters only as the left operand of T01_inv = T-- G1 (row i of it and of the new J0- needs row i of T-- and J0- only,
+ * interaction.jl:207-266), postprocessing_vza! reads J0- at the n_stokes rows of each VZA node, and interaction_hdrf! reads J0+
+ * alone.  Two equal ways to create one: vsm_run_create_view_* with flags = VSM_RUN_SOURCES_ONLY | VSM_RUN_VIEW_ROWS and rows_h[nrows]
+ * (global rows 0 .. N - 1, distinct, 1 <= nrows <= VSM_RUN_VIEW_MAX), or vsm_run_view_rows(run, nrows, rows_h) on a sources-only
+ * run before its first layer step and before any vsm_run_import.  The flag is valid only with VSM_RUN_SOURCES_ONLY; vsm_run_create_ex_*
+ * with it has no list and is refused, as is a list that is empty or too long (no silent fallback).  The layer steps carry T-- as
+ * nrows row vectors: they pass through the product T-- W as ONE row tile (1 / RT of the product's MFMAs) and J0- is updated in
+ * those rows only; the full T-- record is neither read nor written.  Every element goes through the operations of the full
+ * product, so T-- and J0- in the viewing rows, R+- and J0+ equal those of a plain sources-only run bit for bit.  vsm_run_export
+ * writes T-- and J0- valid in the viewing rows and quiet NaN elsewhere (undefined, never stale); vsm_run_import reads T-- and J0-
+ * in the viewing rows only.  FP64 runs only: an _f32 run accepts the calls and keeps the full recurrences.
+ * Viewing rows.  vsm_run_create_view_* with flags = VSM_RUN_SOURCES_ONLY | VSM_RUN_VIEW_ROWS (the second flag is valid only with the
+ * first and only through this entry point) and rows_h[nrows] (global rows 0 .. N - 1, 1 <= nrows <= VSM_RUN_VIEW_MAX, distinct)
+ * (or vsm_run_view_rows(run, nrows, rows_h) on a sources-only run before its first layer step: the same; vsm_run_create_ex_* with
+ * the flag has no list and is refused)
+ * creates a sources-only run for callers that read T-- and J0- in those rows alone: rt_run's SFI outputs after a surface step,
+ * where T-- enters only as the left operand of T01_inv = T-- G1 (row i of it and of the new J0- needs row i of T-- and J0- only,
+ * interaction.jl:207-266), postprocessing_vza! reads J0- at the n_stokes rows of each VZA node, and interaction_hdrf! reads J0+
+ * alone.  The layer steps carry T-- as nrows row vectors (row v of T--' = T-- W is (row v of T--) W: a handful of vector x matrix
+ * products instead of one matrix product) and update J0- in those rows only; the full T-- record is neither read nor written.
+ * vsm_run_export writes T-- and J0- valid in the viewing rows and quiet NaN elsewhere (undefined, never stale); vsm_run_import
+ * reads T-- and J0- in the viewing rows only.  R+- and J0+ are those of a sources-only run; T-- and J0- in the viewing rows
+ * equal its values up to rounding.  FP64 runs only: an _f32 run accepts the call and keeps the full recurrences.
  * Stream: see Conventions; library scratch (the pre-pass images of the layer). */
 typedef struct vsm_run vsm_run;
-enum { VSM_RUN_SOURCES_ONLY = 1, VSM_RUN_ZW_TAIL = 2 };
+enum { VSM_RUN_SOURCES_ONLY = 1, VSM_RUN_ZW_TAIL = 2, VSM_RUN_VIEW_ROWS = 4 };
+enum { VSM_RUN_VIEW_MAX = 16 };   /* viewing rows per run: four VZAs x IQUV */
 int vsm_run_supported(int N, int n_stokes, int coupling);
 size_t vsm_run_workspace_bytes(int N, int n_stokes, int S, int nm, const int* coupling_h);
 int vsm_run_supported_f32(int N, int n_stokes, int coupling);
@@ -649,6 +674,14 @@ int vsm_run_create_ex_f64(const vsm_quad_f64* q, int S, int nm, const int* m_h, 
                           size_t workspace_bytes, unsigned flags, vsm_run** run);
 int vsm_run_create_ex_f32(const vsm_quad_f32* q, int S, int nm, const int* m_h, const int* coupling_h, void* workspace,
                           size_t workspace_bytes, unsigned flags, vsm_run** run);
+int vsm_run_create_view_f64(const vsm_quad_f64* q, int S, int nm, const int* m_h, const int* coupling_h, void* workspace,
+                            size_t workspace_bytes, unsigned flags, int nrows, const int* rows_h, vsm_run** run);
+int vsm_run_create_view_f32(const vsm_quad_f32* q, int S, int nm, const int* m_h, const int* coupling_h, void* workspace,
+                            size_t workspace_bytes, unsigned flags, int nrows, const int* rows_h, vsm_run** run);
+int vsm_run_create_view_f64(const vsm_quad_f64* q, int S, int nm, const int* m_h, const int* coupling_h, void* workspace,
+                            size_t workspace_bytes, unsigned flags, int nrows, const int* rows_h, vsm_run** run);
+int vsm_run_create_view_f32(const vsm_quad_f32* q, int S, int nm, const int* m_h, const int* coupling_h, void* workspace,
+                            size_t workspace_bytes, unsigned flags, int nrows, const int* rows_h, vsm_run** run);
 int vsm_run_layer_f64(vsm_run* run, int ndoubl, const double* dtau, const double* varpi, const double* tau_sum,
                       const double* F0, int ncomp, const double* const* Zpp, const double* const* Zmp, long long z_stride,
                       const double* fcomp, int toa, const int* layer_coupling_h, void* stream);
@@ -660,6 +693,14 @@ int vsm_run_export_f32(vsm_run* run, const vsm_composite_f32* comps, void* strea
 int vsm_run_import_f64(vsm_run* run, const vsm_composite_f64* comps, void* stream);
 int vsm_run_import_f32(vsm_run* run, const vsm_composite_f32* comps, void* stream);
 int vsm_run_zw_tail(vsm_run* run);
+int vsm_run_view_rows(vsm_run* run, int nrows, const int* rows_h);
+/* block `block` (0 .. blocks - 1, moment-major; VSM_ERR_INVALID_ARG past the last) of the run: its moment index, its rows and the
+ * viewing rows that fall into it as local rows (local_rows[VSM_RUN_VIEW_MAX]; *nv = 0: the block carries no row of T--) */
+int vsm_run_view_block(const vsm_run* run, int block, int* im, int* n, int* nv, int* local_rows);
+int vsm_run_view_rows(vsm_run* run, int nrows, const int* rows_h);
+/* block `block` (0 .. blocks - 1, moment-major; VSM_ERR_INVALID_ARG past the last) of the run: its moment index, its rows and the
+ * viewing rows that fall into it as local rows (local_rows[VSM_RUN_VIEW_MAX]; *nv = 0: the block carries no row of T--) */
+int vsm_run_view_block(const vsm_run* run, int block, int* im, int* n, int* nv, int* local_rows);
 int vsm_run_destroy(vsm_run* run);
 int vsm_stokes_coupling_f64(int N, int n_stokes, int nblocks, const double* Zpp, const double* Zmp, int* mask_d, void* stream);
 int vsm_stokes_coupling_f32(int N, int n_stokes, int nblocks, const float* Zpp, const float* Zmp, int* mask_d, void* stream);

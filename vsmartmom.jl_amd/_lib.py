@@ -146,10 +146,13 @@ _SIGS = {
     "vsm_run_workspace_bytes_f32": (_SZ, [_I, _I, _I, _I, _P]),
     "vsm_run_create_{T}": (_I, [_P, _I, _I, _P, _P, _P, _SZ, _P]),
     "vsm_run_create_ex_{T}": (_I, [_P, _I, _I, _P, _P, _P, _SZ, C.c_uint, _P]),
+    "vsm_run_create_view_{T}": (_I, [_P, _I, _I, _P, _P, _P, _SZ, C.c_uint, _I, _P, _P]),
     "vsm_run_layer_{T}": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _P, _LL, _P, _I, _P, _P]),
     "vsm_run_export_{T}": (_I, [_P, _P, _P]),
     "vsm_run_import_{T}": (_I, [_P, _P, _P]),
     "vsm_run_zw_tail": (_I, [_P]),
+    "vsm_run_view_rows": (_I, [_P, _I, _P]),
+    "vsm_run_view_block": (_I, [_P, _I, _P, _P, _P, _P]),
     "vsm_run_destroy": (_I, [_P]),
     "vsm_stokes_coupling_{T}": (_I, [_I, _I, _I, _P, _P, _P, _P]),
     "vsm_level_radiance_work_elems": (_SZ, [_I, _I]),

@@ -41,6 +41,9 @@ THERMAL_FUSION = True   # False: the `:thermal` slot at operator level (tools/th
 NATIVE_RUN = True       # False: the layer loop on the reference-layout CompositeLayer (vsm_layer_forward_multi) instead of vsm_run_*
 NATIVE_SOURCES_ONLY = True  # Scene.run without `streams`: the native run keeps only R+-, T-- and J0+- of the composite (vsm_run_create_ex,
 #                         VSM_RUN_SOURCES_ONLY: the SFI outputs read nothing else); its exported R-+ / T++ are NaN.  False: full runs
+NATIVE_VIEW_ROWS = True  # ... and carries T-- / J0- in the rows of the VZA nodes alone (vsm_run_view_rows, VSM_RUN_VIEW_ROWS: nothing
+#                         below the layer walk reads another row); its exported T-- / J0- are NaN elsewhere.  False: the whole T--
+VIEW_ROWS_MAX = 16      # VSM_RUN_VIEW_MAX of the library: with more viewing rows the run stays a plain sources-only run
 NATIVE_ZW_TAIL = True   # Scene's native runs skip the k-steps of the zero-weight VZA / SZA streams in every product (vsm_run_zw_tail =
 #                         VSM_RUN_ZW_TAIL: those columns are zero off the diagonal in every matrix of the layer steps).  False: dense
 NATIVE_DROPIN = True    # rt_kernel_ keeps the CompositeLayer it is handed in the kernels' native layout between its calls (a per-
@@ -203,6 +206,7 @@ class CompositeLayer:
         z = lambda: torch.zeros((nSpec, N, N), dtype=dt, device=dev)
         self._native = None       # NativeSlot while rt_kernel_ keeps this composite in the kernels' strip layout
         self._sources_only = False  # set by Scene.run for its own walk: the native copy may be a sources-only run (R-+, T++ NaN)
+        self._view_rows = None      # ... and with it the rows of T-- / J0- that walk reads (view_rows_of): a view-row run
         self._native_ws = None    # its workspace (grow-only, reused from moment to moment)
         # the reference's arrays; read through the properties below, which bring them up to date first
         self._arr = dict(R_mp=z(), R_pm=z(), T_pp=z(), T_mm=z(), J0_p=torch.zeros((nSpec, N), dtype=dt, device=dev),
@@ -608,6 +612,29 @@ def run_workspace_bytes(dtype, N: int, ns: int, S: int, nm: int, carr) -> int:
     return int((L.vsm_run_workspace_bytes_f32 if dtype == torch.float32 else L.vsm_run_workspace_bytes)(N, ns, S, nm, carr))
 
 
+def view_rows_of(pol, vza, qp) -> list:
+    """The rows of the composite that postprocessing_vza_ reads (its index rule): the n_stokes rows of each VZA's quadrature node,
+    each node once."""
+    n, rows = pol.n, []
+    for v in range(len(vza)):
+        imu = int(np.argmin(np.abs(qp.qp_mu - qp.qp_mu.dtype.type(H.cosd(vza[v])))))
+        rows += [imu * n + k for k in range(n) if imu * n + k not in rows]
+    return rows
+
+
+def run_create_(dtype, q, S: int, nm: int, marr, carr, ws, nbytes: int, sources_only: bool, view_rows, run) -> None:
+    """vsm_run_create_ex from the A/B switches: sources_only -> VSM_RUN_SOURCES_ONLY; with it, view_rows (a list of rows, or None)
+    -> vsm_run_view_rows (VSM_RUN_VIEW_ROWS) for FP64 runs whose list fits the library's maximum."""
+    flags = 1 if (sources_only and NATIVE_SOURCES_ONLY) else 0   # VSM_RUN_SOURCES_ONLY
+    _lib.call("vsm_run_create_ex", dtype, C.byref(q), S, nm, marr, carr, _ptr(ws), nbytes, flags, C.byref(run))
+    if flags and NATIVE_VIEW_ROWS and view_rows and len(view_rows) <= VIEW_ROWS_MAX and dtype == torch.float64:
+        L = _lib.lib()
+        rc = L.vsm_run_view_rows(run, len(view_rows), (C.c_int * len(view_rows))(*[int(r) for r in view_rows]))
+        if rc:
+            L.vsm_run_destroy(run)
+            _lib.check(rc)
+
+
 def _native_open(comp: CompositeLayer, dq: DeviceQuad, m: int, mask: int, import_arrays: bool) -> bool:
     """make_composite_layer in native layout for ONE Fourier moment (vsm_run_create on the composite's own workspace);
     import_arrays: continue from the composite's current [N,N,S] arrays (vsm_run_import).  False: the blocks do not fit."""
@@ -623,8 +650,7 @@ def _native_open(comp: CompositeLayer, dq: DeviceQuad, m: int, mask: int, import
     q = dq.cstruct()
     comp._native_q = (q, dq)                     # (the run keeps q's mu / wt pointers: they must outlive it)
     run = C.c_void_p()
-    flags = 1 if (comp._sources_only and NATIVE_SOURCES_ONLY) else 0   # VSM_RUN_SOURCES_ONLY
-    _lib.call("vsm_run_create_ex", comp.dtype, C.byref(q), S, 1, marr, carr, _ptr(ws), nbytes, flags, C.byref(run))
+    run_create_(comp.dtype, q, S, 1, marr, carr, ws, nbytes, comp._sources_only, comp._view_rows, run)
     if import_arrays:
         try:
             cc = (_lib.vsm_composite * 1)(comp._cstruct_raw())
@@ -1004,14 +1030,21 @@ class Scene:
         # (nothing of this walk reads R-+ / T++ of its composites unless `streams` asks for them: the REFERENCE_ORDER walk lets the
         #  drop-in registry run sources-only too -- the same kernels as _run_layers_native, the same bits)
         walk_src = streams is None and trace is None and not has_noscat
+        # (... nor any row of T-- / J0- but those of the VZA nodes: postprocessing_vza_ reads J0- there, the surface step has T-- as a
+        #  left operand only, interaction_hdrf_ reads J0+ alone)
+        if getattr(self, "_view_rows", None) is None:      # (the quadrature and the VZAs are the scene's: computed once)
+            self._view_rows = view_rows_of(pol, model.vza, self.qp)
+        view_rows = self._view_rows if streams is None else None
         for c in self._composites:
             c._sources_only = walk_src and REFERENCE_ORDER
+            c._view_rows = view_rows if c._sources_only else None
         for g0 in range(0, len(self.moments), nb):
             group = self.moments[g0:g0 + nb]
             comps = self._composites[:len(group)]
             nat = [k for k in range(len(group)) if (g0 + k) in native]
             if nat:   # the layer loop on the native-layout composite (vsm_run_*), then the reference's arrays for the surface step
-                self._run_layers_native([group[k] for k in nat], [comps[k] for k in nat], sources_only=streams is None)
+                self._run_layers_native([group[k] for k in nat], [comps[k] for k in nat], sources_only=streams is None,
+                                        view_rows=view_rows)
             rest = [k for k in range(len(group)) if (g0 + k) not in native]
             group_l, comps_l = [group[k] for k in rest], [comps[k] for k in rest]
             for iz in range(self.Nz if rest else 0):
@@ -1045,6 +1078,7 @@ class Scene:
                     streams.append(dict(m=m, weight=float(weight), R_mp=comp.R_mp.clone(), T_pp=comp.T_pp.clone(), J0_m=Jm, J0_p=Jp))
         for c in self._composites:
             c._sources_only = False
+            c._view_rows = None
         if isinstance(model.surface, H.CoxMunkSurface) and self.ss_correction:   # rt_run.jl:520-524 (SFI is always on here)
             apply_ss_correction_(self.R_SFI, model.surface, pol, model.vza, model.vaz, self.qp.mu0,
                                  self.moments[-1]["tau_sum_surface"], model.m_max, self.arch, FT)
@@ -1063,11 +1097,13 @@ class Scene:
                 return set()
         return {i for i, mom in enumerate(self.moments) if run_supported(self.dt, self.N, self.pol.n, int(self.coupling[mom["m"]]))}
 
-    def _run_layers_native(self, group, comps, sources_only: bool = True, export_at=None):
+    def _run_layers_native(self, group, comps, sources_only: bool = True, export_at=None, view_rows=None):
         """rt_run's layer loop (rt_run.jl:383-453) for the moments of `group` with the CompositeLayer in kernel-native layout:
         vsm_run_create -> Nz x vsm_run_layer -> vsm_run_export into the reference-layout CompositeLayers `comps`.
         sources_only (and NATIVE_SOURCES_ONLY): only R+-, T-- and J0+- of `comps` are computed, R-+ and T++ come back as NaN --
         for callers that read the composite through the surface step and the SFI post-processing alone.
+        view_rows (with sources_only, and NATIVE_VIEW_ROWS): the caller reads T-- and J0- in these rows only (Scene.run without
+        `streams`: view_rows_of) -- they come back as NaN in every other row.
         export_at: {l: callback} -- after layer l (1-based) the run is also exported into `comps` (the run itself goes on
         unchanged) and callback(comps) is called: the multi-sensor run takes its top composites there (core_rt_ms.py)."""
         L = _lib.lib()
@@ -1080,8 +1116,7 @@ class Scene:
             ws = self._native_ws = _lib.poison(torch.empty(max(nbytes // 8, 2), dtype=torch.float64, device=self.dev))
         q = self.dq.cstruct()
         run = C.c_void_p()
-        flags = 1 if (sources_only and NATIVE_SOURCES_ONLY) else 0   # VSM_RUN_SOURCES_ONLY
-        _lib.call("vsm_run_create_ex", self.dt, C.byref(q), S, nm, marr, carr, _ptr(ws), nbytes, flags, C.byref(run))
+        run_create_(self.dt, q, S, nm, marr, carr, ws, nbytes, sources_only, view_rows, run)
         try:
             # VSM_RUN_ZW_TAIL (the run starts from its own TOA layer).  Its synchronous read of the weights cannot be captured into
             # a graph: a captured run keeps the dense products -- the same bits wherever no pivoted inverse is taken

@@ -359,10 +359,19 @@ __device__ __forceinline__ void nia_body_native(nsmem<RT, (4 * KS + 2 > 16 * RT)
 //   [T--' | T-- g] = T-- [W | g] ;  [R+-' | J0+'] = [r+- | j0+ + t++ J0+] + P [W | g]     A = P = [T--], Q = [P]
 // Products: 2 + the inverse + 1 + 2: four plus the series order (nine at order 7, four products of ninvert7), against the full
 // body's nine plus the order.  At most five live strips.  Blocks without spare columns take the source terms by mat-vecs.
+// VW: a view-row run (VSM_RUN_VIEW_ROWS): everything below the layer walk reads T-- and J0- row-wise, at the run's viewing rows
+// (row i of T--' = T-- W and of J0-' = J0- + T-- g needs row i of T-- only; the surface step has T-- as a left operand alone).  The
+// block's nv <= 16 rows of T-- live as row vectors of NP doubles at the head of the T-- record (row v at T_mm + v NP, plain column
+// order) and pass through the free A-form P as ONE row tile:
+//   y = T--[V, :] [W | g]        KS MFMAs per wave instead of RT KS; column c1 of y is the J0- increment of the viewing rows
+// -- per element the very operations of the full body's product (k-steps in order, the zero-weight tail's diagonal term last), so
+// the viewing rows equal those of a plain sources-only run bit for bit.  No [T--] A-form of RT^2 tiles; the T-- record is neither
+// read nor written, J0- is defined in the viewing rows only.
 // ---------------------------------------------------------------------------------------------------------------------------
-template <int RT, int KS, int KZ = KS>
+template <int RT, int KS, int KZ = KS, bool VW = false>
 __device__ __forceinline__ void nia_body_src(nsmem<RT, (4 * KS + 2 > 16 * RT)>& sm, npos<RT>& p, int n, double* __restrict__ comp,
-                                             nstrip<RT>& r_s, nstrip<RT>& t_s, int* status) {
+                                             nstrip<RT>& r_s, nstrip<RT>& t_s, int* status, const nview* vw = nullptr,
+                                             int isub = 0) {
   using G = ngeo<RT>;
   constexpr unsigned dP = 0, dQ = G::AF * 8;
   double* vjp = sm.vec[0];
@@ -447,6 +456,101 @@ __device__ __forceinline__ void nia_body_src(nsmem<RT, (4 * KS + 2 > 16 * RT)>& 
   }
   __syncthreads();                                               // (d)
   if constexpr (!RID) nmv_rows<RT, KS, KZ>(dP, vu, 1.0, vg, p);      // g = G1 u
+  if constexpr (VW) {
+    constexpr int VQ = VSM_RUN_VIEW_MAX / 4;                     // (NT = 4 NP threads: thread tid takes element tid % NP of rows 4 i + tid / NP)
+    static_assert(VSM_RUN_VIEW_MAX == 16, "the viewing rows fill one row tile");
+    const int nv = vw->nv[isub];
+    int tl = tid;   // (opaque: what the view rows derive from the thread index is computed here, not kept from the kernel's entry)
+    asm volatile("" : "+v"(tl));
+    double tv[VQ];
+#pragma unroll
+    for (int i = 0; i < VQ; ++i) {                               // (requested under the product)
+      const int e = tl + i * G::NT;
+      tv[i] = e < nv * G::NP ? T_mm[e] : 0.0;
+    }
+    if constexpr (PARK) nld_native(r_s, R_pm, p);
+    nmm<RT, KS, true, KZ>(W, dP, Bs, p);                         // [W | g] = G1 [t-- | u]
+    __syncthreads();                                             // (e): [G1] no longer read
+    // the rows of T-- -> P as an A-form of ONE row tile (tile row v = viewing row v, rows >= nv zero; naf_idx<1>)
+    auto vaf = [](int v, int k) { return (k >> 2) * 64 + (((k & 3) << 4) | (v ^ ((k & 3) | (((k >> 2) & 3) << 2)))); };
+    {
+      asm volatile("" : "+v"(tl));
+      const int k = tl % G::NP, v0 = tl / G::NP;
+      if (k < 4 * KS) {
+#pragma unroll
+        for (int i = 0; i < VQ; ++i) sm.P[vaf(v0 + 4 * i, k)] = tv[i];
+      }
+    }
+    __syncthreads();                                             // (f)
+    if constexpr (!RID) {   // T--[V, :] g by wave 0 (nmv_rows on the one tile: the arithmetic of the full body's T-- g) , P g
+      if (p.wave == 0) {
+        double acc = 0.0;
+#pragma unroll
+        for (int ks = 0; ks < KZ; ++ks) {
+          const double a = *(reinterpret_cast<const nlds_d*>((unsigned long long)(p.fb[ks & 3] + dP)) + 64 * ks);
+          acc = fma(a, vg[4 * ks + p.kq], acc);
+        }
+        const bool in = p.l15 < nv;
+        const int row = in ? vw->row(isub, p.l15) : 0;
+        if constexpr (KZ < KS) {
+          if (in && row >= 4 * KZ && row < 4 * KS && p.kq == (row & 3)) acc = fma(sm.P[vaf(p.l15, row)], vg[row], acc);
+        }
+        acc += __shfl_xor(acc, 16);
+        acc += __shfl_xor(acc, 32);
+        if (in && p.kq == 0) J0_m[row] = vJm[row] + acc * 1.0;
+      }
+      nmv_rows<RT, KS, KZ>(dQ, vg, 1.0, sm.mv[1], p);
+    }
+    // y = T--[V, :] [W | g]: the k-steps of the full body's product on the one tile -- element by element the same chain of
+    // operations, so the viewing rows carry the bits of a plain sources-only run
+    d4_t y = acc_zero<double>();
+    {
+      p.opaque();
+      double a[2];
+      a[0] = *(reinterpret_cast<const nlds_d*>((unsigned long long)(p.fb[0] + dP)));
+#pragma unroll
+      for (int ks = 0; ks < KZ; ++ks) {
+        if (ks + 1 < KZ) a[(ks + 1) & 1] = *(reinterpret_cast<const nlds_d*>((unsigned long long)(p.fb[(ks + 1) & 3] + dP)) + 64 * (ks + 1));
+        y = mfma<double>::mma(a[ks & 1], W.v[ks >> 2][ks & 3], y);
+      }
+#pragma unroll
+      for (int ks = KZ; ks < KS; ++ks) {   // the zero-weight tail (nzw_fix): row rho of T-- adds T--[rho, rho] W[rho, :]
+        for (int v = 0; v < nv; ++v) {
+          const int rho = vw->row(isub, v);
+          if ((rho >> 2) != ks) continue;
+          const double d = sm.P[vaf(v, rho)];
+          const double x = __shfl(W.v[ks >> 2][ks & 3], ((rho & 3) << 4) | p.l15);
+          const bool mine = p.kq == (v & 3);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) y[r] = (mine && (v >> 2) == r) ? fma(d, x, y[r]) : y[r];
+        }
+      }
+    }
+    nmm<RT, KS, false, KZ>(r_s, dQ, W, p);                       // [R+-' | J0+'] = r_s + P [W | g]
+    nst_native(R_pm, r_s, p);
+    if (laneA) {
+#pragma unroll
+      for (int ta = 0; ta < RT; ++ta)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) J0_p[p.row(ta, r)] = r_s.v[ta][r];
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {   // tile row kq + 4 r = viewing row v of column col
+      const int v = p.kq + 4 * r;
+      if (v < nv) {
+        T_mm[v * G::NP + p.col] = p.col < n ? y[r] : 0.0;
+        if (laneA) {
+          const int row = vw->row(isub, v);
+          J0_m[row] = vJm[row] + y[r];
+        }
+      }
+    }
+    if constexpr (!RID) {   // J0+ = j0+ + t++ J0+ + P g
+      __syncthreads();
+      if (tid < G::NP) J0_p[tid] = vtJ[tid] + sm.mv[1][tid];
+    }
+    return;
+  }
   {
     nstrip<RT> Tm;
     nld_native(Tm, T_mm, p);                                     // (requested under the product)
@@ -963,10 +1067,12 @@ static_assert(sizeof(nsmem<6, true>) <= 163840 && sizeof(nsmem<6>) <= 163840, "s
 
 // SRC: a sources-only run (VSM_RUN_SOURCES_ONLY): R-+ and T++ of the composite are neither read nor written (nia_body_src)
 // TZ: the last TZ k-steps cover zero-weight streams only (VSM_RUN_ZW_TAIL): every product skips them (KZ = KS - TZ)
-template <int RT, int KS, bool SRC, int TZ>
+// VW: a view-row run (VSM_RUN_VIEW_ROWS, with SRC): T-- as the block's vw.nv[isub] row vectors (nia_body_src)
+template <int RT, int KS, bool SRC, int TZ, bool VW = false>
 __global__ __launch_bounds__(ngeo<RT>::NT, ngeo<RT>::WPS) void k_layer_native(int n, int gsz, unsigned uvmask, int ndoubl,
                                                                                 int toa, const double* __restrict__ pre,
-                                                                                nlayer_comps a, int* status) {
+                                                                                nlayer_comps a, int* status, nview vw) {
+  static_assert(!VW || SRC, "view rows: sources-only runs");
   using G = ngeo<RT>;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   using SM = nsmem<RT, (4 * KS + 2 > 16 * RT)>;
@@ -988,14 +1094,27 @@ __global__ __launch_bounds__(ngeo<RT>::NT, ngeo<RT>::WPS) void k_layer_native(in
     ndsym(d, r_s, dp);
     nst_native(comp + NC_RPM * G::AF, d, p);
     ndsym(d, t_s, dp);
-    nst_native(comp + NC_TMM * G::AF, d, p);
+    if constexpr (VW) {   // the viewing rows of t-- as row vectors (all NP columns: the padding is zero)
+      const int nv = vw.nv[isub];
+      for (int v = 0; v < nv; ++v) {
+        const int row = vw.row(isub, v);
+#pragma unroll
+        for (int ta = 0; ta < RT; ++ta)
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            if (p.row(ta, r) == row) comp[NC_TMM * G::AF + v * G::NP + p.col] = d.v[ta][r];
+      }
+    } else {
+      nst_native(comp + NC_TMM * G::AF, d, p);
+    }
     if (threadIdx.x < G::NP) {
       comp[4 * G::AF + threadIdx.x] = sm.vec[0][threadIdx.x];
       comp[4 * G::AF + G::NP + threadIdx.x] = sm.vec[1][threadIdx.x];
     }
     return;
   }
-  if constexpr (SRC) nia_body_src<RT, KS, KZ>(sm, p, n, comp, r_s, t_s, status);
+  if constexpr (VW) nia_body_src<RT, KS, KZ, true>(sm, p, n, comp, r_s, t_s, status, &vw, isub);
+  else if constexpr (SRC) nia_body_src<RT, KS, KZ>(sm, p, n, comp, r_s, t_s, status);
   else nia_body_native<RT, KS, KZ>(sm, p, n, comp, r_s, t_s, status);
 }
 
@@ -1009,14 +1128,14 @@ __global__ __launch_bounds__(ngeo<RT>::NT, ngeo<RT>::WPS) void k_layer_native(in
 #define VSM_NATIVE_TZ_MAX 1
 #define VSM_NATIVE_DECL(KS) \
   int VSM_NCAT(launch_layer_native_, KS)(int, int, int, unsigned, int, int, int, int, int, const double*, const nlayer_comps&, \
-                                         int*, hipStream_t);                                                                     \
+                                         int*, const nview*, hipStream_t);                                                                   \
   int VSM_NCAT(launch_ia_native_, KS)(int, int, const composite<double>&, const added<double>&, int*, hipStream_t);
 
 #ifdef VSM_NATIVE_KS
 VSM_NATIVE_DECL(VSM_NATIVE_KS)
 int VSM_NCAT(launch_layer_native_, VSM_NATIVE_KS)(int S, int nsub, int n, unsigned uvmask, int gsz, int ndoubl, int toa, int src,
                                                   int tz, const double* pre, const nlayer_comps& comps, int* status,
-                                                  hipStream_t st) {
+                                                  const nview* vw, hipStream_t st) {   // vw: a view-row run (with src)
   constexpr int KS = VSM_NATIVE_KS;
   // KS = 4, 8, 12, 16 (n = 13..16, 29..32, 45..48, 61..64): KS / 4 row tiles without spare columns (mat-vec source path) instead of one row
   // tile more for the two rider columns
@@ -1025,11 +1144,18 @@ int VSM_NCAT(launch_layer_native_, VSM_NATIVE_KS)(int S, int nsub, int n, unsign
   using SM = nsmem<RT, (4 * KS + 2 > 16 * RT)>;
   constexpr int TZ1 = KS - 1 < 1 ? 0 : 1, TZ2 = KS - 1 < VSM_NATIVE_TZ_MAX ? TZ1 : VSM_NATIVE_TZ_MAX;
   tz = tz < TZ2 ? (tz < TZ1 ? 0 : TZ1) : TZ2;
-  auto kern = src ? (tz == TZ2 ? k_layer_native<RT, KS, true, TZ2> : tz == TZ1 ? k_layer_native<RT, KS, true, TZ1> : k_layer_native<RT, KS, true, 0>)
+  static_assert(VSM_RUN_VIEW_MAX * 16 * RT <= 16 * RT * 16 * RT, "the viewing rows fit the A-form they pass through");
+  if (vw && !src) {
+    set_error("launch_layer_native: view rows without a sources-only run");
+    return VSM_ERR_INVALID_ARG;
+  }
+  auto kern = vw  ? (tz == TZ2 ? k_layer_native<RT, KS, true, TZ2, true> : tz == TZ1 ? k_layer_native<RT, KS, true, TZ1, true> : k_layer_native<RT, KS, true, 0, true>)
+            : src ? (tz == TZ2 ? k_layer_native<RT, KS, true, TZ2> : tz == TZ1 ? k_layer_native<RT, KS, true, TZ1> : k_layer_native<RT, KS, true, 0>)
                   : (tz == TZ2 ? k_layer_native<RT, KS, false, TZ2> : tz == TZ1 ? k_layer_native<RT, KS, false, TZ1> : k_layer_native<RT, KS, false, 0>);
   const int prepared = ensure_dyn_lds(reinterpret_cast<const void*>(kern), sizeof(SM), "hipFuncSetAttribute(k_layer_native)");
   if (prepared) return prepared;
-  hipLaunchKernelGGL(kern, dim3(S, nsub), dim3(ngeo<RT>::NT), sizeof(SM), st, n, gsz, uvmask, ndoubl, toa, pre, comps, status);
+  hipLaunchKernelGGL(kern, dim3(S, nsub), dim3(ngeo<RT>::NT), sizeof(SM), st, n, gsz, uvmask, ndoubl, toa, pre, comps, status,
+                     vw ? *vw : nview{});
   VSM_LAUNCH_CHECK("k_layer_native");
   return VSM_OK;
 }
@@ -1248,8 +1374,10 @@ __device__ __forceinline__ void nat_elem_rt(const float*, int rt, int e, int& i,
   i = 16 * ta + (lane >> 4) + 4 * r, j = 16 * w + (lane & 15);
 }
 // src: a sources-only run -- its R-+ and T++ are undefined and leave as quiet NaNs (a consumer fails loudly, never on stale data)
+// view: a view-row run (vw: the viewing rows per GROUP of the moment) -- T-- and J0- are defined in the viewing rows (row vectors at
+// the head of the T-- record) and leave as quiet NaNs elsewhere
 template <typename T>
-__global__ __launch_bounds__(256) void k_native_export(int N, int ns, int src, ngroup_map<T> gm, composite<T> c) {
+__global__ __launch_bounds__(256) void k_native_export(int N, int ns, int src, int view, ngroup_map<T> gm, nview vw, composite<T> c) {
   const int s = blockIdx.x, tid = threadIdx.x;
   const long long NN = (long long)N * N;
   T* out[4] = {c.R_mp + s * NN, c.R_pm + s * NN, c.T_pp + s * NN, c.T_mm + s * NN};
@@ -1258,15 +1386,20 @@ __global__ __launch_bounds__(256) void k_native_export(int N, int ns, int src, n
     const int ai = i % ns, aj = j % ns;
     const int gi = gm.grp_of[ai];
     T v[4] = {0, 0, 0, 0};
+    const int is = (i / ns) * gm.gsz[gi] + gm.pos_in[ai];
+    const int at = view ? vw.find(gi, is) : 0;
     if (gi == gm.grp_of[aj]) {
       const int rt = gm.rt[gi], np = 16 * rt, af = np * np;
       const T* cn = gm.base[gi] + (long long)s * (4 * af + 2 * np);
-      const int is = (i / ns) * gm.gsz[gi] + gm.pos_in[ai], js = (j / ns) * gm.gsz[gi] + gm.pos_in[aj];
+      const int js = (j / ns) * gm.gsz[gi] + gm.pos_in[aj];
       const int ix = nat_idx_rt(cn, rt, is, js);
 #pragma unroll
-      for (int k = 0; k < 4; ++k) v[k] = cn[k * af + ix];
+      for (int k = 0; k < 4; ++k)
+        if (!(view && k == NC_TMM)) v[k] = cn[k * af + ix];
+      if (view && at >= 0) v[NC_TMM] = cn[NC_TMM * af + at * np + js];
     }
     if (src) v[NC_RMP] = v[NC_TPP] = (T)__builtin_nan("");
+    if (view && at < 0) v[NC_TMM] = (T)__builtin_nan("");
 #pragma unroll
     for (int k = 0; k < 4; ++k) out[k][e] = v[k];
   }
@@ -1276,13 +1409,14 @@ __global__ __launch_bounds__(256) void k_native_export(int N, int ns, int src, n
     const T* cn = gm.base[gi] + (long long)s * (4 * af + 2 * np);
     const int is = (tid / ns) * gm.gsz[gi] + gm.pos_in[ai];
     c.J0_p[(long long)s * N + tid] = cn[4 * af + is];
-    c.J0_m[(long long)s * N + tid] = cn[4 * af + np + is];
+    c.J0_m[(long long)s * N + tid] = (view && vw.find(gi, is) < 0) ? (T)__builtin_nan("") : cn[4 * af + np + is];
   }
 }
 // reference layout -> native (padding zero); elements that couple different groups are dropped (they are exact zeros for a
-// composite that was built under the same coupling)
+// composite that was built under the same coupling).  view: a view-row run -- T-- is read in the viewing rows only, into the row
+// vectors at the head of its record
 template <typename T>
-__global__ __launch_bounds__(256) void k_native_import(int N, int ns, ngroup_map<T> gm, composite<T> c) {
+__global__ __launch_bounds__(256) void k_native_import(int N, int ns, int view, ngroup_map<T> gm, nview vw, composite<T> c) {
   const int s = blockIdx.x, tid = threadIdx.x;
   const long long NN = (long long)N * N;
   const T* in[4] = {c.R_mp + s * NN, c.R_pm + s * NN, c.T_pp + s * NN, c.T_mm + s * NN};
@@ -1302,7 +1436,15 @@ __global__ __launch_bounds__(256) void k_native_import(int N, int ns, ngroup_map
       }
       const int ix = nat_idx_rt(cn, rt, is, js);
 #pragma unroll
-      for (int k = 0; k < 4; ++k) cn[k * af + ix] = v[k];
+      for (int k = 0; k < 4; ++k)
+        if (!(view && k == NC_TMM)) cn[k * af + ix] = v[k];
+    }
+    if (view) {
+      for (int e = tid; e < vw.nv[g] * np; e += 256) {
+        const int is = vw.row(g, e / np), js = e % np;
+        const int i = (is / gsz) * ns + comp_of[is % gsz], j = (js / gsz) * ns + comp_of[js % gsz];
+        cn[NC_TMM * af + e] = js < n ? in[NC_TMM][i + (long long)N * j] : (T)0;
+      }
     }
     if (tid < np) {
       T vp = 0, vm = 0;
@@ -1372,10 +1514,11 @@ struct ndiag_args {
   int g0[NSUB_MAX];    // the group's Stokes components, 4 bits each
 };
 // mode 0: the scaling above; 1: TOA; 2: the composite is still (R = 0, T = diag, J = 0) -- every layer above was such a step --:
-// only the two diagonals change.  src: a sources-only run -- R-+ and T++ are left alone.
+// only the two diagonals change.  src: a sources-only run -- R-+ and T++ are left alone.  view: a view-row run -- T-- is the block's
+// vw.nv[isub] row vectors at the head of its record: T--[v, :] <- T--[v, :] t (TOA: t[row v] e_(row v)).
 template <typename T>
-__global__ __launch_bounds__(256) void k_native_diag_layer(quad<T> q, int rt, int n, T scale, int mode, int src,
-                                                           const T* __restrict__ dtau, ndiag_args<T> a) {
+__global__ __launch_bounds__(256) void k_native_diag_layer(quad<T> q, int rt, int n, T scale, int mode, int src, int view,
+                                                           const T* __restrict__ dtau, ndiag_args<T> a, nview vw) {
   __shared__ T tt[sizeof(T) == 4 ? NATIVE32_MAX_ROWS : NATIVE_MAX_ROWS];
   const int s = blockIdx.x, isub = blockIdx.y, tid = threadIdx.x;
   const int np = 16 * rt, af = np * np, gsz = a.gsz[isub];
@@ -1390,7 +1533,9 @@ __global__ __launch_bounds__(256) void k_native_diag_layer(quad<T> q, int rt, in
     if (mode == 2 && tid < n) {
       const int ix = nat_idx_rt(comp, rt, tid, tid);
       if (!src) comp[NC_TPP * af + ix] *= t;
-      comp[NC_TMM * af + ix] *= t;
+      if (!view) comp[NC_TMM * af + ix] *= t;
+      const int at = view ? vw.find(isub, tid) : -1;
+      if (at >= 0) comp[NC_TMM * af + at * np + tid] *= t;
     }
   }
   if (mode == 2) return;
@@ -1407,11 +1552,18 @@ __global__ __launch_bounds__(256) void k_native_diag_layer(quad<T> q, int rt, in
         comp[NC_TPP * af + e] = d;
       }
       comp[NC_RPM * af + e] = 0;
-      comp[NC_TMM * af + e] = d;
+      if (!view) comp[NC_TMM * af + e] = d;
     } else {
       comp[NC_RPM * af + e] *= ti * tj;
       if (!src) comp[NC_TPP * af + e] *= ti;
-      comp[NC_TMM * af + e] *= tj;
+      if (!view) comp[NC_TMM * af + e] *= tj;
+    }
+  }
+  if (view) {
+    for (int e = tid; e < vw.nv[isub] * np; e += 256) {
+      const int j = e % np;
+      if (toa) comp[NC_TMM * af + e] = (j == vw.row(isub, e / np)) ? tt[j] : 0;
+      else comp[NC_TMM * af + e] *= tt[j];
     }
   }
   if (tid < np) {
@@ -1498,6 +1650,7 @@ static int plan_subs(bool f32, int N, int ns, int nm, const int* m, const int* c
       sb.ks = (sb.n + 3) / 4;
       sb.kz = sb.ks;
       sb.rt = rt_of(sb.n);
+      sb.nv = 0;
       sb.comp_off = total;
       total += comp_stride_rt(sb.rt) * S;
       subs.push_back(sb);
@@ -1507,11 +1660,11 @@ static int plan_subs(bool f32, int N, int ns, int nm, const int* m, const int* c
 }
 
 static int launch_layer_native(int ks, int tz, int S, int nsub, int n, unsigned uvmask, int gsz, int ndoubl, int toa, int src,
-                               const double* pre, double* const* comps, int* status, hipStream_t st) {
+                               const double* pre, double* const* comps, int* status, const nview* vw, hipStream_t st) {
   nlayer_comps lc;
   for (int k = 0; k < NSUB_MAX; ++k) lc.c[k] = comps[k];
 #define VSM_NL(KS) \
-  case KS: return VSM_NCAT(launch_layer_native_, KS)(S, nsub, n, uvmask, gsz, ndoubl, toa, src, tz, pre, lc, status, st);
+  case KS: return VSM_NCAT(launch_layer_native_, KS)(S, nsub, n, uvmask, gsz, ndoubl, toa, src, tz, pre, lc, status, vw, st);
   switch (ks) {
     VSM_NL(1) VSM_NL(2) VSM_NL(3) VSM_NL(4) VSM_NL(5) VSM_NL(6) VSM_NL(7) VSM_NL(8) VSM_NL(9) VSM_NL(10) VSM_NL(11) VSM_NL(12)
     VSM_NL(13) VSM_NL(14) VSM_NL(15) VSM_NL(16) VSM_NL(17) VSM_NL(18) VSM_NL(19) VSM_NL(20) VSM_NL(21) VSM_NL(22) VSM_NL(23) VSM_NL(24)
@@ -1571,11 +1724,11 @@ static void native_launch_pre(int rt, bool mix, const quad<float>& q, int S, int
   native32_launch_pre(rt, mix, q, S, nsub, n, ndoubl, dtau, varpi, tau_sum, F0, a, pre, st);
 }
 static int native_launch_layer(const nat_sub& h, int S, int nsub, int ndoubl, int toa, int src, const double* pre, double* const* comps,
-                               int* status, hipStream_t st) {
-  return launch_layer_native(h.ks, h.ks - h.kz, S, nsub, h.n, h.uvmask, h.gsz, ndoubl, toa, src, pre, comps, status, st);
+                               int* status, const nview* vw, hipStream_t st) {
+  return launch_layer_native(h.ks, h.ks - h.kz, S, nsub, h.n, h.uvmask, h.gsz, ndoubl, toa, src, pre, comps, status, vw, st);
 }
 static int native_launch_layer(const nat_sub& h, int S, int nsub, int ndoubl, int toa, int, const float* pre, float* const* comps,
-                               int* status, hipStream_t st) {
+                               int* status, const nview*, hipStream_t st) {
   return native32_launch_layer(h.ks, S, nsub, h.n, h.uvmask, h.gsz, ndoubl, toa, pre, comps, status, st);
 }
 
@@ -1604,6 +1757,39 @@ static ngroup_map<T> group_map(const vsm_run* run, int im) {
   return gm;
 }
 
+// the viewing rows of the sub-problems `idx` (indices into run->subs), slot by slot (the slots past the list repeat the first one)
+static nview view_of(const vsm_run* run, const std::vector<int>& idx) {
+  nview vw = {};
+  for (int k = 0; k < NSUB_MAX && !idx.empty(); ++k) {
+    const nat_sub& sb = run->subs[idx[k < (int)idx.size() ? k : 0]];
+    vw.nv[k] = sb.nv;
+    for (int v = 0; v < sb.nv; ++v) vw.pk[k][v >> 2] |= (unsigned)sb.vrow[v] << (8 * (v & 3));
+  }
+  return vw;
+}
+// ... of the groups of moment im, in group_map's order
+static nview view_of_moment(const vsm_run* run, int im) {
+  std::vector<int> idx;
+  for (size_t i = 0; i < run->subs.size(); ++i)
+    if (run->subs[i].im == im) idx.push_back((int)i);
+  nview vw = view_of(run, idx);
+  for (int k = (int)idx.size(); k < NSUB_MAX; ++k) vw.nv[k] = 0;
+  return vw;
+}
+// VSM_RUN_VIEW_ROWS: global row -> (sub-problem, local row) through the Stokes groups of every moment: row = node ns + a lies in the
+// block that holds component a, at local row node gsz + (position of a in the block)
+static void map_view_rows(vsm_run* run) {
+  const int ns = run->ns;
+  for (nat_sub& sb : run->subs) {
+    sb.nv = 0;
+    for (int gr : run->view_rows) {
+      const int a = gr % ns, node = gr / ns;
+      for (int k = 0; k < sb.gsz; ++k)
+        if (sb.g[k] == a) sb.vrow[sb.nv++] = node * sb.gsz + k;
+    }
+  }
+}
+
 template <typename T>
 static quad<T> run_quad(const vsm_run* run) {
   return quad<T>{static_cast<const T*>(run->mu), static_cast<const T*>(run->wt), run->N, run->ns, run->i_mu0, (T)run->mu0};
@@ -1630,11 +1816,30 @@ static int zw_tail(vsm_run* run) {
   return VSM_OK;
 }
 
+static int check_view_rows(unsigned flags, int N, int nrows, const int* rows) {
+  VSM_REQUIRE(flags & VSM_RUN_SOURCES_ONLY, "vsm_run: VSM_RUN_VIEW_ROWS is valid only with VSM_RUN_SOURCES_ONLY");
+  VSM_REQUIRE(rows && nrows >= 1 && nrows <= VSM_RUN_VIEW_MAX,
+              "vsm_run: VSM_RUN_VIEW_ROWS takes 1 .. %d viewing rows (vsm_run_create_view / vsm_run_view_rows), got %d",
+              (int)VSM_RUN_VIEW_MAX, rows ? nrows : 0);
+  for (int v = 0; v < nrows; ++v) {
+    VSM_REQUIRE(rows[v] >= 0 && rows[v] < N, "vsm_run: viewing row %d outside 0 .. N - 1 = %d", rows[v], N - 1);
+    for (int u = 0; u < v; ++u) VSM_REQUIRE(rows[u] != rows[v], "vsm_run: viewing row %d listed twice", rows[v]);
+  }
+  return VSM_OK;
+}
+
 template <typename T, typename Q>
 static int run_create(const Q* q, int S, int nm, const int* m, const int* coupling, void* workspace, size_t workspace_bytes,
-                      unsigned flags, vsm_run** run_out) {
+                      unsigned flags, vsm_run** run_out, int nrows = 0, const int* rows = nullptr) {
   VSM_REQUIRE(q && q->mu && q->wt && run_out && m, "vsm_run_create: null argument");
-  VSM_REQUIRE((flags & ~(unsigned)(VSM_RUN_SOURCES_ONLY | VSM_RUN_ZW_TAIL)) == 0, "vsm_run_create_ex: unknown flags 0x%x", flags);
+  VSM_REQUIRE((flags & ~(unsigned)(VSM_RUN_SOURCES_ONLY | VSM_RUN_ZW_TAIL | VSM_RUN_VIEW_ROWS)) == 0,
+              "vsm_run_create_ex: unknown flags 0x%x", flags);
+  if (flags & VSM_RUN_VIEW_ROWS) {
+    const int rcv = check_view_rows(flags, q->N, nrows, rows);
+    if (rcv) return rcv;
+  } else {
+    VSM_REQUIRE(nrows == 0, "vsm_run_create_view: %d viewing rows without VSM_RUN_VIEW_ROWS", nrows);
+  }
   VSM_REQUIRE(S >= 0 && nm >= 1 && nm <= NSUB_MAX, "vsm_run_create: bad S = %d / nm = %d (at most %d moments per run)", S, nm,
               NSUB_MAX);
   vsm_run* run = new vsm_run;
@@ -1667,6 +1872,10 @@ static int run_create(const Q* q, int S, int nm, const int* m, const int* coupli
       delete run;
       return rc2;
     }
+  }
+  if (run->flags & VSM_RUN_VIEW_ROWS) {
+    run->view_rows.assign(rows, rows + nrows);
+    map_view_rows(run);
   }
   run->ws = workspace;
   run->ws_elems = total;
@@ -1731,6 +1940,7 @@ static int run_layer(vsm_run* run, int ndoubl, const T* dtau, const T* varpi, co
   }
   T* const ws = static_cast<T*>(run->ws);
   const int src = (run->flags & VSM_RUN_SOURCES_ONLY) ? 1 : 0;
+  const int view = (run->flags & VSM_RUN_VIEW_ROWS) ? 1 : 0;
   // the pre-pass images of the layer: one record per (sub-problem, point)
   size_t pre_total = 0;
   for (const nat_sub& sb : run->subs)
@@ -1767,7 +1977,7 @@ static int run_layer(vsm_run* run, int ndoubl, const T* dtau, const T* varpi, co
         da.g0[k] = sb.g[0] | (sb.g[1] << 4) | (sb.g[2] << 8) | (sb.g[3] << 12);
       }
       hipLaunchKernelGGL((k_native_diag_layer<T>), dim3(run->S, nt), dim3(256), 0, st, q, h.rt, h.n, (T)ldexp(1.0, ndoubl), mode,
-                         src, dtau, da);
+                         src, view, dtau, da, view ? view_of(run, triv[mode]) : nview{});
       VSM_LAUNCH_CHECK("k_native_diag_layer");
     }
     const int nsub = (int)act.size();
@@ -1787,7 +1997,8 @@ static int run_layer(vsm_run* run, int ndoubl, const T* dtau, const T* varpi, co
     off += pre_stride_rt(h.rt) * (size_t)run->S * nsub;
     native_launch_pre(h.rt, ncomp > 0, q, run->S, nsub, h.n, ndoubl, dtau, varpi, tau_sum, F0, pa, pre_cl, st);
     VSM_LAUNCH_CHECK("k_elemental_native");
-    const int rc = native_launch_layer(h, run->S, nsub, ndoubl, toa, src, pre_cl, lc, status, st);
+    const nview vw = view ? view_of(run, act) : nview{};
+    const int rc = native_launch_layer(h, run->S, nsub, ndoubl, toa, src, pre_cl, lc, status, view ? &vw : nullptr, st);
     if (rc) return rc;
   }
   return VSM_OK;
@@ -1797,6 +2008,7 @@ template <typename T, typename CS, bool IMPORT>
 static int run_convert(vsm_run* run, const CS* comps, void* stream) {
   VSM_REQUIRE(run && comps, "vsm_run_export / import: null argument");
   VSM_REQUIRE(run->elem_size == (int)sizeof(T), "vsm_run_export / import: the run was created for %d-byte arrays", run->elem_size);
+  if (IMPORT) ++run->imports;
   if (run->S == 0) return VSM_OK;
   if (IMPORT) {
     run->pure_diag.assign(run->subs.size(), 0);
@@ -1809,11 +2021,13 @@ static int run_convert(vsm_run* run, const CS* comps, void* stream) {
     VSM_REQUIRE(c.R_mp && c.R_pm && c.T_pp && c.T_mm && c.J0_p && c.J0_m, "vsm_run_export / import: null composite array (moment %d)", im);
     const composite<T> cc{c.R_mp, c.R_pm, c.T_pp, c.T_mm, c.J0_p, c.J0_m};
     const ngroup_map<T> gm = group_map<T>(run, im);
+    const int view = (run->flags & VSM_RUN_VIEW_ROWS) ? 1 : 0;
+    const nview vw = view ? view_of_moment(run, im) : nview{};
     if (IMPORT)
-      hipLaunchKernelGGL((k_native_import<T>), dim3(run->S), dim3(256), 0, as_stream(stream), run->N, run->ns, gm, cc);
+      hipLaunchKernelGGL((k_native_import<T>), dim3(run->S), dim3(256), 0, as_stream(stream), run->N, run->ns, view, gm, vw, cc);
     else
       hipLaunchKernelGGL((k_native_export<T>), dim3(run->S), dim3(256), 0, as_stream(stream), run->N, run->ns,
-                         (run->flags & VSM_RUN_SOURCES_ONLY) ? 1 : 0, gm, cc);
+                         (run->flags & VSM_RUN_SOURCES_ONLY) ? 1 : 0, view, gm, vw, cc);
     VSM_LAUNCH_CHECK("k_native_export / import");
   }
   return VSM_OK;
@@ -1878,6 +2092,38 @@ int vsm_run_create_ex_f64(const vsm_quad_f64* q, int S, int nm, const int* m, co
 int vsm_run_create_ex_f32(const vsm_quad_f32* q, int S, int nm, const int* m, const int* coupling, void* workspace,
                           size_t workspace_bytes, unsigned flags, vsm_run** run_out) {
   return run_create<float>(q, S, nm, m, coupling, workspace, workspace_bytes, flags, run_out);
+}
+
+int vsm_run_create_view_f64(const vsm_quad_f64* q, int S, int nm, const int* m, const int* coupling, void* workspace,
+                            size_t workspace_bytes, unsigned flags, int nrows, const int* rows, vsm_run** run_out) {
+  return run_create<double>(q, S, nm, m, coupling, workspace, workspace_bytes, flags, run_out, nrows, rows);
+}
+int vsm_run_create_view_f32(const vsm_quad_f32* q, int S, int nm, const int* m, const int* coupling, void* workspace,
+                            size_t workspace_bytes, unsigned flags, int nrows, const int* rows, vsm_run** run_out) {
+  return run_create<float>(q, S, nm, m, coupling, workspace, workspace_bytes, flags, run_out, nrows, rows);
+}
+
+int vsm_run_view_rows(vsm_run* run, int nrows, const int* rows) {
+  VSM_REQUIRE(run, "vsm_run_view_rows: null argument");
+  VSM_REQUIRE(run->layers == 0 && run->imports == 0, "vsm_run_view_rows: the run has taken layer steps or an import already");
+  if (run->elem_size != 8) return VSM_OK;   // (_f32 runs: the full recurrences)
+  const int rc = check_view_rows(run->flags, run->N, nrows, rows);
+  if (rc) return rc;
+  run->flags |= VSM_RUN_VIEW_ROWS;
+  run->view_rows.assign(rows, rows + nrows);
+  map_view_rows(run);
+  return VSM_OK;
+}
+
+int vsm_run_view_block(const vsm_run* run, int block, int* im, int* n, int* nv, int* local_rows) {
+  VSM_REQUIRE(run && im && n && nv && local_rows, "vsm_run_view_block: null argument");
+  VSM_REQUIRE(block >= 0 && block < (int)run->subs.size(), "vsm_run_view_block: the run has %d blocks", (int)run->subs.size());
+  const nat_sub& sb = run->subs[block];
+  *im = sb.im;
+  *n = sb.n;
+  *nv = (run->flags & VSM_RUN_VIEW_ROWS) ? sb.nv : 0;
+  for (int v = 0; v < *nv; ++v) local_rows[v] = sb.vrow[v];
+  return VSM_OK;
 }
 
 int vsm_run_zw_tail(vsm_run* run) {

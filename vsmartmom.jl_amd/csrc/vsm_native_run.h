@@ -18,6 +18,22 @@ struct nat_sub {
   int n, rt, ks;
   int kz;          // k-steps over real streams (VSM_RUN_ZW_TAIL; else ks): ks - kz trailing k-steps cover zero-weight streams only
   size_t comp_off;   // elements (of the run's record type) from the workspace base
+  int nv;                        // VSM_RUN_VIEW_ROWS: viewing rows that fall into this block (0: it carries no T-- rows at all)
+  int vrow[VSM_RUN_VIEW_MAX];    // ... as local rows of the block, in the order of the run's list
+};
+
+// the viewing rows of the sub-problems of one launch / of the groups of one moment (local rows of a block: < 96)
+// (dwords, four rows each: the kernels read them with scalar loads)
+struct nview {
+  int nv[NSUB_MAX];
+  unsigned pk[NSUB_MAX][VSM_RUN_VIEW_MAX / 4];
+  __host__ __device__ int row(int k, int v) const { return (int)((pk[k][v >> 2] >> (8 * (v & 3))) & 255u); }
+  // index of local row `r` in the list of slot k, -1: not a viewing row
+  __host__ __device__ int find(int k, int r) const {
+    int at = -1;
+    for (int v = 0; v < nv[k]; ++v) at = row(k, v) == r ? v : at;
+    return at;
+  }
 };
 
 }  // namespace vsm
@@ -28,13 +44,16 @@ struct vsm_run {
   double mu0;
   int elem_size;           // 8: FP64 model (FP64 records and arithmetic), 4: Float32 model (FP32 records and arithmetic)
   int S, nm;
-  unsigned flags;          // vsm_run_create_ex: VSM_RUN_SOURCES_ONLY, VSM_RUN_ZW_TAIL (FP64 runs; the latter dropped by vsm_run_import)
+  unsigned flags;          // vsm_run_create_ex: VSM_RUN_SOURCES_ONLY, VSM_RUN_ZW_TAIL (FP64 runs; the latter dropped by vsm_run_import),
+                           // vsm_run_create_view: VSM_RUN_VIEW_ROWS (FP64 runs)
+  std::vector<int> view_rows;   // VSM_RUN_VIEW_ROWS: the global viewing rows
   std::vector<int> m;
   std::vector<vsm::nat_sub> subs;
   std::vector<std::vector<int>> classes;   // indices into subs with equal (n, gsz, uvmask)
   void* ws;
   size_t ws_elems;
   int layers = 0;                // vsm_run_layer calls so far
+  int imports = 0;               // vsm_run_import calls so far
   std::vector<char> pure_diag;   // per sub-problem: its composite is still (R = 0, T = diag, J = 0): only diagonal steps so far
 };
 
