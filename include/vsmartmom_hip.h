@@ -898,6 +898,55 @@ int vsm_level_radiance_lin_f32(int N, int n_stokes, int S, int P, int P_top, int
                                long long bot_lin_pstride, const float* bot_J0_m_lin, float* uw_lin, float* dw_lin,
                                float* dw_lin_full, float* uw_lin_full, void* stream);
 
+/* ---- single-scattering runs: rt_run_ss (src/CoreRT/rt_run.jl:574-755) -----------------------------------------------------
+ * One Fourier moment of the single-scattering column walk, all layers and the surface in ONE launch: per layer the exact
+ * finite-tau sources of elemental! with ndoubl = 0 and dtau = the layer's tau (get_elem_rt_SFI!, CoreKernel/elemental.jl:348-392;
+ * rt_kernel_ss!, CoreKernel/rt_kernel_ss.jl:156-238 hard-wires scatter = true and ndoubl_ss = 0, so no D sign goes on j0-), the
+ * TOA copy for the first layer and for every later one the two statements of get_interaction_ss! (CoreKernel/interaction_ss.jl:
+ * 14-19):   J0+[i,n] = J0+[i,n] exp(-tau_iz[n] / mu_i) + j0+[i,n],   J0-[i,n] += j0-[i,n] exp(-tau_sum_iz[n] / mu_i),
+ * then once more with the surface layer's sources (rt_run.jl:715-722: layer tau = 0, tau_sum = tau_sum_surface) and the viewing
+ * rows of postprocessing_vza! (tools/postprocessing_vza.jl:23-94, SFI branch).  No N x N array is formed or read: of Z only the
+ * n_stokes SZA columns.
+ * Layer tables: HOST arrays of L device pointers, tau_h / varpi_h / tau_sum_h [S] each, Zpp_h / Zmp_h with z_stride_h[iz] elements
+ * per spectral point (0 = one [N,N] block shared by every point, N*N = per point [N,N,S]); they reach the device through the
+ * library's scratch, L >= 1 is not capped.  F0 [n_stokes,S] with the F0 / Z indexing of vsm_elemental_* (the j0+- of a layer are
+ * those of vsm_elemental_*(ndoubl = 0, dtau = tau)).  surf_j0_m [N,1,S] = j0- of the surface AddedLayer; surf_j0_p (nullable =
+ * zero) its j0+ (the scalar Lambertian builder puts the direct beam there for m = 0, lambertian_surface.jl:75, and interaction_ss!
+ * adds it); tau_sum_surface [S].  row0_h / w_h [nV] / [nV * n_stokes] exactly as in vsm_postprocess_vza (any nV >= 1).
+ * Outputs: R_SFI / T_SFI [nV,n_stokes,S] are ACCUMULATED (R[v,k,s] += w[v,k] J0-[row0[v]+k, s]); J0_m / J0_p (nullable, [N,1,S])
+ * receive the composite sources at all streams (the driver's hem_R / hem_T read them for m = 0, rt_run.jl:737-748). */
+int vsm_ss_column_f64(const vsm_quad_f64* q, int S, int L, int m, const double* const* tau_h, const double* const* varpi_h,
+                      const double* const* tau_sum_h, const double* const* Zpp_h, const double* const* Zmp_h,
+                      const long long* z_stride_h, const double* F0, const double* surf_j0_m, const double* surf_j0_p,
+                      const double* tau_sum_surface, int nV, const int* row0_h, const double* w_h, double* R_SFI, double* T_SFI,
+                      double* J0_m, double* J0_p, void* stream);
+int vsm_ss_column_f32(const vsm_quad_f32* q, int S, int L, int m, const float* const* tau_h, const float* const* varpi_h,
+                      const float* const* tau_sum_h, const float* const* Zpp_h, const float* const* Zmp_h,
+                      const long long* z_stride_h, const float* F0, const float* surf_j0_m, const float* surf_j0_p,
+                      const float* tau_sum_surface, int nV, const int* row0_h, const float* w_h, float* R_SFI, float* T_SFI,
+                      float* J0_m, float* J0_p, void* stream);
+/* The rotational-Raman twin (rt_kernel_ss!(::RRS), rt_kernel_ss.jl:240-337): per layer the sources of get_elem_rt_SFI_RRS!
+ * (CoreKernel/elemental_inelastic.jl:479-603; near / far branches on rt_close_tol and on the viewing row being the SZA row as
+ * written there) with ndoubl = 0 and dtau = tau, composed by get_interaction_ss_RRS! (interaction_ss.jl:79-90) and summed over the
+ * lines by postprocessing_vza!(::RRS) (postprocessing_vza.jl:139-142); the surface adds nothing.  Donor n0 = n1 + shift[dn];
+ * pairs with n0 outside [0, S) contribute exactly zero.  The line sum is taken inside the kernel and only the viewing rows are
+ * evaluated: no [N,S,K] array exists.  tau_h / tau_sum_h / fscatt_h: HOST arrays of L device pointers ([S] each; fscatt = the
+ * layer's fScattRayleigh); shift [K] (int) and varpi_ie [K] on the device, Zpp_ie / Zmp_ie the flat [N,N] Raman phase matrices of
+ * the moment.  K = 0 is legal (nothing is launched).  ieR_SFI / ieT_SFI [nV,n_stokes,S] are ACCUMULATED.
+ * A workgroup owns VSM_SS_BLOCK consecutive recipient points and stages the per-layer donor factors of the points within `halo`
+ * of its block in LDS (0 <= halo, clamped to VSM_SS_MAX_HALO; the host passes the largest |shift| it wants staged); a line whose
+ * donor lies outside that window reads global memory instead -- the same values, so `halo` never changes a result. */
+#define VSM_SS_BLOCK 128
+#define VSM_SS_MAX_HALO 192
+int vsm_ss_column_rrs_f64(const vsm_quad_f64* q, int S, int L, int m, int K, const double* const* tau_h,
+                          const double* const* tau_sum_h, const double* const* fscatt_h, const int* shift,
+                          const double* varpi_ie, const double* Zpp_ie, const double* Zmp_ie, const double* F0, int halo,
+                          int nV, const int* row0_h, const double* w_h, double* ieR_SFI, double* ieT_SFI, void* stream);
+int vsm_ss_column_rrs_f32(const vsm_quad_f32* q, int S, int L, int m, int K, const float* const* tau_h,
+                          const float* const* tau_sum_h, const float* const* fscatt_h, const int* shift, const float* varpi_ie,
+                          const float* Zpp_ie, const float* Zmp_ie, const float* F0, int halo, int nV, const int* row0_h,
+                          const float* w_h, float* ieR_SFI, float* ieT_SFI, void* stream);
+
 /* ---- diagnostics used by the parity tests -------------------------------- */
 /* Runs the LDS-resident MFMA tile product used inside the fused kernels on plain
  * [N,N,S] inputs: C = A*B.  (Checks fragment layouts / swizzle independently.) */

@@ -9,12 +9,14 @@ be imported with a plain `import` statement; use the shim at the repo root:
 Sub-modules
     Architectures   CPU()/GPU() dispatch surface (src/Architectures.jl)
     CoreRT          batched_mul / batch_inv_ / elemental_ / doubling_ / interaction_ / rt_kernel_ / rt_run /
-                    rt_run_multisensor (core_rt_ms: radiances at any level of the column)
+                    rt_run_multisensor (core_rt_ms: radiances at any level of the column) / rt_run_ss (core_rt_ss: the
+                    single-scattering run)
     host_model      host-side producers of the hot path's inputs (streams, Z moments, layer mixing)
     CoreRTLin       linearized (Jacobian) pass: rt_run(model, lin_model, ...),
                     rt_run_multisensor(model, lin_model, ..., sensor_levels) (core_rt_ms_lin: Jacobians at any level)
     CoreRTRaman     rotational-Raman pass: rt_run(RS_type::RRS, model, iBand),
-                    rt_run_multisensor(RS_type, model, sensor_levels) (core_rt_ms_raman)
+                    rt_run_multisensor(RS_type, model, sensor_levels) (core_rt_ms_raman),
+                    rt_run_ss(RS_type, model, iBand) (core_rt_ss: the single-scatter inelastic correction)
     parallel        spectral-axis sharding over the GPUs of one node (torch.distributed / RCCL)
 """
 from . import _lib, host_model  # noqa: F401
@@ -26,6 +28,7 @@ from . import core_rt_lin as CoreRTLin  # noqa: F401
 from . import core_rt_raman as CoreRTRaman  # noqa: F401
 from . import core_rt_ms_raman  # noqa: F401
 from . import core_rt_ms_lin  # noqa: F401
+from . import core_rt_ss  # noqa: F401
 from . import raman_inputs  # noqa: F401
 from . import io_yaml  # noqa: F401
 from ._lib import VSMError, LIB_PATH  # noqa: F401
@@ -35,6 +38,8 @@ CoreRT.MultiSensorResult = core_rt_ms.MultiSensorResult
 CoreRTRaman.rt_run_multisensor = core_rt_ms_raman.rt_run_multisensor
 CoreRTRaman.MultiSensorRamanResult = core_rt_ms_raman.MultiSensorRamanResult
 CoreRTLin.rt_run_multisensor = core_rt_ms_lin.rt_run_multisensor
+CoreRT.rt_run_ss = core_rt_ss.rt_run_ss
+CoreRTRaman.rt_run_ss = core_rt_ss.rt_run_ss_rrs
 CoreRTLin.MultiSensorLinResult = core_rt_ms_lin.MultiSensorLinResult
 
 __version__ = "0.1.0"

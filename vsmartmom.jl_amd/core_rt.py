@@ -746,7 +746,7 @@ class Scene:
     host mirror (host_model.constructLayerOpticsComponents) instead -- kept as a cross-check."""
 
     def __init__(self, model: H.RTModel, spec_slice: Optional[slice] = None, host_optics: bool = False,
-                 full_added_layer: bool = False):
+                 full_added_layer: bool = False, layers_only: bool = False):
         arch, FT = model.architecture, model.float_type
         _require_gpu(arch)
         self.model, self.arch, self.FT = model, arch, FT
@@ -759,6 +759,9 @@ class Scene:
                                 % len(model.vza))
         self.host_optics = bool(host_optics)
         self.full_added_layer = bool(full_added_layer)   # the linearized run's kernels take the reference's full AddedLayer
+        # layers_only: the layer optics, Z moments, surface layer and outputs alone -- no composite, added layer or work buffer, i.e.
+        # nothing N x N per spectral point (the single-scattering runs, core_rt_ss.py; `run()` is not available on such a scene)
+        self.layers_only = bool(layers_only)
         S_full, self.Nz = model.tau_rayl.shape
         self.S_full = S_full
         self.sl = spec_slice if spec_slice is not None else slice(0, S_full)
@@ -809,13 +812,18 @@ class Scene:
         self.added_surface = make_added_layer(FT, arch, (N, N), S, shared=not self.spectral_surface)
         self.albedo_d = (conv(np.ascontiguousarray(H.surface_albedo_spectrum(model.surface, S_full, FT)[self.sl]))
                          if self.spectral_surface else None)
+        nV = len(model.vza)
+        self.R_SFI = torch.zeros((S, pol.n, nV), dtype=dt, device=dev)
+        self.T_SFI = torch.zeros((S, pol.n, nV), dtype=dt, device=dev)
+        if self.layers_only:
+            self.composite, self._composites, self.work, self.compute_hdrf = None, [], None, False
+            self.upload()
+            self.prepare()
+            return
         self.composite = make_composite_layer(FT, arch, (N, N), S)
         self._composites = [self.composite]     # one per Fourier moment of a batch (run() allocates the others on first use)
         # the interaction work buffer belongs to the scene (a captured graph must not point into a shared cache)
         self.work = _lib.poison(torch.empty(max(int(_lib.lib().vsm_interaction_work_elems(N, max(S, 1))), 1), dtype=dt, device=dev))
-        nV = len(model.vza)
-        self.R_SFI = torch.zeros((S, pol.n, nV), dtype=dt, device=dev)
-        self.T_SFI = torch.zeros((S, pol.n, nV), dtype=dt, device=dev)
         # HDRF / BHR diagnostics of the reference's 7-tuple (rt_run.jl:300-303,467-494,535)
         self.compute_hdrf = True
         self.hdr = torch.zeros((S, pol.n, nV), dtype=dt, device=dev)
@@ -938,6 +946,8 @@ class Scene:
         all11 = all(t == "11" for t in tags)
         fused_ok = self.N <= _lib.lib().vsm_fused_max_n(8 if np.dtype(FT) == np.float64 else 4)
         dsym = self.pol.n if (all11 and fused_ok and not self.full_added_layer) else 0
+        if self.layers_only:
+            return
         if self.added is None or self.added.d_symmetric != dsym:
             self.added = make_added_layer(FT, self.arch, (self.N, self.N), self.S, d_symmetric=dsym)
 
@@ -1005,6 +1015,8 @@ class Scene:
         per Fourier moment, what the reference hands its `streams_callback` (rt_run.jl:496-516): clones of the composite layer's
         R-+, T++ and of J0-+ (per-source slots added) after the surface interaction, with m and the Fourier weight."""
         model, pol, FT = self.model, self.pol, self.FT
+        if self.layers_only:
+            raise _lib.VSMError("Scene(layers_only=True) holds no composite layer: it feeds rt_run_ss only")
         self.R_SFI.zero_()
         self.T_SFI.zero_()
         self.hdr.zero_()

@@ -1,0 +1,431 @@
+// Single-scattering column walks: rt_run_ss (src/CoreRT/rt_run.jl:574-755), one launch per Fourier moment.
+//   vsm_ss_column_*      rt_kernel_ss!(::noRS) (CoreKernel/rt_kernel_ss.jl:156-238): get_elem_rt_SFI! (elemental.jl:348-392) with
+//                        ndoubl = 0 and dtau = tau, get_interaction_ss! (interaction_ss.jl:14-19), the surface's interaction_ss!
+//                        (rt_run.jl:715-722) and the viewing rows of postprocessing_vza! (postprocessing_vza.jl:23-94)
+//   vsm_ss_column_rrs_*  rt_kernel_ss!(::RRS) (:240-337): get_elem_rt_SFI_RRS! (elemental_inelastic.jl:479-603),
+//                        get_interaction_ss_RRS! (interaction_ss.jl:79-90), postprocessing_vza!(::RRS) (:139-142)
+// Lanes run along the spectral axis; a thread carries the running sources of SS_RB rows of its point in registers through all
+// layers.  Nothing here is N x N: of the phase matrices only the n_stokes SZA columns are read.
+#include <string.h>
+
+#include <vector>
+
+#include "vsm_common.h"
+#include "vsm_internal.h"
+
+namespace vsm {
+
+constexpr int SS_TB = VSM_SS_BLOCK;   // spectral points (= threads) per workgroup: two waves
+constexpr int SS_RB = 4;              // rows per thread; more rows go to further workgroups along grid.y
+constexpr int SS_SLOT = 5;            // library scratch slot of the device tables
+
+template <typename T>
+struct ss_layer {
+  const T *tau, *varpi, *tau_sum, *zpp, *zmp, *fscatt;
+  long long zs;
+};
+
+template <typename T>
+struct ss_tol {
+  static __device__ __forceinline__ T close() { return T(1e-8); }   // rt_close_tol (rt_helpers.jl:66-68)
+};
+
+// The rows a thread owns.  VIEW: item e = v + nV k of the viewing table (row row0[v] + k, weight w[e], output (s, k, v));
+// otherwise item e = stream row e of the full source vectors.
+template <typename T>
+struct ss_rows {
+  int i[SS_RB];
+  bool on[SS_RB];
+  T mi[SS_RB];
+};
+template <typename T>
+__device__ __forceinline__ ss_rows<T> ss_pick_rows(bool view, int N, int ns, int nV, const int* __restrict__ row0,
+                                                   const T* __restrict__ mu, int item0) {
+  ss_rows<T> r;
+  const int nitems = view ? nV * ns : N;
+#pragma unroll
+  for (int j = 0; j < SS_RB; ++j) {
+    const int e = item0 + j;
+    r.on[j] = e < nitems;
+    const int ec = r.on[j] ? e : 0;
+    r.i[j] = view ? row0[ec % nV] + ec / nV : ec;
+    r.mi[j] = mu[r.i[j]];
+  }
+  return r;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// elastic column
+// ---------------------------------------------------------------------------------------------------------------------
+template <typename T, bool VIEW>
+__global__ __launch_bounds__(SS_TB) void k_ss_column(int N, int ns, int S, int L, int m, int i_mu0,
+                                                     const ss_layer<T>* __restrict__ lay, const T* __restrict__ F0,
+                                                     const T* __restrict__ sj_m, const T* __restrict__ sj_p,
+                                                     const T* __restrict__ ts_surf, const T* __restrict__ mu, int nV,
+                                                     const int* __restrict__ row0, const T* __restrict__ w, T* R, T* Tt) {
+  const long long s = (long long)blockIdx.x * SS_TB + threadIdx.x;
+  if (s >= S) return;
+  const int i_start = ns * i_mu0;
+  const ss_rows<T> rw = ss_pick_rows<T>(VIEW, N, ns, nV, row0, mu, blockIdx.y * SS_RB);
+  const T ms = mu[i_start];
+  const T wct02 = (m == 0) ? T(0.5) : T(0.25);
+  T f0[4] = {0, 0, 0, 0};
+  for (int q = 0; q < ns; ++q) f0[q] = F0[q + (long long)ns * s];
+  T Jp[SS_RB], Jm[SS_RB];
+#pragma unroll
+  for (int j = 0; j < SS_RB; ++j) Jp[j] = Jm[j] = T(0);
+  for (int iz = 0; iz < L; ++iz) {
+    const ss_layer<T> ly = lay[iz];
+    const T d = ly.tau[s], wv = ly.varpi[s], ts = ly.tau_sum[s];
+    const T att = exp(-ts / ms);
+    const T* zpp = ly.zpp + s * ly.zs;
+    const T* zmp = ly.zmp + s * ly.zs;
+#pragma unroll
+    for (int j = 0; j < SS_RB; ++j) {
+      if (!rw.on[j]) continue;
+      const int i = rw.i[j];
+      const T mi = rw.mi[j];
+      T zp = 0, zm = 0;
+      for (int q = 0; q < ns; ++q) {
+        const long long zo = i + (long long)N * (i_start + q);
+        zp += zpp[zo] * f0[q];
+        zm += zmp[zo] * f0[q];
+      }
+      // get_elem_rt_SFI! with dtau = tau, ndoubl = 0 (the statements of k_elemental_sfi, vsm_generic.hip)
+      T jp;
+      if (i >= i_start && i < i_start + ns)
+        jp = wct02 * wv * zp * (d / mi) * exp(-d / mi);
+      else
+        jp = wct02 * wv * zp * (ms / (mi - ms)) * expdiff_neg<T>(d / mi, d / ms);
+      T jm = wct02 * wv * zm * (ms / (mi + ms)) * (-expm1(-d * ((T(1) / mi) + (T(1) / ms))));
+      jp *= att;
+      jm *= att;
+      if (iz == 0) {   // rt_kernel_ss.jl:213-216: the TOA layer is copied
+        Jp[j] = jp;
+        Jm[j] = jm;
+      } else {         // get_interaction_ss! (interaction_ss.jl:17-18)
+        Jp[j] = Jp[j] * exp(-d / mi) + jp;
+        Jm[j] = Jm[j] + jm * exp(-ts / mi);
+      }
+    }
+  }
+  // interaction_ss! with the surface layer (rt_run.jl:715-722): layer tau = 0, tau_sum = tau_sum_all[:, Nz + 1]
+  const T tss = ts_surf[s];
+#pragma unroll
+  for (int j = 0; j < SS_RB; ++j) {
+    if (!rw.on[j]) continue;
+    const long long src = s * N + rw.i[j];
+    Jp[j] = Jp[j] * exp(-T(0) / rw.mi[j]) + (sj_p ? sj_p[src] : T(0));
+    Jm[j] = Jm[j] + sj_m[src] * exp(-tss / rw.mi[j]);
+    if (VIEW) {
+      const int e = blockIdx.y * SS_RB + j;
+      const long long dst = (s * ns + e / nV) * nV + e % nV;
+      R[dst] += w[e] * Jm[j];
+      Tt[dst] += w[e] * Jp[j];
+    } else {
+      R[src] = Jm[j];
+      Tt[src] = Jp[j];
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Raman column
+// ---------------------------------------------------------------------------------------------------------------------
+// What a (recipient, line) pair reads of its donor n0 in one layer: d0 = tau[n0], x0 = d0 / mu0 as e0 = exp(-x0) and
+// a0 = expm1(-x0), g0 = fscatt[n0] exp(-tau_sum[n0] / mu0) -- formed once per (point, layer) in LDS for the window of the
+// workgroup, not once per line -- and, per row of the thread, Z_ie F0[:, n0] (layer independent: staged once per workgroup).
+template <typename T>
+__global__ __launch_bounds__(SS_TB) void k_ss_column_rrs(int N, int ns, int S, int L, int K, int m, int i_mu0, int halo,
+                                                         const ss_layer<T>* __restrict__ lay, const int* __restrict__ shift,
+                                                         const T* __restrict__ varpi_ie, const T* __restrict__ Zpp,
+                                                         const T* __restrict__ Zmp, const T* __restrict__ F0,
+                                                         const T* __restrict__ mu, int nV, const int* __restrict__ row0,
+                                                         const T* __restrict__ w, T* ieR, T* ieT) {
+  extern __shared__ __align__(16) unsigned char ss_smem[];
+  const int W = SS_TB + 2 * halo;
+  T* sd = reinterpret_cast<T*>(ss_smem);   // [W] each
+  T* se0 = sd + W;
+  T* sa0 = se0 + W;
+  T* sg = sa0 + W;
+  T* szp = sg + W;                         // [SS_RB][W]
+  T* szm = szp + SS_RB * W;
+  const long long b0 = (long long)blockIdx.x * SS_TB;
+  const long long w0 = b0 - halo;
+  const long long n1 = b0 + threadIdx.x;
+  const bool live = n1 < S;
+  const int i_start = ns * i_mu0;
+  const ss_rows<T> rw = ss_pick_rows<T>(true, N, ns, nV, row0, mu, blockIdx.y * SS_RB);
+  const T ms = mu[i_start];
+  const T wct02 = (m == 0) ? T(0.5) : T(0.25);
+  for (int p = threadIdx.x; p < W; p += SS_TB) {
+    const long long n0 = w0 + p;
+    const bool in = n0 >= 0 && n0 < S;
+#pragma unroll
+    for (int j = 0; j < SS_RB; ++j) {
+      T zp = 0, zm = 0;
+      if (in && rw.on[j])
+        for (int q = 0; q < ns; ++q) {
+          const long long zo = rw.i[j] + (long long)N * (i_start + q);
+          const T f = F0[q + (long long)ns * n0];
+          zp += Zpp[zo] * f;
+          zm += Zmp[zo] * f;
+        }
+      szp[j * W + p] = zp;
+      szm[j * W + p] = zm;
+    }
+  }
+  T rm[SS_RB], Sp[SS_RB], Sm[SS_RB];
+  bool sun[SS_RB];
+#pragma unroll
+  for (int j = 0; j < SS_RB; ++j) {
+    rm[j] = rw.mi[j] / ms;
+    sun[j] = rw.i[j] >= i_start && rw.i[j] < i_start + ns;
+    Sp[j] = Sm[j] = T(0);
+  }
+  for (int iz = 0; iz < L; ++iz) {
+    const ss_layer<T> ly = lay[iz];
+    __syncthreads();   // the previous layer's readers are done (first pass: nothing to wait for but the Z F0 stage)
+    for (int p = threadIdx.x; p < W; p += SS_TB) {
+      const long long n0 = w0 + p;
+      T d0 = T(1), e0 = T(0), a0 = T(0), g0 = T(0);
+      if (n0 >= 0 && n0 < S) {
+        d0 = ly.tau[n0];
+        const T x0 = d0 / ms;
+        e0 = exp(-x0);
+        a0 = expm1(-x0);
+        g0 = ly.fscatt[n0] * exp(-ly.tau_sum[n0] / ms);
+      }
+      sd[p] = d0;
+      se0[p] = e0;
+      sa0[p] = a0;
+      sg[p] = g0;
+    }
+    __syncthreads();
+    if (!live) continue;
+    const T d1 = ly.tau[n1], ts1 = ly.tau_sum[n1];
+    T x1[SS_RB], e1[SS_RB], a1[SS_RB], sp[SS_RB], sm[SS_RB];
+#pragma unroll
+    for (int j = 0; j < SS_RB; ++j) {
+      x1[j] = d1 / rw.mi[j];
+      e1[j] = exp(-x1[j]);
+      a1[j] = expm1(-x1[j]);
+      sp[j] = sm[j] = T(0);
+    }
+    for (int dn = 0; dn < K; ++dn) {
+      const long long n0 = n1 + shift[dn];
+      if (n0 < 0 || n0 >= S) continue;   // out of band: exactly zero (elemental_inelastic.jl:500)
+      const T wl = varpi_ie[dn];
+      const long long p = n0 - w0;
+      const bool staged = p >= 0 && p < W;
+      T d0, e0, a0, g0;
+      if (staged) {
+        d0 = sd[p];
+        e0 = se0[p];
+        a0 = sa0[p];
+        g0 = sg[p];
+      } else {   // a shift beyond the staged window: the same factors from global memory
+        d0 = ly.tau[n0];
+        const T x0g = d0 / ms;
+        e0 = exp(-x0g);
+        a0 = expm1(-x0g);
+        g0 = ly.fscatt[n0] * exp(-ly.tau_sum[n0] / ms);
+      }
+      const T x0 = d0 / ms;
+      const T ratio = d1 / d0;
+#pragma unroll
+      for (int j = 0; j < SS_RB; ++j) {
+        if (!rw.on[j]) continue;
+        T zp, zm;
+        if (staged) {
+          zp = szp[j * W + p];
+          zm = szm[j * W + p];
+        } else {
+          zp = zm = T(0);
+          for (int q = 0; q < ns; ++q) {
+            const long long zo = rw.i[j] + (long long)N * (i_start + q);
+            const T f = F0[q + (long long)ns * n0];
+            zp += Zpp[zo] * f;
+            zm += Zmp[zo] * f;
+          }
+        }
+        const T mi = rw.mi[j];
+        // expdiff_neg(d1 / mu_i, d0 / mu_0) (rt_helpers.jl:32-40) from e1 = exp(-x1), e0 = exp(-x0): one expm1 is left
+        const T xa = x1[j];
+        const T ed = (xa == x0) ? T(0) : ((xa < x0) ? e1[j] * (-expm1(-(x0 - xa))) : -e0 * (-expm1(-(xa - x0))));
+        T jp;
+        if (sun[j]) {   // elemental_inelastic.jl:508-548 (mu_i = mu_0 on these rows)
+          if (fabs(d0 - d1) > ss_tol<T>::close())
+            jp = wl * g0 * zp * wct02 * ed / (T(1) - ratio);
+          else
+            jp = (d0 / mi) * wct02 * wl * g0 * zp * e0;
+        } else {        // :549-560
+          const T den = rm[j] - ratio;
+          if (fabs(den) < ss_tol<T>::close())
+            jp = (d0 / mi) * wct02 * wl * g0 * zp * e0;
+          else
+            jp = wct02 * wl * g0 * zp * (T(1) / den) * ed;
+        }
+        // :577-579; 1 - exp(-(x1 + x0)) = -(a1 + a0 + a1 a0) with a = expm1(-x): no cancellation, no transcendental
+        const T jm = wct02 * wl * g0 * zm * (T(1) / (rm[j] + ratio)) * (-(a1[j] + a0 + a1[j] * a0));
+        sp[j] += jp;
+        sm[j] += jm;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < SS_RB; ++j) {
+      if (iz == 0) {   // rt_kernel_ss.jl:308-314
+        Sp[j] = sp[j];
+        Sm[j] = sm[j];
+      } else {         // get_interaction_ss_RRS! (interaction_ss.jl:87-88) on the line sums: exp(-tau[n1] / mu_i) has no line index
+        Sp[j] = Sp[j] * e1[j] + sp[j];
+        Sm[j] = Sm[j] + sm[j] * exp(-ts1 / rw.mi[j]);
+      }
+    }
+  }
+  if (!live) return;
+#pragma unroll
+  for (int j = 0; j < SS_RB; ++j) {
+    if (!rw.on[j]) continue;
+    const int e = blockIdx.y * SS_RB + j;
+    const long long dst = (n1 * ns + e / nV) * nV + e % nV;
+    ieR[dst] += w[e] * Sm[j];
+    ieT[dst] += w[e] * Sp[j];
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------------------------------------
+// Device tables of one call in the library's scratch: ss_layer[L] | w[nV n_stokes] | row0[nV].  One stream-ordered copy of a
+// packed host image (pageable memory: staged by the runtime before the call returns), so L and nV are not capped.
+template <typename T>
+struct ss_tables {
+  const ss_layer<T>* lay;
+  const T* w;
+  const int* row0;
+};
+template <typename T>
+static int ss_upload(int L, const std::vector<ss_layer<T>>& lay, int ns, int nV, const int* row0_h, const T* w_h, hipStream_t st,
+                     ss_tables<T>* out) {
+  const size_t o_w = sizeof(ss_layer<T>) * (size_t)L;
+  const size_t o_r = o_w + sizeof(T) * (size_t)nV * ns;
+  const size_t total = o_r + sizeof(int) * (size_t)nV;
+  std::vector<unsigned char> img(total);
+  memcpy(img.data(), lay.data(), o_w);
+  memcpy(img.data() + o_w, w_h, o_r - o_w);
+  memcpy(img.data() + o_r, row0_h, total - o_r);
+  unsigned char* dev = static_cast<unsigned char*>(scratch(total, SS_SLOT, st));
+  if (!dev) return VSM_ERR_HIP;
+  VSM_HIP(hipMemcpyAsync(dev, img.data(), total, hipMemcpyHostToDevice, st));
+  VSM_HIP(hipStreamSynchronize(st));   // `img` dies with this frame: the copy (a few hundred bytes, once per moment) must have left it
+  out->lay = reinterpret_cast<const ss_layer<T>*>(dev);
+  out->w = reinterpret_cast<const T*>(dev + o_w);
+  out->row0 = reinterpret_cast<const int*>(dev + o_r);
+  return VSM_OK;
+}
+
+template <typename T, typename Q>
+static int ss_check_common(const char* who, const Q* q, int S, int L, int nV, const int* row0_h, const T* w_h) {
+  VSM_REQUIRE(q && q->mu && q->wt, "%s: null quad", who);
+  VSM_REQUIRE(q->N > 0 && q->n_stokes >= 1 && q->n_stokes <= 4 && q->N % q->n_stokes == 0 && q->i_mu0 >= 0 &&
+                  (q->i_mu0 + 1) * q->n_stokes <= q->N,
+              "%s: bad quad", who);
+  VSM_REQUIRE(S >= 0 && L >= 1, "%s: S >= 0 and L >= 1 required (S = %d, L = %d)", who, S, L);
+  VSM_REQUIRE(nV >= 1 && row0_h && w_h, "%s: nV >= 1 viewing rows and their tables required", who);
+  VSM_REQUIRE((long long)nV * q->n_stokes <= 65535LL * SS_RB, "%s: too many viewing rows (%d)", who, nV);
+  for (int v = 0; v < nV; ++v)
+    VSM_REQUIRE(row0_h[v] >= 0 && row0_h[v] + q->n_stokes <= q->N, "%s: row0[%d] = %d out of range", who, v, row0_h[v]);
+  return VSM_OK;
+}
+
+template <typename T, typename Q>
+static int ss_column(const Q* q, int S, int L, int m, const T* const* tau_h, const T* const* varpi_h, const T* const* tau_sum_h,
+                     const T* const* Zpp_h, const T* const* Zmp_h, const long long* zs_h, const T* F0, const T* sj_m, const T* sj_p,
+                     const T* ts_surf, int nV, const int* row0_h, const T* w_h, T* R, T* Tt, T* J0_m, T* J0_p, void* stream) {
+  int rc;
+  if ((rc = ss_check_common<T>("ss_column", q, S, L, nV, row0_h, w_h))) return rc;
+  VSM_REQUIRE(tau_h && varpi_h && tau_sum_h && Zpp_h && Zmp_h && zs_h, "ss_column: null layer table");
+  VSM_REQUIRE(F0 && sj_m && ts_surf && R && Tt, "ss_column: null argument");
+  VSM_REQUIRE((J0_m == nullptr) == (J0_p == nullptr), "ss_column: J0_m and J0_p go together");
+  VSM_REQUIRE(m >= 0, "ss_column: m >= 0");
+  const long long NN = (long long)q->N * q->N;
+  std::vector<ss_layer<T>> lay((size_t)L);
+  for (int iz = 0; iz < L; ++iz) {
+    VSM_REQUIRE(tau_h[iz] && varpi_h[iz] && tau_sum_h[iz] && Zpp_h[iz] && Zmp_h[iz], "ss_column: null entry in layer table %d", iz);
+    VSM_REQUIRE(zs_h[iz] == 0 || zs_h[iz] == NN, "ss_column: z_stride[%d] must be 0 or N*N", iz);
+    lay[iz] = ss_layer<T>{tau_h[iz], varpi_h[iz], tau_sum_h[iz], Zpp_h[iz], Zmp_h[iz], nullptr, zs_h[iz]};
+  }
+  if (S == 0) return VSM_OK;
+  hipStream_t st = as_stream(stream);
+  ss_tables<T> t;
+  if ((rc = ss_upload<T>(L, lay, q->n_stokes, nV, row0_h, w_h, st, &t))) return rc;
+  const unsigned gx = (unsigned)((S + SS_TB - 1) / SS_TB);
+  const unsigned gv = (unsigned)((nV * q->n_stokes + SS_RB - 1) / SS_RB);
+  hipLaunchKernelGGL((k_ss_column<T, true>), dim3(gx, gv), dim3(SS_TB), 0, st, q->N, q->n_stokes, S, L, m, q->i_mu0, t.lay, F0,
+                     sj_m, sj_p, ts_surf, q->mu, nV, t.row0, t.w, R, Tt);
+  VSM_LAUNCH_CHECK("k_ss_column");
+  if (J0_m) {
+    const unsigned gf = (unsigned)((q->N + SS_RB - 1) / SS_RB);
+    hipLaunchKernelGGL((k_ss_column<T, false>), dim3(gx, gf), dim3(SS_TB), 0, st, q->N, q->n_stokes, S, L, m, q->i_mu0, t.lay,
+                       F0, sj_m, sj_p, ts_surf, q->mu, nV, t.row0, t.w, J0_m, J0_p);
+    VSM_LAUNCH_CHECK("k_ss_column (all streams)");
+  }
+  return VSM_OK;
+}
+
+template <typename T, typename Q>
+static int ss_column_rrs(const Q* q, int S, int L, int m, int K, const T* const* tau_h, const T* const* tau_sum_h,
+                         const T* const* fscatt_h, const int* shift, const T* varpi_ie, const T* Zpp_ie, const T* Zmp_ie,
+                         const T* F0, int halo, int nV, const int* row0_h, const T* w_h, T* ieR, T* ieT, void* stream) {
+  int rc;
+  if ((rc = ss_check_common<T>("ss_column_rrs", q, S, L, nV, row0_h, w_h))) return rc;
+  VSM_REQUIRE(K >= 0, "ss_column_rrs: K >= 0 required (K = %d)", K);
+  VSM_REQUIRE(tau_h && tau_sum_h && fscatt_h, "ss_column_rrs: null layer table");
+  VSM_REQUIRE(F0 && ieR && ieT && Zpp_ie && Zmp_ie, "ss_column_rrs: null argument");
+  VSM_REQUIRE(K == 0 || (shift && varpi_ie), "ss_column_rrs: null line table");
+  VSM_REQUIRE(m >= 0 && halo >= 0, "ss_column_rrs: m >= 0 and halo >= 0");
+  std::vector<ss_layer<T>> lay((size_t)L);
+  for (int iz = 0; iz < L; ++iz) {
+    VSM_REQUIRE(tau_h[iz] && tau_sum_h[iz] && fscatt_h[iz], "ss_column_rrs: null entry in layer table %d", iz);
+    lay[iz] = ss_layer<T>{tau_h[iz], nullptr, tau_sum_h[iz], nullptr, nullptr, fscatt_h[iz], 0};
+  }
+  if (S == 0 || K == 0) return VSM_OK;
+  if (halo > VSM_SS_MAX_HALO) halo = VSM_SS_MAX_HALO;
+  hipStream_t st = as_stream(stream);
+  ss_tables<T> t;
+  if ((rc = ss_upload<T>(L, lay, q->n_stokes, nV, row0_h, w_h, st, &t))) return rc;
+  const unsigned gx = (unsigned)((S + SS_TB - 1) / SS_TB);
+  const unsigned gv = (unsigned)((nV * q->n_stokes + SS_RB - 1) / SS_RB);
+  const size_t lds = sizeof(T) * (size_t)(4 + 2 * SS_RB) * (size_t)(SS_TB + 2 * halo);
+  hipLaunchKernelGGL(k_ss_column_rrs<T>, dim3(gx, gv), dim3(SS_TB), lds, st, q->N, q->n_stokes, S, L, K, m, q->i_mu0, halo, t.lay,
+                     shift, varpi_ie, Zpp_ie, Zmp_ie, F0, q->mu, nV, t.row0, t.w, ieR, ieT);
+  VSM_LAUNCH_CHECK("k_ss_column_rrs");
+  return VSM_OK;
+}
+
+}  // namespace vsm
+
+using namespace vsm;
+
+extern "C" {
+
+#define VSM_SS_API(T, SFX)                                                                                                     \
+  int vsm_ss_column_##SFX(const vsm_quad_##SFX* q, int S, int L, int m, const T* const* tau_h, const T* const* varpi_h,        \
+                          const T* const* tau_sum_h, const T* const* Zpp_h, const T* const* Zmp_h, const long long* z_stride_h, \
+                          const T* F0, const T* surf_j0_m, const T* surf_j0_p, const T* tau_sum_surface, int nV,               \
+                          const int* row0_h, const T* w_h, T* R_SFI, T* T_SFI, T* J0_m, T* J0_p, void* stream) {               \
+    return ss_column<T>(q, S, L, m, tau_h, varpi_h, tau_sum_h, Zpp_h, Zmp_h, z_stride_h, F0, surf_j0_m, surf_j0_p,             \
+                        tau_sum_surface, nV, row0_h, w_h, R_SFI, T_SFI, J0_m, J0_p, stream);                                   \
+  }                                                                                                                            \
+  int vsm_ss_column_rrs_##SFX(const vsm_quad_##SFX* q, int S, int L, int m, int K, const T* const* tau_h,                      \
+                              const T* const* tau_sum_h, const T* const* fscatt_h, const int* shift, const T* varpi_ie,        \
+                              const T* Zpp_ie, const T* Zmp_ie, const T* F0, int halo, int nV, const int* row0_h,              \
+                              const T* w_h, T* ieR_SFI, T* ieT_SFI, void* stream) {                                            \
+    return ss_column_rrs<T>(q, S, L, m, K, tau_h, tau_sum_h, fscatt_h, shift, varpi_ie, Zpp_ie, Zmp_ie, F0, halo, nV, row0_h,  \
+                            w_h, ieR_SFI, ieT_SFI, stream);                                                                    \
+  }
+VSM_SS_API(double, f64)
+VSM_SS_API(float, f32)
+
+}  // extern "C"
