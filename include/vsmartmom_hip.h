@@ -925,6 +925,46 @@ int vsm_ss_column_f32(const vsm_quad_f32* q, int S, int L, int m, const float* c
                       const long long* z_stride_h, const float* F0, const float* surf_j0_m, const float* surf_j0_p,
                       const float* tau_sum_surface, int nV, const int* row0_h, const float* w_h, float* R_SFI, float* T_SFI,
                       float* J0_m, float* J0_p, void* stream);
+/* The linearized twin of vsm_ss_column_*: d R_SFI / d x_p and d T_SFI / d x_p of one Fourier moment for the parameter slots
+ * [p_lo, p_hi) of P (slot order of parameter_layout.jl:28-56; the first p_layer slots are layer parameters, the others belong to
+ * the surface).  The reference has no linearized single-scattering driver; the statements are those of its linearized full run
+ * taken at ndoubl = 0: per layer the source derivatives of get_elem_rt_SFI_fused! (CoreKernel/elemental_lin.jl:602-712: chain
+ * rule through tau, varpi, Z and the beam term -tau_sum' / mu_0) with dtau = the layer's tau, and the derivative of the two
+ * statements of get_interaction_ss! (CoreKernel/interaction_ss.jl:14-19), taken on J0+ before its update:
+ *   J0+'[i,n] = (J0+'[i,n] - J0+[i,n] tau'[n] / mu_i) exp(-tau[n] / mu_i) + j0+'[i,n],
+ *   J0-'[i,n] += (j0-'[i,n] - j0-[i,n] tau_sum'[n] / mu_i) exp(-tau_sum[n] / mu_i),
+ * the TOA layer copied (rt_kernel_ss.jl:213-216), the branch of a viewing row equal to the SZA row as elemental_lin.jl writes it;
+ * then the same update with the surface layer (tau = 0, tau_sum = tau_sum_surface) and the rows of postprocessing_vza! (lin)
+ * (tools/postprocessing_vza_lin.jl:18-48).  Surface slots are exact zeros in the atmospheric layers.
+ * Layer tables (HOST arrays of L device pointers, as in vsm_ss_column_*): the forward tau_h / varpi_h / tau_sum_h / Zpp_h / Zmp_h /
+ * z_stride_h, and tau_dot_h / varpi_dot_h / tau_sum_dot_h [S,p_layer] per layer -- the layer slices of vsm_layer_optics_lin_*'s
+ * outputs computed with an all-zero ndoubl table, so that tau_dot is the derivative of the layer's FULL tau.  zdcoef_h (nullable
+ * table, nullable entries = Z_dot is zero): per layer [CT,p_layer,S] coefficients of Z_dot over the CT component blocks
+ * Zc_pp / Zc_mp [N,N,CT] of the moment (vsm_elemental_lin_mix_*), read for the first p_zdot <= p_layer slots only (7 per aerosol:
+ * the coefficients of the gas slots behind them are exact zeros and are skipped): of every block only the n_stokes SZA columns at the viewing
+ * rows are read, and neither Z_dot nor a per-slot source array is ever formed.
+ * Surface: surf_j0_m [N,1,S] and surf_j0_m_lin / surf_j0_p_lin [N,1,S,P] are j0- and ap_J0-+ as vsm_lambertian_surface_lin_* /
+ * vsm_brdf_surface_lin_* write them (all P slots); surf_j0_p (nullable = zero) is the FORWARD builder's j0+ -- the direct beam,
+ * proportional to exp(-tau_sum / mu_0) (lambertian_surface.jl:75) -- and contributes -j0+ tau_sum' / mu_0 to the layer slots;
+ * tau_sum_dot_surface [S,p_layer].  Rdot / Tdot [nV,n_stokes,S,P] are ACCUMULATED for the slots of the range only, each slot
+ * computed independently of the range it is called in.  Invalid arguments (P < 1, L < 1, null tables, rows outside N, a slot
+ * range outside P) return VSM_ERR_INVALID_ARG before any launch. */
+int vsm_ss_column_lin_f64(const vsm_quad_f64* q, int S, int L, int m, int P, int p_layer, int p_zdot, int p_lo, int p_hi,
+                          const double* const* tau_h, const double* const* varpi_h, const double* const* tau_sum_h,
+                          const double* const* Zpp_h, const double* const* Zmp_h, const long long* z_stride_h,
+                          const double* const* tau_dot_h, const double* const* varpi_dot_h, const double* const* tau_sum_dot_h,
+                          const double* const* zdcoef_h, int CT, const double* Zc_pp, const double* Zc_mp, const double* F0,
+                          const double* surf_j0_m, const double* surf_j0_p, const double* surf_j0_m_lin, const double* surf_j0_p_lin,
+                          const double* tau_sum_surface, const double* tau_sum_dot_surface, int nV, const int* row0_h,
+                          const double* w_h, double* Rdot, double* Tdot, void* stream);
+int vsm_ss_column_lin_f32(const vsm_quad_f32* q, int S, int L, int m, int P, int p_layer, int p_zdot, int p_lo, int p_hi,
+                          const float* const* tau_h, const float* const* varpi_h, const float* const* tau_sum_h,
+                          const float* const* Zpp_h, const float* const* Zmp_h, const long long* z_stride_h,
+                          const float* const* tau_dot_h, const float* const* varpi_dot_h, const float* const* tau_sum_dot_h,
+                          const float* const* zdcoef_h, int CT, const float* Zc_pp, const float* Zc_mp, const float* F0,
+                          const float* surf_j0_m, const float* surf_j0_p, const float* surf_j0_m_lin, const float* surf_j0_p_lin,
+                          const float* tau_sum_surface, const float* tau_sum_dot_surface, int nV, const int* row0_h,
+                          const float* w_h, float* Rdot, float* Tdot, void* stream);
 /* The rotational-Raman twin (rt_kernel_ss!(::RRS), rt_kernel_ss.jl:240-337): per layer the sources of get_elem_rt_SFI_RRS!
  * (CoreKernel/elemental_inelastic.jl:479-603; near / far branches on rt_close_tol and on the viewing row being the SZA row as
  * written there) with ndoubl = 0 and dtau = tau, composed by get_interaction_ss_RRS! (interaction_ss.jl:79-90) and summed over the

@@ -13,7 +13,8 @@ Sub-modules
                     single-scattering run)
     host_model      host-side producers of the hot path's inputs (streams, Z moments, layer mixing)
     CoreRTLin       linearized (Jacobian) pass: rt_run(model, lin_model, ...),
-                    rt_run_multisensor(model, lin_model, ..., sensor_levels) (core_rt_ms_lin: Jacobians at any level)
+                    rt_run_multisensor(model, lin_model, ..., sensor_levels) (core_rt_ms_lin: Jacobians at any level),
+                    rt_run_ss(model, lin_model, ...) (core_rt_ss: analytic single-scattering Jacobians)
     CoreRTRaman     rotational-Raman pass: rt_run(RS_type::RRS, model, iBand),
                     rt_run_multisensor(RS_type, model, sensor_levels) (core_rt_ms_raman),
                     rt_run_ss(RS_type, model, iBand) (core_rt_ss: the single-scatter inelastic correction)
@@ -40,6 +41,7 @@ CoreRTRaman.MultiSensorRamanResult = core_rt_ms_raman.MultiSensorRamanResult
 CoreRTLin.rt_run_multisensor = core_rt_ms_lin.rt_run_multisensor
 CoreRT.rt_run_ss = core_rt_ss.rt_run_ss
 CoreRTRaman.rt_run_ss = core_rt_ss.rt_run_ss_rrs
+CoreRTLin.rt_run_ss = core_rt_ss.rt_run_ss_lin
 CoreRTLin.MultiSensorLinResult = core_rt_ms_lin.MultiSensorLinResult
 
 __version__ = "0.1.0"

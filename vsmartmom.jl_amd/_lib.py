@@ -141,6 +141,8 @@ _SIGS = {
     "vsm_copy_added_to_composite_ie_{T}": (_I, [_I, _I, _P, _P, _P]),
     "vsm_postprocess_vza_ie_{T}": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "vsm_ss_column_{T}": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "vsm_ss_column_lin_{T}": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P,
+                                   _P, _P, _I, _P, _P, _P, _P, _P]),
     "vsm_ss_column_rrs_{T}": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
     "vsm_run_supported": (_I, [_I, _I, _I]),
     "vsm_run_workspace_bytes": (_SZ, [_I, _I, _I, _I, _P]),

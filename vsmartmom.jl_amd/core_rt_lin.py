@@ -175,26 +175,15 @@ MIX_Z_MOMENTS_MAX = 24
 REDUCE_M0 = True   # A/B switch (module attribute): False = the moment m = 0 with all Stokes components of the model
 
 
-class SceneLin:
-    """Everything rt_run(model, lin_model, NAer, NGas, NSurf) needs, resident in HBM (the linearized twin of CoreRT.Scene).
-    The raw inputs -- tau_rayl, tau_abs, lin_model.tau_abs_dot [nSpec, Nz] and the small aerosol tables (tau_aer,
-    tau_aer_dot, ssa / f_trunc and their Mie derivatives, Greek coefficients and their derivatives) -- are uploaded ONCE; the
-    forward layer optics come from CoreRT.Scene's device pass (vsm_layer_optics, vsm_compute_Z_moments, vsm_layer_dtau) and
-    their parameter derivatives from vsm_layer_optics_lin (tau_dot, varpi_dot, tau_sum_dot and the COEFFICIENTS of Z_dot over
-    the component phase matrices: constructCoreOpticalProperties with lin_model, compEffectiveLayerProperties_lin.jl:43-197,
-    types_lin.jl:196-380).  Z_dot[N, N, nSpec, P] is never materialised: elemental! (lin) forms it from the coefficients
-    (vsm_elemental_lin_mix).  `run()` only launches kernels; exp(-dtau / mu0) is refreshed on the device per layer.
+class LinInputs:
+    """The upload / prepare half of a linearized scene: the argument checks of rt_run(model, lin_model, NAer, NGas, NSurf), the
+    derivative tables of lin_model in HBM (`upload`), the derivative layer optics of vsm_layer_optics_lin -- dtau_dot_all,
+    varpi_dot, tau_sum_dot, fz, zdcoef -- with the component blocks Zall of every moment (`prepare`), and the Cox-Munk
+    (rho, drho) pairs.  It owns nothing N x N per spectral point and no layer: SceneLin adds those for the full run, the
+    single-scattering scene (core_rt_ss.SceneSSLin) does without them.  A subclass sets `self.fwd` (a CoreRT.Scene) between
+    `_check_lin_args` and `_alloc_lin_optics`."""
 
-    `spec_slice` selects this rank's spectral shard; ndoubl and the tags always come from the FULL spectral axis
-    (rt_kernel_lin.jl:87-95 uses batch-global maxima like the forward kernel).  `host_optics=True` builds the same inputs with
-    the host mirror (host_model.constructCoreOpticalPropertiesLin, Z_dot materialised on the host) -- kept as a cross-check.
-
-    Parameter slots (parameter_layout.jl:28-56): 7 per aerosol (tau_ref, n_r, n_i, r_m, sigma_r, p0, sigma_p; their optics
-    derivatives are inputs: LinModel.tau_aer_dot / lin_aerosol_optics), the gases, then ONE surface slot -- the Lambertian albedo
-    (lambertian_surface_lin.jl:48-162) or the Cox-Munk wind speed (coxmunk_surface_lin.jl:27-102)."""
-
-    def __init__(self, model: H.RTModel, lin_model: H.LinModel, NAer: int, NGas: int, NSurf: int,
-                 spec_slice: Optional[slice] = None, host_optics: bool = False, _reduce_m0: bool = True):
+    def _check_lin_args(self, model: H.RTModel, lin_model: H.LinModel, NAer: int, NGas: int, NSurf: int):
         if NAer != lin_model.n_aer or NAer != len(model.aerosol_optics) or NSurf != 1 or NGas != len(lin_model.tau_abs_dot):
             raise _lib.VSMError("rt_run (linearized): NAer must equal the aerosols of model and lin_model, NGas = "
                                 "len(lin_model.tau_abs_dot), NSurf = 1")
@@ -202,11 +191,6 @@ class SceneLin:
             raise _lib.VSMError("rt_run (linearized): surface %r has no linearized builder here" % (model.surface,))
         arch, FT = model.architecture, model.float_type
         CR._require_gpu(arch)
-        # vsm_elemental_lin_mix forms Z_dot from at most 16 component blocks (1 + 5 NAer: VSM_LIN_CT_MAX of vsm_lin.hip), i.e. three
-        # aerosols; the reference has no such limit, so beyond it the scene takes the host-optics path (Z_dot materialised per
-        # layer and moment, vsm_elemental_lin) from the start instead of failing inside run()
-        if 1 + 5 * NAer > 16:
-            host_optics = True
         self.model, self.lin_model, self.arch, self.FT = model, lin_model, arch, FT
         pol, qp = model.polarization_type, model.quad_points
         self.pol, self.qp = pol, qp
@@ -215,18 +199,13 @@ class SceneLin:
         self.P, self.pl, self.nAer, self.nGas = P, pl, NAer, NGas
         if P > 64:
             raise _lib.VSMError("rt_run (linearized): %d parameter slots (limit 64)" % P)
-        # forward optics, quadrature, F0, composite / added / surface layers and R, T: the forward scene's device state
-        # (rt_kernel_lin.jl:87 hard-codes scatter = true: a layer with tau*varpi <= 2 eps still goes through elemental! and
-        # doubling! with ndoubl = 0 -- Scene.prepare gives such a layer ndoubl = 0 as well -- and only its interaction
-        # follows the 00 / 01 / 10 tag of extractEffectiveProps)
-        self.fwd = CR.Scene(model, spec_slice, host_optics=host_optics, full_added_layer=True)
-        self.fwd.compute_hdrf = False
+
+    def _alloc_lin_optics(self):
         fwd = self.fwd
         self.sl, self.S, self.N, self.dq, self.F0 = fwd.sl, fwd.S, fwd.N, fwd.dq, fwd.F0
-        S, N, L = self.S, self.N, fwd.Nz
-        dt, dev = CR._torch_dtype(FT), devi(arch)
+        S, L, P, pl, NAer = self.S, fwd.Nz, self.P, self.pl, self.nAer
+        dt, dev = CR._torch_dtype(self.FT), devi(self.arch)
         self.dt = dt
-        nV = len(model.vza)
         self.C_, self.CT = 1 + NAer, 1 + NAer + 4 * NAer
         z = lambda *sh: torch.empty(sh, dtype=dt, device=dev)
         # layouts: the reference's column-major [nSpec, p] per layer -> tensors (L, p, S)
@@ -235,52 +214,6 @@ class SceneLin:
         self.zdcoef = z(L, S, pl, self.CT) if NAer else None
         self.Zall = None          # per moment ((CT, N, N), (CT, N, N)): component blocks of Z and of the Greek derivatives
         self.host_zdot = None     # host_optics: per moment and layer the materialised Z_dot
-        self.upload()
-        if host_optics:
-            self._prepare_host()
-        else:
-            self.prepare()
-        self.surf = []
-        for m in range(model.m_max + 1):
-            rho = drho = None
-            if isinstance(model.surface, H.CoxMunkSurface):
-                rho, drho = CR.reflectance(model.surface, self.dq, m, arch, FT, deriv=True)
-            self.surf.append((rho, drho))
-        self.added, self.added_s, self.comp = fwd.added, fwd.added_surface, fwd.composite
-        self.al, self.als = AddedLayerLin(FT, arch, P, N, S), AddedLayerLin(FT, arch, P, N, S, shared=True)
-        self.cl = CompositeLayerLin(FT, arch, P, N, S)
-        self.expk = torch.empty(max(S, 1), dtype=dt, device=dev)
-        self.R, self.T = fwd.R_SFI, fwd.T_SFI
-        self.Rd = torch.zeros((P, S, pol.n, nV), dtype=dt, device=dev)
-        self.Td = torch.zeros_like(self.Rd)
-        self._lanes = []
-        self._fold = {}
-        # The composite above the surface does not depend on a surface parameter: in the atmospheric layers the surface slots of
-        # the added layer's AND of the composite's derivative stacks are zero, and the reference's loop over all Nparams
-        # (interaction_lin.jl:242,291) computes exact zeros for them.  The layer interactions therefore run on the layer slots
-        # [0, n_layer_params) only; the surface interaction on all of them.
-        self._layer_slots = (0, pl) if 0 < pl < P else None
-        # The Fourier moment m = 0 as a Stokes_IQ run (large batches; models without aerosol Jacobian slots over a Lambertian
-        # surface).  At m = 0 no phase matrix couples (I,Q) with (U,V) (compute_Z_matrices.jl:26-110; the forward scene reads the
-        # exact zeros off the device: `coupling`), the Lambertian surface reflects into I only, the gas and albedo derivatives
-        # inherit the structure, and a beam without U / V components drives nothing in the (U,V) block: R, T, Rdot, Tdot of m = 0
-        # are those of the same model carried with two Stokes components, U = V = 0.
-        self.sub0 = None
-        F0m = model.F0
-        c0 = fwd.coupling[0] if getattr(fwd, "coupling", None) else None
-        if (_reduce_m0 and REDUCE_M0 and pol.n >= 3 and S >= self.LANE_POINTS and NAer == 0 and not host_optics and c0 is not None
-                and isinstance(model.surface, H.LambertianSurfaceScalar) and (F0m is None or not np.any(np.asarray(F0m)[2:] != 0))
-                and not any(c0 >> (4 * a + b) & 1 or c0 >> (4 * b + a) & 1 for a in (0, 1) for b in range(2, pol.n))):
-            self.sub0 = SceneLin(self._sub0_model(), lin_model, NAer, NGas, NSurf, spec_slice, _reduce_m0=False)
-
-    def _sub0_model(self):
-        """The Stokes_IQ model of the moment m = 0, derived from the parent's model AS IT IS NOW (a step rebinds model.tau_abs,
-        scene.lin_model, ... and re-uploads: the sub-scene must see the new arrays, not the constructor-time snapshot)."""
-        model, qp = self.model, self.model.quad_points
-        F0m = model.F0
-        qi = H.QuadPoints(qp.mu0, qp.imu0, qp.qp_mu, qp.wt_mu, np.repeat(qp.qp_mu, 2), np.repeat(qp.wt_mu, 2), qp.Nquad, qp.Nstreams)
-        return dataclasses.replace(model, polarization_type=H.Stokes_IQ(), quad_points=qi, m_max=0,
-                                   F0=None if F0m is None else np.ascontiguousarray(np.asarray(F0m)[:2]))
 
     # -- inputs -----------------------------------------------------------------------------------------------------------
     def upload(self):
@@ -332,7 +265,7 @@ class SceneLin:
         _lib.call("vsm_layer_optics_lin", dt, S_full, fwd.lo, self.S, L, self.nAer, self.nGas, self.P, CR._ptr(fwd.tau_rayl_d),
                   CR._ptr(fwd.tau_abs_d), C.c_double(float(model.varpi_Cabannes)), CR._ptr(fwd.tau_aer_d), CR._ptr(fwd.ssa_d),
                   CR._ptr(fwd.ftr_d), CR._ptr(self.tau_abs_dot_d), CR._ptr(self.tau_aer_dot_d), CR._ptr(self.ssa_dot_d),
-                  CR._ptr(self.ftr_dot_d), CR._ptr(fwd.nd_dev), CR._ptr(self.dtau_dot_all), CR._ptr(self.varpi_dot),
+                  CR._ptr(self.ftr_dot_d), CR._ptr(self._ndoubl_table()), CR._ptr(self.dtau_dot_all), CR._ptr(self.varpi_dot),
                   CR._ptr(self.tau_sum_dot), CR._ptr(self.fz), CR._ptr(self.zdcoef), CR._stream_ptr())
         if self.nAer:
             q = self.dq.cstruct()
@@ -345,6 +278,102 @@ class SceneLin:
                     _lib.call("vsm_compute_Z_moments", dt, C.byref(q), m, lmax, CR._ptr(gd), CR._ptr(Zp[k]), CR._ptr(Zm[k]),
                               CR._stream_ptr())
                 self.Zall.append((Zp, Zm))
+
+    def _ndoubl_table(self):
+        """The doubling numbers vsm_layer_optics_lin scales tau_dot by (device int[L])."""
+        return self.fwd.nd_dev
+
+    def _surface_tables(self):
+        model = self.model
+        self.surf = []
+        for m in range(model.m_max + 1):
+            rho = drho = None
+            if isinstance(model.surface, H.CoxMunkSurface):
+                rho, drho = CR.reflectance(model.surface, self.dq, m, self.arch, self.FT, deriv=True)
+            self.surf.append((rho, drho))
+
+
+class SceneLin(LinInputs):
+    """Everything rt_run(model, lin_model, NAer, NGas, NSurf) needs, resident in HBM (the linearized twin of CoreRT.Scene).
+    The raw inputs -- tau_rayl, tau_abs, lin_model.tau_abs_dot [nSpec, Nz] and the small aerosol tables (tau_aer,
+    tau_aer_dot, ssa / f_trunc and their Mie derivatives, Greek coefficients and their derivatives) -- are uploaded ONCE; the
+    forward layer optics come from CoreRT.Scene's device pass (vsm_layer_optics, vsm_compute_Z_moments, vsm_layer_dtau) and
+    their parameter derivatives from vsm_layer_optics_lin (tau_dot, varpi_dot, tau_sum_dot and the COEFFICIENTS of Z_dot over
+    the component phase matrices: constructCoreOpticalProperties with lin_model, compEffectiveLayerProperties_lin.jl:43-197,
+    types_lin.jl:196-380).  Z_dot[N, N, nSpec, P] is never materialised: elemental! (lin) forms it from the coefficients
+    (vsm_elemental_lin_mix).  `run()` only launches kernels; exp(-dtau / mu0) is refreshed on the device per layer.
+
+    `spec_slice` selects this rank's spectral shard; ndoubl and the tags always come from the FULL spectral axis
+    (rt_kernel_lin.jl:87-95 uses batch-global maxima like the forward kernel).  `host_optics=True` builds the same inputs with
+    the host mirror (host_model.constructCoreOpticalPropertiesLin, Z_dot materialised on the host) -- kept as a cross-check.
+
+    Parameter slots (parameter_layout.jl:28-56): 7 per aerosol (tau_ref, n_r, n_i, r_m, sigma_r, p0, sigma_p; their optics
+    derivatives are inputs: LinModel.tau_aer_dot / lin_aerosol_optics), the gases, then ONE surface slot -- the Lambertian albedo
+    (lambertian_surface_lin.jl:48-162) or the Cox-Munk wind speed (coxmunk_surface_lin.jl:27-102)."""
+
+    def __init__(self, model: H.RTModel, lin_model: H.LinModel, NAer: int, NGas: int, NSurf: int,
+                 spec_slice: Optional[slice] = None, host_optics: bool = False, _reduce_m0: bool = True):
+        self._check_lin_args(model, lin_model, NAer, NGas, NSurf)
+        arch, FT = model.architecture, model.float_type
+        # vsm_elemental_lin_mix forms Z_dot from at most 16 component blocks (1 + 5 NAer: VSM_LIN_CT_MAX of vsm_lin.hip), i.e. three
+        # aerosols; the reference has no such limit, so beyond it the scene takes the host-optics path (Z_dot materialised per
+        # layer and moment, vsm_elemental_lin) from the start instead of failing inside run()
+        if 1 + 5 * NAer > 16:
+            host_optics = True
+        pol, qp = self.pol, self.qp
+        P, pl = self.P, self.pl
+        # forward optics, quadrature, F0, composite / added / surface layers and R, T: the forward scene's device state
+        # (rt_kernel_lin.jl:87 hard-codes scatter = true: a layer with tau*varpi <= 2 eps still goes through elemental! and
+        # doubling! with ndoubl = 0 -- Scene.prepare gives such a layer ndoubl = 0 as well -- and only its interaction
+        # follows the 00 / 01 / 10 tag of extractEffectiveProps)
+        self.fwd = CR.Scene(model, spec_slice, host_optics=host_optics, full_added_layer=True)
+        self.fwd.compute_hdrf = False
+        fwd = self.fwd
+        self._alloc_lin_optics()
+        S, N = self.S, self.N
+        dt, dev = self.dt, devi(arch)
+        nV = len(model.vza)
+        self.upload()
+        if host_optics:
+            self._prepare_host()
+        else:
+            self.prepare()
+        self._surface_tables()
+        self.added, self.added_s, self.comp = fwd.added, fwd.added_surface, fwd.composite
+        self.al, self.als = AddedLayerLin(FT, arch, P, N, S), AddedLayerLin(FT, arch, P, N, S, shared=True)
+        self.cl = CompositeLayerLin(FT, arch, P, N, S)
+        self.expk = torch.empty(max(S, 1), dtype=dt, device=dev)
+        self.R, self.T = fwd.R_SFI, fwd.T_SFI
+        self.Rd = torch.zeros((P, S, pol.n, nV), dtype=dt, device=dev)
+        self.Td = torch.zeros_like(self.Rd)
+        self._lanes = []
+        self._fold = {}
+        # The composite above the surface does not depend on a surface parameter: in the atmospheric layers the surface slots of
+        # the added layer's AND of the composite's derivative stacks are zero, and the reference's loop over all Nparams
+        # (interaction_lin.jl:242,291) computes exact zeros for them.  The layer interactions therefore run on the layer slots
+        # [0, n_layer_params) only; the surface interaction on all of them.
+        self._layer_slots = (0, pl) if 0 < pl < P else None
+        # The Fourier moment m = 0 as a Stokes_IQ run (large batches; models without aerosol Jacobian slots over a Lambertian
+        # surface).  At m = 0 no phase matrix couples (I,Q) with (U,V) (compute_Z_matrices.jl:26-110; the forward scene reads the
+        # exact zeros off the device: `coupling`), the Lambertian surface reflects into I only, the gas and albedo derivatives
+        # inherit the structure, and a beam without U / V components drives nothing in the (U,V) block: R, T, Rdot, Tdot of m = 0
+        # are those of the same model carried with two Stokes components, U = V = 0.
+        self.sub0 = None
+        F0m = model.F0
+        c0 = fwd.coupling[0] if getattr(fwd, "coupling", None) else None
+        if (_reduce_m0 and REDUCE_M0 and pol.n >= 3 and S >= self.LANE_POINTS and NAer == 0 and not host_optics and c0 is not None
+                and isinstance(model.surface, H.LambertianSurfaceScalar) and (F0m is None or not np.any(np.asarray(F0m)[2:] != 0))
+                and not any(c0 >> (4 * a + b) & 1 or c0 >> (4 * b + a) & 1 for a in (0, 1) for b in range(2, pol.n))):
+            self.sub0 = SceneLin(self._sub0_model(), lin_model, NAer, NGas, NSurf, spec_slice, _reduce_m0=False)
+
+    def _sub0_model(self):
+        """The Stokes_IQ model of the moment m = 0, derived from the parent's model AS IT IS NOW (a step rebinds model.tau_abs,
+        scene.lin_model, ... and re-uploads: the sub-scene must see the new arrays, not the constructor-time snapshot)."""
+        model, qp = self.model, self.model.quad_points
+        F0m = model.F0
+        qi = H.QuadPoints(qp.mu0, qp.imu0, qp.qp_mu, qp.wt_mu, np.repeat(qp.qp_mu, 2), np.repeat(qp.wt_mu, 2), qp.Nquad, qp.Nstreams)
+        return dataclasses.replace(model, polarization_type=H.Stokes_IQ(), quad_points=qi, m_max=0,
+                                   F0=None if F0m is None else np.ascontiguousarray(np.asarray(F0m)[:2]))
 
     def _prepare_host(self):
         """The same derivative inputs from the host mirror (numpy, Z_dot materialised per layer and moment)."""

@@ -1,5 +1,6 @@
 """Single-scattering runs: rt_run_ss(model) and rt_run_ss(RS_type::RRS, model, iBand) (src/CoreRT/rt_run.jl:574-755) on the MI355X,
-through vsm_ss_column_* / vsm_ss_column_rrs_* (vsmartmom.jl_amd/csrc/vsm_ss.hip).
+through vsm_ss_column_* / vsm_ss_column_rrs_* (vsmartmom.jl_amd/csrc/vsm_ss.hip), and the linearized elastic run
+rt_run_ss(model, lin_model, NAer, NGas, NSurf) through vsm_ss_column_lin_* (SceneSSLin; the reference has no such driver).
 
 Mirrors rt_kernel_ss! (CoreKernel/rt_kernel_ss.jl:156-337: elemental! / elemental_inelastic! with ndoubl = 0 and dtau = the layer's
 tau, scatter hard-wired to true), interaction_ss! / interaction_inelastic_ss! (CoreKernel/interaction_ss.jl), the surface's
@@ -19,6 +20,7 @@ import torch
 from . import _lib
 from . import host_model as H
 from . import core_rt as CR
+from . import core_rt_lin as CL
 from .architectures import array_type, synchronize_if_gpu, to_host
 
 MAX_HALO = 192   # VSM_SS_MAX_HALO of the library
@@ -94,8 +96,11 @@ class SceneSS:
             sh = [abs(int(x)) for x in np.asarray(RS_type.i_lambda1lambda0).ravel() if abs(int(x)) < max(S, 1)]
             self.halo = min(max(sh or [0]), MAX_HALO)     # lines that can be in band at all; larger shifts read global memory
 
-    def run(self):
-        """rt_run.jl:671-749.  Asynchronous; returns the four (S, nStokes, nVZA) device tensors and J0-, J0+ (S, N) of m = 0."""
+    def run(self, after_moment=None):
+        """rt_run.jl:671-749.  Asynchronous; returns the four (S, nStokes, nVZA) device tensors and J0-, J0+ (S, N) of m = 0.
+        after_moment(mom, props, row0, w): called once per Fourier moment after its launches, with the materialised layer optics
+        and the viewing-row tables of the moment while fwd.added_surface still holds the moment's surface layer (the linearized
+        run launches its column there)."""
         model, fwd = self.model, self.fwd
         pol, qp, FT = fwd.pol, fwd.qp, self.FT
         for t in self.out + [self.J0_m, self.J0_p]:
@@ -120,6 +125,8 @@ class SceneSS:
                 Zp, Zm = self.Zie[m]
                 ss_column_rrs_(fwd.dq, m, tau, tau_sum, [self.fscatt[iz] for iz in range(len(layers))], self.drs.shift,
                                self.drs.varpi_ie, Zp, Zm, fwd.F0, self.halo, row0, w, nV, ieR_SFI, ieT_SFI)
+            if after_moment is not None:
+                after_moment(mom, props, row0, w)
             del props
         return tuple(self.out) + (self.J0_m, self.J0_p)
 
@@ -151,3 +158,114 @@ def rt_run_ss_rrs(RS_type, model: H.RTModel, iBand: int = 1):
     """rt_run_ss(RS_type::RRS, model, iBand) (rt_run.jl:593-755): the single-scattering run with rotational Raman scattering -- the
     single-scatter inelastic correction.  Same inputs as CoreRTRaman.rt_run; K = 0 lines is legal."""
     return _run(model, RS_type, iBand)
+
+
+def ss_column_lin_(dq: CR.DeviceQuad, m: int, P: int, p_layer: int, p_zdot: int, tau, varpi, tau_sum, Zpp, Zmp, z_stride, tau_dot, varpi_dot,
+                   tau_sum_dot, zdcoef, CT: int, Zc_pp, Zc_mp, F0, surf_j0_m, surf_j0_p, surf_j0_m_lin, surf_j0_p_lin,
+                   tau_sum_surface, tau_sum_dot_surface, row0, w, nV: int, Rdot, Tdot, p_range=None):
+    """vsm_ss_column_lin_*: one Fourier moment of the linearized single-scattering column.  Layer lists as in ss_column_, plus
+    tau_dot / varpi_dot / tau_sum_dot (lists of L device tensors (p_layer, S); tau_dot of the layer's full tau) and zdcoef (None, or
+    a list whose entries are None or (S, p_layer, CT) tensors, read for the first p_zdot slots: the aerosols').  Rdot / Tdot (P, S, nStokes, nVZA) accumulate the slots of
+    p_range = (p_lo, p_hi) (default: all P)."""
+    L, S = len(tau), int(F0.shape[0])
+    q = dq.cstruct()
+    zs = (C.c_longlong * L)(*[int(z) for z in z_stride])
+    tab = lambda ts: None if ts is None else (C.c_void_p * L)(*[None if t is None else t.data_ptr() for t in ts])
+    p_lo, p_hi = (0, P) if p_range is None else p_range
+    _lib.call("vsm_ss_column_lin", dq.dtype, C.byref(q), S, L, m, P, p_layer, int(p_zdot), int(p_lo), int(p_hi), tab(tau), tab(varpi),
+              tab(tau_sum), tab(Zpp), tab(Zmp), zs, tab(tau_dot), tab(varpi_dot), tab(tau_sum_dot), tab(zdcoef), int(CT),
+              CR._ptr(Zc_pp), CR._ptr(Zc_mp), CR._ptr(F0), CR._ptr(surf_j0_m), CR._ptr(surf_j0_p), CR._ptr(surf_j0_m_lin),
+              CR._ptr(surf_j0_p_lin), CR._ptr(tau_sum_surface), CR._ptr(tau_sum_dot_surface), nV, row0, w, CR._ptr(Rdot),
+              CR._ptr(Tdot), CR._stream_ptr())
+
+
+class SceneSSLin(CL.LinInputs):
+    """What the linearized single-scattering run needs, resident in HBM: a SceneSS without Raman lines (R, T and the surface layer
+    of the forward run come from it, through the same launches as rt_run_ss) plus the derivative optics of SceneLin
+    (CoreRTLin.LinInputs: dtau_dot_all -- here of the layers' FULL tau, vsm_layer_optics_lin with an all-zero doubling table --,
+    varpi_dot, tau_sum_dot, fz, zdcoef, Zall, the Cox-Munk (rho, drho)).  The one derivative layer it owns is the SHARED surface
+    AddedLayerLin the linearized surface builders write (4 P N^2 + 2 P N S elements), with a shared forward AddedLayer beside it
+    for the builder's own j0-: no added or composite layer, no derivative stack, nothing of size P N^2 S."""
+
+    def __init__(self, model: H.RTModel, lin_model: H.LinModel, NAer: int, NGas: int, NSurf: int):
+        _refuse_sources(model)
+        self._check_lin_args(model, lin_model, NAer, NGas, NSurf)
+        if 1 + 5 * NAer > 16:
+            raise NotImplementedError("rt_run_ss (linearized): at most three aerosols (16 component blocks of Z_dot); got %d" % NAer)
+        self.ss = SceneSS(model)
+        self.fwd = fwd = self.ss.fwd
+        self._alloc_lin_optics()
+        self._nd0 = torch.zeros(fwd.Nz, dtype=torch.int32, device=fwd.dev)
+        self.upload()
+        self.prepare()
+        self._surface_tables()
+        arch, FT, pol = self.arch, self.FT, self.pol
+        self.added_s = CR.make_added_layer(FT, arch, (self.N, self.N), self.S, shared=True)
+        self.als = CL.AddedLayerLin(FT, arch, self.P, self.N, self.S, shared=True)
+        self.R, self.T = fwd.R_SFI, fwd.T_SFI
+        self.Rd = torch.zeros((self.P, self.S, pol.n, len(model.vza)), dtype=self.dt, device=fwd.dev)
+        self.Td = torch.zeros_like(self.Rd)
+
+    def _ndoubl_table(self):
+        return self._nd0       # tau_dot itself: this run's layers are not doubled
+
+    def run(self):
+        """Asynchronous; returns R, T (S, nStokes, nVZA) and Rdot, Tdot (P, S, nStokes, nVZA) on the device."""
+        model, fwd = self.model, self.fwd
+        pol, qp, FT, dt = self.pol, self.qp, self.FT, self.dt
+        S, P, pl, L = self.S, self.P, self.pl, fwd.Nz
+        self.Rd.zero_()
+        self.Td.zero_()
+        if S == 0:
+            self.ss.run()
+            return self.R, self.T, self.Rd, self.Td
+        nV = len(model.vza)
+        isurf = self.layout.surface_index(0)
+        q_ = self.dq.cstruct()
+        tsd_s = self.tau_sum_dot[L]
+
+        def lin_moment(mom, props, row0, w):
+            """After the forward launches of the moment (fwd.added_surface holds the forward builder's surface layer: its j0+ is
+            read here): the linearized builder's j0- and ap_J0-+ of all P slots, then the linearized column."""
+            m, layers, tau_sum_s = mom["m"], mom["layers"], mom["tau_sum_surface"]
+            a_, al_ = self.added_s.cstruct(), self.als.cstruct()
+            rho, drho = self.surf[m]
+            if isinstance(model.surface, H.CoxMunkSurface):
+                _lib.call("vsm_brdf_surface_lin", dt, C.byref(q_), S, m, CR._ptr(rho), CR._ptr(drho), isurf, CR._ptr(tau_sum_s),
+                          CR._ptr(tsd_s), pl, CR._ptr(self.F0), C.byref(a_), C.byref(al_), CR._stream_ptr())
+            else:
+                alb = C.c_double(model.surface.albedo) if dt == torch.float64 else C.c_float(model.surface.albedo)
+                _lib.call("vsm_lambertian_surface_lin", dt, C.byref(q_), S, m, alb, isurf, CR._ptr(tau_sum_s), CR._ptr(tsd_s), pl,
+                          CR._ptr(self.F0), C.byref(a_), C.byref(al_), CR._stream_ptr())
+            zall = self.Zall[m] if self.Zall is not None else (None, None)
+            ss_column_lin_(fwd.dq, m, P, pl, 7 * self.nAer if self.Zall is not None else 0, [p.tau for p in props],
+                           [p.varpi for p in props], [ly["tau_sum"] for ly in layers], [p.Zpp for p in props],
+                           [p.Zmp for p in props], [p.z_stride for p in props], [self.dtau_dot_all[iz] for iz in range(L)],
+                           [self.varpi_dot[iz] for iz in range(L)], [self.tau_sum_dot[iz] for iz in range(L)],
+                           None if self.zdcoef is None else [self.zdcoef[iz] for iz in range(L)], self.CT if self.Zall else 0,
+                           zall[0], zall[1], self.F0, self.added_s.j0_m, fwd.added_surface.j0_p, self.als.ap_J0_m, self.als.ap_J0_p,
+                           tau_sum_s, tsd_s, row0, w, nV, self.Rd, self.Td)
+
+        self.ss.run(after_moment=lin_moment)     # R, T: the launches of rt_run_ss (bit for bit); one walk over the moments
+        return self.R, self.T, self.Rd, self.Td
+
+    def results_host(self):
+        """(R, T, Rdot, Tdot): [nVZA, nStokes, nSpec] and [nVZA, nStokes, nSpec, Nparams], as rt_run_lin returns them."""
+        tr = lambda t: to_host(t).transpose(2, 1, 0).copy()
+        tr4 = lambda t: to_host(t).transpose(3, 2, 1, 0).copy()
+        return tr(self.R), tr(self.T), tr4(self.Rd), tr4(self.Td)
+
+
+def rt_run_ss_lin(model: H.RTModel, lin_model: H.LinModel, NAer: int, NGas: int, NSurf: int):
+    """The linearized elastic single-scattering run -> (R, T, Rdot, Tdot).  R, T are rt_run_ss(model)'s, bit for bit; Rdot / Tdot
+    [nVZA, nStokes, nSpec, Nparams] are their analytic Jacobians in the parameter slots of rt_run_lin (ParameterLayout: 7 per
+    aerosol, the gases, one surface slot: the Lambertian albedo or the Cox-Munk wind speed).  Same arguments and refusals as
+    rt_run_lin; SolarBeam is the only source, at most three aerosols, no Cox-Munk single-scattering correction.  The surface
+    slot and the surface's share of every slot are those of the reference's linearized surface builders, which weigh the direct
+    beam with F0 where the forward builders use I0 = e1: with F0[0] = 1 (and, over Cox-Munk, F0 = e1) they are the exact
+    derivatives of rt_run_ss, as in rt_run_lin."""
+    scene = SceneSSLin(model, lin_model, NAer, NGas, NSurf)
+    scene.run()
+    synchronize_if_gpu()
+    _lib.check_device_status("rt_run_ss (linearized)")
+    return scene.results_host()

@@ -4,6 +4,9 @@
 //                        (rt_run.jl:715-722) and the viewing rows of postprocessing_vza! (postprocessing_vza.jl:23-94)
 //   vsm_ss_column_rrs_*  rt_kernel_ss!(::RRS) (:240-337): get_elem_rt_SFI_RRS! (elemental_inelastic.jl:479-603),
 //                        get_interaction_ss_RRS! (interaction_ss.jl:79-90), postprocessing_vza!(::RRS) (:139-142)
+//   vsm_ss_column_lin_*  the parameter derivative of vsm_ss_column_*: the source derivatives of get_elem_rt_SFI_fused!
+//                        (elemental_lin.jl:602-712) with ndoubl = 0 and dtau = tau, the two differentiated statements of
+//                        get_interaction_ss!, the linearized surface builders' sources and postprocessing_vza! (lin)
 // Lanes run along the spectral axis; a thread carries the running sources of SS_RB rows of its point in registers through all
 // layers.  Nothing here is N x N: of the phase matrices only the n_stokes SZA columns are read.
 #include <string.h>
@@ -295,20 +298,185 @@ __global__ __launch_bounds__(SS_TB) void k_ss_column_rrs(int N, int ns, int S, i
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// elastic column, linearized
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int SS_PC = 4;   // parameter slots a thread carries; further slots go to further workgroups along grid.z
+
+template <typename T>
+struct ss_layer_lin {
+  const T *tau, *varpi, *tau_sum, *zpp, *zmp;
+  const T *tau_dot, *varpi_dot, *tau_sum_dot;   // [S, p_layer] each (tau_dot: of the layer's full tau)
+  const T* zdcoef;                              // [CT, p_layer, S] or null (Z_dot = 0)
+  long long zs;
+};
+
+// The derivative of k_ss_column<T, true> for the slots [p_lo + SS_PC blockIdx.z, +SS_PC) below p_hi.  Per layer the forward
+// factors of the thread's rows are formed again (they are cheap), the slot loop applies the chain rule of get_elem_rt_SFI_fused!
+// (the statements of k_elemental_sfi_lin, vsm_lin.hip) and the derivative of get_interaction_ss!, taken on J0+ BEFORE its update:
+//   J0+' = (J0+' - J0+ tau' / mu_i) exp(-tau / mu_i) + j0+',    J0-' += (j0-' - j0- tau_sum' / mu_i) exp(-tau_sum / mu_i).
+// Z_dot F0 at a row is sum_c zdcoef[c, p, s] (Zc[c] F0)_row over the CT component blocks of the moment, for the first p_zdot slots
+// (the aerosols'; the gases' coefficients are exact zeros and are not read): no Z_dot array exists.  ZD = false: no layer has one.
+// Slots >= p_layer (the surface's) are exact zeros in the atmospheric layers and are not touched there.
+template <typename T, bool ZD>
+__global__ __launch_bounds__(SS_TB) void k_ss_column_lin(int N, int ns, int S, int L, int m, int i_mu0, int P, int p_layer,
+                                                         int p_zdot, int p_lo, int p_hi, const ss_layer_lin<T>* __restrict__ lay, int CT,
+                                                         const T* __restrict__ Zc_pp, const T* __restrict__ Zc_mp,
+                                                         const T* __restrict__ F0, const T* __restrict__ sj_m,
+                                                         const T* __restrict__ sj_p, const T* __restrict__ sjd_m,
+                                                         const T* __restrict__ sjd_p, const T* __restrict__ ts_surf,
+                                                         const T* __restrict__ tsd_surf, const T* __restrict__ mu, int nV,
+                                                         const int* __restrict__ row0, const T* __restrict__ w, T* Rd, T* Td) {
+  const long long s = (long long)blockIdx.x * SS_TB + threadIdx.x;
+  if (s >= S) return;
+  const int i_start = ns * i_mu0;
+  const int p0 = p_lo + (int)blockIdx.z * SS_PC;
+  const T ms = mu[i_start];
+  const T wct02 = (m == 0) ? T(0.5) : T(0.25);
+  const long long NN = (long long)N * N;
+  T f0[4] = {0, 0, 0, 0};
+  for (int q = 0; q < ns; ++q) f0[q] = F0[q + (long long)ns * s];
+  T Jp[SS_RB], Dp[SS_RB][SS_PC], Dm[SS_RB][SS_PC];
+#pragma unroll
+  for (int j = 0; j < SS_RB; ++j) {
+    Jp[j] = T(0);
+#pragma unroll
+    for (int k = 0; k < SS_PC; ++k) Dp[j][k] = Dm[j][k] = T(0);
+  }
+  for (int iz = 0; iz < L; ++iz) {
+    const ss_layer_lin<T> ly = lay[iz];
+    const T d = ly.tau[s], wv = ly.varpi[s], ts = ly.tau_sum[s];
+    const T att = exp(-ts / ms);
+    const T* zpp = ly.zpp + s * ly.zs;
+    const T* zmp = ly.zmp + s * ly.zs;
+    // the slots of this chunk in the layer: tau', varpi', the beam term -tau_sum' / mu_0 (elemental_lin.jl:602-712)
+    T td[SS_PC], wd[SS_PC], tsd[SS_PC];
+#pragma unroll
+    for (int k = 0; k < SS_PC; ++k) {
+      const int p = p0 + k;
+      const bool in = p < p_hi && p < p_layer;
+      const long long o = s + (long long)S * (in ? p : 0);
+      td[k] = in ? ly.tau_dot[o] : T(0);
+      wd[k] = in ? ly.varpi_dot[o] : T(0);
+      tsd[k] = in ? ly.tau_sum_dot[o] : T(0);
+    }
+#pragma unroll
+    for (int j = 0; j < SS_RB; ++j) {
+      const int e = blockIdx.y * SS_RB + j;   // item e = v + nV k of the viewing table (ss_pick_rows, VIEW form)
+      if (e >= nV * ns) continue;
+      const int i = row0[e % nV] + e / nV;
+      const T mi = mu[i];
+      T zp = 0, zm = 0;
+      for (int q = 0; q < ns; ++q) {
+        const long long zo = i + (long long)N * (i_start + q);
+        zp += zpp[zo] * f0[q];
+        zm += zmp[zo] * f0[q];
+      }
+      // forward sources and their partial derivatives (k_elemental_sfi_lin with dtau = tau, ndoubl = 0)
+      T jp, jp_tau;
+      if (i >= i_start && i < i_start + ns) {
+        jp = wct02 * wv * zp * (d / mi) * exp(-d / mi);
+        jp_tau = jp * (T(1) / d - T(1) / mi);
+      } else {
+        jp = wct02 * wv * zp * (ms / (mi - ms)) * expdiff_neg<T>(d / mi, d / ms);
+        jp_tau = -wct02 * wv * zp * (ms / (mi - ms)) * (exp(-d / mi) / mi - exp(-d / ms) / ms);
+      }
+      T jp_w = (wv == T(0)) ? T(0) : jp / wv;
+      T jp_Z = (zp == T(0)) ? T(0) : jp / zp;
+      const T gm = ms / (mi + ms);
+      const T arg = d * ((T(1) / mi) + (T(1) / ms));
+      T jm = wct02 * wv * zm * gm * (-expm1(-arg));
+      T jm_tau = wct02 * wv * zm * gm * exp(-arg) * ((T(1) / mi) + (T(1) / ms));
+      T jm_w = (wv == T(0)) ? T(0) : jm / wv;
+      T jm_Z = (zm == T(0)) ? T(0) : jm / zm;
+      jp *= att; jp_tau *= att; jp_w *= att; jp_Z *= att;
+      jm *= att; jm_tau *= att; jm_w *= att; jm_Z *= att;
+      const T ed = exp(-d / mi), es = exp(-ts / mi);
+      // (Z_dot F0) at this row for the slots of the chunk that have one (the first p_zdot: the aerosols'; gas slots have none):
+      // the component products (Zc[c] F0)_row do not depend on the slot, so c is the outer loop
+      T zpd[SS_PC], zmd[SS_PC];
+#pragma unroll
+      for (int k = 0; k < SS_PC; ++k) zpd[k] = zmd[k] = T(0);
+      if constexpr (ZD) {
+        if (ly.zdcoef && p0 < p_zdot) {
+          const T* cf = ly.zdcoef + (long long)CT * (long long)p_layer * s;
+          for (int c = 0; c < CT; ++c) {
+            T cp = 0, cm = 0;
+            for (int q = 0; q < ns; ++q) {
+              const long long zo = c * NN + i + (long long)N * (i_start + q);
+              cp += Zc_pp[zo] * f0[q];
+              cm += Zc_mp[zo] * f0[q];
+            }
+#pragma unroll
+            for (int k = 0; k < SS_PC; ++k) {
+              const int p = p0 + k;
+              const T a = (p < p_hi && p < p_zdot) ? cf[c + (long long)CT * p] : T(0);
+              zpd[k] += a * cp;
+              zmd[k] += a * cm;
+            }
+          }
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < SS_PC; ++k) {
+        const int p = p0 + k;
+        if (p >= p_hi || p >= p_layer) continue;
+        const T beam = -tsd[k] / ms;
+        const T ajp = jp_tau * td[k] + jp_w * wd[k] + jp_Z * zpd[k] + jp * beam;
+        const T ajm = jm_tau * td[k] + jm_w * wd[k] + jm_Z * zmd[k] + jm * beam;
+        if (iz == 0) {   // rt_kernel_ss.jl:213-216: the TOA layer is copied
+          Dp[j][k] = ajp;
+          Dm[j][k] = ajm;
+        } else {         // get_interaction_ss! (interaction_ss.jl:17-18), differentiated
+          Dp[j][k] = (Dp[j][k] - Jp[j] * td[k] / mi) * ed + ajp;
+          Dm[j][k] = Dm[j][k] + (ajm - jm * tsd[k] / mi) * es;
+        }
+      }
+      Jp[j] = (iz == 0) ? jp : Jp[j] * ed + jp;
+    }
+  }
+  // the surface layer: the same update with tau = 0 and tau_sum = tau_sum_all[:, Nz + 1]; j0-+' of all P slots from the linearized
+  // surface builder, whose own j0- multiplies tau_sum'; the forward builder's j0+ (the direct beam, ~ exp(-tau_sum / mu_0))
+  // contributes -j0+ tau_sum' / mu_0
+  const T tss = ts_surf[s];
+#pragma unroll
+  for (int j = 0; j < SS_RB; ++j) {
+    const int e = blockIdx.y * SS_RB + j;
+    if (e >= nV * ns) continue;
+    const int i = row0[e % nV] + e / nV;
+    const long long src = s * N + i;
+    const T mi = mu[i];
+    const T es = exp(-tss / mi);
+    const T bp = sj_p ? sj_p[src] : T(0), bm = sj_m[src];
+#pragma unroll
+    for (int k = 0; k < SS_PC; ++k) {
+      const int p = p0 + k;
+      if (p >= p_hi) continue;
+      const T tsd = (p < p_layer) ? tsd_surf[s + (long long)S * p] : T(0);
+      const long long sp = (long long)N * S * p + src;
+      const T dp = Dp[j][k] + (sjd_p[sp] - bp * tsd / ms);
+      const T dm = Dm[j][k] + (sjd_m[sp] - bm * tsd / mi) * es;
+      const long long dst = ((((long long)p * S + s) * ns + e / nV) * nV) + e % nV;
+      Rd[dst] += w[e] * dm;
+      Td[dst] += w[e] * dp;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
 // Device tables of one call in the library's scratch: ss_layer[L] | w[nV n_stokes] | row0[nV].  One stream-ordered copy of a
 // packed host image (pageable memory: staged by the runtime before the call returns), so L and nV are not capped.
-template <typename T>
+template <typename T, typename LAY = ss_layer<T>>
 struct ss_tables {
-  const ss_layer<T>* lay;
+  const LAY* lay;
   const T* w;
   const int* row0;
 };
-template <typename T>
-static int ss_upload(int L, const std::vector<ss_layer<T>>& lay, int ns, int nV, const int* row0_h, const T* w_h, hipStream_t st,
-                     ss_tables<T>* out) {
-  const size_t o_w = sizeof(ss_layer<T>) * (size_t)L;
+template <typename T, typename LAY>
+static int ss_upload(int L, const std::vector<LAY>& lay, int ns, int nV, const int* row0_h, const T* w_h, hipStream_t st,
+                     ss_tables<T, LAY>* out) {
+  const size_t o_w = sizeof(LAY) * (size_t)L;
   const size_t o_r = o_w + sizeof(T) * (size_t)nV * ns;
   const size_t total = o_r + sizeof(int) * (size_t)nV;
   std::vector<unsigned char> img(total);
@@ -319,7 +487,7 @@ static int ss_upload(int L, const std::vector<ss_layer<T>>& lay, int ns, int nV,
   if (!dev) return VSM_ERR_HIP;
   VSM_HIP(hipMemcpyAsync(dev, img.data(), total, hipMemcpyHostToDevice, st));
   VSM_HIP(hipStreamSynchronize(st));   // `img` dies with this frame: the copy (a few hundred bytes, once per moment) must have left it
-  out->lay = reinterpret_cast<const ss_layer<T>*>(dev);
+  out->lay = reinterpret_cast<const LAY*>(dev);
   out->w = reinterpret_cast<const T*>(dev + o_w);
   out->row0 = reinterpret_cast<const int*>(dev + o_r);
   return VSM_OK;
@@ -359,7 +527,7 @@ static int ss_column(const Q* q, int S, int L, int m, const T* const* tau_h, con
   if (S == 0) return VSM_OK;
   hipStream_t st = as_stream(stream);
   ss_tables<T> t;
-  if ((rc = ss_upload<T>(L, lay, q->n_stokes, nV, row0_h, w_h, st, &t))) return rc;
+  if ((rc = ss_upload<T, ss_layer<T>>(L, lay, q->n_stokes, nV, row0_h, w_h, st, &t))) return rc;
   const unsigned gx = (unsigned)((S + SS_TB - 1) / SS_TB);
   const unsigned gv = (unsigned)((nV * q->n_stokes + SS_RB - 1) / SS_RB);
   hipLaunchKernelGGL((k_ss_column<T, true>), dim3(gx, gv), dim3(SS_TB), 0, st, q->N, q->n_stokes, S, L, m, q->i_mu0, t.lay, F0,
@@ -371,6 +539,59 @@ static int ss_column(const Q* q, int S, int L, int m, const T* const* tau_h, con
                        F0, sj_m, sj_p, ts_surf, q->mu, nV, t.row0, t.w, J0_m, J0_p);
     VSM_LAUNCH_CHECK("k_ss_column (all streams)");
   }
+  return VSM_OK;
+}
+
+template <typename T, typename Q>
+static int ss_column_lin(const Q* q, int S, int L, int m, int P, int p_layer, int p_zdot, int p_lo, int p_hi, const T* const* tau_h,
+                         const T* const* varpi_h, const T* const* tau_sum_h, const T* const* Zpp_h, const T* const* Zmp_h,
+                         const long long* zs_h, const T* const* tau_dot_h, const T* const* varpi_dot_h,
+                         const T* const* tau_sum_dot_h, const T* const* zdcoef_h, int CT, const T* Zc_pp, const T* Zc_mp,
+                         const T* F0, const T* sj_m, const T* sj_p, const T* sjd_m, const T* sjd_p, const T* ts_surf,
+                         const T* tsd_surf, int nV, const int* row0_h, const T* w_h, T* Rd, T* Td, void* stream) {
+  int rc;
+  if ((rc = ss_check_common<T>("ss_column_lin", q, S, L, nV, row0_h, w_h))) return rc;
+  VSM_REQUIRE(P >= 1 && p_layer >= 0 && p_layer <= P, "ss_column_lin: P >= 1 and 0 <= p_layer <= P required (P = %d, p_layer = %d)",
+              P, p_layer);
+  VSM_REQUIRE(p_zdot >= 0 && p_zdot <= p_layer, "ss_column_lin: 0 <= p_zdot <= p_layer required (p_zdot = %d)", p_zdot);
+  VSM_REQUIRE(p_lo >= 0 && p_lo < p_hi && p_hi <= P, "ss_column_lin: slot range [%d, %d) outside [0, %d)", p_lo, p_hi, P);
+  VSM_REQUIRE((p_hi - p_lo + SS_PC - 1) / SS_PC <= 65535, "ss_column_lin: too many slots");
+  VSM_REQUIRE(tau_h && varpi_h && tau_sum_h && Zpp_h && Zmp_h && zs_h, "ss_column_lin: null layer table");
+  VSM_REQUIRE(p_layer == 0 || (tau_dot_h && varpi_dot_h && tau_sum_dot_h && tsd_surf), "ss_column_lin: null derivative table");
+  VSM_REQUIRE(F0 && sj_m && sjd_m && sjd_p && ts_surf && Rd && Td, "ss_column_lin: null argument");
+  VSM_REQUIRE(m >= 0 && CT >= 0, "ss_column_lin: m >= 0 and CT >= 0");
+  const long long NN = (long long)q->N * q->N;
+  std::vector<ss_layer_lin<T>> lay((size_t)L);
+  bool any_zd = false;
+  for (int iz = 0; iz < L; ++iz) {
+    VSM_REQUIRE(tau_h[iz] && varpi_h[iz] && tau_sum_h[iz] && Zpp_h[iz] && Zmp_h[iz], "ss_column_lin: null entry in layer table %d",
+                iz);
+    VSM_REQUIRE(p_layer == 0 || (tau_dot_h[iz] && varpi_dot_h[iz] && tau_sum_dot_h[iz]),
+                "ss_column_lin: null entry in derivative table %d", iz);
+    VSM_REQUIRE(zs_h[iz] == 0 || zs_h[iz] == NN, "ss_column_lin: z_stride[%d] must be 0 or N*N", iz);
+    const T* zc = (zdcoef_h && p_zdot > 0) ? zdcoef_h[iz] : nullptr;
+    any_zd = any_zd || zc;
+    VSM_REQUIRE(!zc || (CT >= 1 && Zc_pp && Zc_mp), "ss_column_lin: Z_dot coefficients without component blocks (layer %d)", iz);
+    lay[iz] = ss_layer_lin<T>{tau_h[iz], varpi_h[iz], tau_sum_h[iz], Zpp_h[iz], Zmp_h[iz],
+                              p_layer ? tau_dot_h[iz] : nullptr, p_layer ? varpi_dot_h[iz] : nullptr,
+                              p_layer ? tau_sum_dot_h[iz] : nullptr, zc, zs_h[iz]};
+  }
+  if (S == 0) return VSM_OK;
+  hipStream_t st = as_stream(stream);
+  ss_tables<T, ss_layer_lin<T>> t;
+  if ((rc = ss_upload<T, ss_layer_lin<T>>(L, lay, q->n_stokes, nV, row0_h, w_h, st, &t))) return rc;
+  const unsigned gx = (unsigned)((S + SS_TB - 1) / SS_TB);
+  const unsigned gv = (unsigned)((nV * q->n_stokes + SS_RB - 1) / SS_RB);
+  const unsigned gp = (unsigned)((p_hi - p_lo + SS_PC - 1) / SS_PC);
+  if (any_zd)
+    hipLaunchKernelGGL((k_ss_column_lin<T, true>), dim3(gx, gv, gp), dim3(SS_TB), 0, st, q->N, q->n_stokes, S, L, m, q->i_mu0, P,
+                       p_layer, p_zdot, p_lo, p_hi, t.lay, CT, Zc_pp, Zc_mp, F0, sj_m, sj_p, sjd_m, sjd_p, ts_surf, tsd_surf, q->mu,
+                       nV, t.row0, t.w, Rd, Td);
+  else
+    hipLaunchKernelGGL((k_ss_column_lin<T, false>), dim3(gx, gv, gp), dim3(SS_TB), 0, st, q->N, q->n_stokes, S, L, m, q->i_mu0, P,
+                       p_layer, 0, p_lo, p_hi, t.lay, 0, (const T*)nullptr, (const T*)nullptr, F0, sj_m, sj_p, sjd_m, sjd_p, ts_surf,
+                       tsd_surf, q->mu, nV, t.row0, t.w, Rd, Td);
+  VSM_LAUNCH_CHECK("k_ss_column_lin");
   return VSM_OK;
 }
 
@@ -394,7 +615,7 @@ static int ss_column_rrs(const Q* q, int S, int L, int m, int K, const T* const*
   if (halo > VSM_SS_MAX_HALO) halo = VSM_SS_MAX_HALO;
   hipStream_t st = as_stream(stream);
   ss_tables<T> t;
-  if ((rc = ss_upload<T>(L, lay, q->n_stokes, nV, row0_h, w_h, st, &t))) return rc;
+  if ((rc = ss_upload<T, ss_layer<T>>(L, lay, q->n_stokes, nV, row0_h, w_h, st, &t))) return rc;
   const unsigned gx = (unsigned)((S + SS_TB - 1) / SS_TB);
   const unsigned gv = (unsigned)((nV * q->n_stokes + SS_RB - 1) / SS_RB);
   const size_t lds = sizeof(T) * (size_t)(4 + 2 * SS_RB) * (size_t)(SS_TB + 2 * halo);
@@ -424,6 +645,20 @@ extern "C" {
                               const T* w_h, T* ieR_SFI, T* ieT_SFI, void* stream) {                                            \
     return ss_column_rrs<T>(q, S, L, m, K, tau_h, tau_sum_h, fscatt_h, shift, varpi_ie, Zpp_ie, Zmp_ie, F0, halo, nV, row0_h,  \
                             w_h, ieR_SFI, ieT_SFI, stream);                                                                    \
+  }                                                                                                                            \
+  int vsm_ss_column_lin_##SFX(const vsm_quad_##SFX* q, int S, int L, int m, int P, int p_layer, int p_zdot, int p_lo,          \
+                              int p_hi,                                                                                        \
+                              const T* const* tau_h, const T* const* varpi_h, const T* const* tau_sum_h,                       \
+                              const T* const* Zpp_h, const T* const* Zmp_h, const long long* z_stride_h,                       \
+                              const T* const* tau_dot_h, const T* const* varpi_dot_h, const T* const* tau_sum_dot_h,           \
+                              const T* const* zdcoef_h, int CT, const T* Zc_pp, const T* Zc_mp, const T* F0,                   \
+                              const T* surf_j0_m, const T* surf_j0_p, const T* surf_j0_m_lin, const T* surf_j0_p_lin,          \
+                              const T* tau_sum_surface, const T* tau_sum_dot_surface, int nV, const int* row0_h,               \
+                              const T* w_h, T* Rdot, T* Tdot, void* stream) {                                                  \
+    return ss_column_lin<T>(q, S, L, m, P, p_layer, p_zdot, p_lo, p_hi, tau_h, varpi_h, tau_sum_h, Zpp_h, Zmp_h, z_stride_h,   \
+                            tau_dot_h, varpi_dot_h, tau_sum_dot_h, zdcoef_h, CT, Zc_pp, Zc_mp, F0, surf_j0_m, surf_j0_p,       \
+                            surf_j0_m_lin, surf_j0_p_lin, tau_sum_surface, tau_sum_dot_surface, nV, row0_h, w_h, Rdot, Tdot,   \
+                            stream);                                                                                           \
   }
 VSM_SS_API(double, f64)
 VSM_SS_API(float, f32)
