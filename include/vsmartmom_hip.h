@@ -449,6 +449,15 @@ int vsm_coxmunk_ss_correction_f64(const vsm_coxmunk_f64* surf, int n_stokes, int
 int vsm_coxmunk_ss_correction_f32(const vsm_coxmunk_f32* surf, int n_stokes, int S, int nV, const float* mu_v_h,
                                   const float* dphi_h, float mu0, int m_max, int nphi, const float* phi, const float* wphi,
                                   const float* tau_total, float* coef, float* R_SFI, void* stream);
+/* The two terms of that coefficient on their own, for StandaloneSS path 2 (surfaces.jl:88-106, truncated.jl:116-184):
+ *   exact[v + nV k] = M[k,1](mu_v, mu0, dphi_v),   trunc[v + nV k] = sum_{m < m_count} w_m az_k1(m dphi_v) c_m[k,1](mu_v, mu0)
+ * (device [nV*n_stokes] each, either may be NULL), by the same kernel and the same Mueller function.  Any nV >= 1. */
+int vsm_coxmunk_first_column_f64(const vsm_coxmunk_f64* surf, int n_stokes, int nV, const double* mu_v_h, const double* dphi_h,
+                                 double mu0, int m_count, int nphi, const double* phi, const double* wphi, double* exact,
+                                 double* trunc, void* stream);
+int vsm_coxmunk_first_column_f32(const vsm_coxmunk_f32* surf, int n_stokes, int nV, const float* mu_v_h, const float* dphi_h,
+                                 float mu0, int m_count, int nphi, const float* phi, const float* wphi, float* exact, float* trunc,
+                                 void* stream);
 
 /* ---- per-scene layer optics on the device ---------------------------------------------------
  * The reference builds these on the host once per Fourier moment (rt_run.jl:390-394) and ships per-layer arrays inside
@@ -986,6 +995,49 @@ int vsm_ss_column_rrs_f32(const vsm_quad_f32* q, int S, int L, int m, int K, con
                           const float* const* tau_sum_h, const float* const* fscatt_h, const int* shift, const float* varpi_ie,
                           const float* Zpp_ie, const float* Zmp_ie, const float* F0, int halo, int nV, const int* row0_h,
                           const float* w_h, float* ieR_SFI, float* ieT_SFI, void* stream);
+
+/* ---- exact single scattering: StandaloneSS (src/StandaloneSS/kernels.jl, linearized_f2.jl) ---------------------------------
+ * The first-order field at the true scattering angle of every viewing geometry, in four paths: (1) one scattering in the
+ * atmosphere, (2) the direct beam reflected by the surface, (3) atmosphere -> surface -> sensor, (4) surface -> atmosphere ->
+ * sensor; (3) and (4) for scalar radiance over a Lambertian surface, as the reference restricts them.
+ * Contributors: tau_c_h is a HOST array of C * L device pointers, entry c * L + iz the [S] optical depths of contributor c in
+ * layer iz; varpi_c_h [C] (host) their single-scattering albedos; the phase functions are spectrally flat and arrive as small HOST
+ * tables per contributor.  The kernels mix them per (layer, point):
+ *   tau = sum_c tau_c,   varpi_eff P_eff = (sum_c tau_c varpi_c p_c) / tau   (zero where tau = 0),
+ * so neither P_eff[nV,n_stokes,L,S] nor the azimuthal averages Pbar[nV,L,S,nQ] of the reference exist.  The tables reach the
+ * device through the library's scratch; L, C and nV <= 65535 are not capped otherwise.  I0 [S], albedo [S] and brdf are device
+ * arrays, mu_v_h [nV] host.  Outputs [nV,n_stokes,S] are WRITTEN.  Invalid arguments (L < 1, C < 1, nV < 1, n_stokes outside 1..4,
+ * nQ < 1, null tables or entries, a cosine <= 0) return VSM_ERR_INVALID_ARG before any launch; S = 0 launches nothing.
+ *   path1: p_c_h [C][nV][n_stokes] = the first column of contributor c's phase matrix at geometry v, rotated into the meridian
+ *          plane (Scattering.phase_matrix_first_column); path1 = I0 / (4 pi mu_v a) sum_iz varpi_eff P_eff (e^{-tau_top a} -
+ *          e^{-tau_bot a}), a = 1 / mu0 + 1 / mu_v, the layer factor as e^{-tau_top a} (-expm1(-tau a)).
+ *   path2: brdf [nV,n_stokes] (brdf_spectral = 0) or [nV,n_stokes,S]; path2 = mu0 I0 brdf e^{-tau/mu0} e^{-tau/mu_v}.
+ *   path34: pbar3_c_h / pbar4_c_h [C][nV][nQ] = the azimuthal averages of contributor c's phase function between inner node k and
+ *          mu0 / mu_v; mu_nodes_h / w_h [nQ] the inner quadrature on (0, 1); _inner_scatter_sum and _tau_integral with its
+ *          |1 / mu_first - 1 / mu_second| < 1e-10 trapezoid branch.  path3 or path4 may be NULL (its table is then not read); a
+ *          point of zero albedo writes zeros.
+ *   jac12: d1_tau / d1_varpi / d1_P [nV,n_stokes,S,L] (together, or all NULL) = d path1 / d (tau_layer, varpi_eff, P_eff);
+ *          d2_tau [nV,n_stokes,S,L] and d2_rho [nV,n_stokes,S] (together, or both NULL) = d path2 / d (tau_layer, brdf). */
+int vsm_exact_ss_path1_f64(int S, int L, int C, int nV, int n_stokes, const double* const* tau_c_h, const double* varpi_c_h,
+                               const double* p_c_h, const double* I0, double mu0, const double* mu_v_h, double* path1, void* stream);
+int vsm_exact_ss_path2_f64(int S, int L, int C, int nV, int n_stokes, const double* const* tau_c_h, const double* brdf,
+                               int brdf_spectral, const double* I0, double mu0, const double* mu_v_h, double* path2, void* stream);
+int vsm_exact_ss_path34_f64(int S, int L, int C, int nV, int nQ, const double* const* tau_c_h, const double* varpi_c_h,
+                                const double* pbar3_c_h, const double* pbar4_c_h, const double* mu_nodes_h, const double* w_h, const double* albedo,
+                                const double* I0, double mu0, const double* mu_v_h, double* path3, double* path4, void* stream);
+int vsm_exact_ss_jac12_f64(int S, int L, int C, int nV, int n_stokes, const double* const* tau_c_h, const double* varpi_c_h,
+                               const double* p_c_h, const double* brdf, int brdf_spectral, const double* I0, double mu0, const double* mu_v_h,
+                               double* d1_tau, double* d1_varpi, double* d1_P, double* d2_tau, double* d2_rho, void* stream);
+int vsm_exact_ss_path1_f32(int S, int L, int C, int nV, int n_stokes, const float* const* tau_c_h, const float* varpi_c_h,
+                               const float* p_c_h, const float* I0, float mu0, const float* mu_v_h, float* path1, void* stream);
+int vsm_exact_ss_path2_f32(int S, int L, int C, int nV, int n_stokes, const float* const* tau_c_h, const float* brdf,
+                               int brdf_spectral, const float* I0, float mu0, const float* mu_v_h, float* path2, void* stream);
+int vsm_exact_ss_path34_f32(int S, int L, int C, int nV, int nQ, const float* const* tau_c_h, const float* varpi_c_h,
+                                const float* pbar3_c_h, const float* pbar4_c_h, const float* mu_nodes_h, const float* w_h, const float* albedo,
+                                const float* I0, float mu0, const float* mu_v_h, float* path3, float* path4, void* stream);
+int vsm_exact_ss_jac12_f32(int S, int L, int C, int nV, int n_stokes, const float* const* tau_c_h, const float* varpi_c_h,
+                               const float* p_c_h, const float* brdf, int brdf_spectral, const float* I0, float mu0, const float* mu_v_h,
+                               float* d1_tau, float* d1_varpi, float* d1_P, float* d2_tau, float* d2_rho, void* stream);
 
 /* ---- diagnostics used by the parity tests -------------------------------- */
 /* Runs the LDS-resident MFMA tile product used inside the fused kernels on plain

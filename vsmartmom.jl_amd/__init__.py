@@ -18,6 +18,8 @@ Sub-modules
     CoreRTRaman     rotational-Raman pass: rt_run(RS_type::RRS, model, iBand),
                     rt_run_multisensor(RS_type, model, sensor_levels) (core_rt_ms_raman),
                     rt_run_ss(RS_type, model, iBand) (core_rt_ss: the single-scatter inelastic correction)
+    StandaloneSS    exact single scattering at the true scattering angle (standalone_ss: run_exact_ss, the four paths,
+                    apply_back_correction = exact - truncated first-order field, Jacobians of paths 1 and 2)
     parallel        spectral-axis sharding over the GPUs of one node (torch.distributed / RCCL)
 """
 from . import _lib, host_model  # noqa: F401
@@ -30,6 +32,7 @@ from . import core_rt_raman as CoreRTRaman  # noqa: F401
 from . import core_rt_ms_raman  # noqa: F401
 from . import core_rt_ms_lin  # noqa: F401
 from . import core_rt_ss  # noqa: F401
+from . import standalone_ss as StandaloneSS  # noqa: F401
 from . import raman_inputs  # noqa: F401
 from . import io_yaml  # noqa: F401
 from ._lib import VSMError, LIB_PATH  # noqa: F401

@@ -122,6 +122,7 @@ _SIGS = {
     "vsm_interaction_hdrf_{T}": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P]),
     "vsm_postprocess_vza_hdrf_{T}": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "vsm_coxmunk_ss_correction_{T}": (_I, [_P, _I, _I, _I, _P, _P, "{R}", _I, _I, _P, _P, _P, _P, _P, _P]),
+    "vsm_coxmunk_first_column_{T}": (_I, [_P, _I, _I, _P, _P, "{R}", _I, _I, _P, _P, _P, _P, _P]),
     "vsm_doubling_lin_work_elems": (_SZ, [_I, _I, _I]),
     "vsm_interaction_lin_work_elems": (_SZ, [_I, _I, _I]),
     "vsm_elemental_lin_{T}": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _LL, _I, _P, _P, _P, _P, _P, _LL, _LL, _P, _P, _P]),
@@ -144,6 +145,10 @@ _SIGS = {
     "vsm_ss_column_lin_{T}": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P,
                                    _P, _P, _I, _P, _P, _P, _P, _P]),
     "vsm_ss_column_rrs_{T}": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
+    "vsm_exact_ss_path1_{T}": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, "{R}", _P, _P, _P]),
+    "vsm_exact_ss_path2_{T}": (_I, [_I, _I, _I, _I, _I, _P, _P, _I, _P, "{R}", _P, _P, _P]),
+    "vsm_exact_ss_path34_{T}": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, "{R}", _P, _P, _P, _P]),
+    "vsm_exact_ss_jac12_{T}": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, "{R}", _P, _P, _P, _P, _P, _P, _P]),
     "vsm_run_supported": (_I, [_I, _I, _I]),
     "vsm_run_workspace_bytes": (_SZ, [_I, _I, _I, _I, _P]),
     "vsm_run_supported_f32": (_I, [_I, _I, _I]),

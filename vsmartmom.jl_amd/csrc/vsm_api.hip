@@ -997,6 +997,14 @@ VSM_LIN_API(float, f32)
                 "coxmunk_ss_correction: bad argument");                                                                \
     return coxmunk_ss_correction<T>(cvt_cm(surf), n_stokes, S, nV, mu_v_h, dphi_h, mu0, m_max, nphi, phi, wphi,        \
                                     tau_total, coef, R_SFI, as_stream(stream));                                        \
+  }                                                                                                                    \
+  extern "C" int vsm_coxmunk_first_column_##SFX(const vsm_coxmunk_##SFX* surf, int n_stokes, int nV, const T* mu_v_h,  \
+                                                const T* dphi_h, T mu0, int m_count, int nphi, const T* phi,           \
+                                                const T* wphi, T* exact, T* trunc, void* stream) {                     \
+    VSM_REQUIRE(surf && mu_v_h && dphi_h && phi && wphi && nV >= 1 && (exact || trunc),                                \
+                "coxmunk_first_column: bad argument");                                                                 \
+    return coxmunk_first_column<T>(cvt_cm(surf), n_stokes, nV, mu_v_h, dphi_h, mu0, m_count, nphi, phi, wphi, exact,   \
+                                   trunc, as_stream(stream));                                                          \
   }
 VSM_SURF_API(double, f64)
 VSM_SURF_API(float, f32)

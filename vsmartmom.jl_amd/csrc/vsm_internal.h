@@ -122,6 +122,9 @@ int postprocess_vza_hdrf(int N, int ns, int S, int nV, const int* row0_h, const 
 template <typename T>
 int coxmunk_ss_correction(const cm_surf<T>& sf, int n_stokes, int S, int nV, const T* mu_v_h, const T* dphi_h, T mu0, int m_max,
                           int nphi, const T* phi, const T* wphi, const T* tau_total, T* coef, T* R_SFI, hipStream_t st);
+template <typename T>
+int coxmunk_first_column(const cm_surf<T>& sf, int n_stokes, int nV, const T* mu_v_h, const T* dphi_h, T mu0, int m_count, int nphi,
+                         const T* phi, const T* wphi, T* exact, T* trunc, hipStream_t st);
 
 // ---- per-scene layer optics on the device: vsm_optics.hip ----
 template <typename T>

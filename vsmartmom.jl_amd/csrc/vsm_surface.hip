@@ -444,10 +444,12 @@ struct ss_geom {
 };
 // coef[v + nV k] = M_exact[k,1](mu_v, mu0, dphi_v) - sum_m w_m az_k1(m dphi_v) c_m[k],
 // c_m[k] = ff_m/pi sum_phi w M[k,1](mu_v, mu0, phi) az_k1(m phi): one workgroup per viewing geometry; the azimuth sums run
-// in the reference's order (one thread per (m, k) walks the nodes).
+// in the reference's order (one thread per (m, k) walks the nodes).  exact / trunc (nullable, [nVtot, NS] at geometry v0 + v): the
+// two terms on their own -- the first Mueller column at the exact geometry and its Fourier reconstruction (StandaloneSS path 2).
 template <typename T, int NS>
 __global__ void __launch_bounds__(128) k_cm_ss_coef(cm_surf<T> sf, int nV, ss_geom g, T mu0, int m_max, int nphi,
-                                                    const T* __restrict__ phi, const T* __restrict__ wphi, T* coef) {
+                                                    const T* __restrict__ phi, const T* __restrict__ wphi, T* coef, T* exact = nullptr,
+                                                    T* trunc = nullptr, int nVtot = 0, int v0 = 0) {
   __shared__ T col[NS][128];
   __shared__ T terms[1024];
   const int v = blockIdx.x, f = threadIdx.x;
@@ -474,7 +476,9 @@ __global__ void __launch_bounds__(128) k_cm_ss_coef(cm_surf<T> sf, int nV, ss_ge
     for (int k = 0; k < NS; ++k) {
       T mf = T(0);
       for (int mm = 0; mm <= m_max; ++mm) mf += terms[mm * NS + k];
-      coef[v + nV * k] = M[k][0] - mf;
+      if (coef) coef[v + nV * k] = M[k][0] - mf;
+      if (exact) exact[v0 + v + nVtot * k] = M[k][0];
+      if (trunc) trunc[v0 + v + nVtot * k] = mf;
     }
   }
 }
@@ -501,11 +505,12 @@ int coxmunk_ss_correction(const cm_surf<T>& sf, int n_stokes, int S, int nV, con
     g.dphi[v] = (double)dphi_h[v];
   }
   const dim3 gr(nV), b(128);
+  T* const none = nullptr;
   switch (n_stokes) {
-    case 1: hipLaunchKernelGGL((k_cm_ss_coef<T, 1>), gr, b, 0, st, sf, nV, g, mu0, m_max, nphi, phi, wphi, coef); break;
-    case 2: hipLaunchKernelGGL((k_cm_ss_coef<T, 2>), gr, b, 0, st, sf, nV, g, mu0, m_max, nphi, phi, wphi, coef); break;
-    case 3: hipLaunchKernelGGL((k_cm_ss_coef<T, 3>), gr, b, 0, st, sf, nV, g, mu0, m_max, nphi, phi, wphi, coef); break;
-    case 4: hipLaunchKernelGGL((k_cm_ss_coef<T, 4>), gr, b, 0, st, sf, nV, g, mu0, m_max, nphi, phi, wphi, coef); break;
+    case 1: hipLaunchKernelGGL((k_cm_ss_coef<T, 1>), gr, b, 0, st, sf, nV, g, mu0, m_max, nphi, phi, wphi, coef, none, none, 0, 0); break;
+    case 2: hipLaunchKernelGGL((k_cm_ss_coef<T, 2>), gr, b, 0, st, sf, nV, g, mu0, m_max, nphi, phi, wphi, coef, none, none, 0, 0); break;
+    case 3: hipLaunchKernelGGL((k_cm_ss_coef<T, 3>), gr, b, 0, st, sf, nV, g, mu0, m_max, nphi, phi, wphi, coef, none, none, 0, 0); break;
+    case 4: hipLaunchKernelGGL((k_cm_ss_coef<T, 4>), gr, b, 0, st, sf, nV, g, mu0, m_max, nphi, phi, wphi, coef, none, none, 0, 0); break;
     default: set_error("coxmunk_ss_correction: n_stokes must be 1..4"); return VSM_ERR_INVALID_ARG;
   }
   VSM_LAUNCH_CHECK("k_cm_ss_coef");
@@ -514,6 +519,36 @@ int coxmunk_ss_correction(const cm_surf<T>& sf, int n_stokes, int S, int nV, con
     hipLaunchKernelGGL(k_ss_apply<T>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, nV, n_stokes, S, mu0, tau_total,
                        coef, R_SFI);
     VSM_LAUNCH_CHECK("k_ss_apply");
+  }
+  return VSM_OK;
+}
+
+// The first Mueller column at the exact geometries [nV, n_stokes] and its reconstruction from the Fourier moments m = 0 .. m_count - 1
+// (StandaloneSS surfaces.jl:88-106, truncated.jl:116-184): the two terms of k_cm_ss_coef, 64 geometries per launch, any nV.
+template <typename T>
+int coxmunk_first_column(const cm_surf<T>& sf, int n_stokes, int nV, const T* mu_v_h, const T* dphi_h, T mu0, int m_count, int nphi,
+                         const T* phi, const T* wphi, T* exact, T* trunc, hipStream_t st) {
+  if (nphi > 128 || nphi < 1 || m_count * n_stokes > 1024 || m_count < 1) {
+    set_error("coxmunk_first_column: nphi <= 128 and 1 <= m_count, m_count n_stokes <= 1024 (got %d, %d)", nphi, m_count);
+    return VSM_ERR_UNSUPPORTED;
+  }
+  for (int v0 = 0; v0 < nV; v0 += 64) {
+    const int nc = nV - v0 < 64 ? nV - v0 : 64;
+    ss_geom g;
+    for (int v = 0; v < nc; ++v) {
+      g.mu_v[v] = (double)mu_v_h[v0 + v];
+      g.dphi[v] = (double)dphi_h[v0 + v];
+    }
+    const dim3 gr(nc), b(128);
+    T* const none = nullptr;
+    switch (n_stokes) {
+      case 1: hipLaunchKernelGGL((k_cm_ss_coef<T, 1>), gr, b, 0, st, sf, nc, g, mu0, m_count - 1, nphi, phi, wphi, none, exact, trunc, nV, v0); break;
+      case 2: hipLaunchKernelGGL((k_cm_ss_coef<T, 2>), gr, b, 0, st, sf, nc, g, mu0, m_count - 1, nphi, phi, wphi, none, exact, trunc, nV, v0); break;
+      case 3: hipLaunchKernelGGL((k_cm_ss_coef<T, 3>), gr, b, 0, st, sf, nc, g, mu0, m_count - 1, nphi, phi, wphi, none, exact, trunc, nV, v0); break;
+      case 4: hipLaunchKernelGGL((k_cm_ss_coef<T, 4>), gr, b, 0, st, sf, nc, g, mu0, m_count - 1, nphi, phi, wphi, none, exact, trunc, nV, v0); break;
+      default: set_error("coxmunk_first_column: n_stokes must be 1..4"); return VSM_ERR_INVALID_ARG;
+    }
+    VSM_LAUNCH_CHECK("k_cm_ss_coef (first column)");
   }
   return VSM_OK;
 }
@@ -606,7 +641,9 @@ int postprocess_vza_hdrf(int N, int ns, int S, int nV, const int* row0_h, const 
   template int interaction_hdrf<T>(const quad<T>&, int, int, const composite<T>&, const added<T>&, T*, T*, T*, hipStream_t);  \
   template int postprocess_vza_hdrf<T>(int, int, int, int, const int*, const T*, const T*, T*, hipStream_t);                  \
   template int coxmunk_ss_correction<T>(const cm_surf<T>&, int, int, int, const T*, const T*, T, int, int, const T*, const T*, \
-                                        const T*, T*, T*, hipStream_t);
+                                        const T*, T*, T*, hipStream_t);                                                      \
+  template int coxmunk_first_column<T>(const cm_surf<T>&, int, int, const T*, const T*, T, int, int, const T*, const T*, T*,  \
+                                       T*, hipStream_t);
 VSM_INST_SURF(double)
 VSM_INST_SURF(float)
 
