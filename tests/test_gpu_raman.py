@@ -144,7 +144,8 @@ def test_elemental_inelastic(vsm, arch, FT, pol, m, ndmode):
 
 
 @pytest.mark.parametrize("FT", [np.float64, np.float32])
-# FP64 N = 4, 7, 11, 16, 19, 21, 24, 27, 30: one wave per line (vsm_raman_wave.hip, k-step counts 1..8; pipelined body up to 24);
+# FP64 N = 4, 7, 11, 16, 19, 21: four lines per wave (vsm_raman_quad.hip; the doubling of 21 in vsm_raman_chain.hip);
+# FP64 N = 24, 27, 30: one wave per line (vsm_raman_wave.hip; pipelined body at 24, unpipelined at 27, 30);
 # FP32 N <= 30: one workgroup per point; 63: operator chain
 @pytest.mark.parametrize("pol,l_trunc", [("I", 1), ("I", 7), ("I", 15), ("I", 25), ("I", 31), ("IQU", 7), ("IQU", 9),
                                          ("IQU", 11), ("IQU", 13), ("IQU", 35), ("IQU", 55)])   # 55: N = 93 (FP32: NP = 96 elastic kernels)
@@ -248,6 +249,17 @@ def test_raman_quad_kernels_every_size(vsm, arch, l_trunc, N):
     15, 16, 18, 19, 21.  The remaining sizes -- every N mod 4, the rider columns inside / outside the last block of real columns, odd and
     even N^2 (the late slot of the LDS-DMA images) -- through five doubling steps incl. the last one (apply_D on the way out) and
     the _11 interaction, partial last quads (K = 7 lines) included."""
+    c = _setup(vsm, arch, np.float64, "I", S=9, l_trunc=l_trunc, seed=3)
+    assert c["N"] == N
+    test_doubling_inelastic(vsm, arch, np.float64, "I", l_trunc)
+    test_interaction_inelastic(vsm, arch, np.float64, "I", l_trunc, False, "11")
+
+
+@pytest.mark.parametrize("l_trunc,N", [(39, 23), (43, 25)])
+def test_raman_wave_kernels_seams(vsm, arch, l_trunc, N):
+    """vsm_raman_wave.hip (one wave per Raman line) owns FP64 N = 1, 2 and 23 .. 30; the lists above hit N = 24, 27, 30.  The two
+    seams of the family -- N = 23, the first size past vsm_raman_quad.hip, and N = 25, the first on the unpipelined doubling
+    body -- through five doubling steps incl. the last one (apply_D on the way out) and the _11 interaction."""
     c = _setup(vsm, arch, np.float64, "I", S=9, l_trunc=l_trunc, seed=3)
     assert c["N"] == N
     test_doubling_inelastic(vsm, arch, np.float64, "I", l_trunc)

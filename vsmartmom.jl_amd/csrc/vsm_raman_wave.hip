@@ -1056,14 +1056,19 @@ int launch_rw(int S, int K, const int* shift, const double* r, const double* t, 
               const double* gr, const double* grt, const double* jp, const double* j1m, const double* tmp1,
               const double* tmp2, const double* expk, double* ier, double* iet, double* ieJp, double* ieJm, int ns,
               double* ier_pm, double* iet_mm, hipStream_t st) {
-  static const bool plain = ab_switch("VSM_RAMAN_WAVE_PLAIN");   // the unpipelined body (A/B)
   using kern_t = void (*)(int, int, const int*, const double*, const double*, const double*, const double*, const double*,
                           const double*, const double*, const double*, const double*, const double*, const double*, double*,
                           double*, double*, double*, int, double*, double*);
   const bool last = ns > 0;
-  kern_t kern = last ? (kern_t)k_raman_doubling_wave<N, true> : (kern_t)k_raman_doubling_wave<N, false>;
-  if constexpr (N <= RW_MAXN_SP) {
-    if (!plain) kern = last ? (kern_t)k_raman_doubling_wave_sp<N, true> : (kern_t)k_raman_doubling_wave_sp<N, false>;
+  kern_t kern;
+  if constexpr (N > RW_MAXN_SP) {
+    kern = last ? (kern_t)k_raman_doubling_wave<N, true> : (kern_t)k_raman_doubling_wave<N, false>;
+  } else {
+    kern = last ? (kern_t)k_raman_doubling_wave_sp<N, true> : (kern_t)k_raman_doubling_wave_sp<N, false>;
+#ifdef VSM_AB_SWITCHES
+    static const bool plain = ab_switch("VSM_RAMAN_WAVE_PLAIN");   // the unpipelined body (A/B)
+    if (plain) kern = last ? (kern_t)k_raman_doubling_wave<N, true> : (kern_t)k_raman_doubling_wave<N, false>;
+#endif
   }
   if (const int prepared = ensure_dyn_lds(reinterpret_cast<const void*>(kern), RW_LDS_BYTES, "hipFuncSetAttribute(k_raman_doubling_wave)"))
     return prepared;   // once per (device, kernel)
@@ -1082,101 +1087,52 @@ int launch_rw_ia(int S, int K, const int* shift, const rs_ia_pass<double>& h, hi
   return VSM_OK;
 }
 
-// N -> instantiation.  The file is built in RW_PARTS objects (parallel build: each covers a range of N; -DRW_PART=k) or,
-// without RW_PART, as one object with every N (tools/variantsrw.sh).
-#ifdef RW_PART
-#if RW_PART == 0
-#define RW_N_LO 1
-#define RW_N_HI 15
-#elif RW_PART == 1
-#define RW_N_LO 16
-#define RW_N_HI 21
+// N -> instantiation.  The library holds the sizes a run can bring here: N = 1, 2 and 23..30.  Both callers try
+// vsm_raman_quad.hip first, which takes every FP64 call with 3 <= N <= 22 under the same K bound.  A diagnostic build
+// with -DVSM_AB_SWITCHES -DRW_ALL_N (tools/variantsrw.sh) holds every N, for VSM_NO_RAMAN_QUAD A/B runs.
+constexpr bool rw_has_n(int n) {
+#if defined(VSM_AB_SWITCHES) && defined(RW_ALL_N)
+  return n >= 1 && n <= RW_MAXN;
 #else
-#define RW_N_LO 22
-#define RW_N_HI 30
+  return n == 1 || n == 2 || (n >= 23 && n <= RW_MAXN);
 #endif
-#else
-#define RW_N_LO 1
-#define RW_N_HI 30
-#endif
-static_assert(RW_N_HI <= RW_MAXN, "range");
-template <int N, typename F>
+}
+template <int N = 1, typename F>
 int dispatch_n(int n, F f) {
-  if constexpr (N > RW_N_HI) {
+  if constexpr (N > RW_MAXN) {
     return VSM_ERR_UNSUPPORTED;
   } else {
-    if (n == N) return f(std::integral_constant<int, N>{});
+    if constexpr (rw_has_n(N)) {
+      if (n == N) return f(std::integral_constant<int, N>{});
+    }
     return dispatch_n<N + 1>(n, f);
   }
 }
 
 }  // namespace
 
-#define RW_DBL_ARGS                                                                                                        \
-  int N, int S, int K, const int *shift, const double *r, const double *t, const double *ttg, const double *gt,            \
-      const double *gr, const double *grt, const double *jp, const double *j1m, const double *tmp1, const double *tmp2,    \
-      const double *expk, double *ier, double *iet, double *ieJp, double *ieJm, int ns, double *ier_pm, double *iet_mm,    \
-      hipStream_t st
-#define RW_DBL_PASS N, S, K, shift, r, t, ttg, gt, gr, grt, jp, j1m, tmp1, tmp2, expk, ier, iet, ieJp, ieJm, ns, ier_pm, iet_mm, st
-#define RW_CAT_(a, b) a##b
-#define RW_CAT(a, b) RW_CAT_(a, b)
-#ifdef RW_PART
-#define RW_PART_FN(name) RW_CAT(name, RW_PART)
-#else
-#define RW_PART_FN(name) RW_CAT(name, all)
-#endif
-int raman_doubling_wave_part_0(RW_DBL_ARGS);
-int raman_doubling_wave_part_1(RW_DBL_ARGS);
-int raman_doubling_wave_part_2(RW_DBL_ARGS);
-int raman_interaction_wave_part_0(int N, int S, int K, const int* shift, const rs_ia_pass<double>& h, hipStream_t st);
-int raman_interaction_wave_part_1(int N, int S, int K, const int* shift, const rs_ia_pass<double>& h, hipStream_t st);
-int raman_interaction_wave_part_2(int N, int S, int K, const int* shift, const rs_ia_pass<double>& h, hipStream_t st);
-
-int RW_PART_FN(raman_doubling_wave_part_)(RW_DBL_ARGS) {
-  if (N < RW_N_LO || N > RW_N_HI) return VSM_ERR_UNSUPPORTED;
-  return dispatch_n<RW_N_LO>(N, [&](auto tag) {
+// FP64, N = 1, 2, 23..30, K <= 128; VSM_ERR_UNSUPPORTED otherwise (the caller falls back to k_raman_doubling_lines / the
+// operator chain).  K > 128: the line list is a 128-bit mask.  N 25..30 run the unpipelined body.  ns > 0 (n_stokes) marks
+// the LAST doubling step of a layer: apply_D! of the inelastic operators happens on the way out (ier_pm, iet_mm are written).
+int raman_doubling_wave(int N, int S, int K, const int* shift, const double* r, const double* t, const double* ttg,
+                        const double* gt, const double* gr, const double* grt, const double* jp, const double* j1m,
+                        const double* tmp1, const double* tmp2, const double* expk, double* ier, double* iet, double* ieJp,
+                        double* ieJm, int ns, double* ier_pm, double* iet_mm, hipStream_t st) {
+  static const bool off = ab_switch("VSM_NO_RAMAN_WAVE");
+  if (off || !rw_has_n(N) || K > 128) return VSM_ERR_UNSUPPORTED;
+  if (S <= 0 || K <= 0) return VSM_OK;
+  return dispatch_n(N, [&](auto tag) {
     return launch_rw<decltype(tag)::value>(S, K, shift, r, t, ttg, gt, gr, grt, jp, j1m, tmp1, tmp2, expk, ier, iet, ieJp, ieJm,
                                            ns, ier_pm, iet_mm, st);
   });
 }
-int RW_PART_FN(raman_interaction_wave_part_)(int N, int S, int K, const int* shift, const rs_ia_pass<double>& h,
-                                             hipStream_t st) {
-  if (N < RW_N_LO || N > RW_N_HI) return VSM_ERR_UNSUPPORTED;
-  return dispatch_n<RW_N_LO>(N, [&](auto tag) { return launch_rw_ia<decltype(tag)::value>(S, K, shift, h, st); });
-}
-
-#if !defined(RW_PART) || RW_PART == 0
-// FP64, N <= 30, K <= 128; VSM_ERR_UNSUPPORTED otherwise (the caller falls back to k_raman_doubling_lines / the operator
-// chain).  K > 128: the line list is a 128-bit mask.  N 25..30 run the unpipelined body.  ns > 0 (n_stokes) marks the
-// LAST doubling step of a layer: apply_D! of the inelastic operators happens on the way out (ier_pm, iet_mm are written).
-int raman_doubling_wave(RW_DBL_ARGS) {
-  static const bool off = ab_switch("VSM_NO_RAMAN_WAVE");
-  if (off || N > RW_MAXN || N < 1 || K > 128) return VSM_ERR_UNSUPPORTED;
-  if (S <= 0 || K <= 0) return VSM_OK;
-#ifdef RW_PART
-  int rc = raman_doubling_wave_part_0(RW_DBL_PASS);
-  if (rc == VSM_ERR_UNSUPPORTED) rc = raman_doubling_wave_part_1(RW_DBL_PASS);
-  if (rc == VSM_ERR_UNSUPPORTED) rc = raman_doubling_wave_part_2(RW_DBL_PASS);
-  return rc;
-#else
-  return raman_doubling_wave_part_all(RW_DBL_PASS);
-#endif
-}
 
 int raman_interaction_wave(int N, int S, int K, const int* shift, const rs_ia_pass<double>& h, hipStream_t st) {
   static const bool off = ab_switch("VSM_NO_RAMAN_WAVE") || ab_switch("VSM_NO_RAMAN_IA_WAVE");
-  if (off || N > RW_MAXN || N < 1 || K > 128) return VSM_ERR_UNSUPPORTED;
+  if (off || !rw_has_n(N) || K > 128) return VSM_ERR_UNSUPPORTED;
   if (S <= 0 || K <= 0) return VSM_OK;
-#ifdef RW_PART
-  int rc = raman_interaction_wave_part_0(N, S, K, shift, h, st);
-  if (rc == VSM_ERR_UNSUPPORTED) rc = raman_interaction_wave_part_1(N, S, K, shift, h, st);
-  if (rc == VSM_ERR_UNSUPPORTED) rc = raman_interaction_wave_part_2(N, S, K, shift, h, st);
-  return rc;
-#else
-  return raman_interaction_wave_part_all(N, S, K, shift, h, st);
-#endif
+  return dispatch_n(N, [&](auto tag) { return launch_rw_ia<decltype(tag)::value>(S, K, shift, h, st); });
 }
-#endif
 
 #ifdef RW_PHASE_TIMING
 extern "C" int vsm_debug_rw_phase(unsigned long long* out_h, int reset) {
