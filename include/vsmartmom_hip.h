@@ -425,6 +425,28 @@ int vsm_brdf_surface_lin_f64(const vsm_quad_f64* q, int S, int m, const double* 
 int vsm_brdf_surface_lin_f32(const vsm_quad_f32* q, int S, int m, const float* rho, const float* drho, int iparam,
                              const float* tau_sum, const float* tau_sum_dot, int p_layer, const float* F0,
                              const vsm_added_f32* added, const vsm_added_lin_f32* added_lin, void* stream);
+/* Kernel-driven land BRDFs with analytic parameter derivatives (the reference linearizes neither surface).
+ * kind = VSM_LAND_BRDF_RPV: rpvSurfaceScalar (types.jl:482-491), params (host) = {rho0, rho_c, k, Theta}, K = 4;
+ * kind = VSM_LAND_BRDF_ROSSLI: RossLiSurfaceScalar (types.jl:505-512), params (host) = {fvol, fgeo, fiso}, K = 3.
+ * For every Fourier moment m = 0 .. m_max, in one launch: rho[m][N,N] = reflectance(brdf, pol, qp_mu, m) (rpv_surface.jl:160-190:
+ * ff/pi sum_phi w rho(mu_i, mu_j, phi) cos(m phi) on the I -> I elements, ff = 1 (m = 0) | 2; the m = 0 block is NOT doubled) and
+ * drho[m][k][N,N], its derivative with respect to parameter k (field order), both column-major blocks like
+ * vsm_coxmunk_reflectance_*'s.  phi / wphi (device, nphi nodes): the azimuth quadrature on [0, pi]. */
+#define VSM_LAND_BRDF_RPV 0
+#define VSM_LAND_BRDF_ROSSLI 1
+int vsm_land_brdf_reflectance_lin_f64(const vsm_quad_f64* q, int kind, const double* params, int m_max, int nphi, const double* phi,
+                                      const double* wphi, double* rho, double* drho, void* stream);
+int vsm_land_brdf_reflectance_lin_f32(const vsm_quad_f32* q, int kind, const float* params, int m_max, int nphi, const float* phi,
+                                      const float* wphi, float* rho, float* drho, void* stream);
+/* vsm_brdf_surface_lin_* for a surface with K parameters: drho[K][N,N], slot isurf + k takes ap_r-+ = (f drho_k) diag(mu w) and
+ * ap_J0- = mu0 sum_s (f drho_k)[:, i0 + s] F0_s exp(-tau_sum/mu0); all other blocks of the surface slots are zero; the layer slots
+ * [0, p_layer), p_layer <= isurf, carry -j0- tau_sum_dot / mu0; j0+ = 0, t-- = 0 as in the one-slot builder. */
+int vsm_brdf_surface_lin_multi_f64(const vsm_quad_f64* q, int S, int m, const double* rho, const double* drho, int K, int isurf,
+                                   const double* tau_sum, const double* tau_sum_dot, int p_layer, const double* F0,
+                                   const vsm_added_f64* added, const vsm_added_lin_f64* added_lin, void* stream);
+int vsm_brdf_surface_lin_multi_f32(const vsm_quad_f32* q, int S, int m, const float* rho, const float* drho, int K, int isurf,
+                                   const float* tau_sum, const float* tau_sum_dot, int p_layer, const float* F0,
+                                   const vsm_added_f32* added, const vsm_added_lin_f32* added_lin, void* stream);
 /* interaction_hdrf! (src/CoreRT/CoreKernel/interaction_hdrf.jl:4-42), called after the surface interaction of each Fourier
  * moment (rt_run.jl:467-476): hdr_J[N,S] = r-+_surf J0+ + j0-_surf; for m == 0 also the hemispheric fluxes bhr_uw / bhr_dw
  * [n_stokes, S] (for m > 0 they are not touched).  The surface layer may be shared (mat_stride 0) or per point. */

@@ -117,6 +117,42 @@ def elemental_lin_(pol, tau_sum, tau_sum_dot, dtau, dtau_dot, F0, props: CR.Devi
               zd_strides[0], zd_strides[1], C.byref(a), C.byref(al), CR._stream_ptr())
 
 
+# The kernel-driven land BRDFs and their Jacobian slots, in the order of the dataclass fields (the reference linearizes neither):
+# surface type -> (kind of vsm_land_brdf_reflectance_lin_*, number of parameters = the NSurf the linearized drivers take)
+LAND_BRDF = {H.rpvSurfaceScalar: (0, 4), H.RossLiSurfaceScalar: (1, 3)}
+
+
+def surface_param_names(surface):
+    """The surface's Jacobian slots in order: the fields of its dataclass."""
+    return [f.name for f in dataclasses.fields(surface)]
+
+
+def land_brdf_reflectance_lin(surface, dq: CR.DeviceQuad, m_max: int, arch, FT):
+    """vsm_land_brdf_reflectance_lin_*: the Fourier blocks of a kernel-driven land BRDF and their parameter derivatives for the
+    moments 0 .. m_max in one launch -> layout tensors rho (m_max + 1, N, N), drho (m_max + 1, K, N, N) [column-major blocks];
+    the integral host_model.brdf_reflectance evaluates, on the azimuth nodes of brdf_azimuth_quadrature."""
+    kind, K = LAND_BRDF[type(surface)]
+    N = int(dq.mu.numel())
+    rho = torch.empty((m_max + 1, N, N), dtype=dq.dtype, device=dq.mu.device)
+    drho = torch.empty((m_max + 1, K, N, N), dtype=dq.dtype, device=dq.mu.device)
+    phi, w = CR.brdf_azimuth_quadrature(arch, FT)
+    ctype = C.c_double if dq.dtype == torch.float64 else C.c_float
+    params = (ctype * K)(*[float(getattr(surface, n)) for n in surface_param_names(surface)])
+    q = dq.cstruct()
+    _lib.call("vsm_land_brdf_reflectance_lin", dq.dtype, C.byref(q), kind, params, int(m_max), int(phi.numel()), CR._ptr(phi),
+              CR._ptr(w), CR._ptr(rho), CR._ptr(drho), CR._stream_ptr())
+    return rho, drho
+
+
+def brdf_surface_lin_multi_(dq: CR.DeviceQuad, S: int, m: int, rho, drho, isurf: int, tau_sum, tau_sum_dot, p_layer: int, F0,
+                            added_s: CR.AddedLayer, als: AddedLayerLin):
+    """vsm_brdf_surface_lin_multi_*: the linearized BRDF surface layer with the K = drho.shape[0] surface slots isurf .. isurf + K - 1
+    into the shared surface layers `added_s` / `als`."""
+    q_, a_, al_ = dq.cstruct(), added_s.cstruct(), als.cstruct()
+    _lib.call("vsm_brdf_surface_lin_multi", added_s.dtype, C.byref(q_), S, m, CR._ptr(rho), CR._ptr(drho), int(drho.shape[0]),
+              int(isurf), CR._ptr(tau_sum), CR._ptr(tau_sum_dot), p_layer, CR._ptr(F0), C.byref(a_), C.byref(al_), CR._stream_ptr())
+
+
 _lin_work = {}
 _lane = 0   # the moment lane (stream) the calling thread launches on: work buffers are per lane
 
@@ -184,11 +220,18 @@ class LinInputs:
     `_check_lin_args` and `_alloc_lin_optics`."""
 
     def _check_lin_args(self, model: H.RTModel, lin_model: H.LinModel, NAer: int, NGas: int, NSurf: int):
-        if NAer != lin_model.n_aer or NAer != len(model.aerosol_optics) or NSurf != 1 or NGas != len(lin_model.tau_abs_dot):
+        land = LAND_BRDF.get(type(model.surface))
+        if land is not None and NSurf != land[1]:
+            raise _lib.VSMError("rt_run (linearized): %s has %d parameters (%s): NSurf = %d expected, got %r"
+                                % (type(model.surface).__name__, land[1], ", ".join(surface_param_names(model.surface)), land[1],
+                                   NSurf))
+        if (NAer != lin_model.n_aer or NAer != len(model.aerosol_optics) or (land is None and NSurf != 1)
+                or NGas != len(lin_model.tau_abs_dot)):
             raise _lib.VSMError("rt_run (linearized): NAer must equal the aerosols of model and lin_model, NGas = "
                                 "len(lin_model.tau_abs_dot), NSurf = 1")
-        if not isinstance(model.surface, (H.LambertianSurfaceScalar, H.CoxMunkSurface)):
+        if land is None and not isinstance(model.surface, (H.LambertianSurfaceScalar, H.CoxMunkSurface)):
             raise _lib.VSMError("rt_run (linearized): surface %r has no linearized builder here" % (model.surface,))
+        self.nSurf = NSurf
         arch, FT = model.architecture, model.float_type
         CR._require_gpu(arch)
         self.model, self.lin_model, self.arch, self.FT = model, lin_model, arch, FT
@@ -286,6 +329,10 @@ class LinInputs:
     def _surface_tables(self):
         model = self.model
         self.surf = []
+        if type(model.surface) in LAND_BRDF:       # all moments and parameters in one launch: (rho[m], drho[m][K])
+            rho, drho = land_brdf_reflectance_lin(model.surface, self.dq, model.m_max, self.arch, self.FT)
+            self.surf = [(rho[m], drho[m]) for m in range(model.m_max + 1)]
+            return
         for m in range(model.m_max + 1):
             rho = drho = None
             if isinstance(model.surface, H.CoxMunkSurface):
@@ -308,8 +355,10 @@ class SceneLin(LinInputs):
     the host mirror (host_model.constructCoreOpticalPropertiesLin, Z_dot materialised on the host) -- kept as a cross-check.
 
     Parameter slots (parameter_layout.jl:28-56): 7 per aerosol (tau_ref, n_r, n_i, r_m, sigma_r, p0, sigma_p; their optics
-    derivatives are inputs: LinModel.tau_aer_dot / lin_aerosol_optics), the gases, then ONE surface slot -- the Lambertian albedo
-    (lambertian_surface_lin.jl:48-162) or the Cox-Munk wind speed (coxmunk_surface_lin.jl:27-102)."""
+    derivatives are inputs: LinModel.tau_aer_dot / lin_aerosol_optics), the gases, then the surface slots -- ONE for the
+    Lambertian albedo (lambertian_surface_lin.jl:48-162) or the Cox-Munk wind speed (coxmunk_surface_lin.jl:27-102); FOUR for
+    rpvSurfaceScalar (rho0, rho_c, k, Theta) and THREE for RossLiSurfaceScalar (fvol, fgeo, fiso), whose derivatives are ours
+    (LAND_BRDF, vsm_land_brdf_reflectance_lin / vsm_brdf_surface_lin_multi)."""
 
     def __init__(self, model: H.RTModel, lin_model: H.LinModel, NAer: int, NGas: int, NSurf: int,
                  spec_slice: Optional[slice] = None, host_optics: bool = False, _reduce_m0: bool = True):
@@ -810,6 +859,8 @@ class SceneLin(LinInputs):
         if isinstance(model.surface, H.CoxMunkSurface):
             _lib.call("vsm_brdf_surface_lin", dt, C.byref(q_), S, m, CR._ptr(rho), CR._ptr(drho), isurf, CR._ptr(tau_sum_s),
                       CR._ptr(tsd_s), pl, CR._ptr(self.F0), C.byref(a_), C.byref(al_), CR._stream_ptr())
+        elif type(model.surface) in LAND_BRDF:
+            brdf_surface_lin_multi_(self.dq, S, m, rho, drho, isurf, tau_sum_s, tsd_s, pl, self.F0, w["added_s"], w["als"])
         else:
             alb = C.c_double(model.surface.albedo) if dt == torch.float64 else C.c_float(model.surface.albedo)
             _lib.call("vsm_lambertian_surface_lin", dt, C.byref(q_), S, m, alb, isurf, CR._ptr(tau_sum_s), CR._ptr(tsd_s), pl,
@@ -848,8 +899,9 @@ def rt_run_lin(model: H.RTModel, lin_model: H.LinModel, NAer: int, NGas: int, NS
     """rt_run(model, lin_model, NAer, NGas, NSurf) (rt_run_lin.jl:72-78 -> :102-326) -> (R, T, Rdot, Tdot);
     Rdot/Tdot: [nVZA, nStokes, nSpec, Nparams].  Supported: NAer = number of aerosols of the model (7 slots each, optics
     derivatives supplied in lin_model), NGas = len(lin_model.tau_abs_dot), NSurf = 1
-    (Lambertian albedo or Cox-Munk wind speed, by the model's surface).  Like the reference's linearized driver this
-    path applies no TMS correction."""
+    (Lambertian albedo or Cox-Munk wind speed, by the model's surface), NSurf = 4 for rpvSurfaceScalar (rho0, rho_c, k, Theta)
+    or NSurf = 3 for RossLiSurfaceScalar (fvol, fgeo, fiso); the surface slots come last.  Like the reference's linearized
+    driver this path applies no TMS correction."""
     scene = SceneLin(model, lin_model, NAer, NGas, NSurf)
     scene.run()
     synchronize_if_gpu()

@@ -160,7 +160,7 @@ def rt_run_multisensor(model: H.RTModel, lin_model: H.LinModel, NAer: int, NGas:
     Levels as in CoreRT.rt_run_multisensor: 0 = TOA, l = below layer l, Nz = just above the surface (the surface layer alone as the
     bottom); duplicates and any order allowed, each distinct level computed once.  Level 0 is (R, T, Rdot, Tdot) of
     SceneLin.run(lanes=1, fold=False) on the same scene bit for bit (rt_run_lin's default lanes / folded walk agree with it to
-    rounding).  Model arguments, NSurf = 1 and the Lambertian / Cox-Munk surfaces as rt_run_lin takes them.
+    rounding).  Model arguments, surfaces and NSurf as rt_run_lin takes them (1: Lambertian / Cox-Munk; 4: RPV; 3: Ross-Li).
 
     streams=True: a MultiSensorLinResult, which also carries the level vectors and their derivatives at all quadrature streams per
     moment.  max_points: run the spectral axis in blocks of about that many points (bit-identical to one pass: points are

@@ -233,6 +233,8 @@ class SceneSSLin(CL.LinInputs):
             if isinstance(model.surface, H.CoxMunkSurface):
                 _lib.call("vsm_brdf_surface_lin", dt, C.byref(q_), S, m, CR._ptr(rho), CR._ptr(drho), isurf, CR._ptr(tau_sum_s),
                           CR._ptr(tsd_s), pl, CR._ptr(self.F0), C.byref(a_), C.byref(al_), CR._stream_ptr())
+            elif type(model.surface) in CL.LAND_BRDF:
+                CL.brdf_surface_lin_multi_(self.dq, S, m, rho, drho, isurf, tau_sum_s, tsd_s, pl, self.F0, self.added_s, self.als)
             else:
                 alb = C.c_double(model.surface.albedo) if dt == torch.float64 else C.c_float(model.surface.albedo)
                 _lib.call("vsm_lambertian_surface_lin", dt, C.byref(q_), S, m, alb, isurf, CR._ptr(tau_sum_s), CR._ptr(tsd_s), pl,
@@ -259,7 +261,8 @@ class SceneSSLin(CL.LinInputs):
 def rt_run_ss_lin(model: H.RTModel, lin_model: H.LinModel, NAer: int, NGas: int, NSurf: int):
     """The linearized elastic single-scattering run -> (R, T, Rdot, Tdot).  R, T are rt_run_ss(model)'s, bit for bit; Rdot / Tdot
     [nVZA, nStokes, nSpec, Nparams] are their analytic Jacobians in the parameter slots of rt_run_lin (ParameterLayout: 7 per
-    aerosol, the gases, one surface slot: the Lambertian albedo or the Cox-Munk wind speed).  Same arguments and refusals as
+    aerosol, the gases, the surface slots: the Lambertian albedo or the Cox-Munk wind speed, or the 4 / 3 parameters of an RPV / Ross-Li
+    surface).  Same arguments and refusals as
     rt_run_lin; SolarBeam is the only source, at most three aerosols, no Cox-Munk single-scattering correction.  The surface
     slot and the surface's share of every slot are those of the reference's linearized surface builders, which weigh the direct
     beam with F0 where the forward builders use I0 = e1: with F0[0] = 1 (and, over Cox-Munk, F0 = e1) they are the exact

@@ -975,6 +975,29 @@ VSM_LIN_API(float, f32)
     return brdf_surface_lin<T>(cvt_quad<T>(q), S, m, rho, drho, iparam, tau_sum, tau_sum_dot, p_layer, F0,             \
                                cvt_added<T>(added), cvt_al<T>(al), as_stream(stream));                                 \
   }                                                                                                                    \
+  extern "C" int vsm_land_brdf_reflectance_lin_##SFX(const vsm_quad_##SFX* q, int kind, const T* params, int m_max,    \
+                                                     int nphi, const T* phi, const T* wphi, T* rho, T* drho,           \
+                                                     void* stream) {                                                   \
+    int rc;                                                                                                            \
+    if ((rc = check_quad(q))) return rc;                                                                               \
+    VSM_REQUIRE(params && phi && wphi && rho && drho, "land_brdf_reflectance_lin: null argument");                     \
+    return land_brdf_reflectance_lin<T>(kind, params, q->n_stokes, q->N / q->n_stokes, q->mu, m_max, nphi, phi, wphi,  \
+                                        rho, drho, as_stream(stream));                                                 \
+  }                                                                                                                    \
+  extern "C" int vsm_brdf_surface_lin_multi_##SFX(const vsm_quad_##SFX* q, int S, int m, const T* rho, const T* drho,  \
+                                                  int K, int isurf, const T* tau_sum, const T* tau_sum_dot,            \
+                                                  int p_layer, const T* F0, const vsm_added_##SFX* added,              \
+                                                  const vsm_added_lin_##SFX* al, void* stream) {                       \
+    int rc;                                                                                                            \
+    VSM_REQUIRE(added && added->d_symmetric == 0, "brdf_surface_lin_multi: d_symmetric layers are not accepted here"); \
+    if ((rc = check_quad(q)) || (rc = check_added(added)) || (rc = check_al(al))) return rc;                           \
+    VSM_REQUIRE(S >= 0 && m >= 0 && rho && drho && (S == 0 || (tau_sum && F0)) && (tau_sum_dot || p_layer == 0) &&     \
+                    K >= 1 && isurf >= 0 && isurf + K <= al->P && p_layer >= 0 && p_layer <= isurf,                    \
+                "brdf_surface_lin_multi: bad argument (K >= 1 surface slots [isurf, isurf + K) within P, the layer "   \
+                "slots [0, p_layer) before them)");                                                                    \
+    return brdf_surface_lin_multi<T>(cvt_quad<T>(q), S, m, rho, drho, K, isurf, tau_sum, tau_sum_dot, p_layer, F0,     \
+                                     cvt_added<T>(added), cvt_al<T>(al), as_stream(stream));                           \
+  }                                                                                                                    \
   extern "C" int vsm_interaction_hdrf_##SFX(const vsm_quad_##SFX* q, int S, int m, const vsm_composite_##SFX* comp,    \
                                             const vsm_added_##SFX* added_surface, T* hdr_J, T* bhr_uw, T* bhr_dw,      \
                                             void* stream) {                                                            \

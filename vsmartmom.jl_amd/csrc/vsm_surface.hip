@@ -5,6 +5,9 @@
 //      Mueller matrix + d/dU :277-370), 100-point Gauss-Legendre over azimuth handed in by the host
 //   brdf_surface          create_surface_layer!(::AbstractSurfaceType)           Surfaces/rpv_surface.jl:51-97
 //   brdf_surface_lin      create_surface_layer!(::noRS, ::CoxMunkSurface, lin)   Surfaces/coxmunk_surface_lin.jl:27-102
+//   land_brdf_reflectance_lin  reflectance(brdf, pol, mu, m) of rpvSurfaceScalar / RossLiSurfaceScalar (rpv_surface.jl:99-190,
+//                         rossli_surface.jl:12-98) with analytic parameter derivatives (ours: the reference has none)
+//   brdf_surface_lin_multi     brdf_surface_lin with K surface slots
 //   coxmunk_ss_correction apply_ss_correction! (TMS)                             Surfaces/coxmunk_surface.jl:481-569
 //
 // The reflectance matrix does not depend on the spectral point (the reference evaluates the water index at 550 nm for
@@ -392,6 +395,195 @@ int brdf_surface_lin(const quad<T>& q, int S, int m, const T* rho, const T* drho
   return VSM_OK;
 }
 
+// ---- kernel-driven land BRDFs (rpvSurfaceScalar, RossLiSurfaceScalar): Fourier blocks WITH parameter derivatives ----------
+// reflectance(brdf, pol, mu, m) (rpv_surface.jl:160-190; BRDFs rpv_surface.jl:99-150, rossli_surface.jl:12-98) as
+// host_model.brdf_reflectance evaluates it -- ff/pi sum_phi w rho(mu_i, mu_j, phi) cos(m phi) on the I -> I elements, ff = 1 (m = 0)
+// | 2, no doubling of the m = 0 block -- for every moment m = 0 .. m_max in ONE launch, together with the analytic derivative of
+// the block with respect to each BRDF parameter, in the order of the surface's fields.  The reference linearizes neither surface:
+//   RPV      rho = rho0 M F H,  M = (mu_i mu_r (mu_i + mu_r))^(k-1),  F = (1 - t^2) / D^(3/2),  D = 1 + t^2 + 2 t cos g,
+//            t = -Theta,  H = 1 + (1 - rho_c) / (1 + G):
+//            d/drho0 = M F H (no division by rho0),  d/drho_c = -rho0 M F / (1 + G),  d/dk = rho ln(mu_i mu_r (mu_i + mu_r)),
+//            d/dTheta = -rho0 M H dF/dt,  dF/dt = -2 t / D^(3/2) - 3 (1 - t^2)(t + cos g) / D^(5/2)
+//   Ross-Li  rho = fvol K_vol + fgeo K_geo + fiso:  d/dfvol = K_vol,  d/dfgeo = K_geo,  d/dfiso = 1 (its block is 0 for m > 0)
+// One thread per (stream pair, moment): it walks the azimuth nodes and sums the block and its K derivatives in the same loop.
+template <typename T>
+struct land_brdf {
+  int kind;  // 0: RPV (K = 4: rho0, rho_c, k, Theta), 1: Ross-Li (K = 3: fvol, fgeo, fiso)
+  T p[4];
+};
+template <typename T>
+__device__ __forceinline__ void land_brdf_value(const land_brdf<T>& sf, T mi, T mr, T ph, T& rho, T (&d)[4]) {
+  const T si = sqrt(max(T(0), T(1) - mi * mi)), sr = sqrt(max(T(0), T(1) - mr * mr));
+  const T ti = si / mi, tr = sr / mr;
+  if (sf.kind == 0) {
+    const T rho0 = sf.p[0], rho_c = sf.p[1], k = sf.p[2], th = -sf.p[3];
+    const T cp = cos(ph);
+    const T cosg = -mi * mr + si * sr * cp;
+    const T G = sqrt(max(T(0), ti * ti + tr * tr + T(2) * ti * tr * cp));
+    const T base = mi * mr * (mi + mr);
+    const T M = pow(base, k - T(1));
+    const T D = T(1) + th * th + T(2) * th * cosg;
+    const T D15 = D * sqrt(D);
+    const T F = (T(1) - th * th) / D15;
+    const T Hh = T(1) + (T(1) - rho_c) / (T(1) + G);
+    const T dF = T(-2) * th / D15 - T(3) * (T(1) - th * th) * (th + cosg) / (D15 * D);
+    const T MFH = M * F * Hh;
+    rho = rho0 * MFH;
+    d[0] = MFH;
+    d[1] = -rho0 * M * F / (T(1) + G);
+    d[2] = rho * log(base);
+    d[3] = -rho0 * M * Hh * dF;
+  } else {
+    const T dd = pi_v<T>() - ph;
+    const T cd = cos(dd), sd = sin(dd);
+    const T cxi = min(max(mi * mr + si * sr * cd, T(-1)), T(1));
+    const T xi = acos(cxi);
+    const T K_vol = ((pi_v<T>() / 2 - xi) * cxi + sin(xi)) / (mi + mr) - pi_v<T>() / 4;
+    const T sec = T(1) / mi + T(1) / mr;  // b/r = 1: the primed angles are the angles
+    const T D2 = max(ti * ti + tr * tr - T(2) * ti * tr * cd, T(0));
+    const T q = ti * tr * sd;
+    const T t = acos(min(max(T(2) * sqrt(D2 + q * q) / sec, T(-1)), T(1)));  // h/b = 2
+    const T K_geo = (t - sin(t) * cos(t)) * sec / pi_v<T>() - sec + (T(1) + cxi) / (2 * (mi * mr));
+    rho = sf.p[2] + sf.p[0] * K_vol + sf.p[1] * K_geo;
+    d[0] = K_vol;
+    d[1] = K_geo;
+    d[2] = T(1);
+    d[3] = T(0);
+  }
+}
+// rho[m][N,N], drho[m][K][N,N] (column-major blocks, element (i ns + a) + N (j ns + b); zero unless a = b = 0)
+template <typename T>
+__global__ void __launch_bounds__(256) k_land_brdf_reflectance_lin(land_brdf<T> sf, int K, int Nmu, int ns, const T* __restrict__ muN,
+                                                                   int m_max, int nphi, const T* __restrict__ phi,
+                                                                   const T* __restrict__ wphi, T* rho, T* drho) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  const long long pairs = (long long)Nmu * Nmu;
+  if (e >= pairs * (m_max + 1)) return;
+  const int m = (int)(e / pairs);
+  const int x = (int)(e % pairs), i = x % Nmu, j = x / Nmu;
+  const T mi = muN[i * ns], mr = muN[j * ns];
+  T acc = T(0), dacc[4] = {T(0), T(0), T(0), T(0)};
+  for (int f = 0; f < nphi; ++f) {
+    const T ph = phi[f];
+    T r, d[4];
+    land_brdf_value<T>(sf, mi, mr, ph, r, d);
+    const T wc = wphi[f] * cos(T(m) * ph);
+    acc += wc * r;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) dacc[k] += wc * d[k];
+  }
+  const T ff = (m == 0 ? T(1) : T(2));
+  const int N = Nmu * ns;
+  const long long NN = (long long)N * N;
+  for (int a = 0; a < ns; ++a)
+    for (int b = 0; b < ns; ++b) {
+      const long long o = (long long)(i * ns + a) + (long long)N * (j * ns + b);
+      const bool ii = (a == 0 && b == 0);
+      rho[NN * m + o] = ii ? ff * acc / pi_v<T>() : T(0);
+      // (Ross-Li d/dfiso = 1 has no azimuthal dependence: its moments m > 0 are exactly zero, not the rounding of the sum)
+      for (int k = 0; k < K; ++k)
+        drho[NN * ((long long)m * K + k) + o] = (ii && !(sf.kind == 1 && k == 2 && m > 0)) ? ff * dacc[k] / pi_v<T>() : T(0);
+    }
+}
+
+template <typename T>
+int land_brdf_reflectance_lin(int kind, const T* params_h, int n_stokes, int Nmu, const T* muN, int m_max, int nphi, const T* phi,
+                              const T* wphi, T* rho, T* drho, hipStream_t st) {
+  if (kind != 0 && kind != 1) {
+    set_error("land_brdf_reflectance_lin: kind must be 0 (RPV) or 1 (Ross-Li), got %d", kind);
+    return VSM_ERR_INVALID_ARG;
+  }
+  if (nphi < 1 || m_max < 0 || Nmu < 1 || n_stokes < 1 || n_stokes > 4) {
+    set_error("land_brdf_reflectance_lin: nphi >= 1, m_max >= 0, 1 <= n_stokes <= 4 (got %d, %d, %d)", nphi, m_max, n_stokes);
+    return VSM_ERR_INVALID_ARG;
+  }
+  land_brdf<T> sf;
+  sf.kind = kind;
+  const int K = kind == 0 ? 4 : 3;
+  for (int k = 0; k < 4; ++k) sf.p[k] = k < K ? params_h[k] : T(0);
+  const long long tot = (long long)Nmu * Nmu * (m_max + 1);
+  hipLaunchKernelGGL(k_land_brdf_reflectance_lin<T>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, sf, K, Nmu, n_stokes, muN,
+                     m_max, nphi, phi, wphi, rho, drho);
+  VSM_LAUNCH_CHECK("k_land_brdf_reflectance_lin");
+  return VSM_OK;
+}
+
+// ---- linearized BRDF surface layer with K surface slots isurf .. isurf + K - 1 (k_brdf_mats / k_brdf_src_lin with one derivative
+// block per slot): ap_r-+[isurf + k] = (f drho_k) diag(mu w), ap_J0-[isurf + k] = mu0 sum_s (f drho_k)[:, i0 + s] F0_s att; every
+// other block of the surface slots is zero, the layer slots p < p_layer carry -j0- tau_sum_dot / mu0; j0+ = 0, t-- = 0.
+template <typename T>
+__global__ void k_brdf_mats_multi(int N, int m, const T* __restrict__ rho, const T* __restrict__ drho, int K, int isurf,
+                                  const T* __restrict__ mu, const T* __restrict__ wt, T* r_mp, T* r_pm, T* t_pp, T* t_mm, int P, T* ar,
+                                  T* arpm, T* at, T* atmm) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= N * N) return;
+  const int i = e % N, j = e / N;
+  const T f = (m == 0) ? T(2) : T(1);
+  const T sc = mu[j] * wt[j];
+  r_mp[e] = (f * rho[e]) * sc;
+  r_pm[e] = T(0);
+  t_pp[e] = (i == j) ? T(1) : T(0);
+  t_mm[e] = T(0);
+  for (int p = 0; p < P; ++p) {
+    const long long o = e + (long long)N * N * p;
+    const int k = p - isurf;
+    ar[o] = (k >= 0 && k < K) ? (f * drho[e + (long long)N * N * k]) * sc : T(0);
+    arpm[o] = T(0);
+    at[o] = T(0);
+    atmm[o] = T(0);
+  }
+}
+template <typename T>
+__global__ void k_brdf_src_lin_multi(int N, int ns, int S, int m, const T* __restrict__ rho, const T* __restrict__ drho, int K,
+                                     int isurf, int P, int p_layer, int i_mu0, T mu0, const T* __restrict__ tau_sum,
+                                     const T* __restrict__ tau_sum_dot, const T* __restrict__ F0, T* j0_p, T* j0_m, T* aJp, T* aJm) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (long long)N * S) return;
+  const int i = (int)(e % N);
+  const long long s = e / N;
+  const T att = exp(-tau_sum[s] / mu0);
+  const int i0 = ns * i_mu0;
+  const T f = (m == 0) ? T(2) : T(1);
+  T a = T(0);
+  for (int k = 0; k < ns; ++k) a += (f * rho[i + (long long)N * (i0 + k)]) * (F0[k + (long long)ns * s] * att);
+  const T jm = mu0 * a;
+  j0_p[e] = T(0);
+  j0_m[e] = jm;
+  for (int p = 0; p < P; ++p) {
+    const long long o = e + (long long)N * S * p;
+    aJp[o] = T(0);
+    T v = T(0);
+    if (p < p_layer) v = -jm * tau_sum_dot[s + (long long)S * p] / mu0;
+    if (p >= isurf && p < isurf + K) {
+      const T* dr = drho + (long long)N * N * (p - isurf);
+      T da = T(0);
+      for (int k = 0; k < ns; ++k) da += (f * dr[i + (long long)N * (i0 + k)]) * (F0[k + (long long)ns * s] * att);
+      v = mu0 * da;
+    }
+    aJm[o] = v;
+  }
+}
+
+template <typename T>
+int brdf_surface_lin_multi(const quad<T>& q, int S, int m, const T* rho, const T* drho, int K, int isurf, const T* tau_sum,
+                           const T* tau_sum_dot, int p_layer, const T* F0, const added<T>& a, const added_lin<T>& al, hipStream_t st) {
+  if (a.mat_stride != 0 || al.mat_stride != 0) {
+    set_error("brdf_surface_lin_multi: surface layers use ONE shared block (mat_stride must be 0)");
+    return VSM_ERR_INVALID_ARG;
+  }
+  const int N = q.N;
+  hipLaunchKernelGGL(k_brdf_mats_multi<T>, dim3((N * N + 255) / 256), dim3(256), 0, st, N, m, rho, drho, K, isurf, q.mu, q.wt,
+                     a.r_mp, a.r_pm, a.t_pp, a.t_mm, al.P, al.ap_r_mp, al.ap_r_pm, al.ap_t_pp, al.ap_t_mm);
+  VSM_LAUNCH_CHECK("k_brdf_mats_multi");
+  if (S > 0) {
+    hipLaunchKernelGGL(k_brdf_src_lin_multi<T>, dim3((unsigned)(((long long)N * S + 255) / 256)), dim3(256), 0, st, N, q.n_stokes,
+                       S, m, rho, drho, K, isurf, al.P, p_layer, q.i_mu0, q.mu0, tau_sum, tau_sum_dot, F0, a.j0_p, a.j0_m,
+                       al.ap_J0_p, al.ap_J0_m);
+    VSM_LAUNCH_CHECK("k_brdf_src_lin_multi");
+  }
+  return VSM_OK;
+}
+
 // ---- Lambertian surface with a spectrally varying albedo (LambertianSurfaceLegendre / LambertianSurfaceSpline,
 // lambertian_surface.jl:97-213): per-point blocks r-+[:,:,s] = 2 a_s E11 (x) (mu w); the builder's quirks kept: j0+ = 0, and for
 // m > 0 the transmission blocks are ZERO (the scalar builder writes the identity there).
@@ -638,6 +830,10 @@ int postprocess_vza_hdrf(int N, int ns, int S, int nV, const int* row0_h, const 
   template int lambertian_surface_spectral<T>(const quad<T>&, int, int, const T*, const T*, const added<T>&, hipStream_t);    \
   template int brdf_surface_lin<T>(const quad<T>&, int, int, const T*, const T*, int, const T*, const T*, int, const T*,      \
                                    const added<T>&, const added_lin<T>&, hipStream_t);                                        \
+  template int land_brdf_reflectance_lin<T>(int, const T*, int, int, const T*, int, int, const T*, const T*, T*, T*,          \
+                                            hipStream_t);                                                                   \
+  template int brdf_surface_lin_multi<T>(const quad<T>&, int, int, const T*, const T*, int, int, const T*, const T*, int,     \
+                                         const T*, const added<T>&, const added_lin<T>&, hipStream_t);                      \
   template int interaction_hdrf<T>(const quad<T>&, int, int, const composite<T>&, const added<T>&, T*, T*, T*, hipStream_t);  \
   template int postprocess_vza_hdrf<T>(int, int, int, int, const int*, const T*, const T*, T*, hipStream_t);                  \
   template int coxmunk_ss_correction<T>(const cm_surf<T>&, int, int, int, const T*, const T*, T, int, int, const T*, const T*, \
