@@ -334,6 +334,17 @@ int vsm_elemental_lin_mix_f32(const vsm_quad_f32* q, int S, int m, int ndoubl, c
                               const float* Zc_mp, int zsel, const float* fz, int p_layer, const float* dtau_dot,
                               const float* varpi_dot, const float* tau_sum_dot, const float* zdcoef,
                               const vsm_added_f32* added, const vsm_added_lin_f32* added_lin, void* stream);
+/* The linearized elemental thermal source (the `:thermal` slot of a linearized run; called after vsm_elemental_lin* with F0 = 0
+ * and before vsm_doubling_lin_*, which then runs with the slot's expk = 1 and a zero dtau_dot table, i.e. ekl = 0).  On the
+ * Stokes-I rows, x = dtau / mu_i:  j0+ = j0- = 2 pi (1 - varpi) B (1 - e^-x)  -- the bits of vsm_thermal_source_* -- and
+ * ap_J0+-[p] = 2 pi B [ -varpi_dot_p (1 - e^-x) + (1 - varpi) e^-x dtau_dot_p / mu_i ]  for p < p_layer; zero on the Q/U/V rows
+ * and in every slot p >= p_layer of added_lin.  dtau_dot[S,p_layer] = tau_dot / 2^ndoubl, varpi_dot[S,p_layer]. */
+int vsm_thermal_source_lin_f64(const vsm_quad_f64* q, int S, const double* dtau, const double* varpi, const double* B,
+                               int p_layer, const double* dtau_dot, const double* varpi_dot, const vsm_added_f64* added,
+                               const vsm_added_lin_f64* added_lin, void* stream);
+int vsm_thermal_source_lin_f32(const vsm_quad_f32* q, int S, const float* dtau, const float* varpi, const float* B,
+                               int p_layer, const float* dtau_dot, const float* varpi_dot, const vsm_added_f32* added,
+                               const vsm_added_lin_f32* added_lin, void* stream);
 /* doubling_allparams! (doubling_lin.jl:216-339): forward + the first n_active parameter slots; the D-symmetry at
  * the end covers all P slots.  dtau_dot_all[S,P] (zero beyond the layer parameters); expk[S] updated in place. */
 size_t vsm_doubling_lin_work_elems(int N, int S, int P);

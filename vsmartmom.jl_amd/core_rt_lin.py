@@ -358,7 +358,9 @@ class SceneLin(LinInputs):
     derivatives are inputs: LinModel.tau_aer_dot / lin_aerosol_optics), the gases, then the surface slots -- ONE for the
     Lambertian albedo (lambertian_surface_lin.jl:48-162) or the Cox-Munk wind speed (coxmunk_surface_lin.jl:27-102); FOUR for
     rpvSurfaceScalar (rho0, rho_c, k, Theta) and THREE for RossLiSurfaceScalar (fvol, fgeo, fiso), whose derivatives are ours
-    (LAND_BRDF, vsm_land_brdf_reflectance_lin / vsm_brdf_surface_lin_multi)."""
+    (LAND_BRDF, vsm_land_brdf_reflectance_lin / vsm_brdf_surface_lin_multi).  With a ThermalEmission source the
+    `:thermal` slot and its derivatives are added for m = 0 (_run_thermal, vsm_thermal_source_lin), and the nPlanck slots of
+    ThermalEmission.B_layer_dot follow the surface slots in Rd / Td."""
 
     def __init__(self, model: H.RTModel, lin_model: H.LinModel, NAer: int, NGas: int, NSurf: int,
                  spec_slice: Optional[slice] = None, host_optics: bool = False, _reduce_m0: bool = True):
@@ -371,6 +373,14 @@ class SceneLin(LinInputs):
             host_optics = True
         pol, qp = self.pol, self.qp
         P, pl = self.P, self.pl
+        # Planck slots: ThermalEmission.B_layer_dot [nPlanck, rows, nSpec], appended after the surface slots
+        th_src = [s_ for s_ in (model.sources or ()) if isinstance(s_, H.ThermalEmission)]
+        Bd = getattr(th_src[0], "B_layer_dot", None) if th_src else None
+        self.nPlanck = 0 if Bd is None else int(Bd.shape[0])
+        if P + self.nPlanck > 64:
+            raise _lib.VSMError("rt_run (linearized): %d parameter slots + %d Planck slots (limit 64)" % (P, self.nPlanck))
+        if Bd is not None and Bd.shape[2] != model.tau_rayl.shape[0]:
+            raise _lib.VSMError("ThermalEmission: B_layer_dot has %d spectral points, the model %d" % (Bd.shape[2], model.tau_rayl.shape[0]))
         # forward optics, quadrature, F0, composite / added / surface layers and R, T: the forward scene's device state
         # (rt_kernel_lin.jl:87 hard-codes scatter = true: a layer with tau*varpi <= 2 eps still goes through elemental! and
         # doubling! with ndoubl = 0 -- Scene.prepare gives such a layer ndoubl = 0 as well -- and only its interaction
@@ -393,7 +403,11 @@ class SceneLin(LinInputs):
         self.cl = CompositeLayerLin(FT, arch, P, N, S)
         self.expk = torch.empty(max(S, 1), dtype=dt, device=dev)
         self.R, self.T = fwd.R_SFI, fwd.T_SFI
-        self.Rd = torch.zeros((P, S, pol.n, nV), dtype=dt, device=dev)
+        # the thermal slot: its layers are allocated on first use (_thermal_state); the Planck tables as (nPlanck, rows, S)
+        self.thermal_B_dot = (array_type(arch)(np.ascontiguousarray(Bd[:, :, self.sl].astype(FT))) if self.nPlanck else None)
+        self._th = None
+        self._check_thermal()
+        self.Rd = torch.zeros((P + self.nPlanck, S, pol.n, nV), dtype=dt, device=dev)
         self.Td = torch.zeros_like(self.Rd)
         self._lanes = []
         self._fold = {}
@@ -420,6 +434,8 @@ class SceneLin(LinInputs):
         scene.lin_model, ... and re-uploads: the sub-scene must see the new arrays, not the constructor-time snapshot)."""
         model, qp = self.model, self.model.quad_points
         F0m = model.F0
+        if model.sources is not None:   # (the sub-scene carries no thermal slot; without a SolarBeam its F0 stays 0)
+            model = dataclasses.replace(model, sources=tuple(s_ for s_ in model.sources if not isinstance(s_, H.ThermalEmission)))
         qi = H.QuadPoints(qp.mu0, qp.imu0, qp.qp_mu, qp.wt_mu, np.repeat(qp.qp_mu, 2), np.repeat(qp.wt_mu, 2), qp.Nquad, qp.Nstreams)
         return dataclasses.replace(model, polarization_type=H.Stokes_IQ(), quad_points=qi, m_max=0,
                                    F0=None if F0m is None else np.ascontiguousarray(np.asarray(F0m)[:2]))
@@ -503,11 +519,29 @@ class SceneLin(LinInputs):
         5 ms of launch-bound input folding in front of either).  The launch sequence depends only on the layer structure (ndoubl,
         interface tags, lanes / fold) -- the graph is captured once per such key, on buffers the scene owns, and reads the
         optics where `prepare()` puts them."""
+        thermal = self._check_thermal()
         if graph is None:
-            graph = bool(getattr(self, "graph_replay", False)) and self.S > 0 and not torch.cuda.is_current_stream_capturing()
+            graph = (bool(getattr(self, "graph_replay", False)) and self.S > 0 and not torch.cuda.is_current_stream_capturing()
+                     and not thermal)
+        if graph and thermal:
+            raise NotImplementedError("SceneLin.run(graph=True): a scene with a ThermalEmission source is not captured "
+                                      "(run it with graph=False or graph=None)")
         if graph:
             return self._run_graph(lanes, fold)
         return self._run_eager(lanes, fold)
+
+    def _check_thermal(self) -> bool:
+        """Is there a thermal slot to run (a non-zero B_layer or Planck tables)?  Its scope limit is checked here, on host values,
+        before anything is launched: every layer must scatter (the slot state the reference's forward run carries through
+        non-scattering layers, Scene._thermal_slot, has no linearized meaning)."""
+        if self.fwd.thermal_B is None and not self.nPlanck:
+            return False
+        eps2 = 2 * np.finfo(self.FT).eps
+        for iz, ly in enumerate(self.fwd.moments[0]["layers"]):
+            if not ly["props"].max_tau_varpi > eps2:
+                raise NotImplementedError("rt_run (linearized): layer %d does not scatter; a ThermalEmission source needs a column "
+                                          "whose layers all scatter" % (iz + 1))
+        return True
 
     def _run_graph(self, lanes, fold):
         key = (lanes, fold, tuple((ly["nd"], ly["iface"]) for ly in self.fwd.moments[0]["layers"]), len(self.fwd.moments),
@@ -533,6 +567,12 @@ class SceneLin(LinInputs):
         return self.R, self.T, self.Rd, self.Td
 
     def _run_eager(self, lanes: Optional[int] = None, fold: Optional[bool] = None):
+        out = self._run_solar(lanes, fold)
+        if self.S > 0 and (self.fwd.thermal_B is not None or self.nPlanck):
+            self._run_thermal()
+        return out
+
+    def _run_solar(self, lanes: Optional[int] = None, fold: Optional[bool] = None):
         global _lane
         S = self.S
         nm = len(self.fwd.moments)
@@ -557,8 +597,8 @@ class SceneLin(LinInputs):
                 r0, t0, rd0, td0 = self.sub0.run(lanes=1, fold=False)
                 self.R[:, :2, :].copy_(r0)
                 self.T[:, :2, :].copy_(t0)
-                self.Rd[:, :, :2, :].copy_(rd0)
-                self.Td[:, :, :2, :].copy_(td0)
+                self.Rd[:self.P, :, :2, :].copy_(rd0)
+                self.Td[:self.P, :, :2, :].copy_(td0)
             for mom in self.fwd.moments:
                 if reduced and mom["m"] == 0:
                     continue
@@ -846,30 +886,125 @@ class SceneLin(LinInputs):
 
     def _finish_moment(self, mom, w):
         """Surface layer, its interaction and the post-processing of one Fourier moment on the workspace `w`."""
-        model, pol, qp, FT, dt, fwd = self.model, self.pol, self.qp, self.FT, self.dt, self.fwd
-        N, S, P, pl = self.N, self.S, self.P, self.pl
+        model, pol, qp, FT, dt = self.model, self.pol, self.qp, self.FT, self.dt
+        N, S, P = self.N, self.S, self.P
         comp, cl = w["comp"], w["cl"]
-        isurf = self.layout.surface_index(0)
-        q_ = self.dq.cstruct()
         m = mom["m"]
         weight = FT(0.5 / math.pi) if m == 0 else FT(1.0 / math.pi)
-        a_, al_ = w["added_s"].cstruct(), w["als"].cstruct()
-        tau_sum_s, tsd_s = mom["tau_sum_surface"], self.tau_sum_dot[fwd.Nz]
-        rho, drho = self.surf[m]
-        if isinstance(model.surface, H.CoxMunkSurface):
-            _lib.call("vsm_brdf_surface_lin", dt, C.byref(q_), S, m, CR._ptr(rho), CR._ptr(drho), isurf, CR._ptr(tau_sum_s),
-                      CR._ptr(tsd_s), pl, CR._ptr(self.F0), C.byref(a_), C.byref(al_), CR._stream_ptr())
-        elif type(model.surface) in LAND_BRDF:
-            brdf_surface_lin_multi_(self.dq, S, m, rho, drho, isurf, tau_sum_s, tsd_s, pl, self.F0, w["added_s"], w["als"])
-        else:
-            alb = C.c_double(model.surface.albedo) if dt == torch.float64 else C.c_float(model.surface.albedo)
-            _lib.call("vsm_lambertian_surface_lin", dt, C.byref(q_), S, m, alb, isurf, CR._ptr(tau_sum_s), CR._ptr(tsd_s), pl,
-                      CR._ptr(self.F0), C.byref(a_), C.byref(al_), CR._stream_ptr())
+        self._surface_lin(mom, w["added_s"], w["als"], self.F0)
         interaction_lin_(mom["iface_surface"], comp, cl, w["added_s"], w["als"])
         CR.postprocessing_vza_(pol, comp, model.vza, model.vaz, qp, m, float(weight), w["R"], w["T"])
         row0, wts = _pp_args(pol, qp, model.vza, model.vaz, m, weight, dt)
         _lib.call("vsm_postprocess_vza_lin", dt, N, pol.n, S, len(model.vza), P, row0, wts, CR._ptr(cl.J0_m), CR._ptr(cl.J0_p),
                   CR._ptr(w["Rd"]), CR._ptr(w["Td"]), CR._stream_ptr())
+
+    def _surface_lin(self, mom, added_s, als, F0):
+        """create_surface_layer! (lin) of one Fourier moment into the surface layers `added_s` / `als`, driven by the beam F0."""
+        model, dt, S, pl = self.model, self.dt, self.S, self.pl
+        isurf = self.layout.surface_index(0)
+        q_ = self.dq.cstruct()
+        m = mom["m"]
+        a_, al_ = added_s.cstruct(), als.cstruct()
+        tau_sum_s, tsd_s = mom["tau_sum_surface"], self.tau_sum_dot[self.fwd.Nz]
+        rho, drho = self.surf[m]
+        if isinstance(model.surface, H.CoxMunkSurface):
+            _lib.call("vsm_brdf_surface_lin", dt, C.byref(q_), S, m, CR._ptr(rho), CR._ptr(drho), isurf, CR._ptr(tau_sum_s),
+                      CR._ptr(tsd_s), pl, CR._ptr(F0), C.byref(a_), C.byref(al_), CR._stream_ptr())
+        elif type(model.surface) in LAND_BRDF:
+            brdf_surface_lin_multi_(self.dq, S, m, rho, drho, isurf, tau_sum_s, tsd_s, pl, F0, added_s, als)
+        else:
+            alb = C.c_double(model.surface.albedo) if dt == torch.float64 else C.c_float(model.surface.albedo)
+            _lib.call("vsm_lambertian_surface_lin", dt, C.byref(q_), S, m, alb, isurf, CR._ptr(tau_sum_s), CR._ptr(tsd_s), pl,
+                      CR._ptr(F0), C.byref(a_), C.byref(al_), CR._stream_ptr())
+
+    # ---- the thermal slot (DESIGN 4.12) ----------------------------------------------------------------------------------------
+    def _thermal_state(self):
+        """The slot's own layers, forward and derivative (allocated on first use), its zero beam, its expk = 1 and the zero
+        dtau_dot table that makes doubling! (lin) form ekl = 0."""
+        if self._th is None:
+            FT, arch, P, N, S = self.FT, self.arch, self.P, self.N, self.S
+            dev = self.expk.device
+            self._th = dict(added=CR.make_added_layer(FT, arch, (N, N), S), al=AddedLayerLin(FT, arch, P, N, S),
+                            comp=CR.make_composite_layer(FT, arch, (N, N), S), cl=CompositeLayerLin(FT, arch, P, N, S),
+                            added_s=self._new_surface_added(), als=AddedLayerLin(FT, arch, P, N, S, shared=True),
+                            F0=torch.zeros_like(self.F0), ones=torch.empty(max(S, 1), dtype=self.dt, device=dev),
+                            zero_dtd=torch.zeros((P, max(S, 1)), dtype=self.dt, device=dev))
+        return self._th
+
+    def _run_thermal(self):
+        """The `:thermal` per-source slot of the linearized run, on the current stream after the solar moments (whatever lanes
+        they ran on have joined it): Scene._thermal_slot step by step with the derivative stacks beside it, m = 0 only (the
+        source is isotropic), into the same R, T, Rdot, Tdot; then the Planck block."""
+        global _lane
+        _lane = 0
+        fwd = self.fwd
+        mom = fwd.moments[0]
+        if fwd.thermal_B is not None:
+            self._thermal_lin_slot(mom)
+        if self.nPlanck:
+            self._planck_block(mom)
+
+    def _thermal_lin_slot(self, mom):
+        model, pol, qp, FT, dt, fwd = self.model, self.pol, self.qp, self.FT, self.dt, self.fwd
+        N, S, P, pl = self.N, self.S, self.P, self.pl
+        t = self._thermal_state()
+        added, al, comp, cl = t["added"], t["al"], t["comp"], t["cl"]
+        q_ = self.dq.cstruct()
+        m = mom["m"]
+        rows = fwd.thermal_B.shape[0]
+        for iz, ly in enumerate(mom["layers"]):
+            props = ly["props"]
+            dtd, vd, tsd = self.dtau_dot_all[iz], self.varpi_dot[iz], self.tau_sum_dot[iz]
+            a_, al_ = added.cstruct(), al.cstruct()
+            # elemental! (lin) with F0 = 0: r, t and their derivatives as in the solar walk, j and jdot reset to zero
+            if self.Zall is not None:
+                mixed, k = fwd.zcomp[iz]
+                _lib.call("vsm_elemental_lin_mix", dt, C.byref(q_), S, m, ly["nd"], CR._ptr(ly["dtau"]), CR._ptr(props.varpi),
+                          CR._ptr(ly["tau_sum"]), CR._ptr(t["F0"]), self.C_, self.CT, CR._ptr(self.Zall[m][0]),
+                          CR._ptr(self.Zall[m][1]), -1 if mixed else k, CR._ptr(self.fz[iz]), pl, CR._ptr(dtd), CR._ptr(vd),
+                          CR._ptr(tsd), CR._ptr(self.zdcoef[iz]), C.byref(a_), C.byref(al_), CR._stream_ptr())
+            else:
+                zpd, zmd, zds = self.host_zdot[m][iz] if self.host_zdot is not None else (None, None, (0, 0))
+                elemental_lin_(pol, ly["tau_sum"], tsd, ly["dtau"], dtd, t["F0"], props.materialize(), vd, zpd, zmd, zds, pl,
+                               m, ly["nd"], self.dq, added, al)
+            if iz < rows:      # contribute! and its derivatives
+                _lib.call("vsm_thermal_source_lin", dt, C.byref(q_), S, CR._ptr(ly["dtau"]), CR._ptr(props.varpi),
+                          CR._ptr(fwd.thermal_B[iz]), pl, CR._ptr(dtd), CR._ptr(vd), C.byref(a_), C.byref(al_), CR._stream_ptr())
+            t["ones"].fill_(1.0)    # the slot's expk = 1 (the doubling kernels square it in place); zero_dtd: ekl = 0
+            doubling_allparams_(pol, t["ones"], ly["nd"], added, al, t["zero_dtd"], qp.mu0, pl)
+            if iz == 0:
+                CR.copy_added_to_composite_(comp, added)
+                c_ = cl.cstruct()
+                _lib.call("vsm_copy_added_to_composite_lin", dt, N, S, C.byref(al_), C.byref(c_), CR._stream_ptr())
+            else:
+                interaction_lin_(ly["iface"], comp, cl, added, al, p_range=self._layer_slots)
+        # the surface layer of the solar walk without its beam terms (surface emission is a separate source type)
+        self._surface_lin(mom, t["added_s"], t["als"], t["F0"])
+        torch._foreach_zero_([t["added_s"].j0_p, t["added_s"].j0_m, t["als"].ap_J0_p, t["als"].ap_J0_m])
+        interaction_lin_(mom["iface_surface"], comp, cl, t["added_s"], t["als"])
+        weight = FT(0.5 / math.pi)
+        CR.postprocessing_vza_(pol, comp, model.vza, model.vaz, qp, m, float(weight), self.R, self.T)
+        row0, wts = _pp_args(pol, qp, model.vza, model.vaz, m, weight, dt)
+        _lib.call("vsm_postprocess_vza_lin", dt, N, pol.n, S, len(model.vza), P, row0, wts, CR._ptr(cl.J0_m), CR._ptr(cl.J0_p),
+                  CR._ptr(self.Rd), CR._ptr(self.Td), CR._stream_ptr())
+
+    def _planck_block(self, mom):
+        """The slot is linear in B: dR / dx_k is the FORWARD thermal slot (Scene._thermal_walk / _thermal_surface, fused layer
+        kernels included) of B := B_layer_dot[k], post-processed into slot P + k of Rdot / Tdot."""
+        model, pol, qp, fwd, P = self.model, self.pol, self.qp, self.fwd, self.P
+        weight = float(self.FT(0.5 / math.pi))
+        B0 = fwd.thermal_B
+        try:
+            for k in range(self.nPlanck):
+                fwd.thermal_B = self.thermal_B_dot[k]
+                fwd._thermal_begin(mom)
+                comp = fwd._th_comp
+                fwd._thermal_walk(mom, comp, 0, fwd.Nz)
+                surf = fwd._thermal_surface(mom)
+                CR.interaction_(mom["iface_surface"], comp, surf, oplevel=True, work=fwd.work)
+                CR.postprocessing_vza_(pol, comp, model.vza, model.vaz, qp, mom["m"], weight, self.Rd[P + k], self.Td[P + k])
+        finally:
+            fwd.thermal_B = B0
 
     def results_host(self):
         """(R, T, Rdot, Tdot) as the reference returns them: [nVZA, nStokes, nSpec] and [nVZA, nStokes, nSpec, Nparams]."""
@@ -901,7 +1036,13 @@ def rt_run_lin(model: H.RTModel, lin_model: H.LinModel, NAer: int, NGas: int, NS
     derivatives supplied in lin_model), NGas = len(lin_model.tau_abs_dot), NSurf = 1
     (Lambertian albedo or Cox-Munk wind speed, by the model's surface), NSurf = 4 for rpvSurfaceScalar (rho0, rho_c, k, Theta)
     or NSurf = 3 for RossLiSurfaceScalar (fvol, fgeo, fiso); the surface slots come last.  Like the reference's linearized
-    driver this path applies no TMS correction."""
+    driver this path applies no TMS correction.
+
+    Sources: model.sources may hold SolarBeam and / or ThermalEmission, as CoreRT.rt_run takes them (without a SolarBeam F0 = 0).
+    R, T then include the thermal radiance and every slot of Rdot / Tdot the derivative of the thermal slot (m = 0
+    only, no surface emission).  ThermalEmission(B_layer_dot=[nPlanck, rows, nSpec]) appends nPlanck Planck (temperature) slots
+    after the surface slots: Nparams = 7 NAer + NGas + NSurf + nPlanck <= 64, slot k of the block = d/dx_k for B_layer_dot[k] =
+    dB_layer / dx_k.  Not supported with a thermal source: a column with a non-scattering layer (NotImplementedError)."""
     scene = SceneLin(model, lin_model, NAer, NGas, NSurf)
     scene.run()
     synchronize_if_gpu()

@@ -854,6 +854,17 @@ static int check_cl(const C* c) {
                                 Zc_mp, zsel, fz, p_layer, dtau_dot, varpi_dot, tau_sum_dot, zdcoef,                    \
                                 cvt_added<T>(added), cvt_al<T>(al), as_stream(stream));                                \
   }                                                                                                                    \
+  int vsm_thermal_source_lin_##SFX(const vsm_quad_##SFX* q, int S, const T* dtau, const T* varpi, const T* B,          \
+                                   int p_layer, const T* dtau_dot, const T* varpi_dot, const vsm_added_##SFX* added,   \
+                                   const vsm_added_lin_##SFX* al, void* stream) {                                      \
+    int rc;                                                                                                            \
+    if ((rc = check_quad(q)) || (rc = check_added(added)) || (rc = check_al(al))) return rc;                           \
+    VSM_REQUIRE(S >= 0 && (S == 0 || (dtau && varpi && B)), "thermal_source_lin: null input");                         \
+    VSM_REQUIRE(p_layer >= 0 && p_layer <= al->P && (p_layer == 0 || S == 0 || (dtau_dot && varpi_dot)),               \
+                "thermal_source_lin: bad p_layer / null derivative input");                                            \
+    return thermal_source_lin<T>(cvt_quad<T>(q), S, dtau, varpi, B, p_layer, dtau_dot, varpi_dot, cvt_added<T>(added), \
+                                 cvt_al<T>(al), as_stream(stream));                                                    \
+  }                                                                                                                    \
   int vsm_doubling_lin_##SFX(int N, int n_stokes, int S, int ndoubl, T* expk, const T* dtau_dot_all, T mu0,            \
                              int n_active, const vsm_added_##SFX* added, const vsm_added_lin_##SFX* al, T* work,       \
                              void* stream) {                                                                           \

@@ -78,6 +78,10 @@ int elemental_lin_mix(const quad<T>& q, int S, int m, int ndoubl, const T* dtau,
                       const T* F0, int ncomp, int ncomp_total, const T* Zc_pp, const T* Zc_mp, int zsel, const T* fz,
                       int p_layer, const T* dtau_dot, const T* varpi_dot, const T* tau_sum_dot, const T* zdcoef,
                       const added<T>& a, const added_lin<T>& al, hipStream_t st);
+// the linearized elemental thermal source: forward j0+- as thermal_source + ap_J0+- of the slots [0, p_layer), zero beyond
+template <typename T>
+int thermal_source_lin(const quad<T>& q, int S, const T* dtau, const T* varpi, const T* B, int p_layer, const T* dtau_dot,
+                       const T* varpi_dot, const added<T>& a, const added_lin<T>& al, hipStream_t st);
 template <typename T>
 size_t doubling_lin_work_elems(int N, int S, int P);
 template <typename T>

@@ -291,6 +291,51 @@ int elemental_lin_mix(const quad<T>& q, int S, int m, int ndoubl, const T* dtau,
 }
 
 // ---------------------------------------------------------------------------
+// linearized elemental thermal source (the `:thermal` slot of a linearized run; the reference has none:
+// rt_helper_functions_lin.jl:70).  Forward as k_thermal_source (vsm_generic.hip), with x = dtau / mu_i on the I rows
+//   j0+ = j0- = 2 pi (1 - varpi) B (1 - e^-x),   ap_J0+-[p] = 2 pi B [ -varpi_dot_p (1 - e^-x) + (1 - varpi) e^-x tau_dot_p / mu_i ]
+// for p < p_layer; zero on the Q/U/V rows and in every slot p >= p_layer.  One thread per (row, point): it reads the point's
+// dtau, varpi, B once and writes the 1 + P vectors, each store coalesced along the row axis (the contiguous one of [N,S,P]).
+// ---------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void k_thermal_source_lin(int N, int ns, int S, int p_layer, int P, const T* __restrict__ dtau,
+                                                            const T* __restrict__ varpi, const T* __restrict__ B,
+                                                            const T* __restrict__ dtau_dot, const T* __restrict__ varpi_dot,
+                                                            const T* __restrict__ mu, T* j0_p, T* j0_m, T* ap_J0_p, T* ap_J0_m) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  const long long VS = (long long)N * S;
+  if (e >= VS) return;
+  const int i = (int)(e % N);
+  const long long s = e / N;
+  const bool on = (i % ns == 0) && mu[i] > num<T>::eps();
+  T v = T(0), c_w = T(0), c_tau = T(0);
+  if (on) {
+    const T d = dtau[s], w = varpi[s], b = B[s], mi = mu[i];
+    v = T(6.283185307179586476925286766559) * (T(1) - w) * b * (-expm1(-d / mi));   // (k_thermal_source's expression: same bits)
+    c_w = T(6.283185307179586476925286766559) * b * (-expm1(-d / mi));
+    c_tau = T(6.283185307179586476925286766559) * b * (T(1) - w) * exp(-d / mi) / mi;
+  }
+  j0_p[e] = v;
+  j0_m[e] = v;
+  for (int p = 0; p < P; ++p) {
+    T a = T(0);
+    if (on && p < p_layer) a = c_tau * dtau_dot[s + (long long)S * p] - c_w * varpi_dot[s + (long long)S * p];
+    ap_J0_p[e + VS * p] = a;
+    ap_J0_m[e + VS * p] = a;
+  }
+}
+template <typename T>
+int thermal_source_lin(const quad<T>& q, int S, const T* dtau, const T* varpi, const T* B, int p_layer, const T* dtau_dot,
+                       const T* varpi_dot, const added<T>& a, const added_lin<T>& al, hipStream_t st) {
+  if (S <= 0) return VSM_OK;
+  const long long n = (long long)q.N * S;
+  hipLaunchKernelGGL(k_thermal_source_lin<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, q.N, q.n_stokes, S, p_layer,
+                     al.P, dtau, varpi, B, dtau_dot, varpi_dot, q.mu, a.j0_p, a.j0_m, al.ap_J0_p, al.ap_J0_m);
+  VSM_LAUNCH_CHECK("k_thermal_source_lin");
+  return VSM_OK;
+}
+
+// ---------------------------------------------------------------------------
 // doubling, all parameters (doubling_lin.jl:216-339)
 // ---------------------------------------------------------------------------
 template <typename T>
@@ -851,6 +896,8 @@ int postprocess_vza_lin(int N, int ns, int S, int nV, int P, const int* row0_h, 
   template int elemental_lin_mix<T>(const quad<T>&, int, int, int, const T*, const T*, const T*, const T*, int, int,   \
                                     const T*, const T*, int, const T*, int, const T*, const T*, const T*, const T*,     \
                                     const added<T>&, const added_lin<T>&, hipStream_t);                                 \
+  template int thermal_source_lin<T>(const quad<T>&, int, const T*, const T*, const T*, int, const T*, const T*,      \
+                                     const added<T>&, const added_lin<T>&, hipStream_t);                               \
   template int doubling_lin<T>(int, int, int, int, T*, const T*, T, int, const added<T>&, const added_lin<T>&, T*,   \
                                hipStream_t);                                                                          \
   template int interaction_lin<T>(int, int, int, const composite<T>&, const composite_lin<T>&, const added<T>&,      \

@@ -490,13 +490,25 @@ class ThermalEmission:
     the AddedLayer only in its scatter branch (rt_kernel.jl:217-221); a non-scattering layer therefore interacts with the doubled
     slot the last scattering layer before it left in place, and a column that BEGINS with non-scattering layers carries the slot
     of moment m = 0 into moment m = 1.  True selects the corrected variant (a non-scattering layer emits nothing and carries
-    nothing over)."""
+    nothing over).
 
-    def __init__(self, T_layers=None, nu=None, B_layer=None, reset_slot_in_nonscattering_layers: bool = False):
+    `B_layer_dot` [nPlanck, rows, nSpec] (default None; one [rows, nSpec] table counts as nPlanck = 1): the derivative tables
+    dB_layer / dx_k of nPlanck user parameters -- a temperature shift of the profile, a unit table per layer for weighting
+    functions, ...  Only the linearized run reads them (CoreRTLin.rt_run_lin: the Planck slots, appended after the surface
+    slots of Rdot / Tdot)."""
+
+    def __init__(self, T_layers=None, nu=None, B_layer=None, reset_slot_in_nonscattering_layers: bool = False, B_layer_dot=None):
         if B_layer is None and T_layers is not None:
             B_layer = np.stack([planck_spectrum_wn(float(T), nu) for T in T_layers])
         self.B_layer = None if B_layer is None else np.atleast_2d(np.asarray(B_layer, dtype=np.float64))
         self.reset_slot_in_nonscattering_layers = bool(reset_slot_in_nonscattering_layers)
+        if B_layer_dot is not None:
+            B_layer_dot = np.asarray(B_layer_dot, dtype=np.float64)
+            if B_layer_dot.ndim == 2:
+                B_layer_dot = B_layer_dot[None]
+            if B_layer_dot.ndim != 3:
+                raise ValueError("ThermalEmission: B_layer_dot must be [nPlanck, rows, nSpec], got %d dimensions" % B_layer_dot.ndim)
+        self.B_layer_dot = B_layer_dot
 
 
 @dataclass
