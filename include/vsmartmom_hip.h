@@ -940,6 +940,32 @@ int vsm_level_radiance_lin_f32(int N, int n_stokes, int S, int P, int P_top, int
                                long long bot_lin_pstride, const float* bot_J0_m_lin, float* uw_lin, float* dw_lin,
                                float* dw_lin_full, float* uw_lin_full, void* stream);
 
+/* vsm_level_radiance_lin_* with P_src >= 0 further SOURCE-ONLY slots behind the P parameter slots: the Planck (temperature) slots
+ * of a linearized multi-sensor run with thermal emission (vsmartmom.jl_amd/core_rt_ms_lin.py).  The level equation
+ * is linear in (a, c), so for a parameter x_k that enters through the sources alone, with a_k = d top_J0_p / dx_k = src_top_J0_p
+ * [N,1,S,P_src] and c_k = d bot_J0_m / dx_k = src_bot_J0_m [N,1,S,P_src] (the parameter axis slowest),
+ *   dw'_(P+k) = M^-1 (a_k + A c_k),   uw'_(P+k) = c_k + B dw'_(P+k)
+ * on the same M = I - A B; no operator derivative is read for such a slot.  Slots p < P exactly as in vsm_level_radiance_lin_*.
+ * Outputs: uw_lin / dw_lin [nV,n_stokes,S,P+P_src] ACCUMULATED, dw_lin_full / uw_lin_full (nullable) [N,1,S,P+P_src].  All
+ * P + P_src slots run in the chunks of vsm_level_radiance_lin_* as right-hand sides of ONE elimination per chunk; a chunk may hold
+ * both kinds.  N <= 128, 1 <= P, P + P_src <= 64, anything else is VSM_ERR_INVALID_ARG before any launch (P_src = 0: both source
+ * stacks may be NULL, and the outputs are the bits of vsm_level_radiance_lin_*: same system, same pivots, same order of
+ * additions).  Status words and pivot rule as there.  No work buffer. */
+int vsm_level_radiance_lin_src_f64(int N, int n_stokes, int S, int P, int P_top, int P_src, int nV, const int* row0_h,
+                                   const double* w_h, const double* top_R_pm, const double* bot_R_mp, long long bot_stride,
+                                   const double* dw_full, const double* uw_full, const double* top_R_pm_lin,
+                                   long long top_lin_pstride, const double* top_J0_p_lin, const double* bot_R_mp_lin,
+                                   long long bot_lin_stride, long long bot_lin_pstride, const double* bot_J0_m_lin,
+                                   const double* src_top_J0_p, const double* src_bot_J0_m, double* uw_lin, double* dw_lin,
+                                   double* dw_lin_full, double* uw_lin_full, void* stream);
+int vsm_level_radiance_lin_src_f32(int N, int n_stokes, int S, int P, int P_top, int P_src, int nV, const int* row0_h,
+                                   const float* w_h, const float* top_R_pm, const float* bot_R_mp, long long bot_stride,
+                                   const float* dw_full, const float* uw_full, const float* top_R_pm_lin,
+                                   long long top_lin_pstride, const float* top_J0_p_lin, const float* bot_R_mp_lin,
+                                   long long bot_lin_stride, long long bot_lin_pstride, const float* bot_J0_m_lin,
+                                   const float* src_top_J0_p, const float* src_bot_J0_m, float* uw_lin, float* dw_lin,
+                                   float* dw_lin_full, float* uw_lin_full, void* stream);
+
 /* ---- single-scattering runs: rt_run_ss (src/CoreRT/rt_run.jl:574-755) -----------------------------------------------------
  * One Fourier moment of the single-scattering column walk, all layers and the surface in ONE launch: per layer the exact
  * finite-tau sources of elemental! with ndoubl = 0 and dtau = the layer's tau (get_elem_rt_SFI!, CoreKernel/elemental.jl:348-392;

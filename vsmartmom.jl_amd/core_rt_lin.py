@@ -944,15 +944,20 @@ class SceneLin(LinInputs):
         if self.nPlanck:
             self._planck_block(mom)
 
-    def _thermal_lin_slot(self, mom):
-        model, pol, qp, FT, dt, fwd = self.model, self.pol, self.qp, self.FT, self.dt, self.fwd
-        N, S, P, pl = self.N, self.S, self.P, self.pl
+    def _thermal_lin_walk(self, mom, comp, cl, first, end, after_layer=None):
+        """Layers first+1 .. end (1-based) of the linearized slot into the thermal composite `comp` / `cl`, the first one a copy
+        (the linearized twin of Scene._thermal_walk: expk = 1 and no beam attenuation, so a range that starts below the TOA needs
+        no absolute tau_sum).  after_layer(l, comp, cl): called once layer l is in the composite (the multi-sensor run keeps its
+        thermal tops there, core_rt_ms_lin.py)."""
+        pol, qp, dt, fwd = self.pol, self.qp, self.dt, self.fwd
+        N, S, pl = self.N, self.S, self.pl
         t = self._thermal_state()
-        added, al, comp, cl = t["added"], t["al"], t["comp"], t["cl"]
+        added, al = t["added"], t["al"]
         q_ = self.dq.cstruct()
         m = mom["m"]
-        rows = fwd.thermal_B.shape[0]
-        for iz, ly in enumerate(mom["layers"]):
+        rows = fwd.thermal_B.shape[0] if fwd.thermal_B is not None else 0
+        for iz in range(first, end):
+            ly = mom["layers"][iz]
             props = ly["props"]
             dtd, vd, tsd = self.dtau_dot_all[iz], self.varpi_dot[iz], self.tau_sum_dot[iz]
             a_, al_ = added.cstruct(), al.cstruct()
@@ -972,16 +977,36 @@ class SceneLin(LinInputs):
                           CR._ptr(fwd.thermal_B[iz]), pl, CR._ptr(dtd), CR._ptr(vd), C.byref(a_), C.byref(al_), CR._stream_ptr())
             t["ones"].fill_(1.0)    # the slot's expk = 1 (the doubling kernels square it in place); zero_dtd: ekl = 0
             doubling_allparams_(pol, t["ones"], ly["nd"], added, al, t["zero_dtd"], qp.mu0, pl)
-            if iz == 0:
+            if iz == first:
                 CR.copy_added_to_composite_(comp, added)
                 c_ = cl.cstruct()
                 _lib.call("vsm_copy_added_to_composite_lin", dt, N, S, C.byref(al_), C.byref(c_), CR._stream_ptr())
             else:
                 interaction_lin_(ly["iface"], comp, cl, added, al, p_range=self._layer_slots)
-        # the surface layer of the solar walk without its beam terms (surface emission is a separate source type)
+            if after_layer is not None:
+                after_layer(iz + 1, comp, cl)
+
+    def _thermal_lin_surface(self, mom):
+        """The slot's surface layers: those of the solar walk without their beam terms (surface emission is a separate source
+        type)."""
+        t = self._thermal_state()
         self._surface_lin(mom, t["added_s"], t["als"], t["F0"])
         torch._foreach_zero_([t["added_s"].j0_p, t["added_s"].j0_m, t["als"].ap_J0_p, t["als"].ap_J0_m])
-        interaction_lin_(mom["iface_surface"], comp, cl, t["added_s"], t["als"])
+        return t["added_s"], t["als"]
+
+    def _thermal_lin_slot(self, mom, after_layer=None, post=True):
+        """Walk layers 1 .. Nz (_thermal_lin_walk), surface, post-process into R, T, Rdot, Tdot (post=False: the composite is left
+        after its surface interaction and nothing is added to the outputs)."""
+        model, pol, qp, FT, dt = self.model, self.pol, self.qp, self.FT, self.dt
+        N, S, P = self.N, self.S, self.P
+        t = self._thermal_state()
+        comp, cl = t["comp"], t["cl"]
+        m = mom["m"]
+        self._thermal_lin_walk(mom, comp, cl, 0, len(mom["layers"]), after_layer)
+        added_s, als = self._thermal_lin_surface(mom)
+        interaction_lin_(mom["iface_surface"], comp, cl, added_s, als)
+        if not post:
+            return
         weight = FT(0.5 / math.pi)
         CR.postprocessing_vza_(pol, comp, model.vza, model.vaz, qp, m, float(weight), self.R, self.T)
         row0, wts = _pp_args(pol, qp, model.vza, model.vaz, m, weight, dt)

@@ -19,6 +19,13 @@ the layers above it.  Per Fourier moment, on one stream:
 
 Per moment: Nz + (Nz - l_1) linearized layer steps, L + 1 further linearized interactions (L interior levels) and one elastic and one
 linearized level call per level other than 0.
+
+With a ThermalEmission source the `:thermal` per-source slot of rt_run_lin and its Planck slots follow the solar
+moments, for m = 0 alone (_run_thermal): the same four steps on the slot's own linearized composites (SceneLin._thermal_lin_walk:
+expk = 1, so a segment needs no tau_sum) and, per Planck table, on the forward thermal composites of Scene._thermal_walk, of which
+only the source vectors J0+ (top) and J0- (bottom) are kept.  The slot solves its level equation on ITS OWN operators, not on the
+solar ones as the forward run does (§4.8d): the solar m = 0 may have run as a Stokes_IQ sub-scene at another N.  Per level other
+than 0: one elastic call on the thermal composites and ONE vsm_level_radiance_lin_src_* call for all Nparams + nPlanck slots.
 """
 from __future__ import annotations
 
@@ -59,13 +66,34 @@ def level_radiance_lin_(pol, qp, vza, vaz, m: int, weight: float, P: int, P_top:
               CR._stream_ptr())
 
 
+def level_radiance_lin_src_(pol, qp, vza, vaz, m: int, weight: float, P: int, P_top: int, top_R_pm, bot_R_mp, dw_full, uw_full,
+                            top_R_pm_lin, top_J0_p_lin, bot_R_mp_lin, bot_J0_m_lin, src_top_J0_p, src_bot_J0_m, uw_lin, dw_lin,
+                            dw_lin_full=None, uw_lin_full=None):
+    """level_radiance_lin_ with P_src source-only slots behind the P parameter slots (vsm_level_radiance_lin_src_*): for slot
+    P + k, dw' = (I - A B)^-1 (a_k + A c_k), uw' = c_k + B dw', a_k = src_top_J0_p[k], c_k = src_bot_J0_m[k] ((P_src, S, N)
+    tensors, or None for P_src = 0).  uw_lin / dw_lin (P + P_src, S, n, nV), dw_lin_full / uw_lin_full (P + P_src, S, N)."""
+    setup = MS.level_call_setup(pol, qp, vza, vaz, m, weight, dw_full, bot_R_mp)
+    if setup is None:
+        return
+    S, N, dt, row0, w, bot_stride = setup
+    sb = int(bot_R_mp_lin.shape[1])
+    bd_stride = 0 if sb == 1 and S > 1 else N * N
+    P_src = 0 if src_top_J0_p is None else int(src_top_J0_p.shape[0])
+    Pt = CR._ptr
+    _lib.call("vsm_level_radiance_lin_src", dt, N, pol.n, S, int(P), int(P_top), P_src, len(vza), row0, w, Pt(top_R_pm), Pt(bot_R_mp),
+              bot_stride, Pt(dw_full), Pt(uw_full), Pt(top_R_pm_lin) if P_top else None, S * N * N,
+              Pt(top_J0_p_lin) if P_top else None, Pt(bot_R_mp_lin), bd_stride, sb * N * N, Pt(bot_J0_m_lin),
+              Pt(src_top_J0_p) if P_src else None, Pt(src_bot_J0_m) if P_src else None, Pt(uw_lin), Pt(dw_lin), Pt(dw_lin_full),
+              Pt(uw_lin_full), CR._stream_ptr())
+
+
 @dataclass
 class MultiSensorLinResult(MS.MultiSensorResult):
     """rt_run_multisensor(model, lin_model, ..., streams=True): per entry of sensor_levels the VZA outputs and their Jacobians and,
     per Fourier moment, the level vectors and their derivatives at ALL quadrature streams: the fields of MultiSensorResult and"""
-    uw_dot: List[np.ndarray]                # [nVZA, nStokes, nSpec, Nparams] per level
+    uw_dot: List[np.ndarray]                # [nVZA, nStokes, nSpec, Nparams (+ nPlanck)] per level
     dw_dot: List[np.ndarray]
-    uw_dot_streams: List[List[np.ndarray]]  # [level][moment] -> [N, 1, nSpec, Nparams]
+    uw_dot_streams: List[List[np.ndarray]]  # [level][moment] -> [N, 1, nSpec, Nparams (+ nPlanck)]
     dw_dot_streams: List[List[np.ndarray]]
 
     FIELDS = ("uw", "dw", "uw_dot", "dw_dot")
@@ -82,7 +110,9 @@ def _run_scene(sc: CL.SceneLin, plan: MS.LevelPlan, streams: bool):
     dev = sc.R.device
     nV = len(model.vza)
     z = lambda *sh: torch.zeros(sh, dtype=dt, device=dev)
-    out = {l: [z(S, pol.n, nV), z(S, pol.n, nV), z(P, S, pol.n, nV), z(P, S, pol.n, nV)] for l in plan.distinct if l != 0}
+    thermal = sc.fwd.thermal_B is not None or sc.nPlanck > 0
+    Pa = P + sc.nPlanck      # (the Planck slots follow the parameter slots; the solar level calls fill the first P)
+    out = {l: [z(S, pol.n, nV), z(S, pol.n, nV), z(Pa, S, pol.n, nV), z(Pa, S, pol.n, nV)] for l in plan.distinct if l != 0}
     out[0] = [sc.R, sc.T, sc.Rd, sc.Td]
     full = {} if streams else None
     weights = [float(MS.fourier_weight(FT, m)) for m in range(model.m_max + 1)]
@@ -90,7 +120,8 @@ def _run_scene(sc: CL.SceneLin, plan: MS.LevelPlan, streams: bool):
         return out, full, weights
     reduced = sc.sub0 is not None
     if reduced:      # m = 0 first, like SceneLin.run
-        MS.merge_sub0(_run_scene(sc.sub0, plan, streams), pol.n, out, full)
+        MS.merge_sub0(_run_scene(sc.sub0, plan, streams), pol.n,
+                      {l: o[:2] + [o[2][:P], o[3][:P]] for l, o in out.items()} if thermal else out, full)
     segs = [(CR.make_composite_layer(FT, sc.arch, (N, N), S), CL.CompositeLayerLin(FT, sc.arch, P, N, S))
             for _ in range(2 if plan.interior else 0)]
     for mom in fwd.moments:
@@ -138,16 +169,112 @@ def _run_scene(sc: CL.SceneLin, plan: MS.LevelPlan, streams: bool):
                                                                         CL._CompositeLinAsAdded(bot[1])), level)
         if streams:
             full[m] = fv
+    if thermal:
+        _run_thermal(sc, plan, segs, out, full)
     return out, full, weights
 
 
+def _run_thermal(sc: CL.SceneLin, plan: MS.LevelPlan, segs, out, full):
+    """The `:thermal` slot and the Planck slots of a linearized multi-sensor run (m = 0), after the solar moments, in the order
+    of SceneLin._run_thermal at level 0 (its R, T, Rdot, Tdot bit for bit).  segs: the two segment composites of the solar walk,
+    free by now.  The Planck sources come first: their vectors a_k, c_k of every level are kept ((K, S, N) each), the operators of
+    those forward walks are not read; then the linearized slot, whose bottoms live only until the level above has used them."""
+    model, fwd, dt = sc.model, sc.fwd, sc.dt
+    pol, qp = sc.pol, sc.qp
+    N, S, P, pl, K = sc.N, sc.S, sc.P, sc.pl, sc.nPlanck
+    dev = sc.R.device
+    mom = fwd.moments[0]
+    weight = float(MS.fourier_weight(sc.FT, 0))
+    CL._lane = 0
+    new = lambda *sh: torch.empty(sh, dtype=dt, device=dev)
+    below = [l for l in plan.distinct if l != 0]
+    src = {l: (torch.zeros((K, S, N), dtype=dt, device=dev), torch.zeros((K, S, N), dtype=dt, device=dev)) for l in below} if K else {}
+    fv = None
+    if full is not None:      # the solar level vectors of m = 0 (the sub-scene's, expanded), their derivative stacks padded to P + K
+        pad = (lambda v: torch.cat([v, torch.zeros((K,) + tuple(v.shape[1:]), dtype=dt, device=dev)])) if K else (lambda v: v)
+        for m_, f in full.items():
+            full[m_] = {l: (vs[0], vs[1], pad(vs[2]), pad(vs[3])) for l, vs in f.items()}
+        fv = full[0]
+    # 4. the Planck sources: per table the forward slot of B := B_layer_dot[k], cut at the plan's levels as DESIGN 4.8d cuts it
+    if K:
+        th_segs = [CR.make_composite_layer(sc.FT, sc.arch, (N, N), S) for _ in range(2 if plan.interior else 0)]
+        B0 = fwd.thermal_B
+        try:
+            for k in range(K):
+                fwd.thermal_B = sc.thermal_B_dot[k]
+                fwd._thermal_begin(mom)
+                comp = fwd._th_comp
+                fwd._thermal_walk(mom, comp, 0, fwd.Nz,
+                                  after={l: (lambda c, l=l: src[l][0][k].copy_(c.J0_p)) for l in plan.tops_at})
+                surf = fwd._thermal_surface(mom)
+
+                def keep_bottom(l, seg):
+                    if seg is not None:      # (level Nz: the surface layer alone emits nothing, c_k = 0)
+                        src[l][1][k].copy_(seg.J0_m)
+                MS.walk_levels(plan, th_segs, lambda seg, first, end: fwd._thermal_walk(mom, seg, first, end),
+                               lambda seg: CR.interaction_(mom["iface_surface"], seg, surf, oplevel=True, work=fwd.work),
+                               lambda seg, bot, first, end: CR.interaction_("11", seg, MS._CompositeAsAdded(bot), oplevel=True,
+                                                                            work=fwd.work), keep_bottom)
+                CR.interaction_(mom["iface_surface"], comp, surf, oplevel=True, work=fwd.work)
+                CR.postprocessing_vza_(pol, comp, model.vza, model.vaz, qp, 0, weight, sc.Rd[P + k], sc.Td[P + k])
+                if fv is not None:
+                    fv[0][2][P + k].copy_(comp.J0_m)
+                    fv[0][3][P + k].copy_(comp.J0_p)
+        finally:
+            fwd.thermal_B = B0
+            for c in th_segs:
+                c.drop_native()
+    # 1. the top pass of the linearized slot and level 0 (B_layer = 0 with Planck tables: SceneLin.run adds no slot, the walk
+    # still supplies the operators the Planck slots are solved on)
+    tops = {}
+
+    def keep(l, comp, cl):
+        if l in plan.tops_at:
+            tops[l] = (comp.R_pm.clone(), comp.J0_p.clone(), cl.R_pm[:pl].clone(), cl.J0_p[:pl].clone())
+    sc._thermal_lin_slot(mom, after_layer=keep, post=fwd.thermal_B is not None)
+    t = sc._thermal_state()
+    asurf, als = t["added_s"], t["als"]
+    if fv is not None and fwd.thermal_B is not None:
+        fv[0][0].add_(t["comp"].J0_m)
+        fv[0][1].add_(t["comp"].J0_p)
+        fv[0][2][:P].add_(t["cl"].J0_m)
+        fv[0][3][:P].add_(t["cl"].J0_p)
+
+    def level(l, seg):
+        top = tops.pop(l)
+        bot = (asurf.r_mp, asurf.j0_m, als.ap_r_mp, als.ap_J0_m) if seg is None else (seg[0].R_mp, seg[0].J0_m, seg[1].R_mp,
+                                                                                      seg[1].J0_m)
+        dwf, uwf = new(S, N), new(S, N)
+        MS.level_radiance_(pol, qp, model.vza, model.vaz, 0, weight, top[0], top[1], bot[0], bot[1], out[l][0], out[l][1], dwf, uwf)
+        dwd, uwd = (new(P + K, S, N), new(P + K, S, N)) if fv is not None else (None, None)
+        a_k, c_k = src[l] if K else (None, None)
+        level_radiance_lin_src_(pol, qp, model.vza, model.vaz, 0, weight, P, pl, top[0], bot[0], dwf, uwf, top[2], top[3], bot[2],
+                                bot[3], a_k, c_k, out[l][2], out[l][3], dwd, uwd)
+        if fv is not None:
+            for acc, v in zip(fv[l], (uwf, dwf, uwd, dwd)):
+                acc.add_(v)
+    # 2.-4. the slot's segments and bottoms from the surface up, the two level calls of each level
+    MS.walk_levels(plan, segs, lambda seg, first, end: sc._thermal_lin_walk(mom, seg[0], seg[1], first, end),
+                   lambda seg: CL.interaction_lin_(mom["iface_surface"], seg[0], seg[1], asurf, als),
+                   lambda seg, bot, first, end: CL.interaction_lin_("11", seg[0], seg[1], CL._CompositeAsAdded(bot[0]),
+                                                                    CL._CompositeLinAsAdded(bot[1])), level)
+
+
 def bytes_per_point(N: int, P: int, pl: int, Nz: int, n_tops: int, segments: bool, n_levels: int, n_stokes: int, nV: int,
-                    itemsize: int) -> int:
+                    itemsize: int, thermal: bool = False, nPlanck: int = 0) -> int:
     """Device bytes per spectral point of a linearized multi-sensor run (an estimate on the safe side): the kept tops, the two
-    segment composites, the scene's own added / composite / surface layers, its per-layer optics and the outputs."""
+    segment composites, the scene's own added / composite / surface layers, its per-layer optics and the outputs.  thermal: what
+    the thermal slot keeps beside them (m = 0 only, on the parent's N): its own tops, R and Rdot included ((1 + pl)(N^2 + N) each,
+    while the solar tops of the last moment are still alive), its linearized added / composite / surface layers, the forward
+    slot's three layers and two segment composites (the Planck walks), the Planck source vectors of every level, the Planck
+    slots of the outputs and the padded level vectors."""
     layer = (1 + P) * (4 * N * N + 2 * N)
     elems = (n_tops * (1 + pl) * (N * N + N) + (2 * layer if segments else 0) + 3 * layer + Nz * (8 + 3 * P)
              + n_levels * 2 * (1 + P) * n_stokes * nV + 4 * (1 + P) * N)
+    if thermal:
+        fwd_layer = 4 * N * N + 2 * N
+        elems += (n_tops * (1 + pl) * (N * N + N) + 3 * layer + (5 if segments else 3) * fwd_layer * (1 if nPlanck else 0)
+                  + n_levels * 2 * nPlanck * (N + n_stokes * nV) + Nz * (1 + nPlanck) + 4 * (1 + P + nPlanck) * N)
     return elems * itemsize
 
 
@@ -166,8 +293,24 @@ def rt_run_multisensor(model: H.RTModel, lin_model: H.LinModel, NAer: int, NGas:
     moment.  max_points: run the spectral axis in blocks of about that many points (bit-identical to one pass: points are
     independent, ndoubl and the interface tags come from the full axis; a block has at least SceneLin.LANE_POINTS points where the
     axis has, so that the m = 0 sub-scene applies alike); None = as many as fit the device.
-    SolarBeam sources only; columns with a non-scattering layer raise NotImplementedError; N <= 128."""
-    plan = MS._validate(model, sensor_levels)
+    Sources: model.sources may hold SolarBeam and / or ThermalEmission(B_layer=..., B_layer_dot=...), by rt_run_lin's rule
+    (without a SolarBeam F0 = 0).  The source must state B_layer_dot ([0, rows, nSpec] for no Planck slot): this run has no
+    `thermal=` keyword, and a ThermalEmission with B_layer_dot = None stays refused with a VSMError, as before.  uw / dw per level are then the sum of the solar and the `:thermal` slot, as in
+    CoreRT.rt_run_multisensor(thermal=True); uw_dot / dw_dot are [nVZA, nStokes, nSpec, Nparams + nPlanck]: every slot below Nparams
+    is the sum of the solar and the thermal derivative, slot Nparams + k is d/dx_k for B_layer_dot[k] (the thermal part alone),
+    after the surface slots as rt_run_lin places them; Nparams + nPlanck <= 64.  The slot exists for m = 0 only; with
+    streams=True the derivative level vectors of every moment carry all Nparams + nPlanck slots (zero Planck slots for m > 0).
+    Level 0 is again SceneLin.run(lanes=1, fold=False) bit for bit.  No surface emission.  DESIGN.md §4.8e.
+
+    Columns with a non-scattering layer raise NotImplementedError; N <= 128."""
+    plan = MS._validate(model, sensor_levels, thermal=True)
+    # There is no `thermal=` keyword here: a ThermalEmission opts into this run by stating its Planck tables ([0, rows, nSpec] for
+    # none).  One that leaves B_layer_dot at None is a forward-only source and is refused as it always was (DESIGN 4.8e "Opt-in").
+    fwd_only = [s_ for s_ in (model.sources or ()) if isinstance(s_, H.ThermalEmission) and getattr(s_, "B_layer_dot", None) is None]
+    if fwd_only:
+        raise _lib.VSMError("rt_run_multisensor (linearized): SolarBeam is the only source of this run beside a ThermalEmission that "
+                            "states its Planck tables, B_layer_dot = [nPlanck, rows, nSpec] (nPlanck = 0: no Planck slot); "
+                            "got %r with B_layer_dot = None" % (fwd_only[0],))
     qp, pol = model.quad_points, model.polarization_type
     N = qp.Nquad * pol.n
     if N > LEVEL_LIN_MAX_N:
@@ -178,7 +321,11 @@ def rt_run_multisensor(model: H.RTModel, lin_model: H.LinModel, NAer: int, NGas:
         layout = H.ParameterLayout(n_aerosols=NAer, n_gases=NGas, n_surface=NSurf)
         P, pl = layout.n_total, layout.n_layer_params
         isz, nV = np.dtype(model.float_type).itemsize, len(model.vza)
-        per = bytes_per_point(N, P, pl, plan.Nz, plan.n_tops, bool(plan.interior), len(plan.distinct), pol.n, nV, isz)
+        th = [s_ for s_ in (model.sources or ()) if isinstance(s_, H.ThermalEmission)]
+        kw = {}
+        if th:     # (a model without the source takes the call as it always was)
+            kw = dict(thermal=True, nPlanck=int(th[0].B_layer_dot.shape[0]))
+        per = bytes_per_point(N, P, pl, plan.Nz, plan.n_tops, bool(plan.interior), len(plan.distinct), pol.n, nV, isz, **kw)
         if CL.REDUCE_M0 and pol.n >= 3:     # (the Stokes_IQ scene of m = 0, where it applies)
             per += bytes_per_point(2 * qp.Nquad, P, pl, plan.Nz, plan.n_tops, bool(plan.interior), len(plan.distinct), 2, nV, isz)
         free, _total = torch.cuda.mem_get_info()

@@ -15,7 +15,8 @@
 // vsm_level_radiance_ie_*: the first-order (Raman) part of the same equation, interlayer_flux_helper!(::RRS) (interlayer_flux.jl:
 // 21-77), per recipient point with the lines summed before ONE solve of the same [I - A B | r] (k_level_radiance_ie, below).
 // vsm_level_radiance_lin_*: its derivative with respect to the Jacobian parameters, the parameters as extra right-hand sides of
-// ONE solve per chunk (k_level_radiance_lin, below).
+// ONE solve per chunk (k_level_radiance_lin, below).  vsm_level_radiance_lin_src_*: the same with P_src further SOURCE-ONLY slots
+// (the Planck slots of a linearized multi-sensor run with thermal emission), one body (level_lin_body, k_level_radiance_lin_src).
 // vsm_level_radiance_src_*: the same equation for up to VSM_LEVEL_MAX_SRC source pairs (a_k, c_k) on the same A, B (the solar and
 // the thermal slot), the pairs as right-hand sides of ONE solve, their level vectors summed (k_level_radiance_src, below).
 #include "vsm_common.h"
@@ -425,14 +426,21 @@ static int level_radiance_ie_fused(int N, int ns, int S, int K, const int* shift
 //      (level_eliminate: same M, same rule as the elastic call, hence its pivots);
 //   3. dw'_p = column / m_ii (in place), uw'_p = q_p + B dw'_p (into Q), the VZA rows ACCUMULATED into [P, S, n_stokes, nV].
 // LDS: L [N][N + PC], Q [PC][N], dw / uw [2][N], partial sums [2][G][N].
-template <typename T>
-__global__ void __launch_bounds__(LEVEL_NT) k_level_radiance_lin(int N, int ns, int S, int P, int P_top, int PC, int nV, level_pp pa,
-                                                                 const T* __restrict__ A, const T* __restrict__ B, long long bstride,
-                                                                 const T* __restrict__ dwf, const T* __restrict__ uwf,
-                                                                 const T* __restrict__ Ad, long long ad_pstride,
-                                                                 const T* __restrict__ ad, const T* __restrict__ Bd,
-                                                                 long long bd_stride, long long bd_pstride, const T* __restrict__ cd,
-                                                                 T* uwd, T* dwd, T* dwd_full, T* uwd_full, int* status) {
+// SRC: P_src further slots p = P .. P + P_src - 1 that carry a SOURCE alone (vsm_level_radiance_lin_src_*: the equation is linear
+// in (a, c), so the derivative with respect to a parameter that only scales the sources is the level equation of those sources):
+//   q_p = c_k,   r_p = a_k + A c_k,   dw'_p = (I - A B)^-1 r_p,   uw'_p = c_k + B dw'_p        (k = p - P)
+// a_k = asrc [N,1,S,P_src], c_k = csrc likewise.  Such a slot reads no operator derivative: step 1 copies c_k into Q[pc] and a_k into
+// column N + pc of L, and steps 2-3 do not tell the two kinds apart (the c_k ride as spare columns of B like every q_p), so a chunk
+// may mix them.  SRC = false is k_level_radiance_lin as it was, statement for statement; SRC = true with P_src = 0 issues the same
+// arithmetic in the same order (one more barrier per chunk).
+template <typename T, bool SRC>
+__device__ __forceinline__ void level_lin_body(int N, int ns, int S, int P, int P_top, int P_src, int PC, int nV, const level_pp& pa,
+                                               const T* __restrict__ A, const T* __restrict__ B, long long bstride,
+                                               const T* __restrict__ dwf, const T* __restrict__ uwf, const T* __restrict__ Ad,
+                                               long long ad_pstride, const T* __restrict__ ad, const T* __restrict__ Bd,
+                                               long long bd_stride, long long bd_pstride, const T* __restrict__ cd,
+                                               const T* __restrict__ asrc, const T* __restrict__ csrc, T* uwd, T* dwd, T* dwd_full,
+                                               T* uwd_full, int* status) {
   extern __shared__ __align__(16) unsigned char lds_raw[];
   const int LD = N + PC;
   T* L = reinterpret_cast<T*>(lds_raw);          // [M | r_1 .. r_PC], row-major, leading dimension N + PC
@@ -451,13 +459,22 @@ __global__ void __launch_bounds__(LEVEL_NT) k_level_radiance_lin(int N, int ns, 
     xs[i] = dwf[s * N + i];
     ys[i] = uwf[s * N + i];
   }
-  for (int p0 = 0; p0 < P; p0 += PC) {
-    const int pc_n = P - p0 < PC ? P - p0 : PC;
+  const int Ptot = SRC ? P + P_src : P;
+  for (int p0 = 0; p0 < Ptot; p0 += PC) {
+    const int pc_n = Ptot - p0 < PC ? Ptot - p0 : PC;
     if (tid == 0) sh[1] = 0;
     __syncthreads();   // (dw / uw loaded; the previous chunk's outputs read L and Q)
     // 1. q_p and s_p of the chunk
     for (int pc = 0; pc < pc_n; ++pc) {
       const int p = p0 + pc;
+      if (SRC && p >= P) {   // a source-only slot (the whole workgroup takes this branch together)
+        const long long o = (long long)(p - P) * SN + s * N;
+        for (int i = tid; i < N; i += LEVEL_NT) {
+          Q[pc * N + i] = csrc[o + i];
+          L[i * LD + N + pc] = asrc[o + i];
+        }
+        continue;
+      }
       const bool top = p < P_top;
       level_sums<T> acc = {T(0), T(0)};
       if (g < G)
@@ -465,6 +482,7 @@ __global__ void __launch_bounds__(LEVEL_NT) k_level_radiance_lin(int N, int ns, 
                                    top ? Ad + p * ad_pstride + s * NN : nullptr, top ? ad + p * SN + s * N : nullptr, ys, acc);
       level_stream_reduce<T>(N, G, g, i1, acc, part, Q + pc * N, 1, L + N + pc, LD);
     }
+    if (SRC) __syncthreads();   // (a chunk may end with source-only slots, which end without a barrier)
     // 2. [M | r] and its elimination
     const int NC = N + pc_n;
     level_form_system<T>(N, NC, LD, As, Bs, Q, L, sh, status);
@@ -495,6 +513,32 @@ __global__ void __launch_bounds__(LEVEL_NT) k_level_radiance_lin(int N, int ns, 
   }
 }
 
+template <typename T>
+__global__ void __launch_bounds__(LEVEL_NT) k_level_radiance_lin(int N, int ns, int S, int P, int P_top, int PC, int nV, level_pp pa,
+                                                                 const T* __restrict__ A, const T* __restrict__ B, long long bstride,
+                                                                 const T* __restrict__ dwf, const T* __restrict__ uwf,
+                                                                 const T* __restrict__ Ad, long long ad_pstride,
+                                                                 const T* __restrict__ ad, const T* __restrict__ Bd,
+                                                                 long long bd_stride, long long bd_pstride, const T* __restrict__ cd,
+                                                                 T* uwd, T* dwd, T* dwd_full, T* uwd_full, int* status) {
+  level_lin_body<T, false>(N, ns, S, P, P_top, 0, PC, nV, pa, A, B, bstride, dwf, uwf, Ad, ad_pstride, ad, Bd, bd_stride, bd_pstride,
+                           cd, nullptr, nullptr, uwd, dwd, dwd_full, uwd_full, status);
+}
+
+template <typename T>
+__global__ void __launch_bounds__(LEVEL_NT) k_level_radiance_lin_src(int N, int ns, int S, int P, int P_top, int P_src, int PC, int nV,
+                                                                     level_pp pa, const T* __restrict__ A, const T* __restrict__ B,
+                                                                     long long bstride, const T* __restrict__ dwf,
+                                                                     const T* __restrict__ uwf, const T* __restrict__ Ad,
+                                                                     long long ad_pstride, const T* __restrict__ ad,
+                                                                     const T* __restrict__ Bd, long long bd_stride,
+                                                                     long long bd_pstride, const T* __restrict__ cd,
+                                                                     const T* __restrict__ asrc, const T* __restrict__ csrc, T* uwd,
+                                                                     T* dwd, T* dwd_full, T* uwd_full, int* status) {
+  level_lin_body<T, true>(N, ns, S, P, P_top, P_src, PC, nV, pa, A, B, bstride, dwf, uwf, Ad, ad_pstride, ad, Bd, bd_stride,
+                          bd_pstride, cd, asrc, csrc, uwd, dwd, dwd_full, uwd_full, status);
+}
+
 // Parameters per chunk of k_level_radiance_lin: as many as the LDS holds (160 KiB less room for the static words), at most P
 template <typename T>
 static int level_lin_chunk(int N, int P) {
@@ -523,6 +567,32 @@ static int level_radiance_lin_fused(int N, int ns, int S, int P, int P_top, int 
         return (int)VSM_OK;
       },
       [&](const T* uf, const T* df) { return postprocess_vza_lin<T>(N, ns, S, nV, P, row0_h, w_h, uf, df, uwd, dwd, st); });
+}
+
+// vsm_level_radiance_lin_src_*: the chunks of level_lin_chunk over all P + P_src slots, the same LDS layout and bound
+template <typename T>
+static int level_radiance_lin_src_fused(int N, int ns, int S, int P, int P_top, int P_src, int nV, const int* row0_h, const T* w_h,
+                                        const T* A, const T* B, long long bstride, const T* dwf, const T* uwf, const T* Ad,
+                                        long long ad_pstride, const T* ad, const T* Bd, long long bd_stride, long long bd_pstride,
+                                        const T* cd, const T* asrc, const T* csrc, T* uwd, T* dwd, T* dwd_full, T* uwd_full,
+                                        hipStream_t st) {
+  int* status = device_status();
+  if (!status) return VSM_ERR_HIP;
+  const int Ptot = P + P_src;
+  const int PC = level_lin_chunk<T>(N, Ptot);
+  const size_t lds = ((size_t)N * (N + PC) + (size_t)PC * N + 2 * (size_t)N + 2 * (size_t)LEVEL_NT) * sizeof(T);
+  const int rc =
+      ensure_dyn_lds(reinterpret_cast<const void*>(k_level_radiance_lin_src<T>), lds, "hipFuncSetAttribute(k_level_radiance_lin_src)");
+  if (rc) return rc;
+  return level_launch<T>(
+      ns, nV, row0_h, w_h, (size_t)Ptot * N * S, dwd_full, uwd_full, st,
+      [&](int nv, const level_pp& pa, T* df, T* uf) {
+        hipLaunchKernelGGL(k_level_radiance_lin_src<T>, dim3(S), dim3(LEVEL_NT), lds, st, N, ns, S, P, P_top, P_src, PC, nv, pa, A, B,
+                           bstride, dwf, uwf, Ad, ad_pstride, ad, Bd, bd_stride, bd_pstride, cd, asrc, csrc, uwd, dwd, df, uf, status);
+        VSM_LAUNCH_CHECK("k_level_radiance_lin_src");
+        return (int)VSM_OK;
+      },
+      [&](const T* uf, const T* df) { return postprocess_vza_lin<T>(N, ns, S, nV, Ptot, row0_h, w_h, uf, df, uwd, dwd, st); });
 }
 
 // operator-level twin: M = I - A B, d = a + A c (two batched products), dw = M^-1 d (vsm_batch_inv + product), uw = c + B dw
@@ -604,6 +674,14 @@ static int level_lin_check(int N, int ns, int S, int P, int P_top, int nV, const
               "level_radiance_lin: a per-parameter stride is shorter than one parameter's blocks");
   VSM_REQUIRE(S == 0 || (A && B && dwf && uwf && Bd && cd), "level_radiance_lin: null operand");
   VSM_REQUIRE(S == 0 || P_top == 0 || (Ad && ad), "level_radiance_lin: null top derivative operand");
+  return VSM_OK;
+}
+
+template <typename T>
+static int level_lin_src_check(int P, int P_src, int S, const T* asrc, const T* csrc) {
+  VSM_REQUIRE(P_src >= 0 && P + P_src <= 64, "level_radiance_lin_src: bad slot count (P %d + P_src %d, P_src >= 0, at most 64 in all)", P,
+              P_src);
+  VSM_REQUIRE(S == 0 || P_src == 0 || (asrc && csrc), "level_radiance_lin_src: null source operand");
   return VSM_OK;
 }
 
@@ -690,5 +768,26 @@ VSM_LEVEL_IE_API(float, f32)
   }
 VSM_LEVEL_LIN_API(double, f64)
 VSM_LEVEL_LIN_API(float, f32)
+
+#define VSM_LEVEL_LIN_SRC_API(T, SFX)                                                                                          \
+  int vsm_level_radiance_lin_src_##SFX(int N, int n_stokes, int S, int P, int P_top, int P_src, int nV, const int* row0_h,    \
+                                       const T* w_h, const T* top_R_pm, const T* bot_R_mp, long long bot_stride,              \
+                                       const T* dw_full, const T* uw_full, const T* top_R_pm_lin, long long top_lin_pstride,  \
+                                       const T* top_J0_p_lin, const T* bot_R_mp_lin, long long bot_lin_stride,                \
+                                       long long bot_lin_pstride, const T* bot_J0_m_lin, const T* src_top_J0_p,               \
+                                       const T* src_bot_J0_m, T* uw_lin, T* dw_lin, T* dw_lin_full, T* uw_lin_full,           \
+                                       void* stream) {                                                                        \
+    int rc = level_lin_check<T>(N, n_stokes, S, P, P_top, nV, row0_h, w_h, top_R_pm, bot_R_mp, bot_stride, dw_full, uw_full,  \
+                                top_R_pm_lin, top_lin_pstride, top_J0_p_lin, bot_R_mp_lin, bot_lin_stride, bot_lin_pstride,   \
+                                bot_J0_m_lin, uw_lin, dw_lin);                                                                \
+    if (!rc) rc = level_lin_src_check<T>(P, P_src, S, src_top_J0_p, src_bot_J0_m);                                            \
+    if (rc || S == 0) return rc;                                                                                              \
+    return level_radiance_lin_src_fused<T>(N, n_stokes, S, P, P_top, P_src, nV, row0_h, w_h, top_R_pm, bot_R_mp, bot_stride,  \
+                                           dw_full, uw_full, top_R_pm_lin, top_lin_pstride, top_J0_p_lin, bot_R_mp_lin,       \
+                                           bot_lin_stride, bot_lin_pstride, bot_J0_m_lin, src_top_J0_p, src_bot_J0_m, uw_lin, \
+                                           dw_lin, dw_lin_full, uw_lin_full, as_stream(stream));                              \
+  }
+VSM_LEVEL_LIN_SRC_API(double, f64)
+VSM_LEVEL_LIN_SRC_API(float, f32)
 
 }  // extern "C"
