@@ -458,6 +458,16 @@ int vsm_brdf_surface_lin_multi_f64(const vsm_quad_f64* q, int S, int m, const do
 int vsm_brdf_surface_lin_multi_f32(const vsm_quad_f32* q, int S, int m, const float* rho, const float* drho, int K, int isurf,
                                    const float* tau_sum, const float* tau_sum_dot, int p_layer, const float* F0,
                                    const vsm_added_f32* added, const vsm_added_lin_f32* added_lin, void* stream);
+/* SurfaceSIF (src/CoreRT/Sources/surface_sif.jl:168-179; the same statement as inject_surface_SIF!, Surfaces/lambertian_surface.jl:
+ * 239-254): hemispheric isotropic emission at the lower boundary, applied to the surface AddedLayer AFTER its builder
+ * (vsm_lambertian_surface_* / vsm_lambertian_surface_spectral_*) and BEFORE the surface interaction, at Fourier moment m = 0 only:
+ *   j0_m[i n_stokes + c, s] += 2 sif[c, s]     for every stream i and Stokes component c
+ * sif: DEVICE array [n_stokes][S] (the spectral axis contiguous).  Only added_surface->j0_m ([N,1,S], per point whether the
+ * layer's matrices are shared or not) is read and written; one thread per (row, point).  The caller carries the no-op rules
+ * (m > 0, an all-zero table, a non-Lambertian surface: no call). */
+int vsm_surface_sif_f64(int N, int n_stokes, int S, const double* sif, const vsm_added_f64* added_surface, void* stream);
+int vsm_surface_sif_f32(int N, int n_stokes, int S, const float* sif, const vsm_added_f32* added_surface, void* stream);
+
 /* interaction_hdrf! (src/CoreRT/CoreKernel/interaction_hdrf.jl:4-42), called after the surface interaction of each Fourier
  * moment (rt_run.jl:467-476): hdr_J[N,S] = r-+_surf J0+ + j0-_surf; for m == 0 also the hemispheric fluxes bhr_uw / bhr_dw
  * [n_stokes, S] (for m > 0 they are not touched).  The surface layer may be shared (mat_stride 0) or per point. */
@@ -890,6 +900,24 @@ int vsm_level_radiance_src_f32(int N, int n_stokes, int S, int nV, const int* ro
                                int n_src, const float* const* top_J0_p, const float* bot_R_mp, long long bot_stride,
                                const float* const* bot_J0_m, float* uw, float* dw, float* dw_full, float* uw_full, float* work,
                                void* stream);
+
+/* The response of the column to a UNIT surface emission (the SIF Jacobian slots of the linearized run, vsmartmom.jl_amd/
+ * core_rt_lin.py).  vsm_surface_sif_* adds the same value to j0- of the surface layer at every stream, so the radiance is
+ * sum_c 2 sif[c, s] G_c(s), G_c = the response to the pattern e_c (1 on the rows of Stokes component c, 0 elsewhere).  For the K
+ * components comp_h[0..K-1] (HOST array, each in 0..n_stokes-1), with A = top_R_pm (R+- of the atmosphere's composite BEFORE the
+ * surface interaction), B = bot_R_mp (the surface r-+, bot_stride 0 or N*N) and T = top_T_mm (T-- of the same composite):
+ *   dw_k = (I - A B)^-1 A e_k,   y_k = e_k + B dw_k      (ONE pivoted elimination of [I - A B | A e_0 .. A e_{K-1}] per point)
+ *   up[k][s][c][v] = w[v,c] sum_j T[row0[v] + c, j] y_k[j]      dn[k][s][c][v] = w[v,c] dw_k[row0[v] + c]
+ * WRITTEN (not accumulated), per component and not summed; row0_h / w_h as in vsm_postprocess_vza at m = 0.  up is the share of
+ * interaction!'s J0- (TOA), dn that of its J0+ (BOA; the surface layer's t++ = I).  1 <= K <= 4 and N <= 128, anything else is
+ * VSM_ERR_INVALID_ARG before any launch (larger N: one vsm_level_radiance_oplevel_* call per component with top_J0_p = 0,
+ * bot_J0_m = e_k and uw_full = y_k, then the row products).  Status words and pivot rule as in vsm_level_radiance_*. */
+int vsm_surface_emission_response_f64(int N, int n_stokes, int S, int K, const int* comp_h, int nV, const int* row0_h,
+                                      const double* w_h, const double* top_R_pm, const double* top_T_mm, const double* bot_R_mp,
+                                      long long bot_stride, double* up, double* dn, void* stream);
+int vsm_surface_emission_response_f32(int N, int n_stokes, int S, int K, const int* comp_h, int nV, const int* row0_h,
+                                      const float* w_h, const float* top_R_pm, const float* top_T_mm, const float* bot_R_mp,
+                                      long long bot_stride, float* up, float* dn, void* stream);
 
 /* The inelastic (rotational-Raman) level equation of rt_run_test_ms(::RRS) (interlayer_flux_helper!(::RRS), CoreKernel/
  * interlayer_flux.jl:21-77, applied by postprocessing_vza_ms!(::RRS), tools/postprocessing_vza_ms.jl:55-118) at ONE boundary, the

@@ -108,6 +108,7 @@ _SIGS = {
     "vsm_interaction_{T}": (_I, [_I, _I, _I, _P, _P, _P, _P]),
     "vsm_interaction_oplevel_{T}": (_I, [_I, _I, _I, _P, _P, _P, _P]),
     "vsm_lambertian_surface_{T}": (_I, [_P, _I, _I, "{R}", _P, _P, _P]),
+    "vsm_surface_sif_{T}": (_I, [_I, _I, _I, _P, _P, _P]),
     "vsm_postprocess_vza_{T}": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "vsm_compute_Z_moments_{T}": (_I, [_P, _I, _I, _P, _P, _P, _P]),
     "vsm_layer_optics_{T}": (_I, [_I, _I, _I, _P, _P, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
@@ -171,6 +172,7 @@ _SIGS = {
     "vsm_level_radiance_{T}": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _LL, _P, _P, _P, _P, _P, _P, _P]),
     "vsm_level_radiance_oplevel_{T}": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _LL, _P, _P, _P, _P, _P, _P, _P]),
     "vsm_level_radiance_src_{T}": (_I, [_I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _LL, _P, _P, _P, _P, _P, _P, _P]),
+    "vsm_surface_emission_response_{T}": (_I, [_I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _LL, _P, _P, _P]),
     "vsm_level_radiance_ie_{T}": (_I, [_I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _LL, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vsm_level_radiance_lin_{T}": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _LL, _P, _P, _P, _LL, _P, _P, _LL, _LL, _P, _P, _P, _P, _P,
                                         _P]),

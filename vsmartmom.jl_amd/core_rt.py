@@ -22,6 +22,7 @@ import ctypes as C
 import dataclasses
 import math
 import os
+import warnings
 from dataclasses import dataclass
 from typing import List, Optional
 
@@ -485,6 +486,35 @@ def create_surface_layer_(surface, added_surface: AddedLayer, m: int, dq: Device
                         % (surface,))
 
 
+SIF_SURFACES = (H.LambertianSurfaceScalar, H.LambertianSurfaceLegendre, H.LambertianSurfaceSpline)
+
+
+def surface_source_contribute_(scene_or_table, surface, added_surface: AddedLayer, m: int) -> bool:
+    """contribute!(::SurfaceSIF) on the surface layer (Sources/surface_sif.jl:168-179 == inject_surface_SIF!, lambertian_surface.jl:
+    239-254), called after create_surface_layer_ and before the surface interaction: j0-[i n + c, s] += 2 SIF0[c, s] at every
+    stream (vsm_surface_sif).  scene_or_table: a Scene (its `sif` table) or the (nStokes, S) device table itself.  No-ops, as in
+    the reference: m > 0, no table (Scene drops an all-zero one), and any surface that is not Lambertian (`surface` may be the bare
+    albedo) -- there the scene warns, once.  Returns whether the kernel was launched."""
+    scene = scene_or_table if isinstance(scene_or_table, Scene) else None
+    table = scene.sif if scene is not None else scene_or_table
+    if table is None or m != 0:
+        return False
+    if not isinstance(surface, SIF_SURFACES + (int, float)):
+        if scene is None or not scene._sif_warned:
+            warnings.warn("SurfaceSIF has no effect over %s: the source is applied over Lambertian surfaces only "
+                          "(LambertianSurfaceScalar / Legendre / Spline)" % type(surface).__name__, stacklevel=2)
+        if scene is not None:
+            scene._sif_warned = True
+        return False
+    n, S = int(table.shape[0]), int(table.shape[1])
+    if S != added_surface.nSpec or added_surface.N % n or table.dtype != added_surface.dtype:
+        raise _lib.VSMError("SurfaceSIF: table %s (%s) does not fit a surface layer of %d rows and %d points (%s)"
+                            % (tuple(table.shape), table.dtype, added_surface.N, added_surface.nSpec, added_surface.dtype))
+    a = added_surface.cstruct()
+    _lib.call("vsm_surface_sif", added_surface.dtype, added_surface.N, n, S, _ptr(table), C.byref(a), _stream_ptr())
+    return True
+
+
 def apply_ss_correction_(R_SFI: torch.Tensor, surf: H.CoxMunkSurface, pol, vza, vaz, mu0, tau_total: torch.Tensor, m_max: int,
                          arch, FT):
     """apply_ss_correction! (coxmunk_surface.jl:481-545; rt_run.jl:520-524): R_SFI (S, n, nV) layout tensor, in place.
@@ -780,9 +810,9 @@ class Scene:
         # sources (rt_run(model; sources = ...)): the solar slot lives inside the layer kernels (F0), every other source
         # has a slot of its own (here: :thermal)
         srcs = tuple(model.sources) if model.sources is not None else (H.SolarBeam(),)
-        unknown = [s_ for s_ in srcs if not isinstance(s_, (H.SolarBeam, H.ThermalEmission))]
+        unknown = [s_ for s_ in srcs if not isinstance(s_, (H.SolarBeam, H.ThermalEmission, H.SurfaceSIF))]
         if unknown:
-            raise _lib.VSMError("rt_run: unsupported source %r (SolarBeam, ThermalEmission)" % (unknown[0],))
+            raise _lib.VSMError("rt_run: unsupported source %r (SolarBeam, ThermalEmission, SurfaceSIF)" % (unknown[0],))
         if not any(isinstance(s_, H.SolarBeam) for s_ in srcs):
             F0 = np.zeros((pol.n, S_full))
         th = [s_ for s_ in srcs if isinstance(s_, H.ThermalEmission) and s_.B_layer is not None and np.any(s_.B_layer != 0)]
@@ -795,6 +825,15 @@ class Scene:
                 raise _lib.VSMError("ThermalEmission: B_layer has %d spectral points, the model %d" % (B.shape[1], S_full))
             self.thermal_B = conv(np.ascontiguousarray(B[:, self.sl].astype(FT)))          # (rows, S)
         self.F0 = conv(np.ascontiguousarray(np.asarray(F0, dtype=FT)[:, self.sl].T))  # [n,S] col-major == (S,n)
+        # SurfaceSIF: its table [nStokes, nSpec], this rank's columns as (n, S); None without the source or with an all-zero table
+        # (nothing is allocated or launched then).  Injected into the SOLAR slot's surface layer at m = 0 (surface_source_contribute_)
+        self.sif = None
+        self._sif_warned = False
+        sif = [s_ for s_ in srcs if isinstance(s_, H.SurfaceSIF)]
+        if sif:
+            tab = sif[0].table(pol.n, S_full)
+            if np.any(tab != 0):
+                self.sif = conv(np.ascontiguousarray(tab[:, self.sl].astype(FT)))               # (n, S)
         N, S, L, C_ = self.N, self.S, self.Nz, 1 + len(model.aerosol_optics)
         # device state of the optics pass (full spectral axis; layout [nSpec, Nz] column-major == tensors (Nz, nSpec))
         z = lambda *sh: torch.empty(sh, dtype=dt, device=dev)
@@ -1074,6 +1113,7 @@ class Scene:
                 m = mom["m"]
                 weight = FT(0.5 / math.pi) if m == 0 else FT(1.0 / math.pi)
                 create_surface_layer_(model.surface, self.added_surface, m, self.dq, mom["tau_sum_surface"], rho=mom["rho"])
+                surface_source_contribute_(self, model.surface, self.added_surface, m)
                 interaction_(mom["iface_surface"], comp, self.added_surface, work=self.work)
                 if self.compute_hdrf:
                     interaction_hdrf_(pol, comp, self.added_surface, m, self.dq, model.vza, model.vaz, self.qp, float(weight),
@@ -1245,7 +1285,8 @@ class Scene:
                 after[iz + 1](comp)
 
     def _thermal_surface(self, mom):
-        """The slot's surface layer: the solar one without its beam terms (surface emission is a separate source type)."""
+        """The slot's surface layer: the solar one without its beam terms (surface emission is a separate source type: SurfaceSIF
+        is counted once, in the solar slot, and never injected here)."""
         create_surface_layer_(self.model.surface, self._th_surf, mom["m"], self.dq, mom["tau_sum_surface"], rho=mom["rho"])
         self._th_surf.j0_p.zero_()      # no solar beam in this slot
         self._th_surf.j0_m.zero_()
@@ -1346,7 +1387,11 @@ def rt_run_streams(model: H.RTModel) -> StreamRTResult:
 def rt_run(model: H.RTModel, trace: Optional[list] = None, full_output: bool = False):
     """rt_run(model) (rt_run.jl:53-58 -> :238-539): returns (R_SFI, T_SFI) as host arrays [nVZA, nStokes, nSpec] -- the
     reference's first two return values -- or, with `full_output`, its whole SFI tuple
-    (R_SFI, T_SFI, ieR_SFI, ieT_SFI, hdr, bhr_uw[1,:], bhr_dw[1,:]) (rt_run.jl:535)."""
+    (R_SFI, T_SFI, ieR_SFI, ieT_SFI, hdr, bhr_uw[1,:], bhr_dw[1,:]) (rt_run.jl:535).
+
+    Sources: model.sources may hold SolarBeam, ThermalEmission and SurfaceSIF (None = SolarBeam alone; without a SolarBeam
+    F0 = 0).  The thermal radiance is a slot of its own added to R_SFI / T_SFI; SurfaceSIF is injected into the surface layer of
+    the solar slot at m = 0 (surface_source_contribute_), over Lambertian surfaces only."""
     scene = prepare_scene(model)
     scene.compute_hdrf = bool(full_output)
     scene.run(trace)

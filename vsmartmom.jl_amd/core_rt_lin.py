@@ -21,6 +21,7 @@ import torch
 from . import _lib
 from . import host_model as H
 from . import core_rt as CR
+from . import core_rt_ms as MS
 from .architectures import array_type, devi, synchronize_if_gpu, to_host
 
 
@@ -377,8 +378,15 @@ class SceneLin(LinInputs):
         th_src = [s_ for s_ in (model.sources or ()) if isinstance(s_, H.ThermalEmission)]
         Bd = getattr(th_src[0], "B_layer_dot", None) if th_src else None
         self.nPlanck = 0 if Bd is None else int(Bd.shape[0])
-        if P + self.nPlanck > 64:
+        # SIF slots: SurfaceSIF.SIF0_dot [nSIF, nStokes, nSpec], appended after the Planck slots
+        sif_src = [s_ for s_ in (model.sources or ()) if isinstance(s_, H.SurfaceSIF)]
+        self.nSIF = sif_src[0].nSIF if sif_src else 0
+        if P + self.nPlanck + self.nSIF > 64:
+            if self.nSIF:
+                raise _lib.VSMError("rt_run (linearized): %d parameter slots + %d Planck slots + %d SIF slots (limit 64)"
+                                    % (P, self.nPlanck, self.nSIF))
             raise _lib.VSMError("rt_run (linearized): %d parameter slots + %d Planck slots (limit 64)" % (P, self.nPlanck))
+        sif_dot = sif_src[0].dot_tables(pol.n, model.tau_rayl.shape[0]) if self.nSIF else None
         if Bd is not None and Bd.shape[2] != model.tau_rayl.shape[0]:
             raise _lib.VSMError("ThermalEmission: B_layer_dot has %d spectral points, the model %d" % (Bd.shape[2], model.tau_rayl.shape[0]))
         # forward optics, quadrature, F0, composite / added / surface layers and R, T: the forward scene's device state
@@ -407,7 +415,14 @@ class SceneLin(LinInputs):
         self.thermal_B_dot = (array_type(arch)(np.ascontiguousarray(Bd[:, :, self.sl].astype(FT))) if self.nPlanck else None)
         self._th = None
         self._check_thermal()
-        self.Rd = torch.zeros((P + self.nPlanck, S, pol.n, nV), dtype=dt, device=dev)
+        # the SIF slots: 2 SIF0_dot as (nSIF, nStokes, S) and the Stokes components some table uses -- the right-hand sides of the
+        # response solve (_sif_slots), chosen on the FULL spectral axis so that every shard solves the same ones.  Over a surface
+        # that is not Lambertian the source does nothing (CoreRT.surface_source_contribute_) and the slots stay zero.
+        self.sif_dot2, self._sif_comps = None, []
+        if self.nSIF and isinstance(model.surface, H.LambertianSurfaceScalar):
+            self._sif_comps = [c for c in range(pol.n) if np.any(sif_dot[:, c, :] != 0)]
+            self.sif_dot2 = array_type(arch)(np.ascontiguousarray((2.0 * sif_dot[:, :, self.sl]).astype(FT)))
+        self.Rd = torch.zeros((P + self.nPlanck + self.nSIF, S, pol.n, nV), dtype=dt, device=dev)
         self.Td = torch.zeros_like(self.Rd)
         self._lanes = []
         self._fold = {}
@@ -426,6 +441,7 @@ class SceneLin(LinInputs):
         c0 = fwd.coupling[0] if getattr(fwd, "coupling", None) else None
         if (_reduce_m0 and REDUCE_M0 and pol.n >= 3 and S >= self.LANE_POINTS and NAer == 0 and not host_optics and c0 is not None
                 and isinstance(model.surface, H.LambertianSurfaceScalar) and (F0m is None or not np.any(np.asarray(F0m)[2:] != 0))
+                and not any(s_.has_uv() for s_ in sif_src)   # (a surface emission with a U / V row drives the (U,V) block)
                 and not any(c0 >> (4 * a + b) & 1 or c0 >> (4 * b + a) & 1 for a in (0, 1) for b in range(2, pol.n))):
             self.sub0 = SceneLin(self._sub0_model(), lin_model, NAer, NGas, NSurf, spec_slice, _reduce_m0=False)
 
@@ -434,8 +450,10 @@ class SceneLin(LinInputs):
         scene.lin_model, ... and re-uploads: the sub-scene must see the new arrays, not the constructor-time snapshot)."""
         model, qp = self.model, self.model.quad_points
         F0m = model.F0
-        if model.sources is not None:   # (the sub-scene carries no thermal slot; without a SolarBeam its F0 stays 0)
-            model = dataclasses.replace(model, sources=tuple(s_ for s_ in model.sources if not isinstance(s_, H.ThermalEmission)))
+        if model.sources is not None:   # (the sub-scene carries no thermal slot; without a SolarBeam its F0 stays 0; a SurfaceSIF
+            # without U / V rows -- the constructor's condition -- comes along with its I, Q rows and its SIF slots)
+            model = dataclasses.replace(model, sources=tuple(s_.stokes_iq() if isinstance(s_, H.SurfaceSIF) else s_
+                                                             for s_ in model.sources if not isinstance(s_, H.ThermalEmission)))
         qi = H.QuadPoints(qp.mu0, qp.imu0, qp.qp_mu, qp.wt_mu, np.repeat(qp.qp_mu, 2), np.repeat(qp.wt_mu, 2), qp.Nquad, qp.Nstreams)
         return dataclasses.replace(model, polarization_type=H.Stokes_IQ(), quad_points=qi, m_max=0,
                                    F0=None if F0m is None else np.ascontiguousarray(np.asarray(F0m)[:2]))
@@ -520,9 +538,13 @@ class SceneLin(LinInputs):
         interface tags, lanes / fold) -- the graph is captured once per such key, on buffers the scene owns, and reads the
         optics where `prepare()` puts them."""
         thermal = self._check_thermal()
+        sif = self.fwd.sif is not None or self.nSIF > 0
         if graph is None:
             graph = (bool(getattr(self, "graph_replay", False)) and self.S > 0 and not torch.cuda.is_current_stream_capturing()
-                     and not thermal)
+                     and not thermal and not sif)
+        if graph and sif:
+            raise NotImplementedError("SceneLin.run(graph=True): a scene with a SurfaceSIF source is not captured "
+                                      "(run it with graph=False or graph=None)")
         if graph and thermal:
             raise NotImplementedError("SceneLin.run(graph=True): a scene with a ThermalEmission source is not captured "
                                       "(run it with graph=False or graph=None)")
@@ -597,8 +619,12 @@ class SceneLin(LinInputs):
                 r0, t0, rd0, td0 = self.sub0.run(lanes=1, fold=False)
                 self.R[:, :2, :].copy_(r0)
                 self.T[:, :2, :].copy_(t0)
-                self.Rd[:self.P, :, :2, :].copy_(rd0)
-                self.Td[:self.P, :, :2, :].copy_(td0)
+                self.Rd[:self.P, :, :2, :].copy_(rd0[:self.P])
+                self.Td[:self.P, :, :2, :].copy_(td0[:self.P])
+                if self.nSIF:      # (the sub-scene has no Planck slot: its SIF slots follow its surface slots)
+                    o = self.P + self.nPlanck
+                    self.Rd[o:, :, :2, :].copy_(rd0[self.P:])
+                    self.Td[o:, :, :2, :].copy_(td0[self.P:])
             for mom in self.fwd.moments:
                 if reduced and mom["m"] == 0:
                     continue
@@ -892,14 +918,37 @@ class SceneLin(LinInputs):
         m = mom["m"]
         weight = FT(0.5 / math.pi) if m == 0 else FT(1.0 / math.pi)
         self._surface_lin(mom, w["added_s"], w["als"], self.F0)
+        if m == 0 and self._sif_comps:
+            self._sif_slots(comp, w, float(weight))     # (reads the composite BEFORE its surface interaction)
         interaction_lin_(mom["iface_surface"], comp, cl, w["added_s"], w["als"])
         CR.postprocessing_vza_(pol, comp, model.vza, model.vaz, qp, m, float(weight), w["R"], w["T"])
         row0, wts = _pp_args(pol, qp, model.vza, model.vaz, m, weight, dt)
         _lib.call("vsm_postprocess_vza_lin", dt, N, pol.n, S, len(model.vza), P, row0, wts, CR._ptr(cl.J0_m), CR._ptr(cl.J0_p),
                   CR._ptr(w["Rd"]), CR._ptr(w["Td"]), CR._stream_ptr())
 
+    def _sif_slots(self, comp, w, weight):
+        """The SIF slots.  The radiance is linear in SIF0 and the emission is the same at every stream, so
+        dR / dx_k = sum_c 2 SIF0_dot[k, c, s] G_c(s) with G_c the response of the column to a unit emission in Stokes component c:
+        ONE elimination per point for the components some table uses (MS.surface_emission_response_), combined here into the slots
+        P + nPlanck + k of the workspace's Rdot / Tdot.  Like the Planck slots they are forward quantities: no derivative stack and
+        no layer kernel knows of them."""
+        model, pol = self.model, self.pol
+        comps, K, nV = self._sif_comps, len(self._sif_comps), len(model.vza)
+        if w.get("sif_up") is None:
+            w["sif_up"] = torch.empty((K, self.S, pol.n, nV), dtype=self.dt, device=self.expk.device)
+            w["sif_dn"] = torch.empty_like(w["sif_up"])
+        up, dn = w["sif_up"], w["sif_dn"]
+        MS.surface_emission_response_(pol, self.qp, model.vza, model.vaz, weight, comp.R_pm, comp.T_mm, w["added_s"].r_mp, comps,
+                                      up, dn)
+        coef = self.sif_dot2[:, comps, :]                       # (nSIF, K, S)
+        o = self.P + self.nPlanck
+        w["Rd"][o:o + self.nSIF].add_(torch.einsum("kis,iscv->kscv", coef, up))
+        w["Td"][o:o + self.nSIF].add_(torch.einsum("kis,iscv->kscv", coef, dn))
+
     def _surface_lin(self, mom, added_s, als, F0):
-        """create_surface_layer! (lin) of one Fourier moment into the surface layers `added_s` / `als`, driven by the beam F0."""
+        """create_surface_layer! (lin) of one Fourier moment into the surface layers `added_s` / `als`, driven by the beam F0; at
+        m = 0 SurfaceSIF is then injected into the forward j0- (rt_run_lin.jl:292; it depends on no parameter, so the derivative
+        stacks stay what the builder wrote -- and the builder has formed its -tau_sum_dot / mu0 terms from the beam term alone)."""
         model, dt, S, pl = self.model, self.dt, self.S, self.pl
         isurf = self.layout.surface_index(0)
         q_ = self.dq.cstruct()
@@ -916,6 +965,7 @@ class SceneLin(LinInputs):
             alb = C.c_double(model.surface.albedo) if dt == torch.float64 else C.c_float(model.surface.albedo)
             _lib.call("vsm_lambertian_surface_lin", dt, C.byref(q_), S, m, alb, isurf, CR._ptr(tau_sum_s), CR._ptr(tsd_s), pl,
                       CR._ptr(F0), C.byref(a_), C.byref(al_), CR._stream_ptr())
+        CR.surface_source_contribute_(self.fwd, model.surface, added_s, m)
 
     # ---- the thermal slot ----------------------------------------------------------------------------------------
     def _thermal_state(self):
@@ -988,7 +1038,7 @@ class SceneLin(LinInputs):
 
     def _thermal_lin_surface(self, mom):
         """The slot's surface layers: those of the solar walk without their beam terms (surface emission is a separate source
-        type)."""
+        type: what _surface_lin injected for SurfaceSIF is zeroed with the beam term, the emission counts once, in the solar slot)."""
         t = self._thermal_state()
         self._surface_lin(mom, t["added_s"], t["als"], t["F0"])
         torch._foreach_zero_([t["added_s"].j0_p, t["added_s"].j0_m, t["als"].ap_J0_p, t["als"].ap_J0_m])
@@ -1067,7 +1117,11 @@ def rt_run_lin(model: H.RTModel, lin_model: H.LinModel, NAer: int, NGas: int, NS
     R, T then include the thermal radiance and every slot of Rdot / Tdot the derivative of the thermal slot (m = 0
     only, no surface emission).  ThermalEmission(B_layer_dot=[nPlanck, rows, nSpec]) appends nPlanck Planck (temperature) slots
     after the surface slots: Nparams = 7 NAer + NGas + NSurf + nPlanck <= 64, slot k of the block = d/dx_k for B_layer_dot[k] =
-    dB_layer / dx_k.  Not supported with a thermal source: a column with a non-scattering layer (NotImplementedError)."""
+    dB_layer / dx_k.  Not supported with a thermal source: a column with a non-scattering layer (NotImplementedError).
+
+    SurfaceSIF(SIF0, SIF0_dot) (DESIGN 4.13): R, T and every slot carry the emission's share (m = 0, Lambertian surface);
+    SIF0_dot [nSIF, nStokes, nSpec] appends nSIF slots after the Planck slots, slot k of the block = d/dx_k for SIF0_dot[k] =
+    dSIF0 / dx_k; 7 NAer + NGas + NSurf + nPlanck + nSIF <= 64."""
     scene = SceneLin(model, lin_model, NAer, NGas, NSurf)
     scene.run()
     synchronize_if_gpu()

@@ -98,6 +98,42 @@ def level_radiance_(pol, qp, vza, vaz, m: int, weight: float, top_R_pm, top_J0_p
               P(dw), P(dw_full), P(uw_full), P(work), CR._stream_ptr())
 
 
+def surface_emission_response_(pol, qp, vza, vaz, weight: float, top_R_pm, top_T_mm, bot_R_mp, comps, up, dn,
+                               oplevel: bool = False):
+    """The response of the column to a unit surface emission in the Stokes components `comps` (a list of K indices), at m = 0
+    (vsm_surface_emission_response_*): with A = top_R_pm, T = top_T_mm (R+-, T-- of the atmosphere's composite before the surface
+    interaction), B = bot_R_mp (the surface r-+, (S | 1, N, N)) and e_k the unit pattern of component comps[k],
+        dw_k = (I - A B)^-1 A e_k,   y_k = e_k + B dw_k,
+        up[k] (S, n, nV) = weight * rows of T y_k,   dn[k] (S, n, nV) = weight * rows of dw_k       (written, not accumulated).
+    N <= 128: ONE call, one elimination for all K <= 4 right-hand sides.  N > 128 or operator level: one
+    vsm_level_radiance_oplevel_* call per component (a = 0, c = e_k, uw_full = y_k, dw_full = dw_k) and a batched row product."""
+    S, N = int(top_R_pm.shape[0]), int(top_R_pm.shape[1])
+    K, n, nV, dt, dev = len(comps), pol.n, len(vza), top_R_pm.dtype, top_R_pm.device
+    row0, w = CR._vza_rows_weights(pol, vza, vaz, qp, 0, weight, dt)
+    bot_stride = 0 if int(bot_R_mp.shape[0]) == 1 and S > 1 else N * N
+    P = CR._ptr
+    if not (oplevel or LEVEL_OPLEVEL or N > LEVEL_FUSED_MAX_N):
+        _lib.call("vsm_surface_emission_response", dt, N, n, S, K, (C.c_int * max(K, 1))(*[int(c) for c in comps]), nV, row0, w,
+                  P(top_R_pm), P(top_T_mm), P(bot_R_mp), bot_stride, P(up), P(dn), CR._stream_ptr())
+        return
+    if not 1 <= K <= 4 or any(not 0 <= int(c) < n for c in comps):
+        raise _lib.VSMError("surface_emission_response_: %d components %r (1..4 of 0..%d)" % (K, list(comps), n - 1))
+    if S == 0 or nV == 0:
+        return
+    rows = torch.as_tensor([row0[v] + c for c in range(n) for v in range(nV)], dtype=torch.long, device=dev)
+    wt = torch.as_tensor([w[v + nV * c] for c in range(n) for v in range(nV)], dtype=dt, device=dev).view(1, n, nV)
+    T_rows = top_T_mm[:, :, rows].contiguous()                       # (S, N, n nV): the [n nV, N] row blocks of T--
+    zero = torch.zeros((S, N), dtype=dt, device=dev)
+    sink = torch.zeros((2, S, n, nV), dtype=dt, device=dev)          # (the call's own VZA rows, without T--: not used)
+    for k, c in enumerate(comps):
+        e = torch.zeros((S, N), dtype=dt, device=dev)
+        e[:, int(c)::n] = 1
+        d, y = torch.empty_like(e), torch.empty_like(e)
+        level_radiance_(pol, qp, vza, vaz, 0, weight, top_R_pm, zero, bot_R_mp, e, sink[0], sink[1], d, y, oplevel=True)
+        up[k].copy_(CR.batched_mul(T_rows, y).view(S, n, nV) * wt)
+        dn[k].copy_(d[:, rows].view(S, n, nV) * wt)
+
+
 LEVEL_MAX_SRC = 4          # VSM_LEVEL_MAX_SRC
 
 
@@ -180,9 +216,11 @@ class LevelPlan:
         return len(self.tops_at)
 
 
-def _validate(model: H.RTModel, sensor_levels, thermal: bool = False) -> LevelPlan:
+def _validate(model: H.RTModel, sensor_levels, thermal: bool = False, sif: bool = False,
+              who: str = "rt_run_multisensor") -> LevelPlan:
     """The level plan of a run.  thermal: ThermalEmission is accepted beside (or instead of) SolarBeam -- rt_run_multisensor's
-    thermal=True; the Raman and linearized runs leave it off."""
+    thermal=True; the Raman and linearized runs leave it off.  sif: SurfaceSIF is accepted too (CoreRT.rt_run_multisensor alone:
+    the Raman and the linearized multi-sensor run refuse it with NotImplementedError, before anything is launched)."""
     Nz = int(np.asarray(model.tau_rayl).shape[1])
     levels = []
     for l in sensor_levels:
@@ -194,7 +232,9 @@ def _validate(model: H.RTModel, sensor_levels, thermal: bool = False) -> LevelPl
     if not levels:
         raise ValueError("rt_run_multisensor: no sensor level given")
     srcs = tuple(model.sources) if model.sources is not None else (H.SolarBeam(),)
-    accepted = (H.SolarBeam, H.ThermalEmission) if thermal else (H.SolarBeam,)
+    if not sif and any(isinstance(s, H.SurfaceSIF) for s in srcs):
+        raise NotImplementedError("%s: SurfaceSIF is not a source of this run (CoreRT.rt_run_multisensor takes it)" % who)
+    accepted = ((H.SolarBeam, H.ThermalEmission) if thermal else (H.SolarBeam,)) + ((H.SurfaceSIF,) if sif else ())
     other = [s for s in srcs if not isinstance(s, accepted)]
     if other or not srcs:
         if thermal:
@@ -405,6 +445,8 @@ def _run(scene: CR.Scene, plan: LevelPlan, streams: bool):
                 fv = {}
                 asurf = scene.added_surface
                 CR.create_surface_layer_(model.surface, asurf, m, scene.dq, mom["tau_sum_surface"], rho=mom["rho"])
+                # SurfaceSIF (m = 0, Lambertian surfaces): the bottoms are built upward from this layer, so every level sees it
+                CR.surface_source_contribute_(scene, model.surface, asurf, m)
                 # the thermal slot (m = 0): its top pass on the slot's own composite, J0+ kept after each level of tops_at
                 th = thermal and m == 0
                 th_tops, th_surf = {}, None
@@ -493,8 +535,12 @@ def rt_run_multisensor(model: H.RTModel, sensor_levels, streams: bool = False, t
     dw per level are the sum of the solar and the thermal slot, as rt_run's R_SFI / T_SFI are, level 0 again rt_run's result bit
     for bit; with streams=True the level vectors of m = 0 are the sum as well.  Columns with a non-scattering layer are refused
     as before, so the slot-state behaviour of such layers never arises here and
-    ThermalEmission.reset_slot_in_nonscattering_layers has no effect.  No surface emission."""
-    plan = _validate(model, sensor_levels, thermal=bool(thermal))
+    ThermalEmission.reset_slot_in_nonscattering_layers has no effect.  The thermal slot has no surface emission of its own.
+
+    SurfaceSIF (with or without thermal=True): injected into the solar slot's surface layer at m = 0 as rt_run injects it
+    (rt_run_multisensor.jl:140); every bottom composite is built upward from that layer, so every level carries the emission,
+    and level 0 stays rt_run's result bit for bit."""
+    plan = _validate(model, sensor_levels, thermal=bool(thermal), sif=True)
 
     def run_block(_sl):
         scene = CR.prepare_scene(model)

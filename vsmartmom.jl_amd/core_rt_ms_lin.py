@@ -300,10 +300,11 @@ def rt_run_multisensor(model: H.RTModel, lin_model: H.LinModel, NAer: int, NGas:
     is the sum of the solar and the thermal derivative, slot Nparams + k is d/dx_k for B_layer_dot[k] (the thermal part alone),
     after the surface slots as rt_run_lin places them; Nparams + nPlanck <= 64.  The slot exists for m = 0 only; with
     streams=True the derivative level vectors of every moment carry all Nparams + nPlanck slots (zero Planck slots for m > 0).
-    Level 0 is again SceneLin.run(lanes=1, fold=False) bit for bit.  No surface emission.  DESIGN.md §4.8e.
+    Level 0 is again SceneLin.run(lanes=1, fold=False) bit for bit.  No surface emission: SurfaceSIF raises NotImplementedError
+    before anything is launched (rt_run_lin takes it).  DESIGN.md §4.8e.
 
     Columns with a non-scattering layer raise NotImplementedError; N <= 128."""
-    plan = MS._validate(model, sensor_levels, thermal=True)
+    plan = MS._validate(model, sensor_levels, thermal=True, who="rt_run_multisensor (linearized)")
     # There is no `thermal=` keyword here: a ThermalEmission opts into this run by stating its Planck tables ([0, rows, nSpec] for
     # none).  One that leaves B_layer_dot at None is a forward-only source and is refused as it always was (DESIGN 4.8e "Opt-in").
     fwd_only = [s_ for s_ in (model.sources or ()) if isinstance(s_, H.ThermalEmission) and getattr(s_, "B_layer_dot", None) is None]

@@ -246,13 +246,18 @@ class SceneRRS:
         # (2/3)^3 of the products and (2/3)^2 of the bytes for Stokes_IQU.
         self.sub0 = None
         F0 = model.F0
+        # (SurfaceSIF: an emission with a U or V row drives the (U,V) block of m = 0 -- no reduction then; else the sub-scene carries
+        #  the I, Q rows of the table)
+        sif = [s_ for s_ in (model.sources or ()) if isinstance(s_, H.SurfaceSIF)]
         if (_reduce_m0 and REDUCE_M0 and pol.n >= 3 and S > 0 and (F0 is None or not np.any(np.asarray(F0)[2:] != 0))
-                and fwd.coupling is not None and zie_mask0 is not None
+                and not any(s_.has_uv() for s_ in sif) and fwd.coupling is not None and zie_mask0 is not None
                 and not any((fwd.coupling[0] | zie_mask0) >> (4 * a + b) & 1 or (fwd.coupling[0] | zie_mask0) >> (4 * b + a) & 1
                             for a in (0, 1) for b in range(2, pol.n))):
             qi = H.QuadPoints(qp.mu0, qp.imu0, qp.qp_mu, qp.wt_mu, np.repeat(qp.qp_mu, 2), np.repeat(qp.wt_mu, 2), qp.Nquad, qp.Nstreams)
             m_iq = dataclasses.replace(model, polarization_type=H.Stokes_IQ(), quad_points=qi, m_max=0,
                                        F0=None if F0 is None else np.ascontiguousarray(np.asarray(F0)[:2]))
+            if sif:
+                m_iq.sources = tuple(s_.stokes_iq() if isinstance(s_, H.SurfaceSIF) else s_ for s_ in model.sources)
             self.sub0 = SceneRRS(RS_type, m_iq, iBand, spec_slice, _reduce_m0=False)
 
     def run(self, trace: Optional[list] = None):
@@ -286,6 +291,8 @@ class SceneRRS:
                                self.arch, iz + 1, fwd.F0, FT, model.numerics, dtau=ly["dtau"], ndoubl=ly["nd"], expk=self.expk,
                                trace=trace, iface=ly["iface"])
             CR.create_surface_layer_(model.albedo, fwd.added_surface, m, fwd.dq, mom["tau_sum_surface"])
+            # SurfaceSIF (rt_run.jl:711-712): the elastic j0- carries the emission, the inelastic interaction below scatters it
+            CR.surface_source_contribute_(fwd, model.albedo, fwd.added_surface, m)
             interaction_inelastic_(drs, mom["iface_surface"], comp, self.comp_rs, fwd.added_surface, self.surf_rs)
             postprocessing_vza_rs_(pol, comp, self.comp_rs, model.vza, model.vaz, qp, m, float(weight), R_SFI, T_SFI, ieR_SFI, ieT_SFI)
         return tuple(self.out)
@@ -315,6 +322,10 @@ def rt_run(RS_type: RRS, model: H.RTModel, iBand: int = 1, trace: Optional[list]
     [nVZA, nStokes, nSpec].  `model.greek_rayleigh` must hold the Cabannes phase matrix and `model.varpi_Cabannes`
     the elastic Rayleigh single-scattering albedo (compEffectiveLayerProperties.jl:36-41).  `spec_slice`: see SceneRRS;
     `device_out=True` returns the four (S_local, nStokes, nVZA) device tensors instead (for the gather).
+
+    Sources: SolarBeam and SurfaceSIF (the flagship O2-A configuration of the reference, prototype_O2ABand_RRS_SIF.jl); the
+    emission enters the elastic surface layer at m = 0 and is Raman-scattered on its way up like every elastic field.  The walk
+    in blocks slices the table with the block.
 
     Footprint: the reference pages its N x N x nSpec x nRaman arrays through the host (interaction_inelastic.jl:16-35,427-438).
     Here a run whose arrays would not fit the device (or `max_points` recipient points per pass, if given) walks the recipient

@@ -56,6 +56,8 @@ def _refuse_sources(model: H.RTModel):
     for s_ in (model.sources or ()):
         if isinstance(s_, H.ThermalEmission):
             raise NotImplementedError("rt_run_ss: SolarBeam is the only source of a single-scattering run (got ThermalEmission)")
+        if isinstance(s_, H.SurfaceSIF):
+            raise NotImplementedError("rt_run_ss: SolarBeam is the only source of a single-scattering run (got SurfaceSIF)")
 
 
 class SceneSS:

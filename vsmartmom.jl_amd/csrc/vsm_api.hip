@@ -1009,6 +1009,15 @@ VSM_LIN_API(float, f32)
     return brdf_surface_lin_multi<T>(cvt_quad<T>(q), S, m, rho, drho, K, isurf, tau_sum, tau_sum_dot, p_layer, F0,     \
                                      cvt_added<T>(added), cvt_al<T>(al), as_stream(stream));                           \
   }                                                                                                                    \
+  extern "C" int vsm_surface_sif_##SFX(int N, int n_stokes, int S, const T* sif, const vsm_added_##SFX* added_surface,  \
+                                       void* stream) {                                                                 \
+    int rc;                                                                                                            \
+    if ((rc = check_added(added_surface))) return rc;                                                                  \
+    VSM_REQUIRE(N > 0 && n_stokes >= 1 && n_stokes <= 4 && N % n_stokes == 0 && S >= 0 &&                              \
+                    (S == 0 || (sif && added_surface->j0_m)),                                                          \
+                "surface_sif: bad argument (N a multiple of n_stokes in 1..4, sif [n_stokes][S], j0_m)");              \
+    return surface_sif<T>(N, n_stokes, S, sif, cvt_added<T>(added_surface), as_stream(stream));                        \
+  }                                                                                                                    \
   extern "C" int vsm_interaction_hdrf_##SFX(const vsm_quad_##SFX* q, int S, int m, const vsm_composite_##SFX* comp,    \
                                             const vsm_added_##SFX* added_surface, T* hdr_J, T* bhr_uw, T* bhr_dw,      \
                                             void* stream) {                                                            \

@@ -124,6 +124,9 @@ int land_brdf_reflectance_lin(int kind, const T* params_h, int n_stokes, int Nmu
 template <typename T>
 int brdf_surface_lin_multi(const quad<T>& q, int S, int m, const T* rho, const T* drho, int K, int isurf, const T* tau_sum,
                            const T* tau_sum_dot, int p_layer, const T* F0, const added<T>& a, const added_lin<T>& al, hipStream_t st);
+// SurfaceSIF: j0- += 2 sif on the rows of every stream (sif [n_stokes][S]); nothing else of the surface layer is touched
+template <typename T>
+int surface_sif(int N, int ns, int S, const T* sif, const added<T>& a, hipStream_t st);
 template <typename T>
 int interaction_hdrf(const quad<T>& q, int S, int m, const composite<T>& c, const added<T>& a, T* hdr_J, T* bhr_uw, T* bhr_dw,
                      hipStream_t st);

@@ -19,6 +19,8 @@
 // (the Planck slots of a linearized multi-sensor run with thermal emission), one body (level_lin_body, k_level_radiance_lin_src).
 // vsm_level_radiance_src_*: the same equation for up to VSM_LEVEL_MAX_SRC source pairs (a_k, c_k) on the same A, B (the solar and
 // the thermal slot), the pairs as right-hand sides of ONE solve, their level vectors summed (k_level_radiance_src, below).
+// vsm_surface_emission_response_*: the same system between the atmosphere and the surface layer for the unit emission patterns of
+// SurfaceSIF, kept per component (k_emission_response, below).
 #include "vsm_common.h"
 #include "vsm_internal.h"
 #include "vsm_inverse.h"
@@ -685,6 +687,146 @@ static int level_lin_src_check(int P, int P_src, int S, const T* asrc, const T* 
   return VSM_OK;
 }
 
+// The response of the column to a unit hemispheric emission at the lower boundary (vsm_surface_emission_response_*: the SIF
+// Jacobian slots of the linearized run).  SurfaceSIF adds the SAME value to j0- of the surface layer at every stream, so the
+// radiance is sum_c 2 SIF0[c, s] G_c(s) with G_c the response to the unit pattern e_c (1 on the rows of Stokes component c, 0
+// elsewhere): the level equation at the boundary between the atmosphere (A = its R+-, a = 0) and the surface (B = its r-+,
+// c_k = e_comp[k]), k_level_radiance_src's system with K <= 4 right-hand sides and no top source, point s = blockIdx.x:
+//   [M | d_1 .. d_K] = [I - A B | A c_k],  ONE Gauss-Jordan elimination,  dw_k = column / m_ii,  y_k = c_k + B dw_k,
+//   up_k[v, c, s] = w[v, c] sum_j T--[row0[v] + c, j] y_k[j]   (the TOA leg: interaction!'s J0- = .. + T-- (I - r-+ R+-)^-1 (j0- + r-+ J0+))
+//   dn_k[v, c, s] = w[v, c] dw_k[row0[v] + c]                  (the BOA leg: J0+ = t++ (I - R+- r-+)^-1 R+- j0-, t++ = I at m = 0)
+// written (not accumulated) per component into up / dn [K][S][n_stokes][nVtot].  y_full / dw_full [K][S][N] (nullable): the
+// vectors at all streams, for the caller's own row products above 64 viewing angles.  LDS: L [N][N + K], Q [K][N].
+struct emission_comps {
+  int c[4];
+};
+
+template <typename T>
+__global__ void __launch_bounds__(LEVEL_NT) k_emission_response(int N, int ns, int S, int K, emission_comps comps, int nV, level_pp pa,
+                                                                const T* __restrict__ A, const T* __restrict__ Tmm,
+                                                                const T* __restrict__ B, long long bstride, T* up, T* dn,
+                                                                T* y_full, T* dw_full, int* status) {
+  extern __shared__ __align__(16) unsigned char lds_raw[];
+  const int LD = N + K;
+  T* L = reinterpret_cast<T*>(lds_raw);          // [M | d_1 .. d_K], row-major, leading dimension N + K
+  T* Q = L + (size_t)N * LD;                     // c_k, then y_k
+  __shared__ int sh[2];
+  const int tid = threadIdx.x;
+  const long long s = blockIdx.x;
+  const long long NN = (long long)N * N;
+  const T* Bs = B + s * bstride;
+  const T* Ts = Tmm + s * NN;
+  if (tid == 0) sh[1] = 0;
+  for (int e = tid; e < N * K; e += LEVEL_NT) {
+    const int i = e % N, k = e / N;
+    L[i * LD + N + k] = T(0);
+    Q[k * N + i] = (i % ns == comps.c[k]) ? T(1) : T(0);
+  }
+  __syncthreads();
+  level_form_system<T>(N, N + K, LD, A + s * NN, Bs, Q, L, sh, status);
+  level_eliminate<T>(N, N + K, LD, L, sh, status);
+  for (int e = tid; e < N * K; e += LEVEL_NT) {
+    const int i = e % N, k = e / N;
+    L[i * LD + N + k] = L[i * LD + N + k] / L[i * LD + i];
+  }
+  __syncthreads();
+  for (int e = tid; e < N * K; e += LEVEL_NT) {
+    const int i = e % N, k = e / N;
+    T y = Q[k * N + i];
+    for (int j = 0; j < N; ++j) y += Bs[(long long)j * N + i] * L[j * LD + N + k];
+    Q[k * N + i] = y;   // (row i of Q[k] is read by this thread alone until the barrier)
+    const long long o = ((long long)k * S + s) * N + i;
+    if (y_full) y_full[o] = y;
+    if (dw_full) dw_full[o] = L[i * LD + N + k];
+  }
+  __syncthreads();
+  for (int e = tid; e < nV * ns * K; e += LEVEL_NT) {
+    const int v = e % nV, c = (e / nV) % ns, k = e / (nV * ns), row = pa.row0[v] + c;
+    const T w = (T)pa.w[v + nV * c];
+    T u = T(0);
+    for (int j = 0; j < N; ++j) u += Ts[(long long)j * N + row] * Q[k * N + j];
+    const long long dst = (((long long)k * S + s) * ns + c) * nV + v;
+    up[dst] = w * u;
+    dn[dst] = w * L[row * LD + N + k];
+  }
+}
+
+// The row products of k_emission_response for a chunk of at most 64 viewing angles [v0, v0 + nV) out of nVtot, from the vectors at
+// all streams: one thread per (v, c, point, k).
+template <typename T>
+__global__ void __launch_bounds__(256) k_emission_rows(int N, int ns, long long S, int K, int nV, int nVtot, int v0, level_pp pa,
+                                                       const T* __restrict__ Tmm, const T* __restrict__ y_full,
+                                                       const T* __restrict__ dw_full, T* up, T* dn) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (long long)nV * ns * S * K) return;
+  const int v = (int)(e % nV), c = (int)((e / nV) % ns);
+  const long long ks = e / ((long long)nV * ns);   // k S + s
+  const long long s = ks % S;
+  const int row = pa.row0[v] + c;
+  const T w = (T)pa.w[v + nV * c];
+  const T* Ts = Tmm + s * (long long)N * N;
+  const T* y = y_full + ks * N;
+  T u = T(0);
+  for (int j = 0; j < N; ++j) u += Ts[(long long)j * N + row] * y[j];
+  const long long dst = (ks * ns + c) * nVtot + v0 + v;
+  up[dst] = w * u;
+  dn[dst] = w * dw_full[ks * N + row];
+}
+
+template <typename T>
+static int emission_response_fused(int N, int ns, int S, int K, const int* comp_h, int nV, const int* row0_h, const T* w_h, const T* A,
+                                   const T* Tmm, const T* B, long long bstride, T* up, T* dn, hipStream_t st) {
+  int* status = device_status();
+  if (!status) return VSM_ERR_HIP;
+  const size_t lds = level_src_lds<T>(N, K);
+  VSM_REQUIRE(lds <= 160 * 1024 - 256, "surface_emission_response: N = %d with %d components needs %zu bytes of LDS", N, K, lds);
+  const int rc = ensure_dyn_lds(reinterpret_cast<const void*>(k_emission_response<T>), lds, "hipFuncSetAttribute(k_emission_response)");
+  if (rc) return rc;
+  emission_comps comps = {};
+  for (int k = 0; k < K; ++k) comps.c[k] = comp_h[k];
+  level_pp pa = {};
+  if (nV <= 64) {
+    for (int v = 0; v < nV; ++v) pa.row0[v] = row0_h[v];
+    for (int c = 0; c < ns; ++c)
+      for (int v = 0; v < nV; ++v) pa.w[v + nV * c] = (double)w_h[v + nV * c];
+    hipLaunchKernelGGL(k_emission_response<T>, dim3(S), dim3(LEVEL_NT), lds, st, N, ns, S, K, comps, nV, pa, A, Tmm, B, bstride, up, dn,
+                       (T*)nullptr, (T*)nullptr, status);
+    VSM_LAUNCH_CHECK("k_emission_response");
+    return VSM_OK;
+  }
+  // more viewing angles than one table carries: the vectors at all streams, then the row products in chunks of 64 angles
+  const size_t full_elems = (size_t)K * S * N;
+  T* full = static_cast<T*>(scratch(2 * full_elems * sizeof(T), 0, st));
+  if (!full) return VSM_ERR_HIP;
+  hipLaunchKernelGGL(k_emission_response<T>, dim3(S), dim3(LEVEL_NT), lds, st, N, ns, S, K, comps, 0, pa, A, Tmm, B, bstride, up, dn, full,
+                     full + full_elems, status);
+  VSM_LAUNCH_CHECK("k_emission_response");
+  for (int v0 = 0; v0 < nV; v0 += 64) {
+    const int nc = nV - v0 < 64 ? nV - v0 : 64;
+    for (int v = 0; v < nc; ++v) pa.row0[v] = row0_h[v0 + v];
+    for (int c = 0; c < ns; ++c)
+      for (int v = 0; v < nc; ++v) pa.w[v + nc * c] = (double)w_h[v0 + v + nV * c];
+    const long long tot = (long long)nc * ns * S * K;
+    hipLaunchKernelGGL(k_emission_rows<T>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, N, ns, (long long)S, K, nc, nV, v0, pa,
+                       Tmm, full, full + full_elems, up, dn);
+    VSM_LAUNCH_CHECK("k_emission_rows");
+  }
+  return VSM_OK;
+}
+
+template <typename T>
+static int emission_response_check(int N, int ns, int S, int K, const int* comp_h, int nV, const int* row0_h, const T* w_h, const T* A,
+                                   const T* Tmm, const T* B, long long bstride, const T* up, const T* dn) {
+  VSM_REQUIRE(K >= 1 && K <= 4, "surface_emission_response: K = %d outside 1..4", K);
+  const int rc = level_check_common<T>("surface_emission_response", N, LEVEL_FUSED_MAX_N, ns, S, nV, row0_h, w_h, bstride, up, dn);
+  if (rc) return rc;
+  VSM_REQUIRE(comp_h, "surface_emission_response: null component list");
+  for (int k = 0; k < K; ++k)
+    VSM_REQUIRE(comp_h[k] >= 0 && comp_h[k] < ns, "surface_emission_response: component %d = %d outside 0..%d", k, comp_h[k], ns - 1);
+  VSM_REQUIRE(S == 0 || (A && Tmm && B), "surface_emission_response: null operand");
+  return VSM_OK;
+}
+
 }  // namespace vsm
 
 using namespace vsm;
@@ -789,5 +931,18 @@ VSM_LEVEL_LIN_API(float, f32)
   }
 VSM_LEVEL_LIN_SRC_API(double, f64)
 VSM_LEVEL_LIN_SRC_API(float, f32)
+
+#define VSM_EMISSION_RESPONSE_API(T, SFX)                                                                                       \
+  int vsm_surface_emission_response_##SFX(int N, int n_stokes, int S, int K, const int* comp_h, int nV, const int* row0_h,      \
+                                          const T* w_h, const T* top_R_pm, const T* top_T_mm, const T* bot_R_mp,               \
+                                          long long bot_stride, T* up, T* dn, void* stream) {                                  \
+    int rc = emission_response_check<T>(N, n_stokes, S, K, comp_h, nV, row0_h, w_h, top_R_pm, top_T_mm, bot_R_mp, bot_stride,  \
+                                        up, dn);                                                                               \
+    if (rc || S == 0 || nV == 0) return rc;                                                                                    \
+    return emission_response_fused<T>(N, n_stokes, S, K, comp_h, nV, row0_h, w_h, top_R_pm, top_T_mm, bot_R_mp, bot_stride,    \
+                                      up, dn, as_stream(stream));                                                              \
+  }
+VSM_EMISSION_RESPONSE_API(double, f64)
+VSM_EMISSION_RESPONSE_API(float, f32)
 
 }  // extern "C"

@@ -824,7 +824,29 @@ int postprocess_vza_hdrf(int N, int ns, int S, int nV, const int* row0_h, const 
   return VSM_OK;
 }
 
+// ---- SurfaceSIF: hemispheric isotropic emission at the lower boundary (Sources/surface_sif.jl:168-179; the same statement as
+// inject_surface_SIF!, Surfaces/lambertian_surface.jl:239-254): j0-[i n + c, s] += 2 SIF0[c, s] at every stream i.  One thread per
+// (row, point), the row axis fastest: j0- [N, 1, S] is read and written in consecutive addresses, the n_stokes values of a point
+// come out of the cache.  Nothing else of the layer is touched.  sif: [n_stokes][S], the spectral axis contiguous. ----
+template <typename T>
+__global__ void __launch_bounds__(256) k_surface_sif(int N, int ns, long long S, const T* __restrict__ sif, T* __restrict__ j0_m) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (long long)N * S) return;
+  const long long s = e / N;
+  const int c = (int)(e - s * N) % ns;
+  j0_m[e] += T(2) * sif[(long long)c * S + s];
+}
+template <typename T>
+int surface_sif(int N, int ns, int S, const T* sif, const added<T>& a, hipStream_t st) {
+  if (S <= 0) return VSM_OK;
+  const long long tot = (long long)N * S;
+  hipLaunchKernelGGL(k_surface_sif<T>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, N, ns, (long long)S, sif, a.j0_m);
+  VSM_LAUNCH_CHECK("k_surface_sif");
+  return VSM_OK;
+}
+
 #define VSM_INST_SURF(T)                                                                                                     \
+  template int surface_sif<T>(int, int, int, const T*, const added<T>&, hipStream_t);                                        \
   template int coxmunk_reflectance<T>(const cm_surf<T>&, int, int, const T*, int, int, const T*, const T*, T*, T*, hipStream_t); \
   template int brdf_surface<T>(const quad<T>&, int, int, const T*, const T*, const added<T>&, hipStream_t);                   \
   template int lambertian_surface_spectral<T>(const quad<T>&, int, int, const T*, const T*, const added<T>&, hipStream_t);    \

@@ -511,6 +511,76 @@ class ThermalEmission:
         self.B_layer_dot = B_layer_dot
 
 
+class SurfaceSIF:
+    """SurfaceSIF (Sources/surface_sif.jl): solar-induced fluorescence, hemispheric isotropic emission at the lower boundary.
+    `SIF0` [nSpec] (Stokes I only) or [nStokes, nSpec]: j0- of the surface layer receives 2 SIF0[c, s] at every stream, at
+    Fourier moment m = 0, over the Lambertian surfaces (LambertianSurfaceScalar / Legendre / Spline) only -- over any other
+    surface the source does nothing, as in the reference's dispatch table, and the scene warns once.  The radiance is linear in
+    SIF0.
+
+    `SIF0_dot` [nSIF, nSpec] or [nSIF, nStokes, nSpec] (default None): the derivative tables dSIF0 / dx_k of nSIF user parameters
+    (an amplitude, a spectral slope, ...).  Only the linearized run reads them (CoreRTLin.rt_run_lin: the SIF slots, appended
+    after the Planck slots of Rdot / Tdot)."""
+
+    def __init__(self, SIF0, SIF0_dot=None):
+        from ._lib import VSMError
+        SIF0 = np.asarray(SIF0, dtype=np.float64)
+        if SIF0.ndim not in (1, 2):
+            raise VSMError("SurfaceSIF: SIF0 must be [nSpec] or [nStokes, nSpec], got %d dimensions" % SIF0.ndim)
+        if SIF0.ndim == 2 and not 1 <= SIF0.shape[0] <= 4:
+            raise VSMError("SurfaceSIF: SIF0 has %d Stokes rows (1..4)" % SIF0.shape[0])
+        self.SIF0 = SIF0
+        if SIF0_dot is not None:
+            SIF0_dot = np.asarray(SIF0_dot, dtype=np.float64)
+            if SIF0_dot.ndim not in (2, 3):
+                raise VSMError("SurfaceSIF: SIF0_dot must be [nSIF, nSpec] or [nSIF, nStokes, nSpec], got %d dimensions" % SIF0_dot.ndim)
+            if SIF0_dot.shape[-1] != SIF0.shape[-1]:
+                raise VSMError("SurfaceSIF: SIF0_dot has %d spectral points, SIF0 %d" % (SIF0_dot.shape[-1], SIF0.shape[-1]))
+            if SIF0_dot.ndim == 3 and SIF0.ndim == 2 and SIF0_dot.shape[1] != SIF0.shape[0]:
+                raise VSMError("SurfaceSIF: SIF0_dot has %d Stokes rows, SIF0 %d" % (SIF0_dot.shape[1], SIF0.shape[0]))
+        self.SIF0_dot = SIF0_dot
+
+    @property
+    def nSIF(self) -> int:
+        return 0 if self.SIF0_dot is None else int(self.SIF0_dot.shape[0])
+
+    @staticmethod
+    def _rows(tab, what, n_stokes, nSpec):
+        """[..., nSpec] (Stokes I only) or [..., rows, nSpec] -> [..., n_stokes, nSpec] of a model with n_stokes components."""
+        from ._lib import VSMError
+        full = tab.ndim == (3 if what == "SIF0_dot" else 2)
+        if tab.shape[-1] != nSpec:
+            raise VSMError("SurfaceSIF: %s has %d spectral points, the model %d" % (what, tab.shape[-1], nSpec))
+        if full and tab.shape[-2] != n_stokes:
+            raise VSMError("SurfaceSIF: %s has %d Stokes rows, the model %d" % (what, tab.shape[-2], n_stokes))
+        if full:
+            return tab
+        out = np.zeros(tab.shape[:-1] + (n_stokes, nSpec))
+        out[..., 0, :] = tab
+        return out
+
+    def table(self, n_stokes: int, nSpec: int) -> np.ndarray:
+        """SIF0 as [n_stokes, nSpec] of a model (VSMError on a shape the model does not have)."""
+        return self._rows(self.SIF0, "SIF0", n_stokes, nSpec)
+
+    def dot_tables(self, n_stokes: int, nSpec: int) -> np.ndarray:
+        """SIF0_dot as [nSIF, n_stokes, nSpec] ([0, n_stokes, nSpec] without tables)."""
+        if self.SIF0_dot is None:
+            return np.zeros((0, n_stokes, nSpec))
+        return self._rows(self.SIF0_dot, "SIF0_dot", n_stokes, nSpec)
+
+    def has_uv(self) -> bool:
+        """Does SIF0 or a derivative table set a U or V row?  (Such a source drives the (U,V) block of moment m = 0.)"""
+        uv = lambda t, full: bool(full and t.shape[-2] > 2 and np.any(t[..., 2:, :] != 0))
+        return uv(self.SIF0, self.SIF0.ndim == 2) or (self.SIF0_dot is not None and uv(self.SIF0_dot, self.SIF0_dot.ndim == 3))
+
+    def stokes_iq(self) -> "SurfaceSIF":
+        """The source of the Stokes_IQ sub-scene of moment m = 0: the I, Q rows (callers check has_uv() first)."""
+        cut = lambda t, full: t[..., :2, :] if full else t
+        return SurfaceSIF(cut(self.SIF0, self.SIF0.ndim == 2),
+                          None if self.SIF0_dot is None else cut(self.SIF0_dot, self.SIF0_dot.ndim == 3))
+
+
 @dataclass
 class RTModel:
     """The fields of the reference's RTModel that rt_run consumes on this path (one band)."""
@@ -532,7 +602,7 @@ class RTModel:
     numerics: RTNumericalParameters = field(default_factory=RTNumericalParameters)
     F0: Optional[np.ndarray] = None   # [nStokes, S]; None = SolarBeam default e1
     surface: Optional[object] = None  # LambertianSurfaceScalar | CoxMunkSurface; None = LambertianSurfaceScalar(albedo)
-    sources: Optional[Sequence] = None   # None = (SolarBeam(),); e.g. (ThermalEmission(...),) or (SolarBeam(), ThermalEmission(...))
+    sources: Optional[Sequence] = None   # None = (SolarBeam(),); e.g. (ThermalEmission(...),), (SolarBeam(), ThermalEmission(...)), (SolarBeam(), SurfaceSIF(...))
 
     def __post_init__(self):
         if self.surface is None:
