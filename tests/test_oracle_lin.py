@@ -114,3 +114,44 @@ def test_aerosol_jacobians_match_finite_differences(pol):
             scale = np.abs(fd).max()
             assert scale > 0
             assert np.abs(an - fd).max() <= 5e-6 * scale, (pol, k, name, np.abs(an - fd).max() / scale)
+
+
+def test_fp32_storage_reference_of_the_doubling_kernels():
+    """doubling_lin_storage (tests/test_gpu_lin_kernels.py), the reference of the FP32-storage doubling kernels: with float64
+    "storage" it is OL.doubling_lin bit for bit; with float32 storage -- the ekl table and the derivative source vectors rounded
+    between the steps -- it differs from OL.doubling_lin in the derivative source vectors only, by less than 4 * 2^-23 of their
+    maximum."""
+    import copy
+    from tests.test_gpu_lin_kernels import EPS32, FWD_A, LIN_A, MU0, doubling_inputs, doubling_lin_storage, stokes_for
+    S, P, nd = 3, 2, 2
+    for N in (1, 16, 33, 60, 96, 128):
+        pol = stokes_for(N)
+        add, al, expk, dall = doubling_inputs(np.random.default_rng(N), N, S, P, np.float32)
+        runs = {}
+        for name, f in (("oracle", lambda a, l: OL.doubling_lin(pol, expk, nd, a, l, dall, MU0, 0, np.float64)),
+                        ("storage64", lambda a, l: doubling_lin_storage(pol, expk, nd, a, l, dall, MU0, 0, np.float64)),
+                        ("storage32", lambda a, l: doubling_lin_storage(pol, expk, nd, a, l, dall, MU0, 0, np.float32))):
+            a, l = copy.deepcopy(add), copy.deepcopy(al)
+            f(a, l)
+            runs[name] = {**{k: getattr(a, k) for k in FWD_A}, **{k: getattr(l, k) for k in LIN_A}}
+        for k, ref in runs["oracle"].items():
+            assert np.array_equal(runs["storage64"][k], ref), (N, k)
+            if k in ("ap_J0_p", "ap_J0_m"):
+                d = np.abs(runs["storage32"][k] - ref).max() / np.abs(ref).max()
+                assert 0 < d < 4 * EPS32, (N, k, d / EPS32)
+            else:
+                assert np.array_equal(runs["storage32"][k], ref), (N, k)
+
+
+def test_ill_conditioned_cases_keep_their_tolerance():
+    """The cases of test_interaction_lin_pivoted_inverse_near_and_beyond_unit_spectral_radius hit their spectral radius and keep
+    the derivative tolerance max(1e-9, 50 cond^2 eps) below 1e-6 -- no rho of the list had to be dropped."""
+    from tests.test_gpu_lin_kernels import ill_conditioned_layers
+    for N in (24, 64, 72, 128):
+        for rho in (0.9, 0.97, 0.995, 1.7):
+            (comp, add, _, _), cond = ill_conditioned_layers(N, rho)
+            for s in range(3):
+                assert abs(np.max(np.abs(np.linalg.eigvals(add.r_mp[s] @ comp.R_pm[s]))) - rho) < 1e-9
+            tol = max(1e-9, 50 * cond ** 2 * np.finfo(np.float64).eps)
+            print("N = %d, rho = %g: cond %.4g, derivative tolerance %.3g" % (N, rho, cond, tol))
+            assert tol < 1e-6, (N, rho, cond)
