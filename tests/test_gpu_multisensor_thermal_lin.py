@@ -335,7 +335,7 @@ def test_model_without_the_source_takes_the_parent_path(vsm, arch, monkeypatch):
     monkeypatch.setattr(CL.SceneLin, "__init__", spy)
     levels = [0, 2, 6]
     calls, first = _count_calls(vsm, lambda: CL.rt_run_multisensor(pm, pl, 0, 1, 1, levels))
-    assert scenes and all(sc._th is None and getattr(sc.fwd, "_th_added", None) is None and sc.nPlanck == 0 for sc in scenes)
+    assert scenes and all(sc._th is None and sc.fwd._thermal is None and sc.nPlanck == 0 for sc in scenes)
     assert not {"vsm_thermal_source_lin", "vsm_thermal_source", "vsm_layer_forward_thermal", "vsm_level_radiance_lin_src"} & set(calls)
     nm = pm.m_max + 1
     assert calls.count("vsm_level_radiance_lin") == 2 * nm and calls.count("vsm_level_radiance") == 2 * nm

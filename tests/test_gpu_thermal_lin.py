@@ -357,7 +357,7 @@ def test_model_without_thermal_source_allocates_and_launches_nothing_new(vsm, ar
         vsm._lib.call = orig
     torch.cuda.synchronize()
     assert "vsm_thermal_source_lin" not in calls and "vsm_thermal_source" not in calls and "vsm_layer_forward_thermal" not in calls
-    assert scene._th is None and scene.nPlanck == 0 and getattr(scene.fwd, "_th_added", None) is None
+    assert scene._th is None and scene.nPlanck == 0 and scene.fwd._thermal is None
     assert first[2].shape[0] == 3
     again = scene.run(lanes=1, fold=False)
     torch.cuda.synchronize()

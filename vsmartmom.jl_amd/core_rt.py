@@ -18,6 +18,7 @@ contiguous tensor of shape (S, N, N) whose slice [s] holds the matrix
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import dataclasses
 import math
@@ -231,6 +232,19 @@ class CompositeLayer:
         finally:
             _lib.lib().vsm_run_destroy(slot.run)
         return self
+
+    def snapshot_top(self):
+        """Clones of (R+-, J0+) of a composite in the middle of its walk, without disturbing the walk: a composite that rt_kernel_
+        keeps in native layout is exported (vsm_run_export leaves the run as it is) instead of materialised (which would end the
+        run)."""
+        slot = self._native
+        if slot is not None:
+            cc = (_lib.vsm_composite * 1)(self._cstruct_raw())
+            _lib.call("vsm_run_export", self.dtype, slot.run, cc, _stream_ptr())
+            a = self._arr
+        else:
+            a = self.materialize()._arr
+        return a["R_pm"].clone(), a["J0_p"].clone()
 
     def drop_native(self):
         """Forget the native copy without exporting it (a TOA layer overwrites the composite)."""
@@ -531,38 +545,37 @@ def apply_ss_correction_(R_SFI: torch.Tensor, surf: H.CoxMunkSurface, pol, vza, 
     return coef
 
 
-def postprocessing_vza_(pol: H.PolarizationType, comp: CompositeLayer, vza, vaz, qp: H.QuadPoints, m: int, weight: float,
-                        R_SFI: torch.Tensor, T_SFI: torch.Tensor):
-    """postprocessing_vza! noRS / SFI (postprocessing_vza.jl:23-94).  R_SFI/T_SFI: (S, nStokes, nVZA) layout tensors
-    of the reference's [nVZA, nStokes, nSpec] arrays."""
-    n, nV = pol.n, len(vza)
-    row0 = (C.c_int * nV)()
-    ctype = C.c_double if comp.dtype == torch.float64 else C.c_float
-    w = (ctype * (nV * n))()
-    for v in range(nV):
-        imu = int(np.argmin(np.abs(qp.qp_mu - qp.qp_mu.dtype.type(H.cosd(vza[v])))))
-        row0[v] = imu * n
-        c, s = H.cosd(m * vaz[v]), H.sind(m * vaz[v])
-        ws = [c, c, s, s][:n]
-        for k in range(n):
-            w[v + nV * k] = weight * ws[k]
-    _lib.call("vsm_postprocess_vza", comp.dtype, comp.N, n, comp.nSpec, nV, row0, w, _ptr(comp.J0_m), _ptr(comp.J0_p),
-              _ptr(R_SFI), _ptr(T_SFI), _stream_ptr())
+def fourier_weight(FT, m: int):
+    """The weight of Fourier moment m in the azimuthal sum (rt_run.jl:384): 0.5 / pi for m = 0, 1 / pi for every other."""
+    return FT(0.5 / math.pi) if m == 0 else FT(1.0 / math.pi)
+
+
+def _vza_nodes(vza, qp) -> list:
+    """The quadrature node of each viewing zenith angle (the index rule of postprocessing_vza!): the nearest one."""
+    return [int(np.argmin(np.abs(qp.qp_mu - qp.qp_mu.dtype.type(H.cosd(v))))) for v in vza]
 
 
 def _vza_rows_weights(pol, vza, vaz, qp, m, weight, dtype):
     """_precompute_vza_weights (postprocessing_vza.jl): first row of each viewing stream and weight * {cos, cos, sin, sin}(m vaz)."""
     n, nV = pol.n, len(vza)
-    row0 = (C.c_int * nV)()
+    row0 = (C.c_int * nV)(*[imu * n for imu in _vza_nodes(vza, qp)])
     ctype = C.c_double if dtype == torch.float64 else C.c_float
     w = (ctype * (nV * n))()
     for v in range(nV):
-        imu = int(np.argmin(np.abs(qp.qp_mu - qp.qp_mu.dtype.type(H.cosd(vza[v])))))
-        row0[v] = imu * n
         c, s = H.cosd(m * vaz[v]), H.sind(m * vaz[v])
         for k in range(n):
             w[v + nV * k] = weight * [c, c, s, s][k]
     return row0, w
+
+
+def postprocessing_vza_(pol: H.PolarizationType, comp: CompositeLayer, vza, vaz, qp: H.QuadPoints, m: int, weight: float,
+                        R_SFI: torch.Tensor, T_SFI: torch.Tensor):
+    """postprocessing_vza! noRS / SFI (postprocessing_vza.jl:23-94).  R_SFI/T_SFI: (S, nStokes, nVZA) layout tensors
+    of the reference's [nVZA, nStokes, nSpec] arrays."""
+    n, nV = pol.n, len(vza)
+    row0, w = _vza_rows_weights(pol, vza, vaz, qp, m, weight, comp.dtype)
+    _lib.call("vsm_postprocess_vza", comp.dtype, comp.N, n, comp.nSpec, nV, row0, w, _ptr(comp.J0_m), _ptr(comp.J0_p),
+              _ptr(R_SFI), _ptr(T_SFI), _stream_ptr())
 
 
 def interaction_hdrf_(pol, comp: CompositeLayer, added_surface: AddedLayer, m: int, dq: DeviceQuad, vza, vaz, qp, weight: float,
@@ -646,8 +659,7 @@ def view_rows_of(pol, vza, qp) -> list:
     """The rows of the composite that postprocessing_vza_ reads (its index rule): the n_stokes rows of each VZA's quadrature node,
     each node once."""
     n, rows = pol.n, []
-    for v in range(len(vza)):
-        imu = int(np.argmin(np.abs(qp.qp_mu - qp.qp_mu.dtype.type(H.cosd(vza[v])))))
+    for imu in _vza_nodes(vza, qp):
         rows += [imu * n + k for k in range(n) if imu * n + k not in rows]
     return rows
 
@@ -818,7 +830,7 @@ class Scene:
         th = [s_ for s_ in srcs if isinstance(s_, H.ThermalEmission) and s_.B_layer is not None and np.any(s_.B_layer != 0)]
         self.thermal_B = None
         self.thermal_reset_noscat = bool(th and th[0].reset_slot_in_nonscattering_layers)
-        self._thermal_carry = False
+        self._thermal = None      # the slot's ThermalSlot, allocated on first use (thermal_slot())
         if th:
             B = th[0].B_layer
             if B.shape[1] != S_full:
@@ -1069,12 +1081,7 @@ class Scene:
         # zero_added_noscat! never writes it, rt_helpers.jl:174-180 -- which ties the moments to their sequential order)
         eps2 = 2 * np.finfo(FT).eps
         has_noscat = any(ly["props"].max_tau_varpi <= eps2 for ly in self.moments[0]["layers"])
-        sequential = trace is not None or not MOMENT_BATCHING or has_noscat or REFERENCE_ORDER
-        # small batches are launch-latency bound (C3: 2 points, 22 moments x 33 layers): as many moments per launch as fill the chip
-        want = max(MOMENT_BATCH, min(MOMENT_BATCH_MAX, 4096 // max(self.S, 1)))
-        nb = 1 if sequential else min(want, len(self.moments))
-        while len(self._composites) < nb:
-            self._composites.append(make_composite_layer(FT, self.arch, (self.N, self.N), self.S))
+        nb = self._group_size(trace is not None or not MOMENT_BATCHING or has_noscat or REFERENCE_ORDER)
         # (REFERENCE_ORDER: every layer step is an rt_kernel_ call on the ONE CompositeLayer, like the reference's driver; the native
         # layout is then reached through rt_kernel_'s per-composite registry, NATIVE_DROPIN, instead of _run_layers_native)
         native = self._native_moments() if trace is None and not has_noscat and not REFERENCE_ORDER else set()
@@ -1086,55 +1093,92 @@ class Scene:
         if getattr(self, "_view_rows", None) is None:      # (the quadrature and the VZAs are the scene's: computed once)
             self._view_rows = view_rows_of(pol, model.vza, self.qp)
         view_rows = self._view_rows if streams is None else None
-        for c in self._composites:
-            c._sources_only = walk_src and REFERENCE_ORDER
-            c._view_rows = view_rows if c._sources_only else None
-        for g0 in range(0, len(self.moments), nb):
-            group = self.moments[g0:g0 + nb]
-            comps = self._composites[:len(group)]
-            nat = [k for k in range(len(group)) if (g0 + k) in native]
-            if nat:   # the layer loop on the native-layout composite (vsm_run_*), then the reference's arrays for the surface step
-                self._run_layers_native([group[k] for k in nat], [comps[k] for k in nat], sources_only=streams is None,
-                                        view_rows=view_rows)
-            rest = [k for k in range(len(group)) if (g0 + k) not in native]
-            group_l, comps_l = [group[k] for k in rest], [comps[k] for k in rest]
-            for iz in range(self.Nz if rest else 0):
-                ly0 = group_l[0]["layers"][iz]
-                if len(group_l) > 1 and ly0["props"].max_tau_varpi > eps2 and (iz == 0 or ly0["iface"] == "11"):
-                    layer_forward_multi_(ly0["tau_sum"], ly0["dtau"], self.F0, [mom["layers"][iz]["props"] for mom in group_l],
-                                         [mom["m"] for mom in group_l], ly0["nd"], self.dq, iz == 0, comps_l, self.added)
-                    continue
-                for mom, comp in zip(group_l, comps_l):
-                    ly = mom["layers"][iz]
-                    rt_kernel_(pol, self.added, comp, ly["props"], ly["iface"], ly["tau_sum"], mom["m"], self.dq,
-                               self.arch, iz + 1, self.F0, FT, model.numerics, dtau=ly["dtau"], ndoubl=ly["nd"], trace=trace,
-                               work=self.work, keep_added=has_noscat)
-            for mom, comp in zip(group, comps):
-                m = mom["m"]
-                weight = FT(0.5 / math.pi) if m == 0 else FT(1.0 / math.pi)
-                create_surface_layer_(model.surface, self.added_surface, m, self.dq, mom["tau_sum_surface"], rho=mom["rho"])
-                surface_source_contribute_(self, model.surface, self.added_surface, m)
-                interaction_(mom["iface_surface"], comp, self.added_surface, work=self.work)
-                if self.compute_hdrf:
-                    interaction_hdrf_(pol, comp, self.added_surface, m, self.dq, model.vza, model.vaz, self.qp, float(weight),
-                                      self.hdr_J, self.hdr, self.bhr_uw, self.bhr_dw)
-                postprocessing_vza_(pol, comp, model.vza, model.vaz, self.qp, m, float(weight), self.R_SFI, self.T_SFI)
-                thermal_pass = self.thermal_B is not None and (m == 0 or (m == 1 and self._thermal_carry))
-                if thermal_pass:
-                    self._thermal_slot(mom, float(weight))
-                if streams is not None:
-                    Jm, Jp = comp.J0_m.clone(), comp.J0_p.clone()
+        with self._walk_composites(nb, walk_src and REFERENCE_ORDER, view_rows):
+            for g0 in range(0, len(self.moments), nb):
+                group = self.moments[g0:g0 + nb]
+                comps = self._composites[:len(group)]
+                self._walk_layers(group, comps, [k for k in range(len(group)) if (g0 + k) in native], sources_only=streams is None,
+                                  view_rows=view_rows, trace=trace, keep_added=has_noscat)
+                for mom, comp in zip(group, comps):
+                    m = mom["m"]
+                    weight = float(fourier_weight(FT, m))
+                    create_surface_layer_(model.surface, self.added_surface, m, self.dq, mom["tau_sum_surface"], rho=mom["rho"])
+                    surface_source_contribute_(self, model.surface, self.added_surface, m)
+                    interaction_(mom["iface_surface"], comp, self.added_surface, work=self.work)
+                    if self.compute_hdrf:
+                        interaction_hdrf_(pol, comp, self.added_surface, m, self.dq, model.vza, model.vaz, self.qp, weight,
+                                          self.hdr_J, self.hdr, self.bhr_uw, self.bhr_dw)
+                    postprocessing_vza_(pol, comp, model.vza, model.vaz, self.qp, m, weight, self.R_SFI, self.T_SFI)
+                    thermal_pass = self.thermal_B is not None and (m == 0 or (m == 1 and self.thermal_slot().carry))
                     if thermal_pass:
-                        Jm += self._th_comp.J0_m
-                        Jp += self._th_comp.J0_p
-                    streams.append(dict(m=m, weight=float(weight), R_mp=comp.R_mp.clone(), T_pp=comp.T_pp.clone(), J0_m=Jm, J0_p=Jp))
-        for c in self._composites:
-            c._sources_only = False
-            c._view_rows = None
+                        self._thermal_slot(mom, weight)
+                    if streams is not None:
+                        Jm, Jp = comp.J0_m.clone(), comp.J0_p.clone()
+                        if thermal_pass:
+                            Jm += self._thermal.comp.J0_m
+                            Jp += self._thermal.comp.J0_p
+                        streams.append(dict(m=m, weight=weight, R_mp=comp.R_mp.clone(), T_pp=comp.T_pp.clone(), J0_m=Jm, J0_p=Jp))
         if isinstance(model.surface, H.CoxMunkSurface) and self.ss_correction:   # rt_run.jl:520-524 (SFI is always on here)
             apply_ss_correction_(self.R_SFI, model.surface, pol, model.vza, model.vaz, self.qp.mu0,
                                  self.moments[-1]["tau_sum_surface"], model.m_max, self.arch, FT)
         return self.R_SFI, self.T_SFI
+
+    def _group_size(self, sequential: bool) -> int:
+        """Fourier moments per group of a layer walk (1: moment by moment).  Small batches are launch-latency bound (C3: 2 points,
+        22 moments x 33 layers): as many moments per launch as fill the chip."""
+        want = max(MOMENT_BATCH, min(MOMENT_BATCH_MAX, 4096 // max(self.S, 1)))
+        return 1 if sequential else min(want, len(self.moments))
+
+    @contextlib.contextmanager
+    def _walk_composites(self, nb: int, sources_only: bool, view_rows):
+        """The composites of a walk in groups of nb moments (allocated on first use), flagged for the walk: sources_only -- the
+        native copy rt_kernel_ keeps of them may be a sources-only run -- and with it view_rows, the rows of T-- / J0- the walk
+        reads.  The flags are cleared on the way out, whatever happened: a flagged composite hands NaN rows to its next reader."""
+        while len(self._composites) < nb:
+            self._composites.append(make_composite_layer(self.FT, self.arch, (self.N, self.N), self.S))
+        for c in self._composites:
+            c._sources_only = bool(sources_only)
+            c._view_rows = view_rows if sources_only else None
+        try:
+            yield
+        finally:
+            for c in self._composites:
+                c._sources_only = False
+                c._view_rows = None
+
+    def _walk_layers(self, group, comps, nat, sources_only: bool, view_rows, trace=None, keep_added: bool = False, tops_at=(),
+                     keep_top=None):
+        """The top pass: the layers of the moments `group` into their composites `comps`.  nat: the indices (into group) of the
+        moments that walk on the native-layout composite (vsm_run_*, _run_layers_native with sources_only / view_rows), exported
+        into the reference's arrays at the end; the others take a scattering "11" / TOA layer as ONE call for all of them
+        (vsm_layer_forward_multi) and rt_kernel_ (trace, keep_added) otherwise.  keep_top(k, l, (R+-, J0+)): called for every l of
+        tops_at once layer l (1-based) has joined composite k of the group, with clones of its operators (the multi-sensor run
+        keeps its tops there)."""
+        eps2 = 2 * np.finfo(self.FT).eps
+        if nat:
+            def export(l):
+                def cb(cs):
+                    for k, c in zip(nat, cs):
+                        keep_top(k, l, (c._arr["R_pm"].clone(), c._arr["J0_p"].clone()))
+                return cb
+            self._run_layers_native([group[k] for k in nat], [comps[k] for k in nat], sources_only=sources_only,
+                                    export_at={l: export(l) for l in tops_at}, view_rows=view_rows)
+        rest = [k for k in range(len(group)) if k not in nat]
+        group_l, comps_l = [group[k] for k in rest], [comps[k] for k in rest]
+        for iz in range(self.Nz if rest else 0):
+            ly0 = group_l[0]["layers"][iz]
+            if len(group_l) > 1 and ly0["props"].max_tau_varpi > eps2 and (iz == 0 or ly0["iface"] == "11"):
+                layer_forward_multi_(ly0["tau_sum"], ly0["dtau"], self.F0, [mom["layers"][iz]["props"] for mom in group_l],
+                                     [mom["m"] for mom in group_l], ly0["nd"], self.dq, iz == 0, comps_l, self.added)
+            else:
+                for mom, comp in zip(group_l, comps_l):
+                    ly = mom["layers"][iz]
+                    rt_kernel_(self.pol, self.added, comp, ly["props"], ly["iface"], ly["tau_sum"], mom["m"], self.dq, self.arch,
+                               iz + 1, self.F0, self.FT, self.model.numerics, dtau=ly["dtau"], ndoubl=ly["nd"], trace=trace,
+                               work=self.work, keep_added=keep_added)
+            if iz + 1 in tops_at:
+                for k, comp in zip(rest, comps_l):
+                    keep_top(k, iz + 1, comp.snapshot_top())
 
     def _native_moments(self):
         """Indices of the Fourier moments whose layer loop runs on the native-layout composite (vsm_run_*): every layer scattering
@@ -1193,104 +1237,19 @@ class Scene:
         finally:
             L.vsm_run_destroy(run)
 
+    def thermal_slot(self) -> "ThermalSlot":
+        """The state of the `:thermal` per-source slot, allocated on first use (a model without the source never asks)."""
+        if self._thermal is None:
+            self._thermal = ThermalSlot(self)
+        return self._thermal
+
     def _thermal_slot(self, mom, weight):
-        """The `:thermal` per-source slot (rt_kernel.jl:204-232, doubling.jl:62-81, interaction.jl per-source recurrences,
-        postprocessing_vza.jl:68-82): the solar slot's linear source recurrences driven by the thermal source
-        (vsm_thermal_source between elemental! and doubling!, the slot's own expk = 1); its J0 is added to R_SFI / T_SFI.
-        On an AddedLayer / CompositeLayer of its own (r, t, R, T evolve exactly like the solar pass's): walk layers 1..Nz
-        (_thermal_walk), surface (_thermal_surface), post-process.
-
-        State, as the reference carries it (default; ThermalEmission(reset_slot_in_nonscattering_layers=True) = the corrected
-        variant): the slot's j0+- belong to the AddedLayer that is allocated once per run (rt_run.jl:326-335); only the scatter
-        branch resets them (rt_kernel.jl:217-221), so a non-scattering layer interacts with the doubled slot of the last
-        scattering layer before it, and a column that begins with non-scattering layers enters moment m = 1 with the slot the
-        last scattering layer of moment m = 0 left behind -- that is the one case in which this pass runs for m = 1 (contribute!
-        itself is m = 0 only; with a zero slot on entry every later moment stays zero)."""
-        self._thermal_begin(mom)
-        comp = self._th_comp
-        self._thermal_walk(mom, comp, 0, self.Nz)
-        surf = self._thermal_surface(mom)
-        interaction_(mom["iface_surface"], comp, surf, oplevel=True, work=self.work)
-        postprocessing_vza_(self.pol, comp, self.model.vza, self.model.vaz, self.qp, mom["m"], weight, self.R_SFI, self.T_SFI)
-
-    def _thermal_begin(self, mom):
-        """The slot's own layers (allocated on first use) and, for m = 0, the slot state of a fresh AddedLayer."""
-        N, S, FT = self.N, self.S, self.FT
-        if getattr(self, "_th_added", None) is None:
-            self._th_added = make_added_layer(FT, self.arch, (N, N), S, d_symmetric=0)
-            self._th_surf = make_added_layer(FT, self.arch, (N, N), S, shared=not self.spectral_surface)
-            self._th_comp = make_composite_layer(FT, self.arch, (N, N), S)
-            self._th_F0 = torch.zeros_like(self.F0)
-            self._th_ones = torch.ones(max(S, 1), dtype=self.dt, device=self.dev)
-        if mom["m"] == 0:
-            eps2 = 2 * np.finfo(FT).eps
-            scat = [ly["props"].max_tau_varpi > eps2 for ly in mom["layers"]]
-            self._th_added.j0_p.zero_()                      # a fresh AddedLayer (rt_run.jl:326-335)
-            self._th_added.j0_m.zero_()
-            self._thermal_carry = (not self.thermal_reset_noscat and any(scat) and not scat[0] and self.model.m_max >= 1)
-
-    def _thermal_walk(self, mom, comp, first, end, after=None):
-        """Layers first+1 .. end (1-based) of the slot into the thermal composite `comp`, the first one a copy.  The slot has
-        expk = 1 and no beam attenuation, so a range that starts below the TOA needs no absolute tau_sum: its first layer is the
-        `first = 1` of the fused call.  after: {l: callback(comp)}, called once layer l is in the composite (like export_at of
-        _run_layers_native: the multi-sensor run takes its thermal tops there, core_rt_ms.py)."""
-        pol, FT = self.pol, self.FT
-        N, S = self.N, self.S
-        m = mom["m"]
-        added = self._th_added
-        q = self.dq.cstruct()
-        eps2 = 2 * np.finfo(FT).eps
-        scat = [ly["props"].max_tau_varpi > eps2 for ly in mom["layers"]]
-        keep_state = not self.thermal_reset_noscat          # the reference as written
-        # FP64, 32 < N <= 60 / FP32, 64 < N <= 96: a scattering layer's slot in ONE fused launch (vsm_layer_forward_thermal: the strip layer kernel
-        # with the thermal source and expk = 1; m = 0); everything else operator level, layer by layer on the same composite.  With
-        # the reference's slot state and a non-scattering layer in the column the doubled slot must stay in the AddedLayer for the
-        # layers below: no fused step then (as in the solar pass, rt_kernel_'s keep_added)
-        fused = (THERMAL_FUSION and m == 0 and (all(scat) or not keep_state)
-                 and _lib.lib().vsm_layer_thermal_fused(N, 1 if FT == np.float64 else 0) != 0)
-        for iz in range(first, end):
-            ly = mom["layers"][iz]
-            props = ly["props"]
-            scatter = scat[iz]
-            if (fused and scatter and (iz == first or ly["iface"] == "11") and iz < self.thermal_B.shape[0]
-                    and (props.fcomp is None or props.fcomp.shape[1] <= 4)):
-                c = comp.cstruct()
-                ncomp = 0 if props.fcomp is None else int(props.fcomp.shape[1])
-                _lib.call("vsm_layer_forward_thermal", self.dt, C.byref(q), S, ly["nd"], _ptr(ly["dtau"]), _ptr(props.varpi),
-                          _ptr(self.thermal_B[iz]), ncomp, _ptr(props.Zpp), _ptr(props.Zmp),
-                          0 if ncomp else props.z_stride, _ptr(props.fcomp), 1 if iz == first else 0, C.byref(c), _stream_ptr())
-            else:
-                if scatter:
-                    # elemental! with F0 = 0 leaves j0+- = 0: the slot reset of rt_kernel.jl:217-221
-                    elemental_(pol, ly["tau_sum"], ly["dtau"], self._th_F0, props.materialize(), m, ly["nd"], self.dq, added)
-                    if m == 0 and iz < self.thermal_B.shape[0]:           # contribute! (isotropic: m = 0 only)
-                        a = added.cstruct()
-                        _lib.call("vsm_thermal_source", self.dt, C.byref(q), S, _ptr(ly["dtau"]), _ptr(props.varpi),
-                                  _ptr(self.thermal_B[iz]), C.byref(a), _stream_ptr())
-                    self._th_ones.fill_(1.0)             # doubling! squares the slot's expk in place (1 stays 1)
-                    doubling_(pol, self._th_ones, ly["nd"], added)
-                elif keep_state:
-                    jm = added.j0_m.clone()              # zero_added_noscat! zeroes the SOLAR j0-, never a per-source slot
-                    zero_added_noscat_(added, props.tau, self.dq)
-                    added.j0_m.copy_(jm)
-                else:
-                    zero_added_noscat_(added, props.tau, self.dq)
-                    added.j0_p.zero_()
-                    added.j0_m.zero_()
-                if iz == first:
-                    copy_added_to_composite_(comp, added)
-                else:
-                    interaction_(ly["iface"], comp, added, oplevel=True, work=self.work)
-            if after and (iz + 1) in after:
-                after[iz + 1](comp)
-
-    def _thermal_surface(self, mom):
-        """The slot's surface layer: the solar one without its beam terms (surface emission is a separate source type: SurfaceSIF
-        is counted once, in the solar slot, and never injected here)."""
-        create_surface_layer_(self.model.surface, self._th_surf, mom["m"], self.dq, mom["tau_sum_surface"], rho=mom["rho"])
-        self._th_surf.j0_p.zero_()      # no solar beam in this slot
-        self._th_surf.j0_m.zero_()
-        return self._th_surf
+        """The `:thermal` slot of one moment for the scene's own Planck table, added to R_SFI / T_SFI (ThermalSlot)."""
+        th = self.thermal_slot()
+        th.begin(mom)
+        th.walk(mom, th.comp, 0, self.Nz, self.thermal_B)
+        th.surface(mom)
+        th.finish(mom, weight, self.R_SFI, self.T_SFI)
 
     def run_graph(self):
         """`run()` replayed from a HIP graph: the launch sequence of a scene (per moment: one launch per layer, surface,
@@ -1340,6 +1299,113 @@ class Scene:
                     tot += 24 * N ** 3 + 8 * N ** 2
             tot += 24 * N ** 3 + 8 * N ** 2  # surface interaction
         return tot
+
+
+class ThermalSlot:
+    """The `:thermal` per-source slot of a Scene (rt_kernel.jl:204-232, doubling.jl:62-81, interaction.jl per-source recurrences,
+    postprocessing_vza.jl:68-82): the solar slot's linear source recurrences driven by the thermal source (vsm_thermal_source
+    between elemental! and doubling!, the slot's own expk = 1); its J0 is added to R_SFI / T_SFI.  On an AddedLayer (`added`), a
+    surface layer (`surf`) and a CompositeLayer (`comp`) of its own (r, t, R, T evolve exactly like the solar pass's), with its
+    zero beam and its expk = 1 vector: begin, walk layers 1..Nz, surface, finish.  The Planck table is an argument of walk(): the
+    slot is linear in it, and the linearized runs walk it once per derivative table.
+
+    State, as the reference carries it (default; ThermalEmission(reset_slot_in_nonscattering_layers=True) = the corrected
+    variant): the slot's j0+- belong to the AddedLayer that is allocated once per run (rt_run.jl:326-335); only the scatter
+    branch resets them (rt_kernel.jl:217-221), so a non-scattering layer interacts with the doubled slot of the last
+    scattering layer before it, and a column that begins with non-scattering layers enters moment m = 1 with the slot the
+    last scattering layer of moment m = 0 left behind -- `carry`, the one case in which the slot runs for m = 1 (contribute!
+    itself is m = 0 only; with a zero slot on entry every later moment stays zero)."""
+
+    def __init__(self, scene: "Scene"):
+        sc = self.scene = scene
+        N, S, FT = sc.N, sc.S, sc.FT
+        self.added = make_added_layer(FT, sc.arch, (N, N), S, d_symmetric=0)
+        self.surf = make_added_layer(FT, sc.arch, (N, N), S, shared=not sc.spectral_surface)
+        self.comp = make_composite_layer(FT, sc.arch, (N, N), S)
+        self.F0 = torch.zeros_like(sc.F0)
+        self.ones = torch.ones(max(S, 1), dtype=sc.dt, device=sc.dev)
+        self.carry = False
+
+    def _scatters(self, mom):
+        eps2 = 2 * np.finfo(self.scene.FT).eps
+        return [ly["props"].max_tau_varpi > eps2 for ly in mom["layers"]]
+
+    def begin(self, mom):
+        """For m = 0, the slot state of a fresh AddedLayer."""
+        if mom["m"] == 0:
+            sc, scat = self.scene, self._scatters(mom)
+            self.added.j0_p.zero_()                      # a fresh AddedLayer (rt_run.jl:326-335)
+            self.added.j0_m.zero_()
+            self.carry = (not sc.thermal_reset_noscat and any(scat) and not scat[0] and sc.model.m_max >= 1)
+
+    def walk(self, mom, comp, first, end, B, after=None):
+        """Layers first+1 .. end (1-based) of the slot for the Planck table B (rows, S) into the thermal composite `comp`, the first
+        one a copy.  The slot has expk = 1 and no beam attenuation, so a range that starts below the TOA needs no absolute tau_sum:
+        its first layer is the `first = 1` of the fused call.  after: {l: callback(comp)}, called once layer l is in the composite
+        (like export_at of _run_layers_native: the multi-sensor run takes its thermal tops there, core_rt_ms.py)."""
+        sc = self.scene
+        pol, FT, N, S = sc.pol, sc.FT, sc.N, sc.S
+        m = mom["m"]
+        added = self.added
+        q = sc.dq.cstruct()
+        scat = self._scatters(mom)
+        keep_state = not sc.thermal_reset_noscat          # the reference as written
+        # FP64, 32 < N <= 60 / FP32, 64 < N <= 96: a scattering layer's slot in ONE fused launch (vsm_layer_forward_thermal: the strip layer kernel
+        # with the thermal source and expk = 1; m = 0); everything else operator level, layer by layer on the same composite.  With
+        # the reference's slot state and a non-scattering layer in the column the doubled slot must stay in the AddedLayer for the
+        # layers below: no fused step then (as in the solar pass, rt_kernel_'s keep_added)
+        fused = (THERMAL_FUSION and m == 0 and (all(scat) or not keep_state)
+                 and _lib.lib().vsm_layer_thermal_fused(N, 1 if FT == np.float64 else 0) != 0)
+        for iz in range(first, end):
+            ly = mom["layers"][iz]
+            props = ly["props"]
+            scatter = scat[iz]
+            if (fused and scatter and (iz == first or ly["iface"] == "11") and iz < B.shape[0]
+                    and (props.fcomp is None or props.fcomp.shape[1] <= 4)):
+                c = comp.cstruct()
+                ncomp = 0 if props.fcomp is None else int(props.fcomp.shape[1])
+                _lib.call("vsm_layer_forward_thermal", sc.dt, C.byref(q), S, ly["nd"], _ptr(ly["dtau"]), _ptr(props.varpi),
+                          _ptr(B[iz]), ncomp, _ptr(props.Zpp), _ptr(props.Zmp),
+                          0 if ncomp else props.z_stride, _ptr(props.fcomp), 1 if iz == first else 0, C.byref(c), _stream_ptr())
+            else:
+                if scatter:
+                    # elemental! with F0 = 0 leaves j0+- = 0: the slot reset of rt_kernel.jl:217-221
+                    elemental_(pol, ly["tau_sum"], ly["dtau"], self.F0, props.materialize(), m, ly["nd"], sc.dq, added)
+                    if m == 0 and iz < B.shape[0]:           # contribute! (isotropic: m = 0 only)
+                        a = added.cstruct()
+                        _lib.call("vsm_thermal_source", sc.dt, C.byref(q), S, _ptr(ly["dtau"]), _ptr(props.varpi),
+                                  _ptr(B[iz]), C.byref(a), _stream_ptr())
+                    self.ones.fill_(1.0)             # doubling! squares the slot's expk in place (1 stays 1)
+                    doubling_(pol, self.ones, ly["nd"], added)
+                elif keep_state:
+                    jm = added.j0_m.clone()              # zero_added_noscat! zeroes the SOLAR j0-, never a per-source slot
+                    zero_added_noscat_(added, props.tau, sc.dq)
+                    added.j0_m.copy_(jm)
+                else:
+                    zero_added_noscat_(added, props.tau, sc.dq)
+                    added.j0_p.zero_()
+                    added.j0_m.zero_()
+                if iz == first:
+                    copy_added_to_composite_(comp, added)
+                else:
+                    interaction_(ly["iface"], comp, added, oplevel=True, work=sc.work)
+            if after and (iz + 1) in after:
+                after[iz + 1](comp)
+
+    def surface(self, mom):
+        """The slot's surface layer: the solar one without its beam terms (surface emission is a separate source type: SurfaceSIF
+        is counted once, in the solar slot, and never injected here)."""
+        sc = self.scene
+        create_surface_layer_(sc.model.surface, self.surf, mom["m"], sc.dq, mom["tau_sum_surface"], rho=mom["rho"])
+        self.surf.j0_p.zero_()      # no solar beam in this slot
+        self.surf.j0_m.zero_()
+        return self.surf
+
+    def finish(self, mom, weight, R_SFI, T_SFI):
+        """The surface interaction of the slot's own composite and its post-processing, added to R_SFI / T_SFI."""
+        sc = self.scene
+        interaction_(mom["iface_surface"], self.comp, self.surf, oplevel=True, work=sc.work)
+        postprocessing_vza_(sc.pol, self.comp, sc.model.vza, sc.model.vaz, sc.qp, mom["m"], weight, R_SFI, T_SFI)
 
 
 def prepare_scene(model: H.RTModel, spec_slice: Optional[slice] = None) -> Scene:

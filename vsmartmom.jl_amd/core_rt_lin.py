@@ -12,7 +12,6 @@ from __future__ import annotations
 import contextlib
 import ctypes as C
 import dataclasses
-import math
 from typing import Optional
 
 import numpy as np
@@ -155,11 +154,11 @@ def brdf_surface_lin_multi_(dq: CR.DeviceQuad, S: int, m: int, rho, drho, isurf:
 
 
 _lin_work = {}
-_lane = 0   # the moment lane (stream) the calling thread launches on: work buffers are per lane
 
 
-def _work(kind, n, dtype, device):
-    key = (kind, dtype, str(device), _lane)
+def _work(kind, n, dtype, device, lane):
+    """The scratch buffer of kernel `kind` on moment lane `lane` (the stream the caller launches on): one per lane, grow-only."""
+    key = (kind, dtype, str(device), lane)
     w = _lin_work.get(key)
     if w is None or w.numel() < n:
         w = _lib.poison(torch.empty(int(n), dtype=dtype, device=device))
@@ -167,10 +166,10 @@ def _work(kind, n, dtype, device):
     return w
 
 
-def doubling_allparams_(pol, expk, ndoubl, added: CR.AddedLayer, added_lin: AddedLayerLin, dtau_dot_all, mu0, N_active):
-    """doubling_allparams! (doubling_lin.jl:216-339)."""
+def doubling_allparams_(pol, expk, ndoubl, added: CR.AddedLayer, added_lin: AddedLayerLin, dtau_dot_all, mu0, N_active, lane=0):
+    """doubling_allparams! (doubling_lin.jl:216-339).  lane: the moment lane the caller launches on (its scratch buffer)."""
     n = _lib.lib().vsm_doubling_lin_work_elems(added.N, added.nSpec, max(N_active, 1) if N_active else added_lin.P)
-    work = _work("dbl", max(int(n), 1), added.dtype, added.r_mp.device)
+    work = _work("dbl", max(int(n), 1), added.dtype, added.r_mp.device, lane)
     a, al = added.cstruct(), added_lin.cstruct()
     mu = C.c_double(mu0) if added.dtype == torch.float64 else C.c_float(mu0)
     _lib.call("vsm_doubling_lin", added.dtype, added.N, pol.n, added.nSpec, ndoubl, CR._ptr(expk), CR._ptr(dtau_dot_all),
@@ -178,11 +177,12 @@ def doubling_allparams_(pol, expk, ndoubl, added: CR.AddedLayer, added_lin: Adde
 
 
 def interaction_lin_(scattering_interface, comp: CR.CompositeLayer, comp_lin: CompositeLayerLin, added: CR.AddedLayer,
-                     added_lin: AddedLayerLin, p_range=None):
+                     added_lin: AddedLayerLin, p_range=None, lane=0):
     """interaction! (lin) (interaction_lin.jl:337-351).  `p_range = (p_lo, p_hi)`: only these parameter slots (the caller knows
-    the others to be zero in both operands, where the reference's loop over all Nparams computes exact zeros)."""
+    the others to be zero in both operands, where the reference's loop over all Nparams computes exact zeros).  lane: as in
+    doubling_allparams_."""
     n = _lib.lib().vsm_interaction_lin_work_elems(comp.N, comp.nSpec, comp_lin.P)
-    work = _work("ia", int(n), comp.dtype, comp.R_mp.device)
+    work = _work("ia", int(n), comp.dtype, comp.R_mp.device, lane)
     c, cl, a, al = comp.cstruct(), comp_lin.cstruct(), added.cstruct(), added_lin.cstruct()
     if p_range is not None and (p_range[0] > 0 or p_range[1] < comp_lin.P) and p_range[1] > p_range[0]:
         _lib.call("vsm_interaction_lin_range", comp.dtype, CR.IFACE[scattering_interface], comp.N, comp.nSpec, C.byref(c),
@@ -192,19 +192,20 @@ def interaction_lin_(scattering_interface, comp: CR.CompositeLayer, comp_lin: Co
               C.byref(cl), C.byref(a), C.byref(al), CR._ptr(work), CR._stream_ptr())
 
 
-def _pp_args(pol, qp, vza, vaz, m, weight, dtype):
-    """row0 / weights of postprocessing_vza! (postprocessing_vza.jl:23-94) as ctypes arrays."""
-    n, nV = pol.n, len(vza)
-    row0 = (C.c_int * nV)()
-    ctype = C.c_double if dtype == torch.float64 else C.c_float
-    w = (ctype * (nV * n))()
-    for v in range(nV):
-        imu = int(np.argmin(np.abs(qp.qp_mu - qp.qp_mu.dtype.type(H.cosd(vza[v])))))
-        row0[v] = imu * n
-        c0, s0 = H.cosd(m * vaz[v]), H.sind(m * vaz[v])
-        for k in range(n):
-            w[v + nV * k] = float(weight) * [c0, c0, s0, s0][k]
-    return row0, w
+def copy_added_to_composite_lin_(comp: CR.CompositeLayer, comp_lin: CompositeLayerLin, added: CR.AddedLayer, added_lin: AddedLayerLin):
+    """The TOA layer of a walk: the added layer and its derivative stacks become the composite."""
+    CR.copy_added_to_composite_(comp, added)
+    a, c = added_lin.cstruct(), comp_lin.cstruct()
+    _lib.call("vsm_copy_added_to_composite_lin", added.dtype, added.N, added.nSpec, C.byref(a), C.byref(c), CR._stream_ptr())
+
+
+def postprocessing_vza_lin_(pol, comp: CR.CompositeLayer, comp_lin: CompositeLayerLin, vza, vaz, qp, m, weight: float, R, T, Rd, Td):
+    """postprocessing_vza! and its linearized twin (postprocessing_vza.jl:23-94): R / T (S, nStokes, nVZA) and Rd / Td
+    (P, S, nStokes, nVZA) accumulate the moment's viewing rows."""
+    CR.postprocessing_vza_(pol, comp, vza, vaz, qp, m, weight, R, T)
+    row0, w = CR._vza_rows_weights(pol, vza, vaz, qp, m, weight, comp.dtype)
+    _lib.call("vsm_postprocess_vza_lin", comp.dtype, comp.N, pol.n, comp.nSpec, len(vza), comp_lin.P, row0, w,
+              CR._ptr(comp_lin.J0_m), CR._ptr(comp_lin.J0_p), CR._ptr(Rd), CR._ptr(Td), CR._stream_ptr())
 
 
 # Fourier moments per vsm_mix_Z_moments call (VSM_MM_MAX of the library: the kernel's argument block holds that many stacks)
@@ -506,11 +507,11 @@ class SceneLin(LinInputs):
     TREE_INTERACTIONS = True  # the interactions of a pre-doubled column whose tags are all 11 as a tree over the lane streams
 
     def _lane_state(self, k):
-        """Workspace of moment lane k (lane 0: the scene's own buffers)."""
+        """Workspace of moment lane k (lane 0: the scene's own buffers); its `lane` entry picks the scratch buffers of its kernels."""
         while len(self._lanes) <= k:
             if not self._lanes:
                 self._lanes.append(dict(added=self.added, al=self.al, comp=self.comp, cl=self.cl, added_s=self.added_s, als=self.als,
-                                        expk=self.expk, R=self.R, T=self.T, Rd=self.Rd, Td=self.Td, stream=None))
+                                        expk=self.expk, R=self.R, T=self.T, Rd=self.Rd, Td=self.Td, stream=None, lane=0))
                 continue
             FT, arch, P, N, S = self.FT, self.arch, self.P, self.N, self.S
             self._lanes.append(dict(
@@ -518,7 +519,7 @@ class SceneLin(LinInputs):
                 comp=CR.make_composite_layer(FT, arch, (N, N), S), cl=CompositeLayerLin(FT, arch, P, N, S),
                 added_s=self._new_surface_added(), als=AddedLayerLin(FT, arch, P, N, S, shared=True),
                 expk=torch.empty_like(self.expk), R=torch.zeros_like(self.R), T=torch.zeros_like(self.T),
-                Rd=torch.zeros_like(self.Rd), Td=torch.zeros_like(self.Td), stream=torch.cuda.Stream()))
+                Rd=torch.zeros_like(self.Rd), Td=torch.zeros_like(self.Td), stream=torch.cuda.Stream(), lane=len(self._lanes)))
         return self._lanes[k]
 
     def _new_surface_added(self):
@@ -555,7 +556,7 @@ class SceneLin(LinInputs):
     def _check_thermal(self) -> bool:
         """Is there a thermal slot to run (a non-zero B_layer or Planck tables)?  Its scope limit is checked here, on host values,
         before anything is launched: every layer must scatter (the slot state the reference's forward run carries through
-        non-scattering layers, Scene._thermal_slot, has no linearized meaning)."""
+        non-scattering layers, CoreRT.ThermalSlot, has no linearized meaning)."""
         if self.fwd.thermal_B is None and not self.nPlanck:
             return False
         eps2 = 2 * np.finfo(self.FT).eps
@@ -595,7 +596,6 @@ class SceneLin(LinInputs):
         return out
 
     def _run_solar(self, lanes: Optional[int] = None, fold: Optional[bool] = None):
-        global _lane
         S = self.S
         nm = len(self.fwd.moments)
         small = 0 < S < self.LANE_POINTS
@@ -633,17 +633,13 @@ class SceneLin(LinInputs):
         main = torch.cuda.current_stream()
         for w in st[1:]:
             w["stream"].wait_stream(main)       # (the zeroing above and whatever produced the inputs)
-        try:
-            for i, mom in enumerate(self.fwd.moments):
-                k = i % lanes
-                _lane = k
-                if k == 0:
-                    self._run_moment(mom, st[0])
-                else:
-                    with torch.cuda.stream(st[k]["stream"]):
-                        self._run_moment(mom, st[k])
-        finally:
-            _lane = 0
+        for i, mom in enumerate(self.fwd.moments):
+            k = i % lanes
+            if k == 0:
+                self._run_moment(mom, st[0])
+            else:
+                with torch.cuda.stream(st[k]["stream"]):
+                    self._run_moment(mom, st[k])
         for w in st[1:]:
             main.wait_stream(w["stream"])
         for w in st[1:]:
@@ -705,7 +701,6 @@ class SceneLin(LinInputs):
         return g
 
     def _run_folded(self, st):
-        global _lane
         pol, qp, dt, S, N, P, pl = self.pol, self.qp, self.dt, self.S, self.N, self.P, self.pl
         moms = self.fwd.moments
         groups = [[m_ for m_ in moms if m_["m"] == 0], [m_ for m_ in moms if m_["m"] > 0]]
@@ -721,15 +716,13 @@ class SceneLin(LinInputs):
 
         def double_layer(gi, group, iz, lane, added, al, expk):
             """elemental! (lin) + doubling! (lin) of layer iz of a folded group on the current stream (work buffers of `lane`)."""
-            global _lane
-            _lane = lane
             g = self._fold_group(gi, group)
             fl, ly0 = g["layers"][iz], group[0]["layers"][iz]
             n_m0 = S * sum(1 for m_ in group if m_["m"] == 0) if group[-1]["m"] > 0 else 0
             elemental_lin_(pol, fl["tau_sum"], fl["tsd"], fl["dtau"], fl["dtd"], g["F0"], fl["props"], fl["vd"], None, None, (0, 0),
                            pl, group[-1]["m"], ly0["nd"], self.dq, added, al, n_m0=n_m0)
             _lib.call("vsm_layer_expk", dt, len(group) * S, CR._ptr(fl["dtau"]), mu0, CR._ptr(expk), CR._stream_ptr())
-            doubling_allparams_(pol, expk, ly0["nd"], added, al, fl["dtd"], qp.mu0, pl)
+            doubling_allparams_(pol, expk, ly0["nd"], added, al, fl["dtd"], qp.mu0, pl, lane=lane)
 
         # elemental! + doubling! of a layer depend on nothing but its own optics (rt_kernel_lin.jl:87-160: the added layer is built
         # before interaction! is called).  With so few (moment, point) pairs that one layer's launch fills a sixth of the chip, ALL
@@ -750,7 +743,6 @@ class SceneLin(LinInputs):
                     b = gstate[gi]["per_layer"][iz]
                     with torch.cuda.stream(st[k]["stream"]):
                         double_layer(gi, grp, iz, k, b["added"], b["al"], b["expk"])
-            _lane = 0
             for w in st[1:]:
                 main.wait_stream(w["stream"])
             for w in st[1:]:
@@ -760,7 +752,6 @@ class SceneLin(LinInputs):
             """The interactions of a pre-doubled column as a tree (every tag 11): pairs of neighbouring sub-columns are combined
             level by level -- composite (upper) (+) composite-as-added-layer (lower) -- on the lane streams, ceil(log2 Nz) dependent
             interactions instead of Nz - 1.  Same equations, another association: results agree with the chain to rounding."""
-            global _lane
             g = gstate[gi]
             Sf = len(group) * S
             FT, arch = self.FT, self.arch
@@ -774,7 +765,6 @@ class SceneLin(LinInputs):
                 for ip in range(len(nodes) // 2):
                     a, b = nodes[2 * ip], nodes[2 * ip + 1]
                     k = ip % lanes
-                    _lane = k
                     ctx = torch.cuda.stream(st[k]["stream"]) if st[k]["stream"] is not None else contextlib.nullcontext()
                     with ctx:
                         if a[0] == "leaf":
@@ -783,20 +773,17 @@ class SceneLin(LinInputs):
                             comp, cl = pool[used]
                             used += 1
                             la = g["per_layer"][a[1]]
-                            CR.copy_added_to_composite_(comp, la["added"])
-                            a_, c_ = la["al"].cstruct(), cl.cstruct()
-                            _lib.call("vsm_copy_added_to_composite_lin", dt, N, Sf, C.byref(a_), C.byref(c_), CR._stream_ptr())
+                            copy_added_to_composite_lin_(comp, cl, la["added"], la["al"])
                         else:
                             comp, cl = a[1], a[2]
                         if b[0] == "leaf":
                             added, al = g["per_layer"][b[1]]["added"], g["per_layer"][b[1]]["al"]
                         else:
                             added, al = _CompositeAsAdded(b[1]), _CompositeLinAsAdded(b[2])
-                        interaction_lin_("11", comp, cl, added, al, p_range=self._layer_slots)
+                        interaction_lin_("11", comp, cl, added, al, p_range=self._layer_slots, lane=k)
                     nxt.append(("comp", comp, cl))
                 if len(nodes) % 2:
                     nxt.append(nodes[-1])
-                _lane = 0
                 for w in st[1:]:
                     main.wait_stream(w["stream"])
                 nodes = nxt
@@ -804,10 +791,7 @@ class SceneLin(LinInputs):
 
         def chain(gi, group, lane):
             """The layer walk of a folded group on the current stream (work buffers of `lane`)."""
-            global _lane
-            _lane = lane
             g = gstate[gi]
-            Sf = len(group) * S
             comp, cl = g["comp"], g["cl"]
             if (pre and self.TREE_INTERACTIONS and lane == 0 and self.fwd.Nz >= 4
                     and all(group[0]["layers"][iz]["iface"] == "11" for iz in range(1, self.fwd.Nz))):
@@ -820,48 +804,41 @@ class SceneLin(LinInputs):
                     added, al = g["added"], g["al"]
                     double_layer(gi, group, iz, lane, added, al, g["expk"])
                 if iz == 0:
-                    CR.copy_added_to_composite_(comp, added)
-                    a_, c_ = al.cstruct(), cl.cstruct()
-                    _lib.call("vsm_copy_added_to_composite_lin", dt, N, Sf, C.byref(a_), C.byref(c_), CR._stream_ptr())
+                    copy_added_to_composite_lin_(comp, cl, added, al)
                 else:
-                    interaction_lin_(ly0["iface"], comp, cl, added, al, p_range=self._layer_slots)
+                    interaction_lin_(ly0["iface"], comp, cl, added, al, p_range=self._layer_slots, lane=lane)
             return comp, cl
 
-        def finish(mom, w, lane, comp, cl, im):
-            """Moment `im` of a folded composite -> lane workspace `w`, then surface / interaction / post-processing."""
-            global _lane
-            _lane = lane
+        def finish(mom, w, comp, cl, im):
+            """Moment `im` of a folded composite -> lane workspace `w`, then surface / interaction / post-processing there."""
             sl = slice(im * S, (im + 1) * S)
             fields = ("R_mp", "R_pm", "T_pp", "T_mm", "J0_p", "J0_m")
             torch._foreach_copy_([getattr(w["comp"], f) for f in fields] + [getattr(w["cl"], f) for f in fields],
                                  [getattr(comp, f)[sl] for f in fields] + [getattr(cl, f)[:, sl] for f in fields])   # (one multi-tensor launch)
             self._finish_moment(mom, w)
 
-        try:
-            # the m = 0 chain (and its finish) on lane 1's stream, concurrent with the m >= 1 chain on the main stream
-            if groups[0]:
-                if lanes > 1:
-                    with torch.cuda.stream(st[1]["stream"]):
-                        comp0, cl0 = chain(0, groups[0], 1)
-                        for im, mom in enumerate(groups[0]):
-                            finish(mom, st[1], 1, comp0, cl0, im)
-                else:
-                    comp0, cl0 = chain(0, groups[0], 0)
+        # the m = 0 chain (and its finish) on lane 1's stream, concurrent with the m >= 1 chain on the main stream
+        if groups[0]:
+            if lanes > 1:
+                with torch.cuda.stream(st[1]["stream"]):
+                    comp0, cl0 = chain(0, groups[0], 1)
                     for im, mom in enumerate(groups[0]):
-                        finish(mom, st[0], 0, comp0, cl0, im)
-            if groups[1]:
-                comp1, cl1 = chain(1, groups[1], 0)
-                for w in st[1:]:
-                    w["stream"].wait_stream(main)
-                for im, mom in enumerate(groups[1]):
-                    kk = im % lanes
-                    if st[kk]["stream"] is None:
-                        finish(mom, st[kk], kk, comp1, cl1, im)
-                    else:
-                        with torch.cuda.stream(st[kk]["stream"]):
-                            finish(mom, st[kk], kk, comp1, cl1, im)
-        finally:
-            _lane = 0
+                        finish(mom, st[1], comp0, cl0, im)
+            else:
+                comp0, cl0 = chain(0, groups[0], 0)
+                for im, mom in enumerate(groups[0]):
+                    finish(mom, st[0], comp0, cl0, im)
+        if groups[1]:
+            comp1, cl1 = chain(1, groups[1], 0)
+            for w in st[1:]:
+                w["stream"].wait_stream(main)
+            for im, mom in enumerate(groups[1]):
+                kk = im % lanes
+                if st[kk]["stream"] is None:
+                    finish(mom, st[kk], comp1, cl1, im)
+                else:
+                    with torch.cuda.stream(st[kk]["stream"]):
+                        finish(mom, st[kk], comp1, cl1, im)
         for w in st[1:]:
             main.wait_stream(w["stream"])
         for w in st[1:]:
@@ -871,60 +848,57 @@ class SceneLin(LinInputs):
     def _run_moment(self, mom, w, after_layer=None):
         """One Fourier moment on the workspace `w` (launches on the current stream).  after_layer(l, comp, cl): called after layer l
         (1-based) has joined the composite (the multi-sensor run keeps its tops there)."""
-        N, S = self.N, self.S
         added, al, comp, cl = w["added"], w["al"], w["comp"], w["cl"]
         for iz, ly in enumerate(mom["layers"]):
             self._double_layer(mom, iz, w)
             if iz == 0:
-                CR.copy_added_to_composite_(comp, added)
-                a_, c_ = al.cstruct(), cl.cstruct()
-                _lib.call("vsm_copy_added_to_composite_lin", self.dt, N, S, C.byref(a_), C.byref(c_), CR._stream_ptr())
+                copy_added_to_composite_lin_(comp, cl, added, al)
             else:
-                interaction_lin_(ly["iface"], comp, cl, added, al, p_range=self._layer_slots)
+                interaction_lin_(ly["iface"], comp, cl, added, al, p_range=self._layer_slots, lane=w["lane"])
             if after_layer is not None:
                 after_layer(iz + 1, comp, cl)
         self._finish_moment(mom, w)
 
-    def _double_layer(self, mom, iz, w):
-        """elemental! (lin) + doubling! (lin) of layer iz (0-based) of one moment into w["added"] / w["al"]."""
-        pol, qp, dt, fwd = self.pol, self.qp, self.dt, self.fwd
-        S, pl = self.S, self.pl
-        added, al = w["added"], w["al"]
-        mu0 = C.c_double(qp.mu0) if dt == torch.float64 else C.c_float(qp.mu0)
-        q_ = self.dq.cstruct()
-        m = mom["m"]
+    def _elemental_layer(self, mom, iz, added, al, F0):
+        """elemental! (lin) of layer iz (0-based) of one moment into added / al, driven by the beam F0 (the thermal slot's is zero:
+        r, t and their derivatives as in the solar walk, j and jdot reset to zero)."""
+        dt, fwd, S, pl, m = self.dt, self.fwd, self.S, self.pl, mom["m"]
         ly = mom["layers"][iz]
         props = ly["props"]
         dtd, vd, tsd = self.dtau_dot_all[iz], self.varpi_dot[iz], self.tau_sum_dot[iz]
         if self.Zall is not None:
             mixed, k = fwd.zcomp[iz]
-            a_, al_ = added.cstruct(), al.cstruct()
+            q_, a_, al_ = self.dq.cstruct(), added.cstruct(), al.cstruct()
             _lib.call("vsm_elemental_lin_mix", dt, C.byref(q_), S, m, ly["nd"], CR._ptr(ly["dtau"]), CR._ptr(props.varpi),
-                      CR._ptr(ly["tau_sum"]), CR._ptr(self.F0), self.C_, self.CT, CR._ptr(self.Zall[m][0]),
+                      CR._ptr(ly["tau_sum"]), CR._ptr(F0), self.C_, self.CT, CR._ptr(self.Zall[m][0]),
                       CR._ptr(self.Zall[m][1]), -1 if mixed else k, CR._ptr(self.fz[iz]), pl, CR._ptr(dtd), CR._ptr(vd),
                       CR._ptr(tsd), CR._ptr(self.zdcoef[iz]), C.byref(a_), C.byref(al_), CR._stream_ptr())
         else:
             zpd, zmd, zds = self.host_zdot[m][iz] if self.host_zdot is not None else (None, None, (0, 0))
-            elemental_lin_(pol, ly["tau_sum"], tsd, ly["dtau"], dtd, self.F0, props.materialize(), vd, zpd, zmd, zds, pl,
+            elemental_lin_(self.pol, ly["tau_sum"], tsd, ly["dtau"], dtd, F0, props.materialize(), vd, zpd, zmd, zds, pl,
                            m, ly["nd"], self.dq, added, al)
-        _lib.call("vsm_layer_expk", dt, S, CR._ptr(ly["dtau"]), mu0, CR._ptr(w["expk"]), CR._stream_ptr())
-        doubling_allparams_(pol, w["expk"], ly["nd"], added, al, dtd, qp.mu0, pl)
+
+    def _double_layer(self, mom, iz, w):
+        """elemental! (lin) + doubling! (lin) of layer iz (0-based) of one moment into w["added"] / w["al"]."""
+        qp, dt = self.qp, self.dt
+        added, al = w["added"], w["al"]
+        ly = mom["layers"][iz]
+        self._elemental_layer(mom, iz, added, al, self.F0)
+        mu0 = C.c_double(qp.mu0) if dt == torch.float64 else C.c_float(qp.mu0)
+        _lib.call("vsm_layer_expk", dt, self.S, CR._ptr(ly["dtau"]), mu0, CR._ptr(w["expk"]), CR._stream_ptr())
+        doubling_allparams_(self.pol, w["expk"], ly["nd"], added, al, self.dtau_dot_all[iz], qp.mu0, self.pl, lane=w["lane"])
 
     def _finish_moment(self, mom, w):
         """Surface layer, its interaction and the post-processing of one Fourier moment on the workspace `w`."""
-        model, pol, qp, FT, dt = self.model, self.pol, self.qp, self.FT, self.dt
-        N, S, P = self.N, self.S, self.P
+        model = self.model
         comp, cl = w["comp"], w["cl"]
         m = mom["m"]
-        weight = FT(0.5 / math.pi) if m == 0 else FT(1.0 / math.pi)
+        weight = float(CR.fourier_weight(self.FT, m))
         self._surface_lin(mom, w["added_s"], w["als"], self.F0)
         if m == 0 and self._sif_comps:
-            self._sif_slots(comp, w, float(weight))     # (reads the composite BEFORE its surface interaction)
-        interaction_lin_(mom["iface_surface"], comp, cl, w["added_s"], w["als"])
-        CR.postprocessing_vza_(pol, comp, model.vza, model.vaz, qp, m, float(weight), w["R"], w["T"])
-        row0, wts = _pp_args(pol, qp, model.vza, model.vaz, m, weight, dt)
-        _lib.call("vsm_postprocess_vza_lin", dt, N, pol.n, S, len(model.vza), P, row0, wts, CR._ptr(cl.J0_m), CR._ptr(cl.J0_p),
-                  CR._ptr(w["Rd"]), CR._ptr(w["Td"]), CR._stream_ptr())
+            self._sif_slots(comp, w, weight)     # (reads the composite BEFORE its surface interaction)
+        interaction_lin_(mom["iface_surface"], comp, cl, w["added_s"], w["als"], lane=w["lane"])
+        postprocessing_vza_lin_(self.pol, comp, cl, model.vza, model.vaz, self.qp, m, weight, w["R"], w["T"], w["Rd"], w["Td"])
 
     def _sif_slots(self, comp, w, weight):
         """The SIF slots.  The radiance is linear in SIF0 and the emission is the same at every stream, so
@@ -970,7 +944,7 @@ class SceneLin(LinInputs):
     # ---- the thermal slot ----------------------------------------------------------------------------------------
     def _thermal_state(self):
         """The slot's own layers, forward and derivative (allocated on first use), its zero beam, its expk = 1 and the zero
-        dtau_dot table that makes doubling! (lin) form ekl = 0."""
+        dtau_dot table that makes doubling! (lin) form ekl = 0.  The slot runs on the main stream: lane 0."""
         if self._th is None:
             FT, arch, P, N, S = self.FT, self.arch, self.P, self.N, self.S
             dev = self.expk.device
@@ -978,15 +952,13 @@ class SceneLin(LinInputs):
                             comp=CR.make_composite_layer(FT, arch, (N, N), S), cl=CompositeLayerLin(FT, arch, P, N, S),
                             added_s=self._new_surface_added(), als=AddedLayerLin(FT, arch, P, N, S, shared=True),
                             F0=torch.zeros_like(self.F0), ones=torch.empty(max(S, 1), dtype=self.dt, device=dev),
-                            zero_dtd=torch.zeros((P, max(S, 1)), dtype=self.dt, device=dev))
+                            zero_dtd=torch.zeros((P, max(S, 1)), dtype=self.dt, device=dev), lane=0)
         return self._th
 
     def _run_thermal(self):
         """The `:thermal` per-source slot of the linearized run, on the current stream after the solar moments (whatever lanes
-        they ran on have joined it): Scene._thermal_slot step by step with the derivative stacks beside it, m = 0 only (the
+        they ran on have joined it): ThermalSlot step by step with the derivative stacks beside it, m = 0 only (the
         source is isotropic), into the same R, T, Rdot, Tdot; then the Planck block."""
-        global _lane
-        _lane = 0
         fwd = self.fwd
         mom = fwd.moments[0]
         if fwd.thermal_B is not None:
@@ -994,45 +966,29 @@ class SceneLin(LinInputs):
         if self.nPlanck:
             self._planck_block(mom)
 
-    def _thermal_lin_walk(self, mom, comp, cl, first, end, after_layer=None):
-        """Layers first+1 .. end (1-based) of the linearized slot into the thermal composite `comp` / `cl`, the first one a copy
-        (the linearized twin of Scene._thermal_walk: expk = 1 and no beam attenuation, so a range that starts below the TOA needs
-        no absolute tau_sum).  after_layer(l, comp, cl): called once layer l is in the composite (the multi-sensor run keeps its
-        thermal tops there, core_rt_ms_lin.py)."""
-        pol, qp, dt, fwd = self.pol, self.qp, self.dt, self.fwd
-        N, S, pl = self.N, self.S, self.pl
+    def _thermal_lin_walk(self, mom, comp, cl, first, end, B, after_layer=None):
+        """Layers first+1 .. end (1-based) of the linearized slot for the Planck table B ((rows, S), or None) into the thermal
+        composite `comp` / `cl`, the first one a copy (the linearized twin of ThermalSlot.walk: expk = 1 and no beam attenuation,
+        so a range that starts below the TOA needs no absolute tau_sum).  after_layer(l, comp, cl): called once layer l is in the
+        composite (the multi-sensor run keeps its thermal tops there, core_rt_ms_lin.py)."""
+        dt, S, pl = self.dt, self.S, self.pl
         t = self._thermal_state()
         added, al = t["added"], t["al"]
-        q_ = self.dq.cstruct()
-        m = mom["m"]
-        rows = fwd.thermal_B.shape[0] if fwd.thermal_B is not None else 0
+        rows = B.shape[0] if B is not None else 0
         for iz in range(first, end):
             ly = mom["layers"][iz]
-            props = ly["props"]
-            dtd, vd, tsd = self.dtau_dot_all[iz], self.varpi_dot[iz], self.tau_sum_dot[iz]
-            a_, al_ = added.cstruct(), al.cstruct()
-            # elemental! (lin) with F0 = 0: r, t and their derivatives as in the solar walk, j and jdot reset to zero
-            if self.Zall is not None:
-                mixed, k = fwd.zcomp[iz]
-                _lib.call("vsm_elemental_lin_mix", dt, C.byref(q_), S, m, ly["nd"], CR._ptr(ly["dtau"]), CR._ptr(props.varpi),
-                          CR._ptr(ly["tau_sum"]), CR._ptr(t["F0"]), self.C_, self.CT, CR._ptr(self.Zall[m][0]),
-                          CR._ptr(self.Zall[m][1]), -1 if mixed else k, CR._ptr(self.fz[iz]), pl, CR._ptr(dtd), CR._ptr(vd),
-                          CR._ptr(tsd), CR._ptr(self.zdcoef[iz]), C.byref(a_), C.byref(al_), CR._stream_ptr())
-            else:
-                zpd, zmd, zds = self.host_zdot[m][iz] if self.host_zdot is not None else (None, None, (0, 0))
-                elemental_lin_(pol, ly["tau_sum"], tsd, ly["dtau"], dtd, t["F0"], props.materialize(), vd, zpd, zmd, zds, pl,
-                               m, ly["nd"], self.dq, added, al)
+            self._elemental_layer(mom, iz, added, al, t["F0"])
             if iz < rows:      # contribute! and its derivatives
-                _lib.call("vsm_thermal_source_lin", dt, C.byref(q_), S, CR._ptr(ly["dtau"]), CR._ptr(props.varpi),
-                          CR._ptr(fwd.thermal_B[iz]), pl, CR._ptr(dtd), CR._ptr(vd), C.byref(a_), C.byref(al_), CR._stream_ptr())
+                q_, a_, al_ = self.dq.cstruct(), added.cstruct(), al.cstruct()
+                _lib.call("vsm_thermal_source_lin", dt, C.byref(q_), S, CR._ptr(ly["dtau"]), CR._ptr(ly["props"].varpi),
+                          CR._ptr(B[iz]), pl, CR._ptr(self.dtau_dot_all[iz]), CR._ptr(self.varpi_dot[iz]), C.byref(a_),
+                          C.byref(al_), CR._stream_ptr())
             t["ones"].fill_(1.0)    # the slot's expk = 1 (the doubling kernels square it in place); zero_dtd: ekl = 0
-            doubling_allparams_(pol, t["ones"], ly["nd"], added, al, t["zero_dtd"], qp.mu0, pl)
+            doubling_allparams_(self.pol, t["ones"], ly["nd"], added, al, t["zero_dtd"], self.qp.mu0, pl, lane=t["lane"])
             if iz == first:
-                CR.copy_added_to_composite_(comp, added)
-                c_ = cl.cstruct()
-                _lib.call("vsm_copy_added_to_composite_lin", dt, N, S, C.byref(al_), C.byref(c_), CR._stream_ptr())
+                copy_added_to_composite_lin_(comp, cl, added, al)
             else:
-                interaction_lin_(ly["iface"], comp, cl, added, al, p_range=self._layer_slots)
+                interaction_lin_(ly["iface"], comp, cl, added, al, p_range=self._layer_slots, lane=t["lane"])
             if after_layer is not None:
                 after_layer(iz + 1, comp, cl)
 
@@ -1047,39 +1003,27 @@ class SceneLin(LinInputs):
     def _thermal_lin_slot(self, mom, after_layer=None, post=True):
         """Walk layers 1 .. Nz (_thermal_lin_walk), surface, post-process into R, T, Rdot, Tdot (post=False: the composite is left
         after its surface interaction and nothing is added to the outputs)."""
-        model, pol, qp, FT, dt = self.model, self.pol, self.qp, self.FT, self.dt
-        N, S, P = self.N, self.S, self.P
+        model = self.model
         t = self._thermal_state()
         comp, cl = t["comp"], t["cl"]
-        m = mom["m"]
-        self._thermal_lin_walk(mom, comp, cl, 0, len(mom["layers"]), after_layer)
+        self._thermal_lin_walk(mom, comp, cl, 0, len(mom["layers"]), self.fwd.thermal_B, after_layer)
         added_s, als = self._thermal_lin_surface(mom)
-        interaction_lin_(mom["iface_surface"], comp, cl, added_s, als)
-        if not post:
-            return
-        weight = FT(0.5 / math.pi)
-        CR.postprocessing_vza_(pol, comp, model.vza, model.vaz, qp, m, float(weight), self.R, self.T)
-        row0, wts = _pp_args(pol, qp, model.vza, model.vaz, m, weight, dt)
-        _lib.call("vsm_postprocess_vza_lin", dt, N, pol.n, S, len(model.vza), P, row0, wts, CR._ptr(cl.J0_m), CR._ptr(cl.J0_p),
-                  CR._ptr(self.Rd), CR._ptr(self.Td), CR._stream_ptr())
+        interaction_lin_(mom["iface_surface"], comp, cl, added_s, als, lane=t["lane"])
+        if post:
+            postprocessing_vza_lin_(self.pol, comp, cl, model.vza, model.vaz, self.qp, mom["m"], float(CR.fourier_weight(self.FT, 0)),
+                                    self.R, self.T, self.Rd, self.Td)
 
     def _planck_block(self, mom):
-        """The slot is linear in B: dR / dx_k is the FORWARD thermal slot (Scene._thermal_walk / _thermal_surface, fused layer
-        kernels included) of B := B_layer_dot[k], post-processed into slot P + k of Rdot / Tdot."""
-        model, pol, qp, fwd, P = self.model, self.pol, self.qp, self.fwd, self.P
-        weight = float(self.FT(0.5 / math.pi))
-        B0 = fwd.thermal_B
-        try:
-            for k in range(self.nPlanck):
-                fwd.thermal_B = self.thermal_B_dot[k]
-                fwd._thermal_begin(mom)
-                comp = fwd._th_comp
-                fwd._thermal_walk(mom, comp, 0, fwd.Nz)
-                surf = fwd._thermal_surface(mom)
-                CR.interaction_(mom["iface_surface"], comp, surf, oplevel=True, work=fwd.work)
-                CR.postprocessing_vza_(pol, comp, model.vza, model.vaz, qp, mom["m"], weight, self.Rd[P + k], self.Td[P + k])
-        finally:
-            fwd.thermal_B = B0
+        """The slot is linear in B: dR / dx_k is the FORWARD thermal slot (CoreRT.ThermalSlot, fused layer kernels included) of
+        B := B_layer_dot[k], post-processed into slot P + k of Rdot / Tdot."""
+        fwd, P = self.fwd, self.P
+        weight = float(CR.fourier_weight(self.FT, 0))
+        th = fwd.thermal_slot()
+        for k in range(self.nPlanck):
+            th.begin(mom)
+            th.walk(mom, th.comp, 0, fwd.Nz, self.thermal_B_dot[k])
+            th.surface(mom)
+            th.finish(mom, weight, self.Rd[P + k], self.Td[P + k])
 
     def results_host(self):
         """(R, T, Rdot, Tdot) as the reference returns them: [nVZA, nStokes, nSpec] and [nVZA, nStokes, nSpec, Nparams]."""

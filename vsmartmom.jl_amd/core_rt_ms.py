@@ -17,8 +17,8 @@ prototype runs one interaction per sensor and layer, O(Nz K) for K sensors.  Add
 
 Per moment: Nz + (Nz - l_1) layer steps, K + 1 further interactions and at most K + 1 level calls.
 
-thermal=True adds the `:thermal` per-source slot of rt_run (Scene._thermal_slot) for m = 0, the one moment an isotropic source
-has: the same four steps on thermal composites of its own (Scene._thermal_walk: the top pass keeps J0+ after each level, the
+thermal=True adds the `:thermal` per-source slot of rt_run (CoreRT.ThermalSlot) for m = 0, the one moment an isotropic source
+has: the same four steps on thermal composites of its own (ThermalSlot.walk: the top pass keeps J0+ after each level, the
 segments need no tau_sum), thermal bottoms built beside the solar ones, and per level ONE call of vsm_level_radiance_src_*, which
 solves the solar and the thermal right-hand side on one elimination of [I - A B | .] with A, B of the solar pass (the thermal
 composites' own R differ from them only by rounding and are not read).  DESIGN.md §4.8d.
@@ -30,8 +30,8 @@ spectral axis and the assembly of the results (spectral_blocks, gather_blocks).
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
-import math
 from dataclasses import dataclass
 from typing import List
 
@@ -248,8 +248,7 @@ def _validate(model: H.RTModel, sensor_levels, thermal: bool = False, sif: bool 
     return LevelPlan(levels, distinct, interior, interior + ([Nz] if Nz in distinct else []), interior[1:] + [Nz], Nz)
 
 
-def fourier_weight(FT, m: int):
-    return FT(0.5 / math.pi) if m == 0 else FT(1.0 / math.pi)
+fourier_weight = CR.fourier_weight
 
 
 def refuse_non_scattering(layers, FT, who: str, why: str):
@@ -344,19 +343,6 @@ def gather_blocks(model: H.RTModel, plan: LevelPlan, blocks, run_block, who: str
                       **dict(zip(result_cls.FIELDS, outs)), **{f + "_streams": x for f, x in zip(result_cls.FIELDS, st)})
 
 
-def _snapshot(comp: CR.CompositeLayer):
-    """(R+-, J0+) of a composite in the middle of its walk, without disturbing the walk: a composite that rt_kernel_ keeps in
-    native layout is exported (vsm_run_export leaves the run as it is) instead of materialised (which would end the run)."""
-    slot = comp._native
-    if slot is not None:
-        cc = (_lib.vsm_composite * 1)(comp._cstruct_raw())
-        _lib.call("vsm_run_export", comp.dtype, slot.run, cc, CR._stream_ptr())
-        a = comp._arr
-    else:
-        a = comp.materialize()._arr
-    return a["R_pm"].clone(), a["J0_p"].clone()
-
-
 def _run_segment(scene: CR.Scene, mom, seg: CR.CompositeLayer, first: int, end: int):
     """Layers first+1 .. end (1-based) as a composite of their own, full mode: the first is a TOA copy (iz = 1), every layer keeps
     its absolute tau_sum.  rt_kernel_ takes the native drop-in path where the shape allows."""
@@ -388,9 +374,7 @@ def _run(scene: CR.Scene, plan: LevelPlan, streams: bool):
         return out, full, [float(fourier_weight(FT, m)) for m in range(model.m_max + 1)]
     scene.added.j0_p.zero_()
     # the moment groups of Scene.run (level 0 is then rt_run's result bit for bit), fewer where the tops would not fit the device
-    sequential = not CR.MOMENT_BATCHING or CR.REFERENCE_ORDER
-    want = max(CR.MOMENT_BATCH, min(CR.MOMENT_BATCH_MAX, 4096 // max(S, 1)))
-    nb = 1 if sequential else min(want, len(scene.moments))
+    nb = scene._group_size(not CR.MOMENT_BATCHING or CR.REFERENCE_ORDER)
     thermal = scene.thermal_B is not None
     if tops_at and dev.type == "cuda":
         elt = torch.finfo(dt).bits // 8
@@ -399,45 +383,20 @@ def _run(scene: CR.Scene, plan: LevelPlan, streams: bool):
             per_moment += len(tops_at) * N * S * elt
         free = torch.cuda.mem_get_info(dev)[0]
         nb = max(1, min(nb, int(0.5 * free // per_moment)))
-    while len(scene._composites) < nb:
-        scene._composites.append(CR.make_composite_layer(FT, scene.arch, (N, N), S))
     segs = [CR.make_composite_layer(FT, scene.arch, (N, N), S) for _ in range(2 if plan.interior else 0)]
     # the thermal twin of each segment composite (m = 0 only; never in native layout: the slot's calls take the reference's arrays)
     th_of = {id(seg): CR.make_composite_layer(FT, scene.arch, (N, N), S) for seg in segs} if thermal else {}
     native = scene._native_moments() if not CR.REFERENCE_ORDER else set()
-    for c in scene._composites:
-        c._sources_only = CR.REFERENCE_ORDER
-    try:
+    with contextlib.ExitStack() as stack:
+        stack.callback(lambda: [c.drop_native() for c in segs])
+        stack.enter_context(scene._walk_composites(nb, CR.REFERENCE_ORDER, None))
         for g0 in range(0, len(scene.moments), nb):
             group = scene.moments[g0:g0 + nb]
             comps = scene._composites[:len(group)]
             tops = [dict() for _ in group]
-            nat = [k for k in range(len(group)) if (g0 + k) in native]
-            # 1. the top pass
-            if nat:
-                def keep(l):
-                    def cb(cs):
-                        for k, c in zip(nat, cs):
-                            tops[k][l] = (c._arr["R_pm"].clone(), c._arr["J0_p"].clone())
-                    return cb
-                scene._run_layers_native([group[k] for k in nat], [comps[k] for k in nat], sources_only=True,
-                                         export_at={l: keep(l) for l in tops_at})
-            rest = [k for k in range(len(group)) if (g0 + k) not in native]
-            group_l, comps_l = [group[k] for k in rest], [comps[k] for k in rest]
-            for iz in range(Nz if rest else 0):
-                ly0 = group_l[0]["layers"][iz]
-                if len(group_l) > 1 and (iz == 0 or ly0["iface"] == "11"):
-                    CR.layer_forward_multi_(ly0["tau_sum"], ly0["dtau"], scene.F0, [mom["layers"][iz]["props"] for mom in group_l],
-                                            [mom["m"] for mom in group_l], ly0["nd"], scene.dq, iz == 0, comps_l, scene.added)
-                else:
-                    for mom, comp in zip(group_l, comps_l):
-                        ly = mom["layers"][iz]
-                        CR.rt_kernel_(pol, scene.added, comp, ly["props"], ly["iface"], ly["tau_sum"], mom["m"], scene.dq,
-                                      scene.arch, iz + 1, scene.F0, FT, model.numerics, dtau=ly["dtau"], ndoubl=ly["nd"],
-                                      work=scene.work)
-                if iz + 1 in tops_at:
-                    for k, comp in zip(rest, comps_l):
-                        tops[k][iz + 1] = _snapshot(comp)
+            # 1. the top pass: Scene.run's walk, the tops kept on the way
+            scene._walk_layers(group, comps, [k for k in range(len(group)) if (g0 + k) in native], sources_only=True, view_rows=None,
+                               tops_at=tops_at, keep_top=lambda k, l, top, tops=tops: tops[k].__setitem__(l, top))
             for k, (mom, comp) in enumerate(zip(group, comps)):
                 m = mom["m"]
                 weight = fourier_weight(FT, m)
@@ -451,14 +410,11 @@ def _run(scene: CR.Scene, plan: LevelPlan, streams: bool):
                 th = thermal and m == 0
                 th_tops, th_surf = {}, None
                 if th:
-                    scene._thermal_begin(mom)
-
-                    def keep_th(l):
-                        def cb(c):
-                            th_tops[l] = c.J0_p.clone()
-                        return cb
-                    scene._thermal_walk(mom, scene._th_comp, 0, Nz, after={l: keep_th(l) for l in tops_at})
-                    th_surf = scene._thermal_surface(mom)
+                    slot = scene.thermal_slot()
+                    slot.begin(mom)
+                    slot.walk(mom, slot.comp, 0, Nz, scene.thermal_B,
+                              after={l: (lambda c, l=l: th_tops.__setitem__(l, c.J0_p.clone())) for l in tops_at})
+                    th_surf = slot.surface(mom)
 
                 def level(l, seg):
                     A, a = tops[k].pop(l)
@@ -478,7 +434,7 @@ def _run(scene: CR.Scene, plan: LevelPlan, streams: bool):
                 def run_segment(seg, first, end):
                     _run_segment(scene, mom, seg, first, end)
                     if th:
-                        scene._thermal_walk(mom, th_of[id(seg)], first, end)
+                        slot.walk(mom, th_of[id(seg)], first, end, scene.thermal_B)
 
                 def join_surface(seg):
                     CR.interaction_(mom["iface_surface"], seg, asurf, work=scene.work)
@@ -496,21 +452,14 @@ def _run(scene: CR.Scene, plan: LevelPlan, streams: bool):
                 CR.interaction_(mom["iface_surface"], comp, asurf, work=scene.work)
                 CR.postprocessing_vza_(pol, comp, model.vza, model.vaz, scene.qp, m, float(weight), scene.R_SFI, scene.T_SFI)
                 if th:
-                    CR.interaction_(mom["iface_surface"], scene._th_comp, th_surf, oplevel=True, work=scene.work)
-                    CR.postprocessing_vza_(pol, scene._th_comp, model.vza, model.vaz, scene.qp, m, float(weight), scene.R_SFI,
-                                           scene.T_SFI)
+                    slot.finish(mom, float(weight), scene.R_SFI, scene.T_SFI)
                 if streams:
                     fv[0] = (comp.J0_m.clone(), comp.J0_p.clone())
                     if th:     # per-source slots added, as Scene.run(streams=...) sums J0
-                        fv[0][0].add_(scene._th_comp.J0_m)
-                        fv[0][1].add_(scene._th_comp.J0_p)
+                        fv[0][0].add_(slot.comp.J0_m)
+                        fv[0][1].add_(slot.comp.J0_p)
                     full[m] = fv
                 tops[k].clear()
-    finally:
-        for c in scene._composites:
-            c._sources_only = False
-        for c in segs:
-            c.drop_native()
     return out, full, weights
 
 

@@ -22,14 +22,13 @@ linearized level call per level other than 0.
 
 With a ThermalEmission source the `:thermal` per-source slot of rt_run_lin and its Planck slots follow the solar
 moments, for m = 0 alone (_run_thermal): the same four steps on the slot's own linearized composites (SceneLin._thermal_lin_walk:
-expk = 1, so a segment needs no tau_sum) and, per Planck table, on the forward thermal composites of Scene._thermal_walk, of which
+expk = 1, so a segment needs no tau_sum) and, per Planck table, on the forward thermal composites of CoreRT.ThermalSlot.walk, of which
 only the source vectors J0+ (top) and J0- (bottom) are kept.  The slot solves its level equation on ITS OWN operators, not on the
 solar ones as the forward run does (§4.8d): the solar m = 0 may have run as a Stokes_IQ sub-scene at another N.  Per level other
 than 0: one elastic call on the thermal composites and ONE vsm_level_radiance_lin_src_* call for all Nparams + nPlanck slots.
 """
 from __future__ import annotations
 
-import ctypes as C
 from dataclasses import dataclass
 from typing import List, Optional
 
@@ -105,7 +104,8 @@ def _run_scene(sc: CL.SceneLin, plan: MS.LevelPlan, streams: bool):
     model, fwd, FT, dt = sc.model, sc.fwd, sc.FT, sc.dt
     pol, qp = sc.pol, sc.qp
     N, S, P, pl = sc.N, sc.S, sc.P, sc.pl
-    w = sc._lane_state(0)
+    w = sc._lane_state(0)      # (the whole run is on one stream: lane 0)
+    lane = w["lane"]
     torch._foreach_zero_([w["R"], w["T"], w["Rd"], w["Td"]])
     dev = sc.R.device
     nV = len(model.vza)
@@ -146,11 +146,10 @@ def _run_scene(sc: CL.SceneLin, plan: MS.LevelPlan, streams: bool):
             for iz in range(first, end):
                 sc._double_layer(mom, iz, w)
                 if iz == first:
-                    CR.copy_added_to_composite_(seg[0], w["added"])
-                    a_, c_ = w["al"].cstruct(), seg[1].cstruct()
-                    _lib.call("vsm_copy_added_to_composite_lin", dt, N, S, C.byref(a_), C.byref(c_), CR._stream_ptr())
+                    CL.copy_added_to_composite_lin_(seg[0], seg[1], w["added"], w["al"])
                 else:
-                    CL.interaction_lin_(mom["layers"][iz]["iface"], seg[0], seg[1], w["added"], w["al"], p_range=sc._layer_slots)
+                    CL.interaction_lin_(mom["layers"][iz]["iface"], seg[0], seg[1], w["added"], w["al"], p_range=sc._layer_slots,
+                                        lane=lane)
 
         def level(l, seg):
             top = tops.pop(l)
@@ -164,9 +163,9 @@ def _run_scene(sc: CL.SceneLin, plan: MS.LevelPlan, streams: bool):
                 fv[l] = vs
         # 2.-4. linearized segments and bottoms from the surface up, the level calls of each level
         MS.walk_levels(plan, segs, run_segment,
-                       lambda seg: CL.interaction_lin_(mom["iface_surface"], seg[0], seg[1], asurf, als),
+                       lambda seg: CL.interaction_lin_(mom["iface_surface"], seg[0], seg[1], asurf, als, lane=lane),
                        lambda seg, bot, first, end: CL.interaction_lin_("11", seg[0], seg[1], CL._CompositeAsAdded(bot[0]),
-                                                                        CL._CompositeLinAsAdded(bot[1])), level)
+                                                                        CL._CompositeLinAsAdded(bot[1]), lane=lane), level)
         if streams:
             full[m] = fv
     if thermal:
@@ -185,7 +184,7 @@ def _run_thermal(sc: CL.SceneLin, plan: MS.LevelPlan, segs, out, full):
     dev = sc.R.device
     mom = fwd.moments[0]
     weight = float(MS.fourier_weight(sc.FT, 0))
-    CL._lane = 0
+    lane = sc._thermal_state()["lane"]
     new = lambda *sh: torch.empty(sh, dtype=dt, device=dev)
     below = [l for l in plan.distinct if l != 0]
     src = {l: (torch.zeros((K, S, N), dtype=dt, device=dev), torch.zeros((K, S, N), dtype=dt, device=dev)) for l in below} if K else {}
@@ -198,30 +197,26 @@ def _run_thermal(sc: CL.SceneLin, plan: MS.LevelPlan, segs, out, full):
     # 4. the Planck sources: per table the forward slot of B := B_layer_dot[k], cut at the plan's levels as DESIGN 4.8d cuts it
     if K:
         th_segs = [CR.make_composite_layer(sc.FT, sc.arch, (N, N), S) for _ in range(2 if plan.interior else 0)]
-        B0 = fwd.thermal_B
+        th = fwd.thermal_slot()
         try:
             for k in range(K):
-                fwd.thermal_B = sc.thermal_B_dot[k]
-                fwd._thermal_begin(mom)
-                comp = fwd._th_comp
-                fwd._thermal_walk(mom, comp, 0, fwd.Nz,
-                                  after={l: (lambda c, l=l: src[l][0][k].copy_(c.J0_p)) for l in plan.tops_at})
-                surf = fwd._thermal_surface(mom)
+                B = sc.thermal_B_dot[k]
+                th.begin(mom)
+                th.walk(mom, th.comp, 0, fwd.Nz, B, after={l: (lambda c, l=l: src[l][0][k].copy_(c.J0_p)) for l in plan.tops_at})
+                surf = th.surface(mom)
 
                 def keep_bottom(l, seg):
                     if seg is not None:      # (level Nz: the surface layer alone emits nothing, c_k = 0)
                         src[l][1][k].copy_(seg.J0_m)
-                MS.walk_levels(plan, th_segs, lambda seg, first, end: fwd._thermal_walk(mom, seg, first, end),
+                MS.walk_levels(plan, th_segs, lambda seg, first, end: th.walk(mom, seg, first, end, B),
                                lambda seg: CR.interaction_(mom["iface_surface"], seg, surf, oplevel=True, work=fwd.work),
                                lambda seg, bot, first, end: CR.interaction_("11", seg, MS._CompositeAsAdded(bot), oplevel=True,
                                                                             work=fwd.work), keep_bottom)
-                CR.interaction_(mom["iface_surface"], comp, surf, oplevel=True, work=fwd.work)
-                CR.postprocessing_vza_(pol, comp, model.vza, model.vaz, qp, 0, weight, sc.Rd[P + k], sc.Td[P + k])
+                th.finish(mom, weight, sc.Rd[P + k], sc.Td[P + k])
                 if fv is not None:
-                    fv[0][2][P + k].copy_(comp.J0_m)
-                    fv[0][3][P + k].copy_(comp.J0_p)
+                    fv[0][2][P + k].copy_(th.comp.J0_m)
+                    fv[0][3][P + k].copy_(th.comp.J0_p)
         finally:
-            fwd.thermal_B = B0
             for c in th_segs:
                 c.drop_native()
     # 1. the top pass of the linearized slot and level 0 (B_layer = 0 with Planck tables: SceneLin.run adds no slot, the walk
@@ -254,10 +249,10 @@ def _run_thermal(sc: CL.SceneLin, plan: MS.LevelPlan, segs, out, full):
             for acc, v in zip(fv[l], (uwf, dwf, uwd, dwd)):
                 acc.add_(v)
     # 2.-4. the slot's segments and bottoms from the surface up, the two level calls of each level
-    MS.walk_levels(plan, segs, lambda seg, first, end: sc._thermal_lin_walk(mom, seg[0], seg[1], first, end),
-                   lambda seg: CL.interaction_lin_(mom["iface_surface"], seg[0], seg[1], asurf, als),
+    MS.walk_levels(plan, segs, lambda seg, first, end: sc._thermal_lin_walk(mom, seg[0], seg[1], first, end, fwd.thermal_B),
+                   lambda seg: CL.interaction_lin_(mom["iface_surface"], seg[0], seg[1], asurf, als, lane=lane),
                    lambda seg, bot, first, end: CL.interaction_lin_("11", seg[0], seg[1], CL._CompositeAsAdded(bot[0]),
-                                                                    CL._CompositeLinAsAdded(bot[1])), level)
+                                                                    CL._CompositeLinAsAdded(bot[1]), lane=lane), level)
 
 
 def bytes_per_point(N: int, P: int, pl: int, Nz: int, n_tops: int, segments: bool, n_levels: int, n_stokes: int, nV: int,

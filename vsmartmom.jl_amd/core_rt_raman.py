@@ -12,7 +12,6 @@ from __future__ import annotations
 
 import ctypes as C
 import dataclasses
-import math
 from dataclasses import dataclass
 from typing import Optional
 
@@ -157,16 +156,7 @@ def postprocessing_vza_rs_(pol, comp, comp_rs: CompositeLayerRS, vza, vaz, qp, m
     """postprocessing_vza!(::RRS, ...) (postprocessing_vza.jl:117-151), SFI branch."""
     CR.postprocessing_vza_(pol, comp, vza, vaz, qp, m, weight, R_SFI, T_SFI)
     n, nV = pol.n, len(vza)
-    row0 = (C.c_int * nV)()
-    ctype = C.c_double if comp.dtype == torch.float64 else C.c_float
-    w = (ctype * (nV * n))()
-    for v in range(nV):
-        imu = int(np.argmin(np.abs(qp.qp_mu - qp.qp_mu.dtype.type(H.cosd(vza[v])))))
-        row0[v] = imu * n
-        c, s = H.cosd(m * vaz[v]), H.sind(m * vaz[v])
-        ws = [c, c, s, s][:n]
-        for k in range(n):
-            w[v + nV * k] = weight * ws[k]
+    row0, w = CR._vza_rows_weights(pol, vza, vaz, qp, m, weight, comp.dtype)
     _lib.call("vsm_postprocess_vza_ie", comp.dtype, comp.N, n, comp.nSpec, comp_rs.K, nV, row0, w, CR._ptr(comp_rs.ieJ0_m),
               CR._ptr(comp_rs.ieJ0_p), CR._ptr(ieR_SFI), CR._ptr(ieT_SFI), CR._stream_ptr())
 
@@ -280,7 +270,7 @@ class SceneRRS:
             m = mom["m"]
             if m == 0 and reduced:
                 continue           # (below: the Stokes_IQ run of this moment)
-            weight = FT(0.5 / math.pi) if m == 0 else FT(1.0 / math.pi)
+            weight = CR.fourier_weight(FT, m)
             drs.Zpp, drs.Zmp = self.Zie[m]
             # the reference dispatches interaction!(RS_type, scattering_interfaces_all[iz], ...) on the tags of
             # extractEffectiveProps (rt_kernel!(::RRS) itself hard-wires scatter = true, rt_kernel.jl:365)

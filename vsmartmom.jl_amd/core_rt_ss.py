@@ -13,7 +13,6 @@ layer, no [N,S,K] source array.
 from __future__ import annotations
 
 import ctypes as C
-import math
 import numpy as np
 import torch
 
@@ -113,7 +112,7 @@ class SceneSS:
         nV = len(model.vza)
         for mom in fwd.moments:
             m = mom["m"]
-            weight = FT(0.5 / math.pi) if m == 0 else FT(1.0 / math.pi)
+            weight = CR.fourier_weight(FT, m)
             layers = mom["layers"]
             props = [ly["props"].materialize() for ly in layers]     # Z[N,N,S] only where a layer mixes scatterers per point
             tau, tau_sum = [p.tau for p in props], [ly["tau_sum"] for ly in layers]
