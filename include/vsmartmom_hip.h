@@ -399,6 +399,32 @@ int vsm_lambertian_surface_spectral_f64(const vsm_quad_f64* q, int S, int m, con
                                         const vsm_added_f64* added, void* stream);
 int vsm_lambertian_surface_spectral_f32(const vsm_quad_f32* q, int S, int m, const float* albedo, const float* tau_sum,
                                         const vsm_added_f32* added, void* stream);
+/* The same surface with K albedo Jacobian slots isurf .. isurf + K - 1 (the reference linearizes LambertianSurfaceScalar only: this
+ * is the exact derivative of the builder above).  albedo[S] and basis[K][S] (device, table k contiguous over the spectral axis):
+ * basis[k][s] = d albedo[s] / d x_k -- the Legendre polynomial P_k on the band grid for the coefficients of
+ * LambertianSurfaceLegendre, the values of the user's basis functions for LambertianSurfaceSpline.  With n = n_stokes,
+ * Rw[i, j] = [i % n == 0 and j % n == 0] mu[j] wt[j] and att_s = exp(-tau_sum[s] / mu0):
+ *   m = 0, forward (what vsm_lambertian_surface_spectral_* writes, the beam weighted by F0[0, s] like the other linearized builders):
+ *     r-+[:, :, s] = 2 albedo[s] Rw,  r+- = 0,  t++ = t-- = I,  j0+ = 0,  j0-[i, s] = [i % n == 0] mu0 F0[0, s] 2 albedo[s] att_s
+ *   m = 0, derivatives (all six stacks of all P slots are written, zero where nothing is stated):
+ *     layer slots p < p_layer (p_layer <= isurf):  ap_J0-[p][i, s] = -j0-[i, s] tau_sum_dot[p][s] / mu0, with the j0- formed here
+ *       (a SurfaceSIF injected into j0- afterwards does not enter it)
+ *     surface slots k < K:  ap_r-+[isurf + k][:, :, s] = 2 basis[k][s] Rw,
+ *                           ap_J0-[isurf + k][i, s] = [i % n == 0] mu0 F0[0, s] 2 basis[k][s] att_s
+ *   m > 0: every forward block (t++ and t-- included, the forward builder's quirk) and every derivative block is zero.
+ * tau_sum_dot [S, p_layer] and F0 [n_stokes, S] as vsm_lambertian_surface_lin_* takes them.  added / added_lin: one block per
+ * spectral point (mat_stride = N*N) in both.  vectors_only != 0: only j0+-, ap_J0+- are written and the matrices may be shared
+ * blocks (mat_stride 0), for callers that read the vectors alone (the single-scattering run).  One thread per matrix element, the
+ * row axis fastest.  VSM_ERR_INVALID_ARG before any launch: K < 1, isurf < 0, isurf + K > P, p_layer > isurf, a null table, a
+ * d_symmetric layer. */
+int vsm_lambertian_surface_spectral_lin_f64(const vsm_quad_f64* q, int S, int m, const double* albedo, const double* basis, int K,
+                                            int isurf, const double* tau_sum, const double* tau_sum_dot, int p_layer,
+                                            const double* F0, const vsm_added_f64* added, const vsm_added_lin_f64* added_lin,
+                                            int vectors_only, void* stream);
+int vsm_lambertian_surface_spectral_lin_f32(const vsm_quad_f32* q, int S, int m, const float* albedo, const float* basis, int K,
+                                            int isurf, const float* tau_sum, const float* tau_sum_dot, int p_layer,
+                                            const float* F0, const vsm_added_f32* added, const vsm_added_lin_f32* added_lin,
+                                            int vectors_only, void* stream);
 
 /* ---- BRDF surfaces: Cox-Munk ocean + the generic BRDF surface layer ------------------------------------------
  * CoxMunkSurface{FT} (src/CoreRT/types.jl:525-536); n_water is the complex index the reference's call sites use

@@ -118,6 +118,7 @@ _SIGS = {
     "vsm_layer_expk_{T}": (_I, [_I, _P, "{R}", _P, _P]),
     "vsm_coxmunk_reflectance_{T}": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P]),
     "vsm_lambertian_surface_spectral_{T}": (_I, [_P, _I, _I, _P, _P, _P, _P]),
+    "vsm_lambertian_surface_spectral_lin_{T}": (_I, [_P, _I, _I, _P, _P, _I, _I, _P, _P, _I, _P, _P, _P, _I, _P]),
     "vsm_brdf_surface_{T}": (_I, [_P, _I, _I, _P, _P, _P, _P]),
     "vsm_brdf_surface_lin_{T}": (_I, [_P, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P]),
     "vsm_land_brdf_reflectance_lin_{T}": (_I, [_P, _I, _P, _I, _I, _P, _P, _P, _P, _P]),

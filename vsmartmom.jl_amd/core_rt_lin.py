@@ -122,8 +122,16 @@ def elemental_lin_(pol, tau_sum, tau_sum_dot, dtau, dtau_dot, F0, props: CR.Devi
 LAND_BRDF = {H.rpvSurfaceScalar: (0, 4), H.RossLiSurfaceScalar: (1, 3)}
 
 
+SPECTRAL_LAMBERTIAN = (H.LambertianSurfaceLegendre, H.LambertianSurfaceSpline)   # per-point albedo: per-point surface layers
+LAMBERTIAN = (H.LambertianSurfaceScalar,) + SPECTRAL_LAMBERTIAN
+
+
 def surface_param_names(surface):
-    """The surface's Jacobian slots in order: the fields of its dataclass."""
+    """The surface's Jacobian slots in order: the fields of its dataclass; the coefficients c0 .. c{K-1} of
+    LambertianSurfaceLegendre; the tables albedo_dot[k] of LambertianSurfaceSpline."""
+    if isinstance(surface, SPECTRAL_LAMBERTIAN):
+        fmt = "c%d" if isinstance(surface, H.LambertianSurfaceLegendre) else "albedo_dot[%d]"
+        return [fmt % k for k in range(H.surface_albedo_slots(surface))]
     return [f.name for f in dataclasses.fields(surface)]
 
 
@@ -151,6 +159,17 @@ def brdf_surface_lin_multi_(dq: CR.DeviceQuad, S: int, m: int, rho, drho, isurf:
     q_, a_, al_ = dq.cstruct(), added_s.cstruct(), als.cstruct()
     _lib.call("vsm_brdf_surface_lin_multi", added_s.dtype, C.byref(q_), S, m, CR._ptr(rho), CR._ptr(drho), int(drho.shape[0]),
               int(isurf), CR._ptr(tau_sum), CR._ptr(tau_sum_dot), p_layer, CR._ptr(F0), C.byref(a_), C.byref(al_), CR._stream_ptr())
+
+
+def lambertian_surface_spectral_lin_(dq: CR.DeviceQuad, S: int, m: int, albedo, basis, isurf: int, tau_sum, tau_sum_dot, p_layer: int,
+                                     F0, added_s: CR.AddedLayer, als: AddedLayerLin, vectors_only: bool = False):
+    """vsm_lambertian_surface_spectral_lin_*: the linearized surface layer of a spectrally varying Lambertian albedo -- albedo (S,),
+    basis (K, S) device tensors -- with the K = basis.shape[0] albedo slots isurf .. isurf + K - 1 into the PER-POINT surface
+    layers `added_s` / `als`; vectors_only: j0+-, ap_J0+- alone (the layers may then be the shared ones)."""
+    q_, a_, al_ = dq.cstruct(), added_s.cstruct(), als.cstruct()
+    _lib.call("vsm_lambertian_surface_spectral_lin", added_s.dtype, C.byref(q_), S, m, CR._ptr(albedo), CR._ptr(basis),
+              int(basis.shape[0]), int(isurf), CR._ptr(tau_sum), CR._ptr(tau_sum_dot), p_layer, CR._ptr(F0), C.byref(a_), C.byref(al_),
+              1 if vectors_only else 0, CR._stream_ptr())
 
 
 _lin_work = {}
@@ -223,6 +242,10 @@ class LinInputs:
 
     def _check_lin_args(self, model: H.RTModel, lin_model: H.LinModel, NAer: int, NGas: int, NSurf: int):
         land = LAND_BRDF.get(type(model.surface))
+        if isinstance(model.surface, SPECTRAL_LAMBERTIAN):   # K albedo slots: treated like a K-parameter land surface below
+            land = (None, H.surface_albedo_slots(model.surface))
+            if land[1] < 2 and isinstance(model.surface, H.LambertianSurfaceLegendre):
+                raise _lib.VSMError("rt_run (linearized): LambertianSurfaceLegendre needs at least two coefficients")
         if land is not None and NSurf != land[1]:
             raise _lib.VSMError("rt_run (linearized): %s has %d parameters (%s): NSurf = %d expected, got %r"
                                 % (type(model.surface).__name__, land[1], ", ".join(surface_param_names(model.surface)), land[1],
@@ -331,6 +354,12 @@ class LinInputs:
     def _surface_tables(self):
         model = self.model
         self.surf = []
+        # the albedo basis of a spectrally varying Lambertian surface, (K, S): formed on the FULL spectral axis and sliced like the
+        # forward scene's albedo_d (a shard must not rebuild the Legendre abscissa on its own length)
+        self.albedo_basis = None
+        if isinstance(model.surface, SPECTRAL_LAMBERTIAN):
+            basis = H.surface_albedo_basis(model.surface, model.tau_rayl.shape[0], self.FT)
+            self.albedo_basis = array_type(self.arch)(np.ascontiguousarray(basis[:, self.sl].astype(self.FT)))
         if type(model.surface) in LAND_BRDF:       # all moments and parameters in one launch: (rho[m], drho[m][K])
             rho, drho = land_brdf_reflectance_lin(model.surface, self.dq, model.m_max, self.arch, self.FT)
             self.surf = [(rho[m], drho[m]) for m in range(model.m_max + 1)]
@@ -360,7 +389,9 @@ class SceneLin(LinInputs):
     derivatives are inputs: LinModel.tau_aer_dot / lin_aerosol_optics), the gases, then the surface slots -- ONE for the
     Lambertian albedo (lambertian_surface_lin.jl:48-162) or the Cox-Munk wind speed (coxmunk_surface_lin.jl:27-102); FOUR for
     rpvSurfaceScalar (rho0, rho_c, k, Theta) and THREE for RossLiSurfaceScalar (fvol, fgeo, fiso), whose derivatives are ours
-    (LAND_BRDF, vsm_land_brdf_reflectance_lin / vsm_brdf_surface_lin_multi).  With a ThermalEmission source the
+    (LAND_BRDF, vsm_land_brdf_reflectance_lin / vsm_brdf_surface_lin_multi); K for the K coefficients of
+    LambertianSurfaceLegendre or the K tables of LambertianSurfaceSpline.albedo_dot (one without them), also ours
+    (vsm_lambertian_surface_spectral_lin on PER-POINT surface layers, forward and derivative).  With a ThermalEmission source the
     `:thermal` slot and its derivatives are added for m = 0 (_run_thermal, vsm_thermal_source_lin), and the nPlanck slots of
     ThermalEmission.B_layer_dot follow the surface slots in Rd / Td."""
 
@@ -408,7 +439,7 @@ class SceneLin(LinInputs):
             self.prepare()
         self._surface_tables()
         self.added, self.added_s, self.comp = fwd.added, fwd.added_surface, fwd.composite
-        self.al, self.als = AddedLayerLin(FT, arch, P, N, S), AddedLayerLin(FT, arch, P, N, S, shared=True)
+        self.al, self.als = AddedLayerLin(FT, arch, P, N, S), self._new_surface_added_lin()
         self.cl = CompositeLayerLin(FT, arch, P, N, S)
         self.expk = torch.empty(max(S, 1), dtype=dt, device=dev)
         self.R, self.T = fwd.R_SFI, fwd.T_SFI
@@ -420,7 +451,7 @@ class SceneLin(LinInputs):
         # response solve (_sif_slots), chosen on the FULL spectral axis so that every shard solves the same ones.  Over a surface
         # that is not Lambertian the source does nothing (CoreRT.surface_source_contribute_) and the slots stay zero.
         self.sif_dot2, self._sif_comps = None, []
-        if self.nSIF and isinstance(model.surface, H.LambertianSurfaceScalar):
+        if self.nSIF and isinstance(model.surface, CR.SIF_SURFACES):
             self._sif_comps = [c for c in range(pol.n) if np.any(sif_dot[:, c, :] != 0)]
             self.sif_dot2 = array_type(arch)(np.ascontiguousarray((2.0 * sif_dot[:, :, self.sl]).astype(FT)))
         self.Rd = torch.zeros((P + self.nPlanck + self.nSIF, S, pol.n, nV), dtype=dt, device=dev)
@@ -434,14 +465,14 @@ class SceneLin(LinInputs):
         self._layer_slots = (0, pl) if 0 < pl < P else None
         # The Fourier moment m = 0 as a Stokes_IQ run (large batches; models without aerosol Jacobian slots over a Lambertian
         # surface).  At m = 0 no phase matrix couples (I,Q) with (U,V) (compute_Z_matrices.jl:26-110; the forward scene reads the
-        # exact zeros off the device: `coupling`), the Lambertian surface reflects into I only, the gas and albedo derivatives
+        # exact zeros off the device: `coupling`), the Lambertian surface (scalar or per-point albedo) reflects into I only, the gas and albedo derivatives
         # inherit the structure, and a beam without U / V components drives nothing in the (U,V) block: R, T, Rdot, Tdot of m = 0
         # are those of the same model carried with two Stokes components, U = V = 0.
         self.sub0 = None
         F0m = model.F0
         c0 = fwd.coupling[0] if getattr(fwd, "coupling", None) else None
         if (_reduce_m0 and REDUCE_M0 and pol.n >= 3 and S >= self.LANE_POINTS and NAer == 0 and not host_optics and c0 is not None
-                and isinstance(model.surface, H.LambertianSurfaceScalar) and (F0m is None or not np.any(np.asarray(F0m)[2:] != 0))
+                and isinstance(model.surface, LAMBERTIAN) and (F0m is None or not np.any(np.asarray(F0m)[2:] != 0))
                 and not any(s_.has_uv() for s_ in sif_src)   # (a surface emission with a U / V row drives the (U,V) block)
                 and not any(c0 >> (4 * a + b) & 1 or c0 >> (4 * b + a) & 1 for a in (0, 1) for b in range(2, pol.n))):
             self.sub0 = SceneLin(self._sub0_model(), lin_model, NAer, NGas, NSurf, spec_slice, _reduce_m0=False)
@@ -517,7 +548,7 @@ class SceneLin(LinInputs):
             self._lanes.append(dict(
                 added=CR.make_added_layer(FT, arch, (N, N), S), al=AddedLayerLin(FT, arch, P, N, S),
                 comp=CR.make_composite_layer(FT, arch, (N, N), S), cl=CompositeLayerLin(FT, arch, P, N, S),
-                added_s=self._new_surface_added(), als=AddedLayerLin(FT, arch, P, N, S, shared=True),
+                added_s=self._new_surface_added(), als=self._new_surface_added_lin(),
                 expk=torch.empty_like(self.expk), R=torch.zeros_like(self.R), T=torch.zeros_like(self.T),
                 Rd=torch.zeros_like(self.Rd), Td=torch.zeros_like(self.Td), stream=torch.cuda.Stream(), lane=len(self._lanes)))
         return self._lanes[k]
@@ -525,6 +556,11 @@ class SceneLin(LinInputs):
     def _new_surface_added(self):
         a0 = self.added_s
         return CR.AddedLayer(self.FT, self.arch, self.N, self.S, a0.shared, a0.d_symmetric)
+
+    def _new_surface_added_lin(self):
+        """The derivative stacks of a surface layer: shared blocks or one per spectral point, as the forward surface layer has them
+        (per point for the spectrally varying Lambertian surfaces: 4 P N^2 S elements instead of 4 P N^2)."""
+        return AddedLayerLin(self.FT, self.arch, self.P, self.N, self.S, shared=self.added_s.shared)
 
     def run(self, lanes: Optional[int] = None, fold: Optional[bool] = None, graph: Optional[bool] = None):
         """The device-resident part of rt_run_lin.jl:200-322: Fourier loop -> layers -> surface -> post-processing.
@@ -935,6 +971,8 @@ class SceneLin(LinInputs):
                       CR._ptr(tsd_s), pl, CR._ptr(F0), C.byref(a_), C.byref(al_), CR._stream_ptr())
         elif type(model.surface) in LAND_BRDF:
             brdf_surface_lin_multi_(self.dq, S, m, rho, drho, isurf, tau_sum_s, tsd_s, pl, F0, added_s, als)
+        elif isinstance(model.surface, SPECTRAL_LAMBERTIAN):   # (mom["rho"]: the forward scene's per-point albedo)
+            lambertian_surface_spectral_lin_(self.dq, S, m, mom["rho"], self.albedo_basis, isurf, tau_sum_s, tsd_s, pl, F0, added_s, als)
         else:
             alb = C.c_double(model.surface.albedo) if dt == torch.float64 else C.c_float(model.surface.albedo)
             _lib.call("vsm_lambertian_surface_lin", dt, C.byref(q_), S, m, alb, isurf, CR._ptr(tau_sum_s), CR._ptr(tsd_s), pl,
@@ -950,7 +988,7 @@ class SceneLin(LinInputs):
             dev = self.expk.device
             self._th = dict(added=CR.make_added_layer(FT, arch, (N, N), S), al=AddedLayerLin(FT, arch, P, N, S),
                             comp=CR.make_composite_layer(FT, arch, (N, N), S), cl=CompositeLayerLin(FT, arch, P, N, S),
-                            added_s=self._new_surface_added(), als=AddedLayerLin(FT, arch, P, N, S, shared=True),
+                            added_s=self._new_surface_added(), als=self._new_surface_added_lin(),
                             F0=torch.zeros_like(self.F0), ones=torch.empty(max(S, 1), dtype=self.dt, device=dev),
                             zero_dtd=torch.zeros((P, max(S, 1)), dtype=self.dt, device=dev), lane=0)
         return self._th
@@ -1054,8 +1092,10 @@ def rt_run_lin(model: H.RTModel, lin_model: H.LinModel, NAer: int, NGas: int, NS
     Rdot/Tdot: [nVZA, nStokes, nSpec, Nparams].  Supported: NAer = number of aerosols of the model (7 slots each, optics
     derivatives supplied in lin_model), NGas = len(lin_model.tau_abs_dot), NSurf = 1
     (Lambertian albedo or Cox-Munk wind speed, by the model's surface), NSurf = 4 for rpvSurfaceScalar (rho0, rho_c, k, Theta)
-    or NSurf = 3 for RossLiSurfaceScalar (fvol, fgeo, fiso); the surface slots come last.  Like the reference's linearized
-    driver this path applies no TMS correction.
+    or NSurf = 3 for RossLiSurfaceScalar (fvol, fgeo, fiso), NSurf = K for LambertianSurfaceLegendre with K coefficients (slot k =
+    d / d legendre_coeff[k]) and for LambertianSurfaceSpline with albedo_dot [K, nSpec] (slot k = d / d x_k, albedo_dot[k] =
+    d albedo / d x_k on the band grid; without albedo_dot NSurf = 1, a table of ones); the surface slots come last.  Like the
+    reference's linearized driver this path applies no TMS correction.
 
     Sources: model.sources may hold SolarBeam and / or ThermalEmission, as CoreRT.rt_run takes them (without a SolarBeam F0 = 0).
     R, T then include the thermal radiance and every slot of Rdot / Tdot the derivative of the thermal slot (m = 0

@@ -258,7 +258,9 @@ def _run_thermal(sc: CL.SceneLin, plan: MS.LevelPlan, segs, out, full):
 def bytes_per_point(N: int, P: int, pl: int, Nz: int, n_tops: int, segments: bool, n_levels: int, n_stokes: int, nV: int,
                     itemsize: int, thermal: bool = False, nPlanck: int = 0) -> int:
     """Device bytes per spectral point of a linearized multi-sensor run (an estimate on the safe side): the kept tops, the two
-    segment composites, the scene's own added / composite / surface layers, its per-layer optics and the outputs.  thermal: what
+    segment composites, the scene's own added / composite / surface layers (the surface layer counted as a full per-point layer,
+    forward and derivative: what it is over LambertianSurfaceLegendre / Spline, more than the shared blocks of the other surfaces),
+    its per-layer optics and the outputs.  thermal: what
     the thermal slot keeps beside them (m = 0 only, on the parent's N): its own tops, R and Rdot included ((1 + pl)(N^2 + N) each,
     while the solar tops of the last moment are still alive), its linearized added / composite / surface layers, the forward
     slot's three layers and two segment composites (the Planck walks), the Planck source vectors of every level, the Planck
@@ -282,7 +284,8 @@ def rt_run_multisensor(model: H.RTModel, lin_model: H.LinModel, NAer: int, NGas:
     Levels as in CoreRT.rt_run_multisensor: 0 = TOA, l = below layer l, Nz = just above the surface (the surface layer alone as the
     bottom); duplicates and any order allowed, each distinct level computed once.  Level 0 is (R, T, Rdot, Tdot) of
     SceneLin.run(lanes=1, fold=False) on the same scene bit for bit (rt_run_lin's default lanes / folded walk agree with it to
-    rounding).  Model arguments, surfaces and NSurf as rt_run_lin takes them (1: Lambertian / Cox-Munk; 4: RPV; 3: Ross-Li).
+    rounding).  Model arguments, surfaces and NSurf as rt_run_lin takes them (1: Lambertian / Cox-Munk; 4: RPV; 3: Ross-Li; K:
+    LambertianSurfaceLegendre / LambertianSurfaceSpline, whose per-point surface layer is the bottom of level Nz).
 
     streams=True: a MultiSensorLinResult, which also carries the level vectors and their derivatives at all quadrature streams per
     moment.  max_points: run the spectral axis in blocks of about that many points (bit-identical to one pass: points are

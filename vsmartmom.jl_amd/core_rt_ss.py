@@ -186,7 +186,9 @@ class SceneSSLin(CL.LinInputs):
     (CoreRTLin.LinInputs: dtau_dot_all -- here of the layers' FULL tau, vsm_layer_optics_lin with an all-zero doubling table --,
     varpi_dot, tau_sum_dot, fz, zdcoef, Zall, the Cox-Munk (rho, drho)).  The one derivative layer it owns is the SHARED surface
     AddedLayerLin the linearized surface builders write (4 P N^2 + 2 P N S elements), with a shared forward AddedLayer beside it
-    for the builder's own j0-: no added or composite layer, no derivative stack, nothing of size P N^2 S."""
+    for the builder's own j0-: no added or composite layer, no derivative stack, nothing of size P N^2 S -- over the spectrally
+    varying Lambertian surfaces too, whose builder runs in its vectors-only mode here (the column kernel reads j0- and ap_J0-+
+    alone; the forward scene keeps its per-point surface layer)."""
 
     def __init__(self, model: H.RTModel, lin_model: H.LinModel, NAer: int, NGas: int, NSurf: int):
         _refuse_sources(model)
@@ -236,6 +238,9 @@ class SceneSSLin(CL.LinInputs):
                           CR._ptr(tsd_s), pl, CR._ptr(self.F0), C.byref(a_), C.byref(al_), CR._stream_ptr())
             elif type(model.surface) in CL.LAND_BRDF:
                 CL.brdf_surface_lin_multi_(self.dq, S, m, rho, drho, isurf, tau_sum_s, tsd_s, pl, self.F0, self.added_s, self.als)
+            elif isinstance(model.surface, CL.SPECTRAL_LAMBERTIAN):   # (vectors only: the matrices of these shared layers are not read)
+                CL.lambertian_surface_spectral_lin_(self.dq, S, m, mom["rho"], self.albedo_basis, isurf, tau_sum_s, tsd_s, pl, self.F0,
+                                                    self.added_s, self.als, vectors_only=True)
             else:
                 alb = C.c_double(model.surface.albedo) if dt == torch.float64 else C.c_float(model.surface.albedo)
                 _lib.call("vsm_lambertian_surface_lin", dt, C.byref(q_), S, m, alb, isurf, CR._ptr(tau_sum_s), CR._ptr(tsd_s), pl,
@@ -262,8 +267,8 @@ class SceneSSLin(CL.LinInputs):
 def rt_run_ss_lin(model: H.RTModel, lin_model: H.LinModel, NAer: int, NGas: int, NSurf: int):
     """The linearized elastic single-scattering run -> (R, T, Rdot, Tdot).  R, T are rt_run_ss(model)'s, bit for bit; Rdot / Tdot
     [nVZA, nStokes, nSpec, Nparams] are their analytic Jacobians in the parameter slots of rt_run_lin (ParameterLayout: 7 per
-    aerosol, the gases, the surface slots: the Lambertian albedo or the Cox-Munk wind speed, or the 4 / 3 parameters of an RPV / Ross-Li
-    surface).  Same arguments and refusals as
+    aerosol, the gases, the surface slots: the Lambertian albedo or the Cox-Munk wind speed, the 4 / 3 parameters of an RPV / Ross-Li
+    surface, or the K albedo slots of LambertianSurfaceLegendre / LambertianSurfaceSpline).  Same arguments and refusals as
     rt_run_lin; SolarBeam is the only source, at most three aerosols, no Cox-Munk single-scattering correction.  The surface
     slot and the surface's share of every slot are those of the reference's linearized surface builders, which weigh the direct
     beam with F0 where the forward builders use I0 = e1: with F0[0] = 1 (and, over Cox-Munk, F0 = e1) they are the exact

@@ -1009,6 +1009,22 @@ VSM_LIN_API(float, f32)
     return brdf_surface_lin_multi<T>(cvt_quad<T>(q), S, m, rho, drho, K, isurf, tau_sum, tau_sum_dot, p_layer, F0,     \
                                      cvt_added<T>(added), cvt_al<T>(al), as_stream(stream));                           \
   }                                                                                                                    \
+  extern "C" int vsm_lambertian_surface_spectral_lin_##SFX(const vsm_quad_##SFX* q, int S, int m, const T* albedo,     \
+                                                           const T* basis, int K, int isurf, const T* tau_sum,         \
+                                                           const T* tau_sum_dot, int p_layer, const T* F0,             \
+                                                           const vsm_added_##SFX* added, const vsm_added_lin_##SFX* al, \
+                                                           int vectors_only, void* stream) {                           \
+    int rc;                                                                                                            \
+    VSM_REQUIRE(added && added->d_symmetric == 0, "lambertian_surface_spectral_lin: d_symmetric layers are not accepted"); \
+    if ((rc = check_quad(q)) || (rc = check_added(added)) || (rc = check_al(al))) return rc;                           \
+    VSM_REQUIRE(S >= 0 && m >= 0 && albedo && basis && tau_sum && F0 && (tau_sum_dot || p_layer == 0) && K >= 1 &&     \
+                    isurf >= 0 && isurf + K <= al->P && p_layer >= 0 && p_layer <= isurf,                              \
+                "lambertian_surface_spectral_lin: bad argument (albedo [S], basis [K][S], K >= 1 surface slots "       \
+                "[isurf, isurf + K) within P, the layer slots [0, p_layer) before them)");                             \
+    return lambertian_surface_spectral_lin<T>(cvt_quad<T>(q), S, m, albedo, basis, K, isurf, tau_sum, tau_sum_dot,     \
+                                              p_layer, F0, cvt_added<T>(added), cvt_al<T>(al), vectors_only,           \
+                                              as_stream(stream));                                                      \
+  }                                                                                                                    \
   extern "C" int vsm_surface_sif_##SFX(int N, int n_stokes, int S, const T* sif, const vsm_added_##SFX* added_surface,  \
                                        void* stream) {                                                                 \
     int rc;                                                                                                            \

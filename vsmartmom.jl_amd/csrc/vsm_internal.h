@@ -115,6 +115,11 @@ template <typename T>
 int brdf_surface(const quad<T>& q, int S, int m, const T* rho, const T* tau_sum, const added<T>& a, hipStream_t st);
 template <typename T>
 int lambertian_surface_spectral(const quad<T>& q, int S, int m, const T* albedo, const T* tau_sum, const added<T>& a, hipStream_t st);
+// lambertian_surface_spectral with K albedo slots isurf .. isurf + K - 1 (basis[K][S] = d albedo / d x_k); vectors_only: j0+-, ap_J0+- alone
+template <typename T>
+int lambertian_surface_spectral_lin(const quad<T>& q, int S, int m, const T* albedo, const T* basis, int K, int isurf,
+                                    const T* tau_sum, const T* tau_sum_dot, int p_layer, const T* F0, const added<T>& a,
+                                    const added_lin<T>& al, int vectors_only, hipStream_t st);
 template <typename T>
 int brdf_surface_lin(const quad<T>& q, int S, int m, const T* rho, const T* drho, int iparam, const T* tau_sum,
                      const T* tau_sum_dot, int p_layer, const T* F0, const added<T>& a, const added_lin<T>& al, hipStream_t st);

@@ -625,6 +625,86 @@ int lambertian_surface_spectral(const quad<T>& q, int S, int m, const T* albedo,
   return VSM_OK;
 }
 
+// ---- the same surface with K albedo slots isurf .. isurf + K - 1 (ours: the reference linearizes the scalar surface only).  The
+// albedo of point s is a function of K parameters with d albedo[s] / d x_k = basis[k][s] (the Legendre polynomial P_k on the band
+// grid, a spline's hat function, or ones).  Forward half: k_lambertian_spectral element for element, the beam weighted by F0[0, s]
+// as the other linearized builders weigh it.  Derivative half: every block of every slot is written --
+//   ap_r-+[isurf + k][:, :, s] = 2 basis[k][s] E11 (x) (mu w),  ap_J0-[isurf + k][i, s] = [I row] mu0 F0[0, s] 2 basis[k][s] att_s,
+//   ap_J0-[p][i, s] = -j0-[i, s] tau_sum_dot[p][s] / mu0 for the layer slots p < p_layer (from the beam term formed HERE, never read
+//   back: a later SurfaceSIF injection into j0- cannot leak into it), zero everywhere else and for m > 0.
+// One thread per element of a matrix block, the row axis fastest: the per-point blocks of every stack are written in consecutive
+// addresses; the threads of a block's first column write the vectors too.  MATS = false (vectors only, one thread per (row, point)):
+// j0+-, ap_J0+- alone, for callers whose surface matrices are shared blocks nobody reads (the single-scattering scene). ----
+template <typename T, bool MATS>
+__global__ void __launch_bounds__(256) k_lambertian_spectral_lin(int N, int ns, long long S, int m, const T* __restrict__ albedo,
+                                                                 const T* __restrict__ basis, int K, int isurf, int P, int p_layer,
+                                                                 const T* __restrict__ mu, const T* __restrict__ wt, T mu0,
+                                                                 const T* __restrict__ tau_sum, const T* __restrict__ tau_sum_dot,
+                                                                 const T* __restrict__ F0, added<T> a, added_lin<T> al) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  const long long NN = (long long)N * N;
+  const long long per = MATS ? NN : (long long)N;
+  if (e >= per * S) return;
+  const long long s = e / per;
+  const int x = (int)(e - s * per), i = x % N, j = x / N;   // (vectors only: j = 0)
+  if (MATS) {
+    const bool ii = (m == 0) && (i % ns == 0) && (j % ns == 0);
+    const T sc = ii ? T(2) * (mu[j] * wt[j]) : T(0);
+    const T d = (m == 0 && i == j) ? T(1) : T(0);
+    a.r_mp[e] = albedo[s] * sc;
+    a.r_pm[e] = T(0);
+    a.t_pp[e] = d;
+    a.t_mm[e] = d;
+    for (int p = 0; p < P; ++p) {
+      const long long o = e + NN * S * p;
+      const int k = p - isurf;
+      al.ap_r_mp[o] = (k >= 0 && k < K) ? basis[(long long)k * S + s] * sc : T(0);
+      al.ap_r_pm[o] = T(0);
+      al.ap_t_pp[o] = T(0);
+      al.ap_t_mm[o] = T(0);
+    }
+  }
+  if (j == 0) {
+    const long long o = s * N + i;
+    const bool irow = (m == 0) && (i % ns == 0);
+    // the beam term of an albedo (or basis value) v, in k_lambertian_spectral's order of operations: the same bits at F0[0, s] = 1
+    const T att = irow ? exp(-tau_sum[s] / mu0) : T(0), f0 = irow ? F0[(long long)ns * s] : T(0);
+    const T jm = (mu0 * ((T(2) * albedo[s]) * att)) * f0;
+    a.j0_p[o] = T(0);
+    a.j0_m[o] = jm;
+    for (int p = 0; p < P; ++p) {
+      const long long op = o + (long long)N * S * p;
+      const int k = p - isurf;
+      T v = T(0);
+      if (p < p_layer) v = -jm * tau_sum_dot[s + S * p] / mu0;
+      if (k >= 0 && k < K) v = (mu0 * ((T(2) * basis[(long long)k * S + s]) * att)) * f0;
+      al.ap_J0_p[op] = T(0);
+      al.ap_J0_m[op] = v;
+    }
+  }
+}
+template <typename T>
+int lambertian_surface_spectral_lin(const quad<T>& q, int S, int m, const T* albedo, const T* basis, int K, int isurf,
+                                    const T* tau_sum, const T* tau_sum_dot, int p_layer, const T* F0, const added<T>& a,
+                                    const added_lin<T>& al, int vectors_only, hipStream_t st) {
+  const int N = q.N;
+  if (!vectors_only && (a.mat_stride != (long long)N * N || al.mat_stride != (long long)N * N)) {
+    set_error("lambertian_surface_spectral_lin: the surface layers need one block per spectral point (mat_stride = N*N)");
+    return VSM_ERR_INVALID_ARG;
+  }
+  if (S <= 0) return VSM_OK;
+  const long long tot = (long long)N * (vectors_only ? 1 : N) * S;
+  const dim3 g((unsigned)((tot + 255) / 256)), b(256);
+  if (vectors_only)
+    hipLaunchKernelGGL((k_lambertian_spectral_lin<T, false>), g, b, 0, st, N, q.n_stokes, (long long)S, m, albedo, basis, K, isurf, al.P,
+                       p_layer, q.mu, q.wt, q.mu0, tau_sum, tau_sum_dot, F0, a, al);
+  else
+    hipLaunchKernelGGL((k_lambertian_spectral_lin<T, true>), g, b, 0, st, N, q.n_stokes, (long long)S, m, albedo, basis, K, isurf, al.P,
+                       p_layer, q.mu, q.wt, q.mu0, tau_sum, tau_sum_dot, F0, a, al);
+  VSM_LAUNCH_CHECK("k_lambertian_spectral_lin");
+  return VSM_OK;
+}
+
 // ---- TMS single-scattering correction (coxmunk_surface.jl:481-569) ---------------------------------------------------
 struct pp_args_s {
   int row0[64];
@@ -850,6 +930,8 @@ int surface_sif(int N, int ns, int S, const T* sif, const added<T>& a, hipStream
   template int coxmunk_reflectance<T>(const cm_surf<T>&, int, int, const T*, int, int, const T*, const T*, T*, T*, hipStream_t); \
   template int brdf_surface<T>(const quad<T>&, int, int, const T*, const T*, const added<T>&, hipStream_t);                   \
   template int lambertian_surface_spectral<T>(const quad<T>&, int, int, const T*, const T*, const added<T>&, hipStream_t);    \
+  template int lambertian_surface_spectral_lin<T>(const quad<T>&, int, int, const T*, const T*, int, int, const T*, const T*, \
+                                                  int, const T*, const added<T>&, const added_lin<T>&, int, hipStream_t);     \
   template int brdf_surface_lin<T>(const quad<T>&, int, int, const T*, const T*, int, const T*, const T*, int, const T*,      \
                                    const added<T>&, const added_lin<T>&, hipStream_t);                                        \
   template int land_brdf_reflectance_lin<T>(int, const T*, int, int, const T*, int, int, const T*, const T*, T*, T*,          \

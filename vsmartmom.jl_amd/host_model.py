@@ -308,29 +308,75 @@ class LambertianSurfaceLegendre:
 
 @dataclass
 class LambertianSurfaceSpline:
-    """types.jl:546-549 with the interpolator already evaluated on the band grid: albedo[nSpec] = interpolator(wlGrid)."""
+    """types.jl:546-549 with the interpolator already evaluated on the band grid: albedo[nSpec] = interpolator(wlGrid).
+    albedo_dot [K, nSpec] (optional; the linearized runs read it, the convention of SurfaceSIF.SIF0_dot and
+    ThermalEmission.B_layer_dot): table k = d albedo / d x_k on the band grid -- the values of the spline's or hat basis functions
+    of the K retrieved quantities -- gives NSurf = K albedo slots.  None: ONE slot with a table of ones, at point s the derivative
+    with respect to that point's own albedo."""
     albedo: Sequence[float]
+    albedo_dot: Optional[np.ndarray] = None
+
+    def __post_init__(self):
+        if self.albedo_dot is not None:
+            d = np.asarray(self.albedo_dot)
+            if d.ndim != 2 or d.shape[0] < 1 or d.shape[1] != np.asarray(self.albedo).shape[0]:
+                raise ValueError("LambertianSurfaceSpline: albedo_dot must be [K, nSpec] with K >= 1 tables on the grid of albedo "
+                                 "(%d points); got shape %s" % (np.asarray(self.albedo).shape[0], d.shape))
+
+
+def _legendre_columns(nSpec: int, K: int, FT) -> np.ndarray:
+    """P [nSpec, K]: the Legendre polynomials P_0 .. P_{K-1} on x = range(-1, 1, length = nSpec) by the three-term recurrence of
+    compute_legendre_poly (legendre_functions.jl:223-252), arithmetic in FT."""
+    if K < 2:
+        raise ValueError("LambertianSurfaceLegendre needs at least two coefficients (compute_legendre_poly asserts nmax > 1)")
+    x = np.linspace(FT(-1), FT(1), nSpec).astype(FT)
+    P = np.zeros((nSpec, K), dtype=FT)
+    P[:, 0] = 1
+    P[:, 1] = x
+    for n in range(2, K):
+        l = n - 1
+        P[:, n] = ((2 * l + 1) * x * P[:, n - 1] - l * P[:, n - 2]) / (l + 1)
+    return P
 
 
 def surface_albedo_spectrum(surface, nSpec: int, FT=np.float64) -> np.ndarray:
     """The per-point albedo of the spectrally varying Lambertian surfaces (lambertian_surface.jl:113-117, 178): Legendre
-    basis by the three-term recurrence of compute_legendre_poly (legendre_functions.jl:223-252), arithmetic in FT."""
+    basis by the three-term recurrence of compute_legendre_poly (_legendre_columns), arithmetic in FT."""
     if isinstance(surface, LambertianSurfaceSpline):
         a = np.asarray(surface.albedo, dtype=FT)
         if a.shape != (nSpec,):
             raise ValueError("LambertianSurfaceSpline: albedo must be given on the band grid (%d points)" % nSpec)
         return a
     c = np.asarray(surface.legendre_coeff, dtype=FT)
-    if len(c) < 2:
-        raise ValueError("LambertianSurfaceLegendre needs at least two coefficients (compute_legendre_poly asserts nmax > 1)")
-    x = np.linspace(FT(-1), FT(1), nSpec).astype(FT)
-    P = np.zeros((nSpec, len(c)), dtype=FT)
-    P[:, 0] = 1
-    P[:, 1] = x
-    for n in range(2, len(c)):
-        l = n - 1
-        P[:, n] = ((2 * l + 1) * x * P[:, n - 1] - l * P[:, n - 2]) / (l + 1)
-    return (P @ c).astype(FT)
+    return (_legendre_columns(nSpec, len(c), FT) @ c).astype(FT)
+
+
+def surface_albedo_slots(surface) -> Optional[int]:
+    """The number of albedo Jacobian slots (the NSurf of the linearized runs) of a spectrally varying Lambertian surface: the
+    coefficients of LambertianSurfaceLegendre, the tables of LambertianSurfaceSpline.albedo_dot (1 without them); None for any
+    other surface."""
+    if isinstance(surface, LambertianSurfaceLegendre):
+        return len(surface.legendre_coeff)
+    if isinstance(surface, LambertianSurfaceSpline):
+        return 1 if surface.albedo_dot is None else int(np.asarray(surface.albedo_dot).shape[0])
+    return None
+
+
+def surface_albedo_basis(surface, nSpec: int, FT=np.float64) -> np.ndarray:
+    """basis [K, nSpec]: d albedo[s] / d x_k of the K = surface_albedo_slots(surface) albedo parameters, on the FULL band grid (a
+    spectral shard slices it; the Legendre abscissa is that of the whole band).  LambertianSurfaceLegendre: the columns
+    surface_albedo_spectrum multiplies the coefficients with; LambertianSurfaceSpline: albedo_dot, or ones."""
+    if isinstance(surface, LambertianSurfaceSpline):
+        if surface.albedo_dot is None:
+            return np.ones((1, nSpec), dtype=FT)
+        d = np.asarray(surface.albedo_dot, dtype=FT)
+        if d.ndim != 2 or d.shape[1] != nSpec:
+            raise ValueError("LambertianSurfaceSpline: albedo_dot must be [K, nSpec] on the band grid (%d points); got shape %s"
+                             % (nSpec, d.shape))
+        return d
+    if isinstance(surface, LambertianSurfaceLegendre):
+        return np.ascontiguousarray(_legendre_columns(nSpec, len(surface.legendre_coeff), FT).T)
+    raise TypeError("surface_albedo_basis: %r has no albedo spectrum" % (surface,))
 
 
 @dataclass
