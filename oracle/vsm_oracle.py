@@ -540,6 +540,24 @@ def expdiff_neg(a, b):
     return np.where(a == b, np.zeros_like(out), out)
 
 
+def expdiff_neg_mu(d, mi, mj):
+    """expdiff_neg(d / mi, d / mj), the form elemental.jl:323,379 calls it in.  In double precision the exponent difference
+    b - a = d / mj - d / mi is formed as d (mi - mj) / (mi mj): the same quantity without the cancellation.  With two nodes 1e-6
+    apart (a view 1e-4 degrees from the SZA) the reference's statement rounds a and b at eps each, 1e-10 of their difference, which is
+    within every tolerance the oracle is held to but is 4e-6 of a Jacobian in a central difference at h = 1e-5
+    (tests/test_oracle_geometry_nodes.py); as a reference the oracle should not carry that.  For separated nodes the two forms
+    agree within the statement's own rounding, 2 eps mu / |mi - mj| (tests/test_oracle_geometry_nodes.py).  Single-precision arrays keep the reference's statement: there the oracle is the yardstick of the
+    reference's own FP32 arithmetic (tests/test_gpu_fp32_accuracy.py), cancellation included."""
+    a, b = d / mi, d / mj
+    if np.result_type(a, b) != np.float64:
+        return expdiff_neg(a, b)
+    a, b, diff = np.broadcast_arrays(a, b, d * (mi - mj) / (mi * mj))
+    lo = np.exp(-a) * (-np.expm1(-diff))
+    hi = -np.exp(-b) * (-np.expm1(diff))
+    out = np.where(a < b, lo, hi)
+    return np.where(a == b, np.zeros_like(out), out)
+
+
 def _dsign(pol: Polarization, N):
     """D_i = +1 if mod1(i,n) <= 2 else -1."""
     s = np.arange(N) % pol.n
@@ -600,7 +618,7 @@ def elemental(pol: Polarization, tau_sum, dtau, F0, varpi, Zpp, Zmp, m: int, ndo
     active = (wct > eps(DT))[None, None, :]
     with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
         r = w * Zmp * (mj / (mi + mj)) * wj * (-np.expm1(-d * ((one / mi) + (one / mj))))
-        t_off = w * Zpp * (mj / (mi - mj)) * wj * expdiff_neg(d / mi, d / mj)
+        t_off = w * Zpp * (mj / (mi - mj)) * wj * expdiff_neg_mu(d, mi, mj)
         eye = np.eye(N, dtype=bool)[None]
         t_diag = np.exp(-d / mi) * (one + w * Zpp * (d / mi) * wj)          # i == j (w_j == w_i there)
         t_same = np.exp(-d / mj) * (w * Zpp * (d / mi) * wj)                 # mu_i == mu_j, i != j
@@ -625,7 +643,7 @@ def elemental(pol: Polarization, tau_sum, dtau, F0, varpi, Zpp, Zmp, m: int, ndo
     in_sun[i_start:i_end] = True
     with np.errstate(divide="ignore", invalid="ignore"):
         jp_sun = wct02 * w1 * ZF_p * (d1 / mi1) * np.exp(-d1 / mi1)
-        jp_off = wct02 * w1 * ZF_p * (mu_s / (mi1 - mu_s)) * expdiff_neg(d1 / mi1, d1 / mu_s)
+        jp_off = wct02 * w1 * ZF_p * (mu_s / (mi1 - mu_s)) * expdiff_neg_mu(d1, mi1, mu_s)
         jp = np.where(in_sun[None, :], jp_sun, jp_off)
         jm = wct02 * w1 * ZF_m * (mu_s / (mi1 + mu_s)) * (-np.expm1(-d1 * ((one / mi1) + (one / mu_s))))
     att = np.exp(-np.asarray(tau_sum, dtype=FT) / mu_s)[:, None]

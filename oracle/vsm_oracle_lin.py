@@ -121,7 +121,7 @@ def elemental_lin(pol, tau_sum, tau_sum_dot, dtau, F0, varpi, Zpp, Zmp, lin: Lay
         tZ_sm = e_j * w * (d / mi) * wj
         # general
         geo_t = (mj / (mi - mj)) * wj
-        ed = O.expdiff_neg(d / mi, d / mj)
+        ed = O.expdiff_neg_mu(d, mi, mj)
         t_of = w * Zpp_b * geo_t * ed
         tt_of = -w * Zpp_b * geo_t * (e_i / mi - e_j / mj)
         tZ_of = w * geo_t * ed
@@ -169,7 +169,7 @@ def elemental_lin(pol, tau_sum, tau_sum_dot, dtau, F0, varpi, Zpp, Zmp, lin: Lay
     att = np.exp(-np.asarray(tau_sum, dtype=FT) / mu_s)[:, None]
     with np.errstate(divide="ignore", invalid="ignore"):
         jp_sun = wct02 * w1 * ZFp * (d1 / mi1) * np.exp(-d1 / mi1)
-        jp_off = wct02 * w1 * ZFp * (mu_s / (mi1 - mu_s)) * O.expdiff_neg(d1 / mi1, d1 / mu_s)
+        jp_off = wct02 * w1 * ZFp * (mu_s / (mi1 - mu_s)) * O.expdiff_neg_mu(d1, mi1, mu_s)
         jp = np.where(in_sun[None, :], jp_sun, jp_off)
         jp_tau_sun = jp_sun * (one / d1 - one / mi1)
         jp_tau_off = -wct02 * w1 * ZFp * (mu_s / (mi1 - mu_s)) * (np.exp(-d1 / mi1) / mi1 - np.exp(-d1 / mu_s) / mu_s)
