@@ -927,6 +927,27 @@ int vsm_level_radiance_src_f32(int N, int n_stokes, int S, int nV, const int* ro
                                const float* const* bot_J0_m, float* uw, float* dw, float* dw_full, float* uw_full, float* work,
                                void* stream);
 
+/* Hemispheric quadratures of the level vectors at ONE boundary: the up, down and actinic fluxes of rt_run_fluxes
+ * (vsmartmom.jl_amd/core_rt_flux.py).  The system of vsm_level_radiance_src_* for the source pairs k = 0 .. n_src-1 (top_J0_p /
+ * bot_J0_m: HOST arrays of n_src device pointers, each [N,1,S]; A = top_R_pm, B = bot_R_mp / bot_stride as there), ONE pivoted
+ * elimination per point, dw_k = (I - A B)^-1 (a_k + A c_k), uw_k = c_k + B dw_k.  The vectors never leave the chip: with the nW
+ * weight rows q [nW][N / n_stokes] (a DEVICE array, one weight per stream, applied to the rows of Stokes I),
+ *   out[0][r][s] = sum_i q[r][i] sum_k uw_k[i n_stokes, s]      out[1][r][s] = sum_i q[r][i] sum_k dw_k[i n_stokes, s]
+ *   out[2][r][s] = dir_h[r] F0_I[s] exp(-tau_sum[s] / mu0)      (tau_sum, F0_I: [S], given together or both NULL: then 0)
+ * out [3][nW][S] is WRITTEN, not accumulated; dir_h is a HOST array of nW factors (read only with tau_sum / F0_I).  The additions
+ * of a quadrature have a fixed order (one wave per (r, direction), lanes over i, a butterfly), so a point's result depends on
+ * neither its place in the batch nor the run.  top_R_pm == NULL: no layer lies above the boundary (the TOA): no system is formed,
+ * dw = 0 and uw = sum_k c_k (top_J0_p, bot_R_mp are not read).  1 <= n_src <= VSM_LEVEL_MAX_SRC, 1 <= nW <= 4, N <= 128, S >= 0,
+ * the required pointers non-NULL; anything else is VSM_ERR_INVALID_ARG before any launch (larger N: one
+ * vsm_level_radiance_oplevel_* call per source with full vectors, then a batched product with q).  S = 0 launches nothing.
+ * Status words and pivot rule as in vsm_level_radiance_*. */
+int vsm_level_flux_f64(int N, int n_stokes, int S, const double* top_R_pm, int n_src, const double* const* top_J0_p,
+                       const double* bot_R_mp, long long bot_stride, const double* const* bot_J0_m, int nW, const double* q,
+                       const double* dir_h, double mu0, const double* tau_sum, const double* F0_I, double* out, void* stream);
+int vsm_level_flux_f32(int N, int n_stokes, int S, const float* top_R_pm, int n_src, const float* const* top_J0_p,
+                       const float* bot_R_mp, long long bot_stride, const float* const* bot_J0_m, int nW, const float* q,
+                       const float* dir_h, float mu0, const float* tau_sum, const float* F0_I, float* out, void* stream);
+
 /* The response of the column to a UNIT surface emission (the SIF Jacobian slots of the linearized run, vsmartmom.jl_amd/
  * core_rt_lin.py).  vsm_surface_sif_* adds the same value to j0- of the surface layer at every stream, so the radiance is
  * sum_c 2 sif[c, s] G_c(s), G_c = the response to the pattern e_c (1 on the rows of Stokes component c, 0 elsewhere).  For the K

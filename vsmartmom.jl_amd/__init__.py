@@ -10,7 +10,7 @@ Sub-modules
     Architectures   CPU()/GPU() dispatch surface (src/Architectures.jl)
     CoreRT          batched_mul / batch_inv_ / elemental_ / doubling_ / interaction_ / rt_kernel_ / rt_run /
                     rt_run_multisensor (core_rt_ms: radiances at any level of the column) / rt_run_ss (core_rt_ss: the
-                    single-scattering run)
+                    single-scattering run) / rt_run_fluxes (core_rt_flux: up, down and actinic fluxes at the layer boundaries)
     host_model      host-side producers of the hot path's inputs (streams, Z moments, layer mixing)
     CoreRTLin       linearized (Jacobian) pass: rt_run(model, lin_model, ...),
                     rt_run_multisensor(model, lin_model, ..., sensor_levels) (core_rt_ms_lin: Jacobians at any level),
@@ -32,6 +32,7 @@ from . import core_rt_raman as CoreRTRaman  # noqa: F401
 from . import core_rt_ms_raman  # noqa: F401
 from . import core_rt_ms_lin  # noqa: F401
 from . import core_rt_ss  # noqa: F401
+from . import core_rt_flux  # noqa: F401
 from . import standalone_ss as StandaloneSS  # noqa: F401
 from . import raman_inputs  # noqa: F401
 from . import io_yaml  # noqa: F401
@@ -46,5 +47,7 @@ CoreRT.rt_run_ss = core_rt_ss.rt_run_ss
 CoreRTRaman.rt_run_ss = core_rt_ss.rt_run_ss_rrs
 CoreRTLin.rt_run_ss = core_rt_ss.rt_run_ss_lin
 CoreRTLin.MultiSensorLinResult = core_rt_ms_lin.MultiSensorLinResult
+CoreRT.rt_run_fluxes = core_rt_flux.rt_run_fluxes
+CoreRT.FluxResult = core_rt_flux.FluxResult
 
 __version__ = "0.1.0"

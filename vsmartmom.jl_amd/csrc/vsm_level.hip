@@ -19,6 +19,8 @@
 // (the Planck slots of a linearized multi-sensor run with thermal emission), one body (level_lin_body, k_level_radiance_lin_src).
 // vsm_level_radiance_src_*: the same equation for up to VSM_LEVEL_MAX_SRC source pairs (a_k, c_k) on the same A, B (the solar and
 // the thermal slot), the pairs as right-hand sides of ONE solve, their level vectors summed (k_level_radiance_src, below).
+// vsm_level_flux_*: that system again, its level vectors reduced in LDS to hemispheric quadratures (the fluxes of rt_run_fluxes;
+// k_level_flux, below), and the TOA itself, which has no system.
 // vsm_surface_emission_response_*: the same system between the atmosphere and the surface layer for the unit emission patterns of
 // SurfaceSIF, kept per component (k_emission_response, below).
 #include "vsm_common.h"
@@ -240,6 +242,81 @@ __global__ void __launch_bounds__(LEVEL_NT) k_level_radiance_src(int N, int ns, 
   }
 }
 
+// Hemispheric quadratures of the level vectors (vsm_level_flux_*: the up, down and actinic fluxes of rt_run_fluxes), point
+// s = blockIdx.x.  k_level_radiance_src's system for the K source pairs, the same two halves:
+//   [M | d_1 .. d_K] = [I - A B | a_k + A c_k],  ONE Gauss-Jordan elimination,  dw_k = column / m_ii,  uw_k = c_k + B dw_k (into Q);
+// A == nullptr: no layer above the level (the TOA), no system: dw = 0, uw_k = c_k.  The vectors stay in LDS; for each weight row
+// r < nW (q: DEVICE [nW][N / ns], one weight per stream) and direction d, wave (2 r + d) % 4 takes
+//   out[d][r][s] = sum_i q[r][i] * sum_k v_k[i ns]      (v = uw for d = 0, dw for d = 1: the rows of Stokes I)
+// lanes over i (a lane adds its stream i = lane, then lane + 64), then a butterfly over the wave: the order of the additions
+// depends on N, K and nW alone.  out[2][r][s] = dir[r] F0_I[s] exp(-tau_sum[s] / mu0) with both arrays given, else 0.  Every
+// element of out [3][nW][S] is WRITTEN.  LDS: L [N][N + K], Q [K][N].
+template <typename T>
+struct level_flux_dir {
+  T h[4];
+  T mu0;
+};
+
+template <typename T>
+__global__ void __launch_bounds__(LEVEL_NT) k_level_flux(int N, int ns, int K, int nW, long long S, const T* __restrict__ A,
+                                                         level_srcs<T> src, const T* __restrict__ B, long long bstride,
+                                                         const T* __restrict__ q, level_flux_dir<T> dir,
+                                                         const T* __restrict__ tau_sum, const T* __restrict__ F0_I, T* out,
+                                                         int* status) {
+  extern __shared__ __align__(16) unsigned char lds_raw[];
+  const int LD = N + K;
+  T* L = reinterpret_cast<T*>(lds_raw);          // [M | d_1 .. d_K], row-major, leading dimension N + K
+  T* Q = L + (size_t)N * LD;                     // c_k, then uw_k
+  __shared__ int sh[2];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const long long s = blockIdx.x;
+  if (tid == 0) sh[1] = 0;
+#pragma unroll
+  for (int k = 0; k < VSM_LEVEL_MAX_SRC; ++k) {
+    if (k < K) {
+      for (int i = tid; i < N; i += LEVEL_NT) {
+        if (A) L[i * LD + N + k] = src.a[k][s * N + i];
+        Q[k * N + i] = src.c[k][s * N + i];
+      }
+    }
+  }
+  __syncthreads();
+  if (A) {   // (the same for the whole grid)
+    const T* Bs = B + s * bstride;
+    level_form_system<T>(N, N + K, LD, A + s * (long long)N * N, Bs, Q, L, sh, status);
+    level_eliminate<T>(N, N + K, LD, L, sh, status);
+    for (int e = tid; e < N * K; e += LEVEL_NT) {
+      const int i = e % N, k = e / N;
+      L[i * LD + N + k] = L[i * LD + N + k] / L[i * LD + i];
+    }
+    __syncthreads();
+    for (int e = tid; e < N * K; e += LEVEL_NT) {
+      const int i = e % N, k = e / N;
+      T y = Q[k * N + i];
+      for (int j = 0; j < N; ++j) y += Bs[(long long)j * N + i] * L[j * LD + N + k];
+      Q[k * N + i] = y;
+    }
+    __syncthreads();
+  }
+  const int Nq = N / ns;
+  for (int p = wave; p < 2 * nW; p += LEVEL_NT / 64) {
+    const int r = p >> 1, d = p & 1;
+    T acc = T(0);
+    if (d == 0 || A) {
+      for (int i = lane; i < Nq; i += 64) {
+        const int row = i * ns;
+        T v = d ? L[row * LD + N] : Q[row];
+        for (int k = 1; k < K; ++k) v += d ? L[row * LD + N + k] : Q[k * N + row];
+        acc += q[r * Nq + i] * v;
+      }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+    if (lane == 0) out[((long long)d * nW + r) * S + s] = acc;
+  }
+  if (tid < nW) out[((long long)2 * nW + tid) * S + s] = tau_sum ? dir.h[tid] * F0_I[s] * exp(-tau_sum[s] / dir.mu0) : T(0);
+}
+
 // The column-group streaming of the inelastic and the linearized kernel.  Thread (g, i) = (tid / N, tid % N) of the G = 256 / N
 // column groups takes row i of columns j = g, g + G, ... of a block [M | v] (column N = the vector, taken by the group next in
 // turn), so the workgroup reads G consecutive columns, G N contiguous elements, per step.  level_stream_pair adds [M1 | v1] x1 to
@@ -396,6 +473,47 @@ static int level_radiance_src_fused(int N, int ns, int S, int nV, const int* row
         return (int)VSM_OK;
       },
       [&](const T* uwf, const T* dwf) { return postprocess_vza<T>(N, ns, S, nV, row0_h, w_h, uwf, dwf, uw, dw, st); });
+}
+
+template <typename T>
+static int level_flux_fused(int N, int ns, int S, const T* A, int K, const T* const* a, const T* B, long long bstride,
+                            const T* const* c, int nW, const T* q, const T* dir_h, T mu0, const T* tau_sum, const T* F0_I, T* out,
+                            hipStream_t st) {
+  int* status = device_status();
+  if (!status) return VSM_ERR_HIP;
+  const size_t lds = level_src_lds<T>(N, K);
+  VSM_REQUIRE(lds <= 160 * 1024 - 256, "level_flux: N = %d with %d sources needs %zu bytes of LDS", N, K, lds);
+  const int rc = ensure_dyn_lds(reinterpret_cast<const void*>(k_level_flux<T>), lds, "hipFuncSetAttribute(k_level_flux)");
+  if (rc) return rc;
+  level_srcs<T> src = {};
+  for (int k = 0; k < K; ++k) {
+    src.a[k] = A ? a[k] : nullptr;
+    src.c[k] = c[k];
+  }
+  level_flux_dir<T> dir = {};
+  for (int r = 0; r < nW; ++r) dir.h[r] = tau_sum ? dir_h[r] : T(0);
+  dir.mu0 = mu0;
+  hipLaunchKernelGGL(k_level_flux<T>, dim3(S), dim3(LEVEL_NT), lds, st, N, ns, K, nW, (long long)S, A, src, B, bstride, q, dir, tau_sum,
+                     F0_I, out, status);
+  VSM_LAUNCH_CHECK("k_level_flux");
+  return VSM_OK;
+}
+
+template <typename T>
+static int level_flux_check(int N, int ns, int S, const T* A, int K, const T* const* a, const T* B, long long bstride,
+                            const T* const* c, int nW, const T* q, const T* dir_h, T mu0, const T* tau_sum, const T* F0_I,
+                            const T* out) {
+  VSM_REQUIRE(K >= 1 && K <= VSM_LEVEL_MAX_SRC, "level_flux: n_src = %d outside 1..%d", K, (int)VSM_LEVEL_MAX_SRC);
+  VSM_REQUIRE(nW >= 1 && nW <= 4, "level_flux: nW = %d outside 1..4", nW);
+  VSM_REQUIRE(N > 0 && ns >= 1 && ns <= 4 && N % ns == 0 && S >= 0, "level_flux: bad size (N %d, n_stokes %d, S %d)", N, ns, S);
+  VSM_REQUIRE(N <= LEVEL_FUSED_MAX_N, "level_flux: N = %d > %d, the limit of its kernel", N, LEVEL_FUSED_MAX_N);
+  VSM_REQUIRE(bstride == 0 || bstride == (long long)N * N, "level_flux: bot_stride must be 0 or N*N");
+  VSM_REQUIRE((tau_sum == nullptr) == (F0_I == nullptr), "level_flux: tau_sum and F0_I are both given or both NULL");
+  VSM_REQUIRE(!tau_sum || (dir_h && mu0 > T(0)), "level_flux: the direct term needs dir_h and mu0 > 0");
+  VSM_REQUIRE(S == 0 || (c && q && out), "level_flux: null bottom source list / weight rows / output");
+  VSM_REQUIRE(S == 0 || !A || (a && B), "level_flux: a top needs its sources and the bottom's R-+");
+  for (int k = 0; k < K && S > 0; ++k) VSM_REQUIRE(c[k] && (!A || a[k]), "level_flux: null source %d", k);
+  return VSM_OK;
 }
 
 template <typename T>
@@ -877,7 +995,20 @@ VSM_LEVEL_API(float, f32)
 VSM_LEVEL_SRC_API(double, f64)
 VSM_LEVEL_SRC_API(float, f32)
 
-#define VSM_LEVEL_IE_API(T, SFX)                                                                                               \
+#define VSM_LEVEL_FLUX_API(T, SFX)                                                                                              \
+  int vsm_level_flux_##SFX(int N, int n_stokes, int S, const T* top_R_pm, int n_src, const T* const* top_J0_p,                 \
+                           const T* bot_R_mp, long long bot_stride, const T* const* bot_J0_m, int nW, const T* q,              \
+                           const T* dir_h, T mu0, const T* tau_sum, const T* F0_I, T* out, void* stream) {                     \
+    int rc = level_flux_check<T>(N, n_stokes, S, top_R_pm, n_src, top_J0_p, bot_R_mp, bot_stride, bot_J0_m, nW, q, dir_h,      \
+                                 mu0, tau_sum, F0_I, out);                                                                     \
+    if (rc || S == 0) return rc;                                                                                               \
+    return level_flux_fused<T>(N, n_stokes, S, top_R_pm, n_src, top_J0_p, bot_R_mp, bot_stride, bot_J0_m, nW, q, dir_h, mu0,  \
+                               tau_sum, F0_I, out, as_stream(stream));                                                         \
+  }
+VSM_LEVEL_FLUX_API(double, f64)
+VSM_LEVEL_FLUX_API(float, f32)
+
+#define VSM_LEVEL_IE_API(T, SFX)                                                                                              \
   int vsm_level_radiance_ie_##SFX(int N, int n_stokes, int S, int K, const int* shift, int nV, const int* row0_h, const T* w_h,  \
                                   const T* top_R_pm, const T* bot_R_mp, long long bot_stride, const T* dw_full,               \
                                   const T* uw_full, const T* top_ieR_pm, const T* top_ieJ0_p, const T* bot_ieR_mp,            \
