@@ -13,7 +13,8 @@ torch = pytest.importorskip("torch")
 import flux_oracle as FO  # noqa: E402
 import ms_oracle as MS  # noqa: E402
 from oracle import vsm_oracle as O  # noqa: E402
-from test_gpu_multisensor import _err_per_level, _pair, _rand_level_inputs, _sub  # noqa: E402
+from level_cases import contractive  # noqa: E402
+from test_gpu_multisensor import _err_per_level, _pair, _sub  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -53,13 +54,13 @@ def _worst(res, ref, points=None):
 
 
 # ---- the kernel on random inputs -------------------------------------------------------------------------------------------------
-def _kernel_case(vsm, N, FT, S, shared, rng):
+def _kernel_case(vsm, N, FT, S, shared, rng, inputs=contractive):
     H = vsm.host_model
     pol = H.polarization_type("IQU" if N % 3 == 0 else "I")
     dt = torch.float64 if FT == np.float64 else torch.float32
     dev = torch.device("cuda", 0)
     rnd = lambda x: np.asarray(x, dtype=FT).astype(np.float64)           # (the reference sees the inputs the device sees)
-    A, _, B, _ = _rand_level_inputs(N, S, rng, shared)
+    A, _, B, _ = inputs(N, S, rng, shared)
     A, B = rnd(A), rnd(B)
     a, c = rnd(rng.random((4, S, N))), rnd(rng.random((4, S, N)))
     Nq = N // pol.n

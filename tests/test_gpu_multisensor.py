@@ -10,6 +10,7 @@ import pytest
 
 torch = pytest.importorskip("torch")
 import ms_oracle as MS  # noqa: E402
+from level_cases import contractive  # noqa: E402
 from oracle import vsm_oracle as O  # noqa: E402
 from oracle import vsm_oracle_brdf as OB  # noqa: E402
 from oracle import vsm_oracle_coxmunk as CM  # noqa: E402
@@ -164,13 +165,6 @@ def test_multisensor_float32(vsm, arch, pol, lt):
             assert e <= 2e-3, (levels[i], e)
 
 
-def _rand_level_inputs(N, S, rng, shared_bot):
-    A = rng.random((S, N, N)) * (0.6 / N)
-    B = rng.random((1 if shared_bot else S, N, N)) * (0.6 / N)
-    a, c = rng.random((S, N)), rng.random((S, N))
-    return A, a, B, c
-
-
 @pytest.mark.parametrize("N", [8, 60, 64, 96, 112, 128])
 @pytest.mark.parametrize("FT", [np.float64, np.float32], ids=["f64", "f32"])
 def test_level_kernel_fused_vs_oplevel(vsm, N, FT):
@@ -183,22 +177,26 @@ def test_level_kernel_fused_vs_oplevel_many_angles(vsm, FT):
     _fused_vs_oplevel(vsm, 60, FT, list(np.linspace(0.0, 80.0, 70)), list(np.linspace(0.0, 345.0, 70)))
 
 
-def _fused_vs_oplevel(vsm, N, FT, vza, vaz):
-    CR, MSd = vsm.CoreRT, vsm.core_rt_ms
+def _fused_and_oplevel_calls(vsm, N, FT, vza, vaz, inputs=contractive, S=7, ops=(False, True)):
+    """vsm_level_radiance_* and its operator-level twin on the same inputs, per-point then shared bottom: per bottom
+    (shared, (A, a, B, c), [fused, oplevel] each [uw, dw, uw_full, dw_full] in float64), and what the row checks need (ops: which of
+    the two to call, oplevel = False / True).
+    inputs(N, S, rng, shared_bot) -> (A, a, B, c) in math order (tests/level_cases.py)."""
+    MSd = vsm.core_rt_ms
     H = vsm.host_model
     pol = H.polarization_type("IQU" if N % 3 == 0 else "I")
-    S = 7
     rng = np.random.default_rng(N)
     qp = types.SimpleNamespace(qp_mu=np.linspace(1.0, 0.05, N // pol.n))     # (the rows of the viewing angles: all _vza_rows_weights reads)
     dev = torch.device("cuda", 0)
+    runs = []
     for shared in (False, True):
-        A, a, B, c = _rand_level_inputs(N, S, rng, shared)
+        A, a, B, c = inputs(N, S, rng, shared)
         lay = lambda X: torch.tensor(np.ascontiguousarray(X.transpose(0, 2, 1)), dtype=torch.float64 if FT == np.float64 else torch.float32,
                                      device=dev)
         vec = lambda x: torch.tensor(x, dtype=lay(A).dtype, device=dev)
         tA, tB, ta, tc = lay(A), lay(B), vec(a), vec(c)
         outs = []
-        for op in (False, True):
+        for op in ops:
             uw = torch.full((S, pol.n, len(vza)), 0.25, dtype=tA.dtype, device=dev)     # accumulated into
             dw = torch.full_like(uw, -0.5)
             uwf, dwf = torch.empty((S, N), dtype=tA.dtype, device=dev), torch.empty((S, N), dtype=tA.dtype, device=dev)
@@ -206,19 +204,31 @@ def _fused_vs_oplevel(vsm, N, FT, vza, vaz):
             torch.cuda.synchronize()
             outs.append([x.cpu().numpy().astype(np.float64) for x in (uw, dw, uwf, dwf)])
         vsm._lib.check_device_status("level kernel")
+        runs.append((shared, (A, a, B, c), outs))
+    return pol, qp, runs
+
+
+def _check_vza_rows(vsm, pol, qp, vza, vaz, out, tol):
+    """the VZA rows are the full vectors' rows, weighted (out: [uw, dw, uw_full, dw_full] of one call)"""
+    row0, w = vsm.CoreRT._vza_rows_weights(pol, vza, vaz, qp, 1, 1.0 / math.pi, torch.float64)
+    for v in range(len(vza)):
+        for k in range(pol.n):
+            wk = w[v + len(vza) * k]
+            np.testing.assert_allclose(out[0][:, k, v] - 0.25, wk * out[2][:, row0[v] + k], rtol=tol * 10, atol=tol)
+            np.testing.assert_allclose(out[1][:, k, v] + 0.5, wk * out[3][:, row0[v] + k], rtol=tol * 10, atol=tol)
+    return list(row0)
+
+
+def _fused_vs_oplevel(vsm, N, FT, vza, vaz):
+    pol, qp, runs = _fused_and_oplevel_calls(vsm, N, FT, vza, vaz)
+    for shared, (A, a, B, c), outs in runs:
         tol = 1e-12 if FT == np.float64 else 2e-5
         for xf, xo in zip(outs[0], outs[1]):
             assert np.max(np.abs(xf - xo)) <= tol * np.max(np.abs(xo)), (N, shared)
         uwr, dwr = MS.level_push_through(np.float64, A, a, B.astype(np.float64), c)
         assert np.max(np.abs(outs[0][2] - uwr)) <= 10 * tol * np.max(np.abs(uwr))
         assert np.max(np.abs(outs[0][3] - dwr)) <= 10 * tol * np.max(np.abs(dwr))
-        # the VZA rows are the full vectors' rows, weighted
-        row0, w = CR._vza_rows_weights(pol, vza, vaz, qp, 1, 1.0 / math.pi, torch.float64)
-        for v in range(len(vza)):
-            for k in range(pol.n):
-                wk = w[v + len(vza) * k]
-                np.testing.assert_allclose(outs[0][0][:, k, v] - 0.25, wk * outs[0][2][:, row0[v] + k], rtol=tol * 10, atol=tol)
-                np.testing.assert_allclose(outs[0][1][:, k, v] + 0.5, wk * outs[0][3][:, row0[v] + k], rtol=tol * 10, atol=tol)
+        _check_vza_rows(vsm, pol, qp, vza, vaz, outs[0], tol)
 
 
 def test_conservative_column_flux_on_device(vsm, arch):

@@ -172,12 +172,18 @@ def test_multisensor_lin_fp32(vsm, arch, pol, lt):
 
 
 # ---- the kernel alone --------------------------------------------------------------------------------------------------------
-def _kernel_case(vsm, N, P, P_top, shared, S=3, FT=np.float64, ns=3, seed=0, nV=2):
-    rng = np.random.default_rng(seed + N + 7 * P)
-    ns = ns if N % ns == 0 else 1
+def _kernel_inputs(N, S, rng, shared):
+    """The signature of level_cases.contractive (which scales by 0.6 / N and draws a before B)."""
     A = 0.9 * rng.uniform(0, 1, (S, N, N)) / N
     B = 0.9 * rng.uniform(0, 1, (1 if shared else S, N, N)) / N
     a, c = rng.uniform(0, 1, (S, N)), rng.uniform(0, 1, (S, N))
+    return A, a, B, c
+
+
+def _kernel_case(vsm, N, P, P_top, shared, S=3, FT=np.float64, ns=3, seed=0, nV=2, inputs=_kernel_inputs):
+    rng = np.random.default_rng(seed + N + 7 * P)
+    ns = ns if N % ns == 0 else 1
+    A, a, B, c = inputs(N, S, rng, shared)
     Ad = rng.normal(0, 1, (P_top, S, N, N)) / N
     ad = rng.normal(0, 1, (P_top, S, N))
     Bd = rng.normal(0, 1, (P,) + B.shape) / N

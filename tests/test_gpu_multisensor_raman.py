@@ -167,14 +167,22 @@ def test_level_ie_kernel_vs_numpy_many_angles(vsm, FT):
     _level_ie_vs_numpy(vsm, FT, 21, 9, "per_point", 70)
 
 
-def _level_ie_vs_numpy(vsm, FT, N, K, bottom, nV):
-    S = 9 if N <= 33 else 5
+def _ie_inputs(N, S, rng, shared):
+    """(A, dw, B, uw): the operators and the elastic level vectors of the donors; the signature of level_cases.contractive."""
+    A = 0.5 * rng.random((S, N, N)) / N
+    B = 0.5 * rng.random((1 if shared else S, N, N)) / N
+    dwf, uwf = rng.random((S, N)), rng.random((S, N))
+    return A, dwf, B, uwf
+
+
+def _level_ie_vs_numpy(vsm, FT, N, K, bottom, nV, inputs=_ie_inputs, S=None, shifts=None):
+    """Returns the four relative errors (dw_ie, uw_ie in full, then their viewing rows) it has asserted."""
+    S = (9 if N <= 33 else 5) if S is None else S
     rng = np.random.default_rng(N * 1000 + K)
     ns = 3 if N % 3 == 0 else 1
-    shifts = {1: [2], 9: [-4, -2, -1, 0, 1, 2, 4, S + 3, -(S + 7)]}.get(K, list(range(-35, 35)))
-    A = 0.5 * rng.random((S, N, N)) / N
-    B = 0.5 * rng.random((1 if bottom == "shared" else S, N, N)) / N
-    dwf, uwf = rng.random((S, N)), rng.random((S, N))
+    if shifts is None:
+        shifts = {1: [2], 9: [-4, -2, -1, 0, 1, 2, 4, S + 3, -(S + 7)]}.get(K, list(range(-35, 35)))
+    A, dwf, B, uwf = inputs(N, S, rng, bottom == "shared")
     Aie, aie = 0.05 * rng.random((K, S, N, N)) / N, 0.05 * rng.random((K, S, N))
     Bie, cie = (None, None) if bottom == "null" else (0.05 * rng.random((K, S, N, N)) / N, 0.05 * rng.random((K, S, N)))
     cast = lambda x: None if x is None else x.astype(FT).astype(np.float64)
@@ -188,14 +196,18 @@ def _level_ie_vs_numpy(vsm, FT, N, K, bottom, nV):
     uwief = torch.full((S, N), float("nan"), dtype=dt, device="cuda")
     _level_ie_call(vsm, FT, N, ns, S, K, shifts, A, B, dwf, uwf, Aie, aie, Bie, cie, row0, wv, uwie, dwie, dwief, uwief)
     tol = 1e-10 if FT == np.float64 else 5e-4
+    errs = []
     for got, ref in ((dwief, dwie_r), (uwief, uwie_r)):
         g = got.cpu().numpy().astype(np.float64)
         assert np.all(np.isfinite(g))
+        errs.append(np.max(np.abs(g - ref)) / np.max(np.abs(ref)))
         assert np.max(np.abs(g - ref)) <= tol * np.max(np.abs(ref))
     for got, ref in ((uwie, uwie_r), (dwie, dwie_r)):
         rows = np.stack([np.stack([wv[v + nV * k] * ref[:, row0[v] + k] for v in range(nV)], axis=-1) for k in range(ns)], axis=1)
         g = got.cpu().numpy().astype(np.float64)
+        errs.append(np.max(np.abs(g - rows)) / np.max(np.abs(rows)))
         assert np.max(np.abs(g - rows)) <= tol * np.max(np.abs(rows))
+    return errs
 
 
 def test_outputs_finite_with_poisoned_buffers(vsm, arch, monkeypatch):

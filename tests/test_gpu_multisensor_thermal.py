@@ -16,7 +16,8 @@ torch = pytest.importorskip("torch")
 import ms_oracle as MS  # noqa: E402
 import ms_thermal_oracle as MT  # noqa: E402
 from oracle import vsm_oracle as O  # noqa: E402
-from test_gpu_multisensor import _err_per_level, _pair, _rand_level_inputs, _sub  # noqa: E402
+from level_cases import contractive  # noqa: E402
+from test_gpu_multisensor import _err_per_level, _pair, _sub  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -129,11 +130,11 @@ def test_multisensor_thermal_float32(vsm, arch, pol, lt):
 
 
 # ---- the kernel on random inputs -------------------------------------------------------------------------------------------------
-def _kernel_setup(vsm, N, FT, nV):
+def _kernel_setup(vsm, N, FT, nV, vza_max=80.0):
     H = vsm.host_model
     pol = H.polarization_type("IQU" if N % 3 == 0 else "I")
     qp = types.SimpleNamespace(qp_mu=np.linspace(1.0, 0.05, N // pol.n))      # (the rows of the viewing angles)
-    vza, vaz = list(np.linspace(0.0, 80.0, nV)), list(np.linspace(0.0, 345.0, nV))
+    vza, vaz = list(np.linspace(0.0, vza_max, nV)), list(np.linspace(0.0, 345.0, nV))
     dt = torch.float64 if FT == np.float64 else torch.float32
     dev = torch.device("cuda", 0)
     lay = lambda X: torch.tensor(np.ascontiguousarray(X.transpose(0, 2, 1)), dtype=dt, device=dev)
@@ -147,6 +148,30 @@ def _outputs(S, N, pol, nV, dt, dev):
     return uw, dw, torch.empty((S, N), dtype=dt, device=dev), torch.empty((S, N), dtype=dt, device=dev)
 
 
+def _src_inputs(N, S, rng, shared, inputs=contractive, scales=(1.0, 1.0), FT=None):
+    """(A, [a_k], B, [c_k]): the pair of inputs(N, S, rng, shared) times scales[0] and one further random pair per further scale.
+    FT: the sources rounded to FT (a reference computed from them then sees what the device sees)."""
+    A, a, B, c = inputs(N, S, rng, shared)
+    tops, bots = [a * scales[0]], [c * scales[0]]
+    for sc in scales[1:]:
+        a2, c2 = rng.random((S, N)), rng.random((S, N))
+        tops.append(a2 * sc)
+        bots.append(c2 * sc)
+    if FT is not None:
+        tops, bots = ([np.asarray(x, dtype=FT).astype(np.float64) for x in xs] for xs in (tops, bots))
+    return A, tops, B, bots
+
+
+def _level_src_call(vsm, setup, S, N, nV, tA, tops, tB, bots, oplevel=False):
+    """One vsm_level_radiance_src_* call (or its operator-level twin) on device operands: [uw, dw, uw_full, dw_full] on the host."""
+    pol, qp, vza, vaz, dt, dev, lay, vec = setup
+    out = _outputs(S, N, pol, nV, dt, dev)
+    vsm.core_rt_ms.level_radiance_src_(pol, qp, vza, vaz, 1, 1.0 / math.pi, tA, tops, tB, bots, out[0], out[1], out[3], out[2],
+                                       oplevel=oplevel)
+    torch.cuda.synchronize()
+    return [x.cpu().numpy().astype(np.float64) for x in out]
+
+
 @pytest.mark.parametrize("N", [3, 16, 61, 128])
 @pytest.mark.parametrize("FT", [np.float64, np.float32], ids=["f64", "f32"])
 def test_level_src_kernel(vsm, N, FT):
@@ -158,10 +183,10 @@ def test_level_src_kernel(vsm, N, FT):
     tol = 1e-12 if FT == np.float64 else 2e-5
     host = lambda xs: [x.cpu().numpy().astype(np.float64) for x in xs]
     for nV in (3, 70):
-        pol, qp, vza, vaz, dt, dev, lay, vec = _kernel_setup(vsm, N, FT, nV)
+        setup = _kernel_setup(vsm, N, FT, nV)
+        pol, qp, vza, vaz, dt, dev, lay, vec = setup
         for shared in (False, True):
-            A, a, B, c = _rand_level_inputs(N, S, rng, shared)
-            a2, c2 = rng.random((S, N)), rng.random((S, N))
+            A, (a, a2), B, (c, c2) = _src_inputs(N, S, rng, shared)
             tA, tB, ta, tc, ta2, tc2 = lay(A), lay(B), vec(a), vec(c), vec(a2), vec(c2)
             w = 1.0 / math.pi
             # n_src = 1 against the one-source kernel
@@ -178,20 +203,15 @@ def test_level_src_kernel(vsm, N, FT):
             torch.cuda.synchronize()
             assert np.array_equal(host(src1n[:2])[0], host(one[:2])[0]) and np.array_equal(host(src1n[:2])[1], host(one[:2])[1])
             # n_src = 2 against two accumulated operator-level calls
-            src2 = _outputs(S, N, pol, nV, dt, dev)
-            MSd.level_radiance_src_(pol, qp, vza, vaz, 1, w, tA, [ta, ta2], tB, [tc, tc2], src2[0], src2[1], src2[3], src2[2])
-            op2 = _outputs(S, N, pol, nV, dt, dev)
-            MSd.level_radiance_src_(pol, qp, vza, vaz, 1, w, tA, [ta, ta2], tB, [tc, tc2], op2[0], op2[1], op2[3], op2[2],
-                                    oplevel=True)
-            torch.cuda.synchronize()
+            src2 = _level_src_call(vsm, setup, S, N, nV, tA, [ta, ta2], tB, [tc, tc2])
+            op2 = _level_src_call(vsm, setup, S, N, nV, tA, [ta, ta2], tB, [tc, tc2], oplevel=True)
             vsm._lib.check_device_status("level src kernel")
-            for xf, xo in zip(host(src2), host(op2)):
+            for xf, xo in zip(src2, op2):
                 assert np.max(np.abs(xf - xo)) <= tol * np.max(np.abs(xo)), (N, nV, shared)
             # ... and the level vectors against numpy: the equation is linear in (a, c)
             uwr, dwr = MS.level_push_through(np.float64, A, a + a2, B.astype(np.float64), c + c2)
-            got = host(src2)
-            assert np.max(np.abs(got[2] - uwr)) <= 10 * tol * np.max(np.abs(uwr))
-            assert np.max(np.abs(got[3] - dwr)) <= 10 * tol * np.max(np.abs(dwr))
+            assert np.max(np.abs(src2[2] - uwr)) <= 10 * tol * np.max(np.abs(uwr))
+            assert np.max(np.abs(src2[3] - dwr)) <= 10 * tol * np.max(np.abs(dwr))
 
 
 @pytest.mark.parametrize("FT", [np.float64, np.float32], ids=["f64", "f32"])
@@ -202,7 +222,7 @@ def test_level_src_kernel_refuses_bad_source_counts(vsm, FT, n_src):
     assert MSd.LEVEL_MAX_SRC == 4
     N, S, nV = 16, 3, 3
     pol, qp, vza, vaz, dt, dev, lay, vec = _kernel_setup(vsm, N, FT, nV)
-    A, a, B, c = _rand_level_inputs(N, S, np.random.default_rng(0), False)
+    A, a, B, c = contractive(N, S, np.random.default_rng(0), False)
     tA, tB, ta, tc = lay(A), lay(B), vec(a), vec(c)
     uw, dw, _, _ = _outputs(S, N, pol, nV, dt, dev)
     row0, w = CR._vza_rows_weights(pol, vza, vaz, qp, 1, 1.0, dt)

@@ -25,7 +25,7 @@ import ms_thermal_lin_oracle as MTL  # noqa: E402
 import thermal_lin_oracle as TL  # noqa: E402
 from oracle import vsm_oracle as O  # noqa: E402
 from oracle import vsm_oracle_lin as OL  # noqa: E402
-from test_gpu_multisensor_lin import _err, _idx, _pair, _sub  # noqa: E402
+from test_gpu_multisensor_lin import _err, _idx, _kernel_inputs, _pair, _sub  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -381,12 +381,11 @@ def test_refusals(vsm, arch):
 
 
 # ---- the kernel alone --------------------------------------------------------------------------------------------------------
-def _kernel_case(vsm, N, P, P_top, P_src, shared, S=3, FT=np.float64, ns=3, nV=2, entry="vsm_level_radiance_lin_src"):
+def _kernel_case(vsm, N, P, P_top, P_src, shared, S=3, FT=np.float64, ns=3, nV=2, entry="vsm_level_radiance_lin_src",
+                 inputs=_kernel_inputs):
     rng = np.random.default_rng(N + 7 * P + 13 * P_src)
     ns = ns if N % ns == 0 else 1
-    A = 0.9 * rng.uniform(0, 1, (S, N, N)) / N
-    B = 0.9 * rng.uniform(0, 1, (1 if shared else S, N, N)) / N
-    a, c = rng.uniform(0, 1, (S, N)), rng.uniform(0, 1, (S, N))
+    A, a, B, c = inputs(N, S, rng, shared)
     Ad, ad = rng.normal(0, 1, (P_top, S, N, N)) / N, rng.normal(0, 1, (P_top, S, N))
     Bd, cd = rng.normal(0, 1, (P,) + B.shape) / N, rng.normal(0, 1, (P, S, N))
     ak, ck = rng.normal(0, 1, (P_src, S, N)), rng.normal(0, 1, (P_src, S, N))

@@ -134,16 +134,10 @@ def _response_inputs(N, S_, rng, shared):
     return A, B, T
 
 
-@pytest.mark.parametrize("K", [1, 3])
-@pytest.mark.parametrize("N", [3, 16, 61, 128])
-@pytest.mark.parametrize("FT", [np.float64, np.float32], ids=["f64", "f32"])
-def test_emission_response_kernel(vsm, N, FT, K):
-    """vsm_surface_emission_response_*: the fused kernel against the operator-level composition (one vsm_level_radiance_oplevel_*
-    call per component and a batched row product) and against numpy; shared and per-point B, 3 and 70 viewing angles."""
+def _emission_response_case(vsm, N, FT, K, nV, shared, rng, inputs=_response_inputs, S_=5, vza_max=80.0, oplevel=True):
+    """One vsm_surface_emission_response_* call, its operator-level composition (oplevel) and numpy on the operators of
+    inputs(N, S_, rng, shared) -> (A, B, T): a list of (name, k, fused, composition | None, numpy) over up / dn and the components."""
     MSd, H = vsm.core_rt_ms, vsm.host_model
-    S_ = 5
-    rng = np.random.default_rng(N + K)
-    tol = 1e-12 if FT == np.float64 else 2e-5
     pol = _kernel_pol(H, N)
     n = pol.n
     comps = [n - 1] if K == 1 else [c % n for c in (0, 1, 3)]
@@ -152,33 +146,48 @@ def test_emission_response_kernel(vsm, N, FT, K):
     lay = lambda X: torch.tensor(np.ascontiguousarray(X.transpose(0, 2, 1)), dtype=dt, device=dev)
     qp = types.SimpleNamespace(qp_mu=np.linspace(1.0, 0.05, N // n))      # (the rows of the viewing angles)
     w = 0.5 / math.pi
+    vza, vaz = list(np.linspace(0.0, vza_max, nV)), list(np.linspace(0.0, 345.0, nV))
+    row0, wts = vsm.CoreRT._vza_rows_weights(pol, vza, vaz, qp, 0, w, dt)
+    rows = np.array([[row0[v] + c for v in range(nV)] for c in range(n)])
+    wt = np.array([[wts[v + nV * c] for v in range(nV)] for c in range(n)], dtype=np.float64)
+    A, B, T = inputs(N, S_, rng, shared)
+    tA, tB, tT = lay(A), lay(B), lay(T)
+    fused = [torch.full((K, S_, n, nV), 0.25, dtype=dt, device=dev) for _ in range(2)]
+    opl = [torch.full((K, S_, n, nV), -0.5, dtype=dt, device=dev) for _ in range(2)]
+    MSd.surface_emission_response_(pol, qp, vza, vaz, w, tA, tT, tB, comps, *fused)
+    if oplevel:
+        MSd.surface_emission_response_(pol, qp, vza, vaz, w, tA, tT, tB, comps, *opl, oplevel=True)
+    torch.cuda.synchronize()
+    vsm._lib.check_device_status("emission response kernel")
+    Bf = np.broadcast_to(B, A.shape)
+    M = np.eye(N)[None] - Bf @ A
+    out = []
+    for k, c in enumerate(comps):
+        e = np.zeros((S_, N))
+        e[:, c::n] = 1
+        y = np.linalg.solve(M, e[..., None])[..., 0]
+        up = wt[None] * np.einsum("sij,sj->si", T, y)[:, rows]
+        dn = wt[None] * np.einsum("sij,sj->si", A, y)[:, rows]
+        for name, f, o, r in (("up", fused[0], opl[0], up), ("dn", fused[1], opl[1], dn)):
+            xf, xo = f[k].cpu().numpy().astype(np.float64), o[k].cpu().numpy().astype(np.float64)
+            out.append((name, k, xf, xo if oplevel else None, r))
+    return out
+
+
+@pytest.mark.parametrize("K", [1, 3])
+@pytest.mark.parametrize("N", [3, 16, 61, 128])
+@pytest.mark.parametrize("FT", [np.float64, np.float32], ids=["f64", "f32"])
+def test_emission_response_kernel(vsm, N, FT, K):
+    """vsm_surface_emission_response_*: the fused kernel against the operator-level composition (one vsm_level_radiance_oplevel_*
+    call per component and a batched row product) and against numpy; shared and per-point B, 3 and 70 viewing angles."""
+    rng = np.random.default_rng(N + K)
+    tol = 1e-12 if FT == np.float64 else 2e-5
     for nV in (3, 70):
-        vza, vaz = list(np.linspace(0.0, 80.0, nV)), list(np.linspace(0.0, 345.0, nV))
-        row0, wts = vsm.CoreRT._vza_rows_weights(pol, vza, vaz, qp, 0, w, dt)
-        rows = np.array([[row0[v] + c for v in range(nV)] for c in range(n)])
-        wt = np.array([[wts[v + nV * c] for v in range(nV)] for c in range(n)], dtype=np.float64)
         for shared in (False, True):
-            A, B, T = _response_inputs(N, S_, rng, shared)
-            tA, tB, tT = lay(A), lay(B), lay(T)
-            fused = [torch.full((K, S_, n, nV), 0.25, dtype=dt, device=dev) for _ in range(2)]
-            opl = [torch.full((K, S_, n, nV), -0.5, dtype=dt, device=dev) for _ in range(2)]
-            MSd.surface_emission_response_(pol, qp, vza, vaz, w, tA, tT, tB, comps, *fused)
-            MSd.surface_emission_response_(pol, qp, vza, vaz, w, tA, tT, tB, comps, *opl, oplevel=True)
-            torch.cuda.synchronize()
-            vsm._lib.check_device_status("emission response kernel")
-            Bf = np.broadcast_to(B, A.shape)
-            M = np.eye(N)[None] - Bf @ A
-            for k, c in enumerate(comps):
-                e = np.zeros((S_, N))
-                e[:, c::n] = 1
-                y = np.linalg.solve(M, e[..., None])[..., 0]
-                up = wt[None] * np.einsum("sij,sj->si", T, y)[:, rows]
-                dn = wt[None] * np.einsum("sij,sj->si", A, y)[:, rows]
-                for name, f, o, r in (("up", fused[0], opl[0], up), ("dn", fused[1], opl[1], dn)):
-                    xf, xo = f[k].cpu().numpy().astype(np.float64), o[k].cpu().numpy().astype(np.float64)
-                    assert np.max(np.abs(r)) > 0
-                    assert np.max(np.abs(xf - xo)) <= tol * np.max(np.abs(xo)), (name, N, nV, shared, k)
-                    assert np.max(np.abs(xf - r)) <= 10 * tol * np.max(np.abs(r)), (name, N, nV, shared, k)
+            for name, k, xf, xo, r in _emission_response_case(vsm, N, FT, K, nV, shared, rng):
+                assert np.max(np.abs(r)) > 0
+                assert np.max(np.abs(xf - xo)) <= tol * np.max(np.abs(xo)), (name, N, nV, shared, k)
+                assert np.max(np.abs(xf - r)) <= 10 * tol * np.max(np.abs(r)), (name, N, nV, shared, k)
 
 
 @pytest.mark.parametrize("FT", [np.float64, np.float32], ids=["f64", "f32"])
