@@ -1041,6 +1041,39 @@ int vsm_level_radiance_lin_src_f32(int N, int n_stokes, int S, int P, int P_top,
                                    const float* src_top_J0_p, const float* src_bot_J0_m, float* uw_lin, float* dw_lin,
                                    float* dw_lin_full, float* uw_lin_full, void* stream);
 
+/* Hemispheric quadratures of the DERIVATIVE level vectors at ONE boundary: the flux Jacobians of CoreRTLin.rt_run_fluxes
+ * (vsmartmom.jl_amd/core_rt_flux_lin.py).  The operators, vectors and slots of vsm_level_radiance_lin_src_* (P parameter slots, of
+ * which the first P_top have a top derivative, then P_src source-only slots; the same chunks as right-hand sides of ONE pivoted
+ * elimination each, the same LDS bound) without its viewing-angle arguments, and the weight rows and direct-beam arguments of
+ * vsm_level_flux_*: q [nW][N / n_stokes] (DEVICE), dir_h [nW] (HOST), mu0, tau_sum / F0_I [S] (given together or both NULL), and
+ * tau_sum_dot [p_layer][S] (DEVICE; the parameter axis slowest), the derivative of tau_sum with respect to the first p_layer
+ * slots (0 <= p_layer <= P).  The derivative vectors never leave the chip.  out [3][nW][1 + P + P_src][S] is WRITTEN, not
+ * accumulated; for weight row r and point s
+ *   out[0][r][0]     = sum_i q[r][i] uw[i n_stokes]        out[1][r][0]     = sum_i q[r][i] dw[i n_stokes]   (uw_full / dw_full)
+ *   out[0][r][1 + p] = sum_i q[r][i] uw'_p[i n_stokes]     out[1][r][1 + p] = sum_i q[r][i] dw'_p[i n_stokes]
+ *   out[2][r][0]     = dir_h[r] F0_I exp(-tau_sum / mu0)   out[2][r][1 + p] = -out[2][r][0] tau_sum_dot[p] / mu0   (p < p_layer)
+ * and out[2][r][1 + p] = 0 for every other slot; tau_sum == NULL: all of out[2] is 0.  The additions of a quadrature have the
+ * fixed order of vsm_level_flux_* (one wave per (slot, r, direction), lanes over i, a butterfly): a point's bits depend on
+ * neither its place in the batch nor the batch size.  top_R_pm == NULL: no layer lies above the boundary (the TOA), no system is
+ * formed: dw = 0 and every dw' = 0, uw = uw_full (the column's J0-), uw'_p = bot_J0_m_lin[p], or src_bot_J0_m[k] for a
+ * source-only slot; bot_R_mp, dw_full, the operator derivatives and src_top_J0_p are not read.  N <= 128, P >= 0, P_src >= 0,
+ * 1 <= P + P_src <= 64, 1 <= nW <= 4, strides as in vsm_level_radiance_lin_*, the required pointers non-NULL; anything else is
+ * VSM_ERR_INVALID_ARG before any launch.  S = 0 launches nothing.  Status words and pivot rule as in vsm_level_radiance_*. */
+int vsm_level_flux_lin_f64(int N, int n_stokes, int S, int P, int P_top, int P_src, const double* top_R_pm, const double* bot_R_mp,
+                           long long bot_stride, const double* dw_full, const double* uw_full, const double* top_R_pm_lin,
+                           long long top_lin_pstride, const double* top_J0_p_lin, const double* bot_R_mp_lin,
+                           long long bot_lin_stride, long long bot_lin_pstride, const double* bot_J0_m_lin,
+                           const double* src_top_J0_p, const double* src_bot_J0_m, int nW, const double* q, const double* dir_h,
+                           double mu0, const double* tau_sum, const double* F0_I, const double* tau_sum_dot, int p_layer,
+                           double* out, void* stream);
+int vsm_level_flux_lin_f32(int N, int n_stokes, int S, int P, int P_top, int P_src, const float* top_R_pm, const float* bot_R_mp,
+                           long long bot_stride, const float* dw_full, const float* uw_full, const float* top_R_pm_lin,
+                           long long top_lin_pstride, const float* top_J0_p_lin, const float* bot_R_mp_lin,
+                           long long bot_lin_stride, long long bot_lin_pstride, const float* bot_J0_m_lin,
+                           const float* src_top_J0_p, const float* src_bot_J0_m, int nW, const float* q, const float* dir_h,
+                           float mu0, const float* tau_sum, const float* F0_I, const float* tau_sum_dot, int p_layer, float* out,
+                           void* stream);
+
 /* ---- single-scattering runs: rt_run_ss (src/CoreRT/rt_run.jl:574-755) -----------------------------------------------------
  * One Fourier moment of the single-scattering column walk, all layers and the surface in ONE launch: per layer the exact
  * finite-tau sources of elemental! with ndoubl = 0 and dtau = the layer's tau (get_elem_rt_SFI!, CoreKernel/elemental.jl:348-392;

@@ -14,7 +14,8 @@ Sub-modules
     host_model      host-side producers of the hot path's inputs (streams, Z moments, layer mixing)
     CoreRTLin       linearized (Jacobian) pass: rt_run(model, lin_model, ...),
                     rt_run_multisensor(model, lin_model, ..., sensor_levels) (core_rt_ms_lin: Jacobians at any level),
-                    rt_run_ss(model, lin_model, ...) (core_rt_ss: analytic single-scattering Jacobians)
+                    rt_run_ss(model, lin_model, ...) (core_rt_ss: analytic single-scattering Jacobians),
+                    rt_run_fluxes(model, lin_model, ...) (core_rt_flux_lin: flux and heating Jacobians at the layer boundaries)
     CoreRTRaman     rotational-Raman pass: rt_run(RS_type::RRS, model, iBand),
                     rt_run_multisensor(RS_type, model, sensor_levels) (core_rt_ms_raman),
                     rt_run_ss(RS_type, model, iBand) (core_rt_ss: the single-scatter inelastic correction)
@@ -33,6 +34,7 @@ from . import core_rt_ms_raman  # noqa: F401
 from . import core_rt_ms_lin  # noqa: F401
 from . import core_rt_ss  # noqa: F401
 from . import core_rt_flux  # noqa: F401
+from . import core_rt_flux_lin  # noqa: F401
 from . import standalone_ss as StandaloneSS  # noqa: F401
 from . import raman_inputs  # noqa: F401
 from . import io_yaml  # noqa: F401
@@ -49,5 +51,7 @@ CoreRTLin.rt_run_ss = core_rt_ss.rt_run_ss_lin
 CoreRTLin.MultiSensorLinResult = core_rt_ms_lin.MultiSensorLinResult
 CoreRT.rt_run_fluxes = core_rt_flux.rt_run_fluxes
 CoreRT.FluxResult = core_rt_flux.FluxResult
+CoreRTLin.rt_run_fluxes = core_rt_flux_lin.rt_run_fluxes
+CoreRTLin.FluxLinResult = core_rt_flux_lin.FluxLinResult
 
 __version__ = "0.1.0"

@@ -212,7 +212,7 @@ def rt_run_fluxes(model: H.RTModel, levels=None, thermal: bool = False, max_poin
     convergence of layer l and surface_absorbed [nSpec] = net_down[Nz]; otherwise both are None.
 
     Only m = 0 is walked, whatever model.m_max is.  Only the I row is reported: no Q / U / V fluxes; no Cox-Munk single-scattering
-    correction, as the multi-sensor run has none; no Jacobians.
+    correction, as the multi-sensor run has none.  Jacobians of every field: CoreRTLin.rt_run_fluxes (core_rt_flux_lin.py).
 
     Sources as the elastic rt_run_multisensor takes them: SolarBeam and SurfaceSIF always, ThermalEmission under thermal=True
     (VSMError without it), any other source VSMError; every result is the sum over the sources.  Without a SolarBeam F0 = 0 and

@@ -98,9 +98,27 @@ class MultiSensorLinResult(MS.MultiSensorResult):
     FIELDS = ("uw", "dw", "uw_dot", "dw_dot")
 
 
-def _run_scene(sc: CL.SceneLin, plan: MS.LevelPlan, streams: bool):
+class LevelSink:
+    """What a run other than the multi-sensor one does at each level of the walk of _run_scene / _run_thermal, in place of their
+    level calls (core_rt_flux_lin.py: the flux Jacobians).  With a sink no VZA output is allocated and no level call is issued
+    here; the walk itself -- tops, segments, bottoms -- is the same.  top = (R+-, J0+, R+-', J0+' [:pl]) of the composite above
+    the level, bot = (R-+, J0-, R-+', J0-') of the one below, src = the Planck source stacks (a_k, c_k) ((K, S, N) each) or None;
+    thermal: the call comes from the `:thermal` slot (on the scene's own N, after the solar moments)."""
+
+    def level(self, sc, mom, l, top, bot, src, thermal):
+        raise NotImplementedError
+
+    def level0(self, sc, mom, J0_m, J0_m_lin, src_J0_m, thermal):
+        """Level 0, the TOA: J0- of the whole column with the surface, its derivative stack (P, S, N) and the Planck slots'
+        J0- ((K, S, N) or None)."""
+        raise NotImplementedError
+
+
+def _run_scene(sc: CL.SceneLin, plan: MS.LevelPlan, streams: bool, sink: Optional[LevelSink] = None):
     """The linearized multi-sensor algorithm on one SceneLin.  Returns ({level: [uw, dw, uw_dot, dw_dot]} of (S, nStokes, nVZA) /
-    (P, S, nStokes, nVZA) device tensors, {m: {level: (uw, dw, uw_dot, dw_dot) (S, N) / (P, S, N)}} or None, the Fourier weights)."""
+    (P, S, nStokes, nVZA) device tensors, {m: {level: (uw, dw, uw_dot, dw_dot) (S, N) / (P, S, N)}} or None, the Fourier weights).
+    sink: see LevelSink (then the first of these holds level 0 alone and streams is not taken); where the scene runs m = 0 on its
+    Stokes_IQ sub-scene the sink sees that sub-scene's levels, and the thermal slot's on this scene."""
     model, fwd, FT, dt = sc.model, sc.fwd, sc.FT, sc.dt
     pol, qp = sc.pol, sc.qp
     N, S, P, pl = sc.N, sc.S, sc.P, sc.pl
@@ -112,18 +130,21 @@ def _run_scene(sc: CL.SceneLin, plan: MS.LevelPlan, streams: bool):
     z = lambda *sh: torch.zeros(sh, dtype=dt, device=dev)
     thermal = sc.fwd.thermal_B is not None or sc.nPlanck > 0
     Pa = P + sc.nPlanck      # (the Planck slots follow the parameter slots; the solar level calls fill the first P)
-    out = {l: [z(S, pol.n, nV), z(S, pol.n, nV), z(Pa, S, pol.n, nV), z(Pa, S, pol.n, nV)] for l in plan.distinct if l != 0}
+    out = {} if sink is not None else {l: [z(S, pol.n, nV), z(S, pol.n, nV), z(Pa, S, pol.n, nV), z(Pa, S, pol.n, nV)]
+                                       for l in plan.distinct if l != 0}
     out[0] = [sc.R, sc.T, sc.Rd, sc.Td]
     full = {} if streams else None
     weights = [float(MS.fourier_weight(FT, m)) for m in range(model.m_max + 1)]
     if S == 0:
         return out, full, weights
     reduced = sc.sub0 is not None
-    if reduced:      # m = 0 first, like SceneLin.run
+    if reduced and sink is not None:
+        _run_scene(sc.sub0, plan, False, sink)
+    elif reduced:      # m = 0 first, like SceneLin.run
         MS.merge_sub0(_run_scene(sc.sub0, plan, streams), pol.n,
                       {l: o[:2] + [o[2][:P], o[3][:P]] for l, o in out.items()} if thermal else out, full)
     segs = [(CR.make_composite_layer(FT, sc.arch, (N, N), S), CL.CompositeLayerLin(FT, sc.arch, P, N, S))
-            for _ in range(2 if plan.interior else 0)]
+            for _ in range(2 if plan.interior and not (sink is not None and reduced and not thermal) else 0)]
     for mom in fwd.moments:
         m = mom["m"]
         if m == 0 and reduced:
@@ -141,6 +162,8 @@ def _run_scene(sc: CL.SceneLin, plan: MS.LevelPlan, streams: bool):
         if streams:
             fv[0] = (w["comp"].J0_m.clone(), w["comp"].J0_p.clone(), w["cl"].J0_m.clone(), w["cl"].J0_p.clone())
         asurf, als = w["added_s"], w["als"]
+        if sink is not None and 0 in plan.distinct:
+            sink.level0(sc, mom, w["comp"].J0_m, w["cl"].J0_m, None, False)
 
         def run_segment(seg, first, end):
             for iz in range(first, end):
@@ -155,6 +178,9 @@ def _run_scene(sc: CL.SceneLin, plan: MS.LevelPlan, streams: bool):
             top = tops.pop(l)
             bot = (asurf.r_mp, asurf.j0_m, als.ap_r_mp, als.ap_J0_m) if seg is None else (seg[0].R_mp, seg[0].J0_m, seg[1].R_mp,
                                                                                           seg[1].J0_m)
+            if sink is not None:
+                sink.level(sc, mom, l, top, bot, None, False)
+                return
             vs = MS.level_pair_(pol, qp, model.vza, model.vaz, m, weight, top, bot[0], bot[1], out[l],
                                 lambda dwf, uwf, dwdf, uwdf: level_radiance_lin_(
                                     pol, qp, model.vza, model.vaz, m, weight, P, pl, top[0], bot[0], dwf, uwf, top[2], top[3],
@@ -169,15 +195,16 @@ def _run_scene(sc: CL.SceneLin, plan: MS.LevelPlan, streams: bool):
         if streams:
             full[m] = fv
     if thermal:
-        _run_thermal(sc, plan, segs, out, full)
+        _run_thermal(sc, plan, segs, out, full, sink)
     return out, full, weights
 
 
-def _run_thermal(sc: CL.SceneLin, plan: MS.LevelPlan, segs, out, full):
+def _run_thermal(sc: CL.SceneLin, plan: MS.LevelPlan, segs, out, full, sink: Optional[LevelSink] = None):
     """The `:thermal` slot and the Planck slots of a linearized multi-sensor run (m = 0), after the solar moments, in the order
     of SceneLin._run_thermal at level 0 (its R, T, Rdot, Tdot bit for bit).  segs: the two segment composites of the solar walk,
     free by now.  The Planck sources come first: their vectors a_k, c_k of every level are kept ((K, S, N) each), the operators of
-    those forward walks are not read; then the linearized slot, whose bottoms live only until the level above has used them."""
+    those forward walks are not read; then the linearized slot, whose bottoms live only until the level above has used them.
+    sink: see LevelSink."""
     model, fwd, dt = sc.model, sc.fwd, sc.dt
     pol, qp = sc.pol, sc.qp
     N, S, P, pl, K = sc.N, sc.S, sc.P, sc.pl, sc.nPlanck
@@ -188,6 +215,7 @@ def _run_thermal(sc: CL.SceneLin, plan: MS.LevelPlan, segs, out, full):
     new = lambda *sh: torch.empty(sh, dtype=dt, device=dev)
     below = [l for l in plan.distinct if l != 0]
     src = {l: (torch.zeros((K, S, N), dtype=dt, device=dev), torch.zeros((K, S, N), dtype=dt, device=dev)) for l in below} if K else {}
+    src0 = torch.zeros((K, S, N), dtype=dt, device=dev) if K and sink is not None and 0 in plan.distinct else None
     fv = None
     if full is not None:      # the solar level vectors of m = 0 (the sub-scene's, expanded), their derivative stacks padded to P + K
         pad = (lambda v: torch.cat([v, torch.zeros((K,) + tuple(v.shape[1:]), dtype=dt, device=dev)])) if K else (lambda v: v)
@@ -213,6 +241,8 @@ def _run_thermal(sc: CL.SceneLin, plan: MS.LevelPlan, segs, out, full):
                                lambda seg, bot, first, end: CR.interaction_("11", seg, MS._CompositeAsAdded(bot), oplevel=True,
                                                                             work=fwd.work), keep_bottom)
                 th.finish(mom, weight, sc.Rd[P + k], sc.Td[P + k])
+                if src0 is not None:
+                    src0[k].copy_(th.comp.J0_m)
                 if fv is not None:
                     fv[0][2][P + k].copy_(th.comp.J0_m)
                     fv[0][3][P + k].copy_(th.comp.J0_p)
@@ -234,11 +264,16 @@ def _run_thermal(sc: CL.SceneLin, plan: MS.LevelPlan, segs, out, full):
         fv[0][1].add_(t["comp"].J0_p)
         fv[0][2][:P].add_(t["cl"].J0_m)
         fv[0][3][:P].add_(t["cl"].J0_p)
+    if sink is not None and 0 in plan.distinct:
+        sink.level0(sc, mom, t["comp"].J0_m, t["cl"].J0_m, src0, True)
 
     def level(l, seg):
         top = tops.pop(l)
         bot = (asurf.r_mp, asurf.j0_m, als.ap_r_mp, als.ap_J0_m) if seg is None else (seg[0].R_mp, seg[0].J0_m, seg[1].R_mp,
                                                                                       seg[1].J0_m)
+        if sink is not None:
+            sink.level(sc, mom, l, top, bot, src[l] if K else None, True)
+            return
         dwf, uwf = new(S, N), new(S, N)
         MS.level_radiance_(pol, qp, model.vza, model.vaz, 0, weight, top[0], top[1], bot[0], bot[1], out[l][0], out[l][1], dwf, uwf)
         dwd, uwd = (new(P + K, S, N), new(P + K, S, N)) if fv is not None else (None, None)

@@ -20,7 +20,9 @@
 // vsm_level_radiance_src_*: the same equation for up to VSM_LEVEL_MAX_SRC source pairs (a_k, c_k) on the same A, B (the solar and
 // the thermal slot), the pairs as right-hand sides of ONE solve, their level vectors summed (k_level_radiance_src, below).
 // vsm_level_flux_*: that system again, its level vectors reduced in LDS to hemispheric quadratures (the fluxes of rt_run_fluxes;
-// k_level_flux, below), and the TOA itself, which has no system.
+// k_level_flux, below), and the TOA itself, which has no system.  vsm_level_flux_lin_*: the derivative level vectors of
+// vsm_level_radiance_lin_src_* reduced to the same quadratures, one per slot (the flux Jacobians of CoreRTLin.rt_run_fluxes;
+// level_lin_body's third epilogue, k_level_flux_lin, below).
 // vsm_surface_emission_response_*: the same system between the atmosphere and the surface layer for the unit emission patterns of
 // SurfaceSIF, kept per component (k_emission_response, below).
 #include "vsm_common.h"
@@ -553,14 +555,55 @@ static int level_radiance_ie_fused(int N, int ns, int S, int K, const int* shift
 // column N + pc of L, and steps 2-3 do not tell the two kinds apart (the c_k ride as spare columns of B like every q_p), so a chunk
 // may mix them.  SRC = false is k_level_radiance_lin as it was, statement for statement; SRC = true with P_src = 0 issues the same
 // arithmetic in the same order (one more barrier per chunk).
-template <typename T, bool SRC>
+// FLUX (vsm_level_flux_lin_*, SRC = true): steps 1-3 as they are, but the derivative vectors stay in LDS and a third epilogue
+// (level_flux_reduce) writes their hemispheric quadratures, slot 1 + p of fx.out [3][nW][1 + P + P_src][S]; slot 0 is the same
+// quadrature of the elastic vectors dwf / uwf, and row 2 the direct beam and its derivative -direct tau_sum_dot[p] / mu0 (slots
+// p < p_layer; 0 elsewhere and without tau_sum).  A == nullptr (FLUX only; the same for the whole grid): the TOA, no system:
+// dw = 0 and dw'_p = 0, uw = uwf, uw'_p = c'_p (c_k for a source-only slot); B, Ad, ad, Bd, dwf are not read.
+template <typename T>
+struct level_flux_lin_args {
+  const T* q;             // DEVICE [nW][N / ns]
+  level_flux_dir<T> dir;
+  const T* tau_sum;       // [S] or nullptr
+  const T* F0_I;          // [S]
+  const T* tau_sum_dot;   // [p_layer][S]
+  int p_layer, nW;
+  T* out;                 // [3][nW][1 + P + P_src][S], written
+};
+
+// k_level_flux's reduction for n_vec vector pairs in LDS: wave e % 4 takes item e = (v, r, d) and writes
+//   out[d][r][slot0 + v][s] = sum_i q[r][i] vec_d[v][i ns]      (d = 0: up[v up_vs + row up_is], d = 1: dn likewise; !has_dn: 0)
+// a lane adds its stream i = lane, then lane + 64, then a butterfly over the wave: the order depends on N and ns alone.
+template <typename T>
+__device__ __forceinline__ void level_flux_reduce(int Nq, int ns, int nW, int n_vec, const T* __restrict__ q, const T* up, int up_vs,
+                                                  int up_is, const T* dn, int dn_vs, int dn_is, bool has_dn, T* out, int slot0,
+                                                  int slots, long long S, long long s) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  for (int e = wave; e < 2 * nW * n_vec; e += LEVEL_NT / 64) {
+    const int d = e & 1, r = (e >> 1) % nW, v = e / (2 * nW);
+    T acc = T(0);
+    if (d == 0 || has_dn) {
+      for (int i = lane; i < Nq; i += 64) {
+        const int row = i * ns;
+        const T x = d ? dn[v * dn_vs + row * dn_is] : up[v * up_vs + row * up_is];
+        acc += q[r * Nq + i] * x;
+      }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+    if (lane == 0) out[(((long long)d * nW + r) * slots + slot0 + v) * S + s] = acc;
+  }
+}
+
+template <typename T, bool SRC, bool FLUX = false>
 __device__ __forceinline__ void level_lin_body(int N, int ns, int S, int P, int P_top, int P_src, int PC, int nV, const level_pp& pa,
                                                const T* __restrict__ A, const T* __restrict__ B, long long bstride,
                                                const T* __restrict__ dwf, const T* __restrict__ uwf, const T* __restrict__ Ad,
                                                long long ad_pstride, const T* __restrict__ ad, const T* __restrict__ Bd,
                                                long long bd_stride, long long bd_pstride, const T* __restrict__ cd,
                                                const T* __restrict__ asrc, const T* __restrict__ csrc, T* uwd, T* dwd, T* dwd_full,
-                                               T* uwd_full, int* status) {
+                                               T* uwd_full, int* status,
+                                               const level_flux_lin_args<T>& fx = level_flux_lin_args<T>{}) {
   extern __shared__ __align__(16) unsigned char lds_raw[];
   const int LD = N + PC;
   T* L = reinterpret_cast<T*>(lds_raw);          // [M | r_1 .. r_PC], row-major, leading dimension N + PC
@@ -572,14 +615,28 @@ __device__ __forceinline__ void level_lin_body(int N, int ns, int S, int P, int 
   const int tid = threadIdx.x;
   const long long s = blockIdx.x;
   const long long NN = (long long)N * N, SN = (long long)S * N;
-  const T* As = A + s * NN;
-  const T* Bs = B + s * bstride;
+  const bool toa = FLUX && !A;
+  const T* As = toa ? nullptr : A + s * NN;
+  const T* Bs = toa ? nullptr : B + s * bstride;
   const int G = LEVEL_NT / N, g = tid / N, i1 = tid - g * N;
   for (int i = tid; i < N; i += LEVEL_NT) {
-    xs[i] = dwf[s * N + i];
+    xs[i] = toa ? T(0) : dwf[s * N + i];
     ys[i] = uwf[s * N + i];
   }
   const int Ptot = SRC ? P + P_src : P;
+  if (FLUX) {   // slot 0: the quadratures of the elastic vectors; row 2: the direct beam and its derivatives
+    __syncthreads();
+    level_flux_reduce<T>(N / ns, ns, fx.nW, 1, fx.q, ys, 0, 1, xs, 0, 1, !toa, fx.out, 0, 1 + Ptot, S, s);
+    for (int e = tid; e < fx.nW * (1 + Ptot); e += LEVEL_NT) {
+      const int r = e / (1 + Ptot), slot = e - r * (1 + Ptot);
+      T v = T(0);
+      if (fx.tau_sum && slot <= fx.p_layer) {
+        v = fx.dir.h[r] * fx.F0_I[s] * exp(-fx.tau_sum[s] / fx.dir.mu0);
+        if (slot) v = -v * fx.tau_sum_dot[(long long)(slot - 1) * S + s] / fx.dir.mu0;
+      }
+      fx.out[(((long long)2 * fx.nW + r) * (1 + Ptot) + slot) * S + s] = v;
+    }
+  }
   for (int p0 = 0; p0 < Ptot; p0 += PC) {
     const int pc_n = Ptot - p0 < PC ? Ptot - p0 : PC;
     if (tid == 0) sh[1] = 0;
@@ -587,6 +644,14 @@ __device__ __forceinline__ void level_lin_body(int N, int ns, int S, int P, int 
     // 1. q_p and s_p of the chunk
     for (int pc = 0; pc < pc_n; ++pc) {
       const int p = p0 + pc;
+      if (toa) {   // no layer above: uw'_p = c'_p or c_k, dw'_p = 0
+        const T* cp = p >= P ? csrc + (long long)(p - P) * SN + s * N : cd + p * SN + s * N;
+        for (int i = tid; i < N; i += LEVEL_NT) {
+          Q[pc * N + i] = cp[i];
+          L[i * LD + N + pc] = T(0);
+        }
+        continue;
+      }
       if (SRC && p >= P) {   // a source-only slot (the whole workgroup takes this branch together)
         const long long o = (long long)(p - P) * SN + s * N;
         for (int i = tid; i < N; i += LEVEL_NT) {
@@ -603,26 +668,32 @@ __device__ __forceinline__ void level_lin_body(int N, int ns, int S, int P, int 
       level_stream_reduce<T>(N, G, g, i1, acc, part, Q + pc * N, 1, L + N + pc, LD);
     }
     if (SRC) __syncthreads();   // (a chunk may end with source-only slots, which end without a barrier)
-    // 2. [M | r] and its elimination
-    const int NC = N + pc_n;
-    level_form_system<T>(N, NC, LD, As, Bs, Q, L, sh, status);
-    level_eliminate<T>(N, NC, LD, L, sh, status);
-    // 3. dw'_p = r_p / m_ii (in place: each element is read and written by its own thread), then uw'_p = q_p + B dw'_p
-    for (int e = tid; e < N * pc_n; e += LEVEL_NT) {
-      const int i = e % N, pc = e / N;
-      L[i * LD + N + pc] = L[i * LD + N + pc] / L[i * LD + i];
+    if (!toa) {
+      // 2. [M | r] and its elimination
+      const int NC = N + pc_n;
+      level_form_system<T>(N, NC, LD, As, Bs, Q, L, sh, status);
+      level_eliminate<T>(N, NC, LD, L, sh, status);
+      // 3. dw'_p = r_p / m_ii (in place: each element is read and written by its own thread), then uw'_p = q_p + B dw'_p
+      for (int e = tid; e < N * pc_n; e += LEVEL_NT) {
+        const int i = e % N, pc = e / N;
+        L[i * LD + N + pc] = L[i * LD + N + pc] / L[i * LD + i];
+      }
+      __syncthreads();
+      for (int e = tid; e < N * pc_n; e += LEVEL_NT) {
+        const int i = e % N, pc = e / N;
+        T y = Q[pc * N + i];
+        for (int j = 0; j < N; ++j) y += Bs[(long long)j * N + i] * L[j * LD + N + pc];
+        Q[pc * N + i] = y;
+        const long long o = (long long)(p0 + pc) * SN + s * N + i;
+        if (dwd_full) dwd_full[o] = L[i * LD + N + pc];
+        if (uwd_full) uwd_full[o] = y;
+      }
+      __syncthreads();
     }
-    __syncthreads();
-    for (int e = tid; e < N * pc_n; e += LEVEL_NT) {
-      const int i = e % N, pc = e / N;
-      T y = Q[pc * N + i];
-      for (int j = 0; j < N; ++j) y += Bs[(long long)j * N + i] * L[j * LD + N + pc];
-      Q[pc * N + i] = y;
-      const long long o = (long long)(p0 + pc) * SN + s * N + i;
-      if (dwd_full) dwd_full[o] = L[i * LD + N + pc];
-      if (uwd_full) uwd_full[o] = y;
+    if (FLUX) {   // the third epilogue: the quadratures of the chunk's vectors, written
+      level_flux_reduce<T>(N / ns, ns, fx.nW, pc_n, fx.q, Q, N, 1, L + N, 1, LD, true, fx.out, 1 + p0, 1 + Ptot, S, s);
+      continue;
     }
-    __syncthreads();
     for (int e = tid; e < nV * ns * pc_n; e += LEVEL_NT) {
       const int v = e % nV, k = (e / nV) % ns, pc = e / (nV * ns);
       const T w = (T)pa.w[v + nV * k];
@@ -631,6 +702,21 @@ __device__ __forceinline__ void level_lin_body(int N, int ns, int S, int P, int 
       dwd[dst] += w * L[(pa.row0[v] + k) * LD + N + pc];
     }
   }
+}
+
+// vsm_level_flux_lin_*: level_lin_body<T, true, true> (no VZA table, no full vectors out)
+template <typename T>
+__global__ void __launch_bounds__(LEVEL_NT) k_level_flux_lin(int N, int ns, int S, int P, int P_top, int P_src, int PC,
+                                                             const T* __restrict__ A, const T* __restrict__ B, long long bstride,
+                                                             const T* __restrict__ dwf, const T* __restrict__ uwf,
+                                                             const T* __restrict__ Ad, long long ad_pstride,
+                                                             const T* __restrict__ ad, const T* __restrict__ Bd, long long bd_stride,
+                                                             long long bd_pstride, const T* __restrict__ cd,
+                                                             const T* __restrict__ asrc, const T* __restrict__ csrc,
+                                                             level_flux_lin_args<T> fx, int* status) {
+  const level_pp pa = {};
+  level_lin_body<T, true, true>(N, ns, S, P, P_top, P_src, PC, 0, pa, A, B, bstride, dwf, uwf, Ad, ad_pstride, ad, Bd, bd_stride,
+                                bd_pstride, cd, asrc, csrc, nullptr, nullptr, nullptr, nullptr, status, fx);
 }
 
 template <typename T>
@@ -713,6 +799,65 @@ static int level_radiance_lin_src_fused(int N, int ns, int S, int P, int P_top, 
         return (int)VSM_OK;
       },
       [&](const T* uf, const T* df) { return postprocess_vza_lin<T>(N, ns, S, nV, Ptot, row0_h, w_h, uf, df, uwd, dwd, st); });
+}
+
+// vsm_level_flux_lin_*: the chunks and the LDS layout of vsm_level_radiance_lin_src_*, the same bound
+template <typename T>
+static int level_flux_lin_fused(int N, int ns, int S, int P, int P_top, int P_src, const T* A, const T* B, long long bstride,
+                                const T* dwf, const T* uwf, const T* Ad, long long ad_pstride, const T* ad, const T* Bd,
+                                long long bd_stride, long long bd_pstride, const T* cd, const T* asrc, const T* csrc, int nW, const T* q,
+                                const T* dir_h, T mu0, const T* tau_sum, const T* F0_I, const T* tau_sum_dot, int p_layer, T* out,
+                                hipStream_t st) {
+  int* status = device_status();
+  if (!status) return VSM_ERR_HIP;
+  const int Ptot = P + P_src;
+  const int PC = level_lin_chunk<T>(N, Ptot);
+  const size_t lds = ((size_t)N * (N + PC) + (size_t)PC * N + 2 * (size_t)N + 2 * (size_t)LEVEL_NT) * sizeof(T);
+  const int rc = ensure_dyn_lds(reinterpret_cast<const void*>(k_level_flux_lin<T>), lds, "hipFuncSetAttribute(k_level_flux_lin)");
+  if (rc) return rc;
+  level_flux_lin_args<T> fx = {};
+  fx.q = q;
+  for (int r = 0; r < nW; ++r) fx.dir.h[r] = tau_sum ? dir_h[r] : T(0);
+  fx.dir.mu0 = mu0;
+  fx.tau_sum = tau_sum;
+  fx.F0_I = F0_I;
+  fx.tau_sum_dot = tau_sum_dot;
+  fx.p_layer = tau_sum ? p_layer : 0;
+  fx.nW = nW;
+  fx.out = out;
+  hipLaunchKernelGGL(k_level_flux_lin<T>, dim3(S), dim3(LEVEL_NT), lds, st, N, ns, S, P, P_top, P_src, PC, A, B, bstride, dwf, uwf, Ad,
+                     ad_pstride, ad, Bd, bd_stride, bd_pstride, cd, asrc, csrc, fx, status);
+  VSM_LAUNCH_CHECK("k_level_flux_lin");
+  return VSM_OK;
+}
+
+template <typename T>
+static int level_flux_lin_check(int N, int ns, int S, int P, int P_top, int P_src, const T* A, const T* B, long long bstride,
+                                const T* dwf, const T* uwf, const T* Ad, long long ad_pstride, const T* ad, const T* Bd,
+                                long long bd_stride, long long bd_pstride, const T* cd, const T* asrc, const T* csrc, int nW, const T* q,
+                                const T* dir_h, T mu0, const T* tau_sum, const T* F0_I, const T* tau_sum_dot, int p_layer,
+                                const T* out) {
+  VSM_REQUIRE(N > 0 && ns >= 1 && ns <= 4 && N % ns == 0 && S >= 0, "level_flux_lin: bad size (N %d, n_stokes %d, S %d)", N, ns, S);
+  VSM_REQUIRE(N <= LEVEL_FUSED_MAX_N, "level_flux_lin: N = %d > %d, the limit of its kernel", N, LEVEL_FUSED_MAX_N);
+  VSM_REQUIRE(P >= 0 && P_src >= 0 && P + P_src >= 1 && P + P_src <= 64 && P_top >= 0 && P_top <= P,
+              "level_flux_lin: bad slot count (P %d + P_src %d in 1..64, P_top %d in 0..P)", P, P_src, P_top);
+  VSM_REQUIRE(nW >= 1 && nW <= 4, "level_flux_lin: nW = %d outside 1..4", nW);
+  VSM_REQUIRE(bstride == 0 || bstride == (long long)N * N, "level_flux_lin: bot_stride must be 0 or N*N");
+  VSM_REQUIRE(bd_stride == 0 || bd_stride == (long long)N * N, "level_flux_lin: bot_lin_stride must be 0 or N*N");
+  VSM_REQUIRE(!A || P == 0 ||
+                  (bd_pstride >= (bd_stride ? (long long)S * N * N : (long long)N * N) &&
+                   (P_top == 0 || ad_pstride >= (long long)S * N * N)),
+              "level_flux_lin: a per-parameter stride is shorter than one parameter's blocks");
+  VSM_REQUIRE((tau_sum == nullptr) == (F0_I == nullptr), "level_flux_lin: tau_sum and F0_I are both given or both NULL");
+  VSM_REQUIRE(!tau_sum || (dir_h && mu0 > T(0)), "level_flux_lin: the direct term needs dir_h and mu0 > 0");
+  VSM_REQUIRE(p_layer >= 0 && p_layer <= P, "level_flux_lin: p_layer = %d outside 0..P = %d", p_layer, P);
+  VSM_REQUIRE(!tau_sum || p_layer == 0 || tau_sum_dot, "level_flux_lin: the direct term's derivative needs tau_sum_dot");
+  VSM_REQUIRE(S == 0 || (uwf && q && out), "level_flux_lin: null level vector / weight rows / output");
+  VSM_REQUIRE(S == 0 || P == 0 || cd, "level_flux_lin: null bottom source derivative");
+  VSM_REQUIRE(S == 0 || !A || (B && dwf && (P == 0 || Bd)), "level_flux_lin: a top needs the bottom's R-+, its derivative and dw");
+  VSM_REQUIRE(S == 0 || !A || P_top == 0 || (Ad && ad), "level_flux_lin: null top derivative operand");
+  VSM_REQUIRE(S == 0 || P_src == 0 || (csrc && (!A || asrc)), "level_flux_lin: null source operand");
+  return VSM_OK;
 }
 
 // operator-level twin: M = I - A B, d = a + A c (two batched products), dw = M^-1 d (vsm_batch_inv + product), uw = c + B dw
@@ -1062,6 +1207,26 @@ VSM_LEVEL_LIN_API(float, f32)
   }
 VSM_LEVEL_LIN_SRC_API(double, f64)
 VSM_LEVEL_LIN_SRC_API(float, f32)
+
+#define VSM_LEVEL_FLUX_LIN_API(T, SFX)                                                                                         \
+  int vsm_level_flux_lin_##SFX(int N, int n_stokes, int S, int P, int P_top, int P_src, const T* top_R_pm, const T* bot_R_mp,  \
+                               long long bot_stride, const T* dw_full, const T* uw_full, const T* top_R_pm_lin,               \
+                               long long top_lin_pstride, const T* top_J0_p_lin, const T* bot_R_mp_lin,                       \
+                               long long bot_lin_stride, long long bot_lin_pstride, const T* bot_J0_m_lin,                    \
+                               const T* src_top_J0_p, const T* src_bot_J0_m, int nW, const T* q, const T* dir_h, T mu0,       \
+                               const T* tau_sum, const T* F0_I, const T* tau_sum_dot, int p_layer, T* out, void* stream) {    \
+    int rc = level_flux_lin_check<T>(N, n_stokes, S, P, P_top, P_src, top_R_pm, bot_R_mp, bot_stride, dw_full, uw_full,       \
+                                     top_R_pm_lin, top_lin_pstride, top_J0_p_lin, bot_R_mp_lin, bot_lin_stride,               \
+                                     bot_lin_pstride, bot_J0_m_lin, src_top_J0_p, src_bot_J0_m, nW, q, dir_h, mu0, tau_sum,   \
+                                     F0_I, tau_sum_dot, p_layer, out);                                                        \
+    if (rc || S == 0) return rc;                                                                                              \
+    return level_flux_lin_fused<T>(N, n_stokes, S, P, P_top, P_src, top_R_pm, bot_R_mp, bot_stride, dw_full, uw_full,         \
+                                   top_R_pm_lin, top_lin_pstride, top_J0_p_lin, bot_R_mp_lin, bot_lin_stride,                 \
+                                   bot_lin_pstride, bot_J0_m_lin, src_top_J0_p, src_bot_J0_m, nW, q, dir_h, mu0, tau_sum,     \
+                                   F0_I, tau_sum_dot, p_layer, out, as_stream(stream));                                       \
+  }
+VSM_LEVEL_FLUX_LIN_API(double, f64)
+VSM_LEVEL_FLUX_LIN_API(float, f32)
 
 #define VSM_EMISSION_RESPONSE_API(T, SFX)                                                                                       \
   int vsm_surface_emission_response_##SFX(int N, int n_stokes, int S, int K, const int* comp_h, int nV, const int* row0_h,      \
