@@ -494,6 +494,29 @@ int vsm_brdf_surface_lin_multi_f32(const vsm_quad_f32* q, int S, int m, const fl
 int vsm_surface_sif_f64(int N, int n_stokes, int S, const double* sif, const vsm_added_f64* added_surface, void* stream);
 int vsm_surface_sif_f32(int N, int n_stokes, int S, const float* sif, const vsm_added_f32* added_surface, void* stream);
 
+/* SurfaceEmission (ours; the reference has no surface thermal source): thermal emission of the lower boundary, applied to the surface
+ * AddedLayer of the `:thermal` slot AFTER its builder and BEFORE the surface interaction, at Fourier moment m = 0 only (m > 0:
+ * VSM_OK, nothing launched).  B_surface: DEVICE array [S], the Planck radiance of the skin in the units of vsm_thermal_source_*'s B.
+ * emissivity == NULL (Kirchhoff): for every row (stream i, Stokes component c, n = n_stokes) and point s
+ *   j0_m[i n + c, s] += 2 pi B_surface[s] ( delta_{c,0} - sum_j r_mp[i n + c, j n, s] )
+ * -- the sum over the I column of every stream j: the surface builders fold 2 mu_j w_j into column j at m = 0, so it is the
+ * directional-hemispherical reflectance of that row for unpolarized isotropic illumination, zero-weight rows included.
+ * emissivity: DEVICE array [S]: the bracket is delta_{c,0} emissivity[s] (isotropic, unpolarized).
+ * added_surface->r_mp is read with mat_stride 0 (one shared block) or N*N (one per point), j0_m [N,1,S] is read and written,
+ * nothing else is touched; one thread per (row, point).  S = 0: VSM_OK. */
+int vsm_surface_emission_f64(int N, int n_stokes, int S, int m, const double* B_surface, const double* emissivity,
+                             const vsm_added_f64* added_surface, void* stream);
+int vsm_surface_emission_f32(int N, int n_stokes, int S, int m, const float* B_surface, const float* emissivity,
+                             const vsm_added_f32* added_surface, void* stream);
+/* The derivative of the Kirchhoff emission in the K surface slots isurf .. isurf + K - 1 of the linearized surface layer, after its
+ * builder, m = 0 only:  ap_J0_m[p][i n + c, s] += -2 pi B_surface[s] sum_j ap_r_mp[p][i n + c, j n, s].  An explicit emissivity
+ * depends on no parameter (no call); the layer slots need nothing here (the linearized interaction differentiates the propagation
+ * of the forward j0_m).  al->mat_stride 0 or N*N as in the forward layer. */
+int vsm_surface_emission_lin_f64(int N, int n_stokes, int S, int m, const double* B_surface, int isurf, int K,
+                                 const vsm_added_lin_f64* added_surface_lin, void* stream);
+int vsm_surface_emission_lin_f32(int N, int n_stokes, int S, int m, const float* B_surface, int isurf, int K,
+                                 const vsm_added_lin_f32* added_surface_lin, void* stream);
+
 /* interaction_hdrf! (src/CoreRT/CoreKernel/interaction_hdrf.jl:4-42), called after the surface interaction of each Fourier
  * moment (rt_run.jl:467-476): hdr_J[N,S] = r-+_surf J0+ + j0-_surf; for m == 0 also the hemispheric fluxes bhr_uw / bhr_dw
  * [n_stokes, S] (for m > 0 they are not touched).  The surface layer may be shared (mat_stride 0) or per point. */

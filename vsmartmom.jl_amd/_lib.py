@@ -109,6 +109,8 @@ _SIGS = {
     "vsm_interaction_oplevel_{T}": (_I, [_I, _I, _I, _P, _P, _P, _P]),
     "vsm_lambertian_surface_{T}": (_I, [_P, _I, _I, "{R}", _P, _P, _P]),
     "vsm_surface_sif_{T}": (_I, [_I, _I, _I, _P, _P, _P]),
+    "vsm_surface_emission_{T}": (_I, [_I, _I, _I, _I, _P, _P, _P, _P]),
+    "vsm_surface_emission_lin_{T}": (_I, [_I, _I, _I, _I, _P, _I, _I, _P, _P]),
     "vsm_postprocess_vza_{T}": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "vsm_compute_Z_moments_{T}": (_I, [_P, _I, _I, _P, _P, _P, _P]),
     "vsm_layer_optics_{T}": (_I, [_I, _I, _I, _P, _P, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),

@@ -529,6 +529,24 @@ def surface_source_contribute_(scene_or_table, surface, added_surface: AddedLaye
     return True
 
 
+def surface_emission_contribute_(B_surface, emissivity, added_surface: AddedLayer, n_stokes: int, m: int) -> bool:
+    """SurfaceEmission on the surface layer of the `:thermal` slot (vsm_surface_emission), after the surface builder and
+    before the surface interaction: j0-[row, s] += 2 pi B_surface[s] eps[row, s], eps from the layer's own r-+ (emissivity None:
+    Kirchhoff) or emissivity[s] on the I rows.  B_surface, emissivity: (S,) device tensors.  m > 0 or no table: nothing is
+    launched.  Returns whether the kernel was launched."""
+    if B_surface is None or m != 0:
+        return False
+    S, dt = added_surface.nSpec, added_surface.dtype
+    for t, what in ((B_surface, "B_surface"), (emissivity, "emissivity")):
+        if t is not None and (tuple(t.shape) != (S,) or t.dtype != dt):
+            raise _lib.VSMError("SurfaceEmission: %s %s (%s) does not fit a surface layer of %d points (%s)"
+                                % (what, tuple(t.shape), t.dtype, S, dt))
+    a = added_surface.cstruct()
+    _lib.call("vsm_surface_emission", dt, added_surface.N, n_stokes, S, m, _ptr(B_surface), _ptr(emissivity), C.byref(a),
+              _stream_ptr())
+    return True
+
+
 def apply_ss_correction_(R_SFI: torch.Tensor, surf: H.CoxMunkSurface, pol, vza, vaz, mu0, tau_total: torch.Tensor, m_max: int,
                          arch, FT):
     """apply_ss_correction! (coxmunk_surface.jl:481-545; rt_run.jl:520-524): R_SFI (S, n, nV) layout tensor, in place.
@@ -822,9 +840,10 @@ class Scene:
         # sources (rt_run(model; sources = ...)): the solar slot lives inside the layer kernels (F0), every other source
         # has a slot of its own (here: :thermal)
         srcs = tuple(model.sources) if model.sources is not None else (H.SolarBeam(),)
-        unknown = [s_ for s_ in srcs if not isinstance(s_, (H.SolarBeam, H.ThermalEmission, H.SurfaceSIF))]
+        unknown = [s_ for s_ in srcs if not isinstance(s_, (H.SolarBeam, H.ThermalEmission, H.SurfaceSIF, H.SurfaceEmission))]
         if unknown:
-            raise _lib.VSMError("rt_run: unsupported source %r (SolarBeam, ThermalEmission, SurfaceSIF)" % (unknown[0],))
+            raise _lib.VSMError("rt_run: unsupported source %r (SolarBeam, ThermalEmission, SurfaceSIF, SurfaceEmission)"
+                                % (unknown[0],))
         if not any(isinstance(s_, H.SolarBeam) for s_ in srcs):
             F0 = np.zeros((pol.n, S_full))
         th = [s_ for s_ in srcs if isinstance(s_, H.ThermalEmission) and s_.B_layer is not None and np.any(s_.B_layer != 0)]
@@ -836,6 +855,21 @@ class Scene:
             if B.shape[1] != S_full:
                 raise _lib.VSMError("ThermalEmission: B_layer has %d spectral points, the model %d" % (B.shape[1], S_full))
             self.thermal_B = conv(np.ascontiguousarray(B[:, self.sl].astype(FT)))          # (rows, S)
+        # SurfaceEmission: this rank's slice of B_surface (S,) and of an explicit emissivity (None = Kirchhoff), injected
+        # into the surface layer of the `:thermal` slot at m = 0 (ThermalSlot.surface).  None without the source or with an all-zero
+        # B_surface (nothing is allocated or launched then).  Without a ThermalEmission the slot runs on a Planck table of 0 rows
+        # (walk skips contribute!), so `thermal_B is not None` still says whether the scene has a thermal slot.  The emissivity
+        # belongs to the boundary, not to one table: the skin slots of the linearized runs (surface(mom, B_surface_dot[k])) emit
+        # with it too, so it is uploaded for a non-zero dot table as well, whatever B_surface is.
+        self.surface_B = self.surface_emissivity = None
+        se = H.surface_emission_of(model)
+        emits = se is not None and bool(np.any(se.B_surface != 0))
+        if se is not None and se.emissivity is not None and (emits or (se.nSkin and np.any(se.B_surface_dot != 0))):
+            self.surface_emissivity = conv(np.ascontiguousarray(se.emissivity[self.sl].astype(FT)))
+        if emits:
+            self.surface_B = conv(np.ascontiguousarray(se.B_surface[self.sl].astype(FT)))
+            if self.thermal_B is None:
+                self.thermal_B = conv(np.zeros((0, self.S), dtype=FT))
         self.F0 = conv(np.ascontiguousarray(np.asarray(F0, dtype=FT)[:, self.sl].T))  # [n,S] col-major == (S,n)
         # SurfaceSIF: its table [nStokes, nSpec], this rank's columns as (n, S); None without the source or with an all-zero table
         # (nothing is allocated or launched then).  Injected into the SOLAR slot's surface layer at m = 0 (surface_source_contribute_)
@@ -1301,13 +1335,17 @@ class Scene:
         return tot
 
 
+SCENE_TABLE = object()       # ThermalSlot.surface(B_surface=SCENE_TABLE): the scene's own skin table
+
+
 class ThermalSlot:
     """The `:thermal` per-source slot of a Scene (rt_kernel.jl:204-232, doubling.jl:62-81, interaction.jl per-source recurrences,
     postprocessing_vza.jl:68-82): the solar slot's linear source recurrences driven by the thermal source (vsm_thermal_source
     between elemental! and doubling!, the slot's own expk = 1); its J0 is added to R_SFI / T_SFI.  On an AddedLayer (`added`), a
     surface layer (`surf`) and a CompositeLayer (`comp`) of its own (r, t, R, T evolve exactly like the solar pass's), with its
-    zero beam and its expk = 1 vector: begin, walk layers 1..Nz, surface, finish.  The Planck table is an argument of walk(): the
-    slot is linear in it, and the linearized runs walk it once per derivative table.
+    zero beam and its expk = 1 vector: begin, walk layers 1..Nz, surface, finish.  The Planck table is an argument of walk() and the
+    skin table of the emitting boundary (SurfaceEmission) one of surface(): the slot is linear in both, and the
+    linearized runs walk it once per derivative table.
 
     State, as the reference carries it (default; ThermalEmission(reset_slot_in_nonscattering_layers=True) = the corrected
     variant): the slot's j0+- belong to the AddedLayer that is allocated once per run (rt_run.jl:326-335); only the scatter
@@ -1392,13 +1430,18 @@ class ThermalSlot:
             if after and (iz + 1) in after:
                 after[iz + 1](comp)
 
-    def surface(self, mom):
-        """The slot's surface layer: the solar one without its beam terms (surface emission is a separate source type: SurfaceSIF
-        is counted once, in the solar slot, and never injected here)."""
+    def surface(self, mom, B_surface=SCENE_TABLE):
+        """The slot's surface layer: the solar one without its beam terms (SurfaceSIF is counted once, in the solar slot, and never
+        injected here), then the thermal emission of the boundary for the skin table B_surface ((S,), or None for a boundary that
+        does not emit; default: the scene's own SurfaceEmission) -- the slot is linear in it as it is in walk()'s B, and the
+        linearized runs build it once per derivative table.  The emissivity is the scene's."""
         sc = self.scene
         create_surface_layer_(sc.model.surface, self.surf, mom["m"], sc.dq, mom["tau_sum_surface"], rho=mom["rho"])
         self.surf.j0_p.zero_()      # no solar beam in this slot
         self.surf.j0_m.zero_()
+        if B_surface is SCENE_TABLE:
+            B_surface = sc.surface_B
+        surface_emission_contribute_(B_surface, sc.surface_emissivity, self.surf, sc.pol.n, mom["m"])
         return self.surf
 
     def finish(self, mom, weight, R_SFI, T_SFI):
@@ -1455,9 +1498,10 @@ def rt_run(model: H.RTModel, trace: Optional[list] = None, full_output: bool = F
     reference's first two return values -- or, with `full_output`, its whole SFI tuple
     (R_SFI, T_SFI, ieR_SFI, ieT_SFI, hdr, bhr_uw[1,:], bhr_dw[1,:]) (rt_run.jl:535).
 
-    Sources: model.sources may hold SolarBeam, ThermalEmission and SurfaceSIF (None = SolarBeam alone; without a SolarBeam
-    F0 = 0).  The thermal radiance is a slot of its own added to R_SFI / T_SFI; SurfaceSIF is injected into the surface layer of
-    the solar slot at m = 0 (surface_source_contribute_), over Lambertian surfaces only."""
+    Sources: model.sources may hold SolarBeam, ThermalEmission, SurfaceSIF and SurfaceEmission (None = SolarBeam alone; without a
+    SolarBeam F0 = 0).  The thermal radiance is a slot of its own added to R_SFI / T_SFI; SurfaceEmission is the emission of that
+    slot's lower boundary (m = 0, every surface type; with or without a ThermalEmission beside it); SurfaceSIF is injected into the
+    surface layer of the solar slot at m = 0 (surface_source_contribute_), over Lambertian surfaces only."""
     scene = prepare_scene(model)
     scene.compute_hdrf = bool(full_output)
     scene.run(trace)

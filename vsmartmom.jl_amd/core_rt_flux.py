@@ -214,8 +214,8 @@ def rt_run_fluxes(model: H.RTModel, levels=None, thermal: bool = False, max_poin
     Only m = 0 is walked, whatever model.m_max is.  Only the I row is reported: no Q / U / V fluxes; no Cox-Munk single-scattering
     correction, as the multi-sensor run has none.  Jacobians of every field: CoreRTLin.rt_run_fluxes (core_rt_flux_lin.py).
 
-    Sources as the elastic rt_run_multisensor takes them: SolarBeam and SurfaceSIF always, ThermalEmission under thermal=True
-    (VSMError without it), any other source VSMError; every result is the sum over the sources.  Without a SolarBeam F0 = 0 and
+    Sources as the elastic rt_run_multisensor takes them: SolarBeam and SurfaceSIF always, ThermalEmission and SurfaceEmission
+    under thermal=True (VSMError without it; the emitting boundary enters through the slot's surface layer), any other source VSMError; every result is the sum over the sources.  Without a SolarBeam F0 = 0 and
     both direct terms are 0.  Columns with a non-scattering layer raise NotImplementedError.
 
     max_points: run the spectral axis in blocks of that many points (ndoubl and the interface tags stay batch-global); None = as
@@ -226,7 +226,7 @@ def rt_run_fluxes(model: H.RTModel, levels=None, thermal: bool = False, max_poin
     qp, pol = model.quad_points, model.polarization_type
     N = qp.Nquad * pol.n
     S_full = int(np.asarray(model.tau_rayl).shape[0])
-    has_th = any(isinstance(s_, H.ThermalEmission) for s_ in (model.sources or ()))
+    has_th = any(isinstance(s_, (H.ThermalEmission, H.SurfaceEmission)) for s_ in (model.sources or ()))
     if max_points is None and S_full > 0:
         per = bytes_per_point(N, Nz, plan.n_tops, bool(plan.interior), has_th, np.dtype(model.float_type).itemsize)
         free, _total = torch.cuda.mem_get_info()

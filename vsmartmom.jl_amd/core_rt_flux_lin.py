@@ -87,7 +87,7 @@ class _FluxSink(MSL.LevelSink):
 
     def __init__(self, sc: CL.SceneLin, plan: MS.LevelPlan, thermal: bool):
         self.plan, self.thermal = plan, thermal
-        self.nS, self.nT = 1 + sc.P, (1 + sc.P + sc.nPlanck) if thermal else 0
+        self.nS, self.nT = 1 + sc.P, (1 + sc.P + sc.nSrc) if thermal else 0
         dt, dev = sc.dt, sc.R.device
         self.buf = torch.empty((len(plan.distinct), 6 * (self.nS + self.nT), sc.S), dtype=dt, device=dev)
         self.row = {l: i for i, l in enumerate(plan.distinct)}
@@ -131,7 +131,8 @@ class _FluxSink(MSL.LevelSink):
 def bytes_per_point(N: int, P: int, pl: int, Nz: int, n_tops: int, segments: bool, n_levels: int, n_stokes: int, itemsize: int,
                     thermal: bool = False, nPlanck: int = 0) -> int:
     """Device bytes per spectral point of a linearized flux run: the estimate of the linearized multi-sensor run
-    (core_rt_ms_lin.bytes_per_point) without its VZA outputs, and the 6 (1 + P) (+ 6 (1 + P + nPlanck)) scalars per level."""
+    (core_rt_ms_lin.bytes_per_point) without its VZA outputs, and the 6 (1 + P) (+ 6 (1 + P + nPlanck)) scalars per level.
+    nPlanck counts the Planck and the skin tables, as there (core_rt_ms_lin.thermal_estimate)."""
     per = MSL.bytes_per_point(N, P, pl, Nz, n_tops, segments, n_levels, n_stokes, 0, itemsize, thermal=thermal, nPlanck=nPlanck)
     return per + n_levels * 6 * ((1 + P) + ((1 + P + nPlanck) if thermal else 0)) * itemsize
 
@@ -152,7 +153,8 @@ def rt_run_fluxes(model: H.RTModel, lin_model: H.LinModel, NAer: int, NGas: int,
 
     Sources: SolarBeam, and a ThermalEmission that states B_layer_dot ([0, rows, nSpec] for no Planck slot), by the opt-in rule of
     the linearized multi-sensor run; the thermal slot is solved on its own operators, its nPlanck slots follow the surface slots,
-    and every field is the sum of the two slots.  ThermalEmission with B_layer_dot = None raises VSMError, SurfaceSIF and columns
+    and every field is the sum of the two slots.  SurfaceEmission: the slot's emitting lower boundary, its nSkin
+    skin slots after the Planck slots.  ThermalEmission with B_layer_dot = None raises VSMError, SurfaceSIF and columns
     with a non-scattering layer NotImplementedError, N > 128 VSMError (the level kernel has no operator-level twin) -- each before
     any layer or level kernel is launched.
 
@@ -173,13 +175,12 @@ def rt_run_fluxes(model: H.RTModel, lin_model: H.LinModel, NAer: int, NGas: int,
     model0 = dataclasses.replace(model, m_max=0)
     FT = model.float_type
     S_full = int(np.asarray(model.tau_rayl).shape[0])
-    thermal = bool(th)
     if max_points is None and S_full > 0:
         layout = H.ParameterLayout(n_aerosols=NAer, n_gases=NGas, n_surface=NSurf)
         P, pl = layout.n_total, layout.n_layer_params
         isz = np.dtype(FT).itemsize
-        kw = dict(thermal=True, nPlanck=int(th[0].B_layer_dot.shape[0])) if thermal else {}
-        per = bytes_per_point(N, P, pl, Nz, plan.n_tops, bool(plan.interior), len(plan.distinct), pol.n, isz, **kw)
+        per = bytes_per_point(N, P, pl, Nz, plan.n_tops, bool(plan.interior), len(plan.distinct), pol.n, isz,
+                              **MSL.thermal_estimate(model))
         if CL.REDUCE_M0 and pol.n >= 3:     # (the Stokes_IQ scene of m = 0, where it applies)
             per += bytes_per_point(2 * qp.Nquad, P, pl, Nz, plan.n_tops, bool(plan.interior), len(plan.distinct), 2, isz)
         free, _total = torch.cuda.mem_get_info()
@@ -196,7 +197,9 @@ def rt_run_fluxes(model: H.RTModel, lin_model: H.LinModel, NAer: int, NGas: int,
         sc = CL.SceneLin(model0, lin_model, NAer, NGas, NSurf, spec_slice=sl)
         MS.refuse_non_scattering(sc.fwd.moments[0]["layers"], sc.FT, WHO,
                                  "; columns with a non-scattering layer are not supported (as for CoreRT.rt_run_fluxes)")
-        sink = _FluxSink(sc, plan, thermal)
+        # the thermal half of the sink exists where _run_scene runs the slot (SceneLin.has_thermal), and only there: a source that
+        # emits nothing and states no table (an all-zero ThermalEmission or SurfaceEmission) would leave that half unwritten
+        sink = _FluxSink(sc, plan, sc.has_thermal)
         nS, nT = sink.nS, sink.nT
         MSL._run_scene(sc, plan, False, sink)
         synchronize_if_gpu()

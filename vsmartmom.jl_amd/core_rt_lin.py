@@ -413,7 +413,13 @@ class SceneLin(LinInputs):
         # SIF slots: SurfaceSIF.SIF0_dot [nSIF, nStokes, nSpec], appended after the Planck slots
         sif_src = [s_ for s_ in (model.sources or ()) if isinstance(s_, H.SurfaceSIF)]
         self.nSIF = sif_src[0].nSIF if sif_src else 0
-        if P + self.nPlanck + self.nSIF > 64:
+        # skin slots: SurfaceEmission.B_surface_dot [nSkin, nSpec], between the Planck and the SIF slots
+        se_src = H.surface_emission_of(model)
+        self.nSkin = se_src.nSkin if se_src is not None else 0
+        if P + self.nPlanck + self.nSkin + self.nSIF > 64:
+            if self.nSkin:
+                raise _lib.VSMError("rt_run (linearized): %d parameter slots + %d Planck slots + %d skin slots + %d SIF slots "
+                                    "(limit 64)" % (P, self.nPlanck, self.nSkin, self.nSIF))
             if self.nSIF:
                 raise _lib.VSMError("rt_run (linearized): %d parameter slots + %d Planck slots + %d SIF slots (limit 64)"
                                     % (P, self.nPlanck, self.nSIF))
@@ -445,6 +451,8 @@ class SceneLin(LinInputs):
         self.R, self.T = fwd.R_SFI, fwd.T_SFI
         # the thermal slot: its layers are allocated on first use (_thermal_state); the Planck tables as (nPlanck, rows, S)
         self.thermal_B_dot = (array_type(arch)(np.ascontiguousarray(Bd[:, :, self.sl].astype(FT))) if self.nPlanck else None)
+        self.surface_B_dot = (array_type(arch)(np.ascontiguousarray(se_src.B_surface_dot[:, self.sl].astype(FT))) if self.nSkin
+                              else None)
         self._th = None
         self._check_thermal()
         # the SIF slots: 2 SIF0_dot as (nSIF, nStokes, S) and the Stokes components some table uses -- the right-hand sides of the
@@ -454,7 +462,7 @@ class SceneLin(LinInputs):
         if self.nSIF and isinstance(model.surface, CR.SIF_SURFACES):
             self._sif_comps = [c for c in range(pol.n) if np.any(sif_dot[:, c, :] != 0)]
             self.sif_dot2 = array_type(arch)(np.ascontiguousarray((2.0 * sif_dot[:, :, self.sl]).astype(FT)))
-        self.Rd = torch.zeros((P + self.nPlanck + self.nSIF, S, pol.n, nV), dtype=dt, device=dev)
+        self.Rd = torch.zeros((P + self.nPlanck + self.nSkin + self.nSIF, S, pol.n, nV), dtype=dt, device=dev)
         self.Td = torch.zeros_like(self.Rd)
         self._lanes = []
         self._fold = {}
@@ -485,7 +493,8 @@ class SceneLin(LinInputs):
         if model.sources is not None:   # (the sub-scene carries no thermal slot; without a SolarBeam its F0 stays 0; a SurfaceSIF
             # without U / V rows -- the constructor's condition -- comes along with its I, Q rows and its SIF slots)
             model = dataclasses.replace(model, sources=tuple(s_.stokes_iq() if isinstance(s_, H.SurfaceSIF) else s_
-                                                             for s_ in model.sources if not isinstance(s_, H.ThermalEmission)))
+                                                             for s_ in model.sources
+                                                             if not isinstance(s_, (H.ThermalEmission, H.SurfaceEmission))))
         qi = H.QuadPoints(qp.mu0, qp.imu0, qp.qp_mu, qp.wt_mu, np.repeat(qp.qp_mu, 2), np.repeat(qp.wt_mu, 2), qp.Nquad, qp.Nstreams)
         return dataclasses.replace(model, polarization_type=H.Stokes_IQ(), quad_points=qi, m_max=0,
                                    F0=None if F0m is None else np.ascontiguousarray(np.asarray(F0m)[:2]))
@@ -583,8 +592,8 @@ class SceneLin(LinInputs):
             raise NotImplementedError("SceneLin.run(graph=True): a scene with a SurfaceSIF source is not captured "
                                       "(run it with graph=False or graph=None)")
         if graph and thermal:
-            raise NotImplementedError("SceneLin.run(graph=True): a scene with a ThermalEmission source is not captured "
-                                      "(run it with graph=False or graph=None)")
+            raise NotImplementedError("SceneLin.run(graph=True): a scene with a ThermalEmission or SurfaceEmission source is not "
+                                      "captured (run it with graph=False or graph=None)")
         if graph:
             return self._run_graph(lanes, fold)
         return self._run_eager(lanes, fold)
@@ -593,13 +602,13 @@ class SceneLin(LinInputs):
         """Is there a thermal slot to run (a non-zero B_layer or Planck tables)?  Its scope limit is checked here, on host values,
         before anything is launched: every layer must scatter (the slot state the reference's forward run carries through
         non-scattering layers, CoreRT.ThermalSlot, has no linearized meaning)."""
-        if self.fwd.thermal_B is None and not self.nPlanck:
+        if not self.has_thermal:
             return False
         eps2 = 2 * np.finfo(self.FT).eps
         for iz, ly in enumerate(self.fwd.moments[0]["layers"]):
             if not ly["props"].max_tau_varpi > eps2:
-                raise NotImplementedError("rt_run (linearized): layer %d does not scatter; a ThermalEmission source needs a column "
-                                          "whose layers all scatter" % (iz + 1))
+                raise NotImplementedError("rt_run (linearized): layer %d does not scatter; a ThermalEmission or SurfaceEmission "
+                                          "source needs a column whose layers all scatter" % (iz + 1))
         return True
 
     def _run_graph(self, lanes, fold):
@@ -627,7 +636,7 @@ class SceneLin(LinInputs):
 
     def _run_eager(self, lanes: Optional[int] = None, fold: Optional[bool] = None):
         out = self._run_solar(lanes, fold)
-        if self.S > 0 and (self.fwd.thermal_B is not None or self.nPlanck):
+        if self.S > 0 and self.has_thermal:
             self._run_thermal()
         return out
 
@@ -657,8 +666,8 @@ class SceneLin(LinInputs):
                 self.T[:, :2, :].copy_(t0)
                 self.Rd[:self.P, :, :2, :].copy_(rd0[:self.P])
                 self.Td[:self.P, :, :2, :].copy_(td0[:self.P])
-                if self.nSIF:      # (the sub-scene has no Planck slot: its SIF slots follow its surface slots)
-                    o = self.P + self.nPlanck
+                if self.nSIF:      # (the sub-scene has no Planck or skin slot: its SIF slots follow its surface slots)
+                    o = self.P + self.nSrc
                     self.Rd[o:, :, :2, :].copy_(rd0[self.P:])
                     self.Td[o:, :, :2, :].copy_(td0[self.P:])
             for mom in self.fwd.moments:
@@ -951,7 +960,7 @@ class SceneLin(LinInputs):
         MS.surface_emission_response_(pol, self.qp, model.vza, model.vaz, weight, comp.R_pm, comp.T_mm, w["added_s"].r_mp, comps,
                                       up, dn)
         coef = self.sif_dot2[:, comps, :]                       # (nSIF, K, S)
-        o = self.P + self.nPlanck
+        o = self.P + self.nSrc
         w["Rd"][o:o + self.nSIF].add_(torch.einsum("kis,iscv->kscv", coef, up))
         w["Td"][o:o + self.nSIF].add_(torch.einsum("kis,iscv->kscv", coef, dn))
 
@@ -1001,8 +1010,26 @@ class SceneLin(LinInputs):
         mom = fwd.moments[0]
         if fwd.thermal_B is not None:
             self._thermal_lin_slot(mom)
-        if self.nPlanck:
+        if self.nSrc:
             self._planck_block(mom)
+
+    @property
+    def nSrc(self) -> int:
+        """The source-only slots of the thermal slot: nPlanck Planck tables, then nSkin skin tables."""
+        return self.nPlanck + self.nSkin
+
+    @property
+    def has_thermal(self) -> bool:
+        """Does this scene run a `:thermal` slot: a forward emission (a non-zero B_layer or B_surface) or a source-only slot?  The
+        one rule of every linearized driver -- a source that states neither (an all-zero SurfaceEmission, say) runs nothing."""
+        return self.fwd.thermal_B is not None or self.nSrc > 0
+
+    def source_tables(self):
+        """Per source-only slot the pair (B, B_surface) its forward slot runs on: (B_layer_dot[k], None) for the Planck tables, then
+        (a Planck table of 0 rows, B_surface_dot[k]) for the skin tables."""
+        none = torch.empty((0, self.S), dtype=self.dt, device=self.expk.device)
+        return ([(self.thermal_B_dot[k], None) for k in range(self.nPlanck)]
+                + [(none, self.surface_B_dot[k]) for k in range(self.nSkin)])
 
     def _thermal_lin_walk(self, mom, comp, cl, first, end, B, after_layer=None):
         """Layers first+1 .. end (1-based) of the linearized slot for the Planck table B ((rows, S), or None) into the thermal
@@ -1031,12 +1058,21 @@ class SceneLin(LinInputs):
                 after_layer(iz + 1, comp, cl)
 
     def _thermal_lin_surface(self, mom):
-        """The slot's surface layers: those of the solar walk without their beam terms (surface emission is a separate source
-        type: what _surface_lin injected for SurfaceSIF is zeroed with the beam term, the emission counts once, in the solar slot)."""
+        """The slot's surface layers: those of the solar walk without their beam terms (what _surface_lin injected for SurfaceSIF
+        is zeroed with the beam term: that emission counts once, in the solar slot), then the scene's SurfaceEmission: the forward
+        emission in j0- and, in Kirchhoff mode, its derivative in the surface slots of ap_J0- (vsm_surface_emission_lin; the layer
+        slots need nothing here, the linearized interaction differentiates the propagation of the forward j0-).  DESIGN 4.18."""
         t = self._thermal_state()
-        self._surface_lin(mom, t["added_s"], t["als"], t["F0"])
-        torch._foreach_zero_([t["added_s"].j0_p, t["added_s"].j0_m, t["als"].ap_J0_p, t["als"].ap_J0_m])
-        return t["added_s"], t["als"]
+        fwd, added_s, als = self.fwd, t["added_s"], t["als"]
+        self._surface_lin(mom, added_s, als, t["F0"])
+        torch._foreach_zero_([added_s.j0_p, added_s.j0_m, als.ap_J0_p, als.ap_J0_m])
+        if (CR.surface_emission_contribute_(fwd.surface_B, fwd.surface_emissivity, added_s, self.pol.n, mom["m"])
+                and fwd.surface_emissivity is None):
+            isurf = self.layout.surface_index(0)
+            al_ = als.cstruct()
+            _lib.call("vsm_surface_emission_lin", self.dt, self.N, self.pol.n, self.S, mom["m"], CR._ptr(fwd.surface_B), isurf,
+                      self.P - isurf, C.byref(al_), CR._stream_ptr())
+        return added_s, als
 
     def _thermal_lin_slot(self, mom, after_layer=None, post=True):
         """Walk layers 1 .. Nz (_thermal_lin_walk), surface, post-process into R, T, Rdot, Tdot (post=False: the composite is left
@@ -1052,15 +1088,16 @@ class SceneLin(LinInputs):
                                     self.R, self.T, self.Rd, self.Td)
 
     def _planck_block(self, mom):
-        """The slot is linear in B: dR / dx_k is the FORWARD thermal slot (CoreRT.ThermalSlot, fused layer kernels included) of
-        B := B_layer_dot[k], post-processed into slot P + k of Rdot / Tdot."""
+        """The slot is linear in B and in B_surface: dR / dx_k is the FORWARD thermal slot (CoreRT.ThermalSlot, fused layer kernels
+        included) of B := B_layer_dot[k] over a boundary that does not emit, or, for a skin table, of an empty Planck table over
+        B_surface := B_surface_dot[k] (source_tables), post-processed into slot P + k of Rdot / Tdot."""
         fwd, P = self.fwd, self.P
         weight = float(CR.fourier_weight(self.FT, 0))
         th = fwd.thermal_slot()
-        for k in range(self.nPlanck):
+        for k, (B, B_surface) in enumerate(self.source_tables()):
             th.begin(mom)
-            th.walk(mom, th.comp, 0, fwd.Nz, self.thermal_B_dot[k])
-            th.surface(mom)
+            th.walk(mom, th.comp, 0, fwd.Nz, B)
+            th.surface(mom, B_surface)
             th.finish(mom, weight, self.Rd[P + k], self.Td[P + k])
 
     def results_host(self):
@@ -1102,6 +1139,11 @@ def rt_run_lin(model: H.RTModel, lin_model: H.LinModel, NAer: int, NGas: int, NS
     only, no surface emission).  ThermalEmission(B_layer_dot=[nPlanck, rows, nSpec]) appends nPlanck Planck (temperature) slots
     after the surface slots: Nparams = 7 NAer + NGas + NSurf + nPlanck <= 64, slot k of the block = d/dx_k for B_layer_dot[k] =
     dB_layer / dx_k.  Not supported with a thermal source: a column with a non-scattering layer (NotImplementedError).
+
+    SurfaceEmission(B_surface=..., B_surface_dot=...): the emission of the thermal slot's lower boundary, with or without
+    a ThermalEmission; in Kirchhoff mode the surface slots carry the derivative of the emissivity.  B_surface_dot [nSkin, nSpec]
+    appends nSkin skin slots after the Planck slots (slot k = d/dx_k for B_surface_dot[k] = dB_surface / dx_k) and before the SIF
+    slots: Nparams | nPlanck | nSkin | nSIF, at most 64 in all.
 
     SurfaceSIF(SIF0, SIF0_dot) (DESIGN 4.13): R, T and every slot carry the emission's share (m = 0, Lambertian surface);
     SIF0_dot [nSIF, nStokes, nSpec] appends nSIF slots after the Planck slots, slot k of the block = d/dx_k for SIF0_dot[k] =

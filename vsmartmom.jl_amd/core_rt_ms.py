@@ -218,8 +218,8 @@ class LevelPlan:
 
 def _validate(model: H.RTModel, sensor_levels, thermal: bool = False, sif: bool = False,
               who: str = "rt_run_multisensor") -> LevelPlan:
-    """The level plan of a run.  thermal: ThermalEmission is accepted beside (or instead of) SolarBeam -- rt_run_multisensor's
-    thermal=True; the Raman and linearized runs leave it off.  sif: SurfaceSIF is accepted too (CoreRT.rt_run_multisensor alone:
+    """The level plan of a run.  thermal: ThermalEmission and SurfaceEmission are accepted beside (or instead of) SolarBeam --
+    rt_run_multisensor's thermal=True; the Raman run leaves it off.  sif: SurfaceSIF is accepted too (CoreRT.rt_run_multisensor alone:
     the Raman and the linearized multi-sensor run refuse it with NotImplementedError, before anything is launched)."""
     Nz = int(np.asarray(model.tau_rayl).shape[1])
     levels = []
@@ -234,15 +234,18 @@ def _validate(model: H.RTModel, sensor_levels, thermal: bool = False, sif: bool 
     srcs = tuple(model.sources) if model.sources is not None else (H.SolarBeam(),)
     if not sif and any(isinstance(s, H.SurfaceSIF) for s in srcs):
         raise NotImplementedError("%s: SurfaceSIF is not a source of this run (CoreRT.rt_run_multisensor takes it)" % who)
-    accepted = ((H.SolarBeam, H.ThermalEmission) if thermal else (H.SolarBeam,)) + ((H.SurfaceSIF,) if sif else ())
+    accepted = (((H.SolarBeam, H.ThermalEmission, H.SurfaceEmission) if thermal else (H.SolarBeam,))
+                + ((H.SurfaceSIF,) if sif else ()))
     other = [s for s in srcs if not isinstance(s, accepted)]
     if other or not srcs:
         if thermal:
-            raise _lib.VSMError("rt_run_multisensor(thermal=True): SolarBeam and ThermalEmission are the sources of a multi-sensor "
-                                "run; got %r" % (other[0] if other else None,))
+            raise _lib.VSMError("rt_run_multisensor(thermal=True): SolarBeam, ThermalEmission and SurfaceEmission are the sources of "
+                                "a multi-sensor run; got %r" % (other[0] if other else None,))
         raise _lib.VSMError("rt_run_multisensor: SolarBeam is the only source of a multi-sensor run (the prototype passes F0 alone, "
-                            "rt_kernel_multisensor.jl:21; CoreRT.rt_run_multisensor(..., thermal=True) also takes ThermalEmission); "
-                            "got %r" % (other[0] if other else None,))
+                            "rt_kernel_multisensor.jl:21; CoreRT.rt_run_multisensor(..., thermal=True) also takes ThermalEmission "
+                            "and SurfaceEmission); got %r" % (other[0] if other else None,))
+    if thermal:
+        H.surface_emission_of(model)      # (its shape against the model, before anything is launched)
     distinct = sorted(set(levels))
     interior = [l for l in distinct if 0 < l < Nz]
     return LevelPlan(levels, distinct, interior, interior + ([Nz] if Nz in distinct else []), interior[1:] + [Nz], Nz)
@@ -484,7 +487,9 @@ def rt_run_multisensor(model: H.RTModel, sensor_levels, streams: bool = False, t
     dw per level are the sum of the solar and the thermal slot, as rt_run's R_SFI / T_SFI are, level 0 again rt_run's result bit
     for bit; with streams=True the level vectors of m = 0 are the sum as well.  Columns with a non-scattering layer are refused
     as before, so the slot-state behaviour of such layers never arises here and
-    ThermalEmission.reset_slot_in_nonscattering_layers has no effect.  The thermal slot has no surface emission of its own.
+    ThermalEmission.reset_slot_in_nonscattering_layers has no effect.  SurfaceEmission (thermal=True only; VSMError without it)
+    is the emission of the slot's lower boundary: every bottom of the slot is built upward from the emitting surface layer, so every
+    level carries it, level Nz included (there the bottom is the surface layer alone and c is its j0-); DESIGN.md §4.18.
 
     SurfaceSIF (with or without thermal=True): injected into the solar slot's surface layer at m = 0 as rt_run injects it
     (rt_run_multisensor.jl:140); every bottom composite is built upward from that layer, so every level carries the emission,

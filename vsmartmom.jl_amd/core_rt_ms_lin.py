@@ -128,8 +128,8 @@ def _run_scene(sc: CL.SceneLin, plan: MS.LevelPlan, streams: bool, sink: Optiona
     dev = sc.R.device
     nV = len(model.vza)
     z = lambda *sh: torch.zeros(sh, dtype=dt, device=dev)
-    thermal = sc.fwd.thermal_B is not None or sc.nPlanck > 0
-    Pa = P + sc.nPlanck      # (the Planck slots follow the parameter slots; the solar level calls fill the first P)
+    thermal = sc.has_thermal
+    Pa = P + sc.nSrc         # (the Planck and skin slots follow the parameter slots; the solar level calls fill the first P)
     out = {} if sink is not None else {l: [z(S, pol.n, nV), z(S, pol.n, nV), z(Pa, S, pol.n, nV), z(Pa, S, pol.n, nV)]
                                        for l in plan.distinct if l != 0}
     out[0] = [sc.R, sc.T, sc.Rd, sc.Td]
@@ -207,7 +207,7 @@ def _run_thermal(sc: CL.SceneLin, plan: MS.LevelPlan, segs, out, full, sink: Opt
     sink: see LevelSink."""
     model, fwd, dt = sc.model, sc.fwd, sc.dt
     pol, qp = sc.pol, sc.qp
-    N, S, P, pl, K = sc.N, sc.S, sc.P, sc.pl, sc.nPlanck
+    N, S, P, pl, K = sc.N, sc.S, sc.P, sc.pl, sc.nSrc      # (K source-only slots: the Planck tables, then the skin tables)
     dev = sc.R.device
     mom = fwd.moments[0]
     weight = float(MS.fourier_weight(sc.FT, 0))
@@ -222,20 +222,19 @@ def _run_thermal(sc: CL.SceneLin, plan: MS.LevelPlan, segs, out, full, sink: Opt
         for m_, f in full.items():
             full[m_] = {l: (vs[0], vs[1], pad(vs[2]), pad(vs[3])) for l, vs in f.items()}
         fv = full[0]
-    # 4. the Planck sources: per table the forward slot of B := B_layer_dot[k], cut at the plan's levels as DESIGN 4.8d cuts it
+    # 4. the Planck and skin sources: per table the forward slot of B := B_layer_dot[k] (or of B_surface := B_surface_dot[k] under an
+    # empty Planck table), cut at the plan's levels as DESIGN 4.8d cuts it
     if K:
         th_segs = [CR.make_composite_layer(sc.FT, sc.arch, (N, N), S) for _ in range(2 if plan.interior else 0)]
         th = fwd.thermal_slot()
         try:
-            for k in range(K):
-                B = sc.thermal_B_dot[k]
+            for k, (B, B_surface) in enumerate(sc.source_tables()):
                 th.begin(mom)
                 th.walk(mom, th.comp, 0, fwd.Nz, B, after={l: (lambda c, l=l: src[l][0][k].copy_(c.J0_p)) for l in plan.tops_at})
-                surf = th.surface(mom)
+                surf = th.surface(mom, B_surface)
 
-                def keep_bottom(l, seg):
-                    if seg is not None:      # (level Nz: the surface layer alone emits nothing, c_k = 0)
-                        src[l][1][k].copy_(seg.J0_m)
+                def keep_bottom(l, seg):     # (level Nz: the surface layer alone, c_k = its j0-: 0 unless table k is a skin table)
+                    src[l][1][k].copy_(surf.j0_m if seg is None else seg.J0_m)
                 MS.walk_levels(plan, th_segs, lambda seg, first, end: th.walk(mom, seg, first, end, B),
                                lambda seg: CR.interaction_(mom["iface_surface"], seg, surf, oplevel=True, work=fwd.work),
                                lambda seg, bot, first, end: CR.interaction_("11", seg, MS._CompositeAsAdded(bot), oplevel=True,
@@ -299,7 +298,8 @@ def bytes_per_point(N: int, P: int, pl: int, Nz: int, n_tops: int, segments: boo
     the thermal slot keeps beside them (m = 0 only, on the parent's N): its own tops, R and Rdot included ((1 + pl)(N^2 + N) each,
     while the solar tops of the last moment are still alive), its linearized added / composite / surface layers, the forward
     slot's three layers and two segment composites (the Planck walks), the Planck source vectors of every level, the Planck
-    slots of the outputs and the padded level vectors."""
+    slots of the outputs and the padded level vectors.  nPlanck counts every source-only slot of the thermal slot, the Planck
+    tables and the skin tables of a SurfaceEmission alike (SceneLin.nSrc; thermal_estimate(model) gives both arguments)."""
     layer = (1 + P) * (4 * N * N + 2 * N)
     elems = (n_tops * (1 + pl) * (N * N + N) + (2 * layer if segments else 0) + 3 * layer + Nz * (8 + 3 * P)
              + n_levels * 2 * (1 + P) * n_stokes * nV + 4 * (1 + P) * N)
@@ -308,6 +308,18 @@ def bytes_per_point(N: int, P: int, pl: int, Nz: int, n_tops: int, segments: boo
         elems += (n_tops * (1 + pl) * (N * N + N) + 3 * layer + (5 if segments else 3) * fwd_layer * (1 if nPlanck else 0)
                   + n_levels * 2 * nPlanck * (N + n_stokes * nV) + Nz * (1 + nPlanck) + 4 * (1 + P + nPlanck) * N)
     return elems * itemsize
+
+
+def thermal_estimate(model: H.RTModel) -> dict:
+    """The thermal keywords of bytes_per_point (here and in core_rt_flux_lin.py) for a model, on the safe side: thermal=True for
+    any ThermalEmission or SurfaceEmission, nPlanck = the Planck tables + the skin tables, SceneLin.nSrc.  {} for a model without
+    the sources, which takes the estimate as it always was."""
+    th = [s_ for s_ in (model.sources or ()) if isinstance(s_, H.ThermalEmission)]
+    se = H.surface_emission_of(model)
+    if not th and se is None:
+        return {}
+    Bd = getattr(th[0], "B_layer_dot", None) if th else None
+    return dict(thermal=True, nPlanck=(0 if Bd is None else int(Bd.shape[0])) + (se.nSkin if se is not None else 0))
 
 
 def rt_run_multisensor(model: H.RTModel, lin_model: H.LinModel, NAer: int, NGas: int, NSurf: int, sensor_levels, streams: bool = False,
@@ -333,8 +345,12 @@ def rt_run_multisensor(model: H.RTModel, lin_model: H.LinModel, NAer: int, NGas:
     is the sum of the solar and the thermal derivative, slot Nparams + k is d/dx_k for B_layer_dot[k] (the thermal part alone),
     after the surface slots as rt_run_lin places them; Nparams + nPlanck <= 64.  The slot exists for m = 0 only; with
     streams=True the derivative level vectors of every moment carry all Nparams + nPlanck slots (zero Planck slots for m > 0).
-    Level 0 is again SceneLin.run(lanes=1, fold=False) bit for bit.  No surface emission: SurfaceSIF raises NotImplementedError
-    before anything is launched (rt_run_lin takes it).  DESIGN.md §4.8e.
+    Level 0 is again SceneLin.run(lanes=1, fold=False) bit for bit.  SurfaceSIF raises NotImplementedError before anything is
+    launched (rt_run_lin takes it).  DESIGN.md §4.8e.
+
+    SurfaceEmission (with or without B_surface_dot, with or without a ThermalEmission) is the emission of the slot's
+    lower boundary at every level, level Nz included; its nSkin skin slots follow the Planck slots as further source-only slots:
+    uw_dot / dw_dot are [nVZA, nStokes, nSpec, Nparams + nPlanck + nSkin].
 
     Columns with a non-scattering layer raise NotImplementedError; N <= 128."""
     plan = MS._validate(model, sensor_levels, thermal=True, who="rt_run_multisensor (linearized)")
@@ -355,11 +371,8 @@ def rt_run_multisensor(model: H.RTModel, lin_model: H.LinModel, NAer: int, NGas:
         layout = H.ParameterLayout(n_aerosols=NAer, n_gases=NGas, n_surface=NSurf)
         P, pl = layout.n_total, layout.n_layer_params
         isz, nV = np.dtype(model.float_type).itemsize, len(model.vza)
-        th = [s_ for s_ in (model.sources or ()) if isinstance(s_, H.ThermalEmission)]
-        kw = {}
-        if th:     # (a model without the source takes the call as it always was)
-            kw = dict(thermal=True, nPlanck=int(th[0].B_layer_dot.shape[0]))
-        per = bytes_per_point(N, P, pl, plan.Nz, plan.n_tops, bool(plan.interior), len(plan.distinct), pol.n, nV, isz, **kw)
+        per = bytes_per_point(N, P, pl, plan.Nz, plan.n_tops, bool(plan.interior), len(plan.distinct), pol.n, nV, isz,
+                              **thermal_estimate(model))
         if CL.REDUCE_M0 and pol.n >= 3:     # (the Stokes_IQ scene of m = 0, where it applies)
             per += bytes_per_point(2 * qp.Nquad, P, pl, plan.Nz, plan.n_tops, bool(plan.interior), len(plan.distinct), 2, nV, isz)
         free, _total = torch.cuda.mem_get_info()

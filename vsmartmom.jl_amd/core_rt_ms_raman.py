@@ -175,6 +175,9 @@ def _run_scene(sc: RR.SceneRRS, plan: MS.LevelPlan, streams: bool):
 
 
 def _validate(RS_type: RR.RRS, model: H.RTModel, sensor_levels, iBand: int):
+    if any(isinstance(s_, H.SurfaceEmission) for s_ in (model.sources or ())):
+        raise NotImplementedError("rt_run_multisensor (RRS): SurfaceEmission is not a source of the Raman runs "
+                                  "(CoreRT.rt_run_multisensor(..., thermal=True) takes it)")
     plan = MS._validate(model, sensor_levels, who="rt_run_multisensor (RRS)")
     if iBand != 1:
         raise _lib.VSMError("rt_run_multisensor (RRS): single-band models only (iBand = 1), got %r" % (iBand,))
@@ -200,7 +203,8 @@ def rt_run_multisensor(RS_type: RR.RRS, model: H.RTModel, sensor_levels, iBand: 
     max_points: walk the recipient axis in blocks of at most that many points, each extended by the halo of max|shift| donor
     points (bit-identical to the one-pass run: a recipient reads only elastic fields of its donors, its level vectors included);
     None = as many as fit the device (raman_bytes_per_point with the kept tops and the two segment composites).
-    SolarBeam sources only (SurfaceSIF: NotImplementedError, before anything is launched -- CoreRTRaman.rt_run takes it); N <= 128."""
+    SolarBeam sources only (SurfaceSIF: NotImplementedError, before anything is launched -- CoreRTRaman.rt_run takes it;
+    SurfaceEmission: NotImplementedError as well); N <= 128."""
     plan = _validate(RS_type, model, sensor_levels, iBand)
     S_full = int(model.tau_rayl.shape[0])
     shifts = np.asarray(RS_type.i_lambda1lambda0).ravel()

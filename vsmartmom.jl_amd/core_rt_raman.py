@@ -186,6 +186,9 @@ class SceneRRS:
         CR._require_gpu(arch)
         if iBand != 1:
             raise _lib.VSMError("single-band models only (iBand = 1)")
+        # (the Raman drivers run no `:thermal` slot: a SurfaceEmission is refused, never dropped)
+        if any(isinstance(s_, H.SurfaceEmission) for s_ in (model.sources or ())):
+            raise NotImplementedError("rt_run (RRS): SurfaceEmission is not a source of the Raman runs (CoreRT.rt_run takes it)")
         self.model, self.rs, self.arch, self.FT = model, RS_type, arch, FT
         pol, qp = model.polarization_type, model.quad_points
         S_full, Nz = model.tau_rayl.shape

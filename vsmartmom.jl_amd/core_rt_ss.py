@@ -57,6 +57,8 @@ def _refuse_sources(model: H.RTModel):
             raise NotImplementedError("rt_run_ss: SolarBeam is the only source of a single-scattering run (got ThermalEmission)")
         if isinstance(s_, H.SurfaceSIF):
             raise NotImplementedError("rt_run_ss: SolarBeam is the only source of a single-scattering run (got SurfaceSIF)")
+        if isinstance(s_, H.SurfaceEmission):
+            raise NotImplementedError("rt_run_ss: SolarBeam is the only source of a single-scattering run (got SurfaceEmission)")
 
 
 class SceneSS:

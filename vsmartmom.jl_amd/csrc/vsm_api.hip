@@ -1034,6 +1034,29 @@ VSM_LIN_API(float, f32)
                 "surface_sif: bad argument (N a multiple of n_stokes in 1..4, sif [n_stokes][S], j0_m)");              \
     return surface_sif<T>(N, n_stokes, S, sif, cvt_added<T>(added_surface), as_stream(stream));                        \
   }                                                                                                                    \
+  extern "C" int vsm_surface_emission_##SFX(int N, int n_stokes, int S, int m, const T* B_surface,                     \
+                                            const T* emissivity, const vsm_added_##SFX* added_surface, void* stream) { \
+    int rc;                                                                                                            \
+    if ((rc = check_added(added_surface))) return rc;                                                                  \
+    VSM_REQUIRE(N > 0 && n_stokes >= 1 && n_stokes <= 4 && N % n_stokes == 0 && S >= 0 && m >= 0 &&                    \
+                    (S == 0 || B_surface) &&                                                                           \
+                    (added_surface->mat_stride == 0 || added_surface->mat_stride == (long long)N * N),                 \
+                "surface_emission: bad argument (N a multiple of n_stokes in 1..4, B_surface [S], mat_stride 0 or N*N)");\
+    if (m > 0) return VSM_OK;                                                                                          \
+    return surface_emission<T>(N, n_stokes, S, B_surface, emissivity, cvt_added<T>(added_surface), as_stream(stream)); \
+  }                                                                                                                    \
+  extern "C" int vsm_surface_emission_lin_##SFX(int N, int n_stokes, int S, int m, const T* B_surface, int isurf,      \
+                                                int K, const vsm_added_lin_##SFX* al, void* stream) {                  \
+    int rc;                                                                                                            \
+    if ((rc = check_al(al))) return rc;                                                                                \
+    VSM_REQUIRE(N > 0 && n_stokes >= 1 && n_stokes <= 4 && N % n_stokes == 0 && S >= 0 && m >= 0 &&                    \
+                    (S == 0 || B_surface) && K >= 0 && isurf >= 0 && isurf + K <= al->P &&                             \
+                    (al->mat_stride == 0 || al->mat_stride == (long long)N * N),                                       \
+                "surface_emission_lin: bad argument (N a multiple of n_stokes in 1..4, B_surface [S], the surface slots "\
+                "[isurf, isurf + K) within P, mat_stride 0 or N*N)");                                                  \
+    if (m > 0) return VSM_OK;                                                                                          \
+    return surface_emission_lin<T>(N, n_stokes, S, isurf, K, B_surface, cvt_al<T>(al), as_stream(stream));             \
+  }                                                                                                                    \
   extern "C" int vsm_interaction_hdrf_##SFX(const vsm_quad_##SFX* q, int S, int m, const vsm_composite_##SFX* comp,    \
                                             const vsm_added_##SFX* added_surface, T* hdr_J, T* bhr_uw, T* bhr_dw,      \
                                             void* stream) {                                                            \

@@ -132,6 +132,12 @@ int brdf_surface_lin_multi(const quad<T>& q, int S, int m, const T* rho, const T
 // SurfaceSIF: j0- += 2 sif on the rows of every stream (sif [n_stokes][S]); nothing else of the surface layer is touched
 template <typename T>
 int surface_sif(int N, int ns, int S, const T* sif, const added<T>& a, hipStream_t st);
+// SurfaceEmission: j0- += 2 pi B eps (eps from the layer's own r-+, or emissivity [S] on the I rows), and the derivative of the
+// Kirchhoff form in the surface slots [isurf, isurf + K) of the linearized surface layer
+template <typename T>
+int surface_emission(int N, int ns, int S, const T* B, const T* emissivity, const added<T>& a, hipStream_t st);
+template <typename T>
+int surface_emission_lin(int N, int ns, int S, int isurf, int K, const T* B, const added_lin<T>& al, hipStream_t st);
 template <typename T>
 int interaction_hdrf(const quad<T>& q, int S, int m, const composite<T>& c, const added<T>& a, T* hdr_J, T* bhr_uw, T* bhr_dw,
                      hipStream_t st);

@@ -925,8 +925,80 @@ int surface_sif(int N, int ns, int S, const T* sif, const added<T>& a, hipStream
   return VSM_OK;
 }
 
+// ---- SurfaceEmission: thermal emission of the lower boundary (ours: the reference has no such source).  At m = 0 the surface
+// layer's j0- gains 2 pi B_surface[s] eps[row, s].  Kirchhoff mode (emissivity == nullptr):
+//   eps[i n + c, s] = delta_{c,0} - sum_j r-+[i n + c, j n, s]
+// -- the sum over the I column of every stream j is the directional-hemispherical reflectance of row (i, c) for unpolarized
+// isotropic illumination, since every builder of this file (and the Lambertian ones) folds 2 mu_j w_j into column j at m = 0; an
+// isotropic unpolarized field B therefore leaves the boundary as (B, 0, 0, 0) in every row, emitted plus reflected.  The weights sit
+// on the columns, so the zero-weight SZA / VZA rows get their emissivity from the same sum.  Explicit mode: eps = delta_{c,0}
+// emissivity[s].  One thread per (row, point), the row axis fastest: r-+ is column-major per point, so the threads of a point read
+// consecutive addresses at every fixed j, and j0- [N, 1, S] is read and written in consecutive addresses.  The matrices are one
+// shared block (mat_stride 0) or one per point (N * N).  A row reduction of N / n terms, once per slot walk: no LDS, no MFMA. ----
+template <typename T>
+__global__ void __launch_bounds__(256) k_surface_emission(int N, int ns, long long S, const T* __restrict__ B,
+                                                          const T* __restrict__ emissivity, const T* __restrict__ r_mp,
+                                                          long long mat_stride, T* __restrict__ j0_m) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (long long)N * S) return;
+  const long long s = e / N;
+  const int row = (int)(e - s * N);
+  const bool irow = row % ns == 0;
+  T eps;
+  if (emissivity) {
+    eps = irow ? emissivity[s] : T(0);
+  } else {
+    const T* r = r_mp + mat_stride * s + row;
+    T refl = T(0);
+    for (int j = 0; j < N; j += ns) refl += r[(long long)j * N];
+    eps = (irow ? T(1) : T(0)) - refl;
+  }
+  j0_m[e] += (T(6.283185307179586476925286766559) * B[s]) * eps;
+}
+template <typename T>
+int surface_emission(int N, int ns, int S, const T* B, const T* emissivity, const added<T>& a, hipStream_t st) {
+  if (S <= 0) return VSM_OK;
+  const long long tot = (long long)N * S;
+  hipLaunchKernelGGL(k_surface_emission<T>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, N, ns, (long long)S, B, emissivity,
+                     a.r_mp, a.mat_stride, a.j0_m);
+  VSM_LAUNCH_CHECK("k_surface_emission");
+  return VSM_OK;
+}
+// The derivative of the Kirchhoff emission in the surface slots isurf .. isurf + K - 1 of the linearized surface layer:
+//   ap_J0-[p][i n + c, s] += -2 pi B_surface[s] sum_j ap_r-+[p][i n + c, j n, s]
+// (an explicit emissivity depends on no parameter: no call).  One thread per (row, point, slot), the row axis fastest; the stacks
+// are [N, N, S | 1, P] / [N, 1, S, P], the blocks of a slot shared (mat_stride 0) or per point as in the forward layer.
+template <typename T>
+__global__ void __launch_bounds__(256) k_surface_emission_lin(int N, int ns, long long S, int isurf, int K, const T* __restrict__ B,
+                                                              const T* __restrict__ ap_r_mp, long long mat_stride,
+                                                              T* __restrict__ ap_J0_m) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  const long long NS = (long long)N * S;
+  if (e >= NS * K) return;
+  const int p = isurf + (int)(e / NS);
+  const long long x = e - (e / NS) * NS;
+  const long long s = x / N;
+  const int row = (int)(x - s * N);
+  const long long slot = mat_stride ? mat_stride * S : (long long)N * N;
+  const T* r = ap_r_mp + slot * p + mat_stride * s + row;
+  T refl = T(0);
+  for (int j = 0; j < N; j += ns) refl += r[(long long)j * N];
+  ap_J0_m[NS * p + x] -= (T(6.283185307179586476925286766559) * B[s]) * refl;
+}
+template <typename T>
+int surface_emission_lin(int N, int ns, int S, int isurf, int K, const T* B, const added_lin<T>& al, hipStream_t st) {
+  if (S <= 0 || K <= 0) return VSM_OK;
+  const long long tot = (long long)N * S * K;
+  hipLaunchKernelGGL(k_surface_emission_lin<T>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, N, ns, (long long)S, isurf, K, B,
+                     al.ap_r_mp, al.mat_stride, al.ap_J0_m);
+  VSM_LAUNCH_CHECK("k_surface_emission_lin");
+  return VSM_OK;
+}
+
 #define VSM_INST_SURF(T)                                                                                                     \
   template int surface_sif<T>(int, int, int, const T*, const added<T>&, hipStream_t);                                        \
+  template int surface_emission<T>(int, int, int, const T*, const T*, const added<T>&, hipStream_t);                          \
+  template int surface_emission_lin<T>(int, int, int, int, int, const T*, const added_lin<T>&, hipStream_t);                  \
   template int coxmunk_reflectance<T>(const cm_surf<T>&, int, int, const T*, int, int, const T*, const T*, T*, T*, hipStream_t); \
   template int brdf_surface<T>(const quad<T>&, int, int, const T*, const T*, const added<T>&, hipStream_t);                   \
   template int lambertian_surface_spectral<T>(const quad<T>&, int, int, const T*, const T*, const added<T>&, hipStream_t);    \

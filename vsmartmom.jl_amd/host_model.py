@@ -627,6 +627,73 @@ class SurfaceSIF:
                           None if self.SIF0_dot is None else cut(self.SIF0_dot, self.SIF0_dot.ndim == 3))
 
 
+class SurfaceEmission:
+    """Thermal emission of the lower boundary (ours: the reference has no surface thermal source).
+    `SurfaceEmission(B_surface=B)` with B [nSpec], the Planck radiance of the skin in the units of ThermalEmission.B_layer, or
+    `SurfaceEmission(T_surface, nu)`, which evaluates planck_spectrum_wn.  At Fourier moment m = 0 the surface layer of the
+    `:thermal` slot emits 2 pi B_surface eps into j0-.
+
+    `emissivity` None (default): Kirchhoff, eps of every row = [I row] - the directional-hemispherical reflectance of the run's own
+    surface layer, polarizing surfaces included.  A scalar or an [nSpec] array in [0, 1]: isotropic unpolarized emission
+    emissivity * B_surface, whatever the surface reflects.
+
+    `B_surface_dot` [nSkin, nSpec] (default None; one [nSpec] table counts as nSkin = 1): the derivative tables dB_surface / dx_k
+    -- dB / dT_skin makes slot k the skin-temperature Jacobian.  Only the linearized runs read them (the skin slots, after the
+    Planck slots of Rdot / Tdot)."""
+
+    def __init__(self, T_surface=None, nu=None, B_surface=None, emissivity=None, B_surface_dot=None):
+        from ._lib import VSMError
+        if B_surface is None:
+            if T_surface is None or nu is None:
+                raise VSMError("SurfaceEmission: give B_surface [nSpec], or T_surface and the wavenumber grid nu")
+            B_surface = planck_spectrum_wn(float(T_surface), nu)
+        B_surface = np.asarray(B_surface, dtype=np.float64)
+        if B_surface.ndim != 1:
+            raise VSMError("SurfaceEmission: B_surface must be [nSpec], got shape %s" % (B_surface.shape,))
+        self.B_surface = B_surface
+        if emissivity is not None:
+            emissivity = np.asarray(emissivity, dtype=np.float64)
+            if emissivity.ndim == 0:
+                emissivity = np.full(B_surface.shape, float(emissivity))
+            if emissivity.shape != B_surface.shape:
+                raise VSMError("SurfaceEmission: emissivity must be a scalar or [nSpec] = [%d], got shape %s"
+                               % (B_surface.shape[0], emissivity.shape))
+            if not np.all((emissivity >= 0) & (emissivity <= 1)):      # (a NaN fails here too)
+                raise VSMError("SurfaceEmission: emissivity outside [0, 1]")
+        self.emissivity = emissivity
+        if B_surface_dot is not None:
+            B_surface_dot = np.asarray(B_surface_dot, dtype=np.float64)
+            if B_surface_dot.ndim == 1:
+                B_surface_dot = B_surface_dot[None]
+            if B_surface_dot.ndim != 2:
+                raise VSMError("SurfaceEmission: B_surface_dot must be [nSkin, nSpec], got %d dimensions" % B_surface_dot.ndim)
+            if B_surface_dot.shape[1] != B_surface.shape[0]:
+                raise VSMError("SurfaceEmission: B_surface_dot has %d spectral points, B_surface %d"
+                               % (B_surface_dot.shape[1], B_surface.shape[0]))
+        self.B_surface_dot = B_surface_dot
+
+    @property
+    def nSkin(self) -> int:
+        return 0 if self.B_surface_dot is None else int(self.B_surface_dot.shape[0])
+
+    def check(self, nSpec: int):
+        """VSMError unless the tables have the model's spectral length."""
+        from ._lib import VSMError
+        if self.B_surface.shape[0] != nSpec:
+            raise VSMError("SurfaceEmission: B_surface has %d spectral points, the model %d" % (self.B_surface.shape[0], nSpec))
+
+
+def surface_emission_of(model) -> Optional[SurfaceEmission]:
+    """The SurfaceEmission of model.sources, checked against the model's spectral axis (None without one; VSMError for two)."""
+    from ._lib import VSMError
+    se = [s_ for s_ in (model.sources or ()) if isinstance(s_, SurfaceEmission)]
+    if len(se) > 1:
+        raise VSMError("model.sources holds %d SurfaceEmission sources (one lower boundary: at most one)" % len(se))
+    if se:
+        se[0].check(int(np.asarray(model.tau_rayl).shape[0]))
+    return se[0] if se else None
+
+
 @dataclass
 class RTModel:
     """The fields of the reference's RTModel that rt_run consumes on this path (one band)."""

@@ -16,7 +16,7 @@ Units.  Path 1 carries 1 / (4 pi) and path 2 albedo / pi explicitly; CoreRT carr
 path 1 + path 2 with constant 1 in every Stokes row (tests/test_oracle_exact_ss.py), so the back-correction
 adds straight onto an rt_run radiance computed with F0 = e1.  I0 passes through for any other solar scaling; nothing is rescaled.
 
-Sources.  Every path here is SOLAR single scattering: model.sources is not read.  A ThermalEmission or SurfaceSIF source of the model
+Sources.  Every path here is SOLAR single scattering: model.sources is not read.  A ThermalEmission, SurfaceSIF or SurfaceEmission source of the model
 is ignored on purpose -- the emission is no part of the first-order solar field, and the back-correction of a thermal or SIF run
 (exact - truncated solar single scattering, added onto that run's radiance) is legitimate.
 
