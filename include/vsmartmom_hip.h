@@ -908,8 +908,8 @@ int vsm_postprocess_vza_ie_f32(int N, int n_stokes, int S, int K, int nV, const 
  * ALONE as the bottom (the prototype never initialises that composite: a documented deviation).
  * Outputs: uw / dw [nV,n_stokes,S] are ACCUMULATED, R[v,k,s] += w[v,k] * level[row0[v]+k, s], with row0_h / w_h exactly as in
  * vsm_postprocess_vza (the same rows for uw and dw).  dw_full / uw_full (nullable, [N,1,S]): the level vectors at all streams.
- * N <= 128: one fused kernel (MFMA product into LDS, Gauss-Jordan with the pivot rule of vsm_batch_inv, mat-vec, VZA rows; work
- * may be NULL); N > 128: the operator-level twin, which needs work = vsm_level_radiance_work_elems(N, S) elements.
+ * N <= 128: one fused kernel, that of vsm_level_radiance_src_* with one source (MFMA product into LDS, Gauss-Jordan with the pivot
+ * rule of vsm_batch_inv, mat-vec, VZA rows; work may be NULL); N > 128: the operator-level twin, which needs work = vsm_level_radiance_work_elems(N, S) elements.
  * An exactly zero pivot raises VSM_DEVSTAT_SINGULAR, a NaN / Inf in [I - A B | a + A c] VSM_DEVSTAT_NONFINITE (fused path). */
 size_t vsm_level_radiance_work_elems(int N, int S);
 int vsm_level_radiance_f64(int N, int n_stokes, int S, int nV, const int* row0_h, const double* w_h, const double* top_R_pm,
@@ -937,8 +937,8 @@ int vsm_level_radiance_oplevel_f32(int N, int n_stokes, int S, int nV, const int
  * product that forms the system), A = top_R_pm, B = bot_R_mp / bot_stride as in vsm_level_radiance_*.  Outputs: the SUM over k:
  * its VZA rows ACCUMULATED into uw / dw [nV,n_stokes,S] (row0_h / w_h as in vsm_postprocess_vza), dw_full / uw_full (nullable,
  * [N,1,S]) the summed level vectors.  1 <= n_src <= VSM_LEVEL_MAX_SRC and N <= 128, anything else is VSM_ERR_INVALID_ARG before
- * any launch (larger N: one vsm_level_radiance_oplevel_* call per source, whose outputs accumulate).  n_src = 1 returns the
- * bits of vsm_level_radiance_*: same system, same pivots, same order of operations.  Status words and pivot rule as there.
+ * any launch (larger N: one vsm_level_radiance_oplevel_* call per source, whose outputs accumulate).  n_src = 1 is what
+ * vsm_level_radiance_* launches for N <= 128, so the two return the same bits.  Status words and pivot rule as there.
  * work is not used and may be NULL. */
 #define VSM_LEVEL_MAX_SRC 4
 int vsm_level_radiance_src_f64(int N, int n_stokes, int S, int nV, const int* row0_h, const double* w_h, const double* top_R_pm,
@@ -1047,8 +1047,8 @@ int vsm_level_radiance_lin_f32(int N, int n_stokes, int S, int P, int P_top, int
  * Outputs: uw_lin / dw_lin [nV,n_stokes,S,P+P_src] ACCUMULATED, dw_lin_full / uw_lin_full (nullable) [N,1,S,P+P_src].  All
  * P + P_src slots run in the chunks of vsm_level_radiance_lin_* as right-hand sides of ONE elimination per chunk; a chunk may hold
  * both kinds.  N <= 128, 1 <= P, P + P_src <= 64, anything else is VSM_ERR_INVALID_ARG before any launch (P_src = 0: both source
- * stacks may be NULL, and the outputs are the bits of vsm_level_radiance_lin_*: same system, same pivots, same order of
- * additions).  Status words and pivot rule as there.  No work buffer. */
+ * stacks may be NULL: this is the call vsm_level_radiance_lin_* makes, so the two return the same bits).  Status words and pivot
+ * rule as there.  No work buffer. */
 int vsm_level_radiance_lin_src_f64(int N, int n_stokes, int S, int P, int P_top, int P_src, int nV, const int* row0_h,
                                    const double* w_h, const double* top_R_pm, const double* bot_R_mp, long long bot_stride,
                                    const double* dw_full, const double* uw_full, const double* top_R_pm_lin,

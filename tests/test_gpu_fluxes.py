@@ -261,22 +261,29 @@ def _sibling_quadrature(pm, ms, levels):
     return {k: np.array(v) for k, v in rows.items()}
 
 
-@pytest.mark.parametrize("kind", ["m_max_3", "surface_sif", "solar_thermal"])
+@pytest.mark.parametrize("kind", ["m_max_3", "surface_sif", "solar_thermal", "all_sources"])
 def test_fluxes_against_the_multisensor_run(vsm, arch, kind):
     """Every diffuse quantity is the float64 quadrature of rt_run_multisensor(..., streams=True)'s own m = 0 level vectors (1e-11
     of its largest value: ten times the kernel's bound against its composition); m_max does not enter; SurfaceSIF and the thermal
-    slot are carried as there.  down_diffuse at level Nz is the quadrature of the sibling's level-0 dw (rt_run's T)."""
+    slot are carried as there.  down_diffuse at level Nz is the quadrature of the sibling's level-0 dw (rt_run's T).
+    all_sources: SolarBeam + ThermalEmission + SurfaceEmission + SurfaceSIF on levels [2, 0, Nz, 2] -- the one mix in which every
+    source list the walk hands the flux run carries two entries and the surface layer emits in both slots (l_trunc 9: N = 27)."""
     H = vsm.host_model
     S, L = 4, 5
-    pm, om = _pair(vsm, arch, "IQU", 13, S, L, np.random.default_rng(21), m_max=3, albedo=0.2)
-    thermal = kind == "solar_thermal"
-    if kind == "surface_sif":
+    pm, om = _pair(vsm, arch, "IQU", 9 if kind == "all_sources" else 13, S, L, np.random.default_rng(21), m_max=3, albedo=0.2)
+    thermal = kind in ("solar_thermal", "all_sources")
+    levels = list(range(L + 1))
+    if kind == "all_sources":
+        B = 0.05 + 0.1 * np.random.default_rng(23).random((L, S))
+        pm.sources = (H.SolarBeam(), H.ThermalEmission(B_layer=B), H.SurfaceEmission(B_surface=0.1 + 0.1 * np.arange(S)),
+                      H.SurfaceSIF(0.02 + 0.03 * np.random.default_rng(22).random(S)))
+        levels = [2, 0, L, 2]
+    elif kind == "surface_sif":
         sif = 0.02 + 0.03 * np.random.default_rng(22).random(S)
         pm.sources = (H.SolarBeam(), H.SurfaceSIF(sif))
     elif thermal:
         B = 0.05 + 0.1 * np.random.default_rng(23).random((L, S))
         pm.sources = (H.SolarBeam(), H.ThermalEmission(B_layer=B))
-    levels = list(range(L + 1))
     res = vsm.CoreRT.rt_run_fluxes(pm, levels, thermal=thermal)
     ms = vsm.CoreRT.rt_run_multisensor(pm, levels, streams=True, thermal=thermal)
     want = _sibling_quadrature(pm, ms, levels)
@@ -285,8 +292,8 @@ def test_fluxes_against_the_multisensor_run(vsm, arch, kind):
     assert max(errs.values()) <= 1e-11, errs
     qp = pm.quad_points
     t_bottom = (np.asarray(qp.qp_mu, dtype=np.float64) * np.asarray(qp.wt_mu, dtype=np.float64)) @ \
-        ms.dw_streams[0][0][::pm.polarization_type.n, 0, :].astype(np.float64)
-    assert _rel(res.down_diffuse[L], t_bottom) <= 1e-11 and np.max(np.abs(t_bottom)) > 0
+        ms.dw_streams[levels.index(0)][0][::pm.polarization_type.n, 0, :].astype(np.float64)
+    assert _rel(res.down_diffuse[levels.index(L)], t_bottom) <= 1e-11 and np.max(np.abs(t_bottom)) > 0
     if kind == "m_max_3":
         import dataclasses
         r0 = vsm.CoreRT.rt_run_fluxes(dataclasses.replace(pm, m_max=0), levels)

@@ -1,5 +1,6 @@
-"""GPU tests of the pivoted elimination shared by the seven fused level kernels of csrc/vsm_level.hip (level_form_system +
-level_eliminate): every entry point on inputs whose I - A B has its large entries OFF the diagonal (tests/level_cases.py), so that
+"""GPU tests of the pivoted elimination inside the one solve body (level_solve_columns: level_form_system + level_eliminate) of
+the fused level kernels of csrc/vsm_level.hip, through seven entry points (radiance and src share a kernel, as do lin and
+lin_src): every entry point on inputs whose I - A B has its large entries OFF the diagonal (tests/level_cases.py), so that
 almost every step of the Gauss-Jordan elimination exchanges a row -- the wave-0 pivot search with its two ballots (rows 0..63 and
 64..127) and first-occurrence rule, the row exchange over ALL columns k .. NC-1 (the right-hand sides included: K sources, the PC
 parameter columns of a linearized chunk), and the SINGULAR / NONFINITE bits of vsm_device_status raised by this file.
@@ -252,6 +253,8 @@ def test_level_lin_src_pivoting(vsm, N, P, P_top, P_src, shared):
 
 @pytest.mark.parametrize("N,P,P_top,shared", [(21, 3, 2, True), (128, 13, 12, False)])
 def test_level_lin_src_without_sources_is_the_lin_kernel_bitwise_pivoting(vsm, N, P, P_top, shared):
+    """vsm_level_radiance_lin_* launches the source-slot kernel with P_src = 0: an entry point against the kernel it forwards to,
+    on pivoting inputs.  The arithmetic is pinned against numpy by test_level_lin_pivoting and test_level_lin_src_pivoting above."""
     inputs = LC.fixed("pivoting", F64)
     a, _ = TTL._kernel_case(vsm, N, P, P_top, 0, shared, S=S, inputs=inputs)
     b, _ = TTL._kernel_case(vsm, N, P, P_top, 0, shared, S=S, inputs=inputs, entry="vsm_level_radiance_lin")

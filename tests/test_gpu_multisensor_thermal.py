@@ -1,6 +1,6 @@
 """GPU tests of thermal emission in the multi-sensor run (vsm.CoreRT.rt_run_multisensor(..., thermal=True), core_rt_ms.py) and of
 its multi-source level kernel (vsm_level_radiance_src_*, csrc/vsm_level.hip): against the statement-order oracle
-(tests/ms_thermal_oracle.py + tests/ms_oracle.py), level 0 against rt_run bit for bit, the kernel against the one-source kernel
+(tests/ms_thermal_oracle.py + tests/ms_oracle.py), level 0 against rt_run bit for bit, the kernel against the one-source entry point
 (n_src = 1, bit for bit) and against accumulated operator-level calls (n_src = 2), the flags, poisoned work buffers and the
 library calls the host issues."""
 import collections
@@ -175,8 +175,12 @@ def _level_src_call(vsm, setup, S, N, nV, tA, tops, tB, bots, oplevel=False):
 @pytest.mark.parametrize("N", [3, 16, 61, 128])
 @pytest.mark.parametrize("FT", [np.float64, np.float32], ids=["f64", "f32"])
 def test_level_src_kernel(vsm, N, FT):
-    """n_src = 1: the bits of vsm_level_radiance_*.  n_src = 2: two accumulated operator-level calls, within the tolerance of
-    test_gpu_multisensor.py::_fused_vs_oplevel.  Shared and per-point bottoms, 3 and 70 viewing angles."""
+    """n_src = 1: the bits of vsm_level_radiance_* -- which for N <= 128 launches this kernel with one source, so the comparison
+    now pins the forwarding (arguments, LDS size, the path above 64 viewing angles), not two bodies; the arithmetic of the one
+    body is pinned against numpy below (n_src = 2), by test_gpu_multisensor.py::test_level_kernel_fused_vs_oplevel and by
+    test_gpu_level_pivoting.py::test_level_radiance_pivoting / test_level_src_pivoting.  n_src = 2: two accumulated
+    operator-level calls, within the tolerance of test_gpu_multisensor.py::_fused_vs_oplevel.  Shared and per-point bottoms, 3
+    and 70 viewing angles."""
     MSd = vsm.core_rt_ms
     S = 7
     rng = np.random.default_rng(N)
@@ -189,7 +193,7 @@ def test_level_src_kernel(vsm, N, FT):
             A, (a, a2), B, (c, c2) = _src_inputs(N, S, rng, shared)
             tA, tB, ta, tc, ta2, tc2 = lay(A), lay(B), vec(a), vec(c), vec(a2), vec(c2)
             w = 1.0 / math.pi
-            # n_src = 1 against the one-source kernel
+            # n_src = 1 against the one-source entry point
             one = _outputs(S, N, pol, nV, dt, dev)
             MSd.level_radiance_(pol, qp, vza, vaz, 1, w, tA, ta, tB, tc, one[0], one[1], one[3], one[2])
             src1 = _outputs(S, N, pol, nV, dt, dev)

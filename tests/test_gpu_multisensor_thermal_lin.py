@@ -454,6 +454,10 @@ def test_level_kernel_lin_src_many_angles(vsm):
 @pytest.mark.parametrize("FT", [np.float64, np.float32], ids=["fp64", "fp32"])
 @pytest.mark.parametrize("N,P,P_top,shared", [(21, 3, 2, True), (128, 13, 12, False)])
 def test_level_kernel_lin_src_without_sources_is_the_lin_kernel_bitwise(vsm, N, P, P_top, shared, FT):
+    """vsm_level_radiance_lin_* launches the source-slot kernel with P_src = 0, so this compares an entry point with the kernel
+    it forwards to: it pins the forwarding (arguments, chunking, LDS size).  The arithmetic of that one kernel is pinned against
+    numpy by test_level_kernel_lin_src_vs_numpy in this file and by test_gpu_multisensor_lin.py::test_level_kernel_lin_vs_numpy
+    through the other entry point."""
     a, _ = _kernel_case(vsm, N, P, P_top, 0, shared, FT=FT)
     b, _ = _kernel_case(vsm, N, P, P_top, 0, shared, FT=FT, entry="vsm_level_radiance_lin")
     assert all(np.array_equal(x, y) for x, y in zip(a, b))

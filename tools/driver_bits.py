@@ -5,6 +5,7 @@
                                                           device); every returned array as DIR/<scene>.<k>.npy.  --tree: run the
                                                           package, the oracle and the tests' builders of another checkout (its
                                                           library built), e.g. a copy of the parent commit
+                                                          --only NAME[,NAME]: those scenes alone
   python tools/driver_bits.py --compare DIR_A DIR_B       exit 1 on any array that is missing on one side or differs (shape, dtype,
                                                           any element; NaNs must sit in the same places)
 
@@ -23,6 +24,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ap = argparse.ArgumentParser()
 ap.add_argument("--dump", metavar="DIR")
 ap.add_argument("--tree", default=ROOT)
+ap.add_argument("--only", default="", help="comma-separated scene names (default: all)")
 ap.add_argument("--compare", nargs=2, metavar=("DIR_A", "DIR_B"))
 ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
 a = ap.parse_args()
@@ -42,19 +44,25 @@ if not a.dump:
 if not a.child:
     os.makedirs(a.dump, exist_ok=True)
     sys.exit(subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--dump", os.path.abspath(a.dump), "--tree",
-                             os.path.abspath(a.tree)], cwd=a.tree).returncode)
+                             os.path.abspath(a.tree), "--only", a.only], cwd=a.tree).returncode)
 
 sys.path[:0] = [a.tree, os.path.join(a.tree, "tests")]
 import torch  # noqa: E402
 import vsmartmom_jl_amd as vsm  # noqa: E402
 import brdf_lin_oracle as B  # noqa: E402
+import level_cases as LC  # noqa: E402
 import test_gpu_brdf_lin as TB  # noqa: E402
+import test_gpu_fluxes as TF  # noqa: E402
+import test_gpu_fluxes_lin as TFL  # noqa: E402
 import test_gpu_lin as TLIN  # noqa: E402
 import test_gpu_multisensor as TMS  # noqa: E402
 import test_gpu_multisensor_lin as TML  # noqa: E402
 import test_gpu_multisensor_raman as TMR  # noqa: E402
+import test_gpu_multisensor_thermal as TMT  # noqa: E402
 import test_gpu_multisensor_thermal_lin as TMTL  # noqa: E402
 import test_gpu_sif as TS  # noqa: E402
+import test_gpu_surface_emission as TSE  # noqa: E402
+import test_gpu_surface_emission_lin as TSEL  # noqa: E402
 import test_gpu_ss as TSS  # noqa: E402
 
 H, CR, CL, RR = vsm.host_model, vsm.CoreRT, vsm.CoreRTLin, vsm.CoreRTRaman
@@ -69,7 +77,9 @@ def scene(f):
 
 
 def flatten(x):
-    """The arrays of a result, in a fixed order: tuples, lists, dicts, result dataclasses, device tensors."""
+    """The arrays of a result, in a fixed order: tuples, lists, dicts, result dataclasses, device tensors; None holds none."""
+    if x is None:
+        return []
     if torch.is_tensor(x):
         return [x.detach().cpu().numpy()]
     if dataclasses.is_dataclass(x):
@@ -221,6 +231,122 @@ def ms_forward_n128():
     return out, CR.rt_run_multisensor(pm, [1, 2, 3, 0], thermal=True)
 
 
+@scene
+def ms_surface_emission():
+    """SurfaceEmission in the forward run with level vectors, and in the linearized run with its two skin slots."""
+    S = 5
+    out = []
+    for se_kw in ({}, dict(emissivity=0.8)):          # Kirchhoff, explicit
+        pm, _, _ = TSE.scene(vsm, arch, "lambertian", "IQU", S, sources=TSE._sources(H, "all", S, **se_kw))
+        out.append(CR.rt_run_multisensor(pm, TSE.LEVELS, thermal=True, streams=True))
+    pm, _, _ = TSE.scene(vsm, arch, "lambertian", "IQU", S, window=True)
+    pm.sources = TSEL._sources(H, "all", S)
+    return out, CL.rt_run_multisensor(pm, H.LinModel(list(TSEL._gases(S))), 0, 2, 1, TSE.LEVELS, streams=True)
+
+
+# ---- rt_run_fluxes -------------------------------------------------------------------------------------------------------------------
+def emitting_sources(L, S, **se_kw):
+    return thermal_sources(L, S) + (H.SurfaceEmission(B_surface=0.9 + 0.03 * np.arange(S), **se_kw),)
+
+
+@scene
+def fluxes():
+    out = []
+    for pol, lt in (("IQU", 35), ("IQUV", 50)):          # native runs / the reference-layout walk
+        for levels in (None, [4, 0, 2, 4]):
+            pm = small(pol, lt, 4, 6, m_max=1)
+            out.append(CR.rt_run_fluxes(pm, levels))
+            for se_kw in ({}, dict(emissivity=0.8)):      # Kirchhoff, explicit
+                pm.sources = emitting_sources(6, 4, **se_kw)
+                out.append(CR.rt_run_fluxes(pm, levels, thermal=True))
+    pm = small("IQU", 35, 4, 6)
+    pm.sources = (H.SolarBeam(), H.SurfaceSIF(np.linspace(0.1, 0.3, 4)))
+    out.append(CR.rt_run_fluxes(pm, [4, 0, 2, 4]))
+    pm.sources = emitting_sources(6, 4) + (H.SurfaceSIF(np.linspace(0.1, 0.3, 4)),)
+    out.append(CR.rt_run_fluxes(pm, None, thermal=True, max_points=3))
+    with switch("REFERENCE_ORDER", True):
+        out.append(CR.rt_run_fluxes(small("IQU", 35, 4, 6), None))
+    pm = small(m_max=1, **N128)
+    out.append(CR.rt_run_fluxes(pm, None))
+    pm.sources = emitting_sources(3, 2)
+    return out, CR.rt_run_fluxes(pm, None, thermal=True)
+
+
+# ---- the level kernels, called directly (the call helpers of tests/test_gpu_level_pivoting.py) -------------------------------------
+def level_kernels_at(N, FT, vza, vaz, many):
+    """Every entry point of csrc/vsm_level.hip at one size, S = 3, on level_cases.fixed("pivoting", FT); many: the calls that take
+    a viewing-angle table alone (radiance, src, emission response), with the angles given."""
+    S, nV, inputs = 3, len(vza), LC.fixed("pivoting", FT)
+    out = [outs for _, _, outs in TMS._fused_and_oplevel_calls(vsm, N, FT, vza, vaz, inputs=inputs, S=S, ops=(False,))[2]]
+    setup = TMT._kernel_setup(vsm, N, FT, nV, vza_max=88.0)
+    lay, vec = setup[6], setup[7]
+    for shared in (False, True):
+        for n_src in (1, 2, 4):
+            scales = tuple(1.0 if k % 2 == 0 else 1e3 for k in range(n_src))
+            A, tops, B, bots = TMT._src_inputs(N, S, np.random.default_rng(N), shared, inputs=inputs, scales=scales, FT=FT)
+            out.append(TMT._level_src_call(vsm, setup, S, N, nV, lay(A), [vec(x) for x in tops], lay(B), [vec(x) for x in bots]))
+        for K in (1, 3):
+            res = TS._emission_response_case(vsm, N, FT, K, nV, shared, None, inputs=emission_inputs(FT), S_=S, vza_max=88.0,
+                                             oplevel=False)
+            out.append([xf for _, _, xf, _, _ in res])
+    if many:
+        return out
+    for shared in (False, True):
+        pol, dt, dev, host, d = TF._kernel_case(vsm, N, FT, S, shared, np.random.default_rng(N), inputs=inputs)
+        for K in (1, 2, 4):
+            for top in (True, False):
+                o = torch.full((3, 2, S), float("nan"), dtype=dt, device=dev)
+                vsm.core_rt_flux.level_flux_(pol, d["A"] if top else None, d["a"][:K] if top else None, d["B"] if top else None,
+                                             d["c"][:K], d["q"][:2].contiguous(), host["dir_h"][:2], host["mu0"], d["tau"], d["F0"], o)
+                out.append(o)
+        out.append(level_ie(N, FT, S, shared, inputs))
+        # FP64 at N = 128 takes 12 slots per chunk: a chunk boundary inside the parameter slots, and inside the source-only ones
+        two_chunks = N == 128 and FT == np.float64
+        P, P_top = (13, 12) if two_chunks else (3, 2)
+        out.append(TML._kernel_case(vsm, N, P, P_top, shared, S=S, FT=FT, inputs=inputs)[0])
+        P, P_top, P_src = (5, 4, 9) if two_chunks else (3, 2, 2)
+        out.append(TMTL._kernel_case(vsm, N, P, P_top, P_src, shared, S=S, FT=FT, inputs=inputs)[0])
+        case = TFL._Case(N, P, P_top, P_src, shared, S, FT, 3 if N % 3 == 0 else 1)
+        out += [case.call(vsm, 2, top=True), case.call(vsm, 2, top=False)]
+    return out
+
+
+def emission_inputs(FT):
+    """(A, B, T) of the response call: the family's operators and test_gpu_sif's transmission block, rounded to FT."""
+    def gen(N, S, rng, shared):
+        A, _, B, _ = LC.fixed("pivoting", FT)(N, S, None, shared)
+        T = (np.random.default_rng(N).random((S, N, N)) * (1.0 / N) + 0.5 * np.eye(N)[None]).astype(FT).astype(np.float64)
+        return A, B, T
+    return gen
+
+
+def level_ie(N, FT, S, shared, inputs):
+    """vsm_level_radiance_ie_* with 7 lines, as test_gpu_multisensor_raman._level_ie_vs_numpy feeds it: [uwie, dwie, dwie_full,
+    uwie_full]."""
+    K, nV = 7, 3
+    rng = np.random.default_rng(N * 1000 + K)
+    ns = 3 if N % 3 == 0 else 1
+    A, dwf, B, uwf = inputs(N, S, rng, shared)
+    Aie, aie = 0.05 * rng.random((K, S, N, N)) / N, 0.05 * rng.random((K, S, N))
+    Bie, cie = 0.05 * rng.random((K, S, N, N)) / N, 0.05 * rng.random((K, S, N))
+    row0 = [0, ns * ((N // ns) // 2), N - ns]
+    wv = rng.uniform(0.1, 1.0, nV * ns)
+    dt = torch.float64 if FT == np.float64 else torch.float32
+    outs = [torch.zeros((S, ns, nV), dtype=dt, device="cuda") for _ in range(2)]
+    outs += [torch.full((S, N), float("nan"), dtype=dt, device="cuda") for _ in range(2)]
+    TMR._level_ie_call(vsm, FT, N, ns, S, K, [int(x) for x in TMR.SHIFTS], A, B, dwf, uwf, Aie, aie, Bie, cie, row0, wv, *outs)
+    torch.cuda.synchronize()
+    return outs
+
+
+@scene
+def level_kernels():
+    vza, vaz = [0.0, 30.0, 88.0], [0.0, 45.0, 120.0]
+    out = [level_kernels_at(N, FT, vza, vaz, False) for FT in (np.float64, np.float32) for N in (3, 17, 65, 128)]
+    vza, vaz = list(np.linspace(0.0, 88.0, 70)), list(np.linspace(0.0, 345.0, 70))
+    return out, [level_kernels_at(65, FT, vza, vaz, True) for FT in (np.float64, np.float32)]
+
+
 # ---- rt_run_lin --------------------------------------------------------------------------------------------------------------------
 def lin_pair(pol="IQU", lt=9, S=3, L=6, **kw):
     return TML._pair(vsm, arch, pol, lt, S, L, rng(), **kw)[:2]
@@ -311,6 +437,21 @@ for name_ in TMTL.CASES:
     ms_lin_case(name_)
 
 
+# ---- linearized rt_run_fluxes (the cases of tests/test_gpu_fluxes_lin.py) -----------------------------------------------------------------
+@scene
+def fluxes_lin():
+    levels = list(range(6))
+    pm, pl = TML._pair(vsm, arch, "IQU", 13, 4, 5, np.random.default_rng(21), m_max=3, albedo=0.2)[:2]
+    out = [CL.rt_run_fluxes(pm, pl, 0, 1, 1, levels)]
+    Bd = np.stack([np.ones((5, 4)), 0.3 + 0.1 * np.arange(5)[:, None] * np.ones((1, 4))])
+    pm.sources = (H.SolarBeam(), H.ThermalEmission(B_layer=0.05 + 0.1 * np.random.default_rng(23).random((5, 4)), B_layer_dot=Bd))
+    out.append(CL.rt_run_fluxes(pm, pl, 0, 1, 1, levels))
+    out.append(CL.rt_run_fluxes(pm, pl, 0, 1, 1, [2, 0, 5, 2], max_points=3))
+    pm, _, _ = TSE.scene(vsm, arch, "lambertian", "IQU", 5, window=True)
+    pm.sources = TSEL._sources(H, "all", 5)          # one Planck slot, two skin slots
+    return out, CL.rt_run_fluxes(pm, H.LinModel(list(TSEL._gases(5))), 0, 2, 1, TSE.LEVELS)
+
+
 # ---- Raman and single scattering (they share the row / weight table and the Fourier weight) -------------------------------------------
 @scene
 def raman_and_ss():
@@ -323,6 +464,8 @@ def raman_and_ss():
 
 
 for name_, f in SCENES.items():
+    if a.only and name_ not in a.only.split(","):
+        continue
     arrays = flatten(f())
     for k, x in enumerate(arrays):
         np.save(os.path.join(a.dump, "%s.%03d.npy" % (name_, k)), x)

@@ -3,8 +3,8 @@
 The level vectors of the multi-sensor run (core_rt_ms.py) at m = 0, the one Fourier moment that survives the azimuth integral,
 reduced on the device to their hemispheric quadratures: per level ONE call of vsm_level_flux_* (csrc/vsm_level.hip), which solves
 the level equation for every source on one elimination and leaves 3 nW scalars per spectral point -- no [S, N] level vector is
-allocated, none is brought to the host.  The walk is core_rt_ms._run's for one moment: the top pass with the tops kept
-(Scene._walk_layers), the segments and bottoms from the surface up (walk_levels), the thermal slot's twin composites.
+allocated, none is brought to the host.  There is no walk here: the run hands core_rt_ms._run, the one elastic walk, a scene of
+that one moment and a sink (_FluxSink) that takes the place of its level calls.
 
 Convention (the reference's hem_R / hem_T, rt_run.jl:745): with uw / dw the m = 0 level vectors (rows of Stokes I), mu, w the
 quadrature nodes and weights, F = sum_i mu_i w_i v_i and the actinic flux sum_i w_i v_i; the Fourier weight 0.5 / pi and the 2 pi
@@ -13,7 +13,6 @@ of the azimuth integral cancel.  The direct beam, which the diffuse vectors do n
 """
 from __future__ import annotations
 
-import contextlib
 import ctypes as C
 import dataclasses
 from dataclasses import dataclass
@@ -49,7 +48,7 @@ def level_flux_(pol, top_R_pm, tops_J0_p, bot_R_mp, bots_J0_m, q, dir_h, mu0: fl
     dt = bots_J0_m[0].dtype
     if (tau_sum is None) != (F0_I is None):
         raise _lib.VSMError("level_flux_: tau_sum and F0_I are given together or not at all")
-    bot_stride = 0 if bot_R_mp is not None and int(bot_R_mp.shape[0]) == 1 and S > 1 else N * N
+    bot_stride = N * N if bot_R_mp is None else MS.bot_stride_of(bot_R_mp, S, N)
     P = CR._ptr
     ctype = C.c_double if dt == torch.float64 else C.c_float
     if not (oplevel or MS.LEVEL_OPLEVEL or N > MS.LEVEL_FUSED_MAX_N):
@@ -111,86 +110,34 @@ def bytes_per_point(N: int, Nz: int, n_tops: int, segments: bool, thermal: bool,
     return elems * itemsize
 
 
-def _run(scene: CR.Scene, plan: MS.LevelPlan):
-    """One block of points: a (len(plan.distinct), 3, 2, S) device tensor -- per level [up, down, direct] x [flux, actinic].  The
-    m = 0 walk of core_rt_ms._run (the scene has that moment alone), its level calls replaced by level_flux_."""
-    model, pol, FT = scene.model, scene.pol, scene.FT
-    Nz, N, S = scene.Nz, scene.N, scene.S
-    dev, dt = scene.dev, scene.dt
-    MS.refuse_non_scattering(scene.moments[0]["layers"], FT, WHO,
-                             ".  rt_run keeps the reference's stale-j0+ quirk there (DESIGN.md §6), which the level equation "
-                             "does not carry; columns with a non-scattering layer are not supported (as for rt_run_multisensor)")
-    buf = torch.empty((len(plan.distinct), 3, 2, S), dtype=dt, device=dev)      # (one array, so that ONE copy brings a block home)
-    out = {l: buf[i] for i, l in enumerate(plan.distinct)}
-    if S == 0:
-        return buf
-    qp = scene.qp
-    mu, wt = np.asarray(qp.qp_mu, dtype=np.float64), np.asarray(qp.wt_mu, dtype=np.float64)
-    q = torch.as_tensor(np.stack([mu * wt, wt]).astype(FT), device=dev)      # the flux row and the actinic row, uploaded once
-    mu0 = float(qp.mu0)
-    dir_h = (mu0, 1.0)
-    F0_I = scene.F0[:, 0].contiguous()
-    scene.added.j0_p.zero_()
-    thermal = scene.thermal_B is not None
-    mom = scene.moments[0]
-    tau_sum_of = lambda l: mom["tau_sum_surface"] if l == Nz else mom["layers"][l]["tau_sum"]
-    segs = [CR.make_composite_layer(FT, scene.arch, (N, N), S) for _ in range(2 if plan.interior else 0)]
-    th_of = {id(seg): CR.make_composite_layer(FT, scene.arch, (N, N), S) for seg in segs} if thermal else {}
-    native = scene._native_moments() if not CR.REFERENCE_ORDER else set()
-    with contextlib.ExitStack() as stack:
-        stack.callback(lambda: [c.drop_native() for c in segs])
-        stack.enter_context(scene._walk_composites(1, CR.REFERENCE_ORDER, None))
-        comp = scene._composites[0]
-        tops = {}
-        # 1. the top pass, the tops kept on the way
-        scene._walk_layers([mom], [comp], [0] if 0 in native else [], sources_only=True, view_rows=None, tops_at=plan.tops_at,
-                           keep_top=lambda k, l, top: tops.__setitem__(l, top))
-        asurf = scene.added_surface
-        CR.create_surface_layer_(model.surface, asurf, 0, scene.dq, mom["tau_sum_surface"], rho=mom["rho"])
-        CR.surface_source_contribute_(scene, model.surface, asurf, 0)
-        th_tops, th_surf, slot = {}, None, None
-        if thermal:
-            slot = scene.thermal_slot()
-            slot.begin(mom)
-            slot.walk(mom, slot.comp, 0, Nz, scene.thermal_B,
-                      after={l: (lambda c, l=l: th_tops.__setitem__(l, c.J0_p.clone())) for l in plan.tops_at})
-            th_surf = slot.surface(mom)
+class _FluxSink(MS.LevelSink):
+    """The flux run's place in the walk of core_rt_ms._run: one level_flux_ call per level into its row of ONE (len(plan.distinct),
+    3, 2, S) device tensor -- per level [up, down, direct] x [flux, actinic] --, so that ONE copy brings a block home."""
 
-        def level(l, seg):
-            A, a = tops.pop(l)
-            bot_R_mp, bot_J0_m = (asurf.r_mp, asurf.j0_m) if seg is None else (seg.R_mp, seg.J0_m)
-            aa, cc = [a], [bot_J0_m]
-            if thermal:      # the solar and the thermal right-hand side on ONE system (A, B of the solar pass)
-                aa.append(th_tops.pop(l))
-                cc.append(th_surf.j0_m if seg is None else th_of[id(seg)].J0_m)
-            level_flux_(pol, A, aa, bot_R_mp, cc, q, dir_h, mu0, tau_sum_of(l), F0_I, out[l])
+    def __init__(self, scene: CR.Scene, plan: MS.LevelPlan):
+        MS.refuse_non_scattering(scene.moments[0]["layers"], scene.FT, WHO,
+                                 ".  rt_run keeps the reference's stale-j0+ quirk there (DESIGN.md §6), which the level equation "
+                                 "does not carry; columns with a non-scattering layer are not supported (as for rt_run_multisensor)")
+        self.pol, self.Nz = scene.pol, scene.Nz
+        self.buf = torch.empty((len(plan.distinct), 3, 2, scene.S), dtype=scene.dt, device=scene.dev)
+        self.out = {l: self.buf[i] for i, l in enumerate(plan.distinct)}
+        qp = scene.qp
+        mu, wt = np.asarray(qp.qp_mu, dtype=np.float64), np.asarray(qp.wt_mu, dtype=np.float64)
+        # the flux row and the actinic row, uploaded once
+        self.q = torch.as_tensor(np.stack([mu * wt, wt]).astype(scene.FT), device=scene.dev)
+        self.mu0 = float(qp.mu0)
+        self.dir_h = (self.mu0, 1.0)
+        self.F0_I = scene.F0[:, 0].contiguous()
 
-        def run_segment(seg, first, end):
-            MS._run_segment(scene, mom, seg, first, end)
-            if thermal:
-                slot.walk(mom, th_of[id(seg)], first, end, scene.thermal_B)
+    def _flux(self, mom, l, A, aa, bot_R_mp, cc):
+        tau_sum = mom["tau_sum_surface"] if l == self.Nz else mom["layers"][l]["tau_sum"]
+        level_flux_(self.pol, A, aa, bot_R_mp, cc, self.q, self.dir_h, self.mu0, tau_sum, self.F0_I, self.out[l])
 
-        def join_surface(seg):
-            CR.interaction_(mom["iface_surface"], seg, asurf, work=scene.work)
-            if thermal:
-                CR.interaction_(mom["iface_surface"], th_of[id(seg)], th_surf, oplevel=True, work=scene.work)
+    def level(self, mom, l, A, tops_J0_p, bot_R_mp, bots_J0_m):
+        self._flux(mom, l, A, tops_J0_p, bot_R_mp, bots_J0_m)
 
-        def join_bottom(seg, bot, first, end):
-            CR.interaction_("11", seg, MS._CompositeAsAdded(bot), work=scene.work)
-            if thermal:
-                CR.interaction_("11", th_of[id(seg)], MS._CompositeAsAdded(th_of[id(bot)]), oplevel=True, work=scene.work)
-        # 2.-4. the levels below the top pass
-        MS.walk_levels(plan, segs, run_segment, join_surface, join_bottom, level)
-        # level 0, the TOA itself: J0- of the whole column with the surface (and the thermal slot's), nothing diffuse going down
-        if 0 in plan.distinct:
-            CR.interaction_(mom["iface_surface"], comp, asurf, work=scene.work)
-            cc = [comp.J0_m]
-            if thermal:
-                CR.interaction_(mom["iface_surface"], slot.comp, th_surf, oplevel=True, work=scene.work)
-                cc.append(slot.comp.J0_m)
-            level_flux_(pol, None, None, None, cc, q, dir_h, mu0, tau_sum_of(0), F0_I, out[0])
-        tops.clear()
-    return buf
+    def level0(self, mom, J0_m_list):      # nothing diffuse goes down at the TOA
+        self._flux(mom, 0, None, None, None, J0_m_list)
 
 
 def rt_run_fluxes(model: H.RTModel, levels=None, thermal: bool = False, max_points: Optional[int] = None) -> FluxResult:
@@ -238,7 +185,11 @@ def rt_run_fluxes(model: H.RTModel, levels=None, thermal: bool = False, max_poin
     parts = []
     blocks = MS.spectral_blocks(S_full, max_points)
     for sl in blocks:
-        out = _run(CR.prepare_scene(model0, sl), plan)
+        scene = CR.prepare_scene(model0, sl)          # (m = 0 alone)
+        sink = _FluxSink(scene, plan)
+        MS._run(scene, plan, False, sink)
+        out = sink.buf
+        del scene, sink
         synchronize_if_gpu()
         _lib.check_device_status(WHO)
         parts.append(to_host(out))

@@ -23,6 +23,10 @@ segments need no tau_sum), thermal bottoms built beside the solar ones, and per 
 solves the solar and the thermal right-hand side on one elimination of [I - A B | .] with A, B of the solar pass (the thermal
 composites' own R differ from them only by rounding and are not read).  DESIGN.md §4.8d.
 
+_run is the one elastic walk.  A run that wants something else than radiances at each level hands it a LevelSink, which takes
+the place of the level calls: rt_run_fluxes (core_rt_flux.py) walks m = 0 alone and reduces the level vectors to fluxes on the
+device.  The linearized walk has the same arrangement (core_rt_ms_lin.LevelSink, core_rt_flux_lin.py).
+
 The Raman (core_rt_ms_raman.py) and linearized (core_rt_ms_lin.py) runs are the same algorithm on their own composites.  What the
 three share lives here: the level plan, the walk below the top pass (walk_levels), the two-call level of the runs that solve a
 second equation on the elastic level vectors (level_pair_), the Stokes_IQ sub-scene of m = 0 (merge_sub0), the blocks of the
@@ -33,7 +37,7 @@ from __future__ import annotations
 import contextlib
 import ctypes as C
 from dataclasses import dataclass
-from typing import List
+from typing import List, Optional
 
 import numpy as np
 import torch
@@ -63,13 +67,18 @@ class _CompositeAsAdded:
 _level_work = {}
 
 
+def bot_stride_of(bot_R_mp, S: int, N: int) -> int:
+    """bot_stride of a level call: 0 for a bottom R-+ of ONE block shared by every point ((1, N, N) with S > 1), else N * N."""
+    return 0 if int(bot_R_mp.shape[0]) == 1 and S > 1 else N * N
+
+
 def level_call_setup(pol, qp, vza, vaz, m: int, weight: float, vec, bot_R_mp):
     """(S, N, dtype, row0, w, bot_stride) of a level call, from one of its (S, N) vectors and the bottom's R-+; None for S = 0."""
     S, N = int(vec.shape[0]), int(vec.shape[1])
     if S == 0:
         return None
     row0, w = CR._vza_rows_weights(pol, vza, vaz, qp, m, weight, vec.dtype)
-    return S, N, vec.dtype, row0, w, (0 if int(bot_R_mp.shape[0]) == 1 and S > 1 else N * N)
+    return S, N, vec.dtype, row0, w, bot_stride_of(bot_R_mp, S, N)
 
 
 def level_radiance_(pol, qp, vza, vaz, m: int, weight: float, top_R_pm, top_J0_p, bot_R_mp, bot_J0_m, uw, dw,
@@ -110,11 +119,10 @@ def surface_emission_response_(pol, qp, vza, vaz, weight: float, top_R_pm, top_T
     S, N = int(top_R_pm.shape[0]), int(top_R_pm.shape[1])
     K, n, nV, dt, dev = len(comps), pol.n, len(vza), top_R_pm.dtype, top_R_pm.device
     row0, w = CR._vza_rows_weights(pol, vza, vaz, qp, 0, weight, dt)
-    bot_stride = 0 if int(bot_R_mp.shape[0]) == 1 and S > 1 else N * N
     P = CR._ptr
     if not (oplevel or LEVEL_OPLEVEL or N > LEVEL_FUSED_MAX_N):
         _lib.call("vsm_surface_emission_response", dt, N, n, S, K, (C.c_int * max(K, 1))(*[int(c) for c in comps]), nV, row0, w,
-                  P(top_R_pm), P(top_T_mm), P(bot_R_mp), bot_stride, P(up), P(dn), CR._stream_ptr())
+                  P(top_R_pm), P(top_T_mm), P(bot_R_mp), bot_stride_of(bot_R_mp, S, N), P(up), P(dn), CR._stream_ptr())
         return
     if not 1 <= K <= 4 or any(not 0 <= int(c) < n for c in comps):
         raise _lib.VSMError("surface_emission_response_: %d components %r (1..4 of 0..%d)" % (K, list(comps), n - 1))
@@ -356,22 +364,42 @@ def _run_segment(scene: CR.Scene, mom, seg: CR.CompositeLayer, first: int, end: 
                       iz - first + 1, scene.F0, scene.FT, model.numerics, dtau=ly["dtau"], ndoubl=ly["nd"], work=scene.work)
 
 
-def _run(scene: CR.Scene, plan: LevelPlan, streams: bool):
+class LevelSink:
+    """What a run other than the multi-sensor one does at each level of the walk of _run, in place of its level calls
+    (core_rt_flux.py: the fluxes).  With a sink no VZA output is allocated, no level call and no post-processing is issued here and
+    no level vector is collected; the walk itself -- tops, segments, bottoms -- is the same, and level 0 is walked only if the
+    plan asks for it.  The lists carry one vector per source: the solar one, then the thermal slot's where it runs (m = 0)."""
+
+    def level(self, mom, l, A, tops_J0_p, bot_R_mp, bots_J0_m):
+        """Level l > 0: A = R+- of the composite above it and its J0+ per source, R-+ of the one below and its J0- per source."""
+        raise NotImplementedError
+
+    def level0(self, mom, J0_m_list):
+        """Level 0, the TOA: J0- of the whole column with the surface, per source, after the surface interactions."""
+        raise NotImplementedError
+
+
+def _run(scene: CR.Scene, plan: LevelPlan, streams: bool, sink: Optional[LevelSink] = None):
+    """The elastic walk on one Scene, every moment of it.  Returns ({level: (uw, dw)} of (S, nStokes, nVZA) device tensors, {m:
+    {level: (uw, dw) (S, N)}} or None, the Fourier weights); with a sink (see LevelSink) the first holds level 0 alone, untouched,
+    and streams is not taken."""
     model, pol, FT = scene.model, scene.pol, scene.FT
     Nz, N, S = scene.Nz, scene.N, scene.S
-    refuse_non_scattering(scene.moments[0]["layers"], FT, "rt_run_multisensor",
-                          ".  rt_run keeps the reference's stale-j0+ quirk there (DESIGN.md §6) while the prototype hard-codes "
-                          "scatter = true (rt_kernel_multisensor.jl:29), so the two reference drivers disagree on such columns; "
-                          "columns with a non-scattering layer are not supported")
     tops_at = plan.tops_at
     dev, dt = scene.dev, scene.dt
     nV = len(model.vza)
-    out = {l: (torch.zeros((S, pol.n, nV), dtype=dt, device=dev), torch.zeros((S, pol.n, nV), dtype=dt, device=dev))
-           for l in plan.distinct if l != 0}
-    out[0] = (scene.R_SFI, scene.T_SFI)
-    full = {} if streams else None
-    scene.R_SFI.zero_()
-    scene.T_SFI.zero_()
+    out = {0: (scene.R_SFI, scene.T_SFI)}
+    full = {} if streams and sink is None else None
+    if sink is None:
+        refuse_non_scattering(scene.moments[0]["layers"], FT, "rt_run_multisensor",
+                              ".  rt_run keeps the reference's stale-j0+ quirk there (DESIGN.md §6) while the prototype hard-codes "
+                              "scatter = true (rt_kernel_multisensor.jl:29), so the two reference drivers disagree on such columns; "
+                              "columns with a non-scattering layer are not supported")
+        for l in plan.distinct:
+            if l != 0:
+                out[l] = (torch.zeros((S, pol.n, nV), dtype=dt, device=dev), torch.zeros((S, pol.n, nV), dtype=dt, device=dev))
+        scene.R_SFI.zero_()
+        scene.T_SFI.zero_()
     weights = []
     if S == 0:
         return out, full, [float(fourier_weight(FT, m)) for m in range(model.m_max + 1)]
@@ -379,19 +407,20 @@ def _run(scene: CR.Scene, plan: LevelPlan, streams: bool):
     # the moment groups of Scene.run (level 0 is then rt_run's result bit for bit), fewer where the tops would not fit the device
     nb = scene._group_size(not CR.MOMENT_BATCHING or CR.REFERENCE_ORDER)
     thermal = scene.thermal_B is not None
-    if tops_at and dev.type == "cuda":
+    if nb > 1 and tops_at and dev.type == "cuda":
         elt = torch.finfo(dt).bits // 8
         per_moment = len(tops_at) * (N * N + N) * S * elt + (4 * N * N + 2 * N) * S * elt
         if thermal:   # the thermal tops (J0+ alone), counted for every moment of a group although only m = 0 keeps them
             per_moment += len(tops_at) * N * S * elt
         free = torch.cuda.mem_get_info(dev)[0]
         nb = max(1, min(nb, int(0.5 * free // per_moment)))
-    segs = [CR.make_composite_layer(FT, scene.arch, (N, N), S) for _ in range(2 if plan.interior else 0)]
-    # the thermal twin of each segment composite (m = 0 only; never in native layout: the slot's calls take the reference's arrays)
-    th_of = {id(seg): CR.make_composite_layer(FT, scene.arch, (N, N), S) for seg in segs} if thermal else {}
+    # the two alternating segment composites, each with its thermal twin (m = 0 only; never in native layout: the slot's calls
+    # take the reference's arrays) or None
+    new_comp = lambda: CR.make_composite_layer(FT, scene.arch, (N, N), S)
+    segs = [(new_comp(), new_comp() if thermal else None) for _ in range(2 if plan.interior else 0)]
     native = scene._native_moments() if not CR.REFERENCE_ORDER else set()
     with contextlib.ExitStack() as stack:
-        stack.callback(lambda: [c.drop_native() for c in segs])
+        stack.callback(lambda: [seg[0].drop_native() for seg in segs])
         stack.enter_context(scene._walk_composites(nb, CR.REFERENCE_ORDER, None))
         for g0 in range(0, len(scene.moments), nb):
             group = scene.moments[g0:g0 + nb]
@@ -421,13 +450,19 @@ def _run(scene: CR.Scene, plan: LevelPlan, streams: bool):
 
                 def level(l, seg):
                     A, a = tops[k].pop(l)
-                    bot_R_mp, bot_J0_m = (asurf.r_mp, asurf.j0_m) if seg is None else (seg.R_mp, seg.J0_m)
+                    bot_R_mp, bot_J0_m = (asurf.r_mp, asurf.j0_m) if seg is None else (seg[0].R_mp, seg[0].J0_m)
+                    aa, cc = [a], [bot_J0_m]
+                    if th:   # the solar and the thermal right-hand side on ONE system (A, B of the solar pass)
+                        aa.append(th_tops.pop(l))
+                        cc.append(th_surf.j0_m if seg is None else seg[1].J0_m)
+                    if sink is not None:
+                        sink.level(mom, l, A, aa, bot_R_mp, cc)
+                        return
                     dwf = torch.empty((S, N), dtype=dt, device=dev) if streams else None
                     uwf = torch.empty((S, N), dtype=dt, device=dev) if streams else None
-                    if th:   # the solar and the thermal right-hand side on ONE system (A, B of the solar pass)
-                        th_J0_m = th_surf.j0_m if seg is None else th_of[id(seg)].J0_m
-                        level_radiance_src_(pol, scene.qp, model.vza, model.vaz, m, float(weight), A, [a, th_tops.pop(l)], bot_R_mp,
-                                            [bot_J0_m, th_J0_m], out[l][0], out[l][1], dwf, uwf)
+                    if th:
+                        level_radiance_src_(pol, scene.qp, model.vza, model.vaz, m, float(weight), A, aa, bot_R_mp, cc, out[l][0],
+                                            out[l][1], dwf, uwf)
                     else:
                         level_radiance_(pol, scene.qp, model.vza, model.vaz, m, float(weight), A, a, bot_R_mp, bot_J0_m, out[l][0],
                                         out[l][1], dwf, uwf)
@@ -435,21 +470,33 @@ def _run(scene: CR.Scene, plan: LevelPlan, streams: bool):
                         fv[l] = (uwf, dwf)
 
                 def run_segment(seg, first, end):
-                    _run_segment(scene, mom, seg, first, end)
+                    _run_segment(scene, mom, seg[0], first, end)
                     if th:
-                        slot.walk(mom, th_of[id(seg)], first, end, scene.thermal_B)
+                        slot.walk(mom, seg[1], first, end, scene.thermal_B)
 
                 def join_surface(seg):
-                    CR.interaction_(mom["iface_surface"], seg, asurf, work=scene.work)
+                    CR.interaction_(mom["iface_surface"], seg[0], asurf, work=scene.work)
                     if th:
-                        CR.interaction_(mom["iface_surface"], th_of[id(seg)], th_surf, oplevel=True, work=scene.work)
+                        CR.interaction_(mom["iface_surface"], seg[1], th_surf, oplevel=True, work=scene.work)
 
                 def join_bottom(seg, bot, first, end):
-                    CR.interaction_("11", seg, _CompositeAsAdded(bot), work=scene.work)
+                    CR.interaction_("11", seg[0], _CompositeAsAdded(bot[0]), work=scene.work)
                     if th:
-                        CR.interaction_("11", th_of[id(seg)], _CompositeAsAdded(th_of[id(bot)]), oplevel=True, work=scene.work)
+                        CR.interaction_("11", seg[1], _CompositeAsAdded(bot[1]), oplevel=True, work=scene.work)
                 # 2.-4. the levels below the top pass
                 walk_levels(plan, segs, run_segment, join_surface, join_bottom, level)
+                tops[k].clear()
+                if sink is not None:
+                    # level 0, the TOA itself: J0- of the whole column with the surface, and the thermal slot's (ThermalSlot.finish
+                    # without its post-processing)
+                    if 0 in plan.distinct:
+                        CR.interaction_(mom["iface_surface"], comp, asurf, work=scene.work)
+                        J0_m = [comp.J0_m]
+                        if th:
+                            CR.interaction_(mom["iface_surface"], slot.comp, th_surf, oplevel=True, work=scene.work)
+                            J0_m.append(slot.comp.J0_m)
+                        sink.level0(mom, J0_m)
+                    continue
                 # level 0: rt_run's surface interaction and post-processing (no Cox-Munk single-scattering correction), then the
                 # thermal slot's, in rt_run's order of accumulation into R_SFI / T_SFI
                 CR.interaction_(mom["iface_surface"], comp, asurf, work=scene.work)
@@ -462,7 +509,6 @@ def _run(scene: CR.Scene, plan: LevelPlan, streams: bool):
                         fv[0][0].add_(slot.comp.J0_m)
                         fv[0][1].add_(slot.comp.J0_p)
                     full[m] = fv
-                tops[k].clear()
     return out, full, weights
 
 

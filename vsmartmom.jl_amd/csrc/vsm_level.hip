@@ -5,26 +5,29 @@
 //   dw = (I - A B)^-1 (a + A c),   uw = (I - B A)^-1 (c + B a),   A = top R+-, a = top J0+, B = bottom R-+, c = bottom J0-
 //
 // The reference forms two inverses and four products.  Here uw comes from dw by the push-through identity
-// (I - B A)^-1 (c + B a) = c + B (I - A B)^-1 (a + A c) = c + B dw, and dw from ONE pivoted Gauss-Jordan elimination of [M | d]:
-//   1. [M | d] = [I - A B | a + A c] in one MFMA product (c rides as the spare column N of B), written to LDS;
-//   2. Gauss-Jordan on [M | d] in LDS, the pivot rule of vsm_inverse.h (largest |m_ik|, first occurrence) -- no inverse;
-//   3. uw = c + B dw (mat-vec), then the VZA rows of uw / dw added into the caller's [nV, n_stokes, S] outputs.
-// One spectral point per 256-thread workgroup, N <= 128 (FP64 [M | d]: 129 KiB of LDS at N = 128).  Larger N: the operator-level
-// twin (batched products + vsm_batch_inv + products + vsm_postprocess_vza), the same contract.
-//
-// vsm_level_radiance_ie_*: the first-order (Raman) part of the same equation, interlayer_flux_helper!(::RRS) (interlayer_flux.jl:
-// 21-77), per recipient point with the lines summed before ONE solve of the same [I - A B | r] (k_level_radiance_ie, below).
-// vsm_level_radiance_lin_*: its derivative with respect to the Jacobian parameters, the parameters as extra right-hand sides of
-// ONE solve per chunk (k_level_radiance_lin, below).  vsm_level_radiance_lin_src_*: the same with P_src further SOURCE-ONLY slots
-// (the Planck slots of a linearized multi-sensor run with thermal emission), one body (level_lin_body, k_level_radiance_lin_src).
-// vsm_level_radiance_src_*: the same equation for up to VSM_LEVEL_MAX_SRC source pairs (a_k, c_k) on the same A, B (the solar and
-// the thermal slot), the pairs as right-hand sides of ONE solve, their level vectors summed (k_level_radiance_src, below).
-// vsm_level_flux_*: that system again, its level vectors reduced in LDS to hemispheric quadratures (the fluxes of rt_run_fluxes;
-// k_level_flux, below), and the TOA itself, which has no system.  vsm_level_flux_lin_*: the derivative level vectors of
-// vsm_level_radiance_lin_src_* reduced to the same quadratures, one per slot (the flux Jacobians of CoreRTLin.rt_run_fluxes;
-// level_lin_body's third epilogue, k_level_flux_lin, below).
-// vsm_surface_emission_response_*: the same system between the atmosphere and the surface layer for the unit emission patterns of
-// SurfaceSIF, kept per component (k_emission_response, below).
+// (I - B A)^-1 (c + B a) = c + B (I - A B)^-1 (a + A c) = c + B dw, and dw from ONE pivoted Gauss-Jordan elimination of [M | d].
+// Every fused kernel is the same solve body (level_solve_columns) for K right-hand sides at once:
+//   1. [M | d_k] = [I - A B | a_k + A c_k] in one MFMA product (the c_k ride as the spare columns of B), written to LDS;
+//   2. Gauss-Jordan on [M | d_k] in LDS, the pivot rule of vsm_inverse.h (largest |m_ik|, first occurrence) -- no inverse;
+//   3. dw_k = d_k / m_ii,  uw_k = c_k + B dw_k (mat-vec);
+// what differs is where the right-hand sides come from and what is done with the vectors.  One spectral point per 256-thread
+// workgroup, N <= 128 (FP64 [M | d]: 129 KiB of LDS at N = 128).  Six fused kernels:
+//   k_level_radiance_src   vsm_level_radiance_* (K = 1) and vsm_level_radiance_src_* (up to VSM_LEVEL_MAX_SRC source pairs (a_k,
+//                          c_k) on the same A, B: the solar and the thermal slot): the level vectors summed over the sources,
+//                          their VZA rows added into the caller's [nV, n_stokes, S] outputs;
+//   k_level_flux           vsm_level_flux_*: the level vectors of the same sources reduced in LDS to hemispheric quadratures (the
+//                          fluxes of rt_run_fluxes), and the TOA itself, which has no system;
+//   k_level_radiance_ie    vsm_level_radiance_ie_*: the first-order (Raman) part of the same equation, interlayer_flux_helper!(::RRS)
+//                          (interlayer_flux.jl:21-77), per recipient point with the lines summed before ONE solve of [I - A B | r];
+//   k_level_radiance_lin_src   vsm_level_radiance_lin_* (P_src = 0) and vsm_level_radiance_lin_src_*: the derivative with respect
+//                          to the Jacobian parameters, the parameters as right-hand sides of ONE solve per chunk, and P_src
+//                          further SOURCE-ONLY slots (the Planck slots of a linearized run with thermal emission); level_lin_body;
+//   k_level_flux_lin       vsm_level_flux_lin_*: the same derivative vectors reduced to the quadratures, one per slot (the flux
+//                          Jacobians of CoreRTLin.rt_run_fluxes); level_lin_body's other epilogue;
+//   k_emission_response    vsm_surface_emission_response_*: the system between the atmosphere and the surface layer for the unit
+//                          emission patterns of SurfaceSIF, kept per component.
+// Larger N (vsm_level_radiance_* alone): the operator-level twin (batched products + vsm_batch_inv + products +
+// vsm_postprocess_vza), the same contract.
 #include "vsm_common.h"
 #include "vsm_internal.h"
 #include "vsm_inverse.h"
@@ -117,65 +120,72 @@ __device__ __forceinline__ void level_eliminate(int N, int NC, int LD, T* L, int
   }
 }
 
-// Steps 1-3 for ONE point with one right-hand side (elastic and inelastic kernel): [M | d] = [I - A B | a + A c], Gauss-Jordan,
-// dw -> xs, uw = c + B dw -> ys, then dw_full / uw_full [N,1,S] (nullable) and the VZA rows accumulated into uw / dw.  Before the
-// barrier that precedes the call: a in column N of L, c in cs (LDS; cs may be ys: thread i reads c_i before it writes uw_i),
-// sh[1] = 0.
+// The solve body of every fused level kernel, for K right-hand sides (LD >= N + K).  Before the barrier that precedes the call:
+// the right-hand sides s_k in columns N .. N + K - 1 of L, the q_k in Q [K][N], sh[1] = 0.  After it, behind a barrier:
+//   dw_k = (I - A B)^-1 (s_k + A q_k) in column N + k of L,   uw_k = q_k + B dw_k in Q[k].
 template <typename T>
-__device__ __forceinline__ void level_solve_point(int N, int ns, int nV, int nVtot, const level_pp& pa, long long s, const T* As,
-                                                  const T* Bs, const T* cs, T* L, T* xs, T* ys, T* uw, T* dw, T* dw_full,
-                                                  T* uw_full, int* sh, int* status) {
-  const int LD = N + 1, tid = threadIdx.x;
-  level_form_system<T>(N, N + 1, LD, As, Bs, cs, L, sh, status);
-  level_eliminate<T>(N, N + 1, LD, L, sh, status);
-  for (int i = tid; i < N; i += LEVEL_NT) xs[i] = L[i * LD + N] / L[i * LD + i];
-  __syncthreads();
-
-  // 3. uw = c + B dw
-  for (int i = tid; i < N; i += LEVEL_NT) {
-    T y = cs[i];
-    for (int j = 0; j < N; ++j) y += Bs[(long long)j * N + i] * xs[j];
-    ys[i] = y;
-    if (dw_full) dw_full[s * N + i] = xs[i];
-    if (uw_full) uw_full[s * N + i] = y;
+__device__ __forceinline__ void level_solve_columns(int N, int K, int LD, const T* As, const T* Bs, T* L, T* Q, int* sh, int* status) {
+  const int tid = threadIdx.x;
+  level_form_system<T>(N, N + K, LD, As, Bs, Q, L, sh, status);
+  level_eliminate<T>(N, N + K, LD, L, sh, status);
+  // dw_k = column / m_ii (in place: each element is read and written by its own thread)
+  for (int e = tid; e < N * K; e += LEVEL_NT) {
+    const int i = e % N, k = e / N;
+    L[i * LD + N + k] = L[i * LD + N + k] / L[i * LD + i];
   }
   __syncthreads();
-  for (int e = tid; e < nV * ns; e += LEVEL_NT) {
-    const int v = e % nV, k = e / nV;
-    const T w = (T)pa.w[v + nV * k];
-    const long long dst = (s * ns + k) * nVtot + v;
-    uw[dst] += w * ys[pa.row0[v] + k];
-    dw[dst] += w * xs[pa.row0[v] + k];
+  for (int e = tid; e < N * K; e += LEVEL_NT) {
+    const int i = e % N, k = e / N;
+    T y = Q[k * N + i];
+    for (int j = 0; j < N; ++j) y += Bs[(long long)j * N + i] * L[j * LD + N + k];
+    Q[k * N + i] = y;   // (row i of Q[k] is read by this thread alone until the barrier)
   }
+  __syncthreads();
 }
 
+// The sum over the K sources, in place: column N of L = dw_1 + dw_2 + .. and Q[0] = uw_1 + uw_2 + .., added in that order (each
+// row by its own thread), then a barrier.  K = 1: nothing to do.
 template <typename T>
-__global__ void __launch_bounds__(LEVEL_NT) k_level_radiance(int N, int ns, int nV, int nVtot, level_pp pa, const T* __restrict__ A,
-                                                             const T* __restrict__ a, const T* __restrict__ B, long long bstride,
-                                                             const T* __restrict__ c, T* uw, T* dw, T* dw_full, T* uw_full,
-                                                             int* status) {
-  extern __shared__ __align__(16) unsigned char lds_raw[];
-  T* L = reinterpret_cast<T*>(lds_raw);          // [M | d], row-major, leading dimension LD = N + 1
-  T* xs = L + (size_t)N * (N + 1);               // dw
-  T* ys = xs + N;                                // c, then uw
-  __shared__ int sh[2];
-  const long long s = blockIdx.x;
-  if (threadIdx.x == 0) sh[1] = 0;
+__device__ __forceinline__ void level_sum_columns(int N, int K, int LD, T* L, T* Q) {
+  if (K == 1) return;
   for (int i = threadIdx.x; i < N; i += LEVEL_NT) {
-    L[i * (N + 1) + N] = a[s * N + i];
-    ys[i] = c[s * N + i];
+    T x = L[i * LD + N], y = Q[i];
+    for (int k = 1; k < K; ++k) {
+      x += L[i * LD + N + k];
+      y += Q[k * N + i];
+    }
+    L[i * LD + N] = x;
+    Q[i] = y;
   }
   __syncthreads();
-  level_solve_point<T>(N, ns, nV, nVtot, pa, s, A + s * (long long)N * N, B + s * bstride, ys, L, xs, ys, uw, dw, dw_full, uw_full,
-                       sh, status);
+}
+
+// The epilogue of the radiance kernels for ONE vector pair, dw in column N of L and uw in Q[0]: dw_full / uw_full [N,1,S]
+// (nullable) and the VZA rows accumulated into uw / dw [nV, n_stokes, S].
+template <typename T>
+__device__ __forceinline__ void level_radiance_out(int N, int ns, int LD, int nV, const level_pp& pa, long long s, const T* L,
+                                                   const T* Q, T* uw, T* dw, T* dw_full, T* uw_full) {
+  const int tid = threadIdx.x;
+  if (dw_full || uw_full) {
+    for (int i = tid; i < N; i += LEVEL_NT) {
+      if (dw_full) dw_full[s * N + i] = L[i * LD + N];
+      if (uw_full) uw_full[s * N + i] = Q[i];
+    }
+  }
+  for (int e = tid; e < nV * ns; e += LEVEL_NT) {
+    const int v = e % nV, c = e / nV, row = pa.row0[v] + c;
+    const T w = (T)pa.w[v + nV * c];
+    const long long dst = (s * ns + c) * nV + v;
+    uw[dst] += w * Q[row];
+    dw[dst] += w * L[row * LD + N];
+  }
 }
 
 // The level equation for K = n_src source pairs (a_k, c_k) on the SAME operators (vsm_level_radiance_src_*: the solar and the
 // thermal slot of a multi-sensor run), point s = blockIdx.x:
-//   [M | d_1 .. d_K] = [I - A B | a_k + A c_k] (level_form_system, the c_k as spare columns of B), ONE Gauss-Jordan elimination,
-//   dw_k = column / m_ii (in place),  uw_k = c_k + B dw_k (into Q),
-// then the SUM over k: dw_full / uw_full [N,1,S] (nullable) and the VZA rows accumulated into uw / dw.  K = 1 is k_level_radiance
-// operation for operation.  LDS: L [N][N + K], Q [K][N].
+//   level_solve_columns on [M | d_1 .. d_K] = [I - A B | a_k + A c_k],  then the SUM over k (level_sum_columns) and
+//   level_radiance_out of that one vector pair.
+// K = 1 is vsm_level_radiance_* itself (N <= 128): one right-hand side, nothing to sum.  LDS: L [N][N + K], Q [K][N].
 template <typename T>
 struct level_srcs {
   const T* a[VSM_LEVEL_MAX_SRC];
@@ -205,54 +215,46 @@ __global__ void __launch_bounds__(LEVEL_NT) k_level_radiance_src(int N, int ns, 
     }
   }
   __syncthreads();
-  level_form_system<T>(N, N + K, LD, A + s * (long long)N * N, Bs, Q, L, sh, status);
-  level_eliminate<T>(N, N + K, LD, L, sh, status);
-  for (int e = tid; e < N * K; e += LEVEL_NT) {
-    const int i = e % N, k = e / N;
-    L[i * LD + N + k] = L[i * LD + N + k] / L[i * LD + i];
-  }
-  __syncthreads();
-  for (int e = tid; e < N * K; e += LEVEL_NT) {
-    const int i = e % N, k = e / N;
-    T y = Q[k * N + i];
-    for (int j = 0; j < N; ++j) y += Bs[(long long)j * N + i] * L[j * LD + N + k];
-    Q[k * N + i] = y;
-  }
-  __syncthreads();
-  if (dw_full || uw_full) {
-    for (int i = tid; i < N; i += LEVEL_NT) {
-      T x = L[i * LD + N], y = Q[i];
-      for (int k = 1; k < K; ++k) {
-        x += L[i * LD + N + k];
-        y += Q[k * N + i];
+  level_solve_columns<T>(N, K, LD, A + s * (long long)N * N, Bs, L, Q, sh, status);
+  level_sum_columns<T>(N, K, LD, L, Q);
+  level_radiance_out<T>(N, ns, LD, nV, pa, s, L, Q, uw, dw, dw_full, uw_full);
+}
+
+// The hemispheric quadratures of n_vec vector pairs in LDS (level_lin_body; k_level_flux has the same reduction with the sum
+// over its sources inside it): wave e % 4 takes item e = (v, r, d) and writes, for weight row r < nW (q: DEVICE [nW][N / ns], one weight per stream) and direction d,
+//   out[d][r][slot0 + v][s] = sum_i q[r][i] vec_d[v][i ns]      (d = 0: up[v up_vs + row up_is], d = 1: dn likewise; !has_dn: 0)
+// the rows of Stokes I.  A lane adds its stream i = lane, then lane + 64, then a butterfly over the wave: the order of the
+// additions depends on N and ns alone.
+template <typename T>
+__device__ __forceinline__ void level_flux_reduce(int Nq, int ns, int nW, int n_vec, const T* __restrict__ q, const T* up, int up_vs,
+                                                  int up_is, const T* dn, int dn_vs, int dn_is, bool has_dn, T* out, int slot0,
+                                                  int slots, long long S, long long s) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  for (int e = wave; e < 2 * nW * n_vec; e += LEVEL_NT / 64) {
+    const int d = e & 1, r = (e >> 1) % nW, v = e / (2 * nW);
+    T acc = T(0);
+    if (d == 0 || has_dn) {
+      for (int i = lane; i < Nq; i += 64) {
+        const int row = i * ns;
+        const T x = d ? dn[v * dn_vs + row * dn_is] : up[v * up_vs + row * up_is];
+        acc += q[r * Nq + i] * x;
       }
-      if (dw_full) dw_full[s * N + i] = x;
-      if (uw_full) uw_full[s * N + i] = y;
     }
-  }
-  for (int e = tid; e < nV * ns; e += LEVEL_NT) {
-    const int v = e % nV, c = e / nV, row = pa.row0[v] + c;
-    const T w = (T)pa.w[v + nV * c];
-    T x = L[row * LD + N], y = Q[row];
-    for (int k = 1; k < K; ++k) {
-      x += L[row * LD + N + k];
-      y += Q[k * N + row];
-    }
-    const long long dst = (s * ns + c) * nV + v;
-    uw[dst] += w * y;
-    dw[dst] += w * x;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+    if (lane == 0) out[(((long long)d * nW + r) * slots + slot0 + v) * S + s] = acc;
   }
 }
 
 // Hemispheric quadratures of the level vectors (vsm_level_flux_*: the up, down and actinic fluxes of rt_run_fluxes), point
-// s = blockIdx.x.  k_level_radiance_src's system for the K source pairs, the same two halves:
-//   [M | d_1 .. d_K] = [I - A B | a_k + A c_k],  ONE Gauss-Jordan elimination,  dw_k = column / m_ii,  uw_k = c_k + B dw_k (into Q);
-// A == nullptr: no layer above the level (the TOA), no system: dw = 0, uw_k = c_k.  The vectors stay in LDS; for each weight row
-// r < nW (q: DEVICE [nW][N / ns], one weight per stream) and direction d, wave (2 r + d) % 4 takes
+// s = blockIdx.x.  k_level_radiance_src's system for the K source pairs (level_solve_columns); A == nullptr: no layer above the
+// level (the TOA), no system: dw = 0, uw_k = c_k.  The vectors stay in LDS; for each weight row r < nW (q: DEVICE [nW][N / ns], one
+// weight per stream) and direction d, wave (2 r + d) % 4 takes
 //   out[d][r][s] = sum_i q[r][i] * sum_k v_k[i ns]      (v = uw for d = 0, dw for d = 1: the rows of Stokes I)
 // lanes over i (a lane adds its stream i = lane, then lane + 64), then a butterfly over the wave: the order of the additions
-// depends on N, K and nW alone.  out[2][r][s] = dir[r] F0_I[s] exp(-tau_sum[s] / mu0) with both arrays given, else 0.  Every
-// element of out [3][nW][S] is WRITTEN.  LDS: L [N][N + K], Q [K][N].
+// depends on N, K and nW alone.  The sum over k stays inside this reduction and is not level_sum_columns + level_flux_reduce:
+// that form gives the same bits but was measured 2.7 % slower per call.  out[2][r][s] = dir[r] F0_I[s]
+// exp(-tau_sum[s] / mu0) with both arrays given, else 0.  Every element of out [3][nW][S] is WRITTEN.  LDS: L [N][N + K], Q [K][N].
 template <typename T>
 struct level_flux_dir {
   T h[4];
@@ -283,23 +285,8 @@ __global__ void __launch_bounds__(LEVEL_NT) k_level_flux(int N, int ns, int K, i
     }
   }
   __syncthreads();
-  if (A) {   // (the same for the whole grid)
-    const T* Bs = B + s * bstride;
-    level_form_system<T>(N, N + K, LD, A + s * (long long)N * N, Bs, Q, L, sh, status);
-    level_eliminate<T>(N, N + K, LD, L, sh, status);
-    for (int e = tid; e < N * K; e += LEVEL_NT) {
-      const int i = e % N, k = e / N;
-      L[i * LD + N + k] = L[i * LD + N + k] / L[i * LD + i];
-    }
-    __syncthreads();
-    for (int e = tid; e < N * K; e += LEVEL_NT) {
-      const int i = e % N, k = e / N;
-      T y = Q[k * N + i];
-      for (int j = 0; j < N; ++j) y += Bs[(long long)j * N + i] * L[j * LD + N + k];
-      Q[k * N + i] = y;
-    }
-    __syncthreads();
-  }
+  if (A)   // (the same for the whole grid)
+    level_solve_columns<T>(N, K, LD, A + s * (long long)N * N, B + s * bstride, L, Q, sh, status);
   const int Nq = N / ns;
   for (int p = wave; p < 2 * nW; p += LEVEL_NT / 64) {
     const int r = p >> 1, d = p & 1;
@@ -367,20 +354,20 @@ __device__ __forceinline__ void level_stream_reduce(int N, int G, int g, int i, 
 // The inelastic level equation (vsm_level_radiance_ie_*) of recipient point n1 = blockIdx.x, lines summed before the solve:
 //   q = sum_k [c_ie,k + B_ie,k dw(n0)],  r = sum_k [a_ie,k + A_ie,k uw(n0)] + A q,  dw_ie = (I - A B)^-1 r,  uw_ie = q + B dw_ie
 // over the in-band lines k (n0 = n1 + shift[k] in 0..S-1); dw / uw are the ELASTIC level vectors of the donors.
-// Phase 1 streams the 2K ie blocks of the point by column groups; phase 2 is level_solve_point with (a, c) = (r - A q, q).
+// Phase 1 streams the 2K ie blocks of the point by column groups; phase 2 is level_solve_columns with ONE right-hand side,
+// (s, q) = (r - A q, q), and level_radiance_out.  LDS: L [N][N + 1], q [N], partial sums [2][G][N].
 template <typename T>
 __global__ void __launch_bounds__(LEVEL_NT) k_level_radiance_ie(int N, int ns, int S, int K, const int* __restrict__ shift, int nV,
-                                                                int nVtot, level_pp pa, const T* __restrict__ A,
+                                                                level_pp pa, const T* __restrict__ A,
                                                                 const T* __restrict__ B, long long bstride,
                                                                 const T* __restrict__ dwf, const T* __restrict__ uwf,
                                                                 const T* __restrict__ Aie, const T* __restrict__ aie,
                                                                 const T* __restrict__ Bie, const T* __restrict__ cie, T* uwie,
                                                                 T* dwie, T* dwie_full, T* uwie_full, int* status) {
   extern __shared__ __align__(16) unsigned char lds_raw[];
-  T* L = reinterpret_cast<T*>(lds_raw);          // [M | r], row-major, leading dimension N + 1
-  T* xs = L + (size_t)N * (N + 1);               // dw_ie
-  T* ys = xs + N;                                // uw_ie
-  T* qs = ys + N;                                // q
+  const int LD = N + 1;
+  T* L = reinterpret_cast<T*>(lds_raw);          // [M | r], row-major, leading dimension N + 1; column N: then dw_ie
+  T* qs = L + (size_t)N * LD;                    // q, then uw_ie
   T* part = qs + N;                              // [2][G][N] partial sums
   __shared__ int sh[2];
   const int tid = threadIdx.x;
@@ -398,9 +385,9 @@ __global__ void __launch_bounds__(LEVEL_NT) k_level_radiance_ie(int N, int ns, i
                                  cie ? cie + blk * N : nullptr, dwf + (long long)n0 * N, acc);
     }
   }
-  level_stream_reduce<T>(N, G, g, i, acc, part, L + N, N + 1, qs, 1);
-  level_solve_point<T>(N, ns, nV, nVtot, pa, n1, A + n1 * NN, B + n1 * bstride, qs, L, xs, ys, uwie, dwie, dwie_full, uwie_full, sh,
-                       status);
+  level_stream_reduce<T>(N, G, g, i, acc, part, L + N, LD, qs, 1);
+  level_solve_columns<T>(N, 1, LD, A + n1 * NN, B + n1 * bstride, L, qs, sh, status);
+  level_radiance_out<T>(N, ns, LD, nV, pa, n1, L, qs, uwie, dwie, dwie_full, uwie_full);
 }
 
 // The VZA table of one launch and what to do above the 64 viewing angles it carries: the level vectors in full (the caller's
@@ -426,26 +413,7 @@ static int level_launch(int ns, int nV, const int* row0_h, const T* w_h, size_t 
   return rc ? rc : post(uw_full, dw_full);
 }
 
-template <typename T>
-static int level_radiance_fused(int N, int ns, int S, int nV, const int* row0_h, const T* w_h, const T* A, const T* a, const T* B,
-                                long long bstride, const T* c, T* uw, T* dw, T* dw_full, T* uw_full, hipStream_t st) {
-  int* status = device_status();
-  if (!status) return VSM_ERR_HIP;
-  const size_t lds = ((size_t)N * (N + 1) + 2 * (size_t)N) * sizeof(T);
-  const int rc = ensure_dyn_lds(reinterpret_cast<const void*>(k_level_radiance<T>), lds, "hipFuncSetAttribute(k_level_radiance)");
-  if (rc) return rc;
-  return level_launch<T>(
-      ns, nV, row0_h, w_h, (size_t)N * S, dw_full, uw_full, st,
-      [&](int nv, const level_pp& pa, T* dwf, T* uwf) {
-        hipLaunchKernelGGL(k_level_radiance<T>, dim3(S), dim3(LEVEL_NT), lds, st, N, ns, nv, nv, pa, A, a, B, bstride, c, uw, dw, dwf,
-                           uwf, status);
-        VSM_LAUNCH_CHECK("k_level_radiance");
-        return (int)VSM_OK;
-      },
-      [&](const T* uwf, const T* dwf) { return postprocess_vza<T>(N, ns, S, nV, row0_h, w_h, uwf, dwf, uw, dw, st); });
-}
-
-// LDS of k_level_radiance_src against the budget of level_lin_chunk (160 KiB less room for the static words)
+// LDS of the K-source kernels (radiance-src, flux, emission response), checked against 160 KiB less room for the static words
 template <typename T>
 static size_t level_src_lds(int N, int K) {
   return ((size_t)N * (N + K) + (size_t)K * N) * sizeof(T);
@@ -477,6 +445,13 @@ static int level_radiance_src_fused(int N, int ns, int S, int nV, const int* row
       [&](const T* uwf, const T* dwf) { return postprocess_vza<T>(N, ns, S, nV, row0_h, w_h, uwf, dwf, uw, dw, st); });
 }
 
+// vsm_level_radiance_* (N <= 128): the K-source kernel with one source
+template <typename T>
+static int level_radiance_fused(int N, int ns, int S, int nV, const int* row0_h, const T* w_h, const T* A, const T* a, const T* B,
+                                long long bstride, const T* c, T* uw, T* dw, T* dw_full, T* uw_full, hipStream_t st) {
+  return level_radiance_src_fused<T>(N, ns, S, nV, row0_h, w_h, A, 1, &a, B, bstride, &c, uw, dw, dw_full, uw_full, st);
+}
+
 template <typename T>
 static int level_flux_fused(int N, int ns, int S, const T* A, int K, const T* const* a, const T* B, long long bstride,
                             const T* const* c, int nW, const T* q, const T* dir_h, T mu0, const T* tau_sum, const T* F0_I, T* out,
@@ -502,35 +477,18 @@ static int level_flux_fused(int N, int ns, int S, const T* A, int K, const T* co
 }
 
 template <typename T>
-static int level_flux_check(int N, int ns, int S, const T* A, int K, const T* const* a, const T* B, long long bstride,
-                            const T* const* c, int nW, const T* q, const T* dir_h, T mu0, const T* tau_sum, const T* F0_I,
-                            const T* out) {
-  VSM_REQUIRE(K >= 1 && K <= VSM_LEVEL_MAX_SRC, "level_flux: n_src = %d outside 1..%d", K, (int)VSM_LEVEL_MAX_SRC);
-  VSM_REQUIRE(nW >= 1 && nW <= 4, "level_flux: nW = %d outside 1..4", nW);
-  VSM_REQUIRE(N > 0 && ns >= 1 && ns <= 4 && N % ns == 0 && S >= 0, "level_flux: bad size (N %d, n_stokes %d, S %d)", N, ns, S);
-  VSM_REQUIRE(N <= LEVEL_FUSED_MAX_N, "level_flux: N = %d > %d, the limit of its kernel", N, LEVEL_FUSED_MAX_N);
-  VSM_REQUIRE(bstride == 0 || bstride == (long long)N * N, "level_flux: bot_stride must be 0 or N*N");
-  VSM_REQUIRE((tau_sum == nullptr) == (F0_I == nullptr), "level_flux: tau_sum and F0_I are both given or both NULL");
-  VSM_REQUIRE(!tau_sum || (dir_h && mu0 > T(0)), "level_flux: the direct term needs dir_h and mu0 > 0");
-  VSM_REQUIRE(S == 0 || (c && q && out), "level_flux: null bottom source list / weight rows / output");
-  VSM_REQUIRE(S == 0 || !A || (a && B), "level_flux: a top needs its sources and the bottom's R-+");
-  for (int k = 0; k < K && S > 0; ++k) VSM_REQUIRE(c[k] && (!A || a[k]), "level_flux: null source %d", k);
-  return VSM_OK;
-}
-
-template <typename T>
 static int level_radiance_ie_fused(int N, int ns, int S, int K, const int* shift, int nV, const int* row0_h, const T* w_h, const T* A,
                                    const T* B, long long bstride, const T* dwf, const T* uwf, const T* Aie, const T* aie,
                                    const T* Bie, const T* cie, T* uwie, T* dwie, T* dwie_full, T* uwie_full, hipStream_t st) {
   int* status = device_status();
   if (!status) return VSM_ERR_HIP;
-  const size_t lds = ((size_t)N * (N + 1) + 3 * (size_t)N + 2 * (size_t)LEVEL_NT) * sizeof(T);
+  const size_t lds = ((size_t)N * (N + 1) + (size_t)N + 2 * (size_t)LEVEL_NT) * sizeof(T);
   const int rc = ensure_dyn_lds(reinterpret_cast<const void*>(k_level_radiance_ie<T>), lds, "hipFuncSetAttribute(k_level_radiance_ie)");
   if (rc) return rc;
   return level_launch<T>(
       ns, nV, row0_h, w_h, (size_t)N * S, dwie_full, uwie_full, st,
       [&](int nv, const level_pp& pa, T* df, T* uf) {
-        hipLaunchKernelGGL(k_level_radiance_ie<T>, dim3(S), dim3(LEVEL_NT), lds, st, N, ns, S, K, shift, nv, nv, pa, A, B, bstride,
+        hipLaunchKernelGGL(k_level_radiance_ie<T>, dim3(S), dim3(LEVEL_NT), lds, st, N, ns, S, K, shift, nv, pa, A, B, bstride,
                            dwf, uwf, Aie, aie, Bie, cie, uwie, dwie, df, uf, status);
         VSM_LAUNCH_CHECK("k_level_radiance_ie");
         return (int)VSM_OK;
@@ -544,18 +502,17 @@ static int level_radiance_ie_fused(int N, int ns, int S, int K, const int* shift
 // PC; per chunk:
 //   1. the bottom blocks B'_p, c'_p (every slot) and the top blocks A'_p, a'_p (slots < P_top) streamed by column groups:
 //      q_p -> Q[pc], s_p = a'_p + A'_p uw -> column N + pc of L;
-//   2. [M | r_1 .. r_PC] = [I - A B | s + A q] (level_form_system), then ONE Gauss-Jordan elimination of the whole block
-//      (level_eliminate: same M, same rule as the elastic call, hence its pivots);
-//   3. dw'_p = column / m_ii (in place), uw'_p = q_p + B dw'_p (into Q), the VZA rows ACCUMULATED into [P, S, n_stokes, nV].
-// LDS: L [N][N + PC], Q [PC][N], dw / uw [2][N], partial sums [2][G][N].
-// SRC: P_src further slots p = P .. P + P_src - 1 that carry a SOURCE alone (vsm_level_radiance_lin_src_*: the equation is linear
+//   2. level_solve_columns on [M | r_1 .. r_PC] = [I - A B | s + A q]: ONE Gauss-Jordan elimination of the whole block (same M,
+//      same rule as the elastic call, hence its pivots), dw'_p in column N + pc of L, uw'_p = q_p + B dw'_p in Q[pc];
+//   3. dwd_full / uwd_full (nullable) and the VZA rows ACCUMULATED into [P, S, n_stokes, nV].
+// LDS (level_lin_lds): L [N][N + PC], Q [PC][N], dw / uw [2][N], partial sums [2][G][N].
+// P_src further slots p = P .. P + P_src - 1 carry a SOURCE alone (vsm_level_radiance_lin_src_*: the equation is linear
 // in (a, c), so the derivative with respect to a parameter that only scales the sources is the level equation of those sources):
 //   q_p = c_k,   r_p = a_k + A c_k,   dw'_p = (I - A B)^-1 r_p,   uw'_p = c_k + B dw'_p        (k = p - P)
 // a_k = asrc [N,1,S,P_src], c_k = csrc likewise.  Such a slot reads no operator derivative: step 1 copies c_k into Q[pc] and a_k into
 // column N + pc of L, and steps 2-3 do not tell the two kinds apart (the c_k ride as spare columns of B like every q_p), so a chunk
-// may mix them.  SRC = false is k_level_radiance_lin as it was, statement for statement; SRC = true with P_src = 0 issues the same
-// arithmetic in the same order (one more barrier per chunk).
-// FLUX (vsm_level_flux_lin_*, SRC = true): steps 1-3 as they are, but the derivative vectors stay in LDS and a third epilogue
+// may mix them.  P_src = 0 is vsm_level_radiance_lin_* itself: no slot takes that branch.
+// FLUX (vsm_level_flux_lin_*): steps 1-2 as they are, but the derivative vectors stay in LDS and another epilogue
 // (level_flux_reduce) writes their hemispheric quadratures, slot 1 + p of fx.out [3][nW][1 + P + P_src][S]; slot 0 is the same
 // quadrature of the elastic vectors dwf / uwf, and row 2 the direct beam and its derivative -direct tau_sum_dot[p] / mu0 (slots
 // p < p_layer; 0 elsewhere and without tau_sum).  A == nullptr (FLUX only; the same for the whole grid): the TOA, no system:
@@ -571,31 +528,7 @@ struct level_flux_lin_args {
   T* out;                 // [3][nW][1 + P + P_src][S], written
 };
 
-// k_level_flux's reduction for n_vec vector pairs in LDS: wave e % 4 takes item e = (v, r, d) and writes
-//   out[d][r][slot0 + v][s] = sum_i q[r][i] vec_d[v][i ns]      (d = 0: up[v up_vs + row up_is], d = 1: dn likewise; !has_dn: 0)
-// a lane adds its stream i = lane, then lane + 64, then a butterfly over the wave: the order depends on N and ns alone.
-template <typename T>
-__device__ __forceinline__ void level_flux_reduce(int Nq, int ns, int nW, int n_vec, const T* __restrict__ q, const T* up, int up_vs,
-                                                  int up_is, const T* dn, int dn_vs, int dn_is, bool has_dn, T* out, int slot0,
-                                                  int slots, long long S, long long s) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  for (int e = wave; e < 2 * nW * n_vec; e += LEVEL_NT / 64) {
-    const int d = e & 1, r = (e >> 1) % nW, v = e / (2 * nW);
-    T acc = T(0);
-    if (d == 0 || has_dn) {
-      for (int i = lane; i < Nq; i += 64) {
-        const int row = i * ns;
-        const T x = d ? dn[v * dn_vs + row * dn_is] : up[v * up_vs + row * up_is];
-        acc += q[r * Nq + i] * x;
-      }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
-    if (lane == 0) out[(((long long)d * nW + r) * slots + slot0 + v) * S + s] = acc;
-  }
-}
-
-template <typename T, bool SRC, bool FLUX = false>
+template <typename T, bool FLUX>
 __device__ __forceinline__ void level_lin_body(int N, int ns, int S, int P, int P_top, int P_src, int PC, int nV, const level_pp& pa,
                                                const T* __restrict__ A, const T* __restrict__ B, long long bstride,
                                                const T* __restrict__ dwf, const T* __restrict__ uwf, const T* __restrict__ Ad,
@@ -623,7 +556,7 @@ __device__ __forceinline__ void level_lin_body(int N, int ns, int S, int P, int 
     xs[i] = toa ? T(0) : dwf[s * N + i];
     ys[i] = uwf[s * N + i];
   }
-  const int Ptot = SRC ? P + P_src : P;
+  const int Ptot = P + P_src;
   if (FLUX) {   // slot 0: the quadratures of the elastic vectors; row 2: the direct beam and its derivatives
     __syncthreads();
     level_flux_reduce<T>(N / ns, ns, fx.nW, 1, fx.q, ys, 0, 1, xs, 0, 1, !toa, fx.out, 0, 1 + Ptot, S, s);
@@ -652,7 +585,7 @@ __device__ __forceinline__ void level_lin_body(int N, int ns, int S, int P, int 
         }
         continue;
       }
-      if (SRC && p >= P) {   // a source-only slot (the whole workgroup takes this branch together)
+      if (p >= P) {   // a source-only slot (the whole workgroup takes this branch together)
         const long long o = (long long)(p - P) * SN + s * N;
         for (int i = tid; i < N; i += LEVEL_NT) {
           Q[pc * N + i] = csrc[o + i];
@@ -667,32 +600,21 @@ __device__ __forceinline__ void level_lin_body(int N, int ns, int S, int P, int 
                                    top ? Ad + p * ad_pstride + s * NN : nullptr, top ? ad + p * SN + s * N : nullptr, ys, acc);
       level_stream_reduce<T>(N, G, g, i1, acc, part, Q + pc * N, 1, L + N + pc, LD);
     }
-    if (SRC) __syncthreads();   // (a chunk may end with source-only slots, which end without a barrier)
-    if (!toa) {
-      // 2. [M | r] and its elimination
-      const int NC = N + pc_n;
-      level_form_system<T>(N, NC, LD, As, Bs, Q, L, sh, status);
-      level_eliminate<T>(N, NC, LD, L, sh, status);
-      // 3. dw'_p = r_p / m_ii (in place: each element is read and written by its own thread), then uw'_p = q_p + B dw'_p
-      for (int e = tid; e < N * pc_n; e += LEVEL_NT) {
-        const int i = e % N, pc = e / N;
-        L[i * LD + N + pc] = L[i * LD + N + pc] / L[i * LD + i];
-      }
-      __syncthreads();
-      for (int e = tid; e < N * pc_n; e += LEVEL_NT) {
-        const int i = e % N, pc = e / N;
-        T y = Q[pc * N + i];
-        for (int j = 0; j < N; ++j) y += Bs[(long long)j * N + i] * L[j * LD + N + pc];
-        Q[pc * N + i] = y;
-        const long long o = (long long)(p0 + pc) * SN + s * N + i;
-        if (dwd_full) dwd_full[o] = L[i * LD + N + pc];
-        if (uwd_full) uwd_full[o] = y;
-      }
-      __syncthreads();
-    }
-    if (FLUX) {   // the third epilogue: the quadratures of the chunk's vectors, written
+    __syncthreads();   // (a chunk may end with source-only slots, which end without a barrier)
+    // 2. [M | r], its elimination, dw'_p and uw'_p = q_p + B dw'_p
+    if (!toa) level_solve_columns<T>(N, pc_n, LD, As, Bs, L, Q, sh, status);
+    if (FLUX) {   // the quadratures of the chunk's vectors, written
       level_flux_reduce<T>(N / ns, ns, fx.nW, pc_n, fx.q, Q, N, 1, L + N, 1, LD, true, fx.out, 1 + p0, 1 + Ptot, S, s);
       continue;
+    }
+    // 3. the full vectors and the VZA rows
+    if (dwd_full || uwd_full) {
+      for (int e = tid; e < N * pc_n; e += LEVEL_NT) {
+        const int i = e % N, pc = e / N;
+        const long long o = (long long)(p0 + pc) * SN + s * N + i;
+        if (dwd_full) dwd_full[o] = L[i * LD + N + pc];
+        if (uwd_full) uwd_full[o] = Q[pc * N + i];
+      }
     }
     for (int e = tid; e < nV * ns * pc_n; e += LEVEL_NT) {
       const int v = e % nV, k = (e / nV) % ns, pc = e / (nV * ns);
@@ -704,7 +626,7 @@ __device__ __forceinline__ void level_lin_body(int N, int ns, int S, int P, int 
   }
 }
 
-// vsm_level_flux_lin_*: level_lin_body<T, true, true> (no VZA table, no full vectors out)
+// vsm_level_flux_lin_*: level_lin_body<T, true> (no VZA table, no full vectors out)
 template <typename T>
 __global__ void __launch_bounds__(LEVEL_NT) k_level_flux_lin(int N, int ns, int S, int P, int P_top, int P_src, int PC,
                                                              const T* __restrict__ A, const T* __restrict__ B, long long bstride,
@@ -715,22 +637,11 @@ __global__ void __launch_bounds__(LEVEL_NT) k_level_flux_lin(int N, int ns, int 
                                                              const T* __restrict__ asrc, const T* __restrict__ csrc,
                                                              level_flux_lin_args<T> fx, int* status) {
   const level_pp pa = {};
-  level_lin_body<T, true, true>(N, ns, S, P, P_top, P_src, PC, 0, pa, A, B, bstride, dwf, uwf, Ad, ad_pstride, ad, Bd, bd_stride,
-                                bd_pstride, cd, asrc, csrc, nullptr, nullptr, nullptr, nullptr, status, fx);
+  level_lin_body<T, true>(N, ns, S, P, P_top, P_src, PC, 0, pa, A, B, bstride, dwf, uwf, Ad, ad_pstride, ad, Bd, bd_stride,
+                          bd_pstride, cd, asrc, csrc, nullptr, nullptr, nullptr, nullptr, status, fx);
 }
 
-template <typename T>
-__global__ void __launch_bounds__(LEVEL_NT) k_level_radiance_lin(int N, int ns, int S, int P, int P_top, int PC, int nV, level_pp pa,
-                                                                 const T* __restrict__ A, const T* __restrict__ B, long long bstride,
-                                                                 const T* __restrict__ dwf, const T* __restrict__ uwf,
-                                                                 const T* __restrict__ Ad, long long ad_pstride,
-                                                                 const T* __restrict__ ad, const T* __restrict__ Bd,
-                                                                 long long bd_stride, long long bd_pstride, const T* __restrict__ cd,
-                                                                 T* uwd, T* dwd, T* dwd_full, T* uwd_full, int* status) {
-  level_lin_body<T, false>(N, ns, S, P, P_top, 0, PC, nV, pa, A, B, bstride, dwf, uwf, Ad, ad_pstride, ad, Bd, bd_stride, bd_pstride,
-                           cd, nullptr, nullptr, uwd, dwd, dwd_full, uwd_full, status);
-}
-
+// vsm_level_radiance_lin_* (P_src = 0) and vsm_level_radiance_lin_src_*: level_lin_body<T, false>
 template <typename T>
 __global__ void __launch_bounds__(LEVEL_NT) k_level_radiance_lin_src(int N, int ns, int S, int P, int P_top, int P_src, int PC, int nV,
                                                                      level_pp pa, const T* __restrict__ A, const T* __restrict__ B,
@@ -741,79 +652,68 @@ __global__ void __launch_bounds__(LEVEL_NT) k_level_radiance_lin_src(int N, int 
                                                                      long long bd_pstride, const T* __restrict__ cd,
                                                                      const T* __restrict__ asrc, const T* __restrict__ csrc, T* uwd,
                                                                      T* dwd, T* dwd_full, T* uwd_full, int* status) {
-  level_lin_body<T, true>(N, ns, S, P, P_top, P_src, PC, nV, pa, A, B, bstride, dwf, uwf, Ad, ad_pstride, ad, Bd, bd_stride,
-                          bd_pstride, cd, asrc, csrc, uwd, dwd, dwd_full, uwd_full, status);
+  level_lin_body<T, false>(N, ns, S, P, P_top, P_src, PC, nV, pa, A, B, bstride, dwf, uwf, Ad, ad_pstride, ad, Bd, bd_stride,
+                           bd_pstride, cd, asrc, csrc, uwd, dwd, dwd_full, uwd_full, status);
 }
 
-// Parameters per chunk of k_level_radiance_lin: as many as the LDS holds (160 KiB less room for the static words), at most P
+// LDS of the linearized kernels with PC parameters per chunk (level_lin_body's layout)
 template <typename T>
-static int level_lin_chunk(int N, int P) {
-  const size_t budget = (160 * 1024 - 256) / sizeof(T), fixed = (size_t)N * N + 2 * (size_t)N + 2 * (size_t)LEVEL_NT;
-  const int pc = (int)((budget - fixed) / (2 * (size_t)N));
-  return pc < P ? pc : P;
+static size_t level_lin_lds(int N, int PC) {
+  return ((size_t)N * (N + PC) + (size_t)PC * N + 2 * (size_t)N + 2 * (size_t)LEVEL_NT) * sizeof(T);
 }
+
+// What a launch of a linearized kernel over Ptot slots needs: the status word, the parameters per chunk -- as many as the LDS
+// holds (160 KiB less room for the static words), at most Ptot -- and the LDS of that chunk, granted to `kernel`.
+struct level_lin_launch {
+  int* status;
+  int PC;
+  size_t lds;
+};
 
 template <typename T>
-static int level_radiance_lin_fused(int N, int ns, int S, int P, int P_top, int nV, const int* row0_h, const T* w_h, const T* A,
-                                    const T* B, long long bstride, const T* dwf, const T* uwf, const T* Ad, long long ad_pstride,
-                                    const T* ad, const T* Bd, long long bd_stride, long long bd_pstride, const T* cd, T* uwd,
-                                    T* dwd, T* dwd_full, T* uwd_full, hipStream_t st) {
-  int* status = device_status();
-  if (!status) return VSM_ERR_HIP;
-  const int PC = level_lin_chunk<T>(N, P);
-  const size_t lds = ((size_t)N * (N + PC) + (size_t)PC * N + 2 * (size_t)N + 2 * (size_t)LEVEL_NT) * sizeof(T);
-  const int rc = ensure_dyn_lds(reinterpret_cast<const void*>(k_level_radiance_lin<T>), lds, "hipFuncSetAttribute(k_level_radiance_lin)");
-  if (rc) return rc;
-  return level_launch<T>(
-      ns, nV, row0_h, w_h, (size_t)P * N * S, dwd_full, uwd_full, st,
-      [&](int nv, const level_pp& pa, T* df, T* uf) {
-        hipLaunchKernelGGL(k_level_radiance_lin<T>, dim3(S), dim3(LEVEL_NT), lds, st, N, ns, S, P, P_top, PC, nv, pa, A, B, bstride,
-                           dwf, uwf, Ad, ad_pstride, ad, Bd, bd_stride, bd_pstride, cd, uwd, dwd, df, uf, status);
-        VSM_LAUNCH_CHECK("k_level_radiance_lin");
-        return (int)VSM_OK;
-      },
-      [&](const T* uf, const T* df) { return postprocess_vza_lin<T>(N, ns, S, nV, P, row0_h, w_h, uf, df, uwd, dwd, st); });
+static int level_lin_setup(const void* kernel, const char* what, int N, int Ptot, level_lin_launch& su) {
+  su.status = device_status();
+  if (!su.status) return VSM_ERR_HIP;
+  const int pc = (int)((160 * 1024 - 256 - level_lin_lds<T>(N, 0)) / (2 * (size_t)N * sizeof(T)));
+  su.PC = pc < Ptot ? pc : Ptot;
+  su.lds = level_lin_lds<T>(N, su.PC);
+  return ensure_dyn_lds(kernel, su.lds, what);
 }
 
-// vsm_level_radiance_lin_src_*: the chunks of level_lin_chunk over all P + P_src slots, the same LDS layout and bound
+// vsm_level_radiance_lin_* (P_src = 0) and vsm_level_radiance_lin_src_*: the chunks over all P + P_src slots
 template <typename T>
 static int level_radiance_lin_src_fused(int N, int ns, int S, int P, int P_top, int P_src, int nV, const int* row0_h, const T* w_h,
                                         const T* A, const T* B, long long bstride, const T* dwf, const T* uwf, const T* Ad,
                                         long long ad_pstride, const T* ad, const T* Bd, long long bd_stride, long long bd_pstride,
                                         const T* cd, const T* asrc, const T* csrc, T* uwd, T* dwd, T* dwd_full, T* uwd_full,
                                         hipStream_t st) {
-  int* status = device_status();
-  if (!status) return VSM_ERR_HIP;
   const int Ptot = P + P_src;
-  const int PC = level_lin_chunk<T>(N, Ptot);
-  const size_t lds = ((size_t)N * (N + PC) + (size_t)PC * N + 2 * (size_t)N + 2 * (size_t)LEVEL_NT) * sizeof(T);
-  const int rc =
-      ensure_dyn_lds(reinterpret_cast<const void*>(k_level_radiance_lin_src<T>), lds, "hipFuncSetAttribute(k_level_radiance_lin_src)");
+  level_lin_launch su;
+  const int rc = level_lin_setup<T>(reinterpret_cast<const void*>(k_level_radiance_lin_src<T>),
+                                    "hipFuncSetAttribute(k_level_radiance_lin_src)", N, Ptot, su);
   if (rc) return rc;
   return level_launch<T>(
       ns, nV, row0_h, w_h, (size_t)Ptot * N * S, dwd_full, uwd_full, st,
       [&](int nv, const level_pp& pa, T* df, T* uf) {
-        hipLaunchKernelGGL(k_level_radiance_lin_src<T>, dim3(S), dim3(LEVEL_NT), lds, st, N, ns, S, P, P_top, P_src, PC, nv, pa, A, B,
-                           bstride, dwf, uwf, Ad, ad_pstride, ad, Bd, bd_stride, bd_pstride, cd, asrc, csrc, uwd, dwd, df, uf, status);
+        hipLaunchKernelGGL(k_level_radiance_lin_src<T>, dim3(S), dim3(LEVEL_NT), su.lds, st, N, ns, S, P, P_top, P_src, su.PC, nv, pa,
+                           A, B, bstride, dwf, uwf, Ad, ad_pstride, ad, Bd, bd_stride, bd_pstride, cd, asrc, csrc, uwd, dwd, df, uf,
+                           su.status);
         VSM_LAUNCH_CHECK("k_level_radiance_lin_src");
         return (int)VSM_OK;
       },
       [&](const T* uf, const T* df) { return postprocess_vza_lin<T>(N, ns, S, nV, Ptot, row0_h, w_h, uf, df, uwd, dwd, st); });
 }
 
-// vsm_level_flux_lin_*: the chunks and the LDS layout of vsm_level_radiance_lin_src_*, the same bound
+// vsm_level_flux_lin_*: the chunks and the LDS layout of vsm_level_radiance_lin_src_*
 template <typename T>
 static int level_flux_lin_fused(int N, int ns, int S, int P, int P_top, int P_src, const T* A, const T* B, long long bstride,
                                 const T* dwf, const T* uwf, const T* Ad, long long ad_pstride, const T* ad, const T* Bd,
                                 long long bd_stride, long long bd_pstride, const T* cd, const T* asrc, const T* csrc, int nW, const T* q,
                                 const T* dir_h, T mu0, const T* tau_sum, const T* F0_I, const T* tau_sum_dot, int p_layer, T* out,
                                 hipStream_t st) {
-  int* status = device_status();
-  if (!status) return VSM_ERR_HIP;
-  const int Ptot = P + P_src;
-  const int PC = level_lin_chunk<T>(N, Ptot);
-  const size_t lds = ((size_t)N * (N + PC) + (size_t)PC * N + 2 * (size_t)N + 2 * (size_t)LEVEL_NT) * sizeof(T);
-  const int rc = ensure_dyn_lds(reinterpret_cast<const void*>(k_level_flux_lin<T>), lds, "hipFuncSetAttribute(k_level_flux_lin)");
+  level_lin_launch su;
+  const int rc =
+      level_lin_setup<T>(reinterpret_cast<const void*>(k_level_flux_lin<T>), "hipFuncSetAttribute(k_level_flux_lin)", N, P + P_src, su);
   if (rc) return rc;
   level_flux_lin_args<T> fx = {};
   fx.q = q;
@@ -825,38 +725,9 @@ static int level_flux_lin_fused(int N, int ns, int S, int P, int P_top, int P_sr
   fx.p_layer = tau_sum ? p_layer : 0;
   fx.nW = nW;
   fx.out = out;
-  hipLaunchKernelGGL(k_level_flux_lin<T>, dim3(S), dim3(LEVEL_NT), lds, st, N, ns, S, P, P_top, P_src, PC, A, B, bstride, dwf, uwf, Ad,
-                     ad_pstride, ad, Bd, bd_stride, bd_pstride, cd, asrc, csrc, fx, status);
+  hipLaunchKernelGGL(k_level_flux_lin<T>, dim3(S), dim3(LEVEL_NT), su.lds, st, N, ns, S, P, P_top, P_src, su.PC, A, B, bstride, dwf,
+                     uwf, Ad, ad_pstride, ad, Bd, bd_stride, bd_pstride, cd, asrc, csrc, fx, su.status);
   VSM_LAUNCH_CHECK("k_level_flux_lin");
-  return VSM_OK;
-}
-
-template <typename T>
-static int level_flux_lin_check(int N, int ns, int S, int P, int P_top, int P_src, const T* A, const T* B, long long bstride,
-                                const T* dwf, const T* uwf, const T* Ad, long long ad_pstride, const T* ad, const T* Bd,
-                                long long bd_stride, long long bd_pstride, const T* cd, const T* asrc, const T* csrc, int nW, const T* q,
-                                const T* dir_h, T mu0, const T* tau_sum, const T* F0_I, const T* tau_sum_dot, int p_layer,
-                                const T* out) {
-  VSM_REQUIRE(N > 0 && ns >= 1 && ns <= 4 && N % ns == 0 && S >= 0, "level_flux_lin: bad size (N %d, n_stokes %d, S %d)", N, ns, S);
-  VSM_REQUIRE(N <= LEVEL_FUSED_MAX_N, "level_flux_lin: N = %d > %d, the limit of its kernel", N, LEVEL_FUSED_MAX_N);
-  VSM_REQUIRE(P >= 0 && P_src >= 0 && P + P_src >= 1 && P + P_src <= 64 && P_top >= 0 && P_top <= P,
-              "level_flux_lin: bad slot count (P %d + P_src %d in 1..64, P_top %d in 0..P)", P, P_src, P_top);
-  VSM_REQUIRE(nW >= 1 && nW <= 4, "level_flux_lin: nW = %d outside 1..4", nW);
-  VSM_REQUIRE(bstride == 0 || bstride == (long long)N * N, "level_flux_lin: bot_stride must be 0 or N*N");
-  VSM_REQUIRE(bd_stride == 0 || bd_stride == (long long)N * N, "level_flux_lin: bot_lin_stride must be 0 or N*N");
-  VSM_REQUIRE(!A || P == 0 ||
-                  (bd_pstride >= (bd_stride ? (long long)S * N * N : (long long)N * N) &&
-                   (P_top == 0 || ad_pstride >= (long long)S * N * N)),
-              "level_flux_lin: a per-parameter stride is shorter than one parameter's blocks");
-  VSM_REQUIRE((tau_sum == nullptr) == (F0_I == nullptr), "level_flux_lin: tau_sum and F0_I are both given or both NULL");
-  VSM_REQUIRE(!tau_sum || (dir_h && mu0 > T(0)), "level_flux_lin: the direct term needs dir_h and mu0 > 0");
-  VSM_REQUIRE(p_layer >= 0 && p_layer <= P, "level_flux_lin: p_layer = %d outside 0..P = %d", p_layer, P);
-  VSM_REQUIRE(!tau_sum || p_layer == 0 || tau_sum_dot, "level_flux_lin: the direct term's derivative needs tau_sum_dot");
-  VSM_REQUIRE(S == 0 || (uwf && q && out), "level_flux_lin: null level vector / weight rows / output");
-  VSM_REQUIRE(S == 0 || P == 0 || cd, "level_flux_lin: null bottom source derivative");
-  VSM_REQUIRE(S == 0 || !A || (B && dwf && (P == 0 || Bd)), "level_flux_lin: a top needs the bottom's R-+, its derivative and dw");
-  VSM_REQUIRE(S == 0 || !A || P_top == 0 || (Ad && ad), "level_flux_lin: null top derivative operand");
-  VSM_REQUIRE(S == 0 || P_src == 0 || (csrc && (!A || asrc)), "level_flux_lin: null source operand");
   return VSM_OK;
 }
 
@@ -927,18 +798,18 @@ static int level_ie_check(int N, int ns, int S, int K, const int* shift, int nV,
 }
 
 template <typename T>
-static int level_lin_check(int N, int ns, int S, int P, int P_top, int nV, const int* row0_h, const T* w_h, const T* A, const T* B,
-                           long long bstride, const T* dwf, const T* uwf, const T* Ad, long long ad_pstride, const T* ad,
-                           const T* Bd, long long bd_stride, long long bd_pstride, const T* cd, T* uwd, T* dwd) {
-  const int rc = level_check_common<T>("level_radiance_lin", N, LEVEL_FUSED_MAX_N, ns, S, nV, row0_h, w_h, bstride, uwd, dwd);
+static int level_lin_check(const char* who, int N, int ns, int S, int P, int P_top, int nV, const int* row0_h, const T* w_h,
+                           const T* A, const T* B, long long bstride, const T* dwf, const T* uwf, const T* Ad, long long ad_pstride,
+                           const T* ad, const T* Bd, long long bd_stride, long long bd_pstride, const T* cd, const T* uwd,
+                           const T* dwd) {
+  const int rc = level_check_common<T>(who, N, LEVEL_FUSED_MAX_N, ns, S, nV, row0_h, w_h, bstride, uwd, dwd);
   if (rc) return rc;
-  VSM_REQUIRE(P >= 1 && P <= 64 && P_top >= 0 && P_top <= P, "level_radiance_lin: bad parameter count (P %d in 1..64, P_top %d in 0..P)",
-              P, P_top);
-  VSM_REQUIRE(bd_stride == 0 || bd_stride == (long long)N * N, "level_radiance_lin: bot_lin_stride must be 0 or N*N");
+  VSM_REQUIRE(P >= 1 && P <= 64 && P_top >= 0 && P_top <= P, "%s: bad parameter count (P %d in 1..64, P_top %d in 0..P)", who, P, P_top);
+  VSM_REQUIRE(bd_stride == 0 || bd_stride == (long long)N * N, "%s: bot_lin_stride must be 0 or N*N", who);
   VSM_REQUIRE(bd_pstride >= (bd_stride ? (long long)S * N * N : (long long)N * N) && (P_top == 0 || ad_pstride >= (long long)S * N * N),
-              "level_radiance_lin: a per-parameter stride is shorter than one parameter's blocks");
-  VSM_REQUIRE(S == 0 || (A && B && dwf && uwf && Bd && cd), "level_radiance_lin: null operand");
-  VSM_REQUIRE(S == 0 || P_top == 0 || (Ad && ad), "level_radiance_lin: null top derivative operand");
+              "%s: a per-parameter stride is shorter than one parameter's blocks", who);
+  VSM_REQUIRE(S == 0 || (A && B && dwf && uwf && Bd && cd), "%s: null operand", who);
+  VSM_REQUIRE(S == 0 || P_top == 0 || (Ad && ad), "%s: null top derivative operand", who);
   return VSM_OK;
 }
 
@@ -950,12 +821,60 @@ static int level_lin_src_check(int P, int P_src, int S, const T* asrc, const T* 
   return VSM_OK;
 }
 
+// vsm_level_flux_*: level_check_common without a viewing-angle table, the source lists of level_src_check (a top is optional)
+template <typename T>
+static int level_flux_check(int N, int ns, int S, const T* A, int K, const T* const* a, const T* B, long long bstride,
+                            const T* const* c, int nW, const T* q, const T* dir_h, T mu0, const T* tau_sum, const T* F0_I,
+                            const T* out) {
+  VSM_REQUIRE(K >= 1 && K <= VSM_LEVEL_MAX_SRC, "level_flux: n_src = %d outside 1..%d", K, (int)VSM_LEVEL_MAX_SRC);
+  VSM_REQUIRE(nW >= 1 && nW <= 4, "level_flux: nW = %d outside 1..4", nW);
+  const int rc = level_check_common<T>("level_flux", N, LEVEL_FUSED_MAX_N, ns, S, 0, nullptr, nullptr, bstride, nullptr, nullptr);
+  if (rc) return rc;
+  VSM_REQUIRE((tau_sum == nullptr) == (F0_I == nullptr), "level_flux: tau_sum and F0_I are both given or both NULL");
+  VSM_REQUIRE(!tau_sum || (dir_h && mu0 > T(0)), "level_flux: the direct term needs dir_h and mu0 > 0");
+  VSM_REQUIRE(S == 0 || (c && q && out), "level_flux: null bottom source list / weight rows / output");
+  VSM_REQUIRE(S == 0 || !A || (a && B), "level_flux: a top needs its sources and the bottom's R-+");
+  for (int k = 0; k < K && S > 0; ++k) VSM_REQUIRE(c[k] && (!A || a[k]), "level_flux: null source %d", k);
+  return VSM_OK;
+}
+
+// vsm_level_flux_lin_*: with a top and parameter slots, level_lin_check without a viewing-angle table; the TOA and a call with
+// source-only slots alone read no operator derivative and leave those operands out
+template <typename T>
+static int level_flux_lin_check(int N, int ns, int S, int P, int P_top, int P_src, const T* A, const T* B, long long bstride,
+                                const T* dwf, const T* uwf, const T* Ad, long long ad_pstride, const T* ad, const T* Bd,
+                                long long bd_stride, long long bd_pstride, const T* cd, const T* asrc, const T* csrc, int nW, const T* q,
+                                const T* dir_h, T mu0, const T* tau_sum, const T* F0_I, const T* tau_sum_dot, int p_layer,
+                                const T* out) {
+  const char* who = "level_flux_lin";
+  VSM_REQUIRE(P >= 0 && P_src >= 0 && P + P_src >= 1 && P + P_src <= 64 && P_top >= 0 && P_top <= P,
+              "level_flux_lin: bad slot count (P %d + P_src %d in 1..64, P_top %d in 0..P)", P, P_src, P_top);
+  VSM_REQUIRE(nW >= 1 && nW <= 4, "level_flux_lin: nW = %d outside 1..4", nW);
+  if (A && P > 0) {
+    const int rc = level_lin_check<T>(who, N, ns, S, P, P_top, 0, nullptr, nullptr, A, B, bstride, dwf, uwf, Ad, ad_pstride, ad, Bd,
+                                      bd_stride, bd_pstride, cd, nullptr, nullptr);
+    if (rc) return rc;
+  } else {
+    const int rc = level_check_common<T>(who, N, LEVEL_FUSED_MAX_N, ns, S, 0, nullptr, nullptr, bstride, nullptr, nullptr);
+    if (rc) return rc;
+    VSM_REQUIRE(bd_stride == 0 || bd_stride == (long long)N * N, "level_flux_lin: bot_lin_stride must be 0 or N*N");
+    VSM_REQUIRE(S == 0 || (uwf && (P == 0 || cd) && (!A || (B && dwf))), "level_flux_lin: null operand");
+  }
+  VSM_REQUIRE((tau_sum == nullptr) == (F0_I == nullptr), "level_flux_lin: tau_sum and F0_I are both given or both NULL");
+  VSM_REQUIRE(!tau_sum || (dir_h && mu0 > T(0)), "level_flux_lin: the direct term needs dir_h and mu0 > 0");
+  VSM_REQUIRE(p_layer >= 0 && p_layer <= P, "level_flux_lin: p_layer = %d outside 0..P = %d", p_layer, P);
+  VSM_REQUIRE(!tau_sum || p_layer == 0 || tau_sum_dot, "level_flux_lin: the direct term's derivative needs tau_sum_dot");
+  VSM_REQUIRE(S == 0 || (q && out), "level_flux_lin: null weight rows / output");
+  VSM_REQUIRE(S == 0 || P_src == 0 || (csrc && (!A || asrc)), "level_flux_lin: null source operand");
+  return VSM_OK;
+}
+
 // The response of the column to a unit hemispheric emission at the lower boundary (vsm_surface_emission_response_*: the SIF
 // Jacobian slots of the linearized run).  SurfaceSIF adds the SAME value to j0- of the surface layer at every stream, so the
 // radiance is sum_c 2 SIF0[c, s] G_c(s) with G_c the response to the unit pattern e_c (1 on the rows of Stokes component c, 0
 // elsewhere): the level equation at the boundary between the atmosphere (A = its R+-, a = 0) and the surface (B = its r-+,
 // c_k = e_comp[k]), k_level_radiance_src's system with K <= 4 right-hand sides and no top source, point s = blockIdx.x:
-//   [M | d_1 .. d_K] = [I - A B | A c_k],  ONE Gauss-Jordan elimination,  dw_k = column / m_ii,  y_k = c_k + B dw_k,
+//   level_solve_columns on [M | d_1 .. d_K] = [I - A B | A c_k]:  dw_k,  y_k = c_k + B dw_k  (kept apart, not summed),
 //   up_k[v, c, s] = w[v, c] sum_j T--[row0[v] + c, j] y_k[j]   (the TOA leg: interaction!'s J0- = .. + T-- (I - r-+ R+-)^-1 (j0- + r-+ J0+))
 //   dn_k[v, c, s] = w[v, c] dw_k[row0[v] + c]                  (the BOA leg: J0+ = t++ (I - R+- r-+)^-1 R+- j0-, t++ = I at m = 0)
 // written (not accumulated) per component into up / dn [K][S][n_stokes][nVtot].  y_full / dw_full [K][S][N] (nullable): the
@@ -986,23 +905,15 @@ __global__ void __launch_bounds__(LEVEL_NT) k_emission_response(int N, int ns, i
     Q[k * N + i] = (i % ns == comps.c[k]) ? T(1) : T(0);
   }
   __syncthreads();
-  level_form_system<T>(N, N + K, LD, A + s * NN, Bs, Q, L, sh, status);
-  level_eliminate<T>(N, N + K, LD, L, sh, status);
-  for (int e = tid; e < N * K; e += LEVEL_NT) {
-    const int i = e % N, k = e / N;
-    L[i * LD + N + k] = L[i * LD + N + k] / L[i * LD + i];
+  level_solve_columns<T>(N, K, LD, A + s * NN, Bs, L, Q, sh, status);
+  if (y_full) {   // (both or neither: the launch above 64 viewing angles)
+    for (int e = tid; e < N * K; e += LEVEL_NT) {
+      const int i = e % N, k = e / N;
+      const long long o = ((long long)k * S + s) * N + i;
+      y_full[o] = Q[k * N + i];
+      dw_full[o] = L[i * LD + N + k];
+    }
   }
-  __syncthreads();
-  for (int e = tid; e < N * K; e += LEVEL_NT) {
-    const int i = e % N, k = e / N;
-    T y = Q[k * N + i];
-    for (int j = 0; j < N; ++j) y += Bs[(long long)j * N + i] * L[j * LD + N + k];
-    Q[k * N + i] = y;   // (row i of Q[k] is read by this thread alone until the barrier)
-    const long long o = ((long long)k * S + s) * N + i;
-    if (y_full) y_full[o] = y;
-    if (dw_full) dw_full[o] = L[i * LD + N + k];
-  }
-  __syncthreads();
   for (int e = tid; e < nV * ns * K; e += LEVEL_NT) {
     const int v = e % nV, c = (e / nV) % ns, k = e / (nV * ns), row = pa.row0[v] + c;
     const T w = (T)pa.w[v + nV * c];
@@ -1175,14 +1086,14 @@ VSM_LEVEL_IE_API(float, f32)
                                    const T* bot_R_mp_lin, long long bot_lin_stride, long long bot_lin_pstride,               \
                                    const T* bot_J0_m_lin, T* uw_lin, T* dw_lin, T* dw_lin_full, T* uw_lin_full,               \
                                    void* stream) {                                                                            \
-    int rc = level_lin_check<T>(N, n_stokes, S, P, P_top, nV, row0_h, w_h, top_R_pm, bot_R_mp, bot_stride, dw_full, uw_full,  \
-                                top_R_pm_lin, top_lin_pstride, top_J0_p_lin, bot_R_mp_lin, bot_lin_stride, bot_lin_pstride,   \
-                                bot_J0_m_lin, uw_lin, dw_lin);                                                                \
+    int rc = level_lin_check<T>("level_radiance_lin", N, n_stokes, S, P, P_top, nV, row0_h, w_h, top_R_pm, bot_R_mp, bot_stride, \
+                                dw_full, uw_full, top_R_pm_lin, top_lin_pstride, top_J0_p_lin, bot_R_mp_lin, bot_lin_stride,  \
+                                bot_lin_pstride, bot_J0_m_lin, uw_lin, dw_lin);                                               \
     if (rc || S == 0) return rc;                                                                                              \
-    return level_radiance_lin_fused<T>(N, n_stokes, S, P, P_top, nV, row0_h, w_h, top_R_pm, bot_R_mp, bot_stride, dw_full,    \
-                                       uw_full, top_R_pm_lin, top_lin_pstride, top_J0_p_lin, bot_R_mp_lin, bot_lin_stride,    \
-                                       bot_lin_pstride, bot_J0_m_lin, uw_lin, dw_lin, dw_lin_full, uw_lin_full,               \
-                                       as_stream(stream));                                                                    \
+    return level_radiance_lin_src_fused<T>(N, n_stokes, S, P, P_top, 0, nV, row0_h, w_h, top_R_pm, bot_R_mp, bot_stride,      \
+                                           dw_full, uw_full, top_R_pm_lin, top_lin_pstride, top_J0_p_lin, bot_R_mp_lin,       \
+                                           bot_lin_stride, bot_lin_pstride, bot_J0_m_lin, (const T*)nullptr,                  \
+                                           (const T*)nullptr, uw_lin, dw_lin, dw_lin_full, uw_lin_full, as_stream(stream));   \
   }
 VSM_LEVEL_LIN_API(double, f64)
 VSM_LEVEL_LIN_API(float, f32)
@@ -1195,9 +1106,9 @@ VSM_LEVEL_LIN_API(float, f32)
                                        long long bot_lin_pstride, const T* bot_J0_m_lin, const T* src_top_J0_p,               \
                                        const T* src_bot_J0_m, T* uw_lin, T* dw_lin, T* dw_lin_full, T* uw_lin_full,           \
                                        void* stream) {                                                                        \
-    int rc = level_lin_check<T>(N, n_stokes, S, P, P_top, nV, row0_h, w_h, top_R_pm, bot_R_mp, bot_stride, dw_full, uw_full,  \
-                                top_R_pm_lin, top_lin_pstride, top_J0_p_lin, bot_R_mp_lin, bot_lin_stride, bot_lin_pstride,   \
-                                bot_J0_m_lin, uw_lin, dw_lin);                                                                \
+    int rc = level_lin_check<T>("level_radiance_lin", N, n_stokes, S, P, P_top, nV, row0_h, w_h, top_R_pm, bot_R_mp, bot_stride, \
+                                dw_full, uw_full, top_R_pm_lin, top_lin_pstride, top_J0_p_lin, bot_R_mp_lin, bot_lin_stride,  \
+                                bot_lin_pstride, bot_J0_m_lin, uw_lin, dw_lin);                                               \
     if (!rc) rc = level_lin_src_check<T>(P, P_src, S, src_top_J0_p, src_bot_J0_m);                                            \
     if (rc || S == 0) return rc;                                                                                              \
     return level_radiance_lin_src_fused<T>(N, n_stokes, S, P, P_top, P_src, nV, row0_h, w_h, top_R_pm, bot_R_mp, bot_stride,  \
