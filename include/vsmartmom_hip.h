@@ -1012,6 +1012,31 @@ int vsm_level_radiance_ie_f32(int N, int n_stokes, int S, int K, const int* shif
                               const float* uw_full, const float* top_ieR_pm, const float* top_ieJ0_p, const float* bot_ieR_mp,
                               const float* bot_ieJ0_m, float* uwie, float* dwie, float* dwie_full, float* uwie_full, void* stream);
 
+/* Hemispheric quadratures of the elastic AND the inelastic level vectors at ONE boundary: the fluxes of
+ * CoreRTRaman.rt_run_fluxes (vsmartmom.jl_amd/core_rt_flux_raman.py).  The system of vsm_level_radiance_ie_* per recipient point
+ * n1, operands, layouts, in-band rule, elimination and pivots as there (the two return the same dw_ie / uw_ie bits), but the
+ * vectors never leave the chip and no [N,1,S] inelastic vector exists anywhere: with the nW weight rows q [nW][N / n_stokes]
+ * (a DEVICE array, one weight per stream, applied to the rows of Stokes I) as in vsm_level_flux_*,
+ *   out[0][r][n1] = sum_i q[r][i] uw[i n_stokes, n1]          out[1][r][n1] = sum_i q[r][i] dw[i n_stokes, n1]
+ *   out[3][r][n1] = sum_i q[r][i] uw_ie[i n_stokes]           out[4][r][n1] = sum_i q[r][i] dw_ie[i n_stokes]
+ *   out[2][r][n1] = dir_h[r] F0_I[n1] exp(-tau_sum[n1] / mu0)   (tau_sum, F0_I: [S], given together or both NULL: then 0)
+ * uw / dw = uw_full / dw_full [N,1,S] of the ELASTIC level call at the same level, read at the donors for the solve and at n1
+ * itself for rows 0 and 1.  out [5][nW][S] is WRITTEN, not accumulated; dir_h is a HOST array of nW factors (read only with
+ * tau_sum / F0_I).  The additions of a quadrature have the fixed order of vsm_level_flux_*.  top_R_pm == NULL: no layer lies
+ * above the boundary (the TOA): no system is formed, dw = dw_ie = 0, uw = uw_full (J0- of the whole column) and uw_ie = the sum
+ * of bot_ieJ0_m over the in-band lines, in the order of k; dw_full, bot_R_mp, top_ieR_pm, top_ieJ0_p and bot_ieR_mp are not read.
+ * bot_ieR_mp = bot_ieJ0_m = NULL, both or neither, at the TOA too: a bottom without an inelastic part.  K = 0 is legal: rows 3 and 4 are 0.  1 <= nW <= 4,
+ * 1 <= N <= 128, n_stokes divides N, S >= 0, the required pointers non-NULL; anything else is VSM_ERR_INVALID_ARG before any
+ * launch.  S = 0 launches nothing.  Status words and pivot rule as in vsm_level_radiance_*.  No work buffer. */
+int vsm_level_flux_ie_f64(int N, int n_stokes, int S, int K, const int* shift, const double* top_R_pm, const double* bot_R_mp,
+                          long long bot_stride, const double* dw_full, const double* uw_full, const double* top_ieR_pm,
+                          const double* top_ieJ0_p, const double* bot_ieR_mp, const double* bot_ieJ0_m, int nW, const double* q,
+                          const double* dir_h, double mu0, const double* tau_sum, const double* F0_I, double* out, void* stream);
+int vsm_level_flux_ie_f32(int N, int n_stokes, int S, int K, const int* shift, const float* top_R_pm, const float* bot_R_mp,
+                          long long bot_stride, const float* dw_full, const float* uw_full, const float* top_ieR_pm,
+                          const float* top_ieJ0_p, const float* bot_ieR_mp, const float* bot_ieJ0_m, int nW, const float* q,
+                          const float* dir_h, float mu0, const float* tau_sum, const float* F0_I, float* out, void* stream);
+
 /* The derivative of the level equation (vsm_level_radiance_*) with respect to the Jacobian parameters of a linearized multi-sensor
  * run (vsmartmom.jl_amd/core_rt_ms_lin.py) at ONE boundary: for every parameter p, with dw / uw = dw_full / uw_full [N,1,S] of the
  * elastic level call at the same level and M = I - A B,

@@ -18,6 +18,7 @@ Sub-modules
                     rt_run_fluxes(model, lin_model, ...) (core_rt_flux_lin: flux and heating Jacobians at the layer boundaries)
     CoreRTRaman     rotational-Raman pass: rt_run(RS_type::RRS, model, iBand),
                     rt_run_multisensor(RS_type, model, sensor_levels) (core_rt_ms_raman),
+                    rt_run_fluxes(RS_type, model, levels) (core_rt_flux_raman: elastic and inelastic fluxes at the boundaries),
                     rt_run_ss(RS_type, model, iBand) (core_rt_ss: the single-scatter inelastic correction)
     StandaloneSS    exact single scattering at the true scattering angle (standalone_ss: run_exact_ss, the four paths,
                     apply_back_correction = exact - truncated first-order field, Jacobians of paths 1 and 2)
@@ -35,6 +36,7 @@ from . import core_rt_ms_lin  # noqa: F401
 from . import core_rt_ss  # noqa: F401
 from . import core_rt_flux  # noqa: F401
 from . import core_rt_flux_lin  # noqa: F401
+from . import core_rt_flux_raman  # noqa: F401
 from . import standalone_ss as StandaloneSS  # noqa: F401
 from . import raman_inputs  # noqa: F401
 from . import io_yaml  # noqa: F401
@@ -53,5 +55,7 @@ CoreRT.rt_run_fluxes = core_rt_flux.rt_run_fluxes
 CoreRT.FluxResult = core_rt_flux.FluxResult
 CoreRTLin.rt_run_fluxes = core_rt_flux_lin.rt_run_fluxes
 CoreRTLin.FluxLinResult = core_rt_flux_lin.FluxLinResult
+CoreRTRaman.rt_run_fluxes = core_rt_flux_raman.rt_run_fluxes
+CoreRTRaman.RamanFluxResult = core_rt_flux_raman.RamanFluxResult
 
 __version__ = "0.1.0"

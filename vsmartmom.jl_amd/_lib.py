@@ -178,6 +178,7 @@ _SIGS = {
     "vsm_level_flux_{T}": (_I, [_I, _I, _I, _P, _I, _P, _P, _LL, _P, _I, _P, _P, "{R}", _P, _P, _P, _P]),
     "vsm_surface_emission_response_{T}": (_I, [_I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _LL, _P, _P, _P]),
     "vsm_level_radiance_ie_{T}": (_I, [_I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _LL, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "vsm_level_flux_ie_{T}": (_I, [_I, _I, _I, _I, _P, _P, _P, _LL, _P, _P, _P, _P, _P, _P, _I, _P, _P, "{R}", _P, _P, _P, _P]),
     "vsm_level_radiance_lin_{T}": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _LL, _P, _P, _P, _LL, _P, _P, _LL, _LL, _P, _P, _P, _P, _P,
                                         _P]),
     "vsm_level_radiance_lin_src_{T}": (_I, [_I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _LL, _P, _P, _P, _LL, _P, _P, _LL, _LL, _P, _P, _P,

@@ -21,6 +21,10 @@ per-sensor walk up to rounding.  Per moment: Nz + (Nz - l_1) RRS layer steps, L 
 most 2 (L + 1) level calls.  rt_run(RRS)'s statements for the _00 / _01 / _10 tags (non-scattering layers) drop inelastic terms
 and do not associate: a bottom whose lower part holds such a tag is walked layer by layer to the surface instead, like the
 prototype's interaction_bot! (Nz - l_k more layer steps for that level).
+
+_run_scene is the one Raman walk.  A run that wants something else than radiances at each level hands it a LevelSink, which
+takes the place of the level calls: CoreRTRaman.rt_run_fluxes (core_rt_flux_raman.py) walks m = 0 alone and reduces the elastic
+and the inelastic level vectors to fluxes on the device.
 """
 from __future__ import annotations
 
@@ -98,23 +102,44 @@ def _layer(sc: RR.SceneRRS, mom, iz: int, comp, comp_rs, iz_local: int):
                       iface=ly["iface"])
 
 
-def _run_scene(sc: RR.SceneRRS, plan: MS.LevelPlan, streams: bool):
+class LevelSink:
+    """What a run other than the multi-sensor one does at each level of the walk of _run_scene, in place of its level calls
+    (core_rt_flux_raman.py: the fluxes), as core_rt_ms.LevelSink does for the elastic walk.  With a sink no VZA output is
+    allocated or zeroed, no level call and no post-processing is issued here and no level vector is collected; the walk itself --
+    tops, segments, bottoms -- is the same, and level 0 is walked only if the plan asks for it.  The scene handed over is the one
+    that walks the moment: there is no Stokes_IQ detour here (the caller passes SceneRRS.sub0 itself where it wants that)."""
+
+    def level(self, mom, l, top, bot):
+        """Level l > 0: top = (R+-, J0+, ieR+-, ieJ0+) of the composite above it, bot = (R-+, J0-, ieR-+, ieJ0-) of the one below
+        (the last two None: the surface layer alone)."""
+        raise NotImplementedError
+
+    def level0(self, mom, comp, comp_rs):
+        """Level 0, the TOA: the composite of the whole column after the surface interaction."""
+        raise NotImplementedError
+
+
+def _run_scene(sc: RR.SceneRRS, plan: MS.LevelPlan, streams: bool, sink: Optional[LevelSink] = None):
     """The multi-sensor algorithm on one SceneRRS (its whole extended spectral axis).  Returns ({level: [uw, dw, uwie, dwie]} of
-    (S, nStokes, nVZA) device tensors, {m: {level: (uw, dw, uwie, dwie) (S, N)}} or None, the Fourier weights)."""
+    (S, nStokes, nVZA) device tensors, {m: {level: (uw, dw, uwie, dwie) (S, N)}} or None, the Fourier weights); with a sink (see
+    LevelSink) the first is empty and streams is not taken."""
     model, fwd, FT, dt = sc.model, sc.fwd, sc.FT, sc.dt
     pol, qp, drs = fwd.pol, fwd.qp, sc.drs
     Nz, N, S = fwd.Nz, sc.N, sc.S
     dev = sc.out[0].device
     nV = len(model.vza)
-    for t in sc.out:
-        t.zero_()
-    out = {l: [torch.zeros((S, pol.n, nV), dtype=dt, device=dev) for _ in range(4)] for l in plan.distinct if l != 0}
-    out[0] = list(sc.out)
-    full = {} if streams else None
+    if sink is None:
+        for t in sc.out:
+            t.zero_()
+        out = {l: [torch.zeros((S, pol.n, nV), dtype=dt, device=dev) for _ in range(4)] for l in plan.distinct if l != 0}
+        out[0] = list(sc.out)
+    else:
+        out = {}
+    full = {} if streams and sink is None else None
     weights = [float(MS.fourier_weight(FT, m)) for m in range(model.m_max + 1)]
     if S == 0:
         return out, full, weights
-    reduced = sc.sub0 is not None
+    reduced = sc.sub0 is not None and sink is None
     if reduced:      # m = 0 first, like SceneRRS.run
         MS.merge_sub0(_run_scene(sc.sub0, plan, streams), pol.n, out, full)
     comp, comp_rs = fwd.composite, sc.comp_rs
@@ -157,6 +182,9 @@ def _run_scene(sc: RR.SceneRRS, plan: MS.LevelPlan, streams: bool):
         def level(l, seg):      # (the surface layer alone has no inelastic part)
             top = tops.pop(l)
             bot = (asurf.r_mp, asurf.j0_m, None, None) if seg is None else (seg[0].R_mp, seg[0].J0_m, seg[1].ieR_mp, seg[1].ieJ0_m)
+            if sink is not None:
+                sink.level(mom, l, top, bot)
+                return
             vs = MS.level_pair_(pol, qp, model.vza, model.vaz, m, weight, top, bot[0], bot[1], out[l],
                                 lambda dwf, uwf, dwief, uwief: level_radiance_ie_(
                                     pol, qp, model.vza, model.vaz, m, weight, drs.shift, top[0], bot[0], dwf, uwf, top[2], top[3],
@@ -165,6 +193,11 @@ def _run_scene(sc: RR.SceneRRS, plan: MS.LevelPlan, streams: bool):
                 fv[l] = vs
         # 2.-4. RS segments and bottoms from the surface up, the level calls of each level
         MS.walk_levels(plan, segs, lambda seg, first, end: layers(seg, first, first, end), join_surface, join_bottom, level)
+        if sink is not None:      # level 0, the TOA itself: the whole column with the surface
+            if 0 in plan.distinct:
+                RR.interaction_inelastic_(drs, mom["iface_surface"], comp, comp_rs, asurf, sc.surf_rs)
+                sink.level0(mom, comp, comp_rs)
+            continue
         # level 0: SceneRRS.run's surface interaction and post-processing
         RR.interaction_inelastic_(drs, mom["iface_surface"], comp, comp_rs, asurf, sc.surf_rs)
         RR.postprocessing_vza_rs_(pol, comp, comp_rs, model.vza, model.vaz, qp, m, weight, *sc.out)

@@ -11,7 +11,7 @@
 //   2. Gauss-Jordan on [M | d_k] in LDS, the pivot rule of vsm_inverse.h (largest |m_ik|, first occurrence) -- no inverse;
 //   3. dw_k = d_k / m_ii,  uw_k = c_k + B dw_k (mat-vec);
 // what differs is where the right-hand sides come from and what is done with the vectors.  One spectral point per 256-thread
-// workgroup, N <= 128 (FP64 [M | d]: 129 KiB of LDS at N = 128).  Six fused kernels:
+// workgroup, N <= 128 (FP64 [M | d]: 129 KiB of LDS at N = 128).  Seven fused kernels:
 //   k_level_radiance_src   vsm_level_radiance_* (K = 1) and vsm_level_radiance_src_* (up to VSM_LEVEL_MAX_SRC source pairs (a_k,
 //                          c_k) on the same A, B: the solar and the thermal slot): the level vectors summed over the sources,
 //                          their VZA rows added into the caller's [nV, n_stokes, S] outputs;
@@ -19,6 +19,8 @@
 //                          fluxes of rt_run_fluxes), and the TOA itself, which has no system;
 //   k_level_radiance_ie    vsm_level_radiance_ie_*: the first-order (Raman) part of the same equation, interlayer_flux_helper!(::RRS)
 //                          (interlayer_flux.jl:21-77), per recipient point with the lines summed before ONE solve of [I - A B | r];
+//   k_level_flux_ie        vsm_level_flux_ie_*: the same solve (level_ie_solve), its vectors and the point's own elastic ones
+//                          reduced to the hemispheric quadratures (the fluxes of CoreRTRaman.rt_run_fluxes), and the TOA;
 //   k_level_radiance_lin_src   vsm_level_radiance_lin_* (P_src = 0) and vsm_level_radiance_lin_src_*: the derivative with respect
 //                          to the Jacobian parameters, the parameters as right-hand sides of ONE solve per chunk, and P_src
 //                          further SOURCE-ONLY slots (the Planck slots of a linearized run with thermal emission); level_lin_body;
@@ -351,27 +353,19 @@ __device__ __forceinline__ void level_stream_reduce(int N, int G, int g, int i, 
   __syncthreads();
 }
 
-// The inelastic level equation (vsm_level_radiance_ie_*) of recipient point n1 = blockIdx.x, lines summed before the solve:
+// The solve of the two inelastic kernels for recipient point n1, lines summed before it:
 //   q = sum_k [c_ie,k + B_ie,k dw(n0)],  r = sum_k [a_ie,k + A_ie,k uw(n0)] + A q,  dw_ie = (I - A B)^-1 r,  uw_ie = q + B dw_ie
 // over the in-band lines k (n0 = n1 + shift[k] in 0..S-1); dw / uw are the ELASTIC level vectors of the donors.
 // Phase 1 streams the 2K ie blocks of the point by column groups; phase 2 is level_solve_columns with ONE right-hand side,
-// (s, q) = (r - A q, q), and level_radiance_out.  LDS: L [N][N + 1], q [N], partial sums [2][G][N].
+// (s, q) = (r - A q, q).  After it, behind a barrier: dw_ie in column N of L [N][N + 1], uw_ie in qs [N].  part: [2][G][N].
 template <typename T>
-__global__ void __launch_bounds__(LEVEL_NT) k_level_radiance_ie(int N, int ns, int S, int K, const int* __restrict__ shift, int nV,
-                                                                level_pp pa, const T* __restrict__ A,
-                                                                const T* __restrict__ B, long long bstride,
-                                                                const T* __restrict__ dwf, const T* __restrict__ uwf,
-                                                                const T* __restrict__ Aie, const T* __restrict__ aie,
-                                                                const T* __restrict__ Bie, const T* __restrict__ cie, T* uwie,
-                                                                T* dwie, T* dwie_full, T* uwie_full, int* status) {
-  extern __shared__ __align__(16) unsigned char lds_raw[];
+__device__ __forceinline__ void level_ie_solve(int N, int S, int K, const int* __restrict__ shift, int n1, const T* __restrict__ A,
+                                               const T* __restrict__ B, long long bstride, const T* __restrict__ dwf,
+                                               const T* __restrict__ uwf, const T* __restrict__ Aie, const T* __restrict__ aie,
+                                               const T* __restrict__ Bie, const T* __restrict__ cie, T* L, T* qs, T* part, int* sh,
+                                               int* status) {
   const int LD = N + 1;
-  T* L = reinterpret_cast<T*>(lds_raw);          // [M | r], row-major, leading dimension N + 1; column N: then dw_ie
-  T* qs = L + (size_t)N * LD;                    // q, then uw_ie
-  T* part = qs + N;                              // [2][G][N] partial sums
-  __shared__ int sh[2];
   const int tid = threadIdx.x;
-  const int n1 = blockIdx.x;
   const long long NN = (long long)N * N;
   const int G = LEVEL_NT / N, g = tid / N, i = tid - g * N;
   level_sums<T> acc = {T(0), T(0)};
@@ -387,7 +381,76 @@ __global__ void __launch_bounds__(LEVEL_NT) k_level_radiance_ie(int N, int ns, i
   }
   level_stream_reduce<T>(N, G, g, i, acc, part, L + N, LD, qs, 1);
   level_solve_columns<T>(N, 1, LD, A + n1 * NN, B + n1 * bstride, L, qs, sh, status);
+}
+
+// The inelastic level equation (vsm_level_radiance_ie_*) of recipient point n1 = blockIdx.x: level_ie_solve, then
+// level_radiance_out of its vector pair.  LDS: L [N][N + 1], q [N], partial sums [2][G][N].
+template <typename T>
+__global__ void __launch_bounds__(LEVEL_NT) k_level_radiance_ie(int N, int ns, int S, int K, const int* __restrict__ shift, int nV,
+                                                                level_pp pa, const T* __restrict__ A,
+                                                                const T* __restrict__ B, long long bstride,
+                                                                const T* __restrict__ dwf, const T* __restrict__ uwf,
+                                                                const T* __restrict__ Aie, const T* __restrict__ aie,
+                                                                const T* __restrict__ Bie, const T* __restrict__ cie, T* uwie,
+                                                                T* dwie, T* dwie_full, T* uwie_full, int* status) {
+  extern __shared__ __align__(16) unsigned char lds_raw[];
+  const int LD = N + 1;
+  T* L = reinterpret_cast<T*>(lds_raw);          // [M | r], row-major, leading dimension N + 1; column N: then dw_ie
+  T* qs = L + (size_t)N * LD;                    // q, then uw_ie
+  T* part = qs + N;                              // [2][G][N] partial sums
+  __shared__ int sh[2];
+  const int n1 = blockIdx.x;
+  level_ie_solve<T>(N, S, K, shift, n1, A, B, bstride, dwf, uwf, Aie, aie, Bie, cie, L, qs, part, sh, status);
   level_radiance_out<T>(N, ns, LD, nV, pa, n1, L, qs, uwie, dwie, dwie_full, uwie_full);
+}
+
+// Hemispheric quadratures of the elastic AND the inelastic level vectors (vsm_level_flux_ie_*: the fluxes of
+// CoreRTRaman.rt_run_fluxes) of recipient point n1 = blockIdx.x.  level_ie_solve leaves dw_ie / uw_ie in LDS; the point's own
+// elastic vectors dwf[n1] / uwf[n1] are read from global memory; level_flux_reduce (one vector pair each) writes
+//   out[0][r][n1] = sum_i q[r][i] uw[i ns]   out[1] likewise of dw   out[3] of uw_ie   out[4] of dw_ie   (the rows of Stokes I)
+//   out[2][r][n1] = dir[r] F0_I[n1] exp(-tau_sum[n1] / mu0) with both arrays given, else 0.
+// A == nullptr (the same for the whole grid): no layer above the level (the TOA), no system: dw = dw_ie = 0, uw = uwf[n1],
+// uw_ie = sum over the in-band k of c_ie,k, added in the order of k (cie == nullptr: 0); dwf, B, Aie, aie, Bie are not read.
+// Every element of out [5][nW][S] is WRITTEN.  LDS: that of k_level_radiance_ie.
+template <typename T>
+__global__ void __launch_bounds__(LEVEL_NT) k_level_flux_ie(int N, int ns, int S, int K, const int* __restrict__ shift, int nW,
+                                                            const T* __restrict__ A, const T* __restrict__ B, long long bstride,
+                                                            const T* __restrict__ dwf, const T* __restrict__ uwf,
+                                                            const T* __restrict__ Aie, const T* __restrict__ aie,
+                                                            const T* __restrict__ Bie, const T* __restrict__ cie,
+                                                            const T* __restrict__ q, level_flux_dir<T> dir,
+                                                            const T* __restrict__ tau_sum, const T* __restrict__ F0_I, T* out,
+                                                            int* status) {
+  extern __shared__ __align__(16) unsigned char lds_raw[];
+  const int LD = N + 1;
+  T* L = reinterpret_cast<T*>(lds_raw);          // [M | r], row-major, leading dimension N + 1; column N: then dw_ie
+  T* qs = L + (size_t)N * LD;                    // q, then uw_ie
+  T* part = qs + N;                              // [2][G][N] partial sums
+  __shared__ int sh[2];
+  const int tid = threadIdx.x;
+  const int n1 = blockIdx.x;
+  if (A) {
+    level_ie_solve<T>(N, S, K, shift, n1, A, B, bstride, dwf, uwf, Aie, aie, Bie, cie, L, qs, part, sh, status);
+  } else {
+    if (tid < N) {
+      T y = T(0);
+      if (cie) {
+        for (int k = 0; k < K; ++k) {
+          const int n0 = n1 + shift[k];
+          if (n0 >= 0 && n0 < S) y += cie[((long long)k * S + n1) * N + tid];
+        }
+      }
+      qs[tid] = y;
+    }
+    __syncthreads();
+  }
+  const int Nq = N / ns;
+  const T* own = uwf + (long long)n1 * N;
+  level_flux_reduce<T>(Nq, ns, nW, 1, q, own, 0, 1, A ? dwf + (long long)n1 * N : own, 0, 1, A != nullptr, out, 0, 1, (long long)S,
+                       (long long)n1);
+  level_flux_reduce<T>(Nq, ns, nW, 1, q, qs, 0, 1, L + N, 0, LD, A != nullptr, out + 3 * (long long)nW * S, 0, 1, (long long)S,
+                       (long long)n1);
+  if (tid < nW) out[((long long)2 * nW + tid) * S + n1] = tau_sum ? dir.h[tid] * F0_I[n1] * exp(-tau_sum[n1] / dir.mu0) : T(0);
 }
 
 // The VZA table of one launch and what to do above the 64 viewing angles it carries: the level vectors in full (the caller's
@@ -476,13 +539,19 @@ static int level_flux_fused(int N, int ns, int S, const T* A, int K, const T* co
   return VSM_OK;
 }
 
+// LDS of the two inelastic kernels: [M | r], q and the partial sums of the column groups
+template <typename T>
+static size_t level_ie_lds(int N) {
+  return ((size_t)N * (N + 1) + (size_t)N + 2 * (size_t)LEVEL_NT) * sizeof(T);
+}
+
 template <typename T>
 static int level_radiance_ie_fused(int N, int ns, int S, int K, const int* shift, int nV, const int* row0_h, const T* w_h, const T* A,
                                    const T* B, long long bstride, const T* dwf, const T* uwf, const T* Aie, const T* aie,
                                    const T* Bie, const T* cie, T* uwie, T* dwie, T* dwie_full, T* uwie_full, hipStream_t st) {
   int* status = device_status();
   if (!status) return VSM_ERR_HIP;
-  const size_t lds = ((size_t)N * (N + 1) + (size_t)N + 2 * (size_t)LEVEL_NT) * sizeof(T);
+  const size_t lds = level_ie_lds<T>(N);
   const int rc = ensure_dyn_lds(reinterpret_cast<const void*>(k_level_radiance_ie<T>), lds, "hipFuncSetAttribute(k_level_radiance_ie)");
   if (rc) return rc;
   return level_launch<T>(
@@ -494,6 +563,24 @@ static int level_radiance_ie_fused(int N, int ns, int S, int K, const int* shift
         return (int)VSM_OK;
       },
       [&](const T* uf, const T* df) { return postprocess_vza<T>(N, ns, S, nV, row0_h, w_h, uf, df, uwie, dwie, st); });
+}
+
+template <typename T>
+static int level_flux_ie_fused(int N, int ns, int S, int K, const int* shift, const T* A, const T* B, long long bstride, const T* dwf,
+                               const T* uwf, const T* Aie, const T* aie, const T* Bie, const T* cie, int nW, const T* q,
+                               const T* dir_h, T mu0, const T* tau_sum, const T* F0_I, T* out, hipStream_t st) {
+  int* status = device_status();
+  if (!status) return VSM_ERR_HIP;
+  const size_t lds = level_ie_lds<T>(N);
+  const int rc = ensure_dyn_lds(reinterpret_cast<const void*>(k_level_flux_ie<T>), lds, "hipFuncSetAttribute(k_level_flux_ie)");
+  if (rc) return rc;
+  level_flux_dir<T> dir = {};
+  for (int r = 0; r < nW; ++r) dir.h[r] = tau_sum ? dir_h[r] : T(0);
+  dir.mu0 = mu0;
+  hipLaunchKernelGGL(k_level_flux_ie<T>, dim3(S), dim3(LEVEL_NT), lds, st, N, ns, S, K, shift, nW, A, B, bstride, dwf, uwf, Aie, aie,
+                     Bie, cie, q, dir, tau_sum, F0_I, out, status);
+  VSM_LAUNCH_CHECK("k_level_flux_ie");
+  return VSM_OK;
 }
 
 // The derivative of the level equation (vsm_level_radiance_lin_*) at point s = blockIdx.x, for every parameter p:
@@ -797,6 +884,26 @@ static int level_ie_check(int N, int ns, int S, int K, const int* shift, int nV,
   return VSM_OK;
 }
 
+// vsm_level_flux_ie_*: level_check_common without a viewing-angle table; the TOA (no top) reads the point's own uw and the
+// bottom's c_ie alone
+template <typename T>
+static int level_flux_ie_check(int N, int ns, int S, int K, const int* shift, const T* A, const T* B, long long bstride, const T* dwf,
+                               const T* uwf, const T* Aie, const T* aie, const T* Bie, const T* cie, int nW, const T* q,
+                               const T* dir_h, T mu0, const T* tau_sum, const T* F0_I, const T* out) {
+  VSM_REQUIRE(nW >= 1 && nW <= 4, "level_flux_ie: nW = %d outside 1..4", nW);
+  const int rc = level_check_common<T>("level_flux_ie", N, LEVEL_FUSED_MAX_N, ns, S, 0, nullptr, nullptr, bstride, nullptr, nullptr);
+  if (rc) return rc;
+  VSM_REQUIRE(K >= 0, "level_flux_ie: bad size (K %d)", K);
+  VSM_REQUIRE((tau_sum == nullptr) == (F0_I == nullptr), "level_flux_ie: tau_sum and F0_I are both given or both NULL");
+  VSM_REQUIRE(!tau_sum || (dir_h && mu0 > T(0)), "level_flux_ie: the direct term needs dir_h and mu0 > 0");
+  VSM_REQUIRE(S == 0 || (uwf && q && out), "level_flux_ie: null elastic uw / weight rows / output");
+  VSM_REQUIRE(S == 0 || !A || (B && dwf), "level_flux_ie: a top needs the bottom's R-+ and the elastic dw");
+  VSM_REQUIRE(S == 0 || K == 0 || shift, "level_flux_ie: null shift");
+  VSM_REQUIRE(S == 0 || K == 0 || !A || (Aie && aie), "level_flux_ie: null top inelastic operand");
+  VSM_REQUIRE((Bie == nullptr) == (cie == nullptr), "level_flux_ie: bot_ieR_mp and bot_ieJ0_m are both given or both NULL");
+  return VSM_OK;
+}
+
 template <typename T>
 static int level_lin_check(const char* who, int N, int ns, int S, int P, int P_top, int nV, const int* row0_h, const T* w_h,
                            const T* A, const T* B, long long bstride, const T* dwf, const T* uwf, const T* Ad, long long ad_pstride,
@@ -1078,6 +1185,21 @@ VSM_LEVEL_FLUX_API(float, f32)
   }
 VSM_LEVEL_IE_API(double, f64)
 VSM_LEVEL_IE_API(float, f32)
+
+#define VSM_LEVEL_FLUX_IE_API(T, SFX)                                                                                           \
+  int vsm_level_flux_ie_##SFX(int N, int n_stokes, int S, int K, const int* shift, const T* top_R_pm, const T* bot_R_mp,        \
+                              long long bot_stride, const T* dw_full, const T* uw_full, const T* top_ieR_pm,                   \
+                              const T* top_ieJ0_p, const T* bot_ieR_mp, const T* bot_ieJ0_m, int nW, const T* q,               \
+                              const T* dir_h, T mu0, const T* tau_sum, const T* F0_I, T* out, void* stream) {                  \
+    int rc = level_flux_ie_check<T>(N, n_stokes, S, K, shift, top_R_pm, bot_R_mp, bot_stride, dw_full, uw_full, top_ieR_pm,    \
+                                    top_ieJ0_p, bot_ieR_mp, bot_ieJ0_m, nW, q, dir_h, mu0, tau_sum, F0_I, out);                \
+    if (rc || S == 0) return rc;                                                                                               \
+    return level_flux_ie_fused<T>(N, n_stokes, S, K, shift, top_R_pm, bot_R_mp, bot_stride, dw_full, uw_full, top_ieR_pm,      \
+                                  top_ieJ0_p, bot_ieR_mp, bot_ieJ0_m, nW, q, dir_h, mu0, tau_sum, F0_I, out,                   \
+                                  as_stream(stream));                                                                          \
+  }
+VSM_LEVEL_FLUX_IE_API(double, f64)
+VSM_LEVEL_FLUX_IE_API(float, f32)
 
 #define VSM_LEVEL_LIN_API(T, SFX)                                                                                               \
   int vsm_level_radiance_lin_##SFX(int N, int n_stokes, int S, int P, int P_top, int nV, const int* row0_h, const T* w_h,      \
