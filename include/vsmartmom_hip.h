@@ -1210,6 +1210,36 @@ int vsm_ss_column_rrs_f32(const vsm_quad_f32* q, int S, int L, int m, int K, con
                           const float* const* tau_sum_h, const float* const* fscatt_h, const int* shift, const float* varpi_ie,
                           const float* Zpp_ie, const float* Zmp_ie, const float* F0, int halo, int nV, const int* row0_h,
                           const float* w_h, float* ieR_SFI, float* ieT_SFI, void* stream);
+/* The linearized twin of vsm_ss_column_rrs_* (the reference has no linearized Raman driver): d ieR_SFI / d x_p and
+ * d ieT_SFI / d x_p of one Fourier moment for the parameter slots [p_lo, min(p_hi, p_layer)) of P.  A (recipient n1, line, donor
+ * n0) source depends on the run's parameters through d0 = tau[n0], d1 = tau[n1] and g0 = fscatt[n0] exp(-tau_sum[n0] / mu_0) only,
+ * and the interaction through exp(-tau[n1] / mu_i) and exp(-tau_sum[n1] / mu_i); varpi_ie, Z_ie, F0, the layers' varpi and the
+ * surface do not enter.  Statement by statement: the forward factors again, the chain rule through (d0, d1, g0) with
+ * g0' = fscatt'[n0] exp(-tau_sum[n0] / mu_0) - g0 tau_sum'[n0] / mu_0, and on the running line sums BEFORE their update
+ *   S+' = (S+' - S+ tau'[n1] / mu_i) exp(-tau[n1] / mu_i) + s+',   S-' += (s-' - s- tau_sum'[n1] / mu_i) exp(-tau_sum[n1] / mu_i),
+ * the TOA layer copied.  In the two close branches of the forward kernel (|d0 - d1| <= 1e-8 on the SZA rows,
+ * |mu_i / mu_0 - d1 / d0| < 1e-8 elsewhere) the partials are the analytic limits of the regular expression's,
+ *   d/d d0 = exp(-d0 / mu_0) / mu_i (1 - d0 / (2 mu_0)),   d/d d1 = -d0 exp(-d0 / mu_0) / (2 mu_i^2),
+ * not derivatives of the close value taken as a function of d0 alone.
+ * Forward tables and `halo` as in vsm_ss_column_rrs_*; tau_dot_h / tau_sum_dot_h / fscatt_dot_h: HOST arrays of L device pointers,
+ * [S,p_layer] each (tau_dot of the layer's FULL tau, the layout of vsm_ss_column_lin_*; a table may have more than p_layer
+ * slots, only the first p_layer are read), each read at n0 and at n1.  ieRdot / ieTdot [nV,n_stokes,S,P] are ACCUMULATED for the
+ * slots of the range below p_layer, each slot computed independently of the range it is called in; slots >= p_layer (the
+ * surface's) are exact zeros and are not touched.  K = 0, S = 0 and p_lo >= p_layer launch nothing.  Invalid arguments (K < 0,
+ * P < 1, p_layer outside [0, P], a slot range outside P or empty, L < 1, null tables, rows outside N) return
+ * VSM_ERR_INVALID_ARG before any launch. */
+int vsm_ss_column_rrs_lin_f64(const vsm_quad_f64* q, int S, int L, int m, int K, int P, int p_layer, int p_lo, int p_hi,
+                              const double* const* tau_h, const double* const* tau_sum_h, const double* const* fscatt_h,
+                              const double* const* tau_dot_h, const double* const* tau_sum_dot_h,
+                              const double* const* fscatt_dot_h, const int* shift, const double* varpi_ie, const double* Zpp_ie,
+                              const double* Zmp_ie, const double* F0, int halo, int nV, const int* row0_h, const double* w_h,
+                              double* ieRdot, double* ieTdot, void* stream);
+int vsm_ss_column_rrs_lin_f32(const vsm_quad_f32* q, int S, int L, int m, int K, int P, int p_layer, int p_lo, int p_hi,
+                              const float* const* tau_h, const float* const* tau_sum_h, const float* const* fscatt_h,
+                              const float* const* tau_dot_h, const float* const* tau_sum_dot_h,
+                              const float* const* fscatt_dot_h, const int* shift, const float* varpi_ie, const float* Zpp_ie,
+                              const float* Zmp_ie, const float* F0, int halo, int nV, const int* row0_h, const float* w_h,
+                              float* ieRdot, float* ieTdot, void* stream);
 
 /* ---- exact single scattering: StandaloneSS (src/StandaloneSS/kernels.jl, linearized_f2.jl) ---------------------------------
  * The first-order field at the true scattering angle of every viewing geometry, in four paths: (1) one scattering in the

@@ -19,7 +19,8 @@ Sub-modules
     CoreRTRaman     rotational-Raman pass: rt_run(RS_type::RRS, model, iBand),
                     rt_run_multisensor(RS_type, model, sensor_levels) (core_rt_ms_raman),
                     rt_run_fluxes(RS_type, model, levels) (core_rt_flux_raman: elastic and inelastic fluxes at the boundaries),
-                    rt_run_ss(RS_type, model, iBand) (core_rt_ss: the single-scatter inelastic correction)
+                    rt_run_ss(RS_type, model, iBand) (core_rt_ss: the single-scatter inelastic correction),
+                    rt_run_ss_lin(RS_type, model, lin_model, ...) (core_rt_ss: its analytic Jacobians, elastic and inelastic)
     StandaloneSS    exact single scattering at the true scattering angle (standalone_ss: run_exact_ss, the four paths,
                     apply_back_correction = exact - truncated first-order field, Jacobians of paths 1 and 2)
     parallel        spectral-axis sharding over the GPUs of one node (torch.distributed / RCCL)
@@ -50,6 +51,7 @@ CoreRTLin.rt_run_multisensor = core_rt_ms_lin.rt_run_multisensor
 CoreRT.rt_run_ss = core_rt_ss.rt_run_ss
 CoreRTRaman.rt_run_ss = core_rt_ss.rt_run_ss_rrs
 CoreRTLin.rt_run_ss = core_rt_ss.rt_run_ss_lin
+CoreRTRaman.rt_run_ss_lin = core_rt_ss.rt_run_ss_rrs_lin
 CoreRTLin.MultiSensorLinResult = core_rt_ms_lin.MultiSensorLinResult
 CoreRT.rt_run_fluxes = core_rt_flux.rt_run_fluxes
 CoreRT.FluxResult = core_rt_flux.FluxResult

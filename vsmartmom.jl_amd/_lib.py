@@ -152,6 +152,8 @@ _SIGS = {
     "vsm_ss_column_lin_{T}": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P,
                                    _P, _P, _I, _P, _P, _P, _P, _P]),
     "vsm_ss_column_rrs_{T}": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
+    "vsm_ss_column_rrs_lin_{T}": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P,
+                                       _P, _P]),
     "vsm_exact_ss_path1_{T}": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, "{R}", _P, _P, _P]),
     "vsm_exact_ss_path2_{T}": (_I, [_I, _I, _I, _I, _I, _P, _P, _I, _P, "{R}", _P, _P, _P]),
     "vsm_exact_ss_path34_{T}": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, "{R}", _P, _P, _P, _P]),

@@ -31,6 +31,7 @@ class RRS:
     varpi_lambda1lambda0: np.ndarray  # ϖ_λ₁λ₀ [K]
     greek_raman: H.GreekCoefs         # get_greek_raman (inelastic_helper.jl:864-882)
     fscattRayl: Optional[np.ndarray] = None   # [S, Nz] fScattRayleigh per layer (compEffectiveLayerProperties.jl:56)
+    fscattRayl_dot: Optional[np.ndarray] = None   # [7 NAer + NGas, S, Nz]: its parameter derivatives (CoreRTRaman.rt_run_ss_lin only)
 
 
 class AddedLayerRS:

@@ -1,6 +1,7 @@
 """Single-scattering runs: rt_run_ss(model) and rt_run_ss(RS_type::RRS, model, iBand) (src/CoreRT/rt_run.jl:574-755) on the MI355X,
 through vsm_ss_column_* / vsm_ss_column_rrs_* (vsmartmom.jl_amd/csrc/vsm_ss.hip), and the linearized elastic run
-rt_run_ss(model, lin_model, NAer, NGas, NSurf) through vsm_ss_column_lin_* (SceneSSLin; the reference has no such driver).
+rt_run_ss(model, lin_model, NAer, NGas, NSurf) through vsm_ss_column_lin_* (SceneSSLin; the reference has no such driver), and
+the linearized Raman run rt_run_ss_rrs_lin(RS_type, model, lin_model, ...) through vsm_ss_column_rrs_lin_* (SceneSSRamanLin; ours too).
 
 Mirrors rt_kernel_ss! (CoreKernel/rt_kernel_ss.jl:156-337: elemental! / elemental_inelastic! with ndoubl = 0 and dtau = the layer's
 tau, scatter hard-wired to true), interaction_ss! / interaction_inelastic_ss! (CoreKernel/interaction_ss.jl), the surface's
@@ -192,12 +193,12 @@ class SceneSSLin(CL.LinInputs):
     varying Lambertian surfaces too, whose builder runs in its vectors-only mode here (the column kernel reads j0- and ap_J0-+
     alone; the forward scene keeps its per-point surface layer)."""
 
-    def __init__(self, model: H.RTModel, lin_model: H.LinModel, NAer: int, NGas: int, NSurf: int):
+    def __init__(self, model: H.RTModel, lin_model: H.LinModel, NAer: int, NGas: int, NSurf: int, RS_type=None, iBand: int = 1):
         _refuse_sources(model)
         self._check_lin_args(model, lin_model, NAer, NGas, NSurf)
         if 1 + 5 * NAer > 16:
             raise NotImplementedError("rt_run_ss (linearized): at most three aerosols (16 component blocks of Z_dot); got %d" % NAer)
-        self.ss = SceneSS(model)
+        self.ss = SceneSS(model, RS_type, iBand)     # (an RS_type: SceneSSRamanLin's; the scene then launches the Raman column too)
         self.fwd = fwd = self.ss.fwd
         self._alloc_lin_optics()
         self._nd0 = torch.zeros(fwd.Nz, dtype=torch.int32, device=fwd.dev)
@@ -255,9 +256,13 @@ class SceneSSLin(CL.LinInputs):
                            None if self.zdcoef is None else [self.zdcoef[iz] for iz in range(L)], self.CT if self.Zall else 0,
                            zall[0], zall[1], self.F0, self.added_s.j0_m, fwd.added_surface.j0_p, self.als.ap_J0_m, self.als.ap_J0_p,
                            tau_sum_s, tsd_s, row0, w, nV, self.Rd, self.Td)
+            self._after_lin_moment(mom, props, row0, w)
 
         self.ss.run(after_moment=lin_moment)     # R, T: the launches of rt_run_ss (bit for bit); one walk over the moments
         return self.R, self.T, self.Rd, self.Td
+
+    def _after_lin_moment(self, mom, props, row0, w):
+        """Further launches of the moment, after the linearized elastic column (SceneSSRamanLin: the linearized Raman column)."""
 
     def results_host(self):
         """(R, T, Rdot, Tdot): [nVZA, nStokes, nSpec] and [nVZA, nStokes, nSpec, Nparams], as rt_run_lin returns them."""
@@ -279,4 +284,96 @@ def rt_run_ss_lin(model: H.RTModel, lin_model: H.LinModel, NAer: int, NGas: int,
     scene.run()
     synchronize_if_gpu()
     _lib.check_device_status("rt_run_ss (linearized)")
+    return scene.results_host()
+
+
+def ss_column_rrs_lin_(dq: CR.DeviceQuad, m: int, P: int, p_layer: int, tau, tau_sum, fscatt, tau_dot, tau_sum_dot, fscatt_dot, shift,
+                       varpi_ie, Zpp_ie, Zmp_ie, F0, halo: int, row0, w, nV: int, ieRdot, ieTdot, p_range=None):
+    """vsm_ss_column_rrs_lin_*: one Fourier moment of the linearized rotational-Raman single-scattering column.  Layer lists as in
+    ss_column_rrs_, plus tau_dot / tau_sum_dot / fscatt_dot (lists of L device tensors (>= p_layer, S); tau_dot of the layer's full
+    tau; None where p_layer = 0).  ieRdot / ieTdot (P, S, nStokes, nVZA) accumulate the slots of p_range = (p_lo, p_hi) (default:
+    all P) below p_layer; the others are not touched."""
+    L, S, K = len(tau), int(F0.shape[0]), int(shift.numel())
+    q = dq.cstruct()
+    tab = lambda ts: None if ts is None else (C.c_void_p * L)(*[None if t is None else t.data_ptr() for t in ts])
+    p_lo, p_hi = (0, P) if p_range is None else p_range
+    _lib.call("vsm_ss_column_rrs_lin", dq.dtype, C.byref(q), S, L, m, K, P, p_layer, int(p_lo), int(p_hi), tab(tau), tab(tau_sum),
+              tab(fscatt), tab(tau_dot), tab(tau_sum_dot), tab(fscatt_dot), CR._ptr(shift), CR._ptr(varpi_ie), CR._ptr(Zpp_ie),
+              CR._ptr(Zmp_ie), CR._ptr(F0), int(halo), nV, row0, w, CR._ptr(ieRdot), CR._ptr(ieTdot), CR._stream_ptr())
+
+
+class SceneSSRamanLin(SceneSSLin):
+    """The linearized single-scattering run with rotational Raman scattering: a SceneSSLin whose SceneSS carries the RS_type, so
+    that one walk over the moments launches the elastic column, the Raman column (rt_run_ss_rrs's launches, bit for bit), the
+    linearized elastic column (rt_run_ss_lin's) and, in the same after_moment hook, the linearized Raman column
+    (vsm_ss_column_rrs_lin_*).  What it adds to the two scenes: fscatt_dot (Nz, max(p_layer, 1), S) and the two derivative outputs
+    (P, S, nStokes, nVZA) -- nothing with a line axis, nothing of size P N^2 S.
+
+    fscatt_dot: with RS_type.fscattRayl None, fscatt = tau_rayl / tau_scatt (default_fscatt) moves with the aerosol slots alone,
+    whose tau_dot is d tau_scatt / dx exactly: fscatt_dot[p] = -fscatt^2 tau_dot[p] / tau_rayl there (0 where tau_rayl = 0), 0 on
+    the gas slots; formed on the device from dtau_dot_all and the uploaded tau_rayl.  A stated fscattRayl needs a stated
+    RS_type.fscattRayl_dot [7 NAer + NGas, nSpec, Nz]."""
+
+    def __init__(self, RS_type, model: H.RTModel, lin_model: H.LinModel, NAer: int, NGas: int, NSurf: int, iBand: int = 1):
+        if iBand != 1:
+            raise _lib.VSMError("single-band models only (iBand = 1)")
+        fsd = getattr(RS_type, "fscattRayl_dot", None)
+        if RS_type.fscattRayl is not None and fsd is None:
+            raise _lib.VSMError("rt_run_ss (linearized, RRS): a stated fscattRayl needs fscattRayl_dot [7 NAer + NGas, nSpec, Nz]: "
+                                "its dependence on the parameters cannot be guessed")
+        if fsd is not None:
+            fsd = np.asarray(fsd, dtype=model.float_type)
+            want = (7 * NAer + NGas,) + tuple(model.tau_rayl.shape)
+            if fsd.shape != want:
+                raise _lib.VSMError("RRS.fscattRayl_dot: [7 NAer + NGas, nSpec, Nz] = %r expected, got %r" % (want, fsd.shape))
+        super().__init__(model, lin_model, NAer, NGas, NSurf, RS_type=RS_type, iBand=iBand)
+        fwd, L, S, pl = self.fwd, self.fwd.Nz, self.S, self.pl
+        self.fscatt_dot = torch.zeros((L, max(pl, 1), S), dtype=self.dt, device=fwd.dev)
+        if fsd is not None:
+            if pl:
+                self.fscatt_dot.copy_(array_type(self.arch)(np.ascontiguousarray(fsd.transpose(2, 0, 1))))
+        elif NAer:
+            na = 7 * NAer
+            rayl = fwd.tau_rayl_d[:, fwd.lo:fwd.lo + S]                                          # (L, S), FP64
+            fs = self.ss.fscatt.to(torch.float64)
+            d = -(fs * fs / rayl)[:, None, :] * self.dtau_dot_all[:, :na, :].to(torch.float64)
+            self.fscatt_dot[:, :na, :] = torch.where((rayl > 0)[:, None, :], d, torch.zeros_like(d)).to(self.dt)
+        self.ieR, self.ieT = self.ss.out[2], self.ss.out[3]
+        self.ieRd, self.ieTd = torch.zeros_like(self.Rd), torch.zeros_like(self.Rd)
+
+    def _after_lin_moment(self, mom, props, row0, w):
+        L, ss, pl = self.fwd.Nz, self.ss, self.pl
+        Zp, Zm = ss.Zie[mom["m"]]
+        dots = lambda t: [t[iz] for iz in range(L)] if pl else None
+        ss_column_rrs_lin_(self.fwd.dq, mom["m"], self.P, pl, [p.tau for p in props], [ly["tau_sum"] for ly in mom["layers"]],
+                           [ss.fscatt[iz] for iz in range(L)], dots(self.dtau_dot_all), dots(self.tau_sum_dot),
+                           dots(self.fscatt_dot), ss.drs.shift, ss.drs.varpi_ie, Zp, Zm, self.F0, ss.halo, row0, w,
+                           len(self.model.vza), self.ieRd, self.ieTd)
+
+    def run(self):
+        """Asynchronous; returns R, T, ieR, ieT (S, nStokes, nVZA) and Rdot, Tdot, ieRdot, ieTdot (P, S, nStokes, nVZA)."""
+        self.ieRd.zero_()
+        self.ieTd.zero_()
+        R, T, Rd, Td = super().run()
+        return R, T, self.ieR, self.ieT, Rd, Td, self.ieRd, self.ieTd
+
+    def results_host(self):
+        """(R1, T1, ieR1, ieT1, R1dot, T1dot, ieR1dot, ieT1dot): [nVZA, nStokes, nSpec] x 4, [nVZA, nStokes, nSpec, Nparams] x 4."""
+        tr = lambda t: to_host(t).transpose(2, 1, 0).copy()
+        tr4 = lambda t: to_host(t).transpose(3, 2, 1, 0).copy()
+        return (tr(self.R), tr(self.T), tr(self.ieR), tr(self.ieT), tr4(self.Rd), tr4(self.Td), tr4(self.ieRd), tr4(self.ieTd))
+
+
+def rt_run_ss_rrs_lin(RS_type, model: H.RTModel, lin_model: H.LinModel, NAer: int, NGas: int, NSurf: int, iBand: int = 1):
+    """The linearized single-scattering run with rotational Raman scattering -> (R1, T1, ieR1, ieT1, R1dot, T1dot, ieR1dot,
+    ieT1dot).  R1, T1, R1dot, T1dot are rt_run_ss_lin(model, lin_model, ...)'s and ieR1, ieT1 rt_run_ss_rrs(RS_type, model)'s, bit
+    for bit; ieR1dot / ieT1dot [nVZA, nStokes, nSpec, Nparams] are the analytic Jacobians of the inelastic arrays in the slots of
+    rt_run_lin (the surface slots exact zeros: the surface has no inelastic single-scattering part).  The parameters act through
+    the layers' tau and tau_sum and through fScattRayleigh (SceneSSRamanLin); the line strengths and the Raman phase matrix are
+    no parameters.  Refusals: those of rt_run_ss_lin and of rt_run_ss_rrs, and a stated RS_type.fscattRayl without
+    fscattRayl_dot.  No sharding, no hem_R / hem_T derivatives, no spectral blocking."""
+    scene = SceneSSRamanLin(RS_type, model, lin_model, NAer, NGas, NSurf, iBand)
+    scene.run()
+    synchronize_if_gpu()
+    _lib.check_device_status("rt_run_ss (linearized, RRS)")
     return scene.results_host()

@@ -7,6 +7,8 @@
 //   vsm_ss_column_lin_*  the parameter derivative of vsm_ss_column_*: the source derivatives of get_elem_rt_SFI_fused!
 //                        (elemental_lin.jl:602-712) with ndoubl = 0 and dtau = tau, the two differentiated statements of
 //                        get_interaction_ss!, the linearized surface builders' sources and postprocessing_vza! (lin)
+//   vsm_ss_column_rrs_lin_*  the parameter derivative of vsm_ss_column_rrs_* (the reference has none): the chain rule through
+//                        tau[n0], tau[n1] and fscatt[n0] exp(-tau_sum[n0] / mu_0), the close branches by their limit partials
 // Lanes run along the spectral axis; a thread carries the running sources of SS_RB rows of its point in registers through all
 // layers.  Nothing here is N x N: of the phase matrices only the n_stokes SZA columns are read.
 #include <string.h>
@@ -463,6 +465,302 @@ __global__ __launch_bounds__(SS_TB) void k_ss_column_lin(int N, int ns, int S, i
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// Raman column, linearized
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int SS_RPC = 2;   // parameter slots a thread of the Raman derivative carries: (12 + 2 SS_RPC) staged values per window point
+                            // = 64 KB of LDS at FP64 with the maximal halo (the forward kernel's 12 values: 48 KB)
+
+template <typename T>
+struct ss_layer_rrs_lin {
+  const T *tau, *tau_sum, *fscatt;
+  const T *tau_dot, *tau_sum_dot, *fscatt_dot;   // [S, p_layer] each (tau_dot: of the layer's full tau)
+};
+
+// The partial derivatives of the two line sources of k_ss_column_rrs in (d0, d1) = (tau[n0], tau[n1]).  With u = d0 / mu_0,
+// v = d1 / mu_i, psi(x) = (1 - e^-x) / x and phi(u, v) = (e^-v - e^-u) / (u - v) the forward statements are
+//   j+ = c+ g0 G,  G = (e^-v - e^-u) / (mu_i / mu_0 - d1 / d0) = (d0 / mu_i) phi(u, v)
+//   j- = c- g0 H,  H = (1 - e^-(u + v)) / (mu_i / mu_0 + d1 / d0) = (d0 / mu_i) psi(u + v)
+// (the SZA rows are mu_i = mu_0), so that
+//   G_d0 = (phi + u phi_u) / mu_i,        G_d1 = (d0 / mu_i^2) phi_v,      phi_v = -phi - phi_u
+//   H_d0 = (psi + u psi') / mu_i,         H_d1 = (d0 / mu_i^2) psi'        (psi, psi' at u + v).
+// phi = e^-v psi(t) = e^-u psi(-t) with t = u - v, and phi_u = e^-v psi'(t) = -phi - e^-u psi'(-t): psi and psi' are taken at
+// |t| from the side that cannot overflow, as expdiff_neg does.  Written as quotients of the regular expression the partials
+// cancel like eps / (u - v)^2; psi' below does not.  In the close branches of the forward kernel (its tests, on d0 - d1 and on
+// mu_i / mu_0 - d1 / d0: u = v) G = (d0 / mu_i) e^-u, and the partials are the limits phi = e^-u, phi_u = phi_v = -e^-u / 2:
+//   G_d0 = e^-u / mu_i (1 - d0 / (2 mu_0)),   G_d1 = -d0 e^-u / (2 mu_i^2);
+// the close value is NOT differentiated as a function of d0 alone.
+template <typename T>
+struct ss_rrs_partials {
+  T G, G0, G1, H, H0, H1;
+};
+// psi'(x) = (x e^-x - (1 - e^-x)) / x^2 for x >= 0, em = expm1(-x), ix = 1 / x: the closed form cancels like eps / x^2, so below
+// 1/8 the series sum_j (-1)^(j+1) (j + 1) / (j + 2)! x^j (11 terms: 2e-17 at 1/8)
+template <typename T>
+__device__ __forceinline__ T ss_psi1(T x, T em, T ix) {
+  if (x < T(0.125)) {
+    T p = T(-1.0 / 43545600.0);
+    p = p * x + T(1.0 / 3991680.0);
+    p = p * x - T(1.0 / 403200.0);
+    p = p * x + T(1.0 / 45360.0);
+    p = p * x - T(1.0 / 5760.0);
+    p = p * x + T(1.0 / 840.0);
+    p = p * x - T(1.0 / 144.0);
+    p = p * x + T(1.0 / 30.0);
+    p = p * x - T(0.125);
+    p = p * x + T(1.0 / 3.0);
+    return p * x - T(0.5);
+  }
+  return (x * (T(1) + em) + em) * ix * ix;
+}
+// (ratio = d1 / d0 once per line; imi = 1 / mu_i and ims = 1 / mu_0 once per thread: two divisions are left per line and row)
+template <typename T>
+__device__ __forceinline__ ss_rrs_partials<T> ss_rrs_line(bool sun, T d0, T d1, T ratio, T x0, T e0, T a0, T x1, T e1, T a1, T imi,
+                                                          T ims, T rm) {
+  ss_rrs_partials<T> r;
+  const T c = d0 * imi;
+  const bool close = sun ? !(fabs(d0 - d1) > ss_tol<T>::close()) : (fabs(rm - ratio) < ss_tol<T>::close());
+  if (close) {
+    r.G = c * e0;
+    r.G0 = e0 * imi * (T(1) - T(0.5) * x0);
+    r.G1 = -T(0.5) * c * imi * e0;
+  } else {
+    const T t = x0 - x1, at = fabs(t);
+    const T em = expm1(-at), it = T(1) / at;
+    const T psi = (at == T(0)) ? T(1) : -em * it;
+    const T p1 = ss_psi1<T>(at, em, it);
+    const T phi = (t > T(0) ? e1 : e0) * psi;
+    const T phi_u = (t > T(0)) ? e1 * p1 : -phi - e0 * p1;
+    r.G = c * phi;
+    r.G0 = imi * (phi + x0 * phi_u);
+    r.G1 = -c * imi * (phi + phi_u);
+  }
+  const T sm = x0 + x1;
+  const T A = -(a1 + a0 + a1 * a0), is = T(1) / sm;   // 1 - exp(-(x1 + x0)) = -(a1 + a0 + a1 a0) with a = expm1(-x)
+  const T psi = (sm == T(0)) ? T(1) : A * is;
+  const T p1 = ss_psi1<T>(sm, -A, is);
+  r.H = c * psi;
+  r.H0 = imi * (psi + x0 * p1);
+  r.H1 = c * imi * p1;
+  return r;
+}
+
+// The derivative of k_ss_column_rrs for the slots [p_lo + SS_RPC blockIdx.z, +SS_RPC) below min(p_hi, p_layer).  The run's
+// parameters reach a (recipient n1, line, donor n0) source through d0, d1 and g0 = fscatt[n0] exp(-tau_sum[n0] / mu_0) only
+// (varpi_ie, Z_ie, F0, the layers' varpi and the surface do not enter), so per slot the donor side is TWO more staged values per
+// (window point, layer): d0' and g0' = fscatt'[n0] exp(-tau_sum[n0] / mu_0) - g0 tau_sum'[n0] / mu_0.  The forward factors are
+// formed again; the interaction is differentiated on the running line sums before their update:
+//   S+' = (S+' - S+ tau'[n1] / mu_i) e1 + s+',    S-' += (s-' - s- tau_sum'[n1] / mu_i) exp(-tau_sum[n1] / mu_i).
+template <typename T>
+__global__ __launch_bounds__(SS_TB) void k_ss_column_rrs_lin(int N, int ns, int S, int L, int K, int m, int i_mu0, int halo,
+                                                             int p_layer, int p_lo, int p_hi,
+                                                             const ss_layer_rrs_lin<T>* __restrict__ lay,
+                                                             const int* __restrict__ shift, const T* __restrict__ varpi_ie,
+                                                             const T* __restrict__ Zpp, const T* __restrict__ Zmp,
+                                                             const T* __restrict__ F0, const T* __restrict__ mu, int nV,
+                                                             const int* __restrict__ row0, const T* __restrict__ w, T* ieRd,
+                                                             T* ieTd) {
+  extern __shared__ __align__(16) unsigned char ss_smem[];
+  const int W = SS_TB + 2 * halo;
+  T* sd = reinterpret_cast<T*>(ss_smem);   // [W] each
+  T* se0 = sd + W;
+  T* sa0 = se0 + W;
+  T* sg = sa0 + W;
+  T* szp = sg + W;                         // [SS_RB][W]
+  T* szm = szp + SS_RB * W;
+  T* sdd = szm + SS_RB * W;                // [SS_RPC][W]: d0'
+  T* sgd = sdd + SS_RPC * W;               // [SS_RPC][W]: g0'
+  const long long b0 = (long long)blockIdx.x * SS_TB;
+  const long long w0 = b0 - halo;
+  const long long n1 = b0 + threadIdx.x;
+  const bool live = n1 < S;
+  const int i_start = ns * i_mu0;
+  const int p0 = p_lo + (int)blockIdx.z * SS_RPC;
+  const int p_end = p_hi < p_layer ? p_hi : p_layer;
+  const ss_rows<T> rw = ss_pick_rows<T>(true, N, ns, nV, row0, mu, blockIdx.y * SS_RB);
+  const T ms = mu[i_start];
+  const T wct02 = (m == 0) ? T(0.5) : T(0.25);
+  for (int p = threadIdx.x; p < W; p += SS_TB) {
+    const long long n0 = w0 + p;
+    const bool in = n0 >= 0 && n0 < S;
+#pragma unroll
+    for (int j = 0; j < SS_RB; ++j) {
+      T zp = 0, zm = 0;
+      if (in && rw.on[j])
+        for (int q = 0; q < ns; ++q) {
+          const long long zo = rw.i[j] + (long long)N * (i_start + q);
+          const T f = F0[q + (long long)ns * n0];
+          zp += Zpp[zo] * f;
+          zm += Zmp[zo] * f;
+        }
+      szp[j * W + p] = zp;
+      szm[j * W + p] = zm;
+    }
+  }
+  T rm[SS_RB], imi[SS_RB], Sp[SS_RB], Dp[SS_RB][SS_RPC], Dm[SS_RB][SS_RPC];
+  bool sun[SS_RB];
+  const T ims = T(1) / ms;
+#pragma unroll
+  for (int j = 0; j < SS_RB; ++j) {
+    rm[j] = rw.mi[j] / ms;
+    imi[j] = T(1) / rw.mi[j];
+    sun[j] = rw.i[j] >= i_start && rw.i[j] < i_start + ns;
+    Sp[j] = T(0);
+#pragma unroll
+    for (int k = 0; k < SS_RPC; ++k) Dp[j][k] = Dm[j][k] = T(0);
+  }
+  for (int iz = 0; iz < L; ++iz) {
+    const ss_layer_rrs_lin<T> ly = lay[iz];
+    __syncthreads();   // the previous layer's readers are done (first pass: nothing to wait for but the Z F0 stage)
+    for (int p = threadIdx.x; p < W; p += SS_TB) {
+      const long long n0 = w0 + p;
+      T d0 = T(1), e0 = T(0), a0 = T(0), g0 = T(0), dd[SS_RPC], gd[SS_RPC];
+#pragma unroll
+      for (int k = 0; k < SS_RPC; ++k) dd[k] = gd[k] = T(0);
+      if (n0 >= 0 && n0 < S) {
+        d0 = ly.tau[n0];
+        const T x0 = d0 / ms;
+        e0 = exp(-x0);
+        a0 = expm1(-x0);
+        const T att = exp(-ly.tau_sum[n0] / ms);
+        g0 = ly.fscatt[n0] * att;
+#pragma unroll
+        for (int k = 0; k < SS_RPC; ++k)
+          if (p0 + k < p_end) {
+            const long long o = n0 + (long long)S * (p0 + k);
+            dd[k] = ly.tau_dot[o];
+            gd[k] = ly.fscatt_dot[o] * att - g0 * ly.tau_sum_dot[o] / ms;
+          }
+      }
+      sd[p] = d0;
+      se0[p] = e0;
+      sa0[p] = a0;
+      sg[p] = g0;
+#pragma unroll
+      for (int k = 0; k < SS_RPC; ++k) {
+        sdd[k * W + p] = dd[k];
+        sgd[k * W + p] = gd[k];
+      }
+    }
+    __syncthreads();
+    if (!live) continue;
+    const T d1 = ly.tau[n1], ts1 = ly.tau_sum[n1];
+    T d1d[SS_RPC], ts1d[SS_RPC];
+#pragma unroll
+    for (int k = 0; k < SS_RPC; ++k) {
+      const bool in = p0 + k < p_end;
+      const long long o = n1 + (long long)S * (in ? p0 + k : 0);
+      d1d[k] = in ? ly.tau_dot[o] : T(0);
+      ts1d[k] = in ? ly.tau_sum_dot[o] : T(0);
+    }
+    T x1[SS_RB], e1[SS_RB], a1[SS_RB], sp[SS_RB], sm[SS_RB], spd[SS_RB][SS_RPC], smd[SS_RB][SS_RPC];
+#pragma unroll
+    for (int j = 0; j < SS_RB; ++j) {
+      x1[j] = d1 / rw.mi[j];
+      e1[j] = exp(-x1[j]);
+      a1[j] = expm1(-x1[j]);
+      sp[j] = sm[j] = T(0);
+#pragma unroll
+      for (int k = 0; k < SS_RPC; ++k) spd[j][k] = smd[j][k] = T(0);
+    }
+    for (int dn = 0; dn < K; ++dn) {
+      const long long n0 = n1 + shift[dn];
+      if (n0 < 0 || n0 >= S) continue;   // out of band: exactly zero (elemental_inelastic.jl:500)
+      const T wl = varpi_ie[dn];
+      const long long p = n0 - w0;
+      const bool staged = p >= 0 && p < W;
+      T d0, e0, a0, g0, dd[SS_RPC], gd[SS_RPC];
+      if (staged) {
+        d0 = sd[p];
+        e0 = se0[p];
+        a0 = sa0[p];
+        g0 = sg[p];
+#pragma unroll
+        for (int k = 0; k < SS_RPC; ++k) {
+          dd[k] = sdd[k * W + p];
+          gd[k] = sgd[k * W + p];
+        }
+      } else {   // a shift beyond the staged window: the same factors from global memory
+        d0 = ly.tau[n0];
+        const T x0g = d0 / ms;
+        e0 = exp(-x0g);
+        a0 = expm1(-x0g);
+        const T att = exp(-ly.tau_sum[n0] / ms);
+        g0 = ly.fscatt[n0] * att;
+#pragma unroll
+        for (int k = 0; k < SS_RPC; ++k) {
+          dd[k] = gd[k] = T(0);
+          if (p0 + k < p_end) {
+            const long long o = n0 + (long long)S * (p0 + k);
+            dd[k] = ly.tau_dot[o];
+            gd[k] = ly.fscatt_dot[o] * att - g0 * ly.tau_sum_dot[o] / ms;
+          }
+        }
+      }
+      const T x0 = d0 / ms, ratio = d1 / d0;
+#pragma unroll
+      for (int j = 0; j < SS_RB; ++j) {
+        if (!rw.on[j]) continue;
+        T zp, zm;
+        if (staged) {
+          zp = szp[j * W + p];
+          zm = szm[j * W + p];
+        } else {
+          zp = zm = T(0);
+          for (int q = 0; q < ns; ++q) {
+            const long long zo = rw.i[j] + (long long)N * (i_start + q);
+            const T f = F0[q + (long long)ns * n0];
+            zp += Zpp[zo] * f;
+            zm += Zmp[zo] * f;
+          }
+        }
+        const ss_rrs_partials<T> f = ss_rrs_line<T>(sun[j], d0, d1, ratio, x0, e0, a0, x1[j], e1[j], a1[j], imi[j], ims, rm[j]);
+        const T cp = wct02 * wl * zp, cm = wct02 * wl * zm;
+        sp[j] += cp * g0 * f.G;
+        sm[j] += cm * g0 * f.H;
+#pragma unroll
+        for (int k = 0; k < SS_RPC; ++k) {
+          spd[j][k] += cp * (gd[k] * f.G + g0 * (f.G0 * dd[k] + f.G1 * d1d[k]));
+          smd[j][k] += cm * (gd[k] * f.H + g0 * (f.H0 * dd[k] + f.H1 * d1d[k]));
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < SS_RB; ++j) {
+      if (iz == 0) {   // rt_kernel_ss.jl:308-314: the TOA layer is copied
+#pragma unroll
+        for (int k = 0; k < SS_RPC; ++k) {
+          Dp[j][k] = spd[j][k];
+          Dm[j][k] = smd[j][k];
+        }
+        Sp[j] = sp[j];
+      } else {         // get_interaction_ss_RRS! (interaction_ss.jl:87-88) on the line sums, differentiated
+        const T es = exp(-ts1 / rw.mi[j]);
+#pragma unroll
+        for (int k = 0; k < SS_RPC; ++k) {
+          Dp[j][k] = (Dp[j][k] - Sp[j] * d1d[k] * imi[j]) * e1[j] + spd[j][k];
+          Dm[j][k] = Dm[j][k] + (smd[j][k] - sm[j] * ts1d[k] * imi[j]) * es;
+        }
+        Sp[j] = Sp[j] * e1[j] + sp[j];
+      }
+    }
+  }
+  if (!live) return;
+#pragma unroll
+  for (int j = 0; j < SS_RB; ++j) {
+    if (!rw.on[j]) continue;
+    const int e = blockIdx.y * SS_RB + j;
+#pragma unroll
+    for (int k = 0; k < SS_RPC; ++k) {
+      const int p = p0 + k;
+      if (p >= p_end) continue;
+      const long long dst = ((((long long)p * S + n1) * ns + e / nV) * nV) + e % nV;
+      ieRd[dst] += w[e] * Dm[j][k];
+      ieTd[dst] += w[e] * Dp[j][k];
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
 // Device tables of one call in the library's scratch: ss_layer[L] | w[nV n_stokes] | row0[nV].  One stream-ordered copy of a
@@ -625,6 +923,50 @@ static int ss_column_rrs(const Q* q, int S, int L, int m, int K, const T* const*
   return VSM_OK;
 }
 
+template <typename T, typename Q>
+static int ss_column_rrs_lin(const Q* q, int S, int L, int m, int K, int P, int p_layer, int p_lo, int p_hi, const T* const* tau_h,
+                             const T* const* tau_sum_h, const T* const* fscatt_h, const T* const* tau_dot_h,
+                             const T* const* tau_sum_dot_h, const T* const* fscatt_dot_h, const int* shift, const T* varpi_ie,
+                             const T* Zpp_ie, const T* Zmp_ie, const T* F0, int halo, int nV, const int* row0_h, const T* w_h,
+                             T* ieRd, T* ieTd, void* stream) {
+  int rc;
+  if ((rc = ss_check_common<T>("ss_column_rrs_lin", q, S, L, nV, row0_h, w_h))) return rc;
+  VSM_REQUIRE(K >= 0, "ss_column_rrs_lin: K >= 0 required (K = %d)", K);
+  VSM_REQUIRE(P >= 1 && p_layer >= 0 && p_layer <= P,
+              "ss_column_rrs_lin: P >= 1 and 0 <= p_layer <= P required (P = %d, p_layer = %d)", P, p_layer);
+  VSM_REQUIRE(p_lo >= 0 && p_lo < p_hi && p_hi <= P, "ss_column_rrs_lin: slot range [%d, %d) outside [0, %d)", p_lo, p_hi, P);
+  VSM_REQUIRE((p_hi - p_lo + SS_RPC - 1) / SS_RPC <= 65535, "ss_column_rrs_lin: too many slots");
+  VSM_REQUIRE(tau_h && tau_sum_h && fscatt_h, "ss_column_rrs_lin: null layer table");
+  VSM_REQUIRE(p_layer == 0 || (tau_dot_h && tau_sum_dot_h && fscatt_dot_h), "ss_column_rrs_lin: null derivative table");
+  VSM_REQUIRE(F0 && ieRd && ieTd && Zpp_ie && Zmp_ie, "ss_column_rrs_lin: null argument");
+  VSM_REQUIRE(K == 0 || (shift && varpi_ie), "ss_column_rrs_lin: null line table");
+  VSM_REQUIRE(m >= 0 && halo >= 0, "ss_column_rrs_lin: m >= 0 and halo >= 0");
+  std::vector<ss_layer_rrs_lin<T>> lay((size_t)L);
+  for (int iz = 0; iz < L; ++iz) {
+    VSM_REQUIRE(tau_h[iz] && tau_sum_h[iz] && fscatt_h[iz], "ss_column_rrs_lin: null entry in layer table %d", iz);
+    VSM_REQUIRE(p_layer == 0 || (tau_dot_h[iz] && tau_sum_dot_h[iz] && fscatt_dot_h[iz]),
+                "ss_column_rrs_lin: null entry in derivative table %d", iz);
+    lay[iz] = ss_layer_rrs_lin<T>{tau_h[iz], tau_sum_h[iz], fscatt_h[iz], p_layer ? tau_dot_h[iz] : nullptr,
+                                  p_layer ? tau_sum_dot_h[iz] : nullptr, p_layer ? fscatt_dot_h[iz] : nullptr};
+  }
+  const int p_end = p_hi < p_layer ? p_hi : p_layer;   // the surface's slots (and any later ones) are exact zeros: not touched
+  if (S == 0 || K == 0 || p_lo >= p_end) return VSM_OK;
+  if (halo > VSM_SS_MAX_HALO) halo = VSM_SS_MAX_HALO;
+  hipStream_t st = as_stream(stream);
+  ss_tables<T, ss_layer_rrs_lin<T>> t;
+  if ((rc = ss_upload<T, ss_layer_rrs_lin<T>>(L, lay, q->n_stokes, nV, row0_h, w_h, st, &t))) return rc;
+  const unsigned gx = (unsigned)((S + SS_TB - 1) / SS_TB);
+  const unsigned gv = (unsigned)((nV * q->n_stokes + SS_RB - 1) / SS_RB);
+  const unsigned gp = (unsigned)((p_end - p_lo + SS_RPC - 1) / SS_RPC);
+  const size_t lds = sizeof(T) * (size_t)(4 + 2 * SS_RB + 2 * SS_RPC) * (size_t)(SS_TB + 2 * halo);
+  static_assert(sizeof(double) * (4 + 2 * SS_RB + 2 * SS_RPC) * (VSM_SS_BLOCK + 2 * VSM_SS_MAX_HALO) <= 65536,
+                "k_ss_column_rrs_lin: a workgroup stays within 64 KB of LDS");
+  hipLaunchKernelGGL(k_ss_column_rrs_lin<T>, dim3(gx, gv, gp), dim3(SS_TB), lds, st, q->N, q->n_stokes, S, L, K, m, q->i_mu0, halo,
+                     p_layer, p_lo, p_hi, t.lay, shift, varpi_ie, Zpp_ie, Zmp_ie, F0, q->mu, nV, t.row0, t.w, ieRd, ieTd);
+  VSM_LAUNCH_CHECK("k_ss_column_rrs_lin");
+  return VSM_OK;
+}
+
 }  // namespace vsm
 
 using namespace vsm;
@@ -659,6 +1001,15 @@ extern "C" {
                             tau_dot_h, varpi_dot_h, tau_sum_dot_h, zdcoef_h, CT, Zc_pp, Zc_mp, F0, surf_j0_m, surf_j0_p,       \
                             surf_j0_m_lin, surf_j0_p_lin, tau_sum_surface, tau_sum_dot_surface, nV, row0_h, w_h, Rdot, Tdot,   \
                             stream);                                                                                           \
+  }                                                                                                                            \
+  int vsm_ss_column_rrs_lin_##SFX(const vsm_quad_##SFX* q, int S, int L, int m, int K, int P, int p_layer, int p_lo, int p_hi, \
+                                  const T* const* tau_h, const T* const* tau_sum_h, const T* const* fscatt_h,                  \
+                                  const T* const* tau_dot_h, const T* const* tau_sum_dot_h, const T* const* fscatt_dot_h,      \
+                                  const int* shift, const T* varpi_ie, const T* Zpp_ie, const T* Zmp_ie, const T* F0,          \
+                                  int halo, int nV, const int* row0_h, const T* w_h, T* ieRdot, T* ieTdot, void* stream) {     \
+    return ss_column_rrs_lin<T>(q, S, L, m, K, P, p_layer, p_lo, p_hi, tau_h, tau_sum_h, fscatt_h, tau_dot_h, tau_sum_dot_h,   \
+                                fscatt_dot_h, shift, varpi_ie, Zpp_ie, Zmp_ie, F0, halo, nV, row0_h, w_h, ieRdot, ieTdot,      \
+                                stream);                                                                                       \
   }
 VSM_SS_API(double, f64)
 VSM_SS_API(float, f32)
