@@ -334,6 +334,18 @@ def create_surface_layer_brdf(rho_m, added: O.AddedLayer, m, pol, qp, tau_sum, F
     added.t_mm[...] = np.eye(N, dtype=FT)[None]
 
 
+def surface_layer_hook(model: O.RTModel, refl, coxmunk: Optional[CoxMunkSurface] = None):
+    """The `surface` hook of the oracles that take one (m, added_surf, tau_sum): create_surface_layer_brdf of the Fourier blocks
+    refl(m) on the model's quadrature.  coxmunk: the CoxMunkSurface the blocks belong to, kept as the hook's attribute `coxmunk`
+    (vsm_oracle_raman.rt_run_rrs reads it for the single-scattering correction)."""
+    pol, qp, FT = model.pol, model.quad_points, model.FT
+
+    def fill(m, added_surf, tau_sum):
+        create_surface_layer_brdf(refl(m), added_surf, m, pol, qp, tau_sum, FT)
+    fill.coxmunk = coxmunk
+    return fill
+
+
 def create_surface_layer_brdf_lin(rho_m, drho_m, added: O.AddedLayer, al: OL.AddedLayerLin, iparam, m, pol, qp, tau_sum,
                                   tau_sum_dot, F0, FT):
     """coxmunk_surface_lin.jl:27-102 with (rho_m, drho_m) = reflectance_and_deriv(surf, pol, qp_mu, m)."""

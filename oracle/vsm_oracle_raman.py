@@ -402,11 +402,28 @@ def postprocessing_vza_rs(pol, comp, comp_rs, vza, vaz, qp, m, weight, R_SFI, T_
         ieT_SFI[i] += w[:, None] * sJp[:, istart:istart + n].T
 
 
-def rt_run_rrs(model: O.RTModel, rs: RRS, fscatt=None, trace=None, per_m=None):
-    """src/CoreRT/rt_run.jl:238-535 for RS_type::RRS (SFI, Lambertian surface).  `model.greek_rayleigh` is the
+def lambertian_surface_fn(model: O.RTModel):
+    """The default surface hook (m, added_surf, tau_sum): the model's Lambertian albedo, a scalar or a per-point spectrum [S]."""
+    FT, pol, qp = model.FT, model.pol, model.quad_points
+
+    def fill(m, added_surf, tau_sum):
+        if np.ndim(model.albedo) == 1:
+            O.create_surface_layer_lambertian_spectral(model.albedo, added_surf, m, pol, qp, tau_sum, FT)
+        else:
+            O.create_surface_layer_lambertian(model.albedo, added_surf, m, pol, qp, tau_sum, FT)
+    return fill
+
+
+def rt_run_rrs(model: O.RTModel, rs: RRS, fscatt=None, trace=None, per_m=None, surface=None):
+    """src/CoreRT/rt_run.jl:238-535 for RS_type::RRS (SFI).  `model.greek_rayleigh` is the
     elastic (Cabannes) phase matrix and model.varpi_cabannes the Rayleigh single-scattering albedo
     (compEffectiveLayerProperties.jl:36-41).  fscatt [S, L]: per-layer fScattRayleigh (:56); default tau_rayl /
-    (tau_rayl + sum of the delta-M scaled aerosol taus).  Returns (R_SFI, T_SFI, ieR_SFI, ieT_SFI)."""
+    (tau_rayl + sum of the delta-M scaled aerosol taus).  Returns (R_SFI, T_SFI, ieR_SFI, ieT_SFI).
+
+    surface: None = the model's Lambertian albedo; else a function (m, added_surf, tau_sum) that fills the surface AddedLayer of
+    moment m (rt_run.jl:423-455 calls create_surface_layer!(brdf, ...) for every RS_type), e.g.
+    vsm_oracle_coxmunk.surface_layer_hook.  A hook that carries a CoxMunkSurface as its attribute `coxmunk` also gets the elastic
+    single-scattering correction of R_SFI (rt_run.jl:520-524, which does not depend on RS_type)."""
     FT = model.FT
     pol, qp = model.pol, model.quad_points
     S, L = model.tau_rayl.shape
@@ -427,6 +444,8 @@ def rt_run_rrs(model: O.RTModel, rs: RRS, fscatt=None, trace=None, per_m=None):
     add_rs = make_added_layer_rs(FT, K, N, S)
     surf_rs = make_added_layer_rs(FT, K, N, S)   # stays zero: the surface has no inelastic part
     comp_rs = make_composite_layer_rs(FT, K, N, S)
+    fill_surface = lambertian_surface_fn(model) if surface is None else surface
+    tau_sum_all = None
     for m in range(model.m_max + 1):
         weight = FT(0.5 / math.pi) if m == 0 else FT(1.0 / math.pi)
         rs.Zpp_ie, rs.Zmp_ie = O.compute_Z_moments(pol, qp.qp_mu, rs.greek_raman, m)
@@ -437,12 +456,16 @@ def rt_run_rrs(model: O.RTModel, rs: RRS, fscatt=None, trace=None, per_m=None):
             lo = O.expand_optical_properties(lods[iz], FT)
             rt_kernel_rrs(rs, pol, added, add_rs, comp, comp_rs, lo, tau_sum_all[:, iz].astype(FT), m, qp, iz + 1, F0, FT,
                           model.numerics, trace, ifaces[iz])
-        O.create_surface_layer_lambertian(model.albedo, added_surf, m, pol, qp, tau_sum_all[:, -1], FT)
+        fill_surface(m, added_surf, tau_sum_all[:, -1])
         interaction_inelastic(ifaces[-1], rs, comp, comp_rs, added_surf, surf_rs, FT)
         if per_m is not None:
             per_m.append(dict(m=m, J0_m=comp.J0_m.copy(), J0_p=comp.J0_p.copy(), ieJ0_m=comp_rs.ieJ0_m.copy(),
                               ieJ0_p=comp_rs.ieJ0_p.copy(), weight=weight))
         postprocessing_vza_rs(pol, comp, comp_rs, model.vza, model.vaz, qp, m, weight, R_SFI, T_SFI, ieR_SFI, ieT_SFI)
+    coxmunk = getattr(surface, "coxmunk", None)
+    if coxmunk is not None and tau_sum_all is not None:
+        from . import vsm_oracle_coxmunk as CM
+        CM.apply_ss_correction(R_SFI, coxmunk, pol, model.vza, model.vaz, FT(qp.mu0), tau_sum_all[:, -1], model.m_max)
     return R_SFI, T_SFI, ieR_SFI, ieT_SFI
 
 

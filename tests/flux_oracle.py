@@ -33,13 +33,15 @@ def tau_sum_levels(model):
     return np.asarray(tau_sum_all, dtype=np.float64)
 
 
-def level_vectors(model, levels, B_layer=None, solar=True, sif=None, segmented=False):
+def level_vectors(model, levels, B_layer=None, solar=True, sif=None, segmented=False, surface=None):
     """{level: (uw, dw)} [S, N] float64, m = 0, summed over the sources: the solar slot (solar=False: the same slot at F0 = 0,
     ms_thermal_oracle.ms_total_reference's rule), SurfaceSIF in its surface layer (sif: the table, [S] or [n, S]), the thermal slot
-    (B_layer [Nz, S])."""
+    (B_layer [Nz, S]).  surface: the hook (m, added_surf, tau_sum) of ms_oracle for the solar slot (None = the model's Lambertian
+    albedo); not together with sif or B_layer, whose slots build their own Lambertian surface."""
+    if surface is not None and (sif is not None or B_layer is not None):
+        raise ValueError("level_vectors: a surface hook goes with the solar slot alone (no sif, no B_layer)")
     m0 = dataclasses.replace(model, m_max=0)
     ms = m0 if solar else dataclasses.replace(m0, F0=np.zeros((model.pol.n, model.tau_rayl.shape[0]), dtype=model.FT))
-    surface = None
     if sif is not None:
         tab = SIF.sif_table(model.pol.n, model.tau_rayl.shape[0], sif)
 
@@ -95,8 +97,8 @@ def fluxes_from_vectors(model, levels, vec, solar=True, level0_dw=False):
     return res
 
 
-def fluxes_reference(model, levels, B_layer=None, solar=True, sif=None):
-    return fluxes_from_vectors(model, levels, level_vectors(model, levels, B_layer, solar, sif), solar)
+def fluxes_reference(model, levels, B_layer=None, solar=True, sif=None, surface=None):
+    return fluxes_from_vectors(model, levels, level_vectors(model, levels, B_layer, solar, sif, surface=surface), solar)
 
 
 def fluxes_segmented(model, levels, B_layer=None, solar=True, sif=None):

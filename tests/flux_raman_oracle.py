@@ -23,12 +23,13 @@ IE_FIELDS = ("up_ie", "down_diffuse_ie", "actinic_up_ie", "actinic_down_diffuse_
 FIELDS = FO.FIELDS + IE_FIELDS
 
 
-def level_vectors(model, rs, levels, fscatt=None, segmented=False):
-    """{level: (uw, dw, uwie, dwie)} [S, N] float64 of m = 0, the inelastic ones summed over the lines."""
+def level_vectors(model, rs, levels, fscatt=None, segmented=False, surface=None):
+    """{level: (uw, dw, uwie, dwie)} [S, N] float64 of m = 0, the inelastic ones summed over the lines.  surface: the hook of
+    ms_raman_oracle (None = the model's Lambertian albedo)."""
     m0 = dataclasses.replace(model, m_max=0)
     distinct = sorted(set(int(l) for l in levels))
     full = {}
-    (MRO.ms_raman_segmented if segmented else MRO.ms_raman_reference)(m0, rs, distinct, fscatt=fscatt, full=full)
+    (MRO.ms_raman_segmented if segmented else MRO.ms_raman_reference)(m0, rs, distinct, fscatt=fscatt, full=full, surface=surface)
     return {l: tuple(np.asarray(v, dtype=np.float64) for v in full[(l, 0)]) for l in distinct}
 
 
@@ -60,9 +61,9 @@ def fluxes_from_vectors(model, levels, vec):
     return res
 
 
-def fluxes_raman_reference(model, rs, levels, fscatt=None):
-    return fluxes_from_vectors(model, levels, level_vectors(model, rs, levels, fscatt))
+def fluxes_raman_reference(model, rs, levels, fscatt=None, surface=None):
+    return fluxes_from_vectors(model, levels, level_vectors(model, rs, levels, fscatt, surface=surface))
 
 
-def fluxes_raman_segmented(model, rs, levels, fscatt=None):
-    return fluxes_from_vectors(model, levels, level_vectors(model, rs, levels, fscatt, segmented=True))
+def fluxes_raman_segmented(model, rs, levels, fscatt=None, surface=None):
+    return fluxes_from_vectors(model, levels, level_vectors(model, rs, levels, fscatt, segmented=True, surface=surface))

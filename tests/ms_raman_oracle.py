@@ -16,7 +16,8 @@ ms_raman_segmented(model, rs, levels)  the device algorithm in numpy: one top pa
 
 Both return (uw, dw, uwie, dwie): lists with one [nVZA, nStokes, nSpec] array per entry of `levels`, uwie / dwie summed over the
 Raman lines like postprocessing_vza_ms!(::RRS).  Level conventions as in tests/ms_oracle.py (level Nz: the surface layer alone
-below, whose inelastic part is zero).
+below, whose inelastic part is zero).  `surface`: as in tests/ms_oracle.py -- None = the model's Lambertian albedo, else a function
+(m, added_surf, tau_sum) that fills the surface AddedLayer of moment m.
 
 interaction_helper_ms!(::RRS, ::_11) vs interaction_helper!(::RRS, ::_11) (interaction_inelastic.jl:319-521), statement by
 statement: the same right-hand sides; the prototype updates the composite in place (every right-hand side still reads pre-update
@@ -205,16 +206,19 @@ def _setup_rs(model, rs, fscatt):
     return FT, pol, qp, S, L, N, K, _f0(model), (OR.default_fscatt(model) if fscatt is None else fscatt)
 
 
-def _surface(model, m, added_surf, tau_sum):
-    O.create_surface_layer_lambertian(model.albedo, added_surf, m, model.pol, model.quad_points, tau_sum, model.FT)
+def _surface(model, surface=None):
+    """The surface hook (m, added_surf, tau_sum): None = the model's Lambertian albedo (scalar or a per-point spectrum), else
+    `surface` itself (e.g. vsm_oracle_coxmunk.surface_layer_hook of a BRDF's Fourier blocks), as in tests/ms_oracle.py."""
+    return MS._surface_fn(model, surface)
 
 
-def ms_raman_reference(model, rs: OR.RRS, levels, fscatt=None, full=None):
+def ms_raman_reference(model, rs: OR.RRS, levels, fscatt=None, full=None, surface=None):
     """rt_run_test_ms(::RRS, sensor_levels, model, iBand): (uwJ, dwJ, uwieJ, dwieJ) in the order of `levels`, the ie outputs summed
     over the lines.  full: a dict that receives {(level, m): (uw, dw, uwie, dwie)} ([S,N]; ie summed over the lines)."""
     levels, Nz = _check(model, levels)
     FT, pol, qp, S, L, N, K, F0, fscatt = _setup_rs(model, rs, fscatt)
     nV = len(model.vza)
+    fill_surface = _surface(model, surface)
     outs = [[np.zeros((nV, pol.n, S), dtype=FT) for _ in levels] for _ in range(4)]
     added, add_rs = O.make_added_layer(FT, N, S), OR.make_added_layer_rs(FT, K, N, S)
     added_surf, surf_rs = O.make_added_layer(FT, N, S), OR.make_added_layer_rs(FT, K, N, S)
@@ -238,7 +242,7 @@ def ms_raman_reference(model, rs: OR.RRS, levels, fscatt=None, full=None):
                     _ms_interaction(ifaces[iz - 1], rs, *bot[ims], added, add_rs, FT)    # interaction_bot!
                 else:
                     _ms_interaction(ifaces[iz - 1], rs, *top[ims], added, add_rs, FT)    # interaction_top!
-        _surface(model, m, added_surf, tau_sum_all[:, -1])
+        fill_surface(m, added_surf, tau_sum_all[:, -1])
         for ims, lev in enumerate(levels):
             if lev == Nz:
                 bot[ims] = _copy_pair(added_surf, surf_rs)                                # the level-Nz deviation
@@ -260,12 +264,13 @@ def ms_raman_reference(model, rs: OR.RRS, levels, fscatt=None, full=None):
     return tuple(outs)
 
 
-def ms_raman_segmented(model, rs: OR.RRS, levels, fscatt=None, full=None, counts=None):
+def ms_raman_segmented(model, rs: OR.RRS, levels, fscatt=None, full=None, counts=None, surface=None):
     """The device algorithm (core_rt_ms_raman.py) in numpy: same outputs as ms_raman_reference up to rounding; level 0 is
     OR.rt_run_rrs's (R, T, ieR, ieT) exactly.  counts: a dict that receives the number of layer steps and interactions."""
     levels, Nz = _check(model, levels)
     FT, pol, qp, S, L, N, K, F0, fscatt = _setup_rs(model, rs, fscatt)
     nV = len(model.vza)
+    fill_surface = _surface(model, surface)
     distinct = sorted(set(levels))
     interior = [l for l in distinct if 0 < l < Nz]
     out = {l: [np.zeros((nV, pol.n, S), dtype=FT) for _ in range(4)] for l in distinct}
@@ -289,7 +294,7 @@ def ms_raman_segmented(model, rs: OR.RRS, levels, fscatt=None, full=None, counts
                 counts["layers"] += 1
             if iz + 1 in interior or iz + 1 == Nz:
                 tops[iz + 1] = (comp.R_pm.copy(), comp.J0_p.copy(), comp_rs.ieR_pm.copy(), comp_rs.ieJ0_p.copy())
-        _surface(model, m, added_surf, tau_sum_all[:, -1])
+        fill_surface(m, added_surf, tau_sum_all[:, -1])
         res = {}
 
         def level(l, bc, br):

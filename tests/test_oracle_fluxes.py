@@ -134,3 +134,40 @@ def test_rt_run_fluxes_argument_validation():
     for srcs, th in (((OtherSource(),), False), ((H.SolarBeam(), OtherSource()), True), ((), True)):
         with pytest.raises(vsm.VSMError):
             vsm.CoreRT.rt_run_fluxes(_host_model(vsm, sources=srcs), None, thermal=th)
+
+
+# ---- the surface hook (tests/driver_surface_cases.py: the scenes of tests/test_gpu_driver_surfaces.py) ------------------------------
+import driver_surface_cases as DS  # noqa: E402
+
+
+@pytest.fixture(scope="module", params=DS.SHAPES, ids=lambda p: "%s_%d" % p)
+def grid_scene(request):
+    pol, l_trunc = request.param
+    om = DS.oracle_model(pol, l_trunc)
+    return om, FO.fluxes_reference(om, DS.LEVELS)
+
+
+def test_default_hook_is_the_lambertian_builder(grid_scene):
+    om, base = grid_scene
+    got = FO.fluxes_reference(om, DS.LEVELS, surface=DS.lambertian_hook(om))
+    for k in FO.FIELDS:
+        assert np.array_equal(getattr(got, k), getattr(base, k)), k
+    with pytest.raises(ValueError):
+        FO.level_vectors(om, DS.LEVELS, sif=np.ones(DS.S), surface=DS.lambertian_hook(om))
+
+
+@pytest.mark.parametrize("aerosol", [False, True], ids=["rayleigh", "aerosol"])
+def test_degenerate_surfaces_and_black_surface(aerosol):
+    """A constant BRDF and a constant albedo spectrum are the Lambertian surface (1e-13 of each field's largest value); over a black
+    surface `up` at the surface level differs by at least 0.1 (against a vacuous pass on the device; the aerosol scene is that of
+    the linearized cells)."""
+    for pol, l_trunc in DS.SHAPES:
+        om = DS.oracle_model(pol, l_trunc, aerosol=aerosol)
+        base = FO.fluxes_reference(om, DS.LEVELS)
+        for name, model, hook, _ in DS.degenerate_cases(om):
+            got = FO.fluxes_reference(model, DS.LEVELS, surface=hook)
+            for k in FO.FIELDS:
+                assert DS.rel_max(getattr(got, k), getattr(base, k)) <= 1e-13, (pol, name, k)
+        blk = FO.fluxes_reference(DS.black(om), DS.LEVELS)
+        i = DS.LEVELS.index(DS.L)
+        assert DS.rel_max(blk.up[i], base.up[i]) >= 0.1, pol

@@ -126,3 +126,41 @@ def test_rt_run_fluxes_refusals():
         vsm.CoreRTRaman.rt_run_fluxes(rs, big, [1])
     with pytest.raises(vsm.VSMError, match="iBand"):
         vsm.CoreRTRaman.rt_run_fluxes(rs, model, [1], iBand=2)
+
+
+# ---- the surface hook (tests/driver_surface_cases.py: the scenes of tests/test_gpu_driver_surfaces.py) ------------------------------
+import driver_surface_cases as DS  # noqa: E402
+
+
+@pytest.fixture(scope="module", params=DS.SHAPES, ids=lambda p: "%s_%d" % p)
+def grid_scene(request):
+    pol, l_trunc = request.param
+    om = DS.oracle_model(pol, l_trunc)
+    return om, FRO.fluxes_raman_reference(om, DS.oracle_rs(), DS.LEVELS)
+
+
+def test_default_hook_is_the_lambertian_builder(grid_scene):
+    om, base = grid_scene
+    got = FRO.fluxes_raman_reference(om, DS.oracle_rs(), DS.LEVELS, surface=DS.lambertian_hook(om))
+    seg = FRO.fluxes_raman_segmented(om, DS.oracle_rs(), DS.LEVELS)
+    seg_h = FRO.fluxes_raman_segmented(om, DS.oracle_rs(), DS.LEVELS, surface=DS.lambertian_hook(om))
+    for k in FRO.FIELDS:
+        assert np.array_equal(getattr(got, k), getattr(base, k)) and np.array_equal(getattr(seg_h, k), getattr(seg, k)), k
+
+
+def test_degenerate_surfaces(grid_scene):
+    """A constant BRDF and a constant albedo spectrum are the Lambertian surface: every field within 1e-13 of its largest value."""
+    om, base = grid_scene
+    for name, model, hook, _ in DS.degenerate_cases(om):
+        got = FRO.fluxes_raman_reference(model, DS.oracle_rs(), DS.LEVELS, surface=hook)
+        for k in FRO.FIELDS:
+            assert DS.rel_max(getattr(got, k), getattr(base, k)) <= 1e-13, (name, k, DS.rel_max(getattr(got, k), getattr(base, k)))
+
+
+def test_black_surface_is_far_from_the_lambertian_one(grid_scene):
+    """Against a vacuous pass on the device: `up` and `up_ie` at the surface level differ by at least 0.1 of their largest value."""
+    om, base = grid_scene
+    blk = FRO.fluxes_raman_reference(DS.black(om), DS.oracle_rs(), DS.LEVELS)
+    i = DS.LEVELS.index(DS.L)
+    for k in ("up", "up_ie"):
+        assert DS.rel_max(getattr(blk, k)[i], getattr(base, k)[i]) >= 0.1, k

@@ -147,3 +147,45 @@ def test_segmented_equals_reference_nonscattering_layers(pattern):
         for i, l in enumerate(levels):
             e = _rel_per_component(s_list[i], r_list[i])
             assert e <= 1e-12, (pattern, name, l, e)
+
+
+# ---- the surface hook (tests/driver_surface_cases.py: the scenes of tests/test_gpu_driver_surfaces.py) ------------------------------
+import driver_surface_cases as DS  # noqa: E402
+
+
+@pytest.fixture(scope="module", params=DS.SHAPES, ids=lambda p: "%s_%d" % p)
+def grid_scene(request):
+    pol, l_trunc = request.param
+    om = DS.oracle_model(pol, l_trunc)
+    return om, MR.ms_raman_reference(om, DS.oracle_rs(), DS.LEVELS)
+
+
+def test_default_hook_is_the_lambertian_builder(grid_scene):
+    """surface=None builds what both walks had hard-wired: the same bits as the scalar Lambertian builder handed in as a hook."""
+    om, base = grid_scene
+    for fn, ref in ((MR.ms_raman_reference, base), (MR.ms_raman_segmented, MR.ms_raman_segmented(om, DS.oracle_rs(), DS.LEVELS))):
+        got = fn(om, DS.oracle_rs(), DS.LEVELS, surface=DS.lambertian_hook(om))
+        for g_list, r_list in zip(got, ref):
+            assert all(np.array_equal(g, r) for g, r in zip(g_list, r_list))
+
+
+def test_degenerate_surfaces(grid_scene):
+    """A constant BRDF and a constant albedo spectrum are the Lambertian surface, at every level: 1e-13 of the largest value (over
+    the albedo spectrum all but dw / dwie of level 0, which are rt_run's T / ieT: DS.degenerate_cases)."""
+    om, base = grid_scene
+    for name, model, hook, spectral in DS.degenerate_cases(om):
+        got = MR.ms_raman_reference(model, DS.oracle_rs(), DS.LEVELS, surface=hook)
+        for what, g_list, r_list in zip(("uw", "dw", "uwie", "dwie"), got, base):
+            for l, g, r in zip(DS.LEVELS, g_list, r_list):
+                if spectral and l == 0 and what in ("dw", "dwie"):
+                    continue
+                assert DS.rel_max(g, r) <= 1e-13, (name, what, l, DS.rel_max(g, r))
+
+
+def test_black_surface_is_far_from_the_lambertian_one(grid_scene):
+    """Against a vacuous pass on the device: uw and uwie of every level differ by at least 0.1 of their largest value."""
+    om, base = grid_scene
+    blk = MR.ms_raman_reference(DS.black(om), DS.oracle_rs(), DS.LEVELS)
+    for k, what in ((0, "uw"), (2, "uwie")):
+        for l, b, r in zip(DS.LEVELS, blk[k], base[k]):
+            assert DS.rel_max(b, r) >= 0.1, (what, l, DS.rel_max(b, r))

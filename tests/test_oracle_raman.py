@@ -138,3 +138,82 @@ def test_phase1b_rrs_golden_pins_the_oracle(golden_dir):
     rs = OR.RRS(i_shift=bs.i_shift, varpi_ie=bs.varpi_ie, greek_raman=O.greek_from_dict(bs.greek_raman))
     got = OR.rt_run_rrs(model, rs)
     check_phase1b(fx, got, tight=dict(R_rrs=1e-3, ieR=3e-3))
+
+
+# ---- the surface hook of rt_run_rrs (tests/driver_surface_cases.py: the scenes of tests/test_gpu_driver_surfaces.py) ----------------
+import driver_surface_cases as DS  # noqa: E402
+from oracle import vsm_oracle_brdf as OB  # noqa: E402
+
+
+@pytest.fixture(scope="module", params=DS.SHAPES, ids=lambda p: "%s_%d" % p)
+def grid_scene(request):
+    pol, l_trunc = request.param
+    om = DS.oracle_model(pol, l_trunc)
+    return om, OR.rt_run_rrs(om, DS.oracle_rs())
+
+
+def test_rt_run_rrs_default_hook_is_the_lambertian_builder(grid_scene):
+    """surface=None builds what the driver had hard-wired: the same bits as the scalar Lambertian builder handed in as a hook."""
+    om, base = grid_scene
+    for a, b in zip(OR.rt_run_rrs(om, DS.oracle_rs(), surface=DS.lambertian_hook(om)), base):
+        assert np.array_equal(a, b)
+
+
+def test_rt_run_rrs_degenerate_surfaces(grid_scene):
+    """A constant BRDF (RPV(a, 1, 1, 0), Ross-Li(0, 0, a)) and a constant albedo spectrum are the Lambertian surface: 1e-13 of the
+    largest value of R, T, ieR, ieT (measured: 7e-15); over the albedo spectrum R and ieR (DS.degenerate_cases: T, ieT differ)."""
+    om, base = grid_scene
+    for name, model, hook, spectral in DS.degenerate_cases(om):
+        got = OR.rt_run_rrs(model, DS.oracle_rs(), surface=hook)
+        for what, g, b in zip(("R", "T", "ieR", "ieT"), got, base):
+            if spectral and what in ("T", "ieT"):
+                assert DS.rel_max(g, b) > 1e-3, (name, what)      # (the builders do differ there)
+                continue
+            e = DS.rel_max(g, b)
+            print("rt_run_rrs %s %s %s: %.2e" % (om.pol.n, name, what, e))
+            assert e <= 1e-13, (name, what, e)
+
+
+def test_rt_run_rrs_rpv_hook_without_lines_is_the_elastic_brdf_run():
+    """No Raman line: R, T are OB.rt_run's over the same RPV surface, and the inelastic field is exactly zero."""
+    pol, l_trunc = DS.SHAPES[0]
+    om = DS.oracle_model(pol, l_trunc, albedo=DS.ALBEDO_FIELD)
+    surf = OB.RPVSurface(*DS.RPV)
+    rs = OR.RRS(i_shift=DS.SHIFTS[:0], varpi_ie=DS.W_IE[:0], greek_raman=DS.oracle_rs().greek_raman)
+    R, T, ieR, ieT = OR.rt_run_rrs(om, rs, surface=DS.brdf_hook(om, surf))
+    Ro, To = OB.rt_run(om, surf)
+    assert DS.rel_max(R, Ro) <= 1e-13 and DS.rel_max(T, To) <= 1e-13
+    assert np.all(ieR == 0) and np.all(ieT == 0)
+
+
+def test_rt_run_rrs_coxmunk_hook_applies_the_single_scattering_correction():
+    """rt_run.jl:520-524 does not depend on RS_type: R of a run without lines is CM.rt_run's, correction included."""
+    from oracle import vsm_oracle_coxmunk as CM
+    pol, l_trunc = DS.SHAPES[1]
+    om = DS.oracle_model(pol, l_trunc)
+    surf = CM.CoxMunkSurface(DS.WIND)
+    rs = OR.RRS(i_shift=DS.SHIFTS[:0], varpi_ie=DS.W_IE[:0], greek_raman=DS.oracle_rs().greek_raman)
+    R, T, _, _ = OR.rt_run_rrs(om, rs, surface=DS.brdf_hook(om, surf))
+    Ro, To = CM.rt_run(om, surf)
+    Rn, _ = CM.rt_run(om, surf, ss_correction=False)
+    assert DS.rel_max(R, Ro) <= 1e-13 and DS.rel_max(T, To) <= 1e-13
+    assert DS.rel_max(Rn, Ro) > 1e-6      # (the correction is there to be seen)
+
+
+@pytest.mark.parametrize("aerosol", [False, True], ids=["rayleigh", "aerosol"])
+def test_black_surface_is_far_from_the_lambertian_one(aerosol):
+    """Against a vacuous pass of the degenerate identities on the device: over a black surface every compared output of the elastic
+    and of the Raman run differs from Lambertian(a) by at least 0.1 of its largest value (the aerosol scene: the linearized cells,
+    elastic)."""
+    for pol, l_trunc in DS.SHAPES:
+        om = DS.oracle_model(pol, l_trunc, aerosol=aerosol)
+        R, _ = O.rt_run(om)
+        Rb, _ = O.rt_run(DS.black(om))
+        assert DS.rel_max(Rb, R) >= 0.1, (pol, DS.rel_max(Rb, R))
+        if aerosol:
+            continue
+        got, blk = OR.rt_run_rrs(om, DS.oracle_rs()), OR.rt_run_rrs(DS.black(om), DS.oracle_rs())
+        for what, k in (("R", 0), ("ieR", 2)):
+            e = DS.rel_max(blk[k], got[k])
+            print("black vs Lambertian(%.2f) %s %s: %.2f" % (DS.A, pol, what, e))
+            assert e >= 0.1, (pol, what, e)

@@ -133,6 +133,8 @@ def rt_run_fluxes(RS_type: RR.RRS, model: H.RTModel, levels=None, iBand: int = 1
 
     Only m = 0 is walked, whatever model.m_max is, on the scene SceneRRS itself uses for that moment: the Stokes_IQ sub-scene
     where it reduces m = 0.  Only the I row is reported: no Q / U / V fluxes.  No Jacobian, no sharding through vsm.parallel.
+    Surfaces: model.surface, as CoreRTRaman.rt_run_multisensor takes it (no Cox-Munk single-scattering correction, like
+    CoreRT.rt_run_fluxes).
 
     Sources and refusals are those of CoreRTRaman.rt_run_multisensor, before anything is launched: SolarBeam only (SurfaceSIF,
     SurfaceEmission: NotImplementedError; ThermalEmission: VSMError), iBand = 1, N <= 128 (VSMError).  Columns with non-scattering

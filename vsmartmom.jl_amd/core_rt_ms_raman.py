@@ -159,7 +159,7 @@ def _run_scene(sc: RR.SceneRRS, plan: MS.LevelPlan, streams: bool, sink: Optiona
             _layer(sc, mom, iz, comp, comp_rs, iz + 1)
             if iz + 1 in plan.tops_at:
                 tops[iz + 1] = (comp.R_pm.clone(), comp.J0_p.clone(), comp_rs.ieR_pm.clone(), comp_rs.ieJ0_p.clone())
-        CR.create_surface_layer_(model.albedo, asurf, m, fwd.dq, mom["tau_sum_surface"])
+        CR.create_surface_layer_(model.surface, asurf, m, fwd.dq, mom["tau_sum_surface"], rho=mom["rho"])
         tags = [ly["iface"] for ly in mom["layers"]]
 
         def layers(seg, first, lo, hi):      # layers lo+1 .. hi into seg, a composite that starts with layer first+1
@@ -231,6 +231,9 @@ def rt_run_multisensor(RS_type: RR.RRS, model: H.RTModel, sensor_levels, iBand: 
     bottom, whose inelastic part is zero: DESIGN.md §6); duplicates and any order allowed, each distinct level computed once.  Level
     0 is CoreRTRaman.rt_run(RS_type, model)'s (R_SFI, T_SFI, ieR_SFI, ieT_SFI) bit for bit.  Columns with non-scattering layers
     run (both reference RRS drivers hard-wire scatter = true) with rt_run(RRS)'s convention for the _00 / _01 / _10 tags.
+
+    Surfaces: model.surface, every type CoreRTRaman.rt_run takes (scalar and spectral Lambertian, RPV, Ross-Li, Cox-Munk); like
+    CoreRT.rt_run_multisensor, no Cox-Munk single-scattering correction -- over a CoxMunkSurface level 0 is rt_run's field before it.
 
     streams=True: a MultiSensorRamanResult, which also carries the level vectors at all quadrature streams per moment.
     max_points: walk the recipient axis in blocks of at most that many points, each extended by the halo of max|shift| donor

@@ -88,6 +88,9 @@ def device_rrs(rs: RRS, arch, FT) -> DeviceRRS:
 
 
 REDUCE_M0 = True   # A/B switch (module attribute): False = the moment m = 0 with all Stokes components of the model
+# the surfaces whose reflectance has an I -> I element alone (what the Stokes_IQ reduction of m = 0 rests on, SceneRRS)
+SCALAR_SURFACES = (H.LambertianSurfaceScalar, H.LambertianSurfaceLegendre, H.LambertianSurfaceSpline, H.rpvSurfaceScalar,
+                   H.RossLiSurfaceScalar)
 
 _work = {}
 
@@ -198,8 +201,9 @@ class SceneRRS:
         else:
             ext, crop = parallel.raman_halo_slices(S_full, spec_slice, RS_type.i_lambda1lambda0)
         self.ext, self.crop = ext, crop
-        # the surface of the Raman driver is the Lambertian albedo (rt_run.jl:455-463 with the model's brdf; only the scalar
-        # Lambertian builder is wired here, like before)
+        # the surface of the Raman driver is the model's (rt_run.jl:264 brdf = get_surface(model, iBand); :423-455
+        # create_surface_layer!(brdf, ...) for every RS_type): CoreRT.Scene holds its surface layer (one block per point for a
+        # spectral albedo, over the EXTENDED range), the albedo spectrum and the BRDF's Fourier blocks mom["rho"]
         self.fwd = CR.Scene(model, ext, full_added_layer=True)
         self.fwd.compute_hdrf = False
         fwd = self.fwd
@@ -234,17 +238,19 @@ class SceneRRS:
             self.comp_rs = CompositeLayerRS(FT, arch, K, N, S)
         # The Fourier moment m = 0 as a Stokes_IQ run.  No phase matrix -- Cabannes, Raman, aerosol -- couples (I,Q) with (U,V) at
         # m = 0 (compute_Z_matrices.jl:26-110: the T_l^m functions carry a factor m; CoreRT.Scene reads the exact zeros off the
-        # device, `coupling`), the Lambertian surface reflects into I only, and a beam without U / V components drives nothing in the
-        # (U,V) block: its source vectors stay zero through every recurrence, elastic and inelastic, so R / T / ieR / ieT of
+        # device, `coupling`), a surface of SCALAR_SURFACES reflects I into I only, and a beam without U / V components drives nothing
+        # in the (U,V) block: its source vectors stay zero through every recurrence, elastic and inelastic, so R / T / ieR / ieT of
         # m = 0 are those of the same model carried with two Stokes components (the reference's own Stokes_IQ), U = V = 0 -- at
-        # (2/3)^3 of the products and (2/3)^2 of the bytes for Stokes_IQU.
+        # (2/3)^3 of the products and (2/3)^2 of the bytes for Stokes_IQU.  A polarizing surface (CoxMunkSurface) is not in that
+        # list: nothing here reads the coupling of its reflectance blocks, so its m = 0 runs with every component of the model.
         self.sub0 = None
         F0 = model.F0
         # (SurfaceSIF: an emission with a U or V row drives the (U,V) block of m = 0 -- no reduction then; else the sub-scene carries
         #  the I, Q rows of the table)
         sif = [s_ for s_ in (model.sources or ()) if isinstance(s_, H.SurfaceSIF)]
-        if (_reduce_m0 and REDUCE_M0 and pol.n >= 3 and S > 0 and (F0 is None or not np.any(np.asarray(F0)[2:] != 0))
-                and not any(s_.has_uv() for s_ in sif) and fwd.coupling is not None and zie_mask0 is not None
+        self.is_sub = not _reduce_m0      # the Stokes_IQ scene of another scene's m = 0
+        if (_reduce_m0 and REDUCE_M0 and pol.n >= 3 and S > 0 and isinstance(model.surface, SCALAR_SURFACES)
+                and (F0 is None or not np.any(np.asarray(F0)[2:] != 0)) and not any(s_.has_uv() for s_ in sif) and fwd.coupling is not None and zie_mask0 is not None
                 and not any((fwd.coupling[0] | zie_mask0) >> (4 * a + b) & 1 or (fwd.coupling[0] | zie_mask0) >> (4 * b + a) & 1
                             for a in (0, 1) for b in range(2, pol.n))):
             qi = H.QuadPoints(qp.mu0, qp.imu0, qp.qp_mu, qp.wt_mu, np.repeat(qp.qp_mu, 2), np.repeat(qp.wt_mu, 2), qp.Nquad, qp.Nstreams)
@@ -284,11 +290,14 @@ class SceneRRS:
                 rt_kernel_rrs_(drs, pol, added, self.added_rs, comp, self.comp_rs, ly["props"].materialize(), ly["tau_sum"], m, fwd.dq,
                                self.arch, iz + 1, fwd.F0, FT, model.numerics, dtau=ly["dtau"], ndoubl=ly["nd"], expk=self.expk,
                                trace=trace, iface=ly["iface"])
-            CR.create_surface_layer_(model.albedo, fwd.added_surface, m, fwd.dq, mom["tau_sum_surface"])
+            CR.create_surface_layer_(model.surface, fwd.added_surface, m, fwd.dq, mom["tau_sum_surface"], rho=mom["rho"])
             # SurfaceSIF (rt_run.jl:711-712): the elastic j0- carries the emission, the inelastic interaction below scatters it
-            CR.surface_source_contribute_(fwd, model.albedo, fwd.added_surface, m)
+            CR.surface_source_contribute_(fwd, model.surface, fwd.added_surface, m)
             interaction_inelastic_(drs, mom["iface_surface"], comp, self.comp_rs, fwd.added_surface, self.surf_rs)
             postprocessing_vza_rs_(pol, comp, self.comp_rs, model.vza, model.vaz, qp, m, float(weight), R_SFI, T_SFI, ieR_SFI, ieT_SFI)
+        if isinstance(model.surface, H.CoxMunkSurface) and not self.is_sub:   # rt_run.jl:520-524: the elastic R_SFI, whatever RS_type
+            CR.apply_ss_correction_(R_SFI, model.surface, pol, model.vza, model.vaz, qp.mu0, fwd.moments[-1]["tau_sum_surface"],
+                                    model.m_max, self.arch, FT)
         return tuple(self.out)
 
     def results_device(self):
@@ -316,6 +325,11 @@ def rt_run(RS_type: RRS, model: H.RTModel, iBand: int = 1, trace: Optional[list]
     [nVZA, nStokes, nSpec].  `model.greek_rayleigh` must hold the Cabannes phase matrix and `model.varpi_Cabannes`
     the elastic Rayleigh single-scattering albedo (compEffectiveLayerProperties.jl:36-41).  `spec_slice`: see SceneRRS;
     `device_out=True` returns the four (S_local, nStokes, nVZA) device tensors instead (for the gather).
+
+    Surfaces: every surface CoreRT.rt_run takes (model.surface: LambertianSurfaceScalar / Legendre / Spline, rpvSurfaceScalar,
+    RossLiSurfaceScalar, CoxMunkSurface), built by the same create_surface_layer_ call; the surface has no inelastic part.  Over a
+    CoxMunkSurface the elastic R_SFI gets CoreRT.rt_run's single-scattering correction (rt_run.jl:520-524) and m = 0 runs with every
+    Stokes component of the model (no Stokes_IQ reduction).  `model.albedo` is not read.
 
     Sources: SolarBeam and SurfaceSIF (the flagship O2-A configuration of the reference, prototype_O2ABand_RRS_SIF.jl); the
     emission enters the elastic surface layer at m = 0 and is Raman-scattered on its way up like every elastic field.  The walk
