@@ -36,7 +36,10 @@ namespace {
 // ---------------------------------------------------------------------------------------------------------------------------
 // On return (all waves past a barrier): r_s = strip of the final r-+ (row signs of apply_D applied), t_s = strip of t++ (rider
 // columns cleared), sm.vec[0] = j0+, sm.vec[1] = j0- (final sign), sm.usg filled.
-template <int RT, int KS, int KZ = KS>
+// TILE: the identity of the series by nadd_identity_tile (vsm_native_dev.h) -- the sources-only kernels.  In the full-run kernels
+// the register allocator answers that form unevenly (<3, 10, false, 1>: 24 -> 65 spilled registers, a strip's scratch traffic
+// inside the loop), so they keep nadd_identity.
+template <int RT, int KS, int KZ = KS, bool TILE = false>
 __device__ __forceinline__ void ned_body(nsmem<RT, (4 * KS + 2 > 16 * RT)>& sm, npos<RT>& p, int n, int gsz, unsigned uvmask, int ndoubl,
                                          const double* __restrict__ img, nstrip<RT>& r_s, nstrip<RT>& t_s, int* status) {
   using G = ngeo<RT>;
@@ -83,6 +86,7 @@ __device__ __forceinline__ void ned_body(nsmem<RT, (4 * KS + 2 > 16 * RT)>& sm, 
       nmv_rows<RT, KS, KZ>(dP, jp, 1.0, sm.mv[0], p);
       nmv_rows<RT, KS, KZ>(dP, jm, expk, sm.mv[1], p);
     }
+    int K;   // the series order: from the norm every wave reads out of LDS, the same in every wave of the workgroup
     {
       nstrip<RT> Gs;
       {
@@ -104,14 +108,18 @@ __device__ __forceinline__ void ned_body(nsmem<RT, (4 * KS + 2 > 16 * RT)>& sm, 
             sm.vec[5][tid] = jp[tid] + sm.mv[1][tid];
           }
         }
-        ninvert<RT, KS, false, KZ>(ninv_order(nrm, status), E, Gs, n, cx, p);
+        K = ninv_order(nrm, status);
+        ninvert<RT, KS, false, KZ, TILE>(K, E, Gs, n, cx, p);
       }
       nmm<RT, KS, true, KZ>(tt, dQ, Gs, p);    // tt = t G
     }
     nload(t_s, dQ, p);                     // t's strip (with its riders) is not kept in registers across the inverse
-    __syncthreads();                       // P ([E]) and Q ([t]) no longer read
+    // P: at order 1 the inverse is the identity added in registers -- P was last read by the product [E | W], which every wave
+    // finished before the norm's barrier, and nothing was written to it since: no barrier.  Every other order used P ([E], the
+    // out-of-line inverses' scratch) after that barrier.  (Q ([t]) is not written before the barrier below.)
+    if (K != 1) __syncthreads();
     nstore(dP, tt, p);
-    __syncthreads();
+    __syncthreads();                       // [tt] complete; Q ([t]) no longer read by anybody in this step
     if constexpr (!RID) {   // tt u1 , tt u2   (the partial sums of r j were consumed two barriers ago)
       nmv_rows<RT, KS, KZ>(dP, sm.vec[4], 1.0, sm.mv[0], p);
       nmv_rows<RT, KS, KZ>(dP, sm.vec[5], 1.0, sm.mv[1], p);
@@ -123,16 +131,25 @@ __device__ __forceinline__ void ned_body(nsmem<RT, (4 * KS + 2 > 16 * RT)>& sm, 
     }
     const double expk_step = expk;
     expk = expk * expk;
-    if (own_wave) {
-      const double ft = laneB ? expk : 1.0;   // t_s[c1] = j0+', t_s[c2] = j1-' = j0-' expk'
+    if constexpr (RID) {
+      if (own_wave) {
+        // t_s[c1] = j0+' = r_s[c2], t_s[c2] = j1-' = j0-' expk' = r_s[c1] expk'.  c1 = 4 KS is the first lane of a 4-lane DPP bank
+        // (RID: KS is no multiple of 4), so the swapped move is written to that bank alone and the factor is 1.0 (exact) in every
+        // lane but B.  The bank's other two lanes are the padding columns c1 + 2, c1 + 3: r_s and t_s hold +0.0 there -- the
+        // pre-pass writes 0.0 to every column >= n but the riders', a product maps a zero column of its right operand to a zero
+        // column (+0.0 + x 0.0, the accumulators start from +0.0 or from the padding itself), nadd_identity takes col < n and
+        // the out-of-line inverses clear the columns >= n -- so they exchange +0.0 for +0.0.
+        constexpr unsigned bank = 1u << ((c1 & 15) >> 2);
+        static_assert((c1 & 3) == 0 && (c2 & 15) == (c1 & 15) + 1, "the rider columns open a DPP bank");
+        const double ft = laneB ? expk : 1.0;
 #pragma unroll
-      for (int ta = 0; ta < RT; ++ta)
+        for (int ta = 0; ta < RT; ++ta)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const double u = ndpp_swap1(r_s.v[ta][r]) * ft;
-          t_s.v[ta][r] = laneAB ? u : t_s.v[ta][r];
-        }
+          for (int r = 0; r < 4; ++r) t_s.v[ta][r] = ndpp_swap1_bank<bank>(t_s.v[ta][r], r_s.v[ta][r]) * ft;
+      }
     }
+    // Q ([t]) is free since the barrier behind nstore(dP, tt): the new [t] leaves at once, under the other waves' products
+    if (it + 1 < ndoubl) nstore(dQ, t_s, p);
     if (it + 1 < ndoubl || !RID) __syncthreads();   // everybody finished reading P ([tt])
     if constexpr (!RID) {   // j0- += tt u1 ; j0+ = j0+ expk + tt u2   (visible after the barrier below / after the loop)
       if (tid < G::NP) {
@@ -142,7 +159,6 @@ __device__ __forceinline__ void ned_body(nsmem<RT, (4 * KS + 2 > 16 * RT)>& sm, 
     }
     if (it + 1 < ndoubl) {
       nstore(dP, r_s, p);
-      nstore(dQ, t_s, p);
       __syncthreads();
     }
   }
@@ -1083,7 +1099,7 @@ __global__ __launch_bounds__(ngeo<RT>::NT, ngeo<RT>::WPS) void k_layer_native(in
   double* comp = a.c[isub] + (long long)s * G::COMP_STRIDE;
   nstrip<RT> r_s, t_s;
   constexpr int KZ = KS - TZ;
-  ned_body<RT, KS, KZ>(sm, p, n, gsz, uvmask, ndoubl, img, r_s, t_s, status);
+  ned_body<RT, KS, KZ, SRC>(sm, p, n, gsz, uvmask, ndoubl, img, r_s, t_s, status);
   if (toa) {   // copy_added_to_composite! (rt_helpers.jl:188-200)
     const ndpar<RT> dp(sm.usg, p);
     if constexpr (!SRC) {

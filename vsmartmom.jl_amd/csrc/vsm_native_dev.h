@@ -105,6 +105,14 @@ __device__ __forceinline__ double ndpp_swap1(double x) {
   const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), 0xB1, 0xf, 0xf, false);
   return __hiloint2double(hi, lo);
 }
+// the same for the lanes of ONE 4-lane DPP bank (BANK = its bit of bank_mask): they take x of lane ^ 1, every other lane keeps t --
+// the move itself leaves the other banks alone, no select
+template <unsigned BANK>
+__device__ __forceinline__ double ndpp_swap1_bank(double t, double x) {
+  const int lo = __builtin_amdgcn_update_dpp(__double2loint(t), __double2loint(x), 0xB1, 0xf, BANK, false);
+  const int hi = __builtin_amdgcn_update_dpp(__double2hiint(t), __double2hiint(x), 0xB1, 0xf, BANK, false);
+  return __hiloint2double(hi, lo);
+}
 
 // ---- products: acc += [A] B, A-form at byte distance dA, B a strip in registers; pipelined by one k-step -------------------
 // (Z / Z1 / Z2: the accumulator starts from zero -- the first k-step takes the constant 0 as its addend: no register is cleared)
@@ -354,6 +362,23 @@ __device__ __forceinline__ void nadd_identity(nstrip<RT>& G, int n, const npos<R
       for (int r = 0; r < 4; ++r) G.v[ta][r] += (dl && dr == r) ? 1.0 : 0.0;
     }
 }
+// The same sums for the doubling step, whose chain between two products every wave of the workgroup waits for: above, the compiler
+// turns the branch into selects -- four adds and eight selects in EVERY row tile, the addends kept in registers from call to call.
+// Here the branch holds a statement that may not be executed speculatively, so it stays a branch: the four adds run in the wave's
+// own row tile, in place; the addends are formed at use from one opaque register.
+template <int RT>
+__device__ __forceinline__ void nadd_identity_tile(nstrip<RT>& G, int n, const npos<RT>& p) {
+  const bool dl = p.kq == (p.l15 & 3) && p.col < n;
+  int dr = dl ? (p.l15 >> 2) : 4;
+  asm volatile("" : "+v"(dr));
+#pragma unroll
+  for (int ta = 0; ta < RT; ++ta)
+    if (ta == p.wave) {
+      asm volatile("");
+#pragma unroll
+      for (int r = 0; r < 4; ++r) G.v[ta][r] += (dr == r) ? 1.0 : 0.0;
+    }
+}
 
 // In-place Gauss-Jordan with partial pivoting (the pivot rule of getrf: the contract of the reference's LU,
 // cpu_batched.jl:32-47) of the n x n matrix M (plain column-major, pitch NP) in LDS; lane = row, wave w = columns w, w + RT, ...
@@ -537,7 +562,8 @@ __device__ __forceinline__ void ninvert_slow_body(int K, nstrip<RT>& E, nstrip<R
 // On return other waves may still be reading W.
 // KZ: the products of the Horner series skip the zero-weight tail (E = [E] is in the class of DESIGN.md 4.0); the out-of-line
 // orders keep the dense products.
-template <int RT, int KS, bool REGS = false, int KZ = KS>
+// TILE: the identity by nadd_identity_tile (the doubling step).
+template <int RT, int KS, bool REGS = false, int KZ = KS, bool TILE = false>
 __device__ __forceinline__ void ninvert(int K, nstrip<RT>& E, nstrip<RT>& G, int n, const ninv_ctx& cx, npos<RT>& p) {
   if (K < 1 || K > 8) {
     nstrip<RT> Es = E, Gs;
@@ -559,7 +585,8 @@ __device__ __forceinline__ void ninvert(int K, nstrip<RT>& E, nstrip<RT>& G, int
       G = X;
     }
   }
-  nadd_identity(G, n, p);
+  if constexpr (TILE) nadd_identity_tile(G, n, p);
+  else nadd_identity(G, n, p);
 }
 // Order 7 without riders in G, in four products instead of Horner's six:  (I + E)(I + E^2)(I + E^4)  with
 //   W2 = E E,  T = E W2,  W4 = E T  (A = [E]),  S = E + W2 + T,  G = I + S + W4 + W4 S  (A = [W4]: one more A-form store).
