@@ -1284,6 +1284,32 @@ int vsm_exact_ss_jac12_f32(int S, int L, int C, int nV, int n_stokes, const floa
                                const float* p_c_h, const float* brdf, int brdf_spectral, const float* I0, float mu0, const float* mu_v_h,
                                float* d1_tau, float* d1_varpi, float* d1_P, float* d2_tau, float* d2_rho, void* stream);
 
+/* ---- Scattering: Mie (Siewert NAI-2) aerosol optics (src/Scattering/compute_NAI2.jl) ----------------------------------------
+ * The optics of one aerosol -- a size distribution on nquad radius nodes and a refractive index n_r - i n_i at one wavelength --
+ * as the Greek coefficients of its phase matrix, its bulk cross-sections and its single-scattering albedo.  FP64 only: the
+ * reference forces Float64 for the D_n recurrence even in Float32 models.  The host part is small and stays with the caller
+ * (compute_NAI2.jl:80-100, :113, :161); everything with an n_max, n_mu or nquad loop runs here, in three stages on `stream`:
+ *   1. one lane per radius: D_n(y) downwards from round(max(n_max_i, |y|) + 51), a_n, b_n upwards (compute_mie_ab!), C_sca_i, C_ext_i;
+ *   2. S1, S2 of every (angle, radius) on the FP64 MFMA with pi_n, tau_n generated in registers, turned into f11, f33, f12, f34,
+ *      weighted with wr_i 0.5 / x_i^2 and summed over the radii -- no [n_mu, nquad] array exists; partial sums are combined in a
+ *      fixed order, so a call is bit-identical to its repetition;
+ *   3. the Greek coefficients alpha .. zeta, l = 0 .. n_mu - 1, from the quadrature sums of compute_NAI2.jl:188-202 with P, P2, R2,
+ *      T2 generated by the recurrences of compute_legendre_poly.
+ * Device arrays: x [nquad] size parameters 2 pi r_i / lambda (> 0), nmax_i [nquad] = get_n_max(x_i) (int; clamped to 1 .. n_max),
+ * wx [nquad] the distribution's weights (sum 1), wr [nquad] = 4 pi r_i^2 wx_i, mu / w_mu [n_mu] the Gauss-Legendre nodes and
+ * weights on (-1, 1).  Scalars: n_max >= 2 orders (>= every nmax_i), n_mu = 2 n_max - 1, k_wave = 2 pi / lambda.
+ * Outputs (WRITTEN): greek [6, n_mu] row-major (alpha, beta, gamma, delta, epsilon, zeta; coefficient l at [c * n_mu + l]),
+ * bulk_f [4, n_mu] (f11, f33, f12, f34 summed over the distribution, NOT divided by C_sca), scal [3] = bulk C_sca, bulk C_ext,
+ * their ratio (the single-scattering albedo).  work: vsm_mie_work_elems(nquad, n_max, n_mu) doubles, uninitialised (0 is returned
+ * for arguments vsm_mie_nai2 refuses).  No host synchronisation, no library scratch.
+ * n_max above VSM_MIE_MAX_NMAX returns VSM_ERR_UNSUPPORTED (x = 500 needs 542); nquad < 1, n_max < 2, n_mu != 2 n_max - 1,
+ * n_i < 0, n_r <= 0, k_wave <= 0 or a null pointer return VSM_ERR_INVALID_ARG; both before any launch. */
+#define VSM_MIE_MAX_NMAX 1024
+size_t vsm_mie_work_elems(int nquad, int n_max, int n_mu);
+int vsm_mie_nai2(int nquad, int n_max, int n_mu, double n_r, double n_i, double k_wave, const double* x, const int* nmax_i,
+                 const double* wx, const double* wr, const double* mu, const double* w_mu, double* greek, double* bulk_f,
+                 double* scal, double* work, void* stream);
+
 /* ---- diagnostics used by the parity tests -------------------------------- */
 /* Runs the LDS-resident MFMA tile product used inside the fused kernels on plain
  * [N,N,S] inputs: C = A*B.  (Checks fragment layouts / swizzle independently.) */

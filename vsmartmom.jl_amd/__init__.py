@@ -23,6 +23,9 @@ Sub-modules
                     rt_run_ss_lin(RS_type, model, lin_model, ...) (core_rt_ss: its analytic Jacobians, elastic and inelastic)
     StandaloneSS    exact single scattering at the true scattering angle (standalone_ss: run_exact_ss, the four paths,
                     apply_back_correction = exact - truncated first-order field, Jacobians of paths 1 and 2)
+    Scattering      Mie aerosol optics (scattering: LogNormal / TabulatedSizeDistribution, Aerosol, make_mie_model,
+                    compute_aerosol_optical_properties = the Siewert NAI-2 path on the device, FP64: a size distribution and a
+                    refractive index in, a host_model.AerosolOptics with k, C_ext, C_sca out)
     parallel        spectral-axis sharding over the GPUs of one node (torch.distributed / RCCL)
 """
 from . import _lib, host_model  # noqa: F401
@@ -39,6 +42,7 @@ from . import core_rt_flux  # noqa: F401
 from . import core_rt_flux_lin  # noqa: F401
 from . import core_rt_flux_raman  # noqa: F401
 from . import standalone_ss as StandaloneSS  # noqa: F401
+from . import scattering as Scattering  # noqa: F401
 from . import raman_inputs  # noqa: F401
 from . import io_yaml  # noqa: F401
 from ._lib import VSMError, LIB_PATH  # noqa: F401

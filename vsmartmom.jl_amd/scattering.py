@@ -1,0 +1,241 @@
+"""Scattering: Mie aerosol optics by the Siewert NAI-2 method (src/Scattering/types.jl, make_mie_model.jl, compute_NAI2.jl) on the
+MI355X, through vsm_mie_nai2 (vsmartmom.jl_amd/csrc/vsm_mie.hip).
+
+    aerosol = Scattering.Aerosol(Scattering.LogNormal(0.3, 2.1), 1.3, 0.001)          # r_m, sigma_g [um]; n_r - i n_i
+    model   = Scattering.make_mie_model(aerosol, 0.55, r_max=30.0, nquad_radius=2500)   # wavelength, r_max in the radius' unit
+    optics, = Scattering.compute_aerosol_optical_properties(model, vsm.Architectures.GPU())
+    host_model.model_from_arrays(..., tau_aer=..., aerosol_optics=[optics])
+
+The host computes what is small (compute_NAI2.jl:80-100, :113, :161): r_min = max(quantile(1e-8), 1e-6 r_max), the gauleg_log
+nodes and weights, compute_w_x normalised to sum 1, x = 2 pi r / lambda, n_max_i = get_n_max(x_i), n_max, n_mu = 2 n_max - 1, the
+Gauss-Legendre nodes in mu, wr_i = 4 pi r_i^2 wx_i.  Everything with an n_max, n_mu or nquad loop -- D_n, a_n, b_n, S1, S2, the
+bulk functions, the Greek coefficients -- runs on the device in FP64 (the reference forces Float64 there too).  There is no CPU
+path: Architectures.CPU() raises.
+
+The result is a host_model.AerosolOptics with the reference's k (= the bulk extinction cross-section, in the squared unit of the
+radii) and the bulk C_ext / C_sca beside it.  Its f_trunc is 0: the coefficients are untruncated, and 0 is what this package's
+delta-M scaling (host_model.createAero) needs for them.  The reference stores f_trunc = 1 there and relies on a later
+truncate_phase.
+
+n_max = max(get_n_max(x_max), 2): the reference's compute_mie_pi_tau and compute_legendre_poly write two columns unconditionally,
+so it cannot run a distribution whose largest x gives n_max = 1 (x < 0.0019); two orders (three coefficients) is the least here.
+
+Not built: delta-BGE truncation (truncate_phase; a coarse-mode aerosol needs it before a run at small l_trunc), linearized Mie
+(compute_NAI2_lin.jl / LinAerosolOptics), PCW, the YAML `scattering:` block (io_yaml keeps refusing it).
+"""
+from __future__ import annotations
+
+import ctypes as C
+import functools
+import math
+import statistics
+from dataclasses import dataclass
+from typing import Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import host_model as H
+from . import core_rt as CR
+from .architectures import array_type, default_architecture, synchronize_if_gpu, to_host
+
+MAX_N_MAX = 1024      # VSM_MIE_MAX_NMAX of the library: the largest n_max the kernels take (x = 500 needs 542)
+
+
+# ---- types.jl ------------------------------------------------------------------------------------------------------------
+class LogNormal:
+    """LogNormal(r_m, sigma_g): median radius and geometric standard deviation -- the reference's
+    LogNormal(log(r_m), log(sigma_g)) of Distributions.jl."""
+
+    def __init__(self, r_m: float, sigma_g: float):
+        if not (r_m > 0 and sigma_g > 1):
+            raise _lib.VSMError("LogNormal needs r_m > 0 and sigma_g > 1 (got %r, %r)" % (r_m, sigma_g))
+        self.r_m, self.sigma_g = float(r_m), float(sigma_g)
+        self.mu, self.sigma = math.log(r_m), math.log(sigma_g)
+
+    def pdf(self, r):
+        r = np.asarray(r, dtype=np.float64)
+        z = (np.log(r) - self.mu) / self.sigma
+        return np.exp(-0.5 * z * z) / (r * self.sigma * math.sqrt(2 * math.pi))
+
+    def quantile(self, p: float) -> float:
+        return math.exp(self.mu + self.sigma * statistics.NormalDist().inv_cdf(p))
+
+    def __repr__(self):
+        return "LogNormal(%r, %r)" % (self.r_m, self.sigma_g)
+
+
+class TabulatedSizeDistribution:
+    """Any other size distribution (gamma, bimodal, measured): radius nodes r [nquad] and the unnormalised weights pdf(r_i) w_r,i
+    of the caller's own quadrature.  The nodes are used as they are; r_max and nquad_radius of the model are not read."""
+
+    def __init__(self, r: Sequence[float], weights: Sequence[float]):
+        self.r = np.array(r, dtype=np.float64).reshape(-1)
+        self.weights = np.array(weights, dtype=np.float64).reshape(-1)
+        if self.r.shape != self.weights.shape:
+            raise _lib.VSMError("TabulatedSizeDistribution: %d radii, %d weights" % (len(self.r), len(self.weights)))
+
+
+@dataclass
+class Aerosol:
+    """Aerosol(size_distribution, n_r, n_i) (types.jl): refractive index n_r - i n_i, n_i >= 0."""
+    size_distribution: object
+    n_r: float
+    n_i: float
+
+
+@dataclass
+class MieModel:
+    aerosol: Aerosol
+    wavelength: float
+    r_max: Optional[float]
+    nquad_radius: Optional[int]
+
+
+def make_mie_model(aerosol: Aerosol, wavelength: float, r_max: Optional[float] = None, nquad_radius: Optional[int] = None) -> MieModel:
+    """make_mie_model(NAI2(), aerosol, wavelength, ., ., r_max, nquad_radius) (make_mie_model.jl:24-32); wavelength, r_max and the
+    distribution's radii in one unit.  A TabulatedSizeDistribution brings its own nodes: r_max and nquad_radius may be omitted."""
+    return MieModel(aerosol, float(wavelength), r_max, nquad_radius)
+
+
+@dataclass
+class MieHostInputs:
+    """What the host hands the device: the inputs of vsm_mie_nai2."""
+    r: np.ndarray
+    wx: np.ndarray
+    wr: np.ndarray
+    x: np.ndarray
+    nmax_i: np.ndarray
+    n_max: int
+    n_mu: int
+    mu: np.ndarray
+    w_mu: np.ndarray
+    k_wave: float
+
+
+@dataclass
+class MieAerosolOptics(H.AerosolOptics):
+    """host_model.AerosolOptics plus the reference's k and the bulk cross-sections (squared unit of the radii); mu and bulk_f
+    [4, n_mu] are the angle nodes and the bulk f11, f33, f12, f34 there, before the division by C_sca."""
+    k: float = 0.0
+    C_ext: float = 0.0
+    C_sca: float = 0.0
+    mu: Optional[np.ndarray] = None
+    bulk_f: Optional[np.ndarray] = None
+
+
+# ---- mie_helper_functions.jl: the host part -------------------------------------------------------------------------------------
+def get_n_max(size_parameter: float) -> int:
+    """mie_helper_functions.jl:22 (Sanghavi 2014 eq. 6); round to nearest, ties to even, as Julia's round(Int, .)."""
+    x = float(size_parameter)
+    if x > 8.0:
+        return int(round(x + 4.05 * x ** (1 / 3) + 10))
+    return int(round(x + 4.0 * x ** (1 / 3) + 1))
+
+
+@functools.lru_cache(maxsize=16)
+def gausslegendre(n: int):
+    """Gauss-Legendre nodes and weights on (-1, 1), kept per n (read-only arrays): at nquad_radius = 2500 they are nearly all of
+    the host part's time, and a retrieval asks for the same two sizes per band, aerosol and iteration."""
+    xi, w = np.polynomial.legendre.leggauss(int(n))
+    xi.flags.writeable = False
+    w.flags.writeable = False
+    return xi, w
+
+
+def gauleg_log(n: int, r_min: float, r_max: float):
+    """gauleg_log(n, r_min, r_max; norm = false) (mie_helper_functions.jl:369-379): Gauss-Legendre nodes in ln r."""
+    xi, w = gausslegendre(n)
+    ln_min, ln_max = math.log(r_min), math.log(r_max)
+    r = np.exp((ln_max - ln_min) / 2 * xi + (ln_max + ln_min) / 2)
+    return r, w * r * (ln_max - ln_min) / 2
+
+
+def compute_wx(size_distribution, w_r, r):
+    """compute_w_x (mie_helper_functions.jl:511-521)."""
+    wx = size_distribution.pdf(r) * w_r
+    return wx / np.sum(wx)
+
+
+def mie_host_inputs(model: MieModel) -> MieHostInputs:
+    """compute_NAI2.jl:72-100, :113, :161, with the refusals of this backend (VSMError)."""
+    aer = model.aerosol
+    sd = aer.size_distribution
+    if not (aer.n_i >= 0):
+        raise _lib.VSMError("Aerosol: n_i = %r < 0 (the refractive index is n_r - i n_i with n_i >= 0)" % (aer.n_i,))
+    if not (aer.n_r > 0 and model.wavelength > 0):
+        raise _lib.VSMError("Aerosol: n_r = %r and the wavelength %r must be positive" % (aer.n_r, model.wavelength))
+    if isinstance(sd, TabulatedSizeDistribution):
+        if len(sd.r) < 1:
+            raise _lib.VSMError("TabulatedSizeDistribution: nquad_radius = 0 < 1")
+        total = float(np.sum(sd.weights))
+        if not (np.all(sd.r > 0) and np.all(np.isfinite(sd.r)) and np.all(sd.weights >= 0) and 0 < total < math.inf):
+            raise _lib.VSMError("TabulatedSizeDistribution: radii must be positive, weights non-negative with a positive sum")
+        r, wx = sd.r.copy(), sd.weights / total
+    else:
+        if model.nquad_radius is None or int(model.nquad_radius) < 1:
+            raise _lib.VSMError("nquad_radius = %r < 1" % (model.nquad_radius,))
+        if model.r_max is None or not math.isfinite(model.r_max):
+            raise _lib.VSMError("r_max = %r: a finite largest radius is needed" % (model.r_max,))
+        r_min = max(sd.quantile(1e-8), 1e-6 * model.r_max)
+        if not (model.r_max > r_min):
+            raise _lib.VSMError("r_max = %r <= r_min = %r = max(quantile(1e-8), 1e-6 r_max)" % (model.r_max, r_min))
+        r, w_r = gauleg_log(int(model.nquad_radius), r_min, float(model.r_max))
+        wx = compute_wx(sd, w_r, r)
+    k_wave = 2 * math.pi / model.wavelength
+    x = k_wave * r
+    nmax_i = np.array([get_n_max(v) for v in x], dtype=np.int32)
+    n_max = max(get_n_max(np.max(x)), 2)
+    if n_max > MAX_N_MAX:
+        raise _lib.VSMError("n_max = %d (largest size parameter %.1f) above the %d orders the Mie kernels take "
+                            "(VSM_MIE_MAX_NMAX)" % (n_max, float(np.max(x)), MAX_N_MAX))
+    n_mu = 2 * n_max - 1
+    mu, w_mu = gausslegendre(n_mu)
+    wr = 4 * math.pi * r ** 2 * wx
+    return MieHostInputs(r, wx, wr, x, nmax_i, n_max, n_mu, mu, w_mu, k_wave)
+
+
+# ---- compute_NAI2.jl: the driver ------------------------------------------------------------------------------------------------
+def device_inputs(h: MieHostInputs, conv):
+    """The six device arrays of vsm_mie_nai2, in its argument order."""
+    return [conv(a) for a in (h.x, h.nmax_i, h.wx, h.wr, h.mu, h.w_mu)]
+
+
+def launch_nai2(model: MieModel, h: MieHostInputs, dev):
+    """Enqueues vsm_mie_nai2 on the current stream: (greek [6, n_mu], bulk_f [4, n_mu], scal [3], work) device tensors.  Nothing is
+    synchronised; the inputs and the work buffer must outlive the work."""
+    nq, like = len(h.x), dev[0]
+    greek = torch.empty((6, h.n_mu), dtype=torch.float64, device=like.device)
+    bulk_f = torch.empty((4, h.n_mu), dtype=torch.float64, device=like.device)
+    scal = torch.empty(3, dtype=torch.float64, device=like.device)
+    elems = int(_lib.lib().vsm_mie_work_elems(nq, h.n_max, h.n_mu))
+    if elems == 0:
+        raise _lib.VSMError("vsm_mie_work_elems refuses nquad = %d, n_max = %d, n_mu = %d" % (nq, h.n_max, h.n_mu))
+    work = _lib.poison(torch.empty(elems, dtype=torch.float64, device=like.device))
+    _lib.check(_lib.lib().vsm_mie_nai2(nq, h.n_max, h.n_mu, C.c_double(model.aerosol.n_r), C.c_double(model.aerosol.n_i),
+                                       C.c_double(h.k_wave), *[CR._ptr(t) for t in dev], CR._ptr(greek), CR._ptr(bulk_f),
+                                       CR._ptr(scal), CR._ptr(work), CR._stream_ptr()))
+    return greek, bulk_f, scal, work
+
+
+def compute_aerosol_optical_properties(model_or_list, architecture=None):
+    """compute_aerosol_optical_properties(model) (compute_NAI2.jl:63-217) for one MieModel or a list of them: a list with one
+    MieAerosolOptics per model (greek_coefs, ssa, f_trunc = 0 -- see the module's docstring --, k, C_ext, C_sca).  All models are
+    enqueued on the current stream before the one synchronisation that brings the results back."""
+    models = [model_or_list] if isinstance(model_or_list, MieModel) else list(model_or_list)
+    arch = architecture if architecture is not None else default_architecture()
+    CR._require_gpu(arch)
+    _lib.lib()
+    conv = array_type(arch)
+    hosts = [mie_host_inputs(m) for m in models]         # (every refusal before the first launch)
+    devs = [device_inputs(h, conv) for h in hosts]
+    runs = [launch_nai2(m, h, d) for m, h, d in zip(models, hosts, devs)]
+    synchronize_if_gpu()
+    out = []
+    for h, (greek, bulk_f, scal, _work) in zip(hosts, runs):
+        g = to_host(greek)
+        c_sca, c_ext, ssa = (float(v) for v in to_host(scal))
+        out.append(MieAerosolOptics(H.GreekCoefs(*(g[i].copy() for i in range(6))), ssa, 0.0, k=c_ext, C_ext=c_ext, C_sca=c_sca,
+                                    mu=h.mu, bulk_f=to_host(bulk_f)))
+    return out
