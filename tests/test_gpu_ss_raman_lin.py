@@ -196,6 +196,32 @@ def test_halo_and_slot_ranges_do_not_change_results(vsm, arch):
         assert np.all(y[..., 9] == 0)
 
 
+def test_shared_pieces_with_two_live_threads_in_the_second_workgroup(vsm, arch):
+    """What the four column kernels share (rows, Z F0, donors, LDS window, recipient set-up, output index), FP64, where their
+    bookkeeping is thinnest: S = VSM_SS_BLOCK + 2, so the second workgroup has two live threads beside the barriers; IQU with three
+    viewing angles, 9 table items in three row groups, the last holding one row; the middle angle is the solar zenith angle, so
+    the sun-row branches run; |shift| up to 5 in band, 150 and more out of it; one aerosol (the Z_dot kernel).  One run launches all
+    four kernels: its eight arrays against the oracle at the run tolerance; then the derivative kernel with halo = 0 (every donor
+    but shift 0's from global memory) against the clamped halo (every donor staged) at the bound of
+    test_halo_and_slot_ranges_do_not_change_results."""
+    FT, S = np.float64, 130
+    om, ol, pm, hl = _scene(vsm, arch, "IQU", S, 1, 2, FT)
+    qp = om.quad_points
+    mu = np.asarray(qp.qp_mu)
+    assert [int(np.argmin(np.abs(mu - O.cosd(v)))) for v in TGL.VZA][1] == int(qp.imu0)
+    ors, prs = _rs_pair(vsm, SHIFTS_BIG, W_IE_BIG)
+    ref = SRL.rt_run_ss_rrs_lin(om, ol, ors)
+    assert all(np.max(np.abs(r)) > 0 for r in ref)
+    got = vsm.CoreRTRaman.rt_run_ss_lin(prs, pm, hl, 1, 2, 1)
+    _check_run(vsm, got, ref, pm, hl, prs, 1, 2, FT)
+    a = _kernel_case(vsm, arch, om, ol, pm, ors, FT, halo=0)
+    b = _kernel_case(vsm, arch, om, ol, pm, ors, FT, halo=10 ** 6)     # clamped to VSM_SS_MAX_HALO
+    for x, y in zip(a, b):
+        for p in range(9):
+            assert np.max(np.abs(y[..., p])) > 0 and _rel(x[..., p], y[..., p]) <= 1e-13, p
+        assert np.all(x[..., 9] == 0) and np.all(y[..., 9] == 0)
+
+
 # ---- the close branches ----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("which", ["equal tau", "tau ratio = mu ratio"])
 def test_close_branch_scenes_against_oracle(vsm, arch, which):

@@ -64,6 +64,8 @@ import test_gpu_sif as TS  # noqa: E402
 import test_gpu_surface_emission as TSE  # noqa: E402
 import test_gpu_surface_emission_lin as TSEL  # noqa: E402
 import test_gpu_ss as TSS  # noqa: E402
+import test_gpu_ss_lin as TSL  # noqa: E402
+import test_gpu_ss_raman_lin as TSRL  # noqa: E402
 
 H, CR, CL, RR = vsm.host_model, vsm.CoreRT, vsm.CoreRTLin, vsm.CoreRTRaman
 arch = vsm.Architectures.GPU(0)
@@ -461,6 +463,59 @@ def raman_and_ss():
     out.append(RR.rt_run_multisensor(TMR._rs(vsm)[1], pm, TMR.LEVELS))
     _, pm = TSS._models(vsm, arch, "IQU", 7, 6, 3, np.float64)
     return out, CR.rt_run_ss(pm)
+
+
+# ---- the single-scattering column kernels (csrc/vsm_ss.hip): the four drivers and the tests' kernel helpers ---------------------------
+FTS = (np.float64, np.float32)
+SS_SHAPES = [("IQU", 70, TSS.SHIFTS, TSS.W_IE), ("IQUV", 300, TSS.SHIFTS_BIG, TSS.W_IE_BIG), ("I", 1, TSS.SHIFTS, TSS.W_IE),
+             ("I", 7, TSS.SHIFTS, TSS.W_IE)]
+
+
+@scene
+def ss_forward_runs():
+    """rt_run_ss and rt_run_ss_rrs (the columns with hem_R / hem_T, the Raman column with staged and global donors)."""
+    out = []
+    for FT in FTS:
+        for pol, S, shifts, w_ie in SS_SHAPES:
+            _, pm = TSS._models(vsm, arch, pol, 7, S, 3, FT)
+            out += [CR.rt_run_ss(pm), RR.rt_run_ss(TSS._rs_pair(vsm, shifts, w_ie)[1], pm, 1)]
+    return out
+
+
+@scene
+def ss_lin_runs():
+    """rt_run_ss_lin with one aerosol (the Z_dot kernel), without one, and over Cox-Munk; rt_run_ss_rrs_lin."""
+    out = []
+    for FT in FTS:
+        for pol, S, shifts, w_ie in SS_SHAPES[:3]:
+            for naer in (1, 0):
+                _, _, pm, hl = TSL._scene(vsm, arch, pol, S, naer, 2, FT)
+                out.append(CL.rt_run_ss(pm, hl, naer, 2, 1))
+            out.append(RR.rt_run_ss_lin(TSS._rs_pair(vsm, shifts, w_ie)[1], pm, hl, 0, 2, 1))
+        _, _, pm, hl = TSL._scene(vsm, arch, "IQU", 70, 1, 2, FT)
+        out.append(RR.rt_run_ss_lin(TSS._rs_pair(vsm, TSS.SHIFTS, TSS.W_IE)[1], pm, hl, 1, 2, 1))
+        _, _, pm, hl = TSL._scene(vsm, arch, "IQU", 70, 0, 2, FT, surface=H.CoxMunkSurface(wind_speed=5.0))
+        pm.m_max = 3
+        out.append(CL.rt_run_ss(pm, hl, 0, 2, 1))
+    return out
+
+
+@scene
+def ss_kernel_cases():
+    """The _kernel_case helpers of the three test files: the four kernels on the oracle's inputs, with halo = 0 (donors from global
+    memory) and the clamped halo (donors staged), and with a slot sub-range."""
+    out = []
+    for FT in FTS:
+        for pol, S, shifts, w_ie in SS_SHAPES[:3]:
+            om, pm = TSS._models(vsm, arch, pol, 7, S, 3, FT)
+            ors = TSS._rs_pair(vsm, shifts, w_ie)[0]
+            out += [TSS._kernel_case(vsm, arch, om, pm, FT, rs=ors, halo=h) for h in (0, 10 ** 6)]
+            om, ol, pm, _ = TSL._scene(vsm, arch, pol, S, 0, 2, FT)
+            out += [TSL._kernel_case(vsm, arch, om, ol, pm, FT), TSL._kernel_case(vsm, arch, om, ol, pm, FT, p_range=(1, 3))]
+            om, ol, pm, _ = TSL._scene(vsm, arch, pol, S, 1, 2, FT)
+            out += [TSRL._kernel_case(vsm, arch, om, ol, pm, ors, FT, halo=h) for h in (0, 10 ** 6)]
+            out.append(TSRL._kernel_case(vsm, arch, om, ol, pm, ors, FT, halo=10 ** 6, p_ranges=((0, 3), (3, 10))))
+    return out
 
 
 for name_, f in SCENES.items():

@@ -370,6 +370,29 @@ class LinInputs:
                 rho, drho = CR.reflectance(model.surface, self.dq, m, self.arch, self.FT, deriv=True)
             self.surf.append((rho, drho))
 
+    def surface_layer_lin_(self, mom, added_s, als, F0, vectors_only=False):
+        """create_surface_layer! (lin) of one Fourier moment into the surface layers `added_s` / `als`, driven by the beam F0.
+        vectors_only: the spectral Lambertian builder's mode that leaves the matrices of shared layers unwritten."""
+        model, dt, S, pl = self.model, self.dt, self.S, self.pl
+        isurf = self.layout.surface_index(0)
+        q_ = self.dq.cstruct()
+        m = mom["m"]
+        a_, al_ = added_s.cstruct(), als.cstruct()
+        tau_sum_s, tsd_s = mom["tau_sum_surface"], self.tau_sum_dot[self.fwd.Nz]
+        rho, drho = self.surf[m]
+        if isinstance(model.surface, H.CoxMunkSurface):
+            _lib.call("vsm_brdf_surface_lin", dt, C.byref(q_), S, m, CR._ptr(rho), CR._ptr(drho), isurf, CR._ptr(tau_sum_s),
+                      CR._ptr(tsd_s), pl, CR._ptr(F0), C.byref(a_), C.byref(al_), CR._stream_ptr())
+        elif type(model.surface) in LAND_BRDF:
+            brdf_surface_lin_multi_(self.dq, S, m, rho, drho, isurf, tau_sum_s, tsd_s, pl, F0, added_s, als)
+        elif isinstance(model.surface, SPECTRAL_LAMBERTIAN):   # (mom["rho"]: the forward scene's per-point albedo)
+            lambertian_surface_spectral_lin_(self.dq, S, m, mom["rho"], self.albedo_basis, isurf, tau_sum_s, tsd_s, pl, F0, added_s, als,
+                                             vectors_only=vectors_only)
+        else:
+            alb = C.c_double(model.surface.albedo) if dt == torch.float64 else C.c_float(model.surface.albedo)
+            _lib.call("vsm_lambertian_surface_lin", dt, C.byref(q_), S, m, alb, isurf, CR._ptr(tau_sum_s), CR._ptr(tsd_s), pl,
+                      CR._ptr(F0), C.byref(a_), C.byref(al_), CR._stream_ptr())
+
 
 class SceneLin(LinInputs):
     """Everything rt_run(model, lin_model, NAer, NGas, NSurf) needs, resident in HBM (the linearized twin of CoreRT.Scene).
@@ -965,28 +988,11 @@ class SceneLin(LinInputs):
         w["Td"][o:o + self.nSIF].add_(torch.einsum("kis,iscv->kscv", coef, dn))
 
     def _surface_lin(self, mom, added_s, als, F0):
-        """create_surface_layer! (lin) of one Fourier moment into the surface layers `added_s` / `als`, driven by the beam F0; at
-        m = 0 SurfaceSIF is then injected into the forward j0- (rt_run_lin.jl:292; it depends on no parameter, so the derivative
-        stacks stay what the builder wrote -- and the builder has formed its -tau_sum_dot / mu0 terms from the beam term alone)."""
-        model, dt, S, pl = self.model, self.dt, self.S, self.pl
-        isurf = self.layout.surface_index(0)
-        q_ = self.dq.cstruct()
-        m = mom["m"]
-        a_, al_ = added_s.cstruct(), als.cstruct()
-        tau_sum_s, tsd_s = mom["tau_sum_surface"], self.tau_sum_dot[self.fwd.Nz]
-        rho, drho = self.surf[m]
-        if isinstance(model.surface, H.CoxMunkSurface):
-            _lib.call("vsm_brdf_surface_lin", dt, C.byref(q_), S, m, CR._ptr(rho), CR._ptr(drho), isurf, CR._ptr(tau_sum_s),
-                      CR._ptr(tsd_s), pl, CR._ptr(F0), C.byref(a_), C.byref(al_), CR._stream_ptr())
-        elif type(model.surface) in LAND_BRDF:
-            brdf_surface_lin_multi_(self.dq, S, m, rho, drho, isurf, tau_sum_s, tsd_s, pl, F0, added_s, als)
-        elif isinstance(model.surface, SPECTRAL_LAMBERTIAN):   # (mom["rho"]: the forward scene's per-point albedo)
-            lambertian_surface_spectral_lin_(self.dq, S, m, mom["rho"], self.albedo_basis, isurf, tau_sum_s, tsd_s, pl, F0, added_s, als)
-        else:
-            alb = C.c_double(model.surface.albedo) if dt == torch.float64 else C.c_float(model.surface.albedo)
-            _lib.call("vsm_lambertian_surface_lin", dt, C.byref(q_), S, m, alb, isurf, CR._ptr(tau_sum_s), CR._ptr(tsd_s), pl,
-                      CR._ptr(F0), C.byref(a_), C.byref(al_), CR._stream_ptr())
-        CR.surface_source_contribute_(self.fwd, model.surface, added_s, m)
+        """The linearized surface layer (surface_layer_lin_); at m = 0 SurfaceSIF is then injected into the forward j0-
+        (rt_run_lin.jl:292; it depends on no parameter, so the derivative stacks stay what the builder wrote -- and the builder
+        has formed its -tau_sum_dot / mu0 terms from the beam term alone)."""
+        self.surface_layer_lin_(mom, added_s, als, F0)
+        CR.surface_source_contribute_(self.fwd, self.model.surface, added_s, mom["m"])
 
     # ---- the thermal slot (DESIGN 4.12) ----------------------------------------------------------------------------------------
     def _thermal_state(self):

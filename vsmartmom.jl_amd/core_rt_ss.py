@@ -26,8 +26,16 @@ from .architectures import array_type, synchronize_if_gpu, to_host
 MAX_HALO = 192   # VSM_SS_MAX_HALO of the library
 
 
-def _ptr_table(tensors):
-    return (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+def _ptr_table(tensors, L=None):
+    """A host table of device pointers (L entries where given); None stays None, a None entry is a null pointer."""
+    if tensors is None:
+        return None
+    return (C.c_void_p * (len(tensors) if L is None else L))(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+def _tr(t):
+    """A device result (S, nStokes, nVZA) or (P, S, nStokes, nVZA) on the host, axes reversed: [nVZA, nStokes, nSpec(, Nparams)]."""
+    return to_host(t).T.copy()
 
 
 def ss_column_(dq: CR.DeviceQuad, m: int, tau, varpi, tau_sum, Zpp, Zmp, z_stride, F0, surf_j0_m, surf_j0_p, tau_sum_surface,
@@ -174,13 +182,12 @@ def ss_column_lin_(dq: CR.DeviceQuad, m: int, P: int, p_layer: int, p_zdot: int,
     L, S = len(tau), int(F0.shape[0])
     q = dq.cstruct()
     zs = (C.c_longlong * L)(*[int(z) for z in z_stride])
-    tab = lambda ts: None if ts is None else (C.c_void_p * L)(*[None if t is None else t.data_ptr() for t in ts])
     p_lo, p_hi = (0, P) if p_range is None else p_range
-    _lib.call("vsm_ss_column_lin", dq.dtype, C.byref(q), S, L, m, P, p_layer, int(p_zdot), int(p_lo), int(p_hi), tab(tau), tab(varpi),
-              tab(tau_sum), tab(Zpp), tab(Zmp), zs, tab(tau_dot), tab(varpi_dot), tab(tau_sum_dot), tab(zdcoef), int(CT),
-              CR._ptr(Zc_pp), CR._ptr(Zc_mp), CR._ptr(F0), CR._ptr(surf_j0_m), CR._ptr(surf_j0_p), CR._ptr(surf_j0_m_lin),
-              CR._ptr(surf_j0_p_lin), CR._ptr(tau_sum_surface), CR._ptr(tau_sum_dot_surface), nV, row0, w, CR._ptr(Rdot),
-              CR._ptr(Tdot), CR._stream_ptr())
+    tabs = [_ptr_table(t, L) for t in (tau, varpi, tau_sum, Zpp, Zmp, tau_dot, varpi_dot, tau_sum_dot, zdcoef)]
+    _lib.call("vsm_ss_column_lin", dq.dtype, C.byref(q), S, L, m, P, p_layer, int(p_zdot), int(p_lo), int(p_hi), *tabs[:5], zs,
+              *tabs[5:], int(CT), CR._ptr(Zc_pp), CR._ptr(Zc_mp), CR._ptr(F0), CR._ptr(surf_j0_m), CR._ptr(surf_j0_p),
+              CR._ptr(surf_j0_m_lin), CR._ptr(surf_j0_p_lin), CR._ptr(tau_sum_surface), CR._ptr(tau_sum_dot_surface), nV, row0, w,
+              CR._ptr(Rdot), CR._ptr(Tdot), CR._stream_ptr())
 
 
 class SceneSSLin(CL.LinInputs):
@@ -218,7 +225,6 @@ class SceneSSLin(CL.LinInputs):
     def run(self):
         """Asynchronous; returns R, T (S, nStokes, nVZA) and Rdot, Tdot (P, S, nStokes, nVZA) on the device."""
         model, fwd = self.model, self.fwd
-        pol, qp, FT, dt = self.pol, self.qp, self.FT, self.dt
         S, P, pl, L = self.S, self.P, self.pl, fwd.Nz
         self.Rd.zero_()
         self.Td.zero_()
@@ -226,28 +232,13 @@ class SceneSSLin(CL.LinInputs):
             self.ss.run()
             return self.R, self.T, self.Rd, self.Td
         nV = len(model.vza)
-        isurf = self.layout.surface_index(0)
-        q_ = self.dq.cstruct()
         tsd_s = self.tau_sum_dot[L]
 
         def lin_moment(mom, props, row0, w):
             """After the forward launches of the moment (fwd.added_surface holds the forward builder's surface layer: its j0+ is
             read here): the linearized builder's j0- and ap_J0-+ of all P slots, then the linearized column."""
             m, layers, tau_sum_s = mom["m"], mom["layers"], mom["tau_sum_surface"]
-            a_, al_ = self.added_s.cstruct(), self.als.cstruct()
-            rho, drho = self.surf[m]
-            if isinstance(model.surface, H.CoxMunkSurface):
-                _lib.call("vsm_brdf_surface_lin", dt, C.byref(q_), S, m, CR._ptr(rho), CR._ptr(drho), isurf, CR._ptr(tau_sum_s),
-                          CR._ptr(tsd_s), pl, CR._ptr(self.F0), C.byref(a_), C.byref(al_), CR._stream_ptr())
-            elif type(model.surface) in CL.LAND_BRDF:
-                CL.brdf_surface_lin_multi_(self.dq, S, m, rho, drho, isurf, tau_sum_s, tsd_s, pl, self.F0, self.added_s, self.als)
-            elif isinstance(model.surface, CL.SPECTRAL_LAMBERTIAN):   # (vectors only: the matrices of these shared layers are not read)
-                CL.lambertian_surface_spectral_lin_(self.dq, S, m, mom["rho"], self.albedo_basis, isurf, tau_sum_s, tsd_s, pl, self.F0,
-                                                    self.added_s, self.als, vectors_only=True)
-            else:
-                alb = C.c_double(model.surface.albedo) if dt == torch.float64 else C.c_float(model.surface.albedo)
-                _lib.call("vsm_lambertian_surface_lin", dt, C.byref(q_), S, m, alb, isurf, CR._ptr(tau_sum_s), CR._ptr(tsd_s), pl,
-                          CR._ptr(self.F0), C.byref(a_), C.byref(al_), CR._stream_ptr())
+            self.surface_layer_lin_(mom, self.added_s, self.als, self.F0, vectors_only=True)
             zall = self.Zall[m] if self.Zall is not None else (None, None)
             ss_column_lin_(fwd.dq, m, P, pl, 7 * self.nAer if self.Zall is not None else 0, [p.tau for p in props],
                            [p.varpi for p in props], [ly["tau_sum"] for ly in layers], [p.Zpp for p in props],
@@ -266,9 +257,7 @@ class SceneSSLin(CL.LinInputs):
 
     def results_host(self):
         """(R, T, Rdot, Tdot): [nVZA, nStokes, nSpec] and [nVZA, nStokes, nSpec, Nparams], as rt_run_lin returns them."""
-        tr = lambda t: to_host(t).transpose(2, 1, 0).copy()
-        tr4 = lambda t: to_host(t).transpose(3, 2, 1, 0).copy()
-        return tr(self.R), tr(self.T), tr4(self.Rd), tr4(self.Td)
+        return _tr(self.R), _tr(self.T), _tr(self.Rd), _tr(self.Td)
 
 
 def rt_run_ss_lin(model: H.RTModel, lin_model: H.LinModel, NAer: int, NGas: int, NSurf: int):
@@ -295,11 +284,11 @@ def ss_column_rrs_lin_(dq: CR.DeviceQuad, m: int, P: int, p_layer: int, tau, tau
     all P) below p_layer; the others are not touched."""
     L, S, K = len(tau), int(F0.shape[0]), int(shift.numel())
     q = dq.cstruct()
-    tab = lambda ts: None if ts is None else (C.c_void_p * L)(*[None if t is None else t.data_ptr() for t in ts])
     p_lo, p_hi = (0, P) if p_range is None else p_range
-    _lib.call("vsm_ss_column_rrs_lin", dq.dtype, C.byref(q), S, L, m, K, P, p_layer, int(p_lo), int(p_hi), tab(tau), tab(tau_sum),
-              tab(fscatt), tab(tau_dot), tab(tau_sum_dot), tab(fscatt_dot), CR._ptr(shift), CR._ptr(varpi_ie), CR._ptr(Zpp_ie),
-              CR._ptr(Zmp_ie), CR._ptr(F0), int(halo), nV, row0, w, CR._ptr(ieRdot), CR._ptr(ieTdot), CR._stream_ptr())
+    tabs = [_ptr_table(t, L) for t in (tau, tau_sum, fscatt, tau_dot, tau_sum_dot, fscatt_dot)]
+    _lib.call("vsm_ss_column_rrs_lin", dq.dtype, C.byref(q), S, L, m, K, P, p_layer, int(p_lo), int(p_hi), *tabs, CR._ptr(shift),
+              CR._ptr(varpi_ie), CR._ptr(Zpp_ie), CR._ptr(Zmp_ie), CR._ptr(F0), int(halo), nV, row0, w, CR._ptr(ieRdot),
+              CR._ptr(ieTdot), CR._stream_ptr())
 
 
 class SceneSSRamanLin(SceneSSLin):
@@ -359,9 +348,7 @@ class SceneSSRamanLin(SceneSSLin):
 
     def results_host(self):
         """(R1, T1, ieR1, ieT1, R1dot, T1dot, ieR1dot, ieT1dot): [nVZA, nStokes, nSpec] x 4, [nVZA, nStokes, nSpec, Nparams] x 4."""
-        tr = lambda t: to_host(t).transpose(2, 1, 0).copy()
-        tr4 = lambda t: to_host(t).transpose(3, 2, 1, 0).copy()
-        return (tr(self.R), tr(self.T), tr(self.ieR), tr(self.ieT), tr4(self.Rd), tr4(self.Td), tr4(self.ieRd), tr4(self.ieTd))
+        return (_tr(self.R), _tr(self.T), _tr(self.ieR), _tr(self.ieT), _tr(self.Rd), _tr(self.Td), _tr(self.ieRd), _tr(self.ieTd))
 
 
 def rt_run_ss_rrs_lin(RS_type, model: H.RTModel, lin_model: H.LinModel, NAer: int, NGas: int, NSurf: int, iBand: int = 1):

@@ -127,6 +127,14 @@ void* scratch(size_t bytes, int slot, hipStream_t st) {
   return p;
 }
 
+int upload_image(const packed_image& img, int slot, hipStream_t st, unsigned char** dev) {
+  *dev = static_cast<unsigned char*>(scratch(img.b.size(), slot, st));
+  if (!*dev) return VSM_ERR_HIP;
+  VSM_HIP(hipMemcpyAsync(*dev, img.b.data(), img.b.size(), hipMemcpyHostToDevice, st));
+  VSM_HIP(hipStreamSynchronize(st));   // the image dies with the caller's frame: the copy must have left it
+  return VSM_OK;
+}
+
 int release_scratch() {
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);

@@ -10,10 +10,6 @@
 //   varpi_eff P_eff = (sum_c tau_c varpi_c p_c) / tau      (zero where tau = 0)
 // and none of those arrays exists.  Lanes run along the spectral axis; a thread walks the layers of its point for one viewing
 // geometry (grid.y) and carries the running optical depth in registers.  Nothing here is N x N.
-#include <string.h>
-
-#include <vector>
-
 #include "vsm_common.h"
 #include "vsm_internal.h"
 
@@ -252,25 +248,8 @@ __global__ __launch_bounds__(XS_TB) void k_xs_jac12(int S, int L, int C, int nV,
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
-// Device tables of one call in the library's scratch, one stream-ordered copy of a packed host image (as vsm_ss_column_*): the C L
-// layer pointers, then the small tables.  L, C and the number of geometries are not capped by it.
-struct xs_image {
-  std::vector<unsigned char> b;
-  size_t add(const void* p, size_t n) {
-    const size_t o = (b.size() + 7) & ~(size_t)7;
-    b.resize(o + n);
-    if (n) memcpy(b.data() + o, p, n);
-    return o;
-  }
-};
-static int xs_upload(const xs_image& img, hipStream_t st, unsigned char** dev) {
-  *dev = static_cast<unsigned char*>(scratch(img.b.size(), XS_SLOT, st));
-  if (!*dev) return VSM_ERR_HIP;
-  VSM_HIP(hipMemcpyAsync(*dev, img.b.data(), img.b.size(), hipMemcpyHostToDevice, st));
-  VSM_HIP(hipStreamSynchronize(st));   // the image dies with the caller's frame: the copy must have left it
-  return VSM_OK;
-}
-
+// Device tables of one call: a packed_image in the library's scratch (vsm_internal.h) -- the C L layer pointers, then the small
+// tables.  L, C and the number of geometries are not capped by it.
 template <typename T>
 static int xs_check(const char* who, int S, int L, int C, int nV, const T* const* tau_c_h, const T* I0, T mu0, const T* mu_v_h) {
   VSM_REQUIRE(S >= 0 && L >= 1 && C >= 1, "%s: S >= 0, L >= 1 and C >= 1 required (S = %d, L = %d, C = %d)", who, S, L, C);
@@ -293,11 +272,11 @@ static int xs_path1(int S, int L, int C, int nV, int ns, const T* const* tau_c_h
   VSM_REQUIRE(varpi_c_h && p_c_h && path1, "exact_ss_path1: null argument");
   if (S == 0) return VSM_OK;
   hipStream_t st = as_stream(stream);
-  xs_image img;
+  packed_image img;
   const size_t o_t = img.add(tau_c_h, sizeof(T*) * (size_t)C * L), o_w = img.add(varpi_c_h, sizeof(T) * (size_t)C);
   const size_t o_p = img.add(p_c_h, sizeof(T) * (size_t)C * nV * ns), o_m = img.add(mu_v_h, sizeof(T) * (size_t)nV);
   unsigned char* d;
-  if ((rc = xs_upload(img, st, &d))) return rc;
+  if ((rc = upload_image(img, XS_SLOT, st, &d))) return rc;
   hipLaunchKernelGGL(k_xs_path1<T>, XS_GRID, S, L, C, nV, ns, (const T* const*)(d + o_t), (const T*)(d + o_w), (const T*)(d + o_p), I0,
                      mu0, (const T*)(d + o_m), path1);
   VSM_LAUNCH_CHECK("k_xs_path1");
@@ -313,10 +292,10 @@ static int xs_path2(int S, int L, int C, int nV, int ns, const T* const* tau_c_h
   VSM_REQUIRE(brdf && path2, "exact_ss_path2: null argument");
   if (S == 0) return VSM_OK;
   hipStream_t st = as_stream(stream);
-  xs_image img;
+  packed_image img;
   const size_t o_t = img.add(tau_c_h, sizeof(T*) * (size_t)C * L), o_m = img.add(mu_v_h, sizeof(T) * (size_t)nV);
   unsigned char* d;
-  if ((rc = xs_upload(img, st, &d))) return rc;
+  if ((rc = upload_image(img, XS_SLOT, st, &d))) return rc;
   hipLaunchKernelGGL(k_xs_path2<T>, XS_GRID, S, L, C, nV, ns, (const T* const*)(d + o_t), brdf, spectral != 0, I0, mu0,
                      (const T*)(d + o_m), path2);
   VSM_LAUNCH_CHECK("k_xs_path2");
@@ -336,14 +315,14 @@ static int xs_path34(int S, int L, int C, int nV, int nQ, const T* const* tau_c_
   for (int k = 0; k < nQ; ++k) VSM_REQUIRE(mu_nodes_h[k] > T(0), "exact_ss_path34: mu_nodes[%d] must be positive", k);
   if (S == 0) return VSM_OK;
   hipStream_t st = as_stream(stream);
-  xs_image img;
+  packed_image img;
   const size_t nb = sizeof(T) * (size_t)C * nV * nQ;
   const size_t o_t = img.add(tau_c_h, sizeof(T*) * (size_t)C * L), o_w = img.add(varpi_c_h, sizeof(T) * (size_t)C);
   const size_t o_3 = img.add(pbar3_c_h, path3 ? nb : 0), o_4 = img.add(pbar4_c_h, path4 ? nb : 0);
   const size_t o_n = img.add(mu_nodes_h, sizeof(T) * (size_t)nQ), o_q = img.add(w_h, sizeof(T) * (size_t)nQ);
   const size_t o_m = img.add(mu_v_h, sizeof(T) * (size_t)nV);
   unsigned char* d;
-  if ((rc = xs_upload(img, st, &d))) return rc;
+  if ((rc = upload_image(img, XS_SLOT, st, &d))) return rc;
   hipLaunchKernelGGL(k_xs_path34<T>, XS_GRID, S, L, C, nV, nQ, (const T* const*)(d + o_t), (const T*)(d + o_w), (const T*)(d + o_3),
                      (const T*)(d + o_4), (const T*)(d + o_n), (const T*)(d + o_q), albedo, I0, mu0, (const T*)(d + o_m), path3, path4);
   VSM_LAUNCH_CHECK("k_xs_path34");
@@ -363,11 +342,11 @@ static int xs_jac12(int S, int L, int C, int nV, int ns, const T* const* tau_c_h
   VSM_REQUIRE((!d1t || (varpi_c_h && p_c_h)) && (!d2t || brdf), "exact_ss_jac12: null argument");
   if (S == 0) return VSM_OK;
   hipStream_t st = as_stream(stream);
-  xs_image img;
+  packed_image img;
   const size_t o_t = img.add(tau_c_h, sizeof(T*) * (size_t)C * L), o_w = img.add(varpi_c_h, d1t ? sizeof(T) * (size_t)C : 0);
   const size_t o_p = img.add(p_c_h, d1t ? sizeof(T) * (size_t)C * nV * ns : 0), o_m = img.add(mu_v_h, sizeof(T) * (size_t)nV);
   unsigned char* d;
-  if ((rc = xs_upload(img, st, &d))) return rc;
+  if ((rc = upload_image(img, XS_SLOT, st, &d))) return rc;
   hipLaunchKernelGGL(k_xs_jac12<T>, XS_GRID, S, L, C, nV, ns, (const T* const*)(d + o_t), (const T*)(d + o_w), (const T*)(d + o_p), brdf,
                      spectral != 0, I0, mu0, (const T*)(d + o_m), d1t, d1w, d1p, d2t, d2r);
   VSM_LAUNCH_CHECK("k_xs_jac12");

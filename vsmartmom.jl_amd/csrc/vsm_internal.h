@@ -1,6 +1,10 @@
 // Typed (templated) mirrors of the C-ABI structs + declarations of the launchers
 // implemented in vsm_generic.hip / vsm_fused.hip and called from vsm_api.hip.
 #pragma once
+#include <string.h>
+
+#include <vector>
+
 #include "vsm_common.h"
 
 namespace vsm {
@@ -327,6 +331,19 @@ int strip128_interaction11_lin(int N, int S, const composite<ST>& c, const compo
 // different streams are independent".  Grow-only per key; a buffer that is outgrown is retired behind an event recorded on
 // its stream and freed only once that event has completed (never under running work).  nullptr + error set on failure.
 void* scratch(size_t bytes, int slot, hipStream_t st);
+// Small device tables of one call: a packed host image (entries 8-byte aligned; add() returns the entry's offset) and its ONE
+// stream-ordered copy into the scratch buffer of `slot`.  Pageable memory: the copy is synchronised, so the image may die with the
+// caller's frame.  Nothing the image holds is capped by it.
+struct packed_image {
+  std::vector<unsigned char> b;
+  size_t add(const void* p, size_t n) {
+    const size_t o = (b.size() + 7) & ~(size_t)7;
+    b.resize(o + n);
+    if (n) memcpy(b.data() + o, p, n);
+    return o;
+  }
+};
+int upload_image(const packed_image& img, int slot, hipStream_t st, unsigned char** dev);
 int* device_status();   // 4 zero-initialised device words of the current device (vsm_device_status); nullptr + error set on failure
 int release_scratch();   // current device: synchronise, free every scratch buffer
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-device attribute of a kernel: raise it once per (device, kernel).

@@ -11,10 +11,6 @@
 //                        tau[n0], tau[n1] and fscatt[n0] exp(-tau_sum[n0] / mu_0), the close branches by their limit partials
 // Lanes run along the spectral axis; a thread carries the running sources of SS_RB rows of its point in registers through all
 // layers.  Nothing here is N x N: of the phase matrices only the n_stokes SZA columns are read.
-#include <string.h>
-
-#include <vector>
-
 #include "vsm_common.h"
 #include "vsm_internal.h"
 
@@ -22,6 +18,9 @@ namespace vsm {
 
 constexpr int SS_TB = VSM_SS_BLOCK;   // spectral points (= threads) per workgroup: two waves
 constexpr int SS_RB = 4;              // rows per thread; more rows go to further workgroups along grid.y
+constexpr int SS_PC = 4;              // parameter slots a thread of the elastic derivative carries; further slots go along grid.z
+constexpr int SS_RPC = 2;             // parameter slots a thread of the Raman derivative carries: (12 + 2 SS_RPC) staged values per window
+                                      // point = 64 KB of LDS at FP64 with the maximal halo (the forward kernel's 12 values: 48 KB)
 constexpr int SS_SLOT = 5;            // library scratch slot of the device tables
 
 template <typename T>
@@ -29,12 +28,27 @@ struct ss_layer {
   const T *tau, *varpi, *tau_sum, *zpp, *zmp, *fscatt;
   long long zs;
 };
+template <typename T>
+struct ss_layer_lin {
+  const T *tau, *varpi, *tau_sum, *zpp, *zmp;
+  const T *tau_dot, *varpi_dot, *tau_sum_dot;   // [S, p_layer] each (tau_dot: of the layer's full tau)
+  const T* zdcoef;                              // [CT, p_layer, S] or null (Z_dot = 0)
+  long long zs;
+};
+template <typename T>
+struct ss_layer_rrs_lin {
+  const T *tau, *tau_sum, *fscatt;
+  const T *tau_dot, *tau_sum_dot, *fscatt_dot;   // [S, p_layer] each (tau_dot: of the layer's full tau)
+};
 
 template <typename T>
 struct ss_tol {
   static __device__ __forceinline__ T close() { return T(1e-8); }   // rt_close_tol (rt_helpers.jl:66-68)
 };
 
+// ---------------------------------------------------------------------------------------------------------------------
+// the pieces the four column kernels share
+// ---------------------------------------------------------------------------------------------------------------------
 // The rows a thread owns.  VIEW: item e = v + nV k of the viewing table (row row0[v] + k, weight w[e], output (s, k, v));
 // otherwise item e = stream row e of the full source vectors.
 template <typename T>
@@ -58,6 +72,106 @@ __device__ __forceinline__ ss_rows<T> ss_pick_rows(bool view, int N, int ns, int
   }
   return r;
 }
+// where item e of the viewing table goes in an output (S, n_stokes, nV), or in slot p of an output (P, S, n_stokes, nV)
+__device__ __forceinline__ long long ss_view_index(long long s, int ns, int nV, int e, int p = 0, long long S = 0) {
+  return (((long long)p * S + s) * ns + e / nV) * nV + e % nV;
+}
+
+template <typename T>
+struct ss_pair {
+  T p, m;   // the + and the - direction
+};
+// (Z F0) at one row: of the phase matrices Z++ / Z-+ only the n_stokes SZA columns are read.  beam: the point's F0, in registers
+// or in global memory (F0 + ns * n0).
+template <typename T>
+__device__ __forceinline__ ss_pair<T> ss_zf0(const T* zpp, const T* zmp, int N, int ns, int i_start, int row, const T* beam) {
+  T zp = 0, zm = 0;
+  for (int q = 0; q < ns; ++q) {
+    const long long zo = row + (long long)N * (i_start + q);
+    const T f = beam[q];
+    zp += zpp[zo] * f;
+    zm += zmp[zo] * f;
+  }
+  return {zp, zm};
+}
+
+// The elastic sources of one row in one layer: get_elem_rt_SFI! with dtau = tau, ndoubl = 0 (the statements of k_elemental_sfi,
+// vsm_generic.hip), times the beam's attenuation att.  LIN: with their partial derivatives in tau, varpi and (Z F0) (the
+// statements of k_elemental_sfi_lin, vsm_lin.hip); the forward kernel compiles none of them.
+template <typename T, bool LIN>
+struct ss_elastic {
+  T jp, jm;
+};
+template <typename T>
+struct ss_elastic<T, true> {
+  T jp, jm, jp_tau, jp_w, jp_Z, jm_tau, jm_w, jm_Z;
+};
+template <typename T, bool LIN>
+__device__ __forceinline__ ss_elastic<T, LIN> ss_elastic_src(bool sun, T wct02, T wv, ss_pair<T> z, T d, T mi, T ms, T att) {
+  ss_elastic<T, LIN> r;
+  if (sun) {
+    r.jp = wct02 * wv * z.p * (d / mi) * exp(-d / mi);
+    if constexpr (LIN) r.jp_tau = r.jp * (T(1) / d - T(1) / mi);
+  } else {
+    r.jp = wct02 * wv * z.p * (ms / (mi - ms)) * expdiff_neg<T>(d / mi, d / ms);
+    if constexpr (LIN) r.jp_tau = -wct02 * wv * z.p * (ms / (mi - ms)) * (exp(-d / mi) / mi - exp(-d / ms) / ms);
+  }
+  const T gm = ms / (mi + ms);
+  const T narg = -d * ((T(1) / mi) + (T(1) / ms));
+  r.jm = wct02 * wv * z.m * gm * (-expm1(narg));
+  if constexpr (LIN) {
+    r.jp_w = (wv == T(0)) ? T(0) : r.jp / wv;
+    r.jp_Z = (z.p == T(0)) ? T(0) : r.jp / z.p;
+    r.jm_tau = wct02 * wv * z.m * gm * exp(narg) * ((T(1) / mi) + (T(1) / ms));
+    r.jm_w = (wv == T(0)) ? T(0) : r.jm / wv;
+    r.jm_Z = (z.m == T(0)) ? T(0) : r.jm / z.m;
+    r.jp_tau *= att; r.jp_w *= att; r.jp_Z *= att;
+    r.jm_tau *= att; r.jm_w *= att; r.jm_Z *= att;
+  }
+  r.jp *= att;
+  r.jm *= att;
+  return r;
+}
+
+// What a (recipient, line) pair of the Raman columns reads of its donor n0 in one layer: d0 = tau[n0], x0 = d0 / mu0 as
+// e0 = exp(-x0) and a0 = expm1(-x0), g0 = fscatt[n0] exp(-tau_sum[n0] / mu0).  The fill values are those of a window point
+// outside the band, which no line reads.
+template <typename T>
+struct ss_donor {
+  T d0 = T(1), e0 = T(0), a0 = T(0), g0 = T(0);
+  static __device__ __forceinline__ ss_donor load(const ss_layer<T>& ly, long long n0, T ms) {
+    ss_donor r;
+    r.d0 = ly.tau[n0];
+    const T x0 = r.d0 / ms;
+    r.e0 = exp(-x0);
+    r.a0 = expm1(-x0);
+    r.g0 = ly.fscatt[n0] * exp(-ly.tau_sum[n0] / ms);
+    return r;
+  }
+};
+
+// The LDS window of a workgroup of the Raman columns: the points within `halo` of its SS_TB recipients.  Per point the donor
+// factors of the current layer -- formed once per (point, layer), not once per line --, per row of the thread Z_ie F0[:, n0] (layer
+// independent: staged once per workgroup) and, in the derivative kernel, the donor's derivatives:
+//   sd | se0 | sa0 | sg [W] each | szp | szm [SS_RB][W] | sdd | sgd [SS_RPC][W].
+// A line whose donor lies outside the window takes the same values from global memory.  The launchers take the byte count from
+// here and k_ss_column_rrs_lin its carve-up; k_ss_column_rrs carves the same layout by hand (through this struct it measures
+// 0.5 % slower).
+template <typename T, bool LIN>
+struct ss_window {
+  static constexpr int values = 4 + 2 * SS_RB + (LIN ? 2 * SS_RPC : 0);   // staged per window point
+  static constexpr size_t bytes(int halo) { return sizeof(T) * (size_t)values * (size_t)(SS_TB + 2 * halo); }
+  int W;
+  T *sd, *se0, *sa0, *sg, *szp, *szm, *sdd, *sgd;   // (sdd, sgd: LIN only)
+  long long w0;                                     // the window's first point
+  __device__ __forceinline__ ss_window(unsigned char* smem, int halo) {
+    W = SS_TB + 2 * halo;
+    sd = reinterpret_cast<T*>(smem), se0 = sd + W, sa0 = se0 + W, sg = sa0 + W;
+    szp = sg + W, szm = szp + SS_RB * W;
+    sdd = LIN ? szm + SS_RB * W : nullptr, sgd = LIN ? sdd + SS_RPC * W : nullptr;
+    w0 = (long long)blockIdx.x * SS_TB - halo;
+  }
+};
 
 // ---------------------------------------------------------------------------------------------------------------------
 // elastic column
@@ -90,27 +204,14 @@ __global__ __launch_bounds__(SS_TB) void k_ss_column(int N, int ns, int S, int L
       if (!rw.on[j]) continue;
       const int i = rw.i[j];
       const T mi = rw.mi[j];
-      T zp = 0, zm = 0;
-      for (int q = 0; q < ns; ++q) {
-        const long long zo = i + (long long)N * (i_start + q);
-        zp += zpp[zo] * f0[q];
-        zm += zmp[zo] * f0[q];
-      }
-      // get_elem_rt_SFI! with dtau = tau, ndoubl = 0 (the statements of k_elemental_sfi, vsm_generic.hip)
-      T jp;
-      if (i >= i_start && i < i_start + ns)
-        jp = wct02 * wv * zp * (d / mi) * exp(-d / mi);
-      else
-        jp = wct02 * wv * zp * (ms / (mi - ms)) * expdiff_neg<T>(d / mi, d / ms);
-      T jm = wct02 * wv * zm * (ms / (mi + ms)) * (-expm1(-d * ((T(1) / mi) + (T(1) / ms))));
-      jp *= att;
-      jm *= att;
+      const ss_elastic<T, false> e = ss_elastic_src<T, false>(i >= i_start && i < i_start + ns, wct02, wv,
+                                                              ss_zf0<T>(zpp, zmp, N, ns, i_start, i, f0), d, mi, ms, att);
       if (iz == 0) {   // rt_kernel_ss.jl:213-216: the TOA layer is copied
-        Jp[j] = jp;
-        Jm[j] = jm;
+        Jp[j] = e.jp;
+        Jm[j] = e.jm;
       } else {         // get_interaction_ss! (interaction_ss.jl:17-18)
-        Jp[j] = Jp[j] * exp(-d / mi) + jp;
-        Jm[j] = Jm[j] + jm * exp(-ts / mi);
+        Jp[j] = Jp[j] * exp(-d / mi) + e.jp;
+        Jm[j] = Jm[j] + e.jm * exp(-ts / mi);
       }
     }
   }
@@ -124,7 +225,7 @@ __global__ __launch_bounds__(SS_TB) void k_ss_column(int N, int ns, int S, int L
     Jm[j] = Jm[j] + sj_m[src] * exp(-tss / rw.mi[j]);
     if (VIEW) {
       const int e = blockIdx.y * SS_RB + j;
-      const long long dst = (s * ns + e / nV) * nV + e % nV;
+      const long long dst = ss_view_index(s, ns, nV, e);
       R[dst] += w[e] * Jm[j];
       Tt[dst] += w[e] * Jp[j];
     } else {
@@ -137,9 +238,6 @@ __global__ __launch_bounds__(SS_TB) void k_ss_column(int N, int ns, int S, int L
 // ---------------------------------------------------------------------------------------------------------------------
 // Raman column
 // ---------------------------------------------------------------------------------------------------------------------
-// What a (recipient, line) pair reads of its donor n0 in one layer: d0 = tau[n0], x0 = d0 / mu0 as e0 = exp(-x0) and
-// a0 = expm1(-x0), g0 = fscatt[n0] exp(-tau_sum[n0] / mu0) -- formed once per (point, layer) in LDS for the window of the
-// workgroup, not once per line -- and, per row of the thread, Z_ie F0[:, n0] (layer independent: staged once per workgroup).
 template <typename T>
 __global__ __launch_bounds__(SS_TB) void k_ss_column_rrs(int N, int ns, int S, int L, int K, int m, int i_mu0, int halo,
                                                          const ss_layer<T>* __restrict__ lay, const int* __restrict__ shift,
@@ -148,36 +246,23 @@ __global__ __launch_bounds__(SS_TB) void k_ss_column_rrs(int N, int ns, int S, i
                                                          const T* __restrict__ mu, int nV, const int* __restrict__ row0,
                                                          const T* __restrict__ w, T* ieR, T* ieT) {
   extern __shared__ __align__(16) unsigned char ss_smem[];
-  const int W = SS_TB + 2 * halo;
-  T* sd = reinterpret_cast<T*>(ss_smem);   // [W] each
-  T* se0 = sd + W;
-  T* sa0 = se0 + W;
-  T* sg = sa0 + W;
-  T* szp = sg + W;                         // [SS_RB][W]
-  T* szm = szp + SS_RB * W;
-  const long long b0 = (long long)blockIdx.x * SS_TB;
-  const long long w0 = b0 - halo;
-  const long long n1 = b0 + threadIdx.x;
+  const int W = SS_TB + 2 * halo;   // ss_window<T, false>, carved by hand (see there)
+  T *sd = reinterpret_cast<T*>(ss_smem), *se0 = sd + W, *sa0 = se0 + W, *sg = sa0 + W, *szp = sg + W, *szm = szp + SS_RB * W;
+  const long long b0 = (long long)blockIdx.x * SS_TB, w0 = b0 - halo, n1 = b0 + threadIdx.x;
   const bool live = n1 < S;
   const int i_start = ns * i_mu0;
   const ss_rows<T> rw = ss_pick_rows<T>(true, N, ns, nV, row0, mu, blockIdx.y * SS_RB);
   const T ms = mu[i_start];
   const T wct02 = (m == 0) ? T(0.5) : T(0.25);
-  for (int p = threadIdx.x; p < W; p += SS_TB) {
+  for (int p = threadIdx.x; p < W; p += SS_TB) {   // Z_ie F0 of the thread's rows at every window point, once per workgroup
     const long long n0 = w0 + p;
     const bool in = n0 >= 0 && n0 < S;
 #pragma unroll
     for (int j = 0; j < SS_RB; ++j) {
-      T zp = 0, zm = 0;
-      if (in && rw.on[j])
-        for (int q = 0; q < ns; ++q) {
-          const long long zo = rw.i[j] + (long long)N * (i_start + q);
-          const T f = F0[q + (long long)ns * n0];
-          zp += Zpp[zo] * f;
-          zm += Zmp[zo] * f;
-        }
-      szp[j * W + p] = zp;
-      szm[j * W + p] = zm;
+      ss_pair<T> z{T(0), T(0)};
+      if (in && rw.on[j]) z = ss_zf0<T>(Zpp, Zmp, N, ns, i_start, rw.i[j], F0 + (long long)ns * n0);
+      szp[j * W + p] = z.p;
+      szm[j * W + p] = z.m;
     }
   }
   T rm[SS_RB], Sp[SS_RB], Sm[SS_RB];
@@ -191,20 +276,11 @@ __global__ __launch_bounds__(SS_TB) void k_ss_column_rrs(int N, int ns, int S, i
   for (int iz = 0; iz < L; ++iz) {
     const ss_layer<T> ly = lay[iz];
     __syncthreads();   // the previous layer's readers are done (first pass: nothing to wait for but the Z F0 stage)
-    for (int p = threadIdx.x; p < W; p += SS_TB) {
+    for (int p = threadIdx.x; p < W; p += SS_TB) {   // the donor factors of this layer at every window point
       const long long n0 = w0 + p;
-      T d0 = T(1), e0 = T(0), a0 = T(0), g0 = T(0);
-      if (n0 >= 0 && n0 < S) {
-        d0 = ly.tau[n0];
-        const T x0 = d0 / ms;
-        e0 = exp(-x0);
-        a0 = expm1(-x0);
-        g0 = ly.fscatt[n0] * exp(-ly.tau_sum[n0] / ms);
-      }
-      sd[p] = d0;
-      se0[p] = e0;
-      sa0[p] = a0;
-      sg[p] = g0;
+      ss_donor<T> don;
+      if (n0 >= 0 && n0 < S) don = ss_donor<T>::load(ly, n0, ms);
+      sd[p] = don.d0, se0[p] = don.e0, sa0[p] = don.a0, sg[p] = don.g0;
     }
     __syncthreads();
     if (!live) continue;
@@ -225,39 +301,24 @@ __global__ __launch_bounds__(SS_TB) void k_ss_column_rrs(int N, int ns, int S, i
       const bool staged = p >= 0 && p < W;
       T d0, e0, a0, g0;
       if (staged) {
-        d0 = sd[p];
-        e0 = se0[p];
-        a0 = sa0[p];
-        g0 = sg[p];
+        d0 = sd[p], e0 = se0[p], a0 = sa0[p], g0 = sg[p];
       } else {   // a shift beyond the staged window: the same factors from global memory
-        d0 = ly.tau[n0];
-        const T x0g = d0 / ms;
-        e0 = exp(-x0g);
-        a0 = expm1(-x0g);
-        g0 = ly.fscatt[n0] * exp(-ly.tau_sum[n0] / ms);
+        const ss_donor<T> don = ss_donor<T>::load(ly, n0, ms);
+        d0 = don.d0, e0 = don.e0, a0 = don.a0, g0 = don.g0;
       }
       const T x0 = d0 / ms;
       const T ratio = d1 / d0;
 #pragma unroll
       for (int j = 0; j < SS_RB; ++j) {
         if (!rw.on[j]) continue;
-        T zp, zm;
-        if (staged) {
-          zp = szp[j * W + p];
-          zm = szm[j * W + p];
-        } else {
-          zp = zm = T(0);
-          for (int q = 0; q < ns; ++q) {
-            const long long zo = rw.i[j] + (long long)N * (i_start + q);
-            const T f = F0[q + (long long)ns * n0];
-            zp += Zpp[zo] * f;
-            zm += Zmp[zo] * f;
-          }
-        }
+        const ss_pair<T> z = staged ? ss_pair<T>{szp[j * W + p], szm[j * W + p]}
+                                           : ss_zf0<T>(Zpp, Zmp, N, ns, i_start, rw.i[j], F0 + (long long)ns * n0);
+        const T zp = z.p, zm = z.m;
         const T mi = rw.mi[j];
         // expdiff_neg(d1 / mu_i, d0 / mu_0) (rt_helpers.jl:32-40) from e1 = exp(-x1), e0 = exp(-x0): one expm1 is left
         const T xa = x1[j];
         const T ed = (xa == x0) ? T(0) : ((xa < x0) ? e1[j] * (-expm1(-(x0 - xa))) : -e0 * (-expm1(-(xa - x0))));
+        // The line source stays this formulation (not the G / H of ss_rrs_line below): rt_run_ss_rrs promises these bits
         T jp;
         if (sun[j]) {   // elemental_inelastic.jl:508-548 (mu_i = mu_0 on these rows)
           if (fabs(d0 - d1) > ss_tol<T>::close())
@@ -293,7 +354,7 @@ __global__ __launch_bounds__(SS_TB) void k_ss_column_rrs(int N, int ns, int S, i
   for (int j = 0; j < SS_RB; ++j) {
     if (!rw.on[j]) continue;
     const int e = blockIdx.y * SS_RB + j;
-    const long long dst = (n1 * ns + e / nV) * nV + e % nV;
+    const long long dst = ss_view_index(n1, ns, nV, e);
     ieR[dst] += w[e] * Sm[j];
     ieT[dst] += w[e] * Sp[j];
   }
@@ -302,19 +363,9 @@ __global__ __launch_bounds__(SS_TB) void k_ss_column_rrs(int N, int ns, int S, i
 // ---------------------------------------------------------------------------------------------------------------------
 // elastic column, linearized
 // ---------------------------------------------------------------------------------------------------------------------
-constexpr int SS_PC = 4;   // parameter slots a thread carries; further slots go to further workgroups along grid.z
-
-template <typename T>
-struct ss_layer_lin {
-  const T *tau, *varpi, *tau_sum, *zpp, *zmp;
-  const T *tau_dot, *varpi_dot, *tau_sum_dot;   // [S, p_layer] each (tau_dot: of the layer's full tau)
-  const T* zdcoef;                              // [CT, p_layer, S] or null (Z_dot = 0)
-  long long zs;
-};
-
 // The derivative of k_ss_column<T, true> for the slots [p_lo + SS_PC blockIdx.z, +SS_PC) below p_hi.  Per layer the forward
-// factors of the thread's rows are formed again (they are cheap), the slot loop applies the chain rule of get_elem_rt_SFI_fused!
-// (the statements of k_elemental_sfi_lin, vsm_lin.hip) and the derivative of get_interaction_ss!, taken on J0+ BEFORE its update:
+// factors of the thread's rows are formed again (they are cheap: ss_elastic_src with its partials), the slot loop applies the
+// chain rule of get_elem_rt_SFI_fused! and the derivative of get_interaction_ss!, taken on J0+ BEFORE its update:
 //   J0+' = (J0+' - J0+ tau' / mu_i) exp(-tau / mu_i) + j0+',    J0-' += (j0-' - j0- tau_sum' / mu_i) exp(-tau_sum / mu_i).
 // Z_dot F0 at a row is sum_c zdcoef[c, p, s] (Zc[c] F0)_row over the CT component blocks of the moment, for the first p_zdot slots
 // (the aerosols'; the gases' coefficients are exact zeros and are not read): no Z_dot array exists.  ZD = false: no layer has one.
@@ -332,6 +383,7 @@ __global__ __launch_bounds__(SS_TB) void k_ss_column_lin(int N, int ns, int S, i
   if (s >= S) return;
   const int i_start = ns * i_mu0;
   const int p0 = p_lo + (int)blockIdx.z * SS_PC;
+  const ss_rows<T> rw = ss_pick_rows<T>(true, N, ns, nV, row0, mu, blockIdx.y * SS_RB);
   const T ms = mu[i_start];
   const T wct02 = (m == 0) ? T(0.5) : T(0.25);
   const long long NN = (long long)N * N;
@@ -363,35 +415,11 @@ __global__ __launch_bounds__(SS_TB) void k_ss_column_lin(int N, int ns, int S, i
     }
 #pragma unroll
     for (int j = 0; j < SS_RB; ++j) {
-      const int e = blockIdx.y * SS_RB + j;   // item e = v + nV k of the viewing table (ss_pick_rows, VIEW form)
-      if (e >= nV * ns) continue;
-      const int i = row0[e % nV] + e / nV;
+      if (!rw.on[j]) continue;
+      const int i = rw.i[j];
       const T mi = mu[i];
-      T zp = 0, zm = 0;
-      for (int q = 0; q < ns; ++q) {
-        const long long zo = i + (long long)N * (i_start + q);
-        zp += zpp[zo] * f0[q];
-        zm += zmp[zo] * f0[q];
-      }
-      // forward sources and their partial derivatives (k_elemental_sfi_lin with dtau = tau, ndoubl = 0)
-      T jp, jp_tau;
-      if (i >= i_start && i < i_start + ns) {
-        jp = wct02 * wv * zp * (d / mi) * exp(-d / mi);
-        jp_tau = jp * (T(1) / d - T(1) / mi);
-      } else {
-        jp = wct02 * wv * zp * (ms / (mi - ms)) * expdiff_neg<T>(d / mi, d / ms);
-        jp_tau = -wct02 * wv * zp * (ms / (mi - ms)) * (exp(-d / mi) / mi - exp(-d / ms) / ms);
-      }
-      T jp_w = (wv == T(0)) ? T(0) : jp / wv;
-      T jp_Z = (zp == T(0)) ? T(0) : jp / zp;
-      const T gm = ms / (mi + ms);
-      const T arg = d * ((T(1) / mi) + (T(1) / ms));
-      T jm = wct02 * wv * zm * gm * (-expm1(-arg));
-      T jm_tau = wct02 * wv * zm * gm * exp(-arg) * ((T(1) / mi) + (T(1) / ms));
-      T jm_w = (wv == T(0)) ? T(0) : jm / wv;
-      T jm_Z = (zm == T(0)) ? T(0) : jm / zm;
-      jp *= att; jp_tau *= att; jp_w *= att; jp_Z *= att;
-      jm *= att; jm_tau *= att; jm_w *= att; jm_Z *= att;
+      const ss_elastic<T, true> e = ss_elastic_src<T, true>(i >= i_start && i < i_start + ns, wct02, wv,
+                                                            ss_zf0<T>(zpp, zmp, N, ns, i_start, i, f0), d, mi, ms, att);
       const T ed = exp(-d / mi), es = exp(-ts / mi);
       // (Z_dot F0) at this row for the slots of the chunk that have one (the first p_zdot: the aerosols'; gas slots have none):
       // the component products (Zc[c] F0)_row do not depend on the slot, so c is the outer loop
@@ -402,18 +430,13 @@ __global__ __launch_bounds__(SS_TB) void k_ss_column_lin(int N, int ns, int S, i
         if (ly.zdcoef && p0 < p_zdot) {
           const T* cf = ly.zdcoef + (long long)CT * (long long)p_layer * s;
           for (int c = 0; c < CT; ++c) {
-            T cp = 0, cm = 0;
-            for (int q = 0; q < ns; ++q) {
-              const long long zo = c * NN + i + (long long)N * (i_start + q);
-              cp += Zc_pp[zo] * f0[q];
-              cm += Zc_mp[zo] * f0[q];
-            }
+            const ss_pair<T> zc = ss_zf0<T>(Zc_pp + c * NN, Zc_mp + c * NN, N, ns, i_start, i, f0);
 #pragma unroll
             for (int k = 0; k < SS_PC; ++k) {
               const int p = p0 + k;
               const T a = (p < p_hi && p < p_zdot) ? cf[c + (long long)CT * p] : T(0);
-              zpd[k] += a * cp;
-              zmd[k] += a * cm;
+              zpd[k] += a * zc.p;
+              zmd[k] += a * zc.m;
             }
           }
         }
@@ -423,17 +446,17 @@ __global__ __launch_bounds__(SS_TB) void k_ss_column_lin(int N, int ns, int S, i
         const int p = p0 + k;
         if (p >= p_hi || p >= p_layer) continue;
         const T beam = -tsd[k] / ms;
-        const T ajp = jp_tau * td[k] + jp_w * wd[k] + jp_Z * zpd[k] + jp * beam;
-        const T ajm = jm_tau * td[k] + jm_w * wd[k] + jm_Z * zmd[k] + jm * beam;
+        const T ajp = e.jp_tau * td[k] + e.jp_w * wd[k] + e.jp_Z * zpd[k] + e.jp * beam;
+        const T ajm = e.jm_tau * td[k] + e.jm_w * wd[k] + e.jm_Z * zmd[k] + e.jm * beam;
         if (iz == 0) {   // rt_kernel_ss.jl:213-216: the TOA layer is copied
           Dp[j][k] = ajp;
           Dm[j][k] = ajm;
         } else {         // get_interaction_ss! (interaction_ss.jl:17-18), differentiated
           Dp[j][k] = (Dp[j][k] - Jp[j] * td[k] / mi) * ed + ajp;
-          Dm[j][k] = Dm[j][k] + (ajm - jm * tsd[k] / mi) * es;
+          Dm[j][k] = Dm[j][k] + (ajm - e.jm * tsd[k] / mi) * es;
         }
       }
-      Jp[j] = (iz == 0) ? jp : Jp[j] * ed + jp;
+      Jp[j] = (iz == 0) ? e.jp : Jp[j] * ed + e.jp;
     }
   }
   // the surface layer: the same update with tau = 0 and tau_sum = tau_sum_all[:, Nz + 1]; j0-+' of all P slots from the linearized
@@ -442,11 +465,10 @@ __global__ __launch_bounds__(SS_TB) void k_ss_column_lin(int N, int ns, int S, i
   const T tss = ts_surf[s];
 #pragma unroll
   for (int j = 0; j < SS_RB; ++j) {
+    if (!rw.on[j]) continue;
     const int e = blockIdx.y * SS_RB + j;
-    if (e >= nV * ns) continue;
-    const int i = row0[e % nV] + e / nV;
-    const long long src = s * N + i;
-    const T mi = mu[i];
+    const long long src = s * N + rw.i[j];
+    const T mi = mu[rw.i[j]];
     const T es = exp(-tss / mi);
     const T bp = sj_p ? sj_p[src] : T(0), bm = sj_m[src];
 #pragma unroll
@@ -457,7 +479,7 @@ __global__ __launch_bounds__(SS_TB) void k_ss_column_lin(int N, int ns, int S, i
       const long long sp = (long long)N * S * p + src;
       const T dp = Dp[j][k] + (sjd_p[sp] - bp * tsd / ms);
       const T dm = Dm[j][k] + (sjd_m[sp] - bm * tsd / mi) * es;
-      const long long dst = ((((long long)p * S + s) * ns + e / nV) * nV) + e % nV;
+      const long long dst = ss_view_index(s, ns, nV, e, p, S);
       Rd[dst] += w[e] * dm;
       Td[dst] += w[e] * dp;
     }
@@ -467,15 +489,6 @@ __global__ __launch_bounds__(SS_TB) void k_ss_column_lin(int N, int ns, int S, i
 // ---------------------------------------------------------------------------------------------------------------------
 // Raman column, linearized
 // ---------------------------------------------------------------------------------------------------------------------
-constexpr int SS_RPC = 2;   // parameter slots a thread of the Raman derivative carries: (12 + 2 SS_RPC) staged values per window point
-                            // = 64 KB of LDS at FP64 with the maximal halo (the forward kernel's 12 values: 48 KB)
-
-template <typename T>
-struct ss_layer_rrs_lin {
-  const T *tau, *tau_sum, *fscatt;
-  const T *tau_dot, *tau_sum_dot, *fscatt_dot;   // [S, p_layer] each (tau_dot: of the layer's full tau)
-};
-
 // The partial derivatives of the two line sources of k_ss_column_rrs in (d0, d1) = (tau[n0], tau[n1]).  With u = d0 / mu_0,
 // v = d1 / mu_i, psi(x) = (1 - e^-x) / x and phi(u, v) = (e^-v - e^-u) / (u - v) the forward statements are
 //   j+ = c+ g0 G,  G = (e^-v - e^-u) / (mu_i / mu_0 - d1 / d0) = (d0 / mu_i) phi(u, v)
@@ -547,8 +560,8 @@ __device__ __forceinline__ ss_rrs_partials<T> ss_rrs_line(bool sun, T d0, T d1, 
 // The derivative of k_ss_column_rrs for the slots [p_lo + SS_RPC blockIdx.z, +SS_RPC) below min(p_hi, p_layer).  The run's
 // parameters reach a (recipient n1, line, donor n0) source through d0, d1 and g0 = fscatt[n0] exp(-tau_sum[n0] / mu_0) only
 // (varpi_ie, Z_ie, F0, the layers' varpi and the surface do not enter), so per slot the donor side is TWO more staged values per
-// (window point, layer): d0' and g0' = fscatt'[n0] exp(-tau_sum[n0] / mu_0) - g0 tau_sum'[n0] / mu_0.  The forward factors are
-// formed again; the interaction is differentiated on the running line sums before their update:
+// (window point, layer): d0' and g0' = fscatt' att - g0 tau_sum' / mu_0.  The forward factors are formed again; the interaction is differentiated on
+// the running line sums before their update:
 //   S+' = (S+' - S+ tau'[n1] / mu_i) e1 + s+',    S-' += (s-' - s- tau_sum'[n1] / mu_i) exp(-tau_sum[n1] / mu_i).
 template <typename T>
 __global__ __launch_bounds__(SS_TB) void k_ss_column_rrs_lin(int N, int ns, int S, int L, int K, int m, int i_mu0, int halo,
@@ -560,18 +573,10 @@ __global__ __launch_bounds__(SS_TB) void k_ss_column_rrs_lin(int N, int ns, int 
                                                              const int* __restrict__ row0, const T* __restrict__ w, T* ieRd,
                                                              T* ieTd) {
   extern __shared__ __align__(16) unsigned char ss_smem[];
-  const int W = SS_TB + 2 * halo;
-  T* sd = reinterpret_cast<T*>(ss_smem);   // [W] each
-  T* se0 = sd + W;
-  T* sa0 = se0 + W;
-  T* sg = sa0 + W;
-  T* szp = sg + W;                         // [SS_RB][W]
-  T* szm = szp + SS_RB * W;
-  T* sdd = szm + SS_RB * W;                // [SS_RPC][W]: d0'
-  T* sgd = sdd + SS_RPC * W;               // [SS_RPC][W]: g0'
-  const long long b0 = (long long)blockIdx.x * SS_TB;
-  const long long w0 = b0 - halo;
-  const long long n1 = b0 + threadIdx.x;
+  const ss_window<T, true> win(ss_smem, halo);
+  const int W = win.W;
+  T *sd = win.sd, *se0 = win.se0, *sa0 = win.sa0, *sg = win.sg, *szp = win.szp, *szm = win.szm, *sdd = win.sdd, *sgd = win.sgd;
+  const long long w0 = win.w0, n1 = (long long)blockIdx.x * SS_TB + threadIdx.x;   // n1: the thread's recipient
   const bool live = n1 < S;
   const int i_start = ns * i_mu0;
   const int p0 = p_lo + (int)blockIdx.z * SS_RPC;
@@ -579,7 +584,7 @@ __global__ __launch_bounds__(SS_TB) void k_ss_column_rrs_lin(int N, int ns, int 
   const ss_rows<T> rw = ss_pick_rows<T>(true, N, ns, nV, row0, mu, blockIdx.y * SS_RB);
   const T ms = mu[i_start];
   const T wct02 = (m == 0) ? T(0.5) : T(0.25);
-  for (int p = threadIdx.x; p < W; p += SS_TB) {
+  for (int p = threadIdx.x; p < W; p += SS_TB) {   // Z_ie F0 of the thread's rows at every window point, once per workgroup
     const long long n0 = w0 + p;
     const bool in = n0 >= 0 && n0 < S;
 #pragma unroll
@@ -611,7 +616,7 @@ __global__ __launch_bounds__(SS_TB) void k_ss_column_rrs_lin(int N, int ns, int 
   for (int iz = 0; iz < L; ++iz) {
     const ss_layer_rrs_lin<T> ly = lay[iz];
     __syncthreads();   // the previous layer's readers are done (first pass: nothing to wait for but the Z F0 stage)
-    for (int p = threadIdx.x; p < W; p += SS_TB) {
+    for (int p = threadIdx.x; p < W; p += SS_TB) {   // the donor factors of this layer and their derivatives at every window point
       const long long n0 = w0 + p;
       T d0 = T(1), e0 = T(0), a0 = T(0), g0 = T(0), dd[SS_RPC], gd[SS_RPC];
 #pragma unroll
@@ -705,13 +710,8 @@ __global__ __launch_bounds__(SS_TB) void k_ss_column_rrs_lin(int N, int ns, int 
           zp = szp[j * W + p];
           zm = szm[j * W + p];
         } else {
-          zp = zm = T(0);
-          for (int q = 0; q < ns; ++q) {
-            const long long zo = rw.i[j] + (long long)N * (i_start + q);
-            const T f = F0[q + (long long)ns * n0];
-            zp += Zpp[zo] * f;
-            zm += Zmp[zo] * f;
-          }
+          const ss_pair<T> z = ss_zf0<T>(Zpp, Zmp, N, ns, i_start, rw.i[j], F0 + (long long)ns * n0);
+          zp = z.p, zm = z.m;
         }
         const ss_rrs_partials<T> f = ss_rrs_line<T>(sun[j], d0, d1, ratio, x0, e0, a0, x1[j], e1[j], a1[j], imi[j], ims, rm[j]);
         const T cp = wct02 * wl * zp, cm = wct02 * wl * zm;
@@ -753,7 +753,7 @@ __global__ __launch_bounds__(SS_TB) void k_ss_column_rrs_lin(int N, int ns, int 
     for (int k = 0; k < SS_RPC; ++k) {
       const int p = p0 + k;
       if (p >= p_end) continue;
-      const long long dst = ((((long long)p * S + n1) * ns + e / nV) * nV) + e % nV;
+      const long long dst = ss_view_index(n1, ns, nV, e, p, S);
       ieRd[dst] += w[e] * Dm[j][k];
       ieTd[dst] += w[e] * Dp[j][k];
     }
@@ -763,34 +763,6 @@ __global__ __launch_bounds__(SS_TB) void k_ss_column_rrs_lin(int N, int ns, int 
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
-// Device tables of one call in the library's scratch: ss_layer[L] | w[nV n_stokes] | row0[nV].  One stream-ordered copy of a
-// packed host image (pageable memory: staged by the runtime before the call returns), so L and nV are not capped.
-template <typename T, typename LAY = ss_layer<T>>
-struct ss_tables {
-  const LAY* lay;
-  const T* w;
-  const int* row0;
-};
-template <typename T, typename LAY>
-static int ss_upload(int L, const std::vector<LAY>& lay, int ns, int nV, const int* row0_h, const T* w_h, hipStream_t st,
-                     ss_tables<T, LAY>* out) {
-  const size_t o_w = sizeof(LAY) * (size_t)L;
-  const size_t o_r = o_w + sizeof(T) * (size_t)nV * ns;
-  const size_t total = o_r + sizeof(int) * (size_t)nV;
-  std::vector<unsigned char> img(total);
-  memcpy(img.data(), lay.data(), o_w);
-  memcpy(img.data() + o_w, w_h, o_r - o_w);
-  memcpy(img.data() + o_r, row0_h, total - o_r);
-  unsigned char* dev = static_cast<unsigned char*>(scratch(total, SS_SLOT, st));
-  if (!dev) return VSM_ERR_HIP;
-  VSM_HIP(hipMemcpyAsync(dev, img.data(), total, hipMemcpyHostToDevice, st));
-  VSM_HIP(hipStreamSynchronize(st));   // `img` dies with this frame: the copy (a few hundred bytes, once per moment) must have left it
-  out->lay = reinterpret_cast<const LAY*>(dev);
-  out->w = reinterpret_cast<const T*>(dev + o_w);
-  out->row0 = reinterpret_cast<const int*>(dev + o_r);
-  return VSM_OK;
-}
-
 template <typename T, typename Q>
 static int ss_check_common(const char* who, const Q* q, int S, int L, int nV, const int* row0_h, const T* w_h) {
   VSM_REQUIRE(q && q->mu && q->wt, "%s: null quad", who);
@@ -804,6 +776,59 @@ static int ss_check_common(const char* who, const Q* q, int S, int L, int nV, co
     VSM_REQUIRE(row0_h[v] >= 0 && row0_h[v] + q->n_stokes <= q->N, "%s: row0[%d] = %d out of range", who, v, row0_h[v]);
   return VSM_OK;
 }
+// The per-layer tables a call requires (what: "layer" or "derivative"): each is there (iz < 0; a call's first checks) or has its
+// entry of layer iz (where the call builds that layer's struct, so that the checks keep their order).
+template <typename T>
+using ss_tabs = std::initializer_list<const T* const*>;
+template <typename T>
+static int ss_check_layers(const char* who, const char* what, ss_tabs<T> tabs, int iz = -1) {
+  for (const T* const* t : tabs) {
+    if (iz < 0) VSM_REQUIRE(t, "%s: null %s table", who, what);
+    else VSM_REQUIRE(t[iz], "%s: null entry in %s table %d", who, what, iz);
+  }
+  return VSM_OK;
+}
+// the slot arguments of a derivative column whose threads carry PC slots each (grid.z: the chunks of [p_lo, p_hi)); p_zdot: the
+// elastic column's
+static int ss_check_slots(const char* who, int P, int p_layer, int p_lo, int p_hi, int PC, int p_zdot = 0) {
+  VSM_REQUIRE(P >= 1 && p_layer >= 0 && p_layer <= P, "%s: P >= 1 and 0 <= p_layer <= P required (P = %d, p_layer = %d)", who, P,
+              p_layer);
+  VSM_REQUIRE(p_zdot >= 0 && p_zdot <= p_layer, "%s: 0 <= p_zdot <= p_layer required (p_zdot = %d)", who, p_zdot);
+  VSM_REQUIRE(p_lo >= 0 && p_lo < p_hi && p_hi <= P, "%s: slot range [%d, %d) outside [0, %d)", who, p_lo, p_hi, P);
+  VSM_REQUIRE((p_hi - p_lo + PC - 1) / PC <= 65535, "%s: too many slots", who);
+  return VSM_OK;
+}
+// What a launch needs beside the caller's arrays: the device tables of the call -- its layer structs, w[nV n_stokes], row0[nV],
+// one packed_image in the scratch of SS_SLOT --, grid.x and grid.y over the `items` rows of a point and, for the Raman columns
+// (halo >= 0, `bytes` of their ss_window), the clamped halo with the LDS bytes of its window.
+static_assert(ss_window<double, true>::bytes(VSM_SS_MAX_HALO) <= 65536, "k_ss_column_rrs_lin: a workgroup stays within 64 KB of LDS");
+template <typename T, typename LAY>
+struct ss_launch {
+  hipStream_t st;
+  const LAY* lay;   // the three device tables
+  const T* w;
+  const int* row0;
+  unsigned gx, gv;
+  int halo;
+  size_t lds;
+  int prepare(const std::vector<LAY>& lay_h, int S, int items, int nV, const int* row0_h, const T* w_h, void* stream, int halo_ = -1,
+              size_t (*bytes)(int) = nullptr) {
+    st = as_stream(stream);
+    packed_image img;
+    const size_t o_l = img.add(lay_h.data(), sizeof(LAY) * lay_h.size()), o_w = img.add(w_h, sizeof(T) * (size_t)items);
+    const size_t o_r = img.add(row0_h, sizeof(int) * (size_t)nV);
+    unsigned char* d;
+    if (int rc = upload_image(img, SS_SLOT, st, &d)) return rc;
+    lay = reinterpret_cast<const LAY*>(d + o_l);
+    w = reinterpret_cast<const T*>(d + o_w);
+    row0 = reinterpret_cast<const int*>(d + o_r);
+    gx = (unsigned)((S + SS_TB - 1) / SS_TB);
+    gv = (unsigned)((items + SS_RB - 1) / SS_RB);
+    halo = halo_ > VSM_SS_MAX_HALO ? VSM_SS_MAX_HALO : halo_;
+    lds = bytes ? bytes(halo) : 0;
+    return VSM_OK;
+  }
+};
 
 template <typename T, typename Q>
 static int ss_column(const Q* q, int S, int L, int m, const T* const* tau_h, const T* const* varpi_h, const T* const* tau_sum_h,
@@ -811,30 +836,27 @@ static int ss_column(const Q* q, int S, int L, int m, const T* const* tau_h, con
                      const T* ts_surf, int nV, const int* row0_h, const T* w_h, T* R, T* Tt, T* J0_m, T* J0_p, void* stream) {
   int rc;
   if ((rc = ss_check_common<T>("ss_column", q, S, L, nV, row0_h, w_h))) return rc;
-  VSM_REQUIRE(tau_h && varpi_h && tau_sum_h && Zpp_h && Zmp_h && zs_h, "ss_column: null layer table");
+  const ss_tabs<T> tabs = {tau_h, varpi_h, tau_sum_h, Zpp_h, Zmp_h};
+  if ((rc = ss_check_layers<T>("ss_column", "layer", tabs))) return rc;
+  VSM_REQUIRE(zs_h, "ss_column: null layer table");
   VSM_REQUIRE(F0 && sj_m && ts_surf && R && Tt, "ss_column: null argument");
   VSM_REQUIRE((J0_m == nullptr) == (J0_p == nullptr), "ss_column: J0_m and J0_p go together");
   VSM_REQUIRE(m >= 0, "ss_column: m >= 0");
-  const long long NN = (long long)q->N * q->N;
   std::vector<ss_layer<T>> lay((size_t)L);
   for (int iz = 0; iz < L; ++iz) {
-    VSM_REQUIRE(tau_h[iz] && varpi_h[iz] && tau_sum_h[iz] && Zpp_h[iz] && Zmp_h[iz], "ss_column: null entry in layer table %d", iz);
-    VSM_REQUIRE(zs_h[iz] == 0 || zs_h[iz] == NN, "ss_column: z_stride[%d] must be 0 or N*N", iz);
+    if ((rc = ss_check_layers<T>("ss_column", "layer", tabs, iz))) return rc;
+    VSM_REQUIRE(zs_h[iz] == 0 || zs_h[iz] == (long long)q->N * q->N, "ss_column: z_stride[%d] must be 0 or N*N", iz);
     lay[iz] = ss_layer<T>{tau_h[iz], varpi_h[iz], tau_sum_h[iz], Zpp_h[iz], Zmp_h[iz], nullptr, zs_h[iz]};
   }
   if (S == 0) return VSM_OK;
-  hipStream_t st = as_stream(stream);
-  ss_tables<T> t;
-  if ((rc = ss_upload<T, ss_layer<T>>(L, lay, q->n_stokes, nV, row0_h, w_h, st, &t))) return rc;
-  const unsigned gx = (unsigned)((S + SS_TB - 1) / SS_TB);
-  const unsigned gv = (unsigned)((nV * q->n_stokes + SS_RB - 1) / SS_RB);
-  hipLaunchKernelGGL((k_ss_column<T, true>), dim3(gx, gv), dim3(SS_TB), 0, st, q->N, q->n_stokes, S, L, m, q->i_mu0, t.lay, F0,
-                     sj_m, sj_p, ts_surf, q->mu, nV, t.row0, t.w, R, Tt);
+  ss_launch<T, ss_layer<T>> g;
+  if ((rc = g.prepare(lay, S, nV * q->n_stokes, nV, row0_h, w_h, stream))) return rc;
+  hipLaunchKernelGGL((k_ss_column<T, true>), dim3(g.gx, g.gv), dim3(SS_TB), 0, g.st, q->N, q->n_stokes, S, L, m, q->i_mu0, g.lay, F0,
+                     sj_m, sj_p, ts_surf, q->mu, nV, g.row0, g.w, R, Tt);
   VSM_LAUNCH_CHECK("k_ss_column");
   if (J0_m) {
-    const unsigned gf = (unsigned)((q->N + SS_RB - 1) / SS_RB);
-    hipLaunchKernelGGL((k_ss_column<T, false>), dim3(gx, gf), dim3(SS_TB), 0, st, q->N, q->n_stokes, S, L, m, q->i_mu0, t.lay,
-                       F0, sj_m, sj_p, ts_surf, q->mu, nV, t.row0, t.w, J0_m, J0_p);
+    hipLaunchKernelGGL((k_ss_column<T, false>), dim3(g.gx, (unsigned)((q->N + SS_RB - 1) / SS_RB)), dim3(SS_TB), 0, g.st, q->N, q->n_stokes, S,
+                       L, m, q->i_mu0, g.lay, F0, sj_m, sj_p, ts_surf, q->mu, nV, g.row0, g.w, J0_m, J0_p);
     VSM_LAUNCH_CHECK("k_ss_column (all streams)");
   }
   return VSM_OK;
@@ -849,24 +871,20 @@ static int ss_column_lin(const Q* q, int S, int L, int m, int P, int p_layer, in
                          const T* tsd_surf, int nV, const int* row0_h, const T* w_h, T* Rd, T* Td, void* stream) {
   int rc;
   if ((rc = ss_check_common<T>("ss_column_lin", q, S, L, nV, row0_h, w_h))) return rc;
-  VSM_REQUIRE(P >= 1 && p_layer >= 0 && p_layer <= P, "ss_column_lin: P >= 1 and 0 <= p_layer <= P required (P = %d, p_layer = %d)",
-              P, p_layer);
-  VSM_REQUIRE(p_zdot >= 0 && p_zdot <= p_layer, "ss_column_lin: 0 <= p_zdot <= p_layer required (p_zdot = %d)", p_zdot);
-  VSM_REQUIRE(p_lo >= 0 && p_lo < p_hi && p_hi <= P, "ss_column_lin: slot range [%d, %d) outside [0, %d)", p_lo, p_hi, P);
-  VSM_REQUIRE((p_hi - p_lo + SS_PC - 1) / SS_PC <= 65535, "ss_column_lin: too many slots");
-  VSM_REQUIRE(tau_h && varpi_h && tau_sum_h && Zpp_h && Zmp_h && zs_h, "ss_column_lin: null layer table");
-  VSM_REQUIRE(p_layer == 0 || (tau_dot_h && varpi_dot_h && tau_sum_dot_h && tsd_surf), "ss_column_lin: null derivative table");
+  if ((rc = ss_check_slots("ss_column_lin", P, p_layer, p_lo, p_hi, SS_PC, p_zdot))) return rc;
+  const ss_tabs<T> tabs = {tau_h, varpi_h, tau_sum_h, Zpp_h, Zmp_h}, dots = {tau_dot_h, varpi_dot_h, tau_sum_dot_h};
+  if ((rc = ss_check_layers<T>("ss_column_lin", "layer", tabs))) return rc;
+  VSM_REQUIRE(zs_h, "ss_column_lin: null layer table");
+  if (p_layer && (rc = ss_check_layers<T>("ss_column_lin", "derivative", dots))) return rc;
+  VSM_REQUIRE(p_layer == 0 || tsd_surf, "ss_column_lin: null derivative table");
   VSM_REQUIRE(F0 && sj_m && sjd_m && sjd_p && ts_surf && Rd && Td, "ss_column_lin: null argument");
   VSM_REQUIRE(m >= 0 && CT >= 0, "ss_column_lin: m >= 0 and CT >= 0");
-  const long long NN = (long long)q->N * q->N;
   std::vector<ss_layer_lin<T>> lay((size_t)L);
   bool any_zd = false;
   for (int iz = 0; iz < L; ++iz) {
-    VSM_REQUIRE(tau_h[iz] && varpi_h[iz] && tau_sum_h[iz] && Zpp_h[iz] && Zmp_h[iz], "ss_column_lin: null entry in layer table %d",
-                iz);
-    VSM_REQUIRE(p_layer == 0 || (tau_dot_h[iz] && varpi_dot_h[iz] && tau_sum_dot_h[iz]),
-                "ss_column_lin: null entry in derivative table %d", iz);
-    VSM_REQUIRE(zs_h[iz] == 0 || zs_h[iz] == NN, "ss_column_lin: z_stride[%d] must be 0 or N*N", iz);
+    if ((rc = ss_check_layers<T>("ss_column_lin", "layer", tabs, iz))) return rc;
+    if (p_layer && (rc = ss_check_layers<T>("ss_column_lin", "derivative", dots, iz))) return rc;
+    VSM_REQUIRE(zs_h[iz] == 0 || zs_h[iz] == (long long)q->N * q->N, "ss_column_lin: z_stride[%d] must be 0 or N*N", iz);
     const T* zc = (zdcoef_h && p_zdot > 0) ? zdcoef_h[iz] : nullptr;
     any_zd = any_zd || zc;
     VSM_REQUIRE(!zc || (CT >= 1 && Zc_pp && Zc_mp), "ss_column_lin: Z_dot coefficients without component blocks (layer %d)", iz);
@@ -875,20 +893,17 @@ static int ss_column_lin(const Q* q, int S, int L, int m, int P, int p_layer, in
                               p_layer ? tau_sum_dot_h[iz] : nullptr, zc, zs_h[iz]};
   }
   if (S == 0) return VSM_OK;
-  hipStream_t st = as_stream(stream);
-  ss_tables<T, ss_layer_lin<T>> t;
-  if ((rc = ss_upload<T, ss_layer_lin<T>>(L, lay, q->n_stokes, nV, row0_h, w_h, st, &t))) return rc;
-  const unsigned gx = (unsigned)((S + SS_TB - 1) / SS_TB);
-  const unsigned gv = (unsigned)((nV * q->n_stokes + SS_RB - 1) / SS_RB);
+  ss_launch<T, ss_layer_lin<T>> g;
+  if ((rc = g.prepare(lay, S, nV * q->n_stokes, nV, row0_h, w_h, stream))) return rc;
   const unsigned gp = (unsigned)((p_hi - p_lo + SS_PC - 1) / SS_PC);
   if (any_zd)
-    hipLaunchKernelGGL((k_ss_column_lin<T, true>), dim3(gx, gv, gp), dim3(SS_TB), 0, st, q->N, q->n_stokes, S, L, m, q->i_mu0, P,
-                       p_layer, p_zdot, p_lo, p_hi, t.lay, CT, Zc_pp, Zc_mp, F0, sj_m, sj_p, sjd_m, sjd_p, ts_surf, tsd_surf, q->mu,
-                       nV, t.row0, t.w, Rd, Td);
+    hipLaunchKernelGGL((k_ss_column_lin<T, true>), dim3(g.gx, g.gv, gp), dim3(SS_TB), 0, g.st, q->N, q->n_stokes, S, L, m, q->i_mu0, P,
+                       p_layer, p_zdot, p_lo, p_hi, g.lay, CT, Zc_pp, Zc_mp, F0, sj_m, sj_p, sjd_m, sjd_p, ts_surf, tsd_surf, q->mu,
+                       nV, g.row0, g.w, Rd, Td);
   else
-    hipLaunchKernelGGL((k_ss_column_lin<T, false>), dim3(gx, gv, gp), dim3(SS_TB), 0, st, q->N, q->n_stokes, S, L, m, q->i_mu0, P,
-                       p_layer, 0, p_lo, p_hi, t.lay, 0, (const T*)nullptr, (const T*)nullptr, F0, sj_m, sj_p, sjd_m, sjd_p, ts_surf,
-                       tsd_surf, q->mu, nV, t.row0, t.w, Rd, Td);
+    hipLaunchKernelGGL((k_ss_column_lin<T, false>), dim3(g.gx, g.gv, gp), dim3(SS_TB), 0, g.st, q->N, q->n_stokes, S, L, m, q->i_mu0, P,
+                       p_layer, 0, p_lo, p_hi, g.lay, 0, (const T*)nullptr, (const T*)nullptr, F0, sj_m, sj_p, sjd_m, sjd_p, ts_surf,
+                       tsd_surf, q->mu, nV, g.row0, g.w, Rd, Td);
   VSM_LAUNCH_CHECK("k_ss_column_lin");
   return VSM_OK;
 }
@@ -900,25 +915,21 @@ static int ss_column_rrs(const Q* q, int S, int L, int m, int K, const T* const*
   int rc;
   if ((rc = ss_check_common<T>("ss_column_rrs", q, S, L, nV, row0_h, w_h))) return rc;
   VSM_REQUIRE(K >= 0, "ss_column_rrs: K >= 0 required (K = %d)", K);
-  VSM_REQUIRE(tau_h && tau_sum_h && fscatt_h, "ss_column_rrs: null layer table");
+  const ss_tabs<T> tabs = {tau_h, tau_sum_h, fscatt_h};
+  if ((rc = ss_check_layers<T>("ss_column_rrs", "layer", tabs))) return rc;
   VSM_REQUIRE(F0 && ieR && ieT && Zpp_ie && Zmp_ie, "ss_column_rrs: null argument");
   VSM_REQUIRE(K == 0 || (shift && varpi_ie), "ss_column_rrs: null line table");
   VSM_REQUIRE(m >= 0 && halo >= 0, "ss_column_rrs: m >= 0 and halo >= 0");
   std::vector<ss_layer<T>> lay((size_t)L);
   for (int iz = 0; iz < L; ++iz) {
-    VSM_REQUIRE(tau_h[iz] && tau_sum_h[iz] && fscatt_h[iz], "ss_column_rrs: null entry in layer table %d", iz);
+    if ((rc = ss_check_layers<T>("ss_column_rrs", "layer", tabs, iz))) return rc;
     lay[iz] = ss_layer<T>{tau_h[iz], nullptr, tau_sum_h[iz], nullptr, nullptr, fscatt_h[iz], 0};
   }
   if (S == 0 || K == 0) return VSM_OK;
-  if (halo > VSM_SS_MAX_HALO) halo = VSM_SS_MAX_HALO;
-  hipStream_t st = as_stream(stream);
-  ss_tables<T> t;
-  if ((rc = ss_upload<T, ss_layer<T>>(L, lay, q->n_stokes, nV, row0_h, w_h, st, &t))) return rc;
-  const unsigned gx = (unsigned)((S + SS_TB - 1) / SS_TB);
-  const unsigned gv = (unsigned)((nV * q->n_stokes + SS_RB - 1) / SS_RB);
-  const size_t lds = sizeof(T) * (size_t)(4 + 2 * SS_RB) * (size_t)(SS_TB + 2 * halo);
-  hipLaunchKernelGGL(k_ss_column_rrs<T>, dim3(gx, gv), dim3(SS_TB), lds, st, q->N, q->n_stokes, S, L, K, m, q->i_mu0, halo, t.lay,
-                     shift, varpi_ie, Zpp_ie, Zmp_ie, F0, q->mu, nV, t.row0, t.w, ieR, ieT);
+  ss_launch<T, ss_layer<T>> g;
+  if ((rc = g.prepare(lay, S, nV * q->n_stokes, nV, row0_h, w_h, stream, halo, ss_window<T, false>::bytes))) return rc;
+  hipLaunchKernelGGL(k_ss_column_rrs<T>, dim3(g.gx, g.gv), dim3(SS_TB), g.lds, g.st, q->N, q->n_stokes, S, L, K, m, q->i_mu0, g.halo,
+                     g.lay, shift, varpi_ie, Zpp_ie, Zmp_ie, F0, q->mu, nV, g.row0, g.w, ieR, ieT);
   VSM_LAUNCH_CHECK("k_ss_column_rrs");
   return VSM_OK;
 }
@@ -932,37 +943,27 @@ static int ss_column_rrs_lin(const Q* q, int S, int L, int m, int K, int P, int 
   int rc;
   if ((rc = ss_check_common<T>("ss_column_rrs_lin", q, S, L, nV, row0_h, w_h))) return rc;
   VSM_REQUIRE(K >= 0, "ss_column_rrs_lin: K >= 0 required (K = %d)", K);
-  VSM_REQUIRE(P >= 1 && p_layer >= 0 && p_layer <= P,
-              "ss_column_rrs_lin: P >= 1 and 0 <= p_layer <= P required (P = %d, p_layer = %d)", P, p_layer);
-  VSM_REQUIRE(p_lo >= 0 && p_lo < p_hi && p_hi <= P, "ss_column_rrs_lin: slot range [%d, %d) outside [0, %d)", p_lo, p_hi, P);
-  VSM_REQUIRE((p_hi - p_lo + SS_RPC - 1) / SS_RPC <= 65535, "ss_column_rrs_lin: too many slots");
-  VSM_REQUIRE(tau_h && tau_sum_h && fscatt_h, "ss_column_rrs_lin: null layer table");
-  VSM_REQUIRE(p_layer == 0 || (tau_dot_h && tau_sum_dot_h && fscatt_dot_h), "ss_column_rrs_lin: null derivative table");
+  if ((rc = ss_check_slots("ss_column_rrs_lin", P, p_layer, p_lo, p_hi, SS_RPC))) return rc;
+  const ss_tabs<T> tabs = {tau_h, tau_sum_h, fscatt_h}, dots = {tau_dot_h, tau_sum_dot_h, fscatt_dot_h};
+  if ((rc = ss_check_layers<T>("ss_column_rrs_lin", "layer", tabs))) return rc;
+  if (p_layer && (rc = ss_check_layers<T>("ss_column_rrs_lin", "derivative", dots))) return rc;
   VSM_REQUIRE(F0 && ieRd && ieTd && Zpp_ie && Zmp_ie, "ss_column_rrs_lin: null argument");
   VSM_REQUIRE(K == 0 || (shift && varpi_ie), "ss_column_rrs_lin: null line table");
   VSM_REQUIRE(m >= 0 && halo >= 0, "ss_column_rrs_lin: m >= 0 and halo >= 0");
   std::vector<ss_layer_rrs_lin<T>> lay((size_t)L);
   for (int iz = 0; iz < L; ++iz) {
-    VSM_REQUIRE(tau_h[iz] && tau_sum_h[iz] && fscatt_h[iz], "ss_column_rrs_lin: null entry in layer table %d", iz);
-    VSM_REQUIRE(p_layer == 0 || (tau_dot_h[iz] && tau_sum_dot_h[iz] && fscatt_dot_h[iz]),
-                "ss_column_rrs_lin: null entry in derivative table %d", iz);
+    if ((rc = ss_check_layers<T>("ss_column_rrs_lin", "layer", tabs, iz))) return rc;
+    if (p_layer && (rc = ss_check_layers<T>("ss_column_rrs_lin", "derivative", dots, iz))) return rc;
     lay[iz] = ss_layer_rrs_lin<T>{tau_h[iz], tau_sum_h[iz], fscatt_h[iz], p_layer ? tau_dot_h[iz] : nullptr,
                                   p_layer ? tau_sum_dot_h[iz] : nullptr, p_layer ? fscatt_dot_h[iz] : nullptr};
   }
   const int p_end = p_hi < p_layer ? p_hi : p_layer;   // the surface's slots (and any later ones) are exact zeros: not touched
   if (S == 0 || K == 0 || p_lo >= p_end) return VSM_OK;
-  if (halo > VSM_SS_MAX_HALO) halo = VSM_SS_MAX_HALO;
-  hipStream_t st = as_stream(stream);
-  ss_tables<T, ss_layer_rrs_lin<T>> t;
-  if ((rc = ss_upload<T, ss_layer_rrs_lin<T>>(L, lay, q->n_stokes, nV, row0_h, w_h, st, &t))) return rc;
-  const unsigned gx = (unsigned)((S + SS_TB - 1) / SS_TB);
-  const unsigned gv = (unsigned)((nV * q->n_stokes + SS_RB - 1) / SS_RB);
+  ss_launch<T, ss_layer_rrs_lin<T>> g;
+  if ((rc = g.prepare(lay, S, nV * q->n_stokes, nV, row0_h, w_h, stream, halo, ss_window<T, true>::bytes))) return rc;
   const unsigned gp = (unsigned)((p_end - p_lo + SS_RPC - 1) / SS_RPC);
-  const size_t lds = sizeof(T) * (size_t)(4 + 2 * SS_RB + 2 * SS_RPC) * (size_t)(SS_TB + 2 * halo);
-  static_assert(sizeof(double) * (4 + 2 * SS_RB + 2 * SS_RPC) * (VSM_SS_BLOCK + 2 * VSM_SS_MAX_HALO) <= 65536,
-                "k_ss_column_rrs_lin: a workgroup stays within 64 KB of LDS");
-  hipLaunchKernelGGL(k_ss_column_rrs_lin<T>, dim3(gx, gv, gp), dim3(SS_TB), lds, st, q->N, q->n_stokes, S, L, K, m, q->i_mu0, halo,
-                     p_layer, p_lo, p_hi, t.lay, shift, varpi_ie, Zpp_ie, Zmp_ie, F0, q->mu, nV, t.row0, t.w, ieRd, ieTd);
+  hipLaunchKernelGGL(k_ss_column_rrs_lin<T>, dim3(g.gx, g.gv, gp), dim3(SS_TB), g.lds, g.st, q->N, q->n_stokes, S, L, K, m, q->i_mu0,
+                     g.halo, p_layer, p_lo, p_hi, g.lay, shift, varpi_ie, Zpp_ie, Zmp_ie, F0, q->mu, nV, g.row0, g.w, ieRd, ieTd);
   VSM_LAUNCH_CHECK("k_ss_column_rrs_lin");
   return VSM_OK;
 }
