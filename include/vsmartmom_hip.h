@@ -803,6 +803,41 @@ int vsm_run_view_rows(vsm_run* run, int nrows, const int* rows_h);
  * viewing rows that fall into it as local rows (local_rows[VSM_RUN_VIEW_MAX]; *nv = 0: the block carries no row of T--) */
 int vsm_run_view_block(const vsm_run* run, int block, int* im, int* n, int* nv, int* local_rows);
 int vsm_run_destroy(vsm_run* run);
+/* The surface step of a run.  A surface layer with r-+ = r+- = 0, t++ = t-- = I and j0+- = 0 leaves everything that is read below
+ * it as it was under interaction!(::ScatteringInterface_11): J0-' = J0- + T-- G (...) 0, J0+' = I I (J0+ + R+- 0), R' = R + (...) 0,
+ * T' = I G T with G = I -- every added term an exact zero, so the values are those of the full step (only the sign of a zero can
+ * differ).  vsm_surface_layer_flags(kind, m, has_surface_source) tells from the surface type and the Fourier moment alone -- nothing
+ * is read from the device -- whether a builder's layer is such a layer (VSM_SURFACE_LAYER_IDENTITY): only the scalar Lambertian
+ * builder (vsm_lambertian_surface_*) at m >= 1 in a scene without a surface source (SurfaceSIF, SurfaceEmission).  The spectral
+ * Lambertian builders (t = 0 at m >= 1) and the BRDF builders never are.
+ *   vsm_run_export_moment  = vsm_run_export for moment `im` (0 .. nm - 1) of the run alone (comp: ONE composite).
+ *   vsm_run_export_sources = of that, J0+ and J0- (with vsm_run_export's viewing-row / NaN rule) alone: no matrix is read or
+ *                            written, comp's matrix pointers may be NULL.
+ *   vsm_run_surface        = the surface step of moment `im`.  identity == 0: vsm_run_export_moment, then vsm_interaction(iface, N,
+ *                            S, comp, added_surface, work): the kernels and arguments of the two calls.  identity != 0 (the caller
+ *                            vouches for VSM_SURFACE_LAYER_IDENTITY; added_surface may be NULL): no interaction;
+ *                            vsm_run_export_sources when matrices == 0 (the caller reads J0+- alone), vsm_run_export_moment else.
+ * None of them synchronises with the host; all can be captured into a graph, like vsm_run_export.
+ * vsm_run_guard_once(run), before the run's first layer step and any import: the caller's coupling masks come from
+ * vsm_stokes_coupling on the very Z arrays it hands to vsm_run_layer, so the guard of the masks (VSM_DEVSTAT_MASK) runs on the first
+ * layer step alone.  The contract is the caller's: Z arrays overwritten in place after the masks were taken are outside it, and a
+ * coupling that appears that way below the first layer is dropped without a flag.  vsm_run_import ends it (every later layer step is
+ * guarded again).
+ * vsm_run_counters: launches of the run so far, counts_h[4] = { full exports (one per moment), source-only exports, surface
+ * interactions, guard launches }. */
+enum { VSM_SURFACE_LAMBERTIAN_SCALAR = 0, VSM_SURFACE_LAMBERTIAN_SPECTRAL = 1, VSM_SURFACE_BRDF = 2 };
+enum { VSM_SURFACE_LAYER_IDENTITY = 1 };
+unsigned vsm_surface_layer_flags(int kind, int m, int has_surface_source);
+int vsm_run_export_moment_f64(vsm_run* run, int im, const vsm_composite_f64* comp, void* stream);
+int vsm_run_export_moment_f32(vsm_run* run, int im, const vsm_composite_f32* comp, void* stream);
+int vsm_run_export_sources_f64(vsm_run* run, int im, const vsm_composite_f64* comp, void* stream);
+int vsm_run_export_sources_f32(vsm_run* run, int im, const vsm_composite_f32* comp, void* stream);
+int vsm_run_surface_f64(vsm_run* run, int im, int iface, const vsm_added_f64* added_surface, int identity, int matrices,
+                        const vsm_composite_f64* comp, double* work, void* stream);
+int vsm_run_surface_f32(vsm_run* run, int im, int iface, const vsm_added_f32* added_surface, int identity, int matrices,
+                        const vsm_composite_f32* comp, float* work, void* stream);
+int vsm_run_guard_once(vsm_run* run);
+int vsm_run_counters(const vsm_run* run, int* counts_h);
 int vsm_stokes_coupling_f64(int N, int n_stokes, int nblocks, const double* Zpp, const double* Zmp, int* mask_d, void* stream);
 int vsm_stokes_coupling_f32(int N, int n_stokes, int nblocks, const float* Zpp, const float* Zmp, int* mask_d, void* stream);
 

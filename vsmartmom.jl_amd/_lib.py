@@ -172,6 +172,12 @@ _SIGS = {
     "vsm_run_view_rows": (_I, [_P, _I, _P]),
     "vsm_run_view_block": (_I, [_P, _I, _P, _P, _P, _P]),
     "vsm_run_destroy": (_I, [_P]),
+    "vsm_surface_layer_flags": (C.c_uint, [_I, _I, _I]),
+    "vsm_run_export_moment_{T}": (_I, [_P, _I, _P, _P]),
+    "vsm_run_export_sources_{T}": (_I, [_P, _I, _P, _P]),
+    "vsm_run_surface_{T}": (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _P]),
+    "vsm_run_guard_once": (_I, [_P]),
+    "vsm_run_counters": (_I, [_P, _P]),
     "vsm_stokes_coupling_{T}": (_I, [_I, _I, _I, _P, _P, _P, _P]),
     "vsm_level_radiance_work_elems": (_SZ, [_I, _I]),
     "vsm_level_radiance_{T}": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _LL, _P, _P, _P, _P, _P, _P, _P]),

@@ -48,6 +48,9 @@ NATIVE_VIEW_ROWS = True  # ... and carries T-- / J0- in the rows of the VZA node
 VIEW_ROWS_MAX = 16      # VSM_RUN_VIEW_MAX of the library: with more viewing rows the run stays a plain sources-only run
 NATIVE_ZW_TAIL = True   # Scene's native runs skip the k-steps of the zero-weight VZA / SZA streams in every product (vsm_run_zw_tail =
 #                         VSM_RUN_ZW_TAIL: those columns are zero off the diagonal in every matrix of the layer steps).  False: dense
+NATIVE_IDENTITY_SURFACE = True  # Scene.run: a surface layer that is the identity (vsm_surface_layer_flags: scalar Lambertian, m >= 1, no
+#                         surface source) takes no surface interaction, and without `streams` only J0+- leave the native run
+#                         (vsm_run_surface).  False: the full export and interaction for every moment
 NATIVE_DROPIN = True    # rt_kernel_ keeps the CompositeLayer it is handed in the kernels' native layout between its calls (a per-
 #                         composite registry, exported lazily: the path of the reference's own driver order, rt_run.jl:383-453)
 REFERENCE_ORDER = False  # True: Scene.run walks `for m` outside `for iz`, one rt_kernel_ call per (m, iz) on ONE CompositeLayer --
@@ -192,12 +195,41 @@ class AddedLayer:
 def _composite_field(name):
     """A CompositeLayer array as a property.  Read: bring the array up to date first (materialize).  Assign: the caller rebinds the
     array -- CompositeLayer is a mutable struct in the reference -- after the native copy, if any, has been written out."""
+    vector = name in ("J0_p", "J0_m")
+
     def fget(self):
+        if vector and self._vectors_current:     # (a skipped surface step exported J0+- alone: they are the composite's)
+            return self._arr[name]
         return self.materialize()._arr[name]
 
     def fset(self, value):
         self.materialize()._arr[name] = value
     return property(fget, fset)
+
+
+RUN_COUNTERS = ("exports_full", "exports_src", "surface_interactions", "guard_launches")   # vsm_run_counters, in its order
+
+
+class RunRef:
+    """A vsm_run shared by the composites that still live in it (one per Fourier moment of the run; the walk itself holds a reference
+    too): destroyed when the last one lets go, its launch counters (vsm_run_counters) added to `sink` first.  `keep`: what the run
+    points at and must outlive it (its workspace, the quadrature)."""
+
+    def __init__(self, run, sink=None, keep=None, refs: int = 1):
+        self.run, self.sink, self.keep, self.refs = run, sink, keep, refs
+
+    def release(self):
+        self.refs -= 1
+        if self.refs == 0 and self.run is not None:
+            run, self.run = self.run, None
+            L = _lib.lib()
+            if self.sink is not None:
+                counts = (C.c_int * 4)()
+                if L.vsm_run_counters(run, counts) == 0:
+                    for k, v in zip(RUN_COUNTERS, counts):
+                        self.sink[k] = self.sink.get(k, 0) + int(v)
+            L.vsm_run_destroy(run)
+            self.keep = None
 
 
 class CompositeLayer:
@@ -210,6 +242,8 @@ class CompositeLayer:
         self._sources_only = False  # set by Scene.run for its own walk: the native copy may be a sources-only run (R-+, T++ NaN)
         self._view_rows = None      # ... and with it the rows of T-- / J0- that walk reads (view_rows_of): a view-row run
         self._native_ws = None    # its workspace (grow-only, reused from moment to moment)
+        self._vectors_current = False  # J0+- of _arr are up to date although the native copy is still open (a skipped surface step)
+        self._counters = None     # dict that receives the launch counters of the runs behind this composite (Scene.run_counters)
         # the reference's arrays; read through the properties below, which bring them up to date first
         self._arr = dict(R_mp=z(), R_pm=z(), T_pp=z(), T_mm=z(), J0_p=torch.zeros((nSpec, N), dtype=dt, device=dev),
                          J0_m=torch.zeros((nSpec, N), dtype=dt, device=dev))
@@ -225,13 +259,31 @@ class CompositeLayer:
         slot = self._native
         if slot is None:
             return self
-        self._native = None
+        self._native, self._vectors_current = None, False
         try:
-            cc = (_lib.vsm_composite * 1)(self._cstruct_raw())
-            _lib.call("vsm_run_export", self.dtype, slot.run, cc, _stream_ptr())
+            cc = self._cstruct_raw()
+            _lib.call("vsm_run_export_moment", self.dtype, slot.run, slot.im, C.byref(cc), _stream_ptr())
         finally:
-            _lib.lib().vsm_run_destroy(slot.run)
+            slot.ref.release()
         return self
+
+    def surface_step(self, iface: str, added_surface: "AddedLayer", identity: bool, matrices: bool, work) -> bool:
+        """The surface interaction of a composite that is still in native layout (vsm_run_surface); False: it is not -- the caller
+        takes interaction_.  identity: the surface layer is known to be the identity (vsm_surface_layer_flags) -- no interaction,
+        and unless the caller reads the matrices (`matrices`) only J0+- are exported: the native copy stays open behind them, and a
+        later read of a matrix exports the whole composite (materialize).  Else the export and the interaction of today."""
+        slot = self._native
+        if slot is None:
+            return False
+        a, cc = added_surface.cstruct(), self._cstruct_raw()
+        _lib.call("vsm_run_surface", self.dtype, slot.run, slot.im, IFACE[iface], C.byref(a), int(identity), int(matrices),
+                  C.byref(cc), _ptr(work), _stream_ptr())
+        if identity and not matrices:
+            self._vectors_current = True
+        else:
+            self._native = None
+            slot.ref.release()
+        return True
 
     def snapshot_top(self):
         """Clones of (R+-, J0+) of a composite in the middle of its walk, without disturbing the walk: a composite that rt_kernel_
@@ -239,8 +291,8 @@ class CompositeLayer:
         run)."""
         slot = self._native
         if slot is not None:
-            cc = (_lib.vsm_composite * 1)(self._cstruct_raw())
-            _lib.call("vsm_run_export", self.dtype, slot.run, cc, _stream_ptr())
+            cc = self._cstruct_raw()
+            _lib.call("vsm_run_export_moment", self.dtype, slot.run, slot.im, C.byref(cc), _stream_ptr())
             a = self._arr
         else:
             a = self.materialize()._arr
@@ -248,9 +300,9 @@ class CompositeLayer:
 
     def drop_native(self):
         """Forget the native copy without exporting it (a TOA layer overwrites the composite)."""
-        slot, self._native = self._native, None
+        slot, self._native, self._vectors_current = self._native, None, False
         if slot is not None:
-            _lib.lib().vsm_run_destroy(slot.run)
+            slot.ref.release()
 
     def _cstruct_raw(self):
         a = self._arr
@@ -260,6 +312,11 @@ class CompositeLayer:
     def cstruct(self):
         self.materialize()
         return self._cstruct_raw()
+
+    def cstruct_sources(self):
+        """cstruct() for a consumer that reads J0+- alone (interaction_hdrf_): after a skipped surface step they are current while
+        the matrices are still in the native run -- no export then."""
+        return self._cstruct_raw() if self._vectors_current else self.cstruct()
 
     def __del__(self):
         try:
@@ -467,11 +524,22 @@ def reflectance(surf, dq: DeviceQuad, m: int, arch, FT, deriv: bool = False):
     return rho, drho
 
 
+SURFACE_LAMBERTIAN_SCALAR, SURFACE_LAMBERTIAN_SPECTRAL, SURFACE_BRDF = 0, 1, 2   # VSM_SURFACE_* kinds of vsm_surface_layer_flags
+SURFACE_LAYER_IDENTITY = 1                                                   # VSM_SURFACE_LAYER_IDENTITY
+
+
+def surface_layer_flags(kind: int, m: int, has_surface_source: bool = False) -> int:
+    """vsm_surface_layer_flags: what the layer of a surface builder is known to be from the surface type and the moment alone (a
+    host rule; nothing is read from the device).  SURFACE_LAYER_IDENTITY: scalar Lambertian, m >= 1, no surface source."""
+    return int(_lib.lib().vsm_surface_layer_flags(int(kind), int(m), 1 if has_surface_source else 0))
+
+
 def create_surface_layer_(surface, added_surface: AddedLayer, m: int, dq: DeviceQuad, tau_sum: torch.Tensor, rho=None,
-                          arch=None, FT=None):
+                          arch=None, FT=None, has_surface_source: bool = False) -> int:
     """create_surface_layer!: LambertianSurfaceScalar (lambertian_surface.jl:41-95; `surface` may be the bare albedo) or a
     BRDF surface through its Fourier reflectance block (rpv_surface.jl:51-97; CoxMunkSurface: coxmunk_surface.jl:381-460).
-    `rho` = a precomputed reflectance(surface, pol, qp_mu, m) block (Scene caches one per moment)."""
+    `rho` = a precomputed reflectance(surface, pol, qp_mu, m) block (Scene caches one per moment).  Returns the layer's flags
+    (surface_layer_flags; has_surface_source: the caller's scene has a SurfaceSIF / SurfaceEmission source)."""
     q, a = dq.cstruct(), added_surface.cstruct()
     if isinstance(surface, (H.LambertianSurfaceLegendre, H.LambertianSurfaceSpline)):
         # lambertian_surface.jl:97-213: `rho` = the per-point albedo [nSpec] (device), one r-+ block per spectral point
@@ -479,7 +547,7 @@ def create_surface_layer_(surface, added_surface: AddedLayer, m: int, dq: Device
             raise _lib.VSMError("spectral Lambertian surfaces need a per-point surface AddedLayer and their albedo spectrum")
         _lib.call("vsm_lambertian_surface_spectral", added_surface.dtype, C.byref(q), added_surface.nSpec, m, _ptr(rho),
                   _ptr(tau_sum), C.byref(a), _stream_ptr())
-        return
+        return surface_layer_flags(SURFACE_LAMBERTIAN_SPECTRAL, m, has_surface_source)
     if not added_surface.shared:
         raise _lib.VSMError("surface AddedLayer must be allocated with shared=True")
     if isinstance(surface, H.LambertianSurfaceScalar):
@@ -488,13 +556,13 @@ def create_surface_layer_(surface, added_surface: AddedLayer, m: int, dq: Device
         alb = C.c_double(surface) if added_surface.dtype == torch.float64 else C.c_float(surface)
         _lib.call("vsm_lambertian_surface", added_surface.dtype, C.byref(q), added_surface.nSpec, m, alb, _ptr(tau_sum),
                   C.byref(a), _stream_ptr())
-        return
+        return surface_layer_flags(SURFACE_LAMBERTIAN_SCALAR, m, has_surface_source)
     if isinstance(surface, BRDF_SURFACES):
         if rho is None:
             rho, _ = reflectance(surface, dq, m, arch, FT)
         _lib.call("vsm_brdf_surface", added_surface.dtype, C.byref(q), added_surface.nSpec, m, _ptr(rho), _ptr(tau_sum),
                   C.byref(a), _stream_ptr())
-        return
+        return surface_layer_flags(SURFACE_BRDF, m, has_surface_source)
     raise _lib.VSMError("surface %r is not built in this backend (LambertianSurfaceScalar / Legendre / Spline, CoxMunkSurface, "
                         "rpvSurfaceScalar, RossLiSurfaceScalar)"
                         % (surface,))
@@ -600,7 +668,7 @@ def interaction_hdrf_(pol, comp: CompositeLayer, added_surface: AddedLayer, m: i
                       hdr_J: torch.Tensor, hdr: torch.Tensor, bhr_uw: torch.Tensor, bhr_dw: torch.Tensor):
     """interaction_hdrf! + postprocessing_vza_hdrf! (CoreKernel/interaction_hdrf.jl:4-42, tools/postprocessing_vza.jl:103-115):
     hdr (S, n, nV) += w * (r-+_surf J0+ + j0-_surf)[rows(vza)]; bhr_uw / bhr_dw (S, n) written for m == 0."""
-    q, c, a = dq.cstruct(), comp.cstruct(), added_surface.cstruct()
+    q, c, a = dq.cstruct(), comp.cstruct_sources(), added_surface.cstruct()   # (the kernel reads J0+ of the composite alone)
     _lib.call("vsm_interaction_hdrf", comp.dtype, C.byref(q), comp.nSpec, m, C.byref(c), C.byref(a), _ptr(hdr_J), _ptr(bhr_uw),
               _ptr(bhr_dw), _stream_ptr())
     row0, w = _vza_rows_weights(pol, vza, vaz, qp, m, weight, comp.dtype)
@@ -625,6 +693,8 @@ class NativeSlot:
     m: int
     coupling: int          # the run's Stokes coupling mask (vsm_run_create)
     grp_of: List[int]      # block of each Stokes component under that mask
+    ref: RunRef = None     # the run's owner: released when the composite leaves the run
+    im: int = 0            # index of this composite's moment in the run (a run of Scene's own walk holds several)
 
 
 def stokes_groups(n_stokes: int, coupling: int) -> List[int]:
@@ -718,7 +788,7 @@ def _native_open(comp: CompositeLayer, dq: DeviceQuad, m: int, mask: int, import
         except Exception:
             L.vsm_run_destroy(run)
             raise
-    comp._native = NativeSlot(run, int(m), int(mask), stokes_groups(ns, mask))
+    comp._native = NativeSlot(run, int(m), int(mask), stokes_groups(ns, mask), RunRef(run, comp._counters))
     return True
 
 
@@ -1108,6 +1178,8 @@ class Scene:
         if self.S == 0:          # a rank that owns no spectral point (world > nSpec): nothing to launch
             return self.R_SFI, self.T_SFI
         self.added.j0_p.zero_()  # a fresh make_added_layer: zero_added_noscat! never writes j0+ (rt_helpers.jl:174-180)
+        self._drop_lazy()
+        self.__dict__.setdefault("_run_counts", {}).clear()
         # Fourier moments are independent until post-processing (rt_run.jl:383): groups of up to MOMENT_BATCH moments walk the
         # layers together, a scattering "11" / TOA layer step being ONE call for the group (vsm_layer_forward_multi: one launch
         # with three times the workgroups where the strip kernel takes the shape), each moment on a CompositeLayer of its own
@@ -1127,18 +1199,25 @@ class Scene:
         if getattr(self, "_view_rows", None) is None:      # (the quadrature and the VZAs are the scene's: computed once)
             self._view_rows = view_rows_of(pol, model.vza, self.qp)
         view_rows = self._view_rows if streams is None else None
+        has_surface_source = self.sif is not None or self.surface_B is not None
         with self._walk_composites(nb, walk_src and REFERENCE_ORDER, view_rows):
             for g0 in range(0, len(self.moments), nb):
                 group = self.moments[g0:g0 + nb]
                 comps = self._composites[:len(group)]
                 self._walk_layers(group, comps, [k for k in range(len(group)) if (g0 + k) in native], sources_only=streams is None,
-                                  view_rows=view_rows, trace=trace, keep_added=has_noscat)
+                                  view_rows=view_rows, trace=trace, keep_added=has_noscat, keep_native=True)
                 for mom, comp in zip(group, comps):
                     m = mom["m"]
                     weight = float(fourier_weight(FT, m))
-                    create_surface_layer_(model.surface, self.added_surface, m, self.dq, mom["tau_sum_surface"], rho=mom["rho"])
-                    surface_source_contribute_(self, model.surface, self.added_surface, m)
-                    interaction_(mom["iface_surface"], comp, self.added_surface, work=self.work)
+                    flags = create_surface_layer_(model.surface, self.added_surface, m, self.dq, mom["tau_sum_surface"], rho=mom["rho"],
+                                                  has_surface_source=has_surface_source)
+                    if surface_source_contribute_(self, model.surface, self.added_surface, m):
+                        flags &= ~SURFACE_LAYER_IDENTITY
+                    # a composite still in native layout (the native walk, the drop-in walk) takes the surface step there: an identity
+                    # surface layer leaves it as it is -- no interaction, and without `streams` nothing but J0+- is read below
+                    identity = bool(flags & SURFACE_LAYER_IDENTITY) and NATIVE_IDENTITY_SURFACE and mom["iface_surface"] == "11"
+                    if not comp.surface_step(mom["iface_surface"], self.added_surface, identity, streams is not None, self.work):
+                        interaction_(mom["iface_surface"], comp, self.added_surface, work=self.work)
                     if self.compute_hdrf:
                         interaction_hdrf_(pol, comp, self.added_surface, m, self.dq, model.vza, model.vaz, self.qp, weight,
                                           self.hdr_J, self.hdr, self.bhr_uw, self.bhr_dw)
@@ -1157,6 +1236,25 @@ class Scene:
                                  self.moments[-1]["tau_sum_surface"], model.m_max, self.arch, FT)
         return self.R_SFI, self.T_SFI
 
+    def _drop_lazy(self):
+        """Composites that a skipped surface step left in their native run (J0+- exported alone) let go of it: the next walk
+        overwrites them, and the scene's workspace with them."""
+        for c in self._composites:
+            if c._vectors_current:
+                c.drop_native()
+
+    def run_counters(self) -> dict:
+        """Launch counters of the native runs of the last run() (vsm_run_counters, summed over its runs: RUN_COUNTERS)."""
+        tot = {k: 0 for k in RUN_COUNTERS}
+        tot.update(self.__dict__.get("_run_counts", {}))
+        live = {id(c._native.ref): c._native.ref for c in self._composites if c._native is not None}
+        for ref in live.values():
+            counts = (C.c_int * 4)()
+            _lib.check(_lib.lib().vsm_run_counters(ref.run, counts))
+            for k, v in zip(RUN_COUNTERS, counts):
+                tot[k] += int(v)
+        return tot
+
     def _group_size(self, sequential: bool) -> int:
         """Fourier moments per group of a layer walk (1: moment by moment).  Small batches are launch-latency bound (C3: 2 points,
         22 moments x 33 layers): as many moments per launch as fill the chip."""
@@ -1173,6 +1271,7 @@ class Scene:
         for c in self._composites:
             c._sources_only = bool(sources_only)
             c._view_rows = view_rows if sources_only else None
+            c._counters = self.__dict__.setdefault("_run_counts", {})
         try:
             yield
         finally:
@@ -1181,10 +1280,10 @@ class Scene:
                 c._view_rows = None
 
     def _walk_layers(self, group, comps, nat, sources_only: bool, view_rows, trace=None, keep_added: bool = False, tops_at=(),
-                     keep_top=None):
+                     keep_top=None, keep_native: bool = False):
         """The top pass: the layers of the moments `group` into their composites `comps`.  nat: the indices (into group) of the
         moments that walk on the native-layout composite (vsm_run_*, _run_layers_native with sources_only / view_rows), exported
-        into the reference's arrays at the end; the others take a scattering "11" / TOA layer as ONE call for all of them
+        into the reference's arrays at the end (keep_native: left in the run until their first consumer); the others take a scattering "11" / TOA layer as ONE call for all of them
         (vsm_layer_forward_multi) and rt_kernel_ (trace, keep_added) otherwise.  keep_top(k, l, (R+-, J0+)): called for every l of
         tops_at once layer l (1-based) has joined composite k of the group, with clones of its operators (the multi-sensor run
         keeps its tops there)."""
@@ -1196,7 +1295,7 @@ class Scene:
                         keep_top(k, l, (c._arr["R_pm"].clone(), c._arr["J0_p"].clone()))
                 return cb
             self._run_layers_native([group[k] for k in nat], [comps[k] for k in nat], sources_only=sources_only,
-                                    export_at={l: export(l) for l in tops_at}, view_rows=view_rows)
+                                    export_at={l: export(l) for l in tops_at}, view_rows=view_rows, keep_native=keep_native)
         rest = [k for k in range(len(group)) if k not in nat]
         group_l, comps_l = [group[k] for k in rest], [comps[k] for k in rest]
         for iz in range(self.Nz if rest else 0):
@@ -1227,7 +1326,7 @@ class Scene:
                 return set()
         return {i for i, mom in enumerate(self.moments) if run_supported(self.dt, self.N, self.pol.n, int(self.coupling[mom["m"]]))}
 
-    def _run_layers_native(self, group, comps, sources_only: bool = True, export_at=None, view_rows=None):
+    def _run_layers_native(self, group, comps, sources_only: bool = True, export_at=None, view_rows=None, keep_native: bool = False):
         """rt_run's layer loop (rt_run.jl:383-453) for the moments of `group` with the CompositeLayer in kernel-native layout:
         vsm_run_create -> Nz x vsm_run_layer -> vsm_run_export into the reference-layout CompositeLayers `comps`.
         sources_only (and NATIVE_SOURCES_ONLY): only R+-, T-- and J0+- of `comps` are computed, R-+ and T++ come back as NaN --
@@ -1235,8 +1334,14 @@ class Scene:
         view_rows (with sources_only, and NATIVE_VIEW_ROWS): the caller reads T-- and J0- in these rows only (Scene.run without
         `streams`: view_rows_of) -- they come back as NaN in every other row.
         export_at: {l: callback} -- after layer l (1-based) the run is also exported into `comps` (the run itself goes on
-        unchanged) and callback(comps) is called: the multi-sensor run takes its top composites there (core_rt_ms.py)."""
+        unchanged) and callback(comps) is called: the multi-sensor run takes its top composites there (core_rt_ms.py).
+        keep_native: no export at the end -- every composite of `comps` stays in the run (its NativeSlot, moment im of the run) until
+        its first consumer: the surface step (CompositeLayer.surface_step) or a read of its arrays (materialize); the run is
+        destroyed when the last of them has left it (Scene.run).
+        The masks of the run are the scene's own, taken by vsm_stokes_coupling from the very Z stacks whose views the layers hand on
+        (_compute_coupling): the guard of the masks runs on the first layer step alone (vsm_run_guard_once)."""
         L = _lib.lib()
+        self._drop_lazy()                       # (composites of an earlier walk that still live in a run on this workspace)
         nm, N, S, ns = len(group), self.N, self.S, self.pol.n
         marr = (C.c_int * nm)(*[int(mom["m"]) for mom in group])
         carr = (C.c_int * nm)(*[int(self.coupling[mom["m"]]) for mom in group])
@@ -1247,7 +1352,9 @@ class Scene:
         q = self.dq.cstruct()
         run = C.c_void_p()
         run_create_(self.dt, q, S, nm, marr, carr, ws, nbytes, sources_only, view_rows, run)
+        ref = RunRef(run, self.__dict__.setdefault("_run_counts", {}), keep=(ws, self.dq))
         try:
+            _lib.check(L.vsm_run_guard_once(run))
             # VSM_RUN_ZW_TAIL (the run starts from its own TOA layer).  Its synchronous read of the weights cannot be captured into
             # a graph: a captured run keeps the dense products -- the same bits wherever no pivoted inverse is taken
             if NATIVE_ZW_TAIL and not torch.cuda.is_current_stream_capturing():
@@ -1266,10 +1373,17 @@ class Scene:
                     cc = (type(comps[0].cstruct()) * nm)(*[c.cstruct() for c in comps])
                     _lib.call("vsm_run_export", self.dt, run, cc, _stream_ptr())
                     export_at[iz + 1](comps)
-            cc = (type(comps[0].cstruct()) * nm)(*[c.cstruct() for c in comps])
-            _lib.call("vsm_run_export", self.dt, run, cc, _stream_ptr())
+            if keep_native:
+                for im, (mom, c) in enumerate(zip(group, comps)):
+                    c.drop_native()
+                    mask = int(self.coupling[mom["m"]])
+                    c._native = NativeSlot(run, int(mom["m"]), mask, stokes_groups(ns, mask), ref, im)
+                    ref.refs += 1
+            else:
+                cc = (type(comps[0].cstruct()) * nm)(*[c.cstruct() for c in comps])
+                _lib.call("vsm_run_export", self.dt, run, cc, _stream_ptr())
         finally:
-            L.vsm_run_destroy(run)
+            ref.release()
 
     def thermal_slot(self) -> "ThermalSlot":
         """The state of the `:thermal` per-source slot, allocated on first use (a model without the source never asks)."""

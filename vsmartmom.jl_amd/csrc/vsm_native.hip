@@ -1428,6 +1428,21 @@ __global__ __launch_bounds__(256) void k_native_export(int N, int ns, int src, i
     c.J0_m[(long long)s * N + tid] = (view && vw.find(gi, is) < 0) ? (T)__builtin_nan("") : cn[4 * af + np + is];
   }
 }
+// The two source vectors of k_native_export alone (J0+, and J0- with its view-row / NaN rule): what is read below a surface layer
+// that leaves the composite as it is.  One thread per (point, row); no matrix is touched.
+template <typename T>
+__global__ __launch_bounds__(256) void k_native_export_src(int N, int ns, int S, int view, ngroup_map<T> gm, nview vw, T* __restrict__ J0_p,
+                                                           T* __restrict__ J0_m) {
+  const long long e = blockIdx.x * 256ll + threadIdx.x;
+  if (e >= (long long)S * N) return;
+  const int s = (int)(e / N), i = (int)(e % N);
+  const int ai = i % ns, gi = gm.grp_of[ai];
+  const int rt = gm.rt[gi], np = 16 * rt, af = np * np;
+  const T* cn = gm.base[gi] + (long long)s * (4 * af + 2 * np);
+  const int is = (i / ns) * gm.gsz[gi] + gm.pos_in[ai];
+  J0_p[e] = cn[4 * af + is];
+  J0_m[e] = (view && vw.find(gi, is) < 0) ? (T)__builtin_nan("") : cn[4 * af + np + is];
+}
 // reference layout -> native (padding zero); elements that couple different groups are dropped (they are exact zeros for a
 // composite that was built under the same coupling).  view: a view-row run -- T-- is read in the viewing rows only, into the row
 // vectors at the head of its record
@@ -1935,7 +1950,8 @@ static int run_layer(vsm_run* run, int ndoubl, const T* dtau, const T* varpi, co
         if ((layer_coupling[sb.im] >> (4 * sb.g[a] + sb.g[b])) & 1) return false;
     return true;
   };
-  {   // the masks against the layer's actual phase matrices (VSM_DEVSTAT_MASK)
+  // the masks against the layer's actual phase matrices (VSM_DEVSTAT_MASK); vsm_run_guard_once: on the run's first layer step alone
+  if (!run->guard_once || run->layers == 1) {
     nguard_args<T> ga;
     for (int k = 0; k < NSUB_MAX; ++k) {
       const int im = k < run->nm ? k : 0;
@@ -1953,6 +1969,7 @@ static int run_layer(vsm_run* run, int ndoubl, const T* dtau, const T* varpi, co
     hipLaunchKernelGGL((k_coupling_guard<T>), dim3(nmat, run->nm), dim3(256), 0, st, run->N, run->ns,
                        ncomp ? (long long)run->N * run->N : z_stride, ga, status);
     VSM_LAUNCH_CHECK("k_coupling_guard");
+    ++run->guards;
   }
   T* const ws = static_cast<T*>(run->ws);
   const int src = (run->flags & VSM_RUN_SOURCES_ONLY) ? 1 : 0;
@@ -2031,6 +2048,7 @@ static int run_convert(vsm_run* run, const CS* comps, void* stream) {
     // a caller's arrays need not have the zero-weight columns of DESIGN.md 4.0: the dense products from here on
     run->flags &= ~(unsigned)VSM_RUN_ZW_TAIL;
     for (nat_sub& sb : run->subs) sb.kz = sb.ks;
+    run->guard_once = false;   // (nor were they built under this run's masks: every later layer step is checked again)
   }
   for (int im = 0; im < run->nm; ++im) {
     const CS& c = comps[im];
@@ -2045,8 +2063,50 @@ static int run_convert(vsm_run* run, const CS* comps, void* stream) {
       hipLaunchKernelGGL((k_native_export<T>), dim3(run->S), dim3(256), 0, as_stream(stream), run->N, run->ns,
                          (run->flags & VSM_RUN_SOURCES_ONLY) ? 1 : 0, view, gm, vw, cc);
     VSM_LAUNCH_CHECK("k_native_export / import");
+    if (!IMPORT) ++run->exports_full;
   }
   return VSM_OK;
+}
+
+// One moment of vsm_run_export (full: k_native_export with the arguments run_convert gives it), or its two source vectors alone
+// (k_native_export_src).  No host synchronisation: capturable like vsm_run_export.
+template <typename T, typename CS>
+static int run_export_moment(vsm_run* run, int im, const CS* c, bool full, void* stream, const char* who) {
+  VSM_REQUIRE(run && c, "%s: null argument", who);
+  VSM_REQUIRE(run->elem_size == (int)sizeof(T), "%s: the run was created for %d-byte arrays", who, run->elem_size);
+  VSM_REQUIRE(im >= 0 && im < run->nm, "%s: moment index %d outside the run's %d moments", who, im, run->nm);
+  VSM_REQUIRE(c->J0_p && c->J0_m && (!full || (c->R_mp && c->R_pm && c->T_pp && c->T_mm)), "%s: null composite array", who);
+  if (run->S == 0) return VSM_OK;
+  const ngroup_map<T> gm = group_map<T>(run, im);
+  const int view = (run->flags & VSM_RUN_VIEW_ROWS) ? 1 : 0;
+  const nview vw = view ? view_of_moment(run, im) : nview{};
+  if (full) {
+    const composite<T> cc{c->R_mp, c->R_pm, c->T_pp, c->T_mm, c->J0_p, c->J0_m};
+    hipLaunchKernelGGL((k_native_export<T>), dim3(run->S), dim3(256), 0, as_stream(stream), run->N, run->ns,
+                       (run->flags & VSM_RUN_SOURCES_ONLY) ? 1 : 0, view, gm, vw, cc);
+    VSM_LAUNCH_CHECK("k_native_export");
+    ++run->exports_full;
+  } else {
+    const long long tot = (long long)run->S * run->N;
+    hipLaunchKernelGGL((k_native_export_src<T>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, as_stream(stream), run->N, run->ns,
+                       run->S, view, gm, vw, c->J0_p, c->J0_m);
+    VSM_LAUNCH_CHECK("k_native_export_src");
+    ++run->exports_src;
+  }
+  return VSM_OK;
+}
+
+// The surface step of one moment of a run.  identity (the surface layer carries VSM_SURFACE_LAYER_IDENTITY): interaction!(_11) with it
+// changes nothing that is read afterwards, so only the export is left -- of the two source vectors when the caller reads nothing
+// else (matrices == 0), of the whole composite otherwise.  Else: the export and vsm_interaction, as a caller would issue them.
+template <typename T, typename CS, typename AS>
+static int run_surface(vsm_run* run, int im, int iface, const AS* added_surface, int identity, int matrices, const CS* comp, T* work,
+                       void* stream, int (*interaction)(int, int, int, const CS*, const AS*, T*, void*)) {
+  VSM_REQUIRE(run && comp && (identity || added_surface), "vsm_run_surface: null argument");
+  const int rc = run_export_moment<T>(run, im, comp, !identity || matrices, stream, "vsm_run_surface");
+  if (rc || identity) return rc;
+  ++run->surface_ia;
+  return interaction(iface, run->N, run->S, comp, added_surface, work, stream);
 }
 
 template <typename T>
@@ -2175,6 +2235,44 @@ int vsm_run_import_f64(vsm_run* run, const vsm_composite_f64* comps, void* strea
 }
 int vsm_run_import_f32(vsm_run* run, const vsm_composite_f32* comps, void* stream) {
   return run_convert<float, vsm_composite_f32, true>(run, comps, stream);
+}
+
+int vsm_run_export_moment_f64(vsm_run* run, int im, const vsm_composite_f64* comp, void* stream) {
+  return run_export_moment<double>(run, im, comp, true, stream, "vsm_run_export_moment");
+}
+int vsm_run_export_moment_f32(vsm_run* run, int im, const vsm_composite_f32* comp, void* stream) {
+  return run_export_moment<float>(run, im, comp, true, stream, "vsm_run_export_moment");
+}
+int vsm_run_export_sources_f64(vsm_run* run, int im, const vsm_composite_f64* comp, void* stream) {
+  return run_export_moment<double>(run, im, comp, false, stream, "vsm_run_export_sources");
+}
+int vsm_run_export_sources_f32(vsm_run* run, int im, const vsm_composite_f32* comp, void* stream) {
+  return run_export_moment<float>(run, im, comp, false, stream, "vsm_run_export_sources");
+}
+
+int vsm_run_surface_f64(vsm_run* run, int im, int iface, const vsm_added_f64* added_surface, int identity, int matrices,
+                        const vsm_composite_f64* comp, double* work, void* stream) {
+  return run_surface<double>(run, im, iface, added_surface, identity, matrices, comp, work, stream, vsm_interaction_f64);
+}
+int vsm_run_surface_f32(vsm_run* run, int im, int iface, const vsm_added_f32* added_surface, int identity, int matrices,
+                        const vsm_composite_f32* comp, float* work, void* stream) {
+  return run_surface<float>(run, im, iface, added_surface, identity, matrices, comp, work, stream, vsm_interaction_f32);
+}
+
+int vsm_run_guard_once(vsm_run* run) {
+  VSM_REQUIRE(run, "vsm_run_guard_once: null argument");
+  VSM_REQUIRE(run->layers == 0 && run->imports == 0, "vsm_run_guard_once: the run has taken layer steps or an import already");
+  run->guard_once = true;
+  return VSM_OK;
+}
+
+int vsm_run_counters(const vsm_run* run, int* counts) {
+  VSM_REQUIRE(run && counts, "vsm_run_counters: null argument");
+  counts[0] = run->exports_full;
+  counts[1] = run->exports_src;
+  counts[2] = run->surface_ia;
+  counts[3] = run->guards;
+  return VSM_OK;
 }
 
 int vsm_stokes_coupling_f64(int N, int n_stokes, int nblocks, const double* Zpp, const double* Zmp, int* mask_d, void* stream) {

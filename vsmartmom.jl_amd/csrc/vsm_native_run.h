@@ -55,6 +55,9 @@ struct vsm_run {
   int layers = 0;                // vsm_run_layer calls so far
   int imports = 0;               // vsm_run_import calls so far
   std::vector<char> pure_diag;   // per sub-problem: its composite is still (R = 0, T = diag, J = 0): only diagonal steps so far
+  bool guard_once = false;       // vsm_run_guard_once: k_coupling_guard on the first layer step alone (dropped by vsm_run_import)
+  // vsm_run_counters: launches so far -- k_native_export per moment, k_native_export_src, surface interactions, k_coupling_guard
+  int exports_full = 0, exports_src = 0, surface_ia = 0, guards = 0;
 };
 
 namespace vsm {

@@ -1020,3 +1020,12 @@ VSM_INST_SURF(double)
 VSM_INST_SURF(float)
 
 }  // namespace vsm
+
+// What a surface builder's layer is known to be from the surface type and the Fourier moment alone (nothing is read from the
+// device).  VSM_SURFACE_LAYER_IDENTITY: r-+ = r+- = 0, t++ = t-- = I, j0+- = 0 -- k_lambertian_mats / k_lambertian_src at m >= 1.
+// The spectral Lambertian builders write t = 0 there and the BRDF builders a reflectance block at every moment: never identity.
+// A scene with a surface source (SurfaceSIF, SurfaceEmission) keeps the full surface step at every moment.
+extern "C" unsigned vsm_surface_layer_flags(int kind, int m, int has_surface_source) {
+  if (kind == VSM_SURFACE_LAMBERTIAN_SCALAR && m >= 1 && !has_surface_source) return VSM_SURFACE_LAYER_IDENTITY;
+  return 0u;
+}
