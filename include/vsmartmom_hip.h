@@ -1345,6 +1345,35 @@ int vsm_mie_nai2(int nquad, int n_max, int n_mu, double n_r, double n_i, double 
                  const double* wx, const double* wr, const double* mu, const double* w_mu, double* greek, double* bulk_f,
                  double* scal, double* work, void* stream);
 
+/* ---- delta-BGE truncation of a phase matrix (src/Scattering/truncate_phase.jl) ----------------------------------------------------
+ * Fits l_max truncated Greek coefficients to a phase matrix given by n_mu of them (Sanghavi & Stephens 2015): beta on the Legendre
+ * polynomials, gamma and epsilon on fac_l P2_l (l = 2 .. l_max - 1), each a weighted least-squares fit over the Gauss-Legendre
+ * nodes mu, w_mu of order n_mu, solved through its normal equations.  FP64 only.  Three stages on `stream`:
+ *   1. one lane per node: f11, f12, f34 there -- bulk_f / scal[0] if vsm_mie_nai2's bulk_f [4, n_mu] and scal are handed over,
+ *      else reconstructed from the n_mu coefficients (reconstruct_phase) -- and the basis functions times the square root of the
+ *      node's weight, with one more row that makes the right-hand side;
+ *   2. [A | b] = B B^T per system on the FP64 MFMA, tiles on and above the diagonal; the angle axis is split over workgroups whose
+ *      partial sums are added in a fixed order, so a call is bit-identical to its repetition;
+ *   3. one workgroup per system: Cholesky (as L D L^T) and the triangular solves in LDS, then c0 = cl_0, beta_t = cl / c0,
+ *      alpha_t = (alpha - (beta - cl)) / c0 (delta_t, zeta_t alike), gamma_t and epsilon_t the solutions themselves (NOT divided
+ *      by c0, as in the reference).
+ * lowconf = 0: truncate_phase -- all nodes, weights w / f^2 (cos_delta is not read).  lowconf = m > 0: truncate_phase_lowconf --
+ * only the nodes with mu < cos_delta, of which the caller has counted m, weights (w / max(|f|, 1e-8))^2.
+ * Inputs (device, READ): greek [6, n_mu] row-major (alpha .. zeta), bulk_f and scal (both or neither), mu, w_mu [n_mu].
+ * Outputs (WRITTEN): greek_t [6, l_max], scal_t [2] = c0, f_trunc = 1 - c0, info [3] per system (beta, gamma, epsilon):
+ * 0 = solved, 1 = skipped -- a gamma / epsilon series of exact zeros from l = 2 on stays exact zeros (the reference divides by
+ * f12 = 0 there) --, 2 = the normal equations are not positive definite or not finite, or (lowconf = 0) f11 is not positive at
+ * a node; that system's outputs are NaN.  work: vsm_dbge_work_elems(n_mu, l_max) doubles, uninitialised (0 is returned for
+ * arguments vsm_truncate_dbge refuses).  No host synchronisation, no library scratch, no atomics.
+ * l_max above VSM_DBGE_MAX_L returns VSM_ERR_UNSUPPORTED; l_max < 3, n_mu <= l_max, lowconf < 0, 0 < lowconf < l_max,
+ * lowconf > n_mu, exactly one of bulk_f and scal null or a null required pointer return VSM_ERR_INVALID_ARG; both before any
+ * launch. */
+#define VSM_DBGE_MAX_L 128
+size_t vsm_dbge_work_elems(int n_mu, int l_max);
+int vsm_truncate_dbge(int n_mu, int l_max, int lowconf, double cos_delta, const double* greek, const double* bulk_f,
+                      const double* scal, const double* mu, const double* w_mu, double* greek_t, double* scal_t, int* info,
+                      double* work, void* stream);
+
 /* ---- diagnostics used by the parity tests -------------------------------- */
 /* Runs the LDS-resident MFMA tile product used inside the fused kernels on plain
  * [N,N,S] inputs: C = A*B.  (Checks fragment layouts / swizzle independently.) */

@@ -25,7 +25,8 @@ Sub-modules
                     apply_back_correction = exact - truncated first-order field, Jacobians of paths 1 and 2)
     Scattering      Mie aerosol optics (scattering: LogNormal / TabulatedSizeDistribution, Aerosol, make_mie_model,
                     compute_aerosol_optical_properties = the Siewert NAI-2 path on the device, FP64: a size distribution and a
-                    refractive index in, a host_model.AerosolOptics with k, C_ext, C_sca out)
+                    refractive index in, a host_model.AerosolOptics with k, C_ext, C_sca out; truncate_phase /
+                    truncate_phase_lowconf with DeltaBGE(l_max, delta_angle) = the delta-BGE fit on the device, f_trunc = 1 - c0)
     parallel        spectral-axis sharding over the GPUs of one node (torch.distributed / RCCL)
 """
 from . import _lib, host_model  # noqa: F401

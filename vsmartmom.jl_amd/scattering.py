@@ -20,8 +20,19 @@ truncate_phase.
 n_max = max(get_n_max(x_max), 2): the reference's compute_mie_pi_tau and compute_legendre_poly write two columns unconditionally,
 so it cannot run a distribution whose largest x gives n_max = 1 (x < 0.0019); two orders (three coefficients) is the least here.
 
-Not built: delta-BGE truncation (truncate_phase; a coarse-mode aerosol needs it before a run at small l_trunc), linearized Mie
-(compute_NAI2_lin.jl / LinAerosolOptics), PCW, the YAML `scattering:` block (io_yaml keeps refusing it).
+delta-BGE truncation (src/Scattering/truncate_phase.jl) through vsm_truncate_dbge (csrc/vsm_truncate.hip): a coarse-mode aerosol
+has hundreds of coefficients, a run keeps l_trunc of them, and the forward peak that the cut removes belongs into f_trunc.
+
+    optics, = Scattering.compute_aerosol_optical_properties(model, arch, truncation=Scattering.DeltaBGE(20, 2.0))
+    optics  = Scattering.truncate_phase(Scattering.DeltaBGE(20), any_aerosol_optics, arch)     # Mie, Henyey-Greenstein, hand-made
+
+truncate_phase is the variant the reference applies to Mie optics (all nodes, weights w / f^2; delta_angle is carried and not
+read), truncate_phase_lowconf the one it applies to analytic phase functions (the nodes outside the forward cone).  A gamma or
+epsilon series of exact zeros from l = 2 on -- every scalar phase function -- stays exact zeros; the reference divides by
+f12 = 0 there and returns NaN.
+
+Not built: linearized Mie and linearized truncation (compute_NAI2_lin.jl / LinAerosolOptics, truncate_phase_lin.jl), l_max above
+128, PCW, the YAML `scattering:` block (io_yaml keeps refusing it).
 """
 from __future__ import annotations
 
@@ -29,7 +40,7 @@ import ctypes as C
 import functools
 import math
 import statistics
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Optional, Sequence
 
 import numpy as np
@@ -41,6 +52,7 @@ from . import core_rt as CR
 from .architectures import array_type, default_architecture, synchronize_if_gpu, to_host
 
 MAX_N_MAX = 1024      # VSM_MIE_MAX_NMAX of the library: the largest n_max the kernels take (x = 500 needs 542)
+MAX_DBGE_L = 128      # VSM_DBGE_MAX_L of the library: the largest l_max the truncation's solve keeps in LDS
 
 
 # ---- types.jl ------------------------------------------------------------------------------------------------------------
@@ -219,23 +231,206 @@ def launch_nai2(model: MieModel, h: MieHostInputs, dev):
     return greek, bulk_f, scal, work
 
 
-def compute_aerosol_optical_properties(model_or_list, architecture=None):
+def compute_aerosol_optical_properties(model_or_list, architecture=None, truncation=None):
     """compute_aerosol_optical_properties(model) (compute_NAI2.jl:63-217) for one MieModel or a list of them: a list with one
     MieAerosolOptics per model (greek_coefs, ssa, f_trunc = 0 -- see the module's docstring --, k, C_ext, C_sca).  All models are
-    enqueued on the current stream before the one synchronisation that brings the results back."""
+    enqueued on the current stream before the one synchronisation that brings the results back.
+
+    truncation = DeltaBGE(l_max, .): each model's vsm_truncate_dbge is enqueued directly behind its vsm_mie_nai2, on the device
+    arrays greek, bulk_f and scal (truncate_phase, the variant the reference applies to Mie optics), and the list holds
+    TruncatedAerosolOptics whose `untruncated` is the MieAerosolOptics.  NoTruncation() wraps without a fit."""
     models = [model_or_list] if isinstance(model_or_list, MieModel) else list(model_or_list)
     arch = architecture if architecture is not None else default_architecture()
     CR._require_gpu(arch)
     _lib.lib()
+    if truncation is not None:
+        _check_method(truncation)
     conv = array_type(arch)
     hosts = [mie_host_inputs(m) for m in models]         # (every refusal before the first launch)
     devs = [device_inputs(h, conv) for h in hosts]
-    runs = [launch_nai2(m, h, d) for m, h, d in zip(models, hosts, devs)]
+    runs, fits = [], []
+    for m, h, d in zip(models, hosts, devs):
+        runs.append(launch_nai2(m, h, d))
+        fit = None
+        if isinstance(truncation, DeltaBGE) and h.n_mu > truncation.l_max:
+            greek, bulk_f, scal, _work = runs[-1]
+            fit = launch_dbge(h.n_mu, truncation.l_max, 0, 1.0, greek, bulk_f, scal, d[4], d[5])
+        fits.append(fit)
     synchronize_if_gpu()
     out = []
-    for h, (greek, bulk_f, scal, _work) in zip(hosts, runs):
+    for h, (greek, bulk_f, scal, _work), fit in zip(hosts, runs, fits):
         g = to_host(greek)
         c_sca, c_ext, ssa = (float(v) for v in to_host(scal))
-        out.append(MieAerosolOptics(H.GreekCoefs(*(g[i].copy() for i in range(6))), ssa, 0.0, k=c_ext, C_ext=c_ext, C_sca=c_sca,
-                                    mu=h.mu, bulk_f=to_host(bulk_f)))
+        opt = MieAerosolOptics(H.GreekCoefs(*(g[i].copy() for i in range(6))), ssa, 0.0, k=c_ext, C_ext=c_ext, C_sca=c_sca,
+                               mu=h.mu, bulk_f=to_host(bulk_f))
+        if truncation is not None:
+            opt = _untruncated(opt) if fit is None else _collect_dbge(truncation, opt, fit)
+        out.append(opt)
     return out
+
+
+# ---- truncate_phase.jl ----------------------------------------------------------------------------------------------------------
+class NoTruncation:
+    """NoTruncation(): the coefficients as they are, f_trunc = 0."""
+
+    def __repr__(self):
+        return "NoTruncation()"
+
+    def __eq__(self, other):
+        return isinstance(other, NoTruncation)
+
+    def __hash__(self):
+        return hash(NoTruncation)
+
+
+@dataclass(frozen=True)
+class DeltaBGE:
+    """deltaBGE(l_max, delta_angle) (types.jl): keep l_max coefficients; delta_angle [degrees] is the half-angle of the forward
+    cone that truncate_phase_lowconf leaves out of its fit (truncate_phase carries it and does not read it)."""
+    l_max: int
+    delta_angle: float = 0.0
+
+
+δBGE = DeltaBGE
+
+
+@dataclass
+class TruncatedAerosolOptics(H.AerosolOptics):
+    """host_model.AerosolOptics after truncate_phase: greek_coefs of l_max entries, ssa unchanged, f_trunc = 1 - c0 -- what
+    host_model.createAero's delta-M scaling reads --, the method, and the object that went in (the exact single-scattering
+    correction of a truncated run wants the untruncated phase function).  k, C_ext, C_sca are carried over where it has them;
+    info is the device's status of the beta, gamma and epsilon fits (0 = solved, 1 = skipped: a series of exact zeros)."""
+    c0: float = 1.0
+    method: object = field(default_factory=NoTruncation)
+    untruncated: Optional[H.AerosolOptics] = None
+    k: Optional[float] = None
+    C_ext: Optional[float] = None
+    C_sca: Optional[float] = None
+    info: tuple = ()
+
+
+SYSTEMS = ("beta", "gamma", "epsilon")     # the three fits, in the order of vsm_truncate_dbge's info
+
+
+def _check_method(method):
+    if isinstance(method, NoTruncation):
+        return
+    if not isinstance(method, DeltaBGE):
+        raise _lib.VSMError("truncation method %r: NoTruncation() or DeltaBGE(l_max, delta_angle)" % (method,))
+    if int(method.l_max) != method.l_max or method.l_max < 3:
+        raise _lib.VSMError("DeltaBGE: l_max = %r < 3 (the gamma and epsilon fits start at l = 2)" % (method.l_max,))
+    if method.l_max > MAX_DBGE_L:
+        raise _lib.VSMError("DeltaBGE: l_max = %d above the %d coefficients the truncation kernels take (VSM_DBGE_MAX_L)"
+                            % (method.l_max, MAX_DBGE_L))
+    if not (0.0 <= method.delta_angle < 180.0):
+        raise _lib.VSMError("DeltaBGE: delta_angle = %r outside [0, 180) degrees" % (method.delta_angle,))
+
+
+def _carry(optics):
+    return {n: getattr(optics, n) for n in ("k", "C_ext", "C_sca") if getattr(optics, n, None) is not None}
+
+
+def _untruncated(optics):
+    """truncate_phase(NoTruncation(), .): the very same coefficient arrays, f_trunc = 0."""
+    return TruncatedAerosolOptics(optics.greek_coefs, optics.ssa, 0.0, c0=1.0, method=NoTruncation(), untruncated=optics,
+                                  **_carry(optics))
+
+
+def launch_dbge(n_mu, l_max, lowconf, cos_delta, greek, bulk_f, scal, mu, w_mu):
+    """Enqueues vsm_truncate_dbge on the current stream: (greek_t [6, l_max], scal_t [2], info [3], work) device tensors.  Nothing
+    is synchronised; the inputs and the work buffer must outlive the work."""
+    dev = greek.device
+    greek_t = torch.empty((6, l_max), dtype=torch.float64, device=dev)
+    scal_t = torch.empty(2, dtype=torch.float64, device=dev)
+    info = torch.empty(3, dtype=torch.int32, device=dev)
+    elems = int(_lib.lib().vsm_dbge_work_elems(n_mu, l_max))
+    if elems == 0:
+        raise _lib.VSMError("vsm_dbge_work_elems refuses n_mu = %d, l_max = %d" % (n_mu, l_max))
+    work = _lib.poison(torch.empty(elems, dtype=torch.float64, device=dev))
+    _lib.check(_lib.lib().vsm_truncate_dbge(n_mu, l_max, lowconf, C.c_double(cos_delta), CR._ptr(greek), CR._ptr(bulk_f),
+                                            CR._ptr(scal), CR._ptr(mu), CR._ptr(w_mu), CR._ptr(greek_t), CR._ptr(scal_t),
+                                            CR._ptr(info), CR._ptr(work), CR._stream_ptr()))
+    return greek_t, scal_t, info, work
+
+
+def _collect_dbge(method, optics, fit):
+    """After the synchronisation: the device's status per system, then the TruncatedAerosolOptics."""
+    greek_t, scal_t, info, _work = fit
+    status = [int(v) for v in to_host(info)]
+    for name, st in zip(SYSTEMS, status):
+        if st == 2:
+            raise _lib.VSMError("truncate_phase: the %s fit at l_max = %d failed on the device (info = %r): its normal equations "
+                                "are not positive definite or not finite, or f11 is not positive at a node"
+                                % (name, method.l_max, tuple(status)))
+    g = to_host(greek_t)
+    c0, f_trunc = (float(v) for v in to_host(scal_t))
+    return TruncatedAerosolOptics(H.GreekCoefs(*(g[i].copy() for i in range(6))), optics.ssa, f_trunc, c0=c0, method=method,
+                                  untruncated=optics, info=tuple(status), **_carry(optics))
+
+
+def _greek_matrix(optics):
+    g = optics.greek_coefs
+    rows = [np.asarray(v, dtype=np.float64).reshape(-1) for v in (g.alpha, g.beta, g.gamma, g.delta, g.epsilon, g.zeta)]
+    if len({len(r) for r in rows}) != 1:
+        raise _lib.VSMError("truncate_phase: the six coefficient vectors have lengths %r" % ([len(r) for r in rows],))
+    return np.stack(rows)
+
+
+def _truncate(method, optics_or_list, architecture, lowconf):
+    single = isinstance(optics_or_list, H.AerosolOptics)
+    sets = [optics_or_list] if single else list(optics_or_list)
+    arch = architecture if architecture is not None else default_architecture()
+    CR._require_gpu(arch)
+    _lib.lib()
+    _check_method(method)
+    conv = array_type(arch)
+    plans = []                                           # (every refusal before the first launch)
+    for o in sets:
+        if not isinstance(o, H.AerosolOptics):
+            raise _lib.VSMError("truncate_phase: %r is no host_model.AerosolOptics" % (type(o).__name__,))
+        greek = _greek_matrix(o)
+        L = greek.shape[1]
+        if isinstance(method, NoTruncation) or L <= method.l_max:      # (the guard at the reference's call sites)
+            plans.append(None)
+            continue
+        mu, w_mu = gausslegendre(L)
+        count, cos_delta = 0, 1.0
+        if lowconf:
+            cos_delta = math.cos(math.radians(method.delta_angle))
+            count = int(np.count_nonzero(mu < cos_delta))
+            if count < method.l_max:
+                raise _lib.VSMError("truncate_phase_lowconf: %d of the %d nodes lie outside the cone of %g degrees, fewer than "
+                                    "l_max = %d unknowns" % (count, L, method.delta_angle, method.l_max))
+        bulk = getattr(o, "bulk_f", None)                # Mie optics bring f11, f12, f34 at these very nodes
+        if bulk is not None and (np.shape(bulk) != (4, L) or not getattr(o, "C_sca", None)):
+            bulk = None
+        plans.append((L, count, cos_delta, greek, bulk, mu, w_mu))
+    fits = []
+    for o, plan in zip(sets, plans):
+        if plan is None:
+            fits.append(None)
+            continue
+        L, count, cos_delta, greek, bulk, mu, w_mu = plan
+        bulk_d = scal_d = None
+        if bulk is not None:
+            bulk_d, scal_d = conv(np.asarray(bulk, dtype=np.float64)), conv(np.array([o.C_sca, o.C_ext, o.ssa], dtype=np.float64))
+        inputs = (conv(greek), bulk_d, scal_d, conv(mu), conv(w_mu))       # (kept until the synchronisation)
+        fits.append((launch_dbge(L, int(method.l_max), count, cos_delta, *inputs), inputs))
+    synchronize_if_gpu()
+    out = [_untruncated(o) if fit is None else _collect_dbge(method, o, fit[0]) for o, fit in zip(sets, fits)]
+    return out[0] if single else out
+
+
+def truncate_phase(method, optics_or_list, architecture=None):
+    """truncate_phase(method, aero) (truncate_phase.jl:29, :149-273) for one host_model.AerosolOptics (Mie, Henyey-Greenstein or
+    hand-made) or a list of them; a TruncatedAerosolOptics, or a list of them for a list.  The Gauss-Legendre nodes are those of
+    order len(beta).  MieAerosolOptics bring their bulk_f at these nodes and are fitted to it; every other set is reconstructed
+    from its coefficients on the device.  A series with len(beta) <= l_max comes back as NoTruncation() returns it.  All sets are
+    enqueued before the one synchronisation; a fit the device could not solve raises VSMError after it."""
+    return _truncate(method, optics_or_list, architecture, False)
+
+
+def truncate_phase_lowconf(method, optics_or_list, architecture=None):
+    """truncate_phase_lowconf(method, aero) (truncate_phase.jl:39, :56-128): the fit over the nodes with
+    mu < cos(delta_angle), weights w / max(|f|, 1e-8) -- the variant the reference applies to analytic phase functions."""
+    return _truncate(method, optics_or_list, architecture, True)
