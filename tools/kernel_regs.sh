@@ -7,7 +7,7 @@ B=/opt/rocm/lib/llvm/bin
 $B/llvm-objcopy -O binary --only-section=.hip_fatbin "$obj" $tmp/fat.bin
 $B/clang-offload-bundler --type=o --input=$tmp/fat.bin --targets=hipv4-amdgcn-amd-amdhsa--gfx950 --output=$tmp/dev.co --unbundle
 $B/llvm-readelf --notes $tmp/dev.co | awk '
-  /\.agpr_count:/ {a=$2}
+  /\.agpr_count:/ {a=$NF}
   /\.group_segment_fixed_size:/ {g=$2}
   /\.name:/ {name=$2}
   /\.private_segment_fixed_size:/ {ps=$2}

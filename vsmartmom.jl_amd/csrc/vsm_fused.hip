@@ -2,7 +2,8 @@
 // operators on-chip for a whole layer step.
 //
 //   k_elemental_doubling : elemental! + ndoubl x doubling step + apply_D!   (1 launch / layer)
-//   k_interaction11      : interaction_helper!(::ScatteringInterface_11)      (1 launch / layer)
+//   k_interaction11      : interaction_helper!(::ScatteringInterface_11)      (1 launch / layer; FP32, N <= 64 only: the FP64
+//                          interaction of N <= 64 is vsm_native.hip's k_ia_native, FP32 64 < N <= 96 vsm_strip32.hip's k_ia_strip32)
 //
 // LDS layout: column-major NP x NP (NP = N rounded up to 32), row index XOR-swizzled by column so
 // that both MFMA operand fetch patterns (A: 16 rows x 2 k-columns per half-wave, B: 2 k-rows x 16
@@ -1548,9 +1549,6 @@ template int fused_max_n<float>();
 #ifndef ED_WAVES_96
 #define ED_WAVES_96 4
 #endif
-#ifndef IA_WAVES_96
-#define IA_WAVES_96 4
-#endif
 
 template <typename K>
 static int enable_lds(K kern, size_t bytes) {   // once per (device, kernel)
@@ -1562,6 +1560,11 @@ template <int V>
 struct np_tag {
   static constexpr int value = V;
 };
+template <typename T>
+static int beyond_lds(int N) {
+  set_error("fused kernels: N=%d exceeds the LDS-resident limit (%d)", N, fused_max_n<T>());
+  return VSM_ERR_UNSUPPORTED;
+}
 template <typename T, typename F>
 static int dispatch_np(int N, F f) {
   if (N <= 32) return f(np_tag<32>{});
@@ -1569,8 +1572,7 @@ static int dispatch_np(int N, F f) {
   if constexpr (sizeof(T) == 4) {
     if (N <= 96) return f(np_tag<96>{});
   }
-  set_error("fused kernels: N=%d exceeds the LDS-resident limit (%d)", N, fused_max_n<T>());
-  return VSM_ERR_UNSUPPORTED;
+  return beyond_lds<T>(N);
 }
 
 template <typename T>
@@ -1604,26 +1606,24 @@ int fused_interaction(int iface, int N, int S, const composite<T>& c, const adde
     set_error("fused_interaction: only ScatteringInterface_11 is fused");
     return VSM_ERR_UNSUPPORTED;
   }
+  if (N > fused_max_n<T>()) return beyond_lds<T>(N);
   if constexpr (sizeof(T) == 8) {
-    static const bool no_native = ab_switch("VSM_NO_NATIVE_IA");
-    if (!no_native && N <= 64) return native_interaction11(N, S, c, a, st);
-    static const bool no_strip = ab_switch("VSM_NO_STRIP") || ab_switch("VSM_NO_STRIP_IA");
-    if (!no_strip && strip_layer_supported(N)) return strip_interaction11(N, S, c, a, st);
+    return native_interaction11(N, S, c, a, st);   // k_ia_native, every N <= 64
+  } else {
+    if (N > 64) return strip32_interaction11(N, S, c, a, st);
+    auto launch = [&](auto tag) {   // the LDS-resident interaction: FP32, N <= 64
+      constexpr int NP = decltype(tag)::value;
+      constexpr int NW = (NP == 64) ? IA_WAVES_64 : 4;
+      auto kern = k_interaction11<T, NP, NW>;
+      const size_t bytes = sizeof(fsmem<T, NP, NW>);
+      const int prepared = enable_lds(kern, bytes);
+      if (prepared) return prepared;
+      hipLaunchKernelGGL(kern, dim3(S), dim3(fcfg<NP, NW>::NT), bytes, st, N, c, a);
+      VSM_LAUNCH_CHECK("k_interaction11");
+      return (int)VSM_OK;
+    };
+    return N <= 32 ? launch(np_tag<32>{}) : launch(np_tag<64>{});
   }
-  if constexpr (sizeof(T) == 4) {
-    if (strip32_supported(N)) return strip32_interaction11(N, S, c, a, st);
-  }
-  return dispatch_np<T>(N, [&](auto tag) {
-    constexpr int NP = decltype(tag)::value;
-    constexpr int NW = (NP == 64) ? IA_WAVES_64 : (NP == 96) ? IA_WAVES_96 : 4;
-    auto kern = k_interaction11<T, NP, NW>;
-    const size_t bytes = sizeof(fsmem<T, NP, NW>);
-    const int prepared = enable_lds(kern, bytes);
-    if (prepared) return prepared;
-    hipLaunchKernelGGL(kern, dim3(S), dim3(fcfg<NP, NW>::NT), bytes, st, N, c, a);
-    VSM_LAUNCH_CHECK("k_interaction11");
-    return (int)VSM_OK;
-  });
 }
 
 template <typename T>

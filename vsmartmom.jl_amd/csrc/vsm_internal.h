@@ -268,7 +268,7 @@ int mix_Z_moments(int N, int S, int ncomp, int nm, const T* const* Zpp_comp, con
 
 // ---- column-strip kernels (FP64, 32 < N <= 60; two workgroups per CU): vsm_strip.hip ----------------
 bool strip_supported(int N);
-bool strip_layer_supported(int N);   // the layer step and interaction!(_11): 32 < N <= 64
+bool strip_layer_supported(int N);   // the layer step: 32 < N <= 64
 int strip_elemental_doubling(const quad<double>& q, int S, int m, int ndoubl, const double* dtau, const double* varpi,
                              const double* tau_sum, const double* F0, const zsrc<double>& z, const added<double>& a,
                              hipStream_t st);
@@ -276,7 +276,6 @@ int strip_elemental_doubling(const quad<double>& q, int S, int m, int ndoubl, co
 int strip_gemm(int M, int Nc, int K, int S, int P, const double* A, long long sa, long long pa, const double* B, long long sb,
                long long pb, double* C, long long sc, long long pc, double alpha, const double* D, long long sd, long long pd,
                double beta, double gamma, hipStream_t st);
-int strip_interaction11(int N, int S, const composite<double>& c, const added<double>& a, hipStream_t st);
 int strip_doubling_lin_step(int N, int S, int P, double* expk, double* ekl, const added<double>& a,
                             const added_lin<double>& al, hipStream_t st);
 int strip_doubling_lin_multi(int N, int S, int P, int nd, int ns, double* expk, double* ekl, const added<double>& a,

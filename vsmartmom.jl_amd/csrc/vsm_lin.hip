@@ -449,21 +449,28 @@ int doubling_lin(int N, int ns, int S, int ndoubl, T* expk, const T* dtau_dot_al
   VSM_LAUNCH_CHECK("k_ekl_init");
   int n0 = 0;
   if constexpr (std::is_same<T, double>::value) {
-    // one active parameter: all steps in one launch (state stays on the chip between the steps)
-    // (apply_D! rides in its epilogue when every parameter slot is either active there or zero: P == n_active or the
-    //  remaining slots' derivatives of r, t vanish in this layer, which the caller states with n_active > 0)
+    // Which kernel takes an FP64 shape (plain [N,N,S] layout; anything else, and N > 128, is the operator chain below):
+    //   N <= 48 or 60 < N <= 128       k_dbl128_lin (vsm_strip128lin.hip): all steps in one persistent launch, any P
+    //   49 <= N <= 60, 1 <= P <= 3     k_dbl_lin_multi (vsm_striplin.hip): all steps in one launch
+    //   49 <= N <= 60 otherwise        k_dbl_lin_step (vsm_striplin.hip): one launch per step
+    // A kernel answers VSM_ERR_UNSUPPORTED for a shape or layout that is not its own (or when its A/B switch is set).
+    // apply_D! rides in the epilogue of the all-steps kernels when every parameter slot is either active there or zero: P ==
+    // n_active or the remaining slots' derivatives of r, t vanish in this layer, which the caller states with n_active > 0.
+    // VSM_LIN_SEPARATE_APPLY_D (A/B) runs it as its own launch instead, which k_dbl128_lin cannot: its shapes take the chain then.
     static const bool sepD = ab_switch("VSM_LIN_SEPARATE_APPLY_D");
-    rc = strip128_lin_dbl_supported(N) ? (int)VSM_ERR_UNSUPPORTED : strip_doubling_lin_multi(N, S, P, ndoubl, sepD ? 0 : ns, expk, ekl, a, al, st);
-    // 60 < N <= 128, any number of active parameters: all steps in one persistent launch (vsm_strip128lin.hip)
-    if (rc == VSM_ERR_UNSUPPORTED && !sepD) rc = strip128_doubling_lin(N, S, P, ndoubl, ns, expk, ekl, a, al, st);
-    if (rc == VSM_OK && !sepD) return VSM_OK;
-    if (rc == VSM_OK) n0 = ndoubl;
-    else if (rc != VSM_ERR_UNSUPPORTED) return rc;
-    // fused column-strip step (vsm_striplin.hip): one launch per doubling step, forward + all active parameters
-    for (; n0 < ndoubl; ++n0) {
-      rc = strip_doubling_lin_step(N, S, P, expk, ekl, a, al, st);
-      if (rc == VSM_ERR_UNSUPPORTED && n0 == 0) break;
-      if (rc) return rc;
+    if (strip128_lin_dbl_supported(N)) {
+      rc = sepD ? (int)VSM_ERR_UNSUPPORTED : strip128_doubling_lin(N, S, P, ndoubl, ns, expk, ekl, a, al, st);
+      if (rc != VSM_ERR_UNSUPPORTED) return rc;
+    } else {
+      rc = strip_doubling_lin_multi(N, S, P, ndoubl, sepD ? 0 : ns, expk, ekl, a, al, st);
+      if (rc == VSM_OK && !sepD) return VSM_OK;
+      if (rc == VSM_OK) n0 = ndoubl;
+      else if (rc != VSM_ERR_UNSUPPORTED) return rc;
+      for (; n0 < ndoubl; ++n0) {
+        rc = strip_doubling_lin_step(N, S, P, expk, ekl, a, al, st);
+        if (rc == VSM_ERR_UNSUPPORTED && n0 == 0) break;
+        if (rc) return rc;
+      }
     }
   } else {
     // Float32 (N <= 128): the FP64 kernels of vsm_strip128lin.hip on the FP32 arrays -- storage in single, arithmetic in double:

@@ -16,6 +16,10 @@
 //     tt  = t G                                      Q = t                G_s
 //     tmp = tt r ;  t' = tt t   (share A)            P = tt               r_s ; t_s (+ j0+, j1- in spare columns)
 //     r'  = r + tmp t                                Q = tmp              t_s
+//
+// Kernels: k_ed_strip (vsm_elemental_doubling, 32 < N <= 60); k_elemental_img + k_layer_strip_mm (the layer step of
+// vsm_layer_forward*, interaction included, 32 < N <= 64); k_gemm_strip.  The interaction on its own is not here: every FP64
+// N <= 64 runs on vsm_native.hip's k_ia_native.
 #include <stdlib.h>
 
 #include "vsm_internal.h"
@@ -444,9 +448,9 @@ __global__ __launch_bounds__(SNT, 2) void k_ed_strip(quad<double> q, int m, int 
 // interaction_helper!(::ScatteringInterface_11)  (interaction.jl:207-266), strip form
 // ---------------------------------------------------------------------------
 
-// Body shared by k_ia_strip and k_layer_strip.  On entry: r_s / t_s = strips of the added layer's r-+ / t++ (columns >= N zero),
-// sm.vec[0] / vec[1] = its j0+ / j0-, all waves past a barrier, P and Q free.  DSYM: r+- = D r-+ D, t-- = D t++ D (added layers
-// from doubling, ns = n_stokes); otherwise they are read from r_pm / t_mm (surface layers).
+// The interaction of k_layer_strip_mm.  On entry: r_s / t_s = strips of the added layer's r-+ / t++ (columns >= N zero),
+// sm.vec[0] / vec[1] = its j0+ / j0-, all waves past a barrier, P and Q free.  The layer comes from doubling, so r+- = D r-+ D and
+// t-- = D t++ D (sm.usg, filled by ed_body, holds D's signs).
 //
 // The reference's statements (interaction.jl:207-266)
 //   T01 = T-- (I - r-+ R+-)^-1 ;  R-+ += T01 r-+ T++ ;  J0- += T01 (j0- + r-+ J0+) ;  T-- = T01 t--
@@ -463,9 +467,8 @@ __global__ __launch_bounds__(SNT, 2) void k_ed_strip(quad<double> q, int m, int 
 // and the series (the as-written order: twelve and two inverses), seven barriers, three product phases of four, two and four
 // products, six live strips at most; every composite matrix crosses the memory system once in each direction ([R+-], [T--]
 // coalesced into their A-forms, T++ and R-+ as strips).
-template <int KS, bool DSYM>
-__device__ __forceinline__ void ia_body(ssmem& sm, spos& p, int N, int ns, const composite<double>& c, sstrip& r_s,
-                                        sstrip& t_s, const double* __restrict__ r_pm, const double* __restrict__ t_mm) {
+template <int KS>
+__device__ __forceinline__ void ia_body(ssmem& sm, spos& p, int N, const composite<double>& c, sstrip& r_s, sstrip& t_s) {
   double* P = sm.P;
   double* Q = sm.Q;
   double* vjp = sm.vec[0];
@@ -494,7 +497,7 @@ __device__ __forceinline__ void ia_body(ssmem& sm, spos& p, int N, int ns, const
   auto keepN = [N](double x, int r, int cc) { return (r < N && cc < N) ? x : 0.0; };
   int slot = 0;
   double* xw = sm.xw[p.wave];
-  const dpar dp(sm.usg, p);   // (filled by the caller; all +1 for a surface layer)
+  const dpar dp(sm.usg, p);   // (filled by the caller)
 
   VSM_STAMP_DECL;
   // ---- stage: composite vectors, [R+-] -> P, [T--] -> Q (all 32 column loads of a lane in flight together) ---------------
@@ -503,10 +506,8 @@ __device__ __forceinline__ void ia_body(ssmem& sm, spos& p, int N, int ns, const
     vJp[tid] = in ? J0_p[tid] : 0.0;
     vJm[tid] = in ? J0_m[tid] : 0.0;
   }
-  sstrip Z, V, G;                          // (Z doubles as the t-- strip of a surface layer until the first products)
-  if (!DSYM) load_strip_global_c8_issue(G, t_mm, N, p);
+  sstrip Z, V, G;
   stage_aform_full2(P, R_pm, Q, T_mm, N, p);
-  if (!DSYM) load_strip_global_c8_finish(G, p, xw);
   __syncthreads();                                                                                       // (a)
   VSM_STAMP(8);
   if constexpr (!RID) {   // R+- j0- , T-- j0-
@@ -519,18 +520,15 @@ __device__ __forceinline__ void ia_body(ssmem& sm, spos& p, int N, int ns, const
 #pragma unroll
       for (int r = 0; r < 4; ++r) r_s.v[ta][r] = laneB ? vjm[p.row(ta, r)] : r_s.v[ta][r];
   }
-  if (DSYM) dsym_strip(t_s, t_s, dp);   // t-- = D t++ D in place (undone below: D is an involution)
+  dsym_strip(t_s, t_s, dp);   // t-- = D t++ D in place (undone below: D is an involution)
   {
     sstrip E, S;
-    {
-      const sstrip& tb = DSYM ? t_s : G;
-      E.zero();
-      Z.zero();
-      mm_ab2<KS>(E, Z, P, r_s, tb, p);
-      S.zero();
-      V.zero();
-      mm_ab2<KS>(S, V, Q, r_s, tb, p);
-    }
+    E.zero();
+    Z.zero();
+    mm_ab2<KS>(E, Z, P, r_s, t_s, p);
+    S.zero();
+    V.zero();
+    mm_ab2<KS>(S, V, Q, r_s, t_s, p);
     if (own_wave) {
       double* zd = laneB ? vz : sm.vec[7];   // (the other lanes write to a dummy vector)
       double* sd = laneB ? vs : sm.vec[7];
@@ -544,12 +542,8 @@ __device__ __forceinline__ void ia_body(ssmem& sm, spos& p, int N, int ns, const
         }
     }
     // r_s <- r+- (the accumulator of the R+- update; its rider column is never stored), t_s <- t++
-    if (DSYM) {
-      dsym_strip(r_s, r_s, dp);
-      dsym_strip(t_s, t_s, dp);
-    } else {
-      load_strip_global_c8(r_s, r_pm, N, p, xw);
-    }
+    dsym_strip(r_s, r_s, dp);
+    dsym_strip(t_s, t_s, dp);
     VSM_STAMP(9);
     const double nrm = strip_norm_bound_clean(E, N, sm, slot, p);   // (b): every wave is done reading [R+-] and [T--]
     if constexpr (!RID) {   // z = J0+ + R+- j0- ; vs = T-- j0-   (before the inverse may use the Gauss-Jordan scratch)
@@ -636,27 +630,6 @@ __device__ __forceinline__ void ia_body(ssmem& sm, spos& p, int N, int ns, const
   VSM_STAMP_FLUSH();
 }
 
-template <int KS, bool DSYM>
-__global__ __launch_bounds__(SNT, 2) void k_ia_strip(int N, composite<double> c, added<double> a) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  ssmem& sm = *reinterpret_cast<ssmem*>(smem_raw);
-  spos p;
-  p.bind(sm.P);
-  const int s = blockIdx.x, tid = threadIdx.x;
-  if (tid < SNP) {
-    const bool in = tid < N;
-    sm.vec[0][tid] = in ? a.j0_p[(long long)s * N + tid] : 0.0;
-    sm.vec[1][tid] = in ? a.j0_m[(long long)s * N + tid] : 0.0;
-    sm.usg[tid] = (DSYM && is_uv_row(tid, a.d_symmetric)) ? -1.0 : 1.0;
-  }
-  sstrip r_s, t_s;
-  load_strip_global_c8(r_s, a.r_mp + s * a.mat_stride, N, p, sm.xw[p.wave]);
-  load_strip_global_c8(t_s, a.t_pp + s * a.mat_stride, N, p, sm.xw[p.wave]);
-  __syncthreads();
-  ia_body<KS, DSYM>(sm, p, N, a.d_symmetric, c, r_s, t_s, DSYM ? nullptr : a.r_pm + s * a.mat_stride,
-                    DSYM ? nullptr : a.t_mm + s * a.mat_stride);
-}
-
 // rt_kernel!(::noRS) for a scattering layer (rt_kernel.jl:175-250) in ONE launch: elemental! + doubling! and then
 // either the TOA copy (iz == 1: copy_added_to_composite!, rt_helpers.jl:188-200) or interaction!(::_11).  The added
 // layer never leaves the chip.
@@ -672,7 +645,7 @@ __device__ __forceinline__ void layer_body(const quad<double>& q, int m, int ndo
   p.bind(sm.P);
   sstrip r_s, t_s;
   ed_body<KS, MIX, THERMAL, PRE>(sm, p, q, m, ndoubl, dtau, varpi, tau_sum, F0, z, r_s, t_s, img);
-  const int N = q.N, ns = q.n_stokes;
+  const int N = q.N;
   if (toa) {
     const int s = blockIdx.x, tid = threadIdx.x;
     const long long NN = (long long)N * N;
@@ -691,7 +664,7 @@ __device__ __forceinline__ void layer_body(const quad<double>& q, int m, int ndo
     }
     return;
   }
-  ia_body<KS, true>(sm, p, N, ns, c, r_s, t_s, nullptr, nullptr);
+  ia_body<KS>(sm, p, N, c, r_s, t_s);
   VSM_LIFE_FLUSH();
 }
 // The same for several Fourier moments at once: blockIdx.y picks the moment's composite.  The elemental layers come from the
@@ -777,7 +750,6 @@ __global__ __launch_bounds__(SNT, 4) void k_gemm_strip(int M, int Nc, int K, con
 #define VSM_STRIP_DECL(KS)                                                                                                  \
   int VSM_CAT(launch_ed_strip_, KS)(const quad<double>&, int, int, int, const double*, const double*, const double*,       \
                                     const double*, const zsrc<double>&, const added<double>&, hipStream_t);                 \
-  int VSM_CAT(launch_ia_strip_, KS)(int, int, const composite<double>&, const added<double>&, hipStream_t);                \
   int VSM_CAT(launch_layer_strip_mm_, KS)(const quad<double>&, int, int, int, const layer_mm_args<double>&, int,           \
                                           const double*, hipStream_t);
 
@@ -800,18 +772,6 @@ int VSM_CAT(launch_ed_strip_, VSM_STRIP_KS)(const quad<double>& q, int S, int m,
 #else   // N = 61..64: elemental! + doubling! alone stay on the LDS-resident kernels (the strip form needs the pre-pass)
   return VSM_ERR_UNSUPPORTED;
 #endif
-}
-int VSM_CAT(launch_ia_strip_, VSM_STRIP_KS)(int N, int S, const composite<double>& c, const added<double>& a, hipStream_t st) {
-  const int prepared = strip_enable_lds(k_ia_strip<VSM_STRIP_KS, true>, "hipFuncSetAttribute(k_ia_strip)");
-  const int prepared_g = strip_enable_lds(k_ia_strip<VSM_STRIP_KS, false>, "hipFuncSetAttribute(k_ia_strip general)");
-  if (prepared) return prepared;
-  if (prepared_g) return prepared_g;
-  if (a.d_symmetric)   // (d_symmetric carries n_stokes)
-    hipLaunchKernelGGL((k_ia_strip<VSM_STRIP_KS, true>), dim3(S), dim3(SNT), sizeof(ssmem), st, N, c, a);
-  else
-    hipLaunchKernelGGL((k_ia_strip<VSM_STRIP_KS, false>), dim3(S), dim3(SNT), sizeof(ssmem), st, N, c, a);
-  VSM_LAUNCH_CHECK("k_ia_strip");
-  return VSM_OK;
 }
 int VSM_CAT(launch_layer_strip_mm_, VSM_STRIP_KS)(const quad<double>& q, int S, int nm, int ndoubl,
                                                   const layer_mm_args<double>& a, int toa, const double* pre, hipStream_t st) {
@@ -839,8 +799,8 @@ bool strip_supported(int N) {
   const int Kend = ((N + 3) >> 2) << 2;
   return N > 32 && Kend + 2 <= SNP;
 }
-// the layer step (pre-pass + layer kernel) and interaction!(_11) also take N = 61..64 (KS = 16: no spare columns, the source
-// vectors by mat-vecs over the A-forms)
+// the layer step (pre-pass + layer kernel) also takes N = 61..64 (KS = 16: no spare columns, the source vectors by mat-vecs
+// over the A-forms)
 bool strip_layer_supported(int N) { return N > 32 && N <= SNP; }
 
 template <int KS>
@@ -1034,16 +994,6 @@ int strip_layer_forward(const quad<double>& q, int S, int m, int ndoubl, const d
     a.c[i] = c;
   }
   return strip_layer_forward_pre(q, S, 1, ndoubl, dtau, varpi, tau_sum, F0, a, toa, st, thermal);
-}
-
-int strip_interaction11(int N, int S, const composite<double>& c, const added<double>& a, hipStream_t st) {
-  if (S <= 0) return VSM_OK;
-#define VSM_CALL(KS) VSM_CAT(launch_ia_strip_, KS)(N, S, c, a, st)
-  VSM_STRIP_SWITCH16(N, VSM_CALL)
-  VSM_STRIP_SWITCH(N, VSM_CALL)
-#undef VSM_CALL
-  set_error("strip_interaction11: N=%d outside (32, 60]", N);
-  return VSM_ERR_UNSUPPORTED;
 }
 
 int strip_elemental_doubling(const quad<double>& q, int S, int m, int ndoubl, const double* dtau, const double* varpi,

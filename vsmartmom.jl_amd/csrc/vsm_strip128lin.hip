@@ -1,4 +1,5 @@
-// Linearized (Jacobian) doubling and interaction for FP64, 60 < N <= 128, in the column-strip scheme of vsm_strip128.hip:
+// Linearized (Jacobian) doubling and interaction in the column-strip scheme of vsm_strip128.hip.  FP64: the interaction for every
+// N <= 128, the doubling for N <= 48 and 60 < N <= 128 (49 <= N <= 60: vsm_striplin.hip); Float32 arrays: both for every N <= 128.
 //
 //   k_dbl128_lin<RT>   doubling_allparams_helper! (src/CoreRT/CoreKernel/doubling_lin.jl:216-339) + apply_D! with derivative
 //                      slots (:374-421): ALL doubling steps of one spectral point, forward + every active parameter, in one
@@ -641,16 +642,14 @@ int launch_ia128_lin(int N, int S, int P, const ia128_half<ST>& h, hipStream_t s
 // Which shapes land here.  The interaction: every N <= 128 (vsm_striplin.hip's k_ia_lin_half, 0.39 of peak for two rounds, lost to
 // k_ia128_lin<4> on the shapes both took -- 0.867 -> 0.726 ms per half at 2048 points of the C2 shape -- and is gone).  The doubling:
 // beyond the reach of vsm_striplin.hip's k_dbl_lin_multi (49 <= N <= 60 stays there: 12.99 vs 12.61 10^3 points/s on the C2 shape)
-// and N <= 48; the thresholds are build parameters so that tools/variants_lin128.sh can re-measure.
+// and N <= 48.  The upper threshold chooses between two live kernels and is a build parameter so that tools/variants_lin128.sh
+// can re-measure it.
 #ifndef VSM_LIN128_DBL_MIN
 #define VSM_LIN128_DBL_MIN 60
 #endif
-// ... and the shapes of one to three row tiles (N <= 48), where vsm_striplin.hip pads to 64 rows (N = 30: 27.7 -> 84.3 10^3 points/s,
-// N = 48: 20.0 -> 23.4, profiles/r04/shape_sweep_f64.txt)
-#ifndef VSM_LIN128_SMALL_MAX
-#define VSM_LIN128_SMALL_MAX 48
-#endif
-static bool lin128_small(int N) { return N >= 1 && N <= VSM_LIN128_SMALL_MAX; }
+// ... and the shapes of one to three row tiles (N <= 48), where vsm_striplin.hip padded to 64 rows (N = 30: 27.7 -> 84.3 10^3 points/s,
+// N = 48: 20.0 -> 23.4, profiles/r04/shape_sweep_f64.txt).  A constant: the KS = 9 .. 12 instantiations that took them are gone.
+static bool lin128_small(int N) { return N >= 1 && N <= 48; }
 bool strip128_lin_dbl_supported(int N) { return (N > VSM_LIN128_DBL_MIN && N <= 128) || lin128_small(N); }
 
 

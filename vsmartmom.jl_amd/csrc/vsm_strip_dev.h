@@ -545,11 +545,6 @@ __device__ __forceinline__ void load_strip_global_c8_finish(sstrip& x, const spo
     x.v[j >> 1][2 * (j & 1) + 1] = xw[p.l15 * XS8 + p.kq + 4];
   }
 }
-__device__ __forceinline__ void load_strip_global_c8(sstrip& x, const double* __restrict__ g, int N, const spos& p,
-                                                     double* __restrict__ xw) {
-  load_strip_global_c8_issue(x, g, N, p);
-  load_strip_global_c8_finish(x, p, xw);
-}
 __device__ __forceinline__ void store_strip_global_c8(double* __restrict__ g, const sstrip& x, int N, const spos& p,
                                                       double* __restrict__ xw) {
   const int c = p.lane >> 2, q = p.lane & 3;

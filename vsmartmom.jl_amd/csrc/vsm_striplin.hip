@@ -1,4 +1,4 @@
-// Linearized doubling step, column-strip form (FP64, 32 < N <= 60): ONE launch per doubling step does the forward
+// Linearized doubling step, column-strip form (FP64, 49 <= N <= 60, KS = 13, 14, 15): ONE launch per doubling step does the forward
 // recurrences AND the derivative recurrences of every active parameter of doubling_allparams_helper!
 // (doubling_lin.jl:216-339) for one spectral point per workgroup, instead of ~40 batched-operator launches that
 // each stream three [N,N,S] arrays through HBM.
@@ -166,9 +166,9 @@ __device__ __forceinline__ void store_strip_global_c(double* __restrict__ g, con
   }
 }
 
-// First of the two spare columns that carry the riders: N rounded up to a k-step -- and never below the 4 KS contraction range
-// of the instantiation (8 <= N <= 32 runs on KS = 9: riders at columns 36, 37; inside the range they would be contracted against
-// the zero padding rows of every right operand, harmless only as long as every source vector is finite).
+// First of the two spare columns that carry the riders: N rounded up to a k-step.  (The dispatchers send only 4 KS - 3 <= N <= 4 KS
+// to instantiation KS, so this is always kend; the N <= 32 clause dates from round 3, when smaller shapes ran padded on KS = 9 and
+// the riders had to stay outside its 4 KS contraction range.)
 template <int KS>
 __device__ __forceinline__ int rider_base(int N) {
   const int kend = ((N + 3) >> 2) << 2;
@@ -629,34 +629,23 @@ int VSM_CAT(launch_dbl_lin_multi_, VSM_STRIP_KS)(int N, int S, int PA, int nd, i
 
 #else  // ---- dispatcher object -----------------------------------------------------------------------------------------
 
-VSM_STRIPLIN_DECL(9)
-VSM_STRIPLIN_DECL(10)
-VSM_STRIPLIN_DECL(11)
-VSM_STRIPLIN_DECL(12)
 VSM_STRIPLIN_DECL(13)
 VSM_STRIPLIN_DECL(14)
 VSM_STRIPLIN_DECL(15)
 
-// The linearized strip kernels take 8 <= N <= 60; shapes below 33 run on the KS = 9 instantiation (k padded to 36: the strips'
-// padding rows are zero, so the extra k-steps add nothing) -- a quarter of the MFMA work is useful at N = 30, but the operator
-// chain these shapes would take instead is launch-bound (wall ratio 20 against a flop ratio of 3.4 at N = 30).
-static bool strip_lin_supported(int N) { return N >= 8 && (strip_supported(N) || N <= 32); }
-static int strip_lin_ks(int N) { return N <= 32 ? 9 : (N + 3) / 4; }
-// One fused doubling step (forward + P parameters); VSM_ERR_UNSUPPORTED outside 32 < N <= 60 or when the added layer is
+// The linearized strip kernels take 49 <= N <= 60 (KS = 13, 14, 15); every other N <= 128 is vsm_strip128lin.hip's.
+static bool strip_lin_supported(int N) { return N > 48 && N <= 60; }
+// One fused doubling step (forward + P parameters); VSM_ERR_UNSUPPORTED outside 49 <= N <= 60 or when the added layer is
 // not the plain [N,N,S] layout.
 int strip_doubling_lin_step(int N, int S, int P, double* expk, double* ekl, const added<double>& a,
                             const added_lin<double>& al, hipStream_t st) {
   static const bool off = ab_switch("VSM_NO_STRIP_LIN");
   if (off || !strip_lin_supported(N) || a.mat_stride != (long long)N * N || al.mat_stride != (long long)N * N)
     return VSM_ERR_UNSUPPORTED;
-  switch (strip_lin_ks(N)) {
+  switch ((N + 3) / 4) {
 #define VSM_CASE(KS) \
   case KS:           \
     return VSM_CAT(launch_dbl_lin_step_, KS)(N, S, P, expk, ekl, a, al, st);
-    VSM_CASE(9)
-    VSM_CASE(10)
-    VSM_CASE(11)
-    VSM_CASE(12)
     VSM_CASE(13)
     VSM_CASE(14)
     VSM_CASE(15)
@@ -673,14 +662,10 @@ int strip_doubling_lin_multi(int N, int S, int P, int nd, int ns, double* expk, 
   static const bool off = ab_switch("VSM_NO_STRIP_LIN") || ab_switch("VSM_NO_LIN_MULTI");
   if (off || P < 1 || P > 3 || nd < 1 || !strip_lin_supported(N) || a.mat_stride != (long long)N * N || al.mat_stride != (long long)N * N)
     return VSM_ERR_UNSUPPORTED;
-  switch (strip_lin_ks(N)) {
+  switch ((N + 3) / 4) {
 #define VSM_CASE(KS) \
   case KS:           \
     return VSM_CAT(launch_dbl_lin_multi_, KS)(N, S, P, nd, ns, expk, ekl, a, al, st);
-    VSM_CASE(9)
-    VSM_CASE(10)
-    VSM_CASE(11)
-    VSM_CASE(12)
     VSM_CASE(13)
     VSM_CASE(14)
     VSM_CASE(15)
