@@ -1345,6 +1345,20 @@ int vsm_mie_nai2(int nquad, int n_max, int n_mu, double n_r, double n_i, double 
                  const double* wx, const double* wr, const double* mu, const double* w_mu, double* greek, double* bulk_f,
                  double* scal, double* work, void* stream);
 
+/* Linearized Mie (src/Scattering/compute_NAI2_lin.jl): vsm_mie_nai2 with the derivatives of all its outputs with respect to four
+ * parameters, slots (n_r, n_i, p, q); p, q are the two parameters of the size distribution that the caller's wx_dot / wr_dot
+ * [2, nquad] differentiate (d wx / d p, d wx / d q at fixed nodes, and 4 pi r_i^2 times them) -- for the reference's
+ * LogNormal(mu, sigma): mu = ln r_m, sigma = ln sigma_g.  The three stages carry D_n', a_n', b_n', S1', S2' for n_r only: all of
+ * them are holomorphic in m = n_r - i n_i, so d / d n_i = -i d / d n_r.
+ * greek, bulk_f, scal: bit for bit those of vsm_mie_nai2 on the same inputs.  greek_dot [4, 6, n_mu], bulk_f_dot [4, 4, n_mu]
+ * (unnormalised, like bulk_f), scal_dot [4, 3] = (C_sca', C_ext', ssa') per slot.  work: vsm_mie_lin_work_elems doubles.
+ * Contract, limits and return codes: those of vsm_mie_nai2. */
+size_t vsm_mie_lin_work_elems(int nquad, int n_max, int n_mu);
+int vsm_mie_nai2_lin(int nquad, int n_max, int n_mu, double n_r, double n_i, double k_wave, const double* x, const int* nmax_i,
+                     const double* wx, const double* wr, const double* wx_dot, const double* wr_dot, const double* mu,
+                     const double* w_mu, double* greek, double* bulk_f, double* scal, double* greek_dot, double* bulk_f_dot,
+                     double* scal_dot, double* work, void* stream);
+
 /* ---- delta-BGE truncation of a phase matrix (src/Scattering/truncate_phase.jl) ----------------------------------------------------
  * Fits l_max truncated Greek coefficients to a phase matrix given by n_mu of them (Sanghavi & Stephens 2015): beta on the Legendre
  * polynomials, gamma and epsilon on fac_l P2_l (l = 2 .. l_max - 1), each a weighted least-squares fit over the Gauss-Legendre

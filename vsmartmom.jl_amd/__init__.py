@@ -26,7 +26,9 @@ Sub-modules
     Scattering      Mie aerosol optics (scattering: LogNormal / TabulatedSizeDistribution, Aerosol, make_mie_model,
                     compute_aerosol_optical_properties = the Siewert NAI-2 path on the device, FP64: a size distribution and a
                     refractive index in, a host_model.AerosolOptics with k, C_ext, C_sca out; truncate_phase /
-                    truncate_phase_lowconf with DeltaBGE(l_max, delta_angle) = the delta-BGE fit on the device, f_trunc = 1 - c0)
+                    truncate_phase_lowconf with DeltaBGE(l_max, delta_angle) = the delta-BGE fit on the device, f_trunc = 1 - c0;
+                    compute_aerosol_optical_properties_lin = linearized Mie: the same optics and a host_model.LinAerosolOptics
+                    with their derivatives for (n_r, n_i, ln r_m, ln sigma_g))
     parallel        spectral-axis sharding over the GPUs of one node (torch.distributed / RCCL)
 """
 from . import _lib, host_model  # noqa: F401

@@ -195,6 +195,8 @@ _SIGS = {
                                     "{R}", _P, _P, _P, _I, _P, _P]),
     "vsm_mie_work_elems": (_SZ, [_I, _I, _I]),
     "vsm_mie_nai2": (_I, [_I, _I, _I, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "vsm_mie_lin_work_elems": (_SZ, [_I, _I, _I]),
+    "vsm_mie_nai2_lin": (_I, [_I, _I, _I, C.c_double, C.c_double, C.c_double] + [_P] * 16),
     "vsm_dbge_work_elems": (_SZ, [_I, _I]),
     "vsm_truncate_dbge": (_I, [_I, _I, _I, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vsm_test_lds_mm_{T}": (_I, [_I, _I, _P, _P, _P, _P]),

@@ -903,8 +903,10 @@ class CoreScatteringOpticalPropertiesLin:
 @dataclass
 class LinAerosolOptics:
     """lin_aerosol_optics[iaer] (compEffectiveLayerProperties_lin.jl:330-395): derivatives of the aerosol's Greek coefficients,
-    single-scattering albedo and truncation factor with respect to the four Mie parameters (n_r, n_i, r_m, sigma_r).  Mie
-    theory (their producer) is upstream of the hot path: the numbers are inputs here."""
+    single-scattering albedo and truncation factor with respect to the four Mie parameters (n_r, n_i, r_m, sigma_r).  The
+    numbers are inputs here; Scattering.compute_aerosol_optical_properties_lin produces them on the device.  Slots 2 and 3 of
+    its result are d / d mu and d / d sigma with mu = ln r_m, sigma = ln sigma_g, the parameters of the reference's
+    LogNormal(log r_m, log sigma_g) and what the reference's linearized Mie differentiates; d / d r_m is slot 2 divided by r_m."""
     lin_greek_coefs: List[GreekCoefs]   # 4 entries
     ssa_dot: np.ndarray                 # [4]  (lin_aerosol_optics.ω̃̇)
     f_trunc_dot: np.ndarray             # [4]  (lin_aerosol_optics.ḟᵗ)

@@ -31,8 +31,18 @@ read), truncate_phase_lowconf the one it applies to analytic phase functions (th
 epsilon series of exact zeros from l = 2 on -- every scalar phase function -- stays exact zeros; the reference divides by
 f12 = 0 there and returns NaN.
 
-Not built: linearized Mie and linearized truncation (compute_NAI2_lin.jl / LinAerosolOptics, truncate_phase_lin.jl), l_max above
-128, PCW, the YAML `scattering:` block (io_yaml keeps refusing it).
+Linearized Mie (compute_NAI2_lin.jl, mie_helper_functions_lin.jl) through vsm_mie_nai2_lin: the same optics and, in the same
+call, their derivatives with respect to (n_r, n_i, mu, sigma), mu = ln r_m and sigma = ln sigma_g being the parameters of the
+reference's LogNormal(log r_m, log sigma_g), as a host_model.LinAerosolOptics that LinModel takes as it is.
+
+    (optics, lin_optics), = Scattering.compute_aerosol_optical_properties_lin(model, arch)
+    host_model.LinModel(tau_abs_dot, tau_aer_dot=..., lin_aerosol_optics=[lin_optics])
+
+The host adds the derivatives of the weights at fixed nodes (mie_lin_host_inputs); they deviate from the reference's on purpose
+(the reference normalises wx before it differentiates the normalisation and loses a factor 1 / sum).
+
+Not built: linearized truncation (truncate_phase_lin.jl; bulk_f_dot and the derivative coefficients are shaped for it), l_max
+above 128, PCW, the YAML `scattering:` block (io_yaml keeps refusing it).
 """
 from __future__ import annotations
 
@@ -80,13 +90,22 @@ class LogNormal:
 
 class TabulatedSizeDistribution:
     """Any other size distribution (gamma, bimodal, measured): radius nodes r [nquad] and the unnormalised weights pdf(r_i) w_r,i
-    of the caller's own quadrature.  The nodes are used as they are; r_max and nquad_radius of the model are not read."""
+    of the caller's own quadrature.  The nodes are used as they are; r_max and nquad_radius of the model are not read.
+    weights_dot [2, nquad] (optional, read by compute_aerosol_optical_properties_lin only): the derivatives of these unnormalised
+    weights with respect to two parameters of the caller's own choosing, which take slots 2 and 3; without it those slots are
+    exact zeros."""
 
-    def __init__(self, r: Sequence[float], weights: Sequence[float]):
+    def __init__(self, r: Sequence[float], weights: Sequence[float], weights_dot=None):
         self.r = np.array(r, dtype=np.float64).reshape(-1)
         self.weights = np.array(weights, dtype=np.float64).reshape(-1)
         if self.r.shape != self.weights.shape:
             raise _lib.VSMError("TabulatedSizeDistribution: %d radii, %d weights" % (len(self.r), len(self.weights)))
+        self.weights_dot = None
+        if weights_dot is not None:
+            self.weights_dot = np.array(weights_dot, dtype=np.float64)
+            if self.weights_dot.shape != (2, len(self.r)):
+                raise _lib.VSMError("TabulatedSizeDistribution: weights_dot of shape %r, not (2, %d)"
+                                    % (self.weights_dot.shape, len(self.r)))
 
 
 @dataclass
@@ -137,6 +156,19 @@ class MieAerosolOptics(H.AerosolOptics):
     bulk_f: Optional[np.ndarray] = None
 
 
+@dataclass
+class MieLinAerosolOptics(H.LinAerosolOptics):
+    """host_model.LinAerosolOptics from linearized Mie.  Slot order (n_r, n_i, mu, sigma) with mu = ln r_m, sigma = ln sigma_g --
+    what the reference differentiates (compute_w_x(lin, .) forms d / d mu and d / d sigma of LogNormal(mu, sigma)); d / d r_m is
+    slot 2 divided by r_m.  For a TabulatedSizeDistribution slots 2 and 3 are the two parameters of its weights_dot.
+    f_trunc_dot is exact zeros (f_trunc is 0 here).  k_dot, C_ext_dot, C_sca_dot [4]: derivatives of the bulk cross-sections
+    (k = C_ext); bulk_f_dot [4, 4, n_mu]: derivatives of the unnormalised bulk f11, f33, f12, f34 at the angle nodes."""
+    k_dot: Optional[np.ndarray] = None
+    C_ext_dot: Optional[np.ndarray] = None
+    C_sca_dot: Optional[np.ndarray] = None
+    bulk_f_dot: Optional[np.ndarray] = None
+
+
 # ---- mie_helper_functions.jl: the host part -------------------------------------------------------------------------------------
 def get_n_max(size_parameter: float) -> int:
     """mie_helper_functions.jl:22 (Sanghavi 2014 eq. 6); round to nearest, ties to even, as Julia's round(Int, .)."""
@@ -168,6 +200,38 @@ def compute_wx(size_distribution, w_r, r):
     """compute_w_x (mie_helper_functions.jl:511-521)."""
     wx = size_distribution.pdf(r) * w_r
     return wx / np.sum(wx)
+
+
+def weight_derivatives(r, raw, raw_dot):
+    """wx_dot, wr_dot [2, nquad] at fixed nodes from the unnormalised weights raw_i = pdf(r_i) w_r,i and their derivatives
+    raw_dot [2, nquad]: with S = sum raw and wx = raw / S,  wx_dot = (raw_dot - (sum raw_dot) wx) / S,  wr_dot = 4 pi r^2 wx_dot.
+    (The reference divides by sum(wx) = 1 where S belongs: DESIGN.md 6.)"""
+    total = np.sum(raw)
+    wx = raw / total
+    wx_dot = np.stack([(raw_dot[k] - np.sum(raw_dot[k]) * wx) / total for k in range(2)])
+    return wx_dot, 4 * math.pi * r ** 2 * wx_dot
+
+
+def lognormal_raw_dot(sd: LogNormal, r, raw):
+    """d raw / d mu = (ln r - mu) / sigma^2 raw,  d raw / d sigma = ((ln r - mu)^2 / sigma^3 - 1 / sigma) raw."""
+    d = np.log(r) - sd.mu
+    return np.stack([d / sd.sigma ** 2 * raw, (d ** 2 / sd.sigma ** 3 - 1 / sd.sigma) * raw])
+
+
+def mie_lin_host_inputs(model: MieModel):
+    """mie_host_inputs plus (wx_dot, wr_dot) [2, nquad]: the weights' derivatives with respect to (mu, sigma) of a LogNormal, with
+    respect to the two parameters of weights_dot of a TabulatedSizeDistribution (exact zeros without it)."""
+    h = mie_host_inputs(model)
+    sd = model.aerosol.size_distribution
+    if isinstance(sd, TabulatedSizeDistribution):
+        if sd.weights_dot is None:
+            return h, np.zeros((2, len(h.r))), np.zeros((2, len(h.r)))
+        raw, raw_dot = sd.weights, sd.weights_dot
+    else:
+        _, w_r = gauleg_log(int(model.nquad_radius), max(sd.quantile(1e-8), 1e-6 * model.r_max), float(model.r_max))
+        raw = sd.pdf(h.r) * w_r
+        raw_dot = lognormal_raw_dot(sd, h.r, raw)
+    return (h,) + weight_derivatives(h.r, raw, raw_dot)
 
 
 def mie_host_inputs(model: MieModel) -> MieHostInputs:
@@ -266,6 +330,52 @@ def compute_aerosol_optical_properties(model_or_list, architecture=None, truncat
         if truncation is not None:
             opt = _untruncated(opt) if fit is None else _collect_dbge(truncation, opt, fit)
         out.append(opt)
+    return out
+
+
+def launch_nai2_lin(model: MieModel, h: MieHostInputs, dev, dev_dot):
+    """Enqueues vsm_mie_nai2_lin on the current stream: (greek, bulk_f, scal, greek_dot [4, 6, n_mu], bulk_f_dot [4, 4, n_mu],
+    scal_dot [4, 3], work) device tensors; dev as for launch_nai2, dev_dot = (wx_dot, wr_dot) [2, nquad].  Nothing is synchronised."""
+    nq, like = len(h.x), dev[0]
+    new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=like.device)
+    greek, bulk_f, scal = new(6, h.n_mu), new(4, h.n_mu), new(3)
+    greek_dot, bulk_f_dot, scal_dot = new(4, 6, h.n_mu), new(4, 4, h.n_mu), new(4, 3)
+    elems = int(_lib.lib().vsm_mie_lin_work_elems(nq, h.n_max, h.n_mu))
+    if elems == 0:
+        raise _lib.VSMError("vsm_mie_lin_work_elems refuses nquad = %d, n_max = %d, n_mu = %d" % (nq, h.n_max, h.n_mu))
+    work = _lib.poison(new(elems))
+    x, nmax_i, wx, wr, mu, w_mu = dev
+    args = (x, nmax_i, wx, wr, dev_dot[0], dev_dot[1], mu, w_mu, greek, bulk_f, scal, greek_dot, bulk_f_dot, scal_dot, work)
+    _lib.check(_lib.lib().vsm_mie_nai2_lin(nq, h.n_max, h.n_mu, C.c_double(model.aerosol.n_r), C.c_double(model.aerosol.n_i),
+                                           C.c_double(h.k_wave), *[CR._ptr(t) for t in args], CR._stream_ptr()))
+    return greek, bulk_f, scal, greek_dot, bulk_f_dot, scal_dot, work
+
+
+def compute_aerosol_optical_properties_lin(model_or_list, architecture=None):
+    """compute_aerosol_optical_properties(lin, model) (compute_NAI2_lin.jl:16-279) for one MieModel or a list of them: a list of
+    (MieAerosolOptics, MieLinAerosolOptics) pairs.  The first is bit for bit what compute_aerosol_optical_properties returns; the
+    second holds the derivatives in the slot order (n_r, n_i, mu, sigma) -- see MieLinAerosolOptics -- and goes into
+    host_model.LinModel(lin_aerosol_optics=[...]) as it is.  All models are enqueued before the one synchronisation.  Truncation
+    is not linearized yet: truncate_phase on the first of a pair works as ever and carries no derivatives."""
+    models = [model_or_list] if isinstance(model_or_list, MieModel) else list(model_or_list)
+    arch = architecture if architecture is not None else default_architecture()
+    CR._require_gpu(arch)
+    _lib.lib()
+    conv = array_type(arch)
+    hosts = [mie_lin_host_inputs(m) for m in models]     # (every refusal before the first launch)
+    devs = [(device_inputs(h, conv), (conv(wxd), conv(wrd))) for h, wxd, wrd in hosts]
+    runs = [launch_nai2_lin(m, h, d, dd) for m, (h, _, _), (d, dd) in zip(models, hosts, devs)]
+    synchronize_if_gpu()
+    out = []
+    for (h, _, _), (greek, bulk_f, scal, greek_dot, bulk_f_dot, scal_dot, _work) in zip(hosts, runs):
+        g, gd, sd = to_host(greek), to_host(greek_dot), to_host(scal_dot)
+        c_sca, c_ext, ssa = (float(v) for v in to_host(scal))
+        opt = MieAerosolOptics(H.GreekCoefs(*(g[i].copy() for i in range(6))), ssa, 0.0, k=c_ext, C_ext=c_ext, C_sca=c_sca,
+                               mu=h.mu, bulk_f=to_host(bulk_f))
+        lin = MieLinAerosolOptics([H.GreekCoefs(*(gd[s, i].copy() for i in range(6))) for s in range(4)], sd[:, 2].copy(),
+                                  np.zeros(4), k_dot=sd[:, 1].copy(), C_ext_dot=sd[:, 1].copy(), C_sca_dot=sd[:, 0].copy(),
+                                  bulk_f_dot=to_host(bulk_f_dot))
+        out.append((opt, lin))
     return out
 
 
