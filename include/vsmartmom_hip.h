@@ -1388,6 +1388,25 @@ int vsm_truncate_dbge(int n_mu, int l_max, int lowconf, double cos_delta, const 
                       const double* scal, const double* mu, const double* w_mu, double* greek_t, double* scal_t, int* info,
                       double* work, void* stream);
 
+/* Linearized delta-BGE truncation (src/Scattering/truncate_phase_lin.jl): vsm_truncate_dbge and, in the same call, the
+ * derivatives of its outputs with respect to four parameters (the slots of vsm_mie_nai2_lin), FP64.  Only the all-nodes fit is
+ * linearized: lowconf must be 0.  With A x = b the normal equations of a system and B the basis rows sqrt(w) B_i / f that
+ * vsm_truncate_dbge already forms (A = B B^T), x' = A^-1 B g with g_k = (f'_k / f_k) (2 (B^T x)_k - sqrt(w_k)): no second Gram
+ * product; the four right-hand sides go through the factor the forward solve holds.
+ * Inputs beyond vsm_truncate_dbge's: greek_dot [4, 6, n_mu]; bulk_f_dot [4, 4, n_mu] and scal_dot [4, 3] of vsm_mie_nai2_lin,
+ * which come with bulk_f and scal or not at all (without them f' is reconstructed from greek_dot as f is from greek).
+ * Outputs: greek_t, scal_t, info -- bit for bit those of vsm_truncate_dbge on the same inputs --, greek_t_dot [4, 6, l_max],
+ * scal_t_dot [4, 2] = (c0', f_trunc' = -c0') per slot.  A skipped system (info = 1) has exact-zero derivative rows; a failed
+ * one (2) NaN rows; a non-finite derivative of a solved system sets its info to 2 and its derivative rows to NaN.
+ * work: vsm_dbge_lin_work_elems(n_mu, l_max) doubles, uninitialised (0 for refused shapes).  Contract and return codes: those
+ * of vsm_truncate_dbge; lowconf != 0 returns VSM_ERR_UNSUPPORTED; a null greek_dot, greek_t_dot or scal_t_dot, or bulk_f_dot /
+ * scal_dot without bulk_f / scal (or the reverse) VSM_ERR_INVALID_ARG; all before any launch. */
+size_t vsm_dbge_lin_work_elems(int n_mu, int l_max);
+int vsm_truncate_dbge_lin(int n_mu, int l_max, int lowconf, double cos_delta, const double* greek, const double* bulk_f,
+                          const double* scal, const double* greek_dot, const double* bulk_f_dot, const double* scal_dot,
+                          const double* mu, const double* w_mu, double* greek_t, double* scal_t, double* greek_t_dot,
+                          double* scal_t_dot, int* info, double* work, void* stream);
+
 /* ---- diagnostics used by the parity tests -------------------------------- */
 /* Runs the LDS-resident MFMA tile product used inside the fused kernels on plain
  * [N,N,S] inputs: C = A*B.  (Checks fragment layouts / swizzle independently.) */

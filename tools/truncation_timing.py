@@ -8,7 +8,15 @@
 each with device events around `--reps` back-to-back calls, three windows after a warm-up;
   call          compute_aerosol_optical_properties(model, arch, truncation=DeltaBGE(l_max)) as a user calls it, host clock
   host fit      what a caller had before: the untruncated call's D2H, then tests/truncation_oracle.py's numpy fit (a CPU figure, for
-                scale only)"""
+                scale only)
+--lin: the linearized chain at the same shape, the same windows:
+  mie lin            vsm_mie_nai2_lin alone
+  mie lin + bulk     the linearized Mie call and vsm_truncate_dbge_lin on its device arrays: what
+                     compute_truncated_aerosol_optical_properties_lin enqueues
+  lin reconstruct    vsm_truncate_dbge_lin alone, f and f' rebuilt from the 761 coefficients and their derivatives
+  lin bulk           vsm_truncate_dbge_lin alone on bulk_f, scal, bulk_f_dot, scal_dot
+  fwd bulk           vsm_truncate_dbge alone, for the ratio
+  8 x (mie + bulk)   what the call replaces: eight forward Mie + truncation calls for central differences"""
 import argparse
 import os
 import sys
@@ -27,6 +35,7 @@ ap.add_argument("--nquad", type=int, default=2500)
 ap.add_argument("--r-max", type=float, default=30.0)
 ap.add_argument("--reps", type=int, default=20)
 ap.add_argument("--l-max", type=int, nargs="+", default=[20, 64])
+ap.add_argument("--lin", action="store_true")
 a = ap.parse_args()
 
 if not torch.cuda.is_available():
@@ -60,6 +69,40 @@ def line(what, t):
     return min(t)
 
 
+def lin_timing():
+    conv = vsm.Architectures.array_type(arch)
+    _, wx_dot, wr_dot = S.mie_lin_host_inputs(model)
+    dev_dot = (conv(wx_dot), conv(wr_dot))
+    run = S.launch_nai2_lin(model, h, dev, dev_dot)
+    g, b, s, gd, bd, sd = run[:6]
+    torch.cuda.synchronize()
+    line("mie", windows(lambda: S.launch_nai2(model, h, dev)))
+    t_lin = line("mie lin", windows(lambda: S.launch_nai2_lin(model, h, dev, dev_dot)))
+    for l_max in a.l_max:
+        print("l_max = %d" % l_max)
+
+        def both_lin():
+            r = S.launch_nai2_lin(model, h, dev, dev_dot)
+            return r, S.launch_dbge_lin(h.n_mu, l_max, *r[:6], dev[4], dev[5])
+
+        def both():
+            r = S.launch_nai2(model, h, dev)
+            return r, S.launch_dbge(h.n_mu, l_max, 0, 1.0, r[0], r[1], r[2], dev[4], dev[5])
+
+        t_both = line("  mie lin + bulk", windows(both_lin))
+        line("  lin reconstruct", windows(lambda: S.launch_dbge_lin(h.n_mu, l_max, g, None, None, gd, None, None, dev[4], dev[5])))
+        t_lb = line("  lin bulk", windows(lambda: S.launch_dbge_lin(h.n_mu, l_max, g, b, s, gd, bd, sd, dev[4], dev[5])))
+        t_fb = line("  fwd bulk", windows(lambda: S.launch_dbge(h.n_mu, l_max, 0, 1.0, g, b, s, dev[4], dev[5])))
+        t_fd = line("  mie + bulk", windows(both))
+        print("  the linearized truncation adds %.4f ms to the %.4f ms linearized Mie call; alone it is %.2f x the forward fit; "
+              "8 x (mie + bulk) = %.4f ms against %.4f ms" % (t_both - t_lin, t_lin, t_lb / t_fb, 8 * t_fd, t_both))
+        (opt, lin), = S.compute_truncated_aerosol_optical_properties_lin(model, S.DeltaBGE(l_max), arch)
+        print("  c0 %.9f  f_trunc_dot %s  info %r" % (opt.c0, " ".join("%.6f" % v for v in lin.f_trunc_dot), opt.info))
+
+
+if a.lin:
+    lin_timing()
+    sys.exit(0)
 greek, bulk_f, scal, _work = S.launch_nai2(model, h, dev)
 torch.cuda.synchronize()
 t_mie = line("mie", windows(lambda: S.launch_nai2(model, h, dev)))

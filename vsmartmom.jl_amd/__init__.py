@@ -28,7 +28,9 @@ Sub-modules
                     refractive index in, a host_model.AerosolOptics with k, C_ext, C_sca out; truncate_phase /
                     truncate_phase_lowconf with DeltaBGE(l_max, delta_angle) = the delta-BGE fit on the device, f_trunc = 1 - c0;
                     compute_aerosol_optical_properties_lin = linearized Mie: the same optics and a host_model.LinAerosolOptics
-                    with their derivatives for (n_r, n_i, ln r_m, ln sigma_g))
+                    with their derivatives for (n_r, n_i, ln r_m, ln sigma_g); truncate_phase_lin /
+                    compute_truncated_aerosol_optical_properties_lin = the linearized delta-BGE fit: the truncated optics and
+                    their derivatives, f_trunc_dot = -c0_dot)
     parallel        spectral-axis sharding over the GPUs of one node (torch.distributed / RCCL)
 """
 from . import _lib, host_model  # noqa: F401

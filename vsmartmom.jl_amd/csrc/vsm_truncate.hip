@@ -3,6 +3,10 @@
 // applies to Mie optics) and truncate_phase_lowconf (the nodes outside the forward cone, weights (w / max(|f|, 1e-8))^2).
 //   vsm_dbge_work_elems  size of the caller's work buffer
 //   vsm_truncate_dbge    the three stages below on the caller's stream
+//   vsm_truncate_dbge_lin  the same and, behind them, stages 4 and 5: the derivatives of the outputs for four parameters
+//                        (truncate_phase_lin.jl).  With B the rows of stage 1 (A = B B^T), t = B^T x and
+//                        g_slot = (f'_slot / f) (2 t - sqrt(w)):  b' - A' x = B g_slot, so x'_slot = A^-1 B g_slot -- no second
+//                        Gram product; the four right-hand sides go through the factor stage 3 holds.
 // The three fits (beta on P, gamma and epsilon on fac P2) are weighted least-squares problems over the angle nodes.  Each is solved
 // through its normal equations [A | b] = B B^T, where B holds the basis functions scaled by the square root of the node's weight
 // and one more row that turns the same product into the right-hand side.
@@ -36,6 +40,7 @@ __host__ __device__ inline long long dbge_up(long long a, long long m) { return 
 struct dbge_layout {
   long long RP, KP, CH;                  // padded rows of a system (basis + right-hand side), padded angles, angle chunks
   long long o_basis, o_part, total;
+  long long o_fd, o_fac, o_x, o_rhs, total_lin;      // the linearized call's four more regions, behind the forward call's
 };
 static dbge_layout dbge_make_layout(int n_mu, int l_max) {
   dbge_layout L;
@@ -45,10 +50,17 @@ static dbge_layout dbge_make_layout(int n_mu, int l_max) {
   L.o_basis = 0;
   L.o_part = L.o_basis + 3 * L.RP * L.KP;
   L.total = L.o_part + L.CH * 3 * L.RP * L.RP;
+  L.o_fd = L.total;                                  // [system][slot][angle] f', [system][angle] 1 / f, [angle] sqrt(w)
+  L.o_fac = L.o_fd + 16 * L.KP;                      // [system][row][column] the factored triangles
+  L.o_x = L.o_fac + 3LL * l_max * l_max;             // [system][row] the solutions
+  L.o_rhs = L.o_x + 3LL * l_max;                     // [chunk][system][slot][row] the chunks' B g
+  L.total_lin = L.o_rhs + L.CH * 3 * 4 * L.RP;
   return L;
 }
 // stage 3's LDS: the lower triangle of [A | b] as rows of odd stride, and the solution
 static size_t dbge_lds_bytes(int l_max) { return ((size_t)(l_max + 1) * ((l_max + 1) | 1) + (l_max + 1)) * sizeof(double); }
+// stage 5's LDS: the same triangle and four right-hand sides
+static size_t dbge_lin_lds_bytes(int l_max) { return dbge_lds_bytes(l_max) + (size_t)4 * l_max * sizeof(double); }
 
 // does the series c[2 .. n) hold exact zeros only?  (the same answer in every thread of the workgroup)
 __device__ __forceinline__ bool dbge_zero_series(const double* __restrict__ c, int n) {
@@ -60,20 +72,36 @@ __device__ __forceinline__ bool dbge_zero_series(const double* __restrict__ c, i
 // ---------------------------------------------------------------------------------------------------------------------
 // stage 1
 // ---------------------------------------------------------------------------------------------------------------------
+// LIN (lowconf = 0 only): a grid of five rows of workgroups.  Row 0 is the forward workgroup and also leaves 1 / f per system
+// (planes 12 .. 14 of fd) and sqrt(w) (plane 15), exact zeros in the padding angles and in a skipped system.  Row 1 + slot runs the
+// same text on the slot's derivatives up to f11, f12, f34 -- bulk_f_dot and scal_dot as k_mie_greek<true> normalises them, or the
+// reconstruction from the slot's n_mu derivative coefficients -- and leaves them as f' [system][slot][angle] (planes 0 .. 11),
+// exact zeros in the padding angles.
+template <bool LIN>
 __global__ __launch_bounds__(64) void k_dbge_basis(int n_mu, int l_max, int lowconf, double cos_delta, long long RP, long long KP,
                                                   const double* __restrict__ greek, const double* __restrict__ bulk_f,
                                                   const double* __restrict__ scal, const double* __restrict__ mu_,
                                                   const double* __restrict__ w_mu, double* __restrict__ basis,
-                                                  int* __restrict__ info) {
+                                                  int* __restrict__ info, const double* __restrict__ greek_dot,
+                                                  const double* __restrict__ bulk_f_dot, const double* __restrict__ scal_dot,
+                                                  double* __restrict__ fd) {
   __shared__ double cf[5][64];          // per moment of a chunk of 64: 1 / (l + 1), 1 / (l - 1) of the recurrences, then fac and the coefficients
   const int lane = threadIdx.x;
   const long long ia = (long long)blockIdx.x * 64 + lane;
-  const bool skip_g = dbge_zero_series(greek + 2LL * n_mu, n_mu);
-  const bool skip_e = dbge_zero_series(greek + 4LL * n_mu, n_mu);
-  if (blockIdx.x == 0 && lane == 0) {
-    info[0] = 0;
-    info[1] = skip_g ? 1 : 0;
-    info[2] = skip_e ? 1 : 0;
+  const int slot = LIN ? (int)blockIdx.y - 1 : -1;             // (the same value in every thread)
+  const double* __restrict__ series = greek;                   // the coefficients the reconstruction sums
+  if constexpr (LIN) {
+    if (slot >= 0) series = greek_dot + (long long)slot * 6 * n_mu;
+  }
+  bool skip_g = false, skip_e = false;
+  if (slot < 0) {
+    skip_g = dbge_zero_series(greek + 2LL * n_mu, n_mu);
+    skip_e = dbge_zero_series(greek + 4LL * n_mu, n_mu);
+    if (blockIdx.x == 0 && lane == 0) {
+      info[0] = 0;
+      info[1] = skip_g ? 1 : 0;
+      info[2] = skip_e ? 1 : 0;
+    }
   }
   const bool live = ia < n_mu;
   const double x = live ? mu_[ia] : 0.0;
@@ -86,6 +114,15 @@ __global__ __launch_bounds__(64) void k_dbge_basis(int n_mu, int l_max, int lowc
       f11 = bulk_f[ia] / csca;
       f12 = bulk_f[2LL * n_mu + ia] / csca;
       f34 = bulk_f[3LL * n_mu + ia] / csca;
+      if constexpr (LIN) {
+        if (slot >= 0) {                 // (f' - f C_sca') / C_sca of the unnormalised f', as k_mie_greek<true> has it
+          const double* bd = bulk_f_dot + (long long)slot * 4 * n_mu;
+          const double cd = scal_dot[3 * slot];
+          f11 = (bd[ia] - f11 * cd) / csca;
+          f12 = (bd[2LL * n_mu + ia] - f12 * cd) / csca;
+          f34 = (bd[3LL * n_mu + ia] - f34 * cd) / csca;
+        }
+      }
     }
   } else {                               // reconstruct_phase over all n_mu moments
     double p0a = 0.0, p0b = 0.0, p2a = 0.0, p2b = 0.0;
@@ -98,9 +135,9 @@ __global__ __launch_bounds__(64) void k_dbge_basis(int n_mu, int l_max, int lowc
       __syncthreads();
       cf[0][lane] = c >= 1 ? 1.0 / (dl + 1) : 0.0;
       cf[1][lane] = c >= 3 ? 1.0 / (dl - 1) : 0.0;
-      cf[2][lane] = in ? greek[1LL * n_mu + c] : 0.0;
-      cf[3][lane] = in ? fac * greek[2LL * n_mu + c] : 0.0;
-      cf[4][lane] = in ? fac * greek[4LL * n_mu + c] : 0.0;
+      cf[2][lane] = in ? series[1LL * n_mu + c] : 0.0;
+      cf[3][lane] = in ? fac * series[2LL * n_mu + c] : 0.0;
+      cf[4][lane] = in ? fac * series[4LL * n_mu + c] : 0.0;
       __syncthreads();
       const int nj = min(64, n_mu - c0);
       for (int j = 0; j < nj; ++j) {
@@ -116,6 +153,14 @@ __global__ __launch_bounds__(64) void k_dbge_basis(int n_mu, int l_max, int lowc
         f12 += p2 * cf[3][j];
         f34 += p2 * cf[4][j];
       }
+    }
+  }
+  if constexpr (LIN) {
+    if (slot >= 0) {                     // a derivative row of workgroups ends here
+      fd[(0 + slot) * KP + ia] = live ? f11 : 0.0;
+      fd[(4 + slot) * KP + ia] = live ? f12 : 0.0;
+      fd[(8 + slot) * KP + ia] = live ? f34 : 0.0;
+      return;
     }
   }
   // the square root of the node's weight in each system, and the entry of the row that makes the right-hand side
@@ -137,6 +182,13 @@ __global__ __launch_bounds__(64) void k_dbge_basis(int n_mu, int l_max, int lowc
   }
   if (skip_g) s[1] = r[1] = 0.0;
   if (skip_e) s[2] = r[2] = 0.0;
+  if constexpr (LIN) {
+    const double f[3] = {f11, f12, f34};
+    const bool keep[3] = {live, live && !skip_g, live && !skip_e};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) fd[(12 + k) * KP + ia] = keep[k] ? 1.0 / f[k] : 0.0;
+    fd[15 * KP + ia] = live ? sqrt(w) : 0.0;
+  }
   const long long plane = RP * KP;
   double* b0 = basis + ia;               // (ia < KP: the grid is KP / 64 workgroups)
   double p0a = 0.0, p0b = 0.0, p2a = 0.0, p2b = 0.0;
@@ -217,10 +269,14 @@ __global__ __launch_bounds__(64) void k_dbge_gram(int l_max, long long RP, long 
 // ---------------------------------------------------------------------------------------------------------------------
 // stage 3
 // ---------------------------------------------------------------------------------------------------------------------
+// LIN: a solved system also leaves its factored triangle (column j as l_ij d_j, the diagonal d) in fac [system][row][column] and its
+// solution in xsol [system][row], for stages 4 and 5.
+template <bool LIN>
 __global__ __launch_bounds__(DBGE_NT) void k_dbge_solve(int n_mu, int l_max, long long RP, long long CH,
                                                        const double* __restrict__ part, const double* __restrict__ greek,
                                                        double* __restrict__ greek_t, double* __restrict__ scal_t,
-                                                       int* __restrict__ info) {
+                                                       int* __restrict__ info, double* __restrict__ fac,
+                                                       double* __restrict__ xsol) {
   extern __shared__ __align__(16) unsigned char lds_raw[];
   __shared__ int bad;
   const int t = threadIdx.x, sys = blockIdx.x;
@@ -282,6 +338,16 @@ __global__ __launch_bounds__(DBGE_NT) void k_dbge_solve(int n_mu, int l_max, lon
   }
   const bool fail_all = failed || __syncthreads_or(nonfinite) != 0 || (sys == 0 && !(xs[0] != 0.0));
   if (t == 0) info[sys] = fail_all ? 2 : 0;
+  if constexpr (LIN) {
+    if (!fail_all) {
+      double* fo = fac + (long long)sys * l_max * l_max;
+      for (int e = t; e < n * n; e += DBGE_NT) {
+        const int i = e / n, k = e % n;
+        if (k <= i) fo[i * l_max + k] = A[i * ST + k];
+      }
+      for (int i = t; i < n; i += DBGE_NT) xsol[sys * l_max + i] = xs[i];
+    }
+  }
   const double qnan = __builtin_nan("");
   if (sys != 0) {
     for (int l = t; l < l_max; l += DBGE_NT) gt[l] = l < off ? 0.0 : (fail_all ? qnan : xs[l - off]);
@@ -303,6 +369,153 @@ __global__ __launch_bounds__(DBGE_NT) void k_dbge_solve(int n_mu, int l_max, lon
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// stage 4 (linearized call)
+// ---------------------------------------------------------------------------------------------------------------------
+// One workgroup per (chunk of 128 angles, system).  t_k = sum_j B_jk x_j, a lane per node and half of the rows each, the halves
+// added in a fixed order; g_slot,k = f'_slot,k (1 / f_k) (2 t_k - sqrt(w_k)); then the chunk's B g for every row of the system on
+// v_mfma_f64_16x16x4, one wave per tile of 16 rows: the A fragment is stage 2's (a lane reads consecutive doubles of its row),
+// the B fragment holds g in columns 0 .. 3 and zeros in the other twelve.
+__global__ __launch_bounds__(256) void k_dbge_lin_rhs(int l_max, long long RP, long long KP, const double* __restrict__ basis,
+                                                     const double* __restrict__ fd, const double* __restrict__ xsol,
+                                                     const int* __restrict__ info, double* __restrict__ rhs) {
+  using MM = mfma<double>;
+  __shared__ double xs[VSM_DBGE_MAX_L];
+  __shared__ double th[DBGE_KC];
+  __shared__ double g[4][DBGE_KC];
+  const int t = threadIdx.x, sys = blockIdx.y;
+  const long long chunk = blockIdx.x;
+  if (info[sys] != 0) return;                                  // skipped or failed: stage 5 reads nothing of it
+  const int n = sys == 0 ? l_max : l_max - 2;
+  for (int j = t; j < n; j += 256) xs[j] = xsol[sys * l_max + j];
+  __syncthreads();
+  const int k = t & (DBGE_KC - 1), half = t >> 7;
+  const double* bk = basis + sys * RP * KP + chunk * DBGE_KC + k;
+  double tk = 0.0;
+#pragma unroll 4
+  for (int j = half; j < n; j += 2) tk += bk[(long long)j * KP] * xs[j];
+  if (half) th[k] = tk;
+  __syncthreads();
+  if (!half) {
+    tk += th[k];
+    const double* fk = fd + chunk * DBGE_KC + k;
+    const double u = (2.0 * tk - fk[15 * KP]) * fk[(12 + sys) * KP];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) g[q][k] = fk[(4 * sys + q) * KP] * u;
+  }
+  __syncthreads();
+  const int lane = t & 63, wave = t >> 6, col = lane & 15, kq = lane >> 4;
+  const int tiles = (n + 15) / 16;                             // (tiles * 16 <= RP: RP = up(l_max + 1, 16))
+  for (int ti = wave; ti < tiles; ti += 4) {
+    const double* pa = basis + (sys * RP + ti * 16 + col) * KP + chunk * DBGE_KC + kq * DBGE_KQ;
+    MM::acc_t acc = acc_zero<double>();
+    double na = pa[0];
+#pragma unroll 8
+    for (int s = 0; s < DBGE_KQ; ++s) {
+      const double a = na;
+      const int sn = s + 1 < DBGE_KQ ? s + 1 : s;
+      na = pa[sn];
+      const double b = col < 4 ? g[col & 3][kq * DBGE_KQ + s] : 0.0;
+      acc = MM::mma(a, b, acc);
+    }
+    if (col < 4) {
+      double* out = rhs + ((chunk * 3 + sys) * 4 + col) * RP + ti * 16;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) out[MM::crow(lane, r)] = acc[r];
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// stage 5 (linearized call)
+// ---------------------------------------------------------------------------------------------------------------------
+// One workgroup per system: the factor back into LDS, the chunks' B g added in chunk order, the four right-hand sides through
+// L, D, L^T together (thread = (row, slot)), and the closing formulas of truncate_phase_lin.jl:183-207.
+__global__ __launch_bounds__(DBGE_NT) void k_dbge_lin_solve(int n_mu, int l_max, long long RP, long long CH,
+                                                           const double* __restrict__ fac, const double* __restrict__ rhs,
+                                                           const double* __restrict__ greek_dot,
+                                                           const double* __restrict__ greek_t, const double* __restrict__ scal_t,
+                                                           double* __restrict__ greek_t_dot, double* __restrict__ scal_t_dot,
+                                                           int* __restrict__ info) {
+  extern __shared__ __align__(16) unsigned char lds_raw[];
+  const int t = threadIdx.x, sys = blockIdx.x;
+  const int n = sys == 0 ? l_max : l_max - 2;
+  const int off = sys == 0 ? 0 : 2;
+  const int ST = (l_max + 1) | 1;
+  double* A = reinterpret_cast<double*>(lds_raw);
+  double* R = A + (size_t)(l_max + 1) * ST + (l_max + 1);      // [row][slot]
+  const int fam = sys == 0 ? 1 : sys == 1 ? 2 : 4;
+  const int status = info[sys];                                // (the same value in every thread)
+  if (sys != 0 && status == 1) {                               // a series of exact zeros keeps exact-zero derivatives
+    for (int e = t; e < 4 * l_max; e += DBGE_NT) greek_t_dot[((long long)(e / l_max) * 6 + fam) * l_max + e % l_max] = 0.0;
+    return;
+  }
+  bool fail = status != 0;
+  if (!fail) {
+    const double* fi = fac + (long long)sys * l_max * l_max;
+    for (int e = t; e < n * n; e += DBGE_NT) {
+      const int i = e / n, k = e % n;
+      if (k <= i) A[i * ST + k] = fi[i * l_max + k];
+    }
+    for (int e = t; e < 4 * n; e += DBGE_NT) {
+      const int i = e >> 2, q = e & 3;
+      const double* p = rhs + ((long long)sys * 4 + q) * RP + i;
+      double v = 0.0;
+      for (long long ch = 0; ch < CH; ++ch) v += p[ch * 12 * RP];
+      R[e] = v;
+    }
+    __syncthreads();
+    const int q = t & 3, i0 = t >> 2;
+    // y = L^-1 r:  column j of L is u_ij / d_j
+    for (int j = 0; j < n - 1; ++j) {
+      const double c = R[4 * j + q] / A[j * ST + j];           // (final since the barrier that ended step j - 1)
+      for (int i = j + 1 + i0; i < n; i += DBGE_NT / 4) R[4 * i + q] -= A[i * ST + j] * c;
+      __syncthreads();
+    }
+    // L^T x = D^-1 y backwards:  x_j = (y_j - sum_{i > j} u_ij x_i) / d_j; R[j] keeps the numerator, nobody writes it after step j
+    for (int j = n - 1; j > 0; --j) {
+      const double xj = R[4 * j + q] / A[j * ST + j];
+      for (int i = i0; i < j; i += DBGE_NT / 4) R[4 * i + q] -= A[j * ST + i] * xj;
+      __syncthreads();
+    }
+    int nonfinite = 0;
+    for (int e = t; e < 4 * n; e += DBGE_NT) {
+      const double x = R[e] / A[(e >> 2) * ST + (e >> 2)];
+      nonfinite |= !(fabs(x) <= 1.79769313486231570815e308);
+    }
+    fail = __syncthreads_or(nonfinite) != 0;
+    for (int e = t; e < 4 * n; e += DBGE_NT) R[e] = R[e] / A[(e >> 2) * ST + (e >> 2)];     // (each element by its own thread)
+    __syncthreads();
+    if (fail && t == 0) info[sys] = 2;
+  }
+  const double qnan = __builtin_nan("");
+  if (sys != 0) {
+    for (int e = t; e < 4 * l_max; e += DBGE_NT) {
+      const int q = e / l_max, l = e % l_max;
+      greek_t_dot[((long long)q * 6 + fam) * l_max + l] = l < off ? 0.0 : (fail ? qnan : R[4 * (l - off) + q]);
+    }
+    return;
+  }
+  // truncate_phase_lin.jl:183-207
+  const double c0 = scal_t[0];
+  for (int e = t; e < 4 * l_max; e += DBGE_NT) {
+    const int q = e / l_max, l = e % l_max;
+    const double* gd = greek_dot + (long long)q * 6 * n_mu;
+    double* gtd = greek_t_dot + (long long)q * 6 * l_max;
+    const double xd = fail ? qnan : R[4 * l + q], cd = fail ? qnan : R[q];
+    const double cut = gd[1LL * n_mu + l] - xd;                // beta' - x'
+    gtd[0LL * l_max + l] = (gd[0LL * n_mu + l] - cut - greek_t[0LL * l_max + l] * cd) / c0;
+    gtd[1LL * l_max + l] = (xd - greek_t[1LL * l_max + l] * cd) / c0;
+    gtd[3LL * l_max + l] = (gd[3LL * n_mu + l] - cut - greek_t[3LL * l_max + l] * cd) / c0;
+    gtd[5LL * l_max + l] = (gd[5LL * n_mu + l] - cut - greek_t[5LL * l_max + l] * cd) / c0;
+  }
+  if (t < 4) {
+    const double cd = fail ? qnan : R[t];
+    scal_t_dot[2 * t] = cd;
+    scal_t_dot[2 * t + 1] = -cd;
+  }
+}
+
 }  // namespace vsm
 
 using namespace vsm;
@@ -314,37 +527,101 @@ extern "C" size_t vsm_dbge_work_elems(int n_mu, int l_max) {
   return (size_t)dbge_make_layout(n_mu, l_max).total;
 }
 
+extern "C" size_t vsm_dbge_lin_work_elems(int n_mu, int l_max) {
+  if (!dbge_shape_ok(n_mu, l_max)) return 0;
+  return (size_t)dbge_make_layout(n_mu, l_max).total_lin;
+}
+
+// the refusals the two entries share, in the forward entry's order
+static int dbge_check(const char* fn, int n_mu, int l_max, int lowconf, double cos_delta, const double* bulk_f, const double* scal,
+                      bool pointers) {
+  if (l_max > VSM_DBGE_MAX_L) {
+    set_error("%s: l_max = %d above VSM_DBGE_MAX_L = %d", fn, l_max, VSM_DBGE_MAX_L);
+    return VSM_ERR_UNSUPPORTED;
+  }
+  VSM_REQUIRE(l_max >= 3, "%s: l_max = %d < 3", fn, l_max);
+  VSM_REQUIRE(n_mu > l_max, "%s: n_mu = %d <= l_max = %d (nothing to truncate)", fn, n_mu, l_max);
+  VSM_REQUIRE(lowconf >= 0 && lowconf <= n_mu, "%s: lowconf = %d is no count of the %d nodes", fn, lowconf, n_mu);
+  VSM_REQUIRE(lowconf == 0 || lowconf >= l_max, "%s: %d nodes below cos_delta = %g for l_max = %d unknowns", fn, lowconf, cos_delta,
+              l_max);
+  VSM_REQUIRE((bulk_f == nullptr) == (scal == nullptr), "%s: bulk_f and scal come together or not at all", fn);
+  VSM_REQUIRE(pointers, "%s: null pointer", fn);
+  VSM_REQUIRE((n_mu + DBGE_KC - 1) / DBGE_KC <= 65535, "%s: n_mu = %d above %d", fn, n_mu, 65535 * DBGE_KC);
+  return VSM_OK;
+}
+
 extern "C" int vsm_truncate_dbge(int n_mu, int l_max, int lowconf, double cos_delta, const double* greek, const double* bulk_f,
                                  const double* scal, const double* mu, const double* w_mu, double* greek_t, double* scal_t,
                                  int* info, double* work, void* stream) {
-  if (l_max > VSM_DBGE_MAX_L) {
-    set_error("vsm_truncate_dbge: l_max = %d above VSM_DBGE_MAX_L = %d", l_max, VSM_DBGE_MAX_L);
-    return VSM_ERR_UNSUPPORTED;
-  }
-  VSM_REQUIRE(l_max >= 3, "vsm_truncate_dbge: l_max = %d < 3", l_max);
-  VSM_REQUIRE(n_mu > l_max, "vsm_truncate_dbge: n_mu = %d <= l_max = %d (nothing to truncate)", n_mu, l_max);
-  VSM_REQUIRE(lowconf >= 0 && lowconf <= n_mu, "vsm_truncate_dbge: lowconf = %d is no count of the %d nodes", lowconf, n_mu);
-  VSM_REQUIRE(lowconf == 0 || lowconf >= l_max, "vsm_truncate_dbge: %d nodes below cos_delta = %g for l_max = %d unknowns", lowconf,
-              cos_delta, l_max);
-  VSM_REQUIRE((bulk_f == nullptr) == (scal == nullptr), "vsm_truncate_dbge: bulk_f and scal come together or not at all");
-  VSM_REQUIRE(greek && mu && w_mu && greek_t && scal_t && info && work, "vsm_truncate_dbge: null pointer");
+  int rc = dbge_check("vsm_truncate_dbge", n_mu, l_max, lowconf, cos_delta, bulk_f, scal,
+                      greek && mu && w_mu && greek_t && scal_t && info && work);
+  if (rc) return rc;
   const dbge_layout L = dbge_make_layout(n_mu, l_max);
-  VSM_REQUIRE(L.CH <= 65535, "vsm_truncate_dbge: n_mu = %d above %d", n_mu, 65535 * DBGE_KC);
-  const int rc = ensure_dyn_lds(reinterpret_cast<const void*>(k_dbge_solve), dbge_lds_bytes(VSM_DBGE_MAX_L),
-                                "hipFuncSetAttribute(k_dbge_solve)");
+  rc = ensure_dyn_lds(reinterpret_cast<const void*>(k_dbge_solve<false>), dbge_lds_bytes(VSM_DBGE_MAX_L),
+                      "hipFuncSetAttribute(k_dbge_solve)");
   if (rc) return rc;
   hipStream_t st = as_stream(stream);
   double* basis = work + L.o_basis;
   double* part = work + L.o_part;
-  hipLaunchKernelGGL(k_dbge_basis, dim3((unsigned)(L.KP / 64)), dim3(64), 0, st, n_mu, l_max, lowconf, cos_delta, L.RP, L.KP, greek,
-                     bulk_f, scal, mu, w_mu, basis, info);
+  const double* none = nullptr;
+  hipLaunchKernelGGL(k_dbge_basis<false>, dim3((unsigned)(L.KP / 64)), dim3(64), 0, st, n_mu, l_max, lowconf, cos_delta, L.RP, L.KP,
+                     greek, bulk_f, scal, mu, w_mu, basis, info, none, none, none, (double*)nullptr);
   VSM_LAUNCH_CHECK("k_dbge_basis");
   const unsigned T = (unsigned)(L.RP / 16);
   hipLaunchKernelGGL(k_dbge_gram, dim3(T * (T + 1) / 2, (unsigned)L.CH, 3), dim3(64), 0, st, l_max, L.RP, L.KP, (const double*)basis,
                      (const int*)info, part);
   VSM_LAUNCH_CHECK("k_dbge_gram");
-  hipLaunchKernelGGL(k_dbge_solve, dim3(3), dim3(DBGE_NT), dbge_lds_bytes(l_max), st, n_mu, l_max, L.RP, L.CH, (const double*)part,
-                     greek, greek_t, scal_t, info);
+  hipLaunchKernelGGL(k_dbge_solve<false>, dim3(3), dim3(DBGE_NT), dbge_lds_bytes(l_max), st, n_mu, l_max, L.RP, L.CH,
+                     (const double*)part, greek, greek_t, scal_t, info, (double*)nullptr, (double*)nullptr);
   VSM_LAUNCH_CHECK("k_dbge_solve");
   return VSM_OK;
 }
+
+extern "C" int vsm_truncate_dbge_lin(int n_mu, int l_max, int lowconf, double cos_delta, const double* greek, const double* bulk_f,
+                                     const double* scal, const double* greek_dot, const double* bulk_f_dot, const double* scal_dot,
+                                     const double* mu, const double* w_mu, double* greek_t, double* scal_t, double* greek_t_dot,
+                                     double* scal_t_dot, int* info, double* work, void* stream) {
+  const char* fn = "vsm_truncate_dbge_lin";
+  if (l_max <= VSM_DBGE_MAX_L && lowconf != 0) {
+    set_error("%s: lowconf = %d: only the all-nodes fit is linearized", fn, lowconf);
+    return VSM_ERR_UNSUPPORTED;
+  }
+  int rc = dbge_check(fn, n_mu, l_max, lowconf, cos_delta, bulk_f, scal,
+                      greek && greek_dot && mu && w_mu && greek_t && scal_t && greek_t_dot && scal_t_dot && info && work);
+  if (rc) return rc;
+  VSM_REQUIRE((bulk_f_dot == nullptr) == (bulk_f == nullptr) && (scal_dot == nullptr) == (bulk_f == nullptr),
+              "%s: bulk_f_dot and scal_dot come with bulk_f and scal or not at all", fn);
+  const dbge_layout L = dbge_make_layout(n_mu, l_max);
+  rc = ensure_dyn_lds(reinterpret_cast<const void*>(k_dbge_solve<true>), dbge_lds_bytes(VSM_DBGE_MAX_L),
+                      "hipFuncSetAttribute(k_dbge_solve<lin>)");
+  if (rc) return rc;
+  rc = ensure_dyn_lds(reinterpret_cast<const void*>(k_dbge_lin_solve), dbge_lin_lds_bytes(VSM_DBGE_MAX_L),
+                      "hipFuncSetAttribute(k_dbge_lin_solve)");
+  if (rc) return rc;
+  hipStream_t st = as_stream(stream);
+  double* basis = work + L.o_basis;
+  double* part = work + L.o_part;
+  double* fd = work + L.o_fd;
+  double* fac = work + L.o_fac;
+  double* xsol = work + L.o_x;
+  double* rhs = work + L.o_rhs;
+  hipLaunchKernelGGL(k_dbge_basis<true>, dim3((unsigned)(L.KP / 64), 5), dim3(64), 0, st, n_mu, l_max, 0, cos_delta, L.RP, L.KP, greek,
+                     bulk_f, scal, mu, w_mu, basis, info, greek_dot, bulk_f_dot, scal_dot, fd);
+  VSM_LAUNCH_CHECK("k_dbge_basis<lin>");
+  const unsigned T = (unsigned)(L.RP / 16);
+  hipLaunchKernelGGL(k_dbge_gram, dim3(T * (T + 1) / 2, (unsigned)L.CH, 3), dim3(64), 0, st, l_max, L.RP, L.KP, (const double*)basis,
+                     (const int*)info, part);
+  VSM_LAUNCH_CHECK("k_dbge_gram");
+  hipLaunchKernelGGL(k_dbge_solve<true>, dim3(3), dim3(DBGE_NT), dbge_lds_bytes(l_max), st, n_mu, l_max, L.RP, L.CH,
+                     (const double*)part, greek, greek_t, scal_t, info, fac, xsol);
+  VSM_LAUNCH_CHECK("k_dbge_solve<lin>");
+  hipLaunchKernelGGL(k_dbge_lin_rhs, dim3((unsigned)L.CH, 3), dim3(256), 0, st, l_max, L.RP, L.KP, (const double*)basis,
+                     (const double*)fd, (const double*)xsol, (const int*)info, rhs);
+  VSM_LAUNCH_CHECK("k_dbge_lin_rhs");
+  hipLaunchKernelGGL(k_dbge_lin_solve, dim3(3), dim3(DBGE_NT), dbge_lin_lds_bytes(l_max), st, n_mu, l_max, L.RP, L.CH,
+                     (const double*)fac, (const double*)rhs, greek_dot, (const double*)greek_t, (const double*)scal_t, greek_t_dot,
+                     scal_t_dot, info);
+  VSM_LAUNCH_CHECK("k_dbge_lin_solve");
+  return VSM_OK;
+}
+

@@ -41,8 +41,14 @@ reference's LogNormal(log r_m, log sigma_g), as a host_model.LinAerosolOptics th
 The host adds the derivatives of the weights at fixed nodes (mie_lin_host_inputs); they deviate from the reference's on purpose
 (the reference normalises wx before it differentiates the normalisation and loses a factor 1 / sum).
 
-Not built: linearized truncation (truncate_phase_lin.jl; bulk_f_dot and the derivative coefficients are shaped for it), l_max
-above 128, PCW, the YAML `scattering:` block (io_yaml keeps refusing it).
+Linearized truncation (truncate_phase_lin.jl) through vsm_truncate_dbge_lin: the truncated coefficients, f_trunc = 1 - c0 and
+their derivatives in one call, for an aerosol whose series does not fit into l_trunc.
+
+    (optics, lin_optics), = Scattering.compute_truncated_aerosol_optical_properties_lin(model, Scattering.DeltaBGE(20), arch)
+    optics, lin_optics    = Scattering.truncate_phase_lin(Scattering.DeltaBGE(20), any_optics, any_lin_optics, arch)
+
+Not built: the linearized low-confidence variant (the reference has none), l_max above 128, PCW, the YAML `scattering:` block
+(io_yaml keeps refusing it).
 """
 from __future__ import annotations
 
@@ -355,27 +361,57 @@ def compute_aerosol_optical_properties_lin(model_or_list, architecture=None):
     """compute_aerosol_optical_properties(lin, model) (compute_NAI2_lin.jl:16-279) for one MieModel or a list of them: a list of
     (MieAerosolOptics, MieLinAerosolOptics) pairs.  The first is bit for bit what compute_aerosol_optical_properties returns; the
     second holds the derivatives in the slot order (n_r, n_i, mu, sigma) -- see MieLinAerosolOptics -- and goes into
-    host_model.LinModel(lin_aerosol_optics=[...]) as it is.  All models are enqueued before the one synchronisation.  Truncation
-    is not linearized yet: truncate_phase on the first of a pair works as ever and carries no derivatives."""
+    host_model.LinModel(lin_aerosol_optics=[...]) as it is.  All models are enqueued before the one synchronisation.  This call
+    does not truncate: truncate_phase_lin on a pair, or compute_truncated_aerosol_optical_properties_lin, does."""
+    return compute_truncated_aerosol_optical_properties_lin(model_or_list, None, architecture)
+
+
+def _collect_nai2_lin(h: MieHostInputs, run):
+    """After the synchronisation: the (MieAerosolOptics, MieLinAerosolOptics) pair of one launch_nai2_lin."""
+    greek, bulk_f, scal, greek_dot, bulk_f_dot, scal_dot, _work = run
+    g, gd, sd = to_host(greek), to_host(greek_dot), to_host(scal_dot)
+    c_sca, c_ext, ssa = (float(v) for v in to_host(scal))
+    opt = MieAerosolOptics(H.GreekCoefs(*(g[i].copy() for i in range(6))), ssa, 0.0, k=c_ext, C_ext=c_ext, C_sca=c_sca,
+                           mu=h.mu, bulk_f=to_host(bulk_f))
+    lin = MieLinAerosolOptics([H.GreekCoefs(*(gd[s, i].copy() for i in range(6))) for s in range(4)], sd[:, 2].copy(),
+                              np.zeros(4), k_dot=sd[:, 1].copy(), C_ext_dot=sd[:, 1].copy(), C_sca_dot=sd[:, 0].copy(),
+                              bulk_f_dot=to_host(bulk_f_dot))
+    return opt, lin
+
+
+def compute_truncated_aerosol_optical_properties_lin(model_or_list, truncation, architecture=None):
+    """compute_aerosol_optical_properties_lin and truncate_phase_lin in one pass over the device: each model's
+    vsm_truncate_dbge_lin is enqueued directly behind its vsm_mie_nai2_lin, on the device arrays greek, bulk_f, scal, greek_dot,
+    bulk_f_dot and scal_dot, and one synchronisation brings the whole list back.  A list of (TruncatedAerosolOptics,
+    TruncatedLinAerosolOptics) pairs, bit for bit those of truncate_phase_lin on compute_aerosol_optical_properties_lin's pairs
+    (which are their `untruncated`).  truncation: DeltaBGE(l_max, .) or NoTruncation(); None returns the untruncated
+    (MieAerosolOptics, MieLinAerosolOptics) pairs themselves -- compute_aerosol_optical_properties_lin is that call."""
     models = [model_or_list] if isinstance(model_or_list, MieModel) else list(model_or_list)
     arch = architecture if architecture is not None else default_architecture()
     CR._require_gpu(arch)
     _lib.lib()
+    if truncation is not None:
+        _check_method(truncation)
     conv = array_type(arch)
     hosts = [mie_lin_host_inputs(m) for m in models]     # (every refusal before the first launch)
     devs = [(device_inputs(h, conv), (conv(wxd), conv(wrd))) for h, wxd, wrd in hosts]
-    runs = [launch_nai2_lin(m, h, d, dd) for m, (h, _, _), (d, dd) in zip(models, hosts, devs)]
+    runs, fits = [], []
+    for m, (h, _, _), (d, dd) in zip(models, hosts, devs):
+        runs.append(launch_nai2_lin(m, h, d, dd))
+        fit = None
+        if isinstance(truncation, DeltaBGE) and h.n_mu > truncation.l_max:
+            fit = launch_dbge_lin(h.n_mu, int(truncation.l_max), *runs[-1][:6], d[4], d[5])
+        fits.append(fit)
     synchronize_if_gpu()
     out = []
-    for (h, _, _), (greek, bulk_f, scal, greek_dot, bulk_f_dot, scal_dot, _work) in zip(hosts, runs):
-        g, gd, sd = to_host(greek), to_host(greek_dot), to_host(scal_dot)
-        c_sca, c_ext, ssa = (float(v) for v in to_host(scal))
-        opt = MieAerosolOptics(H.GreekCoefs(*(g[i].copy() for i in range(6))), ssa, 0.0, k=c_ext, C_ext=c_ext, C_sca=c_sca,
-                               mu=h.mu, bulk_f=to_host(bulk_f))
-        lin = MieLinAerosolOptics([H.GreekCoefs(*(gd[s, i].copy() for i in range(6))) for s in range(4)], sd[:, 2].copy(),
-                                  np.zeros(4), k_dot=sd[:, 1].copy(), C_ext_dot=sd[:, 1].copy(), C_sca_dot=sd[:, 0].copy(),
-                                  bulk_f_dot=to_host(bulk_f_dot))
-        out.append((opt, lin))
+    for (h, _, _), run, fit in zip(hosts, runs, fits):
+        opt, lin = _collect_nai2_lin(h, run)
+        if truncation is None:
+            out.append((opt, lin))
+        elif fit is None:
+            out.append((_untruncated(opt), _untruncated_lin(lin)))
+        else:
+            out.append(_collect_dbge_lin(truncation, opt, lin, fit))
     return out
 
 
@@ -417,6 +453,20 @@ class TruncatedAerosolOptics(H.AerosolOptics):
     C_ext: Optional[float] = None
     C_sca: Optional[float] = None
     info: tuple = ()
+
+
+@dataclass
+class TruncatedLinAerosolOptics(H.LinAerosolOptics):
+    """host_model.LinAerosolOptics after truncate_phase_lin: lin_greek_coefs of l_max entries per slot, ssa_dot unchanged,
+    f_trunc_dot = -c0_dot -- what host_model.createAeroLin's delta-M scaling reads --, the method, and the derivatives that went
+    in.  k_dot, C_ext_dot, C_sca_dot are carried over where they have them.  LinModel(lin_aerosol_optics=[...]) takes it as it
+    is."""
+    c0_dot: Optional[np.ndarray] = None
+    method: object = field(default_factory=NoTruncation)
+    untruncated: Optional[H.LinAerosolOptics] = None
+    k_dot: Optional[np.ndarray] = None
+    C_ext_dot: Optional[np.ndarray] = None
+    C_sca_dot: Optional[np.ndarray] = None
 
 
 SYSTEMS = ("beta", "gamma", "epsilon")     # the three fits, in the order of vsm_truncate_dbge's info
@@ -544,3 +594,121 @@ def truncate_phase_lowconf(method, optics_or_list, architecture=None):
     """truncate_phase_lowconf(method, aero) (truncate_phase.jl:39, :56-128): the fit over the nodes with
     mu < cos(delta_angle), weights w / max(|f|, 1e-8) -- the variant the reference applies to analytic phase functions."""
     return _truncate(method, optics_or_list, architecture, True)
+
+
+# ---- truncate_phase_lin.jl ------------------------------------------------------------------------------------------------------
+def _carry_dot(lin):
+    return {n: getattr(lin, n) for n in ("k_dot", "C_ext_dot", "C_sca_dot") if getattr(lin, n, None) is not None}
+
+
+def _untruncated_lin(lin):
+    """truncate_phase(NoTruncation(), aero, lin_aero) (truncate_phase_lin.jl:221-229): the very same derivative arrays,
+    f_trunc_dot = 0."""
+    return TruncatedLinAerosolOptics(lin.lin_greek_coefs, lin.ssa_dot, np.zeros(4), c0_dot=np.zeros(4), method=NoTruncation(),
+                                     untruncated=lin, **_carry_dot(lin))
+
+
+def launch_dbge_lin(n_mu, l_max, greek, bulk_f, scal, greek_dot, bulk_f_dot, scal_dot, mu, w_mu):
+    """Enqueues vsm_truncate_dbge_lin on the current stream: (greek_t [6, l_max], scal_t [2], info [3], work, greek_t_dot
+    [4, 6, l_max], scal_t_dot [4, 2]) device tensors -- the first four as launch_dbge returns them.  Nothing is synchronised; the
+    inputs and the work buffer must outlive the work."""
+    dev = greek.device
+    new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
+    greek_t, scal_t, greek_t_dot, scal_t_dot = new(6, l_max), new(2), new(4, 6, l_max), new(4, 2)
+    info = torch.empty(3, dtype=torch.int32, device=dev)
+    elems = int(_lib.lib().vsm_dbge_lin_work_elems(n_mu, l_max))
+    if elems == 0:
+        raise _lib.VSMError("vsm_dbge_lin_work_elems refuses n_mu = %d, l_max = %d" % (n_mu, l_max))
+    work = _lib.poison(new(elems))
+    args = (greek, bulk_f, scal, greek_dot, bulk_f_dot, scal_dot, mu, w_mu, greek_t, scal_t, greek_t_dot, scal_t_dot, info, work)
+    _lib.check(_lib.lib().vsm_truncate_dbge_lin(n_mu, l_max, 0, C.c_double(1.0), *[CR._ptr(t) for t in args], CR._stream_ptr()))
+    return greek_t, scal_t, info, work, greek_t_dot, scal_t_dot
+
+
+def _collect_dbge_lin(method, optics, lin, fit):
+    """After the synchronisation: the status per system (a derivative that is not finite is a failed system too), then the
+    pair."""
+    trunc = _collect_dbge(method, optics, fit[:4])
+    gd, sd = to_host(fit[4]), to_host(fit[5])
+    lin_t = TruncatedLinAerosolOptics([H.GreekCoefs(*(gd[s, i].copy() for i in range(6))) for s in range(4)], lin.ssa_dot,
+                                      sd[:, 1].copy(), c0_dot=sd[:, 0].copy(), method=method, untruncated=lin, **_carry_dot(lin))
+    return trunc, lin_t
+
+
+def _greek_dot_matrix(lin, L):
+    """greek_dot [4, 6, L] of a LinAerosolOptics whose coefficient vectors must have the L entries of the optics'."""
+    slots = list(lin.lin_greek_coefs)
+    if len(slots) != 4:
+        raise _lib.VSMError("truncate_phase_lin: %d derivative slots, not 4" % len(slots))
+    out = np.empty((4, 6, L))
+    for s, g in enumerate(slots):
+        for c, v in enumerate((g.alpha, g.beta, g.gamma, g.delta, g.epsilon, g.zeta)):
+            v = np.asarray(v, dtype=np.float64).reshape(-1)
+            if len(v) != L:
+                raise _lib.VSMError("truncate_phase_lin: a derivative vector of slot %d has %d entries, the coefficients %d"
+                                    % (s, len(v), L))
+            out[s, c] = v
+    return out
+
+
+def truncate_phase_lin(method, optics_or_list, lin_optics_or_list, architecture=None):
+    """truncate_phase(method, aero, lin_aero) (truncate_phase_lin.jl:24-208) for one host_model.AerosolOptics with its
+    host_model.LinAerosolOptics, or two lists of them: (TruncatedAerosolOptics, TruncatedLinAerosolOptics), or a list of such
+    pairs.  The fit is truncate_phase's (all nodes, weights w / f^2); the first of a pair is what truncate_phase returns, bit for
+    bit.  A MieAerosolOptics with a MieLinAerosolOptics is fitted to bulk_f and differentiated through bulk_f_dot; every other
+    pair is reconstructed from its coefficients and their derivatives on the device -- f and f' always from the same source, so a
+    MieAerosolOptics paired with derivatives that bring no bulk_f_dot is reconstructed too (then, and only then, the first of
+    the pair differs from truncate_phase's in the last bits).  NoTruncation() or len(beta) <= l_max returns the very same arrays
+    with f_trunc = 0 and f_trunc_dot zeros.  All pairs are enqueued before the one synchronisation; a fit the device could not
+    solve, or whose derivatives are not finite, raises VSMError after it."""
+    single = isinstance(optics_or_list, H.AerosolOptics)
+    if single != isinstance(lin_optics_or_list, H.LinAerosolOptics):
+        raise _lib.VSMError("truncate_phase_lin: one AerosolOptics with one LinAerosolOptics, or two lists")
+    sets = [optics_or_list] if single else list(optics_or_list)
+    lins = [lin_optics_or_list] if single else list(lin_optics_or_list)
+    if len(sets) != len(lins):
+        raise _lib.VSMError("truncate_phase_lin: %d optics and %d linearized optics" % (len(sets), len(lins)))
+    arch = architecture if architecture is not None else default_architecture()
+    CR._require_gpu(arch)
+    _lib.lib()
+    _check_method(method)
+    conv = array_type(arch)
+    plans = []                                           # (every refusal before the first launch)
+    for o, lo in zip(sets, lins):
+        if not isinstance(o, H.AerosolOptics) or not isinstance(lo, H.LinAerosolOptics):
+            raise _lib.VSMError("truncate_phase_lin: (%s, %s) is no (host_model.AerosolOptics, host_model.LinAerosolOptics)"
+                                % (type(o).__name__, type(lo).__name__))
+        greek = _greek_matrix(o)
+        L = greek.shape[1]
+        greek_dot = _greek_dot_matrix(lo, L)
+        for row, name in ((2, "gamma"), (4, "epsilon")):
+            if not np.any(greek[row, 2:] != 0.0) and np.any(greek_dot[:, row, 2:] != 0.0):
+                raise _lib.VSMError("truncate_phase_lin: the %s series is exact zeros from l = 2 on (its fit is skipped) and its "
+                                    "derivative series is not" % name)
+        if isinstance(method, NoTruncation) or L <= method.l_max:
+            plans.append(None)
+            continue
+        mu, w_mu = gausslegendre(L)
+        bulk, bulk_dot, csca_dot = getattr(o, "bulk_f", None), getattr(lo, "bulk_f_dot", None), getattr(lo, "C_sca_dot", None)
+        mie = (bulk is not None and np.shape(bulk) == (4, L) and bool(getattr(o, "C_sca", None)) and bulk_dot is not None
+               and np.shape(bulk_dot) == (4, 4, L) and csca_dot is not None and np.shape(csca_dot) == (4,))
+        plans.append((L, greek, greek_dot, mie, mu, w_mu))
+    fits = []
+    for o, lo, plan in zip(sets, lins, plans):
+        if plan is None:
+            fits.append(None)
+            continue
+        L, greek, greek_dot, mie, mu, w_mu = plan
+        bulk_d = scal_d = bulk_dot_d = scal_dot_d = None
+        if mie:
+            f64 = lambda a: np.asarray(a, dtype=np.float64)
+            bulk_d, scal_d = conv(f64(o.bulk_f)), conv(np.array([o.C_sca, o.C_ext, o.ssa], dtype=np.float64))
+            c_ext_dot = lo.C_ext_dot if getattr(lo, "C_ext_dot", None) is not None else np.zeros(4)     # (not read by the fit)
+            scal_dot = np.ascontiguousarray(np.stack([f64(lo.C_sca_dot), f64(c_ext_dot), f64(lo.ssa_dot)], axis=1))
+            bulk_dot_d, scal_dot_d = conv(np.ascontiguousarray(f64(lo.bulk_f_dot))), conv(scal_dot)
+        inputs = (conv(greek), bulk_d, scal_d, conv(greek_dot), bulk_dot_d, scal_dot_d, conv(mu), conv(w_mu))
+        fits.append((launch_dbge_lin(L, int(method.l_max), *inputs), inputs))      # (inputs kept until the synchronisation)
+    synchronize_if_gpu()
+    out = [(_untruncated(o), _untruncated_lin(lo)) if fit is None else _collect_dbge_lin(method, o, lo, fit[0])
+           for o, lo, fit in zip(sets, lins, fits)]
+    return out[0] if single else out
