@@ -1407,6 +1407,45 @@ int vsm_truncate_dbge_lin(int n_mu, int l_max, int lowconf, double cos_delta, co
                           const double* mu, const double* w_mu, double* greek_t, double* scal_t, double* greek_t_dot,
                           double* scal_t_dot, int* info, double* work, void* stream);
 
+/* ---- Absorption: line-by-line cross-sections of a whole profile (src/Absorption/compute_absorption_cross_section.jl) ---------
+ * sigma(nu_i) of one gas at every layer of a (p, T, vmr) profile from a HITRAN line table, FP64: per line the pressure shift, the
+ * Lorentz and Doppler widths, S(T) (:108-153, constants of constants/constants.jl) and the index window of the wing cutoff; per
+ * grid point the sum of the line shapes of line_shape_batch! (:252-319) over the lines whose window holds the point, in table
+ * order.  Two launches on `stream` whatever Nz is:
+ *   1. one lane per (layer, line): the line parameters into work [Nz, nLines, VSM_ABS_WORK_FIELDS] = (nu, gamma_d, gamma_l, y, S,
+ *      S c / gamma_d, sqrt(ln 2) / gamma_d, (istart, istop) as two ints).  The window is the fractional 1-based index of nu -/+
+ *      wing_cutoff by linear interpolation on the grid (binary search), clamped to 1 / nSpec, rounded to nearest, ties to even;
+ *      nSpec = 1 gives [1, 1].  A line whose shifted window [nu - wing_cutoff, nu + wing_cutoff] misses the grid gets an EMPTY
+ *      window (the reference extrapolates its upper index with nSpec on both sides and gives such a line every point);
+ *   2. one workgroup per (tile of 256 points, layer), one point per lane: the lines with nu0 within the tile widened by one point,
+ *      wing_cutoff and delta_max p / p_ref (binary search on nu0) pass through LDS in chunks of VSM_ABS_CHUNK lines; a line whose
+ *      window misses all 64 points of a wave is skipped by that wave; scale[layer] multiplies the sum once.
+ * Device arrays (READ): grid [nSpec] wavenumbers, strictly ascending (not necessarily uniform); the table sorted by nu0 ascending:
+ * nu0, S_ref, gamma_air, gamma_self, n_air, delta_air, E_low [nLines] (E_low = -1: S(T) = S_ref), species [nLines] (int, 0 ..
+ * nSpecies - 1); molar_mass [nSpecies]; p (hPa), T (K), vmr_self, scale [Nz] (1 for sigma, vcd vmr for tau); qratio [Nz, nSpecies]
+ * = Q(T_ref) / Q(T), computed by the caller.  Scalars: wing_cutoff >= 0; delta_max >= max |delta_air| of the table (a smaller
+ * value drops lines); broadening VSM_ABS_DOPPLER / LORENTZ / VOIGT; cef VSM_ABS_CEF_* (read under Voigt only; the |x| + y and
+ * CPF12 region branches are taken per lane); accumulate 0: out is WRITTEN, 1: the result is added to out.
+ * out [Nz, nSpec].  work: vsm_absorption_work_elems(Nz, nLines) = VSM_ABS_WORK_FIELDS Nz nLines doubles, uninitialised (0 for
+ * Nz < 1 or nLines < 1).  No host synchronisation, no library scratch, no atomics; a call is bit-identical to its repetition.
+ * A size < 1, Nz > 65535, wing_cutoff or delta_max negative or NaN, a broadening, cef or accumulate outside its values or a null
+ * pointer return VSM_ERR_INVALID_ARG before any launch. */
+#define VSM_ABS_CHUNK 256
+#define VSM_ABS_WORK_FIELDS 8
+#define VSM_ABS_DOPPLER 0
+#define VSM_ABS_LORENTZ 1
+#define VSM_ABS_VOIGT 2
+#define VSM_ABS_CEF_HW32_VOIGT 0 /* HumlicekWeidemann32VoigtErrorFunction */
+#define VSM_ABS_CEF_HW32_SD 1    /* HumlicekWeidemann32SDErrorFunction */
+#define VSM_ABS_CEF_CPF12 2      /* CPF12ErrorFunction */
+int vsm_absorption_chunk(void); /* VSM_ABS_CHUNK of the loaded library */
+size_t vsm_absorption_work_elems(int Nz, int nLines);
+int vsm_absorption_xsec(int nSpec, int nLines, int nSpecies, int Nz, const double* grid, const double* nu0, const double* S_ref,
+                        const double* gamma_air, const double* gamma_self, const double* n_air, const double* delta_air,
+                        const double* E_low, const int* species, const double* molar_mass, const double* p, const double* T,
+                        const double* vmr_self, const double* scale, const double* qratio, double wing_cutoff, double delta_max,
+                        int broadening, int cef, int accumulate, double* out, double* work, void* stream);
+
 /* ---- diagnostics used by the parity tests -------------------------------- */
 /* Runs the LDS-resident MFMA tile product used inside the fused kernels on plain
  * [N,N,S] inputs: C = A*B.  (Checks fragment layouts / swizzle independently.) */

@@ -31,6 +31,10 @@ Sub-modules
                     with their derivatives for (n_r, n_i, ln r_m, ln sigma_g); truncate_phase_lin /
                     compute_truncated_aerosol_optical_properties_lin = the linearized delta-BGE fit: the truncated optics and
                     their derivatives, f_trunc_dot = -c0_dot)
+    Absorption      line-by-line gas absorption (absorption: HitranTable / read_hitran, Doppler / Lorentz / Voigt, three complex error
+                    functions, make_hitran_model, compute_absorption_cross_section = Voigt cross-sections of a whole (p, T, vmr)
+                    profile in one call on the device, FP64; compute_absorption_profile = tau_abs [nSpec, Nz] of a list of gases,
+                    summed on the device, and the gas slots of LinModel.tau_abs_dot)
     parallel        spectral-axis sharding over the GPUs of one node (torch.distributed / RCCL)
 """
 from . import _lib, host_model  # noqa: F401
@@ -48,6 +52,7 @@ from . import core_rt_flux_lin  # noqa: F401
 from . import core_rt_flux_raman  # noqa: F401
 from . import standalone_ss as StandaloneSS  # noqa: F401
 from . import scattering as Scattering  # noqa: F401
+from . import absorption as Absorption  # noqa: F401
 from . import raman_inputs  # noqa: F401
 from . import io_yaml  # noqa: F401
 from ._lib import VSMError, LIB_PATH  # noqa: F401

@@ -201,6 +201,9 @@ _SIGS = {
     "vsm_truncate_dbge": (_I, [_I, _I, _I, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vsm_dbge_lin_work_elems": (_SZ, [_I, _I]),
     "vsm_truncate_dbge_lin": (_I, [_I, _I, _I, C.c_double] + [_P] * 15),
+    "vsm_absorption_chunk": (_I, []),
+    "vsm_absorption_work_elems": (_SZ, [_I, _I]),
+    "vsm_absorption_xsec": (_I, [_I, _I, _I, _I] + [_P] * 15 + [C.c_double, C.c_double, _I, _I, _I, _P, _P, _P]),
     "vsm_test_lds_mm_{T}": (_I, [_I, _I, _P, _P, _P, _P]),
     "vsm_test_lds_inv_{T}": (_I, [_I, _I, _P, _P, _I, _P, _P]),
     "vsm_test_poison_lds": (_I, [_P]),
