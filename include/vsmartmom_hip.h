@@ -1446,6 +1446,43 @@ int vsm_absorption_xsec(int nSpec, int nLines, int nSpecies, int Nz, const doubl
                         const double* vmr_self, const double* scale, const double* qratio, double wing_cutoff, double delta_max,
                         int broadening, int cef, int accumulate, double* out, double* work, void* stream);
 
+/* ---- Linearized Absorption: d sigma / d(T, p, vmr_self) per layer, beside sigma (ours; the reference has no such derivative) ----
+ * The derivative of the function vsm_absorption_xsec evaluates, with the index windows [istart, istop] and, per (line, point), the
+ * region of the error function (Weideman / Humlicek I / II) frozen at the unperturbed state.  With term = pre F(x, y),
+ * x = sx (nu_i - nu): d term / d theta = pre (dlnpre_theta F + F_x x_theta + F_y y_theta), F_x = Re w', F_y = -Im w' under Voigt,
+ * w' the closed-form derivative of each approximant (never -2 z w + 2 i / sqrt(pi)); Doppler and Lorentz have elementary F.
+ *   T:        dlnpre = dlnS/dT - 1/(2T) (Lorentz: dlnS/dT), x_T = -x/(2T) (Lorentz: 0), y_T = -y (n_air + 1/2)/T (Lorentz: -n_air gamma_l/T)
+ *   p:        x_p = -sx delta_air / p_ref, y_p = y / p
+ *   vmr_self: y_v = sqrt(ln 2)/gamma_d (gamma_self - gamma_air) (p/p_ref) (T_ref/T)^n_air (Lorentz: without sqrt(ln 2)/gamma_d; Doppler: 0)
+ *   dlnS/dT = qratio_dlnT + c2 E_low / T^2 - (a/T) / expm1(a), a = c2 nu0 / T; 0 for E_low = -1.
+ * Four launches on `stream`: the two of vsm_absorption_xsec, unchanged, on the first VSM_ABS_WORK_FIELDS Nz nLines doubles of
+ * `work` -- `out` is bit for bit that call's --; k_abs_params_lin, one lane per (layer, line), which takes nu, the window, pre, sx
+ * and y from that record (so x, y, the windows and the regions are the forward's to the bit) and adds the five derivative factors,
+ * VSM_ABS_LIN_WORK_FIELDS doubles per (layer, line) behind the forward's; k_abs_accum_lin, decomposed as the forward's second
+ * kernel (one workgroup per (256 points, layer), binary search on nu0, LDS chunks of VSM_ABS_LIN_CHUNK lines, scalar window skip per
+ * wave, table-order sums), w and w' once per (line, point), three sums per lane.
+ * Inputs: those of vsm_absorption_xsec (p > 0), and qratio_dlnT [Nz, nSpecies] = d ln(Q(T_ref)/Q(T)) / dT.
+ * Outputs: out [Nz, nSpec] as vsm_absorption_xsec's; out_dT (K^-1), out_dp (hPa^-1), out_dvmr (1), each [Nz, nSpec] -- the three
+ * planes of one [3, Nz, nSpec] array or separate arrays (a caller that sums gases through `accumulate` shares the T and p planes
+ * and gives each gas a zeroed vmr plane).  scale[layer] and accumulate apply to all four outputs alike.
+ * work: vsm_absorption_lin_work_elems(Nz, nLines) = (VSM_ABS_WORK_FIELDS + VSM_ABS_LIN_WORK_FIELDS) Nz nLines doubles.
+ * Refusals, before any launch: those of vsm_absorption_xsec; a null qratio_dlnT or output plane; broadening = VSM_ABS_VOIGT with
+ * cef = VSM_ABS_CEF_CPF12 (not linearized: its region II is no analytic formula), all VSM_ERR_INVALID_ARG. */
+#define VSM_ABS_LIN_CHUNK 256
+#define VSM_ABS_LIN_WORK_FIELDS 10
+int vsm_absorption_lin_chunk(void);
+size_t vsm_absorption_lin_work_elems(int Nz, int nLines);
+int vsm_absorption_xsec_lin(int nSpec, int nLines, int nSpecies, int Nz, const double* grid, const double* nu0, const double* S_ref,
+                            const double* gamma_air, const double* gamma_self, const double* n_air, const double* delta_air,
+                            const double* E_low, const int* species, const double* molar_mass, const double* p, const double* T,
+                            const double* vmr_self, const double* scale, const double* qratio, const double* qratio_dlnT,
+                            double wing_cutoff, double delta_max, int broadening, int cef, int accumulate, double* out,
+                            double* out_dT, double* out_dp, double* out_dvmr, double* work, void* stream);
+/* profile slots of compute_absorption_profile_lin: out [K, Nz, nSpec] = dT [Nz, nSpec] T_dot [K, Nz] + dp [Nz, nSpec] p_dot [K, Nz];
+ * one launch on `stream`.  A size < 1, Nz or K > 65535 or a null pointer returns VSM_ERR_INVALID_ARG before it. */
+int vsm_absorption_profile_slots(int nSpec, int Nz, int K, const double* dT, const double* dp, const double* T_dot,
+                                 const double* p_dot, double* out, void* stream);
+
 /* ---- diagnostics used by the parity tests -------------------------------- */
 /* Runs the LDS-resident MFMA tile product used inside the fused kernels on plain
  * [N,N,S] inputs: C = A*B.  (Checks fragment layouts / swizzle independently.) */

@@ -34,7 +34,8 @@ Sub-modules
     Absorption      line-by-line gas absorption (absorption: HitranTable / read_hitran, Doppler / Lorentz / Voigt, three complex error
                     functions, make_hitran_model, compute_absorption_cross_section = Voigt cross-sections of a whole (p, T, vmr)
                     profile in one call on the device, FP64; compute_absorption_profile = tau_abs [nSpec, Nz] of a list of gases,
-                    summed on the device, and the gas slots of LinModel.tau_abs_dot)
+                    summed on the device, and the gas slots of LinModel.tau_abs_dot; compute_absorption_cross_section_lin /
+                    compute_absorption_profile_lin = the same with the analytic T, p and vmr_self derivatives of sigma and tau_abs)
     parallel        spectral-axis sharding over the GPUs of one node (torch.distributed / RCCL)
 """
 from . import _lib, host_model  # noqa: F401

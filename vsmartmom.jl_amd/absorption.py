@@ -11,6 +11,10 @@
                                                   vsm_absorption_xsec call
     compute_absorption_profile                    tau_abs [nSpec, Nz] of a list of gases, summed on the device, and with lin=True
                                                   the gas slots sigma_g vcd_dry of LinModel.tau_abs_dot
+    SLOTS, qoft_lin, compute_absorption_cross_section_lin, compute_absorption_profile_lin, AbsorptionProfileLin
+                                                  ours (the reference has no such derivative): sigma and d sigma / d(T, p, vmr_self)
+                                                  per layer in ONE vsm_absorption_xsec_lin call; tau_abs with dtau_dT, dtau_dp,
+                                                  dtau_dvmr_self[g] and profile slots that LinModel.tau_abs_dot takes
 
 Names follow the reference; its non-ASCII field names are spelled out: nu (νᵢ), S (Sᵢ), A (Aᵢ), gamma_air, gamma_self, E_low (E″),
 n_air, delta_air, g_upper (g′), g_lower (g″).
@@ -19,7 +23,7 @@ What stays on the host: reading and filtering the table, sorting it by nu0 (the 
 nu0 order), the partition-sum spline, one value per (layer, isotopologue).  Everything with a line or grid-point loop runs in
 csrc/vsm_absorption.hip.  No TIPS or molar-mass table ships with this package: `isotopologues` hands them in.
 
-Not built: InterpolationModel / ABSCO tables, CIA, MT_CKD, derivatives with respect to T and p, FP32, the Erfc* error functions
+Not built: InterpolationModel / ABSCO tables, CIA, MT_CKD, linearized CPF12, FP32, the Erfc* error functions
 (they need a complex erfcx) and HumlicekErrorFunction (no `w` method in the reference either).
 
 One deviation from the reference: a line whose pressure-shifted window misses the grid contributes nothing; the
@@ -277,6 +281,26 @@ def qoft(iso_data: IsotopologueData, T, T_ref=t_ref):
     return float(r[0]) if Tv.ndim == 0 else r
 
 
+def _spline_eval_derivative(t, u, z, x):
+    i = np.clip(np.searchsorted(t, x, side="right"), 1, len(t) - 1)
+    h = t[i] - t[i - 1]
+    return (-z[i - 1] * (t[i] - x) ** 2 / (2.0 * h) + z[i] * (x - t[i - 1]) ** 2 / (2.0 * h)
+            + (u[i] / h - z[i] * h / 6.0) - (u[i - 1] / h - z[i - 1] * h / 6.0))
+
+
+def qoft_lin(iso_data: IsotopologueData, T, T_ref=t_ref):
+    """(Q(T_ref) / Q(T), d/dT of it): qoft and the analytic derivative of the same natural spline, -Q(T_ref) Q'(T) / Q(T)^2.  The first
+    value is qoft's bit for bit; the same refusal."""
+    Tv = np.asarray(T, dtype=np.float64)
+    r = qoft(iso_data, Tv, T_ref)
+    z = _natural_spline_second_derivatives(iso_data.TT, iso_data.TQ)
+    q = _spline_eval(iso_data.TT, iso_data.TQ, z, np.atleast_1d(Tv))
+    dq = _spline_eval_derivative(iso_data.TT, iso_data.TQ, z, np.atleast_1d(Tv))
+    q_ref = _spline_eval(iso_data.TT, iso_data.TQ, z, np.asarray([float(T_ref)]))[0]
+    d = -q_ref * dq / (q * q)
+    return (r, float(d[0])) if Tv.ndim == 0 else (r, d)
+
+
 # ---- compute_absorption_cross_section.jl: the host part ------------------------------------------------------------------------------
 @dataclass
 class _Job:
@@ -293,6 +317,8 @@ class _Job:
     broadening: int
     cef: int
     reverse: bool                    # wavelength_flag: the result is reversed along the grid
+    species_keys: Sequence[Tuple[int, int]] = ()   # the (mol, iso) behind each species index
+    qratio_dlnT: Optional[np.ndarray] = None   # [Nz, nSpecies] d ln(Q(T_ref) / Q(T)) / dT: the linearized calls only
 
     @property
     def n_lines(self):
@@ -343,7 +369,7 @@ def _prepare(model: HitranModel, grid, pressure, temperature, wavelength_flag=Fa
     mass = np.asarray([model.isotopologues[k].molar_mass for k in keys] or [1.0], dtype=np.float64)
     dmax = float(np.max(np.abs(lines["delta_air"]))) if len(keep) else 0.0
     return _Job(grid=grid, lines=lines, molar_mass=mass, p=p, T=T, vmr_self=vmr, qratio=qratio, wing_cutoff=cutoff, delta_max=dmax,
-                broadening=model.broadening.code, cef=model.CEF.code, reverse=bool(wavelength_flag))
+                broadening=model.broadening.code, cef=model.CEF.code, reverse=bool(wavelength_flag), species_keys=tuple(keys))
 
 
 class _Device:
@@ -363,16 +389,20 @@ class _Device:
     def zeros(self, Nz, nSpec):
         return self.empty(Nz, nSpec).zero_()
 
-    def profile(self, job: _Job):
-        """The device arrays that do not depend on the scale: uploaded once per job."""
+    def profile(self, job: _Job, lin=False):
+        """The device arrays that do not depend on the scale: uploaded once per job.  lin: the work buffer of the linearized call
+        and qratio_dlnT beside qratio; such a handle serves xsec() too."""
         names = ("nu", "S", "gamma_air", "gamma_self", "n_air", "delta_air", "E_low", "species")
         dev = [self.conv(job.grid)] + [self.conv(job.lines[k]) for k in names]
         dev += [self.conv(a) for a in (job.molar_mass, job.p, job.T, job.vmr_self)]
-        elems = int(_lib.lib().vsm_absorption_work_elems(len(job.p), job.n_lines))
+        sizer = "vsm_absorption_lin_work_elems" if lin else "vsm_absorption_work_elems"
+        elems = int(getattr(_lib.lib(), sizer)(len(job.p), job.n_lines))
         if elems == 0:
-            raise _lib.VSMError("vsm_absorption_work_elems refuses Nz = %d, nLines = %d" % (len(job.p), job.n_lines))
+            raise _lib.VSMError("%s refuses Nz = %d, nLines = %d" % (sizer, len(job.p), job.n_lines))
         work = _lib.poison(torch.empty(elems, dtype=torch.float64, device=dev[0].device))
         h = dict(dev=dev, q=self.conv(job.qratio), work=work)
+        if lin:
+            h["qd"] = self.conv(job.qratio_dlnT)
         self.keep.append(h)
         return h
 
@@ -385,6 +415,31 @@ class _Device:
             len(job.grid), job.n_lines, len(job.molar_mass), len(job.p), *[CR._ptr(t) for t in d[:13]], CR._ptr(sc),
             CR._ptr(handle["q"]), C.c_double(job.wing_cutoff), C.c_double(job.delta_max), job.broadening, job.cef, int(accumulate),
             CR._ptr(out), CR._ptr(handle["work"]), CR._stream_ptr()))
+
+    def profile_lin(self, job: _Job):
+        return self.profile(job, lin=True)
+
+    def xsec_lin(self, job: _Job, handle, scale, out, out_dT, out_dp, out_dvmr, accumulate):
+        """Enqueues one vsm_absorption_xsec_lin: out as xsec's, and the three slot planes [Nz, nSpec] = (accumulate ? plane : 0) +
+        scale[layer] d sigma / d(T, p, vmr_self)."""
+        sc = self.conv(np.ascontiguousarray(scale, dtype=np.float64))
+        self.keep.append(sc)
+        d = handle["dev"]
+        _lib.check(_lib.lib().vsm_absorption_xsec_lin(
+            len(job.grid), job.n_lines, len(job.molar_mass), len(job.p), *[CR._ptr(t) for t in d[:13]], CR._ptr(sc),
+            CR._ptr(handle["q"]), CR._ptr(handle["qd"]), C.c_double(job.wing_cutoff), C.c_double(job.delta_max), job.broadening,
+            job.cef, int(accumulate), CR._ptr(out), CR._ptr(out_dT), CR._ptr(out_dp), CR._ptr(out_dvmr), CR._ptr(handle["work"]),
+            CR._stream_ptr()))
+
+    def profile_slots(self, dT, dp, T_dot, p_dot):
+        """Enqueues vsm_absorption_profile_slots: [K, Nz, nSpec] = dT T_dot[k] + dp p_dot[k] from the planes on the device."""
+        K, (Nz, nSpec) = len(T_dot), dT.shape
+        td, pd = self.conv(np.ascontiguousarray(T_dot, dtype=np.float64)), self.conv(np.ascontiguousarray(p_dot, dtype=np.float64))
+        out = torch.empty((K, Nz, nSpec), dtype=torch.float64, device=dT.device)
+        self.keep += [td, pd]
+        _lib.check(_lib.lib().vsm_absorption_profile_slots(nSpec, Nz, K, CR._ptr(dT), CR._ptr(dp), CR._ptr(td), CR._ptr(pd),
+                                                           CR._ptr(out), CR._stream_ptr()))
+        return out
 
     def fetch(self, outs):
         synchronize_if_gpu()
@@ -463,3 +518,131 @@ def compute_absorption_profile(models_and_vmrs, grid, p_full, T, vcd_dry, lin=Fa
         return tau_abs
     it = iter(host[1:])
     return tau_abs, [np.zeros((nSpec, Nz)) if d is None else np.ascontiguousarray(next(it).T) for d in dots]
+
+
+# ---- linearized: d sigma / d(T, p, vmr_self) per layer and the profile slots of tau_abs (ours) ---------------------------
+SLOTS = ("T", "p", "vmr_self")       # K^-1, hPa^-1, 1
+
+
+def _prepare_lin(model, grid, pressure, temperature, wavelength_flag=False) -> _Job:
+    """_prepare with its refusals, the CPF12 refusal, and d ln(Q(T_ref) / Q(T)) / dT per (layer, species) beside qratio."""
+    job = _prepare(model, grid, pressure, temperature, wavelength_flag)
+    if isinstance(model.broadening, Voigt) and model.CEF.code == CPF12ErrorFunction.code:
+        raise NotImplementedError("linearized CPF12 is not built (its region II is no analytic formula): use "
+                                  "HumlicekWeidemann32SDErrorFunction or HumlicekWeidemann32VoigtErrorFunction")
+    dln = np.zeros_like(job.qratio)
+    for i, k in enumerate(job.species_keys):
+        if np.any(job.lines["E_low"][job.lines["species"] == i] != -1):
+            r, d = qoft_lin(model.isotopologues[k], job.T)
+            dln[:, i] = d / r
+    job.qratio_dlnT = dln
+    return job
+
+
+def compute_absorption_cross_section_lin(model, grid, pressure, temperature, wavelength_flag=False):
+    """(sigma, sigma_dot): compute_absorption_cross_section's sigma, bit for bit, and its derivatives for SLOTS = (T [K^-1],
+    p [hPa^-1], vmr_self [1]) of each layer: sigma_dot [3, nSpec] for scalar p, T, [3, Nz, nSpec] for a profile (layer z depends on
+    p[z], T[z], vmr[z] alone).  It is the derivative of the function the device evaluates with the index windows of the wing cutoff
+    and, per (line, point), the region of the error function frozen: the derivative almost everywhere.  ONE vsm_absorption_xsec_lin
+    call and one synchronisation; wavelength_flag reverses every slot as sigma; an empty selection returns exact zeros without a
+    launch.  Refuses what the forward refuses, and Voigt with CPF12ErrorFunction (NotImplementedError)."""
+    scalar = np.ndim(pressure) == 0 and np.ndim(temperature) == 0
+    job = _prepare_lin(model, grid, pressure, temperature, wavelength_flag)
+    Nz, nSpec = len(job.p), len(job.grid)
+    if job.n_lines == 0:
+        sig, dot = np.zeros((Nz, nSpec)), np.zeros((3, Nz, nSpec))
+    else:
+        dev = _Device(model.architecture)
+        outs = [dev.empty(Nz, nSpec) for _ in range(4)]
+        dev.xsec_lin(job, dev.profile_lin(job), np.ones(Nz), *outs, 0)
+        host = dev.fetch(outs)
+        sig, dot = host[0], np.stack(host[1:])
+    if job.reverse:
+        sig, dot = sig[:, ::-1].copy(), dot[:, :, ::-1].copy()
+    return (sig[0], dot[:, 0]) if scalar else (sig, dot)
+
+
+@dataclass
+class AbsorptionProfileLin:
+    """What compute_absorption_profile_lin returns; every array [nSpec, Nz] unless said otherwise."""
+    tau_abs: np.ndarray                    # bit for bit compute_absorption_profile's
+    tau_abs_dot: list                      # [g]: sigma_g vcd_dry, as lin=True
+    dtau_dT: np.ndarray                    # sum_g vcd_dry vmr_g d sigma_g / dT of the layer's own T (the Jacobian is diagonal in the layer)
+    dtau_dp: np.ndarray                    # the same for p
+    dtau_dvmr_self: list                   # [g]: vcd_dry vmr_g d sigma_g / d vmr_self: add it to tau_abs_dot[g] if the gas broadens itself
+    profile_slots: np.ndarray              # [K, nSpec, Nz]: dtau_dT T_dot[k] + dtau_dp p_dot[k]
+
+    def lin_model_slots(self):
+        """tau_abs_dot + list(profile_slots): what host_model.LinModel(tau_abs_dot=...) takes; NGas is its length."""
+        return list(self.tau_abs_dot) + list(self.profile_slots)
+
+
+def compute_absorption_profile_lin(models_and_vmrs, grid, p_full, T, vcd_dry, T_dot=None, p_dot=None, architecture=None):
+    """compute_absorption_profile(..., lin=True) and the T, p and vmr_self Jacobians of tau_abs: an AbsorptionProfileLin.
+    T_dot, p_dot [K, Nz] (either may be None = zeros) are K perturbation profiles, shaped as B_layer_dot is: a unit table per layer
+    for weighting functions, a row of ones for a profile shift, p_full / p_surf for surface pressure; profile_slots[k] =
+    dtau_dT T_dot[k] + dtau_dp p_dot[k] is formed on the device.  The gases are summed on the device through `accumulate`; one
+    synchronisation for the whole list.  vcd_dry is held FIXED: the caller owns d vcd_dry / d p_surf.  Refuses what
+    compute_absorption_profile refuses, Voigt with CPF12ErrorFunction (NotImplementedError) and tables that are not [K, Nz], all
+    before the first launch."""
+    pairs = list(models_and_vmrs)
+    if not pairs:
+        raise _lib.VSMError("compute_absorption_profile: no (model, vmr) pair")
+    p = np.asarray(p_full, dtype=np.float64).reshape(-1)
+    Tz = np.asarray(T, dtype=np.float64).reshape(-1)
+    vcd = np.asarray(vcd_dry, dtype=np.float64).reshape(-1)
+    Nz = len(p)
+    if len(Tz) != Nz or len(vcd) != Nz or Nz < 1:
+        raise _lib.VSMError("compute_absorption_profile: p_full, T and vcd_dry have %d, %d and %d layers" % (Nz, len(Tz), len(vcd)))
+    tabs = [None if t is None else np.asarray(t, dtype=np.float64) for t in (T_dot, p_dot)]
+    for name, t in zip(("T_dot", "p_dot"), tabs):
+        if t is not None and (t.ndim != 2 or t.shape[1] != Nz or t.shape[0] < 1):
+            raise _lib.VSMError("compute_absorption_profile_lin: %s of shape %r is not [K, %d]" % (name, t.shape, Nz))
+    if tabs[0] is not None and tabs[1] is not None and tabs[0].shape != tabs[1].shape:
+        raise _lib.VSMError("compute_absorption_profile_lin: T_dot %r and p_dot %r differ in K" % (tabs[0].shape, tabs[1].shape))
+    K = next((len(t) for t in tabs if t is not None), 0)
+    if K > 65535:
+        raise _lib.VSMError("compute_absorption_profile_lin: K = %d above 65535 profile slots" % K)
+    tabs = [np.zeros((K, Nz)) if t is None else t for t in tabs]
+    jobs, scales = [], []
+    for model, vmr in pairs:                                        # (every refusal before the first launch)
+        v = np.asarray(vmr, dtype=np.float64)
+        if v.ndim > 0 and v.shape != (Nz,):
+            raise _lib.VSMError("compute_absorption_profile: the length of a vmr array (%r) has to match the profile (%d) or be "
+                                "uniform" % (v.shape, Nz))
+        jobs.append(_prepare_lin(model, grid, p, Tz, False))
+        scales.append(vcd * v)
+    nSpec = len(jobs[0].grid)
+
+    def z():
+        return np.zeros((nSpec, Nz))
+
+    if all(j.n_lines == 0 for j in jobs):
+        return AbsorptionProfileLin(z(), [z() for _ in jobs], z(), z(), [z() for _ in jobs], np.zeros((K, nSpec, Nz)))
+    dev = _Device(architecture if architecture is not None else pairs[0][0].architecture)
+    tau, dT, dp = dev.empty(Nz, nSpec), dev.empty(Nz, nSpec), dev.empty(Nz, nSpec)
+    dots, dvs, started = [], [], False
+    for job, scale in zip(jobs, scales):
+        if job.n_lines == 0:
+            dots.append(None)
+            dvs.append(None)
+            continue
+        h = dev.profile_lin(job)
+        dv = dev.zeros(Nz, nSpec) if started else dev.empty(Nz, nSpec)      # `accumulate` holds for all four outputs of a call
+        dev.xsec_lin(job, h, scale, tau, dT, dp, dv, 1 if started else 0)
+        started = True
+        d = dev.empty(Nz, nSpec)
+        dev.xsec(job, h, vcd, d, 0)
+        dots.append(d)
+        dvs.append(dv)
+    live = [a for pair in zip(dots, dvs) if pair[0] is not None for a in pair]
+    slots = [dev.profile_slots(dT, dp, tabs[0], tabs[1])] if K else []
+    host = dev.fetch([tau, dT, dp] + slots + live)
+    it = iter(host[3 + len(slots):])
+    out_dots, out_dvs = [], []
+    for d in dots:
+        out_dots.append(z() if d is None else np.ascontiguousarray(next(it).T))
+        out_dvs.append(z() if d is None else np.ascontiguousarray(next(it).T))
+    ps = np.ascontiguousarray(np.transpose(host[3], (0, 2, 1))) if K else np.zeros((0, nSpec, Nz))
+    return AbsorptionProfileLin(np.ascontiguousarray(host[0].T), out_dots, np.ascontiguousarray(host[1].T),
+                                np.ascontiguousarray(host[2].T), out_dvs, ps)
