@@ -1483,6 +1483,50 @@ int vsm_absorption_xsec_lin(int nSpec, int nLines, int nSpecies, int Nz, const d
 int vsm_absorption_profile_slots(int nSpec, int Nz, int K, const double* dT, const double* dp, const double* T_dot,
                                  const double* p_dot, double* out, void* stream);
 
+/* ---- Absorption.InterpolationModel: sigma(nu, p, T) lookup tables (make_model_helpers.jl:55-122, ----------------------------
+ * compute_absorption_cross_section.jl:181-233).  Three uniform axes (first, step != 0, n >= 2) with the FP64 nodes x_k = first +
+ * k step; x lies in cell i = [x_i, x_i+1) (the last cell closed; i clamped to 0 .. n - 2) at t = (x - x_i) / (x_i+1 - x_i): that is
+ * (x - first) / step - i up to the rounding of the nodes, and exactly 0 on a node.  VSM_LUT_LINEAR: the coefficients are the values, [nP, nT, nNu] (nu contiguous),
+ * trilinear.  VSM_LUT_CUBIC (the reference's BSpline(Cubic(Line(OnGrid())))): coefficients [nP + 2, nT + 2, nNu + 2], per axis
+ * c[i-1]/6 + 2c[i]/3 + c[i+1]/6 = y[i], c[0] - 2c[1] + c[2] = 0 = c[n-1] - 2c[n] + c[n+1]; 4 taps per axis on c[i .. i+3] with
+ * weights (1-t)^3/6, (3t^3 - 6t^2 + 4)/6, (-3t^3 + 3t^2 + 3t + 1)/6, t^3/6.  Storage VSM_LUT_F64 / VSM_LUT_F32 (float
+ * coefficients, FP64 arithmetic).
+ *
+ * vsm_absorption_lut_prefilter: values [nP nT, nNu] (the layout vsm_absorption_xsec leaves for the nP nT states, T fastest) ->
+ * cubic coefficients, FP64, on `stream`: the nu axis by lanes that each solve VSM_LUT_CHUNK unknowns on a window widened by 32
+ * nodes per side, then the T and the p axis one lane per system; FP32 storage rounds once at the end.  work:
+ * vsm_absorption_lut_work_elems(nNu, nP, nT, storage) doubles, uninitialised (0 for refused sizes).  No atomics.
+ *
+ * vsm_absorption_lut_eval: out [Nz, nSpec] = (accumulate ? out : 0) + scale[z] sigma_itp(grid[s], p[z], T[z]); one launch.  grid
+ * [nSpec] is any finite array (unsorted, descending); a point outside [min, max] of the nu axis gives exact 0 (adds nothing).
+ * p[z], T[z] are the CALLER's to keep inside their axes: outside they are evaluated in the end cell (no fault).  A workgroup
+ * collapses the (p, T) taps once per table column its 256 points touch, in LDS, unless they span more than VSM_LUT_SPAN columns:
+ * then per point from memory; the same fma chain either way.
+ * vsm_absorption_lut_eval_lin: the same sigma, bit for bit, and out_dT (K^-1), out_dp (hPa^-1) [Nz, nSpec] from the derivative
+ * weights of the T and p axis over the step; linear: the derivative of the cell the forward evaluates in.  scale and accumulate
+ * apply to all three outputs.
+ * Contract of vsm_absorption_xsec: no host synchronisation, no library scratch, bit-identical repetitions.  An axis with n < 2, a
+ * size < 1, Nz > 65535, a step that is 0 or not finite, a bad enum or a null pointer return VSM_ERR_INVALID_ARG before any launch. */
+#define VSM_LUT_CHUNK 32
+#define VSM_LUT_SPAN 1024
+#define VSM_LUT_LINEAR 0
+#define VSM_LUT_CUBIC 1
+#define VSM_LUT_F64 0
+#define VSM_LUT_F32 1
+int vsm_absorption_lut_chunk(void); /* VSM_LUT_CHUNK of the loaded library */
+int vsm_absorption_lut_span(void);  /* VSM_LUT_SPAN of the loaded library */
+size_t vsm_absorption_lut_work_elems(int nNu, int nP, int nT, int storage);
+int vsm_absorption_lut_prefilter(int nNu, int nP, int nT, const double* values, int storage, void* coef, double* work,
+                                 void* stream);
+int vsm_absorption_lut_eval(int nSpec, int Nz, int nNu, int nP, int nT, double nu_first, double nu_step, double p_first,
+                            double p_step, double T_first, double T_step, int interp, int storage, const void* coef,
+                            const double* grid, const double* p, const double* T, const double* scale, int accumulate, double* out,
+                            void* stream);
+int vsm_absorption_lut_eval_lin(int nSpec, int Nz, int nNu, int nP, int nT, double nu_first, double nu_step, double p_first,
+                                double p_step, double T_first, double T_step, int interp, int storage, const void* coef,
+                                const double* grid, const double* p, const double* T, const double* scale, int accumulate,
+                                double* out, double* out_dT, double* out_dp, void* stream);
+
 /* ---- diagnostics used by the parity tests -------------------------------- */
 /* Runs the LDS-resident MFMA tile product used inside the fused kernels on plain
  * [N,N,S] inputs: C = A*B.  (Checks fragment layouts / swizzle independently.) */

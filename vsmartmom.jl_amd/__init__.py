@@ -35,7 +35,9 @@ Sub-modules
                     functions, make_hitran_model, compute_absorption_cross_section = Voigt cross-sections of a whole (p, T, vmr)
                     profile in one call on the device, FP64; compute_absorption_profile = tau_abs [nSpec, Nz] of a list of gases,
                     summed on the device, and the gas slots of LinModel.tau_abs_dot; compute_absorption_cross_section_lin /
-                    compute_absorption_profile_lin = the same with the analytic T, p and vmr_self derivatives of sigma and tau_abs)
+                    compute_absorption_profile_lin = the same with the analytic T, p and vmr_self derivatives of sigma and tau_abs;
+                    make_interpolation_model / InterpolationModel = the sigma(nu, p, T) lookup table, linear or cubic B-spline,
+                    built, prefiltered and evaluated on the device, which every one of these calls takes in place of a line table)
     parallel        spectral-axis sharding over the GPUs of one node (torch.distributed / RCCL)
 """
 from . import _lib, host_model  # noqa: F401

@@ -208,6 +208,12 @@ _SIGS = {
     "vsm_absorption_lin_work_elems": (_SZ, [_I, _I]),
     "vsm_absorption_xsec_lin": (_I, [_I, _I, _I, _I] + [_P] * 16 + [C.c_double, C.c_double, _I, _I, _I] + [_P] * 6),
     "vsm_absorption_profile_slots": (_I, [_I, _I, _I] + [_P] * 6),
+    "vsm_absorption_lut_chunk": (_I, []),
+    "vsm_absorption_lut_span": (_I, []),
+    "vsm_absorption_lut_work_elems": (_SZ, [_I, _I, _I, _I]),
+    "vsm_absorption_lut_prefilter": (_I, [_I, _I, _I, _P, _I, _P, _P, _P]),
+    "vsm_absorption_lut_eval": (_I, [_I] * 5 + [C.c_double] * 6 + [_I, _I] + [_P] * 5 + [_I, _P, _P]),
+    "vsm_absorption_lut_eval_lin": (_I, [_I] * 5 + [C.c_double] * 6 + [_I, _I] + [_P] * 5 + [_I, _P, _P, _P, _P]),
     "vsm_test_lds_mm_{T}": (_I, [_I, _I, _P, _P, _P, _P]),
     "vsm_test_lds_inv_{T}": (_I, [_I, _I, _P, _P, _I, _P, _P]),
     "vsm_test_poison_lds": (_I, [_P]),

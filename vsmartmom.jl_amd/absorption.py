@@ -11,6 +11,11 @@
                                                   vsm_absorption_xsec call
     compute_absorption_profile                    tau_abs [nSpec, Nz] of a list of gases, summed on the device, and with lin=True
                                                   the gas slots sigma_g vcd_dry of LinModel.tau_abs_dot
+    InterpolationModel, make_interpolation_model, UniformRange, save_interpolation_model, load_interpolation_model
+                                                  a sigma(nu, p, T) table, linear or cubic B-spline, FP64 or FP32, built in one
+                                                  vsm_absorption_xsec call over the nP nT states and prefiltered on the device; it stays
+                                                  resident there; every entry point below and above takes it where it takes a
+                                                  HitranModel, alone or mixed (csrc/vsm_absorption_lut.hip)
     SLOTS, qoft_lin, compute_absorption_cross_section_lin, compute_absorption_profile_lin, AbsorptionProfileLin
                                                   ours (the reference has no such derivative): sigma and d sigma / d(T, p, vmr_self)
                                                   per layer in ONE vsm_absorption_xsec_lin call; tau_abs with dtau_dT, dtau_dp,
@@ -23,8 +28,9 @@ What stays on the host: reading and filtering the table, sorting it by nu0 (the 
 nu0 order), the partition-sum spline, one value per (layer, isotopologue).  Everything with a line or grid-point loop runs in
 csrc/vsm_absorption.hip.  No TIPS or molar-mass table ships with this package: `isotopologues` hands them in.
 
-Not built: InterpolationModel / ABSCO tables, CIA, MT_CKD, linearized CPF12, FP32, the Erfc* error functions
-(they need a complex erfcx) and HumlicekErrorFunction (no `w` method in the reference either).
+Not built: ABSCO / HDF5 tables and their mixed linear / quadratic interpolant, a vmr axis or extrapolation in p or T of an
+InterpolationModel, CIA, MT_CKD, linearized CPF12, FP32 line-by-line sums, the Erfc* error functions (they need a complex erfcx) and
+HumlicekErrorFunction (no `w` method in the reference either).
 
 One deviation from the reference: a line whose pressure-shifted window misses the grid contributes nothing; the
 reference gives such a line the window [1, N]."""
@@ -329,7 +335,7 @@ def _prepare(model: HitranModel, grid, pressure, temperature, wavelength_flag=Fa
     """:44-105 for a whole profile: unit conversion, the (min - cutoff, max + cutoff) filter on the unshifted nu0, the sort, the species
     index and Q(T_ref) / Q(T) per (layer, species).  Raises before anything is launched."""
     if not isinstance(model, HitranModel):
-        raise _lib.VSMError("compute_absorption_cross_section: %r is no HitranModel (InterpolationModel is not built)"
+        raise _lib.VSMError("compute_absorption_cross_section: %r is neither a HitranModel nor an InterpolationModel"
                             % (type(model).__name__,))
     ht = model.hitran
     grid = np.asarray(grid, dtype=np.float64).reshape(-1)
@@ -441,6 +447,48 @@ class _Device:
                                                            CR._ptr(out), CR._stream_ptr()))
         return out
 
+    def lut_coef(self, model):
+        """The model's coefficients on the device: uploaded on first use and cached on the model."""
+        if model._coef_dev is None:
+            model._coef_dev = self.conv(model._coef_host)
+        return model._coef_dev
+
+    def _lut_args(self, job, coef):
+        m = job.model
+        g, p, T = self.conv(job.grid), self.conv(job.p), self.conv(job.T)
+        self.keep += [g, p, T, coef]
+        return [len(job.grid), len(job.p), m.ν_grid.n, m.p_grid.n, m.t_grid.n] + \
+            [C.c_double(v) for ax in (m.ν_grid, m.p_grid, m.t_grid) for v in (ax.first, ax.step)] + \
+            [_LUT_INTERP[m.interp_type], _LUT_STORAGE[m.storage_type], CR._ptr(coef), CR._ptr(g), CR._ptr(p), CR._ptr(T)]
+
+    def lut_eval(self, job, scale, out, accumulate):
+        """Enqueues one vsm_absorption_lut_eval: out [Nz, nSpec] = (accumulate ? out : 0) + scale[layer] sigma_itp."""
+        sc = self.conv(np.ascontiguousarray(scale, dtype=np.float64))
+        self.keep.append(sc)
+        _lib.check(_lib.lib().vsm_absorption_lut_eval(*self._lut_args(job, self.lut_coef(job.model)), CR._ptr(sc), int(accumulate),
+                                                      CR._ptr(out), CR._stream_ptr()))
+
+    def lut_eval_lin(self, job, scale, out, out_dT, out_dp, accumulate):
+        """Enqueues one vsm_absorption_lut_eval_lin: out as lut_eval's and the T and p planes beside it."""
+        sc = self.conv(np.ascontiguousarray(scale, dtype=np.float64))
+        self.keep.append(sc)
+        _lib.check(_lib.lib().vsm_absorption_lut_eval_lin(*self._lut_args(job, self.lut_coef(job.model)), CR._ptr(sc),
+                                                          int(accumulate), CR._ptr(out), CR._ptr(out_dT), CR._ptr(out_dp),
+                                                          CR._stream_ptr()))
+
+    def lut_prefilter(self, values, nNu, nP, nT, storage_type):
+        """Enqueues vsm_absorption_lut_prefilter on values [nP nT, nNu] (a device array): the coefficients [nP + 2, nT + 2, nNu + 2]."""
+        st = _LUT_STORAGE[storage_type]
+        elems = int(_lib.lib().vsm_absorption_lut_work_elems(nNu, nP, nT, st))
+        if elems == 0:
+            raise _lib.VSMError("vsm_absorption_lut_work_elems refuses nNu = %d, nP = %d, nT = %d" % (nNu, nP, nT))
+        work = _lib.poison(torch.empty(elems, dtype=torch.float64, device=values.device))
+        coef = torch.empty((nP + 2, nT + 2, nNu + 2), dtype=torch.float32 if st else torch.float64, device=values.device)
+        self.keep += [values, work]
+        _lib.check(_lib.lib().vsm_absorption_lut_prefilter(nNu, nP, nT, CR._ptr(values), st, CR._ptr(coef), CR._ptr(work),
+                                                           CR._stream_ptr()))
+        return coef
+
     def fetch(self, outs):
         synchronize_if_gpu()
         self.keep.clear()
@@ -452,7 +500,12 @@ def compute_absorption_cross_section(model, grid, pressure, temperature, wavelen
     (hPa) and temperature (K): sigma [nSpec] (cm^2 / molecule), the reference's call.  Vectors of length Nz, with model.vmr a scalar
     or [Nz]: sigma [Nz, nSpec] from ONE vsm_absorption_xsec call and one synchronisation.  wavelength_flag: the grid is in nm; it is
     converted to wavenumbers and reversed, and the result is reversed back, as the reference does.  An empty selection of lines
-    returns exact zeros without a launch."""
+    returns exact zeros without a launch.
+    compute_absorption_cross_section(model::InterpolationModel, ...) (:181-233): the table's interpolant in ONE
+    vsm_absorption_lut_eval call.  The grid may be any finite array, unsorted or descending; a point outside [min, max] of the
+    table's ν axis gives exact 0, on the boundary it is interpolated; p or T outside their axes raise VSMError before the launch."""
+    if isinstance(model, InterpolationModel):
+        return _lut_cross_section(model, grid, pressure, temperature, wavelength_flag, lin=False)
     scalar = np.ndim(pressure) == 0 and np.ndim(temperature) == 0
     job = _prepare(model, grid, pressure, temperature, wavelength_flag)
     Nz, nSpec = len(job.p), len(job.grid)
@@ -476,7 +529,9 @@ def compute_absorption_profile(models_and_vmrs, grid, p_full, T, vcd_dry, lin=Fa
     scalar or [Nz] --: tau_abs [nSpec, Nz] = sum_g sigma_g(p_full[z], T[z]) vcd_dry[z] vmr_g[z], the layout model_from_arrays takes.
     The gases are summed on the device (`accumulate`); there is no per-layer host loop and one synchronisation for the whole list.
     lin=True: (tau_abs, tau_abs_dot) with tau_abs_dot[g] = sigma_g vcd_dry [nSpec, Nz] (atmo_prof_lin.jl:153), the gas slots of
-    LinModel.tau_abs_dot; tau_abs is bit for bit the one of lin=False."""
+    LinModel.tau_abs_dot; tau_abs is bit for bit the one of lin=False.
+    A model may be a HitranModel or an InterpolationModel, in any mix: a table gas is one vsm_absorption_lut_eval launch with the
+    same scale / accumulate contract; a list of HitranModels alone issues the launches it always issued."""
     pairs = list(models_and_vmrs)
     if not pairs:
         raise _lib.VSMError("compute_absorption_profile: no (model, vmr) pair")
@@ -492,7 +547,7 @@ def compute_absorption_profile(models_and_vmrs, grid, p_full, T, vcd_dry, lin=Fa
         if v.ndim > 0 and v.shape != (Nz,):
             raise _lib.VSMError("compute_absorption_profile: the length of a vmr array (%r) has to match the profile (%d) or be "
                                 "uniform" % (v.shape, Nz))
-        jobs.append(_prepare(model, grid, p, Tz, False))
+        jobs.append(_prepare_any(model, grid, p, Tz, False))
         scales.append(vcd * v)
     nSpec = len(jobs[0].grid)
     if all(j.n_lines == 0 for j in jobs):
@@ -503,6 +558,14 @@ def compute_absorption_profile(models_and_vmrs, grid, p_full, T, vcd_dry, lin=Fa
     for job, scale in zip(jobs, scales):
         if job.n_lines == 0:
             dots.append(None)
+            continue
+        if isinstance(job, _LutJob):                                # a table gas: the same scale / accumulate contract
+            dev.lut_eval(job, scale, tau, 1 if started else 0)
+            started = True
+            if lin:
+                d = dev.empty(Nz, nSpec)
+                dev.lut_eval(job, vcd, d, 0)
+                dots.append(d)
             continue
         h = dev.profile(job)
         dev.xsec(job, h, scale, tau, 1 if started else 0)
@@ -545,7 +608,12 @@ def compute_absorption_cross_section_lin(model, grid, pressure, temperature, wav
     p[z], T[z], vmr[z] alone).  It is the derivative of the function the device evaluates with the index windows of the wing cutoff
     and, per (line, point), the region of the error function frozen: the derivative almost everywhere.  ONE vsm_absorption_xsec_lin
     call and one synchronisation; wavelength_flag reverses every slot as sigma; an empty selection returns exact zeros without a
-    launch.  Refuses what the forward refuses, and Voigt with CPF12ErrorFunction (NotImplementedError)."""
+    launch.  Refuses what the forward refuses, and Voigt with CPF12ErrorFunction (NotImplementedError).
+    An InterpolationModel: sigma of its forward call, bit for bit, and the exact derivative of the interpolant in T and p (linear:
+    of the cell the forward evaluates in) from ONE vsm_absorption_lut_eval_lin call; the vmr_self plane is exact zeros, the table
+    having been built at a fixed vmr."""
+    if isinstance(model, InterpolationModel):
+        return _lut_cross_section(model, grid, pressure, temperature, wavelength_flag, lin=True)
     scalar = np.ndim(pressure) == 0 and np.ndim(temperature) == 0
     job = _prepare_lin(model, grid, pressure, temperature, wavelength_flag)
     Nz, nSpec = len(job.p), len(job.grid)
@@ -584,7 +652,8 @@ def compute_absorption_profile_lin(models_and_vmrs, grid, p_full, T, vcd_dry, T_
     dtau_dT T_dot[k] + dtau_dp p_dot[k] is formed on the device.  The gases are summed on the device through `accumulate`; one
     synchronisation for the whole list.  vcd_dry is held FIXED: the caller owns d vcd_dry / d p_surf.  Refuses what
     compute_absorption_profile refuses, Voigt with CPF12ErrorFunction (NotImplementedError) and tables that are not [K, Nz], all
-    before the first launch."""
+    before the first launch.  InterpolationModels mix in as in compute_absorption_profile: they add to dtau_dT and dtau_dp (and so
+    to profile_slots) through vsm_absorption_lut_eval_lin, and their dtau_dvmr_self[g] is exact zeros."""
     pairs = list(models_and_vmrs)
     if not pairs:
         raise _lib.VSMError("compute_absorption_profile: no (model, vmr) pair")
@@ -610,7 +679,7 @@ def compute_absorption_profile_lin(models_and_vmrs, grid, p_full, T, vcd_dry, T_
         if v.ndim > 0 and v.shape != (Nz,):
             raise _lib.VSMError("compute_absorption_profile: the length of a vmr array (%r) has to match the profile (%d) or be "
                                 "uniform" % (v.shape, Nz))
-        jobs.append(_prepare_lin(model, grid, p, Tz, False))
+        jobs.append(_prepare_any(model, grid, p, Tz, False, lin=True))
         scales.append(vcd * v)
     nSpec = len(jobs[0].grid)
 
@@ -627,6 +696,14 @@ def compute_absorption_profile_lin(models_and_vmrs, grid, p_full, T, vcd_dry, T_
             dots.append(None)
             dvs.append(None)
             continue
+        if isinstance(job, _LutJob):                                # a table gas adds to tau, dT and dp; it has no vmr_self plane
+            dev.lut_eval_lin(job, scale, tau, dT, dp, 1 if started else 0)
+            started = True
+            d = dev.empty(Nz, nSpec)
+            dev.lut_eval(job, vcd, d, 0)
+            dots.append(d)
+            dvs.append(None)
+            continue
         h = dev.profile_lin(job)
         dv = dev.zeros(Nz, nSpec) if started else dev.empty(Nz, nSpec)      # `accumulate` holds for all four outputs of a call
         dev.xsec_lin(job, h, scale, tau, dT, dp, dv, 1 if started else 0)
@@ -635,14 +712,276 @@ def compute_absorption_profile_lin(models_and_vmrs, grid, p_full, T, vcd_dry, T_
         dev.xsec(job, h, vcd, d, 0)
         dots.append(d)
         dvs.append(dv)
-    live = [a for pair in zip(dots, dvs) if pair[0] is not None for a in pair]
+    live = [a for pair in zip(dots, dvs) for a in pair if a is not None]
     slots = [dev.profile_slots(dT, dp, tabs[0], tabs[1])] if K else []
     host = dev.fetch([tau, dT, dp] + slots + live)
     it = iter(host[3 + len(slots):])
     out_dots, out_dvs = [], []
-    for d in dots:
+    for d, dv in zip(dots, dvs):
         out_dots.append(z() if d is None else np.ascontiguousarray(next(it).T))
-        out_dvs.append(z() if d is None else np.ascontiguousarray(next(it).T))
+        out_dvs.append(z() if dv is None else np.ascontiguousarray(next(it).T))
     ps = np.ascontiguousarray(np.transpose(host[3], (0, 2, 1))) if K else np.zeros((0, nSpec, Nz))
     return AbsorptionProfileLin(np.ascontiguousarray(host[0].T), out_dots, np.ascontiguousarray(host[1].T),
                                 np.ascontiguousarray(host[2].T), out_dvs, ps)
+
+
+# ---- InterpolationModel: sigma(nu, p, T) lookup tables (make_model_helpers.jl:55-122, :181-233) --------------------------
+_LUT_INTERP = {"linear": 0, "cubic": 1}
+_LUT_STORAGE = {np.dtype(np.float64): 0, np.dtype(np.float32): 1}
+_LUT_WORK_CAP = 1 << 27              # doubles of vsm_absorption_xsec work per block of states (1 GiB)
+
+
+@dataclass(frozen=True)
+class UniformRange:
+    """first : step : first + (n - 1) step, the reference's AbstractRange: an axis of an InterpolationModel."""
+    first: float
+    step: float
+    n: int
+
+    def __post_init__(self):
+        object.__setattr__(self, "first", float(self.first))
+        object.__setattr__(self, "step", float(self.step))
+        object.__setattr__(self, "n", int(self.n))
+        if self.n < 2:
+            raise _lib.VSMError("UniformRange: an axis needs at least two nodes (n = %d)" % self.n)
+        if not (math.isfinite(self.first) and math.isfinite(self.step) and self.step != 0.0):
+            raise _lib.VSMError("UniformRange: first = %r, step = %r: finite, step != 0" % (self.first, self.step))
+
+    @property
+    def last(self):
+        return self.first + (self.n - 1) * self.step
+
+    @property
+    def lo(self):
+        return min(self.first, self.last)
+
+    @property
+    def hi(self):
+        return max(self.first, self.last)
+
+    def values(self):
+        return self.first + np.arange(self.n) * self.step
+
+    def __len__(self):
+        return self.n
+
+
+def _as_range(x, name):
+    """A UniformRange from a UniformRange, a Python range or an array that is uniform to 1e-9 of its step."""
+    if isinstance(x, UniformRange):
+        return x
+    if isinstance(x, range):
+        return UniformRange(x.start, x.step, len(x))
+    a = np.asarray(x, dtype=np.float64).reshape(-1)
+    if a.size < 2:
+        raise _lib.VSMError("%s: an axis needs at least two nodes (n = %d)" % (name, a.size))
+    if not np.all(np.isfinite(a)):
+        raise _lib.VSMError("%s: the axis is not finite" % name)
+    step = (a[-1] - a[0]) / (a.size - 1)
+    if step == 0.0 or not np.all(np.abs(np.diff(a) - step) <= 1e-9 * abs(step)):
+        raise _lib.VSMError("%s: the axis is not uniform to 1e-9 of its step" % name)
+    return UniformRange(a[0], step, a.size)
+
+
+class InterpolationModel:
+    """The reference's InterpolationModel (types.jl:185-): itp, mol, iso, ν_grid, p_grid, t_grid, with the interpolant spelled out:
+    interp_type "linear" or "cubic", storage_type float64 or float32.  The coefficients live on the device in the layout
+    [nP (+2), nT (+2), nν (+2)] (ν contiguous; +2 for cubic) and are cached on the model; `coefficients` (alias itp) is their host
+    copy in the reference's axis order [ν, p, T], fetched when first asked for."""
+
+    def __init__(self, mol, iso, ν_grid, p_grid, t_grid, interp_type="cubic", storage_type=np.float64, architecture=None,
+                 _coef_host=None, _coef_dev=None, _pending=False):
+        if interp_type not in _LUT_INTERP:
+            raise _lib.VSMError("InterpolationModel: interp_type must be 'linear' or 'cubic', got %r" % (interp_type,))
+        try:
+            storage = np.dtype(storage_type)
+        except TypeError:
+            storage = None
+        if storage not in _LUT_STORAGE:
+            raise _lib.VSMError("InterpolationModel: storage_type must be float64 or float32, got %r" % (storage_type,))
+        self.mol, self.iso = int(mol), int(iso)
+        self.ν_grid, self.p_grid, self.t_grid = _as_range(ν_grid, "ν_grid"), _as_range(p_grid, "p_grid"), _as_range(t_grid, "t_grid")
+        self.interp_type, self.storage_type = interp_type, storage
+        self.architecture = architecture if architecture is not None else default_architecture()
+        self._coef_host, self._coef_dev = _coef_host, _coef_dev
+        if _coef_host is None and _coef_dev is None and not _pending:     # (_pending: the builder attaches them after its launches)
+            raise _lib.VSMError("InterpolationModel: use make_interpolation_model, from_values or from_coefficients")
+        for c in (_coef_host, _coef_dev):
+            if c is not None and tuple(c.shape) != self.table_shape:
+                raise _lib.VSMError("InterpolationModel: coefficients of shape %r for a table of %r" % (tuple(c.shape), self.table_shape))
+
+    @property
+    def table_shape(self):
+        pad = 2 if self.interp_type == "cubic" else 0
+        return (self.p_grid.n + pad, self.t_grid.n + pad, self.ν_grid.n + pad)
+
+    @property
+    def resident(self):
+        return self._coef_dev is not None
+
+    @property
+    def coefficients(self):
+        if self._coef_host is None:
+            synchronize_if_gpu()
+            self._coef_host = np.ascontiguousarray(to_host(self._coef_dev))
+        return np.transpose(self._coef_host, (2, 0, 1))
+
+    itp = coefficients
+
+    def __repr__(self):
+        return "InterpolationModel(mol=%d, iso=%d, %s, %s, table %r%s)" % (
+            self.mol, self.iso, self.interp_type, self.storage_type.name, self.table_shape, ", resident" if self.resident else "")
+
+    @classmethod
+    def from_coefficients(cls, coefficients, mol, iso, ν_grid, p_grid, t_grid, interp_type="cubic", storage_type=None,
+                          architecture=None):
+        """A model from ready coefficients [nν (+2), nP (+2), nT (+2)] (the reference's axis order; +2 for cubic); host only.
+        storage_type None: float32 if the array is float32, else float64."""
+        c = np.asarray(coefficients)
+        if storage_type is None:
+            storage_type = np.float32 if c.dtype == np.float32 else np.float64
+        if c.ndim != 3:
+            raise _lib.VSMError("InterpolationModel.from_coefficients: coefficients of shape %r are not [ν, p, T]" % (c.shape,))
+        host = np.ascontiguousarray(np.transpose(c, (1, 2, 0)), dtype=np.dtype(storage_type))
+        return cls(mol, iso, ν_grid, p_grid, t_grid, interp_type, storage_type, architecture, _coef_host=host)
+
+    @classmethod
+    def from_values(cls, values, mol, iso, ν_grid, p_grid, t_grid, interp_type="cubic", storage_type=np.float64, architecture=None):
+        """A model through the values [nν, nP, nT] (the reference's cs_matrix).  Linear: the coefficients are the values, no device.
+        Cubic: prefiltered on the device in FP64 (vsm_absorption_lut_prefilter); the coefficients stay there."""
+        v = np.asarray(values, dtype=np.float64)
+        axes = _as_range(ν_grid, "ν_grid"), _as_range(p_grid, "p_grid"), _as_range(t_grid, "t_grid")
+        if v.shape != tuple(a.n for a in axes):
+            raise _lib.VSMError("InterpolationModel.from_values: values of shape %r for axes of %r" % (v.shape, tuple(a.n for a in axes)))
+        if interp_type == "linear":
+            return cls.from_coefficients(v, mol, iso, *axes, "linear", storage_type, architecture)
+        model = cls(mol, iso, *axes, interp_type, storage_type, architecture, _pending=True)   # (checks interp_type, storage_type)
+        dev = _Device(model.architecture)
+        flat = dev.conv(np.ascontiguousarray(np.transpose(v, (1, 2, 0))).reshape(axes[1].n * axes[2].n, axes[0].n))
+        model._coef_dev = dev.lut_prefilter(flat, axes[0].n, axes[1].n, axes[2].n, model.storage_type)
+        dev.fetch([])
+        return model
+
+
+def make_interpolation_model(hitran, broadening, wave_grid, p_grid, t_grid, wavelength_flag=False, wing_cutoff=40, vmr=0, CEF=None,
+                             architecture=None, interp_type="cubic", storage_type=np.float64, isotopologues=None):
+    """make_interpolation_model(hitran, broadening, wave_grid, p_grid, t_grid; ...) (make_model_helpers.jl:55-111): the line-by-line
+    cross-sections at every (p_grid[i], t_grid[j]) on the ν axis, and their interpolant.  The nP nT states are the layers of ONE
+    vsm_absorption_xsec call (the reference launches and synchronises nP nT times), in blocks where Nz <= 65535 or the work buffer
+    ask for it; the prefilter follows on the same stream, the table never visits the host, and there is one synchronisation.
+    wavelength_flag: wave_grid is in nm and the ν axis is reverse(1e7 / wave_grid), which must come out uniform.  Scalar vmr only,
+    as in the reference.  mol is the table's first, iso its common isotopologue or -1."""
+    if np.ndim(vmr) != 0:
+        raise _lib.VSMError("make_interpolation_model: vmr must be a scalar (the table has no vmr axis)")
+    hm = make_hitran_model(hitran, broadening, wing_cutoff=wing_cutoff, vmr=float(vmr), CEF=CEF, architecture=architecture,
+                           isotopologues=isotopologues)
+    if wavelength_flag:
+        nm = wave_grid.values() if isinstance(wave_grid, UniformRange) else np.asarray(wave_grid, dtype=np.float64)
+        wave_grid = (nm_per_m / nm)[::-1]
+    axes = _as_range(wave_grid, "wave_grid"), _as_range(p_grid, "p_grid"), _as_range(t_grid, "t_grid")
+    nNu, nP, nT = (a.n for a in axes)
+    mol = int(hitran.mol[0])
+    iso = int(hitran.iso[0]) if np.all(hitran.iso == hitran.iso[0]) else -1
+    model = InterpolationModel(mol, iso, *axes, interp_type, storage_type, hm.architecture, _pending=True)
+    p_states, T_states = np.repeat(axes[1].values(), nT), np.tile(axes[2].values(), nP)
+    job = _prepare(hm, axes[0].values(), p_states, T_states, False)
+    dev = _Device(hm.architecture)
+    Nz = nP * nT
+    values = dev.zeros(Nz, nNu) if job.n_lines == 0 else dev.empty(Nz, nNu)
+    if job.n_lines:
+        per_state = int(_lib.lib().vsm_absorption_work_elems(1, job.n_lines))
+        block = int(max(1, min(65535, _LUT_WORK_CAP // per_state)))
+        for b0 in range(0, Nz, block):
+            b1 = min(Nz, b0 + block)
+            part = _Job(**{**job.__dict__, "p": job.p[b0:b1], "T": job.T[b0:b1], "vmr_self": job.vmr_self[b0:b1],
+                           "qratio": np.ascontiguousarray(job.qratio[b0:b1])})
+            dev.xsec(part, dev.profile(part), np.ones(b1 - b0), values[b0:b1], 0)
+    if interp_type == "cubic":
+        coef = dev.lut_prefilter(values, nNu, nP, nT, model.storage_type)
+    else:
+        coef = values.reshape(nP, nT, nNu)
+        if model.storage_type == np.dtype(np.float32):
+            coef = coef.to(torch.float32)
+    model._coef_host, model._coef_dev = None, coef
+    dev.fetch([])
+    return model
+
+
+def save_interpolation_model(model, path):
+    """One .npz (no pickle): the coefficients in the reference's axis order, the three ranges as (first, step, n), mol, iso,
+    interp_type and storage; load_interpolation_model gives the same bits back."""
+    if not isinstance(model, InterpolationModel):
+        raise _lib.VSMError("save_interpolation_model: %r is no InterpolationModel" % (type(model).__name__,))
+    rng = {k: np.asarray([a.first, a.step, float(a.n)]) for k, a in (("nu_range", model.ν_grid), ("p_range", model.p_grid),
+                                                                      ("t_range", model.t_grid))}
+    with open(path, "wb") as f:
+        np.savez(f, coefficients=np.ascontiguousarray(model.coefficients), mol=np.int64(model.mol), iso=np.int64(model.iso),
+                 interp_type=np.asarray(model.interp_type), storage=np.asarray(model.storage_type.name), **rng)
+
+
+def load_interpolation_model(path, architecture=None):
+    with np.load(path, allow_pickle=False) as z:
+        ax = [UniformRange(z[k][0], z[k][1], int(z[k][2])) for k in ("nu_range", "p_range", "t_range")]
+        return InterpolationModel.from_coefficients(z["coefficients"], int(z["mol"]), int(z["iso"]), *ax, str(z["interp_type"]),
+                                                    np.dtype(str(z["storage"])), architecture)
+
+
+@dataclass
+class _LutJob:
+    """One vsm_absorption_lut_eval call, on the host: the grid in wavenumbers (any order) and the profile."""
+    model: InterpolationModel
+    grid: np.ndarray
+    p: np.ndarray
+    T: np.ndarray
+    reverse: bool
+    n_lines = -1                     # (never the empty selection of a line table)
+
+
+def _prepare_lut(model, grid, pressure, temperature, wavelength_flag=False) -> _LutJob:
+    """:198-233 for a whole profile.  p or T outside their axes raise here, before any launch (the reference throws a BoundsError);
+    exactly on an end is inside."""
+    grid = np.asarray(grid, dtype=np.float64).reshape(-1)
+    if grid.size < 1 or not np.all(np.isfinite(grid)):
+        raise _lib.VSMError("compute_absorption_cross_section: the grid needs at least one finite point")
+    if wavelength_flag:
+        grid = (nm_per_m / grid)[::-1].copy()
+    p = np.atleast_1d(np.asarray(pressure, dtype=np.float64))
+    T = np.atleast_1d(np.asarray(temperature, dtype=np.float64))
+    if p.ndim != 1 or p.shape != T.shape or p.size < 1:
+        raise _lib.VSMError("compute_absorption_cross_section: pressure %r and temperature %r must be scalars or vectors of one "
+                            "length" % (p.shape, T.shape))
+    if p.size > 65535:
+        raise _lib.VSMError("compute_absorption_cross_section: %d layers above 65535" % p.size)
+    for name, v, ax in (("pressure", p, model.p_grid), ("temperature", T, model.t_grid)):
+        if not np.all((v >= ax.lo) & (v <= ax.hi)):
+            raise _lib.VSMError("compute_absorption_cross_section: %s (%s) outside the table's axis [%g, %g] (no extrapolation)"
+                                % (name, np.array2string(v, threshold=8), ax.lo, ax.hi))
+    return _LutJob(model=model, grid=np.ascontiguousarray(grid), p=p, T=T, reverse=bool(wavelength_flag))
+
+
+def _prepare_any(model, grid, pressure, temperature, wavelength_flag=False, lin=False):
+    if isinstance(model, InterpolationModel):
+        return _prepare_lut(model, grid, pressure, temperature, wavelength_flag)
+    return (_prepare_lin if lin else _prepare)(model, grid, pressure, temperature, wavelength_flag)
+
+
+def _lut_cross_section(model, grid, pressure, temperature, wavelength_flag, lin):
+    scalar = np.ndim(pressure) == 0 and np.ndim(temperature) == 0
+    job = _prepare_lut(model, grid, pressure, temperature, wavelength_flag)
+    Nz, nSpec = len(job.p), len(job.grid)
+    dev = _Device(model.architecture)
+    outs = [dev.empty(Nz, nSpec) for _ in range(3 if lin else 1)]
+    if lin:
+        dev.lut_eval_lin(job, np.ones(Nz), *outs, 0)
+    else:
+        dev.lut_eval(job, np.ones(Nz), outs[0], 0)
+    host = dev.fetch(outs)
+    sig = host[0]
+    if job.reverse:
+        sig = sig[:, ::-1].copy()
+    if not lin:
+        return sig[0] if scalar else sig
+    dot = np.stack([host[1], host[2], np.zeros((Nz, nSpec))])       # SLOTS; the table was built at a fixed vmr
+    if job.reverse:
+        dot = dot[:, :, ::-1].copy()
+    return (sig[0], dot[:, 0]) if scalar else (sig, dot)
