@@ -1527,6 +1527,48 @@ int vsm_absorption_lut_eval_lin(int nSpec, int Nz, int nNu, int nP, int nT, doub
                                 const double* grid, const double* p, const double* T, const double* scale, int accumulate,
                                 double* out, double* out_dT, double* out_dp, void* stream);
 
+/* ---- Absorption continua: HITRAN CIA (src/Absorption/cia.jl) and the MT_CKD H2O continuum (src/Absorption/mtckd.jl) -----------
+ * A continuum SET is nTables <= VSM_CONT_MAX_TABLES CIA tables plus at most one MT_CKD band, all on one spectral grid of nSpec
+ * points.  ONE launch on `stream` adds the whole set to its output planes [Nz, nSpec] for all Nz layers: a workgroup owns 256 points
+ * and a tile of VSM_CONT_LAYERS layers, a lane keeps nu and the band values of its point in registers over the tile, and a plane
+ * is read (if it accumulates) and written once per set: plane = (accumulate ? plane : 0) + value, per plane.
+ *
+ * CIA, per table k in list order, FP64, only + - x and no contraction (the chain is fixed and tested to the bit):
+ *   a = table_k[j0, s], b = table_k[j1, s];  s_k = (1 - w) a + w b;  plane_m += s_k A[m, k, z];  plane_1 += (b - a) B[1, k, z].
+ * tables: HOST array of nTables DEVICE pointers, table k [nT[k], nSpec] (nu contiguous); nT: host array.  Device arrays: rows
+ * [nTables, Nz, 2] ints (j0, j1; clamped into the table by the kernel), w [nTables, Nz], A (and B) [nPlanes, nTables, Nz]: the
+ * caller's per-layer coefficients (cia_σ_at_T!'s cell and weight; v_a v_b n_air^2 Δz_cm and its derivatives).  Of B only plane 1
+ * is read.
+ * MT_CKD, behind the tables, self then foreign: nu, C_self, C_for, texp [nSpec] on the device (all null: no band) and band_layer
+ * [Nz, VSM_CONT_BAND_FIELDS] = (T, T_ref / T, S, F, 2S/p, 2F/p, dS/dv, dF/dv, S/Δz, F/Δz) with S = (v p / p_ref) v n_air Δz_cm and
+ * F = ((1 - v) p / p_ref) v n_air Δz_cm.  With x = 1.4388 nu / (2T): g_s = nu tanh(x) C_self (T_ref/T)^texp, g_f = nu tanh(x) C_for,
+ *   tau += g_s S, += g_f F;  d/dT += g_s S t_s, += g_f F t_f, t_s = -(q + texp + 1)/T, t_f = -(q + 1)/T, q = 2x / sinh(2x) (1 at
+ *   nu = 0);  d/dp, d/dv(H2O), d/dΔz += g_s and g_f times fields 4/5, 6/7, 8/9.  nu = 0 and zero coefficients give exact 0.
+ * Planes of vsm_absorption_continuum_lin (HOST arrays `planes` of nPlanes device pointers and `accumulate` of nPlanes flags):
+ * 0 tau, 1 d/dT, 2 d/dp, 3 .. nPlanes - 1 the caller's: vmr planes, which the band enters at h2o_plane, and d/dΔz at ddz_plane (-1:
+ * none).  Plane 0 has the bits of vsm_absorption_continuum with the same inputs.  3 <= nPlanes <= VSM_CONT_MAX_PLANES.
+ * Contract of vsm_absorption_lut_eval: no host synchronisation, no library scratch, no atomics, bit-identical repetitions; a
+ * point's result does not depend on its lane, its layer tile or Nz.  A size < 1, Nz > 65535, nTables outside 0 ..
+ * VSM_CONT_MAX_TABLES, an empty set, nT[k] < 1, a band with one of its five arrays missing, nPlanes, h2o_plane (3 .. nPlanes - 1
+ * with a band, -1 without) or ddz_plane out of range, an accumulate flag outside 0 / 1, two planes that are one array or a null
+ * pointer return VSM_ERR_INVALID_ARG before any launch.
+ *
+ * vsm_absorption_profile_slots_add: out [K, Nz, nSpec] += plane [Nz, nSpec] tab [K, Nz], one launch (the Δz share of the profile
+ * slots behind vsm_absorption_profile_slots); refusals as that call's. */
+#define VSM_CONT_MAX_TABLES 8
+#define VSM_CONT_MAX_PLANES 24
+#define VSM_CONT_LAYERS 4
+#define VSM_CONT_BAND_FIELDS 10
+int vsm_absorption_continuum_layers(void); /* VSM_CONT_LAYERS of the loaded library */
+int vsm_absorption_continuum(int nSpec, int Nz, int nTables, const double* const* tables, const int* nT, const int* rows,
+                             const double* w, const double* A, const double* nu, const double* C_self, const double* C_for,
+                             const double* texp, const double* band_layer, int accumulate, double* out, void* stream);
+int vsm_absorption_continuum_lin(int nSpec, int Nz, int nTables, const double* const* tables, const int* nT, const int* rows,
+                                 const double* w, int nPlanes, const double* A, const double* B, const double* nu,
+                                 const double* C_self, const double* C_for, const double* texp, const double* band_layer,
+                                 int h2o_plane, int ddz_plane, const int* accumulate, double* const* planes, void* stream);
+int vsm_absorption_profile_slots_add(int nSpec, int Nz, int K, const double* plane, const double* tab, double* out, void* stream);
+
 /* ---- diagnostics used by the parity tests -------------------------------- */
 /* Runs the LDS-resident MFMA tile product used inside the fused kernels on plain
  * [N,N,S] inputs: C = A*B.  (Checks fragment layouts / swizzle independently.) */

@@ -214,6 +214,10 @@ _SIGS = {
     "vsm_absorption_lut_prefilter": (_I, [_I, _I, _I, _P, _I, _P, _P, _P]),
     "vsm_absorption_lut_eval": (_I, [_I] * 5 + [C.c_double] * 6 + [_I, _I] + [_P] * 5 + [_I, _P, _P]),
     "vsm_absorption_lut_eval_lin": (_I, [_I] * 5 + [C.c_double] * 6 + [_I, _I] + [_P] * 5 + [_I, _P, _P, _P, _P]),
+    "vsm_absorption_continuum_layers": (_I, []),
+    "vsm_absorption_continuum": (_I, [_I, _I, _I] + [_P] * 10 + [_I, _P, _P]),
+    "vsm_absorption_continuum_lin": (_I, [_I, _I, _I] + [_P] * 4 + [_I] + [_P] * 7 + [_I, _I, _P, _P, _P]),
+    "vsm_absorption_profile_slots_add": (_I, [_I, _I, _I, _P, _P, _P, _P]),
     "vsm_test_lds_mm_{T}": (_I, [_I, _I, _P, _P, _P, _P]),
     "vsm_test_lds_inv_{T}": (_I, [_I, _I, _P, _P, _I, _P, _P]),
     "vsm_test_poison_lds": (_I, [_P]),

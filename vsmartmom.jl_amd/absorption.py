@@ -20,6 +20,17 @@
                                                   ours (the reference has no such derivative): sigma and d sigma / d(T, p, vmr_self)
                                                   per layer in ONE vsm_absorption_xsec_lin call; tau_abs with dtau_dT, dtau_dp,
                                                   dtau_dvmr_self[g] and profile slots that LinModel.tau_abs_dot takes
+    CIABlock, parse_cia_file, CIATable, build_cia_table, load_cia_table
+                                                  HITRAN collision-induced absorption (cia.jl): a local .cia file projected on the
+                                                  grid once, on the host; the table stays resident on the device in FP64
+    MTCKDTable, load_mtckd, MTCKDBand, build_mtckd_band
+                                                  the MT_CKD H2O continuum (mtckd.jl) from a .npz with the AER file's six variables
+    layer_thickness                               the reference's hydrostatic layer thickness (atmo_prof.jl:67)
+    compute_continuum_profile, ContinuumProfileLin
+                                                  tau [nSpec, Nz] of a continuum set -- up to 8 CIATables and one MTCKDBand -- in ONE
+                                                  vsm_absorption_continuum launch, and with lin=True its T, p, vmr and dz derivatives
+                                                  (ours); compute_absorption_profile(_lin) take the set as continua= and add it behind
+                                                  the gases on the device (csrc/vsm_absorption_continuum.hip)
 
 Names follow the reference; its non-ASCII field names are spelled out: nu (νᵢ), S (Sᵢ), A (Aᵢ), gamma_air, gamma_self, E_low (E″),
 n_air, delta_air, g_upper (g′), g_lower (g″).
@@ -29,11 +40,13 @@ nu0 order), the partition-sum spline, one value per (layer, isotopologue).  Ever
 csrc/vsm_absorption.hip.  No TIPS or molar-mass table ships with this package: `isotopologues` hands them in.
 
 Not built: ABSCO / HDF5 tables and their mixed linear / quadratic interpolant, a vmr axis or extrapolation in p or T of an
-InterpolationModel, CIA, MT_CKD, linearized CPF12, FP32 line-by-line sums, the Erfc* error functions (they need a complex erfcx) and
+InterpolationModel, NetCDF ingestion and FP32 storage of the continua, linearized CPF12, FP32 line-by-line sums, the Erfc* error functions (they need a complex erfcx) and
 HumlicekErrorFunction (no `w` method in the reference either).
 
-One deviation from the reference: a line whose pressure-shifted window misses the grid contributes nothing; the
-reference gives such a line the window [1, N]."""
+Deviations from the reference: a line whose pressure-shifted window misses the grid contributes nothing (the
+reference gives such a line the window [1, N]); a continuum set is refused unless the grid is array_equal to the one its members
+were built on (the reference compares lengths); a CIA block whose nu does not ascend strictly is refused (the reference divides
+by zero); load_mtckd reads a .npz, not NetCDF."""
 from __future__ import annotations
 
 import ctypes as C
@@ -489,6 +502,54 @@ class _Device:
                                                            CR._stream_ptr()))
         return coef
 
+    def member(self, m):
+        """A continuum member's arrays on the device: uploaded on first use and cached on the member."""
+        if m._dev is None:
+            m._dev = self.conv(m._host_image())
+        return m._dev
+
+    def _continuum_args(self, job, n_planes):
+        """The arguments both continuum entry points share, up to band_layer; A (and B) cut to the first n_planes planes."""
+        tabs = [self.member(t) for t in job.tables]
+        n = len(tabs)
+        hp = (C.c_void_p * max(n, 1))(*[t.data_ptr() for t in tabs])
+        hn = (C.c_int * max(n, 1))(*[len(t.Ts) for t in job.tables])
+        dev = [self.conv(a) for a in (job.rows, job.w, np.ascontiguousarray(job.A[:n_planes]), np.ascontiguousarray(job.B[:n_planes]))] \
+            if n else [None] * 4
+        band = [None] * 5
+        if job.band is not None:
+            b = self.member(job.band)
+            band = [b[0], b[1], b[2], b[3], self.conv(job.band_layer)]
+        self.keep += tabs + dev + band + [hp, hn]
+        return n, hp, hn, dev, band
+
+    def continuum(self, job, out, accumulate):
+        """Enqueues one vsm_absorption_continuum: out [Nz, nSpec] = (accumulate ? out : 0) + the whole set."""
+        n, hp, hn, dev, band = self._continuum_args(job, 1)
+        _lib.check(_lib.lib().vsm_absorption_continuum(
+            job.nSpec, job.Nz, n, hp, hn, CR._ptr(dev[0]), CR._ptr(dev[1]), CR._ptr(dev[2]), *[CR._ptr(b) for b in band],
+            int(accumulate), CR._ptr(out), CR._stream_ptr()))
+
+    def continuum_lin(self, job, planes, accumulate):
+        """Enqueues one vsm_absorption_continuum_lin on the planes (tau, dT, dp, one per species of the set, ddz), each with its own
+        accumulate flag."""
+        nP = job.n_planes
+        n, hp, hn, dev, band = self._continuum_args(job, nP)
+        pl = (C.c_void_p * nP)(*[t.data_ptr() for t in planes])
+        acc = (C.c_int * nP)(*[int(a) for a in accumulate])
+        h2o = 3 + job.species.index("H2O") if job.band is not None else -1
+        _lib.check(_lib.lib().vsm_absorption_continuum_lin(
+            job.nSpec, job.Nz, n, hp, hn, CR._ptr(dev[0]), CR._ptr(dev[1]), nP, CR._ptr(dev[2]), CR._ptr(dev[3]),
+            *[CR._ptr(b) for b in band], h2o, nP - 1, acc, pl, CR._stream_ptr()))
+
+    def profile_slots_add(self, plane, tab, out):
+        """Enqueues vsm_absorption_profile_slots_add: out [K, Nz, nSpec] += plane [Nz, nSpec] tab [K, Nz]."""
+        K, (Nz, nSpec) = len(tab), plane.shape
+        td = self.conv(np.ascontiguousarray(tab, dtype=np.float64))
+        self.keep.append(td)
+        _lib.check(_lib.lib().vsm_absorption_profile_slots_add(nSpec, Nz, K, CR._ptr(plane), CR._ptr(td), CR._ptr(out),
+                                                               CR._stream_ptr()))
+
     def fetch(self, outs):
         synchronize_if_gpu()
         self.keep.clear()
@@ -524,17 +585,22 @@ def compute_absorption_cross_section(model, grid, pressure, temperature, wavelen
 absorption_cross_section = compute_absorption_cross_section
 
 
-def compute_absorption_profile(models_and_vmrs, grid, p_full, T, vcd_dry, lin=False, architecture=None):
+def compute_absorption_profile(models_and_vmrs, grid, p_full, T, vcd_dry, lin=False, architecture=None, continua=None, dz=None,
+                               vmr=None):
     """compute_absorption_profile! (atmo_prof.jl:464-486) for a list of (model, vmr) pairs -- vmr the gas's volume mixing ratio, a
     scalar or [Nz] --: tau_abs [nSpec, Nz] = sum_g sigma_g(p_full[z], T[z]) vcd_dry[z] vmr_g[z], the layout model_from_arrays takes.
     The gases are summed on the device (`accumulate`); there is no per-layer host loop and one synchronisation for the whole list.
     lin=True: (tau_abs, tau_abs_dot) with tau_abs_dot[g] = sigma_g vcd_dry [nSpec, Nz] (atmo_prof_lin.jl:153), the gas slots of
     LinModel.tau_abs_dot; tau_abs is bit for bit the one of lin=False.
     A model may be a HitranModel or an InterpolationModel, in any mix: a table gas is one vsm_absorption_lut_eval launch with the
-    same scale / accumulate contract; a list of HitranModels alone issues the launches it always issued."""
+    same scale / accumulate contract; a list of HitranModels alone issues the launches it always issued.
+    continua: a continuum set (compute_continuum_profile: CIATables and at most one MTCKDBand built on `grid`), with the layer
+    thicknesses dz [m] and the species' vmr dict; its tau is added behind the gases on the device, in one more launch, through
+    `accumulate`.  None: every launch is the one it always was."""
     pairs = list(models_and_vmrs)
     if not pairs:
         raise _lib.VSMError("compute_absorption_profile: no (model, vmr) pair")
+    cjob = _profile_continuum(continua, grid, p_full, T, dz, vmr, None)
     p = np.asarray(p_full, dtype=np.float64).reshape(-1)
     Tz = np.asarray(T, dtype=np.float64).reshape(-1)
     vcd = np.asarray(vcd_dry, dtype=np.float64).reshape(-1)
@@ -550,7 +616,7 @@ def compute_absorption_profile(models_and_vmrs, grid, p_full, T, vcd_dry, lin=Fa
         jobs.append(_prepare_any(model, grid, p, Tz, False))
         scales.append(vcd * v)
     nSpec = len(jobs[0].grid)
-    if all(j.n_lines == 0 for j in jobs):
+    if all(j.n_lines == 0 for j in jobs) and cjob is None:
         z = np.zeros((nSpec, Nz))
         return (z, [z.copy() for _ in jobs]) if lin else z
     dev = _Device(architecture if architecture is not None else pairs[0][0].architecture)
@@ -574,6 +640,8 @@ def compute_absorption_profile(models_and_vmrs, grid, p_full, T, vcd_dry, lin=Fa
             d = dev.empty(Nz, nSpec)
             dev.xsec(job, h, vcd, d, 0)
             dots.append(d)
+    if cjob is not None:
+        dev.continuum(cjob, tau, 1 if started else 0)
     live = [d for d in dots if d is not None] if lin else []
     host = dev.fetch([tau] + live)
     tau_abs = np.ascontiguousarray(host[0].T)
@@ -581,6 +649,17 @@ def compute_absorption_profile(models_and_vmrs, grid, p_full, T, vcd_dry, lin=Fa
         return tau_abs
     it = iter(host[1:])
     return tau_abs, [np.zeros((nSpec, Nz)) if d is None else np.ascontiguousarray(next(it).T) for d in dots]
+
+
+def _profile_continuum(continua, grid, p_full, T, dz, vmr, dz_dot):
+    """The continuum job of a profile call, with its refusals; None without continua."""
+    if continua is None:
+        if dz_dot is not None:
+            raise _lib.VSMError("compute_absorption_profile_lin: dz_dot without continua (no term depends on Δz)")
+        return None
+    if dz is None:
+        raise _lib.VSMError("compute_absorption_profile: continua need the layer thicknesses dz (layer_thickness)")
+    return _prepare_continuum(continua, grid, p_full, T, dz, vmr, fn="compute_absorption_profile")
 
 
 # ---- linearized: d sigma / d(T, p, vmr_self) per layer and the profile slots of tau_abs (ours; DESIGN 4.26) ---------------------------
@@ -638,14 +717,17 @@ class AbsorptionProfileLin:
     dtau_dT: np.ndarray                    # sum_g vcd_dry vmr_g d sigma_g / dT of the layer's own T (the Jacobian is diagonal in the layer)
     dtau_dp: np.ndarray                    # the same for p
     dtau_dvmr_self: list                   # [g]: vcd_dry vmr_g d sigma_g / d vmr_self: add it to tau_abs_dot[g] if the gas broadens itself
-    profile_slots: np.ndarray              # [K, nSpec, Nz]: dtau_dT T_dot[k] + dtau_dp p_dot[k]
+    profile_slots: np.ndarray              # [K, nSpec, Nz]: dtau_dT T_dot[k] + dtau_dp p_dot[k] (+ dtau_ddz dz_dot[k])
+    dtau_dvmr_continuum: dict = field(default_factory=dict)   # species -> d tau / d vmr of the continuum set (continua=)
+    dtau_ddz: Optional[np.ndarray] = None  # tau_continuum / Δz [m^-1]; None without continua
 
     def lin_model_slots(self):
         """tau_abs_dot + list(profile_slots): what host_model.LinModel(tau_abs_dot=...) takes; NGas is its length."""
         return list(self.tau_abs_dot) + list(self.profile_slots)
 
 
-def compute_absorption_profile_lin(models_and_vmrs, grid, p_full, T, vcd_dry, T_dot=None, p_dot=None, architecture=None):
+def compute_absorption_profile_lin(models_and_vmrs, grid, p_full, T, vcd_dry, T_dot=None, p_dot=None, architecture=None, continua=None,
+                                   dz=None, vmr=None, dz_dot=None):
     """compute_absorption_profile(..., lin=True) and the T, p and vmr_self Jacobians of tau_abs: an AbsorptionProfileLin.
     T_dot, p_dot [K, Nz] (either may be None = zeros) are K perturbation profiles, shaped as B_layer_dot is: a unit table per layer
     for weighting functions, a row of ones for a profile shift, p_full / p_surf for surface pressure; profile_slots[k] =
@@ -653,18 +735,23 @@ def compute_absorption_profile_lin(models_and_vmrs, grid, p_full, T, vcd_dry, T_
     synchronisation for the whole list.  vcd_dry is held FIXED: the caller owns d vcd_dry / d p_surf.  Refuses what
     compute_absorption_profile refuses, Voigt with CPF12ErrorFunction (NotImplementedError) and tables that are not [K, Nz], all
     before the first launch.  InterpolationModels mix in as in compute_absorption_profile: they add to dtau_dT and dtau_dp (and so
-    to profile_slots) through vsm_absorption_lut_eval_lin, and their dtau_dvmr_self[g] is exact zeros."""
+    to profile_slots) through vsm_absorption_lut_eval_lin, and their dtau_dvmr_self[g] is exact zeros.
+    continua, dz, vmr: a continuum set as in compute_absorption_profile; ONE vsm_absorption_continuum_lin launch adds it to tau_abs,
+    dtau_dT and dtau_dp behind the gases and fills dtau_dvmr_continuum[species] and dtau_ddz.  These partial derivatives hold Δz
+    FIXED, as vcd_dry is held fixed; dtau_ddz = tau_continuum / Δz, and dz_dot [K, Nz] adds dtau_ddz dz_dot[k] to profile_slots[k] on
+    the device -- a hydrostatic caller passes dz / T T_dot.  dz_dot without continua is refused."""
     pairs = list(models_and_vmrs)
     if not pairs:
         raise _lib.VSMError("compute_absorption_profile: no (model, vmr) pair")
+    cjob = _profile_continuum(continua, grid, p_full, T, dz, vmr, dz_dot)
     p = np.asarray(p_full, dtype=np.float64).reshape(-1)
     Tz = np.asarray(T, dtype=np.float64).reshape(-1)
     vcd = np.asarray(vcd_dry, dtype=np.float64).reshape(-1)
     Nz = len(p)
     if len(Tz) != Nz or len(vcd) != Nz or Nz < 1:
         raise _lib.VSMError("compute_absorption_profile: p_full, T and vcd_dry have %d, %d and %d layers" % (Nz, len(Tz), len(vcd)))
-    tabs = [None if t is None else np.asarray(t, dtype=np.float64) for t in (T_dot, p_dot)]
-    for name, t in zip(("T_dot", "p_dot"), tabs):
+    tabs = [None if t is None else np.asarray(t, dtype=np.float64) for t in (T_dot, p_dot, dz_dot)]
+    for name, t in zip(("T_dot", "p_dot", "dz_dot"), tabs):
         if t is not None and (t.ndim != 2 or t.shape[1] != Nz or t.shape[0] < 1):
             raise _lib.VSMError("compute_absorption_profile_lin: %s of shape %r is not [K, %d]" % (name, t.shape, Nz))
     if tabs[0] is not None and tabs[1] is not None and tabs[0].shape != tabs[1].shape:
@@ -672,7 +759,10 @@ def compute_absorption_profile_lin(models_and_vmrs, grid, p_full, T, vcd_dry, T_
     K = next((len(t) for t in tabs if t is not None), 0)
     if K > 65535:
         raise _lib.VSMError("compute_absorption_profile_lin: K = %d above 65535 profile slots" % K)
-    tabs = [np.zeros((K, Nz)) if t is None else t for t in tabs]
+    if tabs[2] is not None and tabs[2].shape[0] != K:
+        raise _lib.VSMError("compute_absorption_profile_lin: dz_dot %r differs in K (%d)" % (tabs[2].shape, K))
+    dz_tab = tabs[2]
+    tabs = [np.zeros((K, Nz)) if t is None else t for t in tabs[:2]]
     jobs, scales = [], []
     for model, vmr in pairs:                                        # (every refusal before the first launch)
         v = np.asarray(vmr, dtype=np.float64)
@@ -686,7 +776,7 @@ def compute_absorption_profile_lin(models_and_vmrs, grid, p_full, T, vcd_dry, T_
     def z():
         return np.zeros((nSpec, Nz))
 
-    if all(j.n_lines == 0 for j in jobs):
+    if all(j.n_lines == 0 for j in jobs) and cjob is None:
         return AbsorptionProfileLin(z(), [z() for _ in jobs], z(), z(), [z() for _ in jobs], np.zeros((K, nSpec, Nz)))
     dev = _Device(architecture if architecture is not None else pairs[0][0].architecture)
     tau, dT, dp = dev.empty(Nz, nSpec), dev.empty(Nz, nSpec), dev.empty(Nz, nSpec)
@@ -713,16 +803,28 @@ def compute_absorption_profile_lin(models_and_vmrs, grid, p_full, T, vcd_dry, T_
         dots.append(d)
         dvs.append(dv)
     live = [a for pair in zip(dots, dvs) for a in pair if a is not None]
+    cplanes = []
+    if cjob is not None:                                            # the set: behind the gases on tau, dT and dp; its own planes fresh
+        cplanes = [dev.empty(Nz, nSpec) for _ in range(cjob.n_planes - 3)]
+        acc = 1 if started else 0
+        dev.continuum_lin(cjob, [tau, dT, dp] + cplanes, [acc, acc, acc] + [0] * len(cplanes))
     slots = [dev.profile_slots(dT, dp, tabs[0], tabs[1])] if K else []
-    host = dev.fetch([tau, dT, dp] + slots + live)
+    if K and dz_tab is not None:
+        dev.profile_slots_add(cplanes[-1], dz_tab, slots[0])
+    host = dev.fetch([tau, dT, dp] + slots + live + cplanes)
+    chost = host[len(host) - len(cplanes):]
     it = iter(host[3 + len(slots):])
     out_dots, out_dvs = [], []
     for d, dv in zip(dots, dvs):
         out_dots.append(z() if d is None else np.ascontiguousarray(next(it).T))
         out_dvs.append(z() if dv is None else np.ascontiguousarray(next(it).T))
     ps = np.ascontiguousarray(np.transpose(host[3], (0, 2, 1))) if K else np.zeros((0, nSpec, Nz))
-    return AbsorptionProfileLin(np.ascontiguousarray(host[0].T), out_dots, np.ascontiguousarray(host[1].T),
-                                np.ascontiguousarray(host[2].T), out_dvs, ps)
+    r = AbsorptionProfileLin(np.ascontiguousarray(host[0].T), out_dots, np.ascontiguousarray(host[1].T),
+                             np.ascontiguousarray(host[2].T), out_dvs, ps)
+    if cjob is not None:
+        r.dtau_dvmr_continuum = {sp: np.ascontiguousarray(chost[i].T) for i, sp in enumerate(cjob.species)}
+        r.dtau_ddz = np.ascontiguousarray(chost[-1].T)
+    return r
 
 
 # ---- InterpolationModel: sigma(nu, p, T) lookup tables (make_model_helpers.jl:55-122, :181-233) --------------------------
@@ -985,3 +1087,403 @@ def _lut_cross_section(model, grid, pressure, temperature, wavelength_flag, lin)
     if job.reverse:
         dot = dot[:, :, ::-1].copy()
     return (sig[0], dot[:, 0]) if scalar else (sig, dot)
+
+
+# ---- continua: HITRAN CIA (cia.jl) and the MT_CKD H2O continuum (mtckd.jl), with Jacobians (ours) ------------------------
+k_B = 1.380649e-23                   # _CIA_K_B, J / K
+VMR_DEFAULTS = {"O2": 0.20946, "N2": 0.78084}      # _layer_vmr's USS dry-air fall-backs
+MTCKD_C2 = 1.4388                    # _MTCKD_C2, cm K (the device holds the same value)
+R_GAS = 8.3144598                    # atmo_prof.jl:43
+CONT_MAX_TABLES = 8                  # VSM_CONT_MAX_TABLES
+CONT_MAX_PLANES = 24                 # VSM_CONT_MAX_PLANES
+CONT_LAYERS = 4                      # VSM_CONT_LAYERS
+CONT_BAND_FIELDS = 10                # VSM_CONT_BAND_FIELDS
+
+
+@dataclass
+class CIABlock:
+    """One (T, ν, σ) block of a HITRAN .cia file; σ in cm^5 / molecule^2."""
+    formula: str
+    T: float
+    ν: np.ndarray
+    σ: np.ndarray
+
+    def __post_init__(self):
+        self.T = float(self.T)
+        self.ν = np.asarray(self.ν, dtype=np.float64).reshape(-1)
+        self.σ = np.asarray(self.σ, dtype=np.float64).reshape(-1)
+        if len(self.ν) != len(self.σ):
+            raise _lib.VSMError("CIABlock: ν has %d entries, σ %d" % (len(self.ν), len(self.σ)))
+
+
+def parse_cia_file(path):
+    """parse_cia_file(path) of cia.jl: the blocks of a local HITRAN .cia file, in file order.  A header is read by its fixed columns:
+    1-20 formula, 41-47 n_pts, 48-54 T; a line shorter than 54 characters or blank where a header is expected is skipped; of each of
+    the n_pts data lines the first two fields are taken."""
+    blocks = []
+    with open(path, "r") as f:
+        lines = [ln.rstrip("\r\n") for ln in f]
+    i = 0
+    while i < len(lines):
+        header = lines[i]
+        i += 1
+        if len(header) < 54 or not header.strip():
+            continue
+        formula = header[0:20].strip()
+        n_pts, T_K = int(header[40:47].strip()), float(header[47:54].strip())
+        if i + n_pts > len(lines):
+            raise _lib.VSMError("parse_cia_file: %s ends inside a block of %d points" % (path, n_pts))
+        vals = [ln.split() for ln in lines[i:i + n_pts]]
+        i += n_pts
+        blocks.append(CIABlock(formula, T_K, [float(v[0]) for v in vals], [float(v[1]) for v in vals]))
+    return blocks
+
+
+def _split_pair(formula):
+    parts = str(formula).strip().split("-")
+    if len(parts) < 2:
+        raise _lib.VSMError('CIA pair formula "%s" not recognised (expected "A-B")' % (formula,))
+    return parts[0], parts[1]
+
+
+def _project_linear(x, y_list, xq):
+    """_accumulate_σ! / build_mtckd_band for one block and several columns: (inside, values) with values[c] the linear interpolant of
+    (x, y_list[c]) at the points xq[inside] in the reference's arithmetic, w = (νq - ν1) / (ν2 - ν1), (1 - w) s1 + w s2; a point on
+    the block's first node takes its value."""
+    inside = ~((xq < x[0]) | (xq > x[-1]))
+    q = xq[inside]
+    j = np.searchsorted(x, q, side="left")            # searchsortedfirst, 0-based; <= len(x) - 1 inside the range
+    first = j == 0
+    j1 = np.where(first, 1 if len(x) > 1 else 0, j)
+    j0 = j1 - 1 if len(x) > 1 else j1
+    out = []
+    with np.errstate(invalid="ignore", divide="ignore"):
+        w = (q - x[j0]) / (x[j1] - x[j0])
+        for y in y_list:
+            out.append(np.where(first, y[0], (1 - w) * y[j0] + w * y[j1]))
+    return inside, out
+
+
+class CIATable:
+    """The reference's CIATable (pair, species_a, species_b, Ts ascending, σ_νT [nSpec, nT]) with the grid it was projected on.
+    FP64 only: σ is about 1e-45 cm^5 / molecule^2.  The device copy is [nT, nSpec]; it is uploaded where an MI355X is visible,
+    else on first use, and stays resident."""
+
+    def __init__(self, pair, species_a, species_b, Ts, σ_νT, ν_grid, architecture=None):
+        self.pair, self.species_a, self.species_b = str(pair), str(species_a), str(species_b)
+        self.Ts = np.asarray(Ts, dtype=np.float64).reshape(-1)
+        self.ν_grid = np.asarray(ν_grid, dtype=np.float64).reshape(-1)
+        self.σ_νT = np.asarray(σ_νT, dtype=np.float64)
+        if self.σ_νT.shape != (len(self.ν_grid), len(self.Ts)) or len(self.Ts) < 1 or len(self.ν_grid) < 1:
+            raise _lib.VSMError("CIATable: σ_νT of shape %r for %d grid points and %d temperatures"
+                                % (self.σ_νT.shape, len(self.ν_grid), len(self.Ts)))
+        if not np.all(np.diff(self.Ts) > 0):
+            raise _lib.VSMError("CIATable: Ts must be strictly ascending")
+        if not (np.all(np.isfinite(self.Ts)) and np.all(np.isfinite(self.ν_grid)) and np.all(np.isfinite(self.σ_νT))):
+            raise _lib.VSMError("CIATable: Ts, ν_grid and σ_νT must be finite")
+        self.architecture = architecture if architecture is not None else default_architecture()
+        self._dev = None
+        _make_resident(self)
+
+    @property
+    def resident(self):
+        return self._dev is not None
+
+    def _host_image(self):
+        return np.ascontiguousarray(self.σ_νT.T)
+
+    @classmethod
+    def from_arrays(cls, pair, Ts, σ_νT, ν_grid, architecture=None):
+        """A table from elsewhere: σ_νT [nSpec, nT] already on ν_grid, Ts strictly ascending."""
+        a, b = _split_pair(pair)
+        return cls(pair, a, b, Ts, σ_νT, ν_grid, architecture)
+
+    def __repr__(self):
+        return "CIATable(%s, %d temperatures, %d points%s)" % (self.pair, len(self.Ts), len(self.ν_grid),
+                                                                ", resident" if self.resident else "")
+
+
+def _make_resident(member):
+    """Uploads a continuum member where its architecture is a visible GPU; otherwise it is uploaded on first use."""
+    from .architectures import GPU, has_gpu
+    if member._dev is None and isinstance(member.architecture, GPU) and has_gpu():
+        member._dev = array_type(member.architecture)(member._host_image())
+    return member._dev
+
+
+def build_cia_table(blocks, ν_grid, architecture=None):
+    """build_cia_table(blocks, ν_grid) of cia.jl, on the host, once per band: per block temperature the blocks are projected on
+    ν_grid in file order, linear in ν inside a block's range and exact 0 outside; a later block of the same temperature overwrites
+    an earlier one where they overlap.  The grid may be in any order.  A block whose ν is not strictly ascending is refused (the
+    reference divides by zero there)."""
+    blocks = list(blocks)
+    if not blocks:
+        raise _lib.VSMError("build_cia_table: no blocks")
+    for n, blk in enumerate(blocks):
+        if not isinstance(blk, CIABlock):
+            raise _lib.VSMError("build_cia_table: block %d is no CIABlock" % n)
+        if len(blk.ν) < 1 or not np.all(np.diff(blk.ν) > 0):
+            raise _lib.VSMError("build_cia_table: block %d (%s, %g K): ν is empty or not strictly ascending" % (n, blk.formula, blk.T))
+    pair = blocks[0].formula
+    a, b = _split_pair(pair)
+    Ts = np.unique(np.asarray([blk.T for blk in blocks], dtype=np.float64))
+    grid = np.asarray(ν_grid, dtype=np.float64).reshape(-1)
+    σ = np.zeros((len(grid), len(Ts)))
+    for jt, T_pick in enumerate(Ts):
+        for blk in blocks:
+            if blk.T != T_pick:
+                continue
+            inside, (vals,) = _project_linear(blk.ν, [blk.σ], grid)
+            σ[inside, jt] = vals
+    return CIATable(pair, a, b, Ts, σ, grid, architecture)
+
+
+def load_cia_table(path, ν_grid, architecture=None):
+    return build_cia_table(parse_cia_file(path), ν_grid, architecture)
+
+
+@dataclass
+class MTCKDTable:
+    """The six variables of the AER reference file absco-ref_wv-mt-ckd: ν ascending (cm^-1), the self and foreign continuum
+    coefficients at T_ref (cm^2 / molecule / cm^-1), the self temperature exponent, p_ref (hPa) and T_ref (K)."""
+    ν: np.ndarray
+    C_self: np.ndarray
+    C_for: np.ndarray
+    self_texp: np.ndarray
+    p_ref: float
+    T_ref: float
+
+    def __post_init__(self):
+        for name in ("ν", "C_self", "C_for", "self_texp"):
+            setattr(self, name, np.asarray(getattr(self, name), dtype=np.float64).reshape(-1))
+        self.p_ref, self.T_ref = float(np.asarray(self.p_ref).reshape(-1)[0]), float(np.asarray(self.T_ref).reshape(-1)[0])
+        n = len(self.ν)
+        if n < 1 or any(len(getattr(self, k)) != n for k in ("C_self", "C_for", "self_texp")):
+            raise _lib.VSMError("MTCKDTable: ν, C_self, C_for and self_texp need one length >= 1")
+        if not np.all(np.diff(self.ν) > 0):
+            raise _lib.VSMError("MTCKDTable: ν must be strictly ascending")
+        if not (self.p_ref > 0 and self.T_ref > 0 and all(np.all(np.isfinite(getattr(self, k)))
+                                                          for k in ("ν", "C_self", "C_for", "self_texp"))):
+            raise _lib.VSMError("MTCKDTable: p_ref and T_ref must be positive and the arrays finite")
+
+
+def load_mtckd(path):
+    """load_mtckd(path) on a .npz that holds the AER file's six variables under its own names: wavenumbers, self_absco_ref,
+    for_absco_ref, self_texp, ref_press, ref_temp.  (NetCDF itself is not read: DESIGN 6.)"""
+    with np.load(path, allow_pickle=False) as z:
+        missing = [k for k in ("wavenumbers", "self_absco_ref", "for_absco_ref", "self_texp", "ref_press", "ref_temp") if k not in z]
+        if missing:
+            raise _lib.VSMError("load_mtckd: %s lacks %s" % (path, missing))
+        return MTCKDTable(z["wavenumbers"], z["self_absco_ref"], z["for_absco_ref"], z["self_texp"], z["ref_press"], z["ref_temp"])
+
+
+class MTCKDBand:
+    """The reference's MTCKDBand (C_self, C_for, texp on the model grid, p_ref, T_ref) with that grid; the device copy is
+    [4, nSpec] = (ν, C_self, C_for, texp)."""
+
+    def __init__(self, C_self, C_for, texp, p_ref, T_ref, ν_grid, architecture=None):
+        self.ν_grid = np.asarray(ν_grid, dtype=np.float64).reshape(-1)
+        self.C_self, self.C_for, self.texp = (np.asarray(a, dtype=np.float64).reshape(-1) for a in (C_self, C_for, texp))
+        self.p_ref, self.T_ref = float(p_ref), float(T_ref)
+        n = len(self.ν_grid)
+        if n < 1 or any(len(a) != n for a in (self.C_self, self.C_for, self.texp)):
+            raise _lib.VSMError("MTCKDBand: C_self, C_for, texp and ν_grid need one length >= 1")
+        if not (self.p_ref > 0 and self.T_ref > 0 and all(np.all(np.isfinite(a)) for a in (self.ν_grid, self.C_self, self.C_for, self.texp))):
+            raise _lib.VSMError("MTCKDBand: p_ref and T_ref must be positive and the arrays finite")
+        self.architecture = architecture if architecture is not None else default_architecture()
+        self._dev = None
+        _make_resident(self)
+
+    @property
+    def resident(self):
+        return self._dev is not None
+
+    def _host_image(self):
+        return np.ascontiguousarray(np.stack([self.ν_grid, self.C_self, self.C_for, self.texp]))
+
+
+def build_mtckd_band(table, ν_grid, architecture=None):
+    """build_mtckd_band(table, ν_grid) of mtckd.jl: the three coefficient arrays linear in ν on ν_grid, exact 0 outside the table."""
+    if not isinstance(table, MTCKDTable):
+        raise _lib.VSMError("build_mtckd_band: %r is no MTCKDTable" % (type(table).__name__,))
+    grid = np.asarray(ν_grid, dtype=np.float64).reshape(-1)
+    cols = [np.zeros(len(grid)) for _ in range(3)]
+    inside, vals = _project_linear(table.ν, [table.C_self, table.C_for, table.self_texp], grid)
+    for c, v in zip(cols, vals):
+        c[inside] = v
+    return MTCKDBand(cols[0], cols[1], cols[2], table.p_ref, table.T_ref, grid, architecture)
+
+
+def layer_thickness(p_half, T, vmr_h2o):
+    """The reference's hydrostatic Δz [m] per layer (atmo_prof.jl:67): (ln p_half[i+1] - ln p_half[i]) / (g0 M / (R T[i])) with
+    M = (1 - vmr_h2o) dry_mass + vmr_h2o wet_mass."""
+    from .raman_inputs import DRY_MASS, G0, WET_MASS
+    ph, Tz = np.asarray(p_half, dtype=np.float64).reshape(-1), np.asarray(T, dtype=np.float64).reshape(-1)
+    v = np.asarray(vmr_h2o, dtype=np.float64)
+    if len(ph) != len(Tz) + 1 or (v.ndim > 0 and v.shape != Tz.shape):
+        raise _lib.VSMError("layer_thickness: %d half levels, %d layers, vmr_h2o of shape %r" % (len(ph), len(Tz), v.shape))
+    M = (1 - v) * DRY_MASS + v * WET_MASS
+    return (np.log(ph[1:]) - np.log(ph[:-1])) / (G0 * M / (R_GAS * Tz))
+
+
+@dataclass
+class ContinuumProfileLin:
+    """What compute_continuum_profile(..., lin=True) returns; every array [nSpec, Nz].  The partial derivatives hold Δz FIXED (as
+    vcd_dry is held fixed in AbsorptionProfileLin); dtau_ddz = tau / Δz [m^-1] is the caller's to chain: a hydrostatic column has
+    dΔz / dT = Δz / T."""
+    tau: np.ndarray                        # bit for bit the forward call's
+    dtau_dT: np.ndarray                    # K^-1, of the layer's own T
+    dtau_dp: np.ndarray                    # hPa^-1
+    dtau_dvmr: dict                        # species -> d tau / d vmr of that species
+    dtau_ddz: np.ndarray                   # m^-1
+
+
+@dataclass
+class _ContinuumJob:
+    """One vsm_absorption_continuum(_lin) call, on the host."""
+    tables: list
+    band: object
+    nSpec: int
+    Nz: int
+    species: list                    # the vmr planes of the linearized call, in plane order
+    rows: np.ndarray                 # [nTables, Nz, 2] int32
+    w: np.ndarray                    # [nTables, Nz]
+    A: np.ndarray                    # [nPlanes, nTables, Nz] (plane 0 alone serves the forward call)
+    B: np.ndarray
+    band_layer: Optional[np.ndarray]   # [Nz, CONT_BAND_FIELDS]
+
+    @property
+    def n_planes(self):
+        return 4 + len(self.species)
+
+
+def _cia_cells(Ts, T):
+    """cia_σ_at_T! per layer: (j0, j1, w, 1 / (T2 - T1) or 0 where T is clamped).  T <= Ts[0] and T >= Ts[-1] give the end column back
+    exactly (w = 0, w = 1 on one row); a layer on an interior node lies in the cell below it (searchsortedfirst), with w = 1."""
+    nT = len(Ts)
+    lo, hi = T <= Ts[0], T >= Ts[-1]
+    j = np.clip(np.searchsorted(Ts, T, side="left"), 1, max(nT - 1, 1))
+    j0 = np.where(lo, 0, np.where(hi, nT - 1, j - 1))
+    j1 = np.where(lo, 0, np.where(hi, nT - 1, np.minimum(j, nT - 1)))
+    inner = ~(lo | hi)
+    T1, T2 = Ts[j0], Ts[j1]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        w = np.where(inner, (T - T1) / (T2 - T1), np.where(lo, 0.0, 1.0))
+        inv = np.where(inner, 1.0, 0.0)
+        span = np.where(inner, T2 - T1, 1.0)
+    return j0.astype(np.int32), j1.astype(np.int32), w, inv, span
+
+
+def _prepare_continuum(continua, grid, p_full, T, dz, vmr, fn="compute_continuum_profile") -> _ContinuumJob:
+    """Every refusal of a continuum set, and the per-layer coefficients of DESIGN 4.28 in the reference's order of operations."""
+    members = list(continua)
+    tables = [m for m in members if isinstance(m, CIATable)]
+    bands = [m for m in members if isinstance(m, MTCKDBand)]
+    if len(tables) + len(bands) != len(members):
+        raise _lib.VSMError("%s: continua holds something that is neither a CIATable nor an MTCKDBand" % fn)
+    if not members:
+        raise _lib.VSMError("%s: an empty continuum set" % fn)
+    if len(tables) > CONT_MAX_TABLES:
+        raise _lib.VSMError("%s: %d CIA tables above %d" % (fn, len(tables), CONT_MAX_TABLES))
+    if len(bands) > 1:
+        raise _lib.VSMError("%s: %d MTCKDBands; a set takes one" % (fn, len(bands)))
+    grid = np.asarray(grid, dtype=np.float64).reshape(-1)
+    for m in members:
+        if not np.array_equal(grid, m.ν_grid):
+            raise _lib.VSMError("%s: the grid is not the ν_grid a member of the set was built on" % fn)
+    p, Tz, dzv = (np.asarray(a, dtype=np.float64).reshape(-1) for a in (p_full, T, dz))
+    Nz = len(p)
+    if Nz < 1 or len(Tz) != Nz or len(dzv) != Nz:
+        raise _lib.VSMError("%s: p_full, T and dz have %d, %d and %d layers" % (fn, Nz, len(Tz), len(dzv)))
+    if Nz > 65535:
+        raise _lib.VSMError("%s: %d layers above 65535" % (fn, Nz))
+    for name, a in (("p_full", p), ("T", Tz), ("dz", dzv)):
+        if not np.all(np.isfinite(a) & (a > 0)):
+            raise _lib.VSMError("%s: %s must be finite and positive" % (fn, name))
+    species = []
+    for t in tables:
+        for sp in (t.species_a, t.species_b):
+            if sp not in species:
+                species.append(sp)
+    if bands and "H2O" not in species:
+        species.append("H2O")
+    vmr = dict(vmr or {})
+    vs = {}
+    for sp in species:
+        if sp in vmr:
+            v = np.asarray(vmr[sp], dtype=np.float64)
+        elif sp in VMR_DEFAULTS:
+            v = np.asarray(VMR_DEFAULTS[sp])
+        else:
+            raise _lib.VSMError('%s: no vmr for "%s" and no default defined' % (fn, sp))
+        if v.ndim > 0 and v.shape != (Nz,):
+            raise _lib.VSMError('%s: vmr["%s"] of shape %r is neither a scalar nor [%d]' % (fn, sp, v.shape, Nz))
+        v = np.ascontiguousarray(np.broadcast_to(v, (Nz,)))
+        if not np.all((v >= 0) & (v <= 1)):
+            raise _lib.VSMError('%s: vmr["%s"] outside [0, 1]' % (fn, sp))
+        vs[sp] = v
+    nP, nTab = 4 + len(species), len(tables)
+    if nP > CONT_MAX_PLANES:
+        raise _lib.VSMError("%s: %d species above the %d the planes hold" % (fn, len(species), CONT_MAX_PLANES - 4))
+    n_air = p * 1e2 / (k_B * Tz) * 1e-6
+    dz_cm = dzv * 100.0
+    rows, w = np.zeros((nTab, Nz, 2), dtype=np.int32), np.zeros((nTab, Nz))
+    A, B = np.zeros((nP, nTab, Nz)), np.zeros((nP, nTab, Nz))
+    for k, t in enumerate(tables):
+        j0, j1, wk, inner, span = _cia_cells(t.Ts, Tz)
+        rows[k, :, 0], rows[k, :, 1], w[k] = j0, j1, wk
+        va, vb = vs[t.species_a], vs[t.species_b]
+        prod = va * vb * n_air * n_air * dz_cm
+        n2dz = n_air * n_air * dz_cm
+        A[0, k] = prod
+        A[1, k] = -2.0 * prod / Tz
+        B[1, k] = inner * (prod / span)
+        A[2, k] = 2.0 * prod / p
+        if t.species_a == t.species_b:
+            A[3 + species.index(t.species_a), k] = 2.0 * va * n2dz
+        else:
+            A[3 + species.index(t.species_a), k] = vb * n2dz
+            A[3 + species.index(t.species_b), k] = va * n2dz
+        A[nP - 1, k] = prod / dzv
+    bl = None
+    if bands:
+        b, v = bands[0], vs["H2O"]
+        ppr = p / b.p_ref
+        S = v * p / b.p_ref * (v * n_air) * dz_cm
+        F = (p - v * p) / b.p_ref * (v * n_air) * dz_cm
+        bl = np.stack([Tz, b.T_ref / Tz, S, F, 2.0 * S / p, 2.0 * F / p, 2.0 * v * ppr * n_air * dz_cm,
+                       (1.0 - 2.0 * v) * ppr * n_air * dz_cm, S / dzv, F / dzv], axis=1)
+    return _ContinuumJob(tables=tables, band=bands[0] if bands else None, nSpec=len(grid), Nz=Nz, species=species, rows=rows, w=w,
+                         A=A, B=B, band_layer=None if bl is None else np.ascontiguousarray(bl))
+
+
+def _continuum_architecture(continua, architecture):
+    return architecture if architecture is not None else continua[0].architecture
+
+
+def compute_continuum_profile(continua, grid, p_full, T, dz, vmr, lin=False, architecture=None):
+    """compute_τ_cia! and compute_τ_h2o_continuum! for a whole SET -- a list of up to 8 CIATables and at most one MTCKDBand, all built
+    on `grid` -- and all layers: tau [nSpec, Nz], from ONE vsm_absorption_continuum launch and one synchronisation.  p_full [hPa], T
+    [K], dz [m] per layer (layer_thickness); vmr: species -> scalar or [Nz]; "O2" and "N2" default to 0.20946 and 0.78084, any other
+    species of the set that is missing raises, "H2O" with a band included.  The tables are added in list order, then the band's self
+    and foreign term.
+    lin=True: a ContinuumProfileLin -- tau (bit for bit the forward's), d tau / d(T, p, vmr of each species, Δz) at fixed Δz -- from
+    ONE vsm_absorption_continuum_lin launch.  The T derivative of a CIA table is that of the linear interpolant in the cell the
+    forward evaluates in, 0 where T is clamped to the table's range.
+    Refused before any launch (VSMError): a grid that is not array_equal to a member's ν_grid, more than 8 tables, two bands, an
+    empty set, p, T or dz <= 0, a vmr outside [0, 1], wrong lengths."""
+    continua = list(continua)
+    job = _prepare_continuum(continua, grid, p_full, T, dz, vmr)
+    dev = _Device(_continuum_architecture(continua, architecture))
+    if not lin:
+        out = dev.empty(job.Nz, job.nSpec)
+        dev.continuum(job, out, 0)
+        return np.ascontiguousarray(dev.fetch([out])[0].T)
+    planes = [dev.empty(job.Nz, job.nSpec) for _ in range(job.n_planes)]
+    dev.continuum_lin(job, planes, [0] * job.n_planes)
+    return _continuum_lin_result(job, dev.fetch(planes))
+
+
+def _continuum_lin_result(job, host):
+    t = [np.ascontiguousarray(h.T) for h in host]
+    return ContinuumProfileLin(t[0], t[1], t[2], {sp: t[3 + i] for i, sp in enumerate(job.species)}, t[-1])
