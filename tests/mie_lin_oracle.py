@@ -1,5 +1,6 @@
 """Test oracle of vsm.Scattering's linearized Mie: a numpy restatement of the reference's linearized NAI-2 path
-(src/Scattering/compute_NAI2_lin.jl, mie_helper_functions_lin.jl), float64 throughout.  It imports only mie_oracle.
+(src/Scattering/compute_NAI2_lin.jl, mie_helper_functions_lin.jl), in float64 and, with dtype = np.longdouble, in the x87 format
+on the same float64 inputs (see mie_oracle).  It imports only mie_oracle.
 
 compute_mie_ab_lin, compute_wx_lin restate the linearized compute_mie_ab! and compute_w_x; nai2_lin_reference takes what
 vsm_mie_nai2_lin takes and returns what it returns; compute_aerosol_optical_properties_lin chains the host part and it.
@@ -24,18 +25,20 @@ import mie_oracle as MO
 SLOTS = ("n_r", "n_i", "mu", "sigma")
 
 
-def compute_mie_ab_lin(x, m, nmax_i, n_max):
+def compute_mie_ab_lin(x, m, nmax_i, n_max, dtype=np.float64):
     """The linearized compute_mie_ab! for every radius at once: a_n, b_n [n_max, nquad] and their derivatives [2, n_max, nquad]
     with respect to n_r and n_i, exact zeros above n_max_i."""
-    x = np.asarray(x, dtype=np.float64)
+    R, Cx, _ = MO.arithmetic(dtype)
+    nmx = MO.start_orders(x, m, nmax_i)
+    x = np.asarray(x, dtype=np.float64).astype(R)
+    m = complex(m) if R is np.float64 else Cx(m)
     nq = len(x)
     nmax_i = np.asarray(nmax_i, dtype=np.int64)
     y = x * m
-    nmx = np.rint(np.maximum(nmax_i, np.abs(y)) + 51).astype(np.int64)
-    Dn = np.zeros((n_max + 1, nq), dtype=np.complex128)
-    Dd = np.zeros((2, n_max + 1, nq), dtype=np.complex128)
-    prev = np.zeros(nq, dtype=np.complex128)
-    prev_d = np.zeros((2, nq), dtype=np.complex128)
+    Dn = np.zeros((n_max + 1, nq), dtype=Cx)
+    Dd = np.zeros((2, n_max + 1, nq), dtype=Cx)
+    prev = np.zeros(nq, dtype=Cx)
+    prev_d = np.zeros((2, nq), dtype=Cx)
     for n in range(int(nmx.max()) - 1, 0, -1):
         on = n <= nmx - 1
         ratio = (n + 1) / y
@@ -47,10 +50,10 @@ def compute_mie_ab_lin(x, m, nmax_i, n_max):
         if n <= n_max:
             Dn[n] = prev
             Dd[:, n] = prev_d
-    an = np.zeros((n_max, nq), dtype=np.complex128)
-    bn = np.zeros((n_max, nq), dtype=np.complex128)
-    ad = np.zeros((2, n_max, nq), dtype=np.complex128)
-    bd = np.zeros((2, n_max, nq), dtype=np.complex128)
+    an = np.zeros((n_max, nq), dtype=Cx)
+    bn = np.zeros((n_max, nq), dtype=Cx)
+    ad = np.zeros((2, n_max, nq), dtype=Cx)
+    bd = np.zeros((2, n_max, nq), dtype=Cx)
     psi0, psi1, chi0, chi1 = np.cos(x), np.sin(x), -np.sin(x), np.cos(x)
     xi1 = psi1 + 1j * chi1
     with np.errstate(all="ignore"):       # (a small radius' chi overflows above its own n_max_i, where nothing is kept)
@@ -99,29 +102,43 @@ def compute_wx_lin_reference_form(r, raw, raw_dot):
     return wx_dot, 4 * math.pi * r ** 2 * wx_dot
 
 
-def nai2_lin_reference(x, wx, wr, wx_dot, wr_dot, nmax_i, mu, w_mu, n_r, n_i, k_wave, n_max):
+def greek_dot_from_bulk(bulk_f, C_sca, bulk_f_dot, C_sca_dot, mu, w_mu, dtype=np.float64):
+    """Stage 3 alone, linearized: greek_dot [4, 6, n_mu] from the unnormalised bulk functions [4, n_mu], their derivatives
+    [4, 4, n_mu], the bulk C_sca and its derivatives [4] -- mie_oracle.greek_from_bulk's counterpart."""
+    R = MO.arithmetic(dtype)[0]
+    bn_ = np.asarray(bulk_f).astype(R) / R(C_sca)
+    bulk_dot, cd = np.asarray(bulk_f_dot).astype(R), np.asarray(C_sca_dot).astype(R)
+    return MO.greek_quadrature([(bulk_dot[s] - bn_ * cd[s]) / R(C_sca) for s in range(4)], mu, w_mu, dtype)
+
+
+def nai2_lin_reference(x, wx, wr, wx_dot, wr_dot, nmax_i, mu, w_mu, n_r, n_i, k_wave, n_max, dtype=np.float64, scales=False):
     """compute_aerosol_optical_properties(lin, .) (compute_NAI2_lin.jl:86-253) from the host part's arrays.  Returns greek [6, n_mu],
     (C_sca, C_ext, ssa), bulk_f [4, n_mu] (unnormalised) as mie_oracle.nai2_reference, and greek_dot [4, 6, n_mu], scal_dot [4, 3]
-    (C_sca', C_ext', ssa' per slot), bulk_f_dot [4, 4, n_mu] (unnormalised: the sums over the radii alone)."""
-    x, wx, wr = (np.asarray(a, dtype=np.float64) for a in (x, wx, wr))
+    (C_sca', C_ext', ssa' per slot), bulk_f_dot [4, 4, n_mu] (unnormalised: the sums over the radii alone).  scales = True adds the
+    sums of the absolute terms behind stage 2's sums: bulk_abs [n_mu] and c_abs as mie_oracle.nai2_reference, bulk_dot_abs
+    [4, n_mu] = sum_i |wr_i 0.5 / x_i^2| 2 (|S1'| |S1| + |S2'| |S2|) for n_r and n_i, sum_i |wr_dot_i 0.5 / x_i^2| (|S1|^2 + |S2|^2)
+    for the two weight slots, and c_dot_abs [4, 2] for C_sca' and C_ext' alike."""
+    R, _, pi = MO.arithmetic(dtype)
+    x, wx, wr = (np.asarray(a, dtype=np.float64).astype(R) for a in (x, wx, wr))
+    wx_dot, wr_dot = (np.asarray(a, dtype=np.float64).astype(R) for a in (wx_dot, wr_dot))
     m = complex(n_r, -n_i)
-    pi_, tau_ = MO.compute_mie_pi_tau(mu, n_max)
-    an, bn, ad, bd = compute_mie_ab_lin(x, m, nmax_i, n_max)
-    S1, S2 = MO.compute_mie_S1S2(an, bn, pi_, tau_)
-    Sd = [MO.compute_mie_S1S2(ad[i], bd[i], pi_, tau_) for i in range(2)]
+    pi_, tau_ = MO.compute_mie_pi_tau(mu, n_max, dtype)
+    an, bn, ad, bd = compute_mie_ab_lin(x, m, nmax_i, n_max, dtype)
+    S1, S2 = MO.compute_mie_S1S2(an, bn, pi_, tau_, dtype)
+    Sd = [MO.compute_mie_S1S2(ad[i], bd[i], pi_, tau_, dtype) for i in range(2)]
     n_ = (2.0 * np.arange(1, n_max + 1) + 1)[:, None]
-    coef = 2 * math.pi / k_wave ** 2
+    coef = 2 * pi / k_wave ** 2
     C_sca = coef * np.sum(n_ * (np.abs(an) ** 2 + np.abs(bn) ** 2), axis=0)
     C_ext = coef * np.sum(n_ * np.real(an + bn), axis=0)
     inv_x2 = 0.5 / x ** 2
     cj = np.conj
     f = np.stack([inv_x2 * (np.abs(S1) ** 2 + np.abs(S2) ** 2), inv_x2 * np.real(S1 * cj(S2) + S2 * cj(S1)),
                   -inv_x2 * (np.abs(S1) ** 2 - np.abs(S2) ** 2), -inv_x2 * np.imag(S1 * cj(S2) - S2 * cj(S1))])
-    bulk_C_sca, bulk_C_ext = float(np.sum(wx * C_sca)), float(np.sum(wx * C_ext))
+    bulk_C_sca, bulk_C_ext = R(np.sum(wx * C_sca)), R(np.sum(wx * C_ext))
     ssa = bulk_C_sca / bulk_C_ext
     bulk = f @ wr
-    Cd = np.zeros((4, 2))                                   # (C_sca', C_ext') per slot
-    bulk_dot = np.zeros((4, 4, len(mu)))
+    Cd = np.zeros((4, 2), dtype=R)                          # (C_sca', C_ext') per slot
+    bulk_dot = np.zeros((4, 4, len(mu)), dtype=R)
     for i in range(2):
         d1, d2 = Sd[i]
         cs = coef * np.sum(n_ * np.real(an * cj(ad[i]) + ad[i] * cj(an) + bn * cj(bd[i]) + bd[i] * cj(bn)), axis=0)
@@ -138,19 +155,25 @@ def nai2_lin_reference(x, wx, wr, wx_dot, wr_dot, nmax_i, mu, w_mu, n_r, n_i, k_
     scal_dot = np.stack([Cd[:, 0], Cd[:, 1], (Cd[:, 0] - ssa * Cd[:, 1]) / bulk_C_ext], axis=1)
     bn_ = bulk / bulk_C_sca
     sets = [bn_] + [(bulk_dot[s] - bn_ * Cd[s, 0]) / bulk_C_sca for s in range(4)]
-    l_max = len(mu)
-    P, P2, R2, T2 = MO.compute_legendre_poly(mu, l_max)
-    out = np.zeros((5, 6, l_max))
-    for v, (b11, b33, b12, b34) in enumerate(sets):
-        for l in range(l_max):
-            fac = (2 * l + 1) / 2 * math.sqrt(1 / ((l - 1) * l * (l + 1) * (l + 2))) if l >= 2 else 0.0
-            out[v, 3, l] = (2 * l + 1) / 2 * (w_mu @ (b33 * P[:, l]))
-            out[v, 1, l] = (2 * l + 1) / 2 * (w_mu @ (b11 * P[:, l]))
-            out[v, 2, l] = fac * (w_mu @ (b12 * P2[:, l]))
-            out[v, 4, l] = fac * (w_mu @ (b34 * P2[:, l]))
-            out[v, 5, l] = fac * (w_mu @ (b33 * R2[:, l] + b11 * T2[:, l]))
-            out[v, 0, l] = fac * (w_mu @ (b11 * R2[:, l] + b33 * T2[:, l]))
-    return out[0], (bulk_C_sca, bulk_C_ext, ssa), bulk, out[1:], scal_dot, bulk_dot, (an, bn, ad, bd)
+    out = MO.greek_quadrature(sets, mu, w_mu, dtype)
+    res = out[0], (bulk_C_sca, bulk_C_ext, ssa), bulk, out[1:], scal_dot, bulk_dot, (an, bn, ad, bd)
+    if scales:
+        c_ext_abs = coef * np.sum(n_ * np.abs(np.real(an + bn)), axis=0)
+        awx, awr = np.abs(wx), np.abs(wr)
+        bulk_dot_abs = np.zeros((4, len(mu)), dtype=R)
+        c_dot_abs = np.zeros((4, 2), dtype=R)
+        for i in range(2):
+            d1, d2 = Sd[i]
+            bulk_dot_abs[i] = (inv_x2 * 2 * (np.abs(d1) * np.abs(S1) + np.abs(d2) * np.abs(S2))) @ awr
+            cs = coef * np.sum(n_ * 2 * (np.abs(an) * np.abs(ad[i]) + np.abs(bn) * np.abs(bd[i])), axis=0)
+            ce = coef * np.sum(n_ * np.abs(np.real(ad[i] + bd[i])), axis=0)
+            c_dot_abs[i] = np.sum(awx * cs), np.sum(awx * ce)
+        for k in range(2):
+            bulk_dot_abs[2 + k] = f[0] @ np.abs(wr_dot[k])
+            c_dot_abs[2 + k] = np.sum(np.abs(wx_dot[k]) * C_sca), np.sum(np.abs(wx_dot[k]) * c_ext_abs)
+        res += (types.SimpleNamespace(bulk_abs=f[0] @ awr, c_abs=(np.sum(awx * C_sca), np.sum(awx * c_ext_abs)),
+                                      bulk_dot_abs=bulk_dot_abs, c_dot_abs=c_dot_abs),)
+    return res
 
 
 def mie_lin_inputs(size_distribution, wavelength, r_max, nquad_radius, tabulated=None, weights=compute_wx_lin):

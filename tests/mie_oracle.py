@@ -1,5 +1,8 @@
 """Test oracle of vsm.Scattering: a numpy restatement of the reference's NAI-2 Mie path (src/Scattering/compute_NAI2.jl,
-mie_helper_functions.jl, legendre_functions.jl), float64 throughout.  It imports nothing from the package.
+mie_helper_functions.jl, legendre_functions.jl), in float64 -- and, with dtype = np.longdouble, in the x87 format (64-bit mantissa)
+on the same float64 inputs: the reference against which the float64 path's own rounding is measured (tests/test_oracle_mie.py,
+tests/test_gpu_mie_edges.py).  The float64 path is the default and is pinned to the bit by recorded values.  It imports nothing
+from the package.
 
 get_n_max, compute_mie_ab, compute_mie_pi_tau, compute_mie_S1S2, gauleg_log, compute_wx, compute_legendre_poly restate the
 functions of the same names; the recurrences run in the reference's order of operations, vectorised over the radii (and, for the
@@ -43,23 +46,41 @@ def get_n_max(x):
     return int(round(x + 4.05 * x ** (1 / 3) + 10)) if x > 8.0 else int(round(x + 4.0 * x ** (1 / 3) + 1))
 
 
-def compute_mie_ab(x, m, nmax_i, n_max):
+def arithmetic(dtype):
+    """(real type, complex type, pi) of np.float64 -- the default everywhere, the oracle as it always was, to the bit -- or of
+    np.longdouble with np.clongdouble.  The inputs are the same float64 arrays in both; only the arithmetic widens."""
+    if dtype == np.float64:
+        return np.float64, np.complex128, math.pi
+    if dtype == np.longdouble:
+        return np.longdouble, np.clongdouble, 4 * np.arctan(np.longdouble(1))
+    raise ValueError("dtype %r: np.float64 or np.longdouble" % (dtype,))
+
+
+def start_orders(x, m, nmax_i):
+    """nmx_i = round(max(n_max_i, |y_i|) + 51), in float64 whatever the arithmetic: both formats walk the same recurrence."""
+    y = np.asarray(x, dtype=np.float64) * complex(m)
+    return np.rint(np.maximum(np.asarray(nmax_i, dtype=np.int64), np.abs(y)) + 51).astype(np.int64)
+
+
+def compute_mie_ab(x, m, nmax_i, n_max, dtype=np.float64):
     """compute_mie_ab! (:42-88) for every radius at once: a_n, b_n [n_max, nquad] complex, exact zeros above n_max_i."""
-    x = np.asarray(x, dtype=np.float64)
+    R, Cx, _ = arithmetic(dtype)
+    nmx = start_orders(x, m, nmax_i)
+    x = np.asarray(x, dtype=np.float64).astype(R)
+    m = complex(m) if R is np.float64 else Cx(m)
     nq = len(x)
     nmax_i = np.asarray(nmax_i, dtype=np.int64)
     y = x * m
-    nmx = np.rint(np.maximum(nmax_i, np.abs(y)) + 51).astype(np.int64)
-    Dn = np.zeros((n_max + 1, nq), dtype=np.complex128)           # Dn[n], 1 <= n <= n_max, of each radius
-    prev = np.zeros(nq, dtype=np.complex128)
+    Dn = np.zeros((n_max + 1, nq), dtype=Cx)                      # Dn[n], 1 <= n <= n_max, of each radius
+    prev = np.zeros(nq, dtype=Cx)
     for n in range(int(nmx.max()) - 1, 0, -1):
         on = n <= nmx - 1
         ratio = (n + 1) / y
         prev = np.where(on, ratio - 1 / (prev + ratio), prev)
         if n <= n_max:
             Dn[n] = prev
-    an = np.zeros((n_max, nq), dtype=np.complex128)
-    bn = np.zeros((n_max, nq), dtype=np.complex128)
+    an = np.zeros((n_max, nq), dtype=Cx)
+    bn = np.zeros((n_max, nq), dtype=Cx)
     psi0, psi1, chi0, chi1 = np.cos(x), np.sin(x), -np.sin(x), np.cos(x)
     xi1 = psi1 + 1j * chi1
     with np.errstate(all="ignore"):       # (a small radius' chi overflows above its own n_max_i, where nothing is kept)
@@ -77,9 +98,12 @@ def compute_mie_ab(x, m, nmax_i, n_max):
     return an, bn
 
 
-def compute_mie_S1S2(an, bn, pi_, tau_):
+def compute_mie_S1S2(an, bn, pi_, tau_, dtype=np.float64):
     """compute_mie_S1S2! (:307-320) for every radius: S1, S2 [n_mu, nquad]."""
+    R = arithmetic(dtype)[0]
     n = np.arange(1, an.shape[0] + 1)
+    if R is not np.float64:
+        n = n.astype(R)
     c = ((2 * n + 1) / (n * (n + 1)))[:, None]
     return tau_ @ (c * an) + pi_ @ (c * bn), pi_ @ (c * an) + tau_ @ (c * bn)
 
@@ -111,11 +135,12 @@ def get_greek_rayleigh(depol):
 
 
 # ---- legendre_functions.jl -----------------------------------------------------------------------------------------------
-def compute_mie_pi_tau(mu, nmax):
+def compute_mie_pi_tau(mu, nmax, dtype=np.float64):
     """compute_mie_pi_tau (:195-214): pi_n, tau_n [n_mu, nmax], n = 1 .. nmax in column n - 1."""
-    mu = np.asarray(mu, dtype=np.float64)
-    pi_ = np.zeros((len(mu), nmax))
-    tau_ = np.zeros((len(mu), nmax))
+    R = arithmetic(dtype)[0]
+    mu = np.asarray(mu, dtype=np.float64).astype(R)
+    pi_ = np.zeros((len(mu), nmax), dtype=R)
+    tau_ = np.zeros((len(mu), nmax), dtype=R)
     pi_[:, 0], pi_[:, 1] = 1.0, 3 * mu
     tau_[:, 0], tau_[:, 1] = mu, 6 * mu ** 2 - 3
     for n in range(2, nmax):
@@ -124,24 +149,25 @@ def compute_mie_pi_tau(mu, nmax):
     return pi_, tau_
 
 
-def compute_legendre_poly(x, nmax):
+def compute_legendre_poly(x, nmax, dtype=np.float64):
     """compute_legendre_poly (:223-265): P, P2, R2, T2 [len(x), nmax], moment l in column l."""
     assert nmax > 1
-    x = np.asarray(x, dtype=np.float64)
-    P0, P2, R2, T2 = (np.zeros((len(x), nmax)) for _ in range(4))
+    R = arithmetic(dtype)[0]
+    x = np.asarray(x, dtype=np.float64).astype(R)
+    P0, P2, R2, T2 = (np.zeros((len(x), nmax), dtype=R) for _ in range(4))
     P0[:, 0], P0[:, 1] = 1, x
     if nmax > 2:
         P2[:, 2] = 3 * (1 - x ** 2)
-        R2[:, 2] = math.sqrt(1.5) * (1 + x ** 2)
-        T2[:, 2] = math.sqrt(6) * x
+        R2[:, 2] = np.sqrt(R(1.5)) * (1 + x ** 2)
+        T2[:, 2] = np.sqrt(R(6)) * x
     for n in range(2, nmax):
         l = n - 1
         P0[:, n] = ((2 * l + 1) * x * P0[:, n - 1] - l * P0[:, n - 2]) / (l + 1)
         if n > 2:
             ia = (2 * l + 1) * x
-            ib = math.sqrt((l + 2) * (l - 2)) * (l + 2) / l
-            ic = 4.0 * (2 * l + 1) / ((l + 1) * l)
-            id_ = math.sqrt((l + 3) * (l - 1)) * (l - 1) / (l + 1)
+            ib = np.sqrt(R((l + 2) * (l - 2))) * (l + 2) / l
+            ic = R(4.0) * (2 * l + 1) / ((l + 1) * l)
+            id_ = np.sqrt(R((l + 3) * (l - 1))) * (l - 1) / (l + 1)
             P2[:, n] = (ia * P2[:, n - 1] - (l + 2) * P2[:, n - 2]) / (l - 1)
             R2[:, n] = (ia * R2[:, n - 1] - ib * R2[:, n - 2] - ic * T2[:, n - 1]) / id_
             T2[:, n] = (ia * T2[:, n - 1] - ib * T2[:, n - 2] - ic * R2[:, n - 1]) / id_
@@ -159,38 +185,61 @@ def reconstruct_phase(greek, mu):
 
 
 # ---- compute_NAI2.jl -----------------------------------------------------------------------------------------------------
-def nai2_reference(x, wx, wr, nmax_i, mu, w_mu, n_r, n_i, k_wave, n_max):
+def greek_quadrature(sets, mu, w_mu, dtype=np.float64):
+    """The six quadratures of compute_NAI2.jl:188-202 for each set (b11, b33, b12, b34) [4, n_mu] of normalised functions at the
+    nodes mu: [len(sets), 6, n_mu] (alpha, beta, gamma, delta, epsilon, zeta)."""
+    R = arithmetic(dtype)[0]
+    w_mu = np.asarray(w_mu, dtype=np.float64).astype(R)
+    l_max = len(mu)
+    P, P2, R2, T2 = compute_legendre_poly(mu, l_max, dtype)
+    out = np.zeros((len(sets), 6, l_max), dtype=R)
+    for v, (b11, b33, b12, b34) in enumerate(sets):
+        for l in range(l_max):
+            fac = R(2 * l + 1) / 2 * np.sqrt(1 / R((l - 1) * l * (l + 1) * (l + 2))) if l >= 2 else 0.0
+            out[v, 3, l] = R(2 * l + 1) / 2 * (w_mu @ (b33 * P[:, l]))
+            out[v, 1, l] = R(2 * l + 1) / 2 * (w_mu @ (b11 * P[:, l]))
+            out[v, 2, l] = fac * (w_mu @ (b12 * P2[:, l]))
+            out[v, 4, l] = fac * (w_mu @ (b34 * P2[:, l]))
+            out[v, 5, l] = fac * (w_mu @ (b33 * R2[:, l] + b11 * T2[:, l]))
+            out[v, 0, l] = fac * (w_mu @ (b11 * R2[:, l] + b33 * T2[:, l]))
+    return out
+
+
+def greek_from_bulk(bulk_f, C_sca, mu, w_mu, dtype=np.float64):
+    """Stage 3 alone (compute_NAI2.jl:161-202): greek [6, n_mu] from the unnormalised bulk functions [4, n_mu] at the nodes and the
+    bulk C_sca -- of the oracle's own stage 2 in nai2_reference, of the device's in the tests of its stage 3."""
+    R = arithmetic(dtype)[0]
+    return greek_quadrature([np.asarray(bulk_f).astype(R) / R(C_sca)], mu, w_mu, dtype)[0]
+
+
+def nai2_reference(x, wx, wr, nmax_i, mu, w_mu, n_r, n_i, k_wave, n_max, dtype=np.float64, scales=False):
     """compute_aerosol_optical_properties (compute_NAI2.jl:99-202) from the host part's arrays: the inputs of vsm_mie_nai2.
     Returns greek [6, n_mu] (alpha, beta, gamma, delta, epsilon, zeta), (C_sca, C_ext, ssa), bulk_f [4, n_mu] (f11, f33, f12, f34,
-    NOT yet divided by C_sca: stage 2's output)."""
-    x, wx, wr = (np.asarray(a, dtype=np.float64) for a in (x, wx, wr))
+    NOT yet divided by C_sca: stage 2's output).  scales = True adds the sums of the absolute terms behind the sums of stage 2, the
+    scales a rounding error of theirs is measured on: bulk_abs [n_mu] = sum_i |wr_i 0.5 / x_i^2| (|S1|^2 + |S2|^2) per angle,
+    c_abs = sum_i |wx_i| 2 pi / k^2 sum_n (2n + 1) (|a_n|^2 + |b_n|^2  and  |Re(a_n + b_n)|) for C_sca and C_ext."""
+    R, _, pi = arithmetic(dtype)
+    x, wx, wr = (np.asarray(a, dtype=np.float64).astype(R) for a in (x, wx, wr))
     m = complex(n_r, -n_i)
-    pi_, tau_ = compute_mie_pi_tau(mu, n_max)
-    an, bn = compute_mie_ab(x, m, nmax_i, n_max)
-    S1, S2 = compute_mie_S1S2(an, bn, pi_, tau_)
+    pi_, tau_ = compute_mie_pi_tau(mu, n_max, dtype)
+    an, bn = compute_mie_ab(x, m, nmax_i, n_max, dtype)
+    S1, S2 = compute_mie_S1S2(an, bn, pi_, tau_, dtype)
     n_ = (2.0 * np.arange(1, n_max + 1) + 1)[:, None]
-    C_sca = 2 * math.pi / k_wave ** 2 * np.sum(n_ * (np.abs(an) ** 2 + np.abs(bn) ** 2), axis=0)
-    C_ext = 2 * math.pi / k_wave ** 2 * np.sum(n_ * np.real(an + bn), axis=0)
+    C_sca = 2 * pi / k_wave ** 2 * np.sum(n_ * (np.abs(an) ** 2 + np.abs(bn) ** 2), axis=0)
+    C_ext = 2 * pi / k_wave ** 2 * np.sum(n_ * np.real(an + bn), axis=0)
     inv_x2 = 0.5 / x ** 2
     f11 = inv_x2 * (np.abs(S1) ** 2 + np.abs(S2) ** 2)
     f33 = inv_x2 * np.real(S1 * np.conj(S2) + S2 * np.conj(S1))
     f12 = -inv_x2 * (np.abs(S1) ** 2 - np.abs(S2) ** 2)
     f34 = -inv_x2 * np.imag(S1 * np.conj(S2) - S2 * np.conj(S1))
-    bulk_C_sca, bulk_C_ext = float(np.sum(wx * C_sca)), float(np.sum(wx * C_ext))
+    bulk_C_sca, bulk_C_ext = R(np.sum(wx * C_sca)), R(np.sum(wx * C_ext))
     bulk = np.stack([f11 @ wr, f33 @ wr, f12 @ wr, f34 @ wr])
-    b11, b33, b12, b34 = bulk / bulk_C_sca
-    l_max = len(mu)
-    P, P2, R2, T2 = compute_legendre_poly(mu, l_max)
-    greek = np.zeros((6, l_max))
-    for l in range(l_max):
-        fac = (2 * l + 1) / 2 * math.sqrt(1 / ((l - 1) * l * (l + 1) * (l + 2))) if l >= 2 else 0.0
-        greek[3, l] = (2 * l + 1) / 2 * (w_mu @ (b33 * P[:, l]))
-        greek[1, l] = (2 * l + 1) / 2 * (w_mu @ (b11 * P[:, l]))
-        greek[2, l] = fac * (w_mu @ (b12 * P2[:, l]))
-        greek[4, l] = fac * (w_mu @ (b34 * P2[:, l]))
-        greek[5, l] = fac * (w_mu @ (b33 * R2[:, l] + b11 * T2[:, l]))
-        greek[0, l] = fac * (w_mu @ (b11 * R2[:, l] + b33 * T2[:, l]))
-    return greek, (bulk_C_sca, bulk_C_ext, bulk_C_sca / bulk_C_ext), bulk
+    greek = greek_from_bulk(bulk, bulk_C_sca, mu, w_mu, dtype)
+    out = greek, (bulk_C_sca, bulk_C_ext, bulk_C_sca / bulk_C_ext), bulk
+    if scales:
+        c_ext_abs = 2 * pi / k_wave ** 2 * np.sum(n_ * np.abs(np.real(an + bn)), axis=0)
+        out += (types.SimpleNamespace(bulk_abs=f11 @ np.abs(wr), c_abs=(np.sum(np.abs(wx) * C_sca), np.sum(np.abs(wx) * c_ext_abs))),)
+    return out
 
 
 def mie_inputs(size_distribution, wavelength, r_max, nquad_radius, tabulated=None):

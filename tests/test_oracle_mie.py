@@ -1,9 +1,12 @@
 """CPU tests of tests/mie_oracle.py (the numpy restatement of the reference's NAI-2 Mie path) against numbers that are not ours:
 published single-sphere efficiencies, the Rayleigh limit, the identities a Greek expansion satisfies -- and of the host part of
-vsm.Scattering against the oracle's, bit for bit.  No kernel runs here."""
+vsm.Scattering against the oracle's, bit for bit; and, for the edge cases of tests/mie_cases.py, of the two conditions the GPU edge
+tests (tests/test_gpu_mie_edges.py) rest on: a defect of one order, radius or angle moves the outputs by >= 1e-6, and the float64
+oracle stays within 1e-10 of its long-double form.  No kernel runs here."""
 import math
 import os
 import re
+import types
 
 import numpy as np
 import pytest
@@ -144,3 +147,98 @@ def test_fine_mode_aerosol_drops_into_model_from_arrays(vsm):
         for a, b in zip(H.constructCoreOpticalProperties(pm, m), O.construct_core_optical_properties(om, m)):
             assert np.allclose(a.tau, b.tau, rtol=1e-15) and np.allclose(a.varpi, b.varpi, rtol=1e-15)
             assert np.allclose(a.Zpp, b.Zpp, rtol=1e-12, atol=1e-13)
+
+
+# ---- the edge cases of tests/mie_cases.py: recipe, float64 path unchanged, sensitivity, rounding floor ---------------------------------
+import mie_cases as MC
+
+GOLDEN_F64, GOLDEN_CASES, SENSITIVITY = MC.GOLDEN_F64, MC.GOLDEN_CASES, MC.SENSITIVITY
+perturbations, greek_move = MC.perturbations, MC.greek_move
+
+
+def test_cases_follow_the_recipe():
+    assert [(c.nquad, c.n_max) for c in MC.CASES[:11]] == MC.SHAPES and len(MC.CASES) == 14 and len(set(MC.NAMES)) == 14
+    for c in MC.CASES:
+        h = MC.inputs(c)
+        top = c.n_max if c.cap is None else c.cap
+        nm = h.nmax_i
+        assert nm.dtype == np.int32 and nm.shape == (c.nquad,) and nm.min() >= 1 and nm.max() == top
+        if c.nquad > 1:
+            assert nm.min() == 1 and np.any(np.diff(nm) > 0) and np.any(np.diff(nm) < 0), c.name       # at 1; unsorted
+        if c.n_max >= 6:
+            have = set(nm.tolist())
+            assert any({4 * j - 1, 4 * j, 4 * j + 1} <= have for j in range(1, top // 4 + 1)), c.name
+        u = h.x / (nm + 1)
+        assert np.all(u >= 1.0) and np.all(u <= 1.3) and np.all(h.x > nm)                              # cut-offs below x
+        assert np.all(h.wx > 0) and abs(h.wx.sum() - 1) <= 1e-15 and np.all(h.wx * c.nquad < 3) and np.all(h.wx * c.nquad > 1 / 3)
+        assert np.array_equal(h.wr, 4 * math.pi * h.x ** 2 * h.wx) and np.array_equal(h.wr_dot, 4 * math.pi * h.x ** 2 * h.wx_dot)
+        assert h.k_wave == 1.0 and h.n_mu == 2 * c.n_max - 1 == len(h.mu) == len(h.w_mu)
+        assert h.wx_dot.shape == (2, c.nquad) and np.all(np.abs(h.wx_dot.sum(axis=1)) <= 1e-15)
+        if c.nquad > 1:
+            assert np.any(h.wx_dot > 0) and np.any(h.wx_dot < 0)
+        again = MC.inputs(c)
+        assert all(np.array_equal(getattr(h, k), getattr(again, k)) for k in ("x", "wx", "wx_dot", "nmax_i"))
+    assert MC.inputs(MC.BY_NAME["q33_n32_cap20"]).nmax_i.max() == 20
+    assert MC.BY_NAME["q33_n32_real"].m == (1.33, 0.0) and MC.BY_NAME["q33_n32_absorbing"].m == (2.0, 1.0)
+
+
+@pytest.mark.parametrize("name", GOLDEN_CASES)
+def test_float64_path_is_the_recorded_one_bit_for_bit(name):
+    """The default path against what the oracle returned before it took a dtype (tests/golden/mie_oracle_float64.npz)."""
+    want = np.load(GOLDEN_F64)
+    h = MC.inputs(MC.BY_NAME[name])
+    greek, scal, bulk = MO.nai2_reference(*MC.forward_args(h))
+    assert greek.dtype == bulk.dtype == np.float64
+    assert np.array_equal(greek, want[name + "/greek"]) and np.array_equal(bulk, want[name + "/bulk_f"])
+    assert np.array_equal(np.array(scal, dtype=np.float64), want[name + "/scal"])
+    for explicit in (MO.nai2_reference(*MC.forward_args(h), dtype=np.float64), MO.nai2_reference(*MC.forward_args(h), scales=True)):
+        assert np.array_equal(explicit[0], greek) and explicit[1] == scal and np.array_equal(explicit[2], bulk)
+    # stage 3 factored out: the same numbers from the bulk functions alone
+    assert np.array_equal(MO.greek_from_bulk(bulk, scal[0], h.mu, h.w_mu), greek)
+
+
+def test_long_double_path_widens_the_arithmetic_only():
+    h = MC.inputs(MC.BY_NAME["q33_n32"])
+    g64, s64, b64 = MO.nai2_reference(*MC.forward_args(h))
+    gld, sld, bld, S = MO.nai2_reference(*MC.forward_args(h), dtype=np.longdouble, scales=True)
+    assert gld.dtype == bld.dtype == np.longdouble and isinstance(sld[0], np.longdouble) and np.finfo(np.longdouble).nmant >= 63
+    assert S.bulk_abs.dtype == np.longdouble and np.all(S.bulk_abs > 0) and S.c_abs[0] > 0 and S.c_abs[1] > 0
+    for a, b in ((g64, gld), (b64, bld)):
+        dev = float(np.max(np.abs(a - b)) / np.max(np.abs(b)))
+        assert 0 < dev < 1e-12, dev                          # not the same numbers, and no further apart than float64 rounding
+    for fn, args in ((MO.compute_mie_pi_tau, (h.mu, 5)), (MO.compute_legendre_poly, (h.mu, 5)),
+                     (MO.compute_mie_ab, (h.x, complex(1.4, -0.01), h.nmax_i, 32))):
+        assert all(a.dtype in (np.longdouble, np.clongdouble) for a in fn(*args, dtype=np.longdouble))
+        assert all(a.dtype in (np.float64, np.complex128) for a in fn(*args))
+    with pytest.raises(ValueError):
+        MO.nai2_reference(*MC.forward_args(h), dtype=np.float32)
+
+
+@pytest.mark.parametrize("name", MC.NAMES)
+def test_a_defect_of_one_order_radius_or_angle_moves_the_coefficients(name):
+    """Sensitivity: each perturbation moves at least one Greek vector by >= 1e-6 of max(1, max |vector|) -- three decades above the
+    largest bound tests/test_gpu_mie_edges.py may assert (1e-9)."""
+    c = MC.BY_NAME[name]
+    h = MC.inputs(c)
+    base = MO.nai2_reference(*MC.forward_args(h))[0]
+    least = (math.inf, None)
+    for what, change in perturbations(h, c.n_max):
+        d = dict(vars(h))
+        d.update(change)
+        move = greek_move(MO.nai2_reference(*MC.forward_args(types.SimpleNamespace(**d)))[0], base)
+        least = min(least, (move, what))
+        assert move >= SENSITIVITY, (name, what, move)
+    print("mie sensitivity %s: least move %.2e (%s)" % (name, least[0], least[1]))
+
+
+@pytest.mark.parametrize("name", MC.NAMES)
+def test_rounding_floor_of_the_forward_outputs(name):
+    """Floor: float64 against long double on the comparison scales, over the oracle itself and eight runs with every x_i one ulp
+    off; no case above 1e-10."""
+    ref, floor = MC.case_floors(name)
+    print("mie floor %s: %s" % (name, "  ".join("%s %.1e" % (f, floor[f]) for f in MC.FORWARD)))
+    for f in MC.FORWARD:
+        assert MC.MIN_FLOOR <= floor[f] <= MC.FLOOR_LIMIT, (name, f, floor[f])
+    if MC.BY_NAME[name].m[1] == 0.0:                          # no absorption: the albedo is 1
+        assert abs(MC.oracle(MC.inputs(MC.BY_NAME[name]))["scal"][2] - 1.0) <= 10 * floor["scal"]
+        assert abs(float(ref["scal"][2]) - 1.0) <= 1e-17

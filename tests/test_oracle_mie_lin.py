@@ -134,3 +134,60 @@ def test_host_part_equals_the_oracles_bit_for_bit(vsm, case):
     assert not np.any(wx_0) and not np.any(wr_0) and wx_0.shape == (2, nquad)
     with pytest.raises(vsm.VSMError):
         S.TabulatedSizeDistribution(r, raw, weights_dot=np.zeros((nquad, 2)))
+
+
+# ---- the edge cases of tests/mie_cases.py: float64 path unchanged, sensitivity of the n_r slot, rounding floor ---------------------------
+import types
+
+import mie_cases as MC
+
+GOLDEN_F64, GOLDEN_CASES, SENSITIVITY = MC.GOLDEN_F64, MC.GOLDEN_CASES, MC.SENSITIVITY
+perturbations, greek_move = MC.perturbations, MC.greek_move
+
+
+@pytest.mark.parametrize("name", GOLDEN_CASES)
+def test_float64_path_is_the_recorded_one_bit_for_bit(name):
+    """The default path against what the oracle returned before it took a dtype (tests/golden/mie_oracle_float64.npz)."""
+    want = np.load(GOLDEN_F64)
+    h = MC.inputs(MC.BY_NAME[name])
+    greek, scal, bulk, greek_dot, scal_dot, bulk_dot, _ab = ML.nai2_lin_reference(*MC.lin_args(h))
+    for got, key in ((greek, "lin_greek"), (np.array(scal, dtype=np.float64), "lin_scal"), (bulk, "lin_bulk_f"),
+                     (greek_dot, "greek_dot"), (scal_dot, "scal_dot"), (bulk_dot, "bulk_f_dot")):
+        assert got.dtype == np.float64 and np.array_equal(got, want[name + "/" + key]), key
+    assert np.array_equal(greek, want[name + "/greek"]) and np.array_equal(bulk, want[name + "/bulk_f"])
+    # stage 3 factored out: the same numbers from the bulk functions and their derivatives alone
+    assert np.array_equal(ML.greek_dot_from_bulk(bulk, scal[0], bulk_dot, scal_dot[:, 0], h.mu, h.w_mu), greek_dot)
+    wide = ML.nai2_lin_reference(*MC.lin_args(h), dtype=np.longdouble, scales=True)
+    assert all(a.dtype == np.longdouble for a in (wide[0], wide[2], wide[3], wide[4], wide[5]))
+    assert all(a.dtype == np.clongdouble for a in wide[6])
+    S = wide[7]
+    assert S.bulk_dot_abs.shape == (4, h.n_mu) and S.c_dot_abs.shape == (4, 2) and np.all(S.bulk_dot_abs > 0) and np.all(S.c_dot_abs > 0)
+    dev = float(np.max(np.abs(greek_dot - wide[3])) / np.max(np.abs(wide[3])))
+    assert 0 < dev < 1e-12, dev
+
+
+@pytest.mark.parametrize("name", MC.NAMES)
+def test_a_defect_of_one_order_radius_or_angle_moves_the_n_r_derivatives(name):
+    """Sensitivity of the n_r slot: each perturbation of tests/test_oracle_mie.py moves at least one of its six derivative vectors
+    by >= 1e-6 of max(1, max |vector|)."""
+    c = MC.BY_NAME[name]
+    h = MC.inputs(c)
+    base = ML.nai2_lin_reference(*MC.lin_args(h))[3][0]
+    least = (math.inf, None)
+    for what, change in perturbations(h, c.n_max):
+        d = dict(vars(h))
+        d.update(change)
+        move = greek_move(ML.nai2_lin_reference(*MC.lin_args(types.SimpleNamespace(**d)))[3][0], base)
+        least = min(least, (move, what))
+        assert move >= SENSITIVITY, (name, what, move)
+    print("mie lin sensitivity %s: least move %.2e (%s)" % (name, least[0], least[1]))
+
+
+@pytest.mark.parametrize("name", MC.NAMES)
+def test_rounding_floor_of_every_output(name):
+    ref, floor = MC.case_floors(name)
+    print("mie lin floor %s: %s" % (name, "  ".join("%s %.1e" % (f, floor[f]) for f in MC.FAMILIES)))
+    for f in MC.FAMILIES:
+        assert MC.MIN_FLOOR <= floor[f] <= MC.FLOOR_LIMIT, (name, f, floor[f])
+    if MC.BY_NAME[name].nquad == 1:                           # one radius: its normalised weight has no derivative
+        assert not np.any(ref["greek_dot"][2:]) and not np.any(ref["bulk_f_dot"][2:]) and not np.any(ref["scal_dot"][2:])
