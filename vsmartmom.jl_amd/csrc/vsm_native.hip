@@ -101,7 +101,7 @@ __device__ __forceinline__ void ned_body(nsmem<RT, (4 * KS + 2 > 16 * RT)>& sm, 
               r_s.v[ta][r] *= fR;
             }
         }
-        const double nrm = nnorm(E, n, sm, slot, p);   // (its barrier: [r] is free)
+        const nbound nrm = nnorm(E, n, sm, slot, p);   // (its barrier: [r] is free)
         if constexpr (!RID) {   // u1 = j1- + r j0+ , u2 = j0+ + r j1-   (every wave is past the norm reduction's barrier)
           if (tid < G::NP) {
             sm.vec[4][tid] = jm[tid] * expk + sm.mv[0][tid];
@@ -262,7 +262,7 @@ __device__ __forceinline__ void nia_body_native(nsmem<RT, (4 * KS + 2 > 16 * RT)
         }
     }
     if constexpr (PARK) nst_native(R_pm, Z, p);   // (its old contents are in P; the new R+- overwrites it at the end)
-    const double nrm = nnorm(E, n, sm, slot, p);   // (b): every wave is done reading [R+-]
+    const nbound nrm = nnorm(E, n, sm, slot, p);   // (b): every wave is done reading [R+-]
     if constexpr (!RID) {   // z = J0+ + R+- j0- ; vs = T-- j0-
       if (tid < G::NP) {
         vz[tid] = vJp[tid] + sm.mv[0][tid];
@@ -434,7 +434,7 @@ __device__ __forceinline__ void nia_body_src(nsmem<RT, (4 * KS + 2 > 16 * RT)>& 
     nmv_rows<RT, KS, KZ>(dQ, vJp, 1.0, sm.mv[1], p);
   }
   nstrip<RT> E, Bs;
-  double nrm;
+  nbound nrm;
   {
     nstrip<RT> Pm;
     nmm2a<RT, KS, true, true, KZ>(E, dP, Pm, dQ, B, p);    // [E1 | r-+ J0+] ; [P | t++ J0+]
@@ -887,7 +887,7 @@ __device__ __forceinline__ void nia_body(nsmem<RT, (4 * KS + 2 > 16 * RT)>& sm, 
     }
     VSM_IA_STAMP(1);
     nstore(dQ, A2, p);                             // [T--] -> Q (free since the entry; read after barrier (c))
-    const double nrm = nnorm(E, n, sm, slot, p);   // (b): every wave is done reading [R+-]
+    const nbound nrm = nnorm(E, n, sm, slot, p);   // (b): every wave is done reading [R+-]
     if constexpr (!RID) {   // z = J0+ + R+- j0-
       if (tid < G::NP) vz[tid] = vJp[tid] + sm.mv[0][tid];
     }

@@ -312,24 +312,57 @@ __device__ __forceinline__ void ndsym(nstrip<RT>& d, const nstrip<RT>& x, const 
 }
 
 // ---- norm bound / series order / inverses -------------------------------------------------------------------------------------
-// Frobenius-norm bound of the n x n block whose strips the waves hold (rows >= n are zero by construction; the rider and
-// padding columns are excluded).  ONE barrier inside: on return every wave has finished whatever it did before the call.
+// Two bounds of the n x n block whose strips the waves hold (rows >= n are zero by construction; the rider and padding columns
+// are excluded): fro >= ||E||_F and one >= ||E||_1 = max_j sum_i |E_ij|, the induced 1-norm ("Series order from
+// the induced norm").  A lane holds the rows kq + 4 r of its column in every row tile: the four lane groups kq of a column are the
+// four 16-lane rows of the wave, summed by one v_permlane32_swap and one v_permlane16_swap of the register with itself
+// (tools/permlane_probe.hip: x[l] + x[l ^ 32], then y[l] + y[l ^ 16]), the 16 columns by an in-row DPP maximum on the bit patterns
+// (one v_max_u32_dpp each; the float maximum costs a move, two canonicalising maxima and the maximum per stage).  The lane's sum
+// goes to float by the plain conversion, not rounded up: that conversion, the two float additions and the product with 1.001f are
+// four roundings of 2^-24 each under a factor of 1 + 1e-3 (the emulated round-up is twelve dependent instructions in front of
+// the barrier every wave of the workgroup waits at -- it stays where the existing tests restate it, on the Frobenius sum).
+// ONE barrier inside: on return every wave has finished whatever it did before the call.
+struct nbound {
+  float fro, one;
+};
 template <int RT, typename SM>
-__device__ __forceinline__ double nnorm(const nstrip<RT>& e, int n, SM& sm, int& slot, const npos<RT>& p) {
-  double ss = 0;
+__device__ __forceinline__ nbound nnorm(const nstrip<RT>& e, int n, SM& sm, int& slot, const npos<RT>& p) {
+  double ss = 0, sa = 0;
 #pragma unroll
   for (int ta = 0; ta < RT; ++ta)
 #pragma unroll
-    for (int r = 0; r < 4; ++r) ss = fma(e.v[ta][r], e.v[ta][r], ss);
+    for (int r = 0; r < 4; ++r) {
+      ss = fma(e.v[ta][r], e.v[ta][r], ss);
+      sa += fabs(e.v[ta][r]);
+    }
   ss = (p.col < n) ? ss : 0.0;
   const float ws = wave_sum(to_float_up(ss));
-  if (p.lane == 0) sm.red[slot][p.wave] = ws;
+  float ca = (p.col < n) ? (float)sa : 0.f;
+  {
+    const auto h = __builtin_amdgcn_permlane32_swap(__float_as_uint(ca), __float_as_uint(ca), false, false);
+    ca = __uint_as_float(h[0]) + __uint_as_float(h[1]);
+    const auto q = __builtin_amdgcn_permlane16_swap(__float_as_uint(ca), __float_as_uint(ca), false, false);
+    ca = __uint_as_float(q[0]) + __uint_as_float(q[1]);   // every lane: the sum over the rows of its column
+  }
+  unsigned cu = __float_as_uint(ca);   // (a sum of magnitudes: no sign bit, no NaN below an infinite fro -- the bits order as the values)
+  cu = max(cu, (unsigned)__builtin_amdgcn_update_dpp(0, (int)cu, 0xB1, 0xf, 0xf, false));    // quad_perm [1,0,3,2]
+  cu = max(cu, (unsigned)__builtin_amdgcn_update_dpp(0, (int)cu, 0x4E, 0xf, 0xf, false));    // quad_perm [2,3,0,1]
+  cu = max(cu, (unsigned)__builtin_amdgcn_update_dpp(0, (int)cu, 0x141, 0xf, 0xf, false));   // row_half_mirror
+  cu = max(cu, (unsigned)__builtin_amdgcn_update_dpp(0, (int)cu, 0x140, 0xf, 0xf, false));   // row_mirror: the wave's 16 columns
+  if (p.lane == 0) {
+    sm.red[slot][0][p.wave] = ws;
+    sm.red[slot][1][p.wave] = __uint_as_float(cu);
+  }
   __syncthreads();
   float tot = 0.f;
+  unsigned mx = 0u;
 #pragma unroll
-  for (int w = 0; w < RT; ++w) tot += sm.red[slot][w];
+  for (int w = 0; w < RT; ++w) {
+    tot += sm.red[slot][0][w];
+    mx = max(mx, __float_as_uint(sm.red[slot][1][w]));
+  }
   slot ^= 1;
-  return (double)(sqrtf(tot) * 1.001f);
+  return nbound{sqrtf(tot) * 1.001f, __uint_as_float(mx) * 1.001f};
 }
 // smallest order K of {1,2,3,4,7,8,15,16,31} with nrm^(K+1) / (1 - nrm) <= eps / 4; 0: no series (pivoted inverse)
 __device__ __forceinline__ int nseries_order(double nrm) {
@@ -610,9 +643,12 @@ __device__ __forceinline__ void ninvert7(nstrip<RT>& E, nstrip<RT>& G, int n, co
   nmm<RT, KS, false, KZ>(G, cx.dW, Y, p);    // S + W4 + W4 S
   nadd_identity(G, n, p);
 }
-__device__ __forceinline__ int ninv_order(double nrm, int* status) {
-  if (!(nrm < 1e300) && threadIdx.x == 0) atomicOr(&status[0], (int)VSM_DEVSTAT_NONFINITE);
-  return nseries_order(nrm);
+// The pivot decision (and the non-finite flag) stay on the Frobenius bound; below 0.3 the series order comes from the smaller of
+// the two bounds.  Any induced norm bounds the tail: || sum_{k > K} E^k ||_1 <= ||E||_1^(K+1) / (1 - ||E||_1), and a 1-norm of
+// eps / 4 bounds every element by eps / 4 -- what the Frobenius rule guarantees.  (fro finite: every element is, so is `one`.)
+__device__ __forceinline__ int ninv_order(const nbound& b, int* status) {
+  if (!(b.fro < 3.0e38f) && threadIdx.x == 0) atomicOr(&status[0], (int)VSM_DEVSTAT_NONFINITE);
+  return nseries_order((double)((b.fro < 0.3f) ? fminf(b.fro, b.one) : b.fro));
 }
 
 // Partial sums of the mat-vec source path (blocks without spare columns: 4 KS + 2 > 16 RT, i.e. n = 13..16, 29..32, 45..48, 61..64): the
@@ -630,8 +666,9 @@ struct nsmem : nmv_slots<RT, MV> {
   double Q[ngeo<RT>::AF];
   double vec[8][ngeo<RT>::NP];
   double usg[ngeo<RT>::NP];   // -1.0 on the U/V rows of the sub-problem, +1.0 elsewhere
-  float red[2][8];
-  int flags[4];
+  // nnorm's partials, two slots of [Frobenius sum | 1-norm] per wave.  20 words up to five row tiles -- what `float red[2][8]` and
+  // four flag words nobody read took before; six row tiles (one workgroup per CU, 7 KB to spare) take 24.
+  float red[2][2][RT <= 5 ? 5 : RT];
   int gjs[2 * (ngeo<RT>::NP > 64 ? ngeo<RT>::NP : 64)];
 };
 
